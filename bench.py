@@ -21,6 +21,13 @@ script.  `--mode replicated` selects the round-1 design (all sources on every ra
 all-gathered by torch.distributed over RCCL).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line (figures derived from the timed
+steps' own counters included).  `--full` adds the measurements that take runs of their own: the
+dominant kernel alone, a shard's step phase by phase (N > 1), the kick and PM rows, the PCIe-inclusive
+drop-in legs and the CPU baseline with its accuracy check.  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the particles when the
+whole set would exceed DUMP_LIMIT_BYTES).
 """
 import argparse
 import importlib
@@ -45,6 +52,8 @@ BYTES_PER_GRAV_TARGET = 68.0    # 40 B in + 28 B out
 FLOP_PER_INTERACTION = 38.0     # ~25 flop + sqrt + div
 DT_STEP = 4.0e-3                # the common particle step of the workload (code units)
 BIN = 20                        # its time bin: Timebase_interval = DT_STEP / 2^BIN
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together
+DUMP_SEED = 20260917            # --dump-outputs: the particle sample above that limit
 
 
 def parse():
@@ -60,7 +69,17 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure (kernel alone, shard "
+                         "phases, kick / PM rows, drop-in legs, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 class Timeline:
@@ -328,10 +347,15 @@ def main():
     grav_int_all = float(tot[0])
     assert int(round(tot[4])) == n_total, "particles lost or doubled by the decomposition"
 
+    # before anything below evaluates the state once more
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fp, B, n_total, ngas_total, rank,
+                     dist if dom is not None else None)
+
     # the dominant kernel alone (outside the timed region): in the timed steps it shares the chip
     # with the Ewald walk and the SPH kernels, which stretches its own duration
     iso_ms, iso_steps, iso_int = None, None, None
-    if world == 1:
+    if args.full and world == 1:
         iso, isteps = [], []
         for _ in range(3):
             fp.gravity(gp_rel, B.WALK_NEWTON)
@@ -344,7 +368,7 @@ def main():
     # a rank's share of a step phase by phase (outside the timed region; the device drained between
     # phases, so the numbers add up -- unlike the overlapping spans of the timed steps)
     shard_phases = None
-    if dom is not None:
+    if args.full and dom is not None:
         for _ in range(2):
             dp = pr.g_dens()
             if not args.frozen:
@@ -433,7 +457,8 @@ def main():
         if dom is not None:
             out["transport"] = transport     # "rccl": RCCL from C (ghip_dd_run); "host": staged through gloo
             out["rccl_library"] = B.dd_rccl_library() if transport == "rccl" else None
-            out["shard_phases_ms"] = shard_phases
+            if args.full:
+                out["shard_phases_ms"] = shard_phases
             out["exchange_per_step_rank0"] = {
                 "particles_migrated": migrated / K,
                 "bytes_sent_migration": dd_bytes[0] / K,
@@ -443,13 +468,13 @@ def main():
                         "included); tree nodes = 64-B elements of the locally essential trees, "
                         "ghosts = 128-B gas records sent twice (before density, before hydro)"}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # "next" rows outside the timed region, against their own (HBM) rooflines
         try:
             out["next_rows"] = {"N1_kick": kick_roofline(pr, fp, B), "N3_pm": pm_timing(pr, fp)}
         except Exception as e:   # never let an auxiliary measurement break the bench line
             out["next_rows"] = {"N1_kick": {"error": str(e)}}
-    if rank == 0 and world == 1 and not args.no_dropin:
+    if args.full and rank == 0 and world == 1 and not args.no_dropin:
         try:
             state = device_state(pr, fp, B, tl)
             out["dropin_ms_per_step"] = dropin_timing(pr, state)
@@ -459,7 +484,7 @@ def main():
             del state
         except Exception as e:
             out["dropin_ms_per_step"] = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         pr.ti_current = tl.ti
 
         def device_eval():
@@ -555,6 +580,53 @@ def walk_roofline(work, phase_ms, K, st, iso_ms, iso_steps, args, world, grav_in
         r["algorithmic_frac_alone"] = alg_bytes / s / 1e9 / HBM_PEAK_GBS
         r["hbm_frac_alone"] = (traffic / s / 1e9 / HBM_PEAK_GBS) if traffic else None
     return r
+
+
+def dump_outputs(path, fp, B, n_total, ngas_total, rank, dist=None):
+    """--dump-outputs: what a caller of the step receives after the last timed step, in the global
+    particle order (gas first), one float64 .npy per quantity.  With dist (domain decomposition) the
+    ranks' particles are gathered on rank 0 by their IDs.  Above DUMP_LIMIT_BYTES a fixed, seeded
+    sample of the gas and of the other particles is written, with its indices (sample_index.npy)."""
+    every = {"pos": B.F_POS, "vel": B.F_VEL, "grav_accel": B.F_GRAVACCEL, "grav_cost": B.F_GRAVCOST}
+    gas = {"hsml": B.F_HSML, "density": B.F_DENSITY, "pressure": B.F_PRESSURE,
+           "entropy": B.F_ENTROPY, "dtentropy": B.F_DTENTROPY, "hydro_accel": B.F_HYDROACCEL}
+    if dist is None and rank != 0:
+        return
+    ngl = fp.ngas
+    mine = {k: fp.get_field(f) for k, f in every.items()}
+    mine.update({k: fp.get_field(f)[:ngl] for k, f in gas.items()})
+    if dist is not None:
+        ids = fp.get_field(B.F_ID)
+        parts = [None] * dist.get_world_size() if rank == 0 else None
+        dist.gather_object((ids, ngl, mine), parts, dst=0)
+        if rank != 0:
+            return
+        res = {}
+        for ids, ngl, arrs in parts:
+            for k, a in arrs.items():
+                if k not in res:
+                    res[k] = np.zeros(((n_total if k in every else ngas_total),) + a.shape[1:])
+                res[k][ids if k in every else ids[:ngl]] = a
+    else:
+        res = mine
+    res = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in res.items()}
+    per_particle = sum(a[0].size for k, a in res.items() if k in every) * 8
+    per_gas = sum(a[0].size for k, a in res.items() if k in gas) * 8
+    total = n_total * per_particle + ngas_total * per_gas
+    room = DUMP_LIMIT_BYTES - 4096            # the .npy headers
+    if total > room:
+        # the index costs 8 B per sampled particle
+        f = room / float(total + 8 * n_total)
+        rng = np.random.default_rng(DUMP_SEED)
+        sg = np.sort(rng.choice(ngas_total, int(f * ngas_total), replace=False))
+        so = ngas_total + np.sort(rng.choice(n_total - ngas_total, int(f * (n_total - ngas_total)),
+                                             replace=False))
+        sel = np.concatenate([sg, so])
+        res = {k: (a[sel] if k in every else a[sg]) for k, a in res.items()}
+        res["sample_index"] = sel.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in res.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def device_state(pr, fp, B, tl):

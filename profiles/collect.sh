@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- \
-  python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/stats.log" 2>&1
+  python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/stats.log" 2>&1
 grep '^{"metric"' "$OUT/stats.log" > "$OUT/bench_under_profiler.json" || true
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE" \
@@ -20,7 +20,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE" \
            "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i + 1))
   rocprofv3 --kernel-trace --pmc $grp --output-format csv -d "$OUT/pmc$i" -o p -- \
-    python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/pmc$i.log" 2>&1
+    python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/pmc$i.log" 2>&1
   echo "pmc pass $i ($grp) done"
 done
 find "$OUT" -name '*.csv' | sort

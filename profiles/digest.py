@@ -74,7 +74,7 @@ def main():
             d["mean_clock_GHz"] = (c["GRBM_GUI_ACTIVE"]["mean"] / 8.0 /
                                    c["GRBM_GUI_ACTIVE"]["mean_duration_ns"])
         derived[label] = d
-    out = {"note": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 bench.py --steps 3 "
+    out = {"note": "rocprofv3 --kernel-trace --pmc <one group per pass> -- python3 bench.py --full --steps 3 "
                    "--warmup 1 --no-cpu-baseline (profiles/collect.sh); relative-criterion launches "
                    "only; FETCH_SIZE/WRITE_SIZE in KB as reported (gfx950: FETCH_SIZE counts half the "
                    "bytes of wide reads, MI355X_MICROARCH.md HBM section)",
@@ -130,7 +130,7 @@ def main():
     if os.path.exists(tr) and os.path.exists(bl):
         rec = json.loads(open(bl).read().strip().splitlines()[-1])
         first, k = 2 + int(rec["warmup"]), int(rec["steps"])
-        agree = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps %d --warmup %d "
+        agree = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps %d --warmup %d "
                             "--no-cpu-baseline" % (k, rec["warmup"]),
                  "bench_ms_per_step": rec["ms_per_step"]}
         for label, key in (("k_grav_walk<NEWTON>", "grav"), ("k_grav_walk<EWALD>", "ewald")):
