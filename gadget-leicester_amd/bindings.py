@@ -101,6 +101,14 @@ class BhParams(C.Structure):
                 ("accretion_of_dust_only", C.c_int), ("accretion_density", C.c_int)]
 
 
+class DustParams(C.Structure):
+    """ghip_dust_params: the dust-gas drag passes of the shipped flag bundle (include/ghip.h)"""
+    _fields_ = [("periodic", C.c_int), ("BoxSize", C.c_double), ("dt_fac", C.c_double),
+                ("dt_fac_gas", C.c_double), ("MinEgySpec", C.c_double), ("MeanWeight", C.c_double),
+                ("UnitLength_in_cm", C.c_double), ("UnitMass_in_g", C.c_double),
+                ("UnitDensity_in_cgs", C.c_double), ("UnitVelocity_in_cm_per_s", C.c_double)]
+
+
 class PmParams(C.Structure):
     _fields_ = [("pmgrid", C.c_int), ("BoxSize", C.c_double), ("G", C.c_double),
                 ("Asmth", C.c_double)]
@@ -193,7 +201,8 @@ EXPORTS = [
     "ghip_sink_density", "ghip_sink_reset", "ghip_blackhole_evaluate", "ghip_blackhole_swallow",
     "ghip_sink_get_marks", "ghip_sink_set_marks", "ghip_cooling_and_starformation",
     "ghip_set_async", "ghip_timebin_counts", "ghip_run_begin", "ghip_step_begin", "ghip_step_end",
-    "ghip_run_end"]
+    "ghip_run_end", "ghip_dust_density", "ghip_dust_drag", "ghip_dust_get_drag_heating",
+    "ghip_dust_set_drag_heating"]
 
 
 def lib():
@@ -290,6 +299,10 @@ def lib():
         L.ghip_sink_set_marks.argtypes = [vp, vp, vp]
         L.ghip_cooling_and_starformation.argtypes = [vp, C.c_double, C.c_double, C.c_double,
                                                      C.c_double, vp]
+        L.ghip_dust_density.argtypes = [vp, C.POINTER(DustParams), C.c_int, vp, vp]
+        L.ghip_dust_drag.argtypes = [vp, C.POINTER(DustParams), C.c_int] + [vp] * 10
+        L.ghip_dust_get_drag_heating.argtypes = [vp, vp]
+        L.ghip_dust_set_drag_heating.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -691,6 +704,39 @@ class ForcePath:
                                                         float(min_egy), float(u_to_temp_fac),
                                                         _ptr(flag)))
         return flag
+
+    # ---- dust-gas drag (dust.c): grains in list order ----
+    def dust_density(self, params, dust):
+        dust = np.ascontiguousarray(dust, np.int32)
+        out = np.zeros(len(dust))
+        self._chk(self.L.ghip_dust_density(self.h, C.byref(params), len(dust), _ptr(dust), _ptr(out)))
+        return out
+
+    def dust_drag(self, params, dust, dust_density, dust_entropy, dust_gasvel, dust_radius,
+                  particle_density, particle_velocity, vcoll):
+        """-> dict(particle_velocity, delta_momentum, delta_energy, vcoll); the in/out arrays are copies"""
+        dust = np.ascontiguousarray(dust, np.int32)
+        nd = len(dust)
+        f = [np.ascontiguousarray(a, np.float64) for a in
+             (dust_density, dust_entropy, dust_gasvel, dust_radius, particle_density)]
+        assert f[2].shape == (nd, 3)
+        out = dict(particle_velocity=np.ascontiguousarray(particle_velocity, np.float64).reshape(nd, 3).copy(),
+                   delta_momentum=np.zeros((nd, 3)), delta_energy=np.zeros(nd),
+                   vcoll=np.ascontiguousarray(vcoll, np.float64).copy())
+        self._chk(self.L.ghip_dust_drag(self.h, C.byref(params), nd, _ptr(dust), *[_ptr(a) for a in f],
+                                        _ptr(out["particle_velocity"]), _ptr(out["delta_momentum"]),
+                                        _ptr(out["delta_energy"]), _ptr(out["vcoll"])))
+        return out
+
+    def dust_drag_heating(self):
+        dh = np.zeros(self.ngas)
+        self._chk(self.L.ghip_dust_get_drag_heating(self.h, _ptr(dh)))
+        return dh
+
+    def set_dust_drag_heating(self, dh):
+        dh = np.ascontiguousarray(dh, np.float64)
+        assert dh.shape == (self.ngas,)
+        self._chk(self.L.ghip_dust_set_drag_heating(self.h, _ptr(dh)))
 
     # ---- multi-GPU: domain decomposition with tree-node / ghost exchange (include/ghip.h) ----
     def dd_init(self, rank, nranks):

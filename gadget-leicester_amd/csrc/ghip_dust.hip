@@ -1,0 +1,631 @@
+// ghip_dust.hip -- the dust-gas drag passes of the reference's shipped flag bundle (DUST, DUST_TIMESTEP,
+// DUST_POWERLAW, DOUBLEPRECISION, CONSTANT_MEAN_MOLECULAR_WEIGHT; none of the DUST_GROWTH*,
+// DUST_VAPORIZE, DUST_TWO_POPULATIONS, DUST_REAL_PEBBLE_COLLISIONS, DUST_EPSTEIN,
+// DUST_NO_FRICTION_HEATING sub-flags), called by compute_accelerations() right after
+// blackhole_accretion() (accel.c:194, 198).
+//
+// Replaces the particle loops of
+//   dust_density / dust_evaluate_density         dust.c:60-261, 748-887
+//   dust_drag, the per-grain update              dust.c:263-446
+//   dust_drag / dust_evaluate_select (scatter)   dust.c:889-1029
+//   ngb_treefind_dust_active                     dust.c:1235-1333
+//
+// Grains can be a sizeable fraction of all particles, so a grain is a THREAD, not a wavefront: the
+// grains of a launch are ordered by their place in the gravity tree (a radix sort of the tree's
+// inverse permutation), which makes the walks of the 64 lanes of a wavefront neighbours in space.
+//
+// The scatter into the gas is order dependent (the entropy update is multiplicative, with a floor and a
+// cap): for each gas particle the reference applies the grains in the order of the active list.  The
+// pairs (gas j, grain a) are therefore counted, written as 64-bit keys (j << 32 | a) with their kernel
+// weight, radix sorted, and one thread per gas particle applies its run of pairs in list order.  Every
+// sum is a per-thread loop in a fixed order: two identical calls give identical bits.
+#include <climits>
+
+#include <hipcub/hipcub.hpp>
+
+#include "ghip_internal.h"
+
+#define DUST_KERNEL_COEFF_1 2.546479089470
+#define DUST_KERNEL_COEFF_2 15.278874536822
+#define DUST_KERNEL_COEFF_5 5.092958178941
+#define DUST_FACT1 0.366025403785   // allvars.h:310
+#define DUST_GAMMA (7. / 5.)        // allvars.h:64
+#define DUST_GAMMA_MINUS1 (DUST_GAMMA - 1)
+#define DUST_PROTONMASS 1.6726e-24  // allvars.h:89
+#define DUST_RHO_GRAIN 3.           // rho_dust, dust.c:379
+#define DUST_LEAF 16                // a tree node with at most this many particles is swept flat
+
+// per-grain planes of the staging buffer ([DUST_NPLANES][nd] doubles)
+enum
+{
+  DP_RHO = 0,   // in   d1.DUST_Density
+  DP_ENT,       // in   d2.DUST_Entropy
+  DP_GV,        // in   d3.DUST_SurroundingGasVel [3]
+  DP_RAD = DP_GV + 3,   // in   DustRadius
+  DP_D7,        // in   d7.DUST_particle_density
+  DP_D9,        // in/out d9.DUST_particle_velocity [3]
+  DP_VCOLL = DP_D9 + 3, // in/out DustVcoll
+  DP_DMOM,      // out  DeltaDustMomentum [3]
+  DP_DE = DP_DMOM + 3,  // out  DeltaDragEnergy
+  DUST_NPLANES
+};
+#define DUST_NIN (DP_VCOLL + 1)       // planes uploaded
+#define DUST_NOUT (DUST_NPLANES - DP_D9)   // planes read back: d9, vcoll, dmom, dE
+
+struct DustBox
+{
+  double boxsize, boxhalf;
+  int periodic;
+};
+
+struct DustK
+{
+  DustBox b;
+  double dt_fac, dt_fac_gas, minegy, meanweight, ulength, umass, udens, uvel;
+};
+
+struct __attribute__((aligned(64))) DustSphNode   // = SphNode of ghip_sph.hip
+{
+  double cx, cy, cz, len;
+  double hmax;
+  int skip, pidx, pstart, pcount;
+  int pad[2];
+};
+
+__device__ __forceinline__ double d_dust_wrap(double d, const DustBox &b)
+{
+  if(b.periodic)
+    {
+      if(d > b.boxhalf)
+        d -= b.boxsize;
+      if(d < -b.boxhalf)
+        d += b.boxsize;
+    }
+  return d;
+}
+
+// node test of ngb_treefind_dust_active (dust.c:1303-1313)
+__device__ __forceinline__ bool d_dust_overlaps(double cx, double cy, double cz, double len, double h,
+                                                double px, double py, double pz, const DustBox &b)
+{
+  double dist = h + 0.5 * len;
+  double dx = d_ngb_periodic(cx - px, b.periodic, b.boxsize, b.boxhalf);
+  if(dx > dist)
+    return false;
+  double dy = d_ngb_periodic(cy - py, b.periodic, b.boxsize, b.boxhalf);
+  if(dy > dist)
+    return false;
+  double dz = d_ngb_periodic(cz - pz, b.periodic, b.boxsize, b.boxhalf);
+  if(dz > dist)
+    return false;
+  dist += DUST_FACT1 * len;
+  return !(dx * dx + dy * dy + dz * dz > dist * dist);
+}
+
+// the neighbour test and kernel weight of dust_evaluate_density / _select (dust.c:826-847, 971-983):
+// r <= h from the tree search, then u = r / h < 1.  Returns false for a non-neighbour.
+__device__ __forceinline__ bool d_dust_weight(double px, double py, double pz, double qx, double qy,
+                                              double qz, double h, const DustBox &b, double &wk)
+{
+  const double dx = d_dust_wrap(px - qx, b), dy = d_dust_wrap(py - qy, b), dz = d_dust_wrap(pz - qz, b);
+  const double r2 = dx * dx + dy * dy + dz * dz;
+  if(r2 > h * h)
+    return false;
+  const double u = sqrt(r2) / h;
+  if(!(u < 1))
+    return false;
+  const double hinv = 1 / h, hinv3 = hinv * hinv * hinv;
+  if(u < 0.5)
+    wk = hinv3 * (DUST_KERNEL_COEFF_1 + DUST_KERNEL_COEFF_2 * (u - 1) * u * u);
+  else
+    wk = hinv3 * DUST_KERNEL_COEFF_5 * (1.0 - u) * (1.0 - u) * (1.0 - u);
+  return true;
+}
+
+// one thread's walk of the gravity tree (all types) around (px, py, pz) with radius h; f(p) for every
+// candidate p (sorted index) that the node tests let through
+template <class F>
+__device__ __forceinline__ void d_dust_walk_grav(double px, double py, double pz, double h, int nelem,
+                                                 const int4 *__restrict__ lk, const double4 *__restrict__ cl,
+                                                 const DustBox &b, F &&f)
+{
+  int e = 0;
+  while(e < nelem)
+    {
+      const int4 k = lk[e];
+      if(k.y >= 0)
+        {
+          f(k.y);
+          e = e + 1;
+          continue;
+        }
+      const double4 c = cl[e];
+      if(!d_dust_overlaps(c.x, c.y, c.z, c.w, h, px, py, pz, b))
+        {
+          e = k.x;
+          continue;
+        }
+      if(k.w > DUST_LEAF)
+        {
+          e = e + 1;
+          continue;
+        }
+      for(int p = k.z; p < k.z + k.w; p++)
+        f(p);
+      e = k.x;
+    }
+}
+
+// the same over the gas tree (SphNode records; gas particles only)
+template <class F>
+__device__ __forceinline__ void d_dust_walk_gas(double px, double py, double pz, double h, int nelem,
+                                                const DustSphNode *__restrict__ nodes, const DustBox &b,
+                                                F &&f)
+{
+  int e = 0;
+  while(e < nelem)
+    {
+      const DustSphNode &N = nodes[e];
+      if(N.pidx >= 0)
+        {
+          f(N.pidx);
+          e = e + 1;
+          continue;
+        }
+      if(!d_dust_overlaps(N.cx, N.cy, N.cz, N.len, h, px, py, pz, b))
+        {
+          e = N.skip;
+          continue;
+        }
+      if(N.pcount > DUST_LEAF)
+        {
+          e = e + 1;
+          continue;
+        }
+      for(int p = N.pstart; p < N.pstart + N.pcount; p++)
+        f(p);
+      e = N.skip;
+    }
+}
+
+// sort key of grain a: its place in the gravity tree
+__global__ void k_dust_order_keys(int nd, const int *__restrict__ idx, const int *__restrict__ iperm,
+                                  unsigned int *__restrict__ key, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nd)
+    return;
+  key[a] = (unsigned int) iperm[idx[a]];
+  slot[a] = a;
+}
+
+// dust_evaluate_density (dust.c:748-887): the Type-2 neighbours with Mass > 0 within the grain's h,
+// the grain itself included, each weighted with the GRAIN's own mass (dust.c:849: `dustmass` is
+// PPP[target].Mass -- a reference quirk kept as it is: the result is m_i * sum_j W_ij, not a density of
+// the neighbours' mass)
+__global__ void __launch_bounds__(64)
+k_dust_density(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n,
+               const double *__restrict__ pos, const double *__restrict__ hsml,
+               const double *__restrict__ mass, const int *__restrict__ type, int nelem,
+               const int4 *__restrict__ lk, const double4 *__restrict__ cl, const int *__restrict__ perm,
+               DustBox b, double *__restrict__ out)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= nd)
+    return;
+  const int a = ord[t], i = idx[a];
+  const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i];
+  const double h = hsml[i], mi = mass[i];
+  double rho = 0;
+  d_dust_walk_grav(px, py, pz, h, nelem, lk, cl, b, [&](int p) {
+    const int j = perm[p];
+    if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
+      return;
+    double wk;
+    if(d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
+      rho += mi * wk;
+  });
+  out[a] = rho;
+}
+
+// dust_drag, the per-grain part (dust.c:303-446), one thread per grain of the list
+__global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const int *__restrict__ timebin,
+                             const double *__restrict__ mass, const double *__restrict__ grav,
+                             double *__restrict__ vel, double *__restrict__ w, DustK K)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nd)
+    return;
+  const int i = idx[a];
+  const size_t N = (size_t) n, D = (size_t) nd;
+#define PL(q) w[(size_t) (q) * D + a]
+  const int tb = timebin[i];
+  const double dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac;
+  const double rho = PL(DP_RHO);
+  const double soundspeed = sqrt(8. / M_PI * PL(DP_ENT) * pow(rho, DUST_GAMMA_MINUS1));
+  double v[3], gv[3], g[3];
+  for(int k = 0; k < 3; k++)
+    {
+      v[k] = vel[k * N + i];
+      gv[k] = PL(DP_GV + k);
+      g[k] = grav[k * N + i];
+    }
+  const double delta_vel = sqrt((v[0] - gv[0]) * (v[0] - gv[0]) + (v[1] - gv[1]) * (v[1] - gv[1]) +
+                                (v[2] - gv[2]) * (v[2] - gv[2]));
+  const double d7 = PL(DP_D7);
+  double vcoll = PL(DP_VCOLL);
+  for(int k = 0; k < 3; k++)
+    PL(DP_DMOM + k) = 0.;
+  double de = 0.;
+  if(d7 > 0.)   // dust.c:366-376: d9 divided in place
+    {
+      double d9[3];
+      for(int k = 0; k < 3; k++)
+        {
+          d9[k] = PL(DP_D9 + k) / d7;
+          PL(DP_D9 + k) = d9[k];
+        }
+      const double dpv = sqrt((v[0] - d9[0]) * (v[0] - d9[0]) + (v[1] - d9[1]) * (v[1] - d9[1]) +
+                              (v[2] - d9[2]) * (v[2] - d9[2]));
+      vcoll = dpv * K.uvel / 1.e2 + 1.e-30;
+    }
+  if(dt > 0)   // dust.c:385-444
+    {
+      const double R = PL(DP_RAD);
+      const double lambda_h2 = K.meanweight * DUST_PROTONMASS / (K.udens * rho) / 1.e-15 / K.ulength;
+      const double rey = 6 * delta_vel * R / K.ulength / (lambda_h2 * soundspeed);
+      double ts;
+      if(3. / 2 * lambda_h2 * K.ulength >= R)   // Epstein
+        ts = 1. / (rho * soundspeed / (DUST_RHO_GRAIN * R) * K.umass / K.ulength / K.ulength);
+      else if(delta_vel > 0)   // Stokes, C_drag of Weidenschilling 1977
+        {
+          double C_drag = 0.;
+          if(rey >= 800.)
+            C_drag = 0.44;
+          if(rey < 800. && rey >= 1.)
+            C_drag = 24. * pow(rey, -0.6);
+          if(rey < 1.)
+            C_drag = 24. / rey;
+          ts = DUST_RHO_GRAIN * R / (rho * delta_vel) / K.umass * K.ulength * K.ulength;
+          ts *= 8. / 3. / C_drag;
+        }
+      else
+        ts = 0.66667 / (rho * soundspeed / (DUST_RHO_GRAIN * R)) / K.umass * K.ulength * R / lambda_h2;
+      const double e1 = exp(-dt / ts), e2 = exp(-2. * dt / ts);
+      for(int k = 0; k < 3; k++)
+        {
+          const double vold = v[k];
+          const double vsteady = (vold * d7 + gv[k] * rho) / (d7 + rho + 1.e-30);
+          const double vnew = vsteady + (vold - vsteady) * e1 + g[k] * ts * (1. - e1);
+          const double vnew_nog = vold + g[k] * dt;
+          PL(DP_DMOM + k) = 0. - mass[i] * (vnew_nog - vnew);
+          de += mass[i] * ((vnew - vsteady) * (vnew - vsteady)) * (1. - e2) / 2.;
+          vel[k * N + i] = vnew;
+        }
+      vcoll = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) * ts * K.uvel / 1.e2;
+      vcoll += 0.2;
+    }
+  PL(DP_DE) = de;
+  PL(DP_VCOLL) = vcoll;
+#undef PL
+}
+
+// the gas neighbours that dust_evaluate_select updates (dust.c:962-1000): Type 0, Mass > 0, u < 1,
+// the gas particle's own dt > 0 and the grain's DUST_Density > 0.  fill == 0: count them into
+// cnt[a]; fill == 1: write (j << 32 | a, W) from off[a] on
+template <int fill>
+__global__ void __launch_bounds__(64)
+k_dust_pairs(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n, int ngas,
+             const double *__restrict__ pos, const double *__restrict__ hsml,
+             const double *__restrict__ mass, const int *__restrict__ type,
+             const int *__restrict__ timebin, const double *__restrict__ w, int nelem,
+             const DustSphNode *__restrict__ nodes, const int *__restrict__ perm, DustBox b, long long *__restrict__ cnt,
+             const long long *__restrict__ off, unsigned long long *__restrict__ key,
+             double *__restrict__ wgt)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= nd)
+    return;
+  const int a = ord[t], i = idx[a];
+  long long c = 0;
+  if(w[(size_t) DP_RHO * nd + a] > 0.)
+    {
+      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i];
+      const double h = hsml[i];
+      const long long o = fill ? off[a] : 0;
+      d_dust_walk_gas(px, py, pz, h, nelem, nodes, b, [&](int p) {
+        const int j = perm[p];
+        if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0) || timebin[j] == 0)
+          return;
+        double wk;
+        if(!d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
+          return;
+        if(fill)
+          {
+            key[o + c] = ((unsigned long long) j << 32) | (unsigned int) a;
+            wgt[o + c] = wk;
+          }
+        c++;
+      });
+    }
+  if(!fill)
+    cnt[a] = c;
+}
+
+// the update of one gas particle by the grains of its run of sorted pairs, in list order
+// (dust.c:987-996)
+__global__ void k_dust_apply(long long npairs, const unsigned long long *__restrict__ key,
+                             const double *__restrict__ wgt, int nd, const double *__restrict__ w,
+                             int n, const double *__restrict__ mass, const int *__restrict__ timebin,
+                             double *__restrict__ vel, double *__restrict__ entropy,
+                             double *__restrict__ heat, DustK K)
+{
+  const long long s0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+  if(s0 >= npairs)
+    return;
+  const unsigned int j = (unsigned int) (key[s0] >> 32);
+  if(s0 > 0 && (unsigned int) (key[s0 - 1] >> 32) == j)
+    return;   // not the first pair of its gas particle
+  const size_t N = (size_t) n, D = (size_t) nd;
+  const int tb = timebin[j];
+  const double dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac_gas;
+  const double mj = mass[j];
+  double v0 = vel[j], v1 = vel[N + j], v2 = vel[2 * N + j], A = entropy[j], dh = heat[j];
+  for(long long s = s0; s < npairs && (unsigned int) (key[s] >> 32) == j; s++)
+    {
+      const unsigned int a = (unsigned int) (key[s] & 0xffffffffULL);
+      const double wk = wgt[s];
+      const double density = w[(size_t) DP_RHO * D + a];
+      const double E = w[(size_t) DP_DE * D + a];
+      v0 -= w[(size_t) DP_DMOM * D + a] / density * wk;
+      v1 -= w[(size_t) (DP_DMOM + 1) * D + a] / density * wk;
+      v2 -= w[(size_t) (DP_DMOM + 2) * D + a] / density * wk;
+      double u_old = A / DUST_GAMMA_MINUS1 * pow(density, DUST_GAMMA_MINUS1);
+      if(K.minegy > u_old)   // DMAX(All.MinEgySpec, ...), allvars.h:273
+        u_old = K.minegy;
+      const double u_new = u_old + E * wk / density;
+      double u_inc = u_new / u_old;
+      if(u_inc > 1.5)
+        u_inc = 1.5;
+      A *= u_inc;
+      dh += 1.e-20 * (E * wk / density * mj / dt);
+    }
+  vel[j] = v0;
+  vel[N + j] = v1;
+  vel[2 * N + j] = v2;
+  entropy[j] = A;
+  heat[j] = dh;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static DustBox dust_box(const ghip_dust_params *p)
+{
+  DustBox b;
+  b.boxsize = p->BoxSize;
+  b.boxhalf = 0.5 * p->BoxSize;
+  b.periodic = p->periodic;
+  return b;
+}
+
+static int dust_heat_buffer(ghip_ctx *ctx)
+{
+  const size_t ng = (size_t) (ctx->ngas > 0 ? ctx->ngas : 1);
+  const size_t before = ctx->dust_heat.cap;
+  GCHK(ghip_ensure(ctx, ctx->dust_heat, ng * 8));
+  if(ctx->dust_heat.cap != before)
+    HIPCHK(hipMemsetAsync(ctx->dust_heat.p, 0, ctx->dust_heat.cap, ctx->stream));
+  return GHIP_OK;
+}
+
+// the checks every entry point makes; the grain list goes to the device, ordered by the gravity tree
+// into dust_ord (slot of the t-th thread)
+static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const int *idx, bool gas,
+                      const char *who)
+{
+  if(!p || nd < 0 || (nd > 0 && !idx))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU context (%d ranks): the "
+                     "dust passes are single-rank only (no dust ghost exchange)", who, ctx->dd.nranks);
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard with %d "
+                     "shards): the dust passes are single-rank only", who, ctx->shard_n);
+  if(nd == 0)
+    return GHIP_OK;
+  if(gas)
+    GCHK(ghip_finish_gas_tree(ctx));
+  if(!ctx->gt.built || (gas && !ctx->st.built))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
+  for(int a = 0; a < nd; a++)
+    if(idx[a] < 0 || idx[a] >= ctx->n)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: grain index %d out of range", who, idx[a]);
+  hipStream_t st = ctx->stream;
+  const size_t D = (size_t) nd;
+  // dust_idx: idx [nd] | ord [nd] | key [nd] | key' [nd] | slot [nd]
+  GCHK(ghip_ensure(ctx, ctx->dust_idx, D * 20 + 256));
+  int *didx = P<int>(ctx->dust_idx), *dord = didx + D, *dslot = dord + 3 * D;
+  unsigned int *dkey = reinterpret_cast<unsigned int *>(dord + D), *dkey2 = dkey + D;
+  HIPCHK(hipMemcpyAsync(didx, idx, D * 4, hipMemcpyHostToDevice, st));
+  k_dust_order_keys<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(ctx->gt.iperm), dkey, dslot);
+  HIPCHK(hipGetLastError());
+  int end_bit = 1;
+  while(end_bit < 32 && (1LL << end_bit) <= (long long) ctx->n)
+    end_bit++;
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
+  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
+                                 double *particle_density)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  if(ndust > 0 && !particle_density)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_density: bad arguments");
+  GCHK(dust_begin(ctx, p, ndust, dust_idx, false, "ghip_dust_density"));
+  if(ndust == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  TreeDev &t = ctx->gt;
+  const size_t D = (size_t) ndust;
+  GCHK(ghip_ensure(ctx, ctx->dust_work, D * 8 + 256));
+  double *dout = P<double>(ctx->dust_work);
+  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
+  k_dust_density<<<cdiv(ndust, 64), 64, 0, st>>>(
+    ndust, dord, didx, ctx->n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
+    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
+    P<int>(t.perm), dust_box(p), dout);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
+                              const double *dust_density, const double *dust_entropy,
+                              const double *dust_gasvel, const double *dust_radius,
+                              const double *particle_density, double *particle_velocity,
+                              double *delta_momentum, double *delta_energy, double *vcoll)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  if(ndust > 0 && (!dust_density || !dust_entropy || !dust_gasvel || !dust_radius || !particle_density ||
+                   !particle_velocity || !delta_momentum || !delta_energy || !vcoll))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_drag: bad arguments");
+  GCHK(dust_begin(ctx, p, ndust, dust_idx, ctx->ngas > 0, "ghip_dust_drag"));
+  GCHK(dust_heat_buffer(ctx));
+  if(ndust == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const size_t D = (size_t) ndust;
+  DustK K;
+  K.b = dust_box(p);
+  K.dt_fac = p->dt_fac;
+  K.dt_fac_gas = p->dt_fac_gas;
+  K.minegy = p->MinEgySpec;
+  K.meanweight = p->MeanWeight;
+  K.ulength = p->UnitLength_in_cm;
+  K.umass = p->UnitMass_in_g;
+  K.udens = p->UnitDensity_in_cgs;
+  K.uvel = p->UnitVelocity_in_cm_per_s;
+  // the per-grain planes, in list order
+  std::vector<double> h((size_t) DUST_NPLANES * D, 0.0);
+  for(size_t a = 0; a < D; a++)
+    {
+      h[DP_RHO * D + a] = dust_density[a];
+      h[DP_ENT * D + a] = dust_entropy[a];
+      h[DP_RAD * D + a] = dust_radius[a];
+      h[DP_D7 * D + a] = particle_density[a];
+      h[DP_VCOLL * D + a] = vcoll[a];
+      for(int k = 0; k < 3; k++)
+        {
+          h[(DP_GV + k) * D + a] = dust_gasvel[3 * a + k];
+          h[(DP_D9 + k) * D + a] = particle_velocity[3 * a + k];
+        }
+    }
+  // dust_work: planes [DUST_NPLANES][nd] | cnt [nd + 1] | off [nd + 1]   (64-bit)
+  GCHK(ghip_ensure(ctx, ctx->dust_work, (DUST_NPLANES * D + 2 * (D + 1)) * 8 + 256));
+  double *dw = P<double>(ctx->dust_work);
+  long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
+  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
+  HIPCHK(hipMemcpyAsync(dw, h.data(), DUST_NIN * D * 8, hipMemcpyHostToDevice, st));
+  k_dust_grain<<<cdiv(ndust, 256), 256, 0, st>>>(ndust, didx, ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                                 P<double>(ctx->f[GHIP_F_MASS]),
+                                                 P<double>(ctx->f[GHIP_F_GRAVACCEL]),
+                                                 P<double>(ctx->f[GHIP_F_VEL]), dw, K);
+  HIPCHK(hipGetLastError());
+  // the scatter: count, scan, fill, sort, apply
+  TreeDev &t = ctx->st;
+  HIPCHK(hipMemsetAsync(dcnt, 0, (D + 1) * 8, st));
+  if(ctx->ngas > 0)
+    k_dust_pairs<0><<<cdiv(ndust, 64), 64, 0, st>>>(
+    ndust, dord, didx, ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
+    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TIMEBIN]), dw, t.nelem,
+    reinterpret_cast<const DustSphNode *>(t.mq.p), P<int>(t.perm), K.b, dcnt, nullptr,
+    nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, dcnt, doff, ndust + 1, st));
+  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->dust_cub.p, tb, dcnt, doff, ndust + 1, st));
+  long long npairs = 0;
+  if(ctx->ngas > 0)
+    HIPCHK(hipMemcpyAsync(&npairs, doff + D, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));   // the pair count sizes the sort
+  if(npairs < 0 || npairs > (long long) INT_MAX)
+    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_dust_drag: %lld dust-gas pairs", npairs);
+  if(npairs > 0)
+    {
+      const size_t np = (size_t) npairs;
+      // dust_pairs: key [np] | key' [np] | W [np] | W' [np]
+      GCHK(ghip_ensure(ctx, ctx->dust_pairs, np * 32 + 256));
+      unsigned long long *k0 = P<unsigned long long>(ctx->dust_pairs), *k1 = k0 + np;
+      double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
+      k_dust_pairs<1><<<cdiv(ndust, 64), 64, 0, st>>>(
+        ndust, dord, didx, ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
+        P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TIMEBIN]), dw,
+        t.nelem, reinterpret_cast<const DustSphNode *>(t.mq.p), P<int>(t.perm), K.b,
+        nullptr, doff, k0, w0);
+      HIPCHK(hipGetLastError());
+      int end_bit = 33;
+      while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
+        end_bit++;
+      tb = 0;
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
+      GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
+      HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
+      k_dust_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, ndust, dw, ctx->n,
+                                                      P<double>(ctx->f[GHIP_F_MASS]),
+                                                      P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                                      P<double>(ctx->f[GHIP_F_VEL]),
+                                                      P<double>(ctx->f[GHIP_F_ENTROPY]),
+                                                      P<double>(ctx->dust_heat), K);
+      HIPCHK(hipGetLastError());
+    }
+  HIPCHK(hipMemcpyAsync(h.data() + DP_D9 * D, dw + DP_D9 * D, DUST_NOUT * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  for(size_t a = 0; a < D; a++)
+    {
+      for(int k = 0; k < 3; k++)
+        {
+          particle_velocity[3 * a + k] = h[(DP_D9 + k) * D + a];
+          delta_momentum[3 * a + k] = h[(DP_DMOM + k) * D + a];
+        }
+      delta_energy[a] = h[DP_DE * D + a];
+      vcoll[a] = h[DP_VCOLL * D + a];
+    }
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(dust_heat_buffer(ctx));
+  if(drag_heating && ctx->ngas > 0)
+    HIPCHK(hipMemcpyAsync(drag_heating, ctx->dust_heat.p, (size_t) ctx->ngas * 8, hipMemcpyDeviceToHost,
+                          ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dust_set_drag_heating(ghip_ctx *ctx, const double *drag_heating)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(dust_heat_buffer(ctx));
+  if(drag_heating && ctx->ngas > 0)
+    HIPCHK(hipMemcpyAsync(ctx->dust_heat.p, drag_heating, (size_t) ctx->ngas * 8, hipMemcpyHostToDevice,
+                          ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}

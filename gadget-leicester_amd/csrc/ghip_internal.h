@@ -329,6 +329,8 @@ struct ghip_ctx
   DDState dd;                // multi-GPU domain decomposition (ghip_dd.hip)
   DevBuf bh_swallow, bh_injected;   // "next" row N4 (ghip_sink.hip): P[].SwallowID u32[n],
                                     // SphP[].i.Injected_BH_Energy f64[ngas]
+  DevBuf dust_heat;                 // dust_drag (ghip_dust.hip): SphP[].dh.DragHeating f64[ngas]
+  DevBuf dust_idx, dust_work, dust_pairs, dust_cub;   // ... its grain list, per-grain planes, sorted pairs
   int timestep_endrun = 0;   // endrun code of the last ghip_advance_timesteps failure
   bool ev_ready = false;
 

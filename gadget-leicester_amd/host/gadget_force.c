@@ -2001,6 +2001,208 @@ void blackhole_accretion_neighbour_passes(void)
 }
 
 /* ------------------------------------------------------------------------------------------
+ * the dust-gas drag passes (dust.c) on bound records
+ * ---------------------------------------------------------------------------------------- */
+static struct gadget_force_dust_layout DustLay;   /* (all -1 until gadget_force_bind_dust) */
+static const char *DustAll = NULL;                /* the host's All for DustLay.a_* */
+__attribute__((constructor)) static void dust_lay_defaults(void)
+{
+  memset(&DustLay, 0xff, sizeof(DustLay));
+}
+
+void gadget_force_bind_dust(void *host_All, const struct gadget_force_dust_layout *lay)
+{
+  if(lay)
+    {
+      DustLay = *lay;
+      DustAll = (const char *) host_All;
+    }
+  else
+    {
+      dust_lay_defaults();
+      DustAll = NULL;
+    }
+}
+
+static double dust_all(int off)
+{
+  return off >= 0 && DustAll ? *(const double *) (DustAll + off) : 0.0;
+}
+
+static void fill_dust_params(ghip_dust_params *d)
+{
+  memset(d, 0, sizeof(*d));
+  double hubble_a = 1, time_hubble_a = 1;
+  if(All.ComovingIntegrationOn)   /* dust.c:75-80, 319-325, 912-918 */
+    {
+      hubble_a = hubble_function(All.Time);
+      time_hubble_a = All.Time * hubble_a;
+    }
+  d->periodic = Cfg.periodic;
+  d->BoxSize = All.BoxSize;
+  d->dt_fac = All.Timebase_interval / hubble_a;
+  d->dt_fac_gas = All.Timebase_interval / time_hubble_a;
+  d->MinEgySpec = All.MinEgySpec;
+  d->MeanWeight = dust_all(DustLay.a_mean_weight);
+  d->UnitLength_in_cm = All.UnitLength_in_cm;
+  d->UnitMass_in_g = All.UnitMass_in_g;
+  d->UnitDensity_in_cgs = dust_all(DustLay.a_unit_density);
+  d->UnitVelocity_in_cm_per_s = dust_all(DustLay.a_unit_velocity);
+}
+
+/* checks + the grain list (active Type 2 in FirstActiveParticle order) into a malloc'd array */
+static int dust_ready(const char *who, int drag, int **idx_out)
+{
+  *idx_out = NULL;
+  if(need_ctx(who))
+    return -1;
+  if(NTask > 1)
+    {
+      /* the passes would need the grains' ghosts on every rank and an ordered scatter into remote gas */
+      snprintf(ErrBuf, sizeof(ErrBuf), "%s: the dust passes run on a single rank only (NTask = %d)", who,
+               NTask);
+      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+      endrun(90010);
+      return -1;
+    }
+  int bad = !Cfg.dust || !RecP || Lay.p_hsml < 0 || DustLay.p_particle_density < 0;
+  if(drag)
+    bad = bad || BhLay.p_dust_density < 0 || BhLay.p_dust_entropy < 0 || BhLay.p_dust_gasvel < 0 ||
+          DustLay.p_particle_velocity < 0 || DustLay.p_delta_momentum < 0 || DustLay.p_delta_energy < 0 ||
+          DustLay.p_radius < 0 || DustLay.p_vcoll < 0 || DustLay.a_mean_weight < 0 ||
+          DustLay.a_unit_density < 0 || DustLay.a_unit_velocity < 0 || !DustAll;
+  if(bad)
+    {
+      snprintf(ErrBuf, sizeof(ErrBuf), "%s: needs a DUST configuration and records bound with their dust "
+               "members (gadget_force_bind_records, gadget_force_bind_dust)", who);
+      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+      endrun(90002);
+      return -1;
+    }
+  gadget_force_flush();   /* results still on the device reach the records first */
+  if(ensure_tree())
+    return -1;
+  int n = 0;
+  for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
+    if(p_type(i) == 2)
+      n++;
+  int *idx = (int *) malloc((size_t) (n + 1) * sizeof(int));
+  if(!idx)
+    {
+      endrun(90003);
+      return -1;
+    }
+  n = 0;
+  for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
+    if(p_type(i) == 2)
+      idx[n++] = i;
+  *idx_out = idx;
+  return n;
+}
+
+/* dust.c:60-261 */
+void dust_density(void)
+{
+  int *idx;
+  const int n = dust_ready("dust_density", 0, &idx);
+  if(n < 0)
+    return;
+  double *rho = (double *) malloc((size_t) (n + 1) * sizeof(double));
+  if(!rho)
+    {
+      free(idx);
+      endrun(90003);
+      return;
+    }
+  ghip_dust_params d;
+  fill_dust_params(&d);
+  if(!chk(ghip_dust_density(Ctx, &d, n, idx, rho), "ghip_dust_density"))
+    for(int k = 0; k < n; k++)
+      *PF64(idx[k], DustLay.p_particle_density) = rho[k];   /* dust.c:242-245 */
+  free(rho);
+  free(idx);
+}
+
+/* dust.c:263-746 */
+void dust_drag(void)
+{
+  int *idx;
+  const int n = dust_ready("dust_drag", 1, &idx);
+  if(n < 0)
+    return;
+  const size_t m = (size_t) n + 1, nall = (size_t) (NumPart > 0 ? NumPart : 1);
+  const size_t ng = (size_t) (N_gas > 0 ? N_gas : 1);
+  /* per grain: rho, A, gasvel[3], radius, d7, d9[3], dmom[3], dE, vcoll (15); per particle: vel[3]
+   * + per gas particle: entropy, heating */
+  double *buf = (double *) malloc((15 * m + 3 * nall + 2 * ng) * sizeof(double));
+  if(!buf)
+    {
+      free(idx);
+      endrun(90003);
+      return;
+    }
+  double *rho = buf, *ent = buf + m, *gv = buf + 2 * m, *rad = buf + 5 * m, *d7 = buf + 6 * m,
+         *d9 = buf + 7 * m, *dmom = buf + 10 * m, *de = buf + 13 * m, *vc = buf + 14 * m;
+  double *vel = buf + 15 * m, *sent = vel + 3 * nall, *heat = sent + ng;
+  for(int k = 0; k < n; k++)
+    {
+      const int i = idx[k];
+      rho[k] = *PF64(i, BhLay.p_dust_density);
+      ent[k] = *PF64(i, BhLay.p_dust_entropy);
+      rad[k] = *PF64(i, DustLay.p_radius);
+      d7[k] = *PF64(i, DustLay.p_particle_density);
+      vc[k] = *PF64(i, DustLay.p_vcoll);
+      for(int c = 0; c < 3; c++)
+        {
+          gv[3 * (size_t) k + c] = PF64(i, BhLay.p_dust_gasvel)[c];
+          d9[3 * (size_t) k + c] = PF64(i, DustLay.p_particle_velocity)[c];
+        }
+    }
+  /* SphP[].dh.DragHeating accumulates on top of what the records hold */
+  for(int j = 0; j < N_gas; j++)
+    heat[j] = DustLay.s_drag_heating >= 0 ? *SF64(j, DustLay.s_drag_heating) : 0.0;
+  ghip_dust_params d;
+  fill_dust_params(&d);
+  int rc = ghip_dust_set_drag_heating(Ctx, heat);
+  if(rc == GHIP_OK)
+    rc = ghip_dust_drag(Ctx, &d, n, idx, rho, ent, gv, rad, d7, d9, dmom, de, vc);
+  if(rc == GHIP_OK)
+    rc = ghip_get_field(Ctx, GHIP_F_VEL, vel);
+  if(rc == GHIP_OK && N_gas > 0)
+    rc = ghip_get_field(Ctx, GHIP_F_ENTROPY, sent);
+  if(rc == GHIP_OK)
+    rc = ghip_dust_get_drag_heating(Ctx, heat);
+  if(rc == GHIP_OK)
+    {
+      for(int k = 0; k < n; k++)
+        {
+          const int i = idx[k];
+          for(int c = 0; c < 3; c++)
+            {
+              PF64(i, Lay.p_vel)[c] = vel[3 * (size_t) i + c];
+              PF64(i, DustLay.p_particle_velocity)[c] = d9[3 * (size_t) k + c];
+              PF64(i, DustLay.p_delta_momentum)[c] = dmom[3 * (size_t) k + c];
+              if(DustLay.p_new_drag_acc >= 0)
+                PF64(i, DustLay.p_new_drag_acc)[c] = 0.;   /* dust.c:333 */
+            }
+          *PF64(i, DustLay.p_delta_energy) = de[k];
+          *PF64(i, DustLay.p_vcoll) = vc[k];
+        }
+      for(int j = 0; j < N_gas; j++)
+        {
+          for(int c = 0; c < 3; c++)
+            PF64(j, Lay.p_vel)[c] = vel[3 * (size_t) j + c];
+          *SF64(j, Lay.s_entropy) = sent[j];
+          if(DustLay.s_drag_heating >= 0)
+            *SF64(j, DustLay.s_drag_heating) = heat[j];
+        }
+    }
+  free(buf);
+  free(idx);
+  chk(rc, "ghip_dust_drag");
+}
+
+/* ------------------------------------------------------------------------------------------
  * more than one rank: the drivers as collectives over the domain-decomposed device path
  * ---------------------------------------------------------------------------------------- */
 int gadget_force_unique_id(void *id128)

@@ -83,6 +83,14 @@ class BhLayout(C.Structure):
         "p_dust_mass", "s_injected_bh_energy")]
 
 
+class DustLayout(C.Structure):
+    """struct gadget_force_dust_layout: byte offsets of the members the dust passes touch (-1: absent)"""
+    _fields_ = [(k, C.c_int) for k in (
+        "p_particle_density", "p_particle_velocity", "p_delta_momentum", "p_new_drag_acc",
+        "p_delta_energy", "p_radius", "p_vcoll", "s_drag_heating", "a_mean_weight", "a_unit_density",
+        "a_unit_velocity")]
+
+
 class TopNode(C.Structure):
     """struct topnode_data, allvars.h:437-447"""
     _fields_ = [("Size", C.c_ulonglong), ("StartKey", C.c_ulonglong), ("Count", C.c_longlong),
@@ -137,7 +145,8 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "blackhole_accretion_neighbour_passes", "N_gas_swallowed", "N_BH_swallowed",
            "N_dust_swallowed", "TopNodes", "NTopnodes", "NTopleaves", "DomainStartList",
            "DomainEndList", "gadget_force_unique_id", "gadget_force_connect",
-           "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush"]
+           "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
+           "gadget_force_bind_dust", "dust_density", "dust_drag"]
 
 _LIB = None
 
@@ -184,6 +193,10 @@ def lib():
         L.gadget_force_connect.argtypes = [C.c_void_p]
         L.gadget_force_set_allgather.argtypes = [HOST_ALLGATHER_CB, C.c_void_p]
         L.gadget_force_set_allgather.restype = None
+        L.gadget_force_bind_dust.argtypes = [C.c_void_p, C.c_void_p]
+        L.gadget_force_bind_dust.restype = None
+        L.dust_density.restype = None
+        L.dust_drag.restype = None
         _LIB = L
     return _LIB
 
@@ -235,6 +248,16 @@ class Host:
         self.L.gadget_force_mark_dirty()
         self._seti("TreeReconstructFlag", 1)
 
+    def bind_dust(self, host_all, lay):
+        """gadget_force_bind_dust: `host_all` a numpy structured scalar holding the host's `All` (for the
+        table's a_* offsets), `lay` a DustLayout; None unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_dust(None, None)
+            self._dust = None
+            return
+        self._dust = (host_all, lay)            # keep alive
+        self.L.gadget_force_bind_dust(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p))
+
     def set_allgather(self, allgather):
         """the host's all-gather for more than one rank: allgather(send: bytes) -> bytes of all ranks"""
         def cb(_user, send, nbytes, recv):
@@ -272,6 +295,7 @@ class Host:
     def close(self):
         self.L.gadget_force_bind_all(None, None)
         self.L.gadget_force_bind_records(None, None, None, None)
+        self.L.gadget_force_bind_dust(None, None)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)
         self._seti("ThisTask", 0)
         self._seti("NTask", 1)

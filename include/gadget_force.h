@@ -396,6 +396,30 @@ int blackhole_evaluate_swallow(int target, int mode, int *nexport, int *nsend_lo
 void blackhole_accretion_neighbour_passes(void);
 extern int N_gas_swallowed, N_BH_swallowed, N_dust_swallowed;
 
+/* DUST builds with bound records: the dust-gas drag passes with the reference's names (dust.c:60, 263;
+ * called at accel.c:194, 198), for the active Type-2 particles in FirstActiveParticle order.  They read
+ * d1.DUST_Density / d2.DUST_Entropy / d3.DUST_SurroundingGasVel through the bh table of
+ * gadget_force_bind_records, and the members below through this table (byte offsets, -1 = absent):
+ *   P[]     d7.DUST_particle_density, d9.DUST_particle_velocity[3], DeltaDustMomentum[3],
+ *           NewDragAcc[3], DeltaDragEnergy, DustRadius, DustVcoll   (allvars.h:1201-1319)
+ *   SphP[]  dh.DragHeating                                         (allvars.h:1440)
+ *   All     MeanWeight, UnitDensity_in_cgs, UnitVelocity_in_cm_per_s, read from `host_All` (the host's
+ *           own `All`; the other members come from the library's `All` or gadget_force_bind_all)
+ * dust_density() writes d7 of the grains; dust_drag() writes the grains' Vel, d9, DeltaDustMomentum,
+ * NewDragAcc (zero), DeltaDragEnergy and DustVcoll, and the gas's Vel, Entropy and dh.DragHeating (in/out:
+ * the records' value plus this step's heating); nothing else.  Single rank: with NTask > 1 both call
+ * endrun(90010).  lay == NULL unbinds. */
+struct gadget_force_dust_layout
+{
+  int p_particle_density, p_particle_velocity, p_delta_momentum, p_new_drag_acc, p_delta_energy,
+    p_radius, p_vcoll;
+  int s_drag_heating;
+  int a_mean_weight, a_unit_density, a_unit_velocity;
+};
+void gadget_force_bind_dust(void *host_All, const struct gadget_force_dust_layout *lay);
+void dust_density(void);
+void dust_drag(void);
+
 /* ---- more than one rank (NTask > 1): the drivers above become collectives ----
  * The host has decomposed the domain (domain_Decomposition, domain.c:100) and every rank holds the
  * particles of its key range in P[0, NumPart).  With NTask > 1 gravity_tree() / density() /

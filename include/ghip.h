@@ -474,6 +474,45 @@ int ghip_cooling_and_starformation(ghip_ctx *ctx, double Timebase_interval,
                                    double CritPhysDensity_code, double MinEgySpec,
                                    double u_to_temp_fac, int *flag_sink_host);
 
+/* ---- the dust-gas drag passes of the shipped flag bundle (DUST, DUST_TIMESTEP, DUST_POWERLAW,
+ * CONSTANT_MEAN_MOLECULAR_WEIGHT; no DUST_GROWTH*, DUST_VAPORIZE, DUST_TWO_POPULATIONS,
+ * DUST_REAL_PEBBLE_COLLISIONS, DUST_EPSTEIN, DUST_NO_FRICTION_HEATING): dust_density() and
+ * dust_drag() (dust.c:60-1029, called at accel.c:194, 198).  The grains are given by their particle
+ * indices (the active Type-2 particles in active-list order); their per-grain state travels in host
+ * arrays in list order.  Read from the resident fields: POS, MASS, TYPE, HSML, TIMEBIN, GRAVACCEL
+ * (the finished value gravity_tree() leaves), VEL and the gas ENTROPY.  Needs the trees of this step;
+ * the trees stay valid (no position or mass changes).  Single rank only: on a sharded or multi-GPU
+ * context both return GHIP_EINVAL. ---- */
+typedef struct
+{
+  int periodic;
+  double BoxSize;
+  double dt_fac;        /* grains: All.Timebase_interval / hubble_a (dust.c:348) */
+  double dt_fac_gas;    /* gas: All.Timebase_interval, / (All.Time * hubble_a) when comoving (:984-987) */
+  double MinEgySpec;
+  double MeanWeight;    /* All.MeanWeight (CONSTANT_MEAN_MOLECULAR_WEIGHT) */
+  double UnitLength_in_cm, UnitMass_in_g, UnitDensity_in_cgs, UnitVelocity_in_cm_per_s;
+} ghip_dust_params;
+/* dust_evaluate_density (dust.c:748-887): particle_density [ndust] = P[].d7.DUST_particle_density,
+ * the sum over the Type-2 neighbours with Mass > 0 within the grain's Hsml (itself included) of
+ * m_i * W(r, h_i) -- the GRAIN's mass m_i, as the reference has it (dust.c:849). */
+int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
+                      double *particle_density);
+/* dust_drag (dust.c:263-746 + dust_evaluate_select :889-1029).  In [ndust]: dust_density (d1),
+ * dust_entropy (d2), dust_gasvel [ndust][3] (d3), dust_radius, particle_density (d7).  In/out:
+ * particle_velocity [ndust][3] (d9: divided by d7 where d7 > 0), vcoll (DustVcoll: kept where
+ * d7 <= 0 and dt == 0).  Out: delta_momentum [ndust][3], delta_energy.  The grains' resident VEL,
+ * the gas's VEL and ENTROPY and the resident DragHeating are updated; each gas particle receives the
+ * grains in list order, as the reference's serial loop applies them (the entropy update is capped
+ * and floored, so the order matters).  Deterministic. */
+int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
+                   const double *dust_density, const double *dust_entropy, const double *dust_gasvel,
+                   const double *dust_radius, const double *particle_density, double *particle_velocity,
+                   double *delta_momentum, double *delta_energy, double *vcoll);
+/* the resident SphP[].dh.DragHeating [ngas] (zero when first used); NULL = skip */
+int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating);
+int ghip_dust_set_drag_heating(ghip_ctx *ctx, const double *drag_heating);
+
 /* The sink passes on a multi-GPU shard (GHIP_DD_SINK_DENSITY / _BH_EVALUATE / _BH_SWALLOW through
  * ghip_dd_begin / ghip_dd_run): the sinks of every shard are made known to all shards (a few hundred
  * 96-byte records), each shard evaluates ALL sinks against ITS OWN particles, and the partial sums
