@@ -109,6 +109,20 @@ class DustParams(C.Structure):
                 ("UnitDensity_in_cgs", C.c_double), ("UnitVelocity_in_cm_per_s", C.c_double)]
 
 
+# DoCooling variants of ghip_sfr_cooling (include/ghip.h)
+COOL_NONE, COOL_ISOTHERM, COOL_EVAPORATION, COOL_EVAPORATION_RADIAL, COOL_BETA = 0, 1, 2, 3, 4
+
+
+class SfrParams(C.Structure):
+    """ghip_sfr_params: cooling_and_starformation with DoCooling and the drag heating (include/ghip.h)"""
+    _fields_ = [("cooling", C.c_int), ("beta_tapper_off", C.c_int), ("dust", C.c_int),
+                ("comoving", C.c_int)] + [(k, C.c_double) for k in (
+                    "Timebase_interval", "Time", "hubble_a", "CritPhysDensity_code", "MinEgySpec",
+                    "OriginalGasMass", "MeanWeight", "UnitEnergy_in_cgs", "UnitMass_in_g",
+                    "UnitDensity_in_cgs", "EqTemp", "BetaCool", "Cool_ind", "rho_cool_ind",
+                    "Evap_dens")] + [("smbh_pos", C.c_double * 3)]
+
+
 class PmParams(C.Structure):
     _fields_ = [("pmgrid", C.c_int), ("BoxSize", C.c_double), ("G", C.c_double),
                 ("Asmth", C.c_double)]
@@ -202,7 +216,7 @@ EXPORTS = [
     "ghip_sink_get_marks", "ghip_sink_set_marks", "ghip_cooling_and_starformation",
     "ghip_set_async", "ghip_timebin_counts", "ghip_run_begin", "ghip_step_begin", "ghip_step_end",
     "ghip_run_end", "ghip_dust_density", "ghip_dust_drag", "ghip_dust_get_drag_heating",
-    "ghip_dust_set_drag_heating"]
+    "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh"]
 
 
 def lib():
@@ -303,6 +317,8 @@ def lib():
         L.ghip_dust_drag.argtypes = [vp, C.POINTER(DustParams), C.c_int] + [vp] * 10
         L.ghip_dust_get_drag_heating.argtypes = [vp, vp]
         L.ghip_dust_set_drag_heating.argtypes = [vp, vp]
+        L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
+        L.ghip_find_smbh.argtypes = [vp, C.c_double, vp, C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -383,10 +399,12 @@ class ForcePath:
     def set_active(self, idx=None):
         if idx is None:
             self._chk(self.L.ghip_set_active(self.h, None, 0))
+            self._active_n = None
         else:
             a = np.ascontiguousarray(idx, dtype=np.int32)
             self._active_keep = a
             self._chk(self.L.ghip_set_active(self.h, _ptr(a), len(a)))
+            self._active_n = len(a)
 
     def set_shard(self, rank, nranks):
         self._chk(self.L.ghip_set_shard(self.h, int(rank), int(nranks)))
@@ -704,6 +722,25 @@ class ForcePath:
                                                         float(min_egy), float(u_to_temp_fac),
                                                         _ptr(flag)))
         return flag
+
+    def sfr_cooling(self, params, count_only=False):
+        """ghip_sfr_cooling -> the sink candidates' particle indices in active-list order (int32);
+        with count_only, their number"""
+        nc = C.c_int(0)
+        if count_only:
+            self._chk(self.L.ghip_sfr_cooling(self.h, C.byref(params), C.byref(nc), None))
+            return nc.value
+        cap = max(self.counts()[0], getattr(self, "_active_n", None) or 0, 1)   # >= the active count
+        cand = np.zeros(cap, np.int32)
+        self._chk(self.L.ghip_sfr_cooling(self.h, C.byref(params), C.byref(nc), _ptr(cand)))
+        return cand[:nc.value].copy()
+
+    def find_smbh(self, smbh_mass):
+        """ghip_find_smbh -> (pos [3], count) of FindQuasars over the active particles"""
+        pos = np.zeros(3)
+        cnt = C.c_int(0)
+        self._chk(self.L.ghip_find_smbh(self.h, float(smbh_mass), _ptr(pos), C.byref(cnt)))
+        return pos, cnt.value
 
     # ---- dust-gas drag (dust.c): grains in list order ----
     def dust_density(self, params, dust):

@@ -331,6 +331,7 @@ struct ghip_ctx
                                     // SphP[].i.Injected_BH_Energy f64[ngas]
   DevBuf dust_heat;                 // dust_drag (ghip_dust.hip): SphP[].dh.DragHeating f64[ngas]
   DevBuf dust_idx, dust_work, dust_pairs, dust_cub;   // ... its grain list, per-grain planes, sorted pairs
+  DevBuf sfr_work, sfr_cub;         // ghip_sfr_cooling (ghip_sfr.hip): candidate flags, offsets, counts
   int timestep_endrun = 0;   // endrun code of the last ghip_advance_timesteps failure
   bool ev_ready = false;
 
@@ -448,6 +449,7 @@ static inline unsigned long long *ghip_rslot(ghip_ctx *ctx, int kind)
 // host copy of a slot buffer added up: out[kind][which], which = 0, 1
 int ghip_read_slots(ghip_ctx *ctx, DevBuf &buf, unsigned long long out[GHIP_CK_COUNT][2]);
 int ghip_mark_converted_gas(ghip_ctx *ctx);
+int ghip_sink_buffers(ghip_ctx *ctx);        // SwallowID / Injected_BH_Energy, zeroed when first made
 int ghip_unmark_massless_for_hydro(ghip_ctx *ctx);
 int ghip_check_gas_types(ghip_ctx *ctx);   // after TYPE changed: recount, sets ctx->gas_mixed (synchronises)
 int ghip_dyn_capture(ghip_ctx *ctx);                 // after a full build: copy the gravity tree, vs / vmax per node

@@ -593,7 +593,7 @@ __global__ void k_bh_scatter(int ns, const SinkRec *__restrict__ sinks, const do
     dst[sinks[a].index] = v[a];
 }
 
-static int sink_buffers(ghip_ctx *ctx)
+int ghip_sink_buffers(ghip_ctx *ctx)
 {
   const size_t n = (size_t) (ctx->n > 0 ? ctx->n : 1), ng = (size_t) (ctx->ngas > 0 ? ctx->ngas : 1);
   size_t before = ctx->bh_swallow.cap;
@@ -645,7 +645,7 @@ extern "C" int ghip_sink_reset(ghip_ctx *ctx)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   HIPCHK(hipMemsetAsync(ctx->bh_swallow.p, 0, ctx->bh_swallow.cap, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->bh_injected.p, 0, ctx->bh_injected.cap, ctx->stream));
   return GHIP_OK;
@@ -660,7 +660,7 @@ extern "C" int ghip_blackhole_evaluate(ghip_ctx *ctx, const ghip_bh_params *p, i
   GCHK(check_bh_call(ctx, p, nsink, sink_idx, sink_id, "ghip_blackhole_evaluate"));
   if(nsink > 0 && (!bh_mdot || !bh_density))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_evaluate: bad arguments");
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   if(nsink == 0)
     return GHIP_OK;
   std::vector<SinkRec> S;
@@ -695,7 +695,7 @@ extern "C" int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, in
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_swallow: bad arguments");
   if(counts)
     counts[0] = counts[1] = counts[2] = 0;
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   if(nsink == 0)
     return GHIP_OK;
   std::vector<SinkRec> S;
@@ -749,7 +749,7 @@ extern "C" int ghip_sink_get_marks(ghip_ctx *ctx, unsigned int *swallow_id, doub
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   hipStream_t st = ctx->stream;
   if(swallow_id && ctx->n > 0)
     HIPCHK(hipMemcpyAsync(swallow_id, ctx->bh_swallow.p, (size_t) ctx->n * 4, hipMemcpyDeviceToHost, st));
@@ -766,7 +766,7 @@ extern "C" int ghip_sink_set_marks(ghip_ctx *ctx, const unsigned int *swallow_id
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   hipStream_t st = ctx->stream;
   if(swallow_id && ctx->n > 0)
     HIPCHK(hipMemcpyAsync(ctx->bh_swallow.p, swallow_id, (size_t) ctx->n * 4, hipMemcpyHostToDevice, st));
@@ -838,7 +838,7 @@ extern "C" int ghip_cooling_and_starformation(ghip_ctx *ctx, double Timebase_int
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(sink_buffers(ctx));
+  GCHK(ghip_sink_buffers(ctx));
   const int ng = ctx->ngas;
   if(ng == 0)
     return GHIP_OK;
@@ -987,7 +987,7 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
           D.phase = 2;
           return dd_sink_density_pass(ctx);
         }
-      GCHK(sink_buffers(ctx));
+      GCHK(ghip_sink_buffers(ctx));
       TreeDev &t = ctx->gt;
       const size_t n = (size_t) ctx->n;
       if(op == GHIP_DD_BH_EVALUATE)

@@ -421,9 +421,9 @@ int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p);
  * BH_THERMALFEEDBACK + TMP_FEEDBACK, DUST, COOLING, SFR, BH_FORM).  The sinks are given by their
  * particle indices; their per-sink state (ID, Mdot, BH_Density, BH_Mass ...) travels in small host
  * arrays, the victims' marks (P[].SwallowID, SphP[].i.Injected_BH_Energy) are resident.  Scalar
- * bookkeeping per sink (blackhole_accretion(), blackhole.c:133-300, 680-760), the conversion of a
- * flagged gas particle into a sink (sfr_eff.c:606-640, GSL stream) and DoCooling (cooling.c) stay
- * host code.  On a multi-GPU shard the neighbour passes run through GHIP_DD_SINK_DENSITY /
+ * bookkeeping per sink (blackhole_accretion(), blackhole.c:133-300, 680-760) and the conversion of a
+ * flagged gas particle into a sink (sfr_eff.c:606-640, GSL stream) stay host code.  The cooling
+ * function (DoCooling, cooling.c) runs on the device in ghip_sfr_cooling below.  On a multi-GPU shard the neighbour passes run through GHIP_DD_SINK_DENSITY /
  * GHIP_DD_BH_EVALUATE / GHIP_DD_BH_SWALLOW below. ---- */
 typedef struct
 {
@@ -467,12 +467,63 @@ int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int nsink, co
 int ghip_sink_get_marks(ghip_ctx *ctx, unsigned int *swallow_id, double *injected_energy);
 int ghip_sink_set_marks(ghip_ctx *ctx, const unsigned int *swallow_id, const double *injected_energy);
 /* cooling_and_starformation (sfr_eff.c:82-947), per active gas particle (ghip_set_active), with the
- * cooling function as identity: flag_sink_host [ngas] = 1 where the particle qualifies for
+ * cooling function as identity (kept as it is; ghip_sfr_cooling below is the complete pass):
+ * flag_sink_host [ngas] = 1 where the particle qualifies for
  * conversion into a sink (:226-229), else the isochoric update of DTENTROPY incl. the injected
  * black-hole energy (:486-531, 582-594).  Non-comoving. */
 int ghip_cooling_and_starformation(ghip_ctx *ctx, double Timebase_interval,
                                    double CritPhysDensity_code, double MinEgySpec,
                                    double u_to_temp_fac, int *flag_sink_host);
+
+/* ---- cooling_and_starformation with the cooling function and the dust drag heating
+ * (sfr_eff.c:183-597 + DoCooling, cooling.c:82-300), per active particle in active-list order
+ * (ghip_set_active), for the shipped bundle (COOLING, SFR, DUST, BH_FORM, FIND_SMBH,
+ * EVAPORATION_RADIAL, CONSTANT_MEAN_MOLECULAR_WEIGHT) and its sibling closed forms.  The TREECOOL
+ * network (cooling.c:459-567) is compiled out under CONSTANT_MEAN_MOLECULAR_WEIGHT and not built. ---- */
+enum
+{
+  GHIP_COOL_NONE = 0,            /* u returned unchanged (also -DADIABATIC without sub-flags) */
+  GHIP_COOL_ISOTHERM,            /* u = EqTemp / u_to_temp_fac (cooling.c:170-173) */
+  GHIP_COOL_EVAPORATION,         /* tcool = BetaCool (1 + (rho / Evap_dens)^5) (:175-183) */
+  GHIP_COOL_EVAPORATION_RADIAL,  /* u_eq / (r^Cool_ind + 1e-10), (rho / Evap_dens)^rho_cool_ind (:185-192; shipped) */
+  GHIP_COOL_BETA                 /* u_eq / (r^0.5 + 1e-10), tcool = BetaCool r^1.5 (:196-198, 282);
+                                    beta_tapper_off: tcool *= 1 + (rho / 1e-10)^2 (:218-222) */
+};
+typedef struct
+{
+  int cooling;              /* GHIP_COOL_* */
+  int beta_tapper_off;      /* -DBETA_COOLING_TAPPER_OFF (GHIP_COOL_BETA only) */
+  int dust;                 /* -DDUST: spend the resident DragHeating (sfr_eff.c:481-499) */
+  int comoving;             /* All.ComovingIntegrationOn */
+  double Timebase_interval; /* All.Timebase_interval */
+  double Time, hubble_a;    /* All.Time, hubble_function(All.Time) (comoving only): a3inv = 1 / Time^3,
+                               dtime = Time dt / (Time hubble_a) (sfr_eff.c:145-156, 191-196) */
+  double CritPhysDensity_code;  /* All.CritPhysDensity * UnitLength_in_cm^3 / UnitMass_in_g (:226-229) */
+  double MinEgySpec, OriginalGasMass;
+  double MeanWeight, UnitEnergy_in_cgs, UnitMass_in_g, UnitDensity_in_cgs;
+  double EqTemp, BetaCool, Cool_ind, rho_cool_ind, Evap_dens;   /* All.* of cooling.c */
+  double smbh_pos[3];       /* All.xbh, ybh, zbh (ghip_find_smbh); the origin when FIND_SMBH is off */
+} ghip_sfr_params;
+/* For each active particle, in active-list order: an active Type-2 grain with Mass <= 1e-5
+ * OriginalGasMass gets Mass = 0 in the resident MASS (:185-187); an active gas particle is a sink
+ * candidate when Density >= CritPhysDensity_code and Mass != 0 (:226-229, 459-462), else
+ *   unew = max(MinEgySpec, (A + dA/dt dt) / (gamma-1) (rho a3inv)^(gamma-1))       (:486-488)
+ *        + DragHeating / Mass dt, DragHeating = 0 (dust; neither when Mass == 0)  (:481-499)
+ *        + Injected_BH_Energy / Mass, 5e9 K ceiling, the injection consumed       (:502-524)
+ *   unew = DoCooling(unew, rho a3inv, dtime, r2)  with r2 = |Pos - smbh_pos|^2 (not wrapped)
+ *   dA/dt = (unew (gamma-1) / (rho a3inv)^(gamma-1) - A) / dt, floor -A / (2 dt)  (:572-595)
+ * Reads POS, MASS, TYPE, TIMEBIN, DENSITY, ENTROPY, DTENTROPY, the resident Injected_BH_Energy and
+ * (dust) DragHeating -- zero when it was never set.  Writes DTENTROPY, MASS (grains), the two marks.
+ * *ncand = the number of candidates; cand_idx [*ncand] (NULL: count only) their particle indices in
+ * active-list order (a stable device compaction: the host reads ncand ints, not ngas).  NULL params or
+ * an unknown cooling: GHIP_EINVAL; so is dust = 1 on a sharded or multi-GPU context (DragHeating
+ * exists on single-rank contexts only).  With dust = 0 a shard runs the pass on its own particles. */
+int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *ncand, int *cand_idx);
+/* the position part of FindQuasars (blackhole.c:1481-1530): over the active particles, pos = the
+ * position of the LAST one in active-list order with Type 5 and Mass > 0.9 SMBHmass (the origin if
+ * none), *count = how many there are.  Across ranks the host adds pos and count (MPI_Allreduce SUM,
+ * as the reference does). */
+int ghip_find_smbh(ghip_ctx *ctx, double SMBHmass, double pos[3], int *count);
 
 /* ---- the dust-gas drag passes of the shipped flag bundle (DUST, DUST_TIMESTEP, DUST_POWERLAW,
  * CONSTANT_MEAN_MOLECULAR_WEIGHT; no DUST_GROWTH*, DUST_VAPORIZE, DUST_TWO_POPULATIONS,
