@@ -109,6 +109,15 @@ class DustParams(C.Structure):
                 ("UnitDensity_in_cgs", C.c_double), ("UnitVelocity_in_cm_per_s", C.c_double)]
 
 
+class IntegrationFlags(C.Structure):
+    """ghip_integration_flags: the shipped bundle's rules of get_timestep / do_the_kick /
+    drift_particle (include/ghip.h)"""
+    _fields_ = [(k, C.c_int) for k in ("dust", "dust_timestep", "black_holes", "accretion_radius",
+                                        "virtual_particles")] + \
+        [(k, C.c_double) for k in ("OuterBoundary", "AccDtBlackHole", "SMBHmass", "InnerBoundary",
+                                   "SinkBoundary", "FeedBackVelocity", "UnitVelocity_in_cm_per_s")]
+
+
 # DoCooling variants of ghip_sfr_cooling (include/ghip.h)
 COOL_NONE, COOL_ISOTHERM, COOL_EVAPORATION, COOL_EVAPORATION_RADIAL, COOL_BETA = 0, 1, 2, 3, 4
 
@@ -216,7 +225,8 @@ EXPORTS = [
     "ghip_sink_get_marks", "ghip_sink_set_marks", "ghip_cooling_and_starformation",
     "ghip_set_async", "ghip_timebin_counts", "ghip_run_begin", "ghip_step_begin", "ghip_step_end",
     "ghip_run_end", "ghip_dust_density", "ghip_dust_drag", "ghip_dust_get_drag_heating",
-    "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh"]
+    "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh", "ghip_set_integration_flags",
+    "ghip_kick_set_fields", "ghip_kick_get_drag_accel"]
 
 
 def lib():
@@ -319,6 +329,9 @@ def lib():
         L.ghip_dust_set_drag_heating.argtypes = [vp, vp]
         L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
         L.ghip_find_smbh.argtypes = [vp, C.c_double, vp, C.POINTER(C.c_int)]
+        L.ghip_set_integration_flags.argtypes = [vp, C.POINTER(IntegrationFlags)]
+        L.ghip_kick_set_fields.argtypes = [vp, vp, vp, vp]
+        L.ghip_kick_get_drag_accel.argtypes = [vp, vp]
         _LIB = L
     return _LIB
 
@@ -774,6 +787,24 @@ class ForcePath:
         dh = np.ascontiguousarray(dh, np.float64)
         assert dh.shape == (self.ngas,)
         self._chk(self.L.ghip_dust_set_drag_heating(self.h, _ptr(dh)))
+
+    # ---- the shipped bundle's integrator rules (ghip_set_integration_flags) ----
+    def set_integration_flags(self, flags=None):
+        """IntegrationFlags or None (the minimal flag set); governs advance_timesteps and drift"""
+        self._chk(self.L.ghip_set_integration_flags(self.h, None if flags is None else C.byref(flags)))
+
+    def kick_set_fields(self, drag_accel=None, gas_dust_momentum=None, new_density=None):
+        """gas DragAccel [ngas][3], gas DeltaDustMomentum [ngas][3], NewDensity [n]; None = zero"""
+        a = [None if v is None else np.ascontiguousarray(v, np.float64) for v in
+             (drag_accel, gas_dust_momentum, new_density)]
+        for v, shape in zip(a, ((self.ngas, 3), (self.ngas, 3), (self.n,))):
+            assert v is None or v.shape == shape
+        self._chk(self.L.ghip_kick_set_fields(self.h, *[None if v is None else _ptr(v) for v in a]))
+
+    def kick_drag_accel(self):
+        out = np.zeros((self.ngas, 3))
+        self._chk(self.L.ghip_kick_get_drag_accel(self.h, _ptr(out)))
+        return out
 
     # ---- multi-GPU: domain decomposition with tree-node / ghost exchange (include/ghip.h) ----
     def dd_init(self, rank, nranks):

@@ -320,7 +320,8 @@ extern "C" void ghip_destroy(ghip_ctx *ctx)
                   &ctx->plan_steps[2][1], &ctx->tax2, &ctx->tay2, &ctx->taz2, &ctx->tcost2,
                   &ctx->plan_nsub2, &ctx->plan_woff2, &ctx->plan_wave2, &ctx->cubtmp2, &ctx->cubtmp3,
                   &ctx->bh_swallow, &ctx->bh_injected, &ctx->dust_heat, &ctx->dust_idx,
-                  &ctx->dust_work, &ctx->dust_pairs, &ctx->dust_cub, &ctx->sfr_work, &ctx->sfr_cub};
+                  &ctx->dust_work, &ctx->dust_pairs, &ctx->dust_cub, &ctx->sfr_work, &ctx->sfr_cub,
+                  &ctx->kick_drag, &ctx->kick_ddm, &ctx->kick_newdens};
   for(DevBuf *b : bs)
     free_buf(*b);
   free_tree(ctx->gt);

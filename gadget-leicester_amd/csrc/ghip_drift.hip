@@ -11,6 +11,16 @@
 
 #include "ghip_timefac.h"
 
+// the shipped bundle's rules (ghip_set_integration_flags); the default kernel has none of them
+struct DriftB
+{
+  int dust, virt;
+  const double *drag;   // SphP[].da.DragAccel [3][ngas] or null (zero)
+};
+
+// X... is empty for the default kernel (the minimal flag set: same signature, same code as before the
+// bundle existed) and one DriftB for the bundle's rules
+template <bool BUNDLE, class... X>
 __global__ void k_drift(int n, int ngas, DriftK k, double *__restrict__ pos,
                         const double *__restrict__ vel, const int *__restrict__ type,
                         int *__restrict__ ti_current, const int *__restrict__ timebin,
@@ -20,20 +30,26 @@ __global__ void k_drift(int n, int ngas, DriftK k, double *__restrict__ pos,
                         double *__restrict__ density, double *__restrict__ hsml,
                         const double *__restrict__ divvel, const double *__restrict__ entropy,
                         const double *__restrict__ dtentropy, double *__restrict__ pressure,
-                        int *__restrict__ err, int *errw)
+                        int *__restrict__ err, int *errw, X... xs)
 {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
     return;
+  bool skip = false;   // predict.c:134-136: a virtual particle is not drifted
+  if constexpr(BUNDLE)
+    {
+      const DriftB &x = (xs, ...);
+      skip = x.virt && type[i] == 3;
+    }
   int time0 = ti_current[i];
-  if(k.time1 < time0)
+  if(k.time1 < time0 && !skip)
     {
       atomicMax(err, 12);  // predict.c:148-152: endrun(12)
       if(errw)             // asynchronous mode: the pinned word the next synchronising call checks
         *(volatile int *) errw = 12;
       return;
     }
-  if(k.time1 != time0)
+  if(k.time1 != time0 && !skip)
     {
       double dt_drift, dt_gravkick, dt_hydrokick;
       if(k.comoving)
@@ -57,6 +73,12 @@ __global__ void k_drift(int n, int ngas, DriftK k, double *__restrict__ pos,
                 g = g + gravpm[(size_t) j * n + i];
               velpred[(size_t) j * ngas + i] +=
                 g * dt_gravkick + hydroaccel[(size_t) j * ngas + i] * dt_hydrokick;
+              if constexpr(BUNDLE)
+                {
+                  const DriftB &x = (xs, ...);
+                  if(x.dust && x.drag)   // predict.c:195-198
+                    velpred[(size_t) j * ngas + i] += x.drag[(size_t) j * ngas + i] * dt_hydrokick;
+                }
             }
           double dv = divvel[i];
           density[i] *= exp(-dv * dt_drift);
@@ -124,17 +146,40 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
       k.gravkick = d + DRIFT_TABLE_LENGTH;
       k.hydrokick = d + 2 * DRIFT_TABLE_LENGTH;
     }
-  k_drift<<<cdiv(n, 256), 256, 0, st>>>(
-    n, ng, k, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_VEL]),
-    P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TI_CURRENT]),
-    P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]),
-    P<double>(ctx->f[GHIP_F_GRAVACCEL]),
-    p->pmgrid ? P<double>(ctx->f[GHIP_F_GRAVPM]) : (const double *) nullptr,
-    P<double>(ctx->f[GHIP_F_VELPRED]),
-    P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DENSITY]),
-    P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]),
-    P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
-    P<double>(ctx->f[GHIP_F_PRESSURE]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_DRIFT) : nullptr);
+  if(ctx->iflags_on && ctx->has_drag && ctx->kick_fields_ngas != ng)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_drift: DragAccel was set for %d gas particles, the context "
+                     "has %d (ghip_kick_set_fields again)", ctx->kick_fields_ngas, ng);
+  if(ctx->iflags_on)
+    {
+      DriftB x;
+      x.dust = ctx->iflags.dust;
+      x.virt = ctx->iflags.virtual_particles;
+      x.drag = ctx->has_drag ? P<double>(ctx->kick_drag) : nullptr;
+      k_drift<true><<<cdiv(n, 256), 256, 0, st>>>(
+        n, ng, k, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_VEL]),
+        P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TI_CURRENT]),
+        P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]),
+        P<double>(ctx->f[GHIP_F_GRAVACCEL]),
+        p->pmgrid ? P<double>(ctx->f[GHIP_F_GRAVPM]) : (const double *) nullptr,
+        P<double>(ctx->f[GHIP_F_VELPRED]),
+        P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DENSITY]),
+        P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]),
+        P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
+        P<double>(ctx->f[GHIP_F_PRESSURE]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_DRIFT) : nullptr,
+        x);
+    }
+  else
+    k_drift<false><<<cdiv(n, 256), 256, 0, st>>>(
+      n, ng, k, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_VEL]),
+      P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TI_CURRENT]),
+      P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]),
+      P<double>(ctx->f[GHIP_F_GRAVACCEL]),
+      p->pmgrid ? P<double>(ctx->f[GHIP_F_GRAVPM]) : (const double *) nullptr,
+      P<double>(ctx->f[GHIP_F_VELPRED]),
+      P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DENSITY]),
+      P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]),
+      P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
+      P<double>(ctx->f[GHIP_F_PRESSURE]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_DRIFT) : nullptr);
   HIPCHK(hipGetLastError());
   ctx->gt.built = false;  // positions moved: the trees are stale
   ctx->st.built = false;

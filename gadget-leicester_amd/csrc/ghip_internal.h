@@ -333,6 +333,12 @@ struct ghip_ctx
   DevBuf dust_idx, dust_work, dust_pairs, dust_cub;   // ... its grain list, per-grain planes, sorted pairs
   DevBuf sfr_work, sfr_cub;         // ghip_sfr_cooling (ghip_sfr.hip): candidate flags, offsets, counts
   int timestep_endrun = 0;   // endrun code of the last ghip_advance_timesteps failure
+  // the shipped bundle's integrator (ghip_set_integration_flags, ghip_kick.hip / ghip_drift.hip)
+  bool iflags_on = false;
+  ghip_integration_flags iflags = {};
+  DevBuf kick_drag, kick_ddm, kick_newdens;   // f64[3][ngas], f64[3][ngas], f64[n]
+  bool has_drag = false, has_ddm = false, has_newdens = false;
+  int kick_fields_n = -1, kick_fields_ngas = -1;   // counts the fields were set for
   bool ev_ready = false;
 
   // ---- asynchronous tree build (ghip_tree.hip) ----

@@ -4,8 +4,11 @@
 // Replaces the loop of advance_and_find_timesteps() (timestep.c:142-260) with get_timestep()
 // (timestep.c:607-1123; flag == 0, TypeOfTimestepCriterion 0) and do_the_kick()
 // (timestep.c:364-605) for the minimal periodic flag set -- no PMGRID long-range kick, no
-// BLACK_HOLES / DUST / MAGNETIC terms -- and the per-type sums of
-// find_dt_displacement_constraint() (timestep.c:1125-1224).  DoDynamicUpdate / force_kick_node
+// MAGNETIC terms -- and the per-type sums of find_dt_displacement_constraint()
+// (timestep.c:1125-1224).  The shipped bundle's rules (DUST, DUST_TIMESTEP, BLACK_HOLES +
+// ACCRETION_RADIUS, VIRTUAL: grains, sinks, virtual particles, DragAccel) are the
+// k_advance_timesteps<true> instantiation, chosen by ghip_set_integration_flags; the default
+// instantiation is the minimal set's kernel, instruction for instruction.  DoDynamicUpdate / force_kick_node
 // (forcetree.c:1474-1651) has no counterpart: the device tree is rebuilt every step.  The host
 // keeps the linked lists of the time bins (FirstInTimeBin...) -- it rebuilds them from the
 // returned TimeBin[] as reconstruct_timebins() does.
@@ -41,6 +44,21 @@ struct KickK
   DriftK tab;   // gravkick / hydrokick tables (comoving)
 };
 
+// the shipped bundle's rules (ghip_set_integration_flags); the default kernel has none of them
+struct KickB
+{
+  int dust, dust_timestep, black_holes, accretion_radius, virt;
+  double dt_abs;     // Type 3: min(0.03 OuterBoundary / C UnitVelocity FeedBackVelocity, dt_ff = 1)
+  double dt_accr0;   // Type 5: 0.03 (OuterBoundary / 100)
+  double acc_dt, smbh_mass, inner, sink;
+  const double *mass;        // [n]
+  double *drag;              // [3][ngas] or null (zero)
+  const double *ddm;         // [3][ngas] or null (zero)
+};
+
+// X... is empty for the default kernel (the minimal flag set: same signature, same code as before the
+// bundle existed) and one KickB for the bundle's rules; every rule sits in an `if constexpr`
+template <bool BUNDLE, class... X>
 __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n, int ngas, KickK k,
                                     const int *__restrict__ type, double *__restrict__ vel,
                                     const double *__restrict__ gravaccel,
@@ -53,7 +71,7 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
                                     const double *__restrict__ maxsignalvel,
                                     int *__restrict__ timebin, int *__restrict__ ti_begstep,
                                     int *__restrict__ err, int *errw, double *__restrict__ kick_dv,
-                                    int *__restrict__ kick_flag)
+                                    int *__restrict__ kick_flag, X... xs)
 {
 // (errw: asynchronous mode, the pinned word the next synchronising call checks)
 #define D_RAISE(code)                   \
@@ -93,11 +111,45 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
       ax += k.fac2 * hy[0];
       ay += k.fac2 * hy[1];
       az += k.fac2 * hy[2];
+      if constexpr(BUNDLE)
+        {
+          const KickB &x = (xs, ...);
+          if(x.dust && gas && x.drag)   // timestep.c:673-677
+            {
+              ax += k.fac2 * x.drag[i];
+              ay += k.fac2 * x.drag[(size_t) ngas + i];
+              az += k.fac2 * x.drag[2 * (size_t) ngas + i];
+            }
+        }
     }
   double ac = sqrt(ax * ax + ay * ay + az * az);
   if(ac == 0)
     ac = 1.0e-30;
   double dt = sqrt(2 * k.errtol * k.atime * k.soft[ty] / ac);
+  if constexpr(BUNDLE)
+    {
+      const KickB &x = (xs, ...);
+      if(x.dust_timestep && ty == 0 && x.mass[i] > 0)   // timestep.c:710-722
+        {
+          const double m = x.mass[i];
+          double d[3] = {0, 0, 0};
+          if(gas && x.ddm)
+            for(int j = 0; j < 3; j++)
+              d[j] = x.ddm[(size_t) j * ngas + i];
+          ax += d[0] / m / dt;
+          ay += d[1] / m / dt;
+          az += d[2] / m / dt;
+          ac = sqrt(ax * ax + ay * ay + az * az);   // (the overwrite below reads this ac)
+          if(ac > 0)   // (ac == 0: the reference compares an uninitialised dt_new; dt stays)
+            {
+              double dt_new = sqrt(2 * k.errtol * k.atime * k.soft[ty] / ac);
+              if(dt_new < dt)
+                dt = dt_new;
+            }
+        }
+      if(x.dust && ty == 2)   // timestep.c:725-726
+        dt = dt / 2;
+    }
   if(k.adaptive_hsml && ty == 0)   // timestep.c:740-743
     dt = sqrt(2 * k.errtol * k.atime * hsml[i] / 2.8 / ac);
   if(gas)
@@ -109,6 +161,32 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
         dt_courant = 2 * k.courant * hsml[i] / maxsignalvel[i];
       if(dt_courant < dt)
         dt = dt_courant;
+    }
+  if constexpr(BUNDLE)
+    {
+      const KickB &x = (xs, ...);
+      if(x.virt && ty == 3)   // timestep.c:887-897
+        {
+          if(dt > x.dt_abs)
+            dt = x.dt_abs;
+        }
+      if(x.black_holes && ty == 5)   // timestep.c:908-947
+        {
+          double dt_accr = x.dt_accr0;
+          if(x.accretion_radius)
+            {
+              const double m = x.mass[i];
+              double dt_a = 1.e10;
+              if(m >= 0.45 * x.smbh_mass && x.inner > 0)
+                dt_a = x.acc_dt * pow((x.inner + 0.5 * hsml[i]), 1.5) / pow(m, 0.5);
+              if(m < 0.45 * x.smbh_mass && x.sink > 0)
+                dt_a = x.acc_dt * pow((x.sink + 0.5 * hsml[i]), 1.5) / pow(m, 0.5);
+              if(dt_accr > dt_a)
+                dt_accr = dt_a;
+            }
+          if(dt_accr < dt)
+            dt = dt_accr;
+        }
     }
   dt *= k.hubble_a;
   if(dt >= k.maxdt)
@@ -160,6 +238,14 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
   const int tend = tb0 + ti_step_old + ti_step / 2;   // midpoint of new step
   const int tcurrent = tb0 + ti_step_old;
   ti_begstep[i] = tcurrent;
+  bool grain = false;   // timestep.c:410-418: dv = 0, dust_drag has integrated the grain's velocity
+  if constexpr(BUNDLE)
+    {
+      const KickB &x = (xs, ...);
+      if(x.virt && ty == 3)
+        return;   // timestep.c:375-377: no kick, no force_kick_node
+      grain = x.dust && ty == 2;
+    }
 
   // ---- do_the_kick, timestep.c:378-395 ----
   double dt_entr, dt_gravkick, dt_hydrokick, dt_gravkick2, dt_hydrokick2;
@@ -177,8 +263,14 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
       dt_gravkick2 = dt_hydrokick2 = (tend - tcurrent) * k.timebase;
     }
   double v[3];
-  for(int j = 0; j < 3; j++)
-    v[j] = vel[(size_t) j * n + i] + g[j] * dt_gravkick;   // timestep.c:413-424
+  if constexpr(BUNDLE)
+    {
+      for(int j = 0; j < 3; j++)
+        v[j] = vel[(size_t) j * n + i] + (grain ? 0.0 : g[j] * dt_gravkick);
+    }
+  else
+    for(int j = 0; j < 3; j++)
+      v[j] = vel[(size_t) j * n + i] + g[j] * dt_gravkick;   // timestep.c:413-424
   if(gas)
     {
       for(int j = 0; j < 3; j++)
@@ -188,6 +280,12 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
           if(k.pmgrid)
             vp += pm[j] * k.dt_gravkickB;   // timestep.c:511-513
           velpred[(size_t) j * ngas + i] = vp;
+          if constexpr(BUNDLE)
+            {
+              const KickB &x = (xs, ...);
+              if(x.dust && x.drag)
+                x.drag[(size_t) j * ngas + i] = 0.;   // timestep.c:508
+            }
         }
       double A = entropy[i], dA = dtentropy[i];
       if(dA * dt_entr > -0.5 * A)   // timestep.c:553-557
@@ -212,8 +310,15 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
   // a kept tree (ghip_set_dynamic_tree): what force_kick_node(i, dv) receives, timestep.c:584-588
   if(kick_dv)
     {
-      for(int j = 0; j < 3; j++)
-        kick_dv[(size_t) j * n + i] = g[j] * dt_gravkick + (gas ? hy[j] * dt_hydrokick : 0.0);
+      if constexpr(BUNDLE)
+        {
+          for(int j = 0; j < 3; j++)
+            kick_dv[(size_t) j * n + i] =
+              (grain ? 0.0 : g[j] * dt_gravkick) + (gas ? hy[j] * dt_hydrokick : 0.0);
+        }
+      else
+        for(int j = 0; j < 3; j++)
+          kick_dv[(size_t) j * n + i] = g[j] * dt_gravkick + (gas ? hy[j] * dt_hydrokick : 0.0);
       kick_flag[i] = 1;
     }
   for(int j = 0; j < 3; j++)
@@ -273,6 +378,128 @@ extern "C" int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long 
       if(TimeBinCountSph)
         TimeBinCountSph[b] = (long long) hist[32 + b];
     }
+  return ghip_check_device_errors(ctx);
+}
+
+// ---- the shipped bundle's rules: switches and the resident per-particle inputs ----
+#define GHIP_C_LIGHT 2.9979e10   // allvars.h:86
+
+static bool kick_sharded(const ghip_ctx *ctx)
+{
+  return ctx->shard_n > 1 || (ctx->dd.on && ctx->dd.nranks > 1);
+}
+
+// the arguments of k_advance_timesteps<true>; fails when fields were set for other particle counts
+static int kick_bundle_args(ghip_ctx *ctx, KickB *x, const char *who)
+{
+  memset(x, 0, sizeof(*x));
+  if(!ctx->iflags_on)
+    return GHIP_OK;
+  const ghip_integration_flags &f = ctx->iflags;
+  x->dust = f.dust;
+  x->dust_timestep = f.dust_timestep;
+  x->black_holes = f.black_holes;
+  x->accretion_radius = f.accretion_radius;
+  x->virt = f.virtual_particles;
+  // timestep.c:891-894, left to right as the host evaluates it; dt_ff = 1
+  double dt_abs = 0.03 * f.OuterBoundary / GHIP_C_LIGHT * f.UnitVelocity_in_cm_per_s * f.FeedBackVelocity;
+  double dt_ff = 1.;
+  if(dt_abs > dt_ff)
+    dt_abs = dt_ff;
+  x->dt_abs = dt_abs;
+  x->dt_accr0 = 0.03 * (f.OuterBoundary / 100.);   // timestep.c:910
+  x->acc_dt = f.AccDtBlackHole;
+  x->smbh_mass = f.SMBHmass;
+  x->inner = f.InnerBoundary;
+  x->sink = f.SinkBoundary;
+  x->mass = P<double>(ctx->f[GHIP_F_MASS]);
+  if((ctx->has_drag || ctx->has_ddm) && ctx->kick_fields_ngas != ctx->ngas)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: DragAccel / DeltaDustMomentum were set for %d gas particles, "
+                     "the context has %d (ghip_kick_set_fields again)", who, ctx->kick_fields_ngas, ctx->ngas);
+  x->drag = ctx->has_drag ? P<double>(ctx->kick_drag) : nullptr;
+  x->ddm = ctx->has_ddm ? P<double>(ctx->kick_ddm) : nullptr;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_set_integration_flags(ghip_ctx *ctx, const ghip_integration_flags *f)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  ctx->iflags_on = f != nullptr;
+  if(f)
+    ctx->iflags = *f;
+  else
+    memset(&ctx->iflags, 0, sizeof(ctx->iflags));
+  return GHIP_OK;
+}
+
+// host [m][3] -> device planes [3][m]
+static int upload_planes(ghip_ctx *ctx, DevBuf &b, const double *h, int m)
+{
+  GCHK(ghip_ensure(ctx, b, 3 * (size_t) (m > 0 ? m : 1) * 8));
+  std::vector<double> t(3 * (size_t) m);
+  for(int a = 0; a < m; a++)
+    for(int j = 0; j < 3; j++)
+      t[(size_t) j * m + a] = h[3 * (size_t) a + j];
+  if(m > 0)
+    HIPCHK(hipMemcpyAsync(b.p, t.data(), t.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_kick_set_fields(ghip_ctx *ctx, const double *drag_accel, const double *gas_dust_momentum,
+                                    const double *new_density)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  if((drag_accel || gas_dust_momentum || new_density) && kick_sharded(ctx))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_kick_set_fields: DragAccel / DeltaDustMomentum / NewDensity "
+                     "are kept on single-rank contexts only (this one is sharded or multi-GPU)");
+  const int n = ctx->n, ng = ctx->ngas;
+  ctx->has_drag = ctx->has_ddm = ctx->has_newdens = false;
+  if(drag_accel)
+    GCHK(upload_planes(ctx, ctx->kick_drag, drag_accel, ng));
+  if(gas_dust_momentum)
+    GCHK(upload_planes(ctx, ctx->kick_ddm, gas_dust_momentum, ng));
+  if(new_density)
+    {
+      GCHK(ghip_ensure(ctx, ctx->kick_newdens, (size_t) (n > 0 ? n : 1) * 8));
+      if(n > 0)
+        HIPCHK(hipMemcpyAsync(ctx->kick_newdens.p, new_density, (size_t) n * 8, hipMemcpyHostToDevice,
+                              ctx->stream));
+      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+    }
+  ctx->has_drag = drag_accel != nullptr;
+  ctx->has_ddm = gas_dust_momentum != nullptr;
+  ctx->has_newdens = new_density != nullptr;
+  ctx->kick_fields_n = n;
+  ctx->kick_fields_ngas = ng;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_kick_get_drag_accel(ghip_ctx *ctx, double *drag_accel)
+{
+  if(!ctx || !drag_accel)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  const int ng = ctx->ngas;
+  if(!ctx->has_drag)
+    {
+      memset(drag_accel, 0, 3 * (size_t) ng * 8);
+      return GHIP_OK;
+    }
+  if(ctx->kick_fields_ngas != ng)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_kick_get_drag_accel: DragAccel was set for %d gas particles, "
+                     "the context has %d", ctx->kick_fields_ngas, ng);
+  std::vector<double> t(3 * (size_t) ng);
+  if(ng > 0)
+    HIPCHK(hipMemcpyAsync(t.data(), ctx->kick_drag.p, t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(int a = 0; a < ng; a++)
+    for(int j = 0; j < 3; j++)
+      drag_accel[3 * (size_t) a + j] = t[(size_t) j * ng + a];
   return ghip_check_device_errors(ctx);
 }
 
@@ -354,8 +581,21 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
       GCHK(ghip_ensure(ctx, ctx->kick_flag, (size_t) n * 4));
       HIPCHK(hipMemsetAsync(ctx->kick_flag.p, 0, (size_t) n * 4, st));
     }
-  if(nact > 0)
-    k_advance_timesteps<<<cdiv(nact, 256), 256, 0, st>>>(
+  KickB x;
+  GCHK(kick_bundle_args(ctx, &x, "ghip_advance_timesteps"));
+  if(nact > 0 && ctx->iflags_on)
+    k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(
+      nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
+      P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),
+      P<double>(ctx->f[GHIP_F_HYDROACCEL]),
+      P<double>(ctx->f[GHIP_F_VELPRED]), P<double>(ctx->f[GHIP_F_ENTROPY]),
+      P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_DENSITY]),
+      P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]),
+      P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr,
+      ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr,
+      record ? P<double>(ctx->kick_dv) : nullptr, record ? P<int>(ctx->kick_flag) : nullptr, x);
+  else if(nact > 0)
+    k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(
       nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
       P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),
       P<double>(ctx->f[GHIP_F_HYDROACCEL]),

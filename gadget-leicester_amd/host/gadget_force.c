@@ -1348,6 +1348,167 @@ int get_timestep_bin(int ti_step)
   return bin;
 }
 
+/* ---- the shipped bundle's integrator (gadget_force_bind_integration) ---- */
+static struct gadget_force_integration_layout IntLay;   /* (all -1 until bound) */
+static const char *IntAll = NULL;                       /* the host's All for IntLay.a_*; NULL: unbound */
+static double *BinSfr = NULL, *BinBhMass = NULL, *BinBhDynMass = NULL, *BinBhMdot = NULL;
+__attribute__((constructor)) static void int_lay_defaults(void)
+{
+  memset(&IntLay, 0xff, sizeof(IntLay));
+}
+
+void gadget_force_bind_integration(void *host_All, const struct gadget_force_integration_layout *lay,
+                                   double *TimeBinSfr, double *TimeBin_BH_mass,
+                                   double *TimeBin_BH_dynamicalmass, double *TimeBin_BH_Mdot)
+{
+  if(lay && host_All)
+    {
+      IntLay = *lay;
+      IntAll = (const char *) host_All;
+      BinSfr = TimeBinSfr;
+      BinBhMass = TimeBin_BH_mass;
+      BinBhDynMass = TimeBin_BH_dynamicalmass;
+      BinBhMdot = TimeBin_BH_Mdot;
+    }
+  else
+    {
+      int_lay_defaults();
+      IntAll = NULL;
+      BinSfr = BinBhMass = BinBhDynMass = BinBhMdot = NULL;
+    }
+}
+
+static int integration_bound(void)
+{
+  return IntAll != NULL;
+}
+
+static double int_all(int off)
+{
+  return off >= 0 ? *(const double *) (IntAll + off) : 0.0;
+}
+
+/* the per-particle inputs are kept on a single GPU: a multi-rank host that names them stops here */
+static int integration_refuse_ranks(void)
+{
+  if(!integration_bound() || NTask <= 1)
+    return 0;
+  if(IntLay.s_drag_accel >= 0 || IntLay.p_delta_dust_momentum >= 0 || IntLay.p_new_density >= 0)
+    {
+      snprintf(ErrBuf, sizeof(ErrBuf), "advance_and_find_timesteps: DragAccel / DeltaDustMomentum / NewDensity "
+               "are kept on a single GPU only (NTask = %d): bind s_drag_accel = p_delta_dust_momentum = "
+               "p_new_density = -1 (offsets %d / %d / %d)", NTask, IntLay.s_drag_accel,
+               IntLay.p_delta_dust_momentum, IntLay.p_new_density);
+      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+      endrun(90011);
+      return -1;
+    }
+  return 0;
+}
+
+/* before the kick: the switches and, on one rank, DragAccel and the gas's DeltaDustMomentum reach the
+ * device.  NewDensity is not uploaded: the kick never reads it (dt_ff = 1); its offset only
+ * takes part in the multi-rank refusal above */
+static int integration_begin(void)
+{
+  if(!integration_bound())
+    return chk(ghip_set_integration_flags(Ctx, NULL), "ghip_set_integration_flags");
+  const int fields = IntLay.s_drag_accel >= 0 || IntLay.p_delta_dust_momentum >= 0;
+  ghip_integration_flags f;
+  memset(&f, 0, sizeof(f));
+  f.dust = Cfg.dust;
+  f.dust_timestep = IntLay.dust_timestep > 0;
+  f.black_holes = Cfg.black_holes;
+  f.accretion_radius = IntLay.accretion_radius > 0;
+  f.virtual_particles = IntLay.virtual_particles > 0;
+  f.OuterBoundary = int_all(IntLay.a_outer_boundary);
+  f.AccDtBlackHole = int_all(IntLay.a_acc_dt_black_hole);
+  f.SMBHmass = All.SMBHmass;
+  f.InnerBoundary = All.InnerBoundary;
+  f.SinkBoundary = All.SinkBoundary;
+  f.FeedBackVelocity = int_all(IntLay.a_feedback_velocity);
+  f.UnitVelocity_in_cm_per_s = int_all(IntLay.a_unit_velocity);
+  if(chk(ghip_set_integration_flags(Ctx, &f), "ghip_set_integration_flags"))
+    return -1;
+  if(!fields)
+    return chk(ghip_kick_set_fields(Ctx, NULL, NULL, NULL), "ghip_kick_set_fields");
+  const int ng = N_gas;
+  double *drag = IntLay.s_drag_accel >= 0 ? (double *) malloc(((size_t) 3 * ng + 1) * 8) : NULL;
+  double *ddm = IntLay.p_delta_dust_momentum >= 0 ? (double *) malloc(((size_t) 3 * ng + 1) * 8) : NULL;
+  if((IntLay.s_drag_accel >= 0 && !drag) || (IntLay.p_delta_dust_momentum >= 0 && !ddm))
+    {
+      free(drag);
+      free(ddm);
+      endrun(90003);
+      return -1;
+    }
+  for(int i = 0; i < ng; i++)
+    for(int j = 0; j < 3; j++)
+      {
+        if(drag)
+          drag[3 * (size_t) i + j] = SF64(i, IntLay.s_drag_accel)[j];
+        if(ddm)
+          ddm[3 * (size_t) i + j] = PF64(i, IntLay.p_delta_dust_momentum)[j];
+      }
+  int rc = chk(ghip_kick_set_fields(Ctx, drag, ddm, NULL), "ghip_kick_set_fields");
+  free(drag);
+  free(ddm);
+  return rc;
+}
+
+/* after the kick and the download: DragAccel back into the gas records, the bound per-bin sums moved
+ * where a bin changed (timestep.c:183-210, FirstActiveParticle order; binold[i] from before the kick) */
+static int integration_end(const short *binold)
+{
+  if(!integration_bound())
+    return 0;
+  if(IntLay.s_drag_accel >= 0 && NTask == 1 && N_gas > 0)
+    {
+      double *drag = (double *) malloc((size_t) 3 * N_gas * 8);
+      if(!drag)
+        {
+          endrun(90003);
+          return -1;
+        }
+      if(chk(ghip_kick_get_drag_accel(Ctx, drag), "ghip_kick_get_drag_accel"))
+        {
+          free(drag);
+          return -1;
+        }
+      for(int i = 0; i < N_gas; i++)
+        for(int j = 0; j < 3; j++)
+          SF64(i, IntLay.s_drag_accel)[j] = drag[3 * (size_t) i + j];
+      free(drag);
+    }
+  const int sfr = IntLay.sfr > 0 && BinSfr && IntLay.s_sfr >= 0;
+  const int bh = Cfg.black_holes && Cfg.dust && BinBhMass && BinBhDynMass && BinBhMdot &&
+                 BhLay.p_dust_mass >= 0 && IntLay.p_total_mass >= 0;
+  if(!binold || (!sfr && !bh))
+    return 0;
+  for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
+    {
+      const int bin = p_timebin(i), b0 = binold[i];
+      if(bin == b0)
+        continue;
+      const int ty = p_type(i);
+      if(ty == 0 && sfr)
+        {
+          BinSfr[b0] -= *SF64(i, IntLay.s_sfr);
+          BinSfr[bin] += *SF64(i, IntLay.s_sfr);
+        }
+      if(ty == 5 && bh)
+        {
+          BinBhMass[b0] -= *PF64(i, BhLay.p_dust_mass);
+          BinBhDynMass[b0] -= *PF64(i, IntLay.p_total_mass);
+          BinBhMdot[b0] -= *PF64(i, Lay.p_mass);
+          BinBhMass[bin] += *PF64(i, BhLay.p_dust_mass);
+          BinBhDynMass[bin] += *PF64(i, IntLay.p_total_mass);
+          BinBhMdot[bin] += *PF64(i, Lay.p_mass);
+        }
+    }
+  return 0;
+}
+
 /* timestep.c:1125-1224: the per-type sums come from the device (ghip_velocity_moments replaces the
  * particle loop and the MPI_Allreduce of a single-rank run), the rest is the reference's host math */
 void find_dt_displacement_constraint(double hfac)
@@ -1363,6 +1524,21 @@ void find_dt_displacement_constraint(double hfac)
   long long count_sum[6];
   if(chk(ghip_velocity_moments(Ctx, v_sum, min_mass, count_sum), "ghip_velocity_moments"))
     return;
+  if(integration_bound() && IntLay.sfr)   /* timestep.c:1160-1172 */
+    {
+      v_sum[0] += v_sum[4];
+      count_sum[0] += count_sum[4];
+      v_sum[4] = v_sum[0];
+      count_sum[4] = count_sum[0];
+      if(Cfg.black_holes)
+        {
+          v_sum[0] += v_sum[5];
+          count_sum[0] += count_sum[5];
+          v_sum[5] = v_sum[0];
+          count_sum[5] = count_sum[0];
+          min_mass[5] = min_mass[0];
+        }
+    }
   for(int type = 0; type < 6; type++)
     if(count_sum[type] > 0)
       {
@@ -1373,6 +1549,9 @@ void find_dt_displacement_constraint(double hfac)
         else
           dmean = pow(min_mass[type] / ((All.Omega0 - All.OmegaBaryon) * 3 * All.Hubble * All.Hubble /
                                         (8 * M_PI * All.G)),
+                      1.0 / 3);
+        if(integration_bound() && Cfg.black_holes && type == 5)   /* timestep.c:1190-1194 */
+          dmean = pow(min_mass[type] / (All.OmegaBaryon * 3 * All.Hubble * All.Hubble / (8 * M_PI * All.G)),
                       1.0 / 3);
         dt = All.MaxRMSDisplacementFac * hfac * dmean / sqrt(v_sum[type] / count_sum[type]);
         if(dt < dt_displacement)
@@ -1417,7 +1596,7 @@ static void rebuild_timebin_lists(void)
  * particle loop :142-260 with get_timestep and do_the_kick runs on the device */
 void advance_and_find_timesteps(void)
 {
-  if(need_ctx("advance_and_find_timesteps"))
+  if(need_ctx("advance_and_find_timesteps") || integration_refuse_ranks())
     return;
   gadget_force_flush();   /* (overlap_sph without a hydro_force() call: the kick needs G * GravAccel) */
   if(All.TypeOfTimestepCriterion != 0)
@@ -1473,17 +1652,36 @@ void advance_and_find_timesteps(void)
   k.logTimeMax = KickLogMax;
   k.GravKickTable = KickTabGrav;
   k.HydroKickTable = KickTabHydro;
+  if(integration_begin())
+    return;
+  short *binold = NULL;   /* (the bins before the kick, for the per-bin sums) */
+  if(integration_bound())
+    {
+      binold = (short *) malloc(((size_t) NumPart + 1) * sizeof(short));
+      if(!binold)
+        {
+          endrun(90003);
+          return;
+        }
+      for(int i = 0; i < NumPart; i++)
+        binold[i] = (short) p_timebin(i);
+    }
   long long cnt[32], sph[32];
   int rc = ghip_advance_timesteps(Ctx, &k, cnt, sph);
   if(rc == GHIP_ETIMESTEP)
     {
+      free(binold);
       endrun(ghip_timestep_endrun_code(Ctx)); /* the reference's own code: 888, 818, 112313 */
       return;
     }
-  if(chk(rc, "ghip_advance_timesteps"))
-    return;
-  if(chk(ghip_download_aos_kick(Ctx, records_p(), records_s(), &Lay), "ghip_download_aos_kick"))
-    return;
+  if(chk(rc, "ghip_advance_timesteps") ||
+     chk(ghip_download_aos_kick(Ctx, records_p(), records_s(), &Lay), "ghip_download_aos_kick") ||
+     integration_end(binold))
+    {
+      free(binold);
+      return;
+    }
+  free(binold);
   rebuild_timebin_lists();
 }
 

@@ -91,6 +91,15 @@ class DustLayout(C.Structure):
         "a_unit_velocity")]
 
 
+class IntegrationLayout(C.Structure):
+    """struct gadget_force_integration_layout: the shipped bundle's integrator switches and the byte
+    offsets of the members it touches (-1: absent)"""
+    _fields_ = [(k, C.c_int) for k in (
+        "dust_timestep", "accretion_radius", "virtual_particles", "sfr", "p_new_density", "p_total_mass",
+        "p_delta_dust_momentum", "s_sfr", "s_drag_accel", "a_outer_boundary", "a_acc_dt_black_hole",
+        "a_feedback_velocity", "a_unit_velocity")]
+
+
 class TopNode(C.Structure):
     """struct topnode_data, allvars.h:437-447"""
     _fields_ = [("Size", C.c_ulonglong), ("StartKey", C.c_ulonglong), ("Count", C.c_longlong),
@@ -146,7 +155,7 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "N_dust_swallowed", "TopNodes", "NTopnodes", "NTopleaves", "DomainStartList",
            "DomainEndList", "gadget_force_unique_id", "gadget_force_connect",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
-           "gadget_force_bind_dust", "dust_density", "dust_drag"]
+           "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration"]
 
 _LIB = None
 
@@ -197,6 +206,8 @@ def lib():
         L.gadget_force_bind_dust.restype = None
         L.dust_density.restype = None
         L.dust_drag.restype = None
+        L.gadget_force_bind_integration.argtypes = [C.c_void_p] * 6
+        L.gadget_force_bind_integration.restype = None
         _LIB = L
     return _LIB
 
@@ -258,6 +269,22 @@ class Host:
         self._dust = (host_all, lay)            # keep alive
         self.L.gadget_force_bind_dust(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p))
 
+    def bind_integration(self, host_all, lay, bin_sfr=None, bin_bh_mass=None, bin_bh_dynmass=None,
+                         bin_bh_mdot=None):
+        """gadget_force_bind_integration: `host_all` as for bind_dust, `lay` an IntegrationLayout, the
+        per-bin sums float64 arrays of TIMEBINS entries that the kick keeps (None: not kept); None
+        unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_integration(None, None, None, None, None, None)
+            self._integ = None
+            return
+        sums = [None if a is None else a for a in (bin_sfr, bin_bh_mass, bin_bh_dynmass, bin_bh_mdot)]
+        for a in sums:
+            assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous)
+        self._integ = (host_all, lay, sums)     # keep alive
+        self.L.gadget_force_bind_integration(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p),
+                                             *[None if a is None else C.c_void_p(a.ctypes.data) for a in sums])
+
     def set_allgather(self, allgather):
         """the host's all-gather for more than one rank: allgather(send: bytes) -> bytes of all ranks"""
         def cb(_user, send, nbytes, recv):
@@ -296,6 +323,7 @@ class Host:
         self.L.gadget_force_bind_all(None, None)
         self.L.gadget_force_bind_records(None, None, None, None)
         self.L.gadget_force_bind_dust(None, None)
+        self.L.gadget_force_bind_integration(None, None, None, None, None, None)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)
         self._seti("ThisTask", 0)
         self._seti("NTask", 1)

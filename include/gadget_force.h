@@ -420,6 +420,33 @@ void gadget_force_bind_dust(void *host_All, const struct gadget_force_dust_layou
 void dust_density(void);
 void dust_drag(void);
 
+/* The integrator of the shipped flag bundle (-DDUST_TIMESTEP -DACCRETION_RADIUS -DVIRTUAL -DSFR with
+ * the configuration's dust / black_holes): once bound, advance_and_find_timesteps() applies the type
+ * rules of get_timestep / do_the_kick (ghip_set_integration_flags, include/ghip.h), keeps the bound
+ * per-bin sums as timestep.c:183-210 does -- incrementally, in FirstActiveParticle order, where a
+ * particle's bin changed -- and find_dt_displacement_constraint() merges types 0/4/5
+ * (timestep.c:1160-1172, 1190-1194).  Byte offsets, -1 = absent:
+ *   P[]     NewDensity, Total_Mass, DeltaDustMomentum[3]   (allvars.h:1201-1222; Dust_Mass comes from
+ *           the bh table of gadget_force_bind_records)
+ *   SphP[]  Sfr, da.DragAccel[3]                          (allvars.h:1435, 1514)
+ *   All     OuterBoundary, AccDtBlackHole, FeedBackVelocity, UnitVelocity_in_cm_per_s, read from
+ *           `host_All` (All.SMBHmass, InnerBoundary and SinkBoundary come from the library's `All`)
+ * DragAccel is read before the kick and written back (zero for the kicked gas); the gas's
+ * DeltaDustMomentum is read.  NewDensity is not (the kick takes dt_ff = 1 whatever it holds).  These three are kept on a single GPU: with NTask > 1 a
+ * table naming any of them calls endrun(90011) (a shipped multi-rank host passes -1: its build never
+ * makes them non-zero).  The sums: TimeBinSfr[] (sfr) and, with black_holes and dust,
+ * TimeBin_BH_mass / _dynamicalmass / _Mdot from Dust_Mass / Total_Mass / Mass; NULL = not kept.
+ * lay == NULL unbinds. */
+struct gadget_force_integration_layout
+{
+  int dust_timestep, accretion_radius, virtual_particles, sfr;   /* flags */
+  int p_new_density, p_total_mass, p_delta_dust_momentum, s_sfr, s_drag_accel;
+  int a_outer_boundary, a_acc_dt_black_hole, a_feedback_velocity, a_unit_velocity;
+};
+void gadget_force_bind_integration(void *host_All, const struct gadget_force_integration_layout *lay,
+                                   double *TimeBinSfr, double *TimeBin_BH_mass,
+                                   double *TimeBin_BH_dynamicalmass, double *TimeBin_BH_Mdot);
+
 /* ---- more than one rank (NTask > 1): the drivers above become collectives ----
  * The host has decomposed the domain (domain_Decomposition, domain.c:100) and every rank holds the
  * particles of its key range in P[0, NumPart).  With NTask > 1 gravity_tree() / density() /

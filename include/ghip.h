@@ -389,6 +389,39 @@ int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p);
 int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p, long long *TimeBinCount,
                            long long *TimeBinCountSph);
 int ghip_timestep_endrun_code(const ghip_ctx *ctx);
+/* ---- the integrator of the shipped flag bundle (-DDUST -DDUST_TIMESTEP -DBLACK_HOLES
+ * -DACCRETION_RADIUS -DVIRTUAL): the type rules of get_timestep, do_the_kick and drift_particle
+ * (timestep.c:364-947, predict.c:129-259), for ghip_advance_timesteps and ghip_drift alike.
+ *   gas     criterion + fac2 DragAccel (timestep.c:673-677); dust_timestep: DeltaDustMomentum /
+ *           Mass / dt joins the acceleration and dt = min(dt, dt_new) (:710-722, nothing when the
+ *           new acceleration is 0); the kick sets DragAccel = 0 (:508); the drift adds
+ *           DragAccel dt_hydrokick to VelPred (predict.c:195-198)
+ *   Type 2  half the gravity step (:725-726), no gravity kick (:410-418; dust_drag has integrated
+ *           the grain's velocity); a kept tree still gets its (zero) kick
+ *   Type 3  step <= min(0.03 OuterBoundary / C UnitVelocity_in_cm_per_s FeedBackVelocity, 1)
+ *           (:887-897, C = 2.9979e10); no kick, no drift (:375-377, predict.c:134-136) -- TimeBin and
+ *           Ti_begstep advance
+ *   Type 5  step <= 0.03 OuterBoundary / 100, and with accretion_radius
+ *           <= AccDtBlackHole (InnerBoundary | SinkBoundary + Hsml / 2)^1.5 / Mass^0.5 (:908-947);
+ *           Hsml is the resident HSML at the sink's index (ghip_sink_density writes it there)
+ * Switches that are 0 take no part; f == NULL restores the minimal flag set (the default kernels).
+ * Works on every kind of context (single, ghip_set_shard, ghip_dd_*). ---- */
+typedef struct
+{
+  int dust, dust_timestep, black_holes, accretion_radius, virtual_particles;
+  double OuterBoundary, AccDtBlackHole, SMBHmass, InnerBoundary, SinkBoundary;
+  double FeedBackVelocity, UnitVelocity_in_cm_per_s;
+} ghip_integration_flags;
+int ghip_set_integration_flags(ghip_ctx *ctx, const ghip_integration_flags *f);
+/* the per-particle inputs of those rules, resident next to the GHIP_F_* fields and zero until set:
+ * gas SphP[].da.DragAccel [ngas][3] (in/out: the kick resets it), gas P[].DeltaDustMomentum
+ * [ngas][3], P[].NewDensity [n] (kept; with VIRTUAL the reference reads it only to divide by an
+ * uninitialised rho, the device takes dt_ff = 1 -- DESIGN 4.6).  NULL = zero.  Values set for one
+ * ngas are refused after ghip_set_counts changes it.  Single-rank contexts only: a non-NULL field
+ * on a sharded or multi-GPU context is GHIP_EINVAL. */
+int ghip_kick_set_fields(ghip_ctx *ctx, const double *drag_accel, const double *gas_dust_momentum,
+                         const double *new_density);
+int ghip_kick_get_drag_accel(ghip_ctx *ctx, double *drag_accel);
 /* the bin populations after the last ghip_advance_timesteps, recounted over all particles
  * (reconstruct_timebins, predict.c:14-127); synchronises */
 int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long long *TimeBinCountSph);
