@@ -922,6 +922,7 @@ class ForcePath:
 # ---- multi-GPU module-level helpers ----
 DD_MIGRATE, DD_GRAVITY, DD_DENSITY, DD_HYDRO = 1, 2, 3, 4
 DD_SINK_DENSITY, DD_BH_EVALUATE, DD_BH_SWALLOW, DD_PM = 5, 6, 7, 8
+DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 
 
 class DdSinkArgs(C.Structure):
@@ -959,6 +960,38 @@ def dd_sink_args(sinks, sink_ids=None, dens=None, ngb_factor=1.0, bh=None, hsml=
     A.bh_gasvel, A.bh_mdot, A.bh_density_in = vp(a["gasvel"]), vp(a["mdot"]), vp(a["bh_density_in"])
     A.sink_bh_mass, A.acc_mass, A.acc_bhmass = vp(a["bh_mass"]), vp(a["acc_mass"]), vp(a["acc_bhmass"])
     A.acc_dustmass, A.acc_momentum, A.counts = vp(a["acc_dustmass"]), vp(a["acc_momentum"]), vp(a["counts"])
+    return A, a
+
+
+class DdDustArgs(C.Structure):
+    """ghip_dd_dust_args (include/ghip.h): the dust passes on a multi-GPU shard"""
+    _fields_ = [("p", C.POINTER(DustParams)), ("ndust", C.c_int), ("dust_idx", C.c_void_p),
+                ("particle_density", C.c_void_p), ("dust_density", C.c_void_p), ("dust_entropy", C.c_void_p),
+                ("dust_gasvel", C.c_void_p), ("dust_radius", C.c_void_p), ("particle_velocity", C.c_void_p),
+                ("delta_momentum", C.c_void_p), ("delta_energy", C.c_void_p), ("vcoll", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
+def dd_dust_args(params, dust, particle_density=None, dust_density=None, dust_entropy=None, dust_gasvel=None,
+                 dust_radius=None, particle_velocity=None, vcoll=None):
+    """(args, arrays) for GHIP_DD_DUST_DENSITY (params, dust) or GHIP_DD_DUST_DRAG (all inputs): a filled
+    DdDustArgs and the dict of numpy arrays it points into -- inputs copied, outputs allocated
+    (particle_density, particle_velocity, delta_momentum, delta_energy, vcoll, counts [4]); keep `arrays`
+    alive until the operation has finished."""
+    nd = len(dust)
+    f64 = lambda v, shape: np.zeros(shape) if v is None else \
+        np.ascontiguousarray(v, np.float64).reshape(shape).copy()
+    a = dict(dust_idx=np.ascontiguousarray(dust, np.int32), particle_density=f64(particle_density, nd),
+             dust_density=f64(dust_density, nd), dust_entropy=f64(dust_entropy, nd),
+             dust_gasvel=f64(dust_gasvel, (nd, 3)), dust_radius=f64(dust_radius, nd),
+             particle_velocity=f64(particle_velocity, (nd, 3)), delta_momentum=np.zeros((nd, 3)),
+             delta_energy=np.zeros(nd), vcoll=f64(vcoll, nd), counts=np.zeros(4, np.int64), _params=params)
+    A = DdDustArgs()
+    A.p = C.pointer(params)
+    A.ndust = nd
+    for k in ("dust_idx", "particle_density", "dust_density", "dust_entropy", "dust_gasvel", "dust_radius",
+              "particle_velocity", "delta_momentum", "delta_energy", "vcoll", "counts"):
+        setattr(A, k, a[k].ctypes.data)
     return A, a
 
 

@@ -450,6 +450,7 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
     {
       ctx->gt.built = false;
       ctx->st.built = false;
+      ctx->dd.geom_kept = false;
       ctx->nactive = -1;
       ctx->lists_dirty = ctx->gas_list_dirty = true;
     }
@@ -534,6 +535,7 @@ extern "C" int ghip_set_field(ghip_ctx *ctx, int field, const void *host)
     {
       ctx->gt.built = false;
       ctx->st.built = false;
+      ctx->dd.geom_kept = false;
     }
   if(field == GHIP_F_TYPE)
     GCHK(ghip_check_gas_types(ctx));
@@ -804,6 +806,7 @@ extern "C" int ghip_upload_aos(ghip_ctx *ctx, const void *Pp, const void *Sp, co
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   ctx->gt.built = false;
   ctx->st.built = false;
+  ctx->dd.geom_kept = false;
   ctx->gas_wait_upload = false;
   ctx->gas_mixed = lay->p_type >= 0 && *reinterpret_cast<volatile int *>(ghip_gas_mixed_word(ctx)) != 0;
   ctx->gas_list_dirty = true;
@@ -829,6 +832,7 @@ extern "C" int ghip_upload_aos_particles(ghip_ctx *ctx, const void *Pp, const gh
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   ctx->gt.built = false;
   ctx->st.built = false;
+  ctx->dd.geom_kept = false;
   ctx->gas_wait_upload = ngas > 0;   // (whatever joins in between must leave the gas tree deferred)
   ctx->gas_mixed = lay->p_type >= 0 && *reinterpret_cast<volatile int *>(ghip_gas_mixed_word(ctx)) != 0;
   ctx->gas_list_dirty = true;

@@ -44,6 +44,8 @@ int ghip_dd_sink_begin(ghip_ctx *ctx, int op);
 int ghip_dd_sink_step(ghip_ctx *ctx);
 int ghip_dd_pm_begin(ghip_ctx *ctx);   // ghip_pm.hip
 int ghip_dd_pm_step(ghip_ctx *ctx);
+int ghip_dd_dust_begin(ghip_ctx *ctx, int op);   // ghip_dust.hip
+int ghip_dd_dust_step(ghip_ctx *ctx);
 extern "C" int ghip_dd_exchange(ghip_ctx *ctx);
 
 #define DD_OP_MIGRATE 1
@@ -73,6 +75,7 @@ extern "C" int ghip_dd_init(ghip_ctx *ctx, int rank, int nranks)
   D.x.kind = 0;
   ctx->gt.built = false;
   ctx->st.built = false;
+  ctx->dd.geom_kept = false;
   ctx->shard_rank = 0;   // (the replicated-source sharding of ghip_set_shard is a different mode)
   ctx->shard_n = 1;
   return ghip_dd_set_splits(ctx, D.splits);
@@ -93,6 +96,7 @@ extern "C" int ghip_dd_set_domain(ghip_ctx *ctx, const double corner[3], const d
     ctx->soft[j] = soft[j];
   ctx->gt.built = false;
   ctx->st.built = false;
+  ctx->dd.geom_kept = false;
   return GHIP_OK;
 }
 
@@ -1074,6 +1078,199 @@ __global__ void k_ghost_growth(int nt, const int *__restrict__ tgt, const int *_
 }
 
 // ---------------------------------------------------------------------------------------------
+// the dust passes: which shards can a grain's sphere reach? (ghip_dust.hip runs the passes)
+// ---------------------------------------------------------------------------------------------
+// the local Type 0 and Type 2 particles (the candidates of both passes) in curve order, as indices of
+// the merged gravity tree
+__global__ void k_flag_dust_partners(int nt, const int *__restrict__ perm, int n, const int *__restrict__ type,
+                                     int *__restrict__ flags)
+{
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= nt)
+    return;
+  const int i = perm[s];
+  flags[s] = (i < n && (type[i] == 0 || type[i] == 2)) ? 1 : 0;
+}
+
+// this shard's group table over its local Type 0 / Type 2 particles; the all-gather is left pending
+int ghip_dd_dust_groups(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int nt = ctx->gt.n;   // local particles + imported elements of the merged tree
+  int nsel = 0;
+  GCHK(ghip_ensure(ctx, D.gas_tgt, (size_t) (nt > 0 ? nt : 1) * 4));
+  if(nt > 0 && ctx->n > 0)
+    {
+      GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
+      hipcub::CountingInputIterator<int> seq(0);
+      k_flag_dust_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n,
+                                                          P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->dflags));
+      HIPCHK(hipGetLastError());
+      int *dnum = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 33);
+      size_t tb = 0;
+      HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, seq, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
+      GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
+      HIPCHK(hipcub::DeviceSelect::Flagged(ctx->cubtmp.p, tb, seq, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum,
+                                           nt, st));
+      HIPCHK(hipMemcpyAsync(&nsel, dnum, 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+    }
+  // (the groups carry the least OldAcc, which the sphere test below does not read)
+  GCHK(build_groups(ctx, false, P<int>(D.gas_tgt), nsel));
+  ghip_dd_set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+  return 1;
+}
+
+// squared distance between the box (c +- e) and the group's box, nearest image when periodic
+__device__ __forceinline__ double d_group_box_dist2(const DDGroup &G, double cx, double cy, double cz, double ex,
+                                                    double ey, double ez, const GhostK &K)
+{
+  double d0 = cx - G.cx, d1 = cy - G.cy, d2 = cz - G.cz;
+  if(K.periodic)
+    {
+      d0 = d_nearest(d0, K.boxsize, K.boxhalf);
+      d1 = d_nearest(d1, K.boxsize, K.boxhalf);
+      d2 = d_nearest(d2, K.boxsize, K.boxhalf);
+    }
+  d0 = fabs(d0) - G.ex - ex;
+  d1 = fabs(d1) - G.ey - ey;
+  d2 = fabs(d2) - G.ez - ez;
+  d0 = d0 > 0 ? d0 : 0;
+  d1 = d1 > 0 ? d1 : 0;
+  d2 = d2 > 0 ? d2 : 0;
+  return d0 * d0 + d1 * d1 + d2 * d2;
+}
+
+// Can a sphere of radius h inside the box (c +- e) reach a particle of the group?  Every particle of
+// the group lies in its box, and a neighbour of a grain is closer than h (u = r / h < 1), so a group
+// farther than h from every point of the sphere's box holds none.  (1e-9: rounding slack.)
+__device__ __forceinline__ bool d_sphere_reaches(const DDGroup &G, double cx, double cy, double cz, double ex,
+                                                 double ey, double ez, double h, const GhostK &K)
+{
+  if(G.ex < 0)
+    return false;
+  const double R = h * (1.0 + 1.0e-9);
+  return d_group_box_dist2(G, cx, cy, cz, ex, ey, ez, K) < R * R;
+}
+
+// One wavefront per (chunk of 64 grains in gravity-tree order, destination rank), as k_ghost_select:
+// the chunk's box (padded by its largest h) against the rank's 64 super-groups, then each lane's own
+// sphere against the groups of the near super-groups.  mask [n] (by local particle index) must be
+// zero on entry for the grains; the ranks' bits are OR-ed in.
+__global__ void __launch_bounds__(64)
+k_dust_select(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n,
+              const double *__restrict__ pos, const double *__restrict__ hsml,
+              const DDGroup *__restrict__ groups, GhostK K, unsigned long long *__restrict__ mask)
+{
+  __shared__ DDGroup sh[DD_NSUB];
+  const int lane = threadIdx.x;
+  const int ndst = K.nranks - 1;
+  const int chunk = blockIdx.x / ndst;
+  int b = blockIdx.x - chunk * ndst;
+  if(b >= K.me)
+    b++;
+  const int t = chunk * 64 + lane;
+  const bool valid = t < nd;
+  int i = 0;
+  double px = 0, py = 0, pz = 0, h = 0;
+  if(valid)
+    {
+      i = idx[ord[t]];
+      px = pos[i];
+      py = pos[(size_t) n + i];
+      pz = pos[2 * (size_t) n + i];
+      h = hsml[i];
+    }
+  const double rx = __shfl(px, 0, 64), ry = __shfl(py, 0, 64), rz = __shfl(pz, 0, 64);
+  double ox = valid ? px - rx : 0, oy = valid ? py - ry : 0, oz = valid ? pz - rz : 0;
+  if(K.periodic)
+    {
+      ox = d_nearest(ox, K.boxsize, K.boxhalf);
+      oy = d_nearest(oy, K.boxsize, K.boxhalf);
+      oz = d_nearest(oz, K.boxsize, K.boxhalf);
+    }
+  double lo[3] = {ox, oy, oz}, hi[3] = {ox, oy, oz}, hm = h;
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      for(int k = 0; k < 3; k++)
+        {
+          double o = __shfl_xor(lo[k], off, 64);
+          lo[k] = o < lo[k] ? o : lo[k];
+          o = __shfl_xor(hi[k], off, 64);
+          hi[k] = o > hi[k] ? o : hi[k];
+        }
+      const double o = __shfl_xor(hm, off, 64);
+      hm = o > hm ? o : hm;
+    }
+  const double cx = rx + 0.5 * (lo[0] + hi[0]), cy = ry + 0.5 * (lo[1] + hi[1]),
+               cz = rz + 0.5 * (lo[2] + hi[2]);
+  const double ex = 0.5 * (hi[0] - lo[0]) * (1 + 1e-12) + 1e-14, ey = 0.5 * (hi[1] - lo[1]) * (1 + 1e-12) + 1e-14,
+               ez = 0.5 * (hi[2] - lo[2]) * (1 + 1e-12) + 1e-14;
+  const DDGroup *tab = groups + (size_t) b * DD_STRIDE;
+  unsigned long long sm = __ballot(d_sphere_reaches(tab[lane], cx, cy, cz, ex, ey, ez, hm, K));
+  bool need = false;
+  while(sm)
+    {
+      const int sg = __builtin_ctzll(sm);
+      sm &= sm - 1;
+      __syncthreads();
+      bool near = false;
+      if(lane < DD_NSUB)
+        {
+          const DDGroup G = tab[DD_NSUPER + sg * DD_NSUB + lane];
+          sh[lane] = G;
+          near = d_sphere_reaches(G, cx, cy, cz, ex, ey, ez, hm, K);
+        }
+      unsigned long long qm = __ballot(near);
+      __syncthreads();
+      while(qm)
+        {
+          const int q = __builtin_ctzll(qm);
+          qm &= qm - 1;
+          if(valid && !need && d_sphere_reaches(sh[q], px, py, pz, 0, 0, 0, h, K))
+            need = true;
+        }
+      if(__ballot(valid && !need) == 0)
+        break;   // every grain of the chunk goes there already
+    }
+  if(need)
+    atomicOr(mask + i, 1ULL << b);
+}
+
+// after the all-gather of the group tables: the destinations of this shard's nd grains (ord: list slots
+// in tree order, idx: local indices, both on the device), the per-destination lists of their local
+// indices in ascending order (D.du_list, D.du_scount / du_soff), the total
+int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
+                        int periodic, int *total)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int P_ = D.nranks, n = ctx->n;
+  GCHK(check_group_status(ctx, what));
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    D.du_scount[r] = D.du_soff[r] = 0;
+  *total = 0;
+  GCHK(ghip_ensure(ctx, D.du_list, 4));
+  if(nd == 0 || P_ < 2)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, D.du_mask, (size_t) n * 8));
+  HIPCHK(hipMemsetAsync(D.du_mask.p, 0, (size_t) n * 8, st));
+  GhostK K;
+  K.boxsize = boxsize;
+  K.boxhalf = 0.5 * boxsize;
+  K.periodic = periodic;
+  K.margin = 1.0;
+  K.nranks = P_;
+  K.me = D.rank;
+  k_dust_select<<<cdiv(nd, 64) * (P_ - 1), 64, 0, st>>>(nd, ord, idx, n, P<double>(ctx->f[GHIP_F_POS]),
+                                                       P<double>(ctx->f[GHIP_F_HSML]), P<DDGroup>(D.grp_all), K,
+                                                       P<unsigned long long>(D.du_mask));
+  HIPCHK(hipGetLastError());
+  return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
+}
+
+// ---------------------------------------------------------------------------------------------
 // the state machine: compute until the next exchange, exchange, continue
 // ---------------------------------------------------------------------------------------------
 #define set_allgather ghip_dd_set_allgather
@@ -1366,7 +1563,8 @@ static int density_step(ghip_ctx *ctx)
 // ---- migration --------------------------------------------------------------------------------
 // domain_exchange (domain.c:665-1060): after a drift some particles lie outside their shard's key
 // range; each moves to the shard that owns its key, with every resident field.  One record per
-// particle: 8-byte slots, the fields in enum order (ints widened), slot MIG_SLOTS-1 = 1 for gas.
+// particle: 8-byte slots, the fields in enum order (ints widened), then the shard's DragHeating when it
+// holds one (ghip_dust.hip), slot MIG_SLOTS-1 = 1 for gas.
 #define MIG_SLOTS 40
 struct MigRec
 {
@@ -1380,7 +1578,7 @@ struct MigField
 struct MigTable
 {
   int nf;
-  MigField f[GHIP_F_COUNT];
+  MigField f[GHIP_F_COUNT + 1];   // the fields, + DragHeating
 };
 struct MigSplits
 {
@@ -1391,7 +1589,8 @@ struct MigSplits
 
 void ghip_field_info(int f, int *gas, int *ncomp, int *isint);   // api.hip
 
-static MigTable mig_table(DevBuf *bufs)
+// heat: the per-gas DragHeating, or nullptr when the shard holds none
+static MigTable mig_table(DevBuf *bufs, DevBuf *heat)
 {
   MigTable T;
   T.nf = GHIP_F_COUNT;
@@ -1403,7 +1602,16 @@ static MigTable mig_table(DevBuf *bufs)
       T.f[f].slot = slot;
       slot += T.f[f].ncomp;
     }
-  return T;   // slot <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
+  if(heat)
+    {
+      MigField &F = T.f[T.nf++];
+      F.p = heat->p;
+      F.ncomp = 1;
+      F.isint = 0;
+      F.gas = 1;
+      F.slot = slot;
+    }
+  return T;   // slot + 1 <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
 }
 
 __global__ void k_mig_dest(int n, const double *__restrict__ x, const double *__restrict__ y,
@@ -1455,6 +1663,8 @@ __global__ void k_mig_pack(int nrec, const int *__restrict__ list, int n, int ng
           r.s[F.slot + c] = v;
         }
     }
+  if(T.nf == GHIP_F_COUNT)   // no DragHeating here: its slot travels as zero
+    r.s[T.f[T.nf - 1].slot + T.f[T.nf - 1].ncomp] = 0;
   r.s[MIG_SLOTS - 1] = isgas ? 1ULL : 0ULL;
 }
 
@@ -1550,6 +1760,9 @@ static int migrate_step(ghip_ctx *ctx)
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
   const int P_ = D.nranks, n = ctx->n, ng = ctx->ngas;
+  // (a DragHeating that no longer matches the gas count -- ghip_set_counts since -- is not carried)
+  DevBuf *heat = (ctx->dust_heat.p && ctx->dust_heat.cap >= (size_t) (ng > 0 ? ng : 1) * 8) ? &ctx->dust_heat
+                                                                                           : nullptr;
   if(D.phase == 0)
     {
       GHIP_JOIN(ctx);
@@ -1578,7 +1791,7 @@ static int migrate_step(ghip_ctx *ctx)
       if(total > 0)
         {
           k_mig_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.mig_list), n, ng,
-                                                      mig_table(ctx->f), P<MigRec>(D.mig_send));
+                                                      mig_table(ctx->f, heat), P<MigRec>(D.mig_send));
           HIPCHK(hipGetLastError());
         }
       D.mig_out = total;
@@ -1628,7 +1841,9 @@ static int migrate_step(ghip_ctx *ctx)
           if(D.fshadow[f].cap != before)
             HIPCHK(hipMemsetAsync(D.fshadow[f].p, 0, D.fshadow[f].cap, st));
         }
-      const MigTable A = mig_table(ctx->f), Bn = mig_table(D.fshadow);
+      if(heat)
+        GCHK(ghip_ensure(ctx, D.heat_shadow, (size_t) (ngn > 0 ? ngn : 1) * 8));
+      const MigTable A = mig_table(ctx->f, heat), Bn = mig_table(D.fshadow, heat ? &D.heat_shadow : nullptr);
       if(n > 0)
         k_mig_move_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), ro, C,
                                                      A, Bn);
@@ -1642,10 +1857,17 @@ static int migrate_step(ghip_ctx *ctx)
           ctx->f[f] = D.fshadow[f];
           D.fshadow[f] = t;
         }
+      if(heat)
+        {
+          DevBuf t = ctx->dust_heat;
+          ctx->dust_heat = D.heat_shadow;
+          D.heat_shadow = t;
+        }
       ctx->n = nn;
       ctx->ngas = ngn;
       ctx->gt.built = false;
       ctx->st.built = false;
+      D.geom_kept = false;
       ctx->nactive = -1;
       ctx->lists_dirty = ctx->gas_list_dirty = true;
       ctx->gas_types_unknown = true;   // (an arrival may be a converted particle of its old gas block)
@@ -1693,6 +1915,11 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
       D.pm = *reinterpret_cast<const ghip_pm_params *>(params);
       GCHK(ghip_dd_pm_begin(ctx));
     }
+  else if(op == GHIP_DD_DUST_DENSITY || op == GHIP_DD_DUST_DRAG)
+    {
+      D.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
+      GCHK(ghip_dd_dust_begin(ctx, op));
+    }
   else if(op == DD_OP_MIGRATE)
     {
       static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
@@ -1703,6 +1930,7 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
           ghip_field_info(f, &gas, &ncomp, &isint);
           slots += ncomp;
         }
+      slots += 1;   // DragHeating, when the shard holds one
       if(slots > MIG_SLOTS - 1)
         return ghip_fail(ctx, GHIP_EINVAL, "migration record too small for %d field slots", slots);
     }
@@ -1728,6 +1956,8 @@ extern "C" int ghip_dd_step(ghip_ctx *ctx)
     return ghip_dd_sink_step(ctx);
   if(D.op == GHIP_DD_PM)
     return ghip_dd_pm_step(ctx);
+  if(D.op == GHIP_DD_DUST_DENSITY || D.op == GHIP_DD_DUST_DRAG)
+    return ghip_dd_dust_step(ctx);
   if(D.op == DD_OP_MIGRATE)
     return migrate_step(ctx);
   if(D.op == DD_OP_GRAVITY)
@@ -1793,7 +2023,9 @@ void ghip_dd_release(ghip_ctx *ctx)
                   &D.src_key, &D.src_lvl, &D.gh_mask, &D.gh_list, &D.gh_send, &D.gh_recv, &D.gsx,
                   &D.gsy, &D.gsz, &D.gsm, &D.gsh, &D.h0, &D.gas_tgt, &D.mig_mask, &D.mig_list,
                   &D.mig_send, &D.mig_recv, &D.mig_scan, &D.gas_src, &D.sk_send, &D.sk_all, &D.sk_part,
-                  &D.sk_parts, &D.sk_work, &D.pm_all, &D.segkey, &D.segowner, &D.ownlo, &D.ownhi};
+                  &D.sk_parts, &D.sk_work, &D.pm_all, &D.segkey, &D.segowner, &D.ownlo, &D.ownhi,
+                  &D.du_mask, &D.du_slot, &D.du_list, &D.du_send, &D.du_recv, &D.du_part, &D.du_back,
+                  &D.heat_shadow};
   for(DevBuf *b : bs)
     {
       if(b->p)

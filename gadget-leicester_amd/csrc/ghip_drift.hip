@@ -183,6 +183,7 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
   HIPCHK(hipGetLastError());
   ctx->gt.built = false;  // positions moved: the trees are stale
   ctx->st.built = false;
+  ctx->dd.geom_kept = false;
   if(ctx->async)
     return GHIP_OK;   // (a particle ahead of time1 is reported by the next call that synchronises)
   int herr = 0;

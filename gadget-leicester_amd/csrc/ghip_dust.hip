@@ -188,6 +188,43 @@ __device__ __forceinline__ void d_dust_walk_gas(double px, double py, double pz,
     }
 }
 
+// Where a grain of a launch comes from: this shard's list (a local particle: position and h from the
+// resident fields) ...
+struct DustGrainLocal
+{
+  const int *idx;              // list slot -> local particle index
+  const double *pos, *hsml;
+  int n;
+  const double *wi;            // the per-grain value by particle (MASS), or
+  const double *wa;            // ... by list slot (the DUST_Density plane)
+  __device__ __forceinline__ void get(int a, double &x, double &y, double &z, double &h, double &w) const
+  {
+    const int i = idx[a];
+    x = pos[i];
+    y = pos[(size_t) n + i];
+    z = pos[2 * (size_t) n + i];
+    h = hsml[i];
+    w = wi ? wi[i] : wa[a];
+  }
+};
+
+// ... or a record another shard sent: {x, y, z, h, w, ...}, `stride` doubles each (w: the grain's mass in
+// the density pass, its DUST_Density in the drag pass)
+struct DustGrainRec
+{
+  const double *rec;
+  int stride;
+  __device__ __forceinline__ void get(int a, double &x, double &y, double &z, double &h, double &w) const
+  {
+    const double *r = rec + (size_t) a * stride;
+    x = r[0];
+    y = r[1];
+    z = r[2];
+    h = r[3];
+    w = r[4];
+  }
+};
+
 // sort key of grain a: its place in the gravity tree
 __global__ void k_dust_order_keys(int nd, const int *__restrict__ idx, const int *__restrict__ iperm,
                                   unsigned int *__restrict__ key, int *__restrict__ slot)
@@ -202,10 +239,12 @@ __global__ void k_dust_order_keys(int nd, const int *__restrict__ idx, const int
 // dust_evaluate_density (dust.c:748-887): the Type-2 neighbours with Mass > 0 within the grain's h,
 // the grain itself included, each weighted with the GRAIN's own mass (dust.c:849: `dustmass` is
 // PPP[target].Mass -- a reference quirk kept as it is: the result is m_i * sum_j W_ij, not a density of
-// the neighbours' mass)
+// the neighbours' mass; an imported grain brings its mass in the record).  Candidates are this context's
+// own particles: imported elements of a shard's merged tree (perm >= n) are skipped.  ord: the launch
+// order of the grains (nullptr: as given)
+template <class G>
 __global__ void __launch_bounds__(64)
-k_dust_density(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n,
-               const double *__restrict__ pos, const double *__restrict__ hsml,
+k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__restrict__ pos,
                const double *__restrict__ mass, const int *__restrict__ type, int nelem,
                const int4 *__restrict__ lk, const double4 *__restrict__ cl, const int *__restrict__ perm,
                DustBox b, double *__restrict__ out)
@@ -213,9 +252,9 @@ k_dust_density(int nd, const int *__restrict__ ord, const int *__restrict__ idx,
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= nd)
     return;
-  const int a = ord[t], i = idx[a];
-  const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i];
-  const double h = hsml[i], mi = mass[i];
+  const int a = ord ? ord[t] : t;
+  double px, py, pz, h, mi;
+  g.get(a, px, py, pz, h, mi);
   double rho = 0;
   d_dust_walk_grav(px, py, pz, h, nelem, lk, cl, b, [&](int p) {
     const int j = perm[p];
@@ -311,27 +350,28 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
 }
 
 // the gas neighbours that dust_evaluate_select updates (dust.c:962-1000): Type 0, Mass > 0, u < 1,
-// the gas particle's own dt > 0 and the grain's DUST_Density > 0.  fill == 0: count them into
-// cnt[a]; fill == 1: write (j << 32 | a, W) from off[a] on
-template <int fill>
+// the gas particle's own dt > 0 and the grain's DUST_Density > 0 -- this context's own gas only (a
+// shard's ghosts, j >= ngas, are skipped).  fill == 0: count them into cnt[a]; fill == 1: write
+// (j << 32 | obase + a, W) from off[a] on.  obase + a is the grain's place in the order in which a gas
+// particle receives the grains.
+template <int fill, class G>
 __global__ void __launch_bounds__(64)
-k_dust_pairs(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n, int ngas,
-             const double *__restrict__ pos, const double *__restrict__ hsml,
-             const double *__restrict__ mass, const int *__restrict__ type,
-             const int *__restrict__ timebin, const double *__restrict__ w, int nelem,
-             const DustSphNode *__restrict__ nodes, const int *__restrict__ perm, DustBox b, long long *__restrict__ cnt,
+k_dust_pairs(int nd, const int *__restrict__ ord, G g, int obase, int n, int ngas,
+             const double *__restrict__ pos, const double *__restrict__ mass, const int *__restrict__ type,
+             const int *__restrict__ timebin, int nelem, const DustSphNode *__restrict__ nodes,
+             const int *__restrict__ perm, DustBox b, long long *__restrict__ cnt,
              const long long *__restrict__ off, unsigned long long *__restrict__ key,
              double *__restrict__ wgt)
 {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= nd)
     return;
-  const int a = ord[t], i = idx[a];
+  const int a = ord ? ord[t] : t;
+  double px, py, pz, h, grho;
+  g.get(a, px, py, pz, h, grho);
   long long c = 0;
-  if(w[(size_t) DP_RHO * nd + a] > 0.)
+  if(grho > 0.)
     {
-      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i];
-      const double h = hsml[i];
       const long long o = fill ? off[a] : 0;
       d_dust_walk_gas(px, py, pz, h, nelem, nodes, b, [&](int p) {
         const int j = perm[p];
@@ -342,7 +382,7 @@ k_dust_pairs(int nd, const int *__restrict__ ord, const int *__restrict__ idx, i
           return;
         if(fill)
           {
-            key[o + c] = ((unsigned long long) j << 32) | (unsigned int) a;
+            key[o + c] = ((unsigned long long) j << 32) | (unsigned int) (obase + a);
             wgt[o + c] = wk;
           }
         c++;
@@ -398,6 +438,82 @@ __global__ void k_dust_apply(long long npairs, const unsigned long long *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// multi-GPU shards: the grain records that travel
+// ---------------------------------------------------------------------------------------------
+#define DUST_REC_DENS 5   // x, y, z, Hsml, Mass
+#define DUST_REC_DRAG 9   // x, y, z, Hsml, DUST_Density, DeltaDustMomentum [3], DeltaDragEnergy
+
+__global__ void k_dust_slots(int nd, const int *__restrict__ idx, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < nd)
+    slot[idx[a]] = a;
+}
+
+// record r of the send lists: local particle list[r], list slot slot[list[r]]; w: the planes (drag)
+template <int K>
+__global__ void k_dust_pack(int nrec, const int *__restrict__ list, const int *__restrict__ slot, int n,
+                            const double *__restrict__ pos, const double *__restrict__ hsml,
+                            const double *__restrict__ mass, int nd, const double *__restrict__ w,
+                            double *__restrict__ out)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r >= nrec)
+    return;
+  const int i = list[r];
+  double *o = out + (size_t) r * K;
+  o[0] = pos[i];
+  o[1] = pos[(size_t) n + i];
+  o[2] = pos[2 * (size_t) n + i];
+  o[3] = hsml[i];
+  if(K == DUST_REC_DENS)
+    o[4] = mass[i];
+  else
+    {
+      const size_t a = (size_t) slot[i], D = (size_t) nd;
+      o[4] = w[DP_RHO * D + a];
+      for(int k = 0; k < 3; k++)
+        o[5 + k] = w[(DP_DMOM + k) * D + a];
+      o[8] = w[DP_DE * D + a];
+    }
+}
+
+// the partial d7 one rank sent back, in the order of this shard's send list for that rank, onto the sums
+__global__ void k_dust_add_parts(int cnt, const int *__restrict__ list, const int *__restrict__ slot,
+                                 const double *__restrict__ part, double *__restrict__ out)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if(k < cnt)
+    out[slot[list[k]]] += part[k];
+}
+
+// the planes k_dust_apply reads, over this shard's grains [0, nd) and the imported ones [nd, nd + nimp)
+__global__ void k_dust_combine(int nd, int nimp, const double *__restrict__ w, const double *__restrict__ rec,
+                               double *__restrict__ cw)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  const int m = nd + nimp;
+  if(a >= m)
+    return;
+  const size_t M = (size_t) m, D = (size_t) nd;
+  if(a < nd)
+    {
+      cw[DP_RHO * M + a] = w[DP_RHO * D + a];
+      for(int k = 0; k < 3; k++)
+        cw[(DP_DMOM + k) * M + a] = w[(DP_DMOM + k) * D + a];
+      cw[DP_DE * M + a] = w[DP_DE * D + a];
+    }
+  else
+    {
+      const double *r = rec + (size_t) (a - nd) * DUST_REC_DRAG;
+      cw[DP_RHO * M + a] = r[4];
+      for(int k = 0; k < 3; k++)
+        cw[(DP_DMOM + k) * M + a] = r[5 + k];
+      cw[DP_DE * M + a] = r[8];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 static DustBox dust_box(const ghip_dust_params *p)
@@ -407,6 +523,21 @@ static DustBox dust_box(const ghip_dust_params *p)
   b.boxhalf = 0.5 * p->BoxSize;
   b.periodic = p->periodic;
   return b;
+}
+
+static DustK dust_k(const ghip_dust_params *p)
+{
+  DustK K;
+  K.b = dust_box(p);
+  K.dt_fac = p->dt_fac;
+  K.dt_fac_gas = p->dt_fac_gas;
+  K.minegy = p->MinEgySpec;
+  K.meanweight = p->MeanWeight;
+  K.ulength = p->UnitLength_in_cm;
+  K.umass = p->UnitMass_in_g;
+  K.udens = p->UnitDensity_in_cgs;
+  K.uvel = p->UnitVelocity_in_cm_per_s;
+  return K;
 }
 
 static int dust_heat_buffer(ghip_ctx *ctx)
@@ -419,25 +550,9 @@ static int dust_heat_buffer(ghip_ctx *ctx)
   return GHIP_OK;
 }
 
-// the checks every entry point makes; the grain list goes to the device, ordered by the gravity tree
-// into dust_ord (slot of the t-th thread)
-static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const int *idx, bool gas,
-                      const char *who)
+// the grain list to the device, ordered by the gravity tree into dust_ord (slot of the t-th thread)
+static int dust_upload_list(ghip_ctx *ctx, int nd, const int *idx, const char *who)
 {
-  if(!p || nd < 0 || (nd > 0 && !idx))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  if(ctx->dd.on && ctx->dd.nranks > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU context (%d ranks): the "
-                     "dust passes are single-rank only (no dust ghost exchange)", who, ctx->dd.nranks);
-  if(ctx->shard_n > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard with %d "
-                     "shards): the dust passes are single-rank only", who, ctx->shard_n);
-  if(nd == 0)
-    return GHIP_OK;
-  if(gas)
-    GCHK(ghip_finish_gas_tree(ctx));
-  if(!ctx->gt.built || (gas && !ctx->st.built))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
   for(int a = 0; a < nd; a++)
     if(idx[a] < 0 || idx[a] >= ctx->n)
       return ghip_fail(ctx, GHIP_EINVAL, "%s: grain index %d out of range", who, idx[a]);
@@ -450,13 +565,162 @@ static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const in
   HIPCHK(hipMemcpyAsync(didx, idx, D * 4, hipMemcpyHostToDevice, st));
   k_dust_order_keys<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(ctx->gt.iperm), dkey, dslot);
   HIPCHK(hipGetLastError());
+  // (sorted positions of a shard's merged tree run up to its local particles + imported elements)
+  const long long nsorted = ctx->gt.n > ctx->n ? ctx->gt.n : ctx->n;
   int end_bit = 1;
-  while(end_bit < 32 && (1LL << end_bit) <= (long long) ctx->n)
+  while(end_bit < 32 && (1LL << end_bit) <= nsorted)
     end_bit++;
   size_t tb = 0;
   HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
   GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
   HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
+  return GHIP_OK;
+}
+
+// the checks every single-rank entry point makes, then the grain list
+static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const int *idx, bool gas,
+                      const char *who)
+{
+  if(!p || nd < 0 || (nd > 0 && !idx))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU context (%d ranks): these entry "
+                     "points are single-rank (shards run GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG)", who,
+                     ctx->dd.nranks);
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard with %d "
+                     "shards): the dust passes are single-rank only", who, ctx->shard_n);
+  if(nd == 0)
+    return GHIP_OK;
+  if(gas)
+    GCHK(ghip_finish_gas_tree(ctx));
+  if(!ctx->gt.built || (gas && !ctx->st.built))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
+  return dust_upload_list(ctx, nd, idx, who);
+}
+
+// the per-grain planes of the drag pass, in list order, to dust_work; returns the planes
+static int dust_upload_planes(ghip_ctx *ctx, int nd, const double *dust_density, const double *dust_entropy,
+                              const double *dust_gasvel, const double *dust_radius,
+                              const double *particle_density, const double *particle_velocity,
+                              const double *vcoll, std::vector<double> &h)
+{
+  const size_t D = (size_t) nd;
+  h.assign((size_t) DUST_NPLANES * D, 0.0);
+  for(size_t a = 0; a < D; a++)
+    {
+      h[DP_RHO * D + a] = dust_density[a];
+      h[DP_ENT * D + a] = dust_entropy[a];
+      h[DP_RAD * D + a] = dust_radius[a];
+      h[DP_D7 * D + a] = particle_density[a];
+      h[DP_VCOLL * D + a] = vcoll[a];
+      for(int k = 0; k < 3; k++)
+        {
+          h[(DP_GV + k) * D + a] = dust_gasvel[3 * a + k];
+          h[(DP_D9 + k) * D + a] = particle_velocity[3 * a + k];
+        }
+    }
+  // dust_work: planes [DUST_NPLANES][nd] | cnt [nd + 1] | off [nd + 1]   (64-bit)
+  GCHK(ghip_ensure(ctx, ctx->dust_work, (DUST_NPLANES * D + 2 * (D + 1)) * 8 + 256));
+  HIPCHK(hipMemcpyAsync(ctx->dust_work.p, h.data(), DUST_NIN * D * 8, hipMemcpyHostToDevice, ctx->stream));
+  return GHIP_OK;
+}
+
+static void dust_run_grains(ghip_ctx *ctx, int nd, const DustK &K)
+{
+  k_dust_grain<<<cdiv(nd, 256), 256, 0, ctx->stream>>>(nd, P<int>(ctx->dust_idx), ctx->n,
+                                                       P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                                       P<double>(ctx->f[GHIP_F_MASS]),
+                                                       P<double>(ctx->f[GHIP_F_GRAVACCEL]),
+                                                       P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K);
+}
+
+// The scatter into this context's gas: count, scan, fill, sort, apply.  Grains [0, nd) are the list's
+// (slots in dust_idx, planes w with stride nd, launched in tree order), [nd, nd + nimp) the imported
+// records rec; cw holds the planes k_dust_apply reads with stride nd + nimp (w itself when nimp = 0).
+// cnt, off: nd + nimp + 1 each.
+static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, int nimp, const double *rec,
+                        const double *cw, long long *dcnt, long long *doff, long long *npairs_out)
+{
+  hipStream_t st = ctx->stream;
+  const int m = nd + nimp;
+  const size_t D = (size_t) nd;
+  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
+  TreeDev &t = ctx->st;
+  const DustSphNode *nodes = reinterpret_cast<const DustSphNode *>(t.mq.p);
+  const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  const int *type = P<int>(ctx->f[GHIP_F_TYPE]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
+  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, nullptr, w + DP_RHO * D};
+  DustGrainRec gr = {rec, DUST_REC_DRAG};
+  HIPCHK(hipMemsetAsync(dcnt, 0, (size_t) (m + 1) * 8, st));
+  if(ctx->ngas > 0 && nd > 0)
+    k_dust_pairs<0><<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, 0, ctx->n, ctx->ngas, pos, mass, type, tbin,
+                                                 t.nelem, nodes, P<int>(t.perm), K.b, dcnt, nullptr, nullptr,
+                                                 nullptr);
+  if(ctx->ngas > 0 && nimp > 0)
+    k_dust_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, nd, ctx->n, ctx->ngas, pos, mass, type,
+                                                   tbin, t.nelem, nodes, P<int>(t.perm), K.b, dcnt + D,
+                                                   nullptr, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, dcnt, doff, m + 1, st));
+  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->dust_cub.p, tb, dcnt, doff, m + 1, st));
+  long long npairs = 0;
+  if(ctx->ngas > 0)
+    HIPCHK(hipMemcpyAsync(&npairs, doff + m, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));   // the pair count sizes the sort
+  *npairs_out = npairs;
+  if(npairs < 0 || npairs > (long long) INT_MAX)
+    return ghip_fail(ctx, GHIP_EDEVICE, "dust_drag: %lld dust-gas pairs", npairs);
+  if(npairs == 0)
+    return GHIP_OK;
+  const size_t np = (size_t) npairs;
+  // dust_pairs: key [np] | key' [np] | W [np] | W' [np]
+  GCHK(ghip_ensure(ctx, ctx->dust_pairs, np * 32 + 256));
+  unsigned long long *k0 = P<unsigned long long>(ctx->dust_pairs), *k1 = k0 + np;
+  double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
+  if(nd > 0)
+    k_dust_pairs<1><<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, 0, ctx->n, ctx->ngas, pos, mass, type, tbin,
+                                                 t.nelem, nodes, P<int>(t.perm), K.b, nullptr, doff, k0, w0);
+  if(nimp > 0)
+    k_dust_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, nd, ctx->n, ctx->ngas, pos, mass, type,
+                                                   tbin, t.nelem, nodes, P<int>(t.perm), K.b, nullptr,
+                                                   doff + D, k0, w0);
+  HIPCHK(hipGetLastError());
+  int end_bit = 33;
+  while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
+    end_bit++;
+  tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
+  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
+  HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
+  k_dust_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, m, cw, ctx->n, mass, tbin,
+                                                  P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_ENTROPY]),
+                                                  P<double>(ctx->dust_heat), K);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// the grain outputs of the drag pass back to the caller's arrays
+static int dust_download_grains(ghip_ctx *ctx, int nd, std::vector<double> &h, double *particle_velocity,
+                                double *delta_momentum, double *delta_energy, double *vcoll)
+{
+  const size_t D = (size_t) nd;
+  const double *dw = P<double>(ctx->dust_work);
+  HIPCHK(hipMemcpyAsync(h.data() + DP_D9 * D, dw + DP_D9 * D, DUST_NOUT * D * 8, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(size_t a = 0; a < D; a++)
+    {
+      for(int k = 0; k < 3; k++)
+        {
+          particle_velocity[3 * a + k] = h[(DP_D9 + k) * D + a];
+          delta_momentum[3 * a + k] = h[(DP_DMOM + k) * D + a];
+        }
+      delta_energy[a] = h[DP_DE * D + a];
+      vcoll[a] = h[DP_VCOLL * D + a];
+    }
   return GHIP_OK;
 }
 
@@ -477,10 +741,11 @@ extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int n
   GCHK(ghip_ensure(ctx, ctx->dust_work, D * 8 + 256));
   double *dout = P<double>(ctx->dust_work);
   const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
-  k_dust_density<<<cdiv(ndust, 64), 64, 0, st>>>(
-    ndust, dord, didx, ctx->n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
-    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
-    P<int>(t.perm), dust_box(p), dout);
+  const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, mass, nullptr};
+  k_dust_density<<<cdiv(ndust, 64), 64, 0, st>>>(ndust, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                 t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
+                                                 dust_box(p), dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
@@ -503,105 +768,18 @@ extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndus
   GCHK(dust_heat_buffer(ctx));
   if(ndust == 0)
     return GHIP_OK;
-  hipStream_t st = ctx->stream;
   const size_t D = (size_t) ndust;
-  DustK K;
-  K.b = dust_box(p);
-  K.dt_fac = p->dt_fac;
-  K.dt_fac_gas = p->dt_fac_gas;
-  K.minegy = p->MinEgySpec;
-  K.meanweight = p->MeanWeight;
-  K.ulength = p->UnitLength_in_cm;
-  K.umass = p->UnitMass_in_g;
-  K.udens = p->UnitDensity_in_cgs;
-  K.uvel = p->UnitVelocity_in_cm_per_s;
-  // the per-grain planes, in list order
-  std::vector<double> h((size_t) DUST_NPLANES * D, 0.0);
-  for(size_t a = 0; a < D; a++)
-    {
-      h[DP_RHO * D + a] = dust_density[a];
-      h[DP_ENT * D + a] = dust_entropy[a];
-      h[DP_RAD * D + a] = dust_radius[a];
-      h[DP_D7 * D + a] = particle_density[a];
-      h[DP_VCOLL * D + a] = vcoll[a];
-      for(int k = 0; k < 3; k++)
-        {
-          h[(DP_GV + k) * D + a] = dust_gasvel[3 * a + k];
-          h[(DP_D9 + k) * D + a] = particle_velocity[3 * a + k];
-        }
-    }
-  // dust_work: planes [DUST_NPLANES][nd] | cnt [nd + 1] | off [nd + 1]   (64-bit)
-  GCHK(ghip_ensure(ctx, ctx->dust_work, (DUST_NPLANES * D + 2 * (D + 1)) * 8 + 256));
+  const DustK K = dust_k(p);
+  std::vector<double> h;
+  GCHK(dust_upload_planes(ctx, ndust, dust_density, dust_entropy, dust_gasvel, dust_radius, particle_density,
+                          particle_velocity, vcoll, h));
+  dust_run_grains(ctx, ndust, K);
+  HIPCHK(hipGetLastError());
   double *dw = P<double>(ctx->dust_work);
   long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
-  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
-  HIPCHK(hipMemcpyAsync(dw, h.data(), DUST_NIN * D * 8, hipMemcpyHostToDevice, st));
-  k_dust_grain<<<cdiv(ndust, 256), 256, 0, st>>>(ndust, didx, ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]),
-                                                 P<double>(ctx->f[GHIP_F_MASS]),
-                                                 P<double>(ctx->f[GHIP_F_GRAVACCEL]),
-                                                 P<double>(ctx->f[GHIP_F_VEL]), dw, K);
-  HIPCHK(hipGetLastError());
-  // the scatter: count, scan, fill, sort, apply
-  TreeDev &t = ctx->st;
-  HIPCHK(hipMemsetAsync(dcnt, 0, (D + 1) * 8, st));
-  if(ctx->ngas > 0)
-    k_dust_pairs<0><<<cdiv(ndust, 64), 64, 0, st>>>(
-    ndust, dord, didx, ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
-    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TIMEBIN]), dw, t.nelem,
-    reinterpret_cast<const DustSphNode *>(t.mq.p), P<int>(t.perm), K.b, dcnt, nullptr,
-    nullptr, nullptr);
-  HIPCHK(hipGetLastError());
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, dcnt, doff, ndust + 1, st));
-  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->dust_cub.p, tb, dcnt, doff, ndust + 1, st));
   long long npairs = 0;
-  if(ctx->ngas > 0)
-    HIPCHK(hipMemcpyAsync(&npairs, doff + D, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));   // the pair count sizes the sort
-  if(npairs < 0 || npairs > (long long) INT_MAX)
-    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_dust_drag: %lld dust-gas pairs", npairs);
-  if(npairs > 0)
-    {
-      const size_t np = (size_t) npairs;
-      // dust_pairs: key [np] | key' [np] | W [np] | W' [np]
-      GCHK(ghip_ensure(ctx, ctx->dust_pairs, np * 32 + 256));
-      unsigned long long *k0 = P<unsigned long long>(ctx->dust_pairs), *k1 = k0 + np;
-      double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
-      k_dust_pairs<1><<<cdiv(ndust, 64), 64, 0, st>>>(
-        ndust, dord, didx, ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
-        P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TIMEBIN]), dw,
-        t.nelem, reinterpret_cast<const DustSphNode *>(t.mq.p), P<int>(t.perm), K.b,
-        nullptr, doff, k0, w0);
-      HIPCHK(hipGetLastError());
-      int end_bit = 33;
-      while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
-        end_bit++;
-      tb = 0;
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
-      GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
-      k_dust_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, ndust, dw, ctx->n,
-                                                      P<double>(ctx->f[GHIP_F_MASS]),
-                                                      P<int>(ctx->f[GHIP_F_TIMEBIN]),
-                                                      P<double>(ctx->f[GHIP_F_VEL]),
-                                                      P<double>(ctx->f[GHIP_F_ENTROPY]),
-                                                      P<double>(ctx->dust_heat), K);
-      HIPCHK(hipGetLastError());
-    }
-  HIPCHK(hipMemcpyAsync(h.data() + DP_D9 * D, dw + DP_D9 * D, DUST_NOUT * D * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  for(size_t a = 0; a < D; a++)
-    {
-      for(int k = 0; k < 3; k++)
-        {
-          particle_velocity[3 * a + k] = h[(DP_D9 + k) * D + a];
-          delta_momentum[3 * a + k] = h[(DP_DMOM + k) * D + a];
-        }
-      delta_energy[a] = h[DP_DE * D + a];
-      vcoll[a] = h[DP_VCOLL * D + a];
-    }
-  return GHIP_OK;
+  GCHK(dust_scatter(ctx, K, ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
+  return dust_download_grains(ctx, ndust, h, particle_velocity, delta_momentum, delta_energy, vcoll);
 }
 
 extern "C" int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating)
@@ -609,6 +787,14 @@ extern "C" int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
+  if(ctx->dd.on && !ctx->dust_heat.p)
+    {
+      // a shard creates its DragHeating in GHIP_DD_DUST_DRAG or ghip_dust_set_drag_heating only: until
+      // then it holds none (ghip_sfr_cooling refuses dust = 1), and it reads as zero
+      if(drag_heating && ctx->ngas > 0)
+        memset(drag_heating, 0, (size_t) ctx->ngas * 8);
+      return GHIP_OK;
+    }
   GCHK(dust_heat_buffer(ctx));
   if(drag_heating && ctx->ngas > 0)
     HIPCHK(hipMemcpyAsync(drag_heating, ctx->dust_heat.p, (size_t) ctx->ngas * 8, hipMemcpyDeviceToHost,
@@ -628,4 +814,212 @@ extern "C" int ghip_dust_set_drag_heating(ghip_ctx *ctx, const double *drag_heat
                           ctx->stream));
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG)
+//
+// The reference exports a grain to every task whose domain its sphere touches and adds the partial
+// results back on the home task (dust.c:60-261, 560-746).  Here a grain goes to every other shard whose
+// local Type 0 / Type 2 particles its sphere can reach (the all-gathered group boxes of those
+// particles, ghip_dd.hip), once per pass:
+//   density  phase 0  own sums; group table -> all-gather
+//            phase 1  selection, records {Pos, Hsml, Mass} -> all-to-all-v
+//            phase 2  the imported grains against this shard's Type-2 particles; partial d7 back to the
+//                     home shards (all-to-all-v with the receive layout as send layout)
+//            phase 3  own sum + the partials in ascending rank order (the export table is sorted by
+//                     task, dust.c:112-116, and the results are added in that order, :223)
+//   drag     phase 0  the per-grain update of this shard's grains; group table -> all-gather
+//            phase 1  selection, records {Pos, Hsml, DUST_Density, DeltaDustMomentum, DeltaDragEnergy}
+//                     -> all-to-all-v
+//            phase 2  the scatter into this shard's gas of its own grains (list order) and the imported
+//                     ones (receive order: by sending rank, within a rank by the sender's local particle
+//                     index -- the send lists are ascending in it, as DataIndexTable[].Index after the
+//                     sort of dust.c:617-621)
+// Under NTask > 1 the reference also adds DustDataOut[].DeltaDustMomentum / .DeltaDragEnergy back to
+// the exported grains (dust.c:727-728), but dust_evaluate_select never writes DustDataResult
+// (dust.c:889-1029): the values it adds are uninitialised memory.  Nothing is added here.
+// ---------------------------------------------------------------------------------------------
+int ghip_dd_dust_groups(ghip_ctx *ctx);   // ghip_dd.hip
+int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
+                        int periodic, int *total);
+
+int ghip_dd_dust_begin(ghip_ctx *ctx, int op)
+{
+  GHIP_JOIN(ctx);
+  const ghip_dd_dust_args &A = ctx->dd.dust;
+  const bool drag = op == GHIP_DD_DUST_DRAG;
+  const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
+  if(!A.p || A.ndust < 0 || (A.ndust > 0 && (!A.dust_idx || !A.particle_density)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(drag && A.ndust > 0 && (!A.dust_density || !A.dust_entropy || !A.dust_gasvel || !A.dust_radius ||
+                             !A.particle_velocity || !A.delta_momentum || !A.delta_energy || !A.vcoll))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  // (after GHIP_DD_BH_SWALLOW the trees are marked stale for their moments; their geometry still holds)
+  if(!ctx->gt.built && !ctx->dd.geom_kept)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_GRAVITY of this step first", who);
+  if(drag && !ctx->st.built && !ctx->dd.geom_kept)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_DENSITY of this step first", who);
+  if(A.counts)
+    for(int k = 0; k < 4; k++)
+      A.counts[k] = 0;
+  ctx->dd.du_sent = ctx->dd.du_recvd = 0;
+  return GHIP_OK;
+}
+
+int ghip_dd_dust_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  const ghip_dd_dust_args &A = D.dust;
+  hipStream_t st = ctx->stream;
+  const bool drag = D.op == GHIP_DD_DUST_DRAG;
+  const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
+  const int nd = A.ndust, n = ctx->n;
+  const size_t Dn = (size_t) nd;
+  const int *didx = P<int>(ctx->dust_idx), *dord = didx + Dn;
+  const double *pos = P<double>(ctx->f[GHIP_F_POS]), *hsml = P<double>(ctx->f[GHIP_F_HSML]),
+               *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  const int recd = drag ? DUST_REC_DRAG : DUST_REC_DENS;
+  if(D.phase == 0)
+    {
+      if(drag)
+        GCHK(dust_heat_buffer(ctx));   // (this shard holds DragHeating from now on)
+      if(nd > 0)
+        {
+          GCHK(dust_upload_list(ctx, nd, A.dust_idx, who));
+          didx = P<int>(ctx->dust_idx);
+          dord = didx + Dn;
+          if(drag)
+            {
+              std::vector<double> h;
+              GCHK(dust_upload_planes(ctx, nd, A.dust_density, A.dust_entropy, A.dust_gasvel, A.dust_radius,
+                                      A.particle_density, A.particle_velocity, A.vcoll, h));
+              dust_run_grains(ctx, nd, dust_k(A.p));
+            }
+          else
+            {
+              TreeDev &t = ctx->gt;
+              GCHK(ghip_ensure(ctx, ctx->dust_work, Dn * 8 + 256));
+              DustGrainLocal gl = {didx, pos, hsml, n, mass, nullptr};
+              k_dust_density<<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                          t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
+                                                          dust_box(A.p), P<double>(ctx->dust_work));
+            }
+          HIPCHK(hipGetLastError());
+          GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
+          k_dust_slots<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(D.du_slot));
+          HIPCHK(hipGetLastError());
+        }
+      D.phase = 1;
+      return ghip_dd_dust_groups(ctx);
+    }
+  if(D.phase == 1)
+    {
+      int total = 0;
+      GCHK(ghip_dd_dust_select(ctx, who, nd, dord, didx, A.p->BoxSize, A.p->periodic, &total));
+      GCHK(ghip_ensure(ctx, D.du_send, (size_t) (total > 0 ? total : 1) * recd * 8));
+      if(total > 0)
+        {
+          if(drag)
+            k_dust_pack<DUST_REC_DRAG><<<cdiv(total, 256), 256, 0, st>>>(
+              total, P<int>(D.du_list), P<int>(D.du_slot), n, pos, hsml, mass, nd, P<double>(ctx->dust_work),
+              P<double>(D.du_send));
+          else
+            k_dust_pack<DUST_REC_DENS><<<cdiv(total, 256), 256, 0, st>>>(
+              total, P<int>(D.du_list), P<int>(D.du_slot), n, pos, hsml, mass, nd, nullptr, P<double>(D.du_send));
+          HIPCHK(hipGetLastError());
+        }
+      D.du_sent = total;
+      ghip_dd_set_alltoallv(D, D.du_send.p, (size_t) recd * 8, D.du_scount, D.du_soff, &D.du_recv);
+      D.phase = 2;
+      return 1;
+    }
+  if(D.phase == 2 && !drag)
+    {
+      // the imported grains against this shard's Type-2 particles; the partial sums go home
+      const int nimp = D.x.rtotal;
+      D.du_recvd = nimp;
+      GCHK(ghip_ensure(ctx, D.du_part, (size_t) (nimp > 0 ? nimp : 1) * 8));
+      if(nimp > 0)
+        {
+          TreeDev &t = ctx->gt;
+          DustGrainRec gr = {P<double>(D.du_recv), DUST_REC_DENS};
+          k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                        t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
+                                                        dust_box(A.p), P<double>(D.du_part));
+          HIPCHK(hipGetLastError());
+        }
+      int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];
+      for(int r = 0; r < D.nranks; r++)
+        {
+          sc[r] = D.x.rcount[r];
+          so[r] = D.x.roff[r];
+        }
+      ghip_dd_set_alltoallv(D, D.du_part.p, 8, sc, so, &D.du_back);
+      D.phase = 3;
+      return 1;
+    }
+  if(D.phase == 3 && !drag)
+    {
+      for(int r = 0; r < D.nranks; r++)
+        if(D.x.rcount[r] != (r == D.rank ? 0 : D.du_scount[r]))
+          return ghip_fail(ctx, GHIP_ECOMM, "%s: %d partial sums came back from rank %d, %d grains went there",
+                           who, D.x.rcount[r], r, D.du_scount[r]);
+      if(nd > 0)
+        {
+          double *dout = P<double>(ctx->dust_work);
+          for(int r = 0; r < D.nranks; r++)   // own sum first, then the ranks in ascending order
+            if(r != D.rank && D.du_scount[r] > 0)
+              k_dust_add_parts<<<cdiv(D.du_scount[r], 256), 256, 0, st>>>(
+                D.du_scount[r], P<int>(D.du_list) + D.du_soff[r], P<int>(D.du_slot),
+                P<double>(D.du_back) + D.x.roff[r], dout);
+          HIPCHK(hipGetLastError());
+          HIPCHK(hipMemcpyAsync(A.particle_density, dout, Dn * 8, hipMemcpyDeviceToHost, st));
+        }
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(A.counts)
+        {
+          A.counts[0] = D.du_sent;
+          A.counts[1] = D.du_recvd;
+          A.counts[3] = D.bytes_sent[D.op];
+        }
+      D.op = 0;
+      return 0;
+    }
+  if(D.phase == 2 && drag)
+    {
+      // this shard's grains in list order, then the imported ones in receive order
+      const int nimp = D.x.rtotal;
+      D.du_recvd = nimp;
+      const int m = nd + nimp;
+      const size_t M = (size_t) m;
+      // du_part: planes [DUST_NPLANES][m] | cnt [m + 1] | off [m + 1]   (64-bit)
+      GCHK(ghip_ensure(ctx, D.du_part, (DUST_NPLANES * M + 2 * (M + 1)) * 8 + 256));
+      double *cw = P<double>(D.du_part);
+      long long *dcnt = reinterpret_cast<long long *>(cw + DUST_NPLANES * M), *doff = dcnt + M + 1;
+      const double *rec = nimp > 0 ? P<double>(D.du_recv) : nullptr;
+      if(m > 0)
+        {
+          k_dust_combine<<<cdiv(m, 256), 256, 0, st>>>(nd, nimp, P<double>(ctx->dust_work), rec, cw);
+          HIPCHK(hipGetLastError());
+        }
+      long long npairs = 0;
+      GCHK(dust_scatter(ctx, dust_k(A.p), nd, P<double>(ctx->dust_work), nimp, rec, cw, dcnt, doff, &npairs));
+      if(nd > 0)
+        {
+          std::vector<double> h((size_t) DUST_NPLANES * Dn);
+          GCHK(dust_download_grains(ctx, nd, h, A.particle_velocity, A.delta_momentum, A.delta_energy, A.vcoll));
+        }
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(A.counts)
+        {
+          A.counts[0] = D.du_sent;
+          A.counts[1] = D.du_recvd;
+          A.counts[2] = npairs;
+          A.counts[3] = D.bytes_sent[D.op];
+        }
+      D.op = 0;
+      return 0;
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the dust passes have no phase %d", D.phase);
 }

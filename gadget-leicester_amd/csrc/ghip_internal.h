@@ -207,8 +207,23 @@ struct DDState
   DevBuf sk_work;                 // per pass: h[total] | slots[total]; swallow: BH masses [n] | victims [n]
   int sk_total = 0, sk_off = 0, sk_iter = 0, sk_ncur = 0;
   SinkIter sk_it;                 // h iteration state of ALL sinks (identical on all ranks)
+  // the dust passes on shards (ghip_dust.hip): this shard's grains go to the shards their spheres reach,
+  // partial d7 come back (density), drag records are scattered into every shard's own gas (drag)
+  ghip_dd_dust_args dust;         // arguments of the operation in progress
+  DevBuf du_mask;                 // u64[n]: ranks each local grain goes to (by local particle index)
+  DevBuf du_slot;                 // i32[n]: list slot of each local grain (read where du_mask is set)
+  DevBuf du_list;                 // i32: per destination, the local particle indices sent (ascending)
+  DevBuf du_send, du_recv;        // grain records [DUST_REC doubles] out / in (source-rank major)
+  DevBuf du_part, du_back;        // f64: partial d7 of the imported grains / of this shard's exported ones
+  DevBuf heat_shadow;             // DragHeating of the migration's new layout
+  int du_scount[GHIP_MAXRANKS], du_soff[GHIP_MAXRANKS];
+  int du_sent = 0, du_recvd = 0;
+  // The trees of this step after GHIP_DD_BH_SWALLOW: only masses changed (the victims' are 0), so their
+  // geometry still serves the dust passes, which read the resident masses.  Cleared wherever particles
+  // move or a tree is built.
+  bool geom_kept = false;
   // traffic of the last operation (bytes this rank sent over links, excluding its own block)
-  long long bytes_sent[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  long long bytes_sent[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   ghip_pm_params pm;              // GHIP_DD_PM
   DevBuf pm_all;                  // the density meshes of all shards
 };

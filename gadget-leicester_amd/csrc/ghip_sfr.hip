@@ -190,9 +190,11 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: bad arguments");
   if(p->cooling < GHIP_COOL_NONE || p->cooling > GHIP_COOL_BETA)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: unknown cooling variant %d", p->cooling);
-  if(p->dust && ctx->dd.on && ctx->dd.nranks > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: dust = 1 on a multi-GPU context (%d ranks): "
-                     "DragHeating exists on single-rank contexts only", ctx->dd.nranks);
+  // (a multi-GPU shard holds DragHeating once GHIP_DD_DUST_DRAG or ghip_dust_set_drag_heating created it)
+  if(p->dust && ctx->dd.on && ctx->dd.nranks > 1 && !ctx->dust_heat.p)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: dust = 1 on a multi-GPU context (%d ranks) that "
+                     "holds no DragHeating: it exists on single-rank contexts, and on shards after "
+                     "GHIP_DD_DUST_DRAG or ghip_dust_set_drag_heating", ctx->dd.nranks);
   if(p->dust && ctx->shard_n > 1)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: dust = 1 on a sharded context (%d shards): "
                      "DragHeating exists on single-rank contexts only", ctx->shard_n);

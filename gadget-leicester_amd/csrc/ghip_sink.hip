@@ -1088,6 +1088,7 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
             A.counts[k] += (long long) (parts[(size_t) D.rank * 9 * ns + (size_t) (6 + k) * ns + g] + 0.5);
       ctx->gt.built = false;   // masses changed: the trees' moments are stale
       ctx->st.built = false;
+      D.geom_kept = true;      // (their geometry is not: the dust passes may still use them)
       D.op = 0;
       return 0;
     }

@@ -1297,6 +1297,7 @@ int ghip_tree_build_impl(ghip_ctx *ctx)
   HIPCHK(hipEventRecord(ctx->evp[0], st));
   tree_reset(ctx->gt, nsrc);
   tree_reset(ctx->st, dd ? 0 : ng);
+  ctx->dd.geom_kept = false;
   if(dd)
     ctx->st.built = false;
   ctx->gas_pending = false;

@@ -2254,11 +2254,11 @@ static int dust_ready(const char *who, int drag, int **idx_out)
   *idx_out = NULL;
   if(need_ctx(who))
     return -1;
-  if(NTask > 1)
+  if(NTask > 1 && !RcclConnected && !AllgatherFn)
     {
-      /* the passes would need the grains' ghosts on every rank and an ordered scatter into remote gas */
-      snprintf(ErrBuf, sizeof(ErrBuf), "%s: the dust passes run on a single rank only (NTask = %d)", who,
-               NTask);
+      /* without a transport the passes cannot export grains to the other ranks */
+      snprintf(ErrBuf, sizeof(ErrBuf), "%s: without a transport (gadget_force_connect or "
+               "gadget_force_set_allgather) the dust passes run on a single rank only (NTask = %d)", who, NTask);
       fprintf(stderr, "gadget_force: %s\n", ErrBuf);
       endrun(90010);
       return -1;
@@ -2278,7 +2278,20 @@ static int dust_ready(const char *who, int drag, int **idx_out)
       return -1;
     }
   gadget_force_flush();   /* results still on the device reach the records first */
-  if(ensure_tree())
+  if(NTask > 1)
+    {
+      /* collectives on the trees gravity_tree() and density() of THIS step left on the device
+       * (accel.c:194, 198 follow them) */
+      if(!DeviceFresh || !DdReady)
+        {
+          snprintf(ErrBuf, sizeof(ErrBuf), "%s on %d ranks must follow gravity_tree() and density() of the "
+                   "same step", who, NTask);
+          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+          endrun(90002);
+          return -1;
+        }
+    }
+  else if(ensure_tree())
     return -1;
   int n = 0;
   for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
@@ -2314,7 +2327,21 @@ void dust_density(void)
     }
   ghip_dust_params d;
   fill_dust_params(&d);
-  if(!chk(ghip_dust_density(Ctx, &d, n, idx, rho), "ghip_dust_density"))
+  int rc;
+  if(NTask > 1)
+    {
+      /* every rank's grains meet every rank's Type-2 particles (dust.c:60-261's export) */
+      ghip_dd_dust_args a;
+      memset(&a, 0, sizeof(a));
+      a.p = &d;
+      a.ndust = n;
+      a.dust_idx = idx;
+      a.particle_density = rho;
+      rc = dd_collective(GHIP_DD_DUST_DENSITY, &a, 0, "dust_density (ranks)") ? GHIP_EDEVICE : GHIP_OK;
+    }
+  else
+    rc = chk(ghip_dust_density(Ctx, &d, n, idx, rho), "ghip_dust_density") ? GHIP_EDEVICE : GHIP_OK;
+  if(rc == GHIP_OK)
     for(int k = 0; k < n; k++)
       *PF64(idx[k], DustLay.p_particle_density) = rho[k];   /* dust.c:242-245 */
   free(rho);
@@ -2362,7 +2389,32 @@ void dust_drag(void)
   ghip_dust_params d;
   fill_dust_params(&d);
   int rc = ghip_dust_set_drag_heating(Ctx, heat);
-  if(rc == GHIP_OK)
+  if(rc == GHIP_OK && NTask > 1)
+    {
+      /* the grains' drag records to the ranks their spheres reach; every rank scatters into its own gas
+       * (dust.c:560-746's export) */
+      ghip_dd_dust_args a;
+      memset(&a, 0, sizeof(a));
+      a.p = &d;
+      a.ndust = n;
+      a.dust_idx = idx;
+      a.particle_density = d7;
+      a.dust_density = rho;
+      a.dust_entropy = ent;
+      a.dust_gasvel = gv;
+      a.dust_radius = rad;
+      a.particle_velocity = d9;
+      a.delta_momentum = dmom;
+      a.delta_energy = de;
+      a.vcoll = vc;
+      if(dd_collective(GHIP_DD_DUST_DRAG, &a, 0, "dust_drag (ranks)"))
+        {
+          free(buf);
+          free(idx);
+          return;
+        }
+    }
+  else if(rc == GHIP_OK)
     rc = ghip_dust_drag(Ctx, &d, n, idx, rho, ent, gv, rad, d7, d9, dmom, de, vc);
   if(rc == GHIP_OK)
     rc = ghip_get_field(Ctx, GHIP_F_VEL, vel);

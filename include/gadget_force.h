@@ -407,8 +407,10 @@ extern int N_gas_swallowed, N_BH_swallowed, N_dust_swallowed;
  *           own `All`; the other members come from the library's `All` or gadget_force_bind_all)
  * dust_density() writes d7 of the grains; dust_drag() writes the grains' Vel, d9, DeltaDustMomentum,
  * NewDragAcc (zero), DeltaDragEnergy and DustVcoll, and the gas's Vel, Entropy and dh.DragHeating (in/out:
- * the records' value plus this step's heating); nothing else.  Single rank: with NTask > 1 both call
- * endrun(90010).  lay == NULL unbinds. */
+ * the records' value plus this step's heating); nothing else.  With NTask > 1 and a transport bound
+ * (gadget_force_connect / gadget_force_set_allgather) both are collectives over all ranks, after
+ * gravity_tree() and density() of the same step (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG); without one
+ * they call endrun(90010).  lay == NULL unbinds. */
 struct gadget_force_dust_layout
 {
   int p_particle_density, p_particle_velocity, p_delta_momentum, p_new_drag_acc, p_delta_energy,

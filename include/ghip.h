@@ -549,8 +549,9 @@ typedef struct
  * (dust) DragHeating -- zero when it was never set.  Writes DTENTROPY, MASS (grains), the two marks.
  * *ncand = the number of candidates; cand_idx [*ncand] (NULL: count only) their particle indices in
  * active-list order (a stable device compaction: the host reads ncand ints, not ngas).  NULL params or
- * an unknown cooling: GHIP_EINVAL; so is dust = 1 on a sharded or multi-GPU context (DragHeating
- * exists on single-rank contexts only).  With dust = 0 a shard runs the pass on its own particles. */
+ * an unknown cooling: GHIP_EINVAL; so is dust = 1 on a replicated shard (ghip_set_shard) and on a
+ * multi-GPU shard that holds no DragHeating (neither GHIP_DD_DUST_DRAG nor ghip_dust_set_drag_heating
+ * has created it there).  Otherwise a shard runs the pass on its own particles. */
 int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *ncand, int *cand_idx);
 /* the position part of FindQuasars (blackhole.c:1481-1530): over the active particles, pos = the
  * position of the LAST one in active-list order with Type 5 and Mass > 0.9 SMBHmass (the origin if
@@ -565,8 +566,9 @@ int ghip_find_smbh(ghip_ctx *ctx, double SMBHmass, double pos[3], int *count);
  * indices (the active Type-2 particles in active-list order); their per-grain state travels in host
  * arrays in list order.  Read from the resident fields: POS, MASS, TYPE, HSML, TIMEBIN, GRAVACCEL
  * (the finished value gravity_tree() leaves), VEL and the gas ENTROPY.  Needs the trees of this step;
- * the trees stay valid (no position or mass changes).  Single rank only: on a sharded or multi-GPU
- * context both return GHIP_EINVAL. ---- */
+ * the trees stay valid (no position or mass changes).  These two entry points are single-rank: on a
+ * sharded or multi-GPU context both return GHIP_EINVAL; multi-GPU shards run GHIP_DD_DUST_DENSITY /
+ * GHIP_DD_DUST_DRAG (below). ---- */
 typedef struct
 {
   int periodic;
@@ -593,9 +595,41 @@ int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const in
                    const double *dust_density, const double *dust_entropy, const double *dust_gasvel,
                    const double *dust_radius, const double *particle_density, double *particle_velocity,
                    double *delta_momentum, double *delta_energy, double *vcoll);
-/* the resident SphP[].dh.DragHeating [ngas] (zero when first used); NULL = skip */
+/* the resident SphP[].dh.DragHeating [ngas] (zero when first used); NULL = skip.  On a multi-GPU shard
+ * (ghip_dd_init) the buffer exists once GHIP_DD_DUST_DRAG or ghip_dust_set_drag_heating has created it;
+ * it then travels with its gas particles in GHIP_DD_MIGRATE.  Before that, get reads zeros and creates
+ * nothing. */
 int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating);
 int ghip_dust_set_drag_heating(ghip_ctx *ctx, const double *drag_heating);
+
+/* The dust passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG through ghip_dd_begin /
+ * ghip_dd_run): the reference's export of the grains (dust.c:60-261, 560-746).  Each grain goes to every
+ * other shard whose local Type 0 / Type 2 particles its sphere (Pos, Hsml) can reach (a sphere test
+ * against the all-gathered group boxes of those particles).
+ *   DUST_DENSITY  every shard sums its own Type-2 neighbours for its own and the imported grains (the
+ *                 grain's own mass, dust.c:849); the partial d7 of an imported grain goes back to its
+ *                 home shard, which adds them to its own sum in ascending rank order (dust.c:223).
+ *   DUST_DRAG     the per-grain update runs on the home shard; the grain's Pos, Hsml, DUST_Density,
+ *                 DeltaDustMomentum and DeltaDragEnergy go to the same shards, and every shard
+ *                 scatters into its own gas.  A gas particle receives this shard's grains in list
+ *                 order, then the imported ones by sending rank and, within a rank, by the sender's
+ *                 local particle index (the reference's order with one export round).
+ * Arrays describe the grains resident on THIS shard, as ghip_dust_density / ghip_dust_drag take them;
+ * the drag pass creates the shard's resident DragHeating.  Members an operation does not use may be
+ * NULL. */
+typedef struct
+{
+  const ghip_dust_params *p;
+  int ndust;                      /* active grains resident on this shard */
+  const int *dust_idx;            /* their local particle indices, in active-list order */
+  double *particle_density;       /* [ndust] d7: DUST_DENSITY out, DUST_DRAG in */
+  const double *dust_density, *dust_entropy, *dust_gasvel, *dust_radius;   /* DUST_DRAG in (d1, d2, d3 [ndust][3]) */
+  double *particle_velocity;      /* DUST_DRAG in/out [ndust][3] (d9) */
+  double *delta_momentum, *delta_energy;   /* DUST_DRAG out ([ndust][3], [ndust]) */
+  double *vcoll;                  /* DUST_DRAG in/out [ndust] */
+  long long *counts;              /* out [4] (may be NULL): grain records this shard sent, records it
+                                     received, (gas, grain) pairs of its scatter (DUST_DRAG), bytes sent */
+} ghip_dd_dust_args;
 
 /* The sink passes on a multi-GPU shard (GHIP_DD_SINK_DENSITY / _BH_EVALUATE / _BH_SWALLOW through
  * ghip_dd_begin / ghip_dd_run): the sinks of every shard are made known to all shards (a few hundred
@@ -630,6 +664,9 @@ typedef struct
  * force for its own particles -- the reference's slab exchange (pm_periodic.c:263-450) with the
  * transform replicated instead of distributed.  Pairs with GHIP_WALK_SHORTRANGE of GHIP_DD_GRAVITY. */
 #define GHIP_DD_PM 8
+/* the dust passes (params: ghip_dd_dust_args, see above) */
+#define GHIP_DD_DUST_DENSITY 9   /* needs GHIP_DD_GRAVITY of this step */
+#define GHIP_DD_DUST_DRAG 10     /* needs GHIP_DD_GRAVITY and GHIP_DD_DENSITY of this step */
 
 /* ---- the path ---- */
 int ghip_tree_build(ghip_ctx *ctx, const double DomainCorner[3], const double DomainCenter[3],
