@@ -137,6 +137,38 @@ class PmParams(C.Structure):
                 ("Asmth", C.c_double)]
 
 
+class PotParams(C.Structure):
+    """ghip_pot_params (compute_potential, potential.c:22-325)"""
+    _fields_ = [("grav", GravParams), ("pm", PmParams), ("G", C.c_double),
+                ("SofteningTable", C.c_double * 6), ("comoving", C.c_int), ("Omega0", C.c_double),
+                ("OmegaLambda", C.c_double), ("Hubble", C.c_double)]
+
+
+class GlobalParams(C.Structure):
+    """ghip_global_params (compute_global_quantities_of_system, global.c:18-238)"""
+    _fields_ = [("Ti_Current", C.c_int), ("Timebase_interval", C.c_double),
+                ("ComovingIntegrationOn", C.c_int), ("Time", C.c_double),
+                ("logTimeBegin", C.c_double), ("logTimeMax", C.c_double),
+                ("GravKickTable", C.c_void_p), ("HydroKickTable", C.c_void_p), ("pmgrid", C.c_int),
+                ("dt_gravkick_pm", C.c_double), ("OldPhotonMomentum", C.c_void_p),
+                ("rad_fac", C.c_double), ("Potential", C.c_void_p)]
+
+
+class GlobalSums(C.Structure):
+    """ghip_global_sums: the per-type members of struct state_of_system (allvars.h:1646-1667)"""
+    _fields_ = [("MassComp", C.c_double * 6), ("EnergyKinComp", C.c_double * 6),
+                ("EnergyPotComp", C.c_double * 6), ("EnergyIntComp", C.c_double * 6),
+                ("MomentumComp", (C.c_double * 4) * 6), ("AngMomentumComp", (C.c_double * 4) * 6),
+                ("CenterOfMassComp", (C.c_double * 4) * 6), ("EnergyRadComp", C.c_double)]
+
+    def asdict(self):
+        out = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            out[k] = float(v) if isinstance(v, float) else np.ctypeslib.as_array(v).copy()
+        return out
+
+
 class NodeLayout(C.Structure):
     """ghip_node_layout: byte offsets of struct NODE / struct extNODE (allvars.h:1847-1916)"""
     _fields_ = [(k, C.c_int) for k in
@@ -332,6 +364,11 @@ def lib():
         L.ghip_set_integration_flags.argtypes = [vp, C.POINTER(IntegrationFlags)]
         L.ghip_kick_set_fields.argtypes = [vp, vp, vp, vp]
         L.ghip_kick_get_drag_accel.argtypes = [vp, vp]
+        L.ghip_potential.argtypes = [vp, C.POINTER(PotParams)]
+        L.ghip_get_potential.argtypes = [vp, vp]
+        L.ghip_potential_interactions.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.ghip_ewald_get_pot_table.argtypes = [vp, C.c_double, vp]
+        L.ghip_global_quantities.argtypes = [vp, C.POINTER(GlobalParams), C.POINTER(GlobalSums)]
         _LIB = L
     return _LIB
 
@@ -575,6 +612,45 @@ class ForcePath:
                                           int(unequal), _ptr(nodes), _ptr(ext), _ptr(nxt), _ptr(fat),
                                           max_nodes, C.byref(nn)))
         return nodes[:nn.value], ext[:nn.value], nxt, fat
+
+    def potential(self, params):
+        """ghip_potential(PotParams): compute_potential() of every particle (see get_potential)."""
+        self._chk(self.L.ghip_potential(self.h, C.byref(params)))
+
+    def get_potential(self):
+        a = np.zeros(self.n)
+        self._chk(self.L.ghip_get_potential(self.h, _ptr(a)))
+        return a
+
+    def potential_interactions(self):
+        """(sum over targets, largest per target) of the last potential walk's interactions"""
+        s, m = C.c_longlong(0), C.c_longlong(0)
+        self._chk(self.L.ghip_potential_interactions(self.h, C.byref(s), C.byref(m)))
+        return s.value, m.value
+
+    def ewald_pot_table(self, boxsize):
+        """potcorr[EN+1][EN+1][EN+1] / BoxSize of ewald_init (forcetree.c:4466-4525)"""
+        t = np.zeros((EN + 1, EN + 1, EN + 1))
+        self._chk(self.L.ghip_ewald_get_pot_table(self.h, float(boxsize), _ptr(t)))
+        return t
+
+    def global_quantities(self, params, grav_kick_table=None, hydro_kick_table=None,
+                          old_photon_momentum=None, potential=None):
+        """ghip_global_quantities(GlobalParams) -> dict of the per-type sums (GlobalSums.asdict).
+        The host arrays go into a copy of params (the caller's object keeps no pointers to them) and
+        stay alive for the call; potential: P[].p.Potential, None = the last potential() of this state."""
+        p = GlobalParams.from_buffer_copy(params)
+        keep = []
+        for name, arr in (("GravKickTable", grav_kick_table), ("HydroKickTable", hydro_kick_table),
+                          ("OldPhotonMomentum", old_photon_momentum), ("Potential", potential)):
+            a = None if arr is None else np.ascontiguousarray(arr, dtype=np.float64)
+            if a is not None and name in ("OldPhotonMomentum", "Potential") and len(a) != self.n:
+                raise ValueError("%s: expected %d values, got %d" % (name, self.n, len(a)))
+            keep.append(a)
+            setattr(p, name, None if a is None else a.ctypes.data)
+        out = GlobalSums()
+        self._chk(self.L.ghip_global_quantities(self.h, C.byref(p), C.byref(out)))
+        return out.asdict()
 
     def pm_periodic(self, pmgrid, boxsize, G, asmth=None):
         """ghip_pm_periodic: fills F_GRAVPM; asmth defaults to ASMTH * BoxSize / PMGRID."""

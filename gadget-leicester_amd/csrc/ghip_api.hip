@@ -321,6 +321,7 @@ extern "C" void ghip_destroy(ghip_ctx *ctx)
                   &ctx->plan_nsub2, &ctx->plan_woff2, &ctx->plan_wave2, &ctx->cubtmp2, &ctx->cubtmp3,
                   &ctx->bh_swallow, &ctx->bh_injected, &ctx->dust_heat, &ctx->dust_idx,
                   &ctx->dust_work, &ctx->dust_pairs, &ctx->dust_cub, &ctx->sfr_work, &ctx->sfr_cub,
+                  &ctx->pot, &ctx->pot_nint, &ctx->potcorr, &ctx->srpot, &ctx->gq_work,
                   &ctx->kick_drag, &ctx->kick_ddm, &ctx->kick_newdens};
   for(DevBuf *b : bs)
     free_buf(*b);
@@ -437,6 +438,8 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_counts: need 0 <= ngas <= numpart");
   HIPCHK(hipSetDevice(ctx->device));
   bool changed = (numpart != ctx->n || ngas != ctx->ngas);
+  if(changed)
+    ctx->pot_n = -1;   // (the potential of ghip_potential belongs to the particle set it was made for)
   ctx->n = numpart;
   ctx->ngas = ngas;
   for(int f = 0; f < GHIP_F_COUNT; f++)
@@ -514,6 +517,8 @@ extern "C" int ghip_set_field(ghip_ctx *ctx, int field, const void *host)
     GHIP_JOIN(ctx);
   if(!ctx || field < 0 || field >= GHIP_F_COUNT)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_field: bad field %d", field);
+  if(field == GHIP_F_POS || field == GHIP_F_MASS || field == GHIP_F_TYPE)
+    ctx->pot_n = -1;   // (what ghip_potential computed no longer belongs to this state)
   size_t cnt = field_count(ctx, field), bytes = field_bytes(ctx, field);
   if(cnt == 0)
     return GHIP_OK;
@@ -797,6 +802,8 @@ extern "C" int ghip_upload_aos(ghip_ctx *ctx, const void *Pp, const void *Sp, co
 {
   if(ctx)
     GHIP_JOIN(ctx);
+  if(ctx)
+    ctx->pot_n = -1;
   GCHK(check_upload_args(ctx, Pp, Sp, lay, numpart, ngas, true));
   GCHK(ghip_set_counts(ctx, numpart, ngas));
   if(numpart == 0)
@@ -821,6 +828,8 @@ extern "C" int ghip_upload_aos_particles(ghip_ctx *ctx, const void *Pp, const gh
 {
   if(ctx)
     GHIP_JOIN(ctx);
+  if(ctx)
+    ctx->pot_n = -1;
   GCHK(check_upload_args(ctx, Pp, nullptr, lay, numpart, ngas, false));
   if(ctx->adaptive_gravsoft && lay->p_hsml < 0 && ngas > 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_upload_aos_particles: with adaptive gravitational softening "

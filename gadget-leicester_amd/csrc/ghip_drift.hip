@@ -114,6 +114,7 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
     GHIP_JOIN(ctx);
   if(!ctx || !p)
     return GHIP_EINVAL;
+  ctx->pot_n = -1;
   if(p->ComovingIntegrationOn && (!p->DriftTable || !p->GravKickTable || !p->HydroKickTable))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_drift: comoving drift needs the three factor tables");
   int n = ctx->n, ng = ctx->ngas;

@@ -411,6 +411,14 @@ struct ghip_ctx
   long long run_steps = 0, run_syncs0 = 0, run_launches0 = 0, run_dens_iter = 0;
   long long n_syncs = 0;               // blocking host waits inside the library since creation
   DevBuf run_acc;                      // u64[16]: counters summed over the steps of a run
+  // ---- ghip_potential / ghip_global_quantities (ghip_potential.hip) ----
+  DevBuf pot;                      // f64[n]: P[].p.Potential of the last ghip_potential, host order
+  DevBuf pot_nint;                 // u64[n]: its interactions per target, tree order
+  int pot_n = -1;                  // particle count of that call (-1: none)
+  DevBuf potcorr;                  // f64[(EN+1)^3]: potcorr / BoxSize (forcetree.c:4466-4525)
+  double potcorr_box = 0;
+  DevBuf srpot;                    // float[NTAB]: shortrange_table_potential (forcetree.c:4201)
+  DevBuf gq_work;                  // partial sums, kick tables and photon momenta of ghip_global_quantities
 };
 #define GHIP_NEV 16
 
@@ -490,6 +498,7 @@ int ghip_finish_gas_tree(ghip_ctx *ctx);   // complete a deferred gas tree (entr
     }                                           \
   while(0)
 void ghip_pm_release(ghip_ctx *ctx);
+int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot);   // pm.hip
 
 #define HIPCHK(call)                                                                         \
   do                                                                                         \

@@ -250,6 +250,76 @@ static int pm_solve_and_interpolate(ghip_ctx *ctx, const ghip_pm_params *p)
   return GHIP_OK;
 }
 
+// pmpotential_periodic (pm_periodic.c:808-1195): the same deposit and Green's function as the force
+// (:1040-1097), the inverse transform is the potential mesh, read out with the CIC weights of :1172-1189
+// and multiplied by fac = G / (pi BoxSize) (:837).  (The fork computes fac and never applies it; without
+// it the mesh potential is not in the units of the tree potential, so it is applied here.)
+__global__ void k_pm_pot_readout(int n, int N, double to_slab_fac, double fac,
+                                 const double *__restrict__ pos, const double *__restrict__ phi,
+                                 double *__restrict__ pot)
+{
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  double px = to_slab_fac * pos[i], py = to_slab_fac * pos[(size_t) n + i],
+         pz = to_slab_fac * pos[2 * (size_t) n + i];
+  int sx = (int) px, sy = (int) py, sz = (int) pz;
+  double dx = px - sx, dy = py - sy, dz = pz - sz;
+  if(sx >= N)
+    sx = N - 1;
+  if(sy >= N)
+    sy = N - 1;
+  if(sz >= N)
+    sz = N - 1;
+  double v = 0;
+  for(int xx = 0; xx < 2; xx++)
+    for(int yy = 0; yy < 2; yy++)
+      for(int zz = 0; zz < 2; zz++)
+        {
+          int gx = sx + xx, gy = sy + yy, gz = sz + zz;
+          if(gx >= N)
+            gx -= N;
+          if(gy >= N)
+            gy -= N;
+          if(gz >= N)
+            gz -= N;
+          double w = (xx ? dx : 1.0 - dx) * (yy ? dy : 1.0 - dy) * (zz ? dz : 1.0 - dz);
+          v += phi[((size_t) gx * N + gy) * N + gz] * w;
+        }
+  pot[i] += fac * v;
+}
+
+// pot[i] += the periodic PM potential of every particle (ghip_potential, PMGRID builds).  GRAVPM and
+// what ghip_pm_periodic computes are not touched.
+int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot)
+{
+  GCHK(pm_check(ctx, p));
+  const int N = p->pmgrid, n = ctx->n;
+  if(n == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  GCHK(pm_prepare(ctx, N));
+  const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
+  const double to_slab_fac = N / p->BoxSize;
+  double *rho = P<double>(ctx->pm_rho);
+  double2 *fk = P<double2>(ctx->pm_k);
+  HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
+  k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
+                                             P<double>(ctx->f[GHIP_F_MASS]), rho);
+  HIPCHK(hipGetLastError());
+  double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;   // :834-835
+  asmth2 *= asmth2;
+  const double fac = p->G / (M_PI * p->BoxSize);        // :837 (pm.G = All.G)
+  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm_fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
+  k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
+  HIPCHK(hipGetLastError());
+  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm_inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  k_pm_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, fac, P<double>(ctx->f[GHIP_F_POS]),
+                                                 rho, pot);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
 extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
 {
   if(ctx)

@@ -1,0 +1,742 @@
+// ghip_potential.hip -- compute_potential() (potential.c:22-325) and the per-type sums of
+// compute_global_quantities_of_system() (global.c:18-238) on gfx950.
+//
+// The potential walk is a kernel of its own, not a mode of k_grav_walk (ghip_walk.h): it is a
+// diagnostic that runs every TimeBetStatistics, and the tuned force walk stays as it is.  It reads
+// the same 64-byte element records (WalkHot / WalkCold) of the tree the gravity walks would use at
+// this moment (the tree of the current positions, or the kept tree of ghip_set_dynamic_tree).
+//
+// Mapping: one lane per target, ALL particles of the context are targets (potential.c:88-97), in
+// tree (curve) order so that the lanes of a wavefront walk similar paths.  Each lane follows the
+// pre-order list with its own cursor: e + 1 opens a node or steps past a particle, the node's skip
+// index accepts it -- the reference's nextnode / sibling order, so every lane adds its terms in the
+// reference's order.  Plain loads (the records are wave-divergent here), no inline assembly.
+//
+// Floating-point contraction is off in this file: the opening decisions and the sums are the
+// reference's operations one by one, so a restatement in numpy reproduces them.
+#pragma clang fp contract(off)
+
+#include <cmath>
+
+#include "ghip_internal.h"
+#include "ghip_walkrec.h"
+#include "ghip_timefac.h"
+
+#define GHIP_POT_ORIGIN 2.8372975   // potcorr[0][0][0] and the comoving self term (forcetree.c:4479,
+                                    // potential.c:253)
+
+struct PotK
+{
+  double theta, errtol;
+  double boxsize, boxhalf;
+  double rcut, asmthfac;   // short-range walk (forcetree.c:3805-3812)
+  double fac_intp;         // 2 EN / BoxSize (forcetree.c:4517)
+};
+
+// ewald_pot_corr (forcetree.c:4633-4684) on the (EN+1)^3 table of psi / BoxSize
+__device__ __forceinline__ double d_ewald_pot_corr(const double *__restrict__ tab, double fac_intp,
+                                                   double dx, double dy, double dz)
+{
+  const int E1 = GHIP_EN + 1;
+  if(dx < 0)
+    dx = -dx;
+  if(dy < 0)
+    dy = -dy;
+  if(dz < 0)
+    dz = -dz;
+  double u = dx * fac_intp;
+  int i = (int) u;
+  if(i >= GHIP_EN)
+    i = GHIP_EN - 1;
+  u -= i;
+  double v = dy * fac_intp;
+  int j = (int) v;
+  if(j >= GHIP_EN)
+    j = GHIP_EN - 1;
+  v -= j;
+  double w = dz * fac_intp;
+  int k = (int) w;
+  if(k >= GHIP_EN)
+    k = GHIP_EN - 1;
+  w -= k;
+  const double f1 = (1 - u) * (1 - v) * (1 - w), f2 = (1 - u) * (1 - v) * (w);
+  const double f3 = (1 - u) * (v) * (1 - w), f4 = (1 - u) * (v) * (w);
+  const double f5 = (u) * (1 - v) * (1 - w), f6 = (u) * (1 - v) * (w);
+  const double f7 = (u) * (v) * (1 - w), f8 = (u) * (v) * (w);
+  const double *t00 = tab + ((size_t) i * E1 + j) * E1 + k;   // [i][j][k]
+  const double *t01 = t00 + E1;                                 // [i][j+1][k]
+  const double *t10 = t00 + (size_t) E1 * E1;                   // [i+1][j][k]
+  const double *t11 = t10 + E1;                                 // [i+1][j+1][k]
+  return t00[0] * f1 + t00[1] * f2 + t01[0] * f3 + t01[1] * f4 + t10[0] * f5 + t10[1] * f6 +
+         t11[0] * f7 + t11[1] * f8;
+}
+
+// the spline potential of forcetree.c:3496-3510 (times mass / h); -mass / r outside h
+__device__ __forceinline__ double d_pot_term(double mass, double r, double h)
+{
+  if(r >= h)
+    return -mass / r;
+  const double h_inv = 1.0 / h;
+  const double u = r * h_inv;
+  double wp;
+  if(u < 0.5)
+    wp = -2.8 + u * u * (5.333333333333 + u * u * (6.4 * u - 9.6));
+  else
+    wp = -3.2 + 0.066666666667 / u +
+         u * u * (10.666666666667 + u * (-16.0 + u * (9.6 - 2.133333333333 * u)));
+  return mass * h_inv * wp;
+}
+
+// force_treeevaluate_potential (forcetree.c:3217-3530; PERIODIC: NEAREST and the Ewald potential
+// correction with every interaction) and force_treeevaluate_potential_shortrange (:3752-4115, SHORT).
+// UNEQUAL: the softening rules of UNEQUALSOFTENINGS, with ADAPTIVE_GRAVSOFT_FORGAS folded into the
+// records (a particle's aux is its softening -- Hsml for gas --, a node's aux is its largest
+// softening, negative when the node opens for every target inside it: mixed softenings, or always
+// with adaptive softening).
+template <bool PERIODIC, bool SHORT, bool UNEQUAL, bool REL>
+__global__ void __launch_bounds__(256)
+  k_pot_walk(const TreeSizes *__restrict__ ts, int n, const WalkHot *__restrict__ hot,
+             const WalkCold *__restrict__ cold, const double *__restrict__ tx,
+             const double *__restrict__ ty, const double *__restrict__ tz,
+             const double *__restrict__ tsoft, const double *__restrict__ toldacc,
+             const int *__restrict__ perm, const double *__restrict__ potcorr,
+             const float *__restrict__ srpot, PotK k, double *__restrict__ pot_out,
+             unsigned long long *__restrict__ nint_out)
+{
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= n)
+    return;
+  const int nelem = ts->nelem;
+  const double px = tx[s], py = ty[s], pz = tz[s];
+  const double hi = tsoft[s];
+  const double aold = REL ? k.errtol * toldacc[s] : 0.0;
+  double pot = 0;
+  unsigned int nint = 0;
+  int e = 0;
+  while(e < nelem)
+    {
+      const WalkHot H = hot[e];
+      double dx = H.x - px, dy = H.y - py, dz = H.z - pz;
+      if(PERIODIC)
+        {
+          dx = d_nearest(dx, k.boxsize, k.boxhalf);
+          dy = d_nearest(dy, k.boxsize, k.boxhalf);
+          dz = d_nearest(dz, k.boxsize, k.boxhalf);
+        }
+      const double r2 = dx * dx + dy * dy + dz * dz;
+      double h = hi;
+      int next;
+      if(H.pidx >= 0)
+        {
+          if(UNEQUAL && h < H.aux)
+            h = H.aux;
+          next = e + 1;
+        }
+      else
+        {
+          if(SHORT)
+            {
+              // the whole cell beyond the cut-off: drop the branch (forcetree.c:3900-3929)
+              const WalkCold C = cold[e];
+              const double eff = k.rcut + 0.5 * C.len;
+              double dxx = C.cx - px, dyy = C.cy - py, dzz = C.cz - pz;
+              if(PERIODIC)
+                {
+                  dxx = d_nearest(dxx, k.boxsize, k.boxhalf);
+                  dyy = d_nearest(dyy, k.boxsize, k.boxhalf);
+                  dzz = d_nearest(dzz, k.boxsize, k.boxhalf);
+                }
+              if(dxx < -eff || dxx > eff || dyy < -eff || dyy > eff || dzz < -eff || dzz > eff)
+                {
+                  e = H.skip;
+                  continue;
+                }
+            }
+          bool open;
+          if(REL)
+            {
+              open = H.mlen2 > r2 * r2 * aold;
+              if(!open)
+                {
+                  // the 0.6 len box test against the unwrapped centre - pos (forcetree.c:3439-3450)
+                  const WalkCold C = cold[e];
+                  open = fabs(C.cx - px) < C.len06 && fabs(C.cy - py) < C.len06 &&
+                         fabs(C.cz - pz) < C.len06;
+                }
+            }
+          else
+            open = H.len2 > r2 * k.theta * k.theta;
+          if(!open && UNEQUAL)
+            {
+              const double ms = fabs(H.aux);
+              if(h < ms)
+                {
+                  h = ms;
+                  if(H.aux < 0 && r2 < h * h)
+                    open = true;
+                }
+            }
+          if(open)
+            {
+              e = e + 1;
+              continue;
+            }
+          next = H.skip;
+        }
+      const double r = sqrt(r2);
+      if(SHORT)
+        {
+          const int tabindex = (int) (r * k.asmthfac);
+          if(tabindex < GHIP_NTAB)
+            {
+              // (-fac * mass / r and fac * mass * h_inv * wp: the product fac * mass first, as :4082-4096)
+              const double fac = srpot[tabindex];
+              pot += d_pot_term(fac * H.m, r, h);
+              nint++;
+            }
+        }
+      else
+        {
+          pot += d_pot_term(H.m, r, h);
+          if(PERIODIC)
+            pot += H.m * d_ewald_pot_corr(potcorr, k.fac_intp, dx, dy, dz);
+          nint++;
+        }
+      e = next;
+    }
+  pot_out[perm[s]] = pot;
+  if(nint_out)
+    nint_out[s] = nint;
+}
+
+// potcorr of ewald_init (forcetree.c:4466-4481, 4518-4525): psi(x) / BoxSize at x = 0.5 (i,j,k) / EN,
+// 2.8372975 / BoxSize at the origin; ewald_psi is forcetree.c:4686-4720
+__global__ void k_ewald_pot_table(double boxsize, double *__restrict__ tab)
+{
+  const int E1 = GHIP_EN + 1;
+  const int nidx = blockIdx.x * blockDim.x + threadIdx.x;
+  if(nidx >= E1 * E1 * E1)
+    return;
+  const int i = nidx / (E1 * E1), j = (nidx / E1) % E1, kk = nidx % E1;
+  double psi;
+  if(i + j + kk == 0)
+    psi = GHIP_POT_ORIGIN;
+  else
+    {
+      const double alpha = 2.0;
+      const double x0 = 0.5 * ((double) i) / GHIP_EN, x1 = 0.5 * ((double) j) / GHIP_EN,
+                   x2 = 0.5 * ((double) kk) / GHIP_EN;
+      double sum1 = 0;
+      for(int n0 = -4; n0 <= 4; n0++)
+        for(int n1 = -4; n1 <= 4; n1++)
+          for(int n2 = -4; n2 <= 4; n2++)
+            {
+              const double d0 = x0 - n0, d1 = x1 - n1, d2 = x2 - n2;
+              const double r = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+              sum1 += erfc(alpha * r) / r;
+            }
+      double sum2 = 0;
+      for(int h0 = -4; h0 <= 4; h0++)
+        for(int h1 = -4; h1 <= 4; h1++)
+          for(int h2i = -4; h2i <= 4; h2i++)
+            {
+              const double hdotx = x0 * h0 + x1 * h1 + x2 * h2i;
+              const int h2 = h0 * h0 + h1 * h1 + h2i * h2i;
+              if(h2 > 0)
+                sum2 += 1 / (M_PI * h2) * exp(-M_PI * M_PI * h2 / (alpha * alpha)) *
+                        cos(2 * M_PI * hdotx);
+            }
+      const double r = sqrt(x0 * x0 + x1 * x1 + x2 * x2);
+      psi = M_PI / (alpha * alpha) - sum1 - sum2 + 1 / r;
+    }
+  tab[nidx] = psi / boxsize;
+}
+
+// potential.c:245-259: the self term, the comoving periodic background term, the factor G
+__global__ void k_pot_finish(int n, const double *__restrict__ mass, const int *__restrict__ type,
+                             double soft0, double soft1, double soft2, double soft3, double soft4,
+                             double soft5, double bgfac, double G, double *__restrict__ pot)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  const int t = type[i];
+  const double st = t == 0 ? soft0 : t == 1 ? soft1 : t == 2 ? soft2 : t == 3 ? soft3 : t == 4 ? soft4 : soft5;
+  double p = pot[i];
+  const double m = mass[i];
+  p += m / st;
+  if(bgfac != 0)
+    p -= GHIP_POT_ORIGIN * pow(m, 2.0 / 3) * bgfac;
+  pot[i] = p * G;
+}
+
+// potential.c:303-325: fac * r^2 with fac = -1/2 Omega0 H^2 (comoving, not periodic) or
+// -1/2 OmegaLambda H^2 (physical)
+__global__ void k_pot_quadratic(int n, const double *__restrict__ pos, double fac,
+                                double *__restrict__ pot)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  double r2 = 0;
+  for(int k = 0; k < 3; k++)
+    r2 += pos[(size_t) k * n + i] * pos[(size_t) k * n + i];
+  pot[i] += fac * r2;
+}
+
+static int ensure_pot_table(ghip_ctx *ctx, double BoxSize)
+{
+  if(ctx->potcorr_box == BoxSize)
+    return GHIP_OK;
+  const int E1 = GHIP_EN + 1;
+  const int nt = E1 * E1 * E1;
+  GCHK(ghip_ensure(ctx, ctx->potcorr, (size_t) nt * sizeof(double)));
+  k_ewald_pot_table<<<cdiv(nt, 64), 64, 0, ctx->stream>>>(BoxSize, P<double>(ctx->potcorr));
+  HIPCHK(hipGetLastError());
+  ctx->potcorr_box = BoxSize;
+  return GHIP_OK;
+}
+
+static int ensure_srpot_table(ghip_ctx *ctx)
+{
+  if(ctx->srpot.p)
+    return GHIP_OK;
+  // forcetree.c:4195-4202: shortrange_table_potential[i] = erfc(u), a float table as in the reference
+  float tab[GHIP_NTAB];
+  for(int i = 0; i < GHIP_NTAB; i++)
+    {
+      const double u = 3.0 / GHIP_NTAB * (i + 0.5);
+      tab[i] = (float) erfc(u);
+    }
+  GCHK(ghip_ensure(ctx, ctx->srpot, sizeof(tab)));
+  HIPCHK(hipMemcpyAsync(ctx->srpot.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *host)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !host || !(BoxSize > 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_ewald_get_pot_table: need BoxSize > 0 and an output");
+  GCHK(ensure_pot_table(ctx, BoxSize));
+  const int E1 = GHIP_EN + 1;
+  HIPCHK(hipMemcpyAsync(host, ctx->potcorr.p, (size_t) E1 * E1 * E1 * sizeof(double),
+                        hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !p)
+    return GHIP_EINVAL;
+  if(ctx->dd.on || ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: not on a multi-GPU shard");
+  if(!ctx->gt.built)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: call ghip_tree_build first");
+  // every argument is checked here, before anything is launched
+  const ghip_grav_params &g = p->grav;
+  const ghip_pm_params &pm = p->pm;
+  const int pmgrid = pm.pmgrid;
+  if(pmgrid != 0)
+    {
+      if(!g.periodic)
+        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: the non-periodic PM potential is not provided");
+      if(pmgrid < 4 || pmgrid > 2048 || (pmgrid & 1) || !(pm.BoxSize > 0) || !(pm.Asmth > 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
+                         "pm.Asmth > 0");
+      if(pm.BoxSize != g.BoxSize)
+        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: pm.BoxSize %g differs from grav.BoxSize %g",
+                         pm.BoxSize, g.BoxSize);
+      if(!(g.Rcut > 0 && g.Asmth > 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: a PM potential needs Rcut, Asmth > 0");
+    }
+  if(g.periodic && !(g.BoxSize > 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: periodic needs BoxSize > 0");
+  for(int t = 0; t < 6; t++)
+    if(!(p->SofteningTable[t] > 0))
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: SofteningTable[%d] must be > 0", t);
+  const bool rel = g.ErrTolTheta == 0;   // (only the relative criterion reads OldAcc)
+  for(int f : {GHIP_F_POS, GHIP_F_MASS, GHIP_F_TYPE, GHIP_F_OLDACC})
+    if(ctx->n > 0 && !ctx->f[f].p && (f != GHIP_F_OLDACC || rel))
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: particle field %d not set", f);
+  GCHK(ghip_tree_verify(ctx));
+  const int n = ctx->n;
+  hipStream_t st = ctx->stream;
+  GCHK(ghip_ensure(ctx, ctx->pot, (size_t) (n > 0 ? n : 1) * sizeof(double)));
+  GCHK(ghip_ensure(ctx, ctx->pot_nint, (size_t) (n > 0 ? n : 1) * sizeof(unsigned long long)));
+  ctx->pot_n = -1;
+  if(n == 0)
+    {
+      ctx->pot_n = 0;
+      return GHIP_OK;
+    }
+  const bool shortrange = pmgrid > 0;
+  const bool periodic = g.periodic != 0;
+  const bool ewald = periodic && !shortrange;
+  const bool unequal = g.unequal_softenings || ctx->adaptive_gravsoft;
+  if(ewald)
+    GCHK(ensure_pot_table(ctx, g.BoxSize));
+  if(shortrange)
+    GCHK(ensure_srpot_table(ctx));
+  PotK k;
+  k.theta = g.ErrTolTheta;
+  k.errtol = g.ErrTolForceAcc;
+  k.boxsize = g.BoxSize;
+  k.boxhalf = 0.5 * g.BoxSize;
+  k.rcut = g.Rcut;
+  k.asmthfac = shortrange ? 0.5 / g.Asmth * (GHIP_NTAB / 3.0) : 0.0;
+  k.fac_intp = periodic ? 2 * GHIP_EN / g.BoxSize : 0.0;
+  // OldAcc of every particle in tree order (the relative criterion of potential.c reads P[].OldAcc)
+  if(rel)
+    GCHK(ghip_gather_f64_lim(ctx, ctx->gt.n, P<int>(ctx->gt.perm), P<double>(ctx->f[GHIP_F_OLDACC]), n,
+                             P<double>(ctx->soldacc)));
+  const TreeDev &t = ctx->dyn_use ? ctx->dyn : ctx->gt;
+#define POT_ARGS                                                                                   \
+  P<TreeSizes>(t.dsz), n, P<WalkHot>(t.mq), P<WalkCold>(t.mq2), P<double>(ctx->sx),                \
+    P<double>(ctx->sy), P<double>(ctx->sz), P<double>(ctx->ssoft),                                  \
+    rel ? P<double>(ctx->soldacc) : nullptr,                                                        \
+    P<int>(ctx->gt.perm), ewald ? P<double>(ctx->potcorr) : nullptr,                                \
+    shortrange ? P<float>(ctx->srpot) : nullptr, k, P<double>(ctx->pot),                            \
+    P<unsigned long long>(ctx->pot_nint)
+#define POT_LAUNCH(PER, SR, UNEQ, REL)                                                             \
+  k_pot_walk<PER, SR, UNEQ, REL><<<cdiv(n, 256), 256, 0, st>>>(POT_ARGS)
+#define POT_LAUNCH_R(PER, SR, UNEQ)                                                                \
+  do                                                                                               \
+    {                                                                                              \
+      if(rel)                                                                                      \
+        POT_LAUNCH(PER, SR, UNEQ, true);                                                           \
+      else                                                                                         \
+        POT_LAUNCH(PER, SR, UNEQ, false);                                                          \
+    }                                                                                              \
+  while(0)
+#define POT_LAUNCH_U(PER, SR)                                                                      \
+  do                                                                                               \
+    {                                                                                              \
+      if(unequal)                                                                                  \
+        POT_LAUNCH_R(PER, SR, true);                                                               \
+      else                                                                                         \
+        POT_LAUNCH_R(PER, SR, false);                                                              \
+    }                                                                                              \
+  while(0)
+  if(periodic)
+    {
+      if(shortrange)
+        POT_LAUNCH_U(true, true);
+      else
+        POT_LAUNCH_U(true, false);
+    }
+  else
+    {
+      if(shortrange)
+        POT_LAUNCH_U(false, true);
+      else
+        POT_LAUNCH_U(false, false);
+    }
+#undef POT_LAUNCH_U
+#undef POT_LAUNCH_R
+#undef POT_LAUNCH
+#undef POT_ARGS
+  HIPCHK(hipGetLastError());
+  // potential.c:245-259
+  double bgfac = 0;
+  if(p->comoving && periodic)
+    bgfac = pow(p->Omega0 * 3 * p->Hubble * p->Hubble / (8 * M_PI * p->G), 1.0 / 3);
+  const double *S = p->SofteningTable;
+  k_pot_finish<<<cdiv(n, 256), 256, 0, st>>>(n, P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]),
+                                             S[0], S[1], S[2], S[3], S[4], S[5], bgfac, p->G,
+                                             P<double>(ctx->pot));
+  HIPCHK(hipGetLastError());
+  // potential.c:262-265: pmpotential_periodic
+  if(shortrange)
+    GCHK(ghip_pm_potential_add(ctx, &p->pm, P<double>(ctx->pot)));
+  // potential.c:301-325
+  double qfac = 0;
+  if(p->comoving)
+    {
+      if(!periodic)
+        qfac = -0.5 * p->Omega0 * p->Hubble * p->Hubble;
+    }
+  else
+    qfac = -0.5 * p->OmegaLambda * p->Hubble * p->Hubble;
+  if(qfac != 0)
+    {
+      k_pot_quadratic<<<cdiv(n, 256), 256, 0, st>>>(n, P<double>(ctx->f[GHIP_F_POS]), qfac, P<double>(ctx->pot));
+      HIPCHK(hipGetLastError());
+    }
+  ctx->pot_n = n;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_get_potential(ghip_ctx *ctx, double *host)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !host)
+    return GHIP_EINVAL;
+  if(ctx->pot_n != ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_get_potential: call ghip_potential first");
+  if(ctx->n > 0)
+    HIPCHK(hipMemcpyAsync(host, ctx->pot.p, (size_t) ctx->n * sizeof(double), hipMemcpyDeviceToHost,
+                          ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return ghip_check_device_errors(ctx);
+}
+
+// interactions per target of the last ghip_potential, in tree order (sum and maximum)
+extern "C" int ghip_potential_interactions(ghip_ctx *ctx, long long *sum, long long *maxval)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || ctx->pot_n != ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential_interactions: call ghip_potential first");
+  std::vector<unsigned long long> v((size_t) ctx->n);
+  if(ctx->n > 0)
+    HIPCHK(hipMemcpyAsync(v.data(), ctx->pot_nint.p, v.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  long long s = 0, m = 0;
+  for(unsigned long long x : v)
+    {
+      s += (long long) x;
+      m = (long long) x > m ? (long long) x : m;
+    }
+  if(sum)
+    *sum = s;
+  if(maxval)
+    *maxval = m;
+  return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// compute_global_quantities_of_system (global.c:18-238): per particle the 14 contributions, per
+// block and type fixed-order partial sums, the blocks added on the host in block order.  No atomics:
+// two calls on the same state give the same bits.
+// ---------------------------------------------------------------------------------------------
+#define GQ_NQ 14          // mass, pot, kin, int, mom[3], com[3], angmom[3], rad
+#define GQ_PER_THREAD 8
+#define GQ_BLOCK 256
+
+struct GqK
+{
+  int n, ngas;
+  int Ti_Current;
+  int comoving;
+  double a1, a2, a3;
+  int pmgrid;
+  double dt_gravkick_pm;   // the PM kick factor, the same for every particle
+  double rad_fac;          // C / UnitVelocity_in_cm_per_s
+  DriftK dk;               // kick tables (comoving)
+};
+
+__device__ __forceinline__ void d_gq_particle(int i, const GqK &k, const double *__restrict__ pos,
+                                              const double *__restrict__ vel, const double *__restrict__ mass,
+                                              const int *__restrict__ type, const int *__restrict__ timebin,
+                                              const int *__restrict__ ti_begstep,
+                                              const double *__restrict__ gacc, const double *__restrict__ gravpm,
+                                              const double *__restrict__ hacc, const double *__restrict__ entropy,
+                                              const double *__restrict__ dtentropy,
+                                              const double *__restrict__ density,
+                                              const double *__restrict__ pot,
+                                              const double *__restrict__ photon, double q[GQ_NQ])
+{
+  const int n = k.n, ng = k.ngas;
+  const int t = type[i];
+  const double m = mass[i];
+  q[13] = (photon && t == 3 && m != 0.) ? photon[i] * k.rad_fac : 0.0;
+  q[0] = m;
+  q[1] = pot ? 0.5 * m * pot[i] / k.a1 : 0.0;
+  const int dt_step = timebin[i] ? (1 << timebin[i]) : 0;
+  const int tb = ti_begstep[i];
+  double dt_entr, dt_gravkick, dt_hydrokick;
+  if(k.comoving)
+    {
+      dt_entr = (k.Ti_Current - (tb + dt_step / 2)) * k.dk.timebase;
+      dt_gravkick = d_table_factor(k.dk.gravkick, tb, k.Ti_Current, k.dk) -
+                    d_table_factor(k.dk.gravkick, tb, tb + dt_step / 2, k.dk);
+      dt_hydrokick = d_table_factor(k.dk.hydrokick, tb, k.Ti_Current, k.dk) -
+                     d_table_factor(k.dk.hydrokick, tb, tb + dt_step / 2, k.dk);
+    }
+  else
+    dt_entr = dt_gravkick = dt_hydrokick = (k.Ti_Current - (tb + dt_step / 2)) * k.dk.timebase;
+  const bool gas = t == 0 && i < ng;
+  double v[3];
+  for(int j = 0; j < 3; j++)
+    {
+      v[j] = vel[(size_t) j * n + i] + gacc[(size_t) j * n + i] * dt_gravkick;
+      if(gas)
+        v[j] += hacc[(size_t) j * ng + i] * dt_hydrokick;
+    }
+  double entr = 0;
+  if(gas)
+    entr = entropy[i] + dtentropy[i] * dt_entr;
+  if(k.pmgrid)
+    for(int j = 0; j < 3; j++)
+      v[j] += gravpm[(size_t) j * n + i] * k.dt_gravkick_pm;
+  q[2] = 0.5 * m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) / k.a2;
+  q[3] = gas ? m * (entr / (GAMMA - 1) * pow(density[i] / k.a3, GAMMA - 1)) : 0.0;
+  const double x0 = pos[i], x1 = pos[(size_t) n + i], x2 = pos[2 * (size_t) n + i];
+  for(int j = 0; j < 3; j++)
+    {
+      q[4 + j] = m * v[j];
+      q[7 + j] = m * pos[(size_t) j * n + i];
+    }
+  q[10] = m * (x1 * v[2] - x2 * v[1]);
+  q[11] = m * (x2 * v[0] - x0 * v[2]);
+  q[12] = m * (x0 * v[1] - x1 * v[0]);
+}
+
+// out[block][type][q]
+__global__ void __launch_bounds__(GQ_BLOCK)
+  k_global_quantities(GqK k, const double *__restrict__ pos, const double *__restrict__ vel,
+                      const double *__restrict__ mass, const int *__restrict__ type,
+                      const int *__restrict__ timebin, const int *__restrict__ ti_begstep,
+                      const double *__restrict__ gacc, const double *__restrict__ gravpm,
+                      const double *__restrict__ hacc, const double *__restrict__ entropy,
+                      const double *__restrict__ dtentropy, const double *__restrict__ density,
+                      const double *__restrict__ pot, const double *__restrict__ photon,
+                      double *__restrict__ out)
+{
+  __shared__ double red[GQ_BLOCK];
+  double acc[6][GQ_NQ];
+  for(int t = 0; t < 6; t++)
+    for(int q = 0; q < GQ_NQ; q++)
+      acc[t][q] = 0;
+  const int base = blockIdx.x * GQ_BLOCK * GQ_PER_THREAD;
+  for(int c = 0; c < GQ_PER_THREAD; c++)
+    {
+      const int i = base + c * GQ_BLOCK + threadIdx.x;
+      if(i < k.n)
+        {
+          double q[GQ_NQ];
+          d_gq_particle(i, k, pos, vel, mass, type, timebin, ti_begstep, gacc, gravpm, hacc, entropy,
+                        dtentropy, density, pot, photon, q);
+          const int t = type[i];
+          for(int tt = 0; tt < 6; tt++)
+            if(tt == t)
+              for(int qq = 0; qq < GQ_NQ; qq++)
+                acc[tt][qq] += q[qq];
+        }
+    }
+  // fixed-order tree reduction of each of the 6 x 14 sums
+  for(int t = 0; t < 6; t++)
+    for(int q = 0; q < GQ_NQ; q++)
+      {
+        red[threadIdx.x] = acc[t][q];
+        __syncthreads();
+        for(int w = GQ_BLOCK / 2; w > 0; w >>= 1)
+          {
+            if((int) threadIdx.x < w)
+              red[threadIdx.x] += red[threadIdx.x + w];
+            __syncthreads();
+          }
+        if(threadIdx.x == 0)
+          out[((size_t) blockIdx.x * 6 + t) * GQ_NQ + q] = red[0];
+        __syncthreads();
+      }
+}
+
+extern "C" int ghip_global_quantities(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums *out)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !p || !out)
+    return GHIP_EINVAL;
+  if(ctx->dd.on || ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: not on a multi-GPU shard");
+  if(p->ComovingIntegrationOn && (!p->GravKickTable || !p->HydroKickTable))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: comoving runs need the kick tables");
+  memset(out, 0, sizeof(*out));
+  const int n = ctx->n, ng = ctx->ngas;
+  if(n == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  GqK k;
+  k.n = n;
+  k.ngas = ng;
+  k.Ti_Current = p->Ti_Current;
+  k.comoving = p->ComovingIntegrationOn;
+  k.a1 = k.a2 = k.a3 = 1;
+  if(k.comoving)
+    {
+      k.a1 = p->Time;
+      k.a2 = p->Time * p->Time;
+      k.a3 = p->Time * p->Time * p->Time;
+    }
+  k.pmgrid = p->pmgrid;
+  k.dt_gravkick_pm = p->dt_gravkick_pm;
+  k.rad_fac = p->rad_fac;
+  k.dk = DriftK();
+  k.dk.timebase = p->Timebase_interval;
+  k.dk.comoving = k.comoving;
+  k.dk.logTimeBegin = p->logTimeBegin;
+  k.dk.logTimeMax = p->logTimeMax;
+  // upload order: kick tables, photon momenta; then the partial sums come back through the same buffer
+  const int nb = cdiv(n, GQ_BLOCK * GQ_PER_THREAD);
+  const size_t npart = (size_t) nb * 6 * GQ_NQ;
+  const size_t ntab = k.comoving ? 2 * DRIFT_TABLE_LENGTH : 0;
+  const size_t nph = p->OldPhotonMomentum ? (size_t) n : 0;
+  const size_t npot = p->Potential ? (size_t) n : 0;
+  GCHK(ghip_ensure(ctx, ctx->gq_work, (npart + ntab + nph + npot + 1) * sizeof(double)));
+  double *w = P<double>(ctx->gq_work);
+  double *tabs = w + npart, *ph = w + npart + ntab, *hpot = ph + nph;
+  if(k.comoving)
+    {
+      HIPCHK(hipMemcpyAsync(tabs, p->GravKickTable, DRIFT_TABLE_LENGTH * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(tabs + DRIFT_TABLE_LENGTH, p->HydroKickTable, DRIFT_TABLE_LENGTH * 8,
+                            hipMemcpyHostToDevice, st));
+      k.dk.gravkick = tabs;
+      k.dk.hydrokick = tabs + DRIFT_TABLE_LENGTH;
+    }
+  if(nph)
+    HIPCHK(hipMemcpyAsync(ph, p->OldPhotonMomentum, nph * 8, hipMemcpyHostToDevice, st));
+  if(npot)
+    HIPCHK(hipMemcpyAsync(hpot, p->Potential, npot * 8, hipMemcpyHostToDevice, st));
+  const bool gas = ng > 0;
+  for(int f : {GHIP_F_POS, GHIP_F_VEL, GHIP_F_MASS, GHIP_F_TYPE, GHIP_F_TIMEBIN, GHIP_F_TI_BEGSTEP,
+               GHIP_F_GRAVACCEL})
+    if(!ctx->f[f].p)
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: particle field %d not set", f);
+  if(p->pmgrid && !ctx->f[GHIP_F_GRAVPM].p)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: PMGRID needs GRAVPM");
+  if(gas)
+    for(int f : {GHIP_F_HYDROACCEL, GHIP_F_ENTROPY, GHIP_F_DTENTROPY, GHIP_F_DENSITY})
+      if(!ctx->f[f].p)
+        return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: gas field %d not set", f);
+  k_global_quantities<<<nb, GQ_BLOCK, 0, st>>>(
+    k, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_MASS]),
+    P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]),
+    P<double>(ctx->f[GHIP_F_GRAVACCEL]), p->pmgrid ? P<double>(ctx->f[GHIP_F_GRAVPM]) : nullptr,
+    gas ? P<double>(ctx->f[GHIP_F_HYDROACCEL]) : nullptr, gas ? P<double>(ctx->f[GHIP_F_ENTROPY]) : nullptr,
+    gas ? P<double>(ctx->f[GHIP_F_DTENTROPY]) : nullptr, gas ? P<double>(ctx->f[GHIP_F_DENSITY]) : nullptr,
+    npot ? hpot : ctx->pot_n == n ? P<double>(ctx->pot) : nullptr, nph ? ph : nullptr, w);
+  HIPCHK(hipGetLastError());
+  std::vector<double> h(npart);
+  HIPCHK(hipMemcpyAsync(h.data(), w, npart * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  GCHK(ghip_check_device_errors(ctx));
+  // the blocks in block order
+  double s[6][GQ_NQ] = {};
+  for(int b = 0; b < nb; b++)
+    for(int t = 0; t < 6; t++)
+      for(int q = 0; q < GQ_NQ; q++)
+        s[t][q] += h[((size_t) b * 6 + t) * GQ_NQ + q];
+  for(int t = 0; t < 6; t++)
+    {
+      out->MassComp[t] = s[t][0];
+      out->EnergyPotComp[t] = s[t][1];
+      out->EnergyKinComp[t] = s[t][2];
+      out->EnergyIntComp[t] = s[t][3];
+      for(int j = 0; j < 3; j++)
+        {
+          out->MomentumComp[t][j] = s[t][4 + j];
+          out->CenterOfMassComp[t][j] = s[t][7 + j];
+          out->AngMomentumComp[t][j] = s[t][10 + j];
+        }
+      out->EnergyRadComp += s[t][13];
+    }
+  return GHIP_OK;
+}

@@ -72,19 +72,7 @@ __device__ int *d_walk_errw = nullptr;
 //   (forcetree.c:2085), aux = max softening below (negative: mixed softenings)
 //   particle: position, 0, 0, aux = its softening
 // cold half (64 B): cx, cy, cz, len | 0.6*len | spare
-struct __attribute__((aligned(64))) WalkHot
-{
-  double x, y, z, m;
-  double mlen2, len2;
-  int skip, pidx;
-  double aux;
-};
-struct __attribute__((aligned(64))) WalkCold
-{
-  double cx, cy, cz, len;
-  double len06;
-  double spare[3];
-};
+#include "ghip_walkrec.h"   // WalkHot, WalkCold
 
 // a 64-byte record in 16 consecutive SGPRs, as eight doubles: every double of a record is an
 // aligned register pair as it arrives (a record of sixteen ints would have to be re-assembled into

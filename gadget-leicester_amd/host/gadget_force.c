@@ -2691,3 +2691,342 @@ static void hydro_force_ranks(void)
   Phase = 0;
   CPU_Step_Hydro += wallclock() - t0;
 }
+
+/* ------------------------------------------------------------------------------------------
+ * compute_potential() / compute_global_quantities_of_system() (potential.c:22-325, global.c:18-238)
+ * ---------------------------------------------------------------------------------------- */
+static struct gadget_force_potential_layout PotLay;
+static int PotBound = 0;
+static char *HostSys = NULL;
+
+void gadget_force_bind_potential(void *host_SysState, const struct gadget_force_potential_layout *lay)
+{
+  PotBound = lay != NULL;
+  if(lay)
+    PotLay = *lay;
+  HostSys = lay ? (char *) host_SysState : NULL;
+}
+
+static int potential_refused(const char *who)
+{
+  if(NTask <= 1)
+    return 0;
+  snprintf(ErrBuf, sizeof(ErrBuf), "%s: the potential and the energy statistics run on one rank only "
+           "(NTask = %d)", who, NTask);
+  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+  endrun(90012);
+  return -1;
+}
+
+static int potential_missing(const char *who, const char *what)
+{
+  snprintf(ErrBuf, sizeof(ErrBuf), "%s: %s", who, what);
+  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+  endrun(90013);
+  return -1;
+}
+
+/* get_gravkick_factor (driftfac.c:166-205) on the host's table */
+static double kick_factor(const double *tab, int time0, int time1)
+{
+  const int len = 1000;
+  double df[2];
+  const int t[2] = { time0, time1 };
+  for(int k = 0; k < 2; k++)
+    {
+      double a = KickLogBegin + t[k] * All.Timebase_interval;
+      double u = (a - KickLogBegin) / (KickLogMax - KickLogBegin) * len;
+      int i = (int) u;
+      if(i >= len)
+        i = len - 1;
+      df[k] = (i <= 1) ? u * tab[0] : tab[i - 1] + (tab[i] - tab[i - 1]) * (u - i);
+    }
+  return df[1] - df[0];
+}
+
+void compute_potential(void)
+{
+  const char *who = "compute_potential";
+  if(need_ctx(who) || potential_refused(who))
+    return;
+  if(!PotBound || PotLay.p_potential < 0)
+    {
+      potential_missing(who, "bind P[].p.Potential with gadget_force_bind_potential() first");
+      return;
+    }
+  gadget_force_flush();
+  all_pull();
+  if(All.ComovingIntegrationOn)
+    set_softenings();   /* potential.c:33-34 */
+  /* the device copy as the host's records are now */
+  DeviceFresh = 0;
+  TreeOnDevice = 0;
+  if(upload_particles(0))
+    return;
+  /* potential.c:74-78: every particle to Ti_Current (on the device only: this function writes nothing
+   * but P[].p.Potential) */
+  int behind = 0;
+  if(Lay.p_ti_current >= 0)
+    for(int i = 0; i < NumPart && !behind; i++)
+      behind = *(int *) (prec(i) + Lay.p_ti_current) != All.Ti_Current;
+  if(behind)
+    {
+      if(All.ComovingIntegrationOn && !(DriftTab && KickTabGrav && KickTabHydro))
+        {
+          potential_missing(who, "a comoving drift needs gadget_force_set_drift_table() and "
+                                 "gadget_force_set_kick_tables()");
+          return;
+        }
+      ghip_drift_params d;
+      memset(&d, 0, sizeof(d));
+      d.time1 = All.Ti_Current;
+      d.Timebase_interval = All.Timebase_interval;
+      d.ComovingIntegrationOn = All.ComovingIntegrationOn;
+      d.logTimeBegin = KickLogBegin;
+      d.logTimeMax = KickLogMax;
+      d.DriftTable = DriftTab;
+      d.GravKickTable = KickTabGrav;
+      d.HydroKickTable = KickTabHydro;
+      d.MinGasHsml = All.MinGasHsml;
+      d.BoxSize = All.BoxSize;
+      d.pmgrid = Cfg.pmgrid != 0;
+      if(chk(ghip_drift(Ctx, &d), "ghip_drift"))
+        return;
+    }
+  /* potential.c:46-60: the tree gravity_tree() would walk now */
+  if(ensure_tree_split(0))
+    return;
+  ghip_pot_params pp;
+  memset(&pp, 0, sizeof(pp));
+  fill_grav_params(&pp.grav);
+  pp.pm.pmgrid = Cfg.pmgrid;
+  pp.pm.BoxSize = All.BoxSize;
+  pp.pm.G = All.G;
+  pp.pm.Asmth = All.Asmth[0];
+  pp.G = All.G;
+  for(int k = 0; k < 6; k++)
+    pp.SofteningTable[k] = All.SofteningTable[k];
+  pp.comoving = All.ComovingIntegrationOn;
+  pp.Omega0 = All.Omega0;
+  pp.OmegaLambda = All.OmegaLambda;
+  pp.Hubble = All.Hubble;
+  if(chk(ghip_potential(Ctx, &pp), "ghip_potential"))
+    return;
+  double *pot = (double *) malloc((size_t) (NumPart > 0 ? NumPart : 1) * sizeof(double));
+  if(!pot)
+    {
+      endrun(90003);
+      return;
+    }
+  if(chk(ghip_get_potential(Ctx, pot), "ghip_get_potential"))
+    {
+      free(pot);
+      return;
+    }
+  for(int i = 0; i < NumPart; i++)
+    *PF64(i, PotLay.p_potential) = pot[i];
+  free(pot);
+  /* the device's records may be ahead of the host's now: the next driver uploads them again */
+  DeviceFresh = 0;
+  TreeOnDevice = 0;
+}
+
+static void sys_put(int off, const double *v, int count)
+{
+  if(off >= 0)
+    memcpy(HostSys + off, v, (size_t) count * sizeof(double));
+}
+
+/* one double member (or ncomp consecutive ones) of every record into a device field */
+static int field_from_records(int field, int off, int ncomp, int gas, double *buf)
+{
+  const int cnt = gas ? N_gas : NumPart;
+  for(int i = 0; i < cnt; i++)
+    {
+      const double *v = (const double *) ((gas ? srec(i) : prec(i)) + off);
+      for(int k = 0; k < ncomp; k++)
+        buf[(size_t) k * cnt + i] = v[k];   /* the field's [n][3] host layout is AoS: fixed below */
+    }
+  if(ncomp == 3)
+    {
+      /* ghip_set_field takes [n][3] */
+      double *t = buf + 3 * (size_t) cnt;
+      for(int i = 0; i < cnt; i++)
+        for(int k = 0; k < 3; k++)
+          t[3 * (size_t) i + k] = buf[(size_t) k * cnt + i];
+      return chk(ghip_set_field(Ctx, field, t), "ghip_set_field");
+    }
+  return chk(ghip_set_field(Ctx, field, buf), "ghip_set_field");
+}
+
+void compute_global_quantities_of_system(void)
+{
+  const char *who = "compute_global_quantities_of_system";
+  if(need_ctx(who) || potential_refused(who))
+    return;
+  if(!PotBound || !HostSys)
+    {
+      potential_missing(who, "bind the SysState with gadget_force_bind_potential() first");
+      return;
+    }
+  if(Cfg.pmgrid && (!HostAll || PotLay.a_pm_ti_begstep < 0 || PotLay.a_pm_ti_endstep < 0))
+    {
+      potential_missing(who, "PMGRID: bind All (gadget_force_bind_all) and a_pm_ti_begstep / a_pm_ti_endstep");
+      return;
+    }
+  if(All.ComovingIntegrationOn && !(KickTabGrav && KickTabHydro))
+    {
+      potential_missing(who, "comoving runs need gadget_force_set_kick_tables()");
+      return;
+    }
+  gadget_force_flush();
+  all_pull();
+  const int n = NumPart, ng = N_gas;
+  double *buf = (double *) malloc((size_t) (n > 0 ? n : 1) * 6 * sizeof(double));
+  double *pot = (double *) malloc((size_t) (n > 0 ? n : 1) * sizeof(double));
+  double *ph = (double *) malloc((size_t) (n > 0 ? n : 1) * sizeof(double));
+  int *ib = (int *) malloc((size_t) (n > 0 ? n : 1) * sizeof(int));
+  if(!buf || !pot || !ph || !ib)
+    {
+      free(buf), free(pot), free(ph), free(ib);
+      endrun(90003);
+      return;
+    }
+  int rc = chk(ghip_set_counts(Ctx, n, ng), "ghip_set_counts");
+  if(!rc)
+    rc = field_from_records(GHIP_F_POS, Lay.p_pos, 3, 0, buf) || field_from_records(GHIP_F_VEL, Lay.p_vel, 3, 0, buf) ||
+         field_from_records(GHIP_F_MASS, Lay.p_mass, 1, 0, buf) ||
+         field_from_records(GHIP_F_GRAVACCEL, Lay.p_gravaccel, 3, 0, buf);
+  if(!rc && Cfg.pmgrid)
+    rc = field_from_records(GHIP_F_GRAVPM, Lay.p_gravpm, 3, 0, buf);
+  if(!rc && ng > 0)
+    rc = field_from_records(GHIP_F_HYDROACCEL, Lay.s_hydroaccel, 3, 1, buf) ||
+         field_from_records(GHIP_F_ENTROPY, Lay.s_entropy, 1, 1, buf) ||
+         field_from_records(GHIP_F_DTENTROPY, Lay.s_dtentropy, 1, 1, buf) ||
+         field_from_records(GHIP_F_DENSITY, Lay.s_density, 1, 1, buf);
+  if(!rc)
+    {
+      for(int i = 0; i < n; i++)
+        ib[i] = p_type(i);
+      rc = chk(ghip_set_field(Ctx, GHIP_F_TYPE, ib), "ghip_set_field");
+    }
+  if(!rc)
+    {
+      for(int i = 0; i < n; i++)
+        ib[i] = p_timebin(i);
+      rc = chk(ghip_set_field(Ctx, GHIP_F_TIMEBIN, ib), "ghip_set_field");
+    }
+  if(!rc)
+    {
+      for(int i = 0; i < n; i++)
+        ib[i] = *(int *) (prec(i) + Lay.p_ti_begstep);
+      rc = chk(ghip_set_field(Ctx, GHIP_F_TI_BEGSTEP, ib), "ghip_set_field");
+    }
+  ghip_global_params gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.Ti_Current = All.Ti_Current;
+  gp.Timebase_interval = All.Timebase_interval;
+  gp.ComovingIntegrationOn = All.ComovingIntegrationOn;
+  gp.Time = All.Time;
+  gp.logTimeBegin = KickLogBegin;
+  gp.logTimeMax = KickLogMax;
+  gp.GravKickTable = KickTabGrav;
+  gp.HydroKickTable = KickTabHydro;
+  gp.pmgrid = Cfg.pmgrid;
+  if(Cfg.pmgrid)
+    {
+      /* global.c:96-103 */
+      const int beg = *(int *) (HostAll + PotLay.a_pm_ti_begstep), end = *(int *) (HostAll + PotLay.a_pm_ti_endstep);
+      gp.dt_gravkick_pm = All.ComovingIntegrationOn
+                            ? kick_factor(KickTabGrav, beg, All.Ti_Current) - kick_factor(KickTabGrav, beg, (beg + end) / 2)
+                            : (All.Ti_Current - (beg + end) / 2) * All.Timebase_interval;
+    }
+  gp.rad_fac = PotLay.rad_fac;
+  if(PotLay.p_old_photon_momentum >= 0)
+    {
+      for(int i = 0; i < n; i++)
+        ph[i] = *PF64(i, PotLay.p_old_photon_momentum);
+      gp.OldPhotonMomentum = ph;
+    }
+  if(PotLay.p_potential >= 0)
+    {
+      for(int i = 0; i < n; i++)
+        pot[i] = *PF64(i, PotLay.p_potential);
+      gp.Potential = pot;
+    }
+  ghip_global_sums s;
+  if(!rc)
+    rc = chk(ghip_global_quantities(Ctx, &gp, &s), "ghip_global_quantities");
+  free(buf), free(pot), free(ph), free(ib);
+  /* the device fields now hold the records' state: the next driver uploads and builds again */
+  DeviceFresh = 0;
+  TreeOnDevice = 0;
+  if(rc)
+    return;
+  /* global.c:163-236 (the MPI_Reduce of one rank is the identity) */
+  double EnergyTotComp[6], Mass = 0, EnergyKin = 0, EnergyPot = 0, EnergyInt = 0, EnergyTot = 0;
+  double Momentum[4] = { 0, 0, 0, 0 }, AngMomentum[4] = { 0, 0, 0, 0 }, CenterOfMass[4] = { 0, 0, 0, 0 };
+  for(int i = 0; i < 6; i++)
+    EnergyTotComp[i] = s.EnergyKinComp[i] + s.EnergyPotComp[i] + s.EnergyIntComp[i];
+  for(int i = 0; i < 6; i++)
+    {
+      Mass += s.MassComp[i];
+      EnergyKin += s.EnergyKinComp[i];
+      EnergyPot += s.EnergyPotComp[i];
+      EnergyInt += s.EnergyIntComp[i];
+      EnergyTot += EnergyTotComp[i];
+      for(int j = 0; j < 3; j++)
+        {
+          Momentum[j] += s.MomentumComp[i][j];
+          AngMomentum[j] += s.AngMomentumComp[i][j];
+          CenterOfMass[j] += s.CenterOfMassComp[i][j];
+        }
+    }
+  for(int i = 0; i < 6; i++)
+    for(int j = 0; j < 3; j++)
+      if(s.MassComp[i] > 0)
+        s.CenterOfMassComp[i][j] /= s.MassComp[i];
+  for(int j = 0; j < 3; j++)
+    if(Mass > 0)
+      CenterOfMass[j] /= Mass;
+  for(int i = 0; i < 6; i++)
+    {
+      s.CenterOfMassComp[i][3] = s.MomentumComp[i][3] = s.AngMomentumComp[i][3] = 0;
+      for(int j = 0; j < 3; j++)
+        {
+          s.CenterOfMassComp[i][3] += s.CenterOfMassComp[i][j] * s.CenterOfMassComp[i][j];
+          s.MomentumComp[i][3] += s.MomentumComp[i][j] * s.MomentumComp[i][j];
+          s.AngMomentumComp[i][3] += s.AngMomentumComp[i][j] * s.AngMomentumComp[i][j];
+        }
+      s.CenterOfMassComp[i][3] = sqrt(s.CenterOfMassComp[i][3]);
+      s.MomentumComp[i][3] = sqrt(s.MomentumComp[i][3]);
+      s.AngMomentumComp[i][3] = sqrt(s.AngMomentumComp[i][3]);
+    }
+  for(int j = 0; j < 3; j++)
+    {
+      CenterOfMass[3] += CenterOfMass[j] * CenterOfMass[j];
+      Momentum[3] += Momentum[j] * Momentum[j];
+      AngMomentum[3] += AngMomentum[j] * AngMomentum[j];
+    }
+  CenterOfMass[3] = sqrt(CenterOfMass[3]);
+  Momentum[3] = sqrt(Momentum[3]);
+  AngMomentum[3] = sqrt(AngMomentum[3]);
+  sys_put(PotLay.sys_Mass, &Mass, 1);
+  sys_put(PotLay.sys_EnergyKin, &EnergyKin, 1);
+  sys_put(PotLay.sys_EnergyPot, &EnergyPot, 1);
+  sys_put(PotLay.sys_EnergyInt, &EnergyInt, 1);
+  sys_put(PotLay.sys_EnergyTot, &EnergyTot, 1);
+  sys_put(PotLay.sys_Momentum, Momentum, 4);
+  sys_put(PotLay.sys_AngMomentum, AngMomentum, 4);
+  sys_put(PotLay.sys_CenterOfMass, CenterOfMass, 4);
+  sys_put(PotLay.sys_MassComp, s.MassComp, 6);
+  sys_put(PotLay.sys_EnergyKinComp, s.EnergyKinComp, 6);
+  sys_put(PotLay.sys_EnergyPotComp, s.EnergyPotComp, 6);
+  sys_put(PotLay.sys_EnergyIntComp, s.EnergyIntComp, 6);
+  sys_put(PotLay.sys_EnergyTotComp, EnergyTotComp, 6);
+  sys_put(PotLay.sys_MomentumComp, &s.MomentumComp[0][0], 24);
+  sys_put(PotLay.sys_AngMomentumComp, &s.AngMomentumComp[0][0], 24);
+  sys_put(PotLay.sys_CenterOfMassComp, &s.CenterOfMassComp[0][0], 24);
+  if(PotLay.p_old_photon_momentum >= 0)
+    sys_put(PotLay.sys_EnergyRadComp, &s.EnergyRadComp, 1);
+}

@@ -100,6 +100,18 @@ class IntegrationLayout(C.Structure):
         "a_feedback_velocity", "a_unit_velocity")]
 
 
+class PotentialLayout(C.Structure):
+    """struct gadget_force_potential_layout: byte offsets of P[].p.Potential, P[].OldPhotonMomentum, the
+    SysState members and All.PM_Ti_begstep / PM_Ti_endstep (-1 = absent), and rad_fac"""
+    _fields_ = [(k, C.c_int) for k in (
+        "p_potential", "p_old_photon_momentum", "sys_Mass", "sys_EnergyRadComp", "sys_EnergyRadAdded",
+        "sys_EnergyRadDeleted", "sys_EnergyKin", "sys_EnergyPot", "sys_EnergyInt", "sys_EnergyTot",
+        "sys_Momentum", "sys_AngMomentum", "sys_CenterOfMass", "sys_MassComp", "sys_EnergyKinComp",
+        "sys_EnergyPotComp", "sys_EnergyIntComp", "sys_EnergyTotComp", "sys_MomentumComp",
+        "sys_AngMomentumComp", "sys_CenterOfMassComp", "a_pm_ti_begstep", "a_pm_ti_endstep")] + \
+        [("rad_fac", C.c_double)]
+
+
 class TopNode(C.Structure):
     """struct topnode_data, allvars.h:437-447"""
     _fields_ = [("Size", C.c_ulonglong), ("StartKey", C.c_ulonglong), ("Count", C.c_longlong),
@@ -155,7 +167,8 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "N_dust_swallowed", "TopNodes", "NTopnodes", "NTopleaves", "DomainStartList",
            "DomainEndList", "gadget_force_unique_id", "gadget_force_connect",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
-           "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration"]
+           "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration",
+           "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system"]
 
 _LIB = None
 
@@ -208,6 +221,10 @@ def lib():
         L.dust_drag.restype = None
         L.gadget_force_bind_integration.argtypes = [C.c_void_p] * 6
         L.gadget_force_bind_integration.restype = None
+        L.gadget_force_bind_potential.argtypes = [C.c_void_p, C.c_void_p]
+        L.gadget_force_bind_potential.restype = None
+        L.compute_potential.restype = None
+        L.compute_global_quantities_of_system.restype = None
         _LIB = L
     return _LIB
 
@@ -285,6 +302,23 @@ class Host:
         self.L.gadget_force_bind_integration(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p),
                                              *[None if a is None else C.c_void_p(a.ctypes.data) for a in sums])
 
+    def bind_potential(self, sysstate, lay):
+        """gadget_force_bind_potential: `sysstate` a numpy structured scalar holding the host's SysState,
+        `lay` a PotentialLayout; None unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_potential(None, None)
+            self._pot = None
+            return
+        self._pot = (sysstate, lay)            # keep alive
+        self.L.gadget_force_bind_potential(None if sysstate is None else C.c_void_p(sysstate.ctypes.data),
+                                           C.cast(C.byref(lay), C.c_void_p))
+
+    def compute_potential(self):
+        self.L.compute_potential()
+
+    def compute_global_quantities_of_system(self):
+        self.L.compute_global_quantities_of_system()
+
     def set_allgather(self, allgather):
         """the host's all-gather for more than one rank: allgather(send: bytes) -> bytes of all ranks"""
         def cb(_user, send, nbytes, recv):
@@ -324,6 +358,7 @@ class Host:
         self.L.gadget_force_bind_records(None, None, None, None)
         self.L.gadget_force_bind_dust(None, None)
         self.L.gadget_force_bind_integration(None, None, None, None, None, None)
+        self.L.gadget_force_bind_potential(None, None)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)
         self._seti("ThisTask", 0)
         self._seti("NTask", 1)

@@ -349,6 +349,39 @@ void gadget_force_mark_dirty(void);
 /* overlap_sph: complete a gravity_tree() whose results are still on the device (no-op otherwise) */
 void gadget_force_flush(void);
 
+/* ---- compute_potential() / compute_global_quantities_of_system() (potential.c:22-325, global.c:18-238;
+ * -DCOMPUTE_POTENTIAL_ENERGY, -DOUTPUTPOTENTIAL).  Where the results go, as BYTE OFFSETS (-1 = the
+ * host's build has no such member; a probe TU fills them with offsetof):
+ *   p_potential            P[].p.Potential (double), written by compute_potential() and read by
+ *                          compute_global_quantities_of_system()
+ *   p_old_photon_momentum  P[].OldPhotonMomentum (VIRTUAL): EnergyRadComp of Type 3
+ *   sys_*                  the members of the host's struct state_of_system (allvars.h:1646-1667) that
+ *                          global.c writes; sys_EnergyRadAdded / sys_EnergyRadDeleted are listed for a
+ *                          complete probe and never written (global.c does not write them)
+ *   a_pm_ti_begstep / a_pm_ti_endstep   All.PM_Ti_begstep / PM_Ti_endstep in the host's `All` bound
+ *                          with gadget_force_bind_all (PMGRID builds: the GravPM kick, global.c:96-103)
+ *   rad_fac                C / All.UnitVelocity_in_cm_per_s (VIRTUAL; not an offset)
+ * Both functions run on one rank only: with NTask > 1 they call endrun(90012).  A missing binding
+ * the build needs (p_potential, the SysState, the PM step or the comoving tables) is endrun(90013). */
+struct gadget_force_potential_layout
+{
+  int p_potential, p_old_photon_momentum;
+  int sys_Mass, sys_EnergyRadComp, sys_EnergyRadAdded, sys_EnergyRadDeleted, sys_EnergyKin, sys_EnergyPot,
+    sys_EnergyInt, sys_EnergyTot, sys_Momentum, sys_AngMomentum, sys_CenterOfMass, sys_MassComp,
+    sys_EnergyKinComp, sys_EnergyPotComp, sys_EnergyIntComp, sys_EnergyTotComp, sys_MomentumComp,
+    sys_AngMomentumComp, sys_CenterOfMassComp;
+  int a_pm_ti_begstep, a_pm_ti_endstep;
+  double rad_fac;
+};
+/* host_SysState: the host's SysState (what energy_statistics() prints); lay == NULL unbinds */
+void gadget_force_bind_potential(void *host_SysState, const struct gadget_force_potential_layout *lay);
+/* potential.c:22-325: every particle behind All.Ti_Current is drifted on the device (potential.c:74-78;
+ * the host's records keep their state), the tree is the one gravity_tree() would walk now (a fresh build,
+ * or the kept tree with cfg.dynamic_tree), and ONLY P[].p.Potential is written */
+void compute_potential(void);
+/* global.c:18-238: SysState from the host's records (P[].p.Potential as compute_potential left it) */
+void compute_global_quantities_of_system(void);
+
 /* ---- the reference's call surface ---- */
 void endrun(int ierr);
 void set_softenings(void);

@@ -25,6 +25,8 @@
  *   ghip_tree_export                      Nodes[] / Extnodes[] / Nextnode[] / Father[] as
  *                                         force_treebuild leaves them  allvars.h:1847-1916
  *   ghip_pm_periodic                      pmforce_periodic()           pm_periodic.c:199-800
+ *   ghip_potential                        compute_potential()          potential.c:22-325
+ *   ghip_global_quantities                compute_global_quantities_of_system()  global.c:18-238
  * The host-side mirror with the reference's own names (gravity_tree(), density(), hydro_force(),
  * force_treeevaluate(), ...) is include/gadget_force.h.
  */
@@ -447,6 +449,69 @@ int ghip_tree_export(ghip_ctx *ctx, const ghip_node_layout *lay, int MaxPart, in
  * (replaces long_range_force() -> pmforce_periodic(), longrange.c / pm_periodic.c:199-800; the
  * field is zeroed first as long_range_force does).  Pairs with GHIP_WALK_SHORTRANGE. ---- */
 int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p);
+
+/* ---- compute_potential() (potential.c:22-325): the potential of EVERY particle of the context from a
+ * walk of the tree the gravity walks would use now (the tree of the last ghip_tree_build, or the kept
+ * tree after ghip_tree_substep when ghip_set_dynamic_tree is on; the caller drifts first), then the
+ * reference's finish: + Mass / SofteningTable[type] (the self term, which adaptive gas softening does
+ * not cancel), comoving periodic runs - 2.8372975 m^(2/3) (Omega0 3 H^2 / (8 pi G))^(1/3), * G,
+ * pm.pmgrid > 0: + the periodic PM potential (pmpotential_periodic, pm_periodic.c:808-1195; the walk is
+ * then the short-range one, grav.Rcut / Asmth), and -1/2 Omega0 H^2 r^2 (comoving, not periodic) or
+ * -1/2 OmegaLambda H^2 r^2 (physical).  grav.periodic without a mesh adds the Ewald potential
+ * correction to every interaction (forcetree.c:3514).  Reads POS, MASS, TYPE, OLDACC (relative
+ * criterion) and, with adaptive softening, the HSML the tree was built with.  The result stays in a
+ * per-context buffer (ghip_get_potential); no GHIP_F_* field changes.  Not on a multi-GPU shard
+ * (GHIP_EINVAL).  pm.G is the mesh part's G (All.G, as for ghip_pm_periodic); pm.BoxSize must equal
+ * grav.BoxSize.  Every argument is checked before anything runs. ---- */
+typedef struct
+{
+  ghip_grav_params grav;     /* opening criterion, softenings, BoxSize, periodic, Rcut / Asmth */
+  ghip_pm_params pm;         /* pm.pmgrid = 0: no mesh */
+  double G;                  /* All.G */
+  double SofteningTable[6];  /* All.SofteningTable (the self term) */
+  int comoving;              /* All.ComovingIntegrationOn */
+  double Omega0, OmegaLambda, Hubble;
+} ghip_pot_params;
+int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p);
+/* P[].p.Potential [n] f64, host order */
+int ghip_get_potential(ghip_ctx *ctx, double *host);
+/* interactions of the last walk: summed over the targets and the largest per target */
+int ghip_potential_interactions(ghip_ctx *ctx, long long *sum, long long *maxval);
+/* potcorr[65][65][65] of ewald_init, already divided by BoxSize (tests) */
+int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *host);
+
+/* ---- compute_global_quantities_of_system() (global.c:18-238), the per-type sums before the
+ * MPI_Reduce: velocities predicted to Ti_Current with the grav / hydro kick factors (+ HydroAccel of gas,
+ * + GravPM dt_gravkick_pm under PMGRID), entropies with DtEntropy, EnergyPotComp from the potential of
+ * the last ghip_potential (0 when there is none for the current particle set).  Reads POS, VEL, MASS,
+ * TYPE, TIMEBIN, TI_BEGSTEP, GRAVACCEL, (PMGRID) GRAVPM, (gas) HYDROACCEL, ENTROPY, DTENTROPY, DENSITY.
+ * The potential is p->Potential when given, else that of the last ghip_potential -- which holds only
+ * while POS, MASS, TYPE and the particle counts are unchanged since (ghip_set_field, ghip_set_counts, the
+ * uploads and ghip_drift discard it): call ghip_potential on the current state first.
+ * Deterministic: fixed-order partial sums, no atomics.  The totals (sys.EnergyKin = sum of the
+ * components, ...) are the host's. ---- */
+typedef struct
+{
+  int Ti_Current;
+  double Timebase_interval;
+  int ComovingIntegrationOn;
+  double Time;                                    /* All.Time (a1, a2, a3 of global.c:26-36) */
+  double logTimeBegin, logTimeMax;                /* driftfac.c:20 */
+  const double *GravKickTable, *HydroKickTable;   /* host, 1000 entries each; comoving only */
+  int pmgrid;                                     /* PMGRID build: vel += GravPM dt_gravkick_pm */
+  double dt_gravkick_pm;                          /* global.c:96-103, from All.PM_Ti_begstep / endstep */
+  const double *OldPhotonMomentum;                /* VIRTUAL: P[].OldPhotonMomentum [n], host; NULL = absent */
+  double rad_fac;                                 /* C / All.UnitVelocity_in_cm_per_s */
+  const double *Potential;                        /* P[].p.Potential [n], host; NULL = the result of the last
+                                                     ghip_potential */
+} ghip_global_params;
+typedef struct
+{
+  double MassComp[6], EnergyKinComp[6], EnergyPotComp[6], EnergyIntComp[6];
+  double MomentumComp[6][4], AngMomentumComp[6][4], CenterOfMassComp[6][4];   /* [3] stays 0 */
+  double EnergyRadComp;                           /* VIRTUAL: Type 3, Mass != 0 */
+} ghip_global_sums;
+int ghip_global_quantities(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums *out);
 
 /* ---- "next" row N4: sink (black-hole) neighbour passes and the per-particle part of
  * cooling_and_starformation, for the reference's shipped flag bundle (BLACK_HOLES, SWALLOWGAS,
