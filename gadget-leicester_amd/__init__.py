@@ -6,6 +6,7 @@ The directory name contains a hyphen, so import it with
 This module only builds and loads the native libraries; there is NO CPU fallback: every compute
 entry point fails loudly when the HIP library or a GPU is missing.
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -41,9 +42,8 @@ def hipcc_path():
 def build(force=False, verbose=False):
     """Compile libghip.so (HIP, gfx950) and libgadget_force.so (host C mirror) in-tree."""
     hipcc = hipcc_path()
-    hdrs = [os.path.join(CSRC, "ghip_internal.h"), os.path.join(CSRC, "ghip_walk.h"), os.path.join(CSRC, "ghip_timefac.h"),
-            os.path.join(CSRC, "ghip_keys.h"), os.path.join(CSRC, "ghip_walkrec.h"),
-            os.path.join(REPO_DIR, "include", "ghip.h")]
+    # every header triggers a rebuild of every object: a new one cannot be forgotten
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(REPO_DIR, "include", "ghip.h")]
     objs = []
     procs = []
     for src in HIP_SOURCES:

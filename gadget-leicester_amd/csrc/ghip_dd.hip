@@ -32,7 +32,7 @@
 // shard's range or it is "shared" and always descended.
 #include <hipcub/hipcub.hpp>
 
-#include "ghip_internal.h"
+#include "ghip_ngb.h"   // BoxK
 #include "ghip_keys.h"
 
 // tree.hip
@@ -295,6 +295,63 @@ __global__ void k_dd_check_range(int n, const double *__restrict__ x, const doub
 // ---------------------------------------------------------------------------------------------
 // target groups
 // ---------------------------------------------------------------------------------------------
+// minimum of every mn[] and maximum of every mx[] over the 64 lanes (in every lane), all in one butterfly.
+// UNROLL writes its six steps out: the lane offsets become constants, which suits the selection kernel
+// (2 vector registers fewer) and not the group kernels (13 more)
+template <bool UNROLL, int NMIN, int NMAX>
+__device__ __forceinline__ void d_wave_minmax(double (&mn)[NMIN], double (&mx)[NMAX])
+{
+  constexpr int steps = UNROLL ? 6 : 1;
+#pragma unroll steps
+  for(int off = 32; off > 0; off >>= 1)
+    {
+      for(int k = 0; k < NMIN; k++)
+        {
+          const double o = __shfl_xor(mn[k], off, 64);
+          mn[k] = o < mn[k] ? o : mn[k];
+        }
+      for(int k = 0; k < NMAX; k++)
+        {
+          const double o = __shfl_xor(mx[k], off, 64);
+          mx[k] = o > mx[k] ? o : mx[k];
+        }
+    }
+}
+
+// half extent of [lo, hi], rounded up a little: the box must contain every point.  `pad` covers the
+// rounding of the centre: 1e-14 * (|c| + 1e-300) in the group tables, a bare 1e-14 for the chunk boxes
+// of the selection kernel
+__device__ __forceinline__ double d_half_extent(double lo, double hi, double pad)
+{
+  return 0.5 * (hi - lo) * (1 + 1e-12) + pad;
+}
+
+// the table entry of the box [lo, hi]; any = false: an empty group, which no test reaches
+__device__ __forceinline__ DDGroup d_group_of_box(bool any, const double *lo, const double *hi,
+                                                  double amin, double rmax)
+{
+  DDGroup G;
+  if(any)
+    {
+      G.cx = 0.5 * (lo[0] + hi[0]);
+      G.cy = 0.5 * (lo[1] + hi[1]);
+      G.cz = 0.5 * (lo[2] + hi[2]);
+      G.ex = d_half_extent(lo[0], hi[0], 1e-14 * (fabs(G.cx) + 1e-300));
+      G.ey = d_half_extent(lo[1], hi[1], 1e-14 * (fabs(G.cy) + 1e-300));
+      G.ez = d_half_extent(lo[2], hi[2], 1e-14 * (fabs(G.cz) + 1e-300));
+      G.amin = amin;
+      G.rmax = rmax;
+    }
+  else
+    {
+      G.cx = G.cy = G.cz = 0;
+      G.ex = G.ey = G.ez = -1;
+      G.amin = 1e300;
+      G.rmax = 0;
+    }
+  return G;
+}
+
 // one wavefront per group of `gsz` consecutive targets of the curve-ordered list (indices of the
 // gravity tree): positions in tree order, val (OldAcc or Hsml, host order) through perm
 __global__ void __launch_bounds__(64)
@@ -307,67 +364,27 @@ k_dd_groups(int nt, int gsz, const int *__restrict__ tgt, const double *__restri
   const long long a0l = (long long) g * gsz;
   const int a0 = a0l > nt ? nt : (int) a0l;
   int a1 = (a0l + gsz > nt) ? nt : (int) (a0l + gsz);
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-  double vmin = 1e300, vmax = 0;
+  double lo[4] = {1e300, 1e300, 1e300, 1e300}, hi[4] = {-1e300, -1e300, -1e300, 0};   // x, y, z, val
   for(int a = a0 + lane; a < a1; a += 64)
     {
       const int s = tgt[a];
-      const double p[3] = {sx[s], sy[s], sz[s]};
-      const double v = val[perm[s]];
-      for(int k = 0; k < 3; k++)
+      const double p[4] = {sx[s], sy[s], sz[s], val[perm[s]]};
+      for(int k = 0; k < 4; k++)
         {
           lo[k] = p[k] < lo[k] ? p[k] : lo[k];
           hi[k] = p[k] > hi[k] ? p[k] : hi[k];
         }
-      vmin = v < vmin ? v : vmin;
-      vmax = v > vmax ? v : vmax;
     }
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      for(int k = 0; k < 3; k++)
-        {
-          double o = __shfl_xor(lo[k], off, 64);
-          lo[k] = o < lo[k] ? o : lo[k];
-          o = __shfl_xor(hi[k], off, 64);
-          hi[k] = o > hi[k] ? o : hi[k];
-        }
-      double o = __shfl_xor(vmin, off, 64);
-      vmin = o < vmin ? o : vmin;
-      o = __shfl_xor(vmax, off, 64);
-      vmax = o > vmax ? o : vmax;
-    }
+  d_wave_minmax<false>(lo, hi);
   if(lane == 0)
-    {
-      DDGroup G;
-      if(a1 > a0)
-        {
-          G.cx = 0.5 * (lo[0] + hi[0]);
-          G.cy = 0.5 * (lo[1] + hi[1]);
-          G.cz = 0.5 * (lo[2] + hi[2]);
-          // (half extents rounded up a little: the box must contain every target)
-          G.ex = 0.5 * (hi[0] - lo[0]) * (1 + 1e-12) + 1e-14 * (fabs(G.cx) + 1e-300);
-          G.ey = 0.5 * (hi[1] - lo[1]) * (1 + 1e-12) + 1e-14 * (fabs(G.cy) + 1e-300);
-          G.ez = 0.5 * (hi[2] - lo[2]) * (1 + 1e-12) + 1e-14 * (fabs(G.cz) + 1e-300);
-          G.amin = vmin;
-          G.rmax = vmax * margin;
-        }
-      else
-        {
-          G.cx = G.cy = G.cz = 0;
-          G.ex = G.ey = G.ez = -1;
-          G.amin = 1e300;
-          G.rmax = 0;
-        }
-      out[DD_NSUPER + g] = G;
-    }
+    out[DD_NSUPER + g] = d_group_of_box(a1 > a0, lo, hi, lo[3], hi[3] * margin);
 }
 
 // super-group s = union of groups [s*DD_NSUB, (s+1)*DD_NSUB)
 __global__ void __launch_bounds__(64) k_dd_supergroups(DDGroup *__restrict__ tab)
 {
   const int s = blockIdx.x, lane = threadIdx.x;
-  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-  double vmin = 1e300, vmax = 0;
+  double lo[4] = {1e300, 1e300, 1e300, 1e300}, hi[4] = {-1e300, -1e300, -1e300, 0};   // x, y, z, amin / rmax
   if(lane < DD_NSUB)
     {
       const DDGroup G = tab[DD_NSUPER + s * DD_NSUB + lane];
@@ -379,47 +396,13 @@ __global__ void __launch_bounds__(64) k_dd_supergroups(DDGroup *__restrict__ tab
           hi[1] = G.cy + G.ey;
           lo[2] = G.cz - G.ez;
           hi[2] = G.cz + G.ez;
-          vmin = G.amin;
-          vmax = G.rmax;
+          lo[3] = G.amin;
+          hi[3] = G.rmax;
         }
     }
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      for(int k = 0; k < 3; k++)
-        {
-          double o = __shfl_xor(lo[k], off, 64);
-          lo[k] = o < lo[k] ? o : lo[k];
-          o = __shfl_xor(hi[k], off, 64);
-          hi[k] = o > hi[k] ? o : hi[k];
-        }
-      double o = __shfl_xor(vmin, off, 64);
-      vmin = o < vmin ? o : vmin;
-      o = __shfl_xor(vmax, off, 64);
-      vmax = o > vmax ? o : vmax;
-    }
+  d_wave_minmax<false>(lo, hi);
   if(lane == 0)
-    {
-      DDGroup G;
-      if(hi[0] >= lo[0])
-        {
-          G.cx = 0.5 * (lo[0] + hi[0]);
-          G.cy = 0.5 * (lo[1] + hi[1]);
-          G.cz = 0.5 * (lo[2] + hi[2]);
-          G.ex = 0.5 * (hi[0] - lo[0]) * (1 + 1e-12) + 1e-14 * (fabs(G.cx) + 1e-300);
-          G.ey = 0.5 * (hi[1] - lo[1]) * (1 + 1e-12) + 1e-14 * (fabs(G.cy) + 1e-300);
-          G.ez = 0.5 * (hi[2] - lo[2]) * (1 + 1e-12) + 1e-14 * (fabs(G.cz) + 1e-300);
-          G.amin = vmin;
-          G.rmax = vmax;
-        }
-      else
-        {
-          G.cx = G.cy = G.cz = 0;
-          G.ex = G.ey = G.ez = -1;
-          G.amin = 1e300;
-          G.rmax = 0;
-        }
-      tab[s] = G;
-    }
+    tab[s] = d_group_of_box(hi[0] >= lo[0], lo, hi, lo[3], hi[3]);
 }
 
 // target list `tgt` (indices of the gravity tree, curve order).  gas = false: groups carry the least
@@ -487,28 +470,28 @@ struct LetK
 {
   double theta2;     // ErrTolTheta^2 (0: relative criterion)
   double errtol;     // ErrTolForceAcc
-  double boxsize, boxhalf;
-  int periodic, unequal;
+  BoxK b;
+  int unequal;
   int nranks, me;
   int nown;                                   // this rank's own pieces of the curve
   const unsigned long long *ownlo, *ownhi;
 };
 
-// smallest possible squared distance between the point s and any point of the group's box
-// (component-wise, with the nearest image when periodic: forcetree.c:2028-2032)
-__device__ __forceinline__ double d_box_r2min(const DDGroup &G, double sx, double sy, double sz,
-                                              const LetK &K)
+// squared distance between the box (c +- e; e = 0: a point) and the group's box, component-wise, with
+// the nearest image when periodic (forcetree.c:2028-2032)
+__device__ __forceinline__ double d_group_box_dist2(const DDGroup &G, double cx, double cy, double cz, double ex,
+                                                    double ey, double ez, const BoxK &b)
 {
-  double d0 = sx - G.cx, d1 = sy - G.cy, d2 = sz - G.cz;
-  if(K.periodic)
+  double d0 = cx - G.cx, d1 = cy - G.cy, d2 = cz - G.cz;
+  if(b.periodic)
     {
-      d0 = d_nearest(d0, K.boxsize, K.boxhalf);
-      d1 = d_nearest(d1, K.boxsize, K.boxhalf);
-      d2 = d_nearest(d2, K.boxsize, K.boxhalf);
+      d0 = d_nearest(d0, b.boxsize, b.boxhalf);
+      d1 = d_nearest(d1, b.boxsize, b.boxhalf);
+      d2 = d_nearest(d2, b.boxsize, b.boxhalf);
     }
-  d0 = fabs(d0) - G.ex;
-  d1 = fabs(d1) - G.ey;
-  d2 = fabs(d2) - G.ez;
+  d0 = fabs(d0) - G.ex - ex;
+  d1 = fabs(d1) - G.ey - ey;
+  d2 = fabs(d2) - G.ez - ez;
   d0 = d0 > 0 ? d0 : 0;
   d1 = d1 > 0 ? d1 : 0;
   d2 = d2 > 0 ? d2 : 0;
@@ -524,7 +507,7 @@ __device__ __forceinline__ bool d_group_can_open(const DDGroup &G, const double4
   if(G.ex < 0)
     return false;
   const double slack = 1.0 - 1.0e-9;
-  const double r2 = d_box_r2min(G, xm.x, xm.y, xm.z, K) * slack;
+  const double r2 = d_group_box_dist2(G, xm.x, xm.y, xm.z, 0, 0, 0, K.b) * slack;
   const double len = cl.w;
   if(K.theta2 != 0)
     {
@@ -699,9 +682,7 @@ k_selm_count(int n, int nranks, const unsigned long long *__restrict__ mask, int
     {
       const int a = base + j * 64 + lane;
       const unsigned long long m = a < n ? mask[a] : 0ULL;
-      unsigned long long any = m;
-      for(int off = 32; off > 0; off >>= 1)
-        any |= __shfl_xor(any, off, 64);
+      unsigned long long any = d_wave_or_u64(m);
       while(any)
         {
           const int b = __builtin_ctzll(any);
@@ -760,9 +741,7 @@ k_selm_scatter(int n, int nranks, const unsigned long long *__restrict__ mask, i
     {
       const int a = base + j * 64 + lane;
       const unsigned long long m = a < n ? mask[a] : 0ULL;
-      unsigned long long any = m;
-      for(int off = 32; off > 0; off >>= 1)
-        any |= __shfl_xor(any, off, 64);
+      unsigned long long any = d_wave_or_u64(m);
       while(any)
         {
           const int b = __builtin_ctzll(any);
@@ -852,126 +831,123 @@ __global__ void k_let_pack(int nrec, const int *__restrict__ list, const int4 *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// SPH: ghost selection
+// which ranks does an item (a gas particle as a ghost, a dust grain) concern?
 // ---------------------------------------------------------------------------------------------
-struct GhostK
-{
-  double boxsize, boxhalf, margin;
-  int periodic, nranks, me;
+// Reach: the distance within which an item of radius h -- or a chunk of items, the largest of radius h --
+// concerns a group
+struct GhostReach   // a gas particle: it can be a neighbour of a target of the group (r < the group's padded
+{                   // search radius), or a target can lie inside ITS smoothing sphere (hydra.c:1266)
+  __device__ static double radius(const DDGroup &G, double h) { return G.rmax > h ? G.rmax : h; }
+};
+struct SphereReach  // a dust grain: every particle of the group lies in its box, and a neighbour of a grain is
+{                   // closer than h (u = r / h < 1), so a group farther than h from the sphere's box holds none
+  __device__ static double radius(const DDGroup &, double h) { return h; }
 };
 
-// gas particle (x, h): can it be a neighbour of a target in the group (r < padded search radius of
-// the group), or can one of the group's targets lie inside ITS smoothing sphere (hydra.c:1266)?
-__device__ __forceinline__ bool d_group_needs(const DDGroup &G, double x, double y, double z, double hj,
-                                              const GhostK &K)
+// does the box (c +- e; e = 0: one item) with radius h come within reach of the group?  (1e-9: rounding slack)
+template <class Reach>
+__device__ __forceinline__ bool d_group_reached(const DDGroup &G, double cx, double cy, double cz, double ex,
+                                                double ey, double ez, double h, const BoxK &b)
 {
   if(G.ex < 0)
     return false;
-  double d0 = x - G.cx, d1 = y - G.cy, d2 = z - G.cz;
-  if(K.periodic)
-    {
-      d0 = d_nearest(d0, K.boxsize, K.boxhalf);
-      d1 = d_nearest(d1, K.boxsize, K.boxhalf);
-      d2 = d_nearest(d2, K.boxsize, K.boxhalf);
-    }
-  d0 = fabs(d0) - G.ex;
-  d1 = fabs(d1) - G.ey;
-  d2 = fabs(d2) - G.ez;
-  d0 = d0 > 0 ? d0 : 0;
-  d1 = d1 > 0 ? d1 : 0;
-  d2 = d2 > 0 ? d2 : 0;
-  const double R = (G.rmax > hj ? G.rmax : hj) * (1.0 + 1.0e-9);
-  return d0 * d0 + d1 * d1 + d2 * d2 < R * R;
+  const double r2 = d_group_box_dist2(G, cx, cy, cz, ex, ey, ez, b);
+  const double R = Reach::radius(G, h) * (1.0 + 1.0e-9);
+  return r2 < R * R;
 }
 
-// distance test between a chunk of particles (box c +- e, largest padded radius hmax) and a group's box
-__device__ __forceinline__ bool d_group_near_box(const DDGroup &G, double cx, double cy, double cz,
-                                                 double ex, double ey, double ez, double hmax,
-                                                 const GhostK &K)
+// Src: where item t of the list comes from -- its mask slot i (the local particle index), position and radius
+struct GhostSrc   // local gas particles as indices `src` of the gravity tree; h is padded by the ghost margin,
+{                 // and the h a ghost was selected with is kept in h0 (by the chunk's first workgroup)
+  const int *src, *perm;
+  const double *sx, *sy, *sz, *hsml;
+  double margin;
+  double *h0;
+  __device__ __forceinline__ void load(int t, bool first, int &i, double &x, double &y, double &z, double &h) const
+  {
+    const int s = src[t];
+    i = perm[s];
+    x = sx[s];
+    y = sy[s];
+    z = sz[s];
+    const double hi = hsml[i];
+    h = hi * margin;
+    if(first)
+      h0[i] = hi;
+  }
+};
+struct DustSrc   // the grains of a dust pass: list slots `ord` in tree order, local indices `idx`
 {
-  if(G.ex < 0)
-    return false;
-  double d0 = cx - G.cx, d1 = cy - G.cy, d2 = cz - G.cz;
-  if(K.periodic)
+  const int *ord, *idx;
+  int n;
+  const double *pos, *hsml;
+  __device__ __forceinline__ void load(int t, bool, int &i, double &x, double &y, double &z, double &h) const
+  {
+    i = idx[ord[t]];
+    x = pos[i];
+    y = pos[(size_t) n + i];
+    z = pos[2 * (size_t) n + i];
+    h = hsml[i];
+  }
+};
+
+// bounding box of the valid lanes' positions around lane 0's (nearest-image offsets: a chunk is compact,
+// the box may straddle the periodic boundary) and their largest radius (h = 0 in the other lanes)
+struct ChunkBox
+{
+  double cx, cy, cz, ex, ey, ez, hmax;
+};
+__device__ __forceinline__ ChunkBox d_chunk_box(bool valid, double px, double py, double pz, double h,
+                                                const BoxK &b)
+{
+  const double rx = __shfl(px, 0, 64), ry = __shfl(py, 0, 64), rz = __shfl(pz, 0, 64);
+  double ox = valid ? px - rx : 0, oy = valid ? py - ry : 0, oz = valid ? pz - rz : 0;
+  if(b.periodic)
     {
-      d0 = d_nearest(d0, K.boxsize, K.boxhalf);
-      d1 = d_nearest(d1, K.boxsize, K.boxhalf);
-      d2 = d_nearest(d2, K.boxsize, K.boxhalf);
+      ox = d_nearest(ox, b.boxsize, b.boxhalf);
+      oy = d_nearest(oy, b.boxsize, b.boxhalf);
+      oz = d_nearest(oz, b.boxsize, b.boxhalf);
     }
-  d0 = fabs(d0) - G.ex - ex;
-  d1 = fabs(d1) - G.ey - ey;
-  d2 = fabs(d2) - G.ez - ez;
-  d0 = d0 > 0 ? d0 : 0;
-  d1 = d1 > 0 ? d1 : 0;
-  d2 = d2 > 0 ? d2 : 0;
-  const double R = (G.rmax > hmax ? G.rmax : hmax) * (1.0 + 1.0e-9);
-  return d0 * d0 + d1 * d1 + d2 * d2 < R * R;
+  double lo[3] = {ox, oy, oz}, hi[4] = {ox, oy, oz, h};
+  d_wave_minmax<true>(lo, hi);
+  ChunkBox C;
+  C.hmax = hi[3];
+  C.cx = rx + 0.5 * (lo[0] + hi[0]);
+  C.cy = ry + 0.5 * (lo[1] + hi[1]);
+  C.cz = rz + 0.5 * (lo[2] + hi[2]);
+  C.ex = d_half_extent(lo[0], hi[0], 1e-14);
+  C.ey = d_half_extent(lo[1], hi[1], 1e-14);
+  C.ez = d_half_extent(lo[2], hi[2], 1e-14);
+  return C;
 }
 
-// One wavefront per (chunk of 64 local gas particles that are neighbours in the gravity tree's
-// (Morton) order, destination rank) -- `src` lists the particles as indices of that tree.  The chunk's
-// bounding box is tested against the 64 super-groups of the rank by the 64 lanes at once; only for
-// the super-groups it comes near are the 16 groups staged through LDS and every lane tests its own
-// particle against the near ones.  Interior chunks -- nearly all of them -- cost one box test.
-// mask[] must be zero on entry; the ranks' bits are OR-ed in.
+// One wavefront per (chunk of 64 items that are neighbours in the gravity tree's (Morton) order,
+// destination rank).  The chunk's bounding box is tested against the 64 super-groups of the rank by the
+// 64 lanes at once; only for the super-groups it comes near are the 16 groups staged through LDS and
+// every lane tests its own item against the near ones.  Interior chunks -- nearly all of them -- cost
+// one box test.  mask[] (by local particle index) must be zero on entry for the items; the ranks' bits
+// are OR-ed in.
+template <class Src, class Reach>
 __global__ void __launch_bounds__(64)
-k_ghost_select(int nsrc, const int *__restrict__ src, const int *__restrict__ perm,
-               const double *__restrict__ sx, const double *__restrict__ sy,
-               const double *__restrict__ sz, const double *__restrict__ h,
-               const DDGroup *__restrict__ groups, GhostK K, unsigned long long *__restrict__ mask,
-               double *__restrict__ h0)
+k_dd_select(int nitem, Src S, const DDGroup *__restrict__ groups, BoxK bx, int nranks, int me,
+            unsigned long long *__restrict__ mask)
 {
   __shared__ DDGroup sh[DD_NSUB];
   const int lane = threadIdx.x;
-  const int nd = K.nranks - 1;                   // destinations per chunk
+  const int nd = nranks - 1;                     // destinations per chunk
   const int chunk = blockIdx.x / nd;
   int b = blockIdx.x - chunk * nd;
-  if(b >= K.me)
+  if(b >= me)
     b++;                                         // skip this rank itself
-  const int a = chunk * 64 + lane;
-  const bool valid = a < nsrc;
+  const int t = chunk * 64 + lane;
+  const bool valid = t < nitem;
   int i = 0;
-  double px = 0, py = 0, pz = 0, hj = 0;
+  double px = 0, py = 0, pz = 0, h = 0;
   if(valid)
-    {
-      const int s = src[a];
-      i = perm[s];
-      px = sx[s];
-      py = sy[s];
-      pz = sz[s];
-      hj = h[i] * K.margin;
-      if(blockIdx.x == chunk * nd)
-        h0[i] = h[i];
-    }
-  // chunk box around lane 0's particle (nearest-image offsets: a chunk is compact, the box may
-  // straddle the periodic boundary)
-  const double rx = __shfl(px, 0, 64), ry = __shfl(py, 0, 64), rz = __shfl(pz, 0, 64);
-  double ox = valid ? px - rx : 0, oy = valid ? py - ry : 0, oz = valid ? pz - rz : 0;
-  if(K.periodic)
-    {
-      ox = d_nearest(ox, K.boxsize, K.boxhalf);
-      oy = d_nearest(oy, K.boxsize, K.boxhalf);
-      oz = d_nearest(oz, K.boxsize, K.boxhalf);
-    }
-  double lo[3] = {ox, oy, oz}, hi[3] = {ox, oy, oz}, hm = hj;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      for(int k = 0; k < 3; k++)
-        {
-          double o = __shfl_xor(lo[k], off, 64);
-          lo[k] = o < lo[k] ? o : lo[k];
-          o = __shfl_xor(hi[k], off, 64);
-          hi[k] = o > hi[k] ? o : hi[k];
-        }
-      const double o = __shfl_xor(hm, off, 64);
-      hm = o > hm ? o : hm;
-    }
-  const double cx = rx + 0.5 * (lo[0] + hi[0]), cy = ry + 0.5 * (lo[1] + hi[1]),
-               cz = rz + 0.5 * (lo[2] + hi[2]);
-  const double ex = 0.5 * (hi[0] - lo[0]) * (1 + 1e-12) + 1e-14, ey = 0.5 * (hi[1] - lo[1]) * (1 + 1e-12) + 1e-14,
-               ez = 0.5 * (hi[2] - lo[2]) * (1 + 1e-12) + 1e-14;
+    S.load(t, blockIdx.x == chunk * nd, i, px, py, pz, h);
+  const ChunkBox C = d_chunk_box(valid, px, py, pz, h, bx);
   const DDGroup *tab = groups + (size_t) b * DD_STRIDE;
-  unsigned long long sm = __ballot(d_group_near_box(tab[lane], cx, cy, cz, ex, ey, ez, hm, K));
+  unsigned long long sm = __ballot(d_group_reached<Reach>(tab[lane], C.cx, C.cy, C.cz, C.ex, C.ey, C.ez, C.hmax, bx));
   bool need = false;
   while(sm)
     {
@@ -983,7 +959,7 @@ k_ghost_select(int nsrc, const int *__restrict__ src, const int *__restrict__ pe
         {
           const DDGroup G = tab[DD_NSUPER + sg * DD_NSUB + lane];
           sh[lane] = G;
-          near = d_group_near_box(G, cx, cy, cz, ex, ey, ez, hm, K);
+          near = d_group_reached<Reach>(G, C.cx, C.cy, C.cz, C.ex, C.ey, C.ez, C.hmax, bx);
         }
       unsigned long long qm = __ballot(near);
       __syncthreads();
@@ -991,16 +967,19 @@ k_ghost_select(int nsrc, const int *__restrict__ src, const int *__restrict__ pe
         {
           const int q = __builtin_ctzll(qm);
           qm &= qm - 1;
-          if(valid && !need && d_group_needs(sh[q], px, py, pz, hj, K))
+          if(valid && !need && d_group_reached<Reach>(sh[q], px, py, pz, 0, 0, 0, h, bx))
             need = true;
         }
       if(__ballot(valid && !need) == 0)
-        break;   // every particle of the chunk is a ghost there already
+        break;   // every item of the chunk goes there already
     }
   if(need)
     atomicOr(mask + i, 1ULL << b);
 }
 
+// ---------------------------------------------------------------------------------------------
+// SPH: the ghost records
+// ---------------------------------------------------------------------------------------------
 // GhostRec of local gas particle i (host order): the two records of the SPH kernels
 // (ghip_tree.hip k_gather_gas)
 __global__ void k_ghost_pack(int nrec, const int *__restrict__ list, int n, int ngas,
@@ -1068,11 +1047,7 @@ __global__ void k_ghost_growth(int nt, const int *__restrict__ tgt, const int *_
       const double hm = right[s] > hcur[s] ? right[s] : hcur[s];
       r = hm / h0[perm[s]];
     }
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      double o = __shfl_xor(r, off, 64);
-      r = o > r ? o : r;
-    }
+  r = d_wave_max_f64(r);
   if((threadIdx.x & 63) == 0 && r > 0)
     atomicMax(out, (unsigned long long) __double_as_longlong(r));   // positive doubles order like integers
 }
@@ -1122,122 +1097,6 @@ int ghip_dd_dust_groups(ghip_ctx *ctx)
   return 1;
 }
 
-// squared distance between the box (c +- e) and the group's box, nearest image when periodic
-__device__ __forceinline__ double d_group_box_dist2(const DDGroup &G, double cx, double cy, double cz, double ex,
-                                                    double ey, double ez, const GhostK &K)
-{
-  double d0 = cx - G.cx, d1 = cy - G.cy, d2 = cz - G.cz;
-  if(K.periodic)
-    {
-      d0 = d_nearest(d0, K.boxsize, K.boxhalf);
-      d1 = d_nearest(d1, K.boxsize, K.boxhalf);
-      d2 = d_nearest(d2, K.boxsize, K.boxhalf);
-    }
-  d0 = fabs(d0) - G.ex - ex;
-  d1 = fabs(d1) - G.ey - ey;
-  d2 = fabs(d2) - G.ez - ez;
-  d0 = d0 > 0 ? d0 : 0;
-  d1 = d1 > 0 ? d1 : 0;
-  d2 = d2 > 0 ? d2 : 0;
-  return d0 * d0 + d1 * d1 + d2 * d2;
-}
-
-// Can a sphere of radius h inside the box (c +- e) reach a particle of the group?  Every particle of
-// the group lies in its box, and a neighbour of a grain is closer than h (u = r / h < 1), so a group
-// farther than h from every point of the sphere's box holds none.  (1e-9: rounding slack.)
-__device__ __forceinline__ bool d_sphere_reaches(const DDGroup &G, double cx, double cy, double cz, double ex,
-                                                 double ey, double ez, double h, const GhostK &K)
-{
-  if(G.ex < 0)
-    return false;
-  const double R = h * (1.0 + 1.0e-9);
-  return d_group_box_dist2(G, cx, cy, cz, ex, ey, ez, K) < R * R;
-}
-
-// One wavefront per (chunk of 64 grains in gravity-tree order, destination rank), as k_ghost_select:
-// the chunk's box (padded by its largest h) against the rank's 64 super-groups, then each lane's own
-// sphere against the groups of the near super-groups.  mask [n] (by local particle index) must be
-// zero on entry for the grains; the ranks' bits are OR-ed in.
-__global__ void __launch_bounds__(64)
-k_dust_select(int nd, const int *__restrict__ ord, const int *__restrict__ idx, int n,
-              const double *__restrict__ pos, const double *__restrict__ hsml,
-              const DDGroup *__restrict__ groups, GhostK K, unsigned long long *__restrict__ mask)
-{
-  __shared__ DDGroup sh[DD_NSUB];
-  const int lane = threadIdx.x;
-  const int ndst = K.nranks - 1;
-  const int chunk = blockIdx.x / ndst;
-  int b = blockIdx.x - chunk * ndst;
-  if(b >= K.me)
-    b++;
-  const int t = chunk * 64 + lane;
-  const bool valid = t < nd;
-  int i = 0;
-  double px = 0, py = 0, pz = 0, h = 0;
-  if(valid)
-    {
-      i = idx[ord[t]];
-      px = pos[i];
-      py = pos[(size_t) n + i];
-      pz = pos[2 * (size_t) n + i];
-      h = hsml[i];
-    }
-  const double rx = __shfl(px, 0, 64), ry = __shfl(py, 0, 64), rz = __shfl(pz, 0, 64);
-  double ox = valid ? px - rx : 0, oy = valid ? py - ry : 0, oz = valid ? pz - rz : 0;
-  if(K.periodic)
-    {
-      ox = d_nearest(ox, K.boxsize, K.boxhalf);
-      oy = d_nearest(oy, K.boxsize, K.boxhalf);
-      oz = d_nearest(oz, K.boxsize, K.boxhalf);
-    }
-  double lo[3] = {ox, oy, oz}, hi[3] = {ox, oy, oz}, hm = h;
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      for(int k = 0; k < 3; k++)
-        {
-          double o = __shfl_xor(lo[k], off, 64);
-          lo[k] = o < lo[k] ? o : lo[k];
-          o = __shfl_xor(hi[k], off, 64);
-          hi[k] = o > hi[k] ? o : hi[k];
-        }
-      const double o = __shfl_xor(hm, off, 64);
-      hm = o > hm ? o : hm;
-    }
-  const double cx = rx + 0.5 * (lo[0] + hi[0]), cy = ry + 0.5 * (lo[1] + hi[1]),
-               cz = rz + 0.5 * (lo[2] + hi[2]);
-  const double ex = 0.5 * (hi[0] - lo[0]) * (1 + 1e-12) + 1e-14, ey = 0.5 * (hi[1] - lo[1]) * (1 + 1e-12) + 1e-14,
-               ez = 0.5 * (hi[2] - lo[2]) * (1 + 1e-12) + 1e-14;
-  const DDGroup *tab = groups + (size_t) b * DD_STRIDE;
-  unsigned long long sm = __ballot(d_sphere_reaches(tab[lane], cx, cy, cz, ex, ey, ez, hm, K));
-  bool need = false;
-  while(sm)
-    {
-      const int sg = __builtin_ctzll(sm);
-      sm &= sm - 1;
-      __syncthreads();
-      bool near = false;
-      if(lane < DD_NSUB)
-        {
-          const DDGroup G = tab[DD_NSUPER + sg * DD_NSUB + lane];
-          sh[lane] = G;
-          near = d_sphere_reaches(G, cx, cy, cz, ex, ey, ez, hm, K);
-        }
-      unsigned long long qm = __ballot(near);
-      __syncthreads();
-      while(qm)
-        {
-          const int q = __builtin_ctzll(qm);
-          qm &= qm - 1;
-          if(valid && !need && d_sphere_reaches(sh[q], px, py, pz, 0, 0, 0, h, K))
-            need = true;
-        }
-      if(__ballot(valid && !need) == 0)
-        break;   // every grain of the chunk goes there already
-    }
-  if(need)
-    atomicOr(mask + i, 1ULL << b);
-}
-
 // after the all-gather of the group tables: the destinations of this shard's nd grains (ord: list slots
 // in tree order, idx: local indices, both on the device), the per-destination lists of their local
 // indices in ascending order (D.du_list, D.du_scount / du_soff), the total
@@ -1256,16 +1115,9 @@ int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord,
     return GHIP_OK;
   GCHK(ghip_ensure(ctx, D.du_mask, (size_t) n * 8));
   HIPCHK(hipMemsetAsync(D.du_mask.p, 0, (size_t) n * 8, st));
-  GhostK K;
-  K.boxsize = boxsize;
-  K.boxhalf = 0.5 * boxsize;
-  K.periodic = periodic;
-  K.margin = 1.0;
-  K.nranks = P_;
-  K.me = D.rank;
-  k_dust_select<<<cdiv(nd, 64) * (P_ - 1), 64, 0, st>>>(nd, ord, idx, n, P<double>(ctx->f[GHIP_F_POS]),
-                                                       P<double>(ctx->f[GHIP_F_HSML]), P<DDGroup>(D.grp_all), K,
-                                                       P<unsigned long long>(D.du_mask));
+  const DustSrc S = {ord, idx, n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML])};
+  k_dd_select<DustSrc, SphereReach><<<cdiv(nd, 64) * (P_ - 1), 64, 0, st>>>(
+    nd, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(D.du_mask));
   HIPCHK(hipGetLastError());
   return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
 }
@@ -1318,9 +1170,7 @@ static int gravity_step(ghip_ctx *ctx)
           LetK K;
           K.theta2 = D.gp.ErrTolTheta * D.gp.ErrTolTheta;
           K.errtol = D.gp.ErrTolForceAcc;
-          K.boxsize = D.gp.BoxSize;
-          K.boxhalf = 0.5 * D.gp.BoxSize;
-          K.periodic = D.gp.periodic;
+          K.b = make_box(D.gp.BoxSize, D.gp.periodic);
           K.unequal = D.gp.unequal_softenings || ctx->adaptive_gravsoft;
           K.nranks = P_;
           K.me = D.rank;
@@ -1437,13 +1287,6 @@ static int density_step(ghip_ctx *ctx)
       if(ng > 0 && P_ > 1)
         {
           GCHK(ghip_ensure(ctx, D.gh_mask, (size_t) ng * 8));
-          GhostK K;
-          K.boxsize = D.dp.BoxSize;
-          K.boxhalf = 0.5 * D.dp.BoxSize;
-          K.periodic = D.dp.periodic;
-          K.margin = D.gh_margin_cur;
-          K.nranks = P_;
-          K.me = D.rank;
           // the local gas particles in the gravity tree's order (chunks of 64 are compact)
           const int nsrc = ctx->gt.n;
           GCHK(ghip_ensure(ctx, D.sendm, (size_t) nsrc * 8));
@@ -1455,10 +1298,11 @@ static int density_step(ghip_ctx *ctx)
             return ghip_fail(ctx, GHIP_EINVAL, "ghost selection: %d of %d gas particles in the tree",
                              nfound, ng);
           HIPCHK(hipMemsetAsync(D.gh_mask.p, 0, (size_t) ng * 8, st));
-          k_ghost_select<<<cdiv(ng, 64) * (P_ - 1), 64, 0, st>>>(
-            ng, P<int>(D.gas_src), P<int>(ctx->gt.perm), P<double>(ctx->sx), P<double>(ctx->sy),
-            P<double>(ctx->sz), P<double>(ctx->f[GHIP_F_HSML]), P<DDGroup>(D.grp_all), K,
-            P<unsigned long long>(D.gh_mask), P<double>(D.h0));
+          const GhostSrc S = {P<int>(D.gas_src), P<int>(ctx->gt.perm), P<double>(ctx->sx), P<double>(ctx->sy),
+                              P<double>(ctx->sz), P<double>(ctx->f[GHIP_F_HSML]), D.gh_margin_cur, P<double>(D.h0)};
+          k_dd_select<GhostSrc, GhostReach><<<cdiv(ng, 64) * (P_ - 1), 64, 0, st>>>(
+            ng, S, P<DDGroup>(D.grp_all), make_box(D.dp.BoxSize, D.dp.periodic), P_, D.rank,
+            P<unsigned long long>(D.gh_mask));
           HIPCHK(hipGetLastError());
           GCHK(multi_select(ctx, ng, P<unsigned long long>(D.gh_mask), D.gh_list, D.gh_scount,
                             D.gh_soff, &total));

@@ -23,15 +23,8 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "ghip_internal.h"
+#include "ghip_ngb.h"
 
-#define DUST_KERNEL_COEFF_1 2.546479089470
-#define DUST_KERNEL_COEFF_2 15.278874536822
-#define DUST_KERNEL_COEFF_5 5.092958178941
-#define DUST_FACT1 0.366025403785   // allvars.h:310
-#define DUST_GAMMA (7. / 5.)        // allvars.h:64
-#define DUST_GAMMA_MINUS1 (DUST_GAMMA - 1)
-#define DUST_PROTONMASS 1.6726e-24  // allvars.h:89
 #define DUST_RHO_GRAIN 3.           // rho_dust, dust.c:379
 #define DUST_LEAF 16                // a tree node with at most this many particles is swept flat
 
@@ -52,140 +45,27 @@ enum
 #define DUST_NIN (DP_VCOLL + 1)       // planes uploaded
 #define DUST_NOUT (DUST_NPLANES - DP_D9)   // planes read back: d9, vcoll, dmom, dE
 
-struct DustBox
-{
-  double boxsize, boxhalf;
-  int periodic;
-};
-
 struct DustK
 {
-  DustBox b;
+  BoxK b;
   double dt_fac, dt_fac_gas, minegy, meanweight, ulength, umass, udens, uvel;
 };
-
-struct __attribute__((aligned(64))) DustSphNode   // = SphNode of ghip_sph.hip
-{
-  double cx, cy, cz, len;
-  double hmax;
-  int skip, pidx, pstart, pcount;
-  int pad[2];
-};
-
-__device__ __forceinline__ double d_dust_wrap(double d, const DustBox &b)
-{
-  if(b.periodic)
-    {
-      if(d > b.boxhalf)
-        d -= b.boxsize;
-      if(d < -b.boxhalf)
-        d += b.boxsize;
-    }
-  return d;
-}
-
-// node test of ngb_treefind_dust_active (dust.c:1303-1313)
-__device__ __forceinline__ bool d_dust_overlaps(double cx, double cy, double cz, double len, double h,
-                                                double px, double py, double pz, const DustBox &b)
-{
-  double dist = h + 0.5 * len;
-  double dx = d_ngb_periodic(cx - px, b.periodic, b.boxsize, b.boxhalf);
-  if(dx > dist)
-    return false;
-  double dy = d_ngb_periodic(cy - py, b.periodic, b.boxsize, b.boxhalf);
-  if(dy > dist)
-    return false;
-  double dz = d_ngb_periodic(cz - pz, b.periodic, b.boxsize, b.boxhalf);
-  if(dz > dist)
-    return false;
-  dist += DUST_FACT1 * len;
-  return !(dx * dx + dy * dy + dz * dz > dist * dist);
-}
 
 // the neighbour test and kernel weight of dust_evaluate_density / _select (dust.c:826-847, 971-983):
 // r <= h from the tree search, then u = r / h < 1.  Returns false for a non-neighbour.
 __device__ __forceinline__ bool d_dust_weight(double px, double py, double pz, double qx, double qy,
-                                              double qz, double h, const DustBox &b, double &wk)
+                                              double qz, double h, const BoxK b, double &wk)
 {
-  const double dx = d_dust_wrap(px - qx, b), dy = d_dust_wrap(py - qy, b), dz = d_dust_wrap(pz - qz, b);
+  const double dx = d_wrap(px - qx, b), dy = d_wrap(py - qy, b), dz = d_wrap(pz - qz, b);
   const double r2 = dx * dx + dy * dy + dz * dz;
   if(r2 > h * h)
     return false;
   const double u = sqrt(r2) / h;
   if(!(u < 1))
     return false;
-  const double hinv = 1 / h, hinv3 = hinv * hinv * hinv;
-  if(u < 0.5)
-    wk = hinv3 * (DUST_KERNEL_COEFF_1 + DUST_KERNEL_COEFF_2 * (u - 1) * u * u);
-  else
-    wk = hinv3 * DUST_KERNEL_COEFF_5 * (1.0 - u) * (1.0 - u) * (1.0 - u);
+  const double hinv = 1 / h;
+  wk = d_spline_wk(u, hinv * hinv * hinv);
   return true;
-}
-
-// one thread's walk of the gravity tree (all types) around (px, py, pz) with radius h; f(p) for every
-// candidate p (sorted index) that the node tests let through
-template <class F>
-__device__ __forceinline__ void d_dust_walk_grav(double px, double py, double pz, double h, int nelem,
-                                                 const int4 *__restrict__ lk, const double4 *__restrict__ cl,
-                                                 const DustBox &b, F &&f)
-{
-  int e = 0;
-  while(e < nelem)
-    {
-      const int4 k = lk[e];
-      if(k.y >= 0)
-        {
-          f(k.y);
-          e = e + 1;
-          continue;
-        }
-      const double4 c = cl[e];
-      if(!d_dust_overlaps(c.x, c.y, c.z, c.w, h, px, py, pz, b))
-        {
-          e = k.x;
-          continue;
-        }
-      if(k.w > DUST_LEAF)
-        {
-          e = e + 1;
-          continue;
-        }
-      for(int p = k.z; p < k.z + k.w; p++)
-        f(p);
-      e = k.x;
-    }
-}
-
-// the same over the gas tree (SphNode records; gas particles only)
-template <class F>
-__device__ __forceinline__ void d_dust_walk_gas(double px, double py, double pz, double h, int nelem,
-                                                const DustSphNode *__restrict__ nodes, const DustBox &b,
-                                                F &&f)
-{
-  int e = 0;
-  while(e < nelem)
-    {
-      const DustSphNode &N = nodes[e];
-      if(N.pidx >= 0)
-        {
-          f(N.pidx);
-          e = e + 1;
-          continue;
-        }
-      if(!d_dust_overlaps(N.cx, N.cy, N.cz, N.len, h, px, py, pz, b))
-        {
-          e = N.skip;
-          continue;
-        }
-      if(N.pcount > DUST_LEAF)
-        {
-          e = e + 1;
-          continue;
-        }
-      for(int p = N.pstart; p < N.pstart + N.pcount; p++)
-        f(p);
-      e = N.skip;
-    }
 }
 
 // Where a grain of a launch comes from: this shard's list (a local particle: position and h from the
@@ -247,7 +127,7 @@ __global__ void __launch_bounds__(64)
 k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__restrict__ pos,
                const double *__restrict__ mass, const int *__restrict__ type, int nelem,
                const int4 *__restrict__ lk, const double4 *__restrict__ cl, const int *__restrict__ perm,
-               DustBox b, double *__restrict__ out)
+               BoxK b, double *__restrict__ out)
 {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= nd)
@@ -256,7 +136,7 @@ k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__
   double px, py, pz, h, mi;
   g.get(a, px, py, pz, h, mi);
   double rho = 0;
-  d_dust_walk_grav(px, py, pz, h, nelem, lk, cl, b, [&](int p) {
+  d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
     const int j = perm[p];
     if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
       return;
@@ -281,7 +161,7 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
   const int tb = timebin[i];
   const double dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac;
   const double rho = PL(DP_RHO);
-  const double soundspeed = sqrt(8. / M_PI * PL(DP_ENT) * pow(rho, DUST_GAMMA_MINUS1));
+  const double soundspeed = sqrt(8. / M_PI * PL(DP_ENT) * pow(rho, GAMMA_MINUS1));
   double v[3], gv[3], g[3];
   for(int k = 0; k < 3; k++)
     {
@@ -311,7 +191,7 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
   if(dt > 0)   // dust.c:385-444
     {
       const double R = PL(DP_RAD);
-      const double lambda_h2 = K.meanweight * DUST_PROTONMASS / (K.udens * rho) / 1.e-15 / K.ulength;
+      const double lambda_h2 = K.meanweight * PROTONMASS / (K.udens * rho) / 1.e-15 / K.ulength;
       const double rey = 6 * delta_vel * R / K.ulength / (lambda_h2 * soundspeed);
       double ts;
       if(3. / 2 * lambda_h2 * K.ulength >= R)   // Epstein
@@ -358,8 +238,8 @@ template <int fill, class G>
 __global__ void __launch_bounds__(64)
 k_dust_pairs(int nd, const int *__restrict__ ord, G g, int obase, int n, int ngas,
              const double *__restrict__ pos, const double *__restrict__ mass, const int *__restrict__ type,
-             const int *__restrict__ timebin, int nelem, const DustSphNode *__restrict__ nodes,
-             const int *__restrict__ perm, DustBox b, long long *__restrict__ cnt,
+             const int *__restrict__ timebin, int nelem, const SphNode *__restrict__ nodes,
+             const int *__restrict__ perm, BoxK b, long long *__restrict__ cnt,
              const long long *__restrict__ off, unsigned long long *__restrict__ key,
              double *__restrict__ wgt)
 {
@@ -373,7 +253,7 @@ k_dust_pairs(int nd, const int *__restrict__ ord, G g, int obase, int n, int nga
   if(grho > 0.)
     {
       const long long o = fill ? off[a] : 0;
-      d_dust_walk_gas(px, py, pz, h, nelem, nodes, b, [&](int p) {
+      d_ngb_walk_thread<DUST_LEAF>(GasElems{nodes}, nelem, px, py, pz, h, b, [&](int p) {
         const int j = perm[p];
         if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0) || timebin[j] == 0)
           return;
@@ -420,7 +300,7 @@ __global__ void k_dust_apply(long long npairs, const unsigned long long *__restr
       v0 -= w[(size_t) DP_DMOM * D + a] / density * wk;
       v1 -= w[(size_t) (DP_DMOM + 1) * D + a] / density * wk;
       v2 -= w[(size_t) (DP_DMOM + 2) * D + a] / density * wk;
-      double u_old = A / DUST_GAMMA_MINUS1 * pow(density, DUST_GAMMA_MINUS1);
+      double u_old = A / GAMMA_MINUS1 * pow(density, GAMMA_MINUS1);
       if(K.minegy > u_old)   // DMAX(All.MinEgySpec, ...), allvars.h:273
         u_old = K.minegy;
       const double u_new = u_old + E * wk / density;
@@ -516,19 +396,10 @@ __global__ void k_dust_combine(int nd, int nimp, const double *__restrict__ w, c
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static DustBox dust_box(const ghip_dust_params *p)
-{
-  DustBox b;
-  b.boxsize = p->BoxSize;
-  b.boxhalf = 0.5 * p->BoxSize;
-  b.periodic = p->periodic;
-  return b;
-}
-
 static DustK dust_k(const ghip_dust_params *p)
 {
   DustK K;
-  K.b = dust_box(p);
+  K.b = make_box(p->BoxSize, p->periodic);
   K.dt_fac = p->dt_fac;
   K.dt_fac_gas = p->dt_fac_gas;
   K.minegy = p->MinEgySpec;
@@ -647,7 +518,7 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
   const size_t D = (size_t) nd;
   const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
   TreeDev &t = ctx->st;
-  const DustSphNode *nodes = reinterpret_cast<const DustSphNode *>(t.mq.p);
+  const SphNode *nodes = P<SphNode>(t.mq);
   const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
   const int *type = P<int>(ctx->f[GHIP_F_TYPE]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
   DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, nullptr, w + DP_RHO * D};
@@ -745,7 +616,7 @@ extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int n
   DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, mass, nullptr};
   k_dust_density<<<cdiv(ndust, 64), 64, 0, st>>>(ndust, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
                                                  t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                 dust_box(p), dout);
+                                                 make_box(p->BoxSize, p->periodic), dout);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
@@ -903,7 +774,7 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
               DustGrainLocal gl = {didx, pos, hsml, n, mass, nullptr};
               k_dust_density<<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
                                                           t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                          dust_box(A.p), P<double>(ctx->dust_work));
+                                                          make_box(A.p->BoxSize, A.p->periodic), P<double>(ctx->dust_work));
             }
           HIPCHK(hipGetLastError());
           GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
@@ -946,7 +817,7 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           DustGrainRec gr = {P<double>(D.du_recv), DUST_REC_DENS};
           k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
                                                         t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                        dust_box(A.p), P<double>(D.du_part));
+                                                        make_box(A.p->BoxSize, A.p->periodic), P<double>(D.du_part));
           HIPCHK(hipGetLastError());
         }
       int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];

@@ -590,16 +590,24 @@ int ghip_walk_layout(const TreeDev &t, WalkSeg &sg, int table);   // returns nsu
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int d_wave_min_i32(int v)
-{
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      int o = __shfl_xor(v, off, 64);
-      v = o < v ? o : v;
-    }
-  return v;
-}
-
+// 64-lane reductions, fixed order.  The butterflies leave the result in every lane.
+#define GHIP_WAVE_REDUCE(name, T, expr)                    \
+  __device__ __forceinline__ T name(T v)                   \
+  {                                                        \
+    for(int off = 32; off > 0; off >>= 1)                  \
+      {                                                    \
+        T o = __shfl_xor(v, off, 64);                      \
+        v = expr;                                          \
+      }                                                    \
+    return v;                                              \
+  }
+GHIP_WAVE_REDUCE(d_wave_min_i32, int, o < v ? o : v)
+GHIP_WAVE_REDUCE(d_wave_max_i32, int, o > v ? o : v)
+GHIP_WAVE_REDUCE(d_wave_min_f64, double, o < v ? o : v)
+GHIP_WAVE_REDUCE(d_wave_max_f64, double, o > v ? o : v)
+GHIP_WAVE_REDUCE(d_wave_sum_f64, double, v + o)
+GHIP_WAVE_REDUCE(d_wave_or_u64, unsigned long long, v | o)
+#undef GHIP_WAVE_REDUCE
 
 // element link record: x = skip (element index after this subtree), y = sorted particle index
 // for a particle element or -(level+1) for a node, z = first particle of the node, w = count
@@ -619,9 +627,10 @@ __device__ __forceinline__ double d_ngb_periodic(double x, int periodic, double 
   return (periodic && xt > boxhalf) ? (boxsize - xt) : xt;
 }
 
+// (a shift-down sum: valid in lane 0 only)
 __device__ __forceinline__ unsigned long long d_wave_sum_u64(unsigned long long v)
 {
   for(int off = 32; off > 0; off >>= 1)
     v += __shfl_down(v, off, 64);
-  return v;  // valid in lane 0
+  return v;
 }

@@ -16,12 +16,8 @@
 // it in the mask.  The host reads two ints and the ncand candidates, never an [ngas] array.
 #include <hipcub/hipcub.hpp>
 
-#include "ghip_internal.h"
+#include "ghip_ngb.h"   // the reference's constants
 
-#define SFR_GAMMA (7. / 5.)        // allvars.h:64
-#define SFR_GAMMA_MINUS1 (SFR_GAMMA - 1)
-#define SFR_PROTONMASS 1.6726e-24  // allvars.h:89
-#define SFR_BOLTZMANN 1.3806e-16   // allvars.h:84
 #define SFR_TAPPER_RHO 1.e-10      // rho_crit of BETA_COOLING_TAPPER_OFF, cooling.c:219
 
 struct SfrK
@@ -114,8 +110,8 @@ __global__ __launch_bounds__(256) void k_sfr_cooling(
                 {
                   const double A = entropy[i];
                   const double prho = rho * K.a3inv;
-                  const double pw = pow(prho, SFR_GAMMA_MINUS1);   // the reference evaluates it twice
-                  double unew = (A + dtentropy[i] * dt) / SFR_GAMMA_MINUS1 * pw;   // :486-488
+                  const double pw = pow(prho, GAMMA_MINUS1);   // the reference evaluates it twice
+                  double unew = (A + dtentropy[i] * dt) / GAMMA_MINUS1 * pw;   // :486-488
                   if(unew < K.minegy)
                     unew = K.minegy;
                   if(dragheat)   // :481-499: neither spent nor cleared when Mass == 0
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256) void k_sfr_cooling(
                   unew = sfr_do_cooling(K, unew, prho, dtime, r2);
                   if(tb && dt > 0)   // :572-595
                     {
-                      double d = (unew * SFR_GAMMA_MINUS1 / pw - A) / dt;
+                      double d = (unew * GAMMA_MINUS1 / pw - A) / dt;
                       if(d < -0.5 * A / dt)
                         d = -0.5 * A / dt;
                       dtentropy[i] = d;
@@ -232,7 +228,7 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
   K.minegy = p->MinEgySpec;
   K.grain_floor = 1.e-5 * p->OriginalGasMass;
   // cooling.c:104-105 and sfr_eff.c:127 (CONSTANT_MEAN_MOLECULAR_WEIGHT): the same factor
-  K.u_to_temp = p->MeanWeight * SFR_PROTONMASS / SFR_BOLTZMANN * SFR_GAMMA_MINUS1 * p->UnitEnergy_in_cgs /
+  K.u_to_temp = p->MeanWeight * PROTONMASS / BOLTZMANN * GAMMA_MINUS1 * p->UnitEnergy_in_cgs /
                 p->UnitMass_in_g;
   K.eqtemp = p->EqTemp;
   K.betacool = p->BetaCool;

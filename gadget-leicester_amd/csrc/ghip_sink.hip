@@ -19,80 +19,13 @@
 // tree with a wave-uniform element index; a cell of <= 256 particles that overlaps the search
 // sphere is swept flat, 64 candidates at a time, one per lane.  Victims are marked by scatter:
 // atomicMax on SwallowID (the largest ID wins, deterministic), atomicAdd on the injected energy.
-#include "ghip_internal.h"
+#include "ghip_ngb.h"
 
-#define KERNEL_COEFF_1 2.546479089470
-#define KERNEL_COEFF_2 15.278874536822
-#define KERNEL_COEFF_5 5.092958178941
-#define NORM_COEFF 4.188790204786
-#define SINK_FACT1 0.366025403785   // allvars.h:310
-#define SINK_GAMMA (7. / 5.)        // allvars.h:64
-#define SINK_GAMMA_MINUS1 (SINK_GAMMA - 1)
 #define SINK_LEAF 256
-
-struct SinkBox
-{
-  double boxsize, boxhalf;
-  int periodic;
-};
-
-__device__ __forceinline__ double d_sink_wrap(double d, const SinkBox &b)
-{
-  if(b.periodic)
-    {
-      if(d > b.boxhalf)
-        d -= b.boxsize;
-      if(d < -b.boxhalf)
-        d += b.boxsize;
-    }
-  return d;
-}
-
-// node test of ngb_treefind_blackhole / ngb_treefind_variable (blackhole.c:1453-1466, ngb.c:276-289)
-__device__ __forceinline__ bool d_sink_overlaps(double cx, double cy, double cz, double len, double h,
-                                                double px, double py, double pz, const SinkBox &b)
-{
-  double dist = h + 0.5 * len;
-  double dx = d_ngb_periodic(cx - px, b.periodic, b.boxsize, b.boxhalf);
-  if(dx > dist)
-    return false;
-  double dy = d_ngb_periodic(cy - py, b.periodic, b.boxsize, b.boxhalf);
-  if(dy > dist)
-    return false;
-  double dz = d_ngb_periodic(cz - pz, b.periodic, b.boxsize, b.boxhalf);
-  if(dz > dist)
-    return false;
-  dist += SINK_FACT1 * len;
-  return !(dx * dx + dy * dy + dz * dz > dist * dist);
-}
-
-__device__ __forceinline__ double d_sink_kernel(double r, double h)
-{
-  const double hinv = 1 / h, hinv3 = hinv * hinv * hinv, u = r * hinv;
-  if(u < 0.5)
-    return hinv3 * (KERNEL_COEFF_1 + KERNEL_COEFF_2 * (u - 1) * u * u);
-  return hinv3 * KERNEL_COEFF_5 * (1.0 - u) * (1.0 - u) * (1.0 - u);
-}
-
-// fixed-order sum over the 64 lanes (valid in every lane)
-__device__ __forceinline__ double d_wave_sum_f64(double v)
-{
-  for(int off = 32; off > 0; off >>= 1)
-    v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // density for sink targets: one fixed-h evaluation per launch (gas tree: SphNode list + gp records)
 // ---------------------------------------------------------------------------------------------
-struct __attribute__((aligned(64))) SinkSphNode   // = SphNode of ghip_sph.hip
-{
-  double cx, cy, cz, len;
-  double hmax;
-  int skip, pidx, pstart, pcount;
-  int pad[2];
-};
-
 struct SinkRec   // what a pass needs of its sink (host fills it from the resident fields' values)
 {
   double x, y, z, vx, vy, vz, mass, h, mdot, rho;
@@ -105,9 +38,9 @@ struct SinkRec   // what a pass needs of its sink (host fills it from the reside
 // shards add theirs
 __global__ void __launch_bounds__(64)
 k_sink_density(int ns, const int *__restrict__ slot, const SinkRec *__restrict__ recs,
-               const double *__restrict__ sh, int nelem, const SinkSphNode *__restrict__ nodes,
+               const double *__restrict__ sh, int nelem, const SphNode *__restrict__ nodes,
                const double *__restrict__ gp, const int *__restrict__ perm,
-               const double *__restrict__ entropy, int ngas, int local_only, SinkBox b,
+               const double *__restrict__ entropy, int ngas, int local_only, BoxK b,
                double *__restrict__ out)
 {
   const int a = slot[blockIdx.x], lane = threadIdx.x;
@@ -115,60 +48,29 @@ k_sink_density(int ns, const int *__restrict__ slot, const SinkRec *__restrict__
   const double h = sh[a], h2 = h * h;
   double rho = 0, wn = 0, se = 0, g0 = 0, g1 = 0, g2 = 0;
   const double hinv = 1.0 / h, hinv3 = hinv * hinv * hinv;
-  int e = 0;
-  while(e < nelem)
-    {
-      const SinkSphNode N = nodes[e];   // wave-uniform address
-      int first, count;
-      if(N.pidx >= 0)
-        {
-          first = N.pidx;
-          count = 1;
-          e = e + 1;
-        }
-      else
-        {
-          if(!d_sink_overlaps(N.cx, N.cy, N.cz, N.len, h, px, py, pz, b))
-            {
-              e = N.skip;
-              continue;
-            }
-          if(N.pcount > SINK_LEAF)
-            {
-              e = e + 1;
-              continue;
-            }
-          first = N.pstart;
-          count = N.pcount;
-          e = N.skip;
-        }
-      for(int p0 = first; p0 < first + count; p0 += 64)
-        {
-          const int p = p0 + lane;
-          if(p >= first + count)
-            continue;
-          const double *r8 = gp + (size_t) 8 * p;
-          const double mass_j = r8[3];
-          if(mass_j <= 0)   // density.c:831-834; < 0: a converted particle of the gas block, not gas
-            continue;
-          const double dx = d_sink_wrap(px - r8[0], b), dy = d_sink_wrap(py - r8[1], b),
-                       dz = d_sink_wrap(pz - r8[2], b);
-          const double r2 = dx * dx + dy * dy + dz * dz;
-          if(r2 < h2)
-            {
-              const int j = perm[p];
-              if(local_only && j >= ngas)
-                continue;
-              const double wk = d_sink_kernel(sqrt(r2), h);
-              rho += mass_j * wk;
-              wn += NORM_COEFF * wk / hinv3;
-              g0 += mass_j * wk * r8[4];
-              g1 += mass_j * wk * r8[5];
-              g2 += mass_j * wk * r8[6];
-              se += mass_j * wk * (j < ngas ? entropy[j] : 0.0);
-            }
-        }
-    }
+  d_ngb_walk_wave<SINK_LEAF>(GasElems{nodes}, nelem, px, py, pz, h, b, [&](int p, bool valid) {
+    if(!valid)
+      return;
+    const double *r8 = gp + (size_t) 8 * p;
+    const double mass_j = r8[3];
+    if(mass_j <= 0)   // density.c:831-834; < 0: a converted particle of the gas block, not gas
+      return;
+    const double dx = d_wrap(px - r8[0], b), dy = d_wrap(py - r8[1], b), dz = d_wrap(pz - r8[2], b);
+    const double r2 = dx * dx + dy * dy + dz * dz;
+    if(r2 < h2)
+      {
+        const int j = perm[p];
+        if(local_only && j >= ngas)
+          return;
+        const double wk = d_spline_wk(sqrt(r2) * hinv, hinv3);
+        rho += mass_j * wk;
+        wn += NORM_COEFF * wk / hinv3;
+        g0 += mass_j * wk * r8[4];
+        g1 += mass_j * wk * r8[5];
+        g2 += mass_j * wk * r8[6];
+        se += mass_j * wk * (j < ngas ? entropy[j] : 0.0);
+      }
+  });
   rho = d_wave_sum_f64(rho);
   wn = d_wave_sum_f64(wn);
   se = d_wave_sum_f64(se);
@@ -303,13 +205,13 @@ static int sink_density_pass(ghip_ctx *ctx, const ghip_dens_params *p, int ns, c
 {
   hipStream_t st = ctx->stream;
   TreeDev &t = ctx->st;
-  SinkBox b = {p->BoxSize, 0.5 * p->BoxSize, p->periodic};
+  const BoxK b = make_box(p->BoxSize, p->periodic);
   HIPCHK(hipMemcpyAsync(dh, I.h.data(), (size_t) ns * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dslot, I.todo.data(), (size_t) ncur * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dout, 0, (size_t) ns * 48, st));
   if(t.nelem > 0)
     k_sink_density<<<ncur, 64, 0, st>>>(ns, dslot, drecs, dh, t.nelem,
-                                        reinterpret_cast<const SinkSphNode *>(t.mq.p), P<double>(ctx->gp),
+                                        P<SphNode>(t.mq), P<double>(ctx->gp),
                                         P<int>(t.perm), P<double>(ctx->f[GHIP_F_ENTROPY]), ctx->ngas,
                                         local_only, b, dout);
   HIPCHK(hipGetLastError());
@@ -388,49 +290,10 @@ extern "C" int ghip_sink_density(ghip_ctx *ctx, const ghip_dens_params *p, doubl
 // ---------------------------------------------------------------------------------------------
 struct BhK
 {
-  SinkBox b;
+  BoxK b;
   double ascale, dt_fac, smbh, inner, sinkb, softb, critdens, fbcoeff, unitmass;
   int dust, dust_only, acc_density;
 };
-
-// walk the gravity tree around sink S; F(p, valid) is called by all 64 lanes with lane-own candidate p
-template <class F>
-__device__ __forceinline__ void d_sink_walk(const SinkRec &S, int nelem, const int4 *__restrict__ lk,
-                                            const double4 *__restrict__ cl, const SinkBox &b, F &&f)
-{
-  const int lane = threadIdx.x;
-  int e = 0;
-  while(e < nelem)
-    {
-      const int4 k = lk[e];   // wave-uniform
-      int first, count;
-      if(k.y >= 0)
-        {
-          first = k.y;
-          count = 1;
-          e = e + 1;
-        }
-      else
-        {
-          const double4 c = cl[e];
-          if(!d_sink_overlaps(c.x, c.y, c.z, c.w, S.h, S.x, S.y, S.z, b))
-            {
-              e = k.x;
-              continue;
-            }
-          if(k.w > SINK_LEAF)
-            {
-              e = e + 1;
-              continue;
-            }
-          first = k.z;
-          count = k.w;
-          e = k.x;
-        }
-      for(int p0 = first; p0 < first + count; p0 += 64)
-        f(p0 + lane, p0 + lane < first + count);
-    }
-}
 
 // blackhole_evaluate (blackhole.c:794-1190) for the shipped bundle.  Per neighbour j within Hsml of
 // the sink (both with mass > 0):
@@ -464,7 +327,7 @@ k_bh_evaluate(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *
   double energy = 0.;   // blackhole.c:1114-1150 TMP_FEEDBACK: the smaller sinks only
   if(S.mass < 0.95 * K.smbh)
     energy = K.fbcoeff * pow(S.mass * K.unitmass, 0.6667) * S.mdot * K.unitmass * dt;
-  d_sink_walk(S, nelem, lk, cl, K.b, [&](int p, bool valid) {
+  d_ngb_walk_wave<SINK_LEAF>(GravElems{lk, cl}, nelem, S.x, S.y, S.z, S.h, K.b, [&](int p, bool valid) {
     if(!valid)
       return;
     const int j = perm[p];
@@ -476,8 +339,8 @@ k_bh_evaluate(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *
     const double mj = mass[j];
     if(!(mj > 0))
       return;
-    const double dx = d_sink_wrap(S.x - sx[p], K.b), dy = d_sink_wrap(S.y - sy[p], K.b),
-                 dz = d_sink_wrap(S.z - sz[p], K.b);
+    const double dx = d_wrap(S.x - sx[p], K.b), dy = d_wrap(S.y - sy[p], K.b),
+                 dz = d_wrap(S.z - sz[p], K.b);
     const double r2 = dx * dx + dy * dy + dz * dz;
     if(!(r2 < h2))
       return;
@@ -499,7 +362,8 @@ k_bh_evaluate(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *
     if(ty == 0)
       {
         const double r = sqrt(r2);
-        const double wk = d_sink_kernel(r, S.h);
+        const double hinv = 1 / S.h;
+        const double wk = d_spline_wk(r * hinv, hinv * hinv * hinv);
         const double etotal = vrel * vrel / 2. - S.mass / (r + 1.e-20);
         if(central)
           {
@@ -534,7 +398,7 @@ k_bh_swallow(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *_
   const SinkRec S = sinks[a];
   const double h2 = S.h * S.h;
   double am = 0, ab = 0, ad = 0, m0 = 0, m1 = 0, m2 = 0, c0 = 0, c1 = 0, c2 = 0;
-  d_sink_walk(S, nelem, lk, cl, K.b, [&](int p, bool valid) {
+  d_ngb_walk_wave<SINK_LEAF>(GravElems{lk, cl}, nelem, S.x, S.y, S.z, S.h, K.b, [&](int p, bool valid) {
     if(!valid)
       return;
     const int j = perm[p];
@@ -546,8 +410,8 @@ k_bh_swallow(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *_
     if(swallow[j] != S.id)
       return;
     // the search sphere of ngb_treefind_blackhole: r2 <= h^2 (blackhole.c:1390-1391)
-    const double dx = d_sink_wrap(S.x - sx[p], K.b), dy = d_sink_wrap(S.y - sy[p], K.b),
-                 dz = d_sink_wrap(S.z - sz[p], K.b);
+    const double dx = d_wrap(S.x - sx[p], K.b), dy = d_wrap(S.y - sy[p], K.b),
+                 dz = d_wrap(S.z - sz[p], K.b);
     if(dx * dx + dy * dy + dz * dz > h2)
       return;
     const double mj = mass_in[j];
@@ -610,9 +474,7 @@ int ghip_sink_buffers(ghip_ctx *ctx)
 static BhK bh_kparams(const ghip_bh_params *p)
 {
   BhK K;
-  K.b.boxsize = p->BoxSize;
-  K.b.boxhalf = 0.5 * p->BoxSize;
-  K.b.periodic = p->periodic;
+  K.b = make_box(p->BoxSize, p->periodic);
   K.ascale = p->ascale;
   K.dt_fac = p->dt_fac;
   K.smbh = p->SMBHmass;
@@ -809,7 +671,7 @@ __global__ void k_cooling_sf(int nact, const int *__restrict__ act, int ngas,
   flag_sink[i] = !flag;
   if(flag == 1)
     {
-      double unew = (entropy[i] + dtentropy[i] * dt) / SINK_GAMMA_MINUS1 * pow(density[i], SINK_GAMMA_MINUS1);
+      double unew = (entropy[i] + dtentropy[i] * dt) / GAMMA_MINUS1 * pow(density[i], GAMMA_MINUS1);
       if(unew < minegy)
         unew = minegy;
       const double inj = injected[i];
@@ -823,7 +685,7 @@ __global__ void k_cooling_sf(int nact, const int *__restrict__ act, int ngas,
         }
       if(tb && dt > 0)
         {
-          double d = (unew * SINK_GAMMA_MINUS1 / pow(density[i], SINK_GAMMA_MINUS1) - entropy[i]) / dt;
+          double d = (unew * GAMMA_MINUS1 / pow(density[i], GAMMA_MINUS1) - entropy[i]) / dt;
           if(d < -0.5 * entropy[i] / dt)
             d = -0.5 * entropy[i] / dt;
           dtentropy[i] = d;

@@ -17,62 +17,7 @@
 // order.  Neighbour SETS are geometric, so they are identical to the reference's; only the
 // summation order differs.
 
-#include "ghip_internal.h"
-
-// allvars.h:247-253
-#define KERNEL_COEFF_1 2.546479089470
-#define KERNEL_COEFF_2 15.278874536822
-#define KERNEL_COEFF_3 45.836623610466
-#define KERNEL_COEFF_4 30.557749073644
-#define KERNEL_COEFF_5 5.092958178941
-#define KERNEL_COEFF_6 (-15.278874536822)
-#define NORM_COEFF 4.188790204786
-#define NUMDIMS 3
-#define GAMMA (7. / 5.)  // allvars.h:64 (this fork: 7/5, not 5/3)
-#define GAMMA_MINUS1 (GAMMA - 1)
-#define FACT1 0.366025403785  // allvars.h:310
-
-struct BoxK
-{
-  double boxsize, boxhalf;
-  int periodic;
-};
-
-// node test of ngb_treefind_* (ngb.c:276-289 / 136-151): true if the node must be opened
-__device__ __forceinline__ bool d_node_overlaps(const double4 c, double dist, double px, double py,
-                                                double pz, const BoxK b)
-{
-  const double len = c.w;
-  dist += 0.5 * len;
-  double dx = d_ngb_periodic(c.x - px, b.periodic, b.boxsize, b.boxhalf);
-  if(dx > dist)
-    return false;
-  double dy = d_ngb_periodic(c.y - py, b.periodic, b.boxsize, b.boxhalf);
-  if(dy > dist)
-    return false;
-  double dz = d_ngb_periodic(c.z - pz, b.periodic, b.boxsize, b.boxhalf);
-  if(dz > dist)
-    return false;
-  dist += FACT1 * len;
-  return !(dx * dx + dy * dy + dz * dz > dist * dist);
-}
-
-__device__ __forceinline__ double d_wrap(double d, const BoxK b)
-{
-  // density.c:838-851 / hydra.c:1251-1264: d > boxhalf -> d - box, d < -boxhalf -> d + box.
-  // Written as one compare on |d| and a subtraction of copysign(box, d) under the execution mask
-  // (the same IEEE operations; 2 vector instructions per axis in the common no-wrap case, the
-  // empty asm keeps the compiler from turning it back into compare+select chains)
-  if(b.periodic)
-    {
-      if(fabs(d) > b.boxhalf)
-        {
-          d -= copysign(b.boxsize, d);
-          asm volatile("" : "+v"(d));
-        }
-    }
-  return d;
-}
+#include "ghip_ngb.h"
 
 // Bounds of a bucket's targets around the first target: half extents per axis (nearest-image
 // offsets) and the largest search radius.  A staged candidate can be a neighbour of SOME lane only
@@ -83,16 +28,6 @@ struct BucketBox
 {
   double cx, cy, cz, ex, ey, ez, hmax;
 };
-
-__device__ __forceinline__ double d_wave_max_f64(double v)
-{
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      double o = __shfl_xor(v, off, 64);
-      v = o > v ? o : v;
-    }
-  return v;
-}
 
 __device__ __forceinline__ double d_first_lane_f64(double v)
 {
@@ -167,6 +102,8 @@ __device__ __forceinline__ void d_density_pair(const double *r8, bool valid,
       // the reference's sqrt and its divisions by r and by hinv3 become multiplications
       const double rinv = r2 > 0 ? d_rsqrt_sph(r2) : 0.0;
       const double r = r2 * rinv;
+      // (wk is d_spline_wk(u, hinv3), kept fused with dwk under one branch: calling the shared
+      // function costs k_density 15 instructions)
       double u = r * hinv, wk, dwk;
       if(u < 0.5)
         {
@@ -191,31 +128,6 @@ __device__ __forceinline__ void d_density_pair(const double *r8, bool valid,
           A.rz += fac * (dy * dvx - dx * dvy);
         }
     }
-}
-
-// One element of the gas tree as the SPH walks read it (64 B, one s_load_dwordx16):
-//   cx, cy, cz, len | hmax | skip, pidx, pstart, pcount | pad
-struct __attribute__((aligned(64))) SphNode
-{
-  double cx, cy, cz, len;
-  double hmax;
-  int skip, pidx, pstart, pcount;
-  int pad[2];
-};
-typedef int v16i_s __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ double d_f64s(const v16i_s &v, int i)
-{
-  return __hiloint2double(v[2 * i + 1], v[2 * i]);
-}
-
-__device__ __forceinline__ void d_load_sphnode(const SphNode *__restrict__ base, int e, v16i_s &R)
-{
-  unsigned long long a = reinterpret_cast<unsigned long long>(base + e);
-  unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int) a);
-  unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int) (a >> 32));
-  const SphNode *p = reinterpret_cast<const SphNode *>(((unsigned long long) hi << 32) | lo);
-  asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(R) : "s"(p) : "memory");
 }
 
 #define SPH_STAGE 64   // candidates staged through LDS per round (= lanes of the staging load)
@@ -788,7 +700,7 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
                         st));
   k_dens_init<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(nt, cur, P<double>(ctx->gp), hcur,
                                              P<double>(ctx->dleft), P<double>(ctx->dright));
-  BoxK b = {p->BoxSize, 0.5 * p->BoxSize, p->periodic};
+  BoxK b = make_box(p->BoxSize, p->periodic);
   DensFin F = {p->DesNumNgb, p->MaxNumNgbDeviation, p->MinGasHsml, p->Ti_Current,
                p->Timebase_interval};
   int maxiter = p->MaxIter > 0 ? p->MaxIter : 150;
@@ -894,7 +806,7 @@ extern "C" int ghip_density_evaluate(ghip_ctx *ctx, const ghip_dens_params *p, i
   int *cur = P<int>(ctx->dtgt_a);
   HIPCHK(hipMemcpyAsync(cur, &s, 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(hcur + s, &h, 8, hipMemcpyHostToDevice, st));
-  BoxK b = {p->BoxSize, 0.5 * p->BoxSize, p->periodic};
+  BoxK b = make_box(p->BoxSize, p->periodic);
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_DENS1);
   k_density<8><<<nsub, 64, 0, st>>>(P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp), 1, nsub, cur, hcur, b,
                               P<double>(ctx->drho), P<double>(ctx->dnumngb),
@@ -992,7 +904,7 @@ extern "C" int ghip_ngb_treefind(ghip_ctx *ctx, const double center[3], double h
   hipStream_t st = ctx->stream;
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) (cap + 4) * 4));
   int *dlist = P<int>(ctx->stage) + 4, *dcount = P<int>(ctx->stage);
-  BoxK b = {boxsize, 0.5 * boxsize, periodic};
+  BoxK b = make_box(boxsize, periodic);
   k_ngb_find<<<1, 64, 0, st>>>(t.nelem, P<double4>(t.cl), P<int4>(t.lk), P<double>(t.aux),
                                P<double>(ctx->gp), P<int>(t.perm), center[0], center[1], center[2],
                                hsml, pairs, b, cap, dlist, dcount);
@@ -1324,7 +1236,7 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
   GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_HYDRO);
   HIPCHK(hipMemsetAsync(counter, 0, GHIP_CKIND_U64 * 8, st));
-  BoxK b = {p->BoxSize, 0.5 * p->BoxSize, p->periodic};
+  BoxK b = make_box(p->BoxSize, p->periodic);
   HydK K = {p->ArtBulkViscConst, p->hubble_a2, p->fac_mu, p->fac_vsic_fix, p->Timebase_interval,
             p->ComovingIntegrationOn, p->raw_dtentropy};
   // Underneath a gravity pair the hydro kernel (128 VGPRs) only fits where an Ewald wavefront would

@@ -151,11 +151,7 @@ __global__ void k_prefix_levels(int n, const unsigned long long *__restrict__ sk
     }
   // deepest node level of the tree = largest shared-digit count: one same-address access per
   // block of 1024 (per wavefront they cost 45 us at 5e5 particles)
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      int o = __shfl_xor(c, off, 64);
-      c = o > c ? o : c;
-    }
+  c = d_wave_max_i32(c);
   __shared__ int wmax[16];
   if((threadIdx.x & 63) == 0)
     wmax[threadIdx.x >> 6] = c;
@@ -198,11 +194,7 @@ __global__ void k_prefix_counts(int n, const unsigned long long *__restrict__ sk
       cnt[i] = d > 0 ? d : 0;
       c = ceff;
     }
-  for(int off = 32; off > 0; off >>= 1)
-    {
-      int o = __shfl_xor(c, off, 64);
-      c = o > c ? o : c;
-    }
+  c = d_wave_max_i32(c);
   __shared__ int wmax[16];
   if((threadIdx.x & 63) == 0)
     wmax[threadIdx.x >> 6] = c;
