@@ -258,7 +258,9 @@ EXPORTS = [
     "ghip_set_async", "ghip_timebin_counts", "ghip_run_begin", "ghip_step_begin", "ghip_step_end",
     "ghip_run_end", "ghip_dust_density", "ghip_dust_drag", "ghip_dust_get_drag_heating",
     "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh", "ghip_set_integration_flags",
-    "ghip_kick_set_fields", "ghip_kick_get_drag_accel"]
+    "ghip_kick_set_fields", "ghip_kick_get_drag_accel", "ghip_potential", "ghip_get_potential",
+    "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
+    "ghip_dd_bytes_sent"]
 
 
 def lib():
@@ -367,6 +369,8 @@ def lib():
         L.ghip_potential.argtypes = [vp, C.POINTER(PotParams)]
         L.ghip_get_potential.argtypes = [vp, vp]
         L.ghip_potential_interactions.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.ghip_get_potential_interactions.argtypes = [vp, vp]
+        L.ghip_dd_bytes_sent.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong)]
         L.ghip_ewald_get_pot_table.argtypes = [vp, C.c_double, vp]
         L.ghip_global_quantities.argtypes = [vp, C.POINTER(GlobalParams), C.POINTER(GlobalSums)]
         _LIB = L
@@ -627,6 +631,12 @@ class ForcePath:
         s, m = C.c_longlong(0), C.c_longlong(0)
         self._chk(self.L.ghip_potential_interactions(self.h, C.byref(s), C.byref(m)))
         return s.value, m.value
+
+    def get_potential_interactions(self):
+        """interactions of the last potential walk per target, host order (ghip_get_potential_interactions)"""
+        a = np.zeros(self.n, np.int64)
+        self._chk(self.L.ghip_get_potential_interactions(self.h, _ptr(a)))
+        return a
 
     def ewald_pot_table(self, boxsize):
         """potcorr[EN+1][EN+1][EN+1] / BoxSize of ewald_init (forcetree.c:4466-4525)"""
@@ -981,6 +991,12 @@ class ForcePath:
                 "numpart", "ngas", "migrated_out", "migrated_in", "bytes_migrate")
         return dict(zip(keys, (int(v) for v in out)))
 
+    def dd_bytes_sent(self, op):
+        """bytes this shard sent over links in its last operation `op` (DD_*)"""
+        b = C.c_longlong(0)
+        self._chk(self.L.ghip_dd_bytes_sent(self.h, int(op), C.byref(b)))
+        return b.value
+
     # ---- multi-GPU shard exchange helpers (device pointers, e.g. torch tensors' data_ptr()) ----
     def shard_count(self, gas):
         per = C.c_int(0)
@@ -999,6 +1015,7 @@ class ForcePath:
 DD_MIGRATE, DD_GRAVITY, DD_DENSITY, DD_HYDRO = 1, 2, 3, 4
 DD_SINK_DENSITY, DD_BH_EVALUATE, DD_BH_SWALLOW, DD_PM = 5, 6, 7, 8
 DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
+DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 
 
 class DdSinkArgs(C.Structure):
@@ -1069,6 +1086,32 @@ def dd_dust_args(params, dust, particle_density=None, dust_density=None, dust_en
               "particle_velocity", "delta_momentum", "delta_energy", "vcoll", "counts"):
         setattr(A, k, a[k].ctypes.data)
     return A, a
+
+
+class DdGlobalArgs(C.Structure):
+    """ghip_dd_global_args (include/ghip.h): compute_global_quantities_of_system() on a multi-GPU shard"""
+    _fields_ = [("p", C.POINTER(GlobalParams)), ("out", C.POINTER(GlobalSums))]
+
+
+def dd_global_args(params, n, grav_kick_table=None, hydro_kick_table=None, old_photon_momentum=None,
+                   potential=None):
+    """(args, keep) for GHIP_DD_GLOBAL_QUANTITIES on a shard of n particles: a filled DdGlobalArgs and the
+    dict it points into -- a copy of params with the host arrays set (as ForcePath.global_quantities takes
+    them; potential None = the shard's last GHIP_DD_POTENTIAL) and the GlobalSums `out` the operation fills.
+    Keep `keep` alive until the operation has finished."""
+    p = GlobalParams.from_buffer_copy(params)
+    keep = dict(params=p, out=GlobalSums())
+    for name, arr in (("GravKickTable", grav_kick_table), ("HydroKickTable", hydro_kick_table),
+                      ("OldPhotonMomentum", old_photon_momentum), ("Potential", potential)):
+        a = None if arr is None else np.ascontiguousarray(arr, dtype=np.float64)
+        if a is not None and name in ("OldPhotonMomentum", "Potential") and len(a) != n:
+            raise ValueError("%s: expected %d values, got %d" % (name, n, len(a)))
+        keep[name] = a
+        setattr(p, name, None if a is None else a.ctypes.data)
+    A = DdGlobalArgs()
+    A.p = C.pointer(p)
+    A.out = C.pointer(keep["out"])
+    return A, keep
 
 
 def dd_rccl_unique_id():

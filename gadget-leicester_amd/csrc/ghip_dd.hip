@@ -406,8 +406,9 @@ __global__ void __launch_bounds__(64) k_dd_supergroups(DDGroup *__restrict__ tab
 }
 
 // target list `tgt` (indices of the gravity tree, curve order).  gas = false: groups carry the least
-// OldAcc; gas = true: the largest smoothing length times the ghost margin.
-static int build_groups(ghip_ctx *ctx, bool gas, const int *tgt, int nt)
+// OldAcc; gas = true: the largest smoothing length times the ghost margin.  val: another per-particle
+// array in place of OldAcc (for a caller whose tests do not read amin and that may hold no OldAcc).
+static int build_groups(ghip_ctx *ctx, bool gas, const int *tgt, int nt, const double *val = nullptr)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
@@ -418,7 +419,7 @@ static int build_groups(ghip_ctx *ctx, bool gas, const int *tgt, int nt)
     gsz = 1;
   k_dd_groups<<<DD_NGROUPS, 64, 0, st>>>(nt, gsz, tgt, P<double>(ctx->sx), P<double>(ctx->sy),
                                          P<double>(ctx->sz), P<int>(ctx->gt.perm),
-                                         P<double>(ctx->f[gas ? GHIP_F_HSML : GHIP_F_OLDACC]),
+                                         val ? val : P<double>(ctx->f[gas ? GHIP_F_HSML : GHIP_F_OLDACC]),
                                          gas ? D.gh_margin_cur : 1.0, tab);
   k_dd_supergroups<<<DD_NSUPER, 64, 0, st>>>(tab);
   HIPCHK(hipGetLastError());
@@ -1129,78 +1130,126 @@ int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord,
 #define set_alltoallv ghip_dd_set_alltoallv
 
 // ---- gravity ------------------------------------------------------------------------------
-static int gravity_step(ghip_ctx *ctx)
+// the shard's own tree (moments of the cells it owns), nothing imported
+int ghip_dd_own_tree(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  GCHK(ghip_join_pair(ctx));
+  D.gt_nimp = 0;
+  D.gt_is_pot = false;
+  if(ctx->n > 0)
+    {
+      const double *x = P<double>(ctx->f[GHIP_F_POS]);
+      const double fac = 1.0 / ctx->dlen * (double) (1ULL << GHIP_BITS);
+      k_dd_check_range<<<cdiv(ctx->n, 256), 256, 0, st>>>(
+        ctx->n, x, x + ctx->n, x + 2 * (size_t) ctx->n, ctx->corner[0], ctx->corner[1],
+        ctx->corner[2], fac, D.nown, P<unsigned long long>(D.ownlo), P<unsigned long long>(D.ownhi),
+        ghip_errword(ctx, GHIP_ERRW_TREE));
+    }
+  return ghip_tree_build_impl(ctx);
+}
+
+__global__ void k_dd_iota(int n, int *__restrict__ out)
+{
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i < n)
+    out[i] = i;
+}
+
+// the group table of the own tree's targets -- the active gravity targets, or (all) every particle of the
+// shard, as compute_potential() has them (potential.c:88-97) -- and its all-gather
+int ghip_dd_post_groups(ghip_ctx *ctx, bool all, bool need_oldacc)
+{
+  DDState &D = ctx->dd;
+  if(all)
+    {
+      const int n = ctx->gt.n;   // (= ctx->n: nothing is imported yet)
+      GCHK(ghip_ensure(ctx, D.pot_tgt, (size_t) (n > 0 ? n : 1) * 4));
+      if(n > 0)
+        {
+          k_dd_iota<<<cdiv(n, 256), 256, 0, ctx->stream>>>(n, P<int>(D.pot_tgt));
+          HIPCHK(hipGetLastError());
+        }
+      // (under the Barnes-Hut criterion no test reads amin and OldAcc need not be set: any array serves)
+      GCHK(build_groups(ctx, false, P<int>(D.pot_tgt), n,
+                        need_oldacc ? nullptr : P<double>(ctx->f[GHIP_F_MASS])));
+    }
+  else
+    {
+      GCHK(ghip_build_target_lists(ctx));
+      GCHK(build_groups(ctx, false, P<int>(ctx->tg_grav), ctx->nt_grav));
+    }
+  set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+  return GHIP_OK;
+}
+
+// after the all-gather of the group tables: what can the others need of this tree?
+int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
   const int P_ = D.nranks;
+  GCHK(check_group_status(ctx, what));   // (all shards together, see DD_STRIDE)
+  TreeDev &t = ctx->gt;
+  int scount[GHIP_MAXRANKS], soff[GHIP_MAXRANKS], total = 0;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    scount[r] = soff[r] = 0;
+  if(t.nelem > 0 && P_ > 1)
+    {
+      GCHK(ghip_ensure(ctx, D.reach, (size_t) t.nelem * 8));
+      GCHK(ghip_ensure(ctx, D.sendm, (size_t) t.nelem * 8));
+      LetK K;
+      K.theta2 = gp.ErrTolTheta * gp.ErrTolTheta;
+      K.errtol = gp.ErrTolForceAcc;
+      K.b = make_box(gp.BoxSize, gp.periodic);
+      K.unequal = gp.unequal_softenings || ctx->adaptive_gravsoft;
+      K.nranks = P_;
+      K.me = D.rank;
+      K.nown = D.nown;
+      K.ownlo = P<unsigned long long>(D.ownlo);
+      K.ownhi = P<unsigned long long>(D.ownhi);
+      unsigned long long all = (P_ >= 64) ? ~0ULL : ((1ULL << P_) - 1ULL);
+      all &= ~(1ULL << D.rank);
+      unsigned long long *reach = P<unsigned long long>(D.reach),
+                         *sendm = P<unsigned long long>(D.sendm);
+      k_let_init<<<cdiv(t.nelem, 256), 256, 0, st>>>(t.nelem, all, reach, sendm);
+      for(int L = 0; L <= t.maxlevel; L++)
+        k_let_level<<<cdiv(t.nelem, LET_EPW), 64, 0, st>>>(
+          t.nelem, L, P<int4>(t.lk), P<double4>(t.xm), P<double4>(t.cl), P<double>(t.aux),
+          P<unsigned long long>(t.skey), P<DDGroup>(D.grp_all), K, reach, sendm);
+      k_let_single<<<1, 64, 0, st>>>(t.nelem, P<int4>(t.lk), reach, sendm);
+      HIPCHK(hipGetLastError());
+      GCHK(multi_select(ctx, t.nelem, sendm, D.let_list, scount, soff, &total));
+    }
+  GCHK(ghip_ensure(ctx, D.let_send, (size_t) (total > 0 ? total : 1) * sizeof(LetRec)));
+  if(total > 0)
+    {
+      k_let_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.let_list), P<int4>(t.lk),
+                                                  P<double4>(t.xm), P<double>(t.aux),
+                                                  P<unsigned long long>(t.skey),
+                                                  P<LetRec>(D.let_send));
+      HIPCHK(hipGetLastError());
+    }
+  D.let_sent = total;
+  set_alltoallv(D, D.let_send.p, sizeof(LetRec), scount, soff, &D.let_recv);
+  return GHIP_OK;
+}
+
+static int gravity_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
   if(D.phase == 0)
     {
-      // the shard's own tree (moments of the cells it owns) and its target groups
-      GCHK(ghip_join_pair(ctx));
-      D.gt_nimp = 0;
-      if(ctx->n > 0)
-        {
-          const double *x = P<double>(ctx->f[GHIP_F_POS]);
-          const double fac = 1.0 / ctx->dlen * (double) (1ULL << GHIP_BITS);
-          k_dd_check_range<<<cdiv(ctx->n, 256), 256, 0, st>>>(
-            ctx->n, x, x + ctx->n, x + 2 * (size_t) ctx->n, ctx->corner[0], ctx->corner[1],
-            ctx->corner[2], fac, D.nown, P<unsigned long long>(D.ownlo), P<unsigned long long>(D.ownhi),
-            ghip_errword(ctx, GHIP_ERRW_TREE));
-        }
-      GCHK(ghip_tree_build_impl(ctx));
-      GCHK(ghip_build_target_lists(ctx));
-      GCHK(build_groups(ctx, false, P<int>(ctx->tg_grav), ctx->nt_grav));
-      set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+      // the shard's own tree and its target groups
+      GCHK(ghip_dd_own_tree(ctx));
+      GCHK(ghip_dd_post_groups(ctx, false, true));
       D.phase = 1;
       return 1;
     }
   if(D.phase == 1)
     {
-      GCHK(check_group_status(ctx, "gravity"));   // (all shards together, see DD_STRIDE)
-      // what can the others need of this tree?
-      TreeDev &t = ctx->gt;
-      int scount[GHIP_MAXRANKS], soff[GHIP_MAXRANKS], total = 0;
-      for(int r = 0; r < GHIP_MAXRANKS; r++)
-        scount[r] = soff[r] = 0;
-      if(t.nelem > 0 && P_ > 1)
-        {
-          GCHK(ghip_ensure(ctx, D.reach, (size_t) t.nelem * 8));
-          GCHK(ghip_ensure(ctx, D.sendm, (size_t) t.nelem * 8));
-          LetK K;
-          K.theta2 = D.gp.ErrTolTheta * D.gp.ErrTolTheta;
-          K.errtol = D.gp.ErrTolForceAcc;
-          K.b = make_box(D.gp.BoxSize, D.gp.periodic);
-          K.unequal = D.gp.unequal_softenings || ctx->adaptive_gravsoft;
-          K.nranks = P_;
-          K.me = D.rank;
-          K.nown = D.nown;
-          K.ownlo = P<unsigned long long>(D.ownlo);
-          K.ownhi = P<unsigned long long>(D.ownhi);
-          unsigned long long all = (P_ >= 64) ? ~0ULL : ((1ULL << P_) - 1ULL);
-          all &= ~(1ULL << D.rank);
-          unsigned long long *reach = P<unsigned long long>(D.reach),
-                             *sendm = P<unsigned long long>(D.sendm);
-          k_let_init<<<cdiv(t.nelem, 256), 256, 0, st>>>(t.nelem, all, reach, sendm);
-          for(int L = 0; L <= t.maxlevel; L++)
-            k_let_level<<<cdiv(t.nelem, LET_EPW), 64, 0, st>>>(
-              t.nelem, L, P<int4>(t.lk), P<double4>(t.xm), P<double4>(t.cl), P<double>(t.aux),
-              P<unsigned long long>(t.skey), P<DDGroup>(D.grp_all), K, reach, sendm);
-          k_let_single<<<1, 64, 0, st>>>(t.nelem, P<int4>(t.lk), reach, sendm);
-          HIPCHK(hipGetLastError());
-          GCHK(multi_select(ctx, t.nelem, sendm, D.let_list, scount, soff, &total));
-        }
-      GCHK(ghip_ensure(ctx, D.let_send, (size_t) (total > 0 ? total : 1) * sizeof(LetRec)));
-      if(total > 0)
-        {
-          k_let_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.let_list), P<int4>(t.lk),
-                                                      P<double4>(t.xm), P<double>(t.aux),
-                                                      P<unsigned long long>(t.skey),
-                                                      P<LetRec>(D.let_send));
-          HIPCHK(hipGetLastError());
-        }
-      D.let_sent = total;
-      set_alltoallv(D, D.let_send.p, sizeof(LetRec), scount, soff, &D.let_recv);
+      GCHK(ghip_dd_post_let(ctx, D.gp, "gravity"));
       D.phase = 2;
       return 1;
     }
@@ -1250,6 +1299,7 @@ static int density_step(ghip_ctx *ctx)
         {
           GCHK(ghip_join_pair(ctx));
           D.gt_nimp = 0;
+          D.gt_is_pot = false;
           GCHK(ghip_tree_build_impl(ctx));
         }
       GCHK(ghip_build_target_lists(ctx));
@@ -1649,6 +1699,7 @@ static int migrate_step(ghip_ctx *ctx)
       D.mig_in = nrecv;
       D.phase = 2;
       D.op = 0;
+      ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
       if(nrecv == 0 && D.mig_out == 0)
         return GHIP_OK;   // nobody left, nobody came: the resident arrays stay as they are
       // new positions: kept gas, received gas, kept others, received others
@@ -1733,6 +1784,12 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: an exchange is still pending");
   HIPCHK(hipSetDevice(ctx->device));
   GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
+  // the tree GHIP_DD_POTENTIAL leaves behind was selected for other targets than the step's gravity tree
+  if(D.gt_is_pot && ctx->gt.built &&
+     (op == DD_OP_DENSITY || (op >= GHIP_DD_SINK_DENSITY && op <= GHIP_DD_BH_SWALLOW) ||
+      op == GHIP_DD_DUST_DENSITY || op == GHIP_DD_DUST_DRAG))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: operation %d needs GHIP_DD_GRAVITY of this step, and the "
+                     "tree in place is the one GHIP_DD_POTENTIAL built: run GHIP_DD_GRAVITY first", op);
   if(op == DD_OP_GRAVITY)
     {
       if(walk < 0 || walk > GHIP_WALK_NEWTON_EWALD)
@@ -1763,6 +1820,16 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
     {
       D.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
       GCHK(ghip_dd_dust_begin(ctx, op));
+    }
+  else if(op == GHIP_DD_POTENTIAL)
+    {
+      D.pot = *reinterpret_cast<const ghip_pot_params *>(params);
+      GCHK(ghip_dd_pot_begin(ctx));
+    }
+  else if(op == GHIP_DD_GLOBAL_QUANTITIES)
+    {
+      D.gq = *reinterpret_cast<const ghip_dd_global_args *>(params);
+      GCHK(ghip_dd_gq_begin(ctx));
     }
   else if(op == DD_OP_MIGRATE)
     {
@@ -1802,6 +1869,10 @@ extern "C" int ghip_dd_step(ghip_ctx *ctx)
     return ghip_dd_pm_step(ctx);
   if(D.op == GHIP_DD_DUST_DENSITY || D.op == GHIP_DD_DUST_DRAG)
     return ghip_dd_dust_step(ctx);
+  if(D.op == GHIP_DD_POTENTIAL)
+    return ghip_dd_pot_step(ctx);
+  if(D.op == GHIP_DD_GLOBAL_QUANTITIES)
+    return ghip_dd_gq_step(ctx);
   if(D.op == DD_OP_MIGRATE)
     return migrate_step(ctx);
   if(D.op == DD_OP_GRAVITY)
@@ -1856,6 +1927,14 @@ extern "C" int ghip_dd_get_info(const ghip_ctx *ctx, long long out[16])
   return GHIP_OK;
 }
 
+extern "C" int ghip_dd_bytes_sent(const ghip_ctx *ctx, int op, long long *bytes)
+{
+  if(!ctx || !bytes || op < 1 || op >= 16)
+    return GHIP_EINVAL;
+  *bytes = ctx->dd.bytes_sent[op];
+  return GHIP_OK;
+}
+
 void ghip_dd_release(ghip_ctx *ctx)
 {
   if(!ctx)
@@ -1869,7 +1948,7 @@ void ghip_dd_release(ghip_ctx *ctx)
                   &D.mig_send, &D.mig_recv, &D.mig_scan, &D.gas_src, &D.sk_send, &D.sk_all, &D.sk_part,
                   &D.sk_parts, &D.sk_work, &D.pm_all, &D.segkey, &D.segowner, &D.ownlo, &D.ownhi,
                   &D.du_mask, &D.du_slot, &D.du_list, &D.du_send, &D.du_recv, &D.du_part, &D.du_back,
-                  &D.heat_shadow};
+                  &D.heat_shadow, &D.pot_tgt, &D.gq_send, &D.gq_all};
   for(DevBuf *b : bs)
     {
       if(b->p)

@@ -226,6 +226,16 @@ struct DDState
   long long bytes_sent[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   ghip_pm_params pm;              // GHIP_DD_PM
   DevBuf pm_all;                  // the density meshes of all shards
+  // GHIP_DD_POTENTIAL / GHIP_DD_GLOBAL_QUANTITIES (ghip_potential.hip)
+  ghip_pot_params pot;            // arguments of the operation in progress
+  DevBuf pot_tgt;                 // i32[n]: 0 .. n-1, the target list "all particles of the shard's own tree"
+  bool gt_is_pot = false;         // the gravity tree in place is the merged tree GHIP_DD_POTENTIAL built
+                                  // (selected for all particles as targets), not the step's GHIP_DD_GRAVITY's
+  int pot_rc = 0;                 // what this shard met in its walk (travels in status_own: all fail together)
+  std::string pot_msg;
+  ghip_dd_global_args gq;         // GHIP_DD_GLOBAL_QUANTITIES: arguments, a copy of *gq.p
+  ghip_global_params gq_p;
+  DevBuf gq_send, gq_all;         // ghip_global_sums of this shard / of all shards (rank order)
 };
 
 // the pending exchange of a state-machine step (ghip_dd.hip, ghip_sink.hip)
@@ -413,7 +423,7 @@ struct ghip_ctx
   DevBuf run_acc;                      // u64[16]: counters summed over the steps of a run
   // ---- ghip_potential / ghip_global_quantities (ghip_potential.hip) ----
   DevBuf pot;                      // f64[n]: P[].p.Potential of the last ghip_potential, host order
-  DevBuf pot_nint;                 // u64[n]: its interactions per target, tree order
+  DevBuf pot_nint;                 // u64[n]: its interactions per target, host order
   int pot_n = -1;                  // particle count of that call (-1: none)
   DevBuf potcorr;                  // f64[(EN+1)^3]: potcorr / BoxSize (forcetree.c:4466-4525)
   double potcorr_box = 0;
@@ -499,6 +509,10 @@ int ghip_finish_gas_tree(ghip_ctx *ctx);   // complete a deferred gas tree (entr
   while(0)
 void ghip_pm_release(ghip_ctx *ctx);
 int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot);   // pm.hip
+// ... in two halves (GHIP_DD_POTENTIAL): this context's particles onto its mesh pm_rho; then, all != nullptr:
+// pm_rho = the nranks meshes of `all` added in rank order, solve, pot[i] += the mesh potential at particle i
+int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p);
+int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot);
 
 #define HIPCHK(call)                                                                         \
   do                                                                                         \
@@ -568,6 +582,18 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p);
 int ghip_sph_fill_nodes(ghip_ctx *ctx, bool hmax_only);
 // dd.hip
 void ghip_dd_release(ghip_ctx *ctx);
+// the pieces of the gravity operation that GHIP_DD_POTENTIAL shares (ghip_potential.hip):
+// the shard's own tree (nothing imported) after the key-range check; the group table over `nt` targets
+// `tgt` of that tree (all = true: every particle of the shard) with its all-gather left pending; after it,
+// the selection of the locally essential trees under the opening rules of gp, packed, the all-to-all-v
+// left pending
+int ghip_dd_own_tree(ghip_ctx *ctx);
+int ghip_dd_post_groups(ghip_ctx *ctx, bool all, bool need_oldacc);
+int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what);
+int ghip_dd_pot_begin(ghip_ctx *ctx);   // potential.hip
+int ghip_dd_pot_step(ghip_ctx *ctx);
+int ghip_dd_gq_begin(ghip_ctx *ctx);
+int ghip_dd_gq_step(ghip_ctx *ctx);
 
 // ---------------------------------------------------------------------------------------------
 // walk segments: the element list of a tree is cut into `ns` contiguous segments and `nsub`

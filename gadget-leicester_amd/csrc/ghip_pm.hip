@@ -289,24 +289,52 @@ __global__ void k_pm_pot_readout(int n, int N, double to_slab_fac, double fac,
   pot[i] += fac * v;
 }
 
-// pot[i] += the periodic PM potential of every particle (ghip_potential, PMGRID builds).  GRAVPM and
-// what ghip_pm_periodic computes are not touched.
-int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot)
+// rank-ordered sum of the all-gathered meshes (identical on every shard, whatever the transport)
+__global__ void k_pm_sum_meshes(size_t n3, int nranks, const double *__restrict__ all,
+                                double *__restrict__ rho)
+{
+  size_t g = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if(g >= n3)
+    return;
+  double s = 0;
+  for(int r = 0; r < nranks; r++)
+    s += all[(size_t) r * n3 + g];
+  rho[g] = s;
+}
+
+// the mass of this context's particles onto its (zeroed) mesh.  GRAVPM is not touched.
+int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p)
 {
   GCHK(pm_check(ctx, p));
   const int N = p->pmgrid, n = ctx->n;
-  if(n == 0)
-    return GHIP_OK;
   hipStream_t st = ctx->stream;
   GCHK(pm_prepare(ctx, N));
+  const size_t n3 = (size_t) N * N * N;
+  const double to_slab_fac = N / p->BoxSize;
+  double *rho = P<double>(ctx->pm_rho);
+  HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
+  if(n > 0)
+    k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
+                                               P<double>(ctx->f[GHIP_F_MASS]), rho);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// (all != nullptr: the mesh is the sum of the nranks all-gathered ones, in rank order) potential mesh,
+// pot[i] += its value at particle i
+int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot)
+{
+  const int N = p->pmgrid, n = ctx->n;
+  hipStream_t st = ctx->stream;
   const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
   const double to_slab_fac = N / p->BoxSize;
   double *rho = P<double>(ctx->pm_rho);
   double2 *fk = P<double2>(ctx->pm_k);
-  HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
-  k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
-                                             P<double>(ctx->f[GHIP_F_MASS]), rho);
-  HIPCHK(hipGetLastError());
+  if(all)
+    {
+      k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, nranks, all, rho);
+      HIPCHK(hipGetLastError());
+    }
   double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;   // :834-835
   asmth2 *= asmth2;
   const double fac = p->G / (M_PI * p->BoxSize);        // :837 (pm.G = All.G)
@@ -314,10 +342,22 @@ int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot)
   k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
   HIPCHK(hipGetLastError());
   FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm_inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
-  k_pm_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, fac, P<double>(ctx->f[GHIP_F_POS]),
-                                                 rho, pot);
+  if(n > 0)
+    k_pm_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, fac, P<double>(ctx->f[GHIP_F_POS]),
+                                                   rho, pot);
   HIPCHK(hipGetLastError());
   return GHIP_OK;
+}
+
+// pot[i] += the periodic PM potential of every particle (ghip_potential, PMGRID builds).  GRAVPM and
+// what ghip_pm_periodic computes are not touched.
+int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot)
+{
+  GCHK(pm_check(ctx, p));
+  if(ctx->n == 0)
+    return GHIP_OK;
+  GCHK(ghip_pm_potential_deposit(ctx, p));
+  return ghip_pm_potential_solve(ctx, p, 1, nullptr, pot);
 }
 
 extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
@@ -338,19 +378,6 @@ extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
   GCHK(pm_solve_and_interpolate(ctx, p));
   HIPCHK(hipEventRecord(ctx->evp[15], st));
   return GHIP_OK;
-}
-
-// rank-ordered sum of the all-gathered meshes (identical on every shard, whatever the transport)
-__global__ void k_pm_sum_meshes(size_t n3, int nranks, const double *__restrict__ all,
-                                double *__restrict__ rho)
-{
-  size_t g = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(g >= n3)
-    return;
-  double s = 0;
-  for(int r = 0; r < nranks; r++)
-    s += all[(size_t) r * n3 + g];
-  rho[g] = s;
 }
 
 // GHIP_DD_PM (ghip_dd_begin / ghip_dd_step): phase 0 deposits and posts the all-gather of the meshes,

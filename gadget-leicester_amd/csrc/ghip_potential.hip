@@ -93,7 +93,11 @@ __device__ __forceinline__ double d_pot_term(double mass, double r, double h)
 // records (a particle's aux is its softening -- Hsml for gas --, a node's aux is its largest
 // softening, negative when the node opens for every target inside it: mixed softenings, or always
 // with adaptive softening).
-template <bool PERIODIC, bool SHORT, bool UNEQUAL, bool REL>
+// SHARD (GHIP_DD_POTENTIAL): the tree is the merged one of a multi-GPU shard.  Its n sources are the shard's
+// own particles (perm < nlocal) and what was imported, particles and pruned nodes (perm >= nlocal): sources,
+// never targets.  A lane that has to open an imported pruned node (a node whose skip link is e + 1) reports
+// it through errw, as the force walk does (ghip_walk.h).
+template <bool PERIODIC, bool SHORT, bool UNEQUAL, bool REL, bool SHARD>
 __global__ void __launch_bounds__(256)
   k_pot_walk(const TreeSizes *__restrict__ ts, int n, const WalkHot *__restrict__ hot,
              const WalkCold *__restrict__ cold, const double *__restrict__ tx,
@@ -101,10 +105,12 @@ __global__ void __launch_bounds__(256)
              const double *__restrict__ tsoft, const double *__restrict__ toldacc,
              const int *__restrict__ perm, const double *__restrict__ potcorr,
              const float *__restrict__ srpot, PotK k, double *__restrict__ pot_out,
-             unsigned long long *__restrict__ nint_out)
+             unsigned long long *__restrict__ nint_out, int nlocal, int *errw)
 {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if(s >= n)
+    return;
+  if(SHARD && perm[s] >= nlocal)
     return;
   const int nelem = ts->nelem;
   const double px = tx[s], py = ty[s], pz = tz[s];
@@ -178,6 +184,8 @@ __global__ void __launch_bounds__(256)
             }
           if(open)
             {
+              if(SHARD && H.skip == e + 1)
+                *(volatile int *) errw = 1;
               e = e + 1;
               continue;
             }
@@ -206,7 +214,7 @@ __global__ void __launch_bounds__(256)
     }
   pot_out[perm[s]] = pot;
   if(nint_out)
-    nint_out[s] = nint;
+    nint_out[perm[s]] = nint;
 }
 
 // potcorr of ewald_init (forcetree.c:4466-4481, 4518-4525): psi(x) / BoxSize at x = 0.5 (i,j,k) / EN,
@@ -328,53 +336,48 @@ extern "C" int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *h
   return GHIP_OK;
 }
 
-extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
+// the argument rules of ghip_potential (and of GHIP_DD_POTENTIAL): everything is checked here, before
+// anything is launched
+static int pot_check(ghip_ctx *ctx, const ghip_pot_params *p, const char *who)
 {
-  if(ctx)
-    GHIP_JOIN(ctx);
-  if(!ctx || !p)
-    return GHIP_EINVAL;
-  if(ctx->dd.on || ctx->shard_n > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: not on a multi-GPU shard");
-  if(!ctx->gt.built)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: call ghip_tree_build first");
-  // every argument is checked here, before anything is launched
   const ghip_grav_params &g = p->grav;
   const ghip_pm_params &pm = p->pm;
   const int pmgrid = pm.pmgrid;
   if(pmgrid != 0)
     {
       if(!g.periodic)
-        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: the non-periodic PM potential is not provided");
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: the non-periodic PM potential is not provided", who);
       if(pmgrid < 4 || pmgrid > 2048 || (pmgrid & 1) || !(pm.BoxSize > 0) || !(pm.Asmth > 0))
-        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
-                         "pm.Asmth > 0");
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
+                         "pm.Asmth > 0", who);
       if(pm.BoxSize != g.BoxSize)
-        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: pm.BoxSize %g differs from grav.BoxSize %g",
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: pm.BoxSize %g differs from grav.BoxSize %g", who,
                          pm.BoxSize, g.BoxSize);
       if(!(g.Rcut > 0 && g.Asmth > 0))
-        return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: a PM potential needs Rcut, Asmth > 0");
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: a PM potential needs Rcut, Asmth > 0", who);
     }
   if(g.periodic && !(g.BoxSize > 0))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: periodic needs BoxSize > 0");
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: periodic needs BoxSize > 0", who);
   for(int t = 0; t < 6; t++)
     if(!(p->SofteningTable[t] > 0))
-      return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: SofteningTable[%d] must be > 0", t);
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: SofteningTable[%d] must be > 0", who, t);
   const bool rel = g.ErrTolTheta == 0;   // (only the relative criterion reads OldAcc)
   for(int f : {GHIP_F_POS, GHIP_F_MASS, GHIP_F_TYPE, GHIP_F_OLDACC})
     if(ctx->n > 0 && !ctx->f[f].p && (f != GHIP_F_OLDACC || rel))
-      return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: particle field %d not set", f);
-  GCHK(ghip_tree_verify(ctx));
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: particle field %d not set", who, f);
+  return GHIP_OK;
+}
+
+// the walk of the gravity tree in place for the context's own particles and potential.c:245-259 (self term,
+// comoving periodic background, * G).  shard: the tree is the merged tree of a multi-GPU shard.
+static int pot_walk_and_finish(ghip_ctx *ctx, const ghip_pot_params *p, bool shard)
+{
+  const ghip_grav_params &g = p->grav;
+  const int pmgrid = p->pm.pmgrid;
+  const bool rel = g.ErrTolTheta == 0;
   const int n = ctx->n;
+  const int nt = shard ? ctx->gt.n : n;   // lanes: the sources of the tree, own particles and imports
   hipStream_t st = ctx->stream;
-  GCHK(ghip_ensure(ctx, ctx->pot, (size_t) (n > 0 ? n : 1) * sizeof(double)));
-  GCHK(ghip_ensure(ctx, ctx->pot_nint, (size_t) (n > 0 ? n : 1) * sizeof(unsigned long long)));
-  ctx->pot_n = -1;
-  if(n == 0)
-    {
-      ctx->pot_n = 0;
-      return GHIP_OK;
-    }
   const bool shortrange = pmgrid > 0;
   const bool periodic = g.periodic != 0;
   const bool ewald = periodic && !shortrange;
@@ -395,23 +398,32 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
   if(rel)
     GCHK(ghip_gather_f64_lim(ctx, ctx->gt.n, P<int>(ctx->gt.perm), P<double>(ctx->f[GHIP_F_OLDACC]), n,
                              P<double>(ctx->soldacc)));
-  const TreeDev &t = ctx->dyn_use ? ctx->dyn : ctx->gt;
+  const TreeDev &t = (ctx->dyn_use && !shard) ? ctx->dyn : ctx->gt;
 #define POT_ARGS                                                                                   \
-  P<TreeSizes>(t.dsz), n, P<WalkHot>(t.mq), P<WalkCold>(t.mq2), P<double>(ctx->sx),                \
+  P<TreeSizes>(t.dsz), nt, P<WalkHot>(t.mq), P<WalkCold>(t.mq2), P<double>(ctx->sx),               \
     P<double>(ctx->sy), P<double>(ctx->sz), P<double>(ctx->ssoft),                                  \
     rel ? P<double>(ctx->soldacc) : nullptr,                                                        \
     P<int>(ctx->gt.perm), ewald ? P<double>(ctx->potcorr) : nullptr,                                \
     shortrange ? P<float>(ctx->srpot) : nullptr, k, P<double>(ctx->pot),                            \
-    P<unsigned long long>(ctx->pot_nint)
-#define POT_LAUNCH(PER, SR, UNEQ, REL)                                                             \
-  k_pot_walk<PER, SR, UNEQ, REL><<<cdiv(n, 256), 256, 0, st>>>(POT_ARGS)
+    P<unsigned long long>(ctx->pot_nint), n, ghip_errword(ctx, GHIP_ERRW_LET)
+#define POT_LAUNCH(PER, SR, UNEQ, REL, SH)                                                         \
+  k_pot_walk<PER, SR, UNEQ, REL, SH><<<cdiv(nt, 256), 256, 0, st>>>(POT_ARGS)
+#define POT_LAUNCH_S(PER, SR, UNEQ, REL)                                                           \
+  do                                                                                               \
+    {                                                                                              \
+      if(shard)                                                                                    \
+        POT_LAUNCH(PER, SR, UNEQ, REL, true);                                                      \
+      else                                                                                         \
+        POT_LAUNCH(PER, SR, UNEQ, REL, false);                                                     \
+    }                                                                                              \
+  while(0)
 #define POT_LAUNCH_R(PER, SR, UNEQ)                                                                \
   do                                                                                               \
     {                                                                                              \
       if(rel)                                                                                      \
-        POT_LAUNCH(PER, SR, UNEQ, true);                                                           \
+        POT_LAUNCH_S(PER, SR, UNEQ, true);                                                         \
       else                                                                                         \
-        POT_LAUNCH(PER, SR, UNEQ, false);                                                          \
+        POT_LAUNCH_S(PER, SR, UNEQ, false);                                                        \
     }                                                                                              \
   while(0)
 #define POT_LAUNCH_U(PER, SR)                                                                      \
@@ -439,6 +451,7 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
     }
 #undef POT_LAUNCH_U
 #undef POT_LAUNCH_R
+#undef POT_LAUNCH_S
 #undef POT_LAUNCH
 #undef POT_ARGS
   HIPCHK(hipGetLastError());
@@ -451,25 +464,166 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
                                              S[0], S[1], S[2], S[3], S[4], S[5], bgfac, p->G,
                                              P<double>(ctx->pot));
   HIPCHK(hipGetLastError());
-  // potential.c:262-265: pmpotential_periodic
-  if(shortrange)
-    GCHK(ghip_pm_potential_add(ctx, &p->pm, P<double>(ctx->pot)));
-  // potential.c:301-325
+  return GHIP_OK;
+}
+
+// potential.c:301-325
+static int pot_quadratic(ghip_ctx *ctx, const ghip_pot_params *p)
+{
+  const int n = ctx->n;
   double qfac = 0;
   if(p->comoving)
     {
-      if(!periodic)
+      if(!p->grav.periodic)
         qfac = -0.5 * p->Omega0 * p->Hubble * p->Hubble;
     }
   else
     qfac = -0.5 * p->OmegaLambda * p->Hubble * p->Hubble;
-  if(qfac != 0)
+  if(qfac != 0 && n > 0)
     {
-      k_pot_quadratic<<<cdiv(n, 256), 256, 0, st>>>(n, P<double>(ctx->f[GHIP_F_POS]), qfac, P<double>(ctx->pot));
+      k_pot_quadratic<<<cdiv(n, 256), 256, 0, ctx->stream>>>(n, P<double>(ctx->f[GHIP_F_POS]), qfac,
+                                                             P<double>(ctx->pot));
       HIPCHK(hipGetLastError());
     }
+  return GHIP_OK;
+}
+
+static int pot_ensure_result(ghip_ctx *ctx)
+{
+  const int n = ctx->n;
+  GCHK(ghip_ensure(ctx, ctx->pot, (size_t) (n > 0 ? n : 1) * sizeof(double)));
+  GCHK(ghip_ensure(ctx, ctx->pot_nint, (size_t) (n > 0 ? n : 1) * sizeof(unsigned long long)));
+  ctx->pot_n = -1;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !p)
+    return GHIP_EINVAL;
+  if(ctx->dd.on)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: on a multi-GPU shard (ghip_dd_init) run the collective "
+                     "GHIP_DD_POTENTIAL through ghip_dd_begin / ghip_dd_run");
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: not on a multi-GPU shard");
+  if(!ctx->gt.built)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_potential: call ghip_tree_build first");
+  GCHK(pot_check(ctx, p, "ghip_potential"));
+  GCHK(ghip_tree_verify(ctx));
+  const int n = ctx->n;
+  GCHK(pot_ensure_result(ctx));
+  if(n == 0)
+    {
+      ctx->pot_n = 0;
+      return GHIP_OK;
+    }
+  GCHK(pot_walk_and_finish(ctx, p, false));
+  // potential.c:262-265: pmpotential_periodic
+  if(p->pm.pmgrid > 0)
+    GCHK(ghip_pm_potential_add(ctx, &p->pm, P<double>(ctx->pot)));
+  GCHK(pot_quadratic(ctx, p));
   ctx->pot_n = n;
   return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// GHIP_DD_POTENTIAL (ghip_dd_begin / ghip_dd_step): compute_potential() on a domain-decomposed shard.
+//   phase 0  the shard's own tree, target groups over ALL its particles (the locally essential tree of the
+//            step's GHIP_DD_GRAVITY was selected against the active targets only)  -> all-gather of the groups
+//   phase 1  selection of the locally essential trees under the opening rules of k_pot_walk, packed
+//                                                                                 -> all-to-all-v of LetRec
+//   phase 2  the merged tree, the walk for the shard's own particles, the finish; what the walk met
+//                                                                                 -> all-gather of the status
+//   phase 3  every shard fails if one did; no mesh: the r^2 term, done.  Mesh: deposit -> all-gather of meshes
+//   phase 4  the meshes added in rank order, solved, read out at the own particles; the r^2 term
+// ---------------------------------------------------------------------------------------------
+int ghip_dd_pot_begin(ghip_ctx *ctx)
+{
+  GHIP_JOIN(ctx);
+  return pot_check(ctx, &ctx->dd.pot, "GHIP_DD_POTENTIAL");
+}
+
+int ghip_dd_pot_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  const ghip_pot_params *p = &D.pot;
+  hipStream_t st = ctx->stream;
+  const int n = ctx->n;
+  const bool mesh = p->pm.pmgrid > 0;
+  if(D.phase == 0)
+    {
+      ctx->pot_n = -1;
+      GCHK(ghip_dd_own_tree(ctx));
+      GCHK(ghip_dd_post_groups(ctx, true, p->grav.ErrTolTheta == 0));
+      D.phase = 1;
+      return 1;
+    }
+  if(D.phase == 1)
+    {
+      GCHK(ghip_dd_post_let(ctx, p->grav, "potential"));
+      D.phase = 2;
+      return 1;
+    }
+  if(D.phase == 2)
+    {
+      D.gt_nimp = D.x.rtotal;
+      GCHK(ghip_tree_build_impl(ctx));
+      D.gt_is_pot = true;
+      D.pot_rc = pot_ensure_result(ctx);
+      if(D.pot_rc == GHIP_OK && n > 0)
+        D.pot_rc = pot_walk_and_finish(ctx, p, true);
+      // did a target have to open a pruned node?  Every shard learns it from every shard's status
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(D.pot_rc == GHIP_OK)
+        D.pot_rc = ghip_check_device_errors(ctx);
+      if(D.pot_rc != GHIP_OK)
+        D.pot_msg = ctx->err;
+      const double mine[2] = {0.0, D.pot_rc != GHIP_OK ? 1.0 : 0.0};
+      GCHK(ghip_ensure(ctx, D.status_own, 16));
+      HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 16, hipMemcpyHostToDevice, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      ghip_dd_set_allgather(D, D.status_own.p, 16, &D.status_all);
+      D.phase = 3;
+      return 1;
+    }
+  if(D.phase == 3)
+    {
+      double all[2 * GHIP_MAXRANKS];
+      HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) D.nranks * 16, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      for(int r = 0; r < D.nranks; r++)
+        if(all[2 * r + 1] != 0)
+          {
+            D.op = 0;
+            if(D.pot_rc != GHIP_OK)
+              return ghip_fail(ctx, D.pot_rc, "%s", D.pot_msg.c_str());
+            return ghip_fail(ctx, GHIP_EDEVICE, "potential: the walk failed on shard %d (its own message says "
+                             "why); every shard stops here", r);
+          }
+      if(mesh)
+        {
+          GCHK(ghip_pm_potential_deposit(ctx, &p->pm));
+          const size_t n3 = (size_t) p->pm.pmgrid * p->pm.pmgrid * p->pm.pmgrid;
+          ghip_dd_set_allgather(D, ctx->pm_rho.p, n3 * sizeof(double), &D.pm_all);
+          D.phase = 4;
+          return 1;
+        }
+      GCHK(pot_quadratic(ctx, p));
+      ctx->pot_n = n;
+      D.op = 0;
+      return 0;
+    }
+  if(D.phase == 4)
+    {
+      GCHK(ghip_pm_potential_solve(ctx, &p->pm, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
+      GCHK(pot_quadratic(ctx, p));
+      ctx->pot_n = n;
+      D.op = 0;
+      return 0;
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the potential has no phase %d", D.phase);
 }
 
 extern "C" int ghip_get_potential(ghip_ctx *ctx, double *host)
@@ -487,7 +641,7 @@ extern "C" int ghip_get_potential(ghip_ctx *ctx, double *host)
   return ghip_check_device_errors(ctx);
 }
 
-// interactions per target of the last ghip_potential, in tree order (sum and maximum)
+// interactions per target of the last ghip_potential (sum and maximum)
 extern "C" int ghip_potential_interactions(ghip_ctx *ctx, long long *sum, long long *maxval)
 {
   if(ctx)
@@ -508,6 +662,22 @@ extern "C" int ghip_potential_interactions(ghip_ctx *ctx, long long *sum, long l
     *sum = s;
   if(maxval)
     *maxval = m;
+  return GHIP_OK;
+}
+
+// ... and per target, host order
+extern "C" int ghip_get_potential_interactions(ghip_ctx *ctx, long long *host)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !host)
+    return GHIP_EINVAL;
+  if(ctx->pot_n != ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_get_potential_interactions: call ghip_potential first");
+  static_assert(sizeof(long long) == sizeof(unsigned long long), "counts are copied as they are");
+  if(ctx->n > 0)
+    HIPCHK(hipMemcpyAsync(host, ctx->pot_nint.p, (size_t) ctx->n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   return GHIP_OK;
 }
 
@@ -639,14 +809,45 @@ __global__ void __launch_bounds__(GQ_BLOCK)
       }
 }
 
+// the arguments and the resident fields the sums read
+static int gq_check(ghip_ctx *ctx, const ghip_global_params *p, const char *who)
+{
+  if(p->ComovingIntegrationOn && (!p->GravKickTable || !p->HydroKickTable))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: comoving runs need the kick tables", who);
+  if(ctx->n == 0)
+    return GHIP_OK;
+  for(int f : {GHIP_F_POS, GHIP_F_VEL, GHIP_F_MASS, GHIP_F_TYPE, GHIP_F_TIMEBIN, GHIP_F_TI_BEGSTEP,
+               GHIP_F_GRAVACCEL})
+    if(!ctx->f[f].p)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: particle field %d not set", who, f);
+  if(p->pmgrid && !ctx->f[GHIP_F_GRAVPM].p)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: PMGRID needs GRAVPM", who);
+  if(ctx->ngas > 0)
+    for(int f : {GHIP_F_HYDROACCEL, GHIP_F_ENTROPY, GHIP_F_DTENTROPY, GHIP_F_DENSITY})
+      if(!ctx->f[f].p)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: gas field %d not set", who, f);
+  return GHIP_OK;
+}
+
+static int gq_local(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums *out);
+
 extern "C" int ghip_global_quantities(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums *out)
 {
   if(ctx)
     GHIP_JOIN(ctx);
   if(!ctx || !p || !out)
     return GHIP_EINVAL;
-  if(ctx->dd.on || ctx->shard_n > 1)
+  if(ctx->dd.on)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: on a multi-GPU shard (ghip_dd_init) run the "
+                     "collective GHIP_DD_GLOBAL_QUANTITIES through ghip_dd_begin / ghip_dd_run");
+  if(ctx->shard_n > 1)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: not on a multi-GPU shard");
+  return gq_local(ctx, p, out);
+}
+
+// the sums over the particles of this context
+static int gq_local(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums *out)
+{
   if(p->ComovingIntegrationOn && (!p->GravKickTable || !p->HydroKickTable))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_global_quantities: comoving runs need the kick tables");
   memset(out, 0, sizeof(*out));
@@ -739,4 +940,56 @@ extern "C" int ghip_global_quantities(ghip_ctx *ctx, const ghip_global_params *p
       out->EnergyRadComp += s[t][13];
     }
   return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// GHIP_DD_GLOBAL_QUANTITIES: phase 0 sums the shard's own particles (k_global_quantities, blocks in block
+// order) and posts the all-gather of its ghip_global_sums; phase 1 adds the shards' sums in rank order --
+// the same additions on every shard, so `out` holds the same bytes everywhere.  (The reference reduces to
+// rank 0 and broadcasts, global.c:146-237.)
+// ---------------------------------------------------------------------------------------------
+#define GQ_SUM_DOUBLES (sizeof(ghip_global_sums) / sizeof(double))
+static_assert(sizeof(ghip_global_sums) % sizeof(double) == 0, "ghip_global_sums is an array of doubles");
+
+int ghip_dd_gq_begin(ghip_ctx *ctx)
+{
+  GHIP_JOIN(ctx);
+  DDState &D = ctx->dd;
+  if(!D.gq.p || !D.gq.out)
+    return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_GLOBAL_QUANTITIES: params needs p and out");
+  D.gq_p = *D.gq.p;
+  return gq_check(ctx, &D.gq_p, "GHIP_DD_GLOBAL_QUANTITIES");
+}
+
+int ghip_dd_gq_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  if(D.phase == 0)
+    {
+      ghip_global_sums mine;
+      GCHK(gq_local(ctx, &D.gq_p, &mine));
+      GCHK(ghip_ensure(ctx, D.gq_send, sizeof(mine)));
+      HIPCHK(hipMemcpyAsync(D.gq_send.p, &mine, sizeof(mine), hipMemcpyHostToDevice, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // (`mine` lives on this frame)
+      ghip_dd_set_allgather(D, D.gq_send.p, sizeof(mine), &D.gq_all);
+      D.phase = 1;
+      return 1;
+    }
+  if(D.phase == 1)
+    {
+      std::vector<double> all((size_t) D.nranks * GQ_SUM_DOUBLES);
+      HIPCHK(hipMemcpyAsync(all.data(), D.gq_all.p, all.size() * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      double s[GQ_SUM_DOUBLES];
+      for(size_t q = 0; q < GQ_SUM_DOUBLES; q++)
+        s[q] = 0;
+      for(int r = 0; r < D.nranks; r++)   // in rank order
+        for(size_t q = 0; q < GQ_SUM_DOUBLES; q++)
+          s[q] += all[(size_t) r * GQ_SUM_DOUBLES + q];
+      memcpy(D.gq.out, s, sizeof(ghip_global_sums));
+      D.op = 0;
+      return 0;
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the global quantities have no phase %d", D.phase);
 }

@@ -2707,12 +2707,14 @@ void gadget_force_bind_potential(void *host_SysState, const struct gadget_force_
   HostSys = lay ? (char *) host_SysState : NULL;
 }
 
+/* NTask > 1: both drivers are collectives over the domain-decomposed device path (GHIP_DD_POTENTIAL,
+ * GHIP_DD_GLOBAL_QUANTITIES) once a transport is bound; without one there is nobody to talk to */
 static int potential_refused(const char *who)
 {
-  if(NTask <= 1)
+  if(NTask <= 1 || RcclConnected || AllgatherFn)
     return 0;
-  snprintf(ErrBuf, sizeof(ErrBuf), "%s: the potential and the energy statistics run on one rank only "
-           "(NTask = %d)", who, NTask);
+  snprintf(ErrBuf, sizeof(ErrBuf), "%s: NTask = %d and no transport: call gadget_force_connect() (RCCL) or "
+           "gadget_force_set_allgather() first", who, NTask);
   fprintf(stderr, "gadget_force: %s\n", ErrBuf);
   endrun(90012);
   return -1;
@@ -2793,8 +2795,8 @@ void compute_potential(void)
       if(chk(ghip_drift(Ctx, &d), "ghip_drift"))
         return;
     }
-  /* potential.c:46-60: the tree gravity_tree() would walk now */
-  if(ensure_tree_split(0))
+  /* potential.c:46-60: the tree gravity_tree() would walk now (ranks: GHIP_DD_POTENTIAL builds its own) */
+  if(NTask == 1 && ensure_tree_split(0))
     return;
   ghip_pot_params pp;
   memset(&pp, 0, sizeof(pp));
@@ -2810,7 +2812,15 @@ void compute_potential(void)
   pp.Omega0 = All.Omega0;
   pp.OmegaLambda = All.OmegaLambda;
   pp.Hubble = All.Hubble;
-  if(chk(ghip_potential(Ctx, &pp), "ghip_potential"))
+  if(NTask > 1)
+    {
+      /* potential.c:75-234 on NTask ranks: the export rounds become one locally essential tree per rank,
+       * selected for ALL particles as targets; every rank enters */
+      Phase = 0;   /* (the trees of this step's gravity_tree() / density() do not survive it) */
+      if(dd_prepare() || dd_collective(GHIP_DD_POTENTIAL, &pp, 0, "compute_potential (ranks)"))
+        return;
+    }
+  else if(chk(ghip_potential(Ctx, &pp), "ghip_potential"))
     return;
   double *pot = (double *) malloc((size_t) (NumPart > 0 ? NumPart : 1) * sizeof(double));
   if(!pot)
@@ -2955,7 +2965,17 @@ void compute_global_quantities_of_system(void)
       gp.Potential = pot;
     }
   ghip_global_sums s;
-  if(!rc)
+  if(!rc && NTask > 1)
+    {
+      /* global.c:146-237 reduces to rank 0 and broadcasts the struct; here every rank adds the ranks' sums
+       * in rank order and holds the same bytes */
+      ghip_dd_global_args a;
+      a.p = &gp;
+      a.out = &s;
+      Phase = 0;
+      rc = dd_prepare() || dd_collective(GHIP_DD_GLOBAL_QUANTITIES, &a, 0, "compute_global_quantities_of_system (ranks)");
+    }
+  else if(!rc)
     rc = chk(ghip_global_quantities(Ctx, &gp, &s), "ghip_global_quantities");
   free(buf), free(pot), free(ph), free(ib);
   /* the device fields now hold the records' state: the next driver uploads and builds again */
@@ -2963,7 +2983,7 @@ void compute_global_quantities_of_system(void)
   TreeOnDevice = 0;
   if(rc)
     return;
-  /* global.c:163-236 (the MPI_Reduce of one rank is the identity) */
+  /* global.c:163-236 (the MPI_Reduce of one rank is the identity; on ranks s already holds the totals) */
   double EnergyTotComp[6], Mass = 0, EnergyKin = 0, EnergyPot = 0, EnergyInt = 0, EnergyTot = 0;
   double Momentum[4] = { 0, 0, 0, 0 }, AngMomentum[4] = { 0, 0, 0, 0 }, CenterOfMass[4] = { 0, 0, 0, 0 };
   for(int i = 0; i < 6; i++)

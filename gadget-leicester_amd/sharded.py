@@ -195,6 +195,20 @@ class DomainShards:
     def migrate(self):
         self.run(self.B.DD_MIGRATE, None)
 
+    def potential(self, params):
+        """GHIP_DD_POTENTIAL(PotParams): afterwards every path's get_potential() / get_potential_interactions()
+        give its own particles"""
+        self.run(self.B.DD_POTENTIAL, params)
+
+    def global_quantities(self, params, tables=None, per_shard=None):
+        """GHIP_DD_GLOBAL_QUANTITIES(GlobalParams): the sums of the whole system as every shard holds them, a
+        list of dicts (GlobalSums.asdict) in shard order.  tables: dict(grav_kick_table=, hydro_kick_table=);
+        per_shard: one dict per shard of its own old_photon_momentum / potential arrays."""
+        built = [self.B.dd_global_args(params, p.n, **(tables or {}), **((per_shard or [{}] * len(self.paths))[r]))
+                 for r, p in enumerate(self.paths)]
+        self.run(self.B.DD_GLOBAL_QUANTITIES, [b[0] for b in built])
+        return [b[1]["out"].asdict() for b in built]
+
 
 class DomainRank:
     """One shard per process.  transport "rccl": the exchanges run in C over RCCL; `bcast(obj)` is
@@ -259,3 +273,17 @@ class DomainRank:
 
     def migrate(self):
         self._run(self.B.DD_MIGRATE, None)
+
+    def potential(self, params):
+        """GHIP_DD_POTENTIAL(PotParams), a collective: afterwards the path's get_potential() gives its own
+        particles"""
+        self._run(self.B.DD_POTENTIAL, params)
+
+    def global_quantities(self, params, grav_kick_table=None, hydro_kick_table=None, old_photon_momentum=None,
+                          potential=None):
+        """GHIP_DD_GLOBAL_QUANTITIES(GlobalParams), a collective: the sums of the whole system (the same bytes
+        on every rank) as a dict (GlobalSums.asdict)"""
+        args, keep = self.B.dd_global_args(params, self.p.n, grav_kick_table, hydro_kick_table,
+                                           old_photon_momentum, potential)
+        self._run(self.B.DD_GLOBAL_QUANTITIES, args)
+        return keep["out"].asdict()

@@ -361,7 +361,13 @@ void gadget_force_flush(void);
  *   a_pm_ti_begstep / a_pm_ti_endstep   All.PM_Ti_begstep / PM_Ti_endstep in the host's `All` bound
  *                          with gadget_force_bind_all (PMGRID builds: the GravPM kick, global.c:96-103)
  *   rad_fac                C / All.UnitVelocity_in_cm_per_s (VIRTUAL; not an offset)
- * Both functions run on one rank only: with NTask > 1 they call endrun(90012).  A missing binding
+ * NTask > 1 with a transport bound (gadget_force_connect or gadget_force_set_allgather): both functions
+ * are collectives that EVERY rank enters, as gravity_tree() is.  compute_potential() uploads this rank's
+ * records, drifts what is behind Ti_Current on the device, runs GHIP_DD_POTENTIAL and writes
+ * P[].p.Potential of this rank's records only; compute_global_quantities_of_system() runs
+ * GHIP_DD_GLOBAL_QUANTITIES and fills the bound SysState on every rank with the same bytes (the reference
+ * reduces to rank 0 and broadcasts the struct, global.c:146-237).  NTask > 1 without a transport: both
+ * call endrun(90012) and write nothing.  cfg.dynamic_tree is not supported on ranks.  A missing binding
  * the build needs (p_potential, the SysState, the PM step or the comoving tables) is endrun(90013). */
 struct gadget_force_potential_layout
 {

@@ -461,7 +461,7 @@ int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p);
  * correction to every interaction (forcetree.c:3514).  Reads POS, MASS, TYPE, OLDACC (relative
  * criterion) and, with adaptive softening, the HSML the tree was built with.  The result stays in a
  * per-context buffer (ghip_get_potential); no GHIP_F_* field changes.  Not on a multi-GPU shard
- * (GHIP_EINVAL).  pm.G is the mesh part's G (All.G, as for ghip_pm_periodic); pm.BoxSize must equal
+ * (GHIP_EINVAL): domain-decomposed shards run the collective GHIP_DD_POTENTIAL (below).  pm.G is the mesh part's G (All.G, as for ghip_pm_periodic); pm.BoxSize must equal
  * grav.BoxSize.  Every argument is checked before anything runs. ---- */
 typedef struct
 {
@@ -477,6 +477,8 @@ int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p);
 int ghip_get_potential(ghip_ctx *ctx, double *host);
 /* interactions of the last walk: summed over the targets and the largest per target */
 int ghip_potential_interactions(ghip_ctx *ctx, long long *sum, long long *maxval);
+/* ... and per target [n], host order (a single context, or a shard after GHIP_DD_POTENTIAL) */
+int ghip_get_potential_interactions(ghip_ctx *ctx, long long *host);
 /* potcorr[65][65][65] of ewald_init, already divided by BoxSize (tests) */
 int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *host);
 
@@ -488,6 +490,8 @@ int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *host);
  * The potential is p->Potential when given, else that of the last ghip_potential -- which holds only
  * while POS, MASS, TYPE and the particle counts are unchanged since (ghip_set_field, ghip_set_counts, the
  * uploads and ghip_drift discard it): call ghip_potential on the current state first.
+ * Domain-decomposed shards run the collective GHIP_DD_GLOBAL_QUANTITIES (below); this call returns
+ * GHIP_EINVAL there.
  * Deterministic: fixed-order partial sums, no atomics.  The totals (sys.EnergyKin = sum of the
  * components, ...) are the host's. ---- */
 typedef struct
@@ -732,6 +736,32 @@ typedef struct
 /* the dust passes (params: ghip_dd_dust_args, see above) */
 #define GHIP_DD_DUST_DENSITY 9   /* needs GHIP_DD_GRAVITY of this step */
 #define GHIP_DD_DUST_DRAG 10     /* needs GHIP_DD_GRAVITY and GHIP_DD_DENSITY of this step */
+/* compute_potential() on shards (params: ghip_pot_params, the argument rules of ghip_potential, checked
+ * by ghip_dd_begin before anything is launched or posted).  The targets are ALL particles of every shard,
+ * so the locally essential trees of the step's GHIP_DD_GRAVITY -- selected against the active targets
+ * only -- do not serve: the operation builds the shard's tree, forms target groups over all its own
+ * particles (with their least OldAcc), all-gathers them, selects / packs / exchanges the tree elements as
+ * GHIP_DD_GRAVITY does, builds the merged tree and walks it for its own particles.  pm.pmgrid > 0: every
+ * shard deposits its own particles, the meshes are all-gathered and added in rank order as in GHIP_DD_PM,
+ * every shard solves and reads out at its own particles.  Afterwards ghip_get_potential /
+ * ghip_get_potential_interactions give the shard's own particles in host order, and
+ * GHIP_DD_GLOBAL_QUANTITIES reads the result; it is discarded where ghip_potential's is, and by
+ * GHIP_DD_MIGRATE.  The gravity tree the operation leaves behind is NOT the one of the step's
+ * GHIP_DD_GRAVITY: the operations that need that one return GHIP_EINVAL until the next GHIP_DD_GRAVITY.
+ * A target that would have to open an imported pruned node makes every shard return GHIP_EDEVICE. */
+#define GHIP_DD_POTENTIAL 11
+/* compute_global_quantities_of_system() on shards (params: ghip_dd_global_args): every shard sums its own
+ * particles as ghip_global_quantities does (the potential: p->Potential, else the shard's last
+ * GHIP_DD_POTENTIAL), the sums are all-gathered and added in rank order on every shard: `out` holds the
+ * same bytes on all shards, on a repeat and for every transport.  No atomics. */
+#define GHIP_DD_GLOBAL_QUANTITIES 12
+typedef struct
+{
+  const ghip_global_params *p;
+  ghip_global_sums *out;
+} ghip_dd_global_args;
+/* bytes this shard sent over links in its last operation `op` (GHIP_DD_*), its own block excluded */
+int ghip_dd_bytes_sent(const ghip_ctx *ctx, int op, long long *bytes);
 
 /* ---- the path ---- */
 int ghip_tree_build(ghip_ctx *ctx, const double DomainCorner[3], const double DomainCenter[3],
