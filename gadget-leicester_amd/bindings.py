@@ -234,7 +234,8 @@ _LIB = None
 ALLGATHER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 EXPORTS = [
-    "ghip_create", "ghip_destroy", "ghip_last_error", "ghip_version", "ghip_set_counts",
+    "ghip_create", "ghip_destroy", "ghip_last_error", "ghip_version", "ghip_device_bytes_in_use",
+    "ghip_set_counts",
     "ghip_set_field", "ghip_get_field", "ghip_upload_aos", "ghip_download_aos", "ghip_set_active",
     "ghip_set_shard", "ghip_tree_build", "ghip_ewald_init", "ghip_ewald_get_table", "ghip_gravity",
     "ghip_gravity_ext", "ghip_gravity_finish", "ghip_gravity_finish_ex", "ghip_gravity_direct",
@@ -274,6 +275,8 @@ def lib():
         L.ghip_last_error.argtypes = [vp]
         L.ghip_last_error.restype = C.c_char_p
         L.ghip_version.restype = C.c_char_p
+        L.ghip_device_bytes_in_use.argtypes = []
+        L.ghip_device_bytes_in_use.restype = C.c_longlong
         L.ghip_set_counts.argtypes = [vp, C.c_int, C.c_int]
         L.ghip_set_field.argtypes = [vp, C.c_int, vp]
         L.ghip_get_field.argtypes = [vp, C.c_int, vp]

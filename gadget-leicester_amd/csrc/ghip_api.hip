@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <dlfcn.h>
+#include <mutex>
 
 #include "ghip_internal.h"
 
@@ -15,39 +16,73 @@
 // ---------------------------------------------------------------------------------------------
 static std::atomic<long long> g_launches{0};
 typedef hipError_t (*launch_fn)(const void *, dim3, dim3, void **, size_t, hipStream_t);
-static launch_fn real_launch(void)
+// Process-wide state, made once by the first ghip_create (process_init) and kept until the process
+// ends: the runtime's hipLaunchKernel and the device error words.  Kernels are only launched on behalf
+// of a context, so both exist wherever they are used.
+static launch_fn g_real_launch = nullptr;
+static int *g_errwords = nullptr;
+static std::once_flag g_process_once;
+
+static launch_fn find_real_launch(void)
 {
-  static launch_fn fn = nullptr;
-  if(!fn)
+  void *p = dlvsym(RTLD_NEXT, "hipLaunchKernel", "hip_4.2");
+  if(!p)
+    p = dlsym(RTLD_NEXT, "hipLaunchKernel");
+  if(!p)
     {
-      void *p = dlvsym(RTLD_NEXT, "hipLaunchKernel", "hip_4.2");
-      if(!p)
-        p = dlsym(RTLD_NEXT, "hipLaunchKernel");
-      if(!p)
+      // the runtime this library is linked against, found through one of its other symbols
+      Dl_info info;
+      if(dladdr((void *) &hipMemsetAsync, &info) && info.dli_fname)
         {
-          // the runtime this library is linked against, found through one of its other symbols
-          Dl_info info;
-          if(dladdr((void *) &hipMemsetAsync, &info) && info.dli_fname)
-            {
-              void *h = dlopen(info.dli_fname, RTLD_LAZY | RTLD_NOLOAD);
-              if(h)
-                p = dlsym(h, "hipLaunchKernel");
-            }
+          void *h = dlopen(info.dli_fname, RTLD_LAZY | RTLD_NOLOAD);
+          if(h)
+            p = dlsym(h, "hipLaunchKernel");
         }
-      fn = (launch_fn) p;
     }
-  return fn;
+  return (launch_fn) p;
 }
 extern "C" hipError_t hipLaunchKernel(const void *function_address, dim3 numBlocks, dim3 dimBlocks,
                                       void **args, size_t sharedMemBytes, hipStream_t stream)
 {
-  launch_fn fn = real_launch();
-  if(!fn)
-    return hipErrorNotInitialized;   // loud: every launch fails
+  if(!g_real_launch)
+    return hipErrorNotInitialized;   // (no context was ever made)
   g_launches.fetch_add(1, std::memory_order_relaxed);
-  return fn(function_address, numBlocks, dimBlocks, args, sharedMemBytes, stream);
+  return g_real_launch(function_address, numBlocks, dimBlocks, args, sharedMemBytes, stream);
 }
 long long ghip_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
+
+// ---------------------------------------------------------------------------------------------
+// Device memory: a DevBuf owns its block.  The bytes held are counted, so that a test can tell that
+// a destroyed context has given everything back.
+// ---------------------------------------------------------------------------------------------
+static std::atomic<long long> g_device_bytes{0};
+extern "C" long long ghip_device_bytes_in_use(void) { return g_device_bytes.load(std::memory_order_relaxed); }
+
+hipError_t DevBuf::alloc(size_t bytes)
+{
+  hipError_t e = hipMalloc(&p, bytes);
+  if(e != hipSuccess)
+    {
+      p = nullptr;
+      return e;
+    }
+  cap = bytes;
+  g_device_bytes.fetch_add((long long) bytes, std::memory_order_relaxed);
+  return hipSuccess;
+}
+
+hipError_t DevBuf::release()
+{
+  hipError_t e = hipSuccess;
+  if(p)
+    {
+      e = hipFree(p);
+      g_device_bytes.fetch_sub((long long) cap, std::memory_order_relaxed);
+    }
+  p = nullptr;
+  cap = 0;
+  return e;
+}
 
 int ghip_fail(ghip_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -78,17 +113,11 @@ int ghip_ensure(ghip_ctx *ctx, DevBuf &b, size_t bytes)
         HIPCHK(ghip_stream_sync(ctx, ctx->stream2));
       if(ctx->stream3)
         HIPCHK(ghip_stream_sync(ctx, ctx->stream3));
-      HIPCHK(hipFree(b.p));
-      b.p = nullptr;
-      b.cap = 0;
+      HIPCHK(b.release());
     }
-  hipError_t e = hipMalloc(&b.p, want);
+  hipError_t e = b.alloc(want);
   if(e != hipSuccess)
-    {
-      b.p = nullptr;
-      return ghip_fail(ctx, GHIP_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    }
-  b.cap = want;
+    return ghip_fail(ctx, GHIP_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
   return GHIP_OK;
 }
 
@@ -115,21 +144,17 @@ int ghip_join(ghip_ctx *ctx)
   return ghip_gas_verify(ctx);
 }
 
-int *ghip_errwords(void)
+int *ghip_errwords(void) { return g_errwords; }
+
+static void process_init(void)
 {
-  static int *words = nullptr;
-  if(!words)
+  g_real_launch = find_real_launch();
+  void *p = nullptr;
+  if(hipHostMalloc(&p, 256, hipHostMallocDefault) == hipSuccess)
     {
-      void *p = nullptr;
-      if(hipHostMalloc(&p, 256, hipHostMallocDefault) != hipSuccess)
-        {
-          static int fallback[64];   // never device-visible: only reached when pinning fails
-          return fallback;
-        }
       memset(p, 0, 256);
-      words = reinterpret_cast<int *>(p);
+      g_errwords = reinterpret_cast<int *>(p);
     }
-  return words;
 }
 
 // call after a stream synchronisation: has a kernel reported a broken invariant?
@@ -143,7 +168,7 @@ int ghip_check_device_errors(ghip_ctx *ctx)
     "essential tree was incomplete",
     "tree emission outside the element list, a malformed imported element (3), a particle outside its "
     "shard's key range (5: migrate first) or outside the domain cube (6: ghip_dd_set_domain with a fresh extent)",
-    "ghost import", "drift", "timestep", "", ""};
+    "", "drift", "timestep", "", ""};
   for(int w = 0; w < GHIP_ERRW_COUNT; w++)
     {
       volatile int *e = ghip_errword(ctx, w);
@@ -167,14 +192,6 @@ int ghip_check_device_errors(ghip_ctx *ctx)
   return GHIP_OK;
 }
 
-static void free_buf(DevBuf &b)
-{
-  if(b.p)
-    (void) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-
 extern "C" const char *ghip_version(void)
 {
   return "ghip 0.3 (gfx950)";
@@ -190,6 +207,17 @@ extern "C" int ghip_create(int device, ghip_ctx **out)
     return GHIP_ENODEVICE;
   if(device < 0 || device >= ndev)
     return GHIP_ENODEVICE;
+  std::call_once(g_process_once, process_init);
+  if(!g_real_launch)
+    {
+      fprintf(stderr, "ghip_create: the HIP runtime's hipLaunchKernel was not found\n");
+      return GHIP_EHIP;
+    }
+  if(!g_errwords)
+    {
+      fprintf(stderr, "ghip_create: the device error words could not be pinned\n");
+      return GHIP_ENOMEM;
+    }
   ghip_ctx *ctx = new(std::nothrow) ghip_ctx();
   if(!ctx)
     return GHIP_ENOMEM;
@@ -212,7 +240,6 @@ extern "C" int ghip_create(int device, ghip_ctx **out)
         delete ctx;
         return GHIP_EHIP;
       }
-  ctx->ev_ready = true;
   ctx->evp = ctx->ev;
   if(hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming) != hipSuccess ||
      hipEventCreateWithFlags(&ctx->ev_sizes, hipEventDisableTiming) != hipSuccess ||
@@ -240,10 +267,9 @@ extern "C" int ghip_create(int device, ghip_ctx **out)
         delete ctx;
         return GHIP_EHIP;
       }
-  ctx->evx_ready = true;
-  // device counters start at zero (hipMalloc does not clear)
-  if(ghip_ensure(ctx, ctx->counters, 64 * 8) != GHIP_OK ||
-     hipMemset(ctx->counters.p, 0, ctx->counters.cap) != hipSuccess)
+  // the scratch words start at zero (hipMalloc does not clear)
+  if(ghip_ensure(ctx, ctx->words, sizeof(DevWords)) != GHIP_OK ||
+     hipMemset(ctx->words.p, 0, ctx->words.cap) != hipSuccess)
     {
       delete ctx;
       return GHIP_ENOMEM;
@@ -256,23 +282,22 @@ extern "C" int ghip_create(int device, ghip_ctx **out)
       delete ctx;
       return GHIP_ENOMEM;
     }
-  // pinned, device-visible host words: tree-build read-back [0..7], device error words [32..39]
-  if(hipHostMalloc(&ctx->pinned, 1024, hipHostMallocDefault) != hipSuccess)
+  // pinned, device-visible host words
+  void *pin = nullptr;
+  if(hipHostMalloc(&pin, sizeof(PinnedWords), hipHostMallocDefault) != hipSuccess)
     {
-      ctx->pinned = nullptr;
       delete ctx;
       return GHIP_ENOMEM;
     }
-  ctx->pinned_cap = 1024;
-  memset(ctx->pinned, 0, 1024);
-  // the trees' sizes: on the device and mirrored in pinned memory ([128..] of the block above)
-  ctx->gt.hsz = reinterpret_cast<TreeSizes *>(reinterpret_cast<char *>(ctx->pinned) + 128);
-  ctx->st.hsz = ctx->gt.hsz + 1;
+  memset(pin, 0, sizeof(PinnedWords));
+  ctx->pinned = reinterpret_cast<PinnedWords *>(pin);
+  // the trees' sizes: on the device and mirrored in pinned memory
+  ctx->gt.hsz = &ctx->pinned->sizes[0];
+  ctx->st.hsz = &ctx->pinned->sizes[1];
   if(ghip_ensure(ctx, ctx->gt.dsz, sizeof(TreeSizes)) != GHIP_OK ||
      ghip_ensure(ctx, ctx->st.dsz, sizeof(TreeSizes)) != GHIP_OK ||
      hipMemset(ctx->gt.dsz.p, 0, sizeof(TreeSizes)) != hipSuccess ||
-     hipMemset(ctx->st.dsz.p, 0, sizeof(TreeSizes)) != hipSuccess ||
-     ghip_ensure(ctx, ctx->run_acc, 80 * 8) != GHIP_OK || hipMemset(ctx->run_acc.p, 0, 80 * 8) != hipSuccess)
+     hipMemset(ctx->st.dsz.p, 0, sizeof(TreeSizes)) != hipSuccess)
     {
       delete ctx;
       return GHIP_ENOMEM;
@@ -285,88 +310,38 @@ extern "C" int ghip_create(int device, ghip_ctx **out)
   return GHIP_OK;
 }
 
-static void free_tree(TreeDev &t)
+ghip_ctx::~ghip_ctx()
 {
-  DevBuf *bs[] = {&t.key, &t.skey, &t.idx, &t.perm, &t.iperm, &t.cpl, &t.cnt, &t.nb,
-                  &t.xm,  &t.cl,   &t.lk,  &t.aux, &t.seg_start, &t.seg_nanc, &t.seg_anc, &t.mq, &t.mq2, &t.phkey, &t.phorder, &t.slvl,
-                  &t.father, &t.arrived, &t.dsz};
-  for(DevBuf *b : bs)
-    free_buf(*b);
+  (void) hipSetDevice(device);
+  for(hipStream_t s : {stream, stream2, stream3})
+    if(s)
+      (void) hipStreamSynchronize(s);
+  ghip_dd_release(this);   // (the communicator and the hipFFT plans go while the streams exist)
+  ghip_pm_release(this);
+  if(pinned)
+    (void) hipHostFree(pinned);
+  for(void *p : host_pins)
+    (void) hipHostUnregister(p);
+  auto destroy = [](hipEvent_t *e, int count) {
+    for(int i = 0; i < count; i++)
+      if(e[i])
+        (void) hipEventDestroy(e[i]);
+  };
+  destroy(ev, 16);
+  destroy(&pc_ev[0][0], 16);
+  destroy(&ev_side, 1);
+  destroy(&ev_sizes, 1);
+  destroy(&ev_sizes_gas, 1);
+  destroy(ev_ring.data(), (int) ev_ring.size());
+  destroy(evx, 4);
+  destroy(evt, 2);
+  for(hipStream_t s : {stream2, stream3, stream})
+    if(s)
+      (void) hipStreamDestroy(s);
 }
 
 extern "C" void ghip_destroy(ghip_ctx *ctx)
 {
-  if(!ctx)
-    return;
-  (void) hipSetDevice(ctx->device);
-
-  if(ctx->stream)
-    (void) hipStreamSynchronize(ctx->stream);
-  if(ctx->stream2)
-    (void) hipStreamSynchronize(ctx->stream2);
-  if(ctx->stream3)
-    (void) hipStreamSynchronize(ctx->stream3);
-  for(int i = 0; i < GHIP_F_COUNT; i++)
-    free_buf(ctx->f[i]);
-  DevBuf *bs[] = {&ctx->stage,  &ctx->aosP,   &ctx->aosS,    &ctx->sx,      &ctx->sy,
-                  &ctx->sz,     &ctx->ssoft,  &ctx->soldacc, &ctx->gp,      &ctx->gq,
-                  &ctx->dleft,  &ctx->dright, &ctx->drho,    &ctx->dnumngb, &ctx->ddhsml,
-                  &ctx->ddivv,  &ctx->drot,   &ctx->dflags,  &ctx->dtgt_a,  &ctx->dtgt_b,
-                  &ctx->act_host_idx, &ctx->tg_grav, &ctx->tg_gas, &ctx->tax, &ctx->tay,
-                  &ctx->taz,    &ctx->tcost,  &ctx->ewtab,   &ctx->ewbrick, &ctx->srtab,   &ctx->cubtmp,
-                  &ctx->counters, &ctx->cslots, &ctx->rslots, &ctx->dhcur, &ctx->hpart, &ctx->plan_nsub, &ctx->plan_woff,
-                  &ctx->plan_wave, &ctx->plan_steps[0][0], &ctx->plan_steps[0][1],
-                  &ctx->plan_steps[1][0], &ctx->plan_steps[1][1], &ctx->plan_steps[2][0],
-                  &ctx->plan_steps[2][1], &ctx->tax2, &ctx->tay2, &ctx->taz2, &ctx->tcost2,
-                  &ctx->plan_nsub2, &ctx->plan_woff2, &ctx->plan_wave2, &ctx->cubtmp2, &ctx->cubtmp3,
-                  &ctx->bh_swallow, &ctx->bh_injected, &ctx->dust_heat, &ctx->dust_idx,
-                  &ctx->dust_work, &ctx->dust_pairs, &ctx->dust_cub, &ctx->sfr_work, &ctx->sfr_cub,
-                  &ctx->pot, &ctx->pot_nint, &ctx->potcorr, &ctx->srpot, &ctx->gq_work,
-                  &ctx->kick_drag, &ctx->kick_ddm, &ctx->kick_newdens};
-  for(DevBuf *b : bs)
-    free_buf(*b);
-  free_tree(ctx->gt);
-  free_tree(ctx->st);
-  ghip_dyn_release(ctx);
-  ghip_dd_release(ctx);
-  ghip_pm_release(ctx);
-  free_buf(ctx->pm_rho);
-  free_buf(ctx->pm_k);
-  free_buf(ctx->pm_force);
-  if(ctx->pinned)
-    (void) hipHostFree(ctx->pinned);
-  for(void *p : ctx->host_pins)
-    (void) hipHostUnregister(p);
-  ctx->host_pins.clear();
-  if(ctx->ev_ready)
-    for(int i = 0; i < 16; i++)
-      (void) hipEventDestroy(ctx->ev[i]);
-  if(ctx->pc_ready)
-    for(int i = 0; i < 4; i++)
-      for(int j = 0; j < 4; j++)
-        (void) hipEventDestroy(ctx->pc_ev[i][j]);
-  if(ctx->ev_side)
-    (void) hipEventDestroy(ctx->ev_side);
-  if(ctx->ev_sizes)
-    (void) hipEventDestroy(ctx->ev_sizes);
-  if(ctx->ev_sizes_gas)
-    (void) hipEventDestroy(ctx->ev_sizes_gas);
-  for(hipEvent_t e : ctx->ev_ring)
-    (void) hipEventDestroy(e);
-  free_buf(ctx->run_acc);
-  if(ctx->evx_ready)
-    {
-      for(int i = 0; i < 4; i++)
-        (void) hipEventDestroy(ctx->evx[i]);
-      for(int i = 0; i < 2; i++)
-        (void) hipEventDestroy(ctx->evt[i]);
-    }
-  if(ctx->stream2)
-    (void) hipStreamDestroy(ctx->stream2);
-  if(ctx->stream3)
-    (void) hipStreamDestroy(ctx->stream3);
-  if(ctx->stream)
-    (void) hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 

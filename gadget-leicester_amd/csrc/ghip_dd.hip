@@ -1083,7 +1083,7 @@ int ghip_dd_dust_groups(ghip_ctx *ctx)
       k_flag_dust_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n,
                                                           P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->dflags));
       HIPCHK(hipGetLastError());
-      int *dnum = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 33);
+      int *dnum = &ghip_words(ctx)->dust_partners;
       size_t tb = 0;
       HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, seq, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
       GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
@@ -1311,7 +1311,7 @@ static int density_step(ghip_ctx *ctx)
           GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
           k_flag_gas_targets<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->tg_grav), P<int>(ctx->gt.perm),
                                                            ng, P<int>(ctx->dflags));
-          int *dnum = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 33);
+          int *dnum = &ghip_words(ctx)->gas_targets;
           size_t tb = 0;
           HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, P<int>(ctx->tg_grav), P<int>(ctx->dflags),
                                                P<int>(D.gas_tgt), dnum, nt, st));
@@ -1384,7 +1384,7 @@ static int density_step(ghip_ctx *ctx)
       double mine[2] = {0.0, 0.0};
       if(D.dens_rc == GHIP_OK && ctx->nt_gas > 0)
         {
-          unsigned long long *dr = P<unsigned long long>(ctx->counters) + 34;
+          unsigned long long *dr = &ghip_words(ctx)->ghost_growth;
           HIPCHK(hipMemsetAsync(dr, 0, 8, st));
           k_ghost_growth<<<cdiv(ctx->nt_gas, 256), 256, 0, st>>>(
             ctx->nt_gas, P<int>(ctx->tg_gas), P<int>(ctx->st.perm), P<double>(ctx->dhcur),
@@ -1747,17 +1747,9 @@ static int migrate_step(ghip_ctx *ctx)
       HIPCHK(hipGetLastError());
       HIPCHK(ghip_stream_sync(ctx, st));
       for(int f = 0; f < GHIP_F_COUNT; f++)
-        {
-          DevBuf t = ctx->f[f];
-          ctx->f[f] = D.fshadow[f];
-          D.fshadow[f] = t;
-        }
+        ctx->f[f].swap(D.fshadow[f]);
       if(heat)
-        {
-          DevBuf t = ctx->dust_heat;
-          ctx->dust_heat = D.heat_shadow;
-          D.heat_shadow = t;
-        }
+        ctx->dust_heat.swap(D.heat_shadow);
       ctx->n = nn;
       ctx->ngas = ngn;
       ctx->gt.built = false;
@@ -1783,7 +1775,6 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
   if(D.x.kind != 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: an exchange is still pending");
   HIPCHK(hipSetDevice(ctx->device));
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
   // the tree GHIP_DD_POTENTIAL leaves behind was selected for other targets than the step's gravity tree
   if(D.gt_is_pot && ctx->gt.built &&
      (op == DD_OP_DENSITY || (op >= GHIP_DD_SINK_DENSITY && op <= GHIP_DD_BH_SWALLOW) ||
@@ -1940,27 +1931,5 @@ void ghip_dd_release(ghip_ctx *ctx)
   if(!ctx)
     return;
   ghip_dd_comm_release(ctx);
-  DDState &D = ctx->dd;
-  DevBuf *bs[] = {&D.status_own, &D.status_all, &D.xstage, &D.grp_own, &D.grp_all, &D.reach, &D.sendm, &D.selcnt, &D.let_list,
-                  &D.let_send, &D.let_recv, &D.src_x, &D.src_y, &D.src_z, &D.src_m, &D.src_aux,
-                  &D.src_key, &D.src_lvl, &D.gh_mask, &D.gh_list, &D.gh_send, &D.gh_recv, &D.gsx,
-                  &D.gsy, &D.gsz, &D.gsm, &D.gsh, &D.h0, &D.gas_tgt, &D.mig_mask, &D.mig_list,
-                  &D.mig_send, &D.mig_recv, &D.mig_scan, &D.gas_src, &D.sk_send, &D.sk_all, &D.sk_part,
-                  &D.sk_parts, &D.sk_work, &D.pm_all, &D.segkey, &D.segowner, &D.ownlo, &D.ownhi,
-                  &D.du_mask, &D.du_slot, &D.du_list, &D.du_send, &D.du_recv, &D.du_part, &D.du_back,
-                  &D.heat_shadow, &D.pot_tgt, &D.gq_send, &D.gq_all};
-  for(DevBuf *b : bs)
-    {
-      if(b->p)
-        (void) hipFree(b->p);
-      b->p = nullptr;
-      b->cap = 0;
-    }
-  for(int f = 0; f < GHIP_F_COUNT; f++)
-    {
-      if(D.fshadow[f].p)
-        (void) hipFree(D.fshadow[f].p);
-      D.fshadow[f].p = nullptr;
-      D.fshadow[f].cap = 0;
-    }
+  ghip_renew(ctx->dd);
 }

@@ -131,8 +131,7 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
   k.minhsml = p->MinGasHsml;
   k.wrap = p->box_wrap;
   k.boxsize = p->BoxSize;
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
-  int *derr = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 40);
+  int *derr = &ghip_words(ctx)->step_err;
   HIPCHK(hipMemsetAsync(derr, 0, 4, st));
   if(k.comoving)
     {

@@ -263,7 +263,7 @@ extern "C" int ghip_tree_export(ghip_ctx *ctx, const ghip_node_layout *lay, int 
 // 2 vmax dt so that the cell still covers its particles, and the momentum the kicked particles gained
 // is folded into vs at the next drift.  Interaction sets on such a tree differ from those on a tree
 // of the current positions, so a host that wants the reference's sub-step forces needs THIS tree.
-// Kept here as a second element list (ctx->dyn): a copy of the gravity tree of the last
+// Kept here as a second element list (ctx->dyn.tree): a copy of the gravity tree of the last
 // ghip_tree_build with (vs, vmax) and the pending kicks per node.  ghip_tree_substep rebuilds the
 // tree of the current positions as ever (target order, the gas tree and everything SPH derive from
 // it; neighbour sets are geometric and do not depend on which tree finds them) and brings the kept
@@ -281,7 +281,7 @@ static int dyn_copy(ghip_ctx *ctx, DevBuf &dst, const DevBuf &src, size_t bytes)
 
 int ghip_dyn_capture(ghip_ctx *ctx)
 {
-  TreeDev &g = ctx->gt, &d = ctx->dyn;
+  TreeDev &g = ctx->gt, &d = ctx->dyn.tree;
   ctx->dyn_valid = false;
   ctx->dyn_use = false;
   if(!g.built || g.n == 0)
@@ -307,23 +307,23 @@ int ghip_dyn_capture(ghip_ctx *ctx)
   GCHK(dyn_copy(ctx, d.perm, g.perm, n * sizeof(int)));
   GCHK(dyn_copy(ctx, d.dsz, g.dsz, sizeof(TreeSizes)));
   d.hsz = g.hsz;
-  GCHK(ghip_ensure(ctx, ctx->dyn_ev, ne * sizeof(double4)));
-  GCHK(ghip_ensure(ctx, ctx->dyn_dp, ne * sizeof(double4)));
-  GCHK(ghip_ensure(ctx, ctx->dyn_kick, ne * sizeof(double4)));
-  GCHK(ghip_ensure(ctx, ctx->dyn_eh, ne * sizeof(double2)));
-  GCHK(ghip_ensure(ctx, ctx->dyn_cnt, ne * 4));
-  GCHK(ghip_ensure(ctx, ctx->dyn_fa, ne * 4));
-  HIPCHK(hipMemsetAsync(ctx->dyn_dp.p, 0, ne * sizeof(double4), st));
+  GCHK(ghip_ensure(ctx, ctx->dyn.ev, ne * sizeof(double4)));
+  GCHK(ghip_ensure(ctx, ctx->dyn.dp, ne * sizeof(double4)));
+  GCHK(ghip_ensure(ctx, ctx->dyn.kick, ne * sizeof(double4)));
+  GCHK(ghip_ensure(ctx, ctx->dyn.eh, ne * sizeof(double2)));
+  GCHK(ghip_ensure(ctx, ctx->dyn.cnt, ne * 4));
+  GCHK(ghip_ensure(ctx, ctx->dyn.fa, ne * 4));
+  HIPCHK(hipMemsetAsync(ctx->dyn.dp.p, 0, ne * sizeof(double4), st));
   const int nelem = g.nelem;
   // vs, vmax per element (force_update_node_recursive, forcetree.c:560-611, 830-846)
   k_ext_particles<<<cdiv(nelem, 256), 256, 0, st>>>(
     nelem, ctx->n, ctx->ngas, P<int4>(d.lk), P<int>(d.perm), P<double>(ctx->f[GHIP_F_VEL]),
     P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]),
-    P<double4>(ctx->dyn_ev), P<double2>(ctx->dyn_eh), P<int>(ctx->dyn_cnt), P<int>(ctx->dyn_fa));
+    P<double4>(ctx->dyn.ev), P<double2>(ctx->dyn.eh), P<int>(ctx->dyn.cnt), P<int>(ctx->dyn.fa));
   for(int L = d.maxlevel; L >= 0; L--)
     k_ext_level<<<cdiv(nelem, 256), 256, 0, st>>>(nelem, L, P<int4>(d.lk), P<double4>(d.xm),
-                                                  P<double4>(ctx->dyn_ev), P<double2>(ctx->dyn_eh),
-                                                  P<int>(ctx->dyn_cnt), P<int>(ctx->dyn_fa));
+                                                  P<double4>(ctx->dyn.ev), P<double2>(ctx->dyn.eh),
+                                                  P<int>(ctx->dyn.cnt), P<int>(ctx->dyn.fa));
   HIPCHK(hipGetLastError());
   d.built = true;
   GCHK(ghip_build_segments(ctx, d, true));
@@ -333,17 +333,7 @@ int ghip_dyn_capture(ghip_ctx *ctx)
 
 void ghip_dyn_release(ghip_ctx *ctx)
 {
-  DevBuf *bs[] = {&ctx->dyn.xm, &ctx->dyn.cl, &ctx->dyn.lk, &ctx->dyn.aux, &ctx->dyn.perm, &ctx->dyn.dsz,
-                  &ctx->dyn.seg_start, &ctx->dyn.seg_nanc, &ctx->dyn.seg_anc, &ctx->dyn.mq, &ctx->dyn.mq2,
-                  &ctx->dyn_ev, &ctx->dyn_dp, &ctx->dyn_eh, &ctx->dyn_cnt, &ctx->dyn_fa, &ctx->dyn_kick,
-                  &ctx->kick_dv, &ctx->kick_flag};
-  for(DevBuf *b : bs)
-    {
-      if(b->p)
-        (void) hipFree(b->p);
-      b->p = nullptr;
-      b->cap = 0;
-    }
+  ghip_renew(ctx->dyn);
   ctx->dyn_valid = ctx->dyn_use = false;
 }
 
@@ -413,15 +403,15 @@ __global__ void k_dyn_kick_level(int nelem, int level, const int4 *__restrict__ 
 
 static int dyn_kick_pass(ghip_ctx *ctx, const double *dv, const int *flag, const double *vmaxk = nullptr)
 {
-  TreeDev &d = ctx->dyn;
+  TreeDev &d = ctx->dyn.tree;
   hipStream_t st = ctx->stream;
   const int nelem = d.nelem;
   k_dyn_kick_particles<<<cdiv(nelem, 256), 256, 0, st>>>(
     nelem, ctx->n, P<int4>(d.lk), P<int>(d.perm), P<double>(ctx->f[GHIP_F_MASS]),
-    P<double>(ctx->f[GHIP_F_VEL]), dv, vmaxk, flag, P<double4>(ctx->dyn_kick));
+    P<double>(ctx->f[GHIP_F_VEL]), dv, vmaxk, flag, P<double4>(ctx->dyn.kick));
   for(int L = d.maxlevel; L >= 0; L--)
-    k_dyn_kick_level<<<cdiv(nelem, 256), 256, 0, st>>>(nelem, L, P<int4>(d.lk), P<double4>(ctx->dyn_kick),
-                                                       P<double4>(ctx->dyn_dp), P<double4>(ctx->dyn_ev));
+    k_dyn_kick_level<<<cdiv(nelem, 256), 256, 0, st>>>(nelem, L, P<int4>(d.lk), P<double4>(ctx->dyn.kick),
+                                                       P<double4>(ctx->dyn.dp), P<double4>(ctx->dyn.ev));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -429,9 +419,9 @@ static int dyn_kick_pass(ghip_ctx *ctx, const double *dv, const int *flag, const
 // what the last ghip_advance_timesteps recorded (kick_dv, kick_flag)
 int ghip_dyn_kick_recorded(ghip_ctx *ctx)
 {
-  if(!ctx->dyn_on || !ctx->dyn_valid || ctx->dyn.n != ctx->n)
+  if(!ctx->dyn_on || !ctx->dyn_valid || ctx->dyn.tree.n != ctx->n)
     return GHIP_OK;
-  return dyn_kick_pass(ctx, P<double>(ctx->kick_dv), P<int>(ctx->kick_flag));
+  return dyn_kick_pass(ctx, P<double>(ctx->dyn.kick_dv), P<int>(ctx->dyn.kick_flag));
 }
 
 // (a particle kicked twice at one sync point -- gravity, then a feedback kick -- hands up the sum of
@@ -481,8 +471,8 @@ static int kick_nodes_host(ghip_ctx *ctx, int nkicked, const int *idx, const dou
     return GHIP_OK;
   const size_t n = (size_t) ctx->n;
   hipStream_t st = ctx->stream;
-  GCHK(ghip_ensure(ctx, ctx->kick_dv, 4 * n * 8));
-  GCHK(ghip_ensure(ctx, ctx->kick_flag, n * 4));
+  GCHK(ghip_ensure(ctx, ctx->dyn.kick_dv, 4 * n * 8));
+  GCHK(ghip_ensure(ctx, ctx->dyn.kick_flag, n * 4));
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) nkicked * 36 + 64));
   int *didx = P<int>(ctx->stage);
   double *ddv = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->stage.p) + (((size_t) nkicked * 4 + 15) & ~(size_t) 15));
@@ -491,12 +481,12 @@ static int kick_nodes_host(ghip_ctx *ctx, int nkicked, const int *idx, const dou
   HIPCHK(hipMemcpyAsync(ddv, dv3, (size_t) nkicked * 24, hipMemcpyHostToDevice, st));
   if(vmaxk)
     HIPCHK(hipMemcpyAsync(dvm, vmaxk, (size_t) nkicked * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(ctx->kick_flag.p, 0, n * 4, st));
-  HIPCHK(hipMemsetAsync(ctx->kick_dv.p, 0, 4 * n * 8, st));
+  HIPCHK(hipMemsetAsync(ctx->dyn.kick_flag.p, 0, n * 4, st));
+  HIPCHK(hipMemsetAsync(ctx->dyn.kick_dv.p, 0, 4 * n * 8, st));
   k_dyn_scatter_kicks<<<cdiv(nkicked, 256), 256, 0, st>>>(nkicked, ctx->n, didx, ddv, vmaxk ? dvm : nullptr,
-                                                          P<double>(ctx->kick_dv), P<int>(ctx->kick_flag));
-  GCHK(dyn_kick_pass(ctx, P<double>(ctx->kick_dv), P<int>(ctx->kick_flag),
-                     vmaxk ? P<double>(ctx->kick_dv) + 3 * n : nullptr));
+                                                          P<double>(ctx->dyn.kick_dv), P<int>(ctx->dyn.kick_flag));
+  GCHK(dyn_kick_pass(ctx, P<double>(ctx->dyn.kick_dv), P<int>(ctx->dyn.kick_flag),
+                     vmaxk ? P<double>(ctx->dyn.kick_dv) + 3 * n : nullptr));
   HIPCHK(ghip_stream_sync(ctx, st));   // (idx / dv3 are the caller's)
   return GHIP_OK;
 }
@@ -556,17 +546,17 @@ extern "C" int ghip_tree_substep(ghip_ctx *ctx, double dt_drift)
   if(!ctx->dyn_on || !ctx->dyn_valid)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_tree_substep: no kept tree (ghip_set_dynamic_tree, then a full "
                      "ghip_tree_build)");
-  if(ctx->dyn.n != ctx->n)
+  if(ctx->dyn.tree.n != ctx->n)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_tree_substep: the particle number changed since the full build "
-                     "(%d -> %d): rebuild", ctx->dyn.n, ctx->n);
+                     "(%d -> %d): rebuild", ctx->dyn.tree.n, ctx->n);
   // the tree of the current positions: target order, the gas tree, everything SPH
   ctx->dyn_use = false;
   GCHK(ghip_tree_build_impl(ctx));
-  TreeDev &d = ctx->dyn;
+  TreeDev &d = ctx->dyn.tree;
   k_dyn_drift<<<cdiv(d.nelem, 256), 256, 0, ctx->stream>>>(
     d.nelem, ctx->n, P<int4>(d.lk), P<int>(d.perm), P<double>(ctx->f[GHIP_F_POS]),
-    P<double>(ctx->f[GHIP_F_MASS]), dt_drift, P<double4>(d.xm), P<double4>(d.cl), P<double4>(ctx->dyn_ev),
-    P<double4>(ctx->dyn_dp));
+    P<double>(ctx->f[GHIP_F_MASS]), dt_drift, P<double4>(d.xm), P<double4>(d.cl), P<double4>(ctx->dyn.ev),
+    P<double4>(ctx->dyn.dp));
   HIPCHK(hipGetLastError());
   GCHK(ghip_fill_walk_records(ctx, d));
   ctx->dyn_use = true;
@@ -581,7 +571,7 @@ extern "C" int ghip_tree_dump_dynamic(ghip_ctx *ctx, int *nelem, double *xm4, do
   GHIP_JOIN(ctx);
   if(!ctx->dyn_valid)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_tree_dump_dynamic: no kept tree");
-  TreeDev &d = ctx->dyn;
+  TreeDev &d = ctx->dyn.tree;
   *nelem = d.nelem;
   hipStream_t st = ctx->stream;
   const size_t ne = (size_t) d.nelem;
@@ -590,7 +580,7 @@ extern "C" int ghip_tree_dump_dynamic(ghip_ctx *ctx, int *nelem, double *xm4, do
   if(cl4)
     HIPCHK(hipMemcpyAsync(cl4, d.cl.p, ne * 32, hipMemcpyDeviceToHost, st));
   if(ev4)
-    HIPCHK(hipMemcpyAsync(ev4, ctx->dyn_ev.p, ne * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ev4, ctx->dyn.ev.p, ne * 32, hipMemcpyDeviceToHost, st));
   if(lk4)
     HIPCHK(hipMemcpyAsync(lk4, d.lk.p, ne * 16, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));

@@ -486,7 +486,6 @@ static int build_plan(ghip_ctx *ctx, int kind, int nb, int ns, WalkPlan &plan, i
         if(k == cur)
           prev_kept = false;
       }
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
   const bool adaptive = !(getenv("GHIP_WALK_ADAPTIVE") && atoi(getenv("GHIP_WALK_ADAPTIVE")) == 0);
   // history of the kind's previous call: usable when that call had about as many buckets (a
   // shard's particle number changes with every migration, the merged tree's segment count may too;
@@ -670,7 +669,7 @@ static int prepare_job(ghip_ctx *ctx, const ghip_grav_params *p, int walk, int n
   GCHK(prepare_tables(ctx, p, walk, J.k));
   // (a sub-step on the kept tree of the last full build walks THAT element list; the targets, their
   // order and the result mapping stay those of the tree of the current positions)
-  walk_layout(ctx->dyn_use ? ctx->dyn : ctx->gt, nt, J.sg, &J.nbuckets, walk == GHIP_WALK_EWALD);
+  walk_layout(ctx->dyn_use ? ctx->dyn.tree : ctx->gt, nt, J.sg, &J.nbuckets, walk == GHIP_WALK_EWALD);
   GCHK(build_plan(ctx, walk == GHIP_WALK_EWALD ? 1 : 0, J.nbuckets, J.sg.ns, J.plan, slot, ps));
   GCHK(ensure_partials(ctx, J.plan.nwaves, slot, J.pb));
   J.counter = ghip_cslot(ctx, walk == GHIP_WALK_EWALD ? GHIP_CK_EWALD : GHIP_CK_NEWTON);
@@ -683,7 +682,7 @@ static int run_walk(ghip_ctx *ctx, const WalkJob &J, int nt, const int *tgt, hip
   int evi = (J.walk == GHIP_WALK_EWALD) ? 4 : 2;
   ctx->plan_writer[J.walk == GHIP_WALK_EWALD ? 1 : 0] = st;
   HIPCHK(hipEventRecord(ctx->evp[evi], st));
-  launch_walk_any(ctx, J.walk, ctx->dyn_use ? ctx->dyn : ctx->gt, J.sg, J.nbuckets, nt, tgt, P<double>(ctx->sx),
+  launch_walk_any(ctx, J.walk, ctx->dyn_use ? ctx->dyn.tree : ctx->gt, J.sg, J.nbuckets, nt, tgt, P<double>(ctx->sx),
                   P<double>(ctx->sy), P<double>(ctx->sz), P<double>(ctx->ssoft),
                   P<double>(ctx->soldacc), J.k, J.counter, J.plan, J.pb, st);
   HIPCHK(hipGetLastError());
@@ -710,12 +709,12 @@ static int combine_walk(ghip_ctx *ctx, const WalkJob &J, int nt, const int *tgt,
 // again for one measurement every 64 pairs.  Scheduling only: the sums of a launch do not depend on it.
 static int pair_balance(ghip_ctx *ctx)
 {
-  if(!ctx->pc_ready)
+  if(!ctx->pc_ev[3][3])
     {
       for(int i = 0; i < 4; i++)
         for(int j = 0; j < 4; j++)
-          HIPCHK(hipEventCreate(&ctx->pc_ev[i][j]));
-      ctx->pc_ready = true;
+          if(!ctx->pc_ev[i][j])
+            HIPCHK(hipEventCreate(&ctx->pc_ev[i][j]));
       return GHIP_OK;
     }
   for(int i = 0; i < 4; i++)
@@ -840,7 +839,7 @@ int ghip_gravity_impl(ghip_ctx *ctx, const ghip_grav_params *p, int walk)
   HIPCHK(hipEventRecord(pc[1], sN));
   // (the word the hydro kernel's start waits for, see k_grav_walk: a stale 1 from the previous pair
   // would only let hydro start early, never hold it back)
-  unsigned int *started = reinterpret_cast<unsigned int *>(P<unsigned long long>(ctx->counters) + 20);
+  unsigned int *started = &ghip_words(ctx)->pair_started;
   HIPCHK(hipMemsetAsync(started, 0, 4, sE));
   E.plan.started = started;
   HIPCHK(hipEventRecord(pc[2], sE));
@@ -923,13 +922,13 @@ extern "C" int ghip_gravity_ext_soft(ghip_ctx *ctx, const ghip_grav_params *p, i
   HIPCHK(hipMemcpyAsync(dtype, type, (size_t) nt * 4, hipMemcpyHostToDevice, st));
   WalkSeg sg;
   int nbuckets;
-  walk_layout(ctx->dyn_use ? ctx->dyn : ctx->gt, nt, sg, &nbuckets, walk == GHIP_WALK_EWALD);
+  walk_layout(ctx->dyn_use ? ctx->dyn.tree : ctx->gt, nt, sg, &nbuckets, walk == GHIP_WALK_EWALD);
   WalkPlan plan;
   GCHK(build_plan(ctx, 2, nbuckets, sg.ns, plan));
   PartialBufs pb;
   GCHK(ensure_partials(ctx, plan.nwaves, 0, pb));
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_EXT);
-  launch_walk_any(ctx, walk, ctx->dyn_use ? ctx->dyn : ctx->gt, sg, nbuckets, nt, nullptr, dx, dy, dz, dsoft, dold, k,
+  launch_walk_any(ctx, walk, ctx->dyn_use ? ctx->dyn.tree : ctx->gt, sg, nbuckets, nt, nullptr, dx, dy, dz, dsoft, dold, k,
                   counter, plan, pb, st);
   k_combine_grav<<<cdiv(nt, 256), 256, 0, st>>>(nt, plan, nullptr, nullptr, P<double>(ctx->tax),
                                                P<double>(ctx->tay), P<double>(ctx->taz),

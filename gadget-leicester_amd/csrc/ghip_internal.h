@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -35,11 +36,38 @@ static inline __host__ __device__ unsigned int ghip_ew_offset(int i, int j, int 
 // ---------------------------------------------------------------------------------------------
 // host-side helpers
 // ---------------------------------------------------------------------------------------------
+// A block of device memory and its owner: a device allocation of the library is a DevBuf member of
+// the context (or of one of its sub-objects) and is freed with it -- there is no list to add it to.
+// Sized by ghip_ensure; the bytes all DevBufs of the process hold are counted
+// (ghip_device_bytes_in_use).
 struct DevBuf
 {
   void *p = nullptr;
   size_t cap = 0;  // bytes
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { (void) release(); }
+  hipError_t alloc(size_t bytes);   // of an empty DevBuf (ghip_api.hip)
+  hipError_t release();             // back to empty; what hipFree said
+  void swap(DevBuf &o)              // the two exchange their blocks
+  {
+    void *tp = p;
+    size_t tc = cap;
+    p = o.p;
+    cap = o.cap;
+    o.p = tp;
+    o.cap = tc;
+  }
 };
+
+// Gives back everything a sub-object of the context owns: it is destroyed and a fresh one made in
+// its place, so that its DevBuf members free themselves and its other members start over.
+template <class T> static inline void ghip_renew(T &x)
+{
+  x.~T();
+  new(&x) T();
+}
 
 // Sizes of a tree as the DEVICE knows them: written by k_tree_info at the end of the counting stage
 // of a build, into device memory (the build's later kernels and every hot-path consumer read them
@@ -192,7 +220,6 @@ struct DDState
   std::string local_msg;
   int dens_rc = 0;                // ... and in the h iteration of the density call in progress
   std::string dens_msg;
-  DevBuf gh_ratio;                // f64[2]: largest Hsml growth seen by the density iterations
   DevBuf gsx, gsy, gsz, gsm, gsh; // gas sources = local gas + ghosts (tree build input)
   DevBuf h0;                      // f64[ngas]: smoothing lengths the ghost selection was made with
   // migration (domain_exchange): destination masks, send lists, records, shadow field arrays
@@ -261,8 +288,61 @@ static inline void ghip_dd_set_alltoallv(DDState &D, const void *send, size_t re
     }
 }
 
+// Named scratch words of a context in device memory (ctx->words, made and zeroed by ghip_create):
+// one field per use, so that no two uses share a word by accident.  ghip_words(ctx) -> the block.
+struct DevWords
+{
+  // own line: the main stream polls it (ghip_hydro_impl) while kernels of other streams write the rest
+  alignas(128) unsigned int pair_started;   // the pair's Ewald walk has dispatched its last workgroup
+  alignas(128) unsigned long long ghost_growth;   // density on shards: largest h growth (bits of a double)
+  unsigned long long timebin_hist[64];      // ghip_timebin_counts: all particles [0, 32), gas [32, 64)
+  int sel_left;        // ghip_density_impl: targets left after an h iteration (k_sel_scan)
+  int list_count;      // make_list (ghip_tree.hip): targets selected
+  int dust_partners;   // ghip_dd_dust_groups: local Type 0 / Type 2 particles selected
+  int gas_targets;     // density on shards: gas targets selected
+  int step_err;        // ghip_drift / ghip_advance_timesteps: what the kernel met
+  int tree_info[2][2]; // count_nodes, per tree (gravity, gas): {deepest level, longest key run the
+                       // 32-bit sort left unsorted}; k_tree_info reads them and leaves them zeroed
+};
+
+// ... and in pinned, device-visible host memory (ctx->pinned): kernels write, the host reads after a wait
+struct alignas(64) PinnedWords
+{
+  TreeSizes sizes[2];   // host mirrors of the trees' sizes (gt.hsz, st.hsz)
+  int gas_mixed;        // the record unpack met a record of the gas block [0, ngas) that is not Type 0
+};
+
+// the gravity tree between two full builds with what moves it (ghip_set_dynamic_tree, ghip_export.hip)
+struct DynTree
+{
+  TreeDev tree;
+  DevBuf ev, dp;             // double4[nelem]: (vs, vmax) / (dp, kicked) per element
+  DevBuf eh, cnt, fa;        // scratch of the moment pass (export's kernels)
+  DevBuf kick;               // double4[nelem]: a kick pass's per-element sums
+  DevBuf kick_dv, kick_flag; // f64[3][n], i32[n]: velocity changes of the last ghip_advance_timesteps
+};
+
+// particle-mesh force (ghip_pm.hip): hipFFT plans for n^3, mesh buffers
+struct PmMesh
+{
+  int n = 0;
+  void *fwd = nullptr, *inv = nullptr;   // hipfftHandle, destroyed with the mesh
+  DevBuf rho, k, force;
+  PmMesh() = default;
+  PmMesh(const PmMesh &) = delete;
+  PmMesh &operator=(const PmMesh &) = delete;
+  ~PmMesh();
+};
+
 struct ghip_ctx
 {
+  ghip_ctx() = default;
+  ghip_ctx(const ghip_ctx &) = delete;
+  ghip_ctx &operator=(const ghip_ctx &) = delete;
+  // waits for the streams, then destroys every handle that was made (all start as nullptr); the
+  // members free their device memory afterwards
+  ~ghip_ctx();
+
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
@@ -272,8 +352,7 @@ struct ghip_ctx
   DevBuf f[GHIP_F_COUNT];
   // staging for host<->device transfers / AoS images
   DevBuf stage, aosP, aosS;
-  void *pinned = nullptr;
-  size_t pinned_cap = 0;
+  PinnedWords *pinned = nullptr;   // hipHostMalloc
 
   // domain
   double corner[3] = {0, 0, 0}, center[3] = {0, 0, 0}, dlen = 0;
@@ -312,16 +391,15 @@ struct ghip_ctx
   hipStream_t stream3 = nullptr;   // ... and its Newtonian walk here, so the main stream stays free
   bool adaptive_gravsoft = false;   // ADAPTIVE_GRAVSOFT_FORGAS: gas softening = Hsml (ghip_set_adaptive_gravsoft)
   bool grav_pending = false;       // a pair is in flight; evx[2] marks its end (see ghip_join)
-  unsigned int *pair_started = nullptr;   // device word: the pair's Ewald walk has dispatched its last workgroup
+  unsigned int *pair_started = nullptr;   // &DevWords::pair_started once a pair has run
   // the second half of the gas tree build (elements, moments, SphNode records, gas records) is
   // deferred to the first call that needs it, so that it runs underneath a gravity pair
   bool gas_pending = false;
   bool gas_wait_upload = false;   // ghip_upload_aos_particles done, ghip_upload_aos_gas not yet: the
                                    // deferred gas-tree work must not run on stale SphP fields
-  hipEvent_t evx[4];               // pair ordering: inputs ready / Newton combined / Ewald combined /
+  hipEvent_t evx[4] = {};          // pair ordering: inputs ready / Newton combined / Ewald combined /
                                    // Ewald walk kernel done (ghip_hydro waits for it)
-  bool evx_ready = false;
-  hipEvent_t evt[2];               // tree build: fork after the tree-order gather / join (curve_order
+  hipEvent_t evt[2] = {};          // tree build: fork after the tree-order gather / join (curve_order
                                    // runs on stream2 next to the element emission on the main stream)
   // adaptive wavefront plan of the gravity walks (ghip_walk.h): per walk kind the elements
   // visited per bucket in the previous call (double-buffered) and the scratch plan arrays
@@ -340,17 +418,13 @@ struct ghip_ctx
 
   // scan/sort temp
   DevBuf cubtmp;
-  // particle-mesh force (ghip_pm.hip): hipFFT plans for pm_n^3, mesh buffers
-  int pm_n = 0;
-  void *pm_fwd = nullptr, *pm_inv = nullptr;
-  DevBuf pm_rho, pm_k, pm_force;
-  // counters (device): 8 x u64
-  DevBuf counters;
+  PmMesh pm;
+  DevBuf words;   // DevWords
   // work counters of the walks and the SPH kernels, 64 slots per kind (ghip_count.h): of the current
   // calls (each call of a kind clears its own) and of the run (ghip_run_begin clears)
   DevBuf cslots, rslots;
   ghip_stats stats;
-  hipEvent_t ev[16];
+  hipEvent_t ev[16] = {};
   DDState dd;                // multi-GPU domain decomposition (ghip_dd.hip)
   DevBuf bh_swallow, bh_injected;   // "next" row N4 (ghip_sink.hip): P[].SwallowID u32[n],
                                     // SphP[].i.Injected_BH_Energy f64[ngas]
@@ -364,7 +438,6 @@ struct ghip_ctx
   DevBuf kick_drag, kick_ddm, kick_newdens;   // f64[3][ngas], f64[3][ngas], f64[n]
   bool has_drag = false, has_ddm = false, has_newdens = false;
   int kick_fields_n = -1, kick_fields_ngas = -1;   // counts the fields were set for
-  bool ev_ready = false;
 
   // ---- asynchronous tree build (ghip_tree.hip) ----
   // A build whose particle number equals the previous build's is enqueued without the host waiting
@@ -396,31 +469,25 @@ struct ghip_ctx
   // the last full build's element list whose nodes are drifted and kicked as forcetree.c:1356-1520
   // does; the gravity walks of a sub-step read it instead of the tree of the current positions ----
   bool dyn_on = false, dyn_valid = false, dyn_use = false;
-  TreeDev dyn;
-  DevBuf dyn_ev, dyn_dp;           // double4[nelem]: (vs, vmax) / (dp, kicked) per element
-  DevBuf dyn_eh, dyn_cnt, dyn_fa;  // scratch of the moment pass (export's kernels)
-  DevBuf dyn_kick;                 // double4[nelem]: a kick pass's per-element sums
-  DevBuf kick_dv, kick_flag;       // f64[3][n], i32[n]: velocity changes of the last ghip_advance_timesteps
+  DynTree dyn;
   // balance of a Newton + Ewald pair (ghip_gravity.hip, pair_balance): dynamic LDS per Newtonian
   // workgroup in use, and a ring of the last pairs' start / end events with the cap they ran under
   int pair_lds = 10240;
-  hipEvent_t pc_ev[4][4] = {};
+  hipEvent_t pc_ev[4][4] = {};         // made by the first pair
   int pc_cap[4] = {0, 0, 0, 0};        // 0: slot empty or already read
   int pc_hyd[4] = {0, 0, 0, 0};        // the hydro kernel was queued underneath that pair
   int pc_head = 0;
-  bool pc_ready = false;
   float pc_cost[2] = {-1.f, -1.f};     // last measured cost of a pair under 8 KB / 10 KB
   int pc_age[2] = {0, 0};              // pairs launched since that measurement
   hipEvent_t ev_side = nullptr;    // end of ghip_gravity_to_records' work on the pair's stream
 
   // ---- run statistics without a host synchronisation per step (ghip_run_begin / ghip_step_begin /
-  // ghip_step_end / ghip_get_run_stats): a ring of event sets, device-side accumulated counters ----
+  // ghip_step_end / ghip_get_run_stats): a ring of event sets, the run's counter slots (rslots) ----
   std::vector<hipEvent_t> ev_ring;     // [slots][GHIP_NEV + 2]: phase events + step begin / end marks
   int ring_slots = 0, ring_cur = -1;   // ring_cur < 0: the fixed set ev[] is in use
   hipEvent_t *evp = nullptr;           // the event set in use (ev[] or a ring slot)
   long long run_steps = 0, run_syncs0 = 0, run_launches0 = 0, run_dens_iter = 0;
   long long n_syncs = 0;               // blocking host waits inside the library since creation
-  DevBuf run_acc;                      // u64[16]: counters summed over the steps of a run
   // ---- ghip_potential / ghip_global_quantities (ghip_potential.hip) ----
   DevBuf pot;                      // f64[n]: P[].p.Potential of the last ghip_potential, host order
   DevBuf pot_nint;                 // u64[n]: its interactions per target, host order
@@ -454,12 +521,12 @@ int ghip_fail(ghip_ctx *ctx, int code, const char *fmt, ...);
 #define GHIP_ERRW_PLAN 0     // wavefront plan of a gravity walk exceeded its grid (ghip_walk.h)
 #define GHIP_ERRW_LET 1      // a target wanted to open a pruned node of another shard's tree
 #define GHIP_ERRW_TREE 2     // tree emission wrote outside the element list / malformed import
-#define GHIP_ERRW_GHOST 3    // spare
+                             // (3: spare)
 #define GHIP_ERRW_DRIFT 4    // a particle was ahead of the drift target (reference: endrun(12), predict.c:148)
 #define GHIP_ERRW_TIMESTEP 5 // the endrun code of a failed timestep criterion (888, 818, 112313)
 #define GHIP_ERRW_COUNT 8
 // (one block per process, shared by its contexts: an error raised by a kernel of one logical shard
-// is seen by whichever context synchronises next)
+// is seen by whichever context synchronises next.  Made once, by the first ghip_create.)
 int *ghip_errwords(void);
 static inline int *ghip_errword(ghip_ctx *, int which) { return ghip_errwords() + which; }
 int ghip_check_device_errors(ghip_ctx *ctx);
@@ -473,10 +540,8 @@ int ghip_join(ghip_ctx *ctx);        // wait for a pair in flight AND complete a
 // one CU at the same moment -- would starve behind them however high its stream's priority.
 static inline int ghip_wg(const ghip_ctx *ctx) { return ctx->grav_pending ? 64 : 256; }
 // pinned word the record unpack sets when a record of the gas block [0, ngas) is not Type 0
-static inline int *ghip_gas_mixed_word(ghip_ctx *ctx)
-{
-  return reinterpret_cast<int *>(reinterpret_cast<char *>(ctx->pinned) + 256);
-}
+static inline int *ghip_gas_mixed_word(ghip_ctx *ctx) { return &ctx->pinned->gas_mixed; }
+static inline DevWords *ghip_words(ghip_ctx *ctx) { return reinterpret_cast<DevWords *>(ctx->words.p); }
 static inline unsigned long long *ghip_cslot(ghip_ctx *ctx, int kind)
 {
   return reinterpret_cast<unsigned long long *>(ctx->cslots.p) + (size_t) kind * GHIP_CKIND_U64;

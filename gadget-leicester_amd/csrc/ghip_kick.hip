@@ -361,9 +361,7 @@ extern "C" int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long 
   if(n == 0)
     return GHIP_OK;
   hipStream_t st = ctx->stream;
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
-  // (its own 64 words behind the run's accumulated counters)
-  unsigned long long *dhist = P<unsigned long long>(ctx->run_acc) + 16;
+  unsigned long long *dhist = ghip_words(ctx)->timebin_hist;
   HIPCHK(hipMemsetAsync(dhist, 0, 64 * 8, st));
   k_timebin_histogram<<<cdiv(n, 256), 256, 0, st>>>(n, P<int>(ctx->f[GHIP_F_TYPE]),
                                                     P<int>(ctx->f[GHIP_F_TIMEBIN]), dhist);
@@ -556,8 +554,7 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
   k.tab.timebase = p->Timebase_interval;
   k.tab.logTimeBegin = p->logTimeBegin;
   k.tab.logTimeMax = p->logTimeMax;
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
-  int *derr = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 40);
+  int *derr = &ghip_words(ctx)->step_err;
   HIPCHK(hipMemsetAsync(derr, 0, 4, st));
   GCHK(ghip_ensure(ctx, ctx->stage, (2 * DRIFT_TABLE_LENGTH + 64) * 8));
   double *d = P<double>(ctx->stage);
@@ -574,12 +571,12 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
   HIPCHK(hipEventRecord(ctx->evp[12], st));
   // with a kept tree the kicks are recorded and handed to the nodes (force_kick_node inside
   // do_the_kick, force_finish_kick_nodes at the end of advance_and_find_timesteps, timestep.c:256-263)
-  const bool record = ctx->dyn_on && ctx->dyn_valid && ctx->dyn.n == n;
+  const bool record = ctx->dyn_on && ctx->dyn_valid && ctx->dyn.tree.n == n;
   if(record)
     {
-      GCHK(ghip_ensure(ctx, ctx->kick_dv, 4 * (size_t) n * 8));
-      GCHK(ghip_ensure(ctx, ctx->kick_flag, (size_t) n * 4));
-      HIPCHK(hipMemsetAsync(ctx->kick_flag.p, 0, (size_t) n * 4, st));
+      GCHK(ghip_ensure(ctx, ctx->dyn.kick_dv, 4 * (size_t) n * 8));
+      GCHK(ghip_ensure(ctx, ctx->dyn.kick_flag, (size_t) n * 4));
+      HIPCHK(hipMemsetAsync(ctx->dyn.kick_flag.p, 0, (size_t) n * 4, st));
     }
   KickB x;
   GCHK(kick_bundle_args(ctx, &x, "ghip_advance_timesteps"));
@@ -593,7 +590,7 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
       P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]),
       P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr,
       ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr,
-      record ? P<double>(ctx->kick_dv) : nullptr, record ? P<int>(ctx->kick_flag) : nullptr, x);
+      record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr, x);
   else if(nact > 0)
     k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(
       nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
@@ -604,7 +601,7 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
       P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]),
       P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr,
       ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr,
-      record ? P<double>(ctx->kick_dv) : nullptr, record ? P<int>(ctx->kick_flag) : nullptr);
+      record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr);
   if(record && nact > 0)
     GCHK(ghip_dyn_kick_recorded(ctx));
   HIPCHK(hipEventRecord(ctx->evp[13], st));

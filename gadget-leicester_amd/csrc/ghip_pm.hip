@@ -183,26 +183,22 @@ static int pm_prepare(ghip_ctx *ctx, int N)
 {
   hipStream_t st = ctx->stream;
   const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
-  if(ctx->pm_n != N)
+  if(ctx->pm.n != N)
     {
-      if(ctx->pm_n)
-        {
-          (void) hipfftDestroy((hipfftHandle) ctx->pm_fwd);
-          (void) hipfftDestroy((hipfftHandle) ctx->pm_inv);
-          ctx->pm_n = 0;
-        }
+      // (the mesh owns each plan from the moment it exists: a failure below leaves nothing behind)
+      ghip_renew(ctx->pm);
       hipfftHandle f, b;
       FFTCHK(hipfftPlan3d(&f, N, N, N, HIPFFT_D2Z));
+      ctx->pm.fwd = (void *) f;
       FFTCHK(hipfftPlan3d(&b, N, N, N, HIPFFT_Z2D));
+      ctx->pm.inv = (void *) b;
       FFTCHK(hipfftSetStream(f, st));
       FFTCHK(hipfftSetStream(b, st));
-      ctx->pm_fwd = (void *) f;
-      ctx->pm_inv = (void *) b;
-      ctx->pm_n = N;
+      ctx->pm.n = N;
     }
-  GCHK(ghip_ensure(ctx, ctx->pm_rho, n3 * sizeof(double)));
-  GCHK(ghip_ensure(ctx, ctx->pm_k, nk * sizeof(double2)));
-  GCHK(ghip_ensure(ctx, ctx->pm_force, 3 * n3 * sizeof(double)));
+  GCHK(ghip_ensure(ctx, ctx->pm.rho, n3 * sizeof(double)));
+  GCHK(ghip_ensure(ctx, ctx->pm.k, nk * sizeof(double2)));
+  GCHK(ghip_ensure(ctx, ctx->pm.force, 3 * n3 * sizeof(double)));
   return GHIP_OK;
 }
 
@@ -213,7 +209,7 @@ static int pm_deposit(ghip_ctx *ctx, const ghip_pm_params *p)
   const int N = p->pmgrid, n = ctx->n;
   const size_t n3 = (size_t) N * N * N;
   const double to_slab_fac = N / p->BoxSize;                   // pm_periodic.c:102
-  double *rho = P<double>(ctx->pm_rho);
+  double *rho = P<double>(ctx->pm.rho);
   HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
   if(n > 0)
     {
@@ -231,17 +227,17 @@ static int pm_solve_and_interpolate(ghip_ctx *ctx, const ghip_pm_params *p)
   hipStream_t st = ctx->stream;
   const int N = p->pmgrid, n = ctx->n;
   const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
-  double *rho = P<double>(ctx->pm_rho), *force = P<double>(ctx->pm_force);
-  double2 *fk = P<double2>(ctx->pm_k);
+  double *rho = P<double>(ctx->pm.rho), *force = P<double>(ctx->pm.force);
+  double2 *fk = P<double2>(ctx->pm.k);
   const double to_slab_fac = N / p->BoxSize;
   double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;          // :221-222
   asmth2 *= asmth2;
   double fac = p->G / (M_PI * p->BoxSize);                     // :224-225
   fac *= 1 / (2 * p->BoxSize / N);
-  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm_fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
+  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
   k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
   HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm_inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
   k_pm_gradient<<<cdiv((long long) n3, 256), 256, 0, st>>>(N, fac, rho, force);
   if(n > 0)
     k_pm_interpolate<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
@@ -311,7 +307,7 @@ int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p)
   GCHK(pm_prepare(ctx, N));
   const size_t n3 = (size_t) N * N * N;
   const double to_slab_fac = N / p->BoxSize;
-  double *rho = P<double>(ctx->pm_rho);
+  double *rho = P<double>(ctx->pm.rho);
   HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
   if(n > 0)
     k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
@@ -328,8 +324,8 @@ int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, 
   hipStream_t st = ctx->stream;
   const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
   const double to_slab_fac = N / p->BoxSize;
-  double *rho = P<double>(ctx->pm_rho);
-  double2 *fk = P<double2>(ctx->pm_k);
+  double *rho = P<double>(ctx->pm.rho);
+  double2 *fk = P<double2>(ctx->pm.k);
   if(all)
     {
       k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, nranks, all, rho);
@@ -338,10 +334,10 @@ int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, 
   double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;   // :834-835
   asmth2 *= asmth2;
   const double fac = p->G / (M_PI * p->BoxSize);        // :837 (pm.G = All.G)
-  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm_fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
+  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
   k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
   HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm_inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
   if(n > 0)
     k_pm_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, fac, P<double>(ctx->f[GHIP_F_POS]),
                                                    rho, pot);
@@ -399,14 +395,14 @@ int ghip_dd_pm_step(ghip_ctx *ctx)
       GCHK(pm_prepare(ctx, p->pmgrid));
       HIPCHK(hipEventRecord(ctx->evp[14], st));
       GCHK(pm_deposit(ctx, p));
-      ghip_dd_set_allgather(D, ctx->pm_rho.p, n3 * sizeof(double), &D.pm_all);
+      ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
       D.phase = 1;
       return 1;
     }
   if(D.phase == 1)
     {
       k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, D.nranks, P<double>(D.pm_all),
-                                                                 P<double>(ctx->pm_rho));
+                                                                 P<double>(ctx->pm.rho));
       HIPCHK(hipGetLastError());
       GCHK(pm_solve_and_interpolate(ctx, p));
       HIPCHK(hipEventRecord(ctx->evp[15], st));
@@ -416,12 +412,16 @@ int ghip_dd_pm_step(ghip_ctx *ctx)
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the mesh force has no phase %d", D.phase);
 }
 
+PmMesh::~PmMesh()
+{
+  if(fwd)
+    (void) hipfftDestroy((hipfftHandle) fwd);
+  if(inv)
+    (void) hipfftDestroy((hipfftHandle) inv);
+}
+
 void ghip_pm_release(ghip_ctx *ctx)
 {
-  if(ctx && ctx->pm_n)
-    {
-      (void) hipfftDestroy((hipfftHandle) ctx->pm_fwd);
-      (void) hipfftDestroy((hipfftHandle) ctx->pm_inv);
-      ctx->pm_n = 0;
-    }
+  if(ctx)
+    ghip_renew(ctx->pm);
 }

@@ -398,7 +398,7 @@ static int pot_walk_and_finish(ghip_ctx *ctx, const ghip_pot_params *p, bool sha
   if(rel)
     GCHK(ghip_gather_f64_lim(ctx, ctx->gt.n, P<int>(ctx->gt.perm), P<double>(ctx->f[GHIP_F_OLDACC]), n,
                              P<double>(ctx->soldacc)));
-  const TreeDev &t = (ctx->dyn_use && !shard) ? ctx->dyn : ctx->gt;
+  const TreeDev &t = (ctx->dyn_use && !shard) ? ctx->dyn.tree : ctx->gt;
 #define POT_ARGS                                                                                   \
   P<TreeSizes>(t.dsz), nt, P<WalkHot>(t.mq), P<WalkCold>(t.mq2), P<double>(ctx->sx),               \
     P<double>(ctx->sy), P<double>(ctx->sz), P<double>(ctx->ssoft),                                  \
@@ -606,7 +606,7 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
         {
           GCHK(ghip_pm_potential_deposit(ctx, &p->pm));
           const size_t n3 = (size_t) p->pm.pmgrid * p->pm.pmgrid * p->pm.pmgrid;
-          ghip_dd_set_allgather(D, ctx->pm_rho.p, n3 * sizeof(double), &D.pm_all);
+          ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
           D.phase = 4;
           return 1;
         }

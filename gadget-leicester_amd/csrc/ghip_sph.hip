@@ -591,7 +591,6 @@ static int dens_alloc(ghip_ctx *ctx)
   GCHK(ghip_ensure(ctx, ctx->dflags, ng * 4));
   GCHK(ghip_ensure(ctx, ctx->dtgt_a, ng * 4 + 16));
   GCHK(ghip_ensure(ctx, ctx->dtgt_b, ng * 4 + 16));
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
   return GHIP_OK;
 }
 
@@ -691,7 +690,7 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
   double *hcur = P<double>(ctx->dhcur);
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_DENS);
   unsigned long long *racc = ghip_rslot(ctx, GHIP_CK_DENS);
-  int *dnum = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 32);
+  int *dnum = &ghip_words(ctx)->sel_left;
   HIPCHK(hipMemsetAsync(counter, 0, GHIP_CKIND_U64 * 8, st));
   HIPCHK(hipEventRecord(ctx->evp[6], st));
 
@@ -1233,7 +1232,6 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
   hipStream_t st = ctx->stream;
   TreeDev &t = ctx->st;
   GCHK(ghip_unmark_massless_for_hydro(ctx));   // (-DDUST without -DBLACK_HOLES)
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_HYDRO);
   HIPCHK(hipMemsetAsync(counter, 0, GHIP_CKIND_U64 * 8, st));
   BoxK b = make_box(p->BoxSize, p->periodic);

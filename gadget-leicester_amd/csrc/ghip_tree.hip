@@ -902,7 +902,7 @@ static int exclusive_sum(ghip_ctx *ctx, const int *in, int *out, int n, hipStrea
 
 static int *tree_dinfo(ghip_ctx *ctx, bool gas)
 {
-  return reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 48) + (gas ? 2 : 0);
+  return ghip_words(ctx)->tree_info[gas ? 1 : 0];
 }
 
 // Morton keys of the gravity tree's particles, sorted -> t.skey, t.perm
@@ -1300,7 +1300,6 @@ int ghip_tree_build_impl(ghip_ctx *ctx)
       HIPCHK(hipEventRecord(ctx->evp[1], st));
       return GHIP_OK;
     }
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
 
   // per-particle softening in host order (aux of the gravity tree's particle elements)
   GCHK(ghip_ensure(ctx, ctx->ssoft, (size_t) nsrc * 8));
@@ -1885,8 +1884,7 @@ static int make_list(ghip_ctx *ctx, TreeDev &t, int host_limit, DevBuf &list, in
   k_gather_i32<<<cdiv(n, 256), 256, 0, st>>>(n, P<int>(t.phorder), P<int>(ctx->dflags),
                                              P<int>(ctx->dtgt_a));
   HIPCHK(hipGetLastError());
-  GCHK(ghip_ensure(ctx, ctx->counters, 64 * 8));
-  int *dnum = reinterpret_cast<int *>(P<unsigned long long>(ctx->counters) + 32);
+  int *dnum = &ghip_words(ctx)->list_count;
   size_t tb = 0;
   HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, P<int>(t.phorder), P<int>(ctx->dtgt_a),
                                        P<int>(list), dnum, n, st));

@@ -243,6 +243,9 @@ int ghip_create(int device, ghip_ctx **out);
 void ghip_destroy(ghip_ctx *ctx);
 const char *ghip_last_error(const ghip_ctx *ctx);
 const char *ghip_version(void);
+/* bytes of device memory the library's contexts of this process hold at the moment (every device
+ * allocation of the library is counted): back at its earlier value once a context is destroyed */
+long long ghip_device_bytes_in_use(void);
 
 /* ---- particle data ---- */
 /* declare particle counts (gas = indices [0,ngas), allvars.h:1384); (re)allocates device arrays */
