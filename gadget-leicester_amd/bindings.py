@@ -144,6 +144,12 @@ class PotParams(C.Structure):
                 ("OmegaLambda", C.c_double), ("Hubble", C.c_double)]
 
 
+class DecompParams(C.Structure):
+    """ghip_dd_decomp_params (GHIP_DD_DECOMPOSE): level 0 = automatic, else 1..7; use_work: weigh by
+    domain_particle_costfactor; find_extent: domain_findExtent over all ranks first"""
+    _fields_ = [("level", C.c_int), ("use_work", C.c_int), ("find_extent", C.c_int), ("reserved", C.c_int)]
+
+
 class GlobalParams(C.Structure):
     """ghip_global_params (compute_global_quantities_of_system, global.c:18-238)"""
     _fields_ = [("Ti_Current", C.c_int), ("Timebase_interval", C.c_double),
@@ -261,7 +267,7 @@ EXPORTS = [
     "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh", "ghip_set_integration_flags",
     "ghip_kick_set_fields", "ghip_kick_get_drag_accel", "ghip_potential", "ghip_get_potential",
     "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
-    "ghip_dd_bytes_sent"]
+    "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain"]
 
 
 def lib():
@@ -374,6 +380,8 @@ def lib():
         L.ghip_potential_interactions.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         L.ghip_get_potential_interactions.argtypes = [vp, vp]
         L.ghip_dd_bytes_sent.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong)]
+        L.ghip_dd_get_splits.argtypes = [vp, vp]
+        L.ghip_dd_get_domain.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
         L.ghip_ewald_get_pot_table.argtypes = [vp, C.c_double, vp]
         L.ghip_global_quantities.argtypes = [vp, C.POINTER(GlobalParams), C.POINTER(GlobalSums)]
         _LIB = L
@@ -909,6 +917,18 @@ class ForcePath:
         sp = np.ascontiguousarray(splits, np.uint64)
         self._chk(self.L.ghip_dd_set_splits(self.h, _ptr(sp)))
 
+    def dd_get_splits(self):
+        """the key ranges in force (nranks + 1 uint64): what dd_set_splits or DD_DECOMPOSE stored last"""
+        out = np.zeros(self.dd_info()["nranks"] + 1, np.uint64)
+        self._chk(self.L.ghip_dd_get_splits(self.h, _ptr(out)))
+        return out
+
+    def dd_get_domain(self):
+        """(corner[3], center[3], len) of the domain cube in force"""
+        corner, center, ln = np.zeros(3), np.zeros(3), C.c_double(0)
+        self._chk(self.L.ghip_dd_get_domain(self.h, _ptr(corner), _ptr(center), C.byref(ln)))
+        return corner, center, ln.value
+
     def dd_keys(self):
         out = np.zeros(self.n, np.uint64)
         self._chk(self.L.ghip_dd_keys(self.h, _ptr(out)))
@@ -1019,6 +1039,7 @@ DD_MIGRATE, DD_GRAVITY, DD_DENSITY, DD_HYDRO = 1, 2, 3, 4
 DD_SINK_DENSITY, DD_BH_EVALUATE, DD_BH_SWALLOW, DD_PM = 5, 6, 7, 8
 DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
+DD_DECOMPOSE = 13
 
 
 class DdSinkArgs(C.Structure):

@@ -158,6 +158,7 @@ extern "C" int ghip_dd_set_splits(ghip_ctx *ctx, const unsigned long long *split
   std::vector<int> owner(D.nranks);
   for(int r = 0; r < D.nranks; r++)
     owner[r] = r;
+  D.seg_layout = false;
   return dd_store_segments(ctx, D.nranks, keys.data(), owner.data());
 }
 
@@ -175,7 +176,31 @@ extern "C" int ghip_dd_set_segments(ghip_ctx *ctx, int nseg, const unsigned long
     }
   if(keys[0] != 0 || keys[nseg] < (1ULL << 63))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_set_segments: the segments must cover [0, 2^63)");
-  return dd_store_segments(ctx, nseg, keys, owner);
+  GCHK(dd_store_segments(ctx, nseg, keys, owner));
+  D.seg_layout = true;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dd_get_splits(const ghip_ctx *ctx, unsigned long long *splits)
+{
+  if(!ctx || !splits || !ctx->dd.on || ctx->dd.seg_layout)   // (a ghip_dd_set_segments layout is not nranks+1 keys)
+    return GHIP_EINVAL;
+  for(int r = 0; r <= ctx->dd.nranks; r++)
+    splits[r] = ctx->dd.splits[r];
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dd_get_domain(const ghip_ctx *ctx, double corner[3], double center[3], double *len)
+{
+  if(!ctx || !corner || !center || !len)
+    return GHIP_EINVAL;
+  for(int j = 0; j < 3; j++)
+    {
+      corner[j] = ctx->corner[j];
+      center[j] = ctx->center[j];
+    }
+  *len = ctx->dlen;
+  return GHIP_OK;
 }
 
 extern "C" int ghip_dd_set_ghost_margin(ghip_ctx *ctx, double margin)
@@ -1822,6 +1847,11 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
       D.gq = *reinterpret_cast<const ghip_dd_global_args *>(params);
       GCHK(ghip_dd_gq_begin(ctx));
     }
+  else if(op == GHIP_DD_DECOMPOSE)
+    {
+      D.dcp = *reinterpret_cast<const ghip_dd_decomp_params *>(params);
+      GCHK(ghip_dd_decomp_begin(ctx));
+    }
   else if(op == DD_OP_MIGRATE)
     {
       static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
@@ -1864,6 +1894,8 @@ extern "C" int ghip_dd_step(ghip_ctx *ctx)
     return ghip_dd_pot_step(ctx);
   if(D.op == GHIP_DD_GLOBAL_QUANTITIES)
     return ghip_dd_gq_step(ctx);
+  if(D.op == GHIP_DD_DECOMPOSE)
+    return ghip_dd_decomp_step(ctx);
   if(D.op == DD_OP_MIGRATE)
     return migrate_step(ctx);
   if(D.op == DD_OP_GRAVITY)

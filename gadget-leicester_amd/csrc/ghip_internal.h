@@ -184,6 +184,7 @@ struct DDState
   // owner merged; ownlo/ownhi = this rank's own pieces.  Device copies for the three kernels that ask
   // "whose is this key" (range check, shared-cell test of the LET selection, migration).
   int nseg = 0, nown = 0;
+  bool seg_layout = false;        // the layout in force came from ghip_dd_set_segments (splits[] does not describe it)
   DevBuf segkey, segowner, ownlo, ownhi;
   void *nccl = nullptr;                           // ncclComm_t (ghip_comm.hip)
   // state machine
@@ -263,6 +264,14 @@ struct DDState
   ghip_dd_global_args gq;         // GHIP_DD_GLOBAL_QUANTITIES: arguments, a copy of *gq.p
   ghip_global_params gq_p;
   DevBuf gq_send, gq_all;         // ghip_global_sums of this shard / of all shards (rank order)
+  // GHIP_DD_DECOMPOSE (ghip_decomp.hip)
+  ghip_dd_decomp_params dcp;      // arguments of the operation in progress
+  DevBuf dc_own, dc_all;          // u64[DC_WORDS]: extent images, count, time bins, error word / of all shards
+  DevBuf dc_hist, dc_hist_all;    // u64[8^level]: this shard's histogram, later the sum / of all shards
+  int dc_level = 0, dc_bmax = 0, dc_shift = 0;
+  int dc_rc = 0;                  // what this shard's own first pass met (travels in the block: all stop together)
+  std::string dc_msg;
+  double dc_corner[3] = {0, 0, 0}, dc_center[3] = {0, 0, 0}, dc_len = 0;   // the cube the keys are formed in
 };
 
 // the pending exchange of a state-machine step (ghip_dd.hip, ghip_sink.hip)
@@ -659,6 +668,8 @@ int ghip_dd_pot_begin(ghip_ctx *ctx);   // potential.hip
 int ghip_dd_pot_step(ghip_ctx *ctx);
 int ghip_dd_gq_begin(ghip_ctx *ctx);
 int ghip_dd_gq_step(ghip_ctx *ctx);
+int ghip_dd_decomp_begin(ghip_ctx *ctx);   // decomp.hip
+int ghip_dd_decomp_step(ghip_ctx *ctx);
 
 // ---------------------------------------------------------------------------------------------
 // walk segments: the element list of a tree is cut into `ns` contiguous segments and `nsub`

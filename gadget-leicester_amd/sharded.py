@@ -195,6 +195,16 @@ class DomainShards:
     def migrate(self):
         self.run(self.B.DD_MIGRATE, None)
 
+    def decompose(self, params=None):
+        """GHIP_DD_DECOMPOSE(DecompParams; None = automatic level, unit weights, the cube kept): new key
+        ranges (and on request a new cube) from the resident particles of all shards.  Moves nothing."""
+        self.run(self.B.DD_DECOMPOSE, params if params is not None else self.B.DecompParams())
+
+    def redistribute(self, params=None):
+        """decompose, then migrate: afterwards every particle sits on the shard its key names"""
+        self.decompose(params)
+        self.migrate()
+
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams): afterwards every path's get_potential() / get_potential_interactions()
         give its own particles"""
@@ -273,6 +283,17 @@ class DomainRank:
 
     def migrate(self):
         self._run(self.B.DD_MIGRATE, None)
+
+    def decompose(self, params=None):
+        """GHIP_DD_DECOMPOSE(DecompParams; None = automatic level, unit weights, the cube kept), a collective:
+        new key ranges (and on request a new cube) from the resident particles of all ranks -- this rank
+        contributes one 128-byte block and one histogram, never its keys.  Moves nothing."""
+        self._run(self.B.DD_DECOMPOSE, params if params is not None else self.B.DecompParams())
+
+    def redistribute(self, params=None):
+        """decompose, then migrate: afterwards every particle sits on the rank its key names"""
+        self.decompose(params)
+        self.migrate()
 
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams), a collective: afterwards the path's get_potential() gives its own

@@ -308,7 +308,9 @@ int ghip_shard_unpack(ghip_ctx *ctx, int group, const void *dev_buf_all, int nra
 /* ---- multi-GPU: Peano-Hilbert domain decomposition with tree-node / ghost exchange ----
  * One process (or, for tests, one context) per GPU; each holds the particles of ONE contiguous
  * Peano-Hilbert key range (domain.c:100 domain_Decomposition; ranges cut by cumulative work,
- * domain.c:378-384, 1075-1113).  Replaces the top-tree pseudo-particles of force_treebuild
+ * domain.c:378-384, 1075-1113 -- by the library itself from the resident particles of all ranks:
+ * GHIP_DD_DECOMPOSE below, then GHIP_DD_MIGRATE; a host that has all keys in one place may still
+ * cut them itself and call ghip_dd_set_splits).  Replaces the top-tree pseudo-particles of force_treebuild
  * (forcetree.c:384-450, 879-1075) and the export rounds of gravity_tree / density / hydro_force
  * (gravtree.c:175-339, density.c:193-389, hydra.c:274-526):
  *   gravity  every shard receives, once per call, the part of every other shard's tree that its
@@ -763,6 +765,48 @@ typedef struct
   const ghip_global_params *p;
   ghip_global_sums *out;
 } ghip_dd_global_args;
+/* domain_Decomposition on shards (params: ghip_dd_decomp_params): the ranges of ghip_dd_set_splits, and on
+ * request the cube of ghip_dd_set_domain, are computed from the RESIDENT particles of all shards; no rank
+ * ever holds another rank's keys.  Three steps, two all-gathers:
+ *   1. every shard reduces its positions to xmin[3] / xmax[3] (integer atomic min / max on the
+ *      order-preserving u64 image of a double), its count and its smallest / largest time bin; one 128-byte
+ *      block per rank is all-gathered.  find_extent: DomainLen = 1.001 max_j(xmax_j - xmin_j), DomainCenter_j =
+ *      0.5 (xmin_j + xmax_j), DomainCorner_j = DomainCenter_j - 0.5 DomainLen (domain.c:1972-2014);
+ *   2. every shard adds the INTEGER weight of each of its particles into a u64 histogram over the 8^level
+ *      cells of the Peano-Hilbert curve in that cube; the histograms are all-gathered (8^level x 8 bytes per
+ *      rank).  use_work = 0: w = 1.  use_work = 1: domain_particle_costfactor (domain.c:378-384) times
+ *      2^bmax, w = ((1 + GravCost) << (bmax - b)) >> s, at least 1, with b = TimeBin ? TimeBin : 29, bmin /
+ *      bmax the smallest / largest b of the run and s = max(0, (bmax - bmin) + 32 + ceil(log2 N) - 63) so that
+ *      no sum leaves 64 bits.  A common power of two does not move a cut, and integer sums do not depend on
+ *      the order in which they are formed;
+ *   3. the histograms are added, converted to double and cut by ghip_dd_find_split; splits[r] = first cell of
+ *      rank r << (63 - 3 level).
+ * Afterwards every rank holds the same splits (one range per rank: a ghip_dd_set_segments layout is replaced)
+ * and the same cube (ForceSoftening is kept); the trees, a kept geometry and the result of GHIP_DD_POTENTIAL
+ * are discarded as ghip_dd_set_splits / ghip_dd_set_domain / GHIP_DD_MIGRATE discard them.  No particle
+ * moves: run GHIP_DD_MIGRATE next, as after a drift.  A position that is not finite, a TimeBin outside
+ * [0, 29] or a negative GravCost under use_work, no particle at all, an extent of length 0, or (find_extent =
+ * 0) a particle outside the kept cube make ALL ranks return GHIP_EINVAL with the same message after the first
+ * all-gather; nothing is changed then.  So does a failure of one rank's own first pass (that rank returns its
+ * own code and message, the others GHIP_EDEVICE naming it).
+ * Precondition, as for every ghip_dd_begin: ghip_dd_set_domain has been called once, also when find_extent = 1
+ * -- ForceSoftening reaches the context only there; the cube given may be any (it is replaced). */
+#define GHIP_DD_DECOMPOSE 13
+typedef struct
+{
+  int level;        /* histogram level L: the curve is cut on 8^L cells.  0: about 32 particles of the whole
+                     * run per cell (L = 1..7), raised until 8^L >= nranks.  Otherwise 1..7; GHIP_EINVAL if
+                     * 8^L < nranks */
+  int use_work;     /* 0: every particle weighs 1.  1: domain_particle_costfactor */
+  int find_extent;  /* 0: keep the cube of ghip_dd_set_domain (periodic runs).  1: domain_findExtent over all
+                     * ranks first */
+  int reserved;
+} ghip_dd_decomp_params;
+/* the ranges (nranks+1 keys) and the cube in force: what ghip_dd_set_splits / ghip_dd_set_domain /
+ * GHIP_DD_DECOMPOSE stored last.  ghip_dd_get_splits returns GHIP_EINVAL while a ghip_dd_set_segments layout is
+ * in force (several pieces per rank are not nranks+1 keys). */
+int ghip_dd_get_splits(const ghip_ctx *ctx, unsigned long long *splits);
+int ghip_dd_get_domain(const ghip_ctx *ctx, double corner[3], double center[3], double *len);
 /* bytes this shard sent over links in its last operation `op` (GHIP_DD_*), its own block excluded */
 int ghip_dd_bytes_sent(const ghip_ctx *ctx, int op, long long *bytes);
 
