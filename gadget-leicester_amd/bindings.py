@@ -28,7 +28,7 @@ EN = 64
 
 GHIP_ERRORS = {-90001: "GHIP_EHIP", -90002: "GHIP_EINVAL", -90003: "GHIP_ENOMEM",
                -90004: "GHIP_ENOCONV", -90005: "GHIP_ENODEVICE", -90006: "GHIP_ETIMESTEP",
-               -90008: "GHIP_EDEVICE", -90009: "GHIP_ECOMM"}
+               -90008: "GHIP_EDEVICE", -90009: "GHIP_ECOMM", -90010: "GHIP_EREGION"}
 
 
 class Layout(C.Structure):
@@ -135,6 +135,23 @@ class SfrParams(C.Structure):
 class PmParams(C.Structure):
     _fields_ = [("pmgrid", C.c_int), ("BoxSize", C.c_double), ("G", C.c_double),
                 ("Asmth", C.c_double)]
+
+
+class PmRegion(C.Structure):
+    """ghip_pm_region: the allowed region of the non-periodic mesh (pm_init_regionsize, pm_nonperiodic.c:91-212)"""
+    _fields_ = [("pmgrid", C.c_int), ("Xmintot", C.c_double * 3), ("Xmaxtot", C.c_double * 3),
+                ("TotalMeshSize", C.c_double), ("Corner", C.c_double * 3), ("UpperCorner", C.c_double * 3),
+                ("Asmth", C.c_double), ("Rcut", C.c_double)]
+
+    def asdict(self):
+        return {k: (np.array(getattr(self, k)) if k in ("Xmintot", "Xmaxtot", "Corner", "UpperCorner")
+                    else getattr(self, k)) for k, _ in self._fields_}
+
+
+class PmnpParams(C.Structure):
+    """ghip_pmnp_params (ghip_pm_nonperiodic / GHIP_DD_PM_NONPERIODIC)"""
+    _fields_ = [("pmgrid", C.c_int), ("G", C.c_double), ("comoving", C.c_int), ("Omega0", C.c_double),
+                ("OmegaLambda", C.c_double), ("Hubble", C.c_double)]
 
 
 class PotParams(C.Structure):
@@ -267,7 +284,8 @@ EXPORTS = [
     "ghip_dust_set_drag_heating", "ghip_sfr_cooling", "ghip_find_smbh", "ghip_set_integration_flags",
     "ghip_kick_set_fields", "ghip_kick_get_drag_accel", "ghip_potential", "ghip_get_potential",
     "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
-    "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain"]
+    "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain",
+    "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic"]
 
 
 def lib():
@@ -328,6 +346,10 @@ def lib():
         L.ghip_velocity_moments.argtypes = [vp, vp, vp, vp]
         L.ghip_download_aos_kick.argtypes = [vp, vp, vp, C.POINTER(Layout)]
         L.ghip_pm_periodic.argtypes = [vp, C.POINTER(PmParams)]
+        L.ghip_pm_find_region.argtypes = [vp, C.c_int, C.POINTER(PmRegion)]
+        L.ghip_pm_set_region.argtypes = [vp, C.POINTER(PmRegion)]
+        L.ghip_pm_get_region.argtypes = [vp, C.POINTER(PmRegion)]
+        L.ghip_pm_nonperiodic.argtypes = [vp, C.POINTER(PmnpParams)]
         L.ghip_tree_export.argtypes = [vp, C.POINTER(NodeLayout), C.c_int, C.c_int, C.c_int, vp, vp,
                                        vp, vp, C.c_int, C.POINTER(C.c_int)]
         L.ghip_shard_count.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -678,6 +700,32 @@ class ForcePath:
         p = PmParams(int(pmgrid), float(boxsize), float(G),
                      float(1.25 * boxsize / pmgrid if asmth is None else asmth))
         self._chk(self.L.ghip_pm_periodic(self.h, C.byref(p)))
+
+
+    def pm_find_region(self, pmgrid):
+        """ghip_pm_find_region: the region of the non-periodic mesh from the resident positions, stored in
+        the context; returns it (PmRegion)"""
+        r = PmRegion()
+        self._chk(self.L.ghip_pm_find_region(self.h, int(pmgrid), C.byref(r)))
+        return r
+
+    def pm_set_region(self, region):
+        """ghip_pm_set_region(PmRegion): a region the host kept (restart)"""
+        self._chk(self.L.ghip_pm_set_region(self.h, C.byref(region)))
+
+    def pm_get_region(self):
+        """ghip_pm_get_region: the region in force (GHIP_EINVAL: none)"""
+        r = PmRegion()
+        rc = self.L.ghip_pm_get_region(self.h, C.byref(r))
+        if rc != 0:
+            raise GhipError(rc, "ghip_pm_get_region: no region is set")
+        return r
+
+    def pm_nonperiodic(self, pmgrid, G, comoving=0, omega0=0.0, omega_lambda=0.0, hubble=0.0):
+        """ghip_pm_nonperiodic: fills F_GRAVPM (mesh force and the tail of long_range_force); GhipError with
+        GHIP_EREGION when a particle left the region: pm_find_region(), then call again"""
+        p = PmnpParams(int(pmgrid), float(G), int(comoving), float(omega0), float(omega_lambda), float(hubble))
+        self._chk(self.L.ghip_pm_nonperiodic(self.h, C.byref(p)))
 
     def velocity_moments(self):
         v2 = (C.c_double * 6)()
@@ -1040,6 +1088,7 @@ DD_SINK_DENSITY, DD_BH_EVALUATE, DD_BH_SWALLOW, DD_PM = 5, 6, 7, 8
 DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 DD_DECOMPOSE = 13
+DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
 
 
 class DdSinkArgs(C.Structure):

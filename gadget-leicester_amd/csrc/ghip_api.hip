@@ -168,7 +168,9 @@ int ghip_check_device_errors(ghip_ctx *ctx)
     "essential tree was incomplete",
     "tree emission outside the element list, a malformed imported element (3), a particle outside its "
     "shard's key range (5: migrate first) or outside the domain cube (6: ghip_dd_set_domain with a fresh extent)",
-    "", "drift", "timestep", "", ""};
+    "a particle that passed the range check of the non-periodic mesh fell outside its lower octant (nothing was "
+    "written for it): the region in force is inconsistent",
+    "drift", "timestep", "", ""};
   for(int w = 0; w < GHIP_ERRW_COUNT; w++)
     {
       volatile int *e = ghip_errword(ctx, w);

@@ -1852,6 +1852,16 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
       D.dcp = *reinterpret_cast<const ghip_dd_decomp_params *>(params);
       GCHK(ghip_dd_decomp_begin(ctx));
     }
+  else if(op == GHIP_DD_PM_REGION)
+    {
+      D.pmreg_grid = *reinterpret_cast<const int *>(params);
+      GCHK(ghip_dd_pmreg_begin(ctx));
+    }
+  else if(op == GHIP_DD_PM_NONPERIODIC)
+    {
+      D.pmnp = *reinterpret_cast<const ghip_pmnp_params *>(params);
+      GCHK(ghip_dd_pmnp_begin(ctx));
+    }
   else if(op == DD_OP_MIGRATE)
     {
       static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
@@ -1896,6 +1906,10 @@ extern "C" int ghip_dd_step(ghip_ctx *ctx)
     return ghip_dd_gq_step(ctx);
   if(D.op == GHIP_DD_DECOMPOSE)
     return ghip_dd_decomp_step(ctx);
+  if(D.op == GHIP_DD_PM_REGION)
+    return ghip_dd_pmreg_step(ctx);
+  if(D.op == GHIP_DD_PM_NONPERIODIC)
+    return ghip_dd_pmnp_step(ctx);
   if(D.op == DD_OP_MIGRATE)
     return migrate_step(ctx);
   if(D.op == DD_OP_GRAVITY)

@@ -185,6 +185,84 @@ __global__ void k_decomp_sum(int ncell, int nranks, const unsigned long long *__
   out[c] = s;
 }
 
+// One pass of k_decomp_extent over the resident positions of the context into `own` (shared with the region of
+// the non-periodic mesh, ghip_pm.hip).  The block is complete when this returns, also after a failure.
+int ghip_extent_pass(ghip_ctx *ctx, DevBuf &own, int use_work)
+{
+  static_assert(DC_WORDS == EXTENT_WORDS && DC_ERR_POS == EXTENT_ERR_POS && DC_ERR_WORK == EXTENT_ERR_WORK &&
+                  DC_ERR_LOCAL == EXTENT_ERR_LOCAL, "the extent block as ghip_internal.h describes it");
+  hipStream_t st = ctx->stream;
+  const int n = ctx->n;
+  const double *x = P<double>(ctx->f[GHIP_F_POS]);
+  const int *cost = P<int>(ctx->f[GHIP_F_GRAVCOST]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
+  unsigned long long blk[DC_WORDS];
+  for(int w = 0; w < DC_WORDS; w++)
+    blk[w] = 0;
+  for(int j = 0; j < 3; j++)   // (an empty shard contributes +MAX / -MAX)
+    {
+      blk[j] = dc_image(DBL_MAX);
+      blk[3 + j] = dc_image(-DBL_MAX);
+    }
+  blk[6] = (unsigned long long) n;
+  blk[7] = 0x7fffffffULL;
+  GCHK(ghip_ensure(ctx, own, sizeof(blk)));
+  auto pass = [&]() -> int {
+    GHIP_JOIN(ctx);
+    HIPCHK(hipMemcpyAsync(own.p, blk, sizeof(blk), hipMemcpyHostToDevice, st));
+    if(n > 0)
+      {
+        const int nb = cdiv(n, 256 * 8);
+        k_decomp_extent<<<nb < 2048 ? nb : 2048, 256, 0, st>>>(n, x, x + n, x + 2 * (size_t) n, use_work, cost,
+                                                                tbin, P<unsigned long long>(own));
+        HIPCHK(hipGetLastError());
+      }
+    HIPCHK(ghip_stream_sync(ctx, st));   // (`blk` lives on this frame)
+    return GHIP_OK;
+  };
+  const int rc = pass();
+  if(rc != GHIP_OK)
+    {
+      const std::string msg = ctx->err;
+      blk[9] = DC_ERR_LOCAL;
+      HIPCHK(hipMemcpy(own.p, blk, sizeof(blk), hipMemcpyHostToDevice));
+      ctx->err = msg;
+    }
+  return rc;
+}
+
+// the same bytes in the same order on every rank: every decision taken on the result is everybody's
+unsigned long long ghip_extent_reduce(const unsigned long long *all, int nranks, double xmin[3], double xmax[3],
+                                      unsigned long long *ntot, int *bmin, int *bmax, int *bad)
+{
+  unsigned long long err = 0;
+  for(int j = 0; j < 3; j++)
+    {
+      xmin[j] = DBL_MAX;
+      xmax[j] = -DBL_MAX;
+    }
+  *ntot = 0;
+  *bmin = 0x7fffffff;
+  *bmax = 0;
+  *bad = -1;
+  for(int r = 0; r < nranks; r++)
+    {
+      const unsigned long long *b = &all[(size_t) r * DC_WORDS];
+      for(int j = 0; j < 3; j++)
+        {
+          const double lo = dc_unimage(b[j]), hi = dc_unimage(b[3 + j]);
+          xmin[j] = lo < xmin[j] ? lo : xmin[j];
+          xmax[j] = hi > xmax[j] ? hi : xmax[j];
+        }
+      *ntot += b[6];
+      *bmin = (int) b[7] < *bmin ? (int) b[7] : *bmin;
+      *bmax = (int) b[8] > *bmax ? (int) b[8] : *bmax;
+      if(b[9] && *bad < 0)
+        *bad = r;
+      err |= b[9];
+    }
+  return err;
+}
+
 int ghip_dd_decomp_begin(ghip_ctx *ctx)
 {
   const DDState &D = ctx->dd;
@@ -216,40 +294,14 @@ int ghip_dd_decomp_step(ghip_ctx *ctx)
   const int *cost = P<int>(ctx->f[GHIP_F_GRAVCOST]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
   if(D.phase == 0)
     {
-      unsigned long long blk[DC_WORDS];
-      for(int w = 0; w < DC_WORDS; w++)
-        blk[w] = 0;
-      for(int j = 0; j < 3; j++)   // (an empty shard contributes +MAX / -MAX)
-        {
-          blk[j] = dc_image(DBL_MAX);
-          blk[3 + j] = dc_image(-DBL_MAX);
-        }
-      blk[6] = (unsigned long long) n;
-      blk[7] = 0x7fffffffULL;
-      GCHK(ghip_ensure(ctx, D.dc_own, sizeof(blk)));   // (without it there is nothing to send)
-      auto pass = [&]() -> int {
-        GHIP_JOIN(ctx);
-        HIPCHK(hipMemcpyAsync(D.dc_own.p, blk, sizeof(blk), hipMemcpyHostToDevice, st));
-        if(n > 0)
-          {
-            const int nb = cdiv(n, 256 * 8);
-            k_decomp_extent<<<nb < 2048 ? nb : 2048, 256, 0, st>>>(n, x, x + n, x + 2 * (size_t) n, p.use_work, cost,
-                                                                    tbin, P<unsigned long long>(D.dc_own));
-            HIPCHK(hipGetLastError());
-          }
-        HIPCHK(ghip_stream_sync(ctx, st));   // (`blk` lives on this frame)
-        return GHIP_OK;
-      };
       // what goes wrong on this shard alone travels in the block too: its peers are inside the same collective
       // and must not be left there (the status_own / status_all pattern of the density and the potential)
-      D.dc_rc = pass();
+      D.dc_rc = ghip_extent_pass(ctx, D.dc_own, p.use_work);
+      if(D.dc_rc != GHIP_OK && !D.dc_own.p)
+        return D.dc_rc;   // (without the block there is nothing to send)
       if(D.dc_rc != GHIP_OK)
-        {
-          D.dc_msg = ctx->err;
-          blk[9] = DC_ERR_LOCAL;
-          HIPCHK(hipMemcpy(D.dc_own.p, blk, sizeof(blk), hipMemcpyHostToDevice));
-        }
-      ghip_dd_set_allgather(D, D.dc_own.p, sizeof(blk), &D.dc_all);
+        D.dc_msg = ctx->err;
+      ghip_dd_set_allgather(D, D.dc_own.p, DC_WORDS * 8, &D.dc_all);
       D.phase = 1;
       return 1;
     }
@@ -259,25 +311,10 @@ int ghip_dd_decomp_step(ghip_ctx *ctx)
       HIPCHK(hipMemcpyAsync(all.data(), D.dc_all.p, all.size() * 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
       // the same bytes in the same order on every rank: every decision below is everybody's
-      double xmin[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, xmax[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-      unsigned long long ntot = 0, err = 0;
+      double xmin[3], xmax[3];
+      unsigned long long ntot = 0;
       int bmin = 0x7fffffff, bmax = 0, bad = -1;
-      for(int r = 0; r < P_; r++)
-        {
-          const unsigned long long *b = &all[(size_t) r * DC_WORDS];
-          for(int j = 0; j < 3; j++)
-            {
-              const double lo = dc_unimage(b[j]), hi = dc_unimage(b[3 + j]);
-              xmin[j] = lo < xmin[j] ? lo : xmin[j];
-              xmax[j] = hi > xmax[j] ? hi : xmax[j];
-            }
-          ntot += b[6];
-          bmin = (int) b[7] < bmin ? (int) b[7] : bmin;
-          bmax = (int) b[8] > bmax ? (int) b[8] : bmax;
-          if(b[9] && bad < 0)
-            bad = r;
-          err |= b[9];
-        }
+      const unsigned long long err = ghip_extent_reduce(all.data(), P_, xmin, xmax, &ntot, &bmin, &bmax, &bad);
       D.op = 0;   // (left as it is only when the histogram is posted)
       if(err & DC_ERR_LOCAL)
         {

@@ -254,6 +254,12 @@ struct DDState
   long long bytes_sent[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   ghip_pm_params pm;              // GHIP_DD_PM
   DevBuf pm_all;                  // the density meshes of all shards
+  // GHIP_DD_PM_REGION / GHIP_DD_PM_NONPERIODIC (ghip_pm.hip): the extent blocks travel in dc_own / dc_all, the
+  // compact octants with their status word in pm_all
+  int pmreg_grid = 0;             // PMGRID of the GHIP_DD_PM_REGION in progress
+  ghip_pmnp_params pmnp;          // arguments of the GHIP_DD_PM_NONPERIODIC in progress
+  int pmnp_rc = 0;                // what this shard's own deposit met (travels in the status word: all stop together)
+  std::string pmnp_msg;
   // GHIP_DD_POTENTIAL / GHIP_DD_GLOBAL_QUANTITIES (ghip_potential.hip)
   ghip_pot_params pot;            // arguments of the operation in progress
   DevBuf pot_tgt;                 // i32[n]: 0 .. n-1, the target list "all particles of the shard's own tree"
@@ -310,6 +316,7 @@ struct DevWords
   int dust_partners;   // ghip_dd_dust_groups: local Type 0 / Type 2 particles selected
   int gas_targets;     // density on shards: gas targets selected
   int step_err;        // ghip_drift / ghip_advance_timesteps: what the kernel met
+  int pm_err;          // non-periodic mesh (ghip_pm.hip): a particle outside the allowed region (the range check)
   int tree_info[2][2]; // count_nodes, per tree (gravity, gas): {deepest level, longest key run the
                        // 32-bit sort left unsorted}; k_tree_info reads them and leaves them zeroed
 };
@@ -337,6 +344,20 @@ struct PmMesh
   int n = 0;
   void *fwd = nullptr, *inv = nullptr;   // hipfftHandle, destroyed with the mesh
   DevBuf rho, k, force;
+  // The non-periodic mesh (ghip_pm.hip, "non-periodic mesh"): plans for GRID^3 = (2 n)^3, the padded mesh and
+  // its transform, the Green's function table, the force components and the density of the lower octant n^3
+  // (+ one status word).  Renewed as a whole, alone (ghip_renew(open)) or with the mesh that owns it.
+  struct Open
+  {
+    int n = 0;                             // PMGRID the plans and buffers are made for
+    int table_n = 0;                       // PMGRID `table` is filled for (0: not filled)
+    void *fwd = nullptr, *inv = nullptr;   // hipfftHandle
+    DevBuf rho, k, table, force, oct;
+    Open() = default;
+    Open(const Open &) = delete;
+    Open &operator=(const Open &) = delete;
+    ~Open();
+  } open;
   PmMesh() = default;
   PmMesh(const PmMesh &) = delete;
   PmMesh &operator=(const PmMesh &) = delete;
@@ -428,6 +449,8 @@ struct ghip_ctx
   // scan/sort temp
   DevBuf cubtmp;
   PmMesh pm;
+  ghip_pm_region pm_region = {};   // the allowed region of the non-periodic mesh (ghip_pm_find_region / _set_region)
+  bool pm_region_set = false;
   DevBuf words;   // DevWords
   // work counters of the walks and the SPH kernels, 64 slots per kind (ghip_count.h): of the current
   // calls (each call of a kind clears its own) and of the run (ghip_run_begin clears)
@@ -530,7 +553,7 @@ int ghip_fail(ghip_ctx *ctx, int code, const char *fmt, ...);
 #define GHIP_ERRW_PLAN 0     // wavefront plan of a gravity walk exceeded its grid (ghip_walk.h)
 #define GHIP_ERRW_LET 1      // a target wanted to open a pruned node of another shard's tree
 #define GHIP_ERRW_TREE 2     // tree emission wrote outside the element list / malformed import
-                             // (3: spare)
+#define GHIP_ERRW_PM 3       // non-periodic mesh: a mesh index outside the lower octant was refused (ghip_pm.hip)
 #define GHIP_ERRW_DRIFT 4    // a particle was ahead of the drift target (reference: endrun(12), predict.c:148)
 #define GHIP_ERRW_TIMESTEP 5 // the endrun code of a failed timestep criterion (888, 818, 112313)
 #define GHIP_ERRW_COUNT 8
@@ -587,6 +610,29 @@ int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot); 
 // pm_rho = the nranks meshes of `all` added in rank order, solve, pot[i] += the mesh potential at particle i
 int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p);
 int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot);
+// The non-periodic mesh potential (pmpotential_nonperiodic(0)), in the same two halves.  _check: the argument
+// rules of ghip_potential for grav.periodic == 0 && pm.pmgrid > 0.  _deposit: range check and deposit of this
+// context's particles into its octant block (ghip_pmnp_block_bytes: PMGRID^3 doubles and the status word, which
+// it sets); *outside = 1 when a particle lies outside the region (nothing deposited then).  _solve: all !=
+// nullptr: the octant is the sum of the nranks gathered blocks in rank order; GHIP_EREGION if a status word says
+// so, before anything is written; else pot[i] += the mesh potential at particle i.
+int ghip_pmnp_potential_check(ghip_ctx *ctx, const ghip_grav_params *g, const ghip_pm_params *pm, const char *who);
+int ghip_pmnp_potential_deposit(ghip_ctx *ctx, int pmgrid, int *outside);
+int ghip_pmnp_potential_solve(ghip_ctx *ctx, int pmgrid, double G, int nranks, const double *all, double *pot);
+size_t ghip_pmnp_block_bytes(int pmgrid);
+const void *ghip_pmnp_block(ghip_ctx *ctx);
+// ghip_decomp.hip: one pass of k_decomp_extent over the resident positions into the block `own` (EXTENT_WORDS
+// u64: images of xmin[3], xmax[3], the count, time bins, the error word; an empty context contributes +MAX / -MAX).
+// A failure of the pass itself is returned AND marked in the block, so that peers of a collective stop with it.
+#define EXTENT_WORDS 16
+int ghip_extent_pass(ghip_ctx *ctx, DevBuf &own, int use_work);
+// ... and the blocks of nranks contexts evaluated in rank order (host copies): 0, or the error bits met
+// (first on rank *bad)
+unsigned long long ghip_extent_reduce(const unsigned long long *all, int nranks, double xmin[3], double xmax[3],
+                                      unsigned long long *ntot, int *bmin, int *bmax, int *bad);
+#define EXTENT_ERR_POS 1ULL     // a position that is not finite
+#define EXTENT_ERR_WORK 2ULL    // a TimeBin outside [0, TIMEBINS] or a negative GravCost
+#define EXTENT_ERR_LOCAL 4ULL   // the pass itself failed on that rank
 
 #define HIPCHK(call)                                                                         \
   do                                                                                         \
@@ -670,6 +716,10 @@ int ghip_dd_gq_begin(ghip_ctx *ctx);
 int ghip_dd_gq_step(ghip_ctx *ctx);
 int ghip_dd_decomp_begin(ghip_ctx *ctx);   // decomp.hip
 int ghip_dd_decomp_step(ghip_ctx *ctx);
+int ghip_dd_pmreg_begin(ghip_ctx *ctx);    // pm.hip: GHIP_DD_PM_REGION
+int ghip_dd_pmreg_step(ghip_ctx *ctx);
+int ghip_dd_pmnp_begin(ghip_ctx *ctx);     // ... GHIP_DD_PM_NONPERIODIC
+int ghip_dd_pmnp_step(ghip_ctx *ctx);
 
 // ---------------------------------------------------------------------------------------------
 // walk segments: the element list of a tree is cut into `ns` contiguous segments and `nsub`

@@ -343,10 +343,13 @@ static int pot_check(ghip_ctx *ctx, const ghip_pot_params *p, const char *who)
   const ghip_grav_params &g = p->grav;
   const ghip_pm_params &pm = p->pm;
   const int pmgrid = pm.pmgrid;
-  if(pmgrid != 0)
+  if(pmgrid != 0 && !g.periodic)
     {
-      if(!g.periodic)
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: the non-periodic PM potential is not provided", who);
+      // pmpotential_nonperiodic: a region is set, of this PMGRID, and the walk is cut where the region says
+      GCHK(ghip_pmnp_potential_check(ctx, &g, &pm, who));
+    }
+  else if(pmgrid != 0)
+    {
       if(pmgrid < 4 || pmgrid > 2048 || (pmgrid & 1) || !(pm.BoxSize > 0) || !(pm.Asmth > 0))
         return ghip_fail(ctx, GHIP_EINVAL, "%s: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
                          "pm.Asmth > 0", who);
@@ -519,9 +522,21 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
       ctx->pot_n = 0;
       return GHIP_OK;
     }
+  // potential.c:262-270: pmpotential_periodic / pmpotential_nonperiodic(0).  The open mesh first checks that
+  // every particle lies inside its region: GHIP_EREGION before any potential is written
+  const bool open_mesh = p->pm.pmgrid > 0 && !p->grav.periodic;
+  if(open_mesh)
+    {
+      int outside = 0;
+      GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
+      if(outside)
+        return ghip_fail(ctx, GHIP_EREGION, "ghip_potential: a particle lies outside the allowed region of the mesh; "
+                         "no potential was written.  Find the region again (ghip_pm_find_region) and repeat the call");
+    }
   GCHK(pot_walk_and_finish(ctx, p, false));
-  // potential.c:262-265: pmpotential_periodic
-  if(p->pm.pmgrid > 0)
+  if(open_mesh)
+    GCHK(ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, 1, nullptr, P<double>(ctx->pot)));
+  else if(p->pm.pmgrid > 0)
     GCHK(ghip_pm_potential_add(ctx, &p->pm, P<double>(ctx->pot)));
   GCHK(pot_quadratic(ctx, p));
   ctx->pot_n = n;
@@ -602,6 +617,16 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
             return ghip_fail(ctx, GHIP_EDEVICE, "potential: the walk failed on shard %d (its own message says "
                              "why); every shard stops here", r);
           }
+      if(mesh && !p->grav.periodic)
+        {
+          // (the compact octant and its status word: a particle outside the region on any shard ends the
+          // call on all of them in phase 4)
+          int outside = 0;
+          GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
+          ghip_dd_set_allgather(D, ghip_pmnp_block(ctx), ghip_pmnp_block_bytes(p->pm.pmgrid), &D.pm_all);
+          D.phase = 4;
+          return 1;
+        }
       if(mesh)
         {
           GCHK(ghip_pm_potential_deposit(ctx, &p->pm));
@@ -617,7 +642,18 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
     }
   if(D.phase == 4)
     {
-      GCHK(ghip_pm_potential_solve(ctx, &p->pm, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
+      if(!p->grav.periodic)
+        {
+          const int rc = ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, D.nranks, P<double>(D.pm_all),
+                                                   P<double>(ctx->pot));
+          if(rc != GHIP_OK)
+            {
+              D.op = 0;
+              return rc;
+            }
+        }
+      else
+        GCHK(ghip_pm_potential_solve(ctx, &p->pm, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
       GCHK(pot_quadratic(ctx, p));
       ctx->pot_n = n;
       D.op = 0;

@@ -205,6 +205,18 @@ class DomainShards:
         self.decompose(params)
         self.migrate()
 
+    def pm_region(self, pmgrid):
+        """GHIP_DD_PM_REGION: the region of the non-periodic mesh from the resident particles of all shards,
+        stored on every shard (the same bytes); returns it (PmRegion)"""
+        import ctypes as C
+        self.run(self.B.DD_PM_REGION, C.c_int(int(pmgrid)))
+        return self.paths[0].pm_get_region()
+
+    def pm_nonperiodic(self, params):
+        """GHIP_DD_PM_NONPERIODIC(PmnpParams): every shard's F_GRAVPM; GhipError with GHIP_EREGION when a
+        particle of any shard left the region: pm_region(), then call again"""
+        self.run(self.B.DD_PM_NONPERIODIC, params)
+
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams): afterwards every path's get_potential() / get_potential_interactions()
         give its own particles"""
@@ -294,6 +306,18 @@ class DomainRank:
         """decompose, then migrate: afterwards every particle sits on the rank its key names"""
         self.decompose(params)
         self.migrate()
+
+    def pm_region(self, pmgrid):
+        """GHIP_DD_PM_REGION, a collective: the region of the non-periodic mesh from the resident particles of
+        all ranks (this rank contributes one 128-byte block), stored on every rank; returns it (PmRegion)"""
+        import ctypes as C
+        self._run(self.B.DD_PM_REGION, C.c_int(int(pmgrid)))
+        return self.p.pm_get_region()
+
+    def pm_nonperiodic(self, params):
+        """GHIP_DD_PM_NONPERIODIC(PmnpParams), a collective: this rank's F_GRAVPM; GhipError with GHIP_EREGION
+        on every rank when a particle of any rank left the region: pm_region(), then call again"""
+        self._run(self.B.DD_PM_NONPERIODIC, params)
 
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams), a collective: afterwards the path's get_potential() gives its own

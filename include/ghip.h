@@ -25,6 +25,7 @@
  *   ghip_tree_export                      Nodes[] / Extnodes[] / Nextnode[] / Father[] as
  *                                         force_treebuild leaves them  allvars.h:1847-1916
  *   ghip_pm_periodic                      pmforce_periodic()           pm_periodic.c:199-800
+ *   ghip_pm_nonperiodic                   pmforce_nonperiodic(0)       pm_nonperiodic.c:576-1175
  *   ghip_potential                        compute_potential()          potential.c:22-325
  *   ghip_global_quantities                compute_global_quantities_of_system()  global.c:18-238
  * The host-side mirror with the reference's own names (gravity_tree(), density(), hydro_force(),
@@ -52,6 +53,8 @@ typedef struct ghip_ctx ghip_ctx;
                                   * node of an imported tree that a target had to open, ...); results
                                   * of the step must not be used */
 #define GHIP_ECOMM (-90009)      /* an RCCL call of the multi-GPU exchange failed */
+#define GHIP_EREGION (-90010)    /* non-periodic mesh: a particle lies outside the allowed region; nothing was
+                                  * written.  Run ghip_pm_find_region (GHIP_DD_PM_REGION) and call again */
 #define GHIP_ETIMESTEP (-90006)  /* timestep criterion failed (reference: endrun(888|818|112313));
                                   * the code is returned by ghip_timestep_endrun_code */
 
@@ -235,7 +238,7 @@ typedef struct
   /* walk efficiency: elements visited summed over wavefronts (64 targets share each visit) */
   long long grav_wave_steps, ewald_wave_steps;
   float ms_kick;                 /* k_advance_timesteps of the last ghip_advance_timesteps */
-  float ms_pm;                   /* the last ghip_pm_periodic (deposit .. interpolation) */
+  float ms_pm;                   /* the last ghip_pm_periodic / ghip_pm_nonperiodic (deposit .. interpolation) */
 } ghip_stats;
 
 /* ---- lifetime ---- */
@@ -455,6 +458,52 @@ int ghip_tree_export(ghip_ctx *ctx, const ghip_node_layout *lay, int MaxPart, in
  * field is zeroed first as long_range_force does).  Pairs with GHIP_WALK_SHORTRANGE. ---- */
 int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p);
 
+/* ---- the non-periodic particle-mesh force of TreePM with open boundaries (PMGRID without PERIODIC:
+ * pm_nonperiodic.c, mesh 0; no PLACEHIGHRESREGION, SCALARFIELD, ENLARGEREGION; GRIDBOOST 2).  The FFT mesh
+ * is GRID^3 = (2 PMGRID)^3, zero padded; the particles occupy cells [2, GRID/2 - 2) of its lower octant.
+ *
+ * The region (pm_init_regionsize, :91-212): the extremes of the resident positions are reduced on the device,
+ * the arithmetic of :123-159 runs on the host in double, operation for operation, and the result is stored
+ * in the context.  ghip_pm_find_region returns GHIP_EINVAL, nothing stored, for: no particle, a position that
+ * is not finite, an extent of zero (one particle, or all coincident), an odd pmgrid or one outside [8, 512].
+ * Not on a multi-GPU shard (GHIP_EINVAL): there GHIP_DD_PM_REGION (below) gives every rank the same bytes.
+ * ghip_pm_set_region stores a region the host kept (All.Xmintot, All.Corner ... of a restart) after checking
+ * that it places [Xmintot, Xmaxtot] into cells [2, GRID/2 - 2); ghip_pm_get_region returns the region in
+ * force (GHIP_EINVAL: none).  The walk's Asmth / Rcut are the region's.  The Green's function table
+ * (pm_setup_nonperiodic_kernel, :371-558) is built on the device by the first call that needs it; it depends
+ * on PMGRID only, so a new region of the same pmgrid keeps it. ---- */
+typedef struct
+{
+  int pmgrid;                       /* PMGRID; the FFT mesh is (2 PMGRID)^3 */
+  double Xmintot[3], Xmaxtot[3];    /* allowed region, symmetrised (:130-135) */
+  double TotalMeshSize;             /* :144 */
+  double Corner[3], UpperCorner[3]; /* :152-153 */
+  double Asmth, Rcut;               /* ASMTH * TotalMeshSize / GRID, RCUT * Asmth (:158-159), ASMTH 1.25, RCUT 4.5 */
+} ghip_pm_region;
+int ghip_pm_find_region(ghip_ctx *ctx, int pmgrid, ghip_pm_region *out);   /* out may be NULL */
+int ghip_pm_set_region(ghip_ctx *ctx, const ghip_pm_region *r);
+int ghip_pm_get_region(const ghip_ctx *ctx, ghip_pm_region *out);
+/* P[].GravPM = pmforce_nonperiodic(0) (:576-1175) and the tail of long_range_force (longrange.c:117-138:
+ * comoving: += 0.5 Hubble^2 Omega0 Pos, else += OmegaLambda Hubble^2 Pos), the field zeroed first.  Needs a
+ * region of the same pmgrid (GHIP_EINVAL otherwise).  A particle outside [Xmintot, Xmaxtot] -- or with a
+ * coordinate that is not a number -- makes the call return GHIP_EREGION and write NOTHING, not even the zeros
+ * (the reference returns 1, :646): run ghip_pm_find_region and call again, as long_range_force does (:88-96),
+ * and build the tree again afterwards as the reference does (:1170).  The range check is one device pass into
+ * an error word; no position is read on the host.  It allows 4 DBL_EPSILON max(|Xmintot|, |Xmaxtot|) along each
+ * axis: the symmetrisation of :133-134 can round a bound one unit in the last place inside the particle that
+ * defines the extent, which the reference then refuses for good (endrun(68687)).  Cells of the force mesh that the reference leaves unwritten
+ * (outside [2, GRID/2 - 2)) are zero.  fp64 atomic adds in the mass assignment: reproducible to rounding, not
+ * bitwise.  ms_pm of ghip_get_stats reports the call.  Pairs with GHIP_WALK_SHORTRANGE at periodic = 0, Rcut
+ * and Asmth from the region.  Not on a multi-GPU shard: GHIP_DD_PM_NONPERIODIC.  n = 0: GHIP_OK. */
+typedef struct
+{
+  int pmgrid;
+  double G;          /* All.G */
+  int comoving;      /* All.ComovingIntegrationOn */
+  double Omega0, OmegaLambda, Hubble;
+} ghip_pmnp_params;
+int ghip_pm_nonperiodic(ghip_ctx *ctx, const ghip_pmnp_params *p);
+
 /* ---- compute_potential() (potential.c:22-325): the potential of EVERY particle of the context from a
  * walk of the tree the gravity walks would use now (the tree of the last ghip_tree_build, or the kept
  * tree after ghip_tree_substep when ghip_set_dynamic_tree is on; the caller drifts first), then the
@@ -467,7 +516,11 @@ int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p);
  * criterion) and, with adaptive softening, the HSML the tree was built with.  The result stays in a
  * per-context buffer (ghip_get_potential); no GHIP_F_* field changes.  Not on a multi-GPU shard
  * (GHIP_EINVAL): domain-decomposed shards run the collective GHIP_DD_POTENTIAL (below).  pm.G is the mesh part's G (All.G, as for ghip_pm_periodic); pm.BoxSize must equal
- * grav.BoxSize.  Every argument is checked before anything runs. ---- */
+ * grav.BoxSize.  grav.periodic == 0 with pm.pmgrid > 0: the short-range walk without nearest images plus the
+ * NON-PERIODIC mesh potential (pmpotential_nonperiodic(0), pm_nonperiodic.c:1354-1750, with the fac of :1378
+ * applied): a region must be set (ghip_pm_find_region), pm.pmgrid == region.pmgrid, grav.Asmth == pm.Asmth ==
+ * region.Asmth, grav.Rcut == region.Rcut; pm.BoxSize is not read.  A particle outside the region: GHIP_EREGION,
+ * no potential written.  Every argument is checked before anything runs. ---- */
 typedef struct
 {
   ghip_grav_params grav;     /* opening criterion, softenings, BoxSize, periodic, Rcut / Asmth */
@@ -802,6 +855,18 @@ typedef struct
                      * ranks first */
   int reserved;
 } ghip_dd_decomp_params;
+/* pm_init_regionsize on shards (params: const int *pmgrid): every shard reduces its own positions, one
+ * 128-byte block per rank (the six extremes, the count, the status) is all-gathered and every rank evaluates
+ * the same blocks in rank order -- the reference's MPI_Allreduce (:118-119) -- and stores the same region,
+ * bit for bit the one ghip_pm_find_region gives for all particles in one context.  An empty shard contributes
+ * +MAX / -MAX.  The refusals of ghip_pm_find_region are GHIP_EINVAL with the same message on every rank. */
+#define GHIP_DD_PM_REGION 14
+/* pmforce_nonperiodic on shards (params: ghip_pmnp_params): every shard checks its own particles against the
+ * region and deposits them into the COMPACT lower octant, PMGRID^3 doubles; the octants and one 8-byte status
+ * word each are all-gathered (8 PMGRID^3 + 8 bytes per shard, not the padded mesh), added in rank order,
+ * scattered into the zeroed padded mesh and solved on every shard, which reads out its own particles.  A
+ * particle outside the region on ANY shard makes EVERY shard return GHIP_EREGION, nothing written anywhere. */
+#define GHIP_DD_PM_NONPERIODIC 15
 /* the ranges (nranks+1 keys) and the cube in force: what ghip_dd_set_splits / ghip_dd_set_domain /
  * GHIP_DD_DECOMPOSE stored last.  ghip_dd_get_splits returns GHIP_EINVAL while a ghip_dd_set_segments layout is
  * in force (several pieces per rank are not nranks+1 keys). */
