@@ -118,6 +118,14 @@ class IntegrationFlags(C.Structure):
                                    "SinkBoundary", "FeedBackVelocity", "UnitVelocity_in_cm_per_s")]
 
 
+class ViscParams(C.Structure):
+    """ghip_visc_params: TIME_DEP_ART_VISC and the uniform switches of the SPH pair loop (include/ghip.h)"""
+    _fields_ = [(k, C.c_int) for k in ("time_dependent", "conventional", "no_limiter",
+                                        "no_shear_limiter")] + \
+        [(k, C.c_double) for k in ("ArtBulkViscConst", "AlphaMin", "ViscSource", "DecayTime",
+                                   "dtalpha_comoving_div")]
+
+
 # DoCooling variants of ghip_sfr_cooling (include/ghip.h)
 COOL_NONE, COOL_ISOTHERM, COOL_EVAPORATION, COOL_EVAPORATION_RADIAL, COOL_BETA = 0, 1, 2, 3, 4
 
@@ -285,7 +293,8 @@ EXPORTS = [
     "ghip_kick_set_fields", "ghip_kick_get_drag_accel", "ghip_potential", "ghip_get_potential",
     "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
     "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain",
-    "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic"]
+    "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic",
+    "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size"]
 
 
 def lib():
@@ -406,8 +415,22 @@ def lib():
         L.ghip_dd_get_domain.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
         L.ghip_ewald_get_pot_table.argtypes = [vp, C.c_double, vp]
         L.ghip_global_quantities.argtypes = [vp, C.POINTER(GlobalParams), C.POINTER(GlobalSums)]
+        L.ghip_set_viscosity.argtypes = [vp, C.POINTER(ViscParams)]
+        L.ghip_visc_set_alpha.argtypes = [vp, vp, vp]
+        L.ghip_visc_get.argtypes = [vp, vp, vp]
+        L.ghip_visc_derive.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.ghip_visc_derive.restype = None
+        L.ghip_visc_params_size.argtypes = []
+        L.ghip_visc_params_size.restype = C.c_size_t
         _LIB = L
     return _LIB
+
+
+def visc_derive(visc_source0, decay_length):
+    """(All.ViscSource, All.DecayTime) of begrun.c:132-133 from the parameter file's ViscSource0, DecayLength"""
+    a, b = C.c_double(), C.c_double()
+    lib().ghip_visc_derive(float(visc_source0), float(decay_length), C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def _ptr(a):
@@ -937,6 +960,27 @@ class ForcePath:
     def set_integration_flags(self, flags=None):
         """IntegrationFlags or None (the minimal flag set); governs advance_timesteps and drift"""
         self._chk(self.L.ghip_set_integration_flags(self.h, None if flags is None else C.byref(flags)))
+
+    # ---- the viscosity of the SPH pair loop (ghip_set_viscosity) ----
+    def set_viscosity(self, params=None):
+        """ViscParams or None (the constant viscosity of HydroParams); governs hydro, DD_HYDRO and
+        advance_timesteps"""
+        self._chk(self.L.ghip_set_viscosity(self.h, None if params is None else C.byref(params)))
+
+    def visc_set_alpha(self, alpha, dtalpha=None):
+        """SphP[].alpha and SphP[].Dtalpha (None: zeros) of the resident gas, [ngas]"""
+        a = np.ascontiguousarray(alpha, np.float64)
+        d = None if dtalpha is None else np.ascontiguousarray(dtalpha, np.float64)
+        assert a.shape == (self.ngas,) and (d is None or d.shape == (self.ngas,))
+        self._chk(self.L.ghip_visc_set_alpha(self.h, _ptr(a), _ptr(d)))
+
+    def visc_get(self):
+        """(alpha, Dtalpha) of the resident gas"""
+        a, d = np.zeros(self.ngas), np.zeros(self.ngas)
+        self._chk(self.L.ghip_visc_get(self.h, _ptr(a), _ptr(d)))
+        return a, d
+
+    visc_derive = staticmethod(visc_derive)
 
     def kick_set_fields(self, drag_accel=None, gas_dust_momentum=None, new_density=None):
         """gas DragAccel [ngas][3], gas DeltaDustMomentum [ngas][3], NewDensity [n]; None = zero"""

@@ -416,7 +416,10 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
   HIPCHK(hipSetDevice(ctx->device));
   bool changed = (numpart != ctx->n || ngas != ctx->ngas);
   if(changed)
-    ctx->pot_n = -1;   // (the potential of ghip_potential belongs to the particle set it was made for)
+    {
+      ctx->pot_n = -1;      // (the potential of ghip_potential belongs to the particle set it was made for)
+      ctx->visc_ngas = -1;  // (... and alpha / Dtalpha of ghip_visc_set_alpha too)
+    }
   ctx->n = numpart;
   ctx->ngas = ngas;
   for(int f = 0; f < GHIP_F_COUNT; f++)

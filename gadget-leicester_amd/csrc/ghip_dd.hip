@@ -1014,7 +1014,8 @@ __global__ void k_ghost_pack(int nrec, const int *__restrict__ list, int n, int 
                              const double *__restrict__ pres, const double *__restrict__ rho,
                              const double *__restrict__ dhf, const double *__restrict__ divv,
                              const double *__restrict__ curl, const int *__restrict__ timebin,
-                             const int *__restrict__ type, GhostRec *__restrict__ out)
+                             const int *__restrict__ type, const double *__restrict__ alpha,
+                             GhostRec *__restrict__ out)
 {
   int a = blockIdx.x * blockDim.x + threadIdx.x;
   if(a >= nrec)
@@ -1036,7 +1037,7 @@ __global__ void k_ghost_pack(int nrec, const int *__restrict__ list, int n, int 
   r.q[3] = divv[i];
   r.q[4] = curl[i];
   r.q[5] = (double) (tb ? (1 << tb) : 0);   // hydra.c:966
-  r.q[6] = 0;
+  r.q[6] = alpha ? alpha[i] : 0;   // (ghip_visc_set_alpha: the owner's alpha, in the slot that was spare)
   r.q[7] = 0;
   out[a] = r;
 }
@@ -1044,6 +1045,7 @@ __global__ void k_ghost_pack(int nrec, const int *__restrict__ list, int n, int 
 static int pack_ghosts(ghip_ctx *ctx, int total)
 {
   DDState &D = ctx->dd;
+  D.gh_alpha_epoch = ctx->visc_epoch;   // (the alpha these records carry: GHIP_DD_HYDRO asks for the same)
   const int n = ctx->n, ng = ctx->ngas;
   GCHK(ghip_ensure(ctx, D.gh_send, (size_t) (total > 0 ? total : 1) * sizeof(GhostRec)));
   if(total == 0)
@@ -1054,7 +1056,7 @@ static int pack_ghosts(ghip_ctx *ctx, int total)
     P<double>(ctx->f[GHIP_F_PRESSURE]), P<double>(ctx->f[GHIP_F_DENSITY]),
     P<double>(ctx->f[GHIP_F_DHSMLFAC]), P<double>(ctx->f[GHIP_F_DIVVEL]),
     P<double>(ctx->f[GHIP_F_CURLVEL]), P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TYPE]),
-    P<GhostRec>(D.gh_send));
+    (ctx->visc_alpha.p && ctx->visc_ngas == ng) ? P<double>(ctx->visc_alpha) : nullptr, P<GhostRec>(D.gh_send));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -1483,7 +1485,9 @@ static int density_step(ghip_ctx *ctx)
 // domain_exchange (domain.c:665-1060): after a drift some particles lie outside their shard's key
 // range; each moves to the shard that owns its key, with every resident field.  One record per
 // particle: 8-byte slots, the fields in enum order (ints widened), then the shard's DragHeating when it
-// holds one (ghip_dust.hip), slot MIG_SLOTS-1 = 1 for gas.
+// holds one (ghip_dust.hip), then alpha and Dtalpha when it holds them (ghip_visc_set_alpha), slot
+// MIG_SLOTS-1 = 1 for gas.  The three optional slots have fixed places and travel as zero from a shard
+// that does not hold the array.
 #define MIG_SLOTS 40
 struct MigRec
 {
@@ -1497,7 +1501,8 @@ struct MigField
 struct MigTable
 {
   int nf;
-  MigField f[GHIP_F_COUNT + 1];   // the fields, + DragHeating
+  MigField f[GHIP_F_COUNT + 3];   // the fields, + DragHeating, alpha, Dtalpha
+  int xslot;                      // first of the three optional slots
 };
 struct MigSplits
 {
@@ -1508,8 +1513,8 @@ struct MigSplits
 
 void ghip_field_info(int f, int *gas, int *ncomp, int *isint);   // api.hip
 
-// heat: the per-gas DragHeating, or nullptr when the shard holds none
-static MigTable mig_table(DevBuf *bufs, DevBuf *heat)
+// heat: the per-gas DragHeating, or nullptr when the shard holds none; visc: alpha and Dtalpha, or nullptr
+static MigTable mig_table(DevBuf *bufs, DevBuf *heat, DevBuf *const *visc)
 {
   MigTable T;
   T.nf = GHIP_F_COUNT;
@@ -1521,16 +1526,19 @@ static MigTable mig_table(DevBuf *bufs, DevBuf *heat)
       T.f[f].slot = slot;
       slot += T.f[f].ncomp;
     }
-  if(heat)
-    {
-      MigField &F = T.f[T.nf++];
-      F.p = heat->p;
-      F.ncomp = 1;
-      F.isint = 0;
-      F.gas = 1;
-      F.slot = slot;
-    }
-  return T;   // slot + 1 <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
+  T.xslot = slot;
+  DevBuf *const opt[3] = {heat, visc ? visc[0] : nullptr, visc ? visc[1] : nullptr};
+  for(int k = 0; k < 3; k++)
+    if(opt[k])
+      {
+        MigField &F = T.f[T.nf++];
+        F.p = opt[k]->p;
+        F.ncomp = 1;
+        F.isint = 0;
+        F.gas = 1;
+        F.slot = slot + k;
+      }
+  return T;   // slot + 3 <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
 }
 
 __global__ void k_mig_dest(int n, const double *__restrict__ x, const double *__restrict__ y,
@@ -1565,6 +1573,8 @@ __global__ void k_mig_pack(int nrec, const int *__restrict__ list, int n, int ng
   const int i = list[a];
   MigRec &r = out[a];
   const bool isgas = i < ngas;
+  for(int k = 0; k < 3; k++)   // an optional array this shard does not hold: its slot travels as zero
+    r.s[T.xslot + k] = 0;
   for(int f = 0; f < T.nf; f++)
     {
       const MigField F = T.f[f];
@@ -1582,8 +1592,6 @@ __global__ void k_mig_pack(int nrec, const int *__restrict__ list, int n, int ng
           r.s[F.slot + c] = v;
         }
     }
-  if(T.nf == GHIP_F_COUNT)   // no DragHeating here: its slot travels as zero
-    r.s[T.f[T.nf - 1].slot + T.f[T.nf - 1].ncomp] = 0;
   r.s[MIG_SLOTS - 1] = isgas ? 1ULL : 0ULL;
 }
 
@@ -1682,6 +1690,10 @@ static int migrate_step(ghip_ctx *ctx)
   // (a DragHeating that no longer matches the gas count -- ghip_set_counts since -- is not carried)
   DevBuf *heat = (ctx->dust_heat.p && ctx->dust_heat.cap >= (size_t) (ng > 0 ? ng : 1) * 8) ? &ctx->dust_heat
                                                                                            : nullptr;
+  // (the same for alpha / Dtalpha: carried when they were given for the gas this shard holds)
+  DevBuf *const visc_bufs[2] = {&ctx->visc_alpha, &ctx->visc_dtalpha};
+  DevBuf *const visc_shadow[2] = {&D.visc_shadow[0], &D.visc_shadow[1]};
+  DevBuf *const *visc = (ctx->visc_alpha.p && ctx->visc_dtalpha.p && ctx->visc_ngas == ng) ? visc_bufs : nullptr;
   if(D.phase == 0)
     {
       GHIP_JOIN(ctx);
@@ -1710,7 +1722,7 @@ static int migrate_step(ghip_ctx *ctx)
       if(total > 0)
         {
           k_mig_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.mig_list), n, ng,
-                                                      mig_table(ctx->f, heat), P<MigRec>(D.mig_send));
+                                                      mig_table(ctx->f, heat, visc), P<MigRec>(D.mig_send));
           HIPCHK(hipGetLastError());
         }
       D.mig_out = total;
@@ -1763,7 +1775,11 @@ static int migrate_step(ghip_ctx *ctx)
         }
       if(heat)
         GCHK(ghip_ensure(ctx, D.heat_shadow, (size_t) (ngn > 0 ? ngn : 1) * 8));
-      const MigTable A = mig_table(ctx->f, heat), Bn = mig_table(D.fshadow, heat ? &D.heat_shadow : nullptr);
+      if(visc)
+        for(int k = 0; k < 2; k++)
+          GCHK(ghip_ensure(ctx, D.visc_shadow[k], (size_t) (ngn > 0 ? ngn : 1) * 8));
+      const MigTable A = mig_table(ctx->f, heat, visc),
+                     Bn = mig_table(D.fshadow, heat ? &D.heat_shadow : nullptr, visc ? visc_shadow : nullptr);
       if(n > 0)
         k_mig_move_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), ro, C,
                                                      A, Bn);
@@ -1775,6 +1791,13 @@ static int migrate_step(ghip_ctx *ctx)
         ctx->f[f].swap(D.fshadow[f]);
       if(heat)
         ctx->dust_heat.swap(D.heat_shadow);
+      if(visc)
+        {
+          ctx->visc_alpha.swap(D.visc_shadow[0]);
+          ctx->visc_dtalpha.swap(D.visc_shadow[1]);
+        }
+      ctx->visc_ngas = visc ? ngn : -1;
+      ctx->visc_epoch++;
       ctx->n = nn;
       ctx->ngas = ngn;
       ctx->gt.built = false;
@@ -1821,7 +1844,15 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
       D.dens_rc = GHIP_OK;
     }
   else if(op == DD_OP_HYDRO)
-    D.hp = *reinterpret_cast<const ghip_hydro_params *>(params);
+    {
+      GCHK(ghip_visc_ready(ctx, "GHIP_DD_HYDRO"));
+      // the ghosts in place carry their owners' alpha as of the refresh that ended GHIP_DD_DENSITY; the local
+      // records take the alpha of this call (k_visc_refresh): a pair across shards must not mix the two
+      if(ctx->visc_on && ctx->visc.time_dependent && D.nranks > 1 && D.gh_alpha_epoch != ctx->visc_epoch)
+        return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_HYDRO: alpha changed (ghip_visc_set_alpha or a kick) since "
+                         "the GHIP_DD_DENSITY that packed the ghosts: run GHIP_DD_DENSITY again, on all ranks");
+      D.hp = *reinterpret_cast<const ghip_hydro_params *>(params);
+    }
   else if(op >= GHIP_DD_SINK_DENSITY && op <= GHIP_DD_BH_SWALLOW)
     {
       D.sink = *reinterpret_cast<const ghip_dd_sink_args *>(params);
@@ -1872,7 +1903,7 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
           ghip_field_info(f, &gas, &ncomp, &isint);
           slots += ncomp;
         }
-      slots += 1;   // DragHeating, when the shard holds one
+      slots += 3;   // DragHeating, alpha, Dtalpha, when the shard holds them
       if(slots > MIG_SLOTS - 1)
         return ghip_fail(ctx, GHIP_EINVAL, "migration record too small for %d field slots", slots);
     }

@@ -244,6 +244,8 @@ struct DDState
   DevBuf du_send, du_recv;        // grain records [DUST_REC doubles] out / in (source-rank major)
   DevBuf du_part, du_back;        // f64: partial d7 of the imported grains / of this shard's exported ones
   DevBuf heat_shadow;             // DragHeating of the migration's new layout
+  DevBuf visc_shadow[2];          // ... and alpha / Dtalpha (ghip_visc_set_alpha)
+  long long gh_alpha_epoch = -1;  // ctx->visc_epoch when the ghost records in place were packed
   int du_scount[GHIP_MAXRANKS], du_soff[GHIP_MAXRANKS];
   int du_sent = 0, du_recvd = 0;
   // The trees of this step after GHIP_DD_BH_SWALLOW: only masses changed (the victims' are 0), so their
@@ -470,6 +472,13 @@ struct ghip_ctx
   DevBuf kick_drag, kick_ddm, kick_newdens;   // f64[3][ngas], f64[3][ngas], f64[n]
   bool has_drag = false, has_ddm = false, has_newdens = false;
   int kick_fields_n = -1, kick_fields_ngas = -1;   // counts the fields were set for
+
+  // the viscosity of the pair loop (ghip_set_viscosity, ghip_sph.hip / ghip_kick.hip)
+  bool visc_on = false;                // any switch set: the k_hydro<TG, HydV> instantiations run
+  ghip_visc_params visc = {};
+  DevBuf visc_alpha, visc_dtalpha;     // f64[ngas] host order: SphP[].alpha, SphP[].Dtalpha (made on demand)
+  int visc_ngas = -1;                  // gas count alpha was given for (-1: none since the counts changed)
+  long long visc_epoch = 0;            // counts every change of alpha (ghip_visc_set_alpha, the kick)
 
   // ---- asynchronous tree build (ghip_tree.hip) ----
   // A build whose particle number equals the previous build's is enqueued without the host waiting
@@ -700,6 +709,8 @@ int ghip_build_segments(ghip_ctx *ctx, TreeDev &t, bool walk_records);
 int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p);
 int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p);
 int ghip_sph_fill_nodes(ghip_ctx *ctx, bool hmax_only);
+int ghip_visc_buffers(ghip_ctx *ctx);                   // alpha / Dtalpha for the current gas count
+int ghip_visc_ready(ghip_ctx *ctx, const char *who);   // the refusals of ghip_set_viscosity's mode
 // dd.hip
 void ghip_dd_release(ghip_ctx *ctx);
 // the pieces of the gravity operation that GHIP_DD_POTENTIAL shares (ghip_potential.hip):

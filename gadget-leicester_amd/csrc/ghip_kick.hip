@@ -23,6 +23,7 @@
 #pragma clang fp contract(off)
 
 #include "ghip_timefac.h"
+#include <type_traits>
 
 #define GHIP_TIMEBINS 29                   // allvars.h:39
 #define GHIP_TIMEBASE (1 << GHIP_TIMEBINS) // allvars.h:41
@@ -55,6 +56,22 @@ struct KickB
   double *drag;              // [3][ngas] or null (zero)
   const double *ddm;         // [3][ngas] or null (zero)
 };
+
+// ghip_set_viscosity with time_dependent: the alpha update of do_the_kick (timestep.c:529-534).  The pack
+// of k_advance_timesteps is then one KickV (minimal flag set) or one KickBV (the bundle's rules, which
+// still find their KickB in it).
+struct KickV
+{
+  double *alpha;           // [ngas]
+  const double *dtalpha;   // [ngas]
+  double alpha_max, alpha_min;   // All.ArtBulkViscConst, All.AlphaMin
+};
+struct KickBV : KickB
+{
+  KickV v;
+};
+__device__ __forceinline__ const KickV &d_kickv(const KickV &v) { return v; }
+__device__ __forceinline__ const KickV &d_kickv(const KickBV &x) { return x.v; }
 
 // X... is empty for the default kernel (the minimal flag set: same signature, same code as before the
 // bundle existed) and one KickB for the bundle's rules; every rule sits in an `if constexpr`
@@ -287,6 +304,16 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
                 x.drag[(size_t) j * ngas + i] = 0.;   // timestep.c:508
             }
         }
+      if constexpr((... || (std::is_same_v<X, KickV> || std::is_same_v<X, KickBV>)))   // timestep.c:530-533
+        {
+          const KickV &w = d_kickv(xs...);
+          double al = w.alpha[i];
+          al += w.dtalpha[i] * dt_entr;
+          al = al < w.alpha_max ? al : w.alpha_max;   // DMIN
+          if(al < w.alpha_min)
+            al = w.alpha_min;
+          w.alpha[i] = al;
+        }
       double A = entropy[i], dA = dtentropy[i];
       if(dA * dt_entr > -0.5 * A)   // timestep.c:553-557
         A += dA * dt_entr;
@@ -513,6 +540,7 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
                      "ghip_advance_timesteps: comoving kicks need the factor tables");
   if(!(p->Timebase_interval > 0))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_advance_timesteps: Timebase_interval must be > 0");
+  GCHK(ghip_visc_ready(ctx, "ghip_advance_timesteps"));
   int n = ctx->n, ng = ctx->ngas;
   if(TimeBinCount)
     memset(TimeBinCount, 0, 32 * sizeof(long long));
@@ -580,28 +608,36 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
     }
   KickB x;
   GCHK(kick_bundle_args(ctx, &x, "ghip_advance_timesteps"));
-  if(nact > 0 && ctx->iflags_on)
-    k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(
-      nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
-      P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),
-      P<double>(ctx->f[GHIP_F_HYDROACCEL]),
-      P<double>(ctx->f[GHIP_F_VELPRED]), P<double>(ctx->f[GHIP_F_ENTROPY]),
-      P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_DENSITY]),
-      P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]),
-      P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr,
-      ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr,
-      record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr, x);
+  // the arguments every instantiation takes, before its pack
+#define KICK_ARGS                                                                                          \
+  nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),                         \
+    P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),                                 \
+    P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_VELPRED]),                               \
+    P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),                                \
+    P<double>(ctx->f[GHIP_F_DENSITY]), P<double>(ctx->f[GHIP_F_HSML]),                                     \
+    P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]), P<int>(ctx->f[GHIP_F_TIMEBIN]),                                \
+    P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr, \
+    record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr
+  if(nact > 0 && ctx->visc_on && ctx->visc.time_dependent)
+    {
+      const KickV w = {P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha), ctx->visc.ArtBulkViscConst,
+                       ctx->visc.AlphaMin};
+      if(ctx->iflags_on)
+        {
+          KickBV xw;
+          static_cast<KickB &>(xw) = x;
+          xw.v = w;
+          k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, xw);
+        }
+      else
+        k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, w);
+      ctx->visc_epoch++;   // (alpha changed: ghosts packed before this carry the old one)
+    }
+  else if(nact > 0 && ctx->iflags_on)
+    k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, x);
   else if(nact > 0)
-    k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(
-      nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
-      P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),
-      P<double>(ctx->f[GHIP_F_HYDROACCEL]),
-      P<double>(ctx->f[GHIP_F_VELPRED]), P<double>(ctx->f[GHIP_F_ENTROPY]),
-      P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_DENSITY]),
-      P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]),
-      P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr,
-      ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr,
-      record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr);
+    k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS);
+#undef KICK_ARGS
   if(record && nact > 0)
     GCHK(ghip_dyn_kick_recorded(ctx));
   HIPCHK(hipEventRecord(ctx->evp[13], st));

@@ -18,6 +18,7 @@
 // summation order differs.
 
 #include "ghip_ngb.h"
+#include <cmath>
 
 // Bounds of a bucket's targets around the first target: half extents per axis (nearest-image
 // offsets) and the largest search radius.  A staged candidate can be a neighbour of SOME lane only
@@ -934,6 +935,13 @@ struct HydAcc
   int np;
 };
 
+// ghip_set_viscosity: the switches of the pair loop that the default kernel does not have.  A kernel
+// argument of the k_hydro<TG, HydV> instantiations only: wave-uniform, every test a scalar branch.
+struct HydV
+{
+  int time_dependent, conventional, no_limiter, no_shear_limiter;
+};
+
 struct HydTgt
 {
   double px, py, pz, vx, vy, vz, h_i, h_i2, mass, rho, f1, p_over_rho2_i, soundspeed_i, timestep;
@@ -962,11 +970,15 @@ __device__ __forceinline__ HydCand d_hydro_candidate(double pres_j, double rho_j
 
 
 // r8: (x,y,z,m,vx,vy,vz,h) of the candidate; q8: (p_over_rho2, rho, dhsml factor, f2, -, timestep,
-// soundspeed, 1/h) -- slots 0, 3, 6, 7 as d_hydro_candidate leaves them
+// soundspeed, 1/h) -- slots 0, 3, 6, 7 as d_hydro_candidate leaves them.  With a HydV (ghip_set_viscosity)
+// slot 4 holds the candidate's alpha and *alpha_i, in LDS, the target's: read where it is used, it costs no
+// register across the walk (the kernel sits at the 128 VGPRs of four wavefronts per SIMD).
+template <class... V>
 __device__ __forceinline__ void d_hydro_pair(const double *r8, const double *q8, bool valid,
                                              const HydTgt &T, const HydK &K, const BoxK b,
-                                             HydAcc &A)
+                                             HydAcc &A, const double *alpha_i, const double *alpha_j, const V &...vs)
 {
+  constexpr bool VISC = sizeof...(V) > 0;
   const double jx = r8[0], jy = r8[1], jz = r8[2], mass_j = r8[3];
   const double jvx = r8[4], jvy = r8[5], jvz = r8[6], h_j = r8[7];
   double dx = d_wrap(T.px - jx, b), dy = d_wrap(T.py - jy, b), dz = d_wrap(T.pz - jz, b);
@@ -1002,7 +1014,46 @@ __device__ __forceinline__ void d_hydro_pair(const double *r8, const double *q8,
       if(vsig > A.maxsig)
         A.maxsig = vsig;
       double visc = 0;
-      if(vdotr2 < 0)
+      if constexpr(VISC)
+        {
+          const HydV &X = (vs, ...);
+          if(vdotr2 < 0)
+            {
+              // hydra.c:1512-1594 with its switches
+              double mu_ij, c_ij = 0;
+              if(X.conventional)   // hydra.c:1516-1518
+                {
+                  c_ij = 0.5 * vsig;   // (vsig is still soundspeed_i + soundspeed_j here)
+                  const double h_ij = 0.5 * (T.h_i + *(const volatile double *) (r8 + 7));   // (h_j again: not kept in a register)
+                  mu_ij = K.fac_mu * h_ij * vdotr2 / (r2 + 0.0001 * h_ij * h_ij);
+                }
+              else
+                mu_ij = K.fac_mu * vdotr2 * rinv;
+              vsig -= 3 * mu_ij;   // hydra.c:1520: whichever mu_ij it is
+              if(vsig > A.maxsig)
+                A.maxsig = vsig;
+              double rho_ij = 0.5 * (T.rho + rho_j);
+              const double f12 = X.no_shear_limiter ? 2.0 : T.f1 + f2;                    // hydra.c:1538-1540
+              const double bulk = X.time_dependent ? 0.5 * (*alpha_i + *alpha_j) : K.visc_const;   // :1541-1545
+              if(X.conventional)   // hydra.c:1549-1551
+                visc = (-bulk * mu_ij * c_ij + 2 * bulk * mu_ij * mu_ij) / rho_ij * f12 * 0.5;
+              else
+                visc = 0.25 * bulk * vsig * (-mu_ij) / rho_ij * f12;
+              if(!X.no_limiter)   // hydra.c:1583-1595
+                {
+                  double tmax = (T.timestep > ts_j) ? T.timestep : ts_j;
+                  double dt = 2 * tmax * K.timebase;
+                  if(dt > 0 && (dwk_i + dwk_j) < 0)
+                    {
+                      double lim = 0.5 * K.fac_vsic_fix * vdotr2 /
+                                   (0.5 * (T.mass + mass_j) * (dwk_i + dwk_j) * r * dt);
+                      if(lim < visc)
+                        visc = lim;
+                    }
+                }
+            }
+        }
+      else if(vdotr2 < 0)
         {
           // hydra.c:1512-1594
           double mu_ij = K.fac_mu * vdotr2 * rinv;
@@ -1035,14 +1086,19 @@ __device__ __forceinline__ void d_hydro_pair(const double *r8, const double *q8,
 // candidate slots, same structure as k_density: scalar node records, candidate records (gp + gq,
 // 128 B) staged through LDS 64 at a time, exact per-lane acceptance r2 < h_i^2 || r2 < h_j^2.  Node
 // pruning uses max(hmax_node, h_i) like ngb_treefind_pairs (ngb.c:136).  Outputs: [5][nt] planes.
-template <int TG>
+// V... is empty for the default kernel (the constant viscosity: same signature, same code as before
+// ghip_set_viscosity existed) and one HydV for the instantiation with the switches; there slot 6 of a gq
+// record holds the particle's alpha (k_visc_refresh) and travels in slot 4 of the staged copy, where the
+// curl is dead once f2 is formed.
+template <int TG, class... V>
 __global__ void __launch_bounds__(64)
 k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, const double *__restrict__ gp,
         const double *__restrict__ gq, int nt, int nsub, const int *__restrict__ tgt, BoxK b, HydK K,
         double *__restrict__ part, unsigned long long *__restrict__ counter,
-        unsigned long long *__restrict__ racc, int xcd, int nblocks)
+        unsigned long long *__restrict__ racc, int xcd, int nblocks, V... vs)
 {
   constexpr int CS = 64 / TG;
+  constexpr bool VISC = sizeof...(V) > 0;
   __shared__ double4 sh[SPH_STAGE][4];
   const int lane = threadIdx.x;
   const int tl = lane & (TG - 1), cs = lane / TG;
@@ -1056,10 +1112,15 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
   const bool valid = ti < nt;
   const int s = valid ? tgt[ti] : 0;
   HydTgt T = {0, 0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 0, 0, 0, 1, 1};
+  __shared__ double sh_alpha[VISC ? TG : 1];
+  const double *alpha_i = sh_alpha + (VISC ? tl : 0);
   if(valid)
     {
       const double *r8 = gp + (size_t) 8 * s;
       const double *q8 = gq + (size_t) 8 * s;
+      if constexpr(VISC)
+        if(cs == 0)
+          sh_alpha[tl] = q8[6];
       T.px = r8[0];
       T.py = r8[1];
       T.pz = r8[2];
@@ -1081,6 +1142,8 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
       T.p_over_rho2_i = pres / (T.rho * T.rho);
       T.p_over_rho2_i *= dhf;
     }
+  if constexpr(VISC)
+    __syncthreads();   // (the CS lanes of a target read the alpha its first lane stored)
   HydAcc A = {0, 0, 0, 0, 0, 0};
   const BucketBox BB = d_bucket_box(valid, T.px, T.py, T.pz, T.h_i, b);
 
@@ -1100,7 +1163,7 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
               const HydCand C = d_hydro_candidate(qs[0], qs[1], gp[(size_t) 8 * pidx + 7], qs[3], qs[4],
                                                   K.fac_mu);
               const double q8[8] = {C.p_over_rho2, qs[1], qs[2], C.f2, 0.0, qs[5], C.soundspeed, C.hinv};
-              d_hydro_pair(gp + (size_t) 8 * pidx, q8, valid && cs == 0, T, K, b, A);
+              d_hydro_pair(gp + (size_t) 8 * pidx, q8, valid && cs == 0, T, K, b, A, alpha_i, qs + 6, vs...);
             }
           e = e + 1;
         }
@@ -1132,6 +1195,8 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
                             const HydCand C = d_hydro_candidate(q0.x, q0.y, c1.w, q0.w, q1.x, K.fac_mu);
                             q0.x = C.p_over_rho2;
                             q0.w = C.f2;
+                            if constexpr(VISC)
+                              q1.x = q1.z;   // alpha, before its slot is taken
                             q1.z = C.soundspeed;
                             q1.w = C.hinv;
                             sh[lane][0] = c0;
@@ -1148,7 +1213,7 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
                             const int jj = j < 0 ? 0 : j;
                             d_hydro_pair(reinterpret_cast<const double *>(&sh[jj][0]),
                                          reinterpret_cast<const double *>(&sh[jj][2]), valid && j >= 0, T,
-                                         K, b, A);
+                                         K, b, A, alpha_i, reinterpret_cast<const double *>(&sh[jj][3]), vs...);
                           }
                       }
                   e = skip;
@@ -1180,13 +1245,38 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
     }
 }
 
+// the post-pass of hydro_force under TIME_DEP_ART_VISC (hydra.c:735-744): what k_hydro_combine<HydD> needs
+struct HydD
+{
+  const double *gp;      // the targets' records: h
+  const double *alpha;   // [ngas], host order
+  double *dtalpha;       // [ngas], host order: written for the targets of the call only
+  double AlphaMin, ViscSource, DecayTime;
+  double comoving_div;   // hubble_a All.Time^2 (read when K.comoving)
+};
+
+// [ngas] host order -> slot 6 of the gq records of the LOCAL particles of the gas tree (a shard's ghosts
+// carry their owner's alpha since k_ghost_pack).  Run by every hydro call of the mode, so that the alpha of
+// the call is the one used, however old the tree is.
+__global__ void k_visc_refresh(int nsrc, int ngas, const int *__restrict__ perm, const double *__restrict__ alpha,
+                               double *__restrict__ gq)
+{
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= nsrc)
+    return;
+  const int i = perm[s];
+  if(i < ngas)
+    gq[(size_t) 8 * s + 6] = alpha[i];
+}
+
 // fixed-order sum of the partial results + the entropy-rate conversion of hydro_force
-// (hydra.c:583), scattered to host order
+// (hydra.c:583), scattered to host order.  With a HydD also Dtalpha of the targets (hydra.c:735-744).
+template <class... D>
 __global__ void k_hydro_combine(int nt, int nsub, const int *__restrict__ tgt,
                                 const int *__restrict__ perm, const double *__restrict__ gq,
                                 const double *__restrict__ part, HydK K, int ngas,
                                 double *__restrict__ o_acc, double *__restrict__ o_dtent,
-                                double *__restrict__ o_maxsig)
+                                double *__restrict__ o_maxsig, D... ds)
 {
   int ti = blockIdx.x * blockDim.x + threadIdx.x;
   if(ti >= nt)
@@ -1211,6 +1301,21 @@ __global__ void k_hydro_combine(int nt, int nsub, const int *__restrict__ tgt,
   o_acc[2 * (size_t) ngas + i] = az;
   o_dtent[i] = K.raw ? de : de * (GAMMA_MINUS1 / (K.hubble_a2 * pow(rho, GAMMA_MINUS1)));
   o_maxsig[i] = ms;
+  if constexpr(sizeof...(D) > 0)
+    {
+      // hydra.c:736-743 with v.DivVel / r.CurlVel (the reference's u.s.* members exist only under
+      // NAVIERSTOKES: DESIGN 4.4.1), ms = the maximum over all partial MaxSignalVel
+      const HydD &X = (ds, ...);
+      const double *q = gq + (size_t) 8 * s;
+      const double pres = q[0], divv = q[3], curl = q[4], h = X.gp[(size_t) 8 * s + 7];
+      const double cs_h = sqrt(GAMMA * pres / rho) / h;
+      const double f = fabs(divv) / (fabs(divv) + curl + 0.0001 * cs_h / K.fac_mu);
+      double da = -(X.alpha[i] - X.AlphaMin) * X.DecayTime * 0.5 * ms / (h * K.fac_mu) +
+                  f * X.ViscSource * (-divv > 0.0 ? -divv : 0.0);
+      if(K.comoving)
+        da /= X.comoving_div;
+      X.dtalpha[i] = da;
+    }
 }
 
 int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
@@ -1220,6 +1325,7 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
   GCHK(ghip_gas_verify(ctx));
   if(!ctx->st.built)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_hydro: call ghip_tree_build first");
+  GCHK(ghip_visc_ready(ctx, "ghip_hydro"));
   GCHK(ghip_build_target_lists(ctx));
   ghip_stats &S = ctx->stats;
   S.hydro_pairs = 0;
@@ -1234,6 +1340,7 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
   GCHK(ghip_unmark_massless_for_hydro(ctx));   // (-DDUST without -DBLACK_HOLES)
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_HYDRO);
   HIPCHK(hipMemsetAsync(counter, 0, GHIP_CKIND_U64 * 8, st));
+  const bool visc = ctx->visc_on;
   BoxK b = make_box(p->BoxSize, p->periodic);
   HydK K = {p->ArtBulkViscConst, p->hubble_a2, p->fac_mu, p->fac_vsic_fix, p->Timebase_interval,
             p->ComovingIntegrationOn, p->raw_dtentropy};
@@ -1259,23 +1366,169 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
         HIPCHK(hipStreamWaitValue32(st, ctx->pair_started, 1, hipStreamWaitValueGte, 0xffffffffu));
     }
   HIPCHK(hipEventRecord(ctx->evp[10], st));
+  if(visc && ctx->visc.time_dependent)   // (inside ms_hydro: the mode's cost)
+    {
+      k_visc_refresh<<<cdiv(t.n, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
+        t.n, ng, P<int>(t.perm), P<double>(ctx->visc_alpha), P<double>(ctx->gq));
+      HIPCHK(hipGetLastError());
+    }
   const int tgw = ghip_sph_tg();
   const int nbk = (nt + tgw - 1) / tgw;
   int nsub = (ghip_sph_target_waves() + nbk - 1) / nbk;
   nsub = nsub < 1 ? 1 : (nsub > GHIP_MAXSUB ? GHIP_MAXSUB : nsub);
   GCHK(ghip_ensure(ctx, ctx->hpart, (size_t) 5 * nsub * nt * 8));
-  SPH_LAUNCH(k_hydro, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp),
-             P<double>(ctx->gq), nt, nsub, P<int>(ctx->tg_gas) + lo, b, K, P<double>(ctx->hpart),
-             counter, ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), nbk * nsub);
+  if(visc)
+    {
+      const ghip_visc_params &v = ctx->visc;
+      const HydV X = {v.time_dependent, v.conventional, v.no_limiter, v.no_shear_limiter};
+      SPH_LAUNCH(k_hydro, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq),
+                 P<double>(ctx->gp), P<double>(ctx->gq), nt, nsub, P<int>(ctx->tg_gas) + lo, b, K,
+                 P<double>(ctx->hpart), counter, ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), nbk * nsub, X);
+    }
+  else
+    SPH_LAUNCH(k_hydro, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp),
+               P<double>(ctx->gq), nt, nsub, P<int>(ctx->tg_gas) + lo, b, K, P<double>(ctx->hpart),
+               counter, ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), nbk * nsub);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->evp[11], st));
-  k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
-    nt, nsub, P<int>(ctx->tg_gas) + lo, P<int>(t.perm), P<double>(ctx->gq),
-    P<double>(ctx->hpart), K, ng, P<double>(ctx->f[GHIP_F_HYDROACCEL]),
-    P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]));
+  if(visc && ctx->visc.time_dependent)
+    {
+      const ghip_visc_params &v = ctx->visc;
+      const HydD X = {P<double>(ctx->gp), P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha),
+                      v.AlphaMin,         v.ViscSource,               v.DecayTime,
+                      v.dtalpha_comoving_div};
+      k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
+        nt, nsub, P<int>(ctx->tg_gas) + lo, P<int>(t.perm), P<double>(ctx->gq), P<double>(ctx->hpart), K, ng,
+        P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
+        P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]), X);
+    }
+  else
+    k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
+      nt, nsub, P<int>(ctx->tg_gas) + lo, P<int>(t.perm), P<double>(ctx->gq),
+      P<double>(ctx->hpart), K, ng, P<double>(ctx->f[GHIP_F_HYDROACCEL]),
+      P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// the viscosity of the pair loop (ghip_set_viscosity): TIME_DEP_ART_VISC and the three uniform switches
+// ---------------------------------------------------------------------------------------------
+// alpha / Dtalpha exist once the mode or the setter asks for them, zeroed when (re)made
+int ghip_visc_buffers(ghip_ctx *ctx)
+{
+  const size_t bytes = (size_t) (ctx->ngas > 0 ? ctx->ngas : 1) * 8;
+  for(DevBuf *b : {&ctx->visc_alpha, &ctx->visc_dtalpha})
+    {
+      const size_t before = b->cap;
+      GCHK(ghip_ensure(ctx, *b, bytes));
+      if(b->cap != before)
+        HIPCHK(hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
+    }
+  return GHIP_OK;
+}
+
+// what ghip_hydro, GHIP_DD_HYDRO and ghip_advance_timesteps ask before they launch anything
+int ghip_visc_ready(ghip_ctx *ctx, const char *who)
+{
+  if(!ctx->visc_on)
+    return GHIP_OK;
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: ghip_set_viscosity is not available on a replicated shard "
+                     "(ghip_set_shard with %d ranks); use the ghip_dd_* contexts", who, ctx->shard_n);
+  if(ctx->visc.time_dependent && ctx->visc_ngas != ctx->ngas)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: time_dependent viscosity, but no alpha has been given for the %d gas "
+                     "particles of the context (ghip_visc_set_alpha after ghip_set_counts)", who, ctx->ngas);
+  return GHIP_OK;
+}
+
+extern "C" int ghip_set_viscosity(ghip_ctx *ctx, const ghip_visc_params *p)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));   // (no join: nothing here touches what a gravity pair in flight uses)
+  if(!p)
+    {
+      ctx->visc_on = false;
+      memset(&ctx->visc, 0, sizeof(ctx->visc));
+      return GHIP_OK;
+    }
+  const double vals[5] = {p->ArtBulkViscConst, p->AlphaMin, p->ViscSource, p->DecayTime, p->dtalpha_comoving_div};
+  static const char *const names[5] = {"ArtBulkViscConst", "AlphaMin", "ViscSource", "DecayTime", "dtalpha_comoving_div"};
+  for(int k = 0; k < 5; k++)
+    if(!std::isfinite(vals[k]))
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_viscosity: %s is not finite", names[k]);
+  if(p->AlphaMin < 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_viscosity: AlphaMin = %g < 0", p->AlphaMin);
+  if(p->AlphaMin > p->ArtBulkViscConst)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_viscosity: AlphaMin = %g > ArtBulkViscConst = %g", p->AlphaMin,
+                     p->ArtBulkViscConst);
+  const bool on = p->time_dependent || p->conventional || p->no_limiter || p->no_shear_limiter;
+  if(on && ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_viscosity: not available on a replicated shard (ghip_set_shard "
+                     "with %d ranks); use the ghip_dd_* contexts", ctx->shard_n);
+  if(p->time_dependent)
+    GCHK(ghip_visc_buffers(ctx));
+  ctx->visc = *p;
+  ctx->visc_on = on;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_visc_set_alpha(ghip_ctx *ctx, const double *alpha, const double *dtalpha)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));   // (no join: nothing here touches what a gravity pair in flight uses)
+  if(!alpha)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_visc_set_alpha: alpha is NULL");
+  const int ng = ctx->ngas;
+  for(int i = 0; i < ng; i++)
+    if(!std::isfinite(alpha[i]) || (dtalpha && !std::isfinite(dtalpha[i])))
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_visc_set_alpha: the value of gas particle %d is not finite", i);
+  GCHK(ghip_visc_buffers(ctx));
+  hipStream_t st = ctx->stream;
+  if(ng > 0)
+    {
+      HIPCHK(hipMemcpyAsync(ctx->visc_alpha.p, alpha, (size_t) ng * 8, hipMemcpyHostToDevice, st));
+      if(dtalpha)
+        HIPCHK(hipMemcpyAsync(ctx->visc_dtalpha.p, dtalpha, (size_t) ng * 8, hipMemcpyHostToDevice, st));
+      else
+        HIPCHK(hipMemsetAsync(ctx->visc_dtalpha.p, 0, (size_t) ng * 8, st));
+    }
+  HIPCHK(ghip_stream_sync(ctx, st));
+  ctx->visc_ngas = ng;
+  ctx->visc_epoch++;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_visc_get(ghip_ctx *ctx, double *alpha, double *dtalpha)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  HIPCHK(hipSetDevice(ctx->device));   // (no join: nothing here touches what a gravity pair in flight uses)
+  const int ng = ctx->ngas;
+  if(ctx->visc_ngas != ng)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_visc_get: no alpha has been given for the %d gas particles of the "
+                     "context (ghip_visc_set_alpha after ghip_set_counts)", ng);
+  hipStream_t st = ctx->stream;
+  if(ng > 0 && alpha)
+    HIPCHK(hipMemcpyAsync(alpha, ctx->visc_alpha.p, (size_t) ng * 8, hipMemcpyDeviceToHost, st));
+  if(ng > 0 && dtalpha)
+    HIPCHK(hipMemcpyAsync(dtalpha, ctx->visc_dtalpha.p, (size_t) ng * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  return ghip_check_device_errors(ctx);
+}
+
+// begrun.c:132-133 as written: (GAMMA - 1) / 2 * GAMMA is the reference's expression, left to right
+extern "C" void ghip_visc_derive(double ViscSource0, double DecayLength, double *ViscSource, double *DecayTime)
+{
+  if(ViscSource)
+    *ViscSource = ViscSource0 / log((GAMMA + 1) / (GAMMA - 1));
+  if(DecayTime)
+    *DecayTime = 1 / DecayLength * sqrt((GAMMA - 1) / 2 * GAMMA);
+}
+
+extern "C" size_t ghip_visc_params_size(void) { return sizeof(ghip_visc_params); }
 
 extern "C" int ghip_set_hydro_release(ghip_ctx *ctx, int early)
 {

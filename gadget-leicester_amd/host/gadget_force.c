@@ -118,6 +118,7 @@ static int KickN = 0, KickCap = 0;
 /* cfg.pin_records: the record arrays page-locked so far */
 static void *PinP, *PinS;
 static size_t PinPBytes, PinSBytes;
+static int ViscOnDevice = 0;     /* the context holds a setting of gadget_force_bind_viscosity */
 static int DensPending = 0;      /* overlap_sph: density()'s results are still on the device */
 static int *ActiveBuf = NULL;
 static int ActiveCap = 0;
@@ -280,6 +281,7 @@ void gadget_force_finalize(void)
   KickN = KickCap = 0;
   KeptTree = 0;
   Ctx = NULL;
+  ViscOnDevice = 0;
   free(ActiveBuf);
   ActiveBuf = NULL;
   ActiveCap = 0;
@@ -1225,10 +1227,135 @@ void force_update_hmax(void)
   CPU_Step_Hmaxupdate += wallclock() - t0;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * TIME_DEP_ART_VISC and the viscosity switches on bound records (gadget_force_bind_viscosity)
+ * ---------------------------------------------------------------------------------------- */
+static struct gadget_force_visc_layout ViscLay;   /* (all -1 until bound) */
+static const char *ViscAll = NULL;                /* the host's All for ViscLay.a_*; NULL: unbound */
+__attribute__((constructor)) static void visc_lay_defaults(void)
+{
+  memset(&ViscLay, 0xff, sizeof(ViscLay));
+}
+
+void gadget_force_bind_viscosity(void *host_All, const struct gadget_force_visc_layout *lay)
+{
+  if(lay)
+    {
+      ViscLay = *lay;
+      ViscAll = (const char *) host_All;
+    }
+  else
+    {
+      visc_lay_defaults();
+      ViscAll = NULL;
+    }
+}
+
+static int visc_bound(void)
+{
+  return ViscLay.time_dependent > 0 || ViscLay.conventional > 0 || ViscLay.no_limiter > 0 ||
+         ViscLay.no_shear_limiter > 0;
+}
+
+static int visc_refuse_ranks(const char *who)
+{
+  if(!visc_bound() || NTask <= 1)
+    return 0;
+  snprintf(ErrBuf, sizeof(ErrBuf), "%s: gadget_force_bind_viscosity serves a single rank (NTask = %d); ranks "
+           "run GHIP_DD_HYDRO with ghip_set_viscosity / ghip_visc_set_alpha of their own", who, NTask);
+  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+  endrun(90014);
+  return -1;
+}
+
+/* the setting and, with time_dependent, alpha and Dtalpha of the records reach the device */
+static int visc_begin(const char *who)
+{
+  if(!visc_bound())
+    {
+      if(ViscOnDevice && chk(ghip_set_viscosity(Ctx, NULL), "ghip_set_viscosity"))
+        return -1;
+      ViscOnDevice = 0;
+      return 0;
+    }
+  const int td = ViscLay.time_dependent > 0;
+  if(td && (!ViscAll || ViscLay.a_alpha_min < 0 || ViscLay.a_visc_source < 0 || ViscLay.a_decay_time < 0 ||
+            ViscLay.s_alpha < 0 || ViscLay.s_dtalpha < 0 || !RecP))
+    {
+      snprintf(ErrBuf, sizeof(ErrBuf), "%s: time_dependent viscosity needs bound records and the offsets of "
+               "AlphaMin, ViscSource, DecayTime, alpha and Dtalpha (gadget_force_bind_records, "
+               "gadget_force_bind_viscosity)", who);
+      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+      endrun(90002);
+      return -1;
+    }
+  ghip_visc_params v;
+  memset(&v, 0, sizeof(v));
+  v.time_dependent = td;
+  v.conventional = ViscLay.conventional > 0;
+  v.no_limiter = ViscLay.no_limiter > 0;
+  v.no_shear_limiter = ViscLay.no_shear_limiter > 0;
+  v.ArtBulkViscConst = All.ArtBulkViscConst;
+  if(td)
+    {
+      v.AlphaMin = *(const double *) (ViscAll + ViscLay.a_alpha_min);
+      v.ViscSource = *(const double *) (ViscAll + ViscLay.a_visc_source);
+      v.DecayTime = *(const double *) (ViscAll + ViscLay.a_decay_time);
+    }
+  v.dtalpha_comoving_div = All.ComovingIntegrationOn ? hubble_function(All.Time) * All.Time * All.Time : 1.0;
+  if(chk(ghip_set_viscosity(Ctx, &v), "ghip_set_viscosity"))
+    return -1;
+  ViscOnDevice = 1;
+  if(!td)
+    return 0;
+  double *a = (double *) malloc(((size_t) 2 * N_gas + 1) * 8);
+  if(!a)
+    {
+      endrun(90003);
+      return -1;
+    }
+  for(int i = 0; i < N_gas; i++)
+    {
+      a[i] = *SF64(i, ViscLay.s_alpha);
+      a[(size_t) N_gas + i] = *SF64(i, ViscLay.s_dtalpha);
+    }
+  int rc = chk(ghip_visc_set_alpha(Ctx, a, a + N_gas), "ghip_visc_set_alpha");
+  free(a);
+  return rc;
+}
+
+/* alpha and Dtalpha back into the records, after the call's download: the download rewrites whole records
+ * from the image of the last upload, so both members are written each time -- the device holds what
+ * visc_begin gathered, with Dtalpha of the targets (hydro_force) or alpha of the kicked gas
+ * (advance_and_find_timesteps) renewed */
+static int visc_end(void)
+{
+  if(!visc_bound() || ViscLay.time_dependent <= 0 || N_gas == 0)
+    return 0;
+  double *a = (double *) malloc((size_t) 2 * N_gas * 8);
+  if(!a)
+    {
+      endrun(90003);
+      return -1;
+    }
+  if(chk(ghip_visc_get(Ctx, a, a + N_gas), "ghip_visc_get"))
+    {
+      free(a);
+      return -1;
+    }
+  for(int i = 0; i < N_gas; i++)
+    {
+      *SF64(i, ViscLay.s_alpha) = a[i];
+      *SF64(i, ViscLay.s_dtalpha) = a[(size_t) N_gas + i];
+    }
+  free(a);
+  return 0;
+}
+
 /* hydra.c:145-813 */
 void hydro_force(void)
 {
-  if(need_ctx("hydro_force"))
+  if(need_ctx("hydro_force") || visc_refuse_ranks("hydro_force"))
     return;
   if(NTask > 1)
     {
@@ -1251,6 +1378,8 @@ void hydro_force(void)
         return;
     }
   else if(chk(ghip_set_active(Ctx, ActiveBuf ? ActiveBuf : &nact, nact), "ghip_set_active"))
+    return;
+  if(visc_begin("hydro_force"))
     return;
   ghip_hydro_params h;
   fill_hydro_params(&h, 0);
@@ -1286,6 +1415,8 @@ void hydro_force(void)
         return;
       trace("hydro_force: download");
     }
+  if(visc_end())   /* (behind the SPH download: nothing of this step is still in flight) */
+    return;
   Phase = 0;
   CPU_Step_Hydro += wallclock() - t0;
 }
@@ -1596,7 +1727,8 @@ static void rebuild_timebin_lists(void)
  * particle loop :142-260 with get_timestep and do_the_kick runs on the device */
 void advance_and_find_timesteps(void)
 {
-  if(need_ctx("advance_and_find_timesteps") || integration_refuse_ranks())
+  if(need_ctx("advance_and_find_timesteps") || integration_refuse_ranks() ||
+     visc_refuse_ranks("advance_and_find_timesteps"))
     return;
   gadget_force_flush();   /* (overlap_sph without a hydro_force() call: the kick needs G * GravAccel) */
   if(All.TypeOfTimestepCriterion != 0)
@@ -1652,7 +1784,7 @@ void advance_and_find_timesteps(void)
   k.logTimeMax = KickLogMax;
   k.GravKickTable = KickTabGrav;
   k.HydroKickTable = KickTabHydro;
-  if(integration_begin())
+  if(integration_begin() || visc_begin("advance_and_find_timesteps"))
     return;
   short *binold = NULL;   /* (the bins before the kick, for the per-bin sums) */
   if(integration_bound())
@@ -1676,7 +1808,7 @@ void advance_and_find_timesteps(void)
     }
   if(chk(rc, "ghip_advance_timesteps") ||
      chk(ghip_download_aos_kick(Ctx, records_p(), records_s(), &Lay), "ghip_download_aos_kick") ||
-     integration_end(binold))
+     integration_end(binold) || visc_end())
     {
       free(binold);
       return;

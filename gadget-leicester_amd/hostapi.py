@@ -91,6 +91,14 @@ class DustLayout(C.Structure):
         "a_unit_velocity")]
 
 
+class ViscLayout(C.Structure):
+    """struct gadget_force_visc_layout: byte offsets of All.AlphaMin / ViscSource / DecayTime and of
+    SphP[].alpha / Dtalpha (-1: absent), and the four viscosity switches"""
+    _fields_ = [(k, C.c_int) for k in (
+        "a_alpha_min", "a_visc_source", "a_decay_time", "s_alpha", "s_dtalpha",
+        "time_dependent", "conventional", "no_limiter", "no_shear_limiter")]
+
+
 class IntegrationLayout(C.Structure):
     """struct gadget_force_integration_layout: the shipped bundle's integrator switches and the byte
     offsets of the members it touches (-1: absent)"""
@@ -168,7 +176,8 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "DomainEndList", "gadget_force_unique_id", "gadget_force_connect",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
            "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration",
-           "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system"]
+           "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system",
+           "gadget_force_bind_viscosity"]
 
 _LIB = None
 
@@ -217,6 +226,8 @@ def lib():
         L.gadget_force_set_allgather.restype = None
         L.gadget_force_bind_dust.argtypes = [C.c_void_p, C.c_void_p]
         L.gadget_force_bind_dust.restype = None
+        L.gadget_force_bind_viscosity.argtypes = [C.c_void_p, C.c_void_p]
+        L.gadget_force_bind_viscosity.restype = None
         L.dust_density.restype = None
         L.dust_drag.restype = None
         L.gadget_force_bind_integration.argtypes = [C.c_void_p] * 6
@@ -285,6 +296,17 @@ class Host:
             return
         self._dust = (host_all, lay)            # keep alive
         self.L.gadget_force_bind_dust(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p))
+
+    def bind_viscosity(self, host_all, lay):
+        """gadget_force_bind_viscosity: `host_all` as for bind_dust (AlphaMin, ViscSource, DecayTime), `lay` a
+        ViscLayout naming them, alpha / Dtalpha of the bound SphP records and the switches; None unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_viscosity(None, None)
+            self._visc = None
+            return
+        self._visc = (host_all, lay)            # keep alive
+        self.L.gadget_force_bind_viscosity(None if host_all is None else C.c_void_p(host_all.ctypes.data),
+                                           C.cast(C.byref(lay), C.c_void_p))
 
     def bind_integration(self, host_all, lay, bin_sfr=None, bin_bh_mass=None, bin_bh_dynmass=None,
                          bin_bh_mdot=None):
@@ -359,6 +381,7 @@ class Host:
         self.L.gadget_force_bind_dust(None, None)
         self.L.gadget_force_bind_integration(None, None, None, None, None, None)
         self.L.gadget_force_bind_potential(None, None)
+        self.L.gadget_force_bind_viscosity(None, None)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)
         self._seti("ThisTask", 0)
         self._seti("NTask", 1)

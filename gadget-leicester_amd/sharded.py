@@ -195,6 +195,21 @@ class DomainShards:
     def migrate(self):
         self.run(self.B.DD_MIGRATE, None)
 
+    def set_viscosity(self, params=None):
+        """ghip_set_viscosity on every shard (the setting must be the same on all of them)"""
+        for p in self.paths:
+            p.set_viscosity(params)
+
+    def visc_set_alpha(self, alpha, dtalpha=None):
+        """per shard: alpha (and Dtalpha or None) of its own gas, in its order.  Before density(): a ghost
+        carries its owner's alpha as of the ghost refresh that ends GHIP_DD_DENSITY."""
+        for r, p in enumerate(self.paths):
+            p.visc_set_alpha(alpha[r], None if dtalpha is None else dtalpha[r])
+
+    def visc_get(self):
+        """[(alpha, Dtalpha)] per shard"""
+        return [p.visc_get() for p in self.paths]
+
     def decompose(self, params=None):
         """GHIP_DD_DECOMPOSE(DecompParams; None = automatic level, unit weights, the cube kept): new key
         ranges (and on request a new cube) from the resident particles of all shards.  Moves nothing."""
@@ -295,6 +310,17 @@ class DomainRank:
 
     def migrate(self):
         self._run(self.B.DD_MIGRATE, None)
+
+    def set_viscosity(self, params=None):
+        """ghip_set_viscosity on this rank; the caller gives every rank the same setting"""
+        self.p.set_viscosity(params)
+
+    def visc_set_alpha(self, alpha, dtalpha=None):
+        """alpha (and Dtalpha or None) of this rank's own gas, before density()"""
+        self.p.visc_set_alpha(alpha, dtalpha)
+
+    def visc_get(self):
+        return self.p.visc_get()
 
     def decompose(self, params=None):
         """GHIP_DD_DECOMPOSE(DecompParams; None = automatic level, unit weights, the cube kept), a collective:

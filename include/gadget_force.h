@@ -458,6 +458,26 @@ struct gadget_force_dust_layout
   int a_mean_weight, a_unit_density, a_unit_velocity;
 };
 void gadget_force_bind_dust(void *host_All, const struct gadget_force_dust_layout *lay);
+
+/* -DTIME_DEP_ART_VISC and the uniform viscosity switches of hydro_evaluate (hydra.c:1512-1595) on bound
+ * records (ghip_set_viscosity, include/ghip.h).  Byte offsets of All.AlphaMin / All.ViscSource /
+ * All.DecayTime (doubles, as begrun.c:132-133 left them) in the host's All, of SphP[].alpha and
+ * SphP[].Dtalpha (doubles) in the bound SphP records, and the four compile-time switches as ints
+ * (> 0: defined).  -1 = absent; time_dependent needs all five offsets.  Once bound, hydro_force()
+ * gathers alpha and Dtalpha from the records, runs, and writes both back once the SPH results have
+ * arrived (also with cfg.overlap_sph): Dtalpha of the active gas is new.
+ * advance_and_find_timesteps() gathers them again, applies timestep.c:530-533 and writes both back:
+ * alpha of the kicked gas is new.  All.ArtBulkViscConst is the mirror's own.  lay == NULL unbinds.
+ * Single rank: with NTask > 1 a bound table makes hydro_force() and advance_and_find_timesteps()
+ * call endrun(90014) and write nothing -- ranks drive GHIP_DD_HYDRO with ghip_set_viscosity /
+ * ghip_visc_set_alpha themselves. */
+struct gadget_force_visc_layout
+{
+  int a_alpha_min, a_visc_source, a_decay_time;
+  int s_alpha, s_dtalpha;
+  int time_dependent, conventional, no_limiter, no_shear_limiter;
+};
+void gadget_force_bind_viscosity(void *host_All, const struct gadget_force_visc_layout *lay);
 void dust_density(void);
 void dust_drag(void);
 

@@ -976,6 +976,50 @@ int ghip_set_massless_gas_rule(ghip_ctx *ctx, int rule);
  * starts at once -- the step's kernels take 0.2 ms longer at c2, but a host that downloads the SPH
  * results gets them across while the walks still run. */
 int ghip_set_hydro_release(ghip_ctx *ctx, int early);
+/* ---- the artificial viscosity of the pair loop beyond the constant All.ArtBulkViscConst of
+ * ghip_hydro_params: -DTIME_DEP_ART_VISC (Morris & Monaghan: every gas particle has its own alpha with a
+ * source in compressions and a decay elsewhere) and the three uniform switches of hydra.c:1512-1595.  A
+ * setting of the context, for ghip_hydro, GHIP_DD_HYDRO and ghip_advance_timesteps alike:
+ *   ghip_hydro   BulkVisc_ij = (alpha_i + alpha_j) / 2 (hydra.c:1541-1545); under `conventional` the
+ *                mu_ij of :1516-1518 also enters vsig (:1520), so MAXSIGNALVEL changes with it; the
+ *                post-pass writes Dtalpha of the call's targets (hydra.c:735-744, evaluated with
+ *                v.DivVel / r.CurlVel: the u.s.* members the reference names exist only under
+ *                -DNAVIERSTOKES), non-targets keep theirs
+ *   ghip_advance_timesteps   alpha += Dtalpha dt_entr, clamped to [AlphaMin, ArtBulkViscConst]
+ *                (timestep.c:530-533), for the active Type 0 records of the gas block; ghip_pm_kick
+ *                leaves alpha alone
+ * The alpha a hydro call uses is the one held when it is called, also on a tree kept across kicks
+ * (ghip_set_dynamic_tree).  p == NULL or all four switches 0: the default kernels, nothing allocated.
+ * Not built: -DALTVISCOSITY, -DALTERNATIVE_VISCOUS_TIMESTEP, -DNAVIERSTOKES, -DHIGH_ART_VISC_START (the
+ * host sets its initial alpha itself).
+ * GHIP_EINVAL, before anything is launched: a value that is not finite; AlphaMin < 0 or
+ * > ArtBulkViscConst; a context of ghip_set_shard (use the ghip_dd_* contexts); ghip_hydro /
+ * GHIP_DD_HYDRO / ghip_advance_timesteps with time_dependent set and no alpha given since
+ * ghip_set_counts last changed the counts; ghip_visc_get without alpha.
+ * On ghip_dd_* contexts the setting must be the same on all ranks (the caller's duty: nothing checks it);
+ * a ghost carries its owner's alpha as of the GHIP_DD_DENSITY before, in the record it has always had --
+ * no byte more on the links -- so alpha is set before GHIP_DD_DENSITY: a GHIP_DD_HYDRO on more than one
+ * rank after alpha changed since (ghip_visc_set_alpha, a kick) is GHIP_EINVAL, not a pair of two epochs;
+ * every shard computes Dtalpha for its own targets. ---- */
+typedef struct
+{
+  int time_dependent;     /* TIME_DEP_ART_VISC: BulkVisc_ij = (alpha_i + alpha_j) / 2  (hydra.c:1541-1545) */
+  int conventional;       /* CONVENTIONAL_VISCOSITY: mu_ij, visc of hydra.c:1516-1518, 1549-1551 */
+  int no_limiter;         /* NOVISCOSITYLIMITER: skip hydra.c:1583-1595 */
+  int no_shear_limiter;   /* NO_SHEAR_VISCOSITY_LIMITER: f1 = f2 = 1 (hydra.c:1538-1540) */
+  double ArtBulkViscConst;/* upper clamp of alpha in the kick (timestep.c:531) */
+  double AlphaMin, ViscSource, DecayTime;   /* All.* after begrun.c:132-133 */
+  double dtalpha_comoving_div;  /* hubble_a * All.Time^2 (hydra.c:742-743); read only when the hydro call is comoving */
+} ghip_visc_params;
+int ghip_set_viscosity(ghip_ctx *ctx, const ghip_visc_params *p);     /* NULL: everything off (the default path) */
+/* SphP[].alpha / SphP[].Dtalpha of the resident gas, [ngas] in host order (a shard's own gas in its
+ * order); dtalpha NULL: zeros.  Resident next to the GHIP_F_* fields from the first call on. */
+int ghip_visc_set_alpha(ghip_ctx *ctx, const double *alpha, const double *dtalpha);
+int ghip_visc_get(ghip_ctx *ctx, double *alpha, double *dtalpha);     /* either may be NULL; synchronises */
+/* All.ViscSource = ViscSource0 / log((GAMMA + 1) / (GAMMA - 1)), All.DecayTime = 1 / DecayLength *
+ * sqrt((GAMMA - 1) / 2 * GAMMA): begrun.c:132-133 as written, GAMMA = 7 / 5.  Host arithmetic. */
+void ghip_visc_derive(double ViscSource0, double DecayLength, double *ViscSource, double *DecayTime);
+size_t ghip_visc_params_size(void);   /* sizeof(ghip_visc_params) of the library, for bindings to check */
 
 /* one fixed-h evaluation for a single target (density_evaluate mode 0, density.c:711):
  * out7 = rho, numngb, dhsmlrho, divv, rot[3] (raw sums, before finalisation) */
