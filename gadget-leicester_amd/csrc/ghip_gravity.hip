@@ -571,11 +571,12 @@ static void launch_walk(ghip_ctx *ctx, const TreeDev &t, const WalkSeg &sg, int 
   // dynamic LDS per one-wavefront workgroup caps it: 8 KB = 20 per CU = 5 per SIMD (13.0 -> 11.4 ms
   // per step at c2 when it was introduced); 10 KB = 4 per SIMD since the round-3 instruction diet of
   // the visit made the Newtonian wavefronts quicker (same build, c2: 8.59 ms with 8 KB -- the Ewald
-  // walk then ends after the Newtonian one and hydro after both -- 8.43 with 10 KB; the LDS
-  // allocation granularity leaves nothing in between).
-  // (which of the two suits depends on the workload: at c2 10 KB balances the pair, at c4's size 8 KB
-  // does -- 75.6 against 80.3 ms per step; the choice follows the measured durations of the last pair
-  // that ran under the cap in use: pair_balance below.  GHIP_PAIR_NEWTON_LDS fixes it.)
+  // walk then ends after the Newtonian one and hydro after both -- 8.43 with 10 KB); 6 KB = 24 per CU
+  // = 6 per SIMD since the walk fits 56 registers (6 * 56 + 112: room for the Ewald walk, none for
+  // density).  The caps are whole LDS allocation granules (GHIP_PAIR_LDS, ghip_internal.h).
+  // (which one suits depends on the workload: with 64 registers c2 wanted 10 KB, c4's size 8 KB
+  // -- 75.6 against 80.3 ms per step; the choice follows the measured durations of the last pairs
+  // that ran under each cap: pair_balance below.  GHIP_PAIR_NEWTON_LDS fixes it.)
   static int lds_env = -1;
   if(lds_env < 0)
     lds_env = getenv("GHIP_PAIR_NEWTON_LDS") ? atoi(getenv("GHIP_PAIR_NEWTON_LDS")) : 0;
@@ -700,13 +701,28 @@ static int combine_walk(ghip_ctx *ctx, const WalkJob &J, int nt, const int *tgt,
   return GHIP_OK;
 }
 
-// How many Newtonian wavefronts a pair admits per SIMD (the dynamic-LDS cap of launch_walk): 8 KB = 5
-// per SIMD or 10 KB = 4 per SIMD -- the allocation granularity leaves nothing in between.  Which one
-// is better depends on the workload, so it is measured: every pair records its walks' start / end
-// events together with the setting it ran under; finished pairs are read back here (never waited
-// for) and cost max(Newtonian, Ewald), or max(Newtonian, 1.1 x Ewald) when the hydro kernel was
-// queued underneath the pair -- about a tenth of the Ewald walk, it can only start when that walk drains.  The cheaper setting is used; the other one is tried
-// again for one measurement every 64 pairs.  Scheduling only: the sums of a launch do not depend on it.
+// How many Newtonian wavefronts a pair admits per SIMD (the dynamic-LDS cap of launch_walk): 6 KB = 6,
+// 8 KB = 5 or 10 KB = 4 per SIMD (GHIP_PAIR_LDS, ghip_internal.h: the allocation granularity leaves
+// nothing in between).  At 56 registers per Newtonian wavefront 5 of them leave room for the Ewald
+// walk AND a density wavefront (5 * 56 + 112 + 112 = 504 of 512), 4 also for hydro (128), 6 for the
+// Ewald walk alone.  Which one is best depends on the workload, so it is measured: every pair records
+// its walks' start / end events together with the setting it ran under; finished pairs are read back
+// here (never waited for) and cost max(Newtonian, Ewald), or max(Newtonian, 1.1 x Ewald) when the
+// hydro kernel was queued underneath the pair -- about a tenth of the Ewald walk, it can only start
+// when that walk drains.  The cheapest setting is used; each of the others is tried again for one
+// measurement every 64 pairs (16 while it is within 10 % of the one in use).  Scheduling only: the
+// sums of a launch do not depend on it.
+static const int pair_caps[GHIP_PAIR_NSET] = {GHIP_PAIR_LDS(6), GHIP_PAIR_LDS(5), GHIP_PAIR_LDS(4)};
+
+static int pair_setting(int lds)   // index of a cap in pair_caps (the nearest one from below)
+{
+  int k = 0;
+  for(int j = 1; j < GHIP_PAIR_NSET; j++)
+    if(lds >= pair_caps[j])
+      k = j;
+  return k;
+}
+
 static int pair_balance(ghip_ctx *ctx)
 {
   if(!ctx->pc_ev[3][3])
@@ -717,6 +733,7 @@ static int pair_balance(ghip_ctx *ctx)
             HIPCHK(hipEventCreate(&ctx->pc_ev[i][j]));
       return GHIP_OK;
     }
+  bool pending[GHIP_PAIR_NSET] = {};   // a pair under that setting is still in flight
   for(int i = 0; i < 4; i++)
     {
       if(ctx->pc_cap[i] == 0)
@@ -725,12 +742,13 @@ static int pair_balance(ghip_ctx *ctx)
       if(hipEventQuery(e[1]) != hipSuccess || hipEventQuery(e[3]) != hipSuccess)
         {
           (void) hipGetLastError();   // (hipErrorNotReady is not an error)
+          pending[pair_setting(ctx->pc_cap[i])] = true;
           continue;
         }
       float tn = 0, te = 0;
       if(hipEventElapsedTime(&tn, e[0], e[1]) == hipSuccess && hipEventElapsedTime(&te, e[2], e[3]) == hipSuccess)
         {
-          const int k = ctx->pc_cap[i] > 8192 ? 1 : 0;
+          const int k = pair_setting(ctx->pc_cap[i]);
           // (only a hydro kernel that waits underneath the pair lengthens the Ewald side)
           const float fe = ctx->pc_hyd[i] ? 1.1f : 1.0f;
           const float c = tn > fe * te ? tn : fe * te;
@@ -741,27 +759,43 @@ static int pair_balance(ghip_ctx *ctx)
         (void) hipGetLastError();
       ctx->pc_cap[i] = 0;
     }
-  ctx->pc_age[0]++;
-  ctx->pc_age[1]++;
-  const int cur = ctx->pair_lds > 8192 ? 1 : 0, oth = cur ^ 1;
-  if(ctx->pc_cost[cur] < 0)
+  for(int k = 0; k < GHIP_PAIR_NSET; k++)
+    ctx->pc_age[k]++;
+  const int cur = pair_setting(ctx->pair_lds);
+  const float *cost = ctx->pc_cost;
+  if(cost[cur] < 0)
     return GHIP_OK;   // nothing known about the setting in use yet: keep it
-  int want = cur;
-  // (a measurement of the other setting goes stale: after 64 pairs, after 16 when the two are within
-  // 10 % of each other -- the first pairs of a run are not representative, their plans have no history)
-  const bool close = ctx->pc_cost[oth] > 0 && ctx->pc_cost[oth] < 1.1f * ctx->pc_cost[cur] &&
-                     ctx->pc_cost[cur] < 1.1f * ctx->pc_cost[oth];
-  if(ctx->pc_cost[oth] < 0 || ctx->pc_age[oth] > (close ? 16 : 64))
-    want = oth;       // (stays there until a pair under it has been measured)
-  else if(ctx->pc_cost[oth] < ctx->pc_cost[cur])
-    want = oth;
-  ctx->pair_lds = want ? 10240 : 8192;
+  // A measurement of a setting not in use goes stale: after 64 pairs, after 16 when it is within 10 %
+  // of the one in use -- the first pairs of a run are not representative, their plans have no history.
+  // The stalest one (an unmeasured one first) gets the next pair, unless one under it is on its way.
+  int want = cur, probe = -1;
+  for(int k = 0; k < GHIP_PAIR_NSET; k++)
+    {
+      if(k == cur || pending[k])
+        continue;
+      const bool close = cost[k] > 0 && cost[k] < 1.1f * cost[cur] && cost[cur] < 1.1f * cost[k];
+      if(cost[k] < 0 || ctx->pc_age[k] > (close ? 16 : 64))
+        {
+          if(probe < 0 || (cost[k] < 0 && cost[probe] >= 0) ||
+             ((cost[k] < 0) == (cost[probe] < 0) && ctx->pc_age[k] > ctx->pc_age[probe]))
+            probe = k;
+        }
+      else if(cost[k] < cost[want])
+        want = k;
+    }
+  if(probe >= 0)
+    want = probe;     // (one pair; its measurement decides at a later call)
+  ctx->pair_lds = pair_caps[want];
   static int dbg = -1;
   if(dbg < 0)
     dbg = getenv("GHIP_PAIR_DEBUG") ? 1 : 0;
   if(dbg)
-    fprintf(stderr, "[pair_balance] cost 8K %.3f (age %d)  10K %.3f (age %d)  -> %d\n", ctx->pc_cost[0],
-            ctx->pc_age[0], ctx->pc_cost[1], ctx->pc_age[1], ctx->pair_lds);
+    {
+      fprintf(stderr, "[pair_balance] cost");
+      for(int k = 0; k < GHIP_PAIR_NSET; k++)
+        fprintf(stderr, " %dK %.3f (age %d)", pair_caps[k] >> 10, cost[k], ctx->pc_age[k]);
+      fprintf(stderr, "  -> %d\n", ctx->pair_lds);
+    }
   return GHIP_OK;
 }
 

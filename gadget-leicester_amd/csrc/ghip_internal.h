@@ -313,7 +313,6 @@ struct DevWords
   alignas(128) unsigned int pair_started;   // the pair's Ewald walk has dispatched its last workgroup
   alignas(128) unsigned long long ghost_growth;   // density on shards: largest h growth (bits of a double)
   unsigned long long timebin_hist[64];      // ghip_timebin_counts: all particles [0, 32), gas [32, 64)
-  int sel_left;        // ghip_density_impl: targets left after an h iteration (k_sel_scan)
   int list_count;      // make_list (ghip_tree.hip): targets selected
   int dust_partners;   // ghip_dd_dust_groups: local Type 0 / Type 2 particles selected
   int gas_targets;     // density on shards: gas targets selected
@@ -328,6 +327,8 @@ struct alignas(64) PinnedWords
 {
   TreeSizes sizes[2];   // host mirrors of the trees' sizes (gt.hsz, st.hsz)
   int gas_mixed;        // the record unpack met a record of the gas block [0, ngas) that is not Type 0
+  int sel_left;         // ghip_density_impl: targets left after an h iteration, written by k_sel_scan (a
+                        // copy to the host would be one more kernel of the runtime's that waits behind the pair)
 };
 
 // the gravity tree between two full builds with what moves it (ghip_set_dynamic_tree, ghip_export.hip)
@@ -365,6 +366,17 @@ struct PmMesh
   PmMesh &operator=(const PmMesh &) = delete;
   ~PmMesh();
 };
+
+// The Newtonian walk of a Newton + Ewald pair is held to W one-wavefront workgroups per SIMD (4 W per
+// CU) by unused dynamic LDS: the largest allocation of which 4 W fit into a CU's 160 KB, a whole
+// number of 2 KB allocation granules.  W = 4: 10 KB (16 per CU), W = 5: 8 KB (20), W = 6: 6 KB (24 fit;
+// the next granule, 8 KB, admits 20 again -- the granules leave nothing in between).
+#define GHIP_LDS_PER_CU 163840
+#define GHIP_LDS_GRANULE 2048
+#define GHIP_PAIR_LDS(W) ((GHIP_LDS_PER_CU / (4 * (W))) / GHIP_LDS_GRANULE * GHIP_LDS_GRANULE)
+#define GHIP_PAIR_NSET 3   // settings the balance chooses from: W = 6, 5, 4
+static_assert(GHIP_PAIR_LDS(4) == 10240 && GHIP_PAIR_LDS(5) == 8192 && GHIP_PAIR_LDS(6) == 6144,
+              "dynamic-LDS caps of the pair");
 
 struct ghip_ctx
 {
@@ -512,14 +524,16 @@ struct ghip_ctx
   bool dyn_on = false, dyn_valid = false, dyn_use = false;
   DynTree dyn;
   // balance of a Newton + Ewald pair (ghip_gravity.hip, pair_balance): dynamic LDS per Newtonian
-  // workgroup in use, and a ring of the last pairs' start / end events with the cap they ran under
-  int pair_lds = 10240;
+  // workgroup in use, and a ring of the last pairs' start / end events with the cap they ran under.
+  // A fresh context starts with 5 Newtonian wavefronts per SIMD: 5 * 56 + 112 + 112 registers host
+  // the Ewald walk and a density wavefront next to them.
+  int pair_lds = GHIP_PAIR_LDS(5);
   hipEvent_t pc_ev[4][4] = {};         // made by the first pair
   int pc_cap[4] = {0, 0, 0, 0};        // 0: slot empty or already read
   int pc_hyd[4] = {0, 0, 0, 0};        // the hydro kernel was queued underneath that pair
   int pc_head = 0;
-  float pc_cost[2] = {-1.f, -1.f};     // last measured cost of a pair under 8 KB / 10 KB
-  int pc_age[2] = {0, 0};              // pairs launched since that measurement
+  float pc_cost[GHIP_PAIR_NSET] = {-1.f, -1.f, -1.f};   // last measured cost of a pair under setting k
+  int pc_age[GHIP_PAIR_NSET] = {0, 0, 0};               // pairs launched since that measurement
   hipEvent_t ev_side = nullptr;    // end of ghip_gravity_to_records' work on the pair's stream
 
   // ---- run statistics without a host synchronisation per step (ghip_run_begin / ghip_step_begin /
@@ -580,6 +594,11 @@ int ghip_join(ghip_ctx *ctx);        // wait for a pair in flight AND complete a
 // one-wavefront workgroups, and a 256-thread workgroup -- which needs four free wavefront slots in
 // one CU at the same moment -- would starve behind them however high its stream's priority.
 static inline int ghip_wg(const ghip_ctx *ctx) { return ctx->grav_pending ? 64 : 256; }
+// The same for a device-to-device copy of 32-bit words on the main stream: hipMemcpyAsync becomes the
+// runtime's copy kernel, whose large workgroups wait for milliseconds behind a pair that fills every
+// register of the SIMDs (3.4 and 1.6 ms for the two 1 MB target lists in front of the density loop
+// at c2).  One-wavefront workgroups of a dozen registers take the first slot that frees (ghip_tree.hip).
+int ghip_copy_i32(ghip_ctx *ctx, int *dst, const int *src, size_t n);
 // pinned word the record unpack sets when a record of the gas block [0, ngas) is not Type 0
 static inline int *ghip_gas_mixed_word(ghip_ctx *ctx) { return &ctx->pinned->gas_mixed; }
 static inline DevWords *ghip_words(ghip_ctx *ctx) { return reinterpret_cast<DevWords *>(ctx->words.p); }

@@ -691,13 +691,12 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
   double *hcur = P<double>(ctx->dhcur);
   unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_DENS);
   unsigned long long *racc = ghip_rslot(ctx, GHIP_CK_DENS);
-  int *dnum = &ghip_words(ctx)->sel_left;
+  int *dnum = &ctx->pinned->sel_left;   // (pinned host memory: read after the wait below)
   HIPCHK(hipMemsetAsync(counter, 0, GHIP_CKIND_U64 * 8, st));
   HIPCHK(hipEventRecord(ctx->evp[6], st));
 
   int *cur = P<int>(ctx->dtgt_a), *nxt = P<int>(ctx->dtgt_b);
-  HIPCHK(hipMemcpyAsync(cur, P<int>(ctx->tg_gas) + lo, (size_t) nt * 4, hipMemcpyDeviceToDevice,
-                        st));
+  GCHK(ghip_copy_i32(ctx, cur, P<int>(ctx->tg_gas) + lo, (size_t) nt));
   k_dens_init<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(nt, cur, P<double>(ctx->gp), hcur,
                                              P<double>(ctx->dleft), P<double>(ctx->dright));
   BoxK b = make_box(p->BoxSize, p->periodic);
@@ -736,9 +735,8 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
       const int nblk = cdiv(ncur, SEL_BLOCK);
       k_sel_count<<<nblk, 64, 0, st>>>(ncur, P<int>(ctx->dflags), seloff);
       k_sel_scan<<<1, 64, 0, st>>>(nblk, seloff, dnum);
-      int left = 0;
-      HIPCHK(hipMemcpyAsync(&left, dnum, 4, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
+      const int left = *reinterpret_cast<const volatile int *>(dnum);
       GCHK(ghip_check_device_errors(ctx));   // (also what an asynchronous drift / kick deferred)
       if(left > 0)
         {

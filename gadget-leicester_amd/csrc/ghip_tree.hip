@@ -578,6 +578,28 @@ int ghip_gather_f64_lim(ghip_ctx *ctx, int n, const int *perm, const double *src
   return GHIP_OK;
 }
 
+// 1024 words per one-wavefront workgroup (ghip_copy_i32, ghip_internal.h)
+__global__ void __launch_bounds__(64) k_copy_i32(size_t n, const int *__restrict__ src, int *__restrict__ dst)
+{
+  const size_t base = (size_t) blockIdx.x * 1024 + threadIdx.x;
+#pragma unroll 4
+  for(int j = 0; j < 16; j++)
+    {
+      const size_t a = base + (size_t) j * 64;
+      if(a < n)
+        dst[a] = src[a];
+    }
+}
+
+int ghip_copy_i32(ghip_ctx *ctx, int *dst, const int *src, size_t n)
+{
+  if(n == 0)
+    return GHIP_OK;
+  k_copy_i32<<<(unsigned int) ((n + 1023) / 1024), 64, 0, ctx->stream>>>(n, src, dst);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
 int ghip_gather_f64(ghip_ctx *ctx, int n, const int *perm, const double *src, double *dst)
 {
   if(n <= 0)
@@ -1860,7 +1882,7 @@ static int make_list(ghip_ctx *ctx, TreeDev &t, int host_limit, DevBuf &list, in
   const bool mixed = (&t == &ctx->st) && ctx->gas_mixed;   // converted particles in the gas block: no targets
   if(ctx->nactive < 0 && !imports && !mixed)
     {
-      HIPCHK(hipMemcpyAsync(list.p, t.phorder.p, (size_t) n * 4, hipMemcpyDeviceToDevice, st));
+      GCHK(ghip_copy_i32(ctx, P<int>(list), P<int>(t.phorder), (size_t) n));
       *count = n;
       return GHIP_OK;
     }

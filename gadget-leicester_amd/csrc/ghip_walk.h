@@ -190,6 +190,37 @@ __device__ __forceinline__ double d_mass_over_r3(double mass, double x, double k
   return fma(c * e, p, c);
 }
 
+// The spline-softened case of the monopole kernel (r2 < h^2, forcetree.c:2150-2171), OUT OF LINE.
+// A vanishing share of the visits gets here, but inlined into the traversal its per-lane loop
+// invariants (1/h, h^-3, the spline constants, the class mask and scale constants of sqrt) and the
+// temporaries of the fp64 division stay allocated across the whole loop: 7 to 13 vector registers
+// of every walk, the difference between 64 and 56 per wavefront, which decides how many
+// wavefronts share a SIMD with the Ewald walk and the SPH kernels.  A real
+// call keeps them in the callee; both results come back by value, in registers (through a
+// pointer, `r` would cost 16 B of scratch per lane).  The operations and their order are those of
+// the inlined form: results do not change.
+struct SoftFac
+{
+  double fac, r;
+};
+static __device__ __attribute__((noinline, cold)) SoftFac d_grav_fac_inside(double mass, double r2,
+                                                                            double h)
+{
+  SoftFac o;
+  double r = sqrt(r2);
+  o.r = r;
+  double h_inv = 1.0 / h;
+  double h3_inv = h_inv * h_inv * h_inv;
+  double u = r * h_inv;
+  if(u < 0.5)
+    o.fac = mass * h3_inv * (10.666666666667 + u * u * (32.0 * u - 38.4));
+  else
+    o.fac = mass * h3_inv *
+            (21.333333333333 - 48.0 * u + 38.4 * u * u - 10.666666666667 * u * u * u -
+             0.066666666667 / (u * u * u));
+  return o;
+}
+
 // softened monopole kernel, forcetree.c:2143-2171.  r2 >= h^2: m / r^3 through d_rsqrt.
 __device__ __forceinline__ double d_grav_fac(double mass, double r2, double h, double h2,
                                              double &r_out)
@@ -200,16 +231,9 @@ __device__ __forceinline__ double d_grav_fac(double mass, double r2, double h, d
       r_out = r2 * rinv;
       return mass * rinv * rinv * rinv;
     }
-  double r = sqrt(r2);
-  r_out = r;
-  double h_inv = 1.0 / h;
-  double h3_inv = h_inv * h_inv * h_inv;
-  double u = r * h_inv;
-  if(u < 0.5)
-    return mass * h3_inv * (10.666666666667 + u * u * (32.0 * u - 38.4));
-  return mass * h3_inv *
-         (21.333333333333 - 48.0 * u + 38.4 * u * u - 10.666666666667 * u * u * u -
-          0.066666666667 / (u * u * u));
+  const SoftFac s = d_grav_fac_inside(mass, r2, h);
+  r_out = s.r;
+  return s.fac;
 }
 
 // trilinear Ewald look-up, forcetree.c:3097-3170, from the one-component table: plain rows of EN+1
@@ -713,7 +737,10 @@ __device__ __forceinline__ void d_walk_run(const WalkSeg &sg, int sub, const Wal
           steps++;
           A.e = __builtin_amdgcn_readfirstlane(
             d_walk_element<MODE, PERIODIC, UNEQUAL, true, REL>(A.e, HA, cold, p, srtab, ewtab, W, skipA));
-          if(A.e >= A.s1)
+          // (marked unlikely for the register allocator: the call in the softened branch reserves
+          // scalar registers, and what no longer fits must be the segment switch's operands, reloaded
+          // here, not the visit's -- by loop depth alone the ancestor replay below looks hotter)
+          if(__builtin_expect(A.e >= A.s1, 0))
             {
               // drain the touches first: their scratch registers must not be live while a load
               // into them is in flight across code the register allocator is free to spill in
