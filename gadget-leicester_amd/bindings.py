@@ -294,7 +294,8 @@ EXPORTS = [
     "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
     "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain",
     "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic",
-    "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size"]
+    "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
+    "ghip_set_rnd_table", "ghip_tree_max_level"]
 
 
 def lib():
@@ -422,6 +423,8 @@ def lib():
         L.ghip_visc_derive.restype = None
         L.ghip_visc_params_size.argtypes = []
         L.ghip_visc_params_size.restype = C.c_size_t
+        L.ghip_set_rnd_table.argtypes = [vp, vp, C.c_int]
+        L.ghip_tree_max_level.argtypes = []
         _LIB = L
     return _LIB
 
@@ -966,6 +969,20 @@ class ForcePath:
         """ViscParams or None (the constant viscosity of HydroParams); governs hydro, DD_HYDRO and
         advance_timesteps"""
         self._chk(self.L.ghip_set_viscosity(self.h, None if params is None else C.byref(params)))
+
+    # ---- randomised subnodes for coincident particles (ghip_set_rnd_table) ----
+    def set_rnd_table(self, table=None):
+        """the host's RndTable (any length; entries in [0, 1)) or None: unbind.  Copied by the call; governs
+        every tree_build after it.  IDs are the F_ID field."""
+        if table is None:
+            self._chk(self.L.ghip_set_rnd_table(self.h, None, 0))
+            return
+        t = np.ascontiguousarray(table, np.float64)
+        self._chk(self.L.ghip_set_rnd_table(self.h, _ptr(t), len(t)))
+
+    def tree_max_level(self):
+        """GHIP_TREE_MAXLEVEL: digits of a particle's path while a table is bound"""
+        return int(self.L.ghip_tree_max_level())
 
     def visc_set_alpha(self, alpha, dtalpha=None):
         """SphP[].alpha and SphP[].Dtalpha (None: zeros) of the resident gas, [ngas]"""

@@ -166,7 +166,8 @@ int ghip_check_device_errors(ghip_ctx *ctx)
     "the wavefront plan of a gravity walk exceeded its grid (ghip_walk.h, k_plan_fill)",
     "a target had to open a pruned node of an imported (other shard's) tree: the locally "
     "essential tree was incomplete",
-    "tree emission outside the element list, a malformed imported element (3), a particle outside its "
+    "tree emission outside the element list, a malformed imported element (3), paths deeper than "
+    "GHIP_TREE_MAXLEVEL (7: ghip_set_rnd_table), a particle outside its "
     "shard's key range (5: migrate first) or outside the domain cube (6: ghip_dd_set_domain with a fresh extent)",
     "a particle that passed the range check of the non-periodic mesh fell outside its lower octant (nothing was "
     "written for it): the region in force is inconsistent",
@@ -1165,6 +1166,35 @@ extern "C" int ghip_set_adaptive_gravsoft(ghip_ctx *ctx, int on)
     ctx->gt.built = false;   // particle and node softenings are baked into the element records
   ctx->adaptive_gravsoft = (on != 0);
   return GHIP_OK;
+}
+
+extern "C" int ghip_set_rnd_table(ghip_ctx *ctx, const double *table, int ntable)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  if(ntable < 0 || (table && ntable > 0x3fffffff))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_rnd_table: bad table size %d", ntable);
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->gt.built = false;   // the tree in place follows the old rule
+  ctx->st.built = false;
+  ctx->gas_pending = false;
+  if(!table || ntable == 0)
+    {
+      ctx->rnd_n = 0;
+      return GHIP_OK;
+    }
+  ctx->rnd_n = 0;
+  GCHK(ghip_ensure(ctx, ctx->rnd_table, (size_t) ntable * 8));
+  HIPCHK(hipMemcpyAsync(ctx->rnd_table.p, table, (size_t) ntable * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));   // (the table is the caller's)
+  ctx->rnd_n = ntable;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_tree_max_level(void)
+{
+  return GHIP_TREE_MAXLEVEL;
 }
 
 int ghip_read_slots(ghip_ctx *ctx, DevBuf &buf, unsigned long long out[GHIP_CK_COUNT][2])

@@ -1820,6 +1820,9 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: call ghip_dd_init first");
   if(!(ctx->dlen > 0))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: call ghip_dd_set_domain first");
+  if(ctx->rnd_n > 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: not while a table is bound with ghip_set_rnd_table (the cell "
+                     "of a pruned node inside a randomised region does not follow from a key range): unbind it");
   if(D.x.kind != 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: an exchange is still pending");
   HIPCHK(hipSetDevice(ctx->device));

@@ -79,7 +79,8 @@ struct TreeSizes
   int nelem;      // n + nnodes; 0 while the tree is unusable (bad != 0): every consumer then does nothing
   int nnodes;
   int maxlevel;
-  int bad;        // 1: more nodes than the element buffers hold; 2: key runs too long for the 32-bit sort
+  int bad;        // 1: more nodes than the element buffers hold; 2: key runs too long for the 32-bit sort;
+                  // 3: paths deeper than GHIP_TREE_MAXLEVEL (ghip_set_rnd_table)
   int n;          // sources
   int gen;        // build generation (host counter): tells a fresh mirror from a stale one
   int longrun;
@@ -94,6 +95,8 @@ struct TreeDev
   int maxlevel = GHIP_BITS;  // deepest node level
   // sort
   DevBuf key, skey, idx, perm, iperm;  // u64[n], u64[n], i32[n], i32[n] (sorted->host index), i32[nhost]
+  DevBuf skey2, rnd_long;              // u64[n]: second word of the paths; long runs of the re-sort (ghip_set_rnd_table)
+  bool rnd = false;                    // this build's paths have two words (a table is bound)
   DevBuf cpl, cnt, nb;                 // i32[n]: common prefix levels, node counts, exclusive scan
   DevBuf phkey, phorder;               // u64[n], i32[n]: tree-order indices in Peano-Hilbert order
   // pre-order element list
@@ -320,6 +323,7 @@ struct DevWords
   int pm_err;          // non-periodic mesh (ghip_pm.hip): a particle outside the allowed region (the range check)
   int tree_info[2][2]; // count_nodes, per tree (gravity, gas): {deepest level, longest key run the
                        // 32-bit sort left unsorted}; k_tree_info reads them and leaves them zeroed
+  int rnd_info[2][2];  // rnd_order (ghip_tree.hip), two sets used in turn: {crowded sources, long runs}
 };
 
 // ... and in pinned, device-visible host memory (ctx->pinned): kernels write, the host reads after a wait
@@ -491,6 +495,11 @@ struct ghip_ctx
   DevBuf visc_alpha, visc_dtalpha;     // f64[ngas] host order: SphP[].alpha, SphP[].Dtalpha (made on demand)
   int visc_ngas = -1;                  // gas count alpha was given for (-1: none since the counts changed)
   long long visc_epoch = 0;            // counts every change of alpha (ghip_visc_set_alpha, the kick)
+
+  // ---- randomised subnodes (ghip_set_rnd_table, ghip_tree.hip) ----
+  DevBuf rnd_table;                // f64[rnd_n]: the host's RndTable
+  int rnd_n = 0;                   // 0: no table bound (the level-GHIP_BITS leaf of identical keys)
+  unsigned int rnd_gen = 0;        // picks the set of DevWords::rnd_info a build counts in
 
   // ---- asynchronous tree build (ghip_tree.hip) ----
   // A build whose particle number equals the previous build's is enqueued without the host waiting
@@ -756,7 +765,7 @@ int ghip_dd_pmnp_step(ghip_ctx *ctx);
 // wavefronts share one bucket of 64 targets (wavefront `sub` takes segments sub, sub+nsub, ...);
 // see ghip_walk.h "Load balance"
 // ---------------------------------------------------------------------------------------------
-#define GHIP_MAXANC 24
+#define GHIP_MAXANC 48      // >= GHIP_TREE_MAXLEVEL: a segment may start below a chain of that many nodes
 #define GHIP_MAXSUB 8
 struct WalkSeg
 {

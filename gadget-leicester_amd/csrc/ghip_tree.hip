@@ -134,6 +134,45 @@ __device__ __forceinline__ int d_common_levels(unsigned long long a, unsigned lo
   return (__clzll((long long) x) - 1) / 3;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Randomised subnodes (ghip_set_rnd_table).  With a table bound a particle's path is a
+// string of GHIP_TREE_MAXLEVEL digits in two 63-bit words: k1 = digits 0..20, k2 = digits 21..41, digit d
+// at bits [60 - 3 (d mod 21), +3).  Without a table the second word does not exist and every kernel below
+// is its RND = false instantiation, which is the code of the one-word tree.
+// ---------------------------------------------------------------------------------------------
+#define RND_DEPTH GHIP_TREE_MAXLEVEL
+
+__device__ __forceinline__ int d_common_levels2(unsigned long long a1, unsigned long long a2,
+                                                unsigned long long b1, unsigned long long b2)
+{
+  if(a1 != b1)
+    return d_common_levels(a1, b1);
+  return GHIP_BITS + d_common_levels(a2, b2);   // RND_DEPTH: the two strings are one
+}
+
+// digit l (1-based: the child chosen in the node of depth l - 1) of a path
+template <bool RND>
+__device__ __forceinline__ int d_path_digit(unsigned long long k1, unsigned long long k2, int l)
+{
+  if(RND && l > GHIP_BITS)
+    return (int) ((k2 >> (63 - 3 * (l - GHIP_BITS))) & 7);
+  return (int) ((k1 >> (63 - 3 * l)) & 7);
+}
+
+// do two paths share their first L digits?
+template <bool RND>
+__device__ __forceinline__ bool d_same_cell(unsigned long long a1, unsigned long long a2, unsigned long long b1,
+                                            unsigned long long b2, int L)
+{
+  if(RND && L > GHIP_BITS)
+    {
+      const int sh = 63 - 3 * (L - GHIP_BITS);
+      return a1 == b1 && (a2 >> sh) == (b2 >> sh);
+    }
+  const int sh = 63 - 3 * L;
+  return (a1 >> sh) == (b1 >> sh);
+}
+
 // slvl (multi-GPU only, else nullptr): level of source i when it is an imported pruned node
 // ("pseudo-leaf", see k_emit_elements), 0 for a particle
 __global__ void k_prefix_levels(int n, const unsigned long long *__restrict__ skey,
@@ -168,7 +207,12 @@ __global__ void k_prefix_levels(int n, const unsigned long long *__restrict__ sk
 
 // k_prefix_levels and k_node_counts in one launch: the shared-digit counts with both neighbours come
 // straight from the keys
+// RND: the paths have a second word (skey2); two paths that are one over all RND_DEPTH digits cannot be told
+// apart by the tree: the deepest level reported is RND_DEPTH then, which k_tree_info turns into
+// TreeSizes.bad = 3, and the tree error word is raised (7)
+template <bool RND>
 __global__ void k_prefix_counts(int n, const unsigned long long *__restrict__ skey,
+                                const unsigned long long *__restrict__ skey2,
                                 const int *__restrict__ slvl, int *__restrict__ cpl,
                                 int *__restrict__ cnt, int *__restrict__ maxlevel,
                                 int *__restrict__ errword)
@@ -178,8 +222,27 @@ __global__ void k_prefix_counts(int n, const unsigned long long *__restrict__ sk
   if(i < n)
     {
       const unsigned long long k = skey[i];
-      const int craw = (i + 1 < n) ? d_common_levels(k, skey[i + 1]) : -1;
-      const int cprev = (i > 0) ? d_common_levels(skey[i - 1], k) : -1;
+      int craw, cprev;
+      if(RND)
+        {
+          const unsigned long long k2 = skey2[i];
+          craw = (i + 1 < n) ? d_common_levels2(k, k2, skey[i + 1], skey2[i + 1]) : -1;
+          cprev = (i > 0) ? d_common_levels2(skey[i - 1], skey2[i - 1], k, k2) : -1;
+          if(craw >= RND_DEPTH)
+            {
+              *(volatile int *) errword = 7;
+              if(RND_DEPTH > *(volatile int *) maxlevel)
+                atomicMax(maxlevel, RND_DEPTH);
+              craw = RND_DEPTH - 1;
+            }
+          if(cprev >= RND_DEPTH)
+            cprev = RND_DEPTH - 1;
+        }
+      else
+        {
+          craw = (i + 1 < n) ? d_common_levels(k, skey[i + 1]) : -1;
+          cprev = (i > 0) ? d_common_levels(skey[i - 1], k) : -1;
+        }
       cpl[i] = craw;
       int ceff = craw;
       if(slvl && slvl[i] > 0)
@@ -234,8 +297,10 @@ __global__ void k_node_counts(int n, const int *__restrict__ cpl, const int *__r
 
 // one thread per particle: emits the nodes that START at this particle (levels cprev+1..c_i, in
 // increasing depth = pre-order) followed by the particle itself.
+template <bool RND>
 __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
                                 const unsigned long long *__restrict__ skey,
+                                const unsigned long long *__restrict__ skey2,
                                 const int *__restrict__ cpl, const int *__restrict__ cnt,
                                 const int *__restrict__ nb, const double *__restrict__ px,
                                 const double *__restrict__ py, const double *__restrict__ pz,
@@ -256,6 +321,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
     ci = plevel - 1;
   int base = i + nb[i];
   unsigned long long ki = skey[i];
+  const unsigned long long ki2 = RND ? skey2[i] : 0ULL;
 
   if(ci > cprev)
     {
@@ -264,7 +330,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
       double len = dlen, cx = ccx, cy = ccy, cz = ccz;
       for(int l = 1; l <= cprev + 1; l++)
         {
-          int digit = (int) ((ki >> (63 - 3 * l)) & 7);
+          int digit = d_path_digit<RND>(ki, ki2, l);
           double lenhalf = 0.25 * len;
           cx = (digit & 1) ? cx + lenhalf : cx - lenhalf;
           cy = (digit & 2) ? cy + lenhalf : cy - lenhalf;
@@ -274,14 +340,12 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
       for(int L = cprev + 1; L <= ci; L++)
         {
           int e = base + (L - cprev - 1);
-          int sh = 63 - 3 * L;
-          unsigned long long prefix = ki >> sh;
           // end of the cell's particle range: gallop, then bisect (most cells hold a handful of
           // particles, so the doubling phase ends after two or three probes)
           int lo = i + 1, hi = n;
           for(int step = 1; lo + step < n; step <<= 1)
             {
-              if((skey[lo + step] >> sh) == prefix)
+              if(d_same_cell<RND>(skey[lo + step], RND ? skey2[lo + step] : 0ULL, ki, ki2, L))
                 lo = lo + step + 1;
               else
                 {
@@ -292,7 +356,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
           while(lo < hi)
             {
               int mid = (lo + hi) >> 1;
-              if((skey[mid] >> sh) == prefix)
+              if(d_same_cell<RND>(skey[mid], RND ? skey2[mid] : 0ULL, ki, ki2, L))
                 lo = mid + 1;
               else
                 hi = mid;
@@ -305,7 +369,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
           aux[e] = 0;
           if(L < ci)
             {
-              int digit = (int) ((ki >> (63 - 3 * (L + 1))) & 7);
+              int digit = d_path_digit<RND>(ki, ki2, L + 1);
               double lenhalf = 0.25 * len;
               cx = (digit & 1) ? cx + lenhalf : cx - lenhalf;
               cy = (digit & 2) ? cy + lenhalf : cy - lenhalf;
@@ -320,7 +384,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
     {
       // A node of another shard's tree that no target of this shard opens, imported as a leaf:
       // its moments (centre of mass, mass, softening word) come with it, its geometry is the
-      // level-`plevel` cell of its key.  lk.y = -(level+1) - 32 keeps the moment passes off it
+      // level-`plevel` cell of its key.  lk.y = -(level+1) - 64 keeps the moment passes off it
       // (they address nodes by -(level+1)); every other consumer sees a node (lk.y < 0) whose
       // skip link is e+1.
       double len = dlen, cx = ccx, cy = ccy, cz = ccz;
@@ -333,7 +397,7 @@ __global__ void k_emit_elements(int n, const TreeSizes *__restrict__ ts,
           cz = (digit & 4) ? cz + lenhalf : cz - lenhalf;
           len = 0.5 * len;
         }
-      lk[pe] = make_int4(pe + 1, -(plevel + 1) - 32, i, 1);
+      lk[pe] = make_int4(pe + 1, -(plevel + 1) - 64, i, 1);
       xm[pe] = make_double4(x, y, z, pm[i]);
       cl[pe] = make_double4(cx, cy, cz, len);
       aux[pe] = paux[i];
@@ -428,7 +492,7 @@ __device__ __forceinline__ void d_node_moments(int e, const int4 me, double4 *xm
 //   k_moments_upper: ONE workgroup takes those lists level by level, deepest first.
 // Children are summed in list (octant) order as ever, so the numbers are those of the level passes.
 #define MOM_CH 2048
-#define MOM_LEVELS (GHIP_BITS + 1)
+#define MOM_LEVELS RND_DEPTH   // node levels 0 .. RND_DEPTH - 1 (0 .. GHIP_BITS without a table)
 
 // BLOCK: 256 threads, or one wavefront for a pass that runs underneath a gravity pair (ghip_wg)
 template <bool GRAV, bool MOMENTS, int BLOCK>
@@ -441,7 +505,7 @@ k_moments_local(const TreeSizes *__restrict__ ts, double4 *xm, const double4 *cl
   if(c0 >= nelem)
     return;
   const int c1 = (c0 + MOM_CH < nelem) ? c0 + MOM_CH : nelem;
-  __shared__ unsigned int levels;           // levels at which this chunk owns nodes
+  __shared__ unsigned long long levels;     // levels at which this chunk owns nodes
   __shared__ signed char lev[MOM_CH];       // level of the node this chunk owns at each slot, -1: none
   if(threadIdx.x == 0)
     levels = 0;
@@ -465,18 +529,18 @@ k_moments_local(const TreeSizes *__restrict__ ts, double4 *xm, const double4 *cl
               else
                 {
                   mine = L;
-                  atomicOr(&levels, 1u << L);
+                  atomicOr(&levels, 1ULL << L);
                 }
             }
         }
       lev[q] = (signed char) mine;
     }
   __syncthreads();
-  unsigned int todo = levels;
+  unsigned long long todo = levels;
   while(todo)
     {
-      const int L = 31 - __clz(todo);   // deepest level first
-      todo &= ~(1u << L);
+      const int L = 63 - __clzll((long long) todo);   // deepest level first
+      todo &= ~(1ULL << L);
       for(int q = threadIdx.x; q < MOM_CH; q += BLOCK)
         if(lev[q] == L)
           d_node_moments<GRAV, MOMENTS>(c0 + q, lk[c0 + q], xm, cl, lk, aux, adaptive);
@@ -491,7 +555,7 @@ k_moments_upper(const TreeSizes *__restrict__ ts, double4 *xm, const double4 *cl
                 double *aux, bool adaptive, const int *__restrict__ upper, int ucap, int *ucount)
 {
   const bool usable = ts->nelem > 0;
-  for(int L = GHIP_BITS; L >= 0; L--)
+  for(int L = MOM_LEVELS - 1; L >= 0; L--)
     {
       const int nu = ucount[L];   // (the same for every thread: the branch is uniform)
       if(nu == 0 || !usable)
@@ -696,6 +760,234 @@ __global__ void k_gather_i32(int n, const int *__restrict__ idx, const int *__re
     dst[i] = src[idx[i]];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Randomised subnodes: the paths of the crowded particles (see RND_DEPTH above)
+// ---------------------------------------------------------------------------------------------
+// Below depth `tmin` (the shallowest depth at which any type randomises, at most GHIP_BITS) every path is
+// its Morton key.  A particle that shares no level-tmin Morton cell with another source is alone in that
+// cell whatever the paths of the others are -- theirs start with their own Morton digits too -- so its
+// path never matters beyond its key.  Everybody else is "crowded" and gets its full path.
+struct RndK
+{
+  const double *table;
+  int ntable;
+  int tmin;
+  double thr[6];   // 1.0e-3 * All.ForceSoftening[type] (forcetree.c:219)
+  double ccx, ccy, ccz, dlen;
+};
+
+// one pass over the sorted keys: flags; for the crowded the two path words (k1 -> key1[s], in sorted
+// order; k2 -> skey2[s]).  info[0] counts the crowded.
+__global__ void k_rnd_paths(int n, RndK K, const unsigned long long *__restrict__ skey,
+                            const int *__restrict__ perm, const double *__restrict__ x,
+                            const double *__restrict__ y, const double *__restrict__ z,
+                            const int *__restrict__ type, const int *__restrict__ id,
+                            unsigned long long *__restrict__ key1, unsigned long long *__restrict__ skey2,
+                            int *__restrict__ flag, int *__restrict__ info)
+{
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= n)
+    return;
+  const unsigned long long k = skey[s];
+  const int cn = (s + 1 < n) ? d_common_levels(k, skey[s + 1]) : -1;
+  const int cp = (s > 0) ? d_common_levels(skey[s - 1], k) : -1;
+  const bool crowded = cn >= K.tmin || cp >= K.tmin;
+  flag[s] = crowded ? 1 : 0;
+  if(!crowded)
+    {
+      skey2[s] = 0;
+      return;
+    }
+  atomicAdd(&info[0], 1);
+  const int i = perm[s];
+  int t = type[i];
+  t = t < 0 ? 0 : t > 5 ? 5 : t;
+  const double thr = K.thr[t];
+  const unsigned int pid = (unsigned int) id[i];
+  const double px = x[i], py = y[i], pz = z[i];
+  double len = K.dlen, cx = K.ccx, cy = K.ccy, cz = K.ccz;
+  unsigned long long k1 = 0, k2 = 0;
+  for(int d = 0; d < RND_DEPTH; d++)
+    {
+      int digit;
+      if(len < thr)
+        {
+          // get_random_number(ID + rep), system.c:161-172: rep = depth of the node
+          const unsigned int u = pid + (unsigned int) d;
+          const unsigned int j = (u % (unsigned int) (K.ntable + (d & 3))) % (unsigned int) K.ntable;
+          digit = (int) (8.0 * K.table[j]);
+          digit = digit > 7 ? 7 : digit < 0 ? 0 : digit;
+        }
+      else if(d < GHIP_BITS)
+        digit = (int) ((k >> (60 - 3 * d)) & 7);
+      else   // forcetree.c:208-217
+        digit = (px > cx ? 1 : 0) + (py > cy ? 2 : 0) + (pz > cz ? 4 : 0);
+      if(d < GHIP_BITS)
+        k1 |= (unsigned long long) digit << (60 - 3 * d);
+      else
+        k2 |= (unsigned long long) digit << (60 - 3 * (d - GHIP_BITS));
+      const double lenhalf = 0.25 * len;   // forcetree.c:260-276, as k_emit_elements
+      cx = (digit & 1) ? cx + lenhalf : cx - lenhalf;
+      cy = (digit & 2) ? cy + lenhalf : cy - lenhalf;
+      cz = (digit & 4) ? cz + lenhalf : cz - lenhalf;
+      len = 0.5 * len;
+    }
+  key1[s] = k1;
+  skey2[s] = k2;
+}
+
+__device__ __forceinline__ bool d_path_after(unsigned long long a1, unsigned long long a2, int ap,
+                                             unsigned long long b1, unsigned long long b2, int bp)
+{
+  return a1 > b1 || (a1 == b1 && (a2 > b2 || (a2 == b2 && ap > bp)));
+}
+
+// The crowded particles of one level-tmin Morton cell are consecutive in the sorted order and stay in that
+// cell: one thread per such run orders them by (k1, k2, index) in key1 / skey2 / perm, in place (the pattern
+// of k_fix_runs; skey still holds the Morton keys and tells the runs apart).  Runs longer than RND_SHORTRUN
+// go to a list for k_rnd_sort_long.
+#define RND_SHORTRUN 48
+__global__ void k_rnd_sort(int n, int tmin, const unsigned long long *__restrict__ skey,
+                           const int *__restrict__ flag, unsigned long long *__restrict__ key1,
+                           unsigned long long *__restrict__ skey2, int *__restrict__ perm,
+                           int *__restrict__ info, int2 *__restrict__ longruns, int maxlong)
+{
+  if(*(volatile int *) &info[0] == 0)
+    return;   // nothing crowded
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= n || !flag[s])
+    return;
+  const unsigned long long k = skey[s];
+  if(s > 0 && flag[s - 1] && d_common_levels(skey[s - 1], k) >= tmin)
+    return;   // not a run start
+  int e = s + 1;
+  while(e < n && flag[e] && d_common_levels(skey[e], k) >= tmin)
+    e++;
+  if(e - s > RND_SHORTRUN)
+    {
+      const int slot = atomicAdd(&info[1], 1);
+      if(slot < maxlong)
+        longruns[slot] = make_int2(s, e);
+      return;
+    }
+  for(int a = s + 1; a < e; a++)
+    {
+      const unsigned long long a1 = key1[a], a2 = skey2[a];
+      const int p = perm[a];
+      int b = a - 1;
+      while(b >= s && d_path_after(key1[b], skey2[b], perm[b], a1, a2, p))
+        {
+          key1[b + 1] = key1[b];
+          skey2[b + 1] = skey2[b];
+          perm[b + 1] = perm[b];
+          b--;
+        }
+      key1[b + 1] = a1;
+      skey2[b + 1] = a2;
+      perm[b + 1] = p;
+    }
+}
+
+// the long runs: one workgroup each, odd-even transposition in place (len passes of len / 2 exchanges)
+__global__ void __launch_bounds__(256)
+k_rnd_sort_long(const int *__restrict__ info, const int2 *__restrict__ longruns, int maxlong,
+                unsigned long long *__restrict__ key1, unsigned long long *__restrict__ skey2,
+                int *__restrict__ perm)
+{
+  int nlong = info[1];
+  nlong = nlong < maxlong ? nlong : maxlong;
+  for(int r = blockIdx.x; r < nlong; r += gridDim.x)
+    {
+      const int s = longruns[r].x, len = longruns[r].y - longruns[r].x;
+      for(int pass = 0; pass < len; pass++)
+        {
+          for(int q = (pass & 1) + 2 * (int) threadIdx.x; q + 1 < len; q += 2 * 256)
+            {
+              const int a = s + q, b = a + 1;
+              const unsigned long long a1 = key1[a], a2 = skey2[a], b1 = key1[b], b2 = skey2[b];
+              const int ap = perm[a], bp = perm[b];
+              if(d_path_after(a1, a2, ap, b1, b2, bp))
+                {
+                  key1[a] = b1;
+                  skey2[a] = b2;
+                  perm[a] = bp;
+                  key1[b] = a1;
+                  skey2[b] = a2;
+                  perm[b] = ap;
+                }
+            }
+          __syncthreads();
+        }
+    }
+}
+
+// the ordered first words take the place of the Morton keys.  The counters are two sets used in turn:
+// this build's stay readable while its kernels run, the next build's are zeroed here.
+__global__ void k_rnd_commit(int n, const int *__restrict__ flag, const unsigned long long *__restrict__ key1,
+                             unsigned long long *__restrict__ skey, const int *__restrict__ info,
+                             int *__restrict__ info_next)
+{
+  const int nc = info[0];
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(nc != 0 && s < n && flag[s])
+    skey[s] = key1[s];
+  if(s == 0)
+    info_next[0] = info_next[1] = 0;
+}
+
+// depth at which a type of softening `soft` starts to randomise in a domain of side dlen: the first d with
+// dlen 2^-d < 1.0e-3 soft (the halving is exact, so this is the device's own comparison)
+static int rnd_first_depth(double dlen, double soft)
+{
+  double len = dlen;
+  for(int d = 0; d < RND_DEPTH; d++)
+    {
+      if(len < 1.0e-3 * soft)
+        return d;
+      len = 0.5 * len;
+    }
+  return RND_DEPTH;
+}
+
+// with a table bound: the paths of the crowded sources of tree t (sorted by Morton key: t.skey, t.perm), their
+// order inside their cells, the second key word t.skey2.  x, y, z: the sources in host order.
+static int rnd_order(ghip_ctx *ctx, TreeDev &t, int n, const double *x, const double *y, const double *z)
+{
+  hipStream_t st = ctx->stream;
+  RndK K;
+  K.table = P<double>(ctx->rnd_table);
+  K.ntable = ctx->rnd_n;
+  K.tmin = GHIP_BITS;
+  for(int q = 0; q < 6; q++)
+    {
+      K.thr[q] = 1.0e-3 * ctx->soft[q];
+      const int d = rnd_first_depth(ctx->dlen, ctx->soft[q]);
+      if(d < K.tmin)
+        K.tmin = d;
+    }
+  K.ccx = ctx->center[0];
+  K.ccy = ctx->center[1];
+  K.ccz = ctx->center[2];
+  K.dlen = ctx->dlen;
+  const int maxlong = n / RND_SHORTRUN + 1;
+  GCHK(ghip_ensure(ctx, t.skey2, (size_t) n * 8));
+  GCHK(ghip_ensure(ctx, t.cnt, (size_t) n * 4));   // (the flags: count_nodes overwrites them)
+  GCHK(ghip_ensure(ctx, t.rnd_long, (size_t) maxlong * sizeof(int2)));
+  int *info = ghip_words(ctx)->rnd_info[ctx->rnd_gen & 1], *info_next = ghip_words(ctx)->rnd_info[(ctx->rnd_gen + 1) & 1];
+  ctx->rnd_gen++;
+  unsigned long long *key1 = P<unsigned long long>(t.key), *skey = P<unsigned long long>(t.skey),
+                     *skey2 = P<unsigned long long>(t.skey2);
+  const int wg = ghip_wg(ctx);
+  k_rnd_paths<<<cdiv(n, wg), wg, 0, st>>>(n, K, skey, P<int>(t.perm), x, y, z, P<int>(ctx->f[GHIP_F_TYPE]),
+                                          P<int>(ctx->f[GHIP_F_ID]), key1, skey2, P<int>(t.cnt), info);
+  k_rnd_sort<<<cdiv(n, wg), wg, 0, st>>>(n, K.tmin, skey, P<int>(t.cnt), key1, skey2, P<int>(t.perm), info,
+                                         P<int2>(t.rnd_long), maxlong);
+  k_rnd_sort_long<<<64, 256, 0, st>>>(info, P<int2>(t.rnd_long), maxlong, key1, skey2, P<int>(t.perm));
+  k_rnd_commit<<<cdiv(n, wg), wg, 0, st>>>(n, P<int>(t.cnt), key1, skey, info, info_next);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
 static int cub_tmp(ghip_ctx *ctx, size_t bytes)
 {
   return ghip_ensure(ctx, ctx->cubtmp, bytes + 256);
@@ -765,7 +1057,7 @@ __global__ void k_tree_info(int n, const int *__restrict__ nb, const int *__rest
   s.nnodes = nb[n - 1] + cnt[n - 1];
   s.maxlevel = dinfo[0];
   s.longrun = dinfo[1];
-  s.bad = (s.nnodes > cap_nodes) ? 1 : ((!wide && s.longrun != 0) ? 2 : 0);
+  s.bad = (s.maxlevel >= RND_DEPTH) ? 3 : (s.nnodes > cap_nodes) ? 1 : ((!wide && s.longrun != 0) ? 2 : 0);
   s.nelem = s.bad ? 0 : n + s.nnodes;
   s.n = n;
   s.gen = gen;
@@ -788,7 +1080,9 @@ __global__ void k_gas_flags(int n, int ngas, const int *__restrict__ perm, int *
 __global__ void k_gas_compact(int n, int ngas, const int *__restrict__ perm,
                               const unsigned long long *__restrict__ skey,
                               const int *__restrict__ rank, int *__restrict__ gperm,
-                              unsigned long long *__restrict__ gskey)
+                              unsigned long long *__restrict__ gskey,
+                              const unsigned long long *__restrict__ skey2,
+                              unsigned long long *__restrict__ gskey2)
 {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if(s >= n)
@@ -799,6 +1093,8 @@ __global__ void k_gas_compact(int n, int ngas, const int *__restrict__ perm,
       int r = rank[s];
       gperm[r] = i;
       gskey[r] = skey[s];
+      if(skey2)   // randomised subnodes: a path is the particle's own, so the gas tree's paths are these
+        gskey2[r] = skey2[s];
     }
 }
 
@@ -1050,9 +1346,14 @@ static int gas_order_from_gravity_tree(ghip_ctx *ctx)
   const int wg = ghip_wg(ctx);
   k_gas_flags<<<cdiv(n, wg), wg, 0, st>>>(n, ng, P<int>(g.perm), P<int>(ctx->dtgt_a));
   GCHK(exclusive_sum(ctx, P<int>(ctx->dtgt_a), P<int>(ctx->dtgt_b), n));
+  t.rnd = g.rnd;
+  if(t.rnd)
+    GCHK(ghip_ensure(ctx, t.skey2, (size_t) ng * 8));
   k_gas_compact<<<cdiv(n, wg), wg, 0, st>>>(n, ng, P<int>(g.perm),
                                               P<unsigned long long>(g.skey), P<int>(ctx->dtgt_b),
-                                              P<int>(t.perm), P<unsigned long long>(t.skey));
+                                              P<int>(t.perm), P<unsigned long long>(t.skey),
+                                              t.rnd ? P<unsigned long long>(g.skey2) : nullptr,
+                                              P<unsigned long long>(t.skey2));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -1076,8 +1377,14 @@ static int count_nodes(ghip_ctx *ctx, TreeDev &t, int n, bool gas, int cap_nodes
       slvl = P<int>(t.slvl);
     }
   const int wgp = ctx->grav_pending ? 64 : 1024, wg = ghip_wg(ctx);
-  k_prefix_counts<<<cdiv(n, wgp), wgp, 0, st>>>(n, P<unsigned long long>(t.skey), slvl, P<int>(t.cpl),
-                                                P<int>(t.cnt), dinfo, ghip_errword(ctx, GHIP_ERRW_TREE));
+  if(t.rnd)
+    k_prefix_counts<true><<<cdiv(n, wgp), wgp, 0, st>>>(n, P<unsigned long long>(t.skey),
+                                                        P<unsigned long long>(t.skey2), slvl, P<int>(t.cpl),
+                                                        P<int>(t.cnt), dinfo, ghip_errword(ctx, GHIP_ERRW_TREE));
+  else
+    k_prefix_counts<false><<<cdiv(n, wgp), wgp, 0, st>>>(n, P<unsigned long long>(t.skey), nullptr, slvl,
+                                                         P<int>(t.cpl), P<int>(t.cnt), dinfo,
+                                                         ghip_errword(ctx, GHIP_ERRW_TREE));
   HIPCHK(hipGetLastError());
   (void) wg;
   GCHK(exclusive_sum(ctx, P<int>(t.cnt), P<int>(t.nb), n));
@@ -1124,7 +1431,18 @@ static int tree_adopt_sizes(ghip_ctx *ctx, TreeDev &t, bool grow)
                      "(%d sources for %d)", ctx->build_gen, z.gen, z.n, t.n);
   t.nnodes = z.nnodes;
   t.nelem = t.n + z.nnodes;
-  t.maxlevel = z.maxlevel < GHIP_BITS ? z.maxlevel : GHIP_BITS;
+  t.maxlevel = z.maxlevel < RND_DEPTH - 1 ? z.maxlevel : RND_DEPTH - 1;
+  if(z.bad == 3)
+    {
+      // two sources whose paths are one over all RND_DEPTH digits (k_prefix_counts): nothing was emitted
+      // (nelem = 0 on the device).  The error is reported here, so its word is taken back.
+      *(volatile int *) ghip_errword(ctx, GHIP_ERRW_TREE) = 0;
+      t.built = false;
+      ctx->gas_pending = false;   // (no gas tree out of this order either)
+      return ghip_fail(ctx, GHIP_EDEVICE, "tree error: two sources share a cell at every one of the %d levels a "
+                       "path has (GHIP_TREE_MAXLEVEL): coincident particles that the table of ghip_set_rnd_table "
+                       "does not separate before that depth (cell side < 1e-3 ForceSoftening)", RND_DEPTH);
+    }
   if(z.bad == 0)
     {
       t.last_n = t.n;
@@ -1183,10 +1501,16 @@ static int emit_tree(ghip_ctx *ctx, TreeDev &t, int n, const double *x, const do
                                         P<int>(t.iperm));
   if(fork_after_gather)
     HIPCHK(hipEventRecord(*fork_after_gather, st));
-  k_emit_elements<<<cdiv(n, wg), wg, 0, st>>>(
-    n, ts, P<unsigned long long>(t.skey), P<int>(t.cpl), P<int>(t.cnt), P<int>(t.nb), ox, oy,
-    oz, om, oa, ctx->center[0], ctx->center[1], ctx->center[2], ctx->dlen, P<double4>(t.xm),
-    P<double4>(t.cl), P<int4>(t.lk), P<double>(t.aux), slvl);
+  if(t.rnd)
+    k_emit_elements<true><<<cdiv(n, wg), wg, 0, st>>>(
+      n, ts, P<unsigned long long>(t.skey), P<unsigned long long>(t.skey2), P<int>(t.cpl), P<int>(t.cnt),
+      P<int>(t.nb), ox, oy, oz, om, oa, ctx->center[0], ctx->center[1], ctx->center[2], ctx->dlen,
+      P<double4>(t.xm), P<double4>(t.cl), P<int4>(t.lk), P<double>(t.aux), slvl);
+  else
+    k_emit_elements<false><<<cdiv(n, wg), wg, 0, st>>>(
+      n, ts, P<unsigned long long>(t.skey), nullptr, P<int>(t.cpl), P<int>(t.cnt), P<int>(t.nb), ox, oy,
+      oz, om, oa, ctx->center[0], ctx->center[1], ctx->center[2], ctx->dlen, P<double4>(t.xm),
+      P<double4>(t.cl), P<int4>(t.lk), P<double>(t.aux), slvl);
   HIPCHK(hipGetLastError());
   if(grav)
     return moment_pass<true, true>(ctx, t, ctx->adaptive_gravsoft);
@@ -1386,6 +1710,9 @@ int ghip_tree_build_impl(ghip_ctx *ctx)
     {
       GCHK(sort_by_key(ctx, G, nsrc, x, y, z, wide, n, given_keys, false,
                        nimp == 0 ? P<int>(ctx->f[GHIP_F_TYPE]) : nullptr, tmp_soft));
+      G.rnd = ctx->rnd_n > 0 && !dd;   // (ghip_dd_begin refuses a bound table)
+      if(G.rnd)
+        GCHK(rnd_order(ctx, G, nsrc, x, y, z));
       GCHK(count_nodes(ctx, G, nsrc, false, async ? G.cap_nodes : 0x7fffffff, wide, src_lvl));
       HIPCHK(hipEventRecord(ctx->ev_sizes, st));
       if(async)
@@ -1564,6 +1891,7 @@ int ghip_dd_build_gas_tree(ghip_ctx *ctx)
   for(;;)
     {
       GCHK(sort_by_key(ctx, t, nsg, gx, gy, gz, wide, -1, nullptr, true));
+      t.rnd = false;
       GCHK(count_nodes(ctx, t, nsg, true, 0x7fffffff, wide));
       HIPCHK(ghip_stream_sync(ctx, st));
       if(wide || t.hsz->bad != 2)

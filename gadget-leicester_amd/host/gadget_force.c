@@ -119,6 +119,8 @@ static int KickN = 0, KickCap = 0;
 static void *PinP, *PinS;
 static size_t PinPBytes, PinSBytes;
 static int ViscOnDevice = 0;     /* the context holds a setting of gadget_force_bind_viscosity */
+static const double *RndTablePtr = NULL;   /* gadget_force_bind_rndtable */
+static int RndTableN = 0, RndOnDevice = 0;
 static int DensPending = 0;      /* overlap_sph: density()'s results are still on the device */
 static int *ActiveBuf = NULL;
 static int ActiveCap = 0;
@@ -282,6 +284,7 @@ void gadget_force_finalize(void)
   KeptTree = 0;
   Ctx = NULL;
   ViscOnDevice = 0;
+  RndOnDevice = 0;
   free(ActiveBuf);
   ActiveBuf = NULL;
   ActiveCap = 0;
@@ -775,6 +778,43 @@ static int export_tree_to_host(void)
   return 0;
 }
 
+/* -DNOTREERND absent (the shipped flags): the host's RndTable, refilled by run.c:620 every step, chooses
+ * the subnodes of (near-)coincident particles (forcetree.c:219-232).  Bound once, uploaded with P[].ID at
+ * every force_treebuild().  RndTable == NULL unbinds.  Single rank: ghip_dd_begin refuses a bound table. */
+
+void gadget_force_bind_rndtable(const double *RndTable, int n)
+{
+  RndTablePtr = (RndTable && n > 0) ? RndTable : NULL;
+  RndTableN = RndTablePtr ? n : 0;
+}
+
+static int upload_rndtable(void)
+{
+  if(!RndTablePtr)
+    {
+      if(RndOnDevice && chk(ghip_set_rnd_table(Ctx, NULL, 0), "ghip_set_rnd_table"))
+        return -1;
+      RndOnDevice = 0;
+      return 0;
+    }
+  if(NumPart > 0)
+    {
+      int *ids = (int *) malloc((size_t) NumPart * sizeof(int));
+      if(!ids)
+        return -1;
+      for(int i = 0; i < NumPart; i++)
+        ids[i] = BhLay.p_id >= 0 ? (int) *(unsigned int *) (prec(i) + BhLay.p_id) : i;
+      int rc = chk(ghip_set_field(Ctx, GHIP_F_ID, ids), "ghip_set_field");
+      free(ids);
+      if(rc)
+        return -1;
+    }
+  if(chk(ghip_set_rnd_table(Ctx, RndTablePtr, RndTableN), "ghip_set_rnd_table"))
+    return -1;
+  RndOnDevice = 1;
+  return 0;
+}
+
 /* forcetree.c:67-103: (re)build the tree over the current particles */
 int force_treebuild(int npart, void *mp)
 {
@@ -787,6 +827,8 @@ int force_treebuild(int npart, void *mp)
       return -1;
   if(DomainLen <= 0)
     domain_findExtent();
+  if(upload_rndtable())
+    return -1;
   if(chk(ghip_tree_build(Ctx, DomainCorner, DomainCenter, DomainLen, All.ForceSoftening),
          "ghip_tree_build"))
     return -1;

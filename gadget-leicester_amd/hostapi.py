@@ -177,7 +177,7 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
            "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration",
            "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system",
-           "gadget_force_bind_viscosity"]
+           "gadget_force_bind_viscosity", "gadget_force_bind_rndtable"]
 
 _LIB = None
 
@@ -228,6 +228,8 @@ def lib():
         L.gadget_force_bind_dust.restype = None
         L.gadget_force_bind_viscosity.argtypes = [C.c_void_p, C.c_void_p]
         L.gadget_force_bind_viscosity.restype = None
+        L.gadget_force_bind_rndtable.argtypes = [C.c_void_p, C.c_int]
+        L.gadget_force_bind_rndtable.restype = None
         L.dust_density.restype = None
         L.dust_drag.restype = None
         L.gadget_force_bind_integration.argtypes = [C.c_void_p] * 6
@@ -308,6 +310,17 @@ class Host:
         self.L.gadget_force_bind_viscosity(None if host_all is None else C.c_void_p(host_all.ctypes.data),
                                            C.cast(C.byref(lay), C.c_void_p))
 
+    def bind_rndtable(self, table):
+        """gadget_force_bind_rndtable: the host's RndTable (a float64 array the host keeps and refills; every
+        force_treebuild() uploads it); None unbinds"""
+        if table is None:
+            self.L.gadget_force_bind_rndtable(None, 0)
+            self._rnd = None
+            return
+        assert table.dtype == np.float64 and table.flags["C_CONTIGUOUS"]
+        self._rnd = table                       # keep alive
+        self.L.gadget_force_bind_rndtable(C.c_void_p(table.ctypes.data), len(table))
+
     def bind_integration(self, host_all, lay, bin_sfr=None, bin_bh_mass=None, bin_bh_dynmass=None,
                          bin_bh_mdot=None):
         """gadget_force_bind_integration: `host_all` as for bind_dust, `lay` an IntegrationLayout, the
@@ -382,6 +395,7 @@ class Host:
         self.L.gadget_force_bind_integration(None, None, None, None, None, None)
         self.L.gadget_force_bind_potential(None, None)
         self.L.gadget_force_bind_viscosity(None, None)
+        self.L.gadget_force_bind_rndtable(None, 0)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)
         self._seti("ThisTask", 0)
         self._seti("NTask", 1)

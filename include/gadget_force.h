@@ -478,6 +478,13 @@ struct gadget_force_visc_layout
   int time_dependent, conventional, no_limiter, no_shear_limiter;
 };
 void gadget_force_bind_viscosity(void *host_All, const struct gadget_force_visc_layout *lay);
+/* The reference built without -DNOTREERND (the shipped flags): RndTable[n] (system.c:161-172; RNDTABLE = 262144),
+ * which run.c:620 refills every step, chooses the subnodes of particles in cells smaller than 1e-3 of their
+ * softening (forcetree.c:219-232).  While a table is bound every force_treebuild() uploads it together with
+ * P[].ID (p_id of the bh table of gadget_force_bind_records; without one the ID is the index) and the device
+ * builds the reference's tree for coincident particles too (ghip_set_rnd_table, include/ghip.h).
+ * RndTable == NULL unbinds: identical keys become one level-21 leaf again.  Single rank only. */
+void gadget_force_bind_rndtable(const double *RndTable, int n);
 void dust_density(void);
 void dust_drag(void);
 

@@ -361,7 +361,7 @@ int ghip_dd_find_split(int ncpu, int ndomain, const double *domainWork, int *sta
 /* search radii are padded by this factor when ghosts are first selected in a density() (default
  * 1.3).  Only a performance knob: when the h iteration takes a smoothing length beyond the padded
  * radius on any shard, all shards restore their starting Hsml, select ghosts again with
- * 1.26 x the worst growth seen and repeat the iteration (a collective decision; DESIGN.md 4.9). */
+ * 1.26 x the worst growth seen and repeat the iteration (a collective decision; DESIGN.md 4.1.1). */
 int ghip_dd_set_ghost_margin(ghip_ctx *ctx, double margin);
 /* RCCL: rank 0 creates the id (128 bytes) and the host broadcasts it (MPI_Bcast in the reference's
  * world); every rank then connects.  The library binds the librccl that sits next to the HIP
@@ -1020,6 +1020,24 @@ int ghip_visc_get(ghip_ctx *ctx, double *alpha, double *dtalpha);     /* either 
  * sqrt((GAMMA - 1) / 2 * GAMMA): begrun.c:132-133 as written, GAMMA = 7 / 5.  Host arithmetic. */
 void ghip_visc_derive(double ViscSource0, double DecayLength, double *ViscSource, double *DecayTime);
 size_t ghip_visc_params_size(void);   /* sizeof(ghip_visc_params) of the library, for bindings to check */
+
+/* ---- Randomised subnodes for (near-)coincident particles: the reference without -DNOTREERND
+ * (forcetree.c:219-232, 303-316; system.c:161-172).  In a node whose side is below
+ * 1.0e-3 * ForceSoftening[Type] a particle's subnode is not taken from its position but is
+ *   min(7, (int) (8.0 * table[((ID + d) % (ntable + (d & 3))) % ntable]))
+ * with d the depth of the node (the root: 0) and ID + d in unsigned 32-bit arithmetic; below level 21 a
+ * position is compared with the node's centre (forcetree.c:208-217).  The table is copied to the device by
+ * this call (the host refills its RndTable every step: call it before every ghip_tree_build); IDs are the
+ * GHIP_F_ID field; the thresholds are the ForceSoftening of ghip_tree_build, also with
+ * ghip_set_adaptive_gravsoft.  Both trees follow the rule.  A particle's path through the tree then has
+ * GHIP_TREE_MAXLEVEL digits: node levels 0 .. GHIP_TREE_MAXLEVEL - 1.  Two sources that share every one of
+ * them make the build fail with GHIP_EDEVICE ("tree error"); the context stays usable.
+ * table == NULL (or ntable == 0) unbinds: identical Morton keys become one level-21 leaf, and every launch and
+ * result is that of a library without this call.  Entries must lie in [0, 1).
+ * Not on domain-decomposed shards: ghip_dd_begin is GHIP_EINVAL while a table is bound. ---- */
+#define GHIP_TREE_MAXLEVEL 42
+int ghip_set_rnd_table(ghip_ctx *ctx, const double *table, int ntable);
+int ghip_tree_max_level(void);   /* GHIP_TREE_MAXLEVEL of the library */
 
 /* one fixed-h evaluation for a single target (density_evaluate mode 0, density.c:711):
  * out7 = rho, numngb, dhsmlrho, divv, rot[3] (raw sums, before finalisation) */
