@@ -30,6 +30,8 @@
 //             updated records follow once between density() and hydro_force().
 // Ownership is by Peano-Hilbert key range [splits[r], splits[r+1]): a cell lies wholly inside a
 // shard's range or it is "shared" and always descended.
+#include <cstdarg>
+
 #include <hipcub/hipcub.hpp>
 
 #include "ghip_ngb.h"   // BoxK
@@ -39,19 +41,7 @@
 int ghip_dd_build_gas_tree(ghip_ctx *ctx);
 int ghip_dd_refresh_ghosts(ghip_ctx *ctx);
 void ghip_dd_comm_release(ghip_ctx *ctx);
-// sink.hip
-int ghip_dd_sink_begin(ghip_ctx *ctx, int op);
-int ghip_dd_sink_step(ghip_ctx *ctx);
-int ghip_dd_pm_begin(ghip_ctx *ctx);   // ghip_pm.hip
-int ghip_dd_pm_step(ghip_ctx *ctx);
-int ghip_dd_dust_begin(ghip_ctx *ctx, int op);   // ghip_dust.hip
-int ghip_dd_dust_step(ghip_ctx *ctx);
 extern "C" int ghip_dd_exchange(ghip_ctx *ctx);
-
-#define DD_OP_MIGRATE 1
-#define DD_OP_GRAVITY 2
-#define DD_OP_DENSITY 3
-#define DD_OP_HYDRO 4
 
 // ---------------------------------------------------------------------------------------------
 // set-up
@@ -71,7 +61,7 @@ extern "C" int ghip_dd_init(ghip_ctx *ctx, int rank, int nranks)
     D.splits[r] = (r == nranks) ? (1ULL << 63) : ((1ULL << 63) / (unsigned long long) nranks) * r;
   D.gt_nimp = 0;
   D.nghost = 0;
-  D.op = 0;
+  D.op = 0;   // (a new set-up abandons whatever operation was in progress, with its pending exchange)
   D.x.kind = 0;
   ctx->gt.built = false;
   ctx->st.built = false;
@@ -451,12 +441,9 @@ static int build_groups(ghip_ctx *ctx, bool gas, const int *tgt, int nt, const d
   // the status record behind the table: has anything gone wrong on this shard so far?  (The error,
   // if any, is kept: after the all-gather every shard fails, this one with its own message.)
   HIPCHK(ghip_stream_sync(ctx, st));
-  D.local_err = ghip_check_device_errors(ctx);
-  if(D.local_err != GHIP_OK)
-    D.local_msg = ctx->err;
   DDGroup status;
   memset(&status, 0, sizeof(status));
-  status.cx = D.local_err != GHIP_OK ? 1.0 : 0.0;
+  status.cx = ghip_dd_hold(ctx, ghip_check_device_errors(ctx)) ? 1.0 : 0.0;
   HIPCHK(hipMemcpyAsync(tab + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, st));
   HIPCHK(ghip_stream_sync(ctx, st));   // (`status` lives on this frame)
   return GHIP_OK;
@@ -480,12 +467,63 @@ static int check_group_status(ghip_ctx *ctx, const char *what)
   double flags[GHIP_MAXRANKS];
   HIPCHK(hipMemcpyAsync(flags, D.status_all.p, (size_t) P_ * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
-  if(D.local_err != GHIP_OK)
-    return ghip_fail(ctx, D.local_err, "%s", D.local_msg.c_str());
+  int failed = -1;
   for(int r = 0; r < P_; r++)
-    if(flags[r] != 0)
-      return ghip_fail(ctx, GHIP_EDEVICE, "%s: shard %d reported an error while it prepared its target "
-                       "groups (its own message says what); every shard stops here", what, r);
+    if(flags[r] != 0 && failed < 0)
+      failed = r;
+  return ghip_dd_raise(ctx, failed, "%s: shard %d reported an error while it prepared its target "
+                       "groups (its own message says what); every shard stops here", what, failed);
+}
+
+// ---- all shards stop together (ghip_internal.h): the held failure, and the status round it can travel in ----
+bool ghip_dd_hold(ghip_ctx *ctx, int rc)
+{
+  ctx->dd.held.rc = rc;
+  if(rc != GHIP_OK)
+    ctx->dd.held.msg = ctx->err;
+  return rc != GHIP_OK;
+}
+
+int ghip_dd_raise(ghip_ctx *ctx, int failed_rank, const char *fmt, ...)
+{
+  if(failed_rank < 0)
+    return GHIP_OK;
+  if(ctx->dd.held.rc != GHIP_OK)
+    return ghip_fail(ctx, ctx->dd.held.rc, "%s", ctx->dd.held.msg.c_str());
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return ghip_fail(ctx, GHIP_EDEVICE, "%s", buf);
+}
+
+int dd_post_status(ghip_ctx *ctx, double value, bool failed)
+{
+  DDState &D = ctx->dd;
+  const double mine[2] = {value, failed ? 1.0 : 0.0};
+  GCHK(ghip_ensure(ctx, D.status_own, 16));
+  HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 16, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));   // (`mine` lives on this frame)
+  ghip_dd_set_allgather(D, D.status_own.p, 16, &D.status_all);
+  return GHIP_OK;
+}
+
+int dd_read_status(ghip_ctx *ctx, double *worst, int *first_failed)
+{
+  DDState &D = ctx->dd;
+  double all[2 * GHIP_MAXRANKS];
+  HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) D.nranks * 16, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  *worst = 0;
+  *first_failed = -1;
+  for(int r = 0; r < D.nranks; r++)
+    {
+      if(all[2 * r] > *worst)
+        *worst = all[2 * r];
+      if(all[2 * r + 1] != 0 && *first_failed < 0)
+        *first_failed = r;
+    }
   return GHIP_OK;
 }
 
@@ -1263,30 +1301,43 @@ int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what
   return GHIP_OK;
 }
 
+// GHIP_DD_GRAVITY:
+//   GROUPS  the shard's own tree and the groups of its active targets          -> all-gather of the groups
+//   LET     every shard fails if one did; selection of the locally essential trees, packed
+//                                                                               -> all-to-all-v of LetRec
+//   WALK    one tree over the local particles and everything that was imported, then the walks
+static int gravity_begin(ghip_ctx *ctx, int, const void *params, int walk)
+{
+  DDState &D = ctx->dd;
+  if(walk < 0 || walk > GHIP_WALK_NEWTON_EWALD)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: unknown walk %d", walk);
+  D.gp = *reinterpret_cast<const ghip_grav_params *>(params);
+  D.walk = walk;
+  return GHIP_OK;
+}
+
 static int gravity_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
-  if(D.phase == 0)
+  enum { GROUPS, LET, WALK, DONE };
+  if(D.phase == GROUPS)
     {
-      // the shard's own tree and its target groups
       GCHK(ghip_dd_own_tree(ctx));
       GCHK(ghip_dd_post_groups(ctx, false, true));
-      D.phase = 1;
+      D.phase = LET;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == LET)
     {
       GCHK(ghip_dd_post_let(ctx, D.gp, "gravity"));
-      D.phase = 2;
+      D.phase = WALK;
       return 1;
     }
-  if(D.phase == 2)
+  if(D.phase == WALK)
     {
-      // one tree over the local particles and everything that was imported, then the walks
       D.gt_nimp = D.x.rtotal;
       GCHK(ghip_tree_build_impl(ctx));
-      D.phase = 3;
-      D.op = 0;
+      D.phase = DONE;
       return ghip_gravity_impl(ctx, &D.gp, D.walk);
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: gravity has no phase %d", D.phase);
@@ -1310,13 +1361,32 @@ __global__ void k_mask_local_gas(int n, int ngas, const int *__restrict__ perm,
     mask[s] = perm[s] < ngas ? 1ULL : 0ULL;
 }
 
+// GHIP_DD_DENSITY:
+//   GROUPS   groups of the gas targets with their padded search radii            -> all-gather of the groups
+//   GHOSTS   every shard fails if one did; which local gas particles are ghosts where, packed
+//                                                                                 -> all-to-all-v of GhostRec
+//   ITERATE  gas tree over the local gas and the ghosts, the h iteration; what it met and the largest growth
+//            of a search radius                                                   -> all-gather of the status
+//   DECIDE   a radius outgrew the padding: back to GROUPS with a larger one; every shard fails if one did;
+//            the ghosts' records as they are after density()                      -> all-to-all-v of GhostRec
+//   REFRESH  the ghosts' records unpacked
+static int density_begin(ghip_ctx *ctx, int, const void *params, int)
+{
+  DDState &D = ctx->dd;
+  D.dp = *reinterpret_cast<const ghip_dens_params *>(params);
+  D.gh_margin_cur = D.gh_margin;   // (grows within the call when a smoothing length outgrows it)
+  D.gh_retries = 0;
+  return GHIP_OK;
+}
+
 static int density_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
   const int P_ = D.nranks;
   const int ng = ctx->ngas;
-  if(D.phase == 0)
+  enum { GROUPS, GHOSTS, ITERATE, DECIDE, REFRESH, DONE };
+  if(D.phase == GROUPS)
     {
       // groups of the gas targets (bounding box, padded search radius) from the curve order of the
       // gravity tree: positions in tree order, smoothing lengths through perm
@@ -1350,10 +1420,10 @@ static int density_step(ghip_ctx *ctx)
         }
       GCHK(build_groups(ctx, true, P<int>(D.gas_tgt), ngt));
       set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
-      D.phase = 1;
+      D.phase = GHOSTS;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == GHOSTS)
     {
       GCHK(check_group_status(ctx, "density"));
       // which local gas particles are ghosts where
@@ -1390,17 +1460,15 @@ static int density_step(ghip_ctx *ctx)
       D.gh_sent = total;
       GCHK(pack_ghosts(ctx, total));
       set_alltoallv(D, D.gh_send.p, sizeof(GhostRec), D.gh_scount, D.gh_soff, &D.gh_recv);
-      D.phase = 2;
+      D.phase = ITERATE;
       return 1;
     }
-  if(D.phase == 2)
+  if(D.phase == ITERATE)
     {
       // gas tree over the local gas and the ghosts, the h iteration for the local targets
       D.nghost = D.x.rtotal;
       GCHK(ghip_dd_build_gas_tree(ctx));
-      D.dens_rc = ghip_density_impl(ctx, &D.dp);
-      if(D.dens_rc != GHIP_OK)
-        D.dens_msg = ctx->err;
+      const bool failed = ghip_dd_hold(ctx, ghip_density_impl(ctx, &D.dp));
       // Every search radius used must have stayed inside the padded radius the ghosts were selected
       // with.  The reference re-exports a target at every h iteration, whatever its radius has become
       // (density.c:160-677); here the ghosts are fixed for the call, so a radius that outgrows the
@@ -1408,40 +1476,27 @@ static int density_step(ghip_ctx *ctx)
       // ghosts again with a larger padding and repeat the call from the smoothing lengths it started
       // with.  The decision is taken by ALL shards on the all-gathered growth factors, so that they
       // repeat (or fail) together; a rank-local failure of the iteration travels the same way.
-      double mine[2] = {0.0, 0.0};
-      if(D.dens_rc == GHIP_OK && ctx->nt_gas > 0)
+      double growth = 0.0;
+      if(!failed && ctx->nt_gas > 0)
         {
           unsigned long long *dr = &ghip_words(ctx)->ghost_growth;
           HIPCHK(hipMemsetAsync(dr, 0, 8, st));
           k_ghost_growth<<<cdiv(ctx->nt_gas, 256), 256, 0, st>>>(
             ctx->nt_gas, P<int>(ctx->tg_gas), P<int>(ctx->st.perm), P<double>(ctx->dhcur),
             P<double>(ctx->dright), P<double>(D.h0), dr);
-          HIPCHK(hipMemcpyAsync(&mine[0], dr, 8, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(&growth, dr, 8, hipMemcpyDeviceToHost, st));
           HIPCHK(ghip_stream_sync(ctx, st));
         }
-      mine[1] = D.dens_rc != GHIP_OK ? 1.0 : 0.0;
-      D.gh_growth = mine[0];
-      GCHK(ghip_ensure(ctx, D.status_own, 16));
-      HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 16, hipMemcpyHostToDevice, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      set_allgather(D, D.status_own.p, 16, &D.status_all);
-      D.phase = 25;
+      D.gh_growth = growth;
+      GCHK(dd_post_status(ctx, growth, failed));
+      D.phase = DECIDE;
       return 1;
     }
-  if(D.phase == 25)
+  if(D.phase == DECIDE)
     {
-      double all[2 * GHIP_MAXRANKS];
-      HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) P_ * 16, hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
       double worst = 0;
       int failed = -1;
-      for(int r = 0; r < P_; r++)
-        {
-          if(all[2 * r] > worst)
-            worst = all[2 * r];
-          if(all[2 * r + 1] != 0 && failed < 0)
-            failed = r;
-        }
+      GCHK(dd_read_status(ctx, &worst, &failed));
       if(worst > D.gh_margin_cur && P_ > 1)
         {
           // (a failed iteration of the incomplete attempt -- non-convergence next to missing ghosts --
@@ -1453,29 +1508,23 @@ static int density_step(ghip_ctx *ctx)
           D.gh_margin_cur = 1.26 * worst;   // one more pass of the reference's growth factor as head-room
           if(ng > 0)
             HIPCHK(hipMemcpyAsync(ctx->f[GHIP_F_HSML].p, D.h0.p, (size_t) ng * 8, hipMemcpyDeviceToDevice, st));
-          D.phase = 0;
+          D.phase = GROUPS;
           return density_step(ctx);   // groups with the larger padding -> all-gather -> ...
         }
-      if(failed >= 0)
-        {
-          if(D.dens_rc != GHIP_OK)
-            return ghip_fail(ctx, D.dens_rc, "%s", D.dens_msg.c_str());
-          return ghip_fail(ctx, GHIP_EDEVICE, "density: the h iteration failed on shard %d (its own message "
-                           "says why); every shard stops here", failed);
-        }
+      GCHK(ghip_dd_raise(ctx, failed, "density: the h iteration failed on shard %d (its own message "
+                         "says why); every shard stops here", failed));
       // the ghosts' records as they are after density(): hydro_force needs h, rho, P, f, div, curl
       GCHK(pack_ghosts(ctx, D.gh_sent));
       set_alltoallv(D, D.gh_send.p, sizeof(GhostRec), D.gh_scount, D.gh_soff, &D.gh_recv);
-      D.phase = 3;
+      D.phase = REFRESH;
       return 1;
     }
-  if(D.phase == 3)
+  if(D.phase == REFRESH)
     {
       if(D.x.rtotal != D.nghost)
         return ghip_fail(ctx, GHIP_ECOMM, "ghost refresh: %d records, expected %d", D.x.rtotal, D.nghost);
       GCHK(ghip_dd_refresh_ghosts(ctx));
-      D.phase = 4;
-      D.op = 0;
+      D.phase = DONE;
       return GHIP_OK;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: density has no phase %d", D.phase);
@@ -1682,6 +1731,25 @@ static int scan_u64(ghip_ctx *ctx, const unsigned long long *in, unsigned long l
   return GHIP_OK;
 }
 
+// GHIP_DD_MIGRATE:
+//   SEND   the owner of every local particle's key; those of other shards packed   -> all-to-all-v of MigRec
+//   MERGE  kept and received particles into the new layout (gas first), the resident arrays swapped
+static int migrate_begin(ghip_ctx *ctx, int, const void *, int)
+{
+  static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
+  int slots = 0;
+  for(int f = 0; f < GHIP_F_COUNT; f++)
+    {
+      int gas, ncomp, isint;
+      ghip_field_info(f, &gas, &ncomp, &isint);
+      slots += ncomp;
+    }
+  slots += 3;   // DragHeating, alpha, Dtalpha, when the shard holds them
+  if(slots > MIG_SLOTS - 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "migration record too small for %d field slots", slots);
+  return GHIP_OK;
+}
+
 static int migrate_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
@@ -1694,7 +1762,8 @@ static int migrate_step(ghip_ctx *ctx)
   DevBuf *const visc_bufs[2] = {&ctx->visc_alpha, &ctx->visc_dtalpha};
   DevBuf *const visc_shadow[2] = {&D.visc_shadow[0], &D.visc_shadow[1]};
   DevBuf *const *visc = (ctx->visc_alpha.p && ctx->visc_dtalpha.p && ctx->visc_ngas == ng) ? visc_bufs : nullptr;
-  if(D.phase == 0)
+  enum { SEND, MERGE, DONE };
+  if(D.phase == SEND)
     {
       GHIP_JOIN(ctx);
       int scount[GHIP_MAXRANKS], soff[GHIP_MAXRANKS], total = 0;
@@ -1727,15 +1796,14 @@ static int migrate_step(ghip_ctx *ctx)
         }
       D.mig_out = total;
       set_alltoallv(D, D.mig_send.p, sizeof(MigRec), scount, soff, &D.mig_recv);
-      D.phase = 1;
+      D.phase = MERGE;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == MERGE)
     {
       const int nrecv = D.x.rtotal;
       D.mig_in = nrecv;
-      D.phase = 2;
-      D.op = 0;
+      D.phase = DONE;
       ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
       if(nrecv == 0 && D.mig_out == 0)
         return GHIP_OK;   // nobody left, nobody came: the resident arrays stay as they are
@@ -1811,9 +1879,56 @@ static int migrate_step(ghip_ctx *ctx)
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: migration has no phase %d", D.phase);
 }
 
+// GHIP_DD_HYDRO: one step.  The ghosts' records are current since the end of GHIP_DD_DENSITY: hydro_force is local
+static int hydro_begin(ghip_ctx *ctx, int, const void *params, int)
+{
+  DDState &D = ctx->dd;
+  GCHK(ghip_visc_ready(ctx, "GHIP_DD_HYDRO"));
+  // the ghosts in place carry their owners' alpha as of the refresh that ended GHIP_DD_DENSITY; the local
+  // records take the alpha of this call (k_visc_refresh): a pair across shards must not mix the two
+  if(ctx->visc_on && ctx->visc.time_dependent && D.nranks > 1 && D.gh_alpha_epoch != ctx->visc_epoch)
+    return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_HYDRO: alpha changed (ghip_visc_set_alpha or a kick) since "
+                     "the GHIP_DD_DENSITY that packed the ghosts: run GHIP_DD_DENSITY again, on all ranks");
+  D.hp = *reinterpret_cast<const ghip_hydro_params *>(params);
+  return GHIP_OK;
+}
+
+static int hydro_step(ghip_ctx *ctx) { return ghip_hydro_impl(ctx, &ctx->dd.hp); }
+
+// The operations, indexed by GHIP_DD_*.  needs_grav_tree: the operation reads the tree of this step's
+// GHIP_DD_GRAVITY and refuses the one GHIP_DD_POTENTIAL leaves behind (selected for other targets).
+struct DDOp
+{
+  const char *name;
+  int (*begin)(ghip_ctx *ctx, int op, const void *params, int walk);
+  int (*step)(ghip_ctx *ctx);
+  bool needs_grav_tree, null_params;
+};
+static const DDOp dd_ops[] = {
+  {nullptr, nullptr, nullptr, false, false},
+  {"GHIP_DD_MIGRATE", migrate_begin, migrate_step, false, true},
+  {"GHIP_DD_GRAVITY", gravity_begin, gravity_step, false, false},
+  {"GHIP_DD_DENSITY", density_begin, density_step, true, false},
+  {"GHIP_DD_HYDRO", hydro_begin, hydro_step, false, false},
+  {"GHIP_DD_SINK_DENSITY", ghip_dd_sink_begin, ghip_dd_sink_step, true, false},
+  {"GHIP_DD_BH_EVALUATE", ghip_dd_sink_begin, ghip_dd_sink_step, true, false},
+  {"GHIP_DD_BH_SWALLOW", ghip_dd_sink_begin, ghip_dd_sink_step, true, false},
+  {"GHIP_DD_PM", ghip_dd_pm_begin, ghip_dd_pm_step, false, false},
+  {"GHIP_DD_DUST_DENSITY", ghip_dd_dust_begin, ghip_dd_dust_step, true, false},
+  {"GHIP_DD_DUST_DRAG", ghip_dd_dust_begin, ghip_dd_dust_step, true, false},
+  {"GHIP_DD_POTENTIAL", ghip_dd_pot_begin, ghip_dd_pot_step, false, false},
+  {"GHIP_DD_GLOBAL_QUANTITIES", ghip_dd_gq_begin, ghip_dd_gq_step, false, false},
+  {"GHIP_DD_DECOMPOSE", ghip_dd_decomp_begin, ghip_dd_decomp_step, false, false},
+  {"GHIP_DD_PM_REGION", ghip_dd_pmreg_begin, ghip_dd_pmreg_step, false, false},
+  {"GHIP_DD_PM_NONPERIODIC", ghip_dd_pmnp_begin, ghip_dd_pmnp_step, false, false},
+};
+static_assert(sizeof(dd_ops) / sizeof(dd_ops[0]) == DD_NOPS && DD_NOPS == GHIP_DD_PM_NONPERIODIC + 1,
+              "one entry of dd_ops per GHIP_DD_* operation");
+
 extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
-  if(!ctx || (!params && op != DD_OP_MIGRATE))
+  const bool known = op >= 1 && op < DD_NOPS;
+  if(!ctx || (!params && !(known && dd_ops[op].null_params)))
     return GHIP_EINVAL;
   DDState &D = ctx->dd;
   if(!D.on)
@@ -1825,93 +1940,14 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
                      "of a pruned node inside a randomised region does not follow from a key range): unbind it");
   if(D.x.kind != 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: an exchange is still pending");
+  if(!known)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: unknown operation %d", op);
   HIPCHK(hipSetDevice(ctx->device));
-  // the tree GHIP_DD_POTENTIAL leaves behind was selected for other targets than the step's gravity tree
-  if(D.gt_is_pot && ctx->gt.built &&
-     (op == DD_OP_DENSITY || (op >= GHIP_DD_SINK_DENSITY && op <= GHIP_DD_BH_SWALLOW) ||
-      op == GHIP_DD_DUST_DENSITY || op == GHIP_DD_DUST_DRAG))
+  if(dd_ops[op].needs_grav_tree && D.gt_is_pot && ctx->gt.built)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: operation %d needs GHIP_DD_GRAVITY of this step, and the "
                      "tree in place is the one GHIP_DD_POTENTIAL built: run GHIP_DD_GRAVITY first", op);
-  if(op == DD_OP_GRAVITY)
-    {
-      if(walk < 0 || walk > GHIP_WALK_NEWTON_EWALD)
-        return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: unknown walk %d", walk);
-      D.gp = *reinterpret_cast<const ghip_grav_params *>(params);
-      D.walk = walk;
-    }
-  else if(op == DD_OP_DENSITY)
-    {
-      D.dp = *reinterpret_cast<const ghip_dens_params *>(params);
-      D.gh_margin_cur = D.gh_margin;   // (grows within the call when a smoothing length outgrows it)
-      D.gh_retries = 0;
-      D.dens_rc = GHIP_OK;
-    }
-  else if(op == DD_OP_HYDRO)
-    {
-      GCHK(ghip_visc_ready(ctx, "GHIP_DD_HYDRO"));
-      // the ghosts in place carry their owners' alpha as of the refresh that ended GHIP_DD_DENSITY; the local
-      // records take the alpha of this call (k_visc_refresh): a pair across shards must not mix the two
-      if(ctx->visc_on && ctx->visc.time_dependent && D.nranks > 1 && D.gh_alpha_epoch != ctx->visc_epoch)
-        return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_HYDRO: alpha changed (ghip_visc_set_alpha or a kick) since "
-                         "the GHIP_DD_DENSITY that packed the ghosts: run GHIP_DD_DENSITY again, on all ranks");
-      D.hp = *reinterpret_cast<const ghip_hydro_params *>(params);
-    }
-  else if(op >= GHIP_DD_SINK_DENSITY && op <= GHIP_DD_BH_SWALLOW)
-    {
-      D.sink = *reinterpret_cast<const ghip_dd_sink_args *>(params);
-      GCHK(ghip_dd_sink_begin(ctx, op));
-    }
-  else if(op == GHIP_DD_PM)
-    {
-      D.pm = *reinterpret_cast<const ghip_pm_params *>(params);
-      GCHK(ghip_dd_pm_begin(ctx));
-    }
-  else if(op == GHIP_DD_DUST_DENSITY || op == GHIP_DD_DUST_DRAG)
-    {
-      D.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
-      GCHK(ghip_dd_dust_begin(ctx, op));
-    }
-  else if(op == GHIP_DD_POTENTIAL)
-    {
-      D.pot = *reinterpret_cast<const ghip_pot_params *>(params);
-      GCHK(ghip_dd_pot_begin(ctx));
-    }
-  else if(op == GHIP_DD_GLOBAL_QUANTITIES)
-    {
-      D.gq = *reinterpret_cast<const ghip_dd_global_args *>(params);
-      GCHK(ghip_dd_gq_begin(ctx));
-    }
-  else if(op == GHIP_DD_DECOMPOSE)
-    {
-      D.dcp = *reinterpret_cast<const ghip_dd_decomp_params *>(params);
-      GCHK(ghip_dd_decomp_begin(ctx));
-    }
-  else if(op == GHIP_DD_PM_REGION)
-    {
-      D.pmreg_grid = *reinterpret_cast<const int *>(params);
-      GCHK(ghip_dd_pmreg_begin(ctx));
-    }
-  else if(op == GHIP_DD_PM_NONPERIODIC)
-    {
-      D.pmnp = *reinterpret_cast<const ghip_pmnp_params *>(params);
-      GCHK(ghip_dd_pmnp_begin(ctx));
-    }
-  else if(op == DD_OP_MIGRATE)
-    {
-      static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
-      int slots = 0;
-      for(int f = 0; f < GHIP_F_COUNT; f++)
-        {
-          int gas, ncomp, isint;
-          ghip_field_info(f, &gas, &ncomp, &isint);
-          slots += ncomp;
-        }
-      slots += 3;   // DragHeating, alpha, Dtalpha, when the shard holds them
-      if(slots > MIG_SLOTS - 1)
-        return ghip_fail(ctx, GHIP_EINVAL, "migration record too small for %d field slots", slots);
-    }
-  else
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_begin: unknown operation %d", op);
+  D.held.rc = GHIP_OK;
+  GCHK(dd_ops[op].begin(ctx, op, params, walk));
   D.op = op;
   D.phase = 0;
   D.bytes_sent[op] = 0;
@@ -1919,7 +1955,8 @@ extern "C" int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk
 }
 
 // 1: an exchange is pending (ghip_dd_exchange / ghip_dd_exchange_local), 0: the operation is
-// complete, < 0: error
+// complete, < 0: error.  The operation is over when its step returns <= 0, complete or failed, and this is the
+// one place that says so: a further ghip_dd_step without a new ghip_dd_begin finds no operation in progress.
 extern "C" int ghip_dd_step(ghip_ctx *ctx)
 {
   if(!ctx)
@@ -1928,35 +1965,12 @@ extern "C" int ghip_dd_step(ghip_ctx *ctx)
   if(D.x.kind != 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: run the pending exchange first");
   HIPCHK(hipSetDevice(ctx->device));
-  if(D.op >= GHIP_DD_SINK_DENSITY && D.op <= GHIP_DD_BH_SWALLOW)
-    return ghip_dd_sink_step(ctx);
-  if(D.op == GHIP_DD_PM)
-    return ghip_dd_pm_step(ctx);
-  if(D.op == GHIP_DD_DUST_DENSITY || D.op == GHIP_DD_DUST_DRAG)
-    return ghip_dd_dust_step(ctx);
-  if(D.op == GHIP_DD_POTENTIAL)
-    return ghip_dd_pot_step(ctx);
-  if(D.op == GHIP_DD_GLOBAL_QUANTITIES)
-    return ghip_dd_gq_step(ctx);
-  if(D.op == GHIP_DD_DECOMPOSE)
-    return ghip_dd_decomp_step(ctx);
-  if(D.op == GHIP_DD_PM_REGION)
-    return ghip_dd_pmreg_step(ctx);
-  if(D.op == GHIP_DD_PM_NONPERIODIC)
-    return ghip_dd_pmnp_step(ctx);
-  if(D.op == DD_OP_MIGRATE)
-    return migrate_step(ctx);
-  if(D.op == DD_OP_GRAVITY)
-    return gravity_step(ctx);
-  if(D.op == DD_OP_DENSITY)
-    return density_step(ctx);
-  if(D.op == DD_OP_HYDRO)
-    {
-      // the ghosts' records are current since the end of density(): hydro_force is local
-      D.op = 0;
-      return ghip_hydro_impl(ctx, &D.hp);
-    }
-  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: no operation in progress");
+  if(D.op < 1 || D.op >= DD_NOPS)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: no operation in progress");
+  const int r = dd_ops[D.op].step(ctx);
+  if(r <= 0)
+    D.op = 0;
+  return r;
 }
 
 // the whole operation over RCCL (one process per GPU)
@@ -1985,8 +1999,8 @@ extern "C" int ghip_dd_get_info(const ghip_ctx *ctx, long long out[16])
   out[3] = D.let_sent;                 // elements this shard sent
   out[4] = D.nghost;                   // ghost gas particles imported
   out[5] = D.gh_sent;                  // ghosts sent
-  out[6] = D.bytes_sent[DD_OP_GRAVITY];
-  out[7] = D.bytes_sent[DD_OP_DENSITY];
+  out[6] = D.bytes_sent[GHIP_DD_GRAVITY];
+  out[7] = D.bytes_sent[GHIP_DD_DENSITY];
   out[8] = (long long) (D.gh_growth * 1.0e6);
   out[9] = ctx->gt.nelem;
   out[10] = ctx->st.nelem;
@@ -1994,13 +2008,13 @@ extern "C" int ghip_dd_get_info(const ghip_ctx *ctx, long long out[16])
   out[12] = ctx->ngas;
   out[13] = D.mig_out;
   out[14] = D.mig_in;
-  out[15] = D.bytes_sent[DD_OP_MIGRATE];
+  out[15] = D.bytes_sent[GHIP_DD_MIGRATE];
   return GHIP_OK;
 }
 
 extern "C" int ghip_dd_bytes_sent(const ghip_ctx *ctx, int op, long long *bytes)
 {
-  if(!ctx || !bytes || op < 1 || op >= 16)
+  if(!ctx || !bytes || op < 1 || op >= DD_NOPS)
     return GHIP_EINVAL;
   *bytes = ctx->dd.bytes_sent[op];
   return GHIP_OK;

@@ -263,9 +263,10 @@ unsigned long long ghip_extent_reduce(const unsigned long long *all, int nranks,
   return err;
 }
 
-int ghip_dd_decomp_begin(ghip_ctx *ctx)
+int ghip_dd_decomp_begin(ghip_ctx *ctx, int, const void *params, int)
 {
-  const DDState &D = ctx->dd;
+  DDState &D = ctx->dd;
+  D.dcp = *reinterpret_cast<const ghip_dd_decomp_params *>(params);
   const ghip_dd_decomp_params &p = D.dcp;
   if(p.level < 0 || p.level > 7)
     return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_DECOMPOSE: level %d is not 0 (automatic) or 1..7", p.level);
@@ -284,6 +285,11 @@ static inline bool dc_inside(double x, double corner, double fac)
   return c >= 0 && c < (double) (1 << GHIP_BITS);
 }
 
+// GHIP_DD_DECOMPOSE:
+//   EXTENT     this shard's extremes, count, time bins and error bits             -> all-gather of the blocks
+//   HISTOGRAM  every shard fails if one did; the cube and the level; this shard's work per cell
+//                                                                                 -> all-gather of the histograms
+//   CUT        the histograms added, the curve cut into ranges, the ranges (and the cube) put in force
 int ghip_dd_decomp_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
@@ -292,20 +298,18 @@ int ghip_dd_decomp_step(ghip_ctx *ctx)
   const int P_ = D.nranks, n = ctx->n;
   const double *x = P<double>(ctx->f[GHIP_F_POS]);
   const int *cost = P<int>(ctx->f[GHIP_F_GRAVCOST]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
-  if(D.phase == 0)
+  enum { EXTENT, HISTOGRAM, CUT };
+  if(D.phase == EXTENT)
     {
       // what goes wrong on this shard alone travels in the block too: its peers are inside the same collective
-      // and must not be left there (the status_own / status_all pattern of the density and the potential)
-      D.dc_rc = ghip_extent_pass(ctx, D.dc_own, p.use_work);
-      if(D.dc_rc != GHIP_OK && !D.dc_own.p)
-        return D.dc_rc;   // (without the block there is nothing to send)
-      if(D.dc_rc != GHIP_OK)
-        D.dc_msg = ctx->err;
+      // and must not be left there (the held failure of the density and the potential, ghip_dd_hold)
+      if(ghip_dd_hold(ctx, ghip_extent_pass(ctx, D.dc_own, p.use_work)) && !D.dc_own.p)
+        return D.held.rc;   // (without the block there is nothing to send)
       ghip_dd_set_allgather(D, D.dc_own.p, DC_WORDS * 8, &D.dc_all);
-      D.phase = 1;
+      D.phase = HISTOGRAM;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == HISTOGRAM)
     {
       std::vector<unsigned long long> all((size_t) P_ * DC_WORDS);
       HIPCHK(hipMemcpyAsync(all.data(), D.dc_all.p, all.size() * 8, hipMemcpyDeviceToHost, st));
@@ -315,14 +319,9 @@ int ghip_dd_decomp_step(ghip_ctx *ctx)
       unsigned long long ntot = 0;
       int bmin = 0x7fffffff, bmax = 0, bad = -1;
       const unsigned long long err = ghip_extent_reduce(all.data(), P_, xmin, xmax, &ntot, &bmin, &bmax, &bad);
-      D.op = 0;   // (left as it is only when the histogram is posted)
       if(err & DC_ERR_LOCAL)
-        {
-          if(D.dc_rc != GHIP_OK)
-            return ghip_fail(ctx, D.dc_rc, "%s", D.dc_msg.c_str());
-          return ghip_fail(ctx, GHIP_EDEVICE, "GHIP_DD_DECOMPOSE: the first pass failed on shard %d (its own message "
-                           "says why); every shard stops here, nothing was changed", bad);
-        }
+        return ghip_dd_raise(ctx, bad, "GHIP_DD_DECOMPOSE: the first pass failed on shard %d (its own message "
+                             "says why); every shard stops here, nothing was changed", bad);
       if(err & DC_ERR_POS)
         return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_DECOMPOSE: a position that is not finite (first on shard %d); "
                          "every shard stops here, nothing was changed", bad);
@@ -405,15 +404,13 @@ int ghip_dd_decomp_step(ghip_ctx *ctx)
               ncell, p.use_work, cost, tbin, bmax, shift, h);
           HIPCHK(hipGetLastError());
         }
-      D.op = GHIP_DD_DECOMPOSE;
       ghip_dd_set_allgather(D, D.dc_hist.p, (size_t) ncell * 8, &D.dc_hist_all);
-      D.phase = 2;
+      D.phase = CUT;
       return 1;
     }
-  if(D.phase == 2)
+  if(D.phase == CUT)
     {
       const int level = D.dc_level, ncell = 1 << (3 * level);
-      D.op = 0;
       k_decomp_sum<<<cdiv(ncell, 256), 256, 0, st>>>(ncell, P_, P<unsigned long long>(D.dc_hist_all),
                                                      P<unsigned long long>(D.dc_hist));
       HIPCHK(hipGetLastError());

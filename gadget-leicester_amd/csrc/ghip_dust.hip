@@ -715,9 +715,10 @@ int ghip_dd_dust_groups(ghip_ctx *ctx);   // ghip_dd.hip
 int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
                         int periodic, int *total);
 
-int ghip_dd_dust_begin(ghip_ctx *ctx, int op)
+int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
   const ghip_dd_dust_args &A = ctx->dd.dust;
   const bool drag = op == GHIP_DD_DUST_DRAG;
   const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
@@ -751,7 +752,8 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
   const double *pos = P<double>(ctx->f[GHIP_F_POS]), *hsml = P<double>(ctx->f[GHIP_F_HSML]),
                *mass = P<double>(ctx->f[GHIP_F_MASS]);
   const int recd = drag ? DUST_REC_DRAG : DUST_REC_DENS;
-  if(D.phase == 0)
+  enum { OWN, SELECT, IMPORTED, ADD };   // (the phases 0 .. 3 of the comment above; drag ends in IMPORTED)
+  if(D.phase == OWN)
     {
       if(drag)
         GCHK(dust_heat_buffer(ctx));   // (this shard holds DragHeating from now on)
@@ -781,10 +783,10 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           k_dust_slots<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(D.du_slot));
           HIPCHK(hipGetLastError());
         }
-      D.phase = 1;
+      D.phase = SELECT;
       return ghip_dd_dust_groups(ctx);
     }
-  if(D.phase == 1)
+  if(D.phase == SELECT)
     {
       int total = 0;
       GCHK(ghip_dd_dust_select(ctx, who, nd, dord, didx, A.p->BoxSize, A.p->periodic, &total));
@@ -802,10 +804,10 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
         }
       D.du_sent = total;
       ghip_dd_set_alltoallv(D, D.du_send.p, (size_t) recd * 8, D.du_scount, D.du_soff, &D.du_recv);
-      D.phase = 2;
+      D.phase = IMPORTED;
       return 1;
     }
-  if(D.phase == 2 && !drag)
+  if(D.phase == IMPORTED && !drag)
     {
       // the imported grains against this shard's Type-2 particles; the partial sums go home
       const int nimp = D.x.rtotal;
@@ -827,10 +829,10 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           so[r] = D.x.roff[r];
         }
       ghip_dd_set_alltoallv(D, D.du_part.p, 8, sc, so, &D.du_back);
-      D.phase = 3;
+      D.phase = ADD;
       return 1;
     }
-  if(D.phase == 3 && !drag)
+  if(D.phase == ADD && !drag)
     {
       for(int r = 0; r < D.nranks; r++)
         if(D.x.rcount[r] != (r == D.rank ? 0 : D.du_scount[r]))
@@ -854,10 +856,9 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           A.counts[1] = D.du_recvd;
           A.counts[3] = D.bytes_sent[D.op];
         }
-      D.op = 0;
       return 0;
     }
-  if(D.phase == 2 && drag)
+  if(D.phase == IMPORTED && drag)
     {
       // this shard's grains in list order, then the imported ones in receive order
       const int nimp = D.x.rtotal;
@@ -889,7 +890,6 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           A.counts[2] = npairs;
           A.counts[3] = D.bytes_sent[D.op];
         }
-      D.op = 0;
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the dust passes have no phase %d", D.phase);

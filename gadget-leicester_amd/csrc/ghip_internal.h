@@ -177,6 +177,8 @@ struct SinkIter
   std::vector<int> todo;
 };
 
+#define DD_NOPS (GHIP_DD_PM_NONPERIODIC + 1)   // operations of ghip_dd_begin, 0 = none (dd_ops[] in ghip_dd.hip)
+
 struct DDState
 {
   bool on = false;
@@ -219,11 +221,10 @@ struct DDState
   double gh_margin = 1.3;         // search radii are padded by this factor when ghosts are selected
   double gh_margin_cur = 1.3;     // ... in the density call in progress: grows when an h outgrew it (see density_step)
   int gh_retries = 0;             // re-selections of the density call in progress
-  DevBuf status_own, status_all;  // f64[2] per shard: {largest Hsml growth, error flag} of a density call
-  int local_err = 0;              // what this shard itself met while it prepared its group table
-  std::string local_msg;
-  int dens_rc = 0;                // ... and in the h iteration of the density call in progress
-  std::string dens_msg;
+  DevBuf status_own, status_all;  // f64[2] per shard: {a value, error flag} (dd_post_status / dd_read_status)
+  // what this shard itself met just before a collective decision, kept while its flag travels and raised as its
+  // own error when all shards stop (ghip_dd_hold / ghip_dd_raise); consumed in the next phase: one slot is enough
+  struct { int rc = 0; std::string msg; } held;
   DevBuf gsx, gsy, gsz, gsm, gsh; // gas sources = local gas + ghosts (tree build input)
   DevBuf h0;                      // f64[ngas]: smoothing lengths the ghost selection was made with
   // migration (domain_exchange): destination masks, send lists, records, shadow field arrays
@@ -256,22 +257,18 @@ struct DDState
   // move or a tree is built.
   bool geom_kept = false;
   // traffic of the last operation (bytes this rank sent over links, excluding its own block)
-  long long bytes_sent[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  long long bytes_sent[DD_NOPS] = {};
   ghip_pm_params pm;              // GHIP_DD_PM
   DevBuf pm_all;                  // the density meshes of all shards
   // GHIP_DD_PM_REGION / GHIP_DD_PM_NONPERIODIC (ghip_pm.hip): the extent blocks travel in dc_own / dc_all, the
   // compact octants with their status word in pm_all
   int pmreg_grid = 0;             // PMGRID of the GHIP_DD_PM_REGION in progress
   ghip_pmnp_params pmnp;          // arguments of the GHIP_DD_PM_NONPERIODIC in progress
-  int pmnp_rc = 0;                // what this shard's own deposit met (travels in the status word: all stop together)
-  std::string pmnp_msg;
   // GHIP_DD_POTENTIAL / GHIP_DD_GLOBAL_QUANTITIES (ghip_potential.hip)
   ghip_pot_params pot;            // arguments of the operation in progress
   DevBuf pot_tgt;                 // i32[n]: 0 .. n-1, the target list "all particles of the shard's own tree"
   bool gt_is_pot = false;         // the gravity tree in place is the merged tree GHIP_DD_POTENTIAL built
                                   // (selected for all particles as targets), not the step's GHIP_DD_GRAVITY's
-  int pot_rc = 0;                 // what this shard met in its walk (travels in status_own: all fail together)
-  std::string pot_msg;
   ghip_dd_global_args gq;         // GHIP_DD_GLOBAL_QUANTITIES: arguments, a copy of *gq.p
   ghip_global_params gq_p;
   DevBuf gq_send, gq_all;         // ghip_global_sums of this shard / of all shards (rank order)
@@ -280,8 +277,6 @@ struct DDState
   DevBuf dc_own, dc_all;          // u64[DC_WORDS]: extent images, count, time bins, error word / of all shards
   DevBuf dc_hist, dc_hist_all;    // u64[8^level]: this shard's histogram, later the sum / of all shards
   int dc_level = 0, dc_bmax = 0, dc_shift = 0;
-  int dc_rc = 0;                  // what this shard's own first pass met (travels in the block: all stop together)
-  std::string dc_msg;
   double dc_corner[3] = {0, 0, 0}, dc_center[3] = {0, 0, 0}, dc_len = 0;   // the cube the keys are formed in
 };
 
@@ -749,16 +744,32 @@ void ghip_dd_release(ghip_ctx *ctx);
 int ghip_dd_own_tree(ghip_ctx *ctx);
 int ghip_dd_post_groups(ghip_ctx *ctx, bool all, bool need_oldacc);
 int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what);
-int ghip_dd_pot_begin(ghip_ctx *ctx);   // potential.hip
-int ghip_dd_pot_step(ghip_ctx *ctx);
-int ghip_dd_gq_begin(ghip_ctx *ctx);
-int ghip_dd_gq_step(ghip_ctx *ctx);
-int ghip_dd_decomp_begin(ghip_ctx *ctx);   // decomp.hip
-int ghip_dd_decomp_step(ghip_ctx *ctx);
-int ghip_dd_pmreg_begin(ghip_ctx *ctx);    // pm.hip: GHIP_DD_PM_REGION
+// the operations of dd_ops[] (ghip_dd.hip; gravity, density, hydro and migration are static there): begin copies
+// its own params into DDState and makes its own checks, step returns what ghip_dd_step returns
+int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // sink.hip: the three sink ops
+int ghip_dd_sink_step(ghip_ctx *ctx);
+int ghip_dd_pm_begin(ghip_ctx *ctx, int op, const void *params, int walk);       // pm.hip: GHIP_DD_PM
+int ghip_dd_pm_step(ghip_ctx *ctx);
+int ghip_dd_pmreg_begin(ghip_ctx *ctx, int op, const void *params, int walk);    // ... GHIP_DD_PM_REGION
 int ghip_dd_pmreg_step(ghip_ctx *ctx);
-int ghip_dd_pmnp_begin(ghip_ctx *ctx);     // ... GHIP_DD_PM_NONPERIODIC
+int ghip_dd_pmnp_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // ... GHIP_DD_PM_NONPERIODIC
 int ghip_dd_pmnp_step(ghip_ctx *ctx);
+int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // dust.hip: the two dust ops
+int ghip_dd_dust_step(ghip_ctx *ctx);
+int ghip_dd_pot_begin(ghip_ctx *ctx, int op, const void *params, int walk);      // potential.hip
+int ghip_dd_pot_step(ghip_ctx *ctx);
+int ghip_dd_gq_begin(ghip_ctx *ctx, int op, const void *params, int walk);
+int ghip_dd_gq_step(ghip_ctx *ctx);
+int ghip_dd_decomp_begin(ghip_ctx *ctx, int op, const void *params, int walk);   // decomp.hip
+int ghip_dd_decomp_step(ghip_ctx *ctx);
+// all shards stop together: hold keeps rc (with ctx->err if it is a failure) and says whether it failed, the flag
+// travels with the next exchange; raise(r = first rank whose flag is set, < 0: none, GHIP_OK) then fails with this
+// shard's own code and message if it holds one, else with the formatted message and GHIP_EDEVICE
+bool ghip_dd_hold(ghip_ctx *ctx, int rc);
+int ghip_dd_raise(ghip_ctx *ctx, int failed_rank, const char *fmt, ...);
+// the status round: {value, failed} uploaded, its all-gather left pending; then the largest value, the first failed rank
+int dd_post_status(ghip_ctx *ctx, double value, bool failed);
+int dd_read_status(ghip_ctx *ctx, double *worst, int *first_failed);
 
 // ---------------------------------------------------------------------------------------------
 // walk segments: the element list of a tree is cut into `ns` contiguous segments and `nsub`

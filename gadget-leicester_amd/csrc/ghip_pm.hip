@@ -383,9 +383,10 @@ extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
 
 // GHIP_DD_PM (ghip_dd_begin / ghip_dd_step): phase 0 deposits and posts the all-gather of the meshes,
 // phase 1 adds them and solves
-int ghip_dd_pm_begin(ghip_ctx *ctx)
+int ghip_dd_pm_begin(ghip_ctx *ctx, int, const void *params, int)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.pm = *reinterpret_cast<const ghip_pm_params *>(params);
   return pm_check(ctx, &ctx->dd.pm);
 }
 
@@ -395,23 +396,23 @@ int ghip_dd_pm_step(ghip_ctx *ctx)
   const ghip_pm_params *p = &D.pm;
   hipStream_t st = ctx->stream;
   const size_t n3 = (size_t) p->pmgrid * p->pmgrid * p->pmgrid;
-  if(D.phase == 0)
+  enum { DEPOSIT, SOLVE };
+  if(D.phase == DEPOSIT)
     {
       GCHK(pm_prepare(ctx, p->pmgrid));
       HIPCHK(hipEventRecord(ctx->evp[14], st));
       GCHK(pm_deposit(ctx, p));
       ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
-      D.phase = 1;
+      D.phase = SOLVE;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == SOLVE)
     {
       k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, n3, D.nranks, P<double>(D.pm_all),
                                                                  P<double>(ctx->pm.rho));
       HIPCHK(hipGetLastError());
       GCHK(pm_solve_and_interpolate(ctx, p));
       HIPCHK(hipEventRecord(ctx->evp[15], st));
-      D.op = 0;
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the mesh force has no phase %d", D.phase);
@@ -741,9 +742,6 @@ static int pmnp_region_from_extremes(ghip_ctx *ctx, int pmgrid, unsigned long lo
                                      ghip_pm_region *out, const char *who)
 {
 #pragma clang fp contract(off)
-  if(err & EXTENT_ERR_LOCAL)
-    return ghip_fail(ctx, GHIP_EDEVICE, "%s: the pass over the positions failed on shard %d (its own message says "
-                     "why); nothing stored", who, bad);
   if(err & EXTENT_ERR_POS)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: a position that is not finite (first on shard %d); nothing stored", who,
                      bad);
@@ -1114,9 +1112,10 @@ int ghip_pmnp_potential_solve(ghip_ctx *ctx, int pmgrid, double G, int nranks, c
 
 // ---- GHIP_DD_PM_REGION: phase 0 reduces this shard's positions and posts the all-gather of the extent blocks,
 // phase 1 evaluates all blocks in rank order (the MPI_Allreduce of :118-119) and stores the region ----
-int ghip_dd_pmreg_begin(ghip_ctx *ctx)
+int ghip_dd_pmreg_begin(ghip_ctx *ctx, int, const void *params, int)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.pmreg_grid = *reinterpret_cast<const int *>(params);
   GCHK(pmnp_check_grid(ctx, ctx->dd.pmreg_grid, "GHIP_DD_PM_REGION"));
   if(ctx->n > 0 && !ctx->f[GHIP_F_POS].p)
     return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_PM_REGION: particle field %d not set", (int) GHIP_F_POS);
@@ -1127,30 +1126,28 @@ int ghip_dd_pmreg_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
-  if(D.phase == 0)
+  enum { EXTENT, REGION };
+  if(D.phase == EXTENT)
     {
-      // (a failure of this shard's own pass is marked in the block: its peers stop with it in phase 1)
-      D.pmnp_rc = ghip_extent_pass(ctx, D.dc_own, 0);
-      if(D.pmnp_rc != GHIP_OK && !D.dc_own.p)
-        return D.pmnp_rc;   // (without the block there is nothing to send)
-      if(D.pmnp_rc != GHIP_OK)
-        D.pmnp_msg = ctx->err;
+      // (a failure of this shard's own pass is marked in the block: its peers stop with it in REGION)
+      if(ghip_dd_hold(ctx, ghip_extent_pass(ctx, D.dc_own, 0)) && !D.dc_own.p)
+        return D.held.rc;   // (without the block there is nothing to send)
       ghip_dd_set_allgather(D, D.dc_own.p, EXTENT_WORDS * 8, &D.dc_all);
-      D.phase = 1;
+      D.phase = REGION;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == REGION)
     {
       std::vector<unsigned long long> all((size_t) D.nranks * EXTENT_WORDS);
       HIPCHK(hipMemcpyAsync(all.data(), D.dc_all.p, all.size() * 8, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
-      D.op = 0;
       double xmin[3], xmax[3];
       unsigned long long ntot;
       int bmin, bmax, bad;
       const unsigned long long err = ghip_extent_reduce(all.data(), D.nranks, xmin, xmax, &ntot, &bmin, &bmax, &bad);
-      if((err & EXTENT_ERR_LOCAL) && D.pmnp_rc != GHIP_OK)
-        return ghip_fail(ctx, D.pmnp_rc, "%s", D.pmnp_msg.c_str());
+      if(err & EXTENT_ERR_LOCAL)
+        return ghip_dd_raise(ctx, bad, "%s: the pass over the positions failed on shard %d (its own message says "
+                             "why); nothing stored", "GHIP_DD_PM_REGION", bad);
       const int rc = pmnp_region_from_extremes(ctx, D.pmreg_grid, err, bad, ntot, xmin, xmax, nullptr,
                                                "GHIP_DD_PM_REGION");
       return rc == GHIP_OK ? 0 : rc;
@@ -1161,9 +1158,10 @@ int ghip_dd_pmreg_step(ghip_ctx *ctx)
 // ---- GHIP_DD_PM_NONPERIODIC: phase 0 checks the range, deposits and posts the all-gather of the compact
 // octants with their status words; phase 1 reads every status (all shards stop together), adds the octants in
 // rank order, solves and reads out ----
-int ghip_dd_pmnp_begin(ghip_ctx *ctx)
+int ghip_dd_pmnp_begin(ghip_ctx *ctx, int, const void *params, int)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.pmnp = *reinterpret_cast<const ghip_pmnp_params *>(params);
   const char *who = "GHIP_DD_PM_NONPERIODIC";
   GCHK(pmnp_check_params(ctx, &ctx->dd.pmnp, who));
   GCHK(pmnp_need_region(ctx, ctx->dd.pmnp.pmgrid, who));
@@ -1180,34 +1178,30 @@ int ghip_dd_pmnp_step(ghip_ctx *ctx)
   hipStream_t st = ctx->stream;
   const int M = p->pmgrid;
   const size_t m3 = (size_t) M * M * M;
-  if(D.phase == 0)
+  enum { DEPOSIT, SOLVE };
+  if(D.phase == DEPOSIT)
     {
       GCHK(pmnp_prepare(ctx, M));
       HIPCHK(hipEventRecord(ctx->evp[14], st));
       int outside = 0;
-      D.pmnp_rc = pmnp_check_and_deposit(ctx, &outside);
-      if(D.pmnp_rc != GHIP_OK)
+      if(ghip_dd_hold(ctx, pmnp_check_and_deposit(ctx, &outside)))
         {
-          D.pmnp_msg = ctx->err;
           const double s = PMNP_ST_LOCAL;
           HIPCHK(hipMemcpy(P<double>(ctx->pm.open.oct) + m3, &s, sizeof(double), hipMemcpyHostToDevice));
         }
       ghip_dd_set_allgather(D, ctx->pm.open.oct.p, ghip_pmnp_block_bytes(M), &D.pm_all);
-      D.phase = 1;
+      D.phase = SOLVE;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == SOLVE)
     {
-      D.op = 0;
       int outside = 0, failed = -1;
       GCHK(pmnp_read_status(ctx, M, D.nranks, P<double>(D.pm_all), &outside, &failed));
       if(failed >= 0)
         {
           HIPCHK(hipEventRecord(ctx->evp[15], st));
-          if(D.pmnp_rc != GHIP_OK)
-            return ghip_fail(ctx, D.pmnp_rc, "%s", D.pmnp_msg.c_str());
-          return ghip_fail(ctx, GHIP_EDEVICE, "GHIP_DD_PM_NONPERIODIC: the deposit failed on shard %d (its own message "
-                           "says why); every shard stops here, nothing was written", failed);
+          return ghip_dd_raise(ctx, failed, "GHIP_DD_PM_NONPERIODIC: the deposit failed on shard %d (its own message "
+                               "says why); every shard stops here, nothing was written", failed);
         }
       if(outside)
         {

@@ -545,18 +545,19 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
 
 // ---------------------------------------------------------------------------------------------
 // GHIP_DD_POTENTIAL (ghip_dd_begin / ghip_dd_step): compute_potential() on a domain-decomposed shard.
-//   phase 0  the shard's own tree, target groups over ALL its particles (the locally essential tree of the
+//   GROUPS   the shard's own tree, target groups over ALL its particles (the locally essential tree of the
 //            step's GHIP_DD_GRAVITY was selected against the active targets only)  -> all-gather of the groups
-//   phase 1  selection of the locally essential trees under the opening rules of k_pot_walk, packed
+//   LET      selection of the locally essential trees under the opening rules of k_pot_walk, packed
 //                                                                                 -> all-to-all-v of LetRec
-//   phase 2  the merged tree, the walk for the shard's own particles, the finish; what the walk met
+//   WALK     the merged tree, the walk for the shard's own particles, the finish; what the walk met
 //                                                                                 -> all-gather of the status
-//   phase 3  every shard fails if one did; no mesh: the r^2 term, done.  Mesh: deposit -> all-gather of meshes
-//   phase 4  the meshes added in rank order, solved, read out at the own particles; the r^2 term
+//   DEPOSIT  every shard fails if one did; no mesh: the r^2 term, done.  Mesh: deposit -> all-gather of meshes
+//   SOLVE    the meshes added in rank order, solved, read out at the own particles; the r^2 term
 // ---------------------------------------------------------------------------------------------
-int ghip_dd_pot_begin(ghip_ctx *ctx)
+int ghip_dd_pot_begin(ghip_ctx *ctx, int, const void *params, int)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.pot = *reinterpret_cast<const ghip_pot_params *>(params);
   return pot_check(ctx, &ctx->dd.pot, "GHIP_DD_POTENTIAL");
 }
 
@@ -567,56 +568,44 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
   hipStream_t st = ctx->stream;
   const int n = ctx->n;
   const bool mesh = p->pm.pmgrid > 0;
-  if(D.phase == 0)
+  enum { GROUPS, LET, WALK, DEPOSIT, SOLVE };
+  if(D.phase == GROUPS)
     {
       ctx->pot_n = -1;
       GCHK(ghip_dd_own_tree(ctx));
       GCHK(ghip_dd_post_groups(ctx, true, p->grav.ErrTolTheta == 0));
-      D.phase = 1;
+      D.phase = LET;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == LET)
     {
       GCHK(ghip_dd_post_let(ctx, p->grav, "potential"));
-      D.phase = 2;
+      D.phase = WALK;
       return 1;
     }
-  if(D.phase == 2)
+  if(D.phase == WALK)
     {
       D.gt_nimp = D.x.rtotal;
       GCHK(ghip_tree_build_impl(ctx));
       D.gt_is_pot = true;
-      D.pot_rc = pot_ensure_result(ctx);
-      if(D.pot_rc == GHIP_OK && n > 0)
-        D.pot_rc = pot_walk_and_finish(ctx, p, true);
+      int rc = pot_ensure_result(ctx);
+      if(rc == GHIP_OK && n > 0)
+        rc = pot_walk_and_finish(ctx, p, true);
       // did a target have to open a pruned node?  Every shard learns it from every shard's status
       HIPCHK(ghip_stream_sync(ctx, st));
-      if(D.pot_rc == GHIP_OK)
-        D.pot_rc = ghip_check_device_errors(ctx);
-      if(D.pot_rc != GHIP_OK)
-        D.pot_msg = ctx->err;
-      const double mine[2] = {0.0, D.pot_rc != GHIP_OK ? 1.0 : 0.0};
-      GCHK(ghip_ensure(ctx, D.status_own, 16));
-      HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 16, hipMemcpyHostToDevice, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      ghip_dd_set_allgather(D, D.status_own.p, 16, &D.status_all);
-      D.phase = 3;
+      if(rc == GHIP_OK)
+        rc = ghip_check_device_errors(ctx);
+      GCHK(dd_post_status(ctx, 0.0, ghip_dd_hold(ctx, rc)));
+      D.phase = DEPOSIT;
       return 1;
     }
-  if(D.phase == 3)
+  if(D.phase == DEPOSIT)
     {
-      double all[2 * GHIP_MAXRANKS];
-      HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) D.nranks * 16, hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      for(int r = 0; r < D.nranks; r++)
-        if(all[2 * r + 1] != 0)
-          {
-            D.op = 0;
-            if(D.pot_rc != GHIP_OK)
-              return ghip_fail(ctx, D.pot_rc, "%s", D.pot_msg.c_str());
-            return ghip_fail(ctx, GHIP_EDEVICE, "potential: the walk failed on shard %d (its own message says "
-                             "why); every shard stops here", r);
-          }
+      double worst;
+      int failed;
+      GCHK(dd_read_status(ctx, &worst, &failed));
+      GCHK(ghip_dd_raise(ctx, failed, "potential: the walk failed on shard %d (its own message says "
+                         "why); every shard stops here", failed));
       if(mesh && !p->grav.periodic)
         {
           // (the compact octant and its status word: a particle outside the region on any shard ends the
@@ -624,7 +613,7 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
           int outside = 0;
           GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
           ghip_dd_set_allgather(D, ghip_pmnp_block(ctx), ghip_pmnp_block_bytes(p->pm.pmgrid), &D.pm_all);
-          D.phase = 4;
+          D.phase = SOLVE;
           return 1;
         }
       if(mesh)
@@ -632,31 +621,22 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
           GCHK(ghip_pm_potential_deposit(ctx, &p->pm));
           const size_t n3 = (size_t) p->pm.pmgrid * p->pm.pmgrid * p->pm.pmgrid;
           ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
-          D.phase = 4;
+          D.phase = SOLVE;
           return 1;
         }
       GCHK(pot_quadratic(ctx, p));
       ctx->pot_n = n;
-      D.op = 0;
       return 0;
     }
-  if(D.phase == 4)
+  if(D.phase == SOLVE)
     {
       if(!p->grav.periodic)
-        {
-          const int rc = ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, D.nranks, P<double>(D.pm_all),
-                                                   P<double>(ctx->pot));
-          if(rc != GHIP_OK)
-            {
-              D.op = 0;
-              return rc;
-            }
-        }
+        GCHK(ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, D.nranks, P<double>(D.pm_all),
+                                       P<double>(ctx->pot)));
       else
         GCHK(ghip_pm_potential_solve(ctx, &p->pm, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
       GCHK(pot_quadratic(ctx, p));
       ctx->pot_n = n;
-      D.op = 0;
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the potential has no phase %d", D.phase);
@@ -987,10 +967,11 @@ static int gq_local(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums
 #define GQ_SUM_DOUBLES (sizeof(ghip_global_sums) / sizeof(double))
 static_assert(sizeof(ghip_global_sums) % sizeof(double) == 0, "ghip_global_sums is an array of doubles");
 
-int ghip_dd_gq_begin(ghip_ctx *ctx)
+int ghip_dd_gq_begin(ghip_ctx *ctx, int, const void *params, int)
 {
   GHIP_JOIN(ctx);
   DDState &D = ctx->dd;
+  D.gq = *reinterpret_cast<const ghip_dd_global_args *>(params);
   if(!D.gq.p || !D.gq.out)
     return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_GLOBAL_QUANTITIES: params needs p and out");
   D.gq_p = *D.gq.p;
@@ -1001,7 +982,8 @@ int ghip_dd_gq_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
-  if(D.phase == 0)
+  enum { OWN_SUMS, ADD };
+  if(D.phase == OWN_SUMS)
     {
       ghip_global_sums mine;
       GCHK(gq_local(ctx, &D.gq_p, &mine));
@@ -1009,10 +991,10 @@ int ghip_dd_gq_step(ghip_ctx *ctx)
       HIPCHK(hipMemcpyAsync(D.gq_send.p, &mine, sizeof(mine), hipMemcpyHostToDevice, st));
       HIPCHK(ghip_stream_sync(ctx, st));   // (`mine` lives on this frame)
       ghip_dd_set_allgather(D, D.gq_send.p, sizeof(mine), &D.gq_all);
-      D.phase = 1;
+      D.phase = ADD;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == ADD)
     {
       std::vector<double> all((size_t) D.nranks * GQ_SUM_DOUBLES);
       HIPCHK(hipMemcpyAsync(all.data(), D.gq_all.p, all.size() * 8, hipMemcpyDeviceToHost, st));
@@ -1024,7 +1006,6 @@ int ghip_dd_gq_step(ghip_ctx *ctx)
         for(size_t q = 0; q < GQ_SUM_DOUBLES; q++)
           s[q] += all[(size_t) r * GQ_SUM_DOUBLES + q];
       memcpy(D.gq.out, s, sizeof(ghip_global_sums));
-      D.op = 0;
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the global quantities have no phase %d", D.phase);

@@ -732,10 +732,11 @@ extern "C" int ghip_cooling_and_starformation(ghip_ctx *ctx, double Timebase_int
 // all-gathered and added in rank order on every shard: the h iteration then takes the same decisions
 // everywhere without another exchange, and a victim, local to exactly one shard, sees every claim.
 // ---------------------------------------------------------------------------------------------
-int ghip_dd_sink_begin(ghip_ctx *ctx, int op)
+int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int)
 {
   GHIP_JOIN(ctx);
   DDState &D = ctx->dd;
+  D.sink = *reinterpret_cast<const ghip_dd_sink_args *>(params);
   const ghip_dd_sink_args &A = D.sink;
   if(A.nsink < 0 || (A.nsink > 0 && !A.sink_idx))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd sinks: bad arguments");
@@ -792,13 +793,20 @@ static int dd_sink_sum_parts(ghip_ctx *ctx, int k, std::vector<double> &parts, s
   return GHIP_OK;
 }
 
+// the three sink operations:
+//   POST     this shard's sinks                                                   -> all-to-all-v of SinkRec
+//   EVALUATE all sinks against this shard's particles.  BH_EVALUATE: done.  SINK_DENSITY: the first pass,
+//            BH_SWALLOW: the sweep                                                -> all-gather of the partial sums
+//   COLLECT  the partial sums added in rank order.  SINK_DENSITY: the next pass of the sinks still iterating
+//            (-> all-gather again, the phase stays) or the results; BH_SWALLOW: the results
 int ghip_dd_sink_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
   const ghip_dd_sink_args &A = D.sink;
   hipStream_t st = ctx->stream;
   const int op = D.op, nloc = A.nsink;
-  if(D.phase == 0)
+  enum { POST, EVALUATE, COLLECT };
+  if(D.phase == POST)
     {
       // this shard's sinks to every shard (itself included: the receive buffer is the rank-ordered
       // list of all sinks)
@@ -819,10 +827,10 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
           soff[r] = 0;
         }
       ghip_dd_set_alltoallv(D, D.sk_send.p, sizeof(SinkRec), scount, soff, &D.sk_all);
-      D.phase = 1;
+      D.phase = EVALUATE;
       return 1;
     }
-  if(D.phase == 1)
+  if(D.phase == EVALUATE)
     {
       D.sk_total = D.x.rtotal;
       D.sk_off = D.x.roff[D.rank];
@@ -832,10 +840,7 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
       if(op == GHIP_DD_BH_SWALLOW && A.counts)
         A.counts[0] = A.counts[1] = A.counts[2] = 0;
       if(ns == 0)
-        {
-          D.op = 0;
-          return 0;
-        }
+        return 0;
       if(op == GHIP_DD_SINK_DENSITY)
         {
           std::vector<SinkRec> all(ns);
@@ -846,7 +851,7 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
             D.sk_it.h[a] = all[a].h;
           D.sk_ncur = ns;
           D.sk_iter = 0;
-          D.phase = 2;
+          D.phase = COLLECT;
           return dd_sink_density_pass(ctx);
         }
       GCHK(ghip_sink_buffers(ctx));
@@ -862,7 +867,6 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
                                            P<unsigned int>(ctx->bh_swallow), P<double>(ctx->bh_injected));
           HIPCHK(hipGetLastError());
           HIPCHK(ghip_stream_sync(ctx, st));
-          D.op = 0;
           return 0;
         }
       // GHIP_DD_BH_SWALLOW: BH masses of this shard's sinks by particle, then every sink's sweep
@@ -888,10 +892,10 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
                                                                    P<double>(ctx->f[GHIP_F_MASS]));
       HIPCHK(hipGetLastError());
       ghip_dd_set_allgather(D, D.sk_part.p, (size_t) ns * 72, &D.sk_parts);
-      D.phase = 2;
+      D.phase = COLLECT;
       return 1;
     }
-  if(D.phase == 2 && op == GHIP_DD_SINK_DENSITY)
+  if(D.phase == COLLECT && op == GHIP_DD_SINK_DENSITY)
     {
       const int ns = D.sk_total;
       std::vector<double> parts, sums;
@@ -919,10 +923,9 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
                                 hipMemcpyHostToDevice, st));
         }
       HIPCHK(ghip_stream_sync(ctx, st));
-      D.op = 0;
       return 0;
     }
-  if(D.phase == 2 && op == GHIP_DD_BH_SWALLOW)
+  if(D.phase == COLLECT && op == GHIP_DD_BH_SWALLOW)
     {
       const int ns = D.sk_total;
       const size_t n = (size_t) ctx->n;
@@ -951,7 +954,6 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
       ctx->gt.built = false;   // masses changed: the trees' moments are stale
       ctx->st.built = false;
       D.geom_kept = true;      // (their geometry is not: the dust passes may still use them)
-      D.op = 0;
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the sink passes have no phase %d", D.phase);

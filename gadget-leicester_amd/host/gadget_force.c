@@ -14,6 +14,7 @@
 #include "gadget_force.h"
 
 #include <math.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -200,6 +201,28 @@ static int chk(int rc, const char *where)
   fprintf(stderr, "gadget_force: %s\n", ErrBuf);
   endrun(rc == GHIP_ENOCONV ? 1155 : -rc);
   return rc;
+}
+
+/* a call the library cannot serve ends the run the same way, with a code of its own */
+static int refuse(int code, const char *fmt, ...)
+{
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(ErrBuf, sizeof(ErrBuf), fmt, ap);
+  va_end(ap);
+  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+  endrun(code);
+  return -1;
+}
+
+/* scratch memory of one call; without it the run ends (90003) and the caller returns.  A call that needs several
+ * arrays takes them out of ONE block, doubles first, so that every way out has one free() */
+static void *scratch(size_t bytes)
+{
+  void *p = malloc(bytes ? bytes : 1);
+  if(!p)
+    endrun(90003);
+  return p;
 }
 
 int gadget_force_init(const struct gadget_force_config *cfg)
@@ -575,11 +598,7 @@ static int need_ctx(const char *who)
   all_pull();   /* every driver starts here: the host's `All` is the state (gadget_force_bind_all) */
   if(Ctx)
     return 0;
-  snprintf(ErrBuf, sizeof(ErrBuf), "%s: gadget_force_init() has not succeeded (no GPU context)",
-           who);
-  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-  endrun(90005);
-  return -1;
+  return refuse(90005, "%s: gadget_force_init() has not succeeded (no GPU context)", who);
 }
 
 static void pin_one(void **have, size_t *have_bytes, void *ptr, size_t bytes)
@@ -1111,28 +1130,16 @@ static int density_of_sinks(const ghip_dens_params *d)
           continue;
         }
       if(Lay.p_hsml < 0)
-        {
-          snprintf(ErrBuf, sizeof(ErrBuf),
-                   "density: %d active particles of type %d are density targets in this build "
-                   "(BLACK_HOLES / DUST), but the bound records keep Hsml in SphP[]: bind the host's "
-                   "records with gadget_force_bind_records()", n, type);
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90007);
-          return -1;
-        }
-      int *idx = (int *) malloc((size_t) (n + 1) * sizeof(int));
-      double *buf = (double *) malloc((size_t) (n + 1) * 7 * sizeof(double));
-      unsigned int *ids = (unsigned int *) malloc((size_t) (n + 1) * sizeof(unsigned int));
-      if(!idx || !buf || !ids)
-        {
-          free(idx);
-          free(buf);
-          free(ids);
-          endrun(90003);
-          return -1;
-        }
+        return refuse(90007, "density: %d active particles of type %d are density targets in this build "
+                             "(BLACK_HOLES / DUST), but the bound records keep Hsml in SphP[]: bind the host's "
+                             "records with gadget_force_bind_records()", n, type);
       const size_t m = (size_t) n + 1;
+      double *buf = (double *) scratch(m * (7 * sizeof(double) + sizeof(int) + sizeof(unsigned int)));
+      if(!buf)
+        return -1;
       double *hs = buf, *nn = buf + m, *rho = buf + 2 * m, *ent = buf + 3 * m, *vel = buf + 4 * m;
+      int *idx = (int *) (buf + 7 * m);
+      unsigned int *ids = (unsigned int *) (idx + m);
       int k = 0;
       for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
         if(p_type(i) == type && density_isactive(i))
@@ -1161,9 +1168,7 @@ static int density_of_sinks(const ghip_dens_params *d)
           rc = dd_collective(GHIP_DD_SINK_DENSITY, &a, 0, "density of sinks (ranks)") ? GHIP_EDEVICE : GHIP_OK;
           if(rc != GHIP_OK)
             {
-              free(idx);
               free(buf);
-              free(ids);
               return -1;
             }
         }
@@ -1189,9 +1194,7 @@ static int density_of_sinks(const ghip_dens_params *d)
                   PF64(i, o_vel)[c] = vel[3 * (size_t) k + c];
             }
         }
-      free(idx);
       free(buf);
-      free(ids);
       if(chk(rc, "ghip_sink_density"))
         return -1;
     }
@@ -1303,11 +1306,8 @@ static int visc_refuse_ranks(const char *who)
 {
   if(!visc_bound() || NTask <= 1)
     return 0;
-  snprintf(ErrBuf, sizeof(ErrBuf), "%s: gadget_force_bind_viscosity serves a single rank (NTask = %d); ranks "
-           "run GHIP_DD_HYDRO with ghip_set_viscosity / ghip_visc_set_alpha of their own", who, NTask);
-  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-  endrun(90014);
-  return -1;
+  return refuse(90014, "%s: gadget_force_bind_viscosity serves a single rank (NTask = %d); ranks "
+                       "run GHIP_DD_HYDRO with ghip_set_viscosity / ghip_visc_set_alpha of their own", who, NTask);
 }
 
 /* the setting and, with time_dependent, alpha and Dtalpha of the records reach the device */
@@ -1323,14 +1323,9 @@ static int visc_begin(const char *who)
   const int td = ViscLay.time_dependent > 0;
   if(td && (!ViscAll || ViscLay.a_alpha_min < 0 || ViscLay.a_visc_source < 0 || ViscLay.a_decay_time < 0 ||
             ViscLay.s_alpha < 0 || ViscLay.s_dtalpha < 0 || !RecP))
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "%s: time_dependent viscosity needs bound records and the offsets of "
-               "AlphaMin, ViscSource, DecayTime, alpha and Dtalpha (gadget_force_bind_records, "
-               "gadget_force_bind_viscosity)", who);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
-      return -1;
-    }
+    return refuse(90002, "%s: time_dependent viscosity needs bound records and the offsets of "
+                         "AlphaMin, ViscSource, DecayTime, alpha and Dtalpha (gadget_force_bind_records, "
+                         "gadget_force_bind_viscosity)", who);
   ghip_visc_params v;
   memset(&v, 0, sizeof(v));
   v.time_dependent = td;
@@ -1350,12 +1345,9 @@ static int visc_begin(const char *who)
   ViscOnDevice = 1;
   if(!td)
     return 0;
-  double *a = (double *) malloc(((size_t) 2 * N_gas + 1) * 8);
+  double *a = (double *) scratch(((size_t) 2 * N_gas + 1) * 8);
   if(!a)
-    {
-      endrun(90003);
-      return -1;
-    }
+    return -1;
   for(int i = 0; i < N_gas; i++)
     {
       a[i] = *SF64(i, ViscLay.s_alpha);
@@ -1374,12 +1366,9 @@ static int visc_end(void)
 {
   if(!visc_bound() || ViscLay.time_dependent <= 0 || N_gas == 0)
     return 0;
-  double *a = (double *) malloc((size_t) 2 * N_gas * 8);
+  double *a = (double *) scratch((size_t) 2 * N_gas * 8);
   if(!a)
-    {
-      endrun(90003);
-      return -1;
-    }
+    return -1;
   if(chk(ghip_visc_get(Ctx, a, a + N_gas), "ghip_visc_get"))
     {
       free(a);
@@ -1567,15 +1556,10 @@ static int integration_refuse_ranks(void)
   if(!integration_bound() || NTask <= 1)
     return 0;
   if(IntLay.s_drag_accel >= 0 || IntLay.p_delta_dust_momentum >= 0 || IntLay.p_new_density >= 0)
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "advance_and_find_timesteps: DragAccel / DeltaDustMomentum / NewDensity "
-               "are kept on a single GPU only (NTask = %d): bind s_drag_accel = p_delta_dust_momentum = "
-               "p_new_density = -1 (offsets %d / %d / %d)", NTask, IntLay.s_drag_accel,
-               IntLay.p_delta_dust_momentum, IntLay.p_new_density);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90011);
-      return -1;
-    }
+    return refuse(90011, "advance_and_find_timesteps: DragAccel / DeltaDustMomentum / NewDensity "
+                         "are kept on a single GPU only (NTask = %d): bind s_drag_accel = p_delta_dust_momentum = "
+                         "p_new_density = -1 (offsets %d / %d / %d)", NTask, IntLay.s_drag_accel,
+                         IntLay.p_delta_dust_momentum, IntLay.p_new_density);
   return 0;
 }
 
@@ -1606,15 +1590,11 @@ static int integration_begin(void)
   if(!fields)
     return chk(ghip_kick_set_fields(Ctx, NULL, NULL, NULL), "ghip_kick_set_fields");
   const int ng = N_gas;
-  double *drag = IntLay.s_drag_accel >= 0 ? (double *) malloc(((size_t) 3 * ng + 1) * 8) : NULL;
-  double *ddm = IntLay.p_delta_dust_momentum >= 0 ? (double *) malloc(((size_t) 3 * ng + 1) * 8) : NULL;
-  if((IntLay.s_drag_accel >= 0 && !drag) || (IntLay.p_delta_dust_momentum >= 0 && !ddm))
-    {
-      free(drag);
-      free(ddm);
-      endrun(90003);
-      return -1;
-    }
+  double *buf = (double *) scratch(((size_t) 6 * ng + 2) * 8);
+  if(!buf)
+    return -1;
+  double *drag = IntLay.s_drag_accel >= 0 ? buf : NULL;
+  double *ddm = IntLay.p_delta_dust_momentum >= 0 ? buf + 3 * (size_t) ng + 1 : NULL;
   for(int i = 0; i < ng; i++)
     for(int j = 0; j < 3; j++)
       {
@@ -1624,8 +1604,7 @@ static int integration_begin(void)
           ddm[3 * (size_t) i + j] = PF64(i, IntLay.p_delta_dust_momentum)[j];
       }
   int rc = chk(ghip_kick_set_fields(Ctx, drag, ddm, NULL), "ghip_kick_set_fields");
-  free(drag);
-  free(ddm);
+  free(buf);
   return rc;
 }
 
@@ -1637,12 +1616,9 @@ static int integration_end(const short *binold)
     return 0;
   if(IntLay.s_drag_accel >= 0 && NTask == 1 && N_gas > 0)
     {
-      double *drag = (double *) malloc((size_t) 3 * N_gas * 8);
+      double *drag = (double *) scratch((size_t) 3 * N_gas * 8);
       if(!drag)
-        {
-          endrun(90003);
-          return -1;
-        }
+        return -1;
       if(chk(ghip_kick_get_drag_accel(Ctx, drag), "ghip_kick_get_drag_accel"))
         {
           free(drag);
@@ -1785,10 +1761,7 @@ void advance_and_find_timesteps(void)
       atime = All.Time;
       if(!KickTabGrav || !KickTabHydro)
         {
-          snprintf(ErrBuf, sizeof(ErrBuf),
-                   "advance_and_find_timesteps: comoving kicks need gadget_force_set_kick_tables()");
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90002);
+          refuse(90002, "advance_and_find_timesteps: comoving kicks need gadget_force_set_kick_tables()");
           return;
         }
     }
@@ -1831,12 +1804,9 @@ void advance_and_find_timesteps(void)
   short *binold = NULL;   /* (the bins before the kick, for the per-bin sums) */
   if(integration_bound())
     {
-      binold = (short *) malloc(((size_t) NumPart + 1) * sizeof(short));
+      binold = (short *) scratch(((size_t) NumPart + 1) * sizeof(short));
       if(!binold)
-        {
-          endrun(90003);
-          return;
-        }
+        return;
       for(int i = 0; i < NumPart; i++)
         binold[i] = (short) p_timebin(i);
     }
@@ -2109,25 +2079,15 @@ static int bh_ready(const char *who)
     return -1;
   if(!Cfg.black_holes || BhLay.p_id < 0 || BhLay.p_swallowid < 0 || BhLay.p_bh_mass < 0 ||
      BhLay.p_bh_mdot < 0 || BhLay.p_bh_density < 0 || Lay.p_hsml < 0)
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "%s: needs a BLACK_HOLES configuration and records bound with "
-               "their black-hole members (gadget_force_bind_records)", who);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
-      return -1;
-    }
+    return refuse(90002, "%s: needs a BLACK_HOLES configuration and records bound with "
+                         "their black-hole members (gadget_force_bind_records)", who);
   if(NTask > 1)
     {
       /* the passes are collectives on the trees gravity_tree() and density() of THIS step left on the
        * device (blackhole_accretion follows them in compute_accelerations / run.c) */
       if(!DeviceFresh || !DdReady)
-        {
-          snprintf(ErrBuf, sizeof(ErrBuf), "%s on %d ranks must follow gravity_tree() and density() of the "
-                   "same step", who, NTask);
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90002);
-          return -1;
-        }
+        return refuse(90002, "%s on %d ranks must follow gravity_tree() and density() of the "
+                             "same step", who, NTask);
       return 0;
     }
   return ensure_tree();
@@ -2136,21 +2096,15 @@ static int bh_ready(const char *who)
 /* device marks <-> records: P[].SwallowID, SphP[].i.Injected_BH_Energy */
 static int bh_marks_to_device(void)
 {
-  unsigned int *sw = (unsigned int *) malloc((size_t) (NumPart > 0 ? NumPart : 1) * sizeof(unsigned int));
-  double *inj = (double *) malloc((size_t) (N_gas > 0 ? N_gas : 1) * sizeof(double));
-  if(!sw || !inj)
-    {
-      free(sw);
-      free(inj);
-      endrun(90003);
-      return -1;
-    }
+  double *inj = (double *) scratch((size_t) N_gas * sizeof(double) + (size_t) NumPart * sizeof(unsigned int));
+  if(!inj)
+    return -1;
+  unsigned int *sw = (unsigned int *) (inj + N_gas);
   for(int i = 0; i < NumPart; i++)
     sw[i] = *(unsigned int *) (prec(i) + BhLay.p_swallowid);
   for(int i = 0; i < N_gas; i++)
     inj[i] = BhLay.s_injected_bh_energy >= 0 ? *SF64(i, BhLay.s_injected_bh_energy) : 0.0;
   int rc = ghip_sink_set_marks(Ctx, sw, inj);
-  free(sw);
   free(inj);
   return chk(rc, "ghip_sink_set_marks") ? -1 : 0;
 }
@@ -2184,16 +2138,12 @@ static int bh_marks_to_records(int with_mass)
 /* blackhole_evaluate / _swallow of the sinks idx[0, n): results into the records */
 static int bh_evaluate_batch(int n, const int *idx)
 {
-  unsigned int *id = (unsigned int *) malloc((size_t) (n + 1) * sizeof(unsigned int));
-  double *md = (double *) malloc((size_t) (n + 1) * 2 * sizeof(double));
-  if(!id || !md)
-    {
-      free(id);
-      free(md);
-      endrun(90003);
-      return -1;
-    }
+  const size_t m = (size_t) n + 1;
+  double *md = (double *) scratch(m * (2 * sizeof(double) + sizeof(unsigned int)));
+  if(!md)
+    return -1;
   double *rho = md + n;
+  unsigned int *id = (unsigned int *) (md + 2 * m);
   for(int k = 0; k < n; k++)
     {
       id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
@@ -2215,29 +2165,22 @@ static int bh_evaluate_batch(int n, const int *idx)
       a.bh_mdot = md;
       a.bh_density_in = rho;
       rc = dd_collective(GHIP_DD_BH_EVALUATE, &a, 0, "blackhole_evaluate (ranks)") ? GHIP_EDEVICE : GHIP_OK;
-      free(id);
       free(md);
       return rc == GHIP_OK ? 0 : -1;
     }
   rc = ghip_blackhole_evaluate(Ctx, &b, n, idx, id, md, rho);
-  free(id);
   free(md);
   return chk(rc, "ghip_blackhole_evaluate") ? -1 : 0;
 }
 
 static int bh_swallow_batch(int n, const int *idx)
 {
-  unsigned int *id = (unsigned int *) malloc((size_t) (n + 1) * sizeof(unsigned int));
-  double *buf = (double *) malloc((size_t) (n + 1) * 7 * sizeof(double));
-  if(!id || !buf)
-    {
-      free(id);
-      free(buf);
-      endrun(90003);
-      return -1;
-    }
   const size_t m = (size_t) n + 1;
+  double *buf = (double *) scratch(m * (7 * sizeof(double) + sizeof(unsigned int)));
+  if(!buf)
+    return -1;
   double *bhm = buf, *am = buf + m, *ab = buf + 2 * m, *ad = buf + 3 * m, *mom = buf + 4 * m;
+  unsigned int *id = (unsigned int *) (buf + 7 * m);
   for(int k = 0; k < n; k++)
     {
       id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
@@ -2264,7 +2207,6 @@ static int bh_swallow_batch(int n, const int *idx)
       rc = dd_collective(GHIP_DD_BH_SWALLOW, &a, 0, "blackhole_evaluate_swallow (ranks)") ? GHIP_EDEVICE : GHIP_OK;
       if(rc != GHIP_OK)
         {
-          free(id);
           free(buf);
           return -1;
         }
@@ -2294,7 +2236,6 @@ static int bh_swallow_batch(int n, const int *idx)
       N_BH_swallowed += (int) counts[1];
       N_dust_swallowed += (int) counts[2];
     }
-  free(id);
   free(buf);
   return chk(rc, "ghip_blackhole_swallow") ? -1 : 0;
 }
@@ -2352,12 +2293,9 @@ void blackhole_accretion_neighbour_passes(void)
     return;
   if(n > 0 || NTask > 1)   /* (ranks: a collective, entered with or without sinks of one's own) */
     {
-      int *idx = (int *) malloc((size_t) (n + 1) * sizeof(int));
+      int *idx = (int *) scratch((size_t) (n + 1) * sizeof(int));
       if(!idx)
-        {
-          endrun(90003);
-          return;
-        }
+        return;
       int k = 0;
       for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
         if(p_type(i) == 5)
@@ -2431,11 +2369,9 @@ static int dust_ready(const char *who, int drag, int **idx_out)
   if(NTask > 1 && !RcclConnected && !AllgatherFn)
     {
       /* without a transport the passes cannot export grains to the other ranks */
-      snprintf(ErrBuf, sizeof(ErrBuf), "%s: without a transport (gadget_force_connect or "
-               "gadget_force_set_allgather) the dust passes run on a single rank only (NTask = %d)", who, NTask);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90010);
-      return -1;
+      return refuse(90010, "%s: without a transport (gadget_force_connect or "
+                           "gadget_force_set_allgather) the dust passes run on a single rank only (NTask = %d)",
+                    who, NTask);
     }
   int bad = !Cfg.dust || !RecP || Lay.p_hsml < 0 || DustLay.p_particle_density < 0;
   if(drag)
@@ -2444,26 +2380,16 @@ static int dust_ready(const char *who, int drag, int **idx_out)
           DustLay.p_radius < 0 || DustLay.p_vcoll < 0 || DustLay.a_mean_weight < 0 ||
           DustLay.a_unit_density < 0 || DustLay.a_unit_velocity < 0 || !DustAll;
   if(bad)
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "%s: needs a DUST configuration and records bound with their dust "
-               "members (gadget_force_bind_records, gadget_force_bind_dust)", who);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
-      return -1;
-    }
+    return refuse(90002, "%s: needs a DUST configuration and records bound with their dust "
+                         "members (gadget_force_bind_records, gadget_force_bind_dust)", who);
   gadget_force_flush();   /* results still on the device reach the records first */
   if(NTask > 1)
     {
       /* collectives on the trees gravity_tree() and density() of THIS step left on the device
        * (accel.c:194, 198 follow them) */
       if(!DeviceFresh || !DdReady)
-        {
-          snprintf(ErrBuf, sizeof(ErrBuf), "%s on %d ranks must follow gravity_tree() and density() of the "
-                   "same step", who, NTask);
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90002);
-          return -1;
-        }
+        return refuse(90002, "%s on %d ranks must follow gravity_tree() and density() of the "
+                             "same step", who, NTask);
     }
   else if(ensure_tree())
     return -1;
@@ -2471,12 +2397,9 @@ static int dust_ready(const char *who, int drag, int **idx_out)
   for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
     if(p_type(i) == 2)
       n++;
-  int *idx = (int *) malloc((size_t) (n + 1) * sizeof(int));
+  int *idx = (int *) scratch((size_t) (n + 1) * sizeof(int));
   if(!idx)
-    {
-      endrun(90003);
-      return -1;
-    }
+    return -1;
   n = 0;
   for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
     if(p_type(i) == 2)
@@ -2492,11 +2415,10 @@ void dust_density(void)
   const int n = dust_ready("dust_density", 0, &idx);
   if(n < 0)
     return;
-  double *rho = (double *) malloc((size_t) (n + 1) * sizeof(double));
+  double *rho = (double *) scratch((size_t) (n + 1) * sizeof(double));
   if(!rho)
     {
       free(idx);
-      endrun(90003);
       return;
     }
   ghip_dust_params d;
@@ -2533,11 +2455,10 @@ void dust_drag(void)
   const size_t ng = (size_t) (N_gas > 0 ? N_gas : 1);
   /* per grain: rho, A, gasvel[3], radius, d7, d9[3], dmom[3], dE, vcoll (15); per particle: vel[3]
    * + per gas particle: entropy, heating */
-  double *buf = (double *) malloc((15 * m + 3 * nall + 2 * ng) * sizeof(double));
+  double *buf = (double *) scratch((15 * m + 3 * nall + 2 * ng) * sizeof(double));
   if(!buf)
     {
       free(idx);
-      endrun(90003);
       return;
     }
   double *rho = buf, *ent = buf + m, *gv = buf + 2 * m, *rad = buf + 5 * m, *d7 = buf + 6 * m,
@@ -2675,13 +2596,8 @@ static int dd_prepare(void)
       DdReady = 1;
     }
   if(!RcclConnected && !AllgatherFn)
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "NTask = %d: call gadget_force_connect() (RCCL) or "
-               "gadget_force_set_allgather() first", NTask);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
-      return -1;
-    }
+    return refuse(90002, "NTask = %d: call gadget_force_connect() (RCCL) or "
+                         "gadget_force_set_allgather() first", NTask);
   if(DomainLen <= 0)
     domain_findExtent();
   if(chk(ghip_dd_set_domain(Ctx, DomainCorner, DomainCenter, DomainLen, All.ForceSoftening),
@@ -2691,12 +2607,9 @@ static int dd_prepare(void)
     {
       /* -DMULTIPLEDOMAINS > 1: the curve leaf by leaf (top-leaves are numbered along the curve,
        * domain.c:1495-1509) with the rank that owns each (DomainTask[], domain.c:1208-1215) */
-      unsigned long long *keys = (unsigned long long *) malloc((size_t) (NTopleaves + 1) * sizeof(unsigned long long));
+      unsigned long long *keys = (unsigned long long *) scratch((size_t) (NTopleaves + 1) * sizeof(unsigned long long));
       if(!keys)
-        {
-          endrun(90003);
-          return -1;
-        }
+        return -1;
       for(int l = 0; l <= NTopleaves; l++)
         keys[l] = ~0ULL;
       for(int i = 0; i < NTopnodes; i++)
@@ -2711,23 +2624,13 @@ static int dd_prepare(void)
       int rc = bad ? GHIP_EINVAL : ghip_dd_set_segments(Ctx, NTopleaves, keys, DomainTask);
       free(keys);
       if(bad)
-        {
-          snprintf(ErrBuf, sizeof(ErrBuf), "TopNodes / DomainTask do not describe %d top-leaves along the curve "
-                   "owned by ranks 0..%d", NTopleaves, NTask - 1);
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90002);
-          return -1;
-        }
+        return refuse(90002, "TopNodes / DomainTask do not describe %d top-leaves along the curve "
+                             "owned by ranks 0..%d", NTopleaves, NTask - 1);
       return chk(rc, "ghip_dd_set_segments") ? -1 : 0;
     }
   if(!TopNodes || !DomainStartList || NTopnodes <= 0)
-    {
-      snprintf(ErrBuf, sizeof(ErrBuf), "NTask = %d: TopNodes / DomainStartList of the host's domain "
-               "decomposition are not set", NTask);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
-      return -1;
-    }
+    return refuse(90002, "NTask = %d: TopNodes / DomainStartList of the host's domain "
+                         "decomposition are not set", NTask);
   unsigned long long splits[GHIP_DD_MAXRANKS_HOST + 1];
   for(int r = 0; r < NTask; r++)
     {
@@ -2739,13 +2642,7 @@ static int dd_prepare(void)
             break;
           }
       if(splits[r] == ~0ULL)
-        {
-          snprintf(ErrBuf, sizeof(ErrBuf), "no top-leaf %d (DomainStartList[%d]) in TopNodes",
-                   DomainStartList[r], r);
-          fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-          endrun(90002);
-          return -1;
-        }
+        return refuse(90002, "no top-leaf %d (DomainStartList[%d]) in TopNodes", DomainStartList[r], r);
     }
   splits[0] = 0;
   splits[NTask] = 1ULL << (3 * BITS_PER_DIMENSION);   /* PEANOCELLS */
@@ -2850,10 +2747,8 @@ static void hydro_force_ranks(void)
   double t0 = wallclock();
   if(Phase != 2)
     {
-      snprintf(ErrBuf, sizeof(ErrBuf), "hydro_force on %d ranks must follow density() and "
-               "force_update_hmax() of the same step (accel.c:84-106)", NTask);
-      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-      endrun(90002);
+      refuse(90002, "hydro_force on %d ranks must follow density() and "
+                    "force_update_hmax() of the same step (accel.c:84-106)", NTask);
       return;
     }
   ghip_hydro_params h;
@@ -2887,19 +2782,13 @@ static int potential_refused(const char *who)
 {
   if(NTask <= 1 || RcclConnected || AllgatherFn)
     return 0;
-  snprintf(ErrBuf, sizeof(ErrBuf), "%s: NTask = %d and no transport: call gadget_force_connect() (RCCL) or "
-           "gadget_force_set_allgather() first", who, NTask);
-  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-  endrun(90012);
-  return -1;
+  return refuse(90012, "%s: NTask = %d and no transport: call gadget_force_connect() (RCCL) or "
+                       "gadget_force_set_allgather() first", who, NTask);
 }
 
 static int potential_missing(const char *who, const char *what)
 {
-  snprintf(ErrBuf, sizeof(ErrBuf), "%s: %s", who, what);
-  fprintf(stderr, "gadget_force: %s\n", ErrBuf);
-  endrun(90013);
-  return -1;
+  return refuse(90013, "%s: %s", who, what);
 }
 
 /* get_gravkick_factor (driftfac.c:166-205) on the host's table */
@@ -2996,12 +2885,9 @@ void compute_potential(void)
     }
   else if(chk(ghip_potential(Ctx, &pp), "ghip_potential"))
     return;
-  double *pot = (double *) malloc((size_t) (NumPart > 0 ? NumPart : 1) * sizeof(double));
+  double *pot = (double *) scratch((size_t) NumPart * sizeof(double));
   if(!pot)
-    {
-      endrun(90003);
-      return;
-    }
+    return;
   if(chk(ghip_get_potential(Ctx, pot), "ghip_get_potential"))
     {
       free(pot);
@@ -3066,16 +2952,12 @@ void compute_global_quantities_of_system(void)
   gadget_force_flush();
   all_pull();
   const int n = NumPart, ng = N_gas;
-  double *buf = (double *) malloc((size_t) (n > 0 ? n : 1) * 6 * sizeof(double));
-  double *pot = (double *) malloc((size_t) (n > 0 ? n : 1) * sizeof(double));
-  double *ph = (double *) malloc((size_t) (n > 0 ? n : 1) * sizeof(double));
-  int *ib = (int *) malloc((size_t) (n > 0 ? n : 1) * sizeof(int));
-  if(!buf || !pot || !ph || !ib)
-    {
-      free(buf), free(pot), free(ph), free(ib);
-      endrun(90003);
-      return;
-    }
+  const size_t m = (size_t) (n > 0 ? n : 1);
+  double *buf = (double *) scratch(m * (8 * sizeof(double) + sizeof(int)));   /* 6 for a field, pot, ph; ib */
+  if(!buf)
+    return;
+  double *pot = buf + 6 * m, *ph = pot + m;
+  int *ib = (int *) (ph + m);
   int rc = chk(ghip_set_counts(Ctx, n, ng), "ghip_set_counts");
   if(!rc)
     rc = field_from_records(GHIP_F_POS, Lay.p_pos, 3, 0, buf) || field_from_records(GHIP_F_VEL, Lay.p_vel, 3, 0, buf) ||
@@ -3151,7 +3033,7 @@ void compute_global_quantities_of_system(void)
     }
   else if(!rc)
     rc = chk(ghip_global_quantities(Ctx, &gp, &s), "ghip_global_quantities");
-  free(buf), free(pot), free(ph), free(ib);
+  free(buf);
   /* the device fields now hold the records' state: the next driver uploads and builds again */
   DeviceFresh = 0;
   TreeOnDevice = 0;

@@ -370,7 +370,9 @@ int ghip_dd_rccl_unique_id(void *id128);
 int ghip_dd_rccl_connect(ghip_ctx *ctx, const void *id128);
 const char *ghip_dd_rccl_library(void);
 int ghip_dd_begin(ghip_ctx *ctx, int op, const void *params, int walk);
-int ghip_dd_step(ghip_ctx *ctx);                 /* 1: exchange pending, 0: done, < 0: error */
+/* 1: exchange pending, 0: done, < 0: error.  A step that returns <= 0 ends the operation, complete or failed:
+ * a further ghip_dd_step without a new ghip_dd_begin fails with "no operation in progress". */
+int ghip_dd_step(ghip_ctx *ctx);
 int ghip_dd_exchange(ghip_ctx *ctx);             /* RCCL */
 int ghip_dd_exchange_local(ghip_ctx **ctxs, int nranks);
 /* the pending exchange staged through host memory and the CALLER's all-gather of equal-sized

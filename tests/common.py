@@ -294,6 +294,34 @@ class ShardSet:
             fp.close()
 
 
+def failing_collective(paths, op, params, walk=0):
+    """`op` on all shards of this process, expected to fail: the GhipError of every shard, in shard order.
+    All shards must fail in the same step (no shard is left inside the collective), and the failed step ends
+    the operation on every one of them: a further ghip_dd_step finds no operation in progress."""
+    import pytest
+    B = bindings()
+    prm = params if isinstance(params, (list, tuple)) else [params] * len(paths)
+    for fp, q in zip(paths, prm):
+        fp.dd_begin(op, q, walk)
+    while True:
+        rcs, errs = [], []
+        for fp in paths:
+            try:
+                rcs.append(fp.dd_step())
+            except B.GhipError as e:
+                errs.append(e)
+        if errs:
+            break
+        assert rcs == [1] * len(paths), "the operation did not fail: %r" % (rcs,)
+        B.dd_exchange_local(paths)
+    assert len(errs) == len(paths), "%d of %d shards failed, the others returned %r" % (len(errs), len(paths), rcs)
+    for fp in paths:
+        with pytest.raises(B.GhipError) as e:
+            fp.dd_step()
+        assert "no operation in progress" in str(e.value)
+    return errs
+
+
 class SinkProblem:
     """A Problem with a few Type-5 sinks and Type-2 dust grains (config c5's ingredients): some DM
     particles are re-typed, one sink is the heavy central object.  Parameters of the shipped flag

@@ -8,7 +8,8 @@ counts must be exact and the sums agree to summation order."""
 import numpy as np
 import pytest
 
-from common import O, Problem, ShardSet, SinkProblem, bindings, relerr, sampled_hydro_check
+from common import (O, Problem, ShardSet, SinkProblem, bindings, failing_collective, relerr,
+                    sampled_hydro_check)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
@@ -324,8 +325,86 @@ def test_a_particle_outside_the_domain_cube_is_refused_by_every_shard():
         with pytest.raises(B.GhipError) as e:
             S.run.gravity(pr.g_grav(pr.theta), B.WALK_NEWTON)
         assert "domain cube" in str(e.value) or "reported an error" in str(e.value)
+        # every shard stops in the same step: the holder with its own message, the others with one message that
+        # names the holder; that step ends the operation (failing_collective checks it on every shard)
+        holder = int(S.owner[far])
+        errs = failing_collective(S.fp, B.DD_GRAVITY, pr.g_grav(pr.theta), B.WALK_NEWTON)
+        assert "domain cube" in str(errs[holder])
+        others = {str(e_) for r, e_ in enumerate(errs) if r != holder}
+        assert len(others) == 1 and "gravity: shard %d reported an error" % holder in others.pop()
+        # ... and with the particle back inside the cube the same operation succeeds on the same contexts
+        S.set_field(B.F_POS, pr.ic["pos"])
+        S.migrate()
+        S.run.gravity(pr.g_grav(pr.theta), B.WALK_NEWTON)
+        assert np.all(S.get_field(B.F_GRAVCOST) > 0)
     finally:
         S.close()
+
+
+def test_a_failed_h_iteration_on_one_shard_stops_every_shard():
+    """GHIP_DD_DENSITY with one active gas target in the whole run, on shard 5, that cannot reach its neighbour
+    count: one h iteration allowed, |NumNgb - DesNumNgb| < 1e-6 asked (test_gpu_parity's endrun(1155) case).
+    The failure travels in the status round: shard 5 raises its own message, every other shard -- none of
+    which has a target -- the message that names shard 5, all in the same step; that step ends the operation,
+    and with the reference's tolerance the same call succeeds on the same contexts."""
+    B = bindings()
+    pr = Problem(ng=12, gas=True, periodic=1)
+    S = ShardSet(pr, 8)
+    try:
+        k = 5
+        assert S.ngas[k] > 0
+        for r, fp in enumerate(S.fp):
+            fp.set_active(np.zeros(1 if r == k else 0, np.int32))   # (gas comes first: local particle 0)
+        dp = pr.g_dens()
+        dp.MaxIter = 1
+        dp.MaxNumNgbDeviation = 1e-6
+        errs = failing_collective(S.fp, B.DD_DENSITY, dp)
+        assert B.GHIP_ERRORS[errs[k].code] == "GHIP_ENOCONV"
+        assert "1 particles not converged after 1 h-iterations" in str(errs[k]) and "1155" in str(errs[k])
+        others = {str(e) for r, e in enumerate(errs) if r != k}
+        assert len(others) == 1
+        msg = others.pop()
+        assert "GHIP_EDEVICE" in msg and "density: the h iteration failed on shard %d " % k in msg
+        S.run.density(pr.g_dens())
+        numngb = S.fp[k].get_field(B.F_NUMNGB)[0]
+        assert abs(numngb - pr.des_ngb) <= pr.max_dev
+    finally:
+        S.close()
+
+
+def test_every_operation_has_an_entry_and_a_traffic_counter():
+    """the operations of ghip_dd_begin are GHIP_DD_MIGRATE .. GHIP_DD_PM_NONPERIODIC without a gap: each is
+    known to ghip_dd_begin (the common refusals come first) and to ghip_dd_bytes_sent, the numbers on either
+    side are not"""
+    import ctypes as C
+    B = bindings()
+    ops = {name: getattr(B, name) for name in dir(B) if name.startswith("DD_") and isinstance(getattr(B, name), int)}
+    assert sorted(ops.values()) == list(range(1, B.DD_PM_NONPERIODIC + 1)), ops
+    pr = Problem(ng=4, gas=True, periodic=1)
+    fp = B.ForcePath(0)
+    try:
+        fp.set_counts(0, 0)
+        dummy = C.c_int(0)    # (never read: the refusals below come before any operation looks at its params)
+        for name, op in ops.items():
+            with pytest.raises(B.GhipError) as e:
+                fp.dd_begin(op, dummy)
+            assert "call ghip_dd_init first" in str(e.value), name
+        with pytest.raises(B.GhipError) as e:
+            fp.dd_begin(B.DD_MIGRATE, None)
+        assert "call ghip_dd_init first" in str(e.value)
+        fp.dd_init(0, 1)
+        fp.dd_set_domain(pr.extent[0], pr.extent[1], pr.extent[2], pr.force_soft)
+        for op in (0, B.DD_PM_NONPERIODIC + 1):
+            with pytest.raises(B.GhipError) as e:
+                fp.dd_begin(op, dummy)
+            assert "unknown operation %d" % op in str(e.value)
+            with pytest.raises(B.GhipError) as e:
+                fp.dd_bytes_sent(op)
+            assert B.GHIP_ERRORS[e.value.code] == "GHIP_EINVAL"
+        for name, op in ops.items():
+            assert fp.dd_bytes_sent(op) == 0, name
+    finally:
+        fp.close()
 
 
 def test_migration_moves_every_field_with_its_particle():

@@ -434,8 +434,11 @@ def test_a_stray_particle_on_one_shard_stops_every_shard():
         fp.dd_begin(B.DD_PM_NONPERIODIC, prm)
     assert [fp.dd_step() for fp in paths] == [1, 1, 1]
     B.dd_exchange_local(paths)
-    for fp in paths:   # EVERY shard, the one that holds the stray and the two that do not
-        assert "outside" in refused(EREGION, fp.dd_step)
+    # EVERY shard, the one that holds the stray and the two that do not, with one message
+    msgs = [refused(EREGION, fp.dd_step) for fp in paths]
+    assert len(set(msgs)) == 1 and "outside" in msgs[0]
+    for fp in paths:   # the failed step ended the operation: nothing pending, nothing in progress
+        assert "no operation in progress" in refused(EINVAL, fp.dd_step)
     for fp, s in zip(paths, sentinels):
         assert np.array_equal(fp.get_field(B.F_GRAVPM), s)
     # the region again over all shards, then the same call succeeds
