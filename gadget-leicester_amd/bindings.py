@@ -295,7 +295,7 @@ EXPORTS = [
     "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain",
     "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic",
     "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
-    "ghip_set_rnd_table", "ghip_tree_max_level"]
+    "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts"]
 
 
 def lib():
@@ -382,6 +382,8 @@ def lib():
         L.ghip_dd_run.argtypes = [vp, C.c_int, vp, C.c_int]
         L.ghip_dd_exchange_host.argtypes = [vp, ALLGATHER_CB, vp]
         L.ghip_dd_get_info.argtypes = [vp, vp]
+        L.ghip_dd_set_guests.argtypes = [vp, C.c_int]
+        L.ghip_dd_guest_counts.argtypes = [vp, vp]
         L.ghip_sink_density.argtypes = [vp, C.POINTER(DensParams), C.c_double, C.c_int, vp, vp, vp,
                                         vp, vp, vp, C.POINTER(C.c_int)]
         L.ghip_sink_reset.argtypes = [vp]
@@ -1046,6 +1048,11 @@ class ForcePath:
     def dd_set_ghost_margin(self, margin):
         self._chk(self.L.ghip_dd_set_ghost_margin(self.h, float(margin)))
 
+    def dd_set_guests(self, on=True):
+        """ghip_dd_set_guests: accept resident particles whose keys left this shard's pieces of the curve
+        (the same value on every shard)"""
+        self._chk(self.L.ghip_dd_set_guests(self.h, int(bool(on))))
+
     def dd_begin(self, op, params, walk=0):
         self._dd_params = params          # keep the struct alive
         ptr = None if params is None else C.cast(C.byref(params), C.c_void_p)
@@ -1121,7 +1128,11 @@ class ForcePath:
         keys = ("rank", "nranks", "let_imported", "let_sent", "ghosts_imported", "ghosts_sent",
                 "bytes_gravity", "bytes_density", "hsml_growth_e6", "grav_elements", "gas_elements",
                 "numpart", "ngas", "migrated_out", "migrated_in", "bytes_migrate")
-        return dict(zip(keys, (int(v) for v in out)))
+        info = dict(zip(keys, (int(v) for v in out)))
+        guests = np.zeros(2, np.int64)
+        self._chk(self.L.ghip_dd_guest_counts(self.h, _ptr(guests)))
+        info["guests_held"], info["guests_hosted"] = int(guests[0]), int(guests[1])
+        return info
 
     def dd_bytes_sent(self, op):
         """bytes this shard sent over links in its last operation `op` (DD_*)"""

@@ -168,7 +168,7 @@ int ghip_check_device_errors(ghip_ctx *ctx)
     "essential tree was incomplete",
     "tree emission outside the element list, a malformed imported element (3), paths deeper than "
     "GHIP_TREE_MAXLEVEL (7: ghip_set_rnd_table), a particle outside its "
-    "shard's key range (5: migrate first) or outside the domain cube (6: ghip_dd_set_domain with a fresh extent)",
+    "shard's key range (5: migrate first, or allow guests with ghip_dd_set_guests) or outside the domain cube (6: ghip_dd_set_domain with a fresh extent)",
     "a particle that passed the range check of the non-periodic mesh fell outside its lower octant (nothing was "
     "written for it): the region in force is inconsistent",
     "drift", "timestep", "", ""};

@@ -29,7 +29,9 @@
 //             whose own smoothing sphere reaches them, are sent as GHOSTS before density(); their
 //             updated records follow once between density() and hydro_force().
 // Ownership is by Peano-Hilbert key range [splits[r], splits[r+1]): a cell lies wholly inside a
-// shard's range or it is "shared" and always descended.
+// shard's range or it is "shared" and always descended.  With ghip_dd_set_guests a shard may hold
+// particles outside its range (guests, between two migrations): a cell whose range holds the key of a
+// guest held elsewhere is shared too, which its owner learns from the guests' keys (k_let_level).
 #include <cstdarg>
 
 #include <hipcub/hipcub.hpp>
@@ -307,6 +309,48 @@ __global__ void k_dd_check_range(int n, const double *__restrict__ x, const doub
     *(volatile int *) errword = 5;
 }
 
+// ghip_dd_set_guests: the same key, and in place of the error the guest's key and the shard that owns it (its
+// host, found as the migration finds a destination: the last piece that starts at or before the key)
+__global__ void k_dd_mark_guests(int n, const double *__restrict__ x, const double *__restrict__ y,
+                                 const double *__restrict__ z, double cx, double cy, double cz,
+                                 double fac, int nown, const unsigned long long *__restrict__ ownlo,
+                                 const unsigned long long *__restrict__ ownhi, int nseg,
+                                 const unsigned long long *__restrict__ segkey,
+                                 const int *__restrict__ segowner, unsigned long long *__restrict__ key,
+                                 unsigned long long *__restrict__ mask, int *__restrict__ errword)
+{
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i >= n)
+    return;
+  // (a particle outside the domain cube stays error 6)
+  const unsigned long long k = d_peano21(d_cell21(x[i], cx, fac, errword), d_cell21(y[i], cy, fac, errword),
+                                         d_cell21(z[i], cz, fac, errword));
+  unsigned long long m = 0;
+  if(!d_owned_range(k, k + 1, nown, ownlo, ownhi))
+    {
+      int lo = 0, hi = nseg - 1;   // largest s with segkey[s] <= k
+      while(lo < hi)
+        {
+          int mid = (lo + hi + 1) >> 1;
+          if(segkey[mid] <= k)
+            lo = mid;
+          else
+            hi = mid - 1;
+        }
+      m = 1ULL << segowner[lo];
+    }
+  key[i] = k;
+  mask[i] = m;
+}
+
+__global__ void k_dd_gather_u64(int n, const int *__restrict__ list, const unsigned long long *__restrict__ in,
+                                unsigned long long *__restrict__ out)
+{
+  int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < n)
+    out[a] = in[list[a]];
+}
+
 // ---------------------------------------------------------------------------------------------
 // target groups
 // ---------------------------------------------------------------------------------------------
@@ -444,6 +488,7 @@ static int build_groups(ghip_ctx *ctx, bool gas, const int *tgt, int nt, const d
   DDGroup status;
   memset(&status, 0, sizeof(status));
   status.cx = ghip_dd_hold(ctx, ghip_check_device_errors(ctx)) ? 1.0 : 0.0;
+  status.cy = D.guests_on ? (double) D.guests_held : 0.0;
   HIPCHK(hipMemcpyAsync(tab + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, st));
   HIPCHK(ghip_stream_sync(ctx, st));   // (`status` lives on this frame)
   return GHIP_OK;
@@ -454,23 +499,33 @@ __global__ void k_dd_collect_status(int nranks, const DDGroup *__restrict__ all,
 {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if(r < nranks)
-    out[r] = all[(size_t) r * DD_STRIDE + DD_TABLE].cx;
+    {
+      out[r] = all[(size_t) r * DD_STRIDE + DD_TABLE].cx;
+      out[nranks + r] = all[(size_t) r * DD_STRIDE + DD_TABLE].cy;
+    }
 }
 
-static int check_group_status(ghip_ctx *ctx, const char *what)
+// guests (if asked for): the guests all shards hold together, as the gravity tree's guest pass counted them
+static int check_group_status(ghip_ctx *ctx, const char *what, long long *guests = nullptr)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
   const int P_ = D.nranks;
   GCHK(ghip_ensure(ctx, D.status_all, (size_t) GHIP_MAXRANKS * 2 * 8));
   k_dd_collect_status<<<1, 64, 0, st>>>(P_, P<DDGroup>(D.grp_all), P<double>(D.status_all));
-  double flags[GHIP_MAXRANKS];
-  HIPCHK(hipMemcpyAsync(flags, D.status_all.p, (size_t) P_ * 8, hipMemcpyDeviceToHost, st));
+  double flags[2 * GHIP_MAXRANKS];
+  HIPCHK(hipMemcpyAsync(flags, D.status_all.p, (size_t) P_ * 16, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
   int failed = -1;
+  long long held = 0;
   for(int r = 0; r < P_; r++)
-    if(flags[r] != 0 && failed < 0)
-      failed = r;
+    {
+      if(flags[r] != 0 && failed < 0)
+        failed = r;
+      held += (long long) flags[P_ + r];
+    }
+  if(guests)
+    *guests = held;
   return ghip_dd_raise(ctx, failed, "%s: shard %d reported an error while it prepared its target "
                        "groups (its own message says what); every shard stops here", what, failed);
 }
@@ -539,6 +594,8 @@ struct LetK
   int nranks, me;
   int nown;                                   // this rank's own pieces of the curve
   const unsigned long long *ownlo, *ownhi;
+  int nguest;                                 // guests other shards hold inside this rank's pieces:
+  const unsigned long long *guest;            // their keys in ascending order (ghip_dd_set_guests)
 };
 
 // squared distance between the box (c +- e; e = 0: a point) and the group's box, component-wise, with
@@ -621,7 +678,12 @@ __device__ __forceinline__ double d_bcast(double v, int j)
 // reaches are tested one after the other against all 64 super-groups at once (and against the 16
 // groups of up to four hit super-groups at a time).  Finally every candidate lane publishes its own
 // result and marks its children.
+// GUESTS: somebody holds a particle inside this shard's pieces of the curve (K.guest, sorted).  A cell with
+// such a key inside its range has partial moments here although it is wholly owned: it is descended like a
+// shared one.  The other ranks need not know: to them the cell is not wholly theirs, so shared already.
+// Without guests the kernel is the <false> one, the code it always was.
 #define LET_EPW 16
+template <bool GUESTS>
 __global__ void __launch_bounds__(64)
 k_let_level(int nelem, int level, const int4 *__restrict__ lk, const double4 *__restrict__ xm,
             const double4 *__restrict__ cl, const double *__restrict__ aux,
@@ -659,6 +721,19 @@ k_let_level(int nelem, int level, const int4 *__restrict__ lk, const double4 *__
           const unsigned long long lo = (ph >> sh) << sh;
           const unsigned long long hi = lo + (1ULL << sh);
           shared = !d_owned_range(lo, hi, K.nown, K.ownlo, K.ownhi);
+          if(GUESTS && !shared)
+            {
+              int a0 = 0, a1 = K.nguest;   // first guest key >= lo
+              while(a0 < a1)
+                {
+                  const int mid = (a0 + a1) >> 1;
+                  if(K.guest[mid] < lo)
+                    a0 = mid + 1;
+                  else
+                    a1 = mid;
+                }
+              shared = a0 < K.nguest && K.guest[a0] < hi;
+            }
         }
       m4 = xm[e];
       c4 = cl[e];
@@ -1195,6 +1270,43 @@ int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord,
 #define set_alltoallv ghip_dd_set_alltoallv
 
 // ---- gravity ------------------------------------------------------------------------------
+// The guest pass (ghip_dd_set_guests) in place of the range check: which resident particles lie outside this
+// shard's pieces of the curve, and their keys listed per host, in the order the shard holds them.
+static int find_guests(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int n = ctx->n;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    D.guest_scount[r] = D.guest_soff[r] = 0;
+  GCHK(ghip_ensure(ctx, D.guest_send, 8));
+  if(n == 0)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, D.guest_mask, (size_t) n * 8));
+  GCHK(ghip_ensure(ctx, D.guest_key, (size_t) n * 8));
+  const double *x = P<double>(ctx->f[GHIP_F_POS]);
+  const double fac = 1.0 / ctx->dlen * (double) (1ULL << GHIP_BITS);
+  k_dd_mark_guests<<<cdiv(n, 256), 256, 0, st>>>(
+    n, x, x + n, x + 2 * (size_t) n, ctx->corner[0], ctx->corner[1], ctx->corner[2], fac, D.nown,
+    P<unsigned long long>(D.ownlo), P<unsigned long long>(D.ownhi), D.nseg, P<unsigned long long>(D.segkey),
+    P<int>(D.segowner), P<unsigned long long>(D.guest_key), P<unsigned long long>(D.guest_mask),
+    ghip_errword(ctx, GHIP_ERRW_TREE));
+  HIPCHK(hipGetLastError());
+  int total = 0;
+  GCHK(multi_select(ctx, n, P<unsigned long long>(D.guest_mask), D.guest_list, D.guest_scount, D.guest_soff,
+                    &total));
+  D.guests_held = total;
+  if(total > 0)
+    {
+      GCHK(ghip_ensure(ctx, D.guest_send, (size_t) total * 8));
+      k_dd_gather_u64<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.guest_list),
+                                                       P<unsigned long long>(D.guest_key),
+                                                       P<unsigned long long>(D.guest_send));
+      HIPCHK(hipGetLastError());
+    }
+  return GHIP_OK;
+}
+
 // the shard's own tree (moments of the cells it owns), nothing imported
 int ghip_dd_own_tree(ghip_ctx *ctx)
 {
@@ -1203,7 +1315,11 @@ int ghip_dd_own_tree(ghip_ctx *ctx)
   GCHK(ghip_join_pair(ctx));
   D.gt_nimp = 0;
   D.gt_is_pot = false;
-  if(ctx->n > 0)
+  D.guests_held = D.guests_hosted = 0;
+  D.guest_xchg = false;
+  if(D.guests_on)
+    GCHK(find_guests(ctx));
+  else if(ctx->n > 0)
     {
       const double *x = P<double>(ctx->f[GHIP_F_POS]);
       const double fac = 1.0 / ctx->dlen * (double) (1ULL << GHIP_BITS);
@@ -1249,13 +1365,47 @@ int ghip_dd_post_groups(ghip_ctx *ctx, bool all, bool need_oldacc)
   return GHIP_OK;
 }
 
-// after the all-gather of the group tables: what can the others need of this tree?
-int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what)
+// after the all-gather of the group tables: every shard fails if one did (all shards together, see DD_STRIDE);
+// does any shard hold a guest?  Then every shard sends the keys of its guests to their hosts, and only there:
+// 1, the all-to-all-v is pending.  Nobody holds one (always so with the mode off): 0, nothing is exchanged.
+int ghip_dd_post_guests(ghip_ctx *ctx, const char *what)
+{
+  DDState &D = ctx->dd;
+  long long held = 0;
+  GCHK(check_group_status(ctx, what, &held));
+  if(!D.guests_on || held == 0)
+    return 0;
+  D.guest_xchg = true;
+  set_alltoallv(D, D.guest_send.p, 8, D.guest_scount, D.guest_soff, &D.guest_recv);
+  return 1;
+}
+
+// the keys of the guests this shard hosts, as the exchange left them, in ascending order
+static int sort_hosted_guests(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  const int ng = D.x.rtotal;
+  D.guests_hosted = ng;
+  if(ng == 0)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, D.guest_sorted, (size_t) ng * 8));
+  const unsigned long long *in = P<unsigned long long>(D.guest_recv);
+  unsigned long long *out = P<unsigned long long>(D.guest_sorted);
+  size_t tb = 0;
+  HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, in, out, ng, 0, 63, ctx->stream));
+  GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
+  HIPCHK(hipcub::DeviceRadixSort::SortKeys(ctx->cubtmp.p, tb, in, out, ng, 0, 63, ctx->stream));
+  return GHIP_OK;
+}
+
+// after ghip_dd_post_guests (and the exchange it asked for): what can the others need of this tree?
+int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
   const int P_ = D.nranks;
-  GCHK(check_group_status(ctx, what));   // (all shards together, see DD_STRIDE)
+  if(D.guest_xchg)
+    GCHK(sort_hosted_guests(ctx));
   TreeDev &t = ctx->gt;
   int scount[GHIP_MAXRANKS], soff[GHIP_MAXRANKS], total = 0;
   for(int r = 0; r < GHIP_MAXRANKS; r++)
@@ -1274,13 +1424,16 @@ int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what
       K.nown = D.nown;
       K.ownlo = P<unsigned long long>(D.ownlo);
       K.ownhi = P<unsigned long long>(D.ownhi);
+      K.nguest = D.guests_hosted;
+      K.guest = P<unsigned long long>(D.guest_sorted);
       unsigned long long all = (P_ >= 64) ? ~0ULL : ((1ULL << P_) - 1ULL);
       all &= ~(1ULL << D.rank);
       unsigned long long *reach = P<unsigned long long>(D.reach),
                          *sendm = P<unsigned long long>(D.sendm);
       k_let_init<<<cdiv(t.nelem, 256), 256, 0, st>>>(t.nelem, all, reach, sendm);
+      auto *level_kernel = K.nguest > 0 ? k_let_level<true> : k_let_level<false>;
       for(int L = 0; L <= t.maxlevel; L++)
-        k_let_level<<<cdiv(t.nelem, LET_EPW), 64, 0, st>>>(
+        level_kernel<<<cdiv(t.nelem, LET_EPW), 64, 0, st>>>(
           t.nelem, L, P<int4>(t.lk), P<double4>(t.xm), P<double4>(t.cl), P<double>(t.aux),
           P<unsigned long long>(t.skey), P<DDGroup>(D.grp_all), K, reach, sendm);
       k_let_single<<<1, 64, 0, st>>>(t.nelem, P<int4>(t.lk), reach, sendm);
@@ -1303,8 +1456,9 @@ int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what
 
 // GHIP_DD_GRAVITY:
 //   GROUPS  the shard's own tree and the groups of its active targets          -> all-gather of the groups
-//   LET     every shard fails if one did; selection of the locally essential trees, packed
-//                                                                               -> all-to-all-v of LetRec
+//   GUESTS  every shard fails if one did; with ghip_dd_set_guests, when any shard holds a guest: the guests' keys
+//           to their hosts (else straight on to LET)                            -> all-to-all-v of u64 keys
+//   LET     selection of the locally essential trees, packed                    -> all-to-all-v of LetRec
 //   WALK    one tree over the local particles and everything that was imported, then the walks
 static int gravity_begin(ghip_ctx *ctx, int, const void *params, int walk)
 {
@@ -1319,17 +1473,24 @@ static int gravity_begin(ghip_ctx *ctx, int, const void *params, int walk)
 static int gravity_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
-  enum { GROUPS, LET, WALK, DONE };
+  enum { GROUPS, GUESTS, LET, WALK, DONE };
   if(D.phase == GROUPS)
     {
       GCHK(ghip_dd_own_tree(ctx));
       GCHK(ghip_dd_post_groups(ctx, false, true));
-      D.phase = LET;
+      D.phase = GUESTS;
       return 1;
+    }
+  if(D.phase == GUESTS)
+    {
+      const int pending = ghip_dd_post_guests(ctx, "gravity");
+      D.phase = LET;
+      if(pending != 0)
+        return pending;
     }
   if(D.phase == LET)
     {
-      GCHK(ghip_dd_post_let(ctx, D.gp, "gravity"));
+      GCHK(ghip_dd_post_let(ctx, D.gp));
       D.phase = WALK;
       return 1;
     }
@@ -2009,6 +2170,25 @@ extern "C" int ghip_dd_get_info(const ghip_ctx *ctx, long long out[16])
   out[13] = D.mig_out;
   out[14] = D.mig_in;
   out[15] = D.bytes_sent[GHIP_DD_MIGRATE];
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dd_set_guests(ghip_ctx *ctx, int on)
+{
+  if(!ctx || !ctx->dd.on)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_set_guests: call ghip_dd_init first");
+  if(ctx->dd.op != 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_set_guests: not while an operation is in progress");
+  ctx->dd.guests_on = on != 0;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_dd_guest_counts(const ghip_ctx *ctx, long long out[2])
+{
+  if(!ctx || !out)
+    return GHIP_EINVAL;
+  out[0] = ctx->dd.guests_held;
+  out[1] = ctx->dd.guests_hosted;
   return GHIP_OK;
 }
 

@@ -129,7 +129,8 @@ struct TreeDev
 // ... and one status record behind them (cx != 0: this shard met an error while it prepared the
 // table -- a particle outside its key range, a device invariant): every shard reads every status after
 // the all-gather and all of them fail TOGETHER, instead of one returning while its peers wait for it
-// inside the next collective
+// inside the next collective.  cy: the guests this shard holds (ghip_dd_set_guests; 0 with the mode off):
+// after the all-gather every shard knows whether anybody holds one
 #define DD_STRIDE (DD_TABLE + 1)
 struct __attribute__((aligned(64))) DDGroup
 {
@@ -222,6 +223,19 @@ struct DDState
   double gh_margin_cur = 1.3;     // ... in the density call in progress: grows when an h outgrew it (see density_step)
   int gh_retries = 0;             // re-selections of the density call in progress
   DevBuf status_own, status_all;  // f64[2] per shard: {a value, error flag} (dd_post_status / dd_read_status)
+  // guests (ghip_dd_set_guests): resident particles whose keys lie outside this shard's pieces of the curve.
+  // The gravity tree's guest pass (ghip_dd_own_tree) finds them and lists their keys per host (the shard
+  // that owns the key); when any shard holds one, the keys go to their hosts before the selection of the
+  // locally essential trees, which then descends every cell that contains one (k_let_level).
+  bool guests_on = false;
+  bool guest_xchg = false;        // the operation in progress exchanged guest keys (their sorted list is in place)
+  int guests_held = 0;            // guests resident here in the last GHIP_DD_GRAVITY / GHIP_DD_POTENTIAL
+  int guests_hosted = 0;          // guest keys received for this shard's pieces of the curve
+  DevBuf guest_mask, guest_key;   // u64[n]: 1 << host of a guest, else 0; u64[n]: the Peano-Hilbert keys
+  DevBuf guest_list;              // i32: per host, the local indices of its guests (ascending)
+  DevBuf guest_send, guest_recv;  // u64: the guests' keys, host-major / the keys received, source-rank major
+  DevBuf guest_sorted;            // u64[guests_hosted]: the received keys in ascending order
+  int guest_scount[GHIP_MAXRANKS], guest_soff[GHIP_MAXRANKS];
   // what this shard itself met just before a collective decision, kept while its flag travels and raised as its
   // own error when all shards stop (ghip_dd_hold / ghip_dd_raise); consumed in the next phase: one slot is enough
   struct { int rc = 0; std::string msg; } held;
@@ -743,7 +757,8 @@ void ghip_dd_release(ghip_ctx *ctx);
 // left pending
 int ghip_dd_own_tree(ghip_ctx *ctx);
 int ghip_dd_post_groups(ghip_ctx *ctx, bool all, bool need_oldacc);
-int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp, const char *what);
+int ghip_dd_post_guests(ghip_ctx *ctx, const char *what);   // 1: the guest keys' exchange is pending, 0: no guests
+int ghip_dd_post_let(ghip_ctx *ctx, const ghip_grav_params &gp);
 // the operations of dd_ops[] (ghip_dd.hip; gravity, density, hydro and migration are static there): begin copies
 // its own params into DDState and makes its own checks, step returns what ghip_dd_step returns
 int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // sink.hip: the three sink ops

@@ -547,6 +547,8 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
 // GHIP_DD_POTENTIAL (ghip_dd_begin / ghip_dd_step): compute_potential() on a domain-decomposed shard.
 //   GROUPS   the shard's own tree, target groups over ALL its particles (the locally essential tree of the
 //            step's GHIP_DD_GRAVITY was selected against the active targets only)  -> all-gather of the groups
+//   GUESTS   with ghip_dd_set_guests, when any shard holds a guest: the guests' keys to their hosts
+//            (else straight on to LET)                                            -> all-to-all-v of u64 keys
 //   LET      selection of the locally essential trees under the opening rules of k_pot_walk, packed
 //                                                                                 -> all-to-all-v of LetRec
 //   WALK     the merged tree, the walk for the shard's own particles, the finish; what the walk met
@@ -568,18 +570,25 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
   hipStream_t st = ctx->stream;
   const int n = ctx->n;
   const bool mesh = p->pm.pmgrid > 0;
-  enum { GROUPS, LET, WALK, DEPOSIT, SOLVE };
+  enum { GROUPS, GUESTS, LET, WALK, DEPOSIT, SOLVE };
   if(D.phase == GROUPS)
     {
       ctx->pot_n = -1;
       GCHK(ghip_dd_own_tree(ctx));
       GCHK(ghip_dd_post_groups(ctx, true, p->grav.ErrTolTheta == 0));
-      D.phase = LET;
+      D.phase = GUESTS;
       return 1;
+    }
+  if(D.phase == GUESTS)
+    {
+      const int pending = ghip_dd_post_guests(ctx, "potential");
+      D.phase = LET;
+      if(pending != 0)
+        return pending;
     }
   if(D.phase == LET)
     {
-      GCHK(ghip_dd_post_let(ctx, p->grav, "potential"));
+      GCHK(ghip_dd_post_let(ctx, p->grav));
       D.phase = WALK;
       return 1;
     }
@@ -609,7 +618,7 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
       if(mesh && !p->grav.periodic)
         {
           // (the compact octant and its status word: a particle outside the region on any shard ends the
-          // call on all of them in phase 4)
+          // call on all of them in SOLVE)
           int outside = 0;
           GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
           ghip_dd_set_allgather(D, ghip_pmnp_block(ctx), ghip_pmnp_block_bytes(p->pm.pmgrid), &D.pm_all);

@@ -2595,6 +2595,9 @@ static int dd_prepare(void)
         return -1;
       DdReady = 1;
     }
+  /* cfg.accept_guests: records that drifted out of the rank's pieces since the last decomposition are legal */
+  if(chk(ghip_dd_set_guests(Ctx, Cfg.accept_guests != 0), "ghip_dd_set_guests"))
+    return -1;
   if(!RcclConnected && !AllgatherFn)
     return refuse(90002, "NTask = %d: call gadget_force_connect() (RCCL) or "
                          "gadget_force_set_allgather() first", NTask);

@@ -71,7 +71,8 @@ class Config(C.Structure):
     _fields_ = [("periodic", C.c_int), ("pmgrid", C.c_int), ("unequal_softenings", C.c_int),
                 ("device", C.c_int), ("black_holes", C.c_int), ("dust", C.c_int),
                 ("accretion_of_dust_only", C.c_int), ("accretion_density", C.c_int),
-                ("overlap_sph", C.c_int), ("dynamic_tree", C.c_int), ("pin_records", C.c_int)]
+                ("overlap_sph", C.c_int), ("dynamic_tree", C.c_int), ("pin_records", C.c_int),
+                ("accept_guests", C.c_int)]
 
 
 class BhLayout(C.Structure):
@@ -248,7 +249,7 @@ class Host:
 
     def __init__(self, periodic=1, pmgrid=0, unequal=0, device=0, black_holes=0, dust=0,
                  overlap_sph=0, accretion_of_dust_only=0, accretion_density=0, rank=0, nranks=1,
-                 pin_records=0, dynamic_tree=0):
+                 pin_records=0, dynamic_tree=0, accept_guests=0):
         self.L = lib()
         self.endrun_codes = []
         self._cb = ENDRUN_CB(lambda code: self.endrun_codes.append(code))
@@ -256,7 +257,7 @@ class Host:
         self._seti("ThisTask", rank)
         self._seti("NTask", nranks)
         cfg = Config(periodic, pmgrid, unequal, device, black_holes, dust, accretion_of_dust_only,
-                     accretion_density, overlap_sph, dynamic_tree, pin_records)
+                     accretion_density, overlap_sph, dynamic_tree, pin_records, accept_guests)
         rc = self.L.gadget_force_init(C.byref(cfg))
         if rc != 0:
             raise RuntimeError("gadget_force_init failed (%d): %s" %

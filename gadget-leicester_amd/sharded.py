@@ -169,6 +169,33 @@ def decompose(keys, nranks, work=None, level=None):
     return splits, owner
 
 
+def find_guests(keys, holder, splits=None, segments=None):
+    """The guests of a layout: particles whose Peano-Hilbert key lies outside every piece of the curve that
+    the rank holding them owns (ghip_dd_set_guests).  keys: uint64 keys; holder: the rank that holds each
+    particle; the layout as `splits` (nranks+1 keys, rank r owns [splits[r], splits[r+1])) or as
+    `segments` = (keys[nseg+1], owner[nseg]) (ghip_dd_set_segments).  A key equal to a boundary belongs to
+    the piece above it; an empty piece owns nothing.  Returns (guest_indices ascending, host_of_guest): the
+    host is the rank that owns the guest's key."""
+    keys = _np.ascontiguousarray(keys, _np.uint64)
+    holder = _np.asarray(holder, _np.int64)
+    if (splits is None) == (segments is None):
+        raise ValueError("find_guests: give the layout as splits or as segments")
+    if segments is not None:
+        bounds = _np.ascontiguousarray(segments[0], _np.uint64)
+        owner = _np.asarray(segments[1], _np.int64)
+    else:
+        bounds = _np.ascontiguousarray(splits, _np.uint64)
+        owner = _np.arange(len(bounds) - 1, dtype=_np.int64)
+    if len(bounds) != len(owner) + 1:
+        raise ValueError("find_guests: nseg + 1 keys for nseg owners")
+    # the last piece that starts at or before the key: empty pieces share their start with the next one,
+    # which side="right" steps over
+    piece = _np.searchsorted(bounds[:-1], keys, side="right") - 1
+    host = owner[piece]
+    guests = _np.nonzero(host != holder)[0]
+    return guests, host[guests].astype(_np.int32)
+
+
 class DomainShards:
     """All shards of a run as contexts of THIS process (one after the other on one GPU, or one per
     visible GPU): the parity-test and rehearsal form of the multi-GPU path.  Exchanges are
@@ -194,6 +221,12 @@ class DomainShards:
 
     def migrate(self):
         self.run(self.B.DD_MIGRATE, None)
+
+    def accept_guests(self, on=True):
+        """ghip_dd_set_guests on every shard: gravity and potential accept resident particles that left
+        their shard's pieces of the curve since the last migration"""
+        for p in self.paths:
+            p.dd_set_guests(on)
 
     def set_viscosity(self, params=None):
         """ghip_set_viscosity on every shard (the setting must be the same on all of them)"""
@@ -310,6 +343,10 @@ class DomainRank:
 
     def migrate(self):
         self._run(self.B.DD_MIGRATE, None)
+
+    def accept_guests(self, on=True):
+        """ghip_dd_set_guests on this rank; the caller gives every rank the same setting"""
+        self.p.dd_set_guests(on)
 
     def set_viscosity(self, params=None):
         """ghip_set_viscosity on this rank; the caller gives every rank the same setting"""

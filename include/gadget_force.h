@@ -293,6 +293,18 @@ struct gadget_force_config
                               are first uploaded (again when the arrays move or grow), so the record
                               copies run at the link's rate; released by gadget_force_finalize().  The
                               reference allocates both arrays once for All.MaxPart (allocate.c:30-60) */
+  int accept_guests;       /* NTask > 1.  0 (default): every record of a rank must lie inside the rank's
+                              DomainTask[] pieces of the curve when a driver is called, i.e. the host runs
+                              domain_Decomposition() before EVERY gravity_tree() / compute_potential(): a
+                              record that has drifted across a split ends the call on all ranks in endrun
+                              (the library's device invariant 2, value 5).  1: the drivers accept such
+                              records (ghip_dd_set_guests, include/ghip.h) -- the reference's own rule:
+                              between two decompositions (domain.c:115-135, TreeDomainUpdateFrequency) a
+                              particle stays in the memory of the rank that holds it.  gravity_tree(),
+                              density(), force_update_hmax(), hydro_force(), compute_potential() and the
+                              sink and dust collectives then give the single global tree's results for the
+                              current positions.  The same value on every rank.  (Last member: a host built
+                              against the shorter struct must zero-fill it -- `= {0}` does.) */
 };
 
 /* ---- globals with the reference's names (allvars.c) ---- */

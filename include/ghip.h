@@ -344,7 +344,8 @@ int ghip_dd_init(ghip_ctx *ctx, int rank, int nranks);
 int ghip_dd_set_domain(ghip_ctx *ctx, const double DomainCorner[3], const double DomainCenter[3],
                        double DomainLen, const double ForceSoftening[6]);
 /* nranks+1 Peano-Hilbert keys (21 bits per dimension): rank r owns [splits[r], splits[r+1]);
- * splits[0] = 0, splits[nranks] = 2^63.  Every resident particle must lie in its rank's range. */
+ * splits[0] = 0, splits[nranks] = 2^63.  Every resident particle must lie in its rank's range
+ * (unless ghip_dd_set_guests allows guests). */
 int ghip_dd_set_splits(ghip_ctx *ctx, const unsigned long long *splits);
 /* The general form, for decompositions in which a rank owns several pieces of the curve
  * (-DMULTIPLEDOMAINS > 1, domain.c:482-494, 1158-1215: DomainTask[] per top-leaf): nseg segments
@@ -363,6 +364,28 @@ int ghip_dd_find_split(int ncpu, int ndomain, const double *domainWork, int *sta
  * radius on any shard, all shards restore their starting Hsml, select ghosts again with
  * 1.26 x the worst growth seen and repeat the iteration (a collective decision). */
 int ghip_dd_set_ghost_margin(ghip_ctx *ctx, double margin);
+/* Guests.  A resident particle whose key lies outside every piece of the curve its shard owns is a GUEST of
+ * that shard; the shard that owns the key is its HOST.  A run that does not migrate before every force
+ * computation has them: the reference decomposes only every TreeDomainUpdateFrequency * TotNumPart force
+ * computations (domain.c:115-135) and in between a particle stays in the memory of the rank that holds it.
+ *   on = 0 (default)  every resident particle must lie in its shard's pieces: one that does not ends
+ *          GHIP_DD_GRAVITY and GHIP_DD_POTENTIAL on all shards (device invariant 2, value 5) -- the host
+ *          runs GHIP_DD_MIGRATE (or its own domain_exchange) before every call.
+ *   on = 1 guests are legal in GHIP_DD_GRAVITY and GHIP_DD_POTENTIAL, and so in the SPH, sink and dust
+ *          operations that follow them: results equal the single global tree of the current positions,
+ *          interaction and neighbour counts bit for bit.  The rule: a host may send a cell as ONE pruned
+ *          element only if its local moments are the cell's global moments, so a cell whose key range holds
+ *          the key of a guest held elsewhere is descended like a cell shared between shards.  Every shard
+ *          counts its guests (the count travels in the status record behind its group table); when any shard
+ *          holds one, one more exchange precedes the selection -- an all-to-all-v of 8-byte keys, each guest's
+ *          key to its host only; when nobody holds one, nothing more is exchanged than with on = 0.
+ * Set the same value on every rank (a collective setting, like the key ranges).  Invalidates nothing.
+ * A particle outside the domain cube stays an error (6).  GHIP_DD_MIGRATE and GHIP_DD_DECOMPOSE are
+ * unchanged: guests are what they exist to move. */
+int ghip_dd_set_guests(ghip_ctx *ctx, int on);
+/* out[0]: guests resident on this shard in its last GHIP_DD_GRAVITY / GHIP_DD_POTENTIAL, out[1]: guest keys
+ * it received as their host (both 0 with the mode off) */
+int ghip_dd_guest_counts(const ghip_ctx *ctx, long long out[2]);
 /* RCCL: rank 0 creates the id (128 bytes) and the host broadcasts it (MPI_Bcast in the reference's
  * world); every rank then connects.  The library binds the librccl that sits next to the HIP
  * runtime the process uses (ghip_dd_rccl_library tells which). */
