@@ -109,6 +109,44 @@ class DustParams(C.Structure):
                 ("UnitDensity_in_cgs", C.c_double), ("UnitVelocity_in_cm_per_s", C.c_double)]
 
 
+class DustModel(C.Structure):
+    """ghip_dust_model: the physics switches of the dust passes (ghip_set_dust_model, include/ghip.h)"""
+    _fields_ = [(k, C.c_int) for k in ("growth", "real_pebble_collisions", "vaporize", "fe_and_ice_grains",
+                                        "epstein", "no_friction_heating")] + \
+        [(k, C.c_double) for k in ("Time", "VirtualTime", "FragmentationVelocity", "InitialDustRadius",
+                                   "UnitEnergy_in_cgs")]
+
+
+class DustGrains(C.Structure):
+    """ghip_dust_grains: the arrays of a grain list (include/ghip.h)"""
+    _fields_ = [("ndust", C.c_int), ("dust_idx", C.c_void_p), ("particle_density", C.c_void_p),
+                ("dust_density", C.c_void_p), ("dust_entropy", C.c_void_p), ("dust_gasvel", C.c_void_p),
+                ("dust_radius", C.c_void_p), ("particle_velocity", C.c_void_p), ("delta_momentum", C.c_void_p),
+                ("delta_energy", C.c_void_p), ("vcoll", C.c_void_p), ("log_radius_by_dt", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
+def dust_grains(dust, particle_density=None, dust_density=None, dust_entropy=None, dust_gasvel=None,
+                dust_radius=None, particle_velocity=None, vcoll=None, log_radius_by_dt=None, logr=True):
+    """(DustGrains, arrays): the struct and the dict of numpy arrays it points into -- inputs copied, outputs
+    allocated; logr = False leaves log_radius_by_dt NULL.  Keep `arrays` alive while the struct is used."""
+    nd = len(dust)
+    f64 = lambda v, shape: np.zeros(shape) if v is None else \
+        np.ascontiguousarray(v, np.float64).reshape(shape).copy()
+    a = dict(dust_idx=np.ascontiguousarray(dust, np.int32), particle_density=f64(particle_density, nd),
+             dust_density=f64(dust_density, nd), dust_entropy=f64(dust_entropy, nd),
+             dust_gasvel=f64(dust_gasvel, (nd, 3)), dust_radius=f64(dust_radius, nd),
+             particle_velocity=f64(particle_velocity, (nd, 3)), delta_momentum=np.zeros((nd, 3)),
+             delta_energy=np.zeros(nd), vcoll=f64(vcoll, nd), counts=np.zeros(4, np.int64))
+    if logr:
+        a["log_radius_by_dt"] = f64(log_radius_by_dt, nd)
+    g = DustGrains()
+    g.ndust = nd
+    for k, v in a.items():
+        setattr(g, k, v.ctypes.data)
+    return g, a
+
+
 class IntegrationFlags(C.Structure):
     """ghip_integration_flags: the shipped bundle's rules of get_timestep / do_the_kick /
     drift_particle (include/ghip.h)"""
@@ -294,6 +332,8 @@ EXPORTS = [
     "ghip_potential_interactions", "ghip_get_potential_interactions", "ghip_global_quantities",
     "ghip_dd_bytes_sent", "ghip_dd_get_splits", "ghip_dd_get_domain",
     "ghip_pm_find_region", "ghip_pm_set_region", "ghip_pm_get_region", "ghip_pm_nonperiodic",
+    "ghip_set_dust_model", "ghip_dust_model_size", "ghip_dust_grains_size", "ghip_dust_density_grains",
+    "ghip_dust_drag_grains",
     "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
     "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts"]
 
@@ -403,6 +443,14 @@ def lib():
         L.ghip_dust_density.argtypes = [vp, C.POINTER(DustParams), C.c_int, vp, vp]
         L.ghip_dust_drag.argtypes = [vp, C.POINTER(DustParams), C.c_int] + [vp] * 10
         L.ghip_dust_get_drag_heating.argtypes = [vp, vp]
+        L.ghip_set_dust_model.argtypes = [vp, C.POINTER(DustModel)]
+        L.ghip_dust_density_grains.argtypes = [vp, C.POINTER(DustParams), C.POINTER(DustGrains)]
+        L.ghip_dust_drag_grains.argtypes = [vp, C.POINTER(DustParams), C.POINTER(DustGrains)]
+        for fn, cls in ((L.ghip_dust_model_size, DustModel), (L.ghip_dust_grains_size, DustGrains)):
+            fn.argtypes = []
+            fn.restype = C.c_size_t
+            if fn() != C.sizeof(cls):
+                raise RuntimeError("%s: %d bytes here, %d in libghip.so" % (cls.__name__, C.sizeof(cls), fn()))
         L.ghip_dust_set_drag_heating.argtypes = [vp, vp]
         L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
         L.ghip_find_smbh.argtypes = [vp, C.c_double, vp, C.POINTER(C.c_int)]
@@ -951,6 +999,29 @@ class ForcePath:
                                         _ptr(out["delta_energy"]), _ptr(out["vcoll"])))
         return out
 
+    def set_dust_model(self, model=None):
+        """DustModel or None (the shipped bundle: no switch); governs both dust passes, on one rank and on
+        shards"""
+        self._chk(self.L.ghip_set_dust_model(self.h, None if model is None else C.byref(model)))
+
+    def dust_density_grains(self, params, dust):
+        """-> dict(particle_density, particle_velocity): d7 and, with real_pebble_collisions, the raw d9 sums
+        (left at zero otherwise)"""
+        g, a = dust_grains(dust)
+        self._chk(self.L.ghip_dust_density_grains(self.h, C.byref(params), C.byref(g)))
+        return dict(particle_density=a["particle_density"], particle_velocity=a["particle_velocity"])
+
+    def dust_drag_grains(self, params, dust, dust_density, dust_entropy, dust_gasvel, dust_radius,
+                         particle_density, particle_velocity, vcoll, log_radius_by_dt=None, logr=True):
+        """-> dict(particle_velocity, delta_momentum, delta_energy, vcoll, dust_radius, log_radius_by_dt); the
+        in/out arrays are copies.  logr = False passes log_radius_by_dt = NULL."""
+        g, a = dust_grains(dust, particle_density, dust_density, dust_entropy, dust_gasvel, dust_radius,
+                           particle_velocity, vcoll, log_radius_by_dt, logr)
+        assert a["dust_gasvel"].shape == (len(a["dust_idx"]), 3)
+        self._chk(self.L.ghip_dust_drag_grains(self.h, C.byref(params), C.byref(g)))
+        return {k: a[k] for k in ("particle_velocity", "delta_momentum", "delta_energy", "vcoll", "dust_radius",
+                                  "log_radius_by_dt") if k in a}
+
     def dust_drag_heating(self):
         dh = np.zeros(self.ngas)
         self._chk(self.L.ghip_dust_get_drag_heating(self.h, _ptr(dh)))
@@ -1161,6 +1232,7 @@ DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 DD_DECOMPOSE = 13
 DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
+DUST_GRAINS_FORM = 1     # `walk` of dd_begin / dd_run for DD_DUST_DENSITY / DD_DUST_DRAG with DdDustGrainsArgs
 
 
 class DdSinkArgs(C.Structure):
@@ -1230,6 +1302,22 @@ def dd_dust_args(params, dust, particle_density=None, dust_density=None, dust_en
     for k in ("dust_idx", "particle_density", "dust_density", "dust_entropy", "dust_gasvel", "dust_radius",
               "particle_velocity", "delta_momentum", "delta_energy", "vcoll", "counts"):
         setattr(A, k, a[k].ctypes.data)
+    return A, a
+
+
+class DdDustGrainsArgs(C.Structure):
+    """ghip_dd_dust_grains_args (include/ghip.h): the dust passes on a shard with the arrays of DustGrains"""
+    _fields_ = [("p", C.POINTER(DustParams)), ("g", DustGrains)]
+
+
+def dd_dust_grains_args(params, dust, **arrays):
+    """(args, arrays) for GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG begun with walk = DUST_GRAINS_FORM:
+    dust_grains() with the params; keep `arrays` alive until the operation has finished."""
+    g, a = dust_grains(dust, **arrays)
+    a["_params"] = params
+    A = DdDustGrainsArgs()
+    A.p = C.pointer(params)
+    A.g = g
     return A, a
 
 

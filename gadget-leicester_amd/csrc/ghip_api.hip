@@ -420,6 +420,7 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
     {
       ctx->pot_n = -1;      // (the potential of ghip_potential belongs to the particle set it was made for)
       ctx->visc_ngas = -1;  // (... and alpha / Dtalpha of ghip_visc_set_alpha too)
+      ctx->id_given = false;
     }
   ctx->n = numpart;
   ctx->ngas = ngas;
@@ -517,6 +518,8 @@ extern "C" int ghip_set_field(ghip_ctx *ctx, int field, const void *host)
       HIPCHK(hipGetLastError());
     }
   HIPCHK(ghip_stream_sync(ctx, st));
+  if(field == GHIP_F_ID)
+    ctx->id_given = true;
   if(field == GHIP_F_POS || field == GHIP_F_MASS || field == GHIP_F_TYPE)
     {
       ctx->gt.built = false;

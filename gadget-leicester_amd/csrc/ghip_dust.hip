@@ -1,12 +1,14 @@
 // ghip_dust.hip -- the dust-gas drag passes of the reference's shipped flag bundle (DUST, DUST_TIMESTEP,
-// DUST_POWERLAW, DOUBLEPRECISION, CONSTANT_MEAN_MOLECULAR_WEIGHT; none of the DUST_GROWTH*,
-// DUST_VAPORIZE, DUST_TWO_POPULATIONS, DUST_REAL_PEBBLE_COLLISIONS, DUST_EPSTEIN,
-// DUST_NO_FRICTION_HEATING sub-flags), called by compute_accelerations() right after
-// blackhole_accretion() (accel.c:194, 198).
+// DUST_POWERLAW, DOUBLEPRECISION, CONSTANT_MEAN_MOLECULAR_WEIGHT), called by compute_accelerations()
+// right after blackhole_accretion() (accel.c:194, 198).  The physics switches DUST_GROWTH,
+// DUST_REAL_PEBBLE_COLLISIONS, DUST_VAPORIZE, DUST_FE_AND_ICE_GRAINS, DUST_EPSTEIN and
+// DUST_NO_FRICTION_HEATING are a run-time setting of the context (ghip_set_dust_model): kernel
+// instantiations of their own, the default ones untouched.  Not built: DUST_TWO_POPULATIONS,
+// DUST_GROWTH_FIXED_SIZE, DUST_MDUST_GROW, DUST_2ND_POPULATION, DUST_PEBBLES_BORN, DUST_SINK_ON_FLY.
 //
 // Replaces the particle loops of
 //   dust_density / dust_evaluate_density         dust.c:60-261, 748-887
-//   dust_drag, the per-grain update              dust.c:263-446
+//   dust_drag, the per-grain update              dust.c:263-446 (:449-609 with ghip_set_dust_model)
 //   dust_drag / dust_evaluate_select (scatter)   dust.c:889-1029
 //   ngb_treefind_dust_active                     dust.c:1235-1333
 //
@@ -50,6 +52,34 @@ struct DustK
   BoxK b;
   double dt_fac, dt_fac_gas, minegy, meanweight, ulength, umass, udens, uvel;
 };
+
+// ghip_set_dust_model: what the k_dust_grain<DustM> instantiation gets beyond DustK.  Wave-uniform: every
+// test of a switch is a scalar branch.
+#define DUST_A_MIN 0.1     // adust_min, adust_max [cm], dust.c:277
+#define DUST_A_MAX 1.e5
+struct DustM
+{
+  int growth, pebble, vaporize, fe_ice, epstein, no_heat;
+  int gate;            // All.Time > 0 && All.Time > All.VirtualTime (dust.c:453)
+  double vfrag, a_init, uenergy;
+  const int *id;       // GHIP_F_ID (fe_ice)
+  double *logr;        // LogDustRadius_by_dt [nd] in list order, or nullptr
+};
+
+// DUST_REAL_PEBBLE_COLLISIONS in the density pass: the velocities gathered, and where grain a's four sums
+// (d7, d9 [3]) go: o[a * sa + c * sc] -- planes for a shard's own list, records of four for imported grains
+struct DustVel
+{
+  const double *vel;
+  double *o;
+  size_t sa, sc;
+};
+
+template <class T>
+__device__ __forceinline__ const T &d_only(const T &t)
+{
+  return t;
+}
 
 // the neighbour test and kernel weight of dust_evaluate_density / _select (dust.c:826-847, 971-983):
 // r <= h from the tree search, then u = r / h < 1.  Returns false for a non-neighbour.
@@ -121,14 +151,17 @@ __global__ void k_dust_order_keys(int nd, const int *__restrict__ idx, const int
 // PPP[target].Mass -- a reference quirk kept as it is: the result is m_i * sum_j W_ij, not a density of
 // the neighbours' mass; an imported grain brings its mass in the record).  Candidates are this context's
 // own particles: imported elements of a shard's merged tree (perm >= n) are skipped.  ord: the launch
-// order of the grains (nullptr: as given)
-template <class G>
+// order of the grains (nullptr: as given).  V... is empty for the default kernel (same signature, same code
+// as before ghip_set_dust_model existed) and one DustVel for DUST_REAL_PEBBLE_COLLISIONS: d9[k] += m_i W
+// Vel_j[k] over the same neighbours (dust.c:851-853), the four sums written through the DustVel
+template <class G, class... V>
 __global__ void __launch_bounds__(64)
 k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__restrict__ pos,
                const double *__restrict__ mass, const int *__restrict__ type, int nelem,
                const int4 *__restrict__ lk, const double4 *__restrict__ cl, const int *__restrict__ perm,
-               BoxK b, double *__restrict__ out)
+               BoxK b, double *__restrict__ out, V... v)
 {
+  constexpr bool VELS = sizeof...(V) > 0;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= nd)
     return;
@@ -136,22 +169,55 @@ k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__
   double px, py, pz, h, mi;
   g.get(a, px, py, pz, h, mi);
   double rho = 0;
-  d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
-    const int j = perm[p];
-    if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
-      return;
-    double wk;
-    if(d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
-      rho += mi * wk;
-  });
-  out[a] = rho;
+  if constexpr(VELS)
+    {
+      const DustVel &dv = d_only(v...);
+      const double *__restrict__ vel = dv.vel;
+      double s0 = 0, s1 = 0, s2 = 0;
+      d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
+        const int j = perm[p];
+        if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
+          return;
+        double wk;
+        if(d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
+          {
+            const double mw = mi * wk;
+            rho += mw;
+            s0 += mw * vel[j];
+            s1 += mw * vel[(size_t) n + j];
+            s2 += mw * vel[2 * (size_t) n + j];
+          }
+      });
+      double *o = dv.o + (size_t) a * dv.sa;
+      o[0] = rho;
+      o[dv.sc] = s0;
+      o[2 * dv.sc] = s1;
+      o[3 * dv.sc] = s2;
+    }
+  else
+    {
+      d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
+        const int j = perm[p];
+        if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
+          return;
+        double wk;
+        if(d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
+          rho += mi * wk;
+      });
+      out[a] = rho;
+    }
 }
 
-// dust_drag, the per-grain part (dust.c:303-446), one thread per grain of the list
+// dust_drag, the per-grain part (dust.c:303-446), one thread per grain of the list.  M... is empty for the
+// default kernel (same signature, same code as before ghip_set_dust_model existed) and one DustM for the
+// instantiation with the switches, which goes on to dust.c:449-609: growth and fragmentation, vaporisation
+// of rock and ice, the radius update with its clamps and the latent heat
+template <class... M>
 __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const int *__restrict__ timebin,
                              const double *__restrict__ mass, const double *__restrict__ grav,
-                             double *__restrict__ vel, double *__restrict__ w, DustK K)
+                             double *__restrict__ vel, double *__restrict__ w, DustK K, M... m)
 {
+  constexpr bool MODEL = sizeof...(M) > 0;
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if(a >= nd)
     return;
@@ -194,7 +260,10 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
       const double lambda_h2 = K.meanweight * PROTONMASS / (K.udens * rho) / 1.e-15 / K.ulength;
       const double rey = 6 * delta_vel * R / K.ulength / (lambda_h2 * soundspeed);
       double ts;
-      if(3. / 2 * lambda_h2 * K.ulength >= R)   // Epstein
+      bool epstein = 3. / 2 * lambda_h2 * K.ulength >= R;
+      if constexpr(MODEL)
+        epstein = epstein || d_only(m...).epstein;   // DUST_EPSTEIN, dust.c:415-416
+      if(epstein)   // Epstein
         ts = 1. / (rho * soundspeed / (DUST_RHO_GRAIN * R) * K.umass / K.ulength / K.ulength);
       else if(delta_vel > 0)   // Stokes, C_drag of Weidenschilling 1977
         {
@@ -218,11 +287,76 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
           const double vnew = vsteady + (vold - vsteady) * e1 + g[k] * ts * (1. - e1);
           const double vnew_nog = vold + g[k] * dt;
           PL(DP_DMOM + k) = 0. - mass[i] * (vnew_nog - vnew);
-          de += mass[i] * ((vnew - vsteady) * (vnew - vsteady)) * (1. - e2) / 2.;
+          if constexpr(MODEL)
+            {
+              if(!d_only(m...).no_heat)   // DUST_NO_FRICTION_HEATING, dust.c:433-435
+                de += mass[i] * ((vnew - vsteady) * (vnew - vsteady)) * (1. - e2) / 2.;
+            }
+          else
+            de += mass[i] * ((vnew - vsteady) * (vnew - vsteady)) * (1. - e2) / 2.;
           vel[k * N + i] = vnew;
         }
       vcoll = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) * ts * K.uvel / 1.e2;
       vcoll += 0.2;
+    }
+  if constexpr(MODEL)
+    {
+      const DustM &mm = d_only(m...);
+      if(mm.growth)   // dust.c:451-609 (vaporize needs growth: ghip_set_dust_model)
+        {
+          const double old_a = PL(DP_RAD);
+          double adot = 0.;
+          if(mm.gate && d7 > 0.)   // :453, 461: with the FINAL DustVcoll of this call
+            {
+              const double t_coll = 4. * (DUST_RHO_GRAIN / K.udens) * (old_a / K.ulength) / d7 /
+                                    (vcoll * 1.e2 / K.uvel + 1.e-20);
+              if(mm.logr)
+                mm.logr[a] = t_coll;
+              adot = old_a / K.ulength / 3. / t_coll;
+              if(mm.pebble)   // growth turns into fragmentation at high collision speeds, :479-490
+                {
+                  if(mm.vfrag < 0.1)
+                    adot = 0.;
+                  else
+                    {
+                      const double xcoll = vcoll / mm.vfrag;
+                      adot *= (1 - xcoll * xcoll) / (1 + xcoll * xcoll);
+                    }
+                }
+            }
+          double latent = 1.e11;   // rocks, erg/g (:268)
+          if(mm.vaporize)
+            {
+              const bool ice = mm.fe_ice && (mm.id[i] & 1);   // P[].ID % 2, :509
+              if(ice)
+                latent = 4.e10;
+              if(rho > 0.)   // :501
+                {
+                  const double csu = soundspeed * K.uvel;
+                  const double T = M_PI / 8. * (csu * csu) * K.meanweight * PROTONMASS / BOLTZMANN;
+                  double pvap;
+                  if(!ice)
+                    pvap = pow(10., (-24605. / T + 13.176));   // rocks, Podolak et al 1988
+                  else if(T <= 600.)
+                    pvap = pow(10., (11.6 - 2104. / T));
+                  else
+                    pvap = 5. + 5.2e-3 * T;
+                  adot -= 1. / (DUST_RHO_GRAIN * sqrt(2. * 3.1415)) / soundspeed / K.uvel * pvap / K.uvel;
+                }
+            }
+          double new_a = old_a + (adot * dt) * K.ulength;   // :551
+          if(new_a < DUST_A_MIN)   // :566-567, for every grain of the list
+            new_a = DUST_A_MIN;
+          if(new_a > DUST_A_MAX)
+            new_a = DUST_A_MAX;
+          PL(DP_RAD) = new_a;
+          if(mm.vaporize)   // :533-548, 591-608: takes heat from the gas where grains vaporise
+            {
+              const double old_l = latent * (old_a - DUST_A_MIN) / (mm.a_init - DUST_A_MIN);
+              const double new_l = latent * (new_a - DUST_A_MIN) / (mm.a_init - DUST_A_MIN);
+              de += (new_l - old_l) * mass[i] * K.umass / mm.uenergy;
+            }
+        }
     }
   PL(DP_DE) = de;
   PL(DP_VCOLL) = vcoll;
@@ -367,6 +501,18 @@ __global__ void k_dust_add_parts(int cnt, const int *__restrict__ list, const in
     out[slot[list[k]]] += part[k];
 }
 
+// DUST_REAL_PEBBLE_COLLISIONS: the partial {d7, d9 [3]} records one rank sent back onto the four planes
+__global__ void k_dust_add_parts4(int cnt, const int *__restrict__ list, const int *__restrict__ slot,
+                                  const double *__restrict__ part, size_t nd, double *__restrict__ out)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if(k >= cnt)
+    return;
+  const size_t a = (size_t) slot[list[k]];
+  for(int c = 0; c < 4; c++)
+    out[c * nd + a] += part[4 * (size_t) k + c];
+}
+
 // the planes k_dust_apply reads, over this shard's grains [0, nd) and the imported ones [nd, nd + nimp)
 __global__ void k_dust_combine(int nd, int nimp, const double *__restrict__ w, const double *__restrict__ rec,
                                double *__restrict__ cw)
@@ -409,6 +555,49 @@ static DustK dust_k(const ghip_dust_params *p)
   K.udens = p->UnitDensity_in_cgs;
   K.uvel = p->UnitVelocity_in_cm_per_s;
   return K;
+}
+
+// the switches of ghip_set_dust_model as the kernel takes them; logr: the device plane of LogDustRadius_by_dt
+static DustM dust_m(ghip_ctx *ctx, double *logr)
+{
+  const ghip_dust_model &s = ctx->dust_model;
+  DustM m;
+  m.growth = s.growth != 0;
+  m.pebble = s.real_pebble_collisions != 0;
+  m.vaporize = s.vaporize != 0;
+  m.fe_ice = s.fe_and_ice_grains != 0;
+  m.epstein = s.epstein != 0;
+  m.no_heat = s.no_friction_heating != 0;
+  m.gate = s.Time > 0 && s.Time > s.VirtualTime;
+  m.vfrag = s.FragmentationVelocity;
+  m.a_init = s.InitialDustRadius;
+  m.uenergy = s.UnitEnergy_in_cgs;
+  m.id = P<int>(ctx->f[GHIP_F_ID]);
+  m.logr = logr;
+  return m;
+}
+
+static bool dust_pebble(const ghip_ctx *ctx) { return ctx->dust_model_on && ctx->dust_model.real_pebble_collisions; }
+static bool dust_growth(const ghip_ctx *ctx) { return ctx->dust_model_on && ctx->dust_model.growth; }
+
+// What a pass asks of the setting before it launches anything.  grains: the caller came through
+// ghip_dust_grains (the *_grains entry points, GHIP_DUST_GRAINS_FORM on shards) and has arrays for what the switches
+// write; `other` names that way for a caller who did not
+static int dust_model_ready(ghip_ctx *ctx, bool drag, bool grains, const char *who, const char *other)
+{
+  if(!ctx->dust_model_on)
+    return GHIP_OK;
+  const ghip_dust_model &s = ctx->dust_model;
+  if(!grains && !drag && s.real_pebble_collisions)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: real_pebble_collisions is set (ghip_set_dust_model) and this entry "
+                     "point has no array for the velocity sums d9: use %s", who, other);
+  if(!grains && drag && (s.growth || s.vaporize))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: growth / vaporize is set (ghip_set_dust_model) and this entry point "
+                     "cannot write the radius: use %s", who, other);
+  if(drag && s.fe_and_ice_grains && !ctx->id_given)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: fe_and_ice_grains reads the particles' IDs, and GHIP_F_ID has not "
+                     "been given since ghip_set_counts (ghip_set_field)", who);
+  return GHIP_OK;
 }
 
 static int dust_heat_buffer(ghip_ctx *ctx)
@@ -474,7 +663,7 @@ static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const in
 static int dust_upload_planes(ghip_ctx *ctx, int nd, const double *dust_density, const double *dust_entropy,
                               const double *dust_gasvel, const double *dust_radius,
                               const double *particle_density, const double *particle_velocity,
-                              const double *vcoll, std::vector<double> &h)
+                              const double *vcoll, const double *logr, std::vector<double> &h)
 {
   const size_t D = (size_t) nd;
   h.assign((size_t) DUST_NPLANES * D, 0.0);
@@ -492,18 +681,80 @@ static int dust_upload_planes(ghip_ctx *ctx, int nd, const double *dust_density,
         }
     }
   // dust_work: planes [DUST_NPLANES][nd] | cnt [nd + 1] | off [nd + 1]   (64-bit)
-  GCHK(ghip_ensure(ctx, ctx->dust_work, (DUST_NPLANES * D + 2 * (D + 1)) * 8 + 256));
+  //            | LogDustRadius_by_dt [nd] when the model writes it (growth and the caller holds the array)
+  const bool lr = logr && dust_growth(ctx);
+  GCHK(ghip_ensure(ctx, ctx->dust_work, (DUST_NPLANES * D + 2 * (D + 1) + (lr ? D : 0)) * 8 + 256));
   HIPCHK(hipMemcpyAsync(ctx->dust_work.p, h.data(), DUST_NIN * D * 8, hipMemcpyHostToDevice, ctx->stream));
+  if(lr)
+    HIPCHK(hipMemcpyAsync(P<double>(ctx->dust_work) + DUST_NPLANES * D + 2 * (D + 1), logr, D * 8,
+                          hipMemcpyHostToDevice, ctx->stream));
   return GHIP_OK;
 }
 
-static void dust_run_grains(ghip_ctx *ctx, int nd, const DustK &K)
+// logr: the caller holds a LogDustRadius_by_dt array (uploaded by dust_upload_planes)
+static void dust_run_grains(ghip_ctx *ctx, int nd, const DustK &K, bool logr)
 {
-  k_dust_grain<<<cdiv(nd, 256), 256, 0, ctx->stream>>>(nd, P<int>(ctx->dust_idx), ctx->n,
-                                                       P<int>(ctx->f[GHIP_F_TIMEBIN]),
-                                                       P<double>(ctx->f[GHIP_F_MASS]),
-                                                       P<double>(ctx->f[GHIP_F_GRAVACCEL]),
-                                                       P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K);
+  if(ctx->dust_model_on)
+    {
+      const size_t D = (size_t) nd;
+      double *dl = logr && dust_growth(ctx) ? P<double>(ctx->dust_work) + DUST_NPLANES * D + 2 * (D + 1) : nullptr;
+      k_dust_grain<DustM><<<cdiv(nd, 256), 256, 0, ctx->stream>>>(
+        nd, P<int>(ctx->dust_idx), ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(ctx->f[GHIP_F_MASS]),
+        P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K,
+        dust_m(ctx, dl));
+      return;
+    }
+  k_dust_grain<><<<cdiv(nd, 256), 256, 0, ctx->stream>>>(nd, P<int>(ctx->dust_idx), ctx->n,
+                                                         P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                                         P<double>(ctx->f[GHIP_F_MASS]),
+                                                         P<double>(ctx->f[GHIP_F_GRAVACCEL]),
+                                                         P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K);
+}
+
+// the density sums of this context's own list: d7 into dust_work [nd], or with real_pebble_collisions d7 and the
+// three velocity sums into its first four planes
+static int dust_run_density(ghip_ctx *ctx, const ghip_dust_params *p, int nd)
+{
+  TreeDev &t = ctx->gt;
+  const size_t D = (size_t) nd;
+  const bool vels = dust_pebble(ctx);
+  GCHK(ghip_ensure(ctx, ctx->dust_work, (vels ? 4 : 1) * D * 8 + 256));
+  double *dout = P<double>(ctx->dust_work);
+  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
+  const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, mass, nullptr};
+  if(vels)
+    k_dust_density<<<cdiv(nd, 64), 64, 0, ctx->stream>>>(
+      nd, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
+      P<int>(t.perm), make_box(p->BoxSize, p->periodic), (double *) nullptr,
+      DustVel{P<double>(ctx->f[GHIP_F_VEL]), dout, 1, D});
+  else
+    k_dust_density<<<cdiv(nd, 64), 64, 0, ctx->stream>>>(nd, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                         t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
+                                                         make_box(p->BoxSize, p->periodic), dout);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// ... and back to the caller: d7 [nd], and the raw d9 sums [nd][3] with real_pebble_collisions
+static int dust_download_density(ghip_ctx *ctx, int nd, double *particle_density, double *particle_velocity)
+{
+  const size_t D = (size_t) nd;
+  const double *dout = P<double>(ctx->dust_work);
+  if(!dust_pebble(ctx))
+    {
+      HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+      return GHIP_OK;
+    }
+  std::vector<double> h(3 * D);
+  HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h.data(), dout + D, 3 * D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(size_t a = 0; a < D; a++)
+    for(int k = 0; k < 3; k++)
+      particle_velocity[3 * a + k] = h[k * D + a];
+  return GHIP_OK;
 }
 
 // The scatter into this context's gas: count, scan, fill, sort, apply.  Grains [0, nd) are the list's
@@ -574,13 +825,19 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
 }
 
 // the grain outputs of the drag pass back to the caller's arrays
+// (radius, logr: the planes the model writes under growth, nullptr where the caller has no array for them)
 static int dust_download_grains(ghip_ctx *ctx, int nd, std::vector<double> &h, double *particle_velocity,
-                                double *delta_momentum, double *delta_energy, double *vcoll)
+                                double *delta_momentum, double *delta_energy, double *vcoll,
+                                double *radius = nullptr, double *logr = nullptr)
 {
   const size_t D = (size_t) nd;
   const double *dw = P<double>(ctx->dust_work);
   HIPCHK(hipMemcpyAsync(h.data() + DP_D9 * D, dw + DP_D9 * D, DUST_NOUT * D * 8, hipMemcpyDeviceToHost,
                         ctx->stream));
+  if(dust_growth(ctx) && radius)
+    HIPCHK(hipMemcpyAsync(radius, dw + DP_RAD * D, D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if(dust_growth(ctx) && logr)
+    HIPCHK(hipMemcpyAsync(logr, dw + DUST_NPLANES * D + 2 * (D + 1), D * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   for(size_t a = 0; a < D; a++)
     {
@@ -595,32 +852,59 @@ static int dust_download_grains(ghip_ctx *ctx, int nd, std::vector<double> &h, d
   return GHIP_OK;
 }
 
+// the two passes on one rank, for the old entry points (grains = false) and the *_grains ones
+static int dust_density_impl(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains &g, bool grains,
+                             const char *who)
+{
+  GHIP_JOIN(ctx);
+  if(g.ndust > 0 && (!g.particle_density || (grains && dust_pebble(ctx) && !g.particle_velocity)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  GCHK(dust_model_ready(ctx, false, grains, who, "ghip_dust_density_grains"));
+  GCHK(dust_begin(ctx, p, g.ndust, g.dust_idx, false, who));
+  if(g.ndust == 0)
+    return GHIP_OK;
+  GCHK(dust_run_density(ctx, p, g.ndust));
+  return dust_download_density(ctx, g.ndust, g.particle_density, g.particle_velocity);
+}
+
+static int dust_drag_impl(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains &g, bool grains,
+                          const char *who)
+{
+  GHIP_JOIN(ctx);
+  const int ndust = g.ndust;
+  if(ndust > 0 && (!g.dust_density || !g.dust_entropy || !g.dust_gasvel || !g.dust_radius || !g.particle_density ||
+                   !g.particle_velocity || !g.delta_momentum || !g.delta_energy || !g.vcoll))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  GCHK(dust_model_ready(ctx, true, grains, who, "ghip_dust_drag_grains"));
+  GCHK(dust_begin(ctx, p, ndust, g.dust_idx, ctx->ngas > 0, who));
+  GCHK(dust_heat_buffer(ctx));
+  if(ndust == 0)
+    return GHIP_OK;
+  const size_t D = (size_t) ndust;
+  const DustK K = dust_k(p);
+  std::vector<double> h;
+  GCHK(dust_upload_planes(ctx, ndust, g.dust_density, g.dust_entropy, g.dust_gasvel, g.dust_radius,
+                          g.particle_density, g.particle_velocity, g.vcoll, g.log_radius_by_dt, h));
+  dust_run_grains(ctx, ndust, K, g.log_radius_by_dt != nullptr);
+  HIPCHK(hipGetLastError());
+  double *dw = P<double>(ctx->dust_work);
+  long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
+  long long npairs = 0;
+  GCHK(dust_scatter(ctx, K, ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
+  return dust_download_grains(ctx, ndust, h, g.particle_velocity, g.delta_momentum, g.delta_energy, g.vcoll,
+                              grains ? g.dust_radius : nullptr, g.log_radius_by_dt);
+}
+
 extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
                                  double *particle_density)
 {
   if(!ctx)
     return GHIP_EINVAL;
-  GHIP_JOIN(ctx);
-  if(ndust > 0 && !particle_density)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_density: bad arguments");
-  GCHK(dust_begin(ctx, p, ndust, dust_idx, false, "ghip_dust_density"));
-  if(ndust == 0)
-    return GHIP_OK;
-  hipStream_t st = ctx->stream;
-  TreeDev &t = ctx->gt;
-  const size_t D = (size_t) ndust;
-  GCHK(ghip_ensure(ctx, ctx->dust_work, D * 8 + 256));
-  double *dout = P<double>(ctx->dust_work);
-  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
-  const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
-  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, mass, nullptr};
-  k_dust_density<<<cdiv(ndust, 64), 64, 0, st>>>(ndust, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                 t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                 make_box(p->BoxSize, p->periodic), dout);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  return GHIP_OK;
+  ghip_dust_grains g = {};
+  g.ndust = ndust;
+  g.dust_idx = dust_idx;
+  g.particle_density = particle_density;
+  return dust_density_impl(ctx, p, g, false, "ghip_dust_density");
 }
 
 extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
@@ -631,27 +915,75 @@ extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndus
 {
   if(!ctx)
     return GHIP_EINVAL;
-  GHIP_JOIN(ctx);
-  if(ndust > 0 && (!dust_density || !dust_entropy || !dust_gasvel || !dust_radius || !particle_density ||
-                   !particle_velocity || !delta_momentum || !delta_energy || !vcoll))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_drag: bad arguments");
-  GCHK(dust_begin(ctx, p, ndust, dust_idx, ctx->ngas > 0, "ghip_dust_drag"));
-  GCHK(dust_heat_buffer(ctx));
-  if(ndust == 0)
-    return GHIP_OK;
-  const size_t D = (size_t) ndust;
-  const DustK K = dust_k(p);
-  std::vector<double> h;
-  GCHK(dust_upload_planes(ctx, ndust, dust_density, dust_entropy, dust_gasvel, dust_radius, particle_density,
-                          particle_velocity, vcoll, h));
-  dust_run_grains(ctx, ndust, K);
-  HIPCHK(hipGetLastError());
-  double *dw = P<double>(ctx->dust_work);
-  long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
-  long long npairs = 0;
-  GCHK(dust_scatter(ctx, K, ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
-  return dust_download_grains(ctx, ndust, h, particle_velocity, delta_momentum, delta_energy, vcoll);
+  ghip_dust_grains g = {};
+  g.ndust = ndust;
+  g.dust_idx = dust_idx;
+  g.dust_density = dust_density;
+  g.dust_entropy = dust_entropy;
+  g.dust_gasvel = dust_gasvel;
+  g.dust_radius = const_cast<double *>(dust_radius);   // (read only: the switches that write it are refused here)
+  g.particle_density = const_cast<double *>(particle_density);
+  g.particle_velocity = particle_velocity;
+  g.delta_momentum = delta_momentum;
+  g.delta_energy = delta_energy;
+  g.vcoll = vcoll;
+  return dust_drag_impl(ctx, p, g, false, "ghip_dust_drag");
 }
+
+extern "C" int ghip_dust_density_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  if(!g)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_density_grains: bad arguments");
+  return dust_density_impl(ctx, p, *g, true, "ghip_dust_density_grains");
+}
+
+extern "C" int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  if(!g)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_drag_grains: bad arguments");
+  return dust_drag_impl(ctx, p, *g, true, "ghip_dust_drag_grains");
+}
+
+extern "C" int ghip_set_dust_model(ghip_ctx *ctx, const ghip_dust_model *m)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  if(!m)
+    {
+      ctx->dust_model_on = false;
+      memset(&ctx->dust_model, 0, sizeof(ctx->dust_model));
+      return GHIP_OK;
+    }
+  const double vals[5] = {m->Time, m->VirtualTime, m->FragmentationVelocity, m->InitialDustRadius, m->UnitEnergy_in_cgs};
+  static const char *const names[5] = {"Time", "VirtualTime", "FragmentationVelocity", "InitialDustRadius",
+                                       "UnitEnergy_in_cgs"};
+  for(int k = 0; k < 5; k++)
+    if(!std::isfinite(vals[k]))
+      return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_dust_model: %s is not finite", names[k]);
+  if(m->vaporize && !m->growth)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_dust_model: vaporize needs growth (DUST_VAPORIZE does not compile "
+                     "without DUST_GROWTH: it uses adust_min)");
+  if(m->fe_and_ice_grains && !m->vaporize)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_dust_model: fe_and_ice_grains needs vaporize");
+  if(m->vaporize && m->InitialDustRadius == DUST_A_MIN)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_dust_model: vaporize with InitialDustRadius == %g: the latent heat "
+                     "divides by InitialDustRadius - %g", DUST_A_MIN, DUST_A_MIN);
+  const bool on = m->growth || m->real_pebble_collisions || m->vaporize || m->fe_and_ice_grains || m->epstein ||
+                  m->no_friction_heating;
+  if(on && ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_set_dust_model: not available on a replicated shard (ghip_set_shard "
+                     "with %d ranks); use the ghip_dd_* contexts", ctx->shard_n);
+  ctx->dust_model = *m;
+  ctx->dust_model_on = on;
+  return GHIP_OK;
+}
+
+extern "C" size_t ghip_dust_model_size(void) { return sizeof(ghip_dust_model); }
+extern "C" size_t ghip_dust_grains_size(void) { return sizeof(ghip_dust_grains); }
 
 extern "C" int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating)
 {
@@ -715,15 +1047,46 @@ int ghip_dd_dust_groups(ghip_ctx *ctx);   // ghip_dd.hip
 int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
                         int periodic, int *total);
 
-int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int)
+int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
   GHIP_JOIN(ctx);
-  ctx->dd.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
-  const ghip_dd_dust_args &A = ctx->dd.dust;
+  const bool grains = walk == GHIP_DUST_GRAINS_FORM;
   const bool drag = op == GHIP_DD_DUST_DRAG;
   const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
+  if(walk != 0 && !grains)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: walk = %d is neither 0 nor GHIP_DUST_GRAINS_FORM", who, walk);
+  ctx->dd.du_radius = ctx->dd.du_logr = nullptr;
+  if(grains)
+    {
+      // the same operation with the arrays of ghip_dust_grains: the members of ghip_dd_dust_args and the two
+      // planes the model writes
+      const ghip_dd_dust_grains_args &G = *reinterpret_cast<const ghip_dd_dust_grains_args *>(params);
+      const ghip_dust_grains &g = G.g;
+      ghip_dd_dust_args &a = ctx->dd.dust;
+      a.p = G.p;
+      a.ndust = g.ndust;
+      a.dust_idx = g.dust_idx;
+      a.particle_density = g.particle_density;
+      a.dust_density = g.dust_density;
+      a.dust_entropy = g.dust_entropy;
+      a.dust_gasvel = g.dust_gasvel;
+      a.dust_radius = g.dust_radius;
+      a.particle_velocity = g.particle_velocity;
+      a.delta_momentum = g.delta_momentum;
+      a.delta_energy = g.delta_energy;
+      a.vcoll = g.vcoll;
+      a.counts = g.counts;
+      ctx->dd.du_radius = g.dust_radius;
+      ctx->dd.du_logr = g.log_radius_by_dt;
+    }
+  else
+    ctx->dd.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
+  const ghip_dd_dust_args &A = ctx->dd.dust;
   if(!A.p || A.ndust < 0 || (A.ndust > 0 && (!A.dust_idx || !A.particle_density)))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(!drag && grains && dust_pebble(ctx) && A.ndust > 0 && !A.particle_velocity)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  GCHK(dust_model_ready(ctx, drag, grains, who, "walk = GHIP_DUST_GRAINS_FORM with ghip_dd_dust_grains_args"));
   if(drag && A.ndust > 0 && (!A.dust_density || !A.dust_entropy || !A.dust_gasvel || !A.dust_radius ||
                              !A.particle_velocity || !A.delta_momentum || !A.delta_energy || !A.vcoll))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
@@ -745,6 +1108,8 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
   const ghip_dd_dust_args &A = D.dust;
   hipStream_t st = ctx->stream;
   const bool drag = D.op == GHIP_DD_DUST_DRAG;
+  const bool vels = !drag && dust_pebble(ctx);   // (the density pass carries d7 and the three velocity sums)
+  const int npart = vels ? 4 : 1;                // doubles of a partial sum that goes home
   const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
   const int nd = A.ndust, n = ctx->n;
   const size_t Dn = (size_t) nd;
@@ -766,18 +1131,11 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
             {
               std::vector<double> h;
               GCHK(dust_upload_planes(ctx, nd, A.dust_density, A.dust_entropy, A.dust_gasvel, A.dust_radius,
-                                      A.particle_density, A.particle_velocity, A.vcoll, h));
-              dust_run_grains(ctx, nd, dust_k(A.p));
+                                      A.particle_density, A.particle_velocity, A.vcoll, D.du_logr, h));
+              dust_run_grains(ctx, nd, dust_k(A.p), D.du_logr != nullptr);
             }
           else
-            {
-              TreeDev &t = ctx->gt;
-              GCHK(ghip_ensure(ctx, ctx->dust_work, Dn * 8 + 256));
-              DustGrainLocal gl = {didx, pos, hsml, n, mass, nullptr};
-              k_dust_density<<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                          t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                          make_box(A.p->BoxSize, A.p->periodic), P<double>(ctx->dust_work));
-            }
+            GCHK(dust_run_density(ctx, A.p, nd));
           HIPCHK(hipGetLastError());
           GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
           k_dust_slots<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(D.du_slot));
@@ -812,14 +1170,20 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
       // the imported grains against this shard's Type-2 particles; the partial sums go home
       const int nimp = D.x.rtotal;
       D.du_recvd = nimp;
-      GCHK(ghip_ensure(ctx, D.du_part, (size_t) (nimp > 0 ? nimp : 1) * 8));
+      GCHK(ghip_ensure(ctx, D.du_part, (size_t) (nimp > 0 ? nimp : 1) * npart * 8));
       if(nimp > 0)
         {
           TreeDev &t = ctx->gt;
           DustGrainRec gr = {P<double>(D.du_recv), DUST_REC_DENS};
-          k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                        t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                        make_box(A.p->BoxSize, A.p->periodic), P<double>(D.du_part));
+          if(vels)
+            k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(
+              nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
+              P<int>(t.perm), make_box(A.p->BoxSize, A.p->periodic), (double *) nullptr,
+              DustVel{P<double>(ctx->f[GHIP_F_VEL]), P<double>(D.du_part), 4, 1});
+          else
+            k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                          t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
+                                                          make_box(A.p->BoxSize, A.p->periodic), P<double>(D.du_part));
           HIPCHK(hipGetLastError());
         }
       int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];
@@ -828,7 +1192,7 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           sc[r] = D.x.rcount[r];
           so[r] = D.x.roff[r];
         }
-      ghip_dd_set_alltoallv(D, D.du_part.p, 8, sc, so, &D.du_back);
+      ghip_dd_set_alltoallv(D, D.du_part.p, (size_t) npart * 8, sc, so, &D.du_back);
       D.phase = ADD;
       return 1;
     }
@@ -843,11 +1207,18 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           double *dout = P<double>(ctx->dust_work);
           for(int r = 0; r < D.nranks; r++)   // own sum first, then the ranks in ascending order
             if(r != D.rank && D.du_scount[r] > 0)
-              k_dust_add_parts<<<cdiv(D.du_scount[r], 256), 256, 0, st>>>(
-                D.du_scount[r], P<int>(D.du_list) + D.du_soff[r], P<int>(D.du_slot),
-                P<double>(D.du_back) + D.x.roff[r], dout);
+              {
+                if(vels)
+                  k_dust_add_parts4<<<cdiv(D.du_scount[r], 256), 256, 0, st>>>(
+                    D.du_scount[r], P<int>(D.du_list) + D.du_soff[r], P<int>(D.du_slot),
+                    P<double>(D.du_back) + 4 * (size_t) D.x.roff[r], Dn, dout);
+                else
+                  k_dust_add_parts<<<cdiv(D.du_scount[r], 256), 256, 0, st>>>(
+                    D.du_scount[r], P<int>(D.du_list) + D.du_soff[r], P<int>(D.du_slot),
+                    P<double>(D.du_back) + D.x.roff[r], dout);
+              }
           HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(A.particle_density, dout, Dn * 8, hipMemcpyDeviceToHost, st));
+          GCHK(dust_download_density(ctx, nd, A.particle_density, A.particle_velocity));
         }
       HIPCHK(ghip_stream_sync(ctx, st));
       if(A.counts)
@@ -880,7 +1251,8 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
       if(nd > 0)
         {
           std::vector<double> h((size_t) DUST_NPLANES * Dn);
-          GCHK(dust_download_grains(ctx, nd, h, A.particle_velocity, A.delta_momentum, A.delta_energy, A.vcoll));
+          GCHK(dust_download_grains(ctx, nd, h, A.particle_velocity, A.delta_momentum, A.delta_energy, A.vcoll,
+                                    D.du_radius, D.du_logr));
         }
       HIPCHK(ghip_stream_sync(ctx, st));
       if(A.counts)

@@ -256,6 +256,7 @@ struct DDState
   // the dust passes on shards (ghip_dust.hip): this shard's grains go to the shards their spheres reach,
   // partial d7 come back (density), drag records are scattered into every shard's own gas (drag)
   ghip_dd_dust_args dust;         // arguments of the operation in progress
+  double *du_radius = nullptr, *du_logr = nullptr;   // ... in the GHIP_DUST_GRAINS_FORM: the planes the model writes
   DevBuf du_mask;                 // u64[n]: ranks each local grain goes to (by local particle index)
   DevBuf du_slot;                 // i32[n]: list slot of each local grain (read where du_mask is set)
   DevBuf du_list;                 // i32: per destination, the local particle indices sent (ascending)
@@ -498,6 +499,10 @@ struct ghip_ctx
   bool has_drag = false, has_ddm = false, has_newdens = false;
   int kick_fields_n = -1, kick_fields_ngas = -1;   // counts the fields were set for
 
+  // the physics switches of the dust passes (ghip_set_dust_model, ghip_dust.hip)
+  bool dust_model_on = false;          // any switch set: the k_dust_grain<DustM> / k_dust_density<G, DustVel> instantiations run
+  ghip_dust_model dust_model = {};
+  bool id_given = false;               // GHIP_F_ID has been set since the counts last changed
   // the viscosity of the pair loop (ghip_set_viscosity, ghip_sph.hip / ghip_kick.hip)
   bool visc_on = false;                // any switch set: the k_hydro<TG, HydV> instantiations run
   ghip_visc_params visc = {};

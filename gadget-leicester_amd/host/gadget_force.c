@@ -120,6 +120,7 @@ static int KickN = 0, KickCap = 0;
 static void *PinP, *PinS;
 static size_t PinPBytes, PinSBytes;
 static int ViscOnDevice = 0;     /* the context holds a setting of gadget_force_bind_viscosity */
+static int DustModelOnDevice = 0;   /* ... of gadget_force_bind_dust_model */
 static const double *RndTablePtr = NULL;   /* gadget_force_bind_rndtable */
 static int RndTableN = 0, RndOnDevice = 0;
 static int DensPending = 0;      /* overlap_sph: density()'s results are still on the device */
@@ -307,6 +308,7 @@ void gadget_force_finalize(void)
   KeptTree = 0;
   Ctx = NULL;
   ViscOnDevice = 0;
+  DustModelOnDevice = 0;
   RndOnDevice = 0;
   free(ActiveBuf);
   ActiveBuf = NULL;
@@ -2360,12 +2362,107 @@ static void fill_dust_params(ghip_dust_params *d)
   d->UnitVelocity_in_cm_per_s = dust_all(DustLay.a_unit_velocity);
 }
 
+/* the physics switches of the dust passes (ghip_set_dust_model) on bound records */
+static struct gadget_force_dust_model_layout DustModelLay;   /* (switches 0, offsets -1 until bound) */
+static const char *DustModelAll = NULL;
+static void dust_model_lay_defaults(void)
+{
+  memset(&DustModelLay, 0xff, sizeof(DustModelLay));
+  DustModelLay.growth = DustModelLay.real_pebble_collisions = DustModelLay.vaporize = 0;
+  DustModelLay.fe_and_ice_grains = DustModelLay.epstein = DustModelLay.no_friction_heating = 0;
+}
+__attribute__((constructor)) static void dust_model_lay_init(void) { dust_model_lay_defaults(); }
+
+void gadget_force_bind_dust_model(void *host_All, const struct gadget_force_dust_model_layout *lay)
+{
+  if(lay)
+    {
+      DustModelLay = *lay;
+      DustModelAll = (const char *) host_All;
+    }
+  else
+    {
+      dust_model_lay_defaults();
+      DustModelAll = NULL;
+    }
+}
+
+static int dust_model_bound(void)
+{
+  return DustModelLay.growth > 0 || DustModelLay.real_pebble_collisions > 0 || DustModelLay.vaporize > 0 ||
+         DustModelLay.fe_and_ice_grains > 0 || DustModelLay.epstein > 0 || DustModelLay.no_friction_heating > 0;
+}
+
+/* the switches that write d9, DustRadius or LogDustRadius_by_dt: the *_grains entry points serve them */
+static int dust_model_planes(void)
+{
+  return DustModelLay.growth > 0 || DustModelLay.real_pebble_collisions > 0 || DustModelLay.vaporize > 0;
+}
+
+static double dust_model_all(int off)
+{
+  return off >= 0 && DustModelAll ? *(const double *) (DustModelAll + off) : 0.0;
+}
+
+/* the setting reaches the device before a dust pass; with fe_and_ice_grains also P[].ID */
+static int dust_model_begin(const char *who)
+{
+  if(!dust_model_bound())
+    {
+      if(DustModelOnDevice && chk(ghip_set_dust_model(Ctx, NULL), "ghip_set_dust_model"))
+        return -1;
+      DustModelOnDevice = 0;
+      return 0;
+    }
+  const struct gadget_force_dust_model_layout *l = &DustModelLay;
+  if((l->growth > 0 && l->a_virtual_time < 0) || (l->real_pebble_collisions > 0 && l->a_fragmentation_velocity < 0) ||
+     (l->vaporize > 0 && (l->a_initial_dust_radius < 0 || l->a_unit_energy < 0)) ||
+     (dust_model_planes() && !DustModelAll) || (l->fe_and_ice_grains > 0 && BhLay.p_id < 0))
+    return refuse(90002, "%s: the dust model needs the offsets of VirtualTime (growth), FragmentationVelocity "
+                         "(real_pebble_collisions), InitialDustRadius and UnitEnergy_in_cgs (vaporize) in the "
+                         "host's All, and P[].ID in the bh table (fe_and_ice_grains) "
+                         "(gadget_force_bind_dust_model, gadget_force_bind_records)", who);
+  ghip_dust_model m;
+  memset(&m, 0, sizeof(m));
+  m.growth = l->growth > 0;
+  m.real_pebble_collisions = l->real_pebble_collisions > 0;
+  m.vaporize = l->vaporize > 0;
+  m.fe_and_ice_grains = l->fe_and_ice_grains > 0;
+  m.epstein = l->epstein > 0;
+  m.no_friction_heating = l->no_friction_heating > 0;
+  m.Time = All.Time;
+  m.VirtualTime = dust_model_all(l->a_virtual_time);
+  m.FragmentationVelocity = dust_model_all(l->a_fragmentation_velocity);
+  m.InitialDustRadius = dust_model_all(l->a_initial_dust_radius);
+  m.UnitEnergy_in_cgs = dust_model_all(l->a_unit_energy);
+  if(chk(ghip_set_dust_model(Ctx, &m), "ghip_set_dust_model"))
+    return -1;
+  DustModelOnDevice = 1;
+  if(m.fe_and_ice_grains && NumPart > 0)
+    {
+      int *ids = (int *) malloc((size_t) NumPart * sizeof(int));
+      if(!ids)
+        return -1;
+      for(int i = 0; i < NumPart; i++)
+        ids[i] = (int) *(unsigned int *) (prec(i) + BhLay.p_id);
+      int rc = chk(ghip_set_field(Ctx, GHIP_F_ID, ids), "ghip_set_field");
+      free(ids);
+      if(rc)
+        return -1;
+    }
+  return 0;
+}
+
 /* checks + the grain list (active Type 2 in FirstActiveParticle order) into a malloc'd array */
 static int dust_ready(const char *who, int drag, int **idx_out)
 {
   *idx_out = NULL;
   if(need_ctx(who))
     return -1;
+  if(NTask > 1 && dust_model_planes())
+    return refuse(90015, "%s: gadget_force_bind_dust_model with growth, real_pebble_collisions or vaporize serves a "
+                         "single rank (NTask = %d); ranks run GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG in the "
+                         "GHIP_DUST_GRAINS_FORM with ghip_set_dust_model of their own", who, NTask);
   if(NTask > 1 && !RcclConnected && !AllgatherFn)
     {
       /* without a transport the passes cannot export grains to the other ranks */
@@ -2393,6 +2490,8 @@ static int dust_ready(const char *who, int drag, int **idx_out)
     }
   else if(ensure_tree())
     return -1;
+  if(dust_model_begin(who))
+    return -1;
   int n = 0;
   for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
     if(p_type(i) == 2)
@@ -2415,12 +2514,15 @@ void dust_density(void)
   const int n = dust_ready("dust_density", 0, &idx);
   if(n < 0)
     return;
-  double *rho = (double *) scratch((size_t) (n + 1) * sizeof(double));
+  /* d7, and the raw d9 sums with real_pebble_collisions (dust.c:851-853) */
+  const int vels = DustModelLay.real_pebble_collisions > 0 && DustLay.p_particle_velocity >= 0;
+  double *rho = (double *) scratch(4 * (size_t) (n + 1) * sizeof(double));
   if(!rho)
     {
       free(idx);
       return;
     }
+  double *d9 = rho + (size_t) n + 1;
   ghip_dust_params d;
   fill_dust_params(&d);
   int rc;
@@ -2435,11 +2537,26 @@ void dust_density(void)
       a.particle_density = rho;
       rc = dd_collective(GHIP_DD_DUST_DENSITY, &a, 0, "dust_density (ranks)") ? GHIP_EDEVICE : GHIP_OK;
     }
+  else if(dust_model_bound())
+    {
+      ghip_dust_grains g;
+      memset(&g, 0, sizeof(g));
+      g.ndust = n;
+      g.dust_idx = idx;
+      g.particle_density = rho;
+      g.particle_velocity = d9;
+      rc = chk(ghip_dust_density_grains(Ctx, &d, &g), "ghip_dust_density_grains") ? GHIP_EDEVICE : GHIP_OK;
+    }
   else
     rc = chk(ghip_dust_density(Ctx, &d, n, idx, rho), "ghip_dust_density") ? GHIP_EDEVICE : GHIP_OK;
   if(rc == GHIP_OK)
     for(int k = 0; k < n; k++)
-      *PF64(idx[k], DustLay.p_particle_density) = rho[k];   /* dust.c:242-245 */
+      {
+        *PF64(idx[k], DustLay.p_particle_density) = rho[k];   /* dust.c:242-245 */
+        if(vels)
+          for(int c = 0; c < 3; c++)
+            PF64(idx[k], DustLay.p_particle_velocity)[c] = d9[3 * (size_t) k + c];
+      }
   free(rho);
   free(idx);
 }
@@ -2455,7 +2572,7 @@ void dust_drag(void)
   const size_t ng = (size_t) (N_gas > 0 ? N_gas : 1);
   /* per grain: rho, A, gasvel[3], radius, d7, d9[3], dmom[3], dE, vcoll (15); per particle: vel[3]
    * + per gas particle: entropy, heating */
-  double *buf = (double *) scratch((15 * m + 3 * nall + 2 * ng) * sizeof(double));
+  double *buf = (double *) scratch((16 * m + 3 * nall + 2 * ng) * sizeof(double));
   if(!buf)
     {
       free(idx);
@@ -2463,7 +2580,10 @@ void dust_drag(void)
     }
   double *rho = buf, *ent = buf + m, *gv = buf + 2 * m, *rad = buf + 5 * m, *d7 = buf + 6 * m,
          *d9 = buf + 7 * m, *dmom = buf + 10 * m, *de = buf + 13 * m, *vc = buf + 14 * m;
-  double *vel = buf + 15 * m, *sent = vel + 3 * nall, *heat = sent + ng;
+  double *logr = buf + 15 * m;   /* LogDustRadius_by_dt (gadget_force_bind_dust_model) */
+  double *vel = buf + 16 * m, *sent = vel + 3 * nall, *heat = sent + ng;
+  const int grow = DustModelLay.growth > 0;
+  const int have_logr = grow && DustModelLay.p_log_radius_by_dt >= 0;
   for(int k = 0; k < n; k++)
     {
       const int i = idx[k];
@@ -2472,6 +2592,8 @@ void dust_drag(void)
       rad[k] = *PF64(i, DustLay.p_radius);
       d7[k] = *PF64(i, DustLay.p_particle_density);
       vc[k] = *PF64(i, DustLay.p_vcoll);
+      if(have_logr)
+        logr[k] = *PF64(i, DustModelLay.p_log_radius_by_dt);
       for(int c = 0; c < 3; c++)
         {
           gv[3 * (size_t) k + c] = PF64(i, BhLay.p_dust_gasvel)[c];
@@ -2509,6 +2631,24 @@ void dust_drag(void)
           return;
         }
     }
+  else if(rc == GHIP_OK && dust_model_bound())
+    {
+      ghip_dust_grains g;
+      memset(&g, 0, sizeof(g));
+      g.ndust = n;
+      g.dust_idx = idx;
+      g.particle_density = d7;
+      g.dust_density = rho;
+      g.dust_entropy = ent;
+      g.dust_gasvel = gv;
+      g.dust_radius = rad;
+      g.particle_velocity = d9;
+      g.delta_momentum = dmom;
+      g.delta_energy = de;
+      g.vcoll = vc;
+      g.log_radius_by_dt = have_logr ? logr : NULL;
+      rc = ghip_dust_drag_grains(Ctx, &d, &g);
+    }
   else if(rc == GHIP_OK)
     rc = ghip_dust_drag(Ctx, &d, n, idx, rho, ent, gv, rad, d7, d9, dmom, de, vc);
   if(rc == GHIP_OK)
@@ -2532,6 +2672,10 @@ void dust_drag(void)
             }
           *PF64(i, DustLay.p_delta_energy) = de[k];
           *PF64(i, DustLay.p_vcoll) = vc[k];
+          if(grow && NTask <= 1)   /* dust.c:551-567, 589; :465 */
+            *PF64(i, DustLay.p_radius) = rad[k];
+          if(have_logr && NTask <= 1)
+            *PF64(i, DustModelLay.p_log_radius_by_dt) = logr[k];
         }
       for(int j = 0; j < N_gas; j++)
         {

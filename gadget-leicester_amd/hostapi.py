@@ -92,6 +92,15 @@ class DustLayout(C.Structure):
         "a_unit_velocity")]
 
 
+class DustModelLayout(C.Structure):
+    """struct gadget_force_dust_model_layout: the six dust sub-flag switches, byte offsets of All.VirtualTime /
+    FragmentationVelocity / InitialDustRadius / UnitEnergy_in_cgs and of P[].LogDustRadius_by_dt (-1: absent)"""
+    _fields_ = [(k, C.c_int) for k in (
+        "growth", "real_pebble_collisions", "vaporize", "fe_and_ice_grains", "epstein", "no_friction_heating",
+        "a_virtual_time", "a_fragmentation_velocity", "a_initial_dust_radius", "a_unit_energy",
+        "p_log_radius_by_dt")]
+
+
 class ViscLayout(C.Structure):
     """struct gadget_force_visc_layout: byte offsets of All.AlphaMin / ViscSource / DecayTime and of
     SphP[].alpha / Dtalpha (-1: absent), and the four viscosity switches"""
@@ -178,7 +187,7 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
            "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration",
            "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system",
-           "gadget_force_bind_viscosity", "gadget_force_bind_rndtable"]
+           "gadget_force_bind_viscosity", "gadget_force_bind_rndtable", "gadget_force_bind_dust_model"]
 
 _LIB = None
 
@@ -227,6 +236,8 @@ def lib():
         L.gadget_force_set_allgather.restype = None
         L.gadget_force_bind_dust.argtypes = [C.c_void_p, C.c_void_p]
         L.gadget_force_bind_dust.restype = None
+        L.gadget_force_bind_dust_model.argtypes = [C.c_void_p, C.c_void_p]
+        L.gadget_force_bind_dust_model.restype = None
         L.gadget_force_bind_viscosity.argtypes = [C.c_void_p, C.c_void_p]
         L.gadget_force_bind_viscosity.restype = None
         L.gadget_force_bind_rndtable.argtypes = [C.c_void_p, C.c_int]
@@ -249,7 +260,7 @@ class Host:
 
     def __init__(self, periodic=1, pmgrid=0, unequal=0, device=0, black_holes=0, dust=0,
                  overlap_sph=0, accretion_of_dust_only=0, accretion_density=0, rank=0, nranks=1,
-                 pin_records=0, dynamic_tree=0, accept_guests=0):
+                 pin_records=0, dynamic_tree=0, accept_guests=0, dust_model=None):
         self.L = lib()
         self.endrun_codes = []
         self._cb = ENDRUN_CB(lambda code: self.endrun_codes.append(code))
@@ -263,6 +274,8 @@ class Host:
             raise RuntimeError("gadget_force_init failed (%d): %s" %
                                (rc, self.L.gadget_force_last_error().decode()))
         self.All = AllStruct.in_dll(self.L, "All")
+        if dust_model is not None:              # (host_all, DustModelLayout), as bind_dust_model takes them
+            self.bind_dust_model(*dust_model)
 
     def bind_all(self, host_all, offsets):
         """gadget_force_bind_all: `host_all` a numpy structured scalar/array holding the host's own
@@ -299,6 +312,18 @@ class Host:
             return
         self._dust = (host_all, lay)            # keep alive
         self.L.gadget_force_bind_dust(C.c_void_p(host_all.ctypes.data), C.cast(C.byref(lay), C.c_void_p))
+
+    def bind_dust_model(self, host_all, lay):
+        """gadget_force_bind_dust_model: `host_all` as for bind_dust (VirtualTime, FragmentationVelocity,
+        InitialDustRadius, UnitEnergy_in_cgs), `lay` a DustModelLayout naming them, P[].LogDustRadius_by_dt and
+        the switches; None unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_dust_model(None, None)
+            self._dust_model = None
+            return
+        self._dust_model = (host_all, lay)      # keep alive
+        self.L.gadget_force_bind_dust_model(None if host_all is None else C.c_void_p(host_all.ctypes.data),
+                                            C.cast(C.byref(lay), C.c_void_p))
 
     def bind_viscosity(self, host_all, lay):
         """gadget_force_bind_viscosity: `host_all` as for bind_dust (AlphaMin, ViscSource, DecayTime), `lay` a
@@ -393,6 +418,7 @@ class Host:
         self.L.gadget_force_bind_all(None, None)
         self.L.gadget_force_bind_records(None, None, None, None)
         self.L.gadget_force_bind_dust(None, None)
+        self.L.gadget_force_bind_dust_model(None, None)
         self.L.gadget_force_bind_integration(None, None, None, None, None, None)
         self.L.gadget_force_bind_potential(None, None)
         self.L.gadget_force_bind_viscosity(None, None)

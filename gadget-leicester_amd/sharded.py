@@ -233,6 +233,11 @@ class DomainShards:
         for p in self.paths:
             p.set_viscosity(params)
 
+    def set_dust_model(self, model=None):
+        """ghip_set_dust_model on every shard (the setting must be the same on all of them)"""
+        for p in self.paths:
+            p.set_dust_model(model)
+
     def visc_set_alpha(self, alpha, dtalpha=None):
         """per shard: alpha (and Dtalpha or None) of its own gas, in its order.  Before density(): a ghost
         carries its owner's alpha as of the ghost refresh that ends GHIP_DD_DENSITY."""
@@ -351,6 +356,10 @@ class DomainRank:
     def set_viscosity(self, params=None):
         """ghip_set_viscosity on this rank; the caller gives every rank the same setting"""
         self.p.set_viscosity(params)
+
+    def set_dust_model(self, model=None):
+        """ghip_set_dust_model on this rank; the caller gives every rank the same setting"""
+        self.p.set_dust_model(model)
 
     def visc_set_alpha(self, alpha, dtalpha=None):
         """alpha (and Dtalpha or None) of this rank's own gas, before density()"""

@@ -470,6 +470,25 @@ struct gadget_force_dust_layout
   int a_mean_weight, a_unit_density, a_unit_velocity;
 };
 void gadget_force_bind_dust(void *host_All, const struct gadget_force_dust_layout *lay);
+/* The physics switches the reference's Makefile lists next to -DDUST (ghip_set_dust_model, include/ghip.h) on
+ * bound records: the six switches as ints (> 0: defined), byte offsets of All.VirtualTime,
+ * All.FragmentationVelocity, All.InitialDustRadius and All.UnitEnergy_in_cgs (doubles) in the host's All, and of
+ * P[].LogDustRadius_by_dt (double) in the bound P records; -1 = absent.  All.Time is the mirror's own, P[].ID the
+ * p_id of the bh table of gadget_force_bind_records (fe_and_ice_grains needs it).  growth needs a_virtual_time,
+ * real_pebble_collisions a_fragmentation_velocity, vaporize a_initial_dust_radius and a_unit_energy: endrun(90002)
+ * otherwise.  Once bound, every dust pass sets the model with the All.Time of the call; dust_density() also writes
+ * the raw d9 sums (real_pebble_collisions), dust_drag() also writes DustRadius and, where dust.c:465 does,
+ * LogDustRadius_by_dt (growth).  lay == NULL unbinds.
+ * Single rank for growth, real_pebble_collisions and vaporize: with NTask > 1 both functions call endrun(90015)
+ * and write nothing -- ranks drive GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG in the GHIP_DUST_GRAINS_FORM with
+ * ghip_set_dust_model themselves.  epstein and no_friction_heating alone also serve ranks. */
+struct gadget_force_dust_model_layout
+{
+  int growth, real_pebble_collisions, vaporize, fe_and_ice_grains, epstein, no_friction_heating;
+  int a_virtual_time, a_fragmentation_velocity, a_initial_dust_radius, a_unit_energy;
+  int p_log_radius_by_dt;
+};
+void gadget_force_bind_dust_model(void *host_All, const struct gadget_force_dust_model_layout *lay);
 
 /* -DTIME_DEP_ART_VISC and the uniform viscosity switches of hydro_evaluate (hydra.c:1512-1595) on bound
  * records (ghip_set_viscosity, include/ghip.h).  Byte offsets of All.AlphaMin / All.ViscSource /

@@ -712,9 +712,12 @@ int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *ncand, int *c
 int ghip_find_smbh(ghip_ctx *ctx, double SMBHmass, double pos[3], int *count);
 
 /* ---- the dust-gas drag passes of the shipped flag bundle (DUST, DUST_TIMESTEP, DUST_POWERLAW,
- * CONSTANT_MEAN_MOLECULAR_WEIGHT; no DUST_GROWTH*, DUST_VAPORIZE, DUST_TWO_POPULATIONS,
- * DUST_REAL_PEBBLE_COLLISIONS, DUST_EPSTEIN, DUST_NO_FRICTION_HEATING): dust_density() and
- * dust_drag() (dust.c:60-1029, called at accel.c:194, 198).  The grains are given by their particle
+ * CONSTANT_MEAN_MOLECULAR_WEIGHT): dust_density() and dust_drag() (dust.c:60-1029, called at accel.c:194,
+ * 198).  The sub-flags DUST_GROWTH, DUST_REAL_PEBBLE_COLLISIONS, DUST_VAPORIZE, DUST_FE_AND_ICE_GRAINS,
+ * DUST_EPSTEIN and DUST_NO_FRICTION_HEATING are a setting of the context (ghip_set_dust_model, below); not
+ * built: DUST_TWO_POPULATIONS, DUST_GROWTH_FIXED_SIZE, DUST_MDUST_GROW, DUST_2ND_POPULATION,
+ * DUST_PEBBLES_BORN, DUST_SINK_ON_FLY, DUST_ENERGY_CONSERVATION, DUST_OPACITY_FIT.
+ * The grains are given by their particle
  * indices (the active Type-2 particles in active-list order); their per-grain state travels in host
  * arrays in list order.  Read from the resident fields: POS, MASS, TYPE, HSML, TIMEBIN, GRAVACCEL
  * (the finished value gravity_tree() leaves), VEL and the gas ENTROPY.  Needs the trees of this step;
@@ -753,6 +756,76 @@ int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const in
  * nothing. */
 int ghip_dust_get_drag_heating(ghip_ctx *ctx, double *drag_heating);
 int ghip_dust_set_drag_heating(ghip_ctx *ctx, const double *drag_heating);
+
+/* ---- the physics switches of the dust passes that the reference's Makefile lists next to -DDUST:
+ * grain growth, fragmentation, vaporisation (dust.c:449-609).  A setting of the context, for
+ * ghip_dust_density / ghip_dust_drag, the two *_grains entry points below and both forms of the GHIP_DD_DUST_*
+ * operations alike.  p == NULL or all six switches 0: the default kernels, nothing allocated.  The setter only copies
+ * the struct (a host sets Time every step).
+ *   real_pebble_collisions   the density pass also sums d9[k] += m_i W(r, h_i) Vel_j[k] over the neighbours
+ *              of d7, with the same weight (dust.c:851-853); the drag pass divides by d7 as it always has.
+ *              In the growth rule: adot = 0 if FragmentationVelocity < 0.1, else
+ *              adot *= (1 - x^2) / (1 + x^2), x = DustVcoll / FragmentationVelocity (:479-490)
+ *   epstein    ts is always the Epstein expression (:415-416)
+ *   no_friction_heating   the friction term of DeltaDragEnergy is dropped (:433-435)
+ *   growth     behind the gate Time > 0 && Time > VirtualTime, for d7 > 0 (:453-494):
+ *              t_coll = 4 (rho_grain / UnitDensity) (a / UnitLength) / d7 / (DustVcoll 1e2 / UnitVelocity
+ *              + 1e-20) with the FINAL DustVcoll of the call -- the value of :374 is overwritten at
+ *              :437-444 whenever dt > 0, a quirk kept --, LogDustRadius_by_dt = t_coll, adot = a / UnitLength
+ *              / 3 / t_coll.  DustRadius += adot dt UnitLength_in_cm (:551), then clamped to [0.1, 1e5] cm
+ *              (:566-567) -- for EVERY grain of the list, also with dt == 0 or behind a closed gate
+ *   vaporize   for DUST_Density > 0, whatever the gate (:501-529): T = pi / 8 (c_s UnitVelocity)^2 MeanWeight
+ *              m_p / k_B, pvap = 10^(-24605 / T + 13.176), adot -= 1 / (rho_grain sqrt(2 * 3.1415)) / c_s
+ *              / UnitVelocity * pvap / UnitVelocity (the literal is 3.1415).  The latent heat 1e11 (a - 0.1) /
+ *              (InitialDustRadius - 0.1) is taken before and after the radius update; the difference times
+ *              Mass UnitMass_in_g / UnitEnergy_in_cgs is added to DeltaDragEnergy (:533-608), so the
+ *              scatter cools or heats the gas by it
+ *   fe_and_ice_grains   grains with an odd ID (the resident GHIP_F_ID) are water ice: pvap = 10^(11.6 -
+ *              2104 / T) for T <= 600, 5 + 5.2e-3 T above; latent constant 4e10 (:509-547, 596-605)
+ * GHIP_EINVAL from the setter, before anything is launched: a value that is not finite; vaporize without
+ * growth; fe_and_ice_grains without vaporize; vaporize with InitialDustRadius == 0.1 (the denominator of the
+ * latent heat); a context of ghip_set_shard (use the ghip_dd_* contexts).  A drag pass with
+ * fe_and_ice_grains returns GHIP_EINVAL when GHIP_F_ID was never given (ghip_set_field).
+ * On ghip_dd_* contexts the setting must be the same on all ranks (the caller's duty: nothing checks it). ---- */
+typedef struct
+{
+  int growth;                   /* DUST_GROWTH */
+  int real_pebble_collisions;   /* DUST_REAL_PEBBLE_COLLISIONS */
+  int vaporize;                 /* DUST_VAPORIZE (needs growth) */
+  int fe_and_ice_grains;        /* DUST_FE_AND_ICE_GRAINS (needs vaporize) */
+  int epstein;                  /* DUST_EPSTEIN */
+  int no_friction_heating;      /* DUST_NO_FRICTION_HEATING */
+  double Time, VirtualTime;     /* All.Time, All.VirtualTime: the gate of growth */
+  double FragmentationVelocity; /* All.FragmentationVelocity, in the units of DustVcoll (m/s) */
+  double InitialDustRadius;     /* All.InitialDustRadius [cm] */
+  double UnitEnergy_in_cgs;
+} ghip_dust_model;
+int ghip_set_dust_model(ghip_ctx *ctx, const ghip_dust_model *m);   /* NULL: everything off (the default path) */
+size_t ghip_dust_model_size(void);    /* sizeof(ghip_dust_model) of the library, for bindings to check */
+/* The arrays of a grain list, in list order: the members of ghip_dust_density / ghip_dust_drag plus the two
+ * that the model writes.  Members a pass does not use may be NULL. */
+typedef struct
+{
+  int ndust;
+  const int *dust_idx;            /* local particle indices, in active-list order */
+  double *particle_density;       /* [ndust] d7: density out, drag in */
+  const double *dust_density, *dust_entropy, *dust_gasvel;   /* drag in (d1, d2, d3 [ndust][3]) */
+  double *dust_radius;            /* drag in/out [ndust] (written with growth only) */
+  double *particle_velocity;      /* [ndust][3] d9: density out -- the raw sums, written with
+                                     real_pebble_collisions only --, drag in/out (divided by d7 where d7 > 0) */
+  double *delta_momentum, *delta_energy;   /* drag out ([ndust][3], [ndust]) */
+  double *vcoll;                  /* drag in/out [ndust] */
+  double *log_radius_by_dt;       /* drag in/out [ndust], may be NULL: t_coll where dust.c:465 writes it (growth,
+                                     the gate open, d7 > 0), the caller's value elsewhere */
+  long long *counts;              /* shards only, out [4] (may be NULL): as ghip_dd_dust_args.counts */
+} ghip_dust_grains;
+size_t ghip_dust_grains_size(void);
+/* ghip_dust_density / ghip_dust_drag for every setting of ghip_set_dust_model (single-rank, like them).  The
+ * two old entry points keep their signatures and honour epstein / no_friction_heating; ghip_dust_density with
+ * real_pebble_collisions set, and ghip_dust_drag with growth or vaporize set, return GHIP_EINVAL: they have
+ * no array for what those switches write. */
+int ghip_dust_density_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g);
+int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g);
 
 /* The dust passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG through ghip_dd_begin /
  * ghip_dd_run): the reference's export of the grains (dust.c:60-261, 560-746).  Each grain goes to every
@@ -819,6 +892,22 @@ typedef struct
 /* the dust passes (params: ghip_dd_dust_args, see above) */
 #define GHIP_DD_DUST_DENSITY 9   /* needs GHIP_DD_GRAVITY of this step */
 #define GHIP_DD_DUST_DRAG 10     /* needs GHIP_DD_GRAVITY and GHIP_DD_DENSITY of this step */
+/* The dust passes with the arrays of ghip_dust_grains, for every setting of ghip_set_dust_model: the same two
+ * operations and the same exchanges, GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG begun with walk =
+ * GHIP_DUST_GRAINS_FORM and params a ghip_dd_dust_grains_args (ghip_dd_begin's `walk` selects the form of an
+ * operation; the operation codes stay below 16 and none moves).  walk = 0 is the form above.  With
+ * real_pebble_collisions the partial an importing shard returns per grain record is d7 and the three velocity
+ * sums (32 bytes, not 8), added on the home shard rank by rank in ascending order; without it not a byte more
+ * travels.  The per-grain update (growth, vaporisation) runs on the home shard only and the 72-byte drag record
+ * is unchanged: DeltaDragEnergy already holds the latent heat.  Radius and LogDustRadius_by_dt are host-held
+ * per-grain arrays and need no migration slot.  With walk = 0 the two operations refuse the switches that
+ * ghip_dust_density / ghip_dust_drag refuse; any other walk is GHIP_EINVAL. */
+typedef struct
+{
+  const ghip_dust_params *p;
+  ghip_dust_grains g;
+} ghip_dd_dust_grains_args;
+#define GHIP_DUST_GRAINS_FORM 1   /* `walk` of ghip_dd_begin / ghip_dd_run for the two dust operations */
 /* compute_potential() on shards (params: ghip_pot_params, the argument rules of ghip_potential, checked
  * by ghip_dd_begin before anything is launched or posted).  The targets are ALL particles of every shard,
  * so the locally essential trees of the step's GHIP_DD_GRAVITY -- selected against the active targets
