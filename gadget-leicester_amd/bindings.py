@@ -1288,20 +1288,13 @@ def dd_dust_args(params, dust, particle_density=None, dust_density=None, dust_en
     DdDustArgs and the dict of numpy arrays it points into -- inputs copied, outputs allocated
     (particle_density, particle_velocity, delta_momentum, delta_energy, vcoll, counts [4]); keep `arrays`
     alive until the operation has finished."""
-    nd = len(dust)
-    f64 = lambda v, shape: np.zeros(shape) if v is None else \
-        np.ascontiguousarray(v, np.float64).reshape(shape).copy()
-    a = dict(dust_idx=np.ascontiguousarray(dust, np.int32), particle_density=f64(particle_density, nd),
-             dust_density=f64(dust_density, nd), dust_entropy=f64(dust_entropy, nd),
-             dust_gasvel=f64(dust_gasvel, (nd, 3)), dust_radius=f64(dust_radius, nd),
-             particle_velocity=f64(particle_velocity, (nd, 3)), delta_momentum=np.zeros((nd, 3)),
-             delta_energy=np.zeros(nd), vcoll=f64(vcoll, nd), counts=np.zeros(4, np.int64), _params=params)
+    g, a = dust_grains(dust, particle_density, dust_density, dust_entropy, dust_gasvel, dust_radius,
+                       particle_velocity, vcoll, logr=False)
     A = DdDustArgs()
     A.p = C.pointer(params)
-    A.ndust = nd
-    for k in ("dust_idx", "particle_density", "dust_density", "dust_entropy", "dust_gasvel", "dust_radius",
-              "particle_velocity", "delta_momentum", "delta_energy", "vcoll", "counts"):
-        setattr(A, k, a[k].ctypes.data)
+    for k, _ in DdDustArgs._fields_[1:]:
+        setattr(A, k, getattr(g, k))
+    a["_params"] = params
     return A, a
 
 

@@ -580,23 +580,23 @@ static DustM dust_m(ghip_ctx *ctx, double *logr)
 static bool dust_pebble(const ghip_ctx *ctx) { return ctx->dust_model_on && ctx->dust_model.real_pebble_collisions; }
 static bool dust_growth(const ghip_ctx *ctx) { return ctx->dust_model_on && ctx->dust_model.growth; }
 
-// What a pass asks of the setting before it launches anything.  grains: the caller came through
+// What a pass asks of the setting before it launches anything.  c.grains: the caller came through
 // ghip_dust_grains (the *_grains entry points, GHIP_DUST_GRAINS_FORM on shards) and has arrays for what the switches
-// write; `other` names that way for a caller who did not
-static int dust_model_ready(ghip_ctx *ctx, bool drag, bool grains, const char *who, const char *other)
+// write; c.other names that way for a caller who did not
+static int dust_model_ready(ghip_ctx *ctx, const DustCall &c)
 {
   if(!ctx->dust_model_on)
     return GHIP_OK;
   const ghip_dust_model &s = ctx->dust_model;
-  if(!grains && !drag && s.real_pebble_collisions)
+  if(!c.grains && !c.drag && s.real_pebble_collisions)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: real_pebble_collisions is set (ghip_set_dust_model) and this entry "
-                     "point has no array for the velocity sums d9: use %s", who, other);
-  if(!grains && drag && (s.growth || s.vaporize))
+                     "point has no array for the velocity sums d9: use %s", c.who, c.other);
+  if(!c.grains && c.drag && (s.growth || s.vaporize))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: growth / vaporize is set (ghip_set_dust_model) and this entry point "
-                     "cannot write the radius: use %s", who, other);
-  if(drag && s.fe_and_ice_grains && !ctx->id_given)
+                     "cannot write the radius: use %s", c.who, c.other);
+  if(c.drag && s.fe_and_ice_grains && !ctx->id_given)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: fe_and_ice_grains reads the particles' IDs, and GHIP_F_ID has not "
-                     "been given since ghip_set_counts (ghip_set_field)", who);
+                     "been given since ghip_set_counts (ghip_set_field)", c.who);
   return GHIP_OK;
 }
 
@@ -637,12 +637,49 @@ static int dust_upload_list(ghip_ctx *ctx, int nd, const int *idx, const char *w
   return GHIP_OK;
 }
 
-// the checks every single-rank entry point makes, then the grain list
-static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const int *idx, bool gas,
-                      const char *who)
+// One pass in the record every layer below the entries reads.  g == nullptr (a *_grains entry without its struct)
+// becomes a list of -1 grains, which dust_call_check refuses like any other missing argument
+static DustCall dust_call(const ghip_dust_params *p, const ghip_dust_grains *g, bool grains, bool drag,
+                          const char *who, const char *other)
 {
-  if(!p || nd < 0 || (nd > 0 && !idx))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  DustCall c;
+  c.p = p;
+  if(g)
+    c.g = *g;
+  else
+    c.g.ndust = -1;
+  c.grains = grains;
+  c.drag = drag;
+  c.who = who;
+  c.other = other;
+  return c;
+}
+
+// The argument rules of all four forms, then what the setting asks of this form.  Required with ndust > 0: the
+// list and d7; in the drag pass all nine arrays; in the density pass of a grains form d9 when it is written
+static int dust_call_check(ghip_ctx *ctx, const DustCall &c)
+{
+  const ghip_dust_grains &g = c.g;
+  bool ok = c.p && g.ndust >= 0;
+  if(ok && g.ndust > 0)
+    {
+      ok = g.dust_idx && g.particle_density;
+      if(c.drag)
+        ok = ok && g.dust_density && g.dust_entropy && g.dust_gasvel && g.dust_radius && g.particle_velocity &&
+             g.delta_momentum && g.delta_energy && g.vcoll;
+      else if(c.grains && dust_pebble(ctx))
+        ok = ok && g.particle_velocity;
+    }
+  if(!ok)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", c.who);
+  return dust_model_ready(ctx, c);
+}
+
+// what every single-rank entry point asks of the context, then the grain list
+static int dust_begin(ghip_ctx *ctx, const DustCall &c, bool gas)
+{
+  const int nd = c.g.ndust;
+  const char *who = c.who;
   if(ctx->dd.on && ctx->dd.nranks > 1)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU context (%d ranks): these entry "
                      "points are single-rank (shards run GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG)", who,
@@ -656,28 +693,27 @@ static int dust_begin(ghip_ctx *ctx, const ghip_dust_params *p, int nd, const in
     GCHK(ghip_finish_gas_tree(ctx));
   if(!ctx->gt.built || (gas && !ctx->st.built))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
-  return dust_upload_list(ctx, nd, idx, who);
+  return dust_upload_list(ctx, nd, c.g.dust_idx, who);
 }
 
 // the per-grain planes of the drag pass, in list order, to dust_work; returns the planes
-static int dust_upload_planes(ghip_ctx *ctx, int nd, const double *dust_density, const double *dust_entropy,
-                              const double *dust_gasvel, const double *dust_radius,
-                              const double *particle_density, const double *particle_velocity,
-                              const double *vcoll, const double *logr, std::vector<double> &h)
+static int dust_upload_planes(ghip_ctx *ctx, const DustCall &c, std::vector<double> &h)
 {
-  const size_t D = (size_t) nd;
+  const ghip_dust_grains &g = c.g;
+  const size_t D = (size_t) g.ndust;
+  const double *logr = g.log_radius_by_dt;
   h.assign((size_t) DUST_NPLANES * D, 0.0);
   for(size_t a = 0; a < D; a++)
     {
-      h[DP_RHO * D + a] = dust_density[a];
-      h[DP_ENT * D + a] = dust_entropy[a];
-      h[DP_RAD * D + a] = dust_radius[a];
-      h[DP_D7 * D + a] = particle_density[a];
-      h[DP_VCOLL * D + a] = vcoll[a];
+      h[DP_RHO * D + a] = g.dust_density[a];
+      h[DP_ENT * D + a] = g.dust_entropy[a];
+      h[DP_RAD * D + a] = g.dust_radius[a];
+      h[DP_D7 * D + a] = g.particle_density[a];
+      h[DP_VCOLL * D + a] = g.vcoll[a];
       for(int k = 0; k < 3; k++)
         {
-          h[(DP_GV + k) * D + a] = dust_gasvel[3 * a + k];
-          h[(DP_D9 + k) * D + a] = particle_velocity[3 * a + k];
+          h[(DP_GV + k) * D + a] = g.dust_gasvel[3 * a + k];
+          h[(DP_D9 + k) * D + a] = g.particle_velocity[3 * a + k];
         }
     }
   // dust_work: planes [DUST_NPLANES][nd] | cnt [nd + 1] | off [nd + 1]   (64-bit)
@@ -691,13 +727,16 @@ static int dust_upload_planes(ghip_ctx *ctx, int nd, const double *dust_density,
   return GHIP_OK;
 }
 
-// logr: the caller holds a LogDustRadius_by_dt array (uploaded by dust_upload_planes)
-static void dust_run_grains(ghip_ctx *ctx, int nd, const DustK &K, bool logr)
+// (a LogDustRadius_by_dt array of the caller's was uploaded by dust_upload_planes)
+static void dust_run_grains(ghip_ctx *ctx, const DustCall &c)
 {
+  const int nd = c.g.ndust;
+  const DustK K = dust_k(c.p);
   if(ctx->dust_model_on)
     {
       const size_t D = (size_t) nd;
-      double *dl = logr && dust_growth(ctx) ? P<double>(ctx->dust_work) + DUST_NPLANES * D + 2 * (D + 1) : nullptr;
+      const bool lr = c.g.log_radius_by_dt && dust_growth(ctx);
+      double *dl = lr ? P<double>(ctx->dust_work) + DUST_NPLANES * D + 2 * (D + 1) : nullptr;
       k_dust_grain<DustM><<<cdiv(nd, 256), 256, 0, ctx->stream>>>(
         nd, P<int>(ctx->dust_idx), ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(ctx->f[GHIP_F_MASS]),
         P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K,
@@ -711,49 +750,55 @@ static void dust_run_grains(ghip_ctx *ctx, int nd, const DustK &K, bool logr)
                                                          P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->dust_work), K);
 }
 
-// the density sums of this context's own list: d7 into dust_work [nd], or with real_pebble_collisions d7 and the
-// three velocity sums into its first four planes
-static int dust_run_density(ghip_ctx *ctx, const ghip_dust_params *p, int nd)
+// k_dust_density for ng grains: this context's own list (ord: its tree order) or imported records.  out holds
+// d7 [ng], or with real_pebble_collisions d7 and the three velocity sums: sum c of grain a at out[a * sa + c * sc]
+template <class G>
+static int dust_launch_density(ghip_ctx *ctx, const ghip_dust_params *p, int ng, const int *ord, const G &grain,
+                               double *out, size_t sa, size_t sc)
 {
   TreeDev &t = ctx->gt;
-  const size_t D = (size_t) nd;
-  const bool vels = dust_pebble(ctx);
-  GCHK(ghip_ensure(ctx, ctx->dust_work, (vels ? 4 : 1) * D * 8 + 256));
-  double *dout = P<double>(ctx->dust_work);
-  const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
   const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
-  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, mass, nullptr};
-  if(vels)
-    k_dust_density<<<cdiv(nd, 64), 64, 0, ctx->stream>>>(
-      nd, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
-      P<int>(t.perm), make_box(p->BoxSize, p->periodic), (double *) nullptr,
-      DustVel{P<double>(ctx->f[GHIP_F_VEL]), dout, 1, D});
+  const int *type = P<int>(ctx->f[GHIP_F_TYPE]);
+  const BoxK b = make_box(p->BoxSize, p->periodic);
+  if(dust_pebble(ctx))
+    k_dust_density<<<cdiv(ng, 64), 64, 0, ctx->stream>>>(ng, ord, grain, ctx->n, pos, mass, type, t.nelem,
+                                                         P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm), b,
+                                                         (double *) nullptr,
+                                                         DustVel{P<double>(ctx->f[GHIP_F_VEL]), out, sa, sc});
   else
-    k_dust_density<<<cdiv(nd, 64), 64, 0, ctx->stream>>>(nd, dord, gl, ctx->n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                         t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                         make_box(p->BoxSize, p->periodic), dout);
+    k_dust_density<<<cdiv(ng, 64), 64, 0, ctx->stream>>>(ng, ord, grain, ctx->n, pos, mass, type, t.nelem,
+                                                         P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm), b, out);
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
 
-// ... and back to the caller: d7 [nd], and the raw d9 sums [nd][3] with real_pebble_collisions
-static int dust_download_density(ghip_ctx *ctx, int nd, double *particle_density, double *particle_velocity)
+// the density sums of this context's own list: d7 into dust_work [nd], or with real_pebble_collisions d7 and the
+// three velocity sums into its first four planes
+static int dust_run_density(ghip_ctx *ctx, const DustCall &c)
 {
+  const int nd = c.g.ndust;
   const size_t D = (size_t) nd;
+  GCHK(ghip_ensure(ctx, ctx->dust_work, (dust_pebble(ctx) ? 4 : 1) * D * 8 + 256));
+  const int *didx = P<int>(ctx->dust_idx);
+  DustGrainLocal gl = {didx, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]), ctx->n,
+                       P<double>(ctx->f[GHIP_F_MASS]), nullptr};
+  return dust_launch_density(ctx, c.p, nd, didx + D, gl, P<double>(ctx->dust_work), 1, D);
+}
+
+// ... and back to the caller: d7 [nd], and the raw d9 sums [nd][3] with real_pebble_collisions
+static int dust_download_density(ghip_ctx *ctx, const DustCall &c)
+{
+  const size_t D = (size_t) c.g.ndust;
   const double *dout = P<double>(ctx->dust_work);
-  if(!dust_pebble(ctx))
-    {
-      HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-      return GHIP_OK;
-    }
-  std::vector<double> h(3 * D);
-  HIPCHK(hipMemcpyAsync(particle_density, dout, D * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(h.data(), dout + D, 3 * D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<double> h(dust_pebble(ctx) ? 3 * D : 0);
+  HIPCHK(hipMemcpyAsync(c.g.particle_density, dout, D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if(dust_pebble(ctx))
+    HIPCHK(hipMemcpyAsync(h.data(), dout + D, 3 * D * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  for(size_t a = 0; a < D; a++)
-    for(int k = 0; k < 3; k++)
-      particle_velocity[3 * a + k] = h[k * D + a];
+  if(dust_pebble(ctx))
+    for(size_t a = 0; a < D; a++)
+      for(int k = 0; k < 3; k++)
+        c.g.particle_velocity[3 * a + k] = h[k * D + a];
   return GHIP_OK;
 }
 
@@ -824,75 +869,65 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
   return GHIP_OK;
 }
 
-// the grain outputs of the drag pass back to the caller's arrays
-// (radius, logr: the planes the model writes under growth, nullptr where the caller has no array for them)
-static int dust_download_grains(ghip_ctx *ctx, int nd, std::vector<double> &h, double *particle_velocity,
-                                double *delta_momentum, double *delta_energy, double *vcoll,
-                                double *radius = nullptr, double *logr = nullptr)
+// The grain outputs of the drag pass back to the caller's arrays.  The two planes the model writes under growth
+// go back here and nowhere else: the radius to a caller of a grains form, LogDustRadius_by_dt where he holds one
+static int dust_download_grains(ghip_ctx *ctx, const DustCall &c, std::vector<double> &h)
 {
-  const size_t D = (size_t) nd;
+  const ghip_dust_grains &g = c.g;
+  const size_t D = (size_t) g.ndust;
   const double *dw = P<double>(ctx->dust_work);
   HIPCHK(hipMemcpyAsync(h.data() + DP_D9 * D, dw + DP_D9 * D, DUST_NOUT * D * 8, hipMemcpyDeviceToHost,
                         ctx->stream));
-  if(dust_growth(ctx) && radius)
-    HIPCHK(hipMemcpyAsync(radius, dw + DP_RAD * D, D * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if(dust_growth(ctx) && logr)
-    HIPCHK(hipMemcpyAsync(logr, dw + DUST_NPLANES * D + 2 * (D + 1), D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if(dust_growth(ctx) && c.grains)
+    HIPCHK(hipMemcpyAsync(g.dust_radius, dw + DP_RAD * D, D * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if(dust_growth(ctx) && g.log_radius_by_dt)
+    HIPCHK(hipMemcpyAsync(g.log_radius_by_dt, dw + DUST_NPLANES * D + 2 * (D + 1), D * 8, hipMemcpyDeviceToHost,
+                          ctx->stream));
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));
   for(size_t a = 0; a < D; a++)
     {
       for(int k = 0; k < 3; k++)
         {
-          particle_velocity[3 * a + k] = h[(DP_D9 + k) * D + a];
-          delta_momentum[3 * a + k] = h[(DP_DMOM + k) * D + a];
+          g.particle_velocity[3 * a + k] = h[(DP_D9 + k) * D + a];
+          g.delta_momentum[3 * a + k] = h[(DP_DMOM + k) * D + a];
         }
-      delta_energy[a] = h[DP_DE * D + a];
-      vcoll[a] = h[DP_VCOLL * D + a];
+      g.delta_energy[a] = h[DP_DE * D + a];
+      g.vcoll[a] = h[DP_VCOLL * D + a];
     }
   return GHIP_OK;
 }
 
-// the two passes on one rank, for the old entry points (grains = false) and the *_grains ones
-static int dust_density_impl(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains &g, bool grains,
-                             const char *who)
+// the two passes on one rank
+static int dust_density_impl(ghip_ctx *ctx, const DustCall &c)
 {
   GHIP_JOIN(ctx);
-  if(g.ndust > 0 && (!g.particle_density || (grains && dust_pebble(ctx) && !g.particle_velocity)))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  GCHK(dust_model_ready(ctx, false, grains, who, "ghip_dust_density_grains"));
-  GCHK(dust_begin(ctx, p, g.ndust, g.dust_idx, false, who));
-  if(g.ndust == 0)
+  GCHK(dust_call_check(ctx, c));
+  GCHK(dust_begin(ctx, c, false));
+  if(c.g.ndust == 0)
     return GHIP_OK;
-  GCHK(dust_run_density(ctx, p, g.ndust));
-  return dust_download_density(ctx, g.ndust, g.particle_density, g.particle_velocity);
+  GCHK(dust_run_density(ctx, c));
+  return dust_download_density(ctx, c);
 }
 
-static int dust_drag_impl(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains &g, bool grains,
-                          const char *who)
+static int dust_drag_impl(ghip_ctx *ctx, const DustCall &c)
 {
   GHIP_JOIN(ctx);
-  const int ndust = g.ndust;
-  if(ndust > 0 && (!g.dust_density || !g.dust_entropy || !g.dust_gasvel || !g.dust_radius || !g.particle_density ||
-                   !g.particle_velocity || !g.delta_momentum || !g.delta_energy || !g.vcoll))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  GCHK(dust_model_ready(ctx, true, grains, who, "ghip_dust_drag_grains"));
-  GCHK(dust_begin(ctx, p, ndust, g.dust_idx, ctx->ngas > 0, who));
+  GCHK(dust_call_check(ctx, c));
+  GCHK(dust_begin(ctx, c, ctx->ngas > 0));
   GCHK(dust_heat_buffer(ctx));
+  const int ndust = c.g.ndust;
   if(ndust == 0)
     return GHIP_OK;
   const size_t D = (size_t) ndust;
-  const DustK K = dust_k(p);
   std::vector<double> h;
-  GCHK(dust_upload_planes(ctx, ndust, g.dust_density, g.dust_entropy, g.dust_gasvel, g.dust_radius,
-                          g.particle_density, g.particle_velocity, g.vcoll, g.log_radius_by_dt, h));
-  dust_run_grains(ctx, ndust, K, g.log_radius_by_dt != nullptr);
+  GCHK(dust_upload_planes(ctx, c, h));
+  dust_run_grains(ctx, c);
   HIPCHK(hipGetLastError());
   double *dw = P<double>(ctx->dust_work);
   long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
   long long npairs = 0;
-  GCHK(dust_scatter(ctx, K, ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
-  return dust_download_grains(ctx, ndust, h, g.particle_velocity, g.delta_momentum, g.delta_energy, g.vcoll,
-                              grains ? g.dust_radius : nullptr, g.log_radius_by_dt);
+  GCHK(dust_scatter(ctx, dust_k(c.p), ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
+  return dust_download_grains(ctx, c, h);
 }
 
 extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
@@ -904,7 +939,7 @@ extern "C" int ghip_dust_density(ghip_ctx *ctx, const ghip_dust_params *p, int n
   g.ndust = ndust;
   g.dust_idx = dust_idx;
   g.particle_density = particle_density;
-  return dust_density_impl(ctx, p, g, false, "ghip_dust_density");
+  return dust_density_impl(ctx, dust_call(p, &g, false, false, "ghip_dust_density", "ghip_dust_density_grains"));
 }
 
 extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndust, const int *dust_idx,
@@ -927,25 +962,21 @@ extern "C" int ghip_dust_drag(ghip_ctx *ctx, const ghip_dust_params *p, int ndus
   g.delta_momentum = delta_momentum;
   g.delta_energy = delta_energy;
   g.vcoll = vcoll;
-  return dust_drag_impl(ctx, p, g, false, "ghip_dust_drag");
+  return dust_drag_impl(ctx, dust_call(p, &g, false, true, "ghip_dust_drag", "ghip_dust_drag_grains"));
 }
 
 extern "C" int ghip_dust_density_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g)
 {
   if(!ctx)
     return GHIP_EINVAL;
-  if(!g)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_density_grains: bad arguments");
-  return dust_density_impl(ctx, p, *g, true, "ghip_dust_density_grains");
+  return dust_density_impl(ctx, dust_call(p, g, true, false, "ghip_dust_density_grains", ""));
 }
 
 extern "C" int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g)
 {
   if(!ctx)
     return GHIP_EINVAL;
-  if(!g)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dust_drag_grains: bad arguments");
-  return dust_drag_impl(ctx, p, *g, true, "ghip_dust_drag_grains");
+  return dust_drag_impl(ctx, dust_call(p, g, true, true, "ghip_dust_drag_grains", ""));
 }
 
 extern "C" int ghip_set_dust_model(ghip_ctx *ctx, const ghip_dust_model *m)
@@ -1047,71 +1078,81 @@ int ghip_dd_dust_groups(ghip_ctx *ctx);   // ghip_dd.hip
 int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
                         int periodic, int *total);
 
+// walk = 0: the params of the two operations as the record
+static DustCall dust_call_dd_args(const void *params, bool drag, const char *who, const char *other)
+{
+  // the arrays of ghip_dust_grains but the two that the model writes, with the params inside and a const radius
+  const ghip_dd_dust_args &a = *reinterpret_cast<const ghip_dd_dust_args *>(params);
+  ghip_dust_grains g = {};
+  g.ndust = a.ndust;
+  g.dust_idx = a.dust_idx;
+  g.particle_density = a.particle_density;
+  g.dust_density = a.dust_density;
+  g.dust_entropy = a.dust_entropy;
+  g.dust_gasvel = a.dust_gasvel;
+  g.dust_radius = const_cast<double *>(a.dust_radius);   // (read only: the switches that write it are refused here)
+  g.particle_velocity = a.particle_velocity;
+  g.delta_momentum = a.delta_momentum;
+  g.delta_energy = a.delta_energy;
+  g.vcoll = a.vcoll;
+  g.counts = a.counts;
+  return dust_call(a.p, &g, false, drag, who, other);
+}
+
 int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
   GHIP_JOIN(ctx);
   const bool grains = walk == GHIP_DUST_GRAINS_FORM;
   const bool drag = op == GHIP_DD_DUST_DRAG;
   const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
+  const char *other = "walk = GHIP_DUST_GRAINS_FORM with ghip_dd_dust_grains_args";
   if(walk != 0 && !grains)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: walk = %d is neither 0 nor GHIP_DUST_GRAINS_FORM", who, walk);
-  ctx->dd.du_radius = ctx->dd.du_logr = nullptr;
+  DustCall &c = ctx->dd.dust;
   if(grains)
     {
-      // the same operation with the arrays of ghip_dust_grains: the members of ghip_dd_dust_args and the two
-      // planes the model writes
       const ghip_dd_dust_grains_args &G = *reinterpret_cast<const ghip_dd_dust_grains_args *>(params);
-      const ghip_dust_grains &g = G.g;
-      ghip_dd_dust_args &a = ctx->dd.dust;
-      a.p = G.p;
-      a.ndust = g.ndust;
-      a.dust_idx = g.dust_idx;
-      a.particle_density = g.particle_density;
-      a.dust_density = g.dust_density;
-      a.dust_entropy = g.dust_entropy;
-      a.dust_gasvel = g.dust_gasvel;
-      a.dust_radius = g.dust_radius;
-      a.particle_velocity = g.particle_velocity;
-      a.delta_momentum = g.delta_momentum;
-      a.delta_energy = g.delta_energy;
-      a.vcoll = g.vcoll;
-      a.counts = g.counts;
-      ctx->dd.du_radius = g.dust_radius;
-      ctx->dd.du_logr = g.log_radius_by_dt;
+      c = dust_call(G.p, &G.g, true, drag, who, other);
     }
   else
-    ctx->dd.dust = *reinterpret_cast<const ghip_dd_dust_args *>(params);
-  const ghip_dd_dust_args &A = ctx->dd.dust;
-  if(!A.p || A.ndust < 0 || (A.ndust > 0 && (!A.dust_idx || !A.particle_density)))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  if(!drag && grains && dust_pebble(ctx) && A.ndust > 0 && !A.particle_velocity)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  GCHK(dust_model_ready(ctx, drag, grains, who, "walk = GHIP_DUST_GRAINS_FORM with ghip_dd_dust_grains_args"));
-  if(drag && A.ndust > 0 && (!A.dust_density || !A.dust_entropy || !A.dust_gasvel || !A.dust_radius ||
-                             !A.particle_velocity || !A.delta_momentum || !A.delta_energy || !A.vcoll))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+    c = dust_call_dd_args(params, drag, who, other);
+  GCHK(dust_call_check(ctx, c));
   // (after GHIP_DD_BH_SWALLOW the trees are marked stale for their moments; their geometry still holds)
   if(!ctx->gt.built && !ctx->dd.geom_kept)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_GRAVITY of this step first", who);
   if(drag && !ctx->st.built && !ctx->dd.geom_kept)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_DENSITY of this step first", who);
-  if(A.counts)
+  if(c.g.counts)
     for(int k = 0; k < 4; k++)
-      A.counts[k] = 0;
+      c.g.counts[k] = 0;
   ctx->dd.du_sent = ctx->dd.du_recvd = 0;
   return GHIP_OK;
+}
+
+// what the operation sent, received and paired, when it ends
+static void dust_write_counts(const DDState &D, long long npairs)
+{
+  long long *counts = D.dust.g.counts;
+  if(!counts)
+    return;
+  counts[0] = D.du_sent;
+  counts[1] = D.du_recvd;
+  if(D.dust.drag)
+    counts[2] = npairs;
+  counts[3] = D.bytes_sent[D.op];
 }
 
 int ghip_dd_dust_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
-  const ghip_dd_dust_args &A = D.dust;
+  const DustCall &c = D.dust;
+  const ghip_dust_params *p = c.p;
   hipStream_t st = ctx->stream;
-  const bool drag = D.op == GHIP_DD_DUST_DRAG;
+  const bool drag = c.drag;
   const bool vels = !drag && dust_pebble(ctx);   // (the density pass carries d7 and the three velocity sums)
   const int npart = vels ? 4 : 1;                // doubles of a partial sum that goes home
-  const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
-  const int nd = A.ndust, n = ctx->n;
+  const char *who = c.who;
+  const int nd = c.g.ndust, n = ctx->n;
   const size_t Dn = (size_t) nd;
   const int *didx = P<int>(ctx->dust_idx), *dord = didx + Dn;
   const double *pos = P<double>(ctx->f[GHIP_F_POS]), *hsml = P<double>(ctx->f[GHIP_F_HSML]),
@@ -1124,18 +1165,17 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
         GCHK(dust_heat_buffer(ctx));   // (this shard holds DragHeating from now on)
       if(nd > 0)
         {
-          GCHK(dust_upload_list(ctx, nd, A.dust_idx, who));
+          GCHK(dust_upload_list(ctx, nd, c.g.dust_idx, who));
           didx = P<int>(ctx->dust_idx);
           dord = didx + Dn;
           if(drag)
             {
               std::vector<double> h;
-              GCHK(dust_upload_planes(ctx, nd, A.dust_density, A.dust_entropy, A.dust_gasvel, A.dust_radius,
-                                      A.particle_density, A.particle_velocity, A.vcoll, D.du_logr, h));
-              dust_run_grains(ctx, nd, dust_k(A.p), D.du_logr != nullptr);
+              GCHK(dust_upload_planes(ctx, c, h));
+              dust_run_grains(ctx, c);
             }
           else
-            GCHK(dust_run_density(ctx, A.p, nd));
+            GCHK(dust_run_density(ctx, c));
           HIPCHK(hipGetLastError());
           GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
           k_dust_slots<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(D.du_slot));
@@ -1147,7 +1187,7 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
   if(D.phase == SELECT)
     {
       int total = 0;
-      GCHK(ghip_dd_dust_select(ctx, who, nd, dord, didx, A.p->BoxSize, A.p->periodic, &total));
+      GCHK(ghip_dd_dust_select(ctx, who, nd, dord, didx, p->BoxSize, p->periodic, &total));
       GCHK(ghip_ensure(ctx, D.du_send, (size_t) (total > 0 ? total : 1) * recd * 8));
       if(total > 0)
         {
@@ -1172,20 +1212,8 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
       D.du_recvd = nimp;
       GCHK(ghip_ensure(ctx, D.du_part, (size_t) (nimp > 0 ? nimp : 1) * npart * 8));
       if(nimp > 0)
-        {
-          TreeDev &t = ctx->gt;
-          DustGrainRec gr = {P<double>(D.du_recv), DUST_REC_DENS};
-          if(vels)
-            k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(
-              nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]), t.nelem, P<int4>(t.lk), P<double4>(t.cl),
-              P<int>(t.perm), make_box(A.p->BoxSize, A.p->periodic), (double *) nullptr,
-              DustVel{P<double>(ctx->f[GHIP_F_VEL]), P<double>(D.du_part), 4, 1});
-          else
-            k_dust_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, n, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                          t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<int>(t.perm),
-                                                          make_box(A.p->BoxSize, A.p->periodic), P<double>(D.du_part));
-          HIPCHK(hipGetLastError());
-        }
+        GCHK(dust_launch_density(ctx, p, nimp, nullptr, DustGrainRec{P<double>(D.du_recv), DUST_REC_DENS},
+                                 P<double>(D.du_part), 4, 1));
       int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];
       for(int r = 0; r < D.nranks; r++)
         {
@@ -1218,15 +1246,10 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
                     P<double>(D.du_back) + D.x.roff[r], dout);
               }
           HIPCHK(hipGetLastError());
-          GCHK(dust_download_density(ctx, nd, A.particle_density, A.particle_velocity));
+          GCHK(dust_download_density(ctx, c));
         }
       HIPCHK(ghip_stream_sync(ctx, st));
-      if(A.counts)
-        {
-          A.counts[0] = D.du_sent;
-          A.counts[1] = D.du_recvd;
-          A.counts[3] = D.bytes_sent[D.op];
-        }
+      dust_write_counts(D, 0);
       return 0;
     }
   if(D.phase == IMPORTED && drag)
@@ -1247,21 +1270,14 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
           HIPCHK(hipGetLastError());
         }
       long long npairs = 0;
-      GCHK(dust_scatter(ctx, dust_k(A.p), nd, P<double>(ctx->dust_work), nimp, rec, cw, dcnt, doff, &npairs));
+      GCHK(dust_scatter(ctx, dust_k(p), nd, P<double>(ctx->dust_work), nimp, rec, cw, dcnt, doff, &npairs));
       if(nd > 0)
         {
           std::vector<double> h((size_t) DUST_NPLANES * Dn);
-          GCHK(dust_download_grains(ctx, nd, h, A.particle_velocity, A.delta_momentum, A.delta_energy, A.vcoll,
-                                    D.du_radius, D.du_logr));
+          GCHK(dust_download_grains(ctx, c, h));
         }
       HIPCHK(ghip_stream_sync(ctx, st));
-      if(A.counts)
-        {
-          A.counts[0] = D.du_sent;
-          A.counts[1] = D.du_recvd;
-          A.counts[2] = npairs;
-          A.counts[3] = D.bytes_sent[D.op];
-        }
+      dust_write_counts(D, npairs);
       return 0;
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the dust passes have no phase %d", D.phase);

@@ -178,6 +178,17 @@ struct SinkIter
   std::vector<int> todo;
 };
 
+// One dust pass as ghip_dust.hip runs it: each of the four entry forms (positional, *_grains, GHIP_DD_DUST_* with
+// walk = 0 or GHIP_DUST_GRAINS_FORM) fills this once, and everything below the entry reads only it
+struct DustCall
+{
+  const ghip_dust_params *p = nullptr;
+  ghip_dust_grains g = {};
+  bool grains = false;            // the caller has arrays for what the model writes (d9 sums, radius)
+  bool drag = false;
+  const char *who = "", *other = "";   // the entry in messages; the form that dust_model_ready points to
+};
+
 #define DD_NOPS (GHIP_DD_PM_NONPERIODIC + 1)   // operations of ghip_dd_begin, 0 = none (dd_ops[] in ghip_dd.hip)
 
 struct DDState
@@ -255,8 +266,7 @@ struct DDState
   SinkIter sk_it;                 // h iteration state of ALL sinks (identical on all ranks)
   // the dust passes on shards (ghip_dust.hip): this shard's grains go to the shards their spheres reach,
   // partial d7 come back (density), drag records are scattered into every shard's own gas (drag)
-  ghip_dd_dust_args dust;         // arguments of the operation in progress
-  double *du_radius = nullptr, *du_logr = nullptr;   // ... in the GHIP_DUST_GRAINS_FORM: the planes the model writes
+  DustCall dust;                  // the operation in progress
   DevBuf du_mask;                 // u64[n]: ranks each local grain goes to (by local particle index)
   DevBuf du_slot;                 // i32[n]: list slot of each local grain (read where du_mask is set)
   DevBuf du_list;                 // i32: per destination, the local particle indices sent (ascending)

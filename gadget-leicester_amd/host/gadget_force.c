@@ -93,6 +93,33 @@ static inline double *ppp_numngb(int i)
 {
   return Lay.p_numngb >= 0 ? PF64(i, Lay.p_numngb) : SF64(i, Lay.s_numngb);
 }
+/* A record member as a plane and back: ncomp doubles at offset off of the P records idx[0, n) (idx == NULL: the
+ * records 0 .. n-1), or of the SphP records 0 .. N_gas-1.  A member the bound layout does not have (off < 0) gathers
+ * zeros and is not scattered */
+static void rec_gather_p(const int *idx, int n, int off, int ncomp, double *dst)
+{
+  for(int k = 0; k < n; k++)
+    for(int c = 0; c < ncomp; c++)
+      dst[(size_t) ncomp * k + c] = off >= 0 ? PF64(idx ? idx[k] : k, off)[c] : 0.0;
+}
+static void rec_scatter_p(const int *idx, int n, int off, int ncomp, const double *src)
+{
+  for(int k = 0; off >= 0 && k < n; k++)
+    for(int c = 0; c < ncomp; c++)
+      PF64(idx ? idx[k] : k, off)[c] = src[(size_t) ncomp * k + c];
+}
+static void rec_gather_s(int off, int ncomp, double *dst)
+{
+  for(int i = 0; i < N_gas; i++)
+    for(int c = 0; c < ncomp; c++)
+      dst[(size_t) ncomp * i + c] = off >= 0 ? SF64(i, off)[c] : 0.0;
+}
+static void rec_scatter_s(int off, int ncomp, const double *src)
+{
+  for(int i = 0; off >= 0 && i < N_gas; i++)
+    for(int c = 0; c < ncomp; c++)
+      SF64(i, off)[c] = src[(size_t) ncomp * i + c];
+}
 static void *records_p(void) { return RecP ? (void *) RecP : (void *) P; }
 static void *records_s(void) { return RecP ? (void *) RecS : (void *) SphP; }
 
@@ -1184,17 +1211,12 @@ static int density_of_sinks(const ghip_dens_params *d)
           const int o_vel = type == 5 ? BhLay.p_bh_gasvel : BhLay.p_dust_gasvel;
           for(k = 0; k < n; k++)
             {
-              const int i = idx[k];
-              *ppp_hsml(i) = hs[k];
-              *ppp_numngb(i) = nn[k];
-              if(o_rho >= 0)
-                *PF64(i, o_rho) = rho[k];
-              if(o_ent >= 0)
-                *PF64(i, o_ent) = ent[k];
-              if(o_vel >= 0)
-                for(int c = 0; c < 3; c++)
-                  PF64(i, o_vel)[c] = vel[3 * (size_t) k + c];
+              *ppp_hsml(idx[k]) = hs[k];
+              *ppp_numngb(idx[k]) = nn[k];
             }
+          rec_scatter_p(idx, n, o_rho, 1, rho);
+          rec_scatter_p(idx, n, o_ent, 1, ent);
+          rec_scatter_p(idx, n, o_vel, 3, vel);
         }
       free(buf);
       if(chk(rc, "ghip_sink_density"))
@@ -1350,11 +1372,8 @@ static int visc_begin(const char *who)
   double *a = (double *) scratch(((size_t) 2 * N_gas + 1) * 8);
   if(!a)
     return -1;
-  for(int i = 0; i < N_gas; i++)
-    {
-      a[i] = *SF64(i, ViscLay.s_alpha);
-      a[(size_t) N_gas + i] = *SF64(i, ViscLay.s_dtalpha);
-    }
+  rec_gather_s(ViscLay.s_alpha, 1, a);
+  rec_gather_s(ViscLay.s_dtalpha, 1, a + N_gas);
   int rc = chk(ghip_visc_set_alpha(Ctx, a, a + N_gas), "ghip_visc_set_alpha");
   free(a);
   return rc;
@@ -1376,11 +1395,8 @@ static int visc_end(void)
       free(a);
       return -1;
     }
-  for(int i = 0; i < N_gas; i++)
-    {
-      *SF64(i, ViscLay.s_alpha) = a[i];
-      *SF64(i, ViscLay.s_dtalpha) = a[(size_t) N_gas + i];
-    }
+  rec_scatter_s(ViscLay.s_alpha, 1, a);
+  rec_scatter_s(ViscLay.s_dtalpha, 1, a + N_gas);
   free(a);
   return 0;
 }
@@ -1597,14 +1613,10 @@ static int integration_begin(void)
     return -1;
   double *drag = IntLay.s_drag_accel >= 0 ? buf : NULL;
   double *ddm = IntLay.p_delta_dust_momentum >= 0 ? buf + 3 * (size_t) ng + 1 : NULL;
-  for(int i = 0; i < ng; i++)
-    for(int j = 0; j < 3; j++)
-      {
-        if(drag)
-          drag[3 * (size_t) i + j] = SF64(i, IntLay.s_drag_accel)[j];
-        if(ddm)
-          ddm[3 * (size_t) i + j] = PF64(i, IntLay.p_delta_dust_momentum)[j];
-      }
+  if(drag)
+    rec_gather_s(IntLay.s_drag_accel, 3, drag);
+  if(ddm)
+    rec_gather_p(NULL, ng, IntLay.p_delta_dust_momentum, 3, ddm);
   int rc = chk(ghip_kick_set_fields(Ctx, drag, ddm, NULL), "ghip_kick_set_fields");
   free(buf);
   return rc;
@@ -1626,9 +1638,7 @@ static int integration_end(const short *binold)
           free(drag);
           return -1;
         }
-      for(int i = 0; i < N_gas; i++)
-        for(int j = 0; j < 3; j++)
-          SF64(i, IntLay.s_drag_accel)[j] = drag[3 * (size_t) i + j];
+      rec_scatter_s(IntLay.s_drag_accel, 3, drag);
       free(drag);
     }
   const int sfr = IntLay.sfr > 0 && BinSfr && IntLay.s_sfr >= 0;
@@ -2104,8 +2114,7 @@ static int bh_marks_to_device(void)
   unsigned int *sw = (unsigned int *) (inj + N_gas);
   for(int i = 0; i < NumPart; i++)
     sw[i] = *(unsigned int *) (prec(i) + BhLay.p_swallowid);
-  for(int i = 0; i < N_gas; i++)
-    inj[i] = BhLay.s_injected_bh_energy >= 0 ? *SF64(i, BhLay.s_injected_bh_energy) : 0.0;
+  rec_gather_s(BhLay.s_injected_bh_energy, 1, inj);
   int rc = ghip_sink_set_marks(Ctx, sw, inj);
   free(inj);
   return chk(rc, "ghip_sink_set_marks") ? -1 : 0;
@@ -2122,14 +2131,10 @@ static int bh_marks_to_records(int with_mass)
   if(rc == GHIP_OK)
     {
       for(int i = 0; i < NumPart; i++)
-        {
-          *(unsigned int *) (prec(i) + BhLay.p_swallowid) = sw[i];
-          if(with_mass)
-            *PF64(i, Lay.p_mass) = mass[i];   /* blackhole.c:1290, 1312, 1330: a victim's mass becomes 0 */
-        }
-      if(BhLay.s_injected_bh_energy >= 0)
-        for(int i = 0; i < N_gas; i++)
-          *SF64(i, BhLay.s_injected_bh_energy) = inj[i];
+        *(unsigned int *) (prec(i) + BhLay.p_swallowid) = sw[i];
+      if(with_mass)   /* blackhole.c:1290, 1312, 1330: a victim's mass becomes 0 */
+        rec_scatter_p(NULL, NumPart, Lay.p_mass, 1, mass);
+      rec_scatter_s(BhLay.s_injected_bh_energy, 1, inj);
     }
   free(sw);
   free(inj);
@@ -2147,11 +2152,9 @@ static int bh_evaluate_batch(int n, const int *idx)
   double *rho = md + n;
   unsigned int *id = (unsigned int *) (md + 2 * m);
   for(int k = 0; k < n; k++)
-    {
-      id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
-      md[k] = *PF64(idx[k], BhLay.p_bh_mdot);
-      rho[k] = *PF64(idx[k], BhLay.p_bh_density);
-    }
+    id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
+  rec_gather_p(idx, n, BhLay.p_bh_mdot, 1, md);
+  rec_gather_p(idx, n, BhLay.p_bh_density, 1, rho);
   ghip_bh_params b;
   fill_bh_params(&b);
   int rc;
@@ -2184,10 +2187,8 @@ static int bh_swallow_batch(int n, const int *idx)
   double *bhm = buf, *am = buf + m, *ab = buf + 2 * m, *ad = buf + 3 * m, *mom = buf + 4 * m;
   unsigned int *id = (unsigned int *) (buf + 7 * m);
   for(int k = 0; k < n; k++)
-    {
-      id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
-      bhm[k] = *PF64(idx[k], BhLay.p_bh_mass);
-    }
+    id[k] = *(unsigned int *) (prec(idx[k]) + BhLay.p_id);
+  rec_gather_p(idx, n, BhLay.p_bh_mass, 1, bhm);
   ghip_bh_params b;
   fill_bh_params(&b);
   long long counts[3] = { 0, 0, 0 };
@@ -2507,6 +2508,32 @@ static int dust_ready(const char *who, int drag, int **idx_out)
   return n;
 }
 
+/* One dust pass (op: GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG) through the entry that serves this run: on ranks the
+ * collective, where every rank's grains meet every rank's particles (the exports of dust.c:60-261, 560-746); on one
+ * rank the *_grains call when a model is bound, else the positional call.  Nonzero: a failure has ended the run */
+static int dust_dispatch(int op, const ghip_dust_params *d, ghip_dust_grains *g, const char *what)
+{
+  const int drag = op == GHIP_DD_DUST_DRAG;
+  if(NTask > 1)
+    {
+      /* (dust_ready refuses the switches that write the radius on ranks: nothing to bring back) */
+      ghip_dd_dust_grains_args a;
+      a.p = d;
+      a.g = *g;
+      a.g.log_radius_by_dt = NULL;
+      a.g.counts = NULL;
+      return dd_collective(op, &a, GHIP_DUST_GRAINS_FORM, what);
+    }
+  if(dust_model_bound())
+    return drag ? chk(ghip_dust_drag_grains(Ctx, d, g), "ghip_dust_drag")
+                : chk(ghip_dust_density_grains(Ctx, d, g), "ghip_dust_density_grains");
+  if(drag)
+    return chk(ghip_dust_drag(Ctx, d, g->ndust, g->dust_idx, g->dust_density, g->dust_entropy, g->dust_gasvel,
+                              g->dust_radius, g->particle_density, g->particle_velocity, g->delta_momentum,
+                              g->delta_energy, g->vcoll), "ghip_dust_drag");
+  return chk(ghip_dust_density(Ctx, d, g->ndust, g->dust_idx, g->particle_density), "ghip_dust_density");
+}
+
 /* dust.c:60-261 */
 void dust_density(void)
 {
@@ -2522,41 +2549,20 @@ void dust_density(void)
       free(idx);
       return;
     }
-  double *d9 = rho + (size_t) n + 1;
   ghip_dust_params d;
   fill_dust_params(&d);
-  int rc;
-  if(NTask > 1)
+  ghip_dust_grains g;
+  memset(&g, 0, sizeof(g));
+  g.ndust = n;
+  g.dust_idx = idx;
+  g.particle_density = rho;
+  g.particle_velocity = rho + (size_t) n + 1;
+  if(dust_dispatch(GHIP_DD_DUST_DENSITY, &d, &g, "dust_density (ranks)") == 0)
     {
-      /* every rank's grains meet every rank's Type-2 particles (dust.c:60-261's export) */
-      ghip_dd_dust_args a;
-      memset(&a, 0, sizeof(a));
-      a.p = &d;
-      a.ndust = n;
-      a.dust_idx = idx;
-      a.particle_density = rho;
-      rc = dd_collective(GHIP_DD_DUST_DENSITY, &a, 0, "dust_density (ranks)") ? GHIP_EDEVICE : GHIP_OK;
+      rec_scatter_p(idx, n, DustLay.p_particle_density, 1, rho);   /* dust.c:242-245 */
+      if(vels)
+        rec_scatter_p(idx, n, DustLay.p_particle_velocity, 3, g.particle_velocity);
     }
-  else if(dust_model_bound())
-    {
-      ghip_dust_grains g;
-      memset(&g, 0, sizeof(g));
-      g.ndust = n;
-      g.dust_idx = idx;
-      g.particle_density = rho;
-      g.particle_velocity = d9;
-      rc = chk(ghip_dust_density_grains(Ctx, &d, &g), "ghip_dust_density_grains") ? GHIP_EDEVICE : GHIP_OK;
-    }
-  else
-    rc = chk(ghip_dust_density(Ctx, &d, n, idx, rho), "ghip_dust_density") ? GHIP_EDEVICE : GHIP_OK;
-  if(rc == GHIP_OK)
-    for(int k = 0; k < n; k++)
-      {
-        *PF64(idx[k], DustLay.p_particle_density) = rho[k];   /* dust.c:242-245 */
-        if(vels)
-          for(int c = 0; c < 3; c++)
-            PF64(idx[k], DustLay.p_particle_velocity)[c] = d9[3 * (size_t) k + c];
-      }
   free(rho);
   free(idx);
 }
@@ -2570,8 +2576,8 @@ void dust_drag(void)
     return;
   const size_t m = (size_t) n + 1, nall = (size_t) (NumPart > 0 ? NumPart : 1);
   const size_t ng = (size_t) (N_gas > 0 ? N_gas : 1);
-  /* per grain: rho, A, gasvel[3], radius, d7, d9[3], dmom[3], dE, vcoll (15); per particle: vel[3]
-   * + per gas particle: entropy, heating */
+  /* per grain: rho, A, gasvel[3], radius, d7, d9[3], dmom[3], dE, vcoll, LogDustRadius_by_dt (16); per particle:
+   * vel[3] + per gas particle: entropy, heating */
   double *buf = (double *) scratch((16 * m + 3 * nall + 2 * ng) * sizeof(double));
   if(!buf)
     {
@@ -2579,78 +2585,44 @@ void dust_drag(void)
       return;
     }
   double *rho = buf, *ent = buf + m, *gv = buf + 2 * m, *rad = buf + 5 * m, *d7 = buf + 6 * m,
-         *d9 = buf + 7 * m, *dmom = buf + 10 * m, *de = buf + 13 * m, *vc = buf + 14 * m;
-  double *logr = buf + 15 * m;   /* LogDustRadius_by_dt (gadget_force_bind_dust_model) */
+         *d9 = buf + 7 * m, *dmom = buf + 10 * m, *de = buf + 13 * m, *vc = buf + 14 * m, *logr = buf + 15 * m;
   double *vel = buf + 16 * m, *sent = vel + 3 * nall, *heat = sent + ng;
   const int grow = DustModelLay.growth > 0;
   const int have_logr = grow && DustModelLay.p_log_radius_by_dt >= 0;
-  for(int k = 0; k < n; k++)
-    {
-      const int i = idx[k];
-      rho[k] = *PF64(i, BhLay.p_dust_density);
-      ent[k] = *PF64(i, BhLay.p_dust_entropy);
-      rad[k] = *PF64(i, DustLay.p_radius);
-      d7[k] = *PF64(i, DustLay.p_particle_density);
-      vc[k] = *PF64(i, DustLay.p_vcoll);
-      if(have_logr)
-        logr[k] = *PF64(i, DustModelLay.p_log_radius_by_dt);
-      for(int c = 0; c < 3; c++)
-        {
-          gv[3 * (size_t) k + c] = PF64(i, BhLay.p_dust_gasvel)[c];
-          d9[3 * (size_t) k + c] = PF64(i, DustLay.p_particle_velocity)[c];
-        }
-    }
+  rec_gather_p(idx, n, BhLay.p_dust_density, 1, rho);
+  rec_gather_p(idx, n, BhLay.p_dust_entropy, 1, ent);
+  rec_gather_p(idx, n, BhLay.p_dust_gasvel, 3, gv);
+  rec_gather_p(idx, n, DustLay.p_radius, 1, rad);
+  rec_gather_p(idx, n, DustLay.p_particle_density, 1, d7);
+  rec_gather_p(idx, n, DustLay.p_particle_velocity, 3, d9);
+  rec_gather_p(idx, n, DustLay.p_vcoll, 1, vc);
+  if(have_logr)
+    rec_gather_p(idx, n, DustModelLay.p_log_radius_by_dt, 1, logr);
   /* SphP[].dh.DragHeating accumulates on top of what the records hold */
-  for(int j = 0; j < N_gas; j++)
-    heat[j] = DustLay.s_drag_heating >= 0 ? *SF64(j, DustLay.s_drag_heating) : 0.0;
+  rec_gather_s(DustLay.s_drag_heating, 1, heat);
   ghip_dust_params d;
   fill_dust_params(&d);
+  ghip_dust_grains g;
+  memset(&g, 0, sizeof(g));
+  g.ndust = n;
+  g.dust_idx = idx;
+  g.particle_density = d7;
+  g.dust_density = rho;
+  g.dust_entropy = ent;
+  g.dust_gasvel = gv;
+  g.dust_radius = rad;
+  g.particle_velocity = d9;
+  g.delta_momentum = dmom;
+  g.delta_energy = de;
+  g.vcoll = vc;
+  g.log_radius_by_dt = have_logr ? logr : NULL;
   int rc = ghip_dust_set_drag_heating(Ctx, heat);
-  if(rc == GHIP_OK && NTask > 1)
+  if(rc == GHIP_OK && dust_dispatch(GHIP_DD_DUST_DRAG, &d, &g, "dust_drag (ranks)"))
     {
-      /* the grains' drag records to the ranks their spheres reach; every rank scatters into its own gas
-       * (dust.c:560-746's export) */
-      ghip_dd_dust_args a;
-      memset(&a, 0, sizeof(a));
-      a.p = &d;
-      a.ndust = n;
-      a.dust_idx = idx;
-      a.particle_density = d7;
-      a.dust_density = rho;
-      a.dust_entropy = ent;
-      a.dust_gasvel = gv;
-      a.dust_radius = rad;
-      a.particle_velocity = d9;
-      a.delta_momentum = dmom;
-      a.delta_energy = de;
-      a.vcoll = vc;
-      if(dd_collective(GHIP_DD_DUST_DRAG, &a, 0, "dust_drag (ranks)"))
-        {
-          free(buf);
-          free(idx);
-          return;
-        }
+      free(buf);
+      free(idx);
+      return;
     }
-  else if(rc == GHIP_OK && dust_model_bound())
-    {
-      ghip_dust_grains g;
-      memset(&g, 0, sizeof(g));
-      g.ndust = n;
-      g.dust_idx = idx;
-      g.particle_density = d7;
-      g.dust_density = rho;
-      g.dust_entropy = ent;
-      g.dust_gasvel = gv;
-      g.dust_radius = rad;
-      g.particle_velocity = d9;
-      g.delta_momentum = dmom;
-      g.delta_energy = de;
-      g.vcoll = vc;
-      g.log_radius_by_dt = have_logr ? logr : NULL;
-      rc = ghip_dust_drag_grains(Ctx, &d, &g);
-    }
-  else if(rc == GHIP_OK)
-    rc = ghip_dust_drag(Ctx, &d, n, idx, rho, ent, gv, rad, d7, d9, dmom, de, vc);
   if(rc == GHIP_OK)
     rc = ghip_get_field(Ctx, GHIP_F_VEL, vel);
   if(rc == GHIP_OK && N_gas > 0)
@@ -2659,32 +2631,24 @@ void dust_drag(void)
     rc = ghip_dust_get_drag_heating(Ctx, heat);
   if(rc == GHIP_OK)
     {
+      rec_scatter_p(idx, n, DustLay.p_particle_velocity, 3, d9);
+      rec_scatter_p(idx, n, DustLay.p_delta_momentum, 3, dmom);
       for(int k = 0; k < n; k++)
-        {
-          const int i = idx[k];
-          for(int c = 0; c < 3; c++)
-            {
-              PF64(i, Lay.p_vel)[c] = vel[3 * (size_t) i + c];
-              PF64(i, DustLay.p_particle_velocity)[c] = d9[3 * (size_t) k + c];
-              PF64(i, DustLay.p_delta_momentum)[c] = dmom[3 * (size_t) k + c];
-              if(DustLay.p_new_drag_acc >= 0)
-                PF64(i, DustLay.p_new_drag_acc)[c] = 0.;   /* dust.c:333 */
-            }
-          *PF64(i, DustLay.p_delta_energy) = de[k];
-          *PF64(i, DustLay.p_vcoll) = vc[k];
-          if(grow && NTask <= 1)   /* dust.c:551-567, 589; :465 */
-            *PF64(i, DustLay.p_radius) = rad[k];
-          if(have_logr && NTask <= 1)
-            *PF64(i, DustModelLay.p_log_radius_by_dt) = logr[k];
-        }
-      for(int j = 0; j < N_gas; j++)
-        {
-          for(int c = 0; c < 3; c++)
-            PF64(j, Lay.p_vel)[c] = vel[3 * (size_t) j + c];
-          *SF64(j, Lay.s_entropy) = sent[j];
-          if(DustLay.s_drag_heating >= 0)
-            *SF64(j, DustLay.s_drag_heating) = heat[j];
-        }
+        for(int c = 0; c < 3; c++)
+          {
+            PF64(idx[k], Lay.p_vel)[c] = vel[3 * (size_t) idx[k] + c];
+            if(DustLay.p_new_drag_acc >= 0)
+              PF64(idx[k], DustLay.p_new_drag_acc)[c] = 0.;   /* dust.c:333 */
+          }
+      rec_scatter_p(idx, n, DustLay.p_delta_energy, 1, de);
+      rec_scatter_p(idx, n, DustLay.p_vcoll, 1, vc);
+      if(grow && NTask <= 1)   /* dust.c:551-567, 589; :465 */
+        rec_scatter_p(idx, n, DustLay.p_radius, 1, rad);
+      if(have_logr && NTask <= 1)
+        rec_scatter_p(idx, n, DustModelLay.p_log_radius_by_dt, 1, logr);
+      rec_scatter_p(NULL, N_gas, Lay.p_vel, 3, vel);
+      rec_scatter_s(Lay.s_entropy, 1, sent);
+      rec_scatter_s(DustLay.s_drag_heating, 1, heat);
     }
   free(buf);
   free(idx);

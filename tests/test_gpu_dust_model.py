@@ -457,3 +457,79 @@ def test_dropin_refuses_the_model_on_more_than_one_rank():
         assert np.array_equal(P, keep)
     finally:
         host.close()
+
+
+# ---- 8. the argument rules, one set for the four entry forms ----------------------------------------
+DRAG_ARRAYS = ("dust_density", "dust_entropy", "dust_gasvel", "dust_radius", "particle_density", "particle_velocity",
+               "delta_momentum", "delta_energy", "vcoll")
+
+
+def _call_form(B, f, form, drag, p, g):
+    """one dust pass on context f with the arrays of the DustGrains g, through entry form `form` -> return code"""
+    L, h = f.L, f.h
+    if form == "positional" and drag:
+        return L.ghip_dust_drag(h, C.byref(p), g.ndust, g.dust_idx, g.dust_density, g.dust_entropy, g.dust_gasvel,
+                                g.dust_radius, g.particle_density, g.particle_velocity, g.delta_momentum,
+                                g.delta_energy, g.vcoll)
+    if form == "positional":
+        return L.ghip_dust_density(h, C.byref(p), g.ndust, g.dust_idx, g.particle_density)
+    if form == "grains":
+        return (L.ghip_dust_drag_grains if drag else L.ghip_dust_density_grains)(h, C.byref(p), C.byref(g))
+    if form == "dd":
+        A = B.DdDustArgs()
+        for k, _ in B.DdDustArgs._fields_[1:]:
+            setattr(A, k, getattr(g, k))
+    else:
+        A = B.DdDustGrainsArgs()
+        A.g = g
+    A.p = C.pointer(p)
+    return L.ghip_dd_begin(h, B.DD_DUST_DRAG if drag else B.DD_DUST_DENSITY, C.cast(C.byref(A), C.c_void_p),
+                           B.DUST_GRAINS_FORM if form == "dd_grains" else 0)
+
+
+def test_every_form_refuses_a_missing_array_alike():
+    """Each member a pass requires set to NULL in turn, ndust > 0, in all four forms: GHIP_EINVAL "bad arguments",
+    nothing launched.  Required: the list and d7; in the drag pass its nine arrays; in the density pass of the
+    grains forms d9 under real_pebble_collisions.  A NULL log_radius_by_dt is accepted."""
+    case = DC.case(1)
+    B, fp = _device(case)
+    T = DdModel(case, 2)
+    try:
+        p = case.gparams()
+        d7, d9 = case.base()
+        f0, o, local = T.S.fp[0], T.lists[0], T.local[0]
+        assert len(local) > 0
+        kw = lambda s: dict(particle_density=d7[s], dust_density=case.rho[s], dust_entropy=case.ent[s],
+                            dust_gasvel=case.gasvel[s], dust_radius=case.radius[s], particle_velocity=d9[s],
+                            vcoll=case.vcoll[s], log_radius_by_dt=case.logr0[s])
+        one = B.dust_grains(case.dust, **kw(slice(None)))
+        shard = B.dust_grains(local, **kw(o))
+        full = case.model(*DC.ALL_SIX)
+        fp.sync()
+        fp.run_begin(1)
+        for form in ("positional", "grains", "dd", "dd_grains"):
+            f, (g, _) = (fp, one) if form in ("positional", "grains") else (f0, shard)
+            grains = form in ("grains", "dd_grains")
+            # (the forms without arrays for what the model writes refuse growth and real_pebble_collisions)
+            f.set_dust_model(case.gmodel(full if grains else case.model("epstein")))
+            for drag in (False, True):
+                needs = ("dust_idx",) + DRAG_ARRAYS if drag else \
+                    ("dust_idx", "particle_density") + (("particle_velocity",) if grains else ())
+                for member in needs:
+                    h = type(g).from_buffer_copy(g)
+                    setattr(h, member, None)
+                    rc = _call_form(B, f, form, drag, p, h)
+                    msg = f.L.ghip_last_error(f.h).decode()
+                    assert rc == -90002 and "bad arguments" in msg, (form, drag, member, rc, msg)
+        assert fp.run_end()["launches"] == 0
+        # log_radius_by_dt == NULL: both grains forms run, under growth too
+        out = _drag(fp, case, full, d7, logr=False)
+        assert "log_radius_by_dt" not in out and not np.array_equal(out["dust_radius"], case.radius)
+        built = [B.dd_dust_grains_args(p, T.local[r], logr=False, **dict(kw(T.lists[r]), log_radius_by_dt=None))
+                 for r in range(2)]
+        T.set_model(full)
+        T.S.run.run(B.DD_DUST_DRAG, [b[0] for b in built], B.DUST_GRAINS_FORM)
+        assert not np.array_equal(built[0][1]["dust_radius"], case.radius[T.lists[0]])
+    finally:
+        T.S.close()
+        fp.close()
