@@ -365,30 +365,33 @@ struct DynTree
   DevBuf kick_dv, kick_flag; // f64[3][n], i32[n]: velocity changes of the last ghip_advance_timesteps
 };
 
-// particle-mesh force (ghip_pm.hip): hipFFT plans for n^3, mesh buffers
+// One real 3-d transform of the particle-mesh force (ghip_pm.hip, pm_fft_prepare): hipFFT plans for n^3 on the
+// context's stream, the mesh and its transform.  Owns the plans: they are destroyed with it, here alone.
+struct PmFft
+{
+  int n = 0;                             // side the plans and buffers are made for
+  void *fwd = nullptr, *inv = nullptr;   // hipfftHandle
+  DevBuf rho, k;
+  PmFft() = default;
+  PmFft(const PmFft &) = delete;
+  PmFft &operator=(const PmFft &) = delete;
+  ~PmFft();
+};
+
+// particle-mesh force (ghip_pm.hip): the periodic mesh PMGRID^3 with its force components
 struct PmMesh
 {
-  int n = 0;
-  void *fwd = nullptr, *inv = nullptr;   // hipfftHandle, destroyed with the mesh
-  DevBuf rho, k, force;
-  // The non-periodic mesh (ghip_pm.hip, "non-periodic mesh"): plans for GRID^3 = (2 n)^3, the padded mesh and
-  // its transform, the Green's function table, the force components and the density of the lower octant n^3
-  // (+ one status word).  Renewed as a whole, alone (ghip_renew(open)) or with the mesh that owns it.
+  PmFft fft;
+  DevBuf force;
+  // The non-periodic mesh (ghip_pm.hip, "non-periodic mesh"): the padded mesh GRID^3 = (2 PMGRID)^3, the Green's
+  // function table, the force components and the density of the lower octant PMGRID^3 (+ one status word).
+  // Renewed as a whole, alone (ghip_renew(open)) or with the mesh that owns it.
   struct Open
   {
-    int n = 0;                             // PMGRID the plans and buffers are made for
-    int table_n = 0;                       // PMGRID `table` is filled for (0: not filled)
-    void *fwd = nullptr, *inv = nullptr;   // hipfftHandle
-    DevBuf rho, k, table, force, oct;
-    Open() = default;
-    Open(const Open &) = delete;
-    Open &operator=(const Open &) = delete;
-    ~Open();
+    PmFft fft;
+    int table_n = 0;   // PMGRID `table` is filled for (0: not filled)
+    DevBuf table, force, oct;
   } open;
-  PmMesh() = default;
-  PmMesh(const PmMesh &) = delete;
-  PmMesh &operator=(const PmMesh &) = delete;
-  ~PmMesh();
 };
 
 // The Newtonian walk of a Newton + Ewald pair is held to W one-wavefront workgroups per SIMD (4 W per
@@ -666,22 +669,22 @@ int ghip_finish_gas_tree(ghip_ctx *ctx);   // complete a deferred gas tree (entr
     }                                           \
   while(0)
 void ghip_pm_release(ghip_ctx *ctx);
-int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot);   // pm.hip
-// ... in two halves (GHIP_DD_POTENTIAL): this context's particles onto its mesh pm_rho; then, all != nullptr:
-// pm_rho = the nranks meshes of `all` added in rank order, solve, pot[i] += the mesh potential at particle i
-int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p);
-int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot);
-// The non-periodic mesh potential (pmpotential_nonperiodic(0)), in the same two halves.  _check: the argument
-// rules of ghip_potential for grav.periodic == 0 && pm.pmgrid > 0.  _deposit: range check and deposit of this
-// context's particles into its octant block (ghip_pmnp_block_bytes: PMGRID^3 doubles and the status word, which
-// it sets); *outside = 1 when a particle lies outside the region (nothing deposited then).  _solve: all !=
-// nullptr: the octant is the sum of the nranks gathered blocks in rank order; GHIP_EREGION if a status word says
-// so, before anything is written; else pot[i] += the mesh potential at particle i.
-int ghip_pmnp_potential_check(ghip_ctx *ctx, const ghip_grav_params *g, const ghip_pm_params *pm, const char *who);
-int ghip_pmnp_potential_deposit(ghip_ctx *ctx, int pmgrid, int *outside);
-int ghip_pmnp_potential_solve(ghip_ctx *ctx, int pmgrid, double G, int nranks, const double *all, double *pot);
-size_t ghip_pmnp_block_bytes(int pmgrid);
-const void *ghip_pmnp_block(ghip_ctx *ctx);
+// The mesh part of the potential (ghip_pm.hip), for pot.pm.pmgrid != 0: pmpotential_periodic with
+// pot.grav.periodic, else pmpotential_nonperiodic(0) -- decided there.  _check: the argument rules of ghip_potential.
+// _deposit: this context's particles onto its (zeroed) mesh; *b is the block a shard all-gathers (the periodic mesh;
+// the open mesh's octant and its status word), outside = 1 when a particle lies outside the open mesh's region
+// (nothing deposited then; always 0 for the periodic mesh).  _solve: all != nullptr: the mesh is the sum of the
+// nranks gathered blocks in rank order, GHIP_EREGION if a status word says so, before anything is written; else
+// pot[i] += the mesh potential at particle i.
+struct PmBlock
+{
+  const void *p;
+  size_t bytes;
+  int outside;
+};
+int ghip_pm_pot_check(ghip_ctx *ctx, const ghip_pot_params *p, const char *who);
+int ghip_pm_pot_deposit(ghip_ctx *ctx, const ghip_pot_params *p, PmBlock *b);
+int ghip_pm_pot_solve(ghip_ctx *ctx, const ghip_pot_params *p, int nranks, const double *all, double *pot);
 // ghip_decomp.hip: one pass of k_decomp_extent over the resident positions into the block `own` (EXTENT_WORDS
 // u64: images of xmin[3], xmax[3], the count, time bins, the error word; an empty context contributes +MAX / -MAX).
 // A failure of the pass itself is returned AND marked in the block, so that peers of a collective stop with it.

@@ -31,6 +31,73 @@
     }                                                                                         \
   while(0)
 
+// One cloud-in-cell cell: the mesh cell below a particle and the particle's offset inside it, in cells.  Both
+// meshes fill it (d_pm_cell, d_pmnp_cell); the weights come from d_cic_weight alone.
+struct CicCell
+{
+  int s[3];
+  double d[3];
+};
+
+// a times the weight of corner (xx, yy, zz), as ((a wx) wy) wz.  a = 1.0 gives the bare weight wx wy wz, exactly.
+__device__ __forceinline__ double d_cic_weight(double a, const CicCell &c, int xx, int yy, int zz)
+{
+  return a * (xx ? c.d[0] : 1.0 - c.d[0]) * (yy ? c.d[1] : 1.0 - c.d[1]) * (zz ? c.d[2] : 1.0 - c.d[2]);
+}
+
+// (f_x f_y f_z)^-4 with f = sin(pi k / N) / (pi k / N): the CIC deconvolution, for assignment and read-out
+// (pm_periodic.c:455-476, pm_nonperiodic.c:520-545); kx, ky, kz are whole wave numbers of a mesh of side N
+__device__ __forceinline__ double d_cic_deconv(double kx, double ky, double kz, int N)
+{
+  double fx = 1, fy = 1, fz = 1;
+  if(kx != 0)
+    {
+      fx = (M_PI * kx) / N;
+      fx = sin(fx) / fx;
+    }
+  if(ky != 0)
+    {
+      fy = (M_PI * ky) / N;
+      fy = sin(fy) / fy;
+    }
+  if(kz != 0)
+    {
+      fz = (M_PI * kz) / N;
+      fz = sin(fz) / fz;
+    }
+  const double ff = 1 / (fx * fy * fz);
+  return ff * ff * ff * ff;
+}
+
+// the periodic cell rule of pm_periodic.c:318-325: scale, truncate, the offset BEFORE the clamp, clamp the
+// upper side (a coordinate equal to BoxSize lands in the last cell with offset 1)
+__device__ __forceinline__ CicCell d_pm_cell(int N, double to_slab_fac, int n, int i, const double *__restrict__ pos)
+{
+  CicCell c;
+  for(int j = 0; j < 3; j++)
+    {
+      const double p = to_slab_fac * pos[(size_t) j * n + i];
+      c.s[j] = (int) p;
+      c.d[j] = p - c.s[j];
+      if(c.s[j] >= N)
+        c.s[j] = N - 1;
+    }
+  return c;
+}
+
+// mesh point of corner (xx, yy, zz) of a periodic cell: the +1 corner of the last cell wraps
+__device__ __forceinline__ size_t d_pm_corner(int N, const CicCell &c, int xx, int yy, int zz)
+{
+  int gx = c.s[0] + xx, gy = c.s[1] + yy, gz = c.s[2] + zz;
+  if(gx >= N)
+    gx -= N;
+  if(gy >= N)
+    gy -= N;
+  if(gz >= N)
+    gz -= N;
+  return ((size_t) gx * N + gy) * N + gz;
+}
+
 // pm_periodic.c:226-330: cloud-in-cell assignment of the particle masses
 __global__ void k_pm_deposit(int n, int N, double to_slab_fac, const double *__restrict__ pos,
                              const double *__restrict__ mass, double *__restrict__ rho)
@@ -38,31 +105,12 @@ __global__ void k_pm_deposit(int n, int N, double to_slab_fac, const double *__r
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
     return;
-  double px = to_slab_fac * pos[i], py = to_slab_fac * pos[(size_t) n + i],
-         pz = to_slab_fac * pos[2 * (size_t) n + i];
-  int sx = (int) px, sy = (int) py, sz = (int) pz;
-  double dx = px - sx, dy = py - sy, dz = pz - sz;   // (before the clamp, as the reference: :318-325)
-  if(sx >= N)
-    sx = N - 1;
-  if(sy >= N)
-    sy = N - 1;
-  if(sz >= N)
-    sz = N - 1;
+  const CicCell c = d_pm_cell(N, to_slab_fac, n, i, pos);
   const double m = mass[i];
   for(int xx = 0; xx < 2; xx++)
     for(int yy = 0; yy < 2; yy++)
       for(int zz = 0; zz < 2; zz++)
-        {
-          int gx = sx + xx, gy = sy + yy, gz = sz + zz;
-          if(gx >= N)
-            gx -= N;
-          if(gy >= N)
-            gy -= N;
-          if(gz >= N)
-            gz -= N;
-          double w = m * (xx ? dx : 1.0 - dx) * (yy ? dy : 1.0 - dy) * (zz ? dz : 1.0 - dz);
-          atomicAdd(&rho[((size_t) gx * N + gy) * N + gz], w);
-        }
+        atomicAdd(&rho[d_pm_corner(N, c, xx, yy, zz)], d_cic_weight(m, c, xx, yy, zz));
 }
 
 // pm_periodic.c:430-486 on hipFFT's layout [x][y][z = 0..N/2]
@@ -79,24 +127,7 @@ __global__ void k_pm_green(int N, double asmth2, double2 *__restrict__ fk)
   if(k2 > 0)
     {
       double smth = -exp(-k2 * asmth2) / k2;
-      double fx = 1, fy = 1, fz = 1;
-      if(kx != 0)
-        {
-          fx = (M_PI * kx) / N;
-          fx = sin(fx) / fx;
-        }
-      if(ky != 0)
-        {
-          fy = (M_PI * ky) / N;
-          fy = sin(fy) / fy;
-        }
-      if(kz != 0)
-        {
-          fz = (M_PI * kz) / N;
-          fz = sin(fz) / fz;
-        }
-      double ff = 1 / (fx * fy * fz);
-      smth *= ff * ff * ff * ff;
+      smth *= d_cic_deconv(kx, ky, kz, N);
       v.x *= smth;
       v.y *= smth;
     }
@@ -143,111 +174,19 @@ __global__ void k_pm_interpolate(int n, int N, double to_slab_fac, const double 
   if(i >= n)
     return;
   const size_t n3 = (size_t) N * N * N;
-  double px = to_slab_fac * pos[i], py = to_slab_fac * pos[(size_t) n + i],
-         pz = to_slab_fac * pos[2 * (size_t) n + i];
-  int sx = (int) px, sy = (int) py, sz = (int) pz;
-  double dx = px - sx, dy = py - sy, dz = pz - sz;
-  if(sx >= N)
-    sx = N - 1;
-  if(sy >= N)
-    sy = N - 1;
-  if(sz >= N)
-    sz = N - 1;
+  const CicCell c = d_pm_cell(N, to_slab_fac, n, i, pos);
   double acc[3] = {0, 0, 0};
   for(int xx = 0; xx < 2; xx++)
     for(int yy = 0; yy < 2; yy++)
       for(int zz = 0; zz < 2; zz++)
         {
-          int gx = sx + xx, gy = sy + yy, gz = sz + zz;
-          if(gx >= N)
-            gx -= N;
-          if(gy >= N)
-            gy -= N;
-          if(gz >= N)
-            gz -= N;
-          double w = (xx ? dx : 1.0 - dx) * (yy ? dy : 1.0 - dy) * (zz ? dz : 1.0 - dz);
-          size_t g = ((size_t) gx * N + gy) * N + gz;
+          const double w = d_cic_weight(1.0, c, xx, yy, zz);
+          const size_t g = d_pm_corner(N, c, xx, yy, zz);
           for(int dim = 0; dim < 3; dim++)
             acc[dim] += force[(size_t) dim * n3 + g] * w;   // same corner order as the reference
         }
   for(int dim = 0; dim < 3; dim++)
     gravpm[(size_t) dim * n + i] += acc[dim];
-}
-
-static int pm_check(ghip_ctx *ctx, const ghip_pm_params *p)
-{
-  const int N = p->pmgrid;
-  if(N < 4 || N > 2048 || (N & 1) || !(p->BoxSize > 0) || !(p->Asmth > 0))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_pm_periodic: need an even PMGRID >= 4, BoxSize > 0, Asmth > 0");
-  return GHIP_OK;
-}
-
-// plans and mesh buffers for PMGRID = N
-static int pm_prepare(ghip_ctx *ctx, int N)
-{
-  hipStream_t st = ctx->stream;
-  const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
-  if(ctx->pm.n != N)
-    {
-      // (the mesh owns each plan from the moment it exists: a failure below leaves nothing behind)
-      ghip_renew(ctx->pm);
-      hipfftHandle f, b;
-      FFTCHK(hipfftPlan3d(&f, N, N, N, HIPFFT_D2Z));
-      ctx->pm.fwd = (void *) f;
-      FFTCHK(hipfftPlan3d(&b, N, N, N, HIPFFT_Z2D));
-      ctx->pm.inv = (void *) b;
-      FFTCHK(hipfftSetStream(f, st));
-      FFTCHK(hipfftSetStream(b, st));
-      ctx->pm.n = N;
-    }
-  GCHK(ghip_ensure(ctx, ctx->pm.rho, n3 * sizeof(double)));
-  GCHK(ghip_ensure(ctx, ctx->pm.k, nk * sizeof(double2)));
-  GCHK(ghip_ensure(ctx, ctx->pm.force, 3 * n3 * sizeof(double)));
-  return GHIP_OK;
-}
-
-// mass of this context's particles onto the (zeroed) mesh; GRAVPM zeroed as long_range_force() does
-static int pm_deposit(ghip_ctx *ctx, const ghip_pm_params *p)
-{
-  hipStream_t st = ctx->stream;
-  const int N = p->pmgrid, n = ctx->n;
-  const size_t n3 = (size_t) N * N * N;
-  const double to_slab_fac = N / p->BoxSize;                   // pm_periodic.c:102
-  double *rho = P<double>(ctx->pm.rho);
-  HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
-  if(n > 0)
-    {
-      HIPCHK(hipMemsetAsync(ctx->f[GHIP_F_GRAVPM].p, 0, (size_t) n * 3 * sizeof(double), st));
-      k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
-                                                 P<double>(ctx->f[GHIP_F_MASS]), rho);
-      HIPCHK(hipGetLastError());
-    }
-  return GHIP_OK;
-}
-
-// mesh density -> potential -> force field -> GRAVPM of this context's particles
-static int pm_solve_and_interpolate(ghip_ctx *ctx, const ghip_pm_params *p)
-{
-  hipStream_t st = ctx->stream;
-  const int N = p->pmgrid, n = ctx->n;
-  const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
-  double *rho = P<double>(ctx->pm.rho), *force = P<double>(ctx->pm.force);
-  double2 *fk = P<double2>(ctx->pm.k);
-  const double to_slab_fac = N / p->BoxSize;
-  double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;          // :221-222
-  asmth2 *= asmth2;
-  double fac = p->G / (M_PI * p->BoxSize);                     // :224-225
-  fac *= 1 / (2 * p->BoxSize / N);
-  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
-  k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
-  HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
-  k_pm_gradient<<<cdiv((long long) n3, 256), 256, 0, st>>>(N, fac, rho, force);
-  if(n > 0)
-    k_pm_interpolate<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
-                                                   force, P<double>(ctx->f[GHIP_F_GRAVPM]));
-  HIPCHK(hipGetLastError());
-  return GHIP_OK;
 }
 
 // pmpotential_periodic (pm_periodic.c:808-1195): the same deposit and Green's function as the force
@@ -261,31 +200,12 @@ __global__ void k_pm_pot_readout(int n, int N, double to_slab_fac, double fac,
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
     return;
-  double px = to_slab_fac * pos[i], py = to_slab_fac * pos[(size_t) n + i],
-         pz = to_slab_fac * pos[2 * (size_t) n + i];
-  int sx = (int) px, sy = (int) py, sz = (int) pz;
-  double dx = px - sx, dy = py - sy, dz = pz - sz;
-  if(sx >= N)
-    sx = N - 1;
-  if(sy >= N)
-    sy = N - 1;
-  if(sz >= N)
-    sz = N - 1;
+  const CicCell c = d_pm_cell(N, to_slab_fac, n, i, pos);
   double v = 0;
   for(int xx = 0; xx < 2; xx++)
     for(int yy = 0; yy < 2; yy++)
       for(int zz = 0; zz < 2; zz++)
-        {
-          int gx = sx + xx, gy = sy + yy, gz = sz + zz;
-          if(gx >= N)
-            gx -= N;
-          if(gy >= N)
-            gy -= N;
-          if(gz >= N)
-            gz -= N;
-          double w = (xx ? dx : 1.0 - dx) * (yy ? dy : 1.0 - dy) * (zz ? dz : 1.0 - dz);
-          v += phi[((size_t) gx * N + gy) * N + gz] * w;
-        }
+        v += phi[d_pm_corner(N, c, xx, yy, zz)] * d_cic_weight(1.0, c, xx, yy, zz);
   pot[i] += fac * v;
 }
 
@@ -303,62 +223,125 @@ __global__ void k_pm_sum_meshes(size_t n3, size_t stride, int nranks, const doub
   rho[g] = s;
 }
 
-// the mass of this context's particles onto its (zeroed) mesh.  GRAVPM is not touched.
-int ghip_pm_potential_deposit(ghip_ctx *ctx, const ghip_pm_params *p)
+static int pm_check(ghip_ctx *ctx, const ghip_pm_params *p)
 {
-  GCHK(pm_check(ctx, p));
-  const int N = p->pmgrid, n = ctx->n;
-  hipStream_t st = ctx->stream;
-  GCHK(pm_prepare(ctx, N));
-  const size_t n3 = (size_t) N * N * N;
-  const double to_slab_fac = N / p->BoxSize;
-  double *rho = P<double>(ctx->pm.rho);
-  HIPCHK(hipMemsetAsync(rho, 0, n3 * sizeof(double), st));
-  if(n > 0)
-    k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, P<double>(ctx->f[GHIP_F_POS]),
-                                               P<double>(ctx->f[GHIP_F_MASS]), rho);
-  HIPCHK(hipGetLastError());
+  const int N = p->pmgrid;
+  if(N < 4 || N > 2048 || (N & 1) || !(p->BoxSize > 0) || !(p->Asmth > 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_pm_periodic: need an even PMGRID >= 4, BoxSize > 0, Asmth > 0");
   return GHIP_OK;
 }
 
-// (all != nullptr: the mesh is the sum of the nranks all-gathered ones, in rank order) potential mesh,
-// pot[i] += its value at particle i
-int ghip_pm_potential_solve(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot)
+// Plans for a real transform of side G on the context's stream, the mesh and its transform: the one place where
+// plans are made, for both meshes.  Another side renews the object (plans and both buffers) and nothing else.
+static int pm_fft_prepare(ghip_ctx *ctx, PmFft &t, int G)
 {
-  const int N = p->pmgrid, n = ctx->n;
+  if(t.n != G)
+    {
+      // (the object owns each plan from the moment it exists: a failure below leaves nothing behind)
+      ghip_renew(t);
+      hipfftHandle f, b;
+      FFTCHK(hipfftPlan3d(&f, G, G, G, HIPFFT_D2Z));
+      t.fwd = (void *) f;
+      FFTCHK(hipfftPlan3d(&b, G, G, G, HIPFFT_Z2D));
+      t.inv = (void *) b;
+      FFTCHK(hipfftSetStream(f, ctx->stream));
+      FFTCHK(hipfftSetStream(b, ctx->stream));
+      t.n = G;
+    }
+  GCHK(ghip_ensure(ctx, t.rho, (size_t) G * G * G * sizeof(double)));
+  GCHK(ghip_ensure(ctx, t.k, (size_t) G * G * (G / 2 + 1) * sizeof(double2)));
+  return GHIP_OK;
+}
+
+PmFft::~PmFft()
+{
+  if(fwd)
+    (void) hipfftDestroy((hipfftHandle) fwd);
+  if(inv)
+    (void) hipfftDestroy((hipfftHandle) inv);
+}
+
+// plans and mesh buffers for PMGRID = N
+static int pm_prepare(ghip_ctx *ctx, int N)
+{
+  GCHK(pm_fft_prepare(ctx, ctx->pm.fft, N));
+  return ghip_ensure(ctx, ctx->pm.force, 3 * (size_t) N * N * N * sizeof(double));
+}
+
+static double pm_to_slab_fac(const ghip_pm_params *p) { return p->pmgrid / p->BoxSize; }   // pm_periodic.c:102
+
+// mass of this context's particles onto the (zeroed) mesh; zero_gravpm: GRAVPM zeroed as long_range_force() does
+static int pm_deposit(ghip_ctx *ctx, const ghip_pm_params *p, bool zero_gravpm)
+{
   hipStream_t st = ctx->stream;
+  const int N = p->pmgrid, n = ctx->n;
+  double *rho = P<double>(ctx->pm.fft.rho);
+  HIPCHK(hipMemsetAsync(rho, 0, (size_t) N * N * N * sizeof(double), st));
+  if(n > 0)
+    {
+      if(zero_gravpm)
+        HIPCHK(hipMemsetAsync(ctx->f[GHIP_F_GRAVPM].p, 0, (size_t) n * 3 * sizeof(double), st));
+      k_pm_deposit<<<cdiv(n, 256), 256, 0, st>>>(n, N, pm_to_slab_fac(p), P<double>(ctx->f[GHIP_F_POS]),
+                                                 P<double>(ctx->f[GHIP_F_MASS]), rho);
+      HIPCHK(hipGetLastError());
+    }
+  return GHIP_OK;
+}
+
+// (all != nullptr: the mesh is the sum of the nranks all-gathered ones, in rank order) mesh density -> the
+// potential mesh, in place
+static int pm_potential_mesh(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all)
+{
+  hipStream_t st = ctx->stream;
+  const int N = p->pmgrid;
   const size_t n3 = (size_t) N * N * N, nk = (size_t) N * N * (N / 2 + 1);
-  const double to_slab_fac = N / p->BoxSize;
-  double *rho = P<double>(ctx->pm.rho);
-  double2 *fk = P<double2>(ctx->pm.k);
+  PmFft &t = ctx->pm.fft;
+  double *rho = P<double>(t.rho);
+  double2 *fk = P<double2>(t.k);
   if(all)
     {
       k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, n3, nranks, all, rho);
       HIPCHK(hipGetLastError());
     }
-  double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;   // :834-835
+  double asmth2 = (2 * M_PI) * p->Asmth / p->BoxSize;          // :221-222, :834-835
   asmth2 *= asmth2;
-  const double fac = p->G / (M_PI * p->BoxSize);        // :837 (pm.G = All.G)
-  FFTCHK(hipfftExecD2Z((hipfftHandle) ctx->pm.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
+  FFTCHK(hipfftExecD2Z((hipfftHandle) t.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
   k_pm_green<<<cdiv((long long) nk, 256), 256, 0, st>>>(N, asmth2, fk);
   HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecZ2D((hipfftHandle) ctx->pm.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  FFTCHK(hipfftExecZ2D((hipfftHandle) t.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  return GHIP_OK;
+}
+
+// the force: potential mesh -> force field -> GRAVPM of this context's particles
+static int pm_force(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all)
+{
+  hipStream_t st = ctx->stream;
+  const int N = p->pmgrid, n = ctx->n;
+  const size_t n3 = (size_t) N * N * N;
+  double *force = P<double>(ctx->pm.force);
+  GCHK(pm_potential_mesh(ctx, p, nranks, all));
+  double fac = p->G / (M_PI * p->BoxSize);                     // :224-225
+  fac *= 1 / (2 * p->BoxSize / N);
+  k_pm_gradient<<<cdiv((long long) n3, 256), 256, 0, st>>>(N, fac, P<double>(ctx->pm.fft.rho), force);
   if(n > 0)
-    k_pm_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, N, to_slab_fac, fac, P<double>(ctx->f[GHIP_F_POS]),
-                                                   rho, pot);
+    k_pm_interpolate<<<cdiv(n, 256), 256, 0, st>>>(n, N, pm_to_slab_fac(p), P<double>(ctx->f[GHIP_F_POS]),
+                                                   force, P<double>(ctx->f[GHIP_F_GRAVPM]));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
 
-// pot[i] += the periodic PM potential of every particle (ghip_potential, PMGRID builds).  GRAVPM and
-// what ghip_pm_periodic computes are not touched.
-int ghip_pm_potential_add(ghip_ctx *ctx, const ghip_pm_params *p, double *pot)
+// the potential: potential mesh -> pot[i] += its value at particle i
+static int pm_potential(ghip_ctx *ctx, const ghip_pm_params *p, int nranks, const double *all, double *pot)
 {
-  GCHK(pm_check(ctx, p));
-  if(ctx->n == 0)
-    return GHIP_OK;
-  GCHK(ghip_pm_potential_deposit(ctx, p));
-  return ghip_pm_potential_solve(ctx, p, 1, nullptr, pot);
+  const int N = p->pmgrid, n = ctx->n;
+  GCHK(pm_potential_mesh(ctx, p, nranks, all));
+  const double fac = p->G / (M_PI * p->BoxSize);               // :837 (pm.G = All.G)
+  if(n > 0)
+    k_pm_pot_readout<<<cdiv(n, 256), 256, 0, ctx->stream>>>(n, N, pm_to_slab_fac(p), fac,
+                                                            P<double>(ctx->f[GHIP_F_POS]),
+                                                            P<double>(ctx->pm.fft.rho), pot);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
 }
 
 extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
@@ -375,8 +358,8 @@ extern "C" int ghip_pm_periodic(ghip_ctx *ctx, const ghip_pm_params *p)
   hipStream_t st = ctx->stream;
   GCHK(pm_prepare(ctx, p->pmgrid));
   HIPCHK(hipEventRecord(ctx->evp[14], st));
-  GCHK(pm_deposit(ctx, p));
-  GCHK(pm_solve_and_interpolate(ctx, p));
+  GCHK(pm_deposit(ctx, p, true));
+  GCHK(pm_force(ctx, p, 1, nullptr));
   HIPCHK(hipEventRecord(ctx->evp[15], st));
   return GHIP_OK;
 }
@@ -401,17 +384,14 @@ int ghip_dd_pm_step(ghip_ctx *ctx)
     {
       GCHK(pm_prepare(ctx, p->pmgrid));
       HIPCHK(hipEventRecord(ctx->evp[14], st));
-      GCHK(pm_deposit(ctx, p));
-      ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
+      GCHK(pm_deposit(ctx, p, true));
+      ghip_dd_set_allgather(D, ctx->pm.fft.rho.p, n3 * sizeof(double), &D.pm_all);
       D.phase = SOLVE;
       return 1;
     }
   if(D.phase == SOLVE)
     {
-      k_pm_sum_meshes<<<cdiv((long long) n3, 256), 256, 0, st>>>(n3, n3, D.nranks, P<double>(D.pm_all),
-                                                                 P<double>(ctx->pm.rho));
-      HIPCHK(hipGetLastError());
-      GCHK(pm_solve_and_interpolate(ctx, p));
+      GCHK(pm_force(ctx, p, D.nranks, P<double>(D.pm_all)));
       HIPCHK(hipEventRecord(ctx->evp[15], st));
       return 0;
     }
@@ -486,9 +466,8 @@ __global__ void k_pmnp_range(int n, const double *__restrict__ pos, double lo0, 
     atomicOr(err, 1);
 }
 
-// slab index and offset of particle i along the three axes (:766-772); false: outside the octant, no index formed
-__device__ __forceinline__ bool d_pmnp_cell(const PmnpGeo &g, int n, int i, const double *__restrict__ pos, int s[3],
-                                            double d[3])
+// the cell of particle i in the octant (:766-772); false: outside the octant, no index formed
+__device__ __forceinline__ bool d_pmnp_cell(const PmnpGeo &g, int n, int i, const double *__restrict__ pos, CicCell &c)
 {
   bool ok = true;
   for(int j = 0; j < 3; j++)
@@ -496,17 +475,24 @@ __device__ __forceinline__ bool d_pmnp_cell(const PmnpGeo &g, int n, int i, cons
       const double p = g.fac * (pos[(size_t) j * n + i] - g.c[j]);
       if(p >= 0.0 && p < (double) (g.M - 1))
         {
-          s[j] = (int) p;
-          d[j] = p - s[j];
+          c.s[j] = (int) p;
+          c.d[j] = p - c.s[j];
         }
       else
         {
-          s[j] = 0;
-          d[j] = 0;
+          c.s[j] = 0;
+          c.d[j] = 0;
           ok = false;
         }
     }
   return ok;
+}
+
+// mesh point of corner (xx, yy, zz) of an open cell in an array of side `side` (the octant M, the padded mesh G):
+// no wrap, d_pmnp_cell keeps the +1 corner inside
+__device__ __forceinline__ size_t d_pmnp_corner(int side, const CicCell &c, int xx, int yy, int zz)
+{
+  return ((size_t) (c.s[0] + xx) * side + (c.s[1] + yy)) * side + (c.s[2] + zz);
 }
 
 // :757-790 into the compact octant oct[M][M][M].  Lanes whose particle has the same base cell as their
@@ -517,22 +503,21 @@ k_pmnp_deposit(int n, PmnpGeo g, const double *__restrict__ pos, const double *_
                double *__restrict__ oct, int *__restrict__ errw)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int s[3] = {0, 0, 0};
-  double d[3] = {0, 0, 0};
-  const bool ok = i < n && d_pmnp_cell(g, n, i, pos, s, d);
+  CicCell c = {{0, 0, 0}, {0, 0, 0}};
+  const bool ok = i < n && d_pmnp_cell(g, n, i, pos, c);
   if(i < n && !ok)
     *errw = 1;
   const int M = g.M;
+  // (whole wavefronts arrive here: the shuffles need all 64 lanes)
+  const int lane = threadIdx.x & (GHIP_WAVE - 1);
+  const unsigned int cell = ok ? (unsigned int) ((c.s[0] * M + c.s[1]) * M + c.s[2]) : 0xffffffffu - (unsigned int) lane;
   const double m = ok ? mass[i] : 0.0;
   double w[8];
   for(int xx = 0; xx < 2; xx++)
     for(int yy = 0; yy < 2; yy++)
       for(int zz = 0; zz < 2; zz++)
-        w[xx * 4 + yy * 2 + zz] = m * (xx ? d[0] : 1.0 - d[0]) * (yy ? d[1] : 1.0 - d[1]) * (zz ? d[2] : 1.0 - d[2]);
+        w[xx * 4 + yy * 2 + zz] = d_cic_weight(m, c, xx, yy, zz);
   bool issue = ok;
-  // (whole wavefronts arrive here: the shuffles need all 64 lanes)
-  const int lane = threadIdx.x & (GHIP_WAVE - 1);
-  const unsigned int cell = ok ? (unsigned int) ((s[0] * M + s[1]) * M + s[2]) : 0xffffffffu - (unsigned int) lane;
   const unsigned int before = __shfl_up(cell, 1, GHIP_WAVE), after = __shfl_down(cell, 1, GHIP_WAVE);
   const bool head = lane == 0 || before != cell, tail = lane == GHIP_WAVE - 1 || after != cell;
   const unsigned long long heads = __ballot(head);
@@ -541,11 +526,11 @@ k_pmnp_deposit(int n, PmnpGeo g, const double *__restrict__ pos, const double *_
       const int first = 63 - __clzll((long long) (heads & (~0ULL >> (63 - lane))));
       const int dist = lane - first;
       for(int off = 1; off < GHIP_WAVE; off <<= 1)
-        for(int c = 0; c < 8; c++)
+        for(int k = 0; k < 8; k++)
           {
-            const double o = __shfl_up(w[c], off, GHIP_WAVE);
+            const double o = __shfl_up(w[k], off, GHIP_WAVE);
             if(dist >= off)
-              w[c] += o;
+              w[k] += o;
           }
       issue = ok && tail;
     }
@@ -553,7 +538,7 @@ k_pmnp_deposit(int n, PmnpGeo g, const double *__restrict__ pos, const double *_
     for(int xx = 0; xx < 2; xx++)
       for(int yy = 0; yy < 2; yy++)
         for(int zz = 0; zz < 2; zz++)
-          atomicAdd(&oct[((size_t) (s[0] + xx) * M + (s[1] + yy)) * M + (s[2] + zz)], w[xx * 4 + yy * 2 + zz]);
+          atomicAdd(&oct[d_pmnp_corner(M, c, xx, yy, zz)], w[xx * 4 + yy * 2 + zz]);
 }
 
 // the octant into the padded mesh, zeros everywhere else (:785-787)
@@ -597,24 +582,7 @@ __global__ void k_pmnp_table_deconv(int G, double2 *__restrict__ fk)
   const double kx = x > G / 2 ? x - G : x, ky = y > G / 2 ? y - G : y, kz = z > G / 2 ? z - G : z;
   if(kx * kx + ky * ky + kz * kz > 0)
     {
-      double fx = 1, fy = 1, fz = 1;
-      if(kx != 0)
-        {
-          fx = (M_PI * kx) / G;
-          fx = sin(fx) / fx;
-        }
-      if(ky != 0)
-        {
-          fy = (M_PI * ky) / G;
-          fy = sin(fy) / fy;
-        }
-      if(kz != 0)
-        {
-          fz = (M_PI * kz) / G;
-          fz = sin(fz) / fz;
-        }
-      double ff = 1 / (fx * fy * fz);
-      ff = ff * ff * ff * ff;
+      const double ff = d_cic_deconv(kx, ky, kz, G);
       double2 v = fk[idx];
       v.x *= ff;
       v.y *= ff;
@@ -666,10 +634,9 @@ __global__ void k_pmnp_interpolate(int n, PmnpGeo g, double tailfac, const doubl
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
     return;
-  int s[3];
-  double d[3];
+  CicCell c;
   double acc[3] = {0, 0, 0};
-  if(d_pmnp_cell(g, n, i, pos, s, d))
+  if(d_pmnp_cell(g, n, i, pos, c))
     {
       const int M = g.M;
       const size_t m3 = (size_t) M * M * M;
@@ -677,10 +644,9 @@ __global__ void k_pmnp_interpolate(int n, PmnpGeo g, double tailfac, const doubl
         for(int yy = 0; yy < 2; yy++)
           for(int zz = 0; zz < 2; zz++)
             {
-              const size_t c = ((size_t) (s[0] + xx) * M + (s[1] + yy)) * M + (s[2] + zz);
+              const size_t at = d_pmnp_corner(M, c, xx, yy, zz);
               for(int dim = 0; dim < 3; dim++)
-                acc[dim] += force[(size_t) dim * m3 + c] * (xx ? d[0] : 1.0 - d[0]) * (yy ? d[1] : 1.0 - d[1]) *
-                            (zz ? d[2] : 1.0 - d[2]);
+                acc[dim] += d_cic_weight(force[(size_t) dim * m3 + at], c, xx, yy, zz);
             }
     }
   else
@@ -698,9 +664,8 @@ __global__ void k_pmnp_pot_readout(int n, PmnpGeo g, double fac, const double *_
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
     return;
-  int s[3];
-  double d[3];
-  if(!d_pmnp_cell(g, n, i, pos, s, d))
+  CicCell c;
+  if(!d_pmnp_cell(g, n, i, pos, c))
     {
       *errw = 1;
       return;
@@ -710,8 +675,7 @@ __global__ void k_pmnp_pot_readout(int n, PmnpGeo g, double fac, const double *_
   for(int xx = 0; xx < 2; xx++)
     for(int yy = 0; yy < 2; yy++)
       for(int zz = 0; zz < 2; zz++)
-        v += phi[((size_t) (s[0] + xx) * G + (s[1] + yy)) * G + (s[2] + zz)] * (xx ? d[0] : 1.0 - d[0]) *
-             (yy ? d[1] : 1.0 - d[1]) * (zz ? d[2] : 1.0 - d[2]);
+        v += d_cic_weight(phi[d_pmnp_corner(G, c, xx, yy, zz)], c, xx, yy, zz);
   pot[i] += fac * v;
 }
 
@@ -839,8 +803,8 @@ static int pmnp_need_region(ghip_ctx *ctx, int pmgrid, const char *who)
   return GHIP_OK;
 }
 
-size_t ghip_pmnp_block_bytes(int pmgrid) { return ((size_t) pmgrid * pmgrid * pmgrid + 1) * sizeof(double); }
-const void *ghip_pmnp_block(ghip_ctx *ctx) { return ctx->pm.open.oct.p; }
+// the block a shard sends: the octant and its status word
+static size_t pmnp_block_bytes(int pmgrid) { return ((size_t) pmgrid * pmgrid * pmgrid + 1) * sizeof(double); }
 
 // Plans, buffers and the Green's function table for PMGRID = M.  The table depends on PMGRID only (ASMTH / GRID
 // is in mesh units, :413): it is keyed on M and survives every change of the region that keeps M.
@@ -850,32 +814,20 @@ static int pmnp_prepare(ghip_ctx *ctx, int M)
   PmMesh::Open &o = ctx->pm.open;
   const int G = 2 * M;
   const size_t g3 = (size_t) G * G * G, nk = (size_t) G * G * (G / 2 + 1), m3 = (size_t) M * M * M;
-  if(o.n != M)
-    {
-      // (the mesh owns each plan from the moment it exists: a failure below leaves nothing behind)
-      ghip_renew(o);
-      hipfftHandle f, b;
-      FFTCHK(hipfftPlan3d(&f, G, G, G, HIPFFT_D2Z));
-      o.fwd = (void *) f;
-      FFTCHK(hipfftPlan3d(&b, G, G, G, HIPFFT_Z2D));
-      o.inv = (void *) b;
-      FFTCHK(hipfftSetStream(f, st));
-      FFTCHK(hipfftSetStream(b, st));
-      o.n = M;
-    }
+  if(o.fft.n != G)
+    ghip_renew(o);   // (the table and the octant go with the plans)
   auto buffers = [&]() -> int {
-    GCHK(ghip_ensure(ctx, o.rho, g3 * sizeof(double)));
-    GCHK(ghip_ensure(ctx, o.k, nk * sizeof(double2)));
+    GCHK(pm_fft_prepare(ctx, o.fft, G));
     GCHK(ghip_ensure(ctx, o.table, nk * sizeof(double2)));
     GCHK(ghip_ensure(ctx, o.force, 3 * m3 * sizeof(double)));
-    GCHK(ghip_ensure(ctx, o.oct, ghip_pmnp_block_bytes(M)));
+    GCHK(ghip_ensure(ctx, o.oct, pmnp_block_bytes(M)));
     if(o.table_n != M)
       {
-        double *kern = P<double>(o.rho);
+        double *kern = P<double>(o.fft.rho);
         double2 *table = P<double2>(o.table);
         k_pmnp_table_fill<<<cdiv((long long) g3, 256), 256, 0, st>>>(G, kern);
         HIPCHK(hipGetLastError());
-        FFTCHK(hipfftExecD2Z((hipfftHandle) o.fwd, kern, reinterpret_cast<hipfftDoubleComplex *>(table)));
+        FFTCHK(hipfftExecD2Z((hipfftHandle) o.fft.fwd, kern, reinterpret_cast<hipfftDoubleComplex *>(table)));
         k_pmnp_table_deconv<<<cdiv((long long) nk, 256), 256, 0, st>>>(G, table);
         HIPCHK(hipGetLastError());
         o.table_n = M;
@@ -967,10 +919,10 @@ static int pmnp_solve(ghip_ctx *ctx, int nranks, const double *all)
 {
   hipStream_t st = ctx->stream;
   PmMesh::Open &o = ctx->pm.open;
-  const int M = o.n, G = 2 * M;
+  const int G = o.fft.n, M = G / 2;
   const size_t g3 = (size_t) G * G * G, nk = (size_t) G * G * (G / 2 + 1), m3 = (size_t) M * M * M;
-  double *rho = P<double>(o.rho), *oct = P<double>(o.oct);
-  double2 *fk = P<double2>(o.k);
+  double *rho = P<double>(o.fft.rho), *oct = P<double>(o.oct);
+  double2 *fk = P<double2>(o.fft.k);
   if(all)
     {
       k_pm_sum_meshes<<<cdiv((long long) m3, 256), 256, 0, st>>>(m3, m3 + 1, nranks, all, oct);
@@ -978,10 +930,10 @@ static int pmnp_solve(ghip_ctx *ctx, int nranks, const double *all)
     }
   k_pmnp_scatter<<<cdiv((long long) g3, 256), 256, 0, st>>>(M, G, oct, rho);
   HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecD2Z((hipfftHandle) o.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
+  FFTCHK(hipfftExecD2Z((hipfftHandle) o.fft.fwd, rho, reinterpret_cast<hipfftDoubleComplex *>(fk)));
   k_pmnp_multiply<<<cdiv((long long) nk, 256), 256, 0, st>>>(nk, P<double2>(o.table), fk);
   HIPCHK(hipGetLastError());
-  FFTCHK(hipfftExecZ2D((hipfftHandle) o.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
+  FFTCHK(hipfftExecZ2D((hipfftHandle) o.fft.inv, reinterpret_cast<hipfftDoubleComplex *>(fk), rho));
   return GHIP_OK;
 }
 
@@ -991,14 +943,14 @@ static int pmnp_force(ghip_ctx *ctx, const ghip_pmnp_params *p)
   hipStream_t st = ctx->stream;
   PmMesh::Open &o = ctx->pm.open;
   const ghip_pm_region &r = ctx->pm_region;
-  const int M = o.n, G = 2 * M, n = ctx->n;
+  const int G = o.fft.n, M = G / 2, n = ctx->n;
   const size_t m3 = (size_t) M * M * M;
   const double tms = r.TotalMeshSize;
   double fac = p->G / pow(tms, 4) * pow(tms / G, 3);   // :606
   fac *= 1 / (2 * tms / G);                             // :607
   // longrange.c:117-138
   const double tailfac = p->comoving ? 0.5 * p->Hubble * p->Hubble * p->Omega0 : p->OmegaLambda * p->Hubble * p->Hubble;
-  k_pmnp_gradient<<<cdiv((long long) m3, 256), 256, 0, st>>>(M, G, fac, P<double>(o.rho), P<double>(o.force));
+  k_pmnp_gradient<<<cdiv((long long) m3, 256), 256, 0, st>>>(M, G, fac, P<double>(o.fft.rho), P<double>(o.force));
   HIPCHK(hipGetLastError());
   if(n > 0)
     {
@@ -1019,10 +971,33 @@ static int pmnp_check_params(ghip_ctx *ctx, const ghip_pmnp_params *p, const cha
   return GHIP_OK;
 }
 
+static int pmnp_need_fields(ghip_ctx *ctx, const char *who)
+{
+  for(int f : {GHIP_F_POS, GHIP_F_MASS, GHIP_F_GRAVPM})
+    if(ctx->n > 0 && !ctx->f[f].p)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: particle field %d not set", who, f);
+  return GHIP_OK;
+}
+
 static int pmnp_outside(ghip_ctx *ctx, const char *who)
 {
   return ghip_fail(ctx, GHIP_EREGION, "%s: a particle lies outside the allowed region of the mesh; nothing was "
                    "written.  Find the region again (ghip_pm_find_region / GHIP_DD_PM_REGION) and repeat the call", who);
+}
+
+// What the deposits left: GHIP_OK to go on and solve.  Else the call ends here, on every shard alike: `failed`
+// is the first shard whose own pass failed (-1: none), `outside` says that a particle lies outside the region.
+// force: the call is one of the force's, whose end event closes ms_pm and which promises that nothing was written
+static int pmnp_verdict(ghip_ctx *ctx, const char *who, int outside, int failed, bool force)
+{
+  if(!outside && failed < 0)
+    return GHIP_OK;
+  if(force)
+    HIPCHK(hipEventRecord(ctx->evp[15], ctx->stream));
+  if(failed >= 0)
+    return ghip_dd_raise(ctx, failed, "%s: the deposit failed on shard %d (its own message says why); every shard "
+                         "stops here%s", who, failed, force ? ", nothing was written" : "");
+  return pmnp_outside(ctx, who);
 }
 
 extern "C" int ghip_pm_nonperiodic(ghip_ctx *ctx, const ghip_pmnp_params *p)
@@ -1038,73 +1013,39 @@ extern "C" int ghip_pm_nonperiodic(ghip_ctx *ctx, const ghip_pmnp_params *p)
   if(ctx->n == 0)
     return GHIP_OK;
   GCHK(pmnp_need_region(ctx, p->pmgrid, who));
-  for(int f : {GHIP_F_POS, GHIP_F_MASS, GHIP_F_GRAVPM})
-    if(!ctx->f[f].p)
-      return ghip_fail(ctx, GHIP_EINVAL, "%s: particle field %d not set", who, f);
+  GCHK(pmnp_need_fields(ctx, who));
   hipStream_t st = ctx->stream;
   GCHK(pmnp_prepare(ctx, p->pmgrid));
   HIPCHK(hipEventRecord(ctx->evp[14], st));
   int outside = 0;
   GCHK(pmnp_check_and_deposit(ctx, &outside));
-  if(outside)
-    {
-      HIPCHK(hipEventRecord(ctx->evp[15], st));
-      return pmnp_outside(ctx, who);
-    }
+  GCHK(pmnp_verdict(ctx, who, outside, -1, true));
   GCHK(pmnp_solve(ctx, 1, nullptr));
   GCHK(pmnp_force(ctx, p));
   HIPCHK(hipEventRecord(ctx->evp[15], st));
   return GHIP_OK;
 }
 
-// ---- the potential (ghip_potential.hip calls these) ----
-int ghip_pmnp_potential_check(ghip_ctx *ctx, const ghip_grav_params *g, const ghip_pm_params *pm, const char *who)
+// the open mesh's potential: (all != nullptr: the statuses of the gathered blocks first) solve, pot[i] += the
+// mesh potential at particle i
+static int pmnp_potential(ghip_ctx *ctx, const ghip_pm_params *pm, int nranks, const double *all, double *pot)
 {
-  GCHK(pmnp_check_grid(ctx, pm->pmgrid, who));
-  GCHK(pmnp_need_region(ctx, pm->pmgrid, who));
-  const ghip_pm_region &r = ctx->pm_region;
-  // (pm.BoxSize is not read: there is no box)
-  if(!(g->Asmth == pm->Asmth && pm->Asmth == r.Asmth))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: grav.Asmth %.17g, pm.Asmth %.17g and the region's Asmth %.17g must be "
-                     "equal (ghip_pm_get_region)", who, g->Asmth, pm->Asmth, r.Asmth);
-  if(!(g->Rcut == r.Rcut))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: grav.Rcut %.17g differs from the region's Rcut %.17g (ghip_pm_get_region)",
-                     who, g->Rcut, r.Rcut);
-  if(!(fabs(pm->G) <= DBL_MAX))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: pm.G must be finite", who);
-  return GHIP_OK;
-}
-
-int ghip_pmnp_potential_deposit(ghip_ctx *ctx, int pmgrid, int *outside)
-{
-  GCHK(pmnp_need_region(ctx, pmgrid, "the non-periodic mesh potential"));
-  GCHK(pmnp_prepare(ctx, pmgrid));
-  return pmnp_check_and_deposit(ctx, outside);
-}
-
-int ghip_pmnp_potential_solve(ghip_ctx *ctx, int pmgrid, double G, int nranks, const double *all, double *pot)
-{
-  hipStream_t st = ctx->stream;
   const ghip_pm_region &r = ctx->pm_region;
   const int n = ctx->n;
   if(all)
     {
       int outside = 0, failed = -1;
-      GCHK(pmnp_read_status(ctx, pmgrid, nranks, all, &outside, &failed));
-      if(failed >= 0)
-        return ghip_fail(ctx, GHIP_EDEVICE, "the non-periodic mesh potential: the deposit failed on shard %d (its own "
-                         "message says why); every shard stops here", failed);
-      if(outside)
-        return pmnp_outside(ctx, "the non-periodic mesh potential");
+      GCHK(pmnp_read_status(ctx, pm->pmgrid, nranks, all, &outside, &failed));
+      GCHK(pmnp_verdict(ctx, "the non-periodic mesh potential", outside, failed, false));
     }
   GCHK(pmnp_solve(ctx, nranks, all));
   const double tms = r.TotalMeshSize;
-  const double fac = G / pow(tms, 4) * pow(tms / (2 * pmgrid), 3);   // :1378
+  const double fac = pm->G / pow(tms, 4) * pow(tms / (2 * pm->pmgrid), 3);   // :1378
   if(n > 0)
     {
-      k_pmnp_pot_readout<<<cdiv(n, 256), 256, 0, st>>>(n, pmnp_geo(r), fac, P<double>(ctx->f[GHIP_F_POS]),
-                                                       P<double>(ctx->pm.open.rho), pot,
-                                                       ghip_errword(ctx, GHIP_ERRW_PM));
+      k_pmnp_pot_readout<<<cdiv(n, 256), 256, 0, ctx->stream>>>(n, pmnp_geo(r), fac, P<double>(ctx->f[GHIP_F_POS]),
+                                                                P<double>(ctx->pm.open.fft.rho), pot,
+                                                                ghip_errword(ctx, GHIP_ERRW_PM));
       HIPCHK(hipGetLastError());
     }
   return GHIP_OK;
@@ -1165,10 +1106,7 @@ int ghip_dd_pmnp_begin(ghip_ctx *ctx, int, const void *params, int)
   const char *who = "GHIP_DD_PM_NONPERIODIC";
   GCHK(pmnp_check_params(ctx, &ctx->dd.pmnp, who));
   GCHK(pmnp_need_region(ctx, ctx->dd.pmnp.pmgrid, who));
-  for(int f : {GHIP_F_POS, GHIP_F_MASS, GHIP_F_GRAVPM})
-    if(ctx->n > 0 && !ctx->f[f].p)
-      return ghip_fail(ctx, GHIP_EINVAL, "%s: particle field %d not set", who, f);
-  return GHIP_OK;
+  return pmnp_need_fields(ctx, who);
 }
 
 int ghip_dd_pmnp_step(ghip_ctx *ctx)
@@ -1189,7 +1127,7 @@ int ghip_dd_pmnp_step(ghip_ctx *ctx)
           const double s = PMNP_ST_LOCAL;
           HIPCHK(hipMemcpy(P<double>(ctx->pm.open.oct) + m3, &s, sizeof(double), hipMemcpyHostToDevice));
         }
-      ghip_dd_set_allgather(D, ctx->pm.open.oct.p, ghip_pmnp_block_bytes(M), &D.pm_all);
+      ghip_dd_set_allgather(D, ctx->pm.open.oct.p, pmnp_block_bytes(M), &D.pm_all);
       D.phase = SOLVE;
       return 1;
     }
@@ -1197,17 +1135,7 @@ int ghip_dd_pmnp_step(ghip_ctx *ctx)
     {
       int outside = 0, failed = -1;
       GCHK(pmnp_read_status(ctx, M, D.nranks, P<double>(D.pm_all), &outside, &failed));
-      if(failed >= 0)
-        {
-          HIPCHK(hipEventRecord(ctx->evp[15], st));
-          return ghip_dd_raise(ctx, failed, "GHIP_DD_PM_NONPERIODIC: the deposit failed on shard %d (its own message "
-                               "says why); every shard stops here, nothing was written", failed);
-        }
-      if(outside)
-        {
-          HIPCHK(hipEventRecord(ctx->evp[15], st));
-          return pmnp_outside(ctx, "GHIP_DD_PM_NONPERIODIC");
-        }
+      GCHK(pmnp_verdict(ctx, "GHIP_DD_PM_NONPERIODIC", outside, failed, true));
       GCHK(pmnp_solve(ctx, D.nranks, P<double>(D.pm_all)));
       GCHK(pmnp_force(ctx, p));
       HIPCHK(hipEventRecord(ctx->evp[15], st));
@@ -1216,20 +1144,63 @@ int ghip_dd_pmnp_step(ghip_ctx *ctx)
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the non-periodic mesh force has no phase %d", D.phase);
 }
 
-PmMesh::Open::~Open()
+// ---- the mesh part of the potential (ghip_potential.hip calls these three, with pm.pmgrid != 0): with
+// grav.periodic pmpotential_periodic, else pmpotential_nonperiodic(0).  GRAVPM is not touched. ----
+int ghip_pm_pot_check(ghip_ctx *ctx, const ghip_pot_params *p, const char *who)
 {
-  if(fwd)
-    (void) hipfftDestroy((hipfftHandle) fwd);
-  if(inv)
-    (void) hipfftDestroy((hipfftHandle) inv);
+  const ghip_grav_params &g = p->grav;
+  const ghip_pm_params &pm = p->pm;
+  if(g.periodic)
+    {
+      if(pm.pmgrid < 4 || pm.pmgrid > 2048 || (pm.pmgrid & 1) || !(pm.BoxSize > 0) || !(pm.Asmth > 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
+                         "pm.Asmth > 0", who);
+      if(pm.BoxSize != g.BoxSize)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: pm.BoxSize %g differs from grav.BoxSize %g", who,
+                         pm.BoxSize, g.BoxSize);
+      if(!(g.Rcut > 0 && g.Asmth > 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: a PM potential needs Rcut, Asmth > 0", who);
+      return GHIP_OK;
+    }
+  // a region is set, of this PMGRID, and the walk is cut where the region says (pm.BoxSize is not read: there is no box)
+  GCHK(pmnp_check_grid(ctx, pm.pmgrid, who));
+  GCHK(pmnp_need_region(ctx, pm.pmgrid, who));
+  const ghip_pm_region &r = ctx->pm_region;
+  if(!(g.Asmth == pm.Asmth && pm.Asmth == r.Asmth))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: grav.Asmth %.17g, pm.Asmth %.17g and the region's Asmth %.17g must be "
+                     "equal (ghip_pm_get_region)", who, g.Asmth, pm.Asmth, r.Asmth);
+  if(!(g.Rcut == r.Rcut))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: grav.Rcut %.17g differs from the region's Rcut %.17g (ghip_pm_get_region)",
+                     who, g.Rcut, r.Rcut);
+  if(!(fabs(pm.G) <= DBL_MAX))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: pm.G must be finite", who);
+  return GHIP_OK;
 }
 
-PmMesh::~PmMesh()
+int ghip_pm_pot_deposit(ghip_ctx *ctx, const ghip_pot_params *p, PmBlock *b)
 {
-  if(fwd)
-    (void) hipfftDestroy((hipfftHandle) fwd);
-  if(inv)
-    (void) hipfftDestroy((hipfftHandle) inv);
+  const int N = p->pm.pmgrid;
+  b->outside = 0;
+  if(p->grav.periodic)
+    {
+      GCHK(pm_prepare(ctx, N));
+      GCHK(pm_deposit(ctx, &p->pm, false));
+      b->p = ctx->pm.fft.rho.p;
+      b->bytes = (size_t) N * N * N * sizeof(double);
+      return GHIP_OK;
+    }
+  GCHK(pmnp_need_region(ctx, N, "the non-periodic mesh potential"));
+  GCHK(pmnp_prepare(ctx, N));
+  GCHK(pmnp_check_and_deposit(ctx, &b->outside));
+  b->p = ctx->pm.open.oct.p;
+  b->bytes = pmnp_block_bytes(N);
+  return GHIP_OK;
+}
+
+int ghip_pm_pot_solve(ghip_ctx *ctx, const ghip_pot_params *p, int nranks, const double *all, double *pot)
+{
+  return p->grav.periodic ? pm_potential(ctx, &p->pm, nranks, all, pot)
+                          : pmnp_potential(ctx, &p->pm, nranks, all, pot);
 }
 
 void ghip_pm_release(ghip_ctx *ctx)

@@ -341,24 +341,8 @@ extern "C" int ghip_ewald_get_pot_table(ghip_ctx *ctx, double BoxSize, double *h
 static int pot_check(ghip_ctx *ctx, const ghip_pot_params *p, const char *who)
 {
   const ghip_grav_params &g = p->grav;
-  const ghip_pm_params &pm = p->pm;
-  const int pmgrid = pm.pmgrid;
-  if(pmgrid != 0 && !g.periodic)
-    {
-      // pmpotential_nonperiodic: a region is set, of this PMGRID, and the walk is cut where the region says
-      GCHK(ghip_pmnp_potential_check(ctx, &g, &pm, who));
-    }
-  else if(pmgrid != 0)
-    {
-      if(pmgrid < 4 || pmgrid > 2048 || (pmgrid & 1) || !(pm.BoxSize > 0) || !(pm.Asmth > 0))
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: need an even PMGRID in [4, 2048], pm.BoxSize > 0, "
-                         "pm.Asmth > 0", who);
-      if(pm.BoxSize != g.BoxSize)
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: pm.BoxSize %g differs from grav.BoxSize %g", who,
-                         pm.BoxSize, g.BoxSize);
-      if(!(g.Rcut > 0 && g.Asmth > 0))
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: a PM potential needs Rcut, Asmth > 0", who);
-    }
+  if(p->pm.pmgrid != 0)
+    GCHK(ghip_pm_pot_check(ctx, p, who));
   if(g.periodic && !(g.BoxSize > 0))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: periodic needs BoxSize > 0", who);
   for(int t = 0; t < 6; t++)
@@ -522,22 +506,20 @@ extern "C" int ghip_potential(ghip_ctx *ctx, const ghip_pot_params *p)
       ctx->pot_n = 0;
       return GHIP_OK;
     }
-  // potential.c:262-270: pmpotential_periodic / pmpotential_nonperiodic(0).  The open mesh first checks that
-  // every particle lies inside its region: GHIP_EREGION before any potential is written
-  const bool open_mesh = p->pm.pmgrid > 0 && !p->grav.periodic;
-  if(open_mesh)
+  // potential.c:262-270: pmpotential_periodic / pmpotential_nonperiodic(0).  The deposit comes first: the open
+  // mesh checks with it that every particle lies inside its region, GHIP_EREGION before any potential is written
+  const bool mesh = p->pm.pmgrid > 0;
+  if(mesh)
     {
-      int outside = 0;
-      GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
-      if(outside)
+      PmBlock b;
+      GCHK(ghip_pm_pot_deposit(ctx, p, &b));
+      if(b.outside)
         return ghip_fail(ctx, GHIP_EREGION, "ghip_potential: a particle lies outside the allowed region of the mesh; "
                          "no potential was written.  Find the region again (ghip_pm_find_region) and repeat the call");
     }
   GCHK(pot_walk_and_finish(ctx, p, false));
-  if(open_mesh)
-    GCHK(ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, 1, nullptr, P<double>(ctx->pot)));
-  else if(p->pm.pmgrid > 0)
-    GCHK(ghip_pm_potential_add(ctx, &p->pm, P<double>(ctx->pot)));
+  if(mesh)
+    GCHK(ghip_pm_pot_solve(ctx, p, 1, nullptr, P<double>(ctx->pot)));
   GCHK(pot_quadratic(ctx, p));
   ctx->pot_n = n;
   return GHIP_OK;
@@ -615,21 +597,13 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
       GCHK(dd_read_status(ctx, &worst, &failed));
       GCHK(ghip_dd_raise(ctx, failed, "potential: the walk failed on shard %d (its own message says "
                          "why); every shard stops here", failed));
-      if(mesh && !p->grav.periodic)
-        {
-          // (the compact octant and its status word: a particle outside the region on any shard ends the
-          // call on all of them in SOLVE)
-          int outside = 0;
-          GCHK(ghip_pmnp_potential_deposit(ctx, p->pm.pmgrid, &outside));
-          ghip_dd_set_allgather(D, ghip_pmnp_block(ctx), ghip_pmnp_block_bytes(p->pm.pmgrid), &D.pm_all);
-          D.phase = SOLVE;
-          return 1;
-        }
       if(mesh)
         {
-          GCHK(ghip_pm_potential_deposit(ctx, &p->pm));
-          const size_t n3 = (size_t) p->pm.pmgrid * p->pm.pmgrid * p->pm.pmgrid;
-          ghip_dd_set_allgather(D, ctx->pm.rho.p, n3 * sizeof(double), &D.pm_all);
+          // (the open mesh's block carries its status word: a particle outside the region on any shard ends the
+          // call on all of them in SOLVE)
+          PmBlock b;
+          GCHK(ghip_pm_pot_deposit(ctx, p, &b));
+          ghip_dd_set_allgather(D, b.p, b.bytes, &D.pm_all);
           D.phase = SOLVE;
           return 1;
         }
@@ -639,11 +613,7 @@ int ghip_dd_pot_step(ghip_ctx *ctx)
     }
   if(D.phase == SOLVE)
     {
-      if(!p->grav.periodic)
-        GCHK(ghip_pmnp_potential_solve(ctx, p->pm.pmgrid, p->pm.G, D.nranks, P<double>(D.pm_all),
-                                       P<double>(ctx->pot)));
-      else
-        GCHK(ghip_pm_potential_solve(ctx, &p->pm, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
+      GCHK(ghip_pm_pot_solve(ctx, p, D.nranks, P<double>(D.pm_all), P<double>(ctx->pot)));
       GCHK(pot_quadratic(ctx, p));
       ctx->pot_n = n;
       return 0;

@@ -131,6 +131,26 @@ class Problem:
         fp.tree_build(self.extent[0], self.extent[1], self.extent[2], self.force_soft)
 
 
+def box_edge_particles(box, pmgrid, on_the_edge=True, n=64, seed=21):
+    """Particles for the cell rule of the periodic mesh (pm_periodic.c:318-325) as an ics dict: for each axis one
+    in the last cell (box (N - 0.5) / N: its +1 corner wraps), one at the origin, random interior ones, and, with
+    on_the_edge, for each axis one whose coordinate there equals the box size (the clamp: last cell, offset 1) and
+    one with all three.  Without on_the_edge the set is the same one less those four."""
+    rng = np.random.default_rng(seed)
+    pos = rng.uniform(0.05 * box, 0.95 * box, (n, 3))
+    mass = rng.uniform(0.5, 1.5, n) / n
+    for j in range(3):
+        pos[j, j] = box
+        pos[4 + j, j] = box * (pmgrid - 0.5) / pmgrid
+    pos[3] = box
+    pos[7] = 0.0
+    keep = np.arange(n) if on_the_edge else np.r_[4:n]
+    pos, mass = np.ascontiguousarray(pos[keep]), np.ascontiguousarray(mass[keep])
+    k = len(keep)
+    return dict(pos=pos, vel=np.zeros((k, 3)), mass=mass, type=np.ones(k, np.int32), ngas=0, boxsize=float(box),
+                spacing=box / 4.0, id=np.arange(1, k + 1, dtype=np.uint32), u=np.zeros(0))
+
+
 def sampled_hydro_check(pr, T, get_field, act, tol=1e-11, hparams=None):
     """hydro_force() of a big configuration against the oracle on the gas targets `act`: the oracle's
     hydro_evaluate for those targets on the DEVICE's density results of all gas particles (smoothing

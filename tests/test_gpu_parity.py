@@ -1875,6 +1875,32 @@ def test_pm_periodic_long_range_force_parity(ng, pmgrid):
 
 
 @pytest.mark.gpu
+def test_pm_periodic_cells_at_the_box_edges():
+    """The cell rule of pm_periodic.c:318-325 where it matters: a coordinate equal to BoxSize (truncates to N, is
+    clamped into the last cell with the offset 1 taken BEFORE the clamp), the last cell (its +1 corner wraps to
+    0) and the origin.  PMGRID 8; the oracle carries the same rule."""
+    from common import box_edge_particles
+    B = bindings()
+    N, box, G = 8, 2.5, 43007.1
+    ic = box_edge_particles(box, N)
+    pos, mass = ic["pos"], ic["mass"]
+    cell = ((N / box) * pos).astype(np.int64)
+    j = np.arange(3)   # (the clamp is met: these truncate to N, not to N - 1)
+    assert len(pos) == 64 and (cell[j, j] == N).all() and (cell[3] == N).all() and (cell[4 + j, j] == N - 1).all()
+    want = O.pm_periodic(pos, mass, box, G, N)
+    assert np.isfinite(want).all()
+    fp = B.ForcePath(0)
+    fp.set_counts(len(pos), 0)
+    fp.set_field(B.F_POS, pos)
+    fp.set_field(B.F_MASS, mass)
+    fp.pm_periodic(N, box, G)
+    got = fp.get_field(B.F_GRAVPM)
+    print("max|got - want| / max|want| = %.3g" % (np.abs(got - want).max() / np.abs(want).max()))
+    assert np.abs(got - want).max() < 1e-11 * np.abs(want).max()
+    fp.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("periodic", [0, 1, 2])
 def test_substeps_walk_the_drifted_and_kicked_tree_of_the_last_full_build(periodic):
     """Sub-step reuse of the tree (forcetree.c:1356-1651, force_drift_node / force_kick_node): after a

@@ -204,6 +204,36 @@ def test_no_particles_no_region_and_a_second_mesh_size():
     fp.close()
 
 
+def test_both_meshes_in_one_context():
+    """the periodic and the open mesh own their plans separately: re-making the periodic plans for another PMGRID
+    leaves the open mesh (plans, table) as it is, and the other way round"""
+    pos, mass = uniform300()
+    pos, box = pos + 1.0, 2.0   # inside [0, box) for the periodic mesh
+    fp = context(pos, mass)
+    want = {}
+
+    def periodic(pmgrid):
+        if pmgrid not in want:
+            want[pmgrid] = O.pm_periodic(pos, mass, box, G, pmgrid)
+        fp.pm_periodic(pmgrid, box, G)
+        got = fp.get_field(B.F_GRAVPM)
+        assert np.abs(got - want[pmgrid]).max() < 1e-11 * np.abs(want[pmgrid]).max(), ("periodic", pmgrid)
+
+    def open_mesh(find):
+        if find:
+            assert same_region(fp.pm_find_region(8), R.region(pos, 8))
+            want["open"] = R.pm_force(pos, mass, R.region(pos, 8), G)
+        fp.pm_nonperiodic(8, G)
+        assert close_enough(fp.get_field(B.F_GRAVPM), want["open"]), "open"
+
+    periodic(16)
+    open_mesh(True)
+    periodic(32)      # the periodic plans are re-made
+    open_mesh(False)  # the table is kept
+    periodic(16)
+    fp.close()
+
+
 def test_set_region_refuses_a_region_that_leaves_the_octant():
     pos, mass = uniform300()
     reg = R.region(pos, 16)

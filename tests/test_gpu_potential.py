@@ -170,6 +170,29 @@ def test_finish_and_mesh_potential(case):
     fp.close()
 
 
+def test_mesh_potential_cells_at_the_box_edges():
+    """the periodic mesh potential with particles in the last cell of every axis (the +1 corner wraps) and at the
+    origin, PMGRID 8: the set of test_pm_periodic_cells_at_the_box_edges without the coordinates equal to BoxSize"""
+    from common import box_edge_particles
+    pmgrid, G = 8, 0.7
+    pr = Problem(ic=box_edge_particles(2.5, pmgrid, on_the_edge=False), periodic=1)
+    ic = pr.ic
+    j = np.arange(3)
+    assert pr.n == 60 and (((pmgrid / pr.box) * ic["pos"]).astype(np.int64)[j, j] == pmgrid - 1).all()
+    fp, old = _device(pr)
+    fp.potential(_pot_params(pr, 0.0, G=G, pmgrid=pmgrid))
+    dev = fp.get_potential()
+    w, _ = _ref_walk(fp, pr, 0.0, old, np.arange(pr.n), pmgrid=pmgrid)
+    pm = dict(pmgrid=pmgrid, box=pr.box, asmth=1.25 * pr.box / pmgrid)
+    ref = R.finish(w, ic["pos"], ic["mass"], ic["type"], pr.force_soft / 2.8, G, periodic=True, pm=pm)
+    assert np.isfinite(ref).all()
+    print("err = %.3g" % _err(dev, ref))
+    assert _err(dev, ref) < 1e-10
+    bare = R.finish(w, ic["pos"], ic["mass"], ic["type"], pr.force_soft / 2.8, G)
+    assert _err(dev, bare) > 1e-6   # (the mesh part is not lost in the tolerance)
+    fp.close()
+
+
 def test_kept_tree_of_a_substep():
     pr = Problem(ng=8, periodic=0, gas=False)
     ic = pr.ic
