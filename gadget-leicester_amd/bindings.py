@@ -24,6 +24,7 @@ _FIELD_INFO = {  # gas-sized?, ncomp, is int
     F_TI_CURRENT: (0, 1, 1), F_GRAVPM: (0, 3, 0), F_ID: (0, 1, 1)}
 
 WALK_NEWTON, WALK_SHORTRANGE, WALK_EWALD, WALK_NEWTON_EWALD = 0, 1, 2, 3
+PRIM_SCAN, PRIM_WSCAN, PRIM_SELECT, PRIM_WSELECT, PRIM_SORT_U32 = 0, 1, 2, 3, 4   # ghip_debug_prim
 EN = 64
 
 GHIP_ERRORS = {-90001: "GHIP_EHIP", -90002: "GHIP_EINVAL", -90003: "GHIP_ENOMEM",
@@ -335,7 +336,8 @@ EXPORTS = [
     "ghip_set_dust_model", "ghip_dust_model_size", "ghip_dust_grains_size", "ghip_dust_density_grains",
     "ghip_dust_drag_grains",
     "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
-    "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts"]
+    "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts",
+    "ghip_debug_prim"]
 
 
 def lib():
@@ -379,6 +381,7 @@ def lib():
         L.ghip_density_evaluate.argtypes = [vp, C.POINTER(DensParams), C.c_int, C.c_double, vp]
         L.ghip_ngb_treefind.argtypes = [vp, vp, C.c_double, C.c_int, C.c_int, C.c_double, vp,
                                         C.c_int, C.POINTER(C.c_int)]
+        L.ghip_debug_prim.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
         L.ghip_peano_hilbert_keys.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
         L.ghip_morton_keys.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
         L.ghip_get_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -834,6 +837,13 @@ class ForcePath:
                                            int(periodic), float(boxsize), _ptr(buf), int(cap),
                                            C.byref(nf)))
         return buf[:min(nf.value, cap)].copy(), nf.value
+
+    def debug_prim(self, prim, values=None, flags=None, end_bit=0):
+        """one device primitive on host ints (PRIM_*): the scan, (the selected values, their count), the sort's permutation"""
+        a, f = [None if v is None else np.ascontiguousarray(v, dtype=np.int32) for v in (values, flags)]
+        out, cnt = np.zeros(len(f if a is None else a), np.int32), C.c_int(-1)
+        self._chk(self.L.ghip_debug_prim(self.h, int(prim), len(out), int(end_bit), _ptr(a), _ptr(f), _ptr(out), C.byref(cnt)))
+        return (out[:cnt.value].copy(), cnt.value) if prim in (PRIM_SELECT, PRIM_WSELECT) else out
 
     def peano_hilbert_keys(self, x, y, z, bits=21):
         x, y, z = [np.ascontiguousarray(a, dtype=np.int32) for a in (x, y, z)]

@@ -34,10 +34,9 @@
 // guest held elsewhere is shared too, which its owner learns from the guests' keys (k_let_level).
 #include <cstdarg>
 
-#include <hipcub/hipcub.hpp>
-
 #include "ghip_ngb.h"   // BoxK
 #include "ghip_keys.h"
+#include "ghip_prim.h"
 
 // tree.hip
 int ghip_dd_build_gas_tree(ghip_ctx *ctx);
@@ -803,7 +802,7 @@ __global__ void k_let_single(int nelem, const int4 *__restrict__ lk,
 
 // ---------------------------------------------------------------------------------------------
 // order-preserving selection of the items whose mask has bit b set, for every rank b at once:
-// count per block of SELM_BLOCK items and rank, scan per rank, scatter the item indices
+// count per block of SELM_BLOCK items and rank, offsets per rank (ghip_block_offsets), scatter the item indices
 // ---------------------------------------------------------------------------------------------
 #define SELM_ITEMS 16
 #define SELM_BLOCK (64 * SELM_ITEMS)
@@ -834,31 +833,6 @@ k_selm_count(int n, int nranks, const unsigned long long *__restrict__ mask, int
   __syncthreads();
   if(lane < nranks)
     blockcnt[(size_t) lane * nblk + blockIdx.x] = cnt[lane];
-}
-
-// one wavefront per rank: block counts -> exclusive offsets (in place), total[rank]
-__global__ void __launch_bounds__(64) k_selm_scan(int nblk, int *__restrict__ blockcnt,
-                                                  int *__restrict__ total)
-{
-  int *row = blockcnt + (size_t) blockIdx.x * nblk;
-  int run = 0;
-  for(int b0 = 0; b0 < nblk; b0 += 64)
-    {
-      const int b = b0 + threadIdx.x;
-      const int c = b < nblk ? row[b] : 0;
-      int incl = c;
-      for(int o = 1; o < 64; o <<= 1)
-        {
-          const int v = __shfl_up(incl, o, 64);
-          if((int) threadIdx.x >= o)
-            incl += v;
-        }
-      if(b < nblk)
-        row[b] = run + incl - c;
-      run += __shfl(incl, 63, 64);
-    }
-  if(threadIdx.x == 0)
-    total[blockIdx.x] = run;
 }
 
 struct SelOff
@@ -908,8 +882,7 @@ static int multi_select(ghip_ctx *ctx, int n, const unsigned long long *mask, De
   GCHK(ghip_ensure(ctx, D.selcnt, ((size_t) P_ * nblk + GHIP_MAXRANKS) * 4));
   int *bc = P<int>(D.selcnt), *tot = bc + (size_t) P_ * nblk;
   k_selm_count<<<nblk, 64, 0, st>>>(n, P_, mask, nblk, bc);
-  k_selm_scan<<<P_, 64, 0, st>>>(nblk, bc, tot);
-  HIPCHK(hipGetLastError());
+  GCHK(ghip_block_offsets(ctx, P_, nblk, bc, tot, st));
   int htot[GHIP_MAXRANKS];
   HIPCHK(hipMemcpyAsync(htot, tot, (size_t) P_ * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
@@ -1219,16 +1192,11 @@ int ghip_dd_dust_groups(ghip_ctx *ctx)
   if(nt > 0 && ctx->n > 0)
     {
       GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
-      hipcub::CountingInputIterator<int> seq(0);
       k_flag_dust_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n,
                                                           P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->dflags));
       HIPCHK(hipGetLastError());
       int *dnum = &ghip_words(ctx)->dust_partners;
-      size_t tb = 0;
-      HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, seq, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
-      GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
-      HIPCHK(hipcub::DeviceSelect::Flagged(ctx->cubtmp.p, tb, seq, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum,
-                                           nt, st));
+      GCHK(ghip_select_flagged(ctx, nullptr, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
       HIPCHK(hipMemcpyAsync(&nsel, dnum, 4, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
     }
@@ -1391,11 +1359,7 @@ static int sort_hosted_guests(ghip_ctx *ctx)
   GCHK(ghip_ensure(ctx, D.guest_sorted, (size_t) ng * 8));
   const unsigned long long *in = P<unsigned long long>(D.guest_recv);
   unsigned long long *out = P<unsigned long long>(D.guest_sorted);
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, in, out, ng, 0, 63, ctx->stream));
-  GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
-  HIPCHK(hipcub::DeviceRadixSort::SortKeys(ctx->cubtmp.p, tb, in, out, ng, 0, 63, ctx->stream));
-  return GHIP_OK;
+  return ghip_sort_keys(ctx, in, out, ng, 63, ctx->stream);
 }
 
 // after ghip_dd_post_guests (and the exchange it asked for): what can the others need of this tree?
@@ -1570,12 +1534,7 @@ static int density_step(ghip_ctx *ctx)
           k_flag_gas_targets<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->tg_grav), P<int>(ctx->gt.perm),
                                                            ng, P<int>(ctx->dflags));
           int *dnum = &ghip_words(ctx)->gas_targets;
-          size_t tb = 0;
-          HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, P<int>(ctx->tg_grav), P<int>(ctx->dflags),
-                                               P<int>(D.gas_tgt), dnum, nt, st));
-          GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
-          HIPCHK(hipcub::DeviceSelect::Flagged(ctx->cubtmp.p, tb, P<int>(ctx->tg_grav),
-                                               P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
+          GCHK(ghip_select_flagged(ctx, P<int>(ctx->tg_grav), P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
           HIPCHK(hipMemcpyAsync(&ngt, dnum, 4, hipMemcpyDeviceToHost, st));
           HIPCHK(ghip_stream_sync(ctx, st));
         }
@@ -1883,15 +1842,6 @@ __global__ void k_mig_move_new(int nrecv, const MigRec *__restrict__ rec,
     }
 }
 
-static int scan_u64(ghip_ctx *ctx, const unsigned long long *in, unsigned long long *out, int n)
-{
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, ctx->stream));
-  GCHK(ghip_ensure(ctx, ctx->cubtmp, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->cubtmp.p, tb, in, out, n, ctx->stream));
-  return GHIP_OK;
-}
-
 // GHIP_DD_MIGRATE:
 //   SEND   the owner of every local particle's key; those of other shards packed   -> all-to-all-v of MigRec
 //   MERGE  kept and received particles into the new layout (gas first), the resident arrays swapped
@@ -1980,8 +1930,8 @@ static int migrate_step(ghip_ctx *ctx)
       if(nrecv > 0)
         k_mig_flags_new<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<MigRec>(D.mig_recv), vn);
       HIPCHK(hipGetLastError());
-      GCHK(scan_u64(ctx, vo, ro, n + 1));
-      GCHK(scan_u64(ctx, vn, rn, nrecv + 1));
+      GCHK(ghip_scan(ctx, vo, ro, n + 1, ctx->stream));
+      GCHK(ghip_scan(ctx, vn, rn, nrecv + 1, ctx->stream));
       unsigned long long tot[2];
       HIPCHK(hipMemcpyAsync(&tot[0], ro + n, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(&tot[1], rn + nrecv, 8, hipMemcpyDeviceToHost, st));

@@ -23,9 +23,8 @@
 // sum is a per-thread loop in a fixed order: two identical calls give identical bits.
 #include <climits>
 
-#include <hipcub/hipcub.hpp>
-
 #include "ghip_ngb.h"
+#include "ghip_prim.h"
 
 #define DUST_RHO_GRAIN 3.           // rho_dust, dust.c:379
 #define DUST_LEAF 16                // a tree node with at most this many particles is swept flat
@@ -630,11 +629,7 @@ static int dust_upload_list(ghip_ctx *ctx, int nd, const int *idx, const char *w
   int end_bit = 1;
   while(end_bit < 32 && (1LL << end_bit) <= nsorted)
     end_bit++;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
-  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, dkey, dkey2, dslot, dord, nd, 0, end_bit, st));
-  return GHIP_OK;
+  return ghip_sort_pairs(ctx, dkey, dkey2, dslot, dord, nd, end_bit, st);
 }
 
 // One pass in the record every layer below the entries reads.  g == nullptr (a *_grains entry without its struct)
@@ -829,10 +824,9 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
                                                    tbin, t.nelem, nodes, P<int>(t.perm), K.b, dcnt + D,
                                                    nullptr, nullptr, nullptr);
   HIPCHK(hipGetLastError());
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, dcnt, doff, m + 1, st));
-  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->dust_cub.p, tb, dcnt, doff, m + 1, st));
+  // (counts: never negative, and a sum of 64-bit words has the same bits signed or unsigned)
+  GCHK(ghip_scan(ctx, reinterpret_cast<const unsigned long long *>(dcnt),
+                     reinterpret_cast<unsigned long long *>(doff), m + 1, st));
   long long npairs = 0;
   if(ctx->ngas > 0)
     HIPCHK(hipMemcpyAsync(&npairs, doff + m, 8, hipMemcpyDeviceToHost, st));
@@ -858,10 +852,7 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
   int end_bit = 33;
   while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
     end_bit++;
-  tb = 0;
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
-  GCHK(ghip_ensure(ctx, ctx->dust_cub, tb + 256));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->dust_cub.p, tb, k0, k1, w0, w1, (int) np, 0, end_bit, st));
+  GCHK(ghip_sort_pairs(ctx, k0, k1, w0, w1, (int) np, end_bit, st));
   k_dust_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, m, cw, ctx->n, mass, tbin,
                                                   P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_ENTROPY]),
                                                   P<double>(ctx->dust_heat), K);

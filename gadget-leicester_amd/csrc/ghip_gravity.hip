@@ -6,8 +6,7 @@
 // the OldAcc / G post-pass (gravtree.c:381-403) and ewald_init() (forcetree.c:4402-4527).
 #include <cmath>
 
-#include <hipcub/hipcub.hpp>
-
+#include "ghip_prim.h"
 #include "ghip_walk.h"
 
 // the post-pass of gravity_tree (gravtree.c:362-403), in the reference's order:
@@ -458,8 +457,7 @@ static int build_plan(ghip_ctx *ctx, int kind, int nb, int ns, WalkPlan &plan, i
 {
   hipStream_t st = on ? on : ctx->stream;
   DevBuf &b_nsub = slot ? ctx->plan_nsub2 : ctx->plan_nsub, &b_woff = slot ? ctx->plan_woff2 : ctx->plan_woff,
-         &b_wave = slot ? ctx->plan_wave2 : ctx->plan_wave,
-         &b_tmp = slot ? ctx->cubtmp2 : (st == ctx->stream3 && st != ctx->stream ? ctx->cubtmp3 : ctx->cubtmp);
+         &b_wave = slot ? ctx->plan_wave2 : ctx->plan_wave;
   int sbase = (49152 + nb - 1) / nb;
   sbase = sbase < 8 ? 8 : (sbase > 64 ? 64 : sbase);
   if(sbase > ns)
@@ -508,12 +506,9 @@ static int build_plan(ghip_ctx *ctx, int kind, int nb, int ns, WalkPlan &plan, i
   unsigned int *prev = P<unsigned int>(ctx->plan_steps[kind][cur]);
   unsigned int *out = P<unsigned int>(ctx->plan_steps[kind][cur ^ 1]);
   k_plan_nsub<<<cdiv(nb, 256), 256, 0, st>>>(nb, ns, sbase, prev, nprev, P<int>(b_nsub));
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, P<int>(b_nsub),
-                                          P<int>(b_woff), nb, st));
-  GCHK(ghip_ensure(ctx, b_tmp, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(b_tmp.p, tb, P<int>(b_nsub),
-                                          P<int>(b_woff), nb, st));
+  // (the scratch of slot 1 is stream2's whichever stream builds the plan: the Ewald plan of a pair is built on
+  // the main stream until an Ewald walk has run on stream2 -- ghip_gravity_impl -- and has always scanned there)
+  GCHK(ghip_scan(ctx, P<int>(b_nsub), P<int>(b_woff), nb, st, slot ? &ghip_prim_scratch(ctx, ctx->stream2) : nullptr));
   HIPCHK(hipMemsetAsync(b_wave.p, 0xff, (size_t) maxwaves * 4, st));
   k_plan_fill<<<cdiv(nb, 256), 256, 0, st>>>(nb, P<int>(b_nsub), P<int>(b_woff),
                                              maxwaves, P<int>(b_wave), out,

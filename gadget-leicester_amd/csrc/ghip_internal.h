@@ -351,7 +351,7 @@ struct alignas(64) PinnedWords
 {
   TreeSizes sizes[2];   // host mirrors of the trees' sizes (gt.hsz, st.hsz)
   int gas_mixed;        // the record unpack met a record of the gas block [0, ngas) that is not Type 0
-  int sel_left;         // ghip_density_impl: targets left after an h iteration, written by k_sel_scan (a
+  int sel_left;         // ghip_density_impl: targets left after an h iteration, written by ghip_wsel_count (a
                         // copy to the host would be one more kernel of the runtime's that waits behind the pair)
 };
 
@@ -502,8 +502,8 @@ struct ghip_ctx
   DevBuf bh_swallow, bh_injected;   // "next" row N4 (ghip_sink.hip): P[].SwallowID u32[n],
                                     // SphP[].i.Injected_BH_Energy f64[ngas]
   DevBuf dust_heat;                 // dust_drag (ghip_dust.hip): SphP[].dh.DragHeating f64[ngas]
-  DevBuf dust_idx, dust_work, dust_pairs, dust_cub;   // ... its grain list, per-grain planes, sorted pairs
-  DevBuf sfr_work, sfr_cub;         // ghip_sfr_cooling (ghip_sfr.hip): candidate flags, offsets, counts
+  DevBuf dust_idx, dust_work, dust_pairs;   // ... its grain list, per-grain planes, sorted pairs
+  DevBuf sfr_work;                  // ghip_sfr_cooling (ghip_sfr.hip): candidate flags, offsets, counts
   int timestep_endrun = 0;   // endrun code of the last ghip_advance_timesteps failure
   // the shipped bundle's integrator (ghip_set_integration_flags, ghip_kick.hip / ghip_drift.hip)
   bool iflags_on = false;

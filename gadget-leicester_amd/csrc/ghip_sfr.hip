@@ -14,9 +14,8 @@
 // mask and its population count per wavefront, an exclusive scan of the counts gives every wavefront
 // its first slot, and a scatter writes each candidate at its slot plus the number of candidates below
 // it in the mask.  The host reads two ints and the ncand candidates, never an [ngas] array.
-#include <hipcub/hipcub.hpp>
-
 #include "ghip_ngb.h"   // the reference's constants
+#include "ghip_prim.h"
 
 #define SFR_TAPPER_RHO 1.e-10      // rho_crit of BETA_COOLING_TAPPER_OFF, cooling.c:219
 
@@ -257,10 +256,7 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
                                     P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
                                     P<double>(ctx->bh_injected), dragheat, K, dmask, dcnt, dnfloor);
   HIPCHK(hipGetLastError());
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, dcnt, doff, (int) nw + 1, st));
-  GCHK(ghip_ensure(ctx, ctx->sfr_cub, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->sfr_cub.p, tb, dcnt, doff, (int) nw + 1, st));
+  GCHK(ghip_scan(ctx, dcnt, doff, (int) nw + 1, st));
   if(cand_idx)
     {
       k_sfr_scatter<<<nb, 256, 0, st>>>(nact, dact, dmask, doff, dcand);

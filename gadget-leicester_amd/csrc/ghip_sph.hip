@@ -18,6 +18,7 @@
 // summation order differs.
 
 #include "ghip_ngb.h"
+#include "ghip_prim.h"
 #include <cmath>
 
 // Bounds of a bucket's targets around the first target: half extents per axis (nearest-image
@@ -595,73 +596,6 @@ static int dens_alloc(ghip_ctx *ctx)
   return GHIP_OK;
 }
 
-// Order-preserving selection of the flagged entries of the target list (the not yet converged
-// particles of an h-iteration, density.c:566-660).  Three small launches of one-wavefront
-// workgroups instead of a library select: its single-pass look-back kernel needs 256-thread
-// workgroups to make progress in order, and underneath a gravity pair -- where the density
-// iterations normally run -- they wait milliseconds for four free wave slots on one CU.
-#define SEL_ITEMS 16
-#define SEL_BLOCK (64 * SEL_ITEMS)
-
-__global__ void __launch_bounds__(64) k_sel_count(int n, const int *__restrict__ flags,
-                                                  int *__restrict__ blockcnt)
-{
-  const int base = blockIdx.x * SEL_BLOCK;
-  int c = 0;
-  for(int j = 0; j < SEL_ITEMS; j++)
-    {
-      const int a = base + j * 64 + threadIdx.x;
-      c += (a < n && flags[a] != 0) ? 1 : 0;
-    }
-  for(int o = 32; o > 0; o >>= 1)
-    c += __shfl_down(c, o, 64);
-  if(threadIdx.x == 0)
-    blockcnt[blockIdx.x] = c;
-}
-
-// counts -> exclusive offsets (in place), total to *total; one wavefront
-__global__ void __launch_bounds__(64) k_sel_scan(int nblk, int *__restrict__ blockcnt,
-                                                 int *__restrict__ total)
-{
-  int run = 0;
-  for(int b0 = 0; b0 < nblk; b0 += 64)
-    {
-      const int b = b0 + threadIdx.x;
-      const int c = b < nblk ? blockcnt[b] : 0;
-      int incl = c;
-      for(int o = 1; o < 64; o <<= 1)
-        {
-          const int v = __shfl_up(incl, o, 64);
-          if((int) threadIdx.x >= o)
-            incl += v;
-        }
-      if(b < nblk)
-        blockcnt[b] = run + incl - c;
-      run += __shfl(incl, 63, 64);
-    }
-  if(threadIdx.x == 0)
-    *total = run;
-}
-
-__global__ void __launch_bounds__(64) k_sel_scatter(int n, const int *__restrict__ in,
-                                                    const int *__restrict__ flags,
-                                                    const int *__restrict__ blockoff,
-                                                    int *__restrict__ out)
-{
-  const int base = blockIdx.x * SEL_BLOCK;
-  int off = blockoff[blockIdx.x];
-  const unsigned long long below = (1ull << threadIdx.x) - 1ull;
-  for(int j = 0; j < SEL_ITEMS; j++)
-    {
-      const int a = base + j * 64 + threadIdx.x;
-      const bool keep = a < n && flags[a] != 0;
-      const unsigned long long m = __ballot(keep);
-      if(keep)
-        out[off + __popcll(m & below)] = in[a];
-      off += __popcll(m);
-    }
-}
-
 int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
 {
   // the first phase of a step that modifies persistent state (smoothing lengths): an asynchronously
@@ -704,7 +638,7 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
                p->Timebase_interval};
   int maxiter = p->MaxIter > 0 ? p->MaxIter : 150;
   int ncur = nt, iter = 0;
-  GCHK(ghip_ensure(ctx, ctx->cubtmp, ((size_t) cdiv(nt, SEL_BLOCK) + 2) * 4));
+  GCHK(ghip_ensure(ctx, ctx->cubtmp, ((size_t) cdiv(nt, PRIM_BLOCK) + 2) * 4));
   int *seloff = P<int>(ctx->cubtmp);
 
   while(ncur > 0)
@@ -731,18 +665,13 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
         P<double>(ctx->f[GHIP_F_PRESSURE]), P<int>(ctx->dflags));
       HIPCHK(hipGetLastError());
       S.dens_target_evals += ncur;
-      // the targets that are not yet converged, in list order (see k_sel_count)
-      const int nblk = cdiv(ncur, SEL_BLOCK);
-      k_sel_count<<<nblk, 64, 0, st>>>(ncur, P<int>(ctx->dflags), seloff);
-      k_sel_scan<<<1, 64, 0, st>>>(nblk, seloff, dnum);
+      // the targets that are not yet converged (density.c:566-660), in list order: the one-wavefront selection
+      GCHK(ghip_wsel_count(ctx, ncur, P<int>(ctx->dflags), seloff, dnum, st));
       HIPCHK(ghip_stream_sync(ctx, st));
       const int left = *reinterpret_cast<const volatile int *>(dnum);
       GCHK(ghip_check_device_errors(ctx));   // (also what an asynchronous drift / kick deferred)
       if(left > 0)
-        {
-          k_sel_scatter<<<nblk, 64, 0, st>>>(ncur, cur, P<int>(ctx->dflags), seloff, nxt);
-          HIPCHK(hipGetLastError());
-        }
+        GCHK(ghip_wsel_scatter(ctx, ncur, cur, P<int>(ctx->dflags), seloff, nxt, st));
       ncur = left;
       int *tmp = cur;
       cur = nxt;

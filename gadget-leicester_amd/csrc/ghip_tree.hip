@@ -14,10 +14,9 @@
 //     simply e+1 and "sibling" is a stored skip index.  A wavefront walks it with a wave-uniform
 //     element index, i.e. with scalar loads.
 // Children are visited in Morton-octant order (x lowest bit), the order of Nodes[].u.suns[].
-#include <hipcub/hipcub.hpp>
-
 #include "ghip_internal.h"
 #include "ghip_keys.h"
+#include "ghip_prim.h"
 
 __global__ void k_morton_from_pos(int n, const double *__restrict__ x, const double *__restrict__ y,
                                   const double *__restrict__ z, double cx, double cy, double cz,
@@ -988,40 +987,6 @@ static int rnd_order(ghip_ctx *ctx, TreeDev &t, int n, const double *x, const do
   return GHIP_OK;
 }
 
-static int cub_tmp(ghip_ctx *ctx, size_t bytes)
-{
-  return ghip_ensure(ctx, ctx->cubtmp, bytes + 256);
-}
-
-// Radix sort of (32-bit key, index) pairs on bits [0, end_bit).  Below 2^20 keys the library picks a
-// block sort followed by ~19 merge passes (~125 us at 5e5 keys, all dependent ~5 us launches).  Its
-// one-sweep radix sort (GHIP_SORT_ONESWEEP=1) needs fewer launches but was measured slower here:
-// a histogram pass, its scan, and per 8-bit digit two clears + one 25 us pass = 157 us.
-// tmp: scratch of the stream the sort runs on (ctx->cubtmp: main stream, ctx->cubtmp2: stream2)
-static int sort_pairs_u32(ghip_ctx *ctx, const unsigned int *kin, unsigned int *kout, const int *vin,
-                          int *vout, int n, int end_bit, hipStream_t st, DevBuf &tmp)
-{
-  static int onesweep = -1;
-  if(onesweep < 0)
-    onesweep = (getenv("GHIP_SORT_ONESWEEP") && atoi(getenv("GHIP_SORT_ONESWEEP")) == 1) ? 1 : 0;
-  size_t tb = 0;
-  if(onesweep && n > 4096)
-    {
-      using cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                             rocprim::default_config, 0>;
-      HIPCHK(rocprim::radix_sort_pairs<cfg>(nullptr, tb, kin, kout, vin, vout, (size_t) n, 0u,
-                                            (unsigned int) end_bit, st));
-      GCHK(ghip_ensure(ctx, tmp, tb + 256));
-      HIPCHK(rocprim::radix_sort_pairs<cfg>(tmp.p, tb, kin, kout, vin, vout, (size_t) n, 0u,
-                                            (unsigned int) end_bit, st));
-      return GHIP_OK;
-    }
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, n, 0, end_bit, st));
-  GCHK(ghip_ensure(ctx, tmp, tb + 256));
-  HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, kin, kout, vin, vout, n, 0, end_bit, st));
-  return GHIP_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // tree construction driver.  The build is latency-bound (dozens of launches of a few us each),
 // so the steps are arranged for few launches and ONE host round trip for both trees:
@@ -1132,92 +1097,6 @@ __global__ void k_peano_hi(int n, int levels, const double *__restrict__ x,
   idx[i] = i;
 }
 
-// Exclusive scan of ints out of one-wavefront workgroups, for scans that run underneath a gravity
-// pair: the library's single-pass scan uses 256-thread workgroups, which wait behind the walks for
-// four free wavefront slots on one CU (see ghip_wg).  Three launches: per-block sums, their scan by
-// one wavefront, the blocks' local scans.
-#define WSCAN_ITEMS 16
-#define WSCAN_BLOCK (64 * WSCAN_ITEMS)
-__global__ void __launch_bounds__(64) k_wscan_sums(int n, const int *__restrict__ in, int *__restrict__ bsum)
-{
-  const int base = blockIdx.x * WSCAN_BLOCK + threadIdx.x * WSCAN_ITEMS;
-  int c = 0;
-  for(int j = 0; j < WSCAN_ITEMS; j++)
-    c += (base + j < n) ? in[base + j] : 0;
-  for(int o = 32; o > 0; o >>= 1)
-    c += __shfl_down(c, o, 64);
-  if(threadIdx.x == 0)
-    bsum[blockIdx.x] = c;
-}
-
-__global__ void __launch_bounds__(64) k_wscan_blocks(int nblk, int *__restrict__ bsum)
-{
-  int run = 0;
-  for(int b0 = 0; b0 < nblk; b0 += 64)
-    {
-      const int b = b0 + threadIdx.x;
-      const int c = b < nblk ? bsum[b] : 0;
-      int incl = c;
-      for(int o = 1; o < 64; o <<= 1)
-        {
-          const int v = __shfl_up(incl, o, 64);
-          if((int) threadIdx.x >= o)
-            incl += v;
-        }
-      if(b < nblk)
-        bsum[b] = run + incl - c;
-      run += __shfl(incl, 63, 64);
-    }
-}
-
-__global__ void __launch_bounds__(64) k_wscan_apply(int n, const int *__restrict__ in,
-                                                    const int *__restrict__ boff, int *__restrict__ out)
-{
-  const int base = blockIdx.x * WSCAN_BLOCK + threadIdx.x * WSCAN_ITEMS;
-  int v[WSCAN_ITEMS], c = 0;
-  for(int j = 0; j < WSCAN_ITEMS; j++)
-    {
-      v[j] = (base + j < n) ? in[base + j] : 0;
-      c += v[j];
-    }
-  int incl = c;
-  for(int o = 1; o < 64; o <<= 1)
-    {
-      const int u = __shfl_up(incl, o, 64);
-      if((int) threadIdx.x >= o)
-        incl += u;
-    }
-  int run = boff[blockIdx.x] + incl - c;
-  for(int j = 0; j < WSCAN_ITEMS; j++)
-    {
-      if(base + j < n)
-        out[base + j] = run;
-      run += v[j];
-    }
-}
-
-static int exclusive_sum(ghip_ctx *ctx, const int *in, int *out, int n, hipStream_t on = nullptr)
-{
-  hipStream_t st = on ? on : ctx->stream;
-  if(ctx->grav_pending && st == ctx->stream)
-    {
-      const int nblk = cdiv(n, WSCAN_BLOCK);
-      GCHK(ghip_ensure(ctx, ctx->cubtmp, (size_t) (nblk + 2) * 4));
-      int *bsum = P<int>(ctx->cubtmp);
-      k_wscan_sums<<<nblk, 64, 0, st>>>(n, in, bsum);
-      k_wscan_blocks<<<1, 64, 0, st>>>(nblk, bsum);
-      k_wscan_apply<<<nblk, 64, 0, st>>>(n, in, bsum, out);
-      HIPCHK(hipGetLastError());
-      return GHIP_OK;
-    }
-  DevBuf &tmp = (st == ctx->stream) ? ctx->cubtmp : ctx->cubtmp2;   // scratch of the stream it runs on
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, st));
-  GCHK(ghip_ensure(ctx, tmp, tb + 256));
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, n, st));
-  return GHIP_OK;
-}
-
 static int *tree_dinfo(ghip_ctx *ctx, bool gas)
 {
   return ghip_words(ctx)->tree_info[gas ? 1 : 0];
@@ -1305,14 +1184,13 @@ static int sort_by_key(ghip_ctx *ctx, TreeDev &t, int n, const double *x, const 
     k_override_keys<<<cdiv(n - nlocal, 256), 256, 0, st>>>(nlocal, n, given_keys,
                                                            P<unsigned long long>(t.key));
   HIPCHK(hipGetLastError());
-  size_t tb = 0;
   if(!wide)
     {
       // top 32 key bits first, then the (rare) runs of equal top bits by their full keys
       unsigned int *hi_in = P<unsigned int>(t.phkey), *hi_out = hi_in + n;
       if(!fused)
         k_key_hi<<<cdiv(n, 256), 256, 0, st>>>(n, 31, P<unsigned long long>(t.key), hi_in);
-      GCHK(sort_pairs_u32(ctx, hi_in, hi_out, P<int>(t.idx), P<int>(t.perm), n, 32, st, ctx->cubtmp));
+      GCHK(ghip_sort_pairs(ctx, hi_in, hi_out, P<int>(t.idx), P<int>(t.perm), n, 32, st));
       k_gather_keys<<<cdiv(n, 256), 256, 0, st>>>(n, P<int>(t.perm), P<unsigned long long>(t.key),
                                                   P<unsigned long long>(t.skey));
       k_fix_runs<<<cdiv(n, 256), 256, 0, st>>>(n, 32, P<unsigned long long>(t.skey),
@@ -1320,15 +1198,8 @@ static int sort_by_key(ghip_ctx *ctx, TreeDev &t, int n, const double *x, const 
       HIPCHK(hipGetLastError());
     }
   else
-    {
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, P<unsigned long long>(t.key),
-                                                P<unsigned long long>(t.skey), P<int>(t.idx),
-                                                P<int>(t.perm), n, 0, 63, st));
-      GCHK(cub_tmp(ctx, tb));
-      HIPCHK(hipcub::DeviceRadixSort::SortPairs(ctx->cubtmp.p, tb, P<unsigned long long>(t.key),
-                                                P<unsigned long long>(t.skey), P<int>(t.idx),
-                                                P<int>(t.perm), n, 0, 63, st));
-    }
+    GCHK(ghip_sort_pairs(ctx, P<unsigned long long>(t.key), P<unsigned long long>(t.skey), P<int>(t.idx),
+                         P<int>(t.perm), n, 63, st));
   return GHIP_OK;
 }
 
@@ -1345,7 +1216,7 @@ static int gas_order_from_gravity_tree(ghip_ctx *ctx)
   GCHK(ghip_ensure(ctx, ctx->dtgt_b, (size_t) n * 4 + 16));
   const int wg = ghip_wg(ctx);
   k_gas_flags<<<cdiv(n, wg), wg, 0, st>>>(n, ng, P<int>(g.perm), P<int>(ctx->dtgt_a));
-  GCHK(exclusive_sum(ctx, P<int>(ctx->dtgt_a), P<int>(ctx->dtgt_b), n));
+  GCHK(ghip_scan_i32_under_pair(ctx, P<int>(ctx->dtgt_a), P<int>(ctx->dtgt_b), n, st));
   t.rnd = g.rnd;
   if(t.rnd)
     GCHK(ghip_ensure(ctx, t.skey2, (size_t) ng * 8));
@@ -1387,7 +1258,7 @@ static int count_nodes(ghip_ctx *ctx, TreeDev &t, int n, bool gas, int cap_nodes
                                                          ghip_errword(ctx, GHIP_ERRW_TREE));
   HIPCHK(hipGetLastError());
   (void) wg;
-  GCHK(exclusive_sum(ctx, P<int>(t.cnt), P<int>(t.nb), n));
+  GCHK(ghip_scan_i32_under_pair(ctx, P<int>(t.cnt), P<int>(t.nb), n, st));
   k_tree_info<<<1, 1, 0, st>>>(n, P<int>(t.nb), P<int>(t.cnt), dinfo, cap_nodes, wide ? 1 : 0,
                                ctx->build_gen, P<TreeSizes>(t.dsz), t.hsz);
   HIPCHK(hipGetLastError());
@@ -1544,9 +1415,8 @@ static int curve_order(ghip_ctx *ctx, hipStream_t st)
                                            P<double>(ctx->sz), ctx->corner[0], ctx->corner[1],
                                            ctx->corner[2], fac, hi_in, P<int>(g.idx));
   HIPCHK(hipGetLastError());
-  // (a 32-bit hipcub sort with begin_bit != 0 mis-sorts on this ROCm: the digits sit at bit 0)
-  DevBuf &tmp = (st == ctx->stream) ? ctx->cubtmp : ctx->cubtmp2;
-  GCHK(sort_pairs_u32(ctx, hi_in, hi_out, P<int>(g.idx), P<int>(g.phorder), n, 3 * levels, st, tmp));
+  // (a 32-bit library sort with begin_bit != 0 mis-sorts on this ROCm: the digits sit at bit 0)
+  GCHK(ghip_sort_pairs(ctx, hi_in, hi_out, P<int>(g.idx), P<int>(g.phorder), n, 3 * levels, st));
   return GHIP_OK;
 }
 
@@ -1568,7 +1438,7 @@ static int gas_curve_order(ghip_ctx *ctx)
   GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) n * 4));
   int *flag = P<int>(ctx->dflags), *pos = P<int>(ctx->dtgt_a);
   k_gas_flags_ph<<<cdiv(n, wg), wg, 0, st>>>(n, ng, P<int>(g.phorder), P<int>(g.perm), flag);
-  GCHK(exclusive_sum(ctx, flag, pos, n, st));
+  GCHK(ghip_scan_i32_under_pair(ctx, flag, pos, n, st));
   k_gas_compact_ph<<<cdiv(n, wg), wg, 0, st>>>(n, ng, P<int>(g.phorder), P<int>(g.perm),
                                                P<int>(ctx->dtgt_b), pos, P<int>(t.phorder));
   HIPCHK(hipGetLastError());
@@ -1939,7 +1809,7 @@ int ghip_dd_build_gas_tree(ghip_ctx *ctx)
                                              ctx->corner[0], ctx->corner[1], ctx->corner[2], fac,
                                              hi_in, P<int>(t.idx));
   HIPCHK(hipGetLastError());
-  GCHK(sort_pairs_u32(ctx, hi_in, hi_out, P<int>(t.idx), P<int>(t.phorder), nsg, 3 * levels, st, ctx->cubtmp));
+  GCHK(ghip_sort_pairs(ctx, hi_in, hi_out, P<int>(t.idx), P<int>(t.phorder), nsg, 3 * levels, st));
   ctx->stats.gastree_nodes = t.nnodes;
   return GHIP_OK;
 }
@@ -2235,12 +2105,7 @@ static int make_list(ghip_ctx *ctx, TreeDev &t, int host_limit, DevBuf &list, in
                                              P<int>(ctx->dtgt_a));
   HIPCHK(hipGetLastError());
   int *dnum = &ghip_words(ctx)->list_count;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tb, P<int>(t.phorder), P<int>(ctx->dtgt_a),
-                                       P<int>(list), dnum, n, st));
-  GCHK(cub_tmp(ctx, tb));
-  HIPCHK(hipcub::DeviceSelect::Flagged(ctx->cubtmp.p, tb, P<int>(t.phorder),
-                                       P<int>(ctx->dtgt_a), P<int>(list), dnum, n, st));
+  GCHK(ghip_select_flagged(ctx, P<int>(t.phorder), P<int>(ctx->dtgt_a), P<int>(list), dnum, n, st));
   HIPCHK(hipMemcpyAsync(count, dnum, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
   return GHIP_OK;

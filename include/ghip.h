@@ -1161,6 +1161,13 @@ int ghip_density_evaluate(ghip_ctx *ctx, const ghip_dens_params *p, int target, 
  * writes up to cap host indices, returns the count in *nfound */
 int ghip_ngb_treefind(ghip_ctx *ctx, const double center[3], double hsml, int pairs,
                       int periodic, double boxsize, int *ngblist, int cap, int *nfound);
+/* diagnostic: one device primitive on n >= 1 host ints, on the main stream; out holds n ints.  prim:
+ *   0, 1  out = exclusive sums of in (the scan library's form, the one-wavefront form)
+ *   2, 3  out = the in[a] with flags[a] != 0, in order (in == NULL: the indices a), *count = their number (same two forms)
+ *   4     out = the permutation that sorts the keys in (unsigned, below 2^end_bit) stably */
+enum { GHIP_PRIM_SCAN, GHIP_PRIM_WSCAN, GHIP_PRIM_SELECT, GHIP_PRIM_WSELECT, GHIP_PRIM_SORT_U32 };
+int ghip_debug_prim(ghip_ctx *ctx, int prim, int n, int end_bit, const int *in, const int *flags,
+                    int *out, int *count);
 
 /* ---- keys (peano.c:300-358), device evaluation of n integer triplets ---- */
 int ghip_peano_hilbert_keys(ghip_ctx *ctx, int n, const int *x, const int *y, const int *z,
