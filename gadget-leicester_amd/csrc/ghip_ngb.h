@@ -2,8 +2,10 @@
 // wrap, the node test of ngb_treefind_*, the gas-tree node record, the cubic-spline kernel and its
 // constants, and two walkers over a pre-order element list.  Included by every file that searches
 // neighbours (ghip_sph.hip, ghip_sink.hip, ghip_dust.hip, ghip_dd.hip) or needs the constants
-// (ghip_sfr.hip).  The hot SPH kernels (k_density, k_hydro, k_ngb_find) use the primitives but keep
-// their own staged loops; the walkers serve the passes with few or cheap targets.
+// (ghip_sfr.hip).  The walkers serve the passes with few or cheap targets.  The hot SPH kernels use the
+// primitives under a loop of their own: k_density and k_hydro share the staged bucket sweep
+// d_sph_sweep of ghip_sph.hip (it stays there, next to the LDS staging, the bucket cull and the
+// candidate slots it is made of); k_ngb_find is one thread with a per-candidate distance.
 #ifndef GHIP_NGB_H
 #define GHIP_NGB_H
 

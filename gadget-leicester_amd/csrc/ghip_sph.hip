@@ -188,6 +188,9 @@ __device__ __forceinline__ double d_slot_max(double v)
 // survivors per target) and CS survivors share one pass of the pair arithmetic: at TG = 16 a
 // candidate test accepts 4 x as often as with 64 targets per wavefront.  The slots' partial sums are
 // added in fixed order at the end.
+// That staged loop is d_sph_sweep below, once for k_density and k_hydro: a kernel loads its targets,
+// bounds them (d_bucket_box), hands the sweep what it does with a candidate, and reduces and writes
+// its sums.
 // Workgroups are dealt to the 8 XCDs in turn (workgroup b runs on XCD b % 8), so with the plain order
 // every XCD's resident buckets are spread over the whole curve and its 4 MB L2 sees the whole gas set
 // (hydro at c2: 1.5 GB of fabric traffic per launch for 1.0 GB of algorithmic bytes, L2 hit rate 46 %).
@@ -203,6 +206,79 @@ __device__ __forceinline__ int d_sph_block(int xcd, int nblocks)
   return lb < nblocks ? lb : -1;
 }
 
+// the callables a kernel hands to d_sph_sweep must dissolve into it: a call would put the target's
+// state into private memory
+#define SPH_INLINE __attribute__((always_inline))
+
+// The bucket sweep under k_density and k_hydro.  Wavefront `sub` of the nsub that share a bucket walks
+// the element list with a wave-uniform index and takes every nsub-th batch, a batch being a
+// lone-particle element or one round of SPH_STAGE candidates of a flat-swept node.  The kernels
+// differ in four callables:
+//   reach(hmax)       the lane's search distance for a node whose particles' h is at most hmax
+//   lone(p)           a lone-particle element p that is alive, on this wavefront's turn
+//   stage(p, c0, c1)  the lane puts candidate p into its LDS slot and leaves what the bucket cull reads:
+//                     (x, y, z, m) in c0 and, in a pair search, (vx, vy, vz, h_j) in c1 -- else c1 stays 0
+//   pair(j)           the lane's pair with staged candidate j (j < 0: none in this pass)
+// (valid, p[xyz]: the lane's target, as the node test needs it.  c1 is a whole half record and not
+// one double because k_hydro is register-bound: with h_j alone handed back its four instantiations
+// take 126 / 127 / 128 / 129 VGPRs instead of 124 / 126 / 127 / 128.  The pointers are the kernels'
+// __restrict__ arguments and carry no qualifier of their own here, and e is declared before batch:
+// the other way round no register count changes, but the schedule does, and k_hydro measured 1 %
+// slower)
+template <int TG, class Reach, class Lone, class Stage, class Pair>
+__device__ __forceinline__ void d_sph_sweep(const TreeSizes *ts, const SphNode *nodes, const double *gp, int nsub,
+                                            int sub, bool valid, double px, double py, double pz,
+                                            const BucketBox &BB, const BoxK b, Reach reach, Lone lone,
+                                            Stage stage, Pair pair)
+{
+  constexpr int CS = 64 / TG;
+  const int lane = threadIdx.x, cs = lane / TG;
+  const int nelem = __builtin_amdgcn_readfirstlane(ts->nelem);   // the gas tree's elements, as the device counted them
+  int e = 0, batch = 0;
+  while(e < nelem)
+    {
+      e = __builtin_amdgcn_readfirstlane(e);
+      v16i_s N;
+      d_load_sphnode(nodes, e, N);
+      const int skip = N[10], pidx = N[11], pstart = N[12], pcount = N[13];
+      if(pidx >= 0)
+        {
+          if((batch++ % nsub) == sub && gp[(size_t) 8 * pidx + 3] >= 0)
+            lone(pidx);
+          e = e + 1;
+        }
+      else
+        {
+          const double4 c = make_double4(d_f64s(N, 0), d_f64s(N, 1), d_f64s(N, 2), d_f64s(N, 3));
+          bool open = valid && d_node_overlaps(c, reach(d_f64s(N, 4)), px, py, pz, b);   // (N 4: Extnodes[].hmax)
+          if(__any(open))
+            {
+              if(pcount <= SPH_LEAF)
+                {
+                  for(int r0 = 0; r0 < pcount; r0 += SPH_STAGE)
+                    if((batch++ % nsub) == sub)
+                      {
+                        const bool staged = r0 + lane < pcount;
+                        __syncthreads();   // previous round fully consumed
+                        double4 c0 = make_double4(0, 0, 0, 0), c1 = make_double4(0, 0, 0, 0);
+                        if(staged)
+                          stage(pstart + r0 + lane, c0, c1);
+                        unsigned long long live = d_cull_batch(BB, staged, c0.x, c0.y, c0.z, c0.w, c1.w, b);
+                        __syncthreads();
+                        while(live)
+                          pair(d_next_candidates<CS>(live, cs));
+                      }
+                  e = skip;
+                }
+              else
+                e = e + 1;
+            }
+          else
+            e = skip;
+        }
+    }
+}
+
 template <int TG>
 __global__ void __launch_bounds__(64)
 k_density(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, const double *__restrict__ gp, int nt,
@@ -212,7 +288,6 @@ k_density(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, c
           unsigned long long *__restrict__ counter, unsigned long long *__restrict__ racc, int xcd,
           int nblocks)
 {
-  constexpr int CS = 64 / TG;
   __shared__ double4 sh[SPH_STAGE][2];
   const int lane = threadIdx.x;
   const int tl = lane & (TG - 1), cs = lane / TG;
@@ -221,7 +296,6 @@ k_density(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, c
     return;
   const int bucket = lb / nsub;
   const int sub = lb - bucket * nsub;   // this wavefront takes every nsub-th batch
-  int batch = 0;
   const int ti = bucket * TG + tl;
   const bool valid = ti < nt;
   const int s = valid ? tgt[ti] : 0;
@@ -242,62 +316,23 @@ k_density(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, c
   DensAcc A = {0, 0, 0, 0, 0, 0, 0, 0};
   const BucketBox BB = d_bucket_box(valid, px, py, pz, h, b);
 
-  const int nelem = __builtin_amdgcn_readfirstlane(ts->nelem);   // the gas tree's elements, as the device counted them
-  int e = 0;
-  while(e < nelem)
-    {
-      e = __builtin_amdgcn_readfirstlane(e);
-      v16i_s N;
-      d_load_sphnode(nodes, e, N);
-      const int skip = N[10], pidx = N[11], pstart = N[12], pcount = N[13];
-      if(pidx >= 0)
-        {
-          if((batch++ % nsub) == sub && gp[(size_t) 8 * pidx + 3] >= 0)
-            d_density_pair(gp + (size_t) 8 * pidx, valid && cs == 0, px, py, pz, vx, vy, vz, h2, hinv,
-                           hinv3, hinv4, h3, b, A);
-          e = e + 1;
-        }
-      else
-        {
-          const double4 c = make_double4(d_f64s(N, 0), d_f64s(N, 1), d_f64s(N, 2), d_f64s(N, 3));
-          bool open = valid && d_node_overlaps(c, h, px, py, pz, b);
-          if(__any(open))
-            {
-              if(pcount <= SPH_LEAF)
-                {
-                  for(int r0 = 0; r0 < pcount; r0 += SPH_STAGE)
-                    if((batch++ % nsub) == sub)
-                      {
-                        const bool staged = r0 + lane < pcount;
-                        __syncthreads();   // previous round fully consumed
-                        double4 c0 = make_double4(0, 0, 0, 0);
-                        if(staged)
-                          {
-                            const double4 *src = reinterpret_cast<const double4 *>(
-                              gp + (size_t) 8 * (pstart + r0 + lane));
-                            c0 = src[0];
-                            sh[lane][0] = c0;
-                            sh[lane][1] = src[1];
-                          }
-                        unsigned long long live = d_cull_batch(BB, staged, c0.x, c0.y, c0.z, c0.w, 0.0, b);
-                        __syncthreads();
-                        while(live)
-                          {
-                            const int j = d_next_candidates<CS>(live, cs);
-                            d_density_pair(reinterpret_cast<const double *>(&sh[j < 0 ? 0 : j][0]),
-                                           valid && j >= 0, px, py, pz, vx, vy, vz, h2, hinv, hinv3,
-                                           hinv4, h3, b, A);
-                          }
-                      }
-                  e = skip;
-                }
-              else
-                e = e + 1;
-            }
-          else
-            e = skip;
-        }
-    }
+  d_sph_sweep<TG>(
+    ts, nodes, gp, nsub, sub, valid, px, py, pz, BB, b,
+    [=](double) SPH_INLINE { return h; },
+    [=, &A](int p) SPH_INLINE {
+      d_density_pair(gp + (size_t) 8 * p, valid && cs == 0, px, py, pz, vx, vy, vz, h2, hinv, hinv3, hinv4,
+                     h3, b, A);
+    },
+    [=](int p, double4 &c0, double4 &c1) SPH_INLINE {
+      const double4 *src = reinterpret_cast<const double4 *>(gp + (size_t) 8 * p);
+      c0 = src[0];
+      sh[lane][0] = c0;
+      sh[lane][1] = src[1];
+    },
+    [=, &A](int j) SPH_INLINE {
+      d_density_pair(reinterpret_cast<const double *>(&sh[j < 0 ? 0 : j][0]), valid && j >= 0, px, py, pz,
+                     vx, vy, vz, h2, hinv, hinv3, hinv4, h3, b, A);
+    });
   const double rho = d_slot_sum<TG>(A.rho), wnum = d_slot_sum<TG>(A.wnum), dh = d_slot_sum<TG>(A.dhsml);
   const double dv = d_slot_sum<TG>(A.divv), rx = d_slot_sum<TG>(A.rx), ry = d_slot_sum<TG>(A.ry);
   const double rz = d_slot_sum<TG>(A.rz);
@@ -543,7 +578,26 @@ static int ghip_sph_tg()
   return v;
 }
 
-#define SPH_LAUNCH(KERNEL, TGV, GRID, ST, ...)                                   \
+// Launch shape of the bucket kernels for nt targets: tgw targets per bucket, nbk buckets, nsub
+// wavefronts per bucket -- enough of them to occupy the chip when the target list is short (late
+// h-iterations, one rank's share of a multi-GPU run), each taking every nsub-th batch -- and the
+// grid of nbk * nsub workgroups padded to the 8 XCDs (d_sph_block)
+struct SphShape
+{
+  int tgw, nbk, nsub, grid;
+};
+static SphShape ghip_sph_shape(int nt)
+{
+  SphShape s;
+  s.tgw = ghip_sph_tg();
+  s.nbk = (nt + s.tgw - 1) / s.tgw;
+  s.nsub = (ghip_sph_target_waves() + s.nbk - 1) / s.nbk;
+  s.nsub = s.nsub < 1 ? 1 : (s.nsub > GHIP_MAXSUB ? GHIP_MAXSUB : s.nsub);
+  s.grid = (s.nbk * s.nsub + 7) & ~7;
+  return s;
+}
+
+#define SPH_LAUNCH(KERNEL, TGV, GRID, ST, ...)                                  \
   do                                                                             \
     {                                                                            \
       if((TGV) == 64)                                                            \
@@ -643,18 +697,13 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
 
   while(ncur > 0)
     {
-      // wavefronts per bucket: enough of them to occupy the chip when the target list is short
-      // (late h-iterations, one rank's share of a multi-GPU run); each takes every nsub-th batch
-      const int tgw = ghip_sph_tg();
-      const int nbk = (ncur + tgw - 1) / tgw;
-      int nsub = (ghip_sph_target_waves() + nbk - 1) / nbk;
-      nsub = nsub < 1 ? 1 : (nsub > GHIP_MAXSUB ? GHIP_MAXSUB : nsub);
-      SPH_LAUNCH(k_density, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp), ncur,
-                 nsub, cur, hcur, b, P<double>(ctx->drho), P<double>(ctx->dnumngb),
+      const SphShape L = ghip_sph_shape(ncur);
+      SPH_LAUNCH(k_density, L.tgw, L.grid, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp), ncur,
+                 L.nsub, cur, hcur, b, P<double>(ctx->drho), P<double>(ctx->dnumngb),
                  P<double>(ctx->ddhsml), P<double>(ctx->ddivv), P<double>(ctx->drot), counter, racc,
-                 ghip_sph_xcd(), nbk * nsub);
+                 ghip_sph_xcd(), L.nbk * L.nsub);
       k_dens_finalize<<<cdiv(ncur, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
-        ncur, nsub, cur, P<int>(t.perm), n, ng, F, P<double>(ctx->drho), P<double>(ctx->dnumngb),
+        ncur, L.nsub, cur, P<int>(t.perm), n, ng, F, P<double>(ctx->drho), P<double>(ctx->dnumngb),
         P<double>(ctx->ddhsml), P<double>(ctx->ddivv), P<double>(ctx->drot), hcur,
         P<double>(ctx->dleft), P<double>(ctx->dright), P<double>(ctx->f[GHIP_F_ENTROPY]),
         P<double>(ctx->f[GHIP_F_DTENTROPY]), P<int>(ctx->f[GHIP_F_TIMEBIN]),
@@ -726,39 +775,19 @@ extern "C" int ghip_density_evaluate(ghip_ctx *ctx, const ghip_dens_params *p, i
   TreeDev &t = ctx->st;
   GCHK(dens_alloc(ctx));
   double *hcur = P<double>(ctx->dhcur);
-  const int nsub = 1;
+  const int *tgt = P<int>(t.iperm) + target;   // the one-entry target list: the particle's gas-tree position
   int s = 0;
-  HIPCHK(hipMemcpyAsync(&s, P<int>(t.iperm) + target, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  int *cur = P<int>(ctx->dtgt_a);
-  HIPCHK(hipMemcpyAsync(cur, &s, 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(&s, tgt, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));   // (s places h)
   HIPCHK(hipMemcpyAsync(hcur + s, &h, 8, hipMemcpyHostToDevice, st));
   BoxK b = make_box(p->BoxSize, p->periodic);
-  unsigned long long *counter = ghip_cslot(ctx, GHIP_CK_DENS1);
-  k_density<8><<<nsub, 64, 0, st>>>(P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp), 1, nsub, cur, hcur, b,
-                              P<double>(ctx->drho), P<double>(ctx->dnumngb),
-                              P<double>(ctx->ddhsml), P<double>(ctx->ddivv), P<double>(ctx->drot),
-                              counter, ghip_rslot(ctx, GHIP_CK_DENS1), 0, nsub);
+  // one wavefront, one target, one plane: the seven sums land side by side (rot: [c], planes of 1)
+  double *o = P<double>(ctx->drot);
+  k_density<8><<<1, 64, 0, st>>>(P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp), 1, 1, tgt, hcur, b, o,
+                                 o + 1, o + 2, o + 3, o + 4, ghip_cslot(ctx, GHIP_CK_DENS1),
+                                 ghip_rslot(ctx, GHIP_CK_DENS1), 0, 1);
   HIPCHK(hipGetLastError());
-  // nt == 1: partial q of component c sits at [q] (rot: [c*nsub + q]); sum in fixed order
-  double part[7][GHIP_MAXSUB * 8];
-  if(nsub > GHIP_MAXSUB * 8)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_density_evaluate: too many sub-walks");
-  HIPCHK(hipMemcpyAsync(part[0], ctx->drho.p, (size_t) nsub * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(part[1], ctx->dnumngb.p, (size_t) nsub * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(part[2], ctx->ddhsml.p, (size_t) nsub * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(part[3], ctx->ddivv.p, (size_t) nsub * 8, hipMemcpyDeviceToHost, st));
-  for(int c = 0; c < 3; c++)
-    HIPCHK(hipMemcpyAsync(part[4 + c], P<double>(ctx->drot) + (size_t) c * nsub,
-                          (size_t) nsub * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  for(int c = 0; c < 7; c++)
-    {
-      double acc = 0;
-      for(int q = 0; q < nsub; q++)
-        acc += part[c][q];
-      out7[c] = acc;
-    }
+  HIPCHK(hipMemcpyAsync(out7, o, 7 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
   return GHIP_OK;
 }
@@ -1010,7 +1039,7 @@ __device__ __forceinline__ void d_hydro_pair(const double *r8, const double *q8,
 }
 
 // hydro_evaluate (hydra.c:822-1995, mode 0) for a bucket of TG curve-consecutive targets x 64/TG
-// candidate slots, same structure as k_density: scalar node records, candidate records (gp + gq,
+// candidate slots, on the same d_sph_sweep as k_density: scalar node records, candidate records (gp + gq,
 // 128 B) staged through LDS 64 at a time, exact per-lane acceptance r2 < h_i^2 || r2 < h_j^2.  Node
 // pruning uses max(hmax_node, h_i) like ngb_treefind_pairs (ngb.c:136).  Outputs: [5][nt] planes.
 // V... is empty for the default kernel (the constant viscosity: same signature, same code as before
@@ -1024,7 +1053,6 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
         double *__restrict__ part, unsigned long long *__restrict__ counter,
         unsigned long long *__restrict__ racc, int xcd, int nblocks, V... vs)
 {
-  constexpr int CS = 64 / TG;
   constexpr bool VISC = sizeof...(V) > 0;
   __shared__ double4 sh[SPH_STAGE][4];
   const int lane = threadIdx.x;
@@ -1034,7 +1062,6 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
     return;
   const int bucket = lb / nsub;
   const int sub = lb - bucket * nsub;
-  int batch = 0;
   const int ti = bucket * TG + tl;
   const bool valid = ti < nt;
   const int s = valid ? tgt[ti] : 0;
@@ -1074,84 +1101,39 @@ k_hydro(const TreeSizes *__restrict__ ts, const SphNode *__restrict__ nodes, con
   HydAcc A = {0, 0, 0, 0, 0, 0};
   const BucketBox BB = d_bucket_box(valid, T.px, T.py, T.pz, T.h_i, b);
 
-  const int nelem = __builtin_amdgcn_readfirstlane(ts->nelem);
-  int e = 0;
-  while(e < nelem)
-    {
-      e = __builtin_amdgcn_readfirstlane(e);
-      v16i_s N;
-      d_load_sphnode(nodes, e, N);
-      const int skip = N[10], pidx = N[11], pstart = N[12], pcount = N[13];
-      if(pidx >= 0)
-        {
-          if((batch++ % nsub) == sub && gp[(size_t) 8 * pidx + 3] >= 0)
-            {
-              const double *qs = gq + (size_t) 8 * pidx;
-              const HydCand C = d_hydro_candidate(qs[0], qs[1], gp[(size_t) 8 * pidx + 7], qs[3], qs[4],
-                                                  K.fac_mu);
-              const double q8[8] = {C.p_over_rho2, qs[1], qs[2], C.f2, 0.0, qs[5], C.soundspeed, C.hinv};
-              d_hydro_pair(gp + (size_t) 8 * pidx, q8, valid && cs == 0, T, K, b, A, alpha_i, qs + 6, vs...);
-            }
-          e = e + 1;
-        }
-      else
-        {
-          const double4 c = make_double4(d_f64s(N, 0), d_f64s(N, 1), d_f64s(N, 2), d_f64s(N, 3));
-          const double hm = d_f64s(N, 4);            // Extnodes[].hmax
-          double dist = (hm > T.h_i) ? hm : T.h_i;   // ngb.c:136
-          bool open = valid && d_node_overlaps(c, dist, T.px, T.py, T.pz, b);
-          if(__any(open))
-            {
-              if(pcount <= SPH_LEAF)
-                {
-                  for(int r0 = 0; r0 < pcount; r0 += SPH_STAGE)
-                    if((batch++ % nsub) == sub)
-                      {
-                        const bool staged = r0 + lane < pcount;
-                        __syncthreads();
-                        double4 c0 = make_double4(0, 0, 0, 0), c1 = make_double4(0, 0, 0, 0);
-                        if(staged)
-                          {
-                            const double4 *s0 =
-                              reinterpret_cast<const double4 *>(gp + (size_t) 8 * (pstart + r0 + lane));
-                            const double4 *s1 =
-                              reinterpret_cast<const double4 *>(gq + (size_t) 8 * (pstart + r0 + lane));
-                            c0 = s0[0];
-                            c1 = s0[1];
-                            double4 q0 = s1[0], q1 = s1[1];   // (P, rho, f, divv) (curl, timestep, -, -)
-                            const HydCand C = d_hydro_candidate(q0.x, q0.y, c1.w, q0.w, q1.x, K.fac_mu);
-                            q0.x = C.p_over_rho2;
-                            q0.w = C.f2;
-                            if constexpr(VISC)
-                              q1.x = q1.z;   // alpha, before its slot is taken
-                            q1.z = C.soundspeed;
-                            q1.w = C.hinv;
-                            sh[lane][0] = c0;
-                            sh[lane][1] = c1;
-                            sh[lane][2] = q0;
-                            sh[lane][3] = q1;
-                          }
-                        // (pairs: the candidate's own smoothing length c1.w counts too, hydra.c:1266)
-                        unsigned long long live = d_cull_batch(BB, staged, c0.x, c0.y, c0.z, c0.w, c1.w, b);
-                        __syncthreads();
-                        while(live)
-                          {
-                            const int j = d_next_candidates<CS>(live, cs);
-                            const int jj = j < 0 ? 0 : j;
-                            d_hydro_pair(reinterpret_cast<const double *>(&sh[jj][0]),
-                                         reinterpret_cast<const double *>(&sh[jj][2]), valid && j >= 0, T,
-                                         K, b, A, alpha_i, reinterpret_cast<const double *>(&sh[jj][3]), vs...);
-                          }
-                      }
-                  e = skip;
-                }
-              else
-                e = e + 1;
-            }
-          else
-            e = skip;
-        }
-    }
+  d_sph_sweep<TG>(
+    ts, nodes, gp, nsub, sub, valid, T.px, T.py, T.pz, BB, b,
+    [=](double hmax) SPH_INLINE { return (hmax > T.h_i) ? hmax : T.h_i; },   // ngb.c:136
+    [=, &A](int p) SPH_INLINE {
+      const double *qs = gq + (size_t) 8 * p;
+      const HydCand C = d_hydro_candidate(qs[0], qs[1], gp[(size_t) 8 * p + 7], qs[3], qs[4], K.fac_mu);
+      const double q8[8] = {C.p_over_rho2, qs[1], qs[2], C.f2, 0.0, qs[5], C.soundspeed, C.hinv};
+      d_hydro_pair(gp + (size_t) 8 * p, q8, valid && cs == 0, T, K, b, A, alpha_i, qs + 6, vs...);
+    },
+    [=](int p, double4 &c0, double4 &c1) SPH_INLINE {
+      const double4 *s0 = reinterpret_cast<const double4 *>(gp + (size_t) 8 * p);
+      const double4 *s1 = reinterpret_cast<const double4 *>(gq + (size_t) 8 * p);
+      c0 = s0[0];
+      c1 = s0[1];
+      double4 q0 = s1[0], q1 = s1[1];   // (P, rho, f, divv) (curl, timestep, -, -)
+      const HydCand C = d_hydro_candidate(q0.x, q0.y, c1.w, q0.w, q1.x, K.fac_mu);
+      q0.x = C.p_over_rho2;
+      q0.w = C.f2;
+      if constexpr(VISC)
+        q1.x = q1.z;   // alpha, before its slot is taken
+      q1.z = C.soundspeed;
+      q1.w = C.hinv;
+      sh[lane][0] = c0;
+      sh[lane][1] = c1;
+      sh[lane][2] = q0;
+      sh[lane][3] = q1;
+      // (pairs: the candidate's own smoothing length counts too, hydra.c:1266)
+    },
+    [=, &A](int j) SPH_INLINE {
+      const int jj = j < 0 ? 0 : j;
+      d_hydro_pair(reinterpret_cast<const double *>(&sh[jj][0]), reinterpret_cast<const double *>(&sh[jj][2]),
+                   valid && j >= 0, T, K, b, A, alpha_i, reinterpret_cast<const double *>(&sh[jj][3]), vs...);
+    });
   const double ax = d_slot_sum<TG>(A.ax), ay = d_slot_sum<TG>(A.ay), az = d_slot_sum<TG>(A.az);
   const double de = d_slot_sum<TG>(A.dtent), ms = d_slot_max<TG>(A.maxsig);
   if(valid && cs == 0)
@@ -1299,41 +1281,33 @@ int ghip_hydro_impl(ghip_ctx *ctx, const ghip_hydro_params *p)
         t.n, ng, P<int>(t.perm), P<double>(ctx->visc_alpha), P<double>(ctx->gq));
       HIPCHK(hipGetLastError());
     }
-  const int tgw = ghip_sph_tg();
-  const int nbk = (nt + tgw - 1) / tgw;
-  int nsub = (ghip_sph_target_waves() + nbk - 1) / nbk;
-  nsub = nsub < 1 ? 1 : (nsub > GHIP_MAXSUB ? GHIP_MAXSUB : nsub);
-  GCHK(ghip_ensure(ctx, ctx->hpart, (size_t) 5 * nsub * nt * 8));
+  const SphShape L = ghip_sph_shape(nt);
+  const ghip_visc_params &v = ctx->visc;
+  const int *tgt = P<int>(ctx->tg_gas) + lo;
+  GCHK(ghip_ensure(ctx, ctx->hpart, (size_t) 5 * L.nsub * nt * 8));
+  // (x: nothing for the default kernels, the setting's record for the instantiations that take one)
+  auto pairs = [&](auto... x) {
+    SPH_LAUNCH(k_hydro, L.tgw, L.grid, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp),
+               P<double>(ctx->gq), nt, L.nsub, tgt, b, K, P<double>(ctx->hpart), counter,
+               ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), L.nbk * L.nsub, x...);
+  };
+  auto combine = [&](auto... x) {
+    k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
+      nt, L.nsub, tgt, P<int>(t.perm), P<double>(ctx->gq), P<double>(ctx->hpart), K, ng,
+      P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
+      P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]), x...);
+  };
   if(visc)
-    {
-      const ghip_visc_params &v = ctx->visc;
-      const HydV X = {v.time_dependent, v.conventional, v.no_limiter, v.no_shear_limiter};
-      SPH_LAUNCH(k_hydro, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq),
-                 P<double>(ctx->gp), P<double>(ctx->gq), nt, nsub, P<int>(ctx->tg_gas) + lo, b, K,
-                 P<double>(ctx->hpart), counter, ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), nbk * nsub, X);
-    }
+    pairs(HydV{v.time_dependent, v.conventional, v.no_limiter, v.no_shear_limiter});
   else
-    SPH_LAUNCH(k_hydro, tgw, (nbk * nsub + 7) & ~7, st, P<TreeSizes>(t.dsz), P<SphNode>(t.mq), P<double>(ctx->gp),
-               P<double>(ctx->gq), nt, nsub, P<int>(ctx->tg_gas) + lo, b, K, P<double>(ctx->hpart),
-               counter, ghip_rslot(ctx, GHIP_CK_HYDRO), ghip_sph_xcd(), nbk * nsub);
+    pairs();
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->evp[11], st));
-  if(visc && ctx->visc.time_dependent)
-    {
-      const ghip_visc_params &v = ctx->visc;
-      const HydD X = {P<double>(ctx->gp), P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha),
-                      v.AlphaMin,         v.ViscSource,               v.DecayTime,
-                      v.dtalpha_comoving_div};
-      k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
-        nt, nsub, P<int>(ctx->tg_gas) + lo, P<int>(t.perm), P<double>(ctx->gq), P<double>(ctx->hpart), K, ng,
-        P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
-        P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]), X);
-    }
+  if(visc && v.time_dependent)
+    combine(HydD{P<double>(ctx->gp), P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha), v.AlphaMin,
+                 v.ViscSource, v.DecayTime, v.dtalpha_comoving_div});
   else
-    k_hydro_combine<<<cdiv(nt, ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(
-      nt, nsub, P<int>(ctx->tg_gas) + lo, P<int>(t.perm), P<double>(ctx->gq),
-      P<double>(ctx->hpart), K, ng, P<double>(ctx->f[GHIP_F_HYDROACCEL]),
-      P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]));
+    combine();
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
