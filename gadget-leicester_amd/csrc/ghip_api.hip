@@ -1,4 +1,6 @@
-// ghip_api.hip -- C-ABI entry points: lifetime, particle data movement, introspection.
+// ghip_api.hip -- C-ABI entry points: context lifetime, the field table with ghip_set_field /
+// ghip_get_field, the active list, tree build and dumps, run statistics.  (Whole P[] / SphP[] records
+// move through ghip_records.hip.)
 // See include/ghip.h for what each entry point replaces in the reference.
 #include <cstdarg>
 
@@ -390,7 +392,7 @@ static const FieldInfo kField[GHIP_F_COUNT] = {
   /* PRESSURE */ {1, 1, 0},   /* HYDROACCEL */ {1, 3, 0}, /* MAXSIGNALVEL */ {1, 1, 0},
   /* TI_CURRENT */ {0, 1, 1}, /* GRAVPM */ {0, 3, 0}, /* ID */ {0, 1, 1}};
 
-// the same table for the migration of ghip_dd.hip
+// the same table for the migration of ghip_dd.hip and the record members of ghip_records.hip
 void ghip_field_info(int f, int *gas, int *ncomp, int *isint)
 {
   *gas = kField[f].gas;
@@ -553,523 +555,6 @@ extern "C" int ghip_get_field(ghip_ctx *ctx, int field, void *host)
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(host, ctx->stage.p, bytes, hipMemcpyDeviceToHost, st));
     }
-  HIPCHK(ghip_stream_sync(ctx, st));
-  return ghip_check_device_errors(ctx);
-}
-
-// ---------------------------------------------------------------------------------------------
-// whole-record (AoS) path: the drop-in boundary under accel.c
-// ---------------------------------------------------------------------------------------------
-__global__ void k_unpack_f64(size_t n, const char *__restrict__ rec, int stride, int off, int ncomp,
-                             double *__restrict__ dst)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  const double *src = reinterpret_cast<const double *>(rec + i * (size_t) stride + off);
-  for(int c = 0; c < ncomp; c++)
-    dst[(size_t) c * n + i] = src[c];
-}
-
-__global__ void k_unpack_i16(size_t n, const char *__restrict__ rec, int stride, int off,
-                             int *__restrict__ dst)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[i] = (int) *reinterpret_cast<const short *>(rec + i * (size_t) stride + off);
-}
-
-__global__ void k_unpack_i32(size_t n, const char *__restrict__ rec, int stride, int off,
-                             int *__restrict__ dst)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i < n)
-    dst[i] = *reinterpret_cast<const int *>(rec + i * (size_t) stride + off);
-}
-
-__global__ void k_pack_f64(size_t n, char *__restrict__ rec, int stride, int off, int ncomp,
-                           const double *__restrict__ src)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i >= n)
-    return;
-  double *dst = reinterpret_cast<double *>(rec + i * (size_t) stride + off);
-  for(int c = 0; c < ncomp; c++)
-    dst[c] = src[(size_t) c * n + i];
-}
-
-__global__ void k_pack_cost_f32(size_t n, char *__restrict__ rec, int stride, int off,
-                                const int *__restrict__ src)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i < n)
-    *reinterpret_cast<float *>(rec + i * (size_t) stride + off) = (float) src[i];  // P[].GravCost
-}
-
-// One pass over a record block for all of its fields (instead of one launch per field: every launch
-// re-reads every line of the image).  kind 0: double[ncomp] <-> SoA component arrays of stride n;
-// 1: short <-> int; 2: int <-> int; 3 (pack only): int -> float (P[].GravCost).
-struct RecField
-{
-  void *soa;
-  int off;
-  short ncomp, kind;
-};
-struct RecMap
-{
-  size_t n;
-  int stride, nf;
-  RecField f[16];
-};
-
-static void rec_add(RecMap &m, int off, int ncomp, int kind, void *soa)
-{
-  if(off < 0 || m.nf >= 16)
-    return;
-  m.f[m.nf].soa = soa;
-  m.f[m.nf].off = off;
-  m.f[m.nf].ncomp = (short) ncomp;
-  m.f[m.nf].kind = (short) kind;
-  m.nf++;
-}
-
-// type_off >= 0: the records [0, ngas) are supposed to be gas (allvars.h:1384); *mixed is set when
-// one of them has another Type
-template <bool PACK>
-__global__ void k_records(RecMap m, char *__restrict__ rec, int type_off, int ngas, int *mixed)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i >= m.n)
-    return;
-  char *r = rec + i * (size_t) m.stride;
-  for(int k = 0; k < m.nf; k++)
-    {
-      const RecField f = m.f[k];
-      if(f.kind == 0)
-        {
-          double *a = reinterpret_cast<double *>(r + f.off);
-          double *s = reinterpret_cast<double *>(f.soa);
-          for(int c = 0; c < f.ncomp; c++)
-            {
-              if(PACK)
-                a[c] = s[(size_t) c * m.n + i];
-              else
-                s[(size_t) c * m.n + i] = a[c];
-            }
-        }
-      else if(f.kind == 1)
-        {
-          if(PACK)
-            *reinterpret_cast<short *>(r + f.off) = (short) reinterpret_cast<int *>(f.soa)[i];
-          else
-            reinterpret_cast<int *>(f.soa)[i] = (int) *reinterpret_cast<const short *>(r + f.off);
-        }
-      else if(f.kind == 2)
-        {
-          if(PACK)
-            *reinterpret_cast<int *>(r + f.off) = reinterpret_cast<int *>(f.soa)[i];
-          else
-            reinterpret_cast<int *>(f.soa)[i] = *reinterpret_cast<const int *>(r + f.off);
-        }
-      else if(PACK)
-        *reinterpret_cast<float *>(r + f.off) = (float) reinterpret_cast<int *>(f.soa)[i];
-    }
-  if(!PACK && type_off >= 0 && i < (size_t) ngas && *reinterpret_cast<const short *>(r + type_off) != 0)
-    *mixed = 1;
-}
-
-template <bool PACK>
-static int run_records(ghip_ctx *ctx, const RecMap &m, void *img, int type_off = -1,
-                       hipStream_t st = nullptr)
-{
-  if(m.n == 0 || m.nf == 0)
-    return GHIP_OK;
-  const int wg = ghip_wg(ctx);
-  k_records<PACK><<<cdiv((long long) m.n, wg), wg, 0, st ? st : ctx->stream>>>(
-    m, (char *) img, type_off, ctx->ngas, ghip_gas_mixed_word(ctx));
-  HIPCHK(hipGetLastError());
-  return GHIP_OK;
-}
-
-#define UNPACK64(cnt, img, stride, off, ncomp, fld)                                           \
-  do                                                                                          \
-    {                                                                                         \
-      if((off) >= 0 && (cnt) > 0)                                                             \
-        k_unpack_f64<<<cdiv((long long) (cnt), ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(         \
-          (size_t) (cnt), (const char *) (img), (stride), (off), (ncomp), P<double>(ctx->f[fld])); \
-    }                                                                                         \
-  while(0)
-
-#define PACK64(cnt, img, stride, off, ncomp, fld)                                             \
-  do                                                                                          \
-    {                                                                                         \
-      if((off) >= 0 && (cnt) > 0)                                                             \
-        k_pack_f64<<<cdiv((long long) (cnt), ghip_wg(ctx)), ghip_wg(ctx), 0, st>>>(           \
-          (size_t) (cnt), (char *) (img), (stride), (off), (ncomp), P<double>(ctx->f[fld]));  \
-    }                                                                                         \
-  while(0)
-
-// the P[] block: copy + unpack of the per-particle fields
-static int upload_p_block(ghip_ctx *ctx, const void *Pp, const ghip_layout *lay)
-{
-  hipStream_t st = ctx->stream;
-  const size_t n = (size_t) ctx->n;
-  if(n == 0)
-    return GHIP_OK;
-  GCHK(ghip_ensure(ctx, ctx->aosP, n * lay->p_stride));
-  HIPCHK(hipMemcpyAsync(ctx->aosP.p, Pp, n * lay->p_stride, hipMemcpyHostToDevice, st));
-  RecMap m;
-  m.n = n;
-  m.stride = lay->p_stride;
-  m.nf = 0;
-  rec_add(m, lay->p_pos, 3, 0, ctx->f[GHIP_F_POS].p);
-  rec_add(m, lay->p_vel, 3, 0, ctx->f[GHIP_F_VEL].p);
-  rec_add(m, lay->p_mass, 1, 0, ctx->f[GHIP_F_MASS].p);
-  rec_add(m, lay->p_oldacc, 1, 0, ctx->f[GHIP_F_OLDACC].p);
-  rec_add(m, lay->p_type, 1, 1, ctx->f[GHIP_F_TYPE].p);
-  rec_add(m, lay->p_timebin, 1, 1, ctx->f[GHIP_F_TIMEBIN].p);
-  rec_add(m, lay->p_ti_begstep, 1, 2, ctx->f[GHIP_F_TI_BEGSTEP].p);
-  rec_add(m, lay->p_ti_current, 1, 2, ctx->f[GHIP_F_TI_CURRENT].p);
-  rec_add(m, lay->p_gravaccel, 3, 0, ctx->f[GHIP_F_GRAVACCEL].p);
-  rec_add(m, lay->p_gravpm, 3, 0, ctx->f[GHIP_F_GRAVPM].p);
-  rec_add(m, lay->p_hsml, 1, 0, ctx->f[GHIP_F_HSML].p);
-  *ghip_gas_mixed_word(ctx) = 0;
-  GCHK(run_records<false>(ctx, m, ctx->aosP.p, lay->p_type));
-  return GHIP_OK;
-}
-
-// the SphP[] block: copy + unpack of the per-gas-particle fields.  The unpack kernels may run
-// underneath a gravity pair in flight: one-wavefront workgroups then (ghip_wg)
-static int upload_s_block(ghip_ctx *ctx, const void *Sp, const ghip_layout *lay)
-{
-  hipStream_t st = ctx->stream;
-  const size_t ng = (size_t) ctx->ngas;
-  if(ng == 0)
-    return GHIP_OK;
-  GCHK(ghip_ensure(ctx, ctx->aosS, ng * lay->s_stride));
-  HIPCHK(hipMemcpyAsync(ctx->aosS.p, Sp, ng * lay->s_stride, hipMemcpyHostToDevice, st));
-  RecMap m;
-  m.n = ng;
-  m.stride = lay->s_stride;
-  m.nf = 0;
-  rec_add(m, lay->s_hsml, 1, 0, ctx->f[GHIP_F_HSML].p);   // first ngas entries
-  rec_add(m, lay->s_velpred, 3, 0, ctx->f[GHIP_F_VELPRED].p);
-  rec_add(m, lay->s_entropy, 1, 0, ctx->f[GHIP_F_ENTROPY].p);
-  rec_add(m, lay->s_dtentropy, 1, 0, ctx->f[GHIP_F_DTENTROPY].p);
-  rec_add(m, lay->s_density, 1, 0, ctx->f[GHIP_F_DENSITY].p);
-  rec_add(m, lay->s_dhsmlfac, 1, 0, ctx->f[GHIP_F_DHSMLFAC].p);
-  rec_add(m, lay->s_divvel, 1, 0, ctx->f[GHIP_F_DIVVEL].p);
-  rec_add(m, lay->s_curlvel, 1, 0, ctx->f[GHIP_F_CURLVEL].p);
-  rec_add(m, lay->s_pressure, 1, 0, ctx->f[GHIP_F_PRESSURE].p);
-  rec_add(m, lay->s_hydroaccel, 3, 0, ctx->f[GHIP_F_HYDROACCEL].p);
-  rec_add(m, lay->s_maxsignalvel, 1, 0, ctx->f[GHIP_F_MAXSIGNALVEL].p);
-  GCHK(run_records<false>(ctx, m, ctx->aosS.p));
-  return GHIP_OK;
-}
-
-static int check_upload_args(ghip_ctx *ctx, const void *Pp, const void *Sp, const ghip_layout *lay,
-                             int numpart, int ngas, bool need_s)
-{
-  if(!ctx || !lay || numpart < 0 || ngas < 0 || ngas > numpart || (numpart > 0 && !Pp) ||
-     (need_s && ngas > 0 && !Sp))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_upload_aos: bad arguments");
-  if(lay->p_stride <= 0 || (ngas > 0 && lay->s_stride <= 0))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_upload_aos: bad strides");
-  if((lay->p_hsml >= 0) == (lay->s_hsml >= 0) && ngas > 0)
-    return ghip_fail(ctx, GHIP_EINVAL,
-                     "ghip_upload_aos: exactly one of p_hsml / s_hsml must be set (PPP macro)");
-  return GHIP_OK;
-}
-
-extern "C" int ghip_upload_aos(ghip_ctx *ctx, const void *Pp, const void *Sp, const ghip_layout *lay,
-                               int numpart, int ngas)
-{
-  if(ctx)
-    GHIP_JOIN(ctx);
-  if(ctx)
-    ctx->pot_n = -1;
-  GCHK(check_upload_args(ctx, Pp, Sp, lay, numpart, ngas, true));
-  GCHK(ghip_set_counts(ctx, numpart, ngas));
-  if(numpart == 0)
-    return GHIP_OK;
-  GCHK(upload_p_block(ctx, Pp, lay));
-  GCHK(upload_s_block(ctx, Sp, lay));
-  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  ctx->gt.built = false;
-  ctx->st.built = false;
-  ctx->dd.geom_kept = false;
-  ctx->gas_wait_upload = false;
-  ctx->gas_mixed = lay->p_type >= 0 && *reinterpret_cast<volatile int *>(ghip_gas_mixed_word(ctx)) != 0;
-  ctx->gas_list_dirty = true;
-  return GHIP_OK;
-}
-
-// The same in two calls, for a host that starts gravity before the gas data are across: the P[]
-// block (everything the gravity tree and its walks read -- unless the smoothing lengths, which
-// ADAPTIVE_GRAVSOFT_FORGAS makes softenings, live in SphP[]) ...
-extern "C" int ghip_upload_aos_particles(ghip_ctx *ctx, const void *Pp, const ghip_layout *lay,
-                                         int numpart, int ngas)
-{
-  if(ctx)
-    GHIP_JOIN(ctx);
-  if(ctx)
-    ctx->pot_n = -1;
-  GCHK(check_upload_args(ctx, Pp, nullptr, lay, numpart, ngas, false));
-  if(ctx->adaptive_gravsoft && lay->p_hsml < 0 && ngas > 0)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_upload_aos_particles: with adaptive gravitational softening "
-                     "the smoothing lengths of SphP[] are needed first: use ghip_upload_aos");
-  GCHK(ghip_set_counts(ctx, numpart, ngas));
-  if(numpart == 0)
-    return GHIP_OK;
-  GCHK(upload_p_block(ctx, Pp, lay));
-  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  ctx->gt.built = false;
-  ctx->st.built = false;
-  ctx->dd.geom_kept = false;
-  ctx->gas_wait_upload = ngas > 0;   // (whatever joins in between must leave the gas tree deferred)
-  ctx->gas_mixed = lay->p_type >= 0 && *reinterpret_cast<volatile int *>(ghip_gas_mixed_word(ctx)) != 0;
-  ctx->gas_list_dirty = true;
-  return GHIP_OK;
-}
-
-// ... and the SphP[] block, which may follow while a gravity pair is in flight (it is not waited
-// for): before the first SPH call of the step.
-extern "C" int ghip_upload_aos_gas(ghip_ctx *ctx, const void *Sp, const ghip_layout *lay)
-{
-  if(!ctx || !lay || (ctx->ngas > 0 && (!Sp || lay->s_stride <= 0)))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_upload_aos_gas: bad arguments");
-  GCHK(upload_s_block(ctx, Sp, lay));
-  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  ctx->gas_wait_upload = false;
-  return GHIP_OK;
-}
-
-static int download_aos_impl(ghip_ctx *ctx, void *Pp, void *Sp, const ghip_layout *lay,
-                             int want_gravity, int want_density, int want_hydro, bool sync)
-{
-  // the SPH results do not depend on a gravity pair still in flight underneath them
-  if(ctx && want_gravity)
-    GHIP_JOIN(ctx);
-  if(!ctx || !lay)
-    return GHIP_EINVAL;
-  size_t n = (size_t) ctx->n, ng = (size_t) ctx->ngas;
-  if(n == 0)
-    return GHIP_OK;
-  if(!Pp || (ng > 0 && !Sp))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_download_aos: null record pointers");
-  if(ctx->aosP.cap < n * lay->p_stride || (ng > 0 && ctx->aosS.cap < ng * lay->s_stride))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_download_aos: no device image (call ghip_upload_aos)");
-  hipStream_t st = ctx->stream;
-  void *ip = ctx->aosP.p, *is = ctx->aosS.p;
-  bool touchP = false, touchS = false;
-  RecMap mp, mg, ms;   // P fields of all particles, P fields of the gas block, SphP fields
-  mp.n = n, mp.stride = lay->p_stride, mp.nf = 0;
-  mg.n = ng, mg.stride = lay->p_stride, mg.nf = 0;
-  ms.n = ng, ms.stride = lay->s_stride, ms.nf = 0;
-  if(want_gravity)
-    {
-      rec_add(mp, lay->p_gravaccel, 3, 0, ctx->f[GHIP_F_GRAVACCEL].p);
-      rec_add(mp, lay->p_oldacc, 1, 0, ctx->f[GHIP_F_OLDACC].p);
-      rec_add(mp, lay->p_gravpm, 3, 0, ctx->f[GHIP_F_GRAVPM].p);
-      rec_add(mp, lay->p_gravcost, 1, 3, ctx->f[GHIP_F_GRAVCOST].p);
-      touchP = true;
-    }
-  if(want_density && ng > 0)
-    {
-      if(lay->p_hsml >= 0)
-        {
-          rec_add(mg, lay->p_hsml, 1, 0, ctx->f[GHIP_F_HSML].p);
-          rec_add(mg, lay->p_numngb, 1, 0, ctx->f[GHIP_F_NUMNGB].p);
-          touchP = true;
-        }
-      else
-        {
-          rec_add(ms, lay->s_hsml, 1, 0, ctx->f[GHIP_F_HSML].p);
-          rec_add(ms, lay->s_numngb, 1, 0, ctx->f[GHIP_F_NUMNGB].p);
-        }
-      rec_add(ms, lay->s_density, 1, 0, ctx->f[GHIP_F_DENSITY].p);
-      rec_add(ms, lay->s_dhsmlfac, 1, 0, ctx->f[GHIP_F_DHSMLFAC].p);
-      rec_add(ms, lay->s_divvel, 1, 0, ctx->f[GHIP_F_DIVVEL].p);
-      rec_add(ms, lay->s_curlvel, 1, 0, ctx->f[GHIP_F_CURLVEL].p);
-      rec_add(ms, lay->s_pressure, 1, 0, ctx->f[GHIP_F_PRESSURE].p);
-      touchS = true;
-    }
-  if(want_hydro && ng > 0)
-    {
-      rec_add(ms, lay->s_hydroaccel, 3, 0, ctx->f[GHIP_F_HYDROACCEL].p);
-      rec_add(ms, lay->s_dtentropy, 1, 0, ctx->f[GHIP_F_DTENTROPY].p);
-      rec_add(ms, lay->s_maxsignalvel, 1, 0, ctx->f[GHIP_F_MAXSIGNALVEL].p);
-      touchS = true;
-    }
-  GCHK(run_records<true>(ctx, mp, ip));
-  GCHK(run_records<true>(ctx, mg, ip));
-  GCHK(run_records<true>(ctx, ms, is));
-  HIPCHK(hipGetLastError());
-  if(touchP)
-    HIPCHK(hipMemcpyAsync(Pp, ip, n * lay->p_stride, hipMemcpyDeviceToHost, st));
-  if(touchS)
-    HIPCHK(hipMemcpyAsync(Sp, is, ng * lay->s_stride, hipMemcpyDeviceToHost, st));
-  if(!sync)
-    return GHIP_OK;
-  HIPCHK(ghip_stream_sync(ctx, st));
-  return ghip_check_device_errors(ctx);
-}
-
-extern "C" int ghip_download_aos(ghip_ctx *ctx, void *Pp, void *Sp, const ghip_layout *lay,
-                                 int want_gravity, int want_density, int want_hydro)
-{
-  return download_aos_impl(ctx, Pp, Sp, lay, want_gravity, want_density, want_hydro, true);
-}
-
-extern "C" int ghip_download_aos_async(ghip_ctx *ctx, void *Pp, void *Sp, const ghip_layout *lay,
-                                       int want_gravity, int want_density, int want_hydro)
-{
-  return download_aos_impl(ctx, Pp, Sp, lay, want_gravity, want_density, want_hydro, false);
-}
-
-// gravity_tree()'s post-pass and the gravity fields of P[] for a host that called the SPH drivers
-// underneath a pair in flight: ordered after the pair on the pair's own stream, not behind the SPH
-// kernels queued on the main stream -- the P[] block crosses the link while hydro's tail still runs.
-extern "C" int ghip_gravity_to_records(ghip_ctx *ctx, double G, int pmgrid, double comoving_fac,
-                                       void *Pp, const ghip_layout *lay)
-{
-  if(!ctx || !lay)
-    return GHIP_EINVAL;
-  GCHK(ghip_tree_verify(ctx));
-  const size_t n = (size_t) ctx->n;
-  if(n == 0)
-    return GHIP_OK;
-  if(!Pp)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_gravity_to_records: null record pointer");
-  if(ctx->aosP.cap < n * lay->p_stride)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_gravity_to_records: no device image (call ghip_upload_aos)");
-  // (records with Hsml in P[] carry SPH results in the same block: a download queued on the main
-  // stream could then copy the block with stale gravity fields over this one -- everything in order on
-  // the main stream for such layouts)
-  const bool side = ctx->grav_pending && lay->p_hsml < 0;
-  hipStream_t st = ctx->stream;
-  if(side)
-    st = ctx->stream2;   // (the pair's last kernel, the Ewald sums' combine, is on this stream)
-  else
-    GHIP_JOIN(ctx);
-  GCHK(ghip_gravity_finish_on(ctx, G, pmgrid, comoving_fac, 0, st));
-  RecMap mp;
-  mp.n = n, mp.stride = lay->p_stride, mp.nf = 0;
-  rec_add(mp, lay->p_gravaccel, 3, 0, ctx->f[GHIP_F_GRAVACCEL].p);
-  rec_add(mp, lay->p_oldacc, 1, 0, ctx->f[GHIP_F_OLDACC].p);
-  rec_add(mp, lay->p_gravpm, 3, 0, ctx->f[GHIP_F_GRAVPM].p);
-  rec_add(mp, lay->p_gravcost, 1, 3, ctx->f[GHIP_F_GRAVCOST].p);
-  GCHK(run_records<true>(ctx, mp, ctx->aosP.p, -1, st));
-  HIPCHK(hipMemcpyAsync(Pp, ctx->aosP.p, n * lay->p_stride, hipMemcpyDeviceToHost, st));
-  if(side)
-    {
-      // whatever the main stream does next comes after the pair and after this
-      HIPCHK(hipEventRecord(ctx->ev_side, st));
-      HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-      ctx->grav_pending = false;
-    }
-  HIPCHK(ghip_stream_sync(ctx, st));
-  return ghip_check_device_errors(ctx);
-}
-
-extern "C" int ghip_gas_block_mixed(ghip_ctx *ctx)
-{
-  if(!ctx)
-    return GHIP_EINVAL;
-  return *reinterpret_cast<volatile int *>(ghip_gas_mixed_word(ctx)) != 0;
-}
-
-extern "C" int ghip_pin_host(ghip_ctx *ctx, void *ptr, size_t bytes)
-{
-  if(!ctx || !ptr || bytes == 0)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_pin_host: bad arguments");
-  (void) hipSetDevice(ctx->device);
-  for(void *p : ctx->host_pins)
-    if(p == ptr)
-      return ghip_fail(ctx, GHIP_EINVAL, "ghip_pin_host: this array is already locked (ghip_unpin_host first)");
-  hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
-  if(e != hipSuccess)
-    {
-      (void) hipGetLastError();   // not an error of the path: the copies stay staged
-      ctx->err = std::string("ghip_pin_host: the range could not be page-locked (") + hipGetErrorString(e) +
-                 "); record copies go through the runtime's staging buffers";
-      return GHIP_OK;
-    }
-  ctx->host_pins.push_back(ptr);
-  return GHIP_OK;
-}
-
-extern "C" int ghip_unpin_host(ghip_ctx *ctx, void *ptr)
-{
-  if(!ctx)
-    return GHIP_EINVAL;
-  for(size_t i = 0; i < ctx->host_pins.size(); i++)
-    if(ctx->host_pins[i] == ptr)
-      {
-        // a copy in flight may still read the range
-        GHIP_JOIN(ctx);
-        (void) ghip_stream_sync(ctx, ctx->stream);
-        (void) hipHostUnregister(ptr);
-        (void) hipGetLastError();
-        ctx->host_pins.erase(ctx->host_pins.begin() + (long) i);
-        return GHIP_OK;
-      }
-  return GHIP_OK;   // never locked (or the lock had failed): nothing to do
-}
-
-__global__ void k_pack_i16(size_t n, char *__restrict__ rec, int stride, int off,
-                           const int *__restrict__ src)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i < n)
-    *reinterpret_cast<short *>(rec + i * (size_t) stride + off) = (short) src[i];
-}
-
-__global__ void k_pack_i32(size_t n, char *__restrict__ rec, int stride, int off,
-                           const int *__restrict__ src)
-{
-  size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if(i < n)
-    *reinterpret_cast<int *>(rec + i * (size_t) stride + off) = src[i];
-}
-
-// results of ghip_advance_timesteps into the record images (timestep.c: P[].Vel, TimeBin,
-// Ti_begstep; SphP[].VelPred, Entropy, e.DtEntropy)
-extern "C" int ghip_download_aos_kick(ghip_ctx *ctx, void *Pp, void *Sp, const ghip_layout *lay)
-{
-  if(ctx)
-    GHIP_JOIN(ctx);
-  if(!ctx || !lay)
-    return GHIP_EINVAL;
-  size_t n = (size_t) ctx->n, ng = (size_t) ctx->ngas;
-  if(n == 0)
-    return GHIP_OK;
-  if(!Pp || (ng > 0 && !Sp))
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_download_aos_kick: null record pointers");
-  if(ctx->aosP.cap < n * lay->p_stride || (ng > 0 && ctx->aosS.cap < ng * lay->s_stride))
-    return ghip_fail(ctx, GHIP_EINVAL,
-                     "ghip_download_aos_kick: no device image (call ghip_upload_aos)");
-  hipStream_t st = ctx->stream;
-  void *ip = ctx->aosP.p, *is = ctx->aosS.p;
-  PACK64(n, ip, lay->p_stride, lay->p_vel, 3, GHIP_F_VEL);
-  if(lay->p_timebin >= 0)
-    k_pack_i16<<<cdiv((long long) n, 256), 256, 0, st>>>(n, (char *) ip, lay->p_stride,
-                                                         lay->p_timebin,
-                                                         P<int>(ctx->f[GHIP_F_TIMEBIN]));
-  if(lay->p_ti_begstep >= 0)
-    k_pack_i32<<<cdiv((long long) n, 256), 256, 0, st>>>(n, (char *) ip, lay->p_stride,
-                                                         lay->p_ti_begstep,
-                                                         P<int>(ctx->f[GHIP_F_TI_BEGSTEP]));
-  if(ng > 0)
-    {
-      PACK64(ng, is, lay->s_stride, lay->s_velpred, 3, GHIP_F_VELPRED);
-      PACK64(ng, is, lay->s_stride, lay->s_entropy, 1, GHIP_F_ENTROPY);
-      PACK64(ng, is, lay->s_stride, lay->s_dtentropy, 1, GHIP_F_DTENTROPY);
-    }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(Pp, ip, n * lay->p_stride, hipMemcpyDeviceToHost, st));
-  if(ng > 0)
-    HIPCHK(hipMemcpyAsync(Sp, is, ng * lay->s_stride, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
   return ghip_check_device_errors(ctx);
 }

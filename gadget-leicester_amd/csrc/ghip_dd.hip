@@ -1680,8 +1680,6 @@ struct MigSplits
   const int *owner;                // [nseg]
 };
 
-void ghip_field_info(int f, int *gas, int *ncomp, int *isint);   // api.hip
-
 // heat: the per-gas DragHeating, or nullptr when the shard holds none; visc: alpha and Dtalpha, or nullptr
 static MigTable mig_table(DevBuf *bufs, DevBuf *heat, DevBuf *const *visc)
 {

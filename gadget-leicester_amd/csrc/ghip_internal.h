@@ -652,6 +652,8 @@ int ghip_mark_converted_gas(ghip_ctx *ctx);
 int ghip_sink_buffers(ghip_ctx *ctx);        // SwallowID / Injected_BH_Energy, zeroed when first made
 int ghip_unmark_massless_for_hydro(ghip_ctx *ctx);
 int ghip_check_gas_types(ghip_ctx *ctx);   // after TYPE changed: recount, sets ctx->gas_mixed (synchronises)
+// kField[] of ghip_api.hip, for the migration (ghip_dd.hip) and the record members (ghip_records.hip)
+void ghip_field_info(int f, int *gas, int *ncomp, int *isint);
 int ghip_dyn_capture(ghip_ctx *ctx);                 // after a full build: copy the gravity tree, vs / vmax per node
 int ghip_dyn_kick_recorded(ghip_ctx *ctx);           // force_kick_node for what ghip_advance_timesteps recorded
 void ghip_dyn_release(ghip_ctx *ctx);
