@@ -214,6 +214,23 @@ class DecompParams(C.Structure):
     _fields_ = [("level", C.c_int), ("use_work", C.c_int), ("find_extent", C.c_int), ("reserved", C.c_int)]
 
 
+class SyncParams(C.Structure):
+    """ghip_sync_params (ghip_find_next_sync_point / GHIP_DD_DECOMPOSE with walk = SYNC_POINT_FORM)"""
+    _fields_ = [("Ti_Current", C.c_int), ("Ti_nextoutput", C.c_int)]
+
+
+class SyncPoint(C.Structure):
+    """ghip_sync_point: what find_next_sync_point_and_drift (run.c:190-340) decides before it drifts"""
+    _fields_ = [("Ti_next", C.c_int), ("output_due", C.c_int), ("TimeBinActive", C.c_uint),
+                ("NumForceUpdate", C.c_longlong), ("GlobNumForceUpdate", C.c_longlong),
+                ("Flag_FullStep", C.c_int), ("TimeBinCount", C.c_longlong * 32),
+                ("TimeBinCountSph", C.c_longlong * 32)]
+
+    def asdict(self):
+        return {k: (np.array(getattr(self, k)[:], dtype=np.int64) if k.startswith("TimeBinCount")
+                    else int(getattr(self, k))) for k, _ in self._fields_}
+
+
 class GlobalParams(C.Structure):
     """ghip_global_params (compute_global_quantities_of_system, global.c:18-238)"""
     _fields_ = [("Ti_Current", C.c_int), ("Timebase_interval", C.c_double),
@@ -337,7 +354,8 @@ EXPORTS = [
     "ghip_dust_drag_grains",
     "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
     "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts",
-    "ghip_debug_prim"]
+    "ghip_debug_prim",
+    "ghip_find_next_sync_point", "ghip_get_active", "ghip_find_extent", "ghip_dd_get_sync_point"]
 
 
 def lib():
@@ -478,6 +496,10 @@ def lib():
         L.ghip_visc_params_size.restype = C.c_size_t
         L.ghip_set_rnd_table.argtypes = [vp, vp, C.c_int]
         L.ghip_tree_max_level.argtypes = []
+        L.ghip_find_next_sync_point.argtypes = [vp, C.POINTER(SyncParams), C.POINTER(SyncPoint)]
+        L.ghip_get_active.argtypes = [vp, vp, C.POINTER(C.c_int)]
+        L.ghip_find_extent.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
+        L.ghip_dd_get_sync_point.argtypes = [vp, C.POINTER(SyncPoint)]
         _LIB = L
     return _LIB
 
@@ -571,6 +593,36 @@ class ForcePath:
             self._active_keep = a
             self._chk(self.L.ghip_set_active(self.h, _ptr(a), len(a)))
             self._active_n = len(a)
+
+    def find_next_sync_point(self, ti_current, ti_nextoutput=-1):
+        """ghip_find_next_sync_point: the next sync point and the active list from the resident TIMEBIN
+        (find_next_sync_point_and_drift, run.c:190-340, without the drift) -> SyncPoint.  With output_due the
+        list stays as it was; drift to .Ti_next yourself (drift())."""
+        p, out = SyncParams(int(ti_current), int(ti_nextoutput)), SyncPoint()
+        self._chk(self.L.ghip_find_next_sync_point(self.h, C.byref(p), C.byref(out)))
+        return out
+
+    def get_active(self):
+        """ghip_get_active: the particle indices of the list in force (int32; 0 .. n-1 when all are active)"""
+        n = C.c_int(0)
+        self._chk(self.L.ghip_get_active(self.h, None, C.byref(n)))
+        idx = np.zeros(n.value, np.int32)
+        if n.value:
+            self._chk(self.L.ghip_get_active(self.h, _ptr(idx), C.byref(n)))
+        return idx
+
+    def find_extent(self):
+        """ghip_find_extent: (corner[3], center[3], len) of domain_findExtent over the resident positions --
+        what tree_build takes"""
+        corner, center, ln = np.zeros(3), np.zeros(3), C.c_double(0)
+        self._chk(self.L.ghip_find_extent(self.h, _ptr(corner), _ptr(center), C.byref(ln)))
+        return corner, center, ln.value
+
+    def dd_get_sync_point(self):
+        """the result of this shard's last completed sync point (DD_DECOMPOSE, walk = SYNC_POINT_FORM) -> SyncPoint"""
+        out = SyncPoint()
+        self._chk(self.L.ghip_dd_get_sync_point(self.h, C.byref(out)))
+        return out
 
     def set_shard(self, rank, nranks):
         self._chk(self.L.ghip_set_shard(self.h, int(rank), int(nranks)))
@@ -1242,6 +1294,7 @@ DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 DD_DECOMPOSE = 13
 DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
+SYNC_POINT_FORM = 1      # `walk` of dd_begin / dd_run for DD_DECOMPOSE with SyncParams: the sync point of all shards
 DUST_GRAINS_FORM = 1     # `walk` of dd_begin / dd_run for DD_DUST_DENSITY / DD_DUST_DRAG with DdDustGrainsArgs
 
 

@@ -263,9 +263,14 @@ unsigned long long ghip_extent_reduce(const unsigned long long *all, int nranks,
   return err;
 }
 
-int ghip_dd_decomp_begin(ghip_ctx *ctx, int, const void *params, int)
+int ghip_dd_decomp_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
   DDState &D = ctx->dd;
+  // the other thing run() does between two steps shares the operation: `walk` selects the form, as for the dust
+  // operations (ghip_sync.hip)
+  D.walk = walk;
+  if(walk == GHIP_SYNC_POINT_FORM)
+    return ghip_dd_sync_begin(ctx, op, params, walk);
   D.dcp = *reinterpret_cast<const ghip_dd_decomp_params *>(params);
   const ghip_dd_decomp_params &p = D.dcp;
   if(p.level < 0 || p.level > 7)
@@ -293,6 +298,8 @@ static inline bool dc_inside(double x, double corner, double fac)
 int ghip_dd_decomp_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
+  if(D.walk == GHIP_SYNC_POINT_FORM)
+    return ghip_dd_sync_step(ctx);
   hipStream_t st = ctx->stream;
   const ghip_dd_decomp_params &p = D.dcp;
   const int P_ = D.nranks, n = ctx->n;

@@ -303,6 +303,12 @@ struct DDState
   DevBuf dc_hist, dc_hist_all;    // u64[8^level]: this shard's histogram, later the sum / of all shards
   int dc_level = 0, dc_bmax = 0, dc_shift = 0;
   double dc_corner[3] = {0, 0, 0}, dc_center[3] = {0, 0, 0}, dc_len = 0;   // the cube the keys are formed in
+  // GHIP_DD_DECOMPOSE begun with walk = GHIP_SYNC_POINT_FORM (ghip_sync.hip)
+  ghip_sync_params sp = {};       // arguments of the operation in progress
+  ghip_sync_point sp_out = {};    // the result of the last completed one (ghip_dd_get_sync_point)
+  ghip_sync_point sp_cur = {};    // ... of the one in progress
+  int sp_selected = 0;            // entries of its list, waiting in act_next for every shard's status
+  DevBuf sp_all;                  // u64[nranks][32]: the TimeBinCount of all shards (this shard's: DevWords::timebin_hist)
 };
 
 // the pending exchange of a state-machine step (ghip_dd.hip, ghip_sink.hip)
@@ -344,6 +350,7 @@ struct DevWords
   int tree_info[2][2]; // count_nodes, per tree (gravity, gas): {deepest level, longest key run the
                        // 32-bit sort left unsorted}; k_tree_info reads them and leaves them zeroed
   int rnd_info[2][2];  // rnd_order (ghip_tree.hip), two sets used in turn: {crowded sources, long runs}
+  int sync_sel[2];     // ghip_find_next_sync_point: {particles selected, TimeBins outside [0, TIMEBINS)}
 };
 
 // ... and in pinned, device-visible host memory (ctx->pinned): kernels write, the host reads after a wait
@@ -443,6 +450,7 @@ struct ghip_ctx
   // active lists
   DevBuf act_host_idx;  // i32[nactive] host indices (uploaded)
   int nactive = -1;     // -1: all
+  DevBuf act_next;      // i32[n]: the list ghip_find_next_sync_point is writing; swapped in when the call succeeds
   bool gas_mixed = false;        // a record of the gas block [0, ngas) has Type != 0 (ghip_check_gas_types)
   int skip_massless = 0;         // a gas particle of mass 0 is nobody's neighbour: 1 in density() (-DDUST or
                                  // -DBLACK_HOLES), 3 in density() and hydro_force() (-DBLACK_HOLES)
@@ -621,6 +629,9 @@ int ghip_fail(ghip_ctx *ctx, int code, const char *fmt, ...);
 int *ghip_errwords(void);
 static inline int *ghip_errword(ghip_ctx *, int which) { return ghip_errwords() + which; }
 int ghip_check_device_errors(ghip_ctx *ctx);
+// ghip_kick.hip: TimeBinCount[32] | TimeBinCountSph[32] recounted over all particles (k_timebin_histogram), on the
+// host when this returns: the one 64-word blocking read of ghip_timebin_counts and ghip_find_next_sync_point
+int ghip_timebin_hist(ghip_ctx *ctx, unsigned long long hist[64]);
 // The overlapped Newton+Ewald pair returns with its walks still running on their own streams, so
 // that the SPH phases -- which read and write nothing the walks touch -- can be enqueued on the
 // main stream underneath them.  Every other entry point first makes the main stream wait for the
@@ -797,6 +808,8 @@ int ghip_dd_gq_begin(ghip_ctx *ctx, int op, const void *params, int walk);
 int ghip_dd_gq_step(ghip_ctx *ctx);
 int ghip_dd_decomp_begin(ghip_ctx *ctx, int op, const void *params, int walk);   // decomp.hip
 int ghip_dd_decomp_step(ghip_ctx *ctx);
+int ghip_dd_sync_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // sync.hip: GHIP_SYNC_POINT_FORM
+int ghip_dd_sync_step(ghip_ctx *ctx);
 // all shards stop together: hold keeps rc (with ctx->err if it is a failure) and says whether it failed, the flag
 // travels with the next exchange; raise(r = first rank whose flag is set, < 0: none, GHIP_OK) then fails with this
 // shard's own code and message if it holds one, else with the formatted message and GHIP_EDEVICE

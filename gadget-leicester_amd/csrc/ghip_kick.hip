@@ -376,14 +376,9 @@ __global__ void k_timebin_histogram(int n, const int *__restrict__ type,
     atomicAdd(out + threadIdx.x, (unsigned long long) h[threadIdx.x]);
 }
 
-extern "C" int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long long *TimeBinCountSph)
+int ghip_timebin_hist(ghip_ctx *ctx, unsigned long long hist[64])
 {
-  if(!ctx)
-    return GHIP_EINVAL;
-  if(TimeBinCount)
-    memset(TimeBinCount, 0, 32 * sizeof(long long));
-  if(TimeBinCountSph)
-    memset(TimeBinCountSph, 0, 32 * sizeof(long long));
+  memset(hist, 0, 64 * 8);
   const int n = ctx->n;
   if(n == 0)
     return GHIP_OK;
@@ -393,9 +388,23 @@ extern "C" int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long 
   k_timebin_histogram<<<cdiv(n, 256), 256, 0, st>>>(n, P<int>(ctx->f[GHIP_F_TYPE]),
                                                     P<int>(ctx->f[GHIP_F_TIMEBIN]), dhist);
   HIPCHK(hipGetLastError());
-  unsigned long long hist[64];
   HIPCHK(hipMemcpyAsync(hist, dhist, 64 * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
+  return GHIP_OK;
+}
+
+extern "C" int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long long *TimeBinCountSph)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  if(TimeBinCount)
+    memset(TimeBinCount, 0, 32 * sizeof(long long));
+  if(TimeBinCountSph)
+    memset(TimeBinCountSph, 0, 32 * sizeof(long long));
+  if(ctx->n == 0)
+    return GHIP_OK;
+  unsigned long long hist[64];
+  GCHK(ghip_timebin_hist(ctx, hist));
   for(int b = 0; b < 32; b++)
     {
       if(TimeBinCount)

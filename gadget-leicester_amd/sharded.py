@@ -270,6 +270,14 @@ class DomainShards:
         particle of any shard left the region: pm_region(), then call again"""
         self.run(self.B.DD_PM_NONPERIODIC, params)
 
+    def sync_point(self, ti_current, ti_nextoutput=-1):
+        """GHIP_DD_DECOMPOSE in its SYNC_POINT_FORM: the next sync point of ALL shards' particles and every shard's own active list
+        (get_active()) -> [SyncPoint] in shard order; Ti_next, TimeBinActive, GlobNumForceUpdate and
+        Flag_FullStep are the same on all of them.  A TIMEBIN outside [0, 28] on one shard: GhipError on all,
+        no list changed."""
+        self.run(self.B.DD_DECOMPOSE, self.B.SyncParams(int(ti_current), int(ti_nextoutput)), self.B.SYNC_POINT_FORM)
+        return [p.dd_get_sync_point() for p in self.paths]
+
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams): afterwards every path's get_potential() / get_potential_interactions()
         give its own particles"""
@@ -390,6 +398,13 @@ class DomainRank:
         """GHIP_DD_PM_NONPERIODIC(PmnpParams), a collective: this rank's F_GRAVPM; GhipError with GHIP_EREGION
         on every rank when a particle of any rank left the region: pm_region(), then call again"""
         self._run(self.B.DD_PM_NONPERIODIC, params)
+
+    def sync_point(self, ti_current, ti_nextoutput=-1):
+        """GHIP_DD_DECOMPOSE in its SYNC_POINT_FORM, a collective: the next sync point of all ranks' particles (this rank contributes
+        its 32 bin populations, 256 bytes, and one status record) and this rank's own active list
+        (self.p.get_active()) -> SyncPoint"""
+        self._run(self.B.DD_DECOMPOSE, self.B.SyncParams(int(ti_current), int(ti_nextoutput)), self.B.SYNC_POINT_FORM)
+        return self.p.dd_get_sync_point()
 
     def potential(self, params):
         """GHIP_DD_POTENTIAL(PotParams), a collective: afterwards the path's get_potential() gives its own

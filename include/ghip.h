@@ -28,6 +28,8 @@
  *   ghip_pm_nonperiodic                   pmforce_nonperiodic(0)       pm_nonperiodic.c:576-1175
  *   ghip_potential                        compute_potential()          potential.c:22-325
  *   ghip_global_quantities                compute_global_quantities_of_system()  global.c:18-238
+ *   ghip_find_next_sync_point             find_next_sync_point_and_drift() without its drift  run.c:190-340
+ *   ghip_find_extent                      domain_findExtent() of one context   domain.c:1972-2014
  * The host-side mirror with the reference's own names (gravity_tree(), density(), hydro_force(),
  * force_treeevaluate(), ...) is include/gadget_force.h.
  */
@@ -294,6 +296,53 @@ int ghip_unpin_host(ghip_ctx *ctx, void *ptr);
 /* ---- active list (FirstActiveParticle/NextActiveParticle, run.c:300-320) ---- */
 /* host indices of the active particles; NULL or n == numpart with idx NULL: all active */
 int ghip_set_active(ghip_ctx *ctx, const int *idx, int nactive);
+/* the list in force, after ghip_set_active and ghip_find_next_sync_point alike: *nactive always, the
+ * indices (ascending where the library made the list) if idx != NULL.  With everybody active: numpart
+ * and 0 .. numpart-1.  Synchronises. */
+int ghip_get_active(ghip_ctx *ctx, int *idx /* may be NULL */, int *nactive);
+
+/* ---- find_next_sync_point_and_drift() without the drift (run.c:190-340), on the resident TIMEBIN ----
+ * The bins are recounted on the device (TimeBinCount / TimeBinCountSph, reconstruct_timebins).  For every
+ * populated bin n > 0 the next kick is (Ti_Current / 2^n) * 2^n + 2^n, for bin 0 it is Ti_Current; Ti_next is
+ * the least of them (run.c:199-219), TIMEBASE = 1 << 29 when no bin is populated.
+ *   output_due (run.c:222: Ti_next >= Ti_nextoutput >= 0): the call reports Ti_next = Ti_nextoutput,
+ *       TimeBinActive = 0 and both force counts 0, and leaves the active list as it was.  The caller drifts
+ *       there with ghip_drift, writes its output (run.c:222-251 stays host code), picks its next output time
+ *       and calls again with the same Ti_Current.
+ *   otherwise bin 0 is active and bin n > 0 is active when 2^n divides Ti_next (run.c:278-289); the active list
+ *       of the context becomes { i : TimeBinActive[TIMEBIN[i]] } in ASCENDING PARTICLE INDEX, for every consumer
+ *       of ghip_set_active (target lists, kick, sfr, sink).  The reference chains the list bin-major
+ *       (run.c:300-320); no device pass depends on the order of the list -- the target lists are sorted along
+ *       the curve, the kick and the cooling act per particle --, only the order in which ghip_sfr_cooling and
+ *       ghip_find_smbh report follows it.  When every particle is active the context is in the state of
+ *       ghip_set_active(ctx, NULL, 0).
+ * The call does not drift: ghip_drift(time1 = out->Ti_next) stays the caller's next call.
+ * GHIP_EINVAL, the active list unchanged: NULL arguments; Ti_Current outside [0, TIMEBASE]; a resident
+ * TIMEBIN outside [0, 28] (the message names how many; they are not folded into the 32 counters).
+ * Host traffic: one blocking read of the 64 counters, one of the list length (with the count of bad bins).
+ * On a multi-GPU shard (ghip_dd_init): GHIP_SYNC_POINT_FORM below; a context of ghip_set_shard holds every
+ * particle and calls this.  The host mirror libgadget_force.so keeps its own FirstActiveParticle chain. ---- */
+typedef struct
+{
+  int Ti_Current;     /* the sync point just completed: All.Ti_Current on entry of run.c:190 */
+  int Ti_nextoutput;  /* All.Ti_nextoutput; < 0: none */
+} ghip_sync_params;
+typedef struct
+{
+  int Ti_next;                 /* ti_next_kick_global (run.c:199-219); Ti_nextoutput when output_due */
+  int output_due;              /* run.c:222: ti_next_kick_global >= Ti_nextoutput >= 0 */
+  unsigned int TimeBinActive;  /* bit b <=> TimeBinActive[b], b in [0, 28] (run.c:278-289); bits 29..31 zero */
+  long long NumForceUpdate;    /* this context's active particles */
+  long long GlobNumForceUpdate;/* all ranks' (equal to NumForceUpdate on one context) */
+  int Flag_FullStep;           /* GlobNumForceUpdate == total particle count (run.c:293) */
+  long long TimeBinCount[32], TimeBinCountSph[32];  /* this context's populations */
+} ghip_sync_point;
+int ghip_find_next_sync_point(ghip_ctx *ctx, const ghip_sync_params *p, ghip_sync_point *out);
+/* domain_findExtent (domain.c:1972-2014) over the resident POS of a single context: len = 1.001 *
+ * max_j(max_j - min_j), center_j = (min_j + max_j) / 2, corner_j = center_j - len / 2 -- what ghip_tree_build
+ * takes, in the operation order of GHIP_DD_DECOMPOSE with find_extent = 1.  GHIP_EINVAL: a coordinate that is
+ * not finite, no particle, len == 0; a multi-GPU shard (GHIP_DD_DECOMPOSE finds the cube of all ranks). */
+int ghip_find_extent(ghip_ctx *ctx, double corner[3], double center[3], double *len);
 /* restrict evaluation to shard `rank` of `nranks` equal-count slices of the space-filling-curve
  * ordered active list (multi-GPU data parallelism; results of other slices are left untouched) */
 int ghip_set_shard(ghip_ctx *ctx, int rank, int nranks);
@@ -981,6 +1030,17 @@ typedef struct
  * scattered into the zeroed padded mesh and solved on every shard, which reads out its own particles.  A
  * particle outside the region on ANY shard makes EVERY shard return GHIP_EREGION, nothing written anywhere. */
 #define GHIP_DD_PM_NONPERIODIC 15
+/* ghip_find_next_sync_point on shards: GHIP_DD_DECOMPOSE begun with walk = GHIP_SYNC_POINT_FORM and params a
+ * ghip_sync_params (the result: ghip_dd_get_sync_point) -- the two things run() does between two steps share one
+ * operation, as the two forms of the dust operations do; no operation code is added.  Every
+ * shard recounts its own bins and all-gathers its 32 TimeBinCount words (256 bytes); the sums give every rank
+ * the same Ti_next -- the MPI_Allreduce(MIN) of run.c:219: a rank that holds none of the earliest bin still
+ * gets the global value --, the same mask, GlobNumForceUpdate and Flag_FullStep.  Each shard then selects its
+ * own local indices, and one status round (16 bytes per rank) carries what it met: a TIMEBIN outside [0, 28]
+ * on one shard makes every shard return GHIP_EINVAL, and no shard's list changes.  Ti_Current is checked by
+ * ghip_dd_begin; nothing of the decomposition (ranges, cube, trees) is touched. */
+#define GHIP_SYNC_POINT_FORM 1   /* `walk` of ghip_dd_begin / ghip_dd_run for GHIP_DD_DECOMPOSE */
+int ghip_dd_get_sync_point(const ghip_ctx *ctx, ghip_sync_point *out);   /* of the last completed one */
 /* the ranges (nranks+1 keys) and the cube in force: what ghip_dd_set_splits / ghip_dd_set_domain /
  * GHIP_DD_DECOMPOSE stored last.  ghip_dd_get_splits returns GHIP_EINVAL while a ghip_dd_set_segments layout is
  * in force (several pieces per rank are not nranks+1 keys). */
