@@ -1111,7 +1111,9 @@ __global__ void k_ghost_pack(int nrec, const int *__restrict__ list, int n, int 
   r.p[0] = pos[i];
   r.p[1] = pos[(size_t) n + i];
   r.p[2] = pos[2 * (size_t) n + i];
-  r.p[3] = type[i] == 0 ? mass[i] : -1.0;   // (a converted particle of the gas block: nobody's neighbour)
+  // (a converted particle of the gas block: nobody's neighbour on any shard, in density() and in hydro_force();
+  // a swallowed one travels with its mass 0 and is marked where it arrives, by that shard's rule)
+  r.p[3] = type[i] == 0 ? mass[i] : GAS_MARK_CONVERTED;
   r.p[4] = velpred[i];
   r.p[5] = velpred[(size_t) ngas + i];
   r.p[6] = velpred[2 * (size_t) ngas + i];

@@ -659,9 +659,14 @@ static inline unsigned long long *ghip_rslot(ghip_ctx *ctx, int kind)
 }
 // host copy of a slot buffer added up: out[kind][which], which = 0, 1
 int ghip_read_slots(ghip_ctx *ctx, DevBuf &buf, unsigned long long out[GHIP_CK_COUNT][2]);
+// the marks in the mass of a gas record, gp[8 s + 3] (k_mark_converted in ghip_tree.hip says who sets and who
+// removes them): a record that no neighbour loop sums.  The loops test mass < 0.
+#define GAS_MARK_CONVERTED (-1.0)   // Type != 0; a ghost carries it from its owner (k_ghost_pack); never removed
+#define GAS_MARK_MASSLESS (-2.0)    // Mass == 0 under ghip_set_massless_gas_rule; off for hydro_force() under rule 1
 int ghip_mark_converted_gas(ghip_ctx *ctx);
 int ghip_sink_buffers(ghip_ctx *ctx);        // SwallowID / Injected_BH_Energy, zeroed when first made
 int ghip_unmark_massless_for_hydro(ghip_ctx *ctx);
+int ghip_remark_massless_for_density(ghip_ctx *ctx);
 int ghip_check_gas_types(ghip_ctx *ctx);   // after TYPE changed: recount, sets ctx->gas_mixed (synchronises)
 // kField[] of ghip_api.hip, for the migration (ghip_dd.hip) and the record members (ghip_records.hip)
 void ghip_field_info(int f, int *gas, int *ncomp, int *isint);

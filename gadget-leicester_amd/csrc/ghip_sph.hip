@@ -663,6 +663,7 @@ int ghip_density_impl(ghip_ctx *ctx, const ghip_dens_params *p)
   GCHK(ghip_gas_verify(ctx));   // (the gas tree's node count, like the gravity tree's above)
   if(!ctx->st.built)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_density: call ghip_tree_build first");
+  GCHK(ghip_remark_massless_for_density(ctx));   // (a hydro call on this gas tree took the mark off: rule 1)
   GCHK(ghip_build_target_lists(ctx));
   ghip_stats &S = ctx->stats;
   S.dens_neighbours = 0;
@@ -771,6 +772,7 @@ extern "C" int ghip_density_evaluate(ghip_ctx *ctx, const ghip_dens_params *p, i
   if(target < 0 || target >= ctx->ngas)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_density_evaluate: target %d is not a gas particle",
                      target);
+  GCHK(ghip_remark_massless_for_density(ctx));
   hipStream_t st = ctx->stream;
   TreeDev &t = ctx->st;
   GCHK(dens_alloc(ctx));
@@ -857,6 +859,9 @@ extern "C" int ghip_ngb_treefind(ghip_ctx *ctx, const double center[3], double h
   TreeDev &t = ctx->st;
   if(t.n == 0)
     return GHIP_OK;
+  // the list is the one the loop of that search sums, whatever ran before: density()'s without pairs,
+  // hydro_force()'s with them
+  GCHK(pairs ? ghip_unmark_massless_for_hydro(ctx) : ghip_remark_massless_for_density(ctx));
   hipStream_t st = ctx->stream;
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) (cap + 4) * 4));
   int *dlist = P<int>(ctx->stage) + 4, *dcount = P<int>(ctx->stage);

@@ -1665,7 +1665,8 @@ __global__ void k_concat_gas_sources(int ng, int nghost, int n, const double *__
       ox[i] = r.p[0];
       oy[i] = r.p[1];
       oz[i] = r.p[2];
-      om[i] = r.p[3];
+      om[i] = r.p[3];   // (GAS_MARK_CONVERTED for a converted ghost: no kernel reads the gas tree's node masses,
+                        // xm -- the SPH walks take centre, side and hmax from SphNode; ghip_tree_dump shows them)
       oh[i] = r.p[7];
     }
 }
@@ -2000,10 +2001,19 @@ __global__ void k_flag_local(int n, int limit, const int *__restrict__ perm, int
 // rearrange_particle_sequence(): the reference rearranges at domain decompositions only, domain.c:128,
 // and its loops test P[].Type) is neither an SPH target (density.c:1049, hydra.c:184) nor anybody's
 // neighbour (ngb.c:93, 213).  It stays in the gas tree; its record is marked with a negative mass, which
-// the neighbour loops skip, and the target lists leave it out.
-// (massless != 0, the -DBLACK_HOLES / -DDUST builds: a swallowed gas particle, Mass == 0, is skipped by
-// the neighbour loops as well -- density.c:831-834, hydra.c:1235-1238 -- while it stays a target; a ghost
-// arrives with its mass and is marked here)
+// the neighbour loops skip (they test mass < 0), and the target lists leave it out.
+// Two marks in gp[8 s + 3]:
+//   GAS_MARK_CONVERTED (-1)  Type != 0.  Set here for a local record, by k_ghost_pack on the owner for a
+//                            ghost (which arrives with it and keeps it).  Never taken off: the record is
+//                            nobody's neighbour in density() and in hydro_force(), under every rule.
+//   GAS_MARK_MASSLESS (-2)   massless != 0, the -DBLACK_HOLES / -DDUST builds: a swallowed gas particle,
+//                            Mass == 0, is skipped by the neighbour loop of density() (density.c:831-834)
+//                            while it stays a target; a ghost arrives with mass 0 and is marked here.
+//                            Rule 3 (-DBLACK_HOLES) keeps the mark through hydro_force() (hydra.c:1235-1238);
+//                            under rule 1 k_unmark_massless takes it off before the hydro sweep and
+//                            ghip_remark_massless_for_density puts it back before the next reader that
+//                            follows the density rule.
+// A record that is both is converted.
 __global__ void k_mark_converted(int nsrc, int ngas, int massless, const int *__restrict__ perm,
                                  const int *__restrict__ type, double *__restrict__ gp)
 {
@@ -2011,8 +2021,10 @@ __global__ void k_mark_converted(int nsrc, int ngas, int massless, const int *__
   if(s >= nsrc)
     return;
   const int i = perm[s];
-  if((i < ngas && type[i] != 0) || (massless && gp[(size_t) 8 * s + 3] == 0))
-    gp[(size_t) 8 * s + 3] = -1.0;
+  if(i < ngas && type[i] != 0)
+    gp[(size_t) 8 * s + 3] = GAS_MARK_CONVERTED;
+  else if(massless && gp[(size_t) 8 * s + 3] == 0)
+    gp[(size_t) 8 * s + 3] = GAS_MARK_MASSLESS;
 }
 
 __global__ void k_unflag_converted(int n, int limit, const int *__restrict__ perm, const int *__restrict__ type,
@@ -2040,16 +2052,26 @@ int ghip_mark_converted_gas(ghip_ctx *ctx)
   return GHIP_OK;
 }
 
+// The readers of the gas records that follow the rule of density() (ghip_density_impl, ghip_density_evaluate,
+// ghip_ngb_treefind): under rule 1 a hydro call on this gas tree has taken the massless mark off
+// (ghip_unmark_massless_for_hydro); it goes back on before they read.  Nothing is launched while the mark is
+// in place, or without a rule.
+int ghip_remark_massless_for_density(ghip_ctx *ctx)
+{
+  if(ctx->skip_massless == 0 || ctx->massless_marked)
+    return GHIP_OK;
+  return ghip_mark_converted_gas(ctx);
+}
+
 // -DDUST without -DBLACK_HOLES: hydro_force() sums the massless gas that density() skipped (hydra.c:1235
-// is under BLACK_HOLES alone): the mark comes off the records that are gas
-__global__ void k_unmark_massless(int nsrc, int ngas, const int *__restrict__ perm, const int *__restrict__ type,
-                                  double *__restrict__ gp)
+// is under BLACK_HOLES alone): GAS_MARK_MASSLESS comes off, from local records and ghosts alike, and the
+// mass is 0 again.  GAS_MARK_CONVERTED stays: a converted ghost is no more a neighbour than a local one.
+__global__ void k_unmark_massless(int nsrc, double *__restrict__ gp)
 {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if(s >= nsrc)
     return;
-  const int i = perm[s];
-  if(gp[(size_t) 8 * s + 3] < 0 && (i >= ngas || type[i] == 0))
+  if(gp[(size_t) 8 * s + 3] == GAS_MARK_MASSLESS)
     gp[(size_t) 8 * s + 3] = 0.0;
 }
 
@@ -2059,8 +2081,7 @@ int ghip_unmark_massless_for_hydro(ghip_ctx *ctx)
   if(!ctx->massless_marked || ctx->skip_massless != 1 || t.n == 0)
     return GHIP_OK;
   const int wg = ghip_wg(ctx);
-  k_unmark_massless<<<cdiv(t.n, wg), wg, 0, ctx->stream>>>(t.n, ctx->ngas, P<int>(t.perm),
-                                                           P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->gp));
+  k_unmark_massless<<<cdiv(t.n, wg), wg, 0, ctx->stream>>>(t.n, P<double>(ctx->gp));
   HIPCHK(hipGetLastError());
   ctx->massless_marked = false;
   return GHIP_OK;

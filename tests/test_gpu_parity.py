@@ -2385,6 +2385,9 @@ def test_converted_particles_in_the_gas_block_are_neither_sph_targets_nor_neighb
     assert fp.stats()["hydro_pairs"] == oh["npairs"]
     ha = fp.get_field(B.F_HYDROACCEL)
     assert np.abs(ha[gas] - oh["hydroaccel"][gas]).max() < TOL * np.abs(oh["hydroaccel"][gas]).max()
+    de = fp.get_field(B.F_DTENTROPY)
+    assert np.abs(de[gas] - oh["dtentropy"][gas]).max() < TOL * np.abs(oh["dtentropy"][gas]).max()
+    assert relerr(fp.get_field(B.F_MAXSIGNALVEL)[gas], oh["maxsignalvel"][gas]) < TOL
     # the same decomposition-free state with an explicit active list that still names the converted ones
     fp.set_active(np.arange(0, n, 3, dtype=np.int32))
     fp.set_field(B.F_DENSITY, sentinel)
@@ -2438,6 +2441,9 @@ def test_swallowed_gas_of_mass_zero_is_skipped_by_the_neighbour_loops_of_a_black
         assert fp.stats()["hydro_pairs"] == oh["npairs"]
         ha = fp.get_field(B.F_HYDROACCEL)
         assert np.abs(ha - oh["hydroaccel"][:ng]).max() < TOL * np.abs(oh["hydroaccel"]).max()
+        de = fp.get_field(B.F_DTENTROPY)
+        assert np.abs(de - oh["dtentropy"][:ng]).max() < TOL * np.abs(oh["dtentropy"][:ng]).max()
+        assert relerr(fp.get_field(B.F_MAXSIGNALVEL), oh["maxsignalvel"][:ng]) < TOL
         # the rule matters: without it the massless neighbours are counted in NumNgb
         O.set_massless_gas_rule(0)
         od0 = T.density(pr.o_dens(), act, pr.velpred, pr.entropy, pr.dtentropy, pr.timebin, pr.ti_begstep,
