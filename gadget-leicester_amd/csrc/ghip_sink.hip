@@ -30,7 +30,8 @@ struct SinkRec   // what a pass needs of its sink (host fills it from the reside
 {
   double x, y, z, vx, vy, vz, mass, h, mdot, rho;
   unsigned int id;
-  int timebin, index, pad;
+  int timebin, index;
+  unsigned int mark;   // the sink's own resident SwallowID (the swallow pass; 0 in the other passes)
 };
 
 // out: [6][ns] planes: rho, weighted numngb, sum m w A, sum m w v[3].  local_only (a multi-GPU shard,
@@ -88,10 +89,14 @@ k_sink_density(int ns, const int *__restrict__ slot, const SinkRec *__restrict__
     }
 }
 
-// the sinks' own state from the resident fields (a few 8-byte reads each) + the per-sink inputs
+// the sinks' own state from the resident fields (a few 8-byte reads each) + the per-sink inputs.
+// with_mark (the swallow pass): also the sink's own SwallowID, as the marking pass left it
 static int gather_sinks(ghip_ctx *ctx, int nsink, const int *idx, const unsigned int *id,
-                        const double *mdot, const double *rho, std::vector<SinkRec> &S)
+                        const double *mdot, const double *rho, std::vector<SinkRec> &S,
+                        bool with_mark = false)
 {
+  if(with_mark)
+    GCHK(ghip_sink_buffers(ctx));
   hipStream_t st = ctx->stream;
   const size_t n = (size_t) ctx->n;
   S.resize(nsink);
@@ -115,7 +120,9 @@ static int gather_sinks(ghip_ctx *ctx, int nsink, const int *idx, const unsigned
       S[a].mdot = mdot ? mdot[a] : 0.0;
       S[a].rho = rho ? rho[a] : 1.0;
       S[a].index = i;
-      S[a].pad = 0;
+      S[a].mark = 0;
+      if(with_mark)
+        HIPCHK(hipMemcpyAsync(&S[a].mark, P<unsigned int>(ctx->bh_swallow) + i, 4, hipMemcpyDeviceToHost, st));
     }
   HIPCHK(ghip_stream_sync(ctx, st));
   for(int a = 0; a < nsink; a++)
@@ -384,7 +391,10 @@ k_bh_evaluate(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *
 }
 
 // blackhole_evaluate_swallow (blackhole.c:1201-1346).  out: [9][ns] planes: mass, bh mass, dust mass,
-// momentum[3], counts gas / sinks / dust
+// momentum[3], counts gas / sinks / dust.  blackhole_accretion() calls it only for a sink that nobody
+// claimed in the marking pass (blackhole.c:528-532: `if(P[i].SwallowID == 0)`): a sink whose own mark
+// is set sweeps nothing -- it and the victims marked with its ID keep their mass -- and reports nine
+// zeros, what its accreted sums hold in the reference after the reset of :713.
 __global__ void __launch_bounds__(64)
 k_bh_swallow(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *__restrict__ lk,
              const double4 *__restrict__ cl, const double *__restrict__ sx,
@@ -398,7 +408,9 @@ k_bh_swallow(int ns, const SinkRec *__restrict__ sinks, int nelem, const int4 *_
   const SinkRec S = sinks[a];
   const double h2 = S.h * S.h;
   double am = 0, ab = 0, ad = 0, m0 = 0, m1 = 0, m2 = 0, c0 = 0, c1 = 0, c2 = 0;
-  d_ngb_walk_wave<SINK_LEAF>(GravElems{lk, cl}, nelem, S.x, S.y, S.z, S.h, K.b, [&](int p, bool valid) {
+  // (S.mark is uniform over the block: all 64 lanes walk or none does)
+  const int nwalk = S.mark == 0 ? nelem : 0;
+  d_ngb_walk_wave<SINK_LEAF>(GravElems{lk, cl}, nwalk, S.x, S.y, S.z, S.h, K.b, [&](int p, bool valid) {
     if(!valid)
       return;
     const int j = perm[p];
@@ -561,7 +573,7 @@ extern "C" int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, in
   if(nsink == 0)
     return GHIP_OK;
   std::vector<SinkRec> S;
-  GCHK(gather_sinks(ctx, nsink, sink_idx, sink_id, nullptr, nullptr, S));
+  GCHK(gather_sinks(ctx, nsink, sink_idx, sink_id, nullptr, nullptr, S, true));
   hipStream_t st = ctx->stream;
   TreeDev &t = ctx->gt;
   const size_t n = (size_t) ctx->n;
@@ -812,7 +824,8 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
       // list of all sinks)
       std::vector<SinkRec> S;
       GCHK(gather_sinks(ctx, nloc, A.sink_idx, A.sink_id, op == GHIP_DD_BH_EVALUATE ? A.bh_mdot : nullptr,
-                        op == GHIP_DD_BH_EVALUATE ? A.bh_density_in : nullptr, S));
+                        op == GHIP_DD_BH_EVALUATE ? A.bh_density_in : nullptr, S,
+                        op == GHIP_DD_BH_SWALLOW));
       if(op == GHIP_DD_SINK_DENSITY)
         for(int a = 0; a < nloc; a++)
           S[a].h = A.hsml[a];

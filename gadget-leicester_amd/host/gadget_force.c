@@ -2303,6 +2303,8 @@ void blackhole_accretion_neighbour_passes(void)
       for(int i = FirstActiveParticle; i >= 0; i = NextActiveParticle[i])
         if(p_type(i) == 5)
           idx[k++] = i;
+      /* blackhole.c:528-532 swallows only for sinks with P[i].SwallowID == 0 after the marking pass: the
+       * list stays whole here, the device skips a sink whose own resident mark is set (ghip.h) */
       int bad = bh_evaluate_batch(n, idx) || bh_swallow_batch(n, idx);
       free(idx);
       if(bad)

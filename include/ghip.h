@@ -692,7 +692,12 @@ int ghip_blackhole_evaluate(ghip_ctx *ctx, const ghip_bh_params *p, int nsink, c
 /* blackhole_evaluate_swallow (blackhole.c:1201-1346): per sink the accreted mass, BH mass, dust
  * mass [nsink] and momentum [nsink][3]; the victims' resident MASS becomes 0 (a tree built before
  * is stale afterwards), sink_bh_mass [nsink] (P[].BH_Mass of the sinks, in/out) becomes 0 for a
- * swallowed sink; counts = gas / sinks / dust swallowed. */
+ * swallowed sink; counts = gas / sinks / dust swallowed.
+ * blackhole_accretion() runs this pass only for a sink that nobody claimed in the marking pass
+ * (blackhole.c:528-532: `if(P[i].Type == 5) if(P[i].SwallowID == 0) blackhole_evaluate_swallow(i, ...)`).
+ * So a sink whose own resident SwallowID is not 0 swallows nothing here: the particles marked with
+ * its ID keep their mass, and its five sums are 0 (what they hold in the reference after :713).
+ * "Swallowed" therefore means: marked by a sink that is itself unmarked. */
 int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int nsink, const int *sink_idx,
                            const unsigned int *sink_id, double *sink_bh_mass, double *acc_mass,
                            double *acc_bhmass, double *acc_dustmass, double *acc_momentum,
@@ -931,7 +936,8 @@ typedef struct
 } ghip_dd_sink_args;
 #define GHIP_DD_SINK_DENSITY 5   /* needs GHIP_DD_DENSITY of this step (the shard's gas tree) */
 #define GHIP_DD_BH_EVALUATE 6    /* needs GHIP_DD_GRAVITY of this step (the shard's gravity tree) */
-#define GHIP_DD_BH_SWALLOW 7
+#define GHIP_DD_BH_SWALLOW 7     /* a sink whose own SwallowID is set swallows nothing (blackhole.c:528-532, see
+                                    ghip_blackhole_swallow): its mark travels to the other shards in its record */
 /* pmforce_periodic on shards (params: ghip_pm_params): every shard deposits ITS particles on the full
  * PMGRID^3 mesh, the meshes are all-gathered and added in rank order (8 PMGRID^3 bytes per shard:
  * 16.8 MB at PMGRID = 128), then every shard transforms the identical mesh and interpolates the

@@ -2466,14 +2466,16 @@ void orc_blackhole_evaluate(const orc_tree *t, const orc_bh_params *p, int nsink
 
 /* blackhole_evaluate_swallow (blackhole.c:1201-1346), mode 0: every neighbour marked with the
  * sink's ID is swallowed -- its mass and momentum are summed, its own mass (and BH_Mass) set to
- * zero.  mass [n] and particle_bh_mass [n] (BH_Mass of sinks, else ignored) are modified.
+ * zero. mass [n] and particle_bh_mass [n] (BH_Mass of sinks, else ignored) are modified.
  * Outputs [nsink]: accreted mass, accreted BH mass, accreted dust mass, momentum [nsink][3];
- * counts[3] = gas, sinks, dust swallowed. */
-void orc_blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink, const int *sink,
-                           const unsigned int *id, const double *hsml,
-                           const unsigned int *swallowid, double *mass, double *particle_bh_mass,
-                           double *acc_mass, double *acc_bhmass, double *acc_dustmass,
-                           double *acc_momentum, long long counts[3])
+ * counts[3] = gas, sinks, dust swallowed.
+ * unclaimed_only: the function under its caller's filter (:528-532: only sinks whose own SwallowID
+ * is 0); else the function for every sink of the list, as it is when called by itself. */
+static void blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink, const int *sink,
+                              const unsigned int *id, const double *hsml,
+                              const unsigned int *swallowid, double *mass, double *particle_bh_mass,
+                              double *acc_mass, double *acc_bhmass, double *acc_dustmass,
+                              double *acc_momentum, long long counts[3], int unclaimed_only)
 {
   int n = t->n;
   int *ngblist = (int *) malloc((size_t) n * sizeof(int));
@@ -2484,7 +2486,10 @@ void orc_blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink,
       const double *pos = t->pos + 3 * (size_t) i;
       unsigned int myid = id[i];
       double am = 0, ab = 0, ad = 0, mom[3] = { 0, 0, 0 };
-      int nn = ngb_treefind_blackhole(t, pos, hsml[i], p->dust, p->periodic, p->BoxSize, ngblist);
+      /* blackhole.c:528-532: the pass runs only for a sink that nobody claimed, `if(P[i].SwallowID == 0)`;
+       * a claimed sink leaves its own victims alone, its sums stay at the 0 of :713 */
+      int nn = (unclaimed_only && swallowid[i] != 0) ? 0 :
+               ngb_treefind_blackhole(t, pos, hsml[i], p->dust, p->periodic, p->BoxSize, ngblist);
       for(int q = 0; q < nn; q++)
         {
           int j = ngblist[q];
@@ -2525,6 +2530,30 @@ void orc_blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink,
         acc_momentum[3 * a + k] = mom[k];
     }
   free(ngblist);
+}
+
+/* the swallow pass of blackhole_accretion(): blackhole_evaluate_swallow for the sinks of the list
+ * that nobody claimed in the marking pass (blackhole.c:528-532) */
+void orc_blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink, const int *sink,
+                           const unsigned int *id, const double *hsml,
+                           const unsigned int *swallowid, double *mass, double *particle_bh_mass,
+                           double *acc_mass, double *acc_bhmass, double *acc_dustmass,
+                           double *acc_momentum, long long counts[3])
+{
+  blackhole_swallow(t, p, nsink, sink, id, hsml, swallowid, mass, particle_bh_mass, acc_mass, acc_bhmass,
+                    acc_dustmass, acc_momentum, counts, 1);
+}
+
+/* blackhole_evaluate_swallow by itself, for every sink of the list (the function has no filter of
+ * its own; the reference never calls it for a claimed sink) */
+void orc_blackhole_evaluate_swallow(const orc_tree *t, const orc_bh_params *p, int nsink, const int *sink,
+                                    const unsigned int *id, const double *hsml,
+                                    const unsigned int *swallowid, double *mass, double *particle_bh_mass,
+                                    double *acc_mass, double *acc_bhmass, double *acc_dustmass,
+                                    double *acc_momentum, long long counts[3])
+{
+  blackhole_swallow(t, p, nsink, sink, id, hsml, swallowid, mass, particle_bh_mass, acc_mass, acc_bhmass,
+                    acc_dustmass, acc_momentum, counts, 0);
 }
 
 /* cooling_and_starformation (sfr_eff.c:82-947), the deterministic per-particle part that is active

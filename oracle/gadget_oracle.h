@@ -243,6 +243,11 @@ void orc_blackhole_swallow(const orc_tree *t, const orc_bh_params *p, int nsink,
                            const unsigned int *swallowid, double *mass, double *particle_bh_mass,
                            double *acc_mass, double *acc_bhmass, double *acc_dustmass,
                            double *acc_momentum, long long counts[3]);
+void orc_blackhole_evaluate_swallow(const orc_tree *t, const orc_bh_params *p, int nsink, const int *sink,
+                                    const unsigned int *id, const double *hsml,
+                                    const unsigned int *swallowid, double *mass, double *particle_bh_mass,
+                                    double *acc_mass, double *acc_bhmass, double *acc_dustmass,
+                                    double *acc_momentum, long long counts[3]);
 void orc_cooling_and_starformation(int nactive, const int *active, int ngas, const int *type,
                                    const double *mass, const int *timebin, double timebase,
                                    double CritPhysDensity_code, double MinEgySpec,

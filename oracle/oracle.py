@@ -381,9 +381,11 @@ def blackhole_evaluate(tree, params, sinks, ids, hsml, timebin, mdot, bh_density
     return sw, inj[:len(injected)]
 
 
-def blackhole_swallow(tree, params, sinks, ids, hsml, swallowid, particle_bh_mass):
-    """blackhole_evaluate_swallow (blackhole.c:1201).  The tree's mass array IS modified (victims
-    are set to zero), as the reference does.  Returns dict."""
+def blackhole_swallow(tree, params, sinks, ids, hsml, swallowid, particle_bh_mass, unclaimed_only=False):
+    """blackhole_evaluate_swallow (blackhole.c:1201) for every sink of the list, as the function is when
+    called by itself; with unclaimed_only the swallow pass of blackhole_accretion(), which calls it only
+    for the sinks whose own SwallowID is 0 (:528-532) -- what the device's pass is compared with.
+    The tree's mass array IS modified (victims are set to zero), as the reference does.  Returns dict."""
     sinks = _i32(sinks)
     ns = len(sinks)
     ids = np.ascontiguousarray(ids, np.uint32)
@@ -391,12 +393,12 @@ def blackhole_swallow(tree, params, sinks, ids, hsml, swallowid, particle_bh_mas
     pbh = _f64(particle_bh_mass).copy()
     out = dict(acc_mass=np.zeros(ns), acc_bhmass=np.zeros(ns), acc_dustmass=np.zeros(ns),
                acc_momentum=np.zeros((ns, 3)), counts=np.zeros(3, np.int64), bh_mass=pbh)
-    L = lib()
-    L.orc_blackhole_swallow.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 11
-    L.orc_blackhole_swallow.restype = None
-    L.orc_blackhole_swallow(tree.h, C.byref(params), ns, _p(sinks), _p(ids), _p(_f64(hsml)), _p(sw),
-                            _p(tree.mass), _p(pbh), _p(out["acc_mass"]), _p(out["acc_bhmass"]),
-                            _p(out["acc_dustmass"]), _p(out["acc_momentum"]), _p(out["counts"]))
+    fn = lib().orc_blackhole_swallow if unclaimed_only else lib().orc_blackhole_evaluate_swallow
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 11
+    fn.restype = None
+    fn(tree.h, C.byref(params), ns, _p(sinks), _p(ids), _p(_f64(hsml)), _p(sw),
+       _p(tree.mass), _p(pbh), _p(out["acc_mass"]), _p(out["acc_bhmass"]),
+       _p(out["acc_dustmass"]), _p(out["acc_momentum"]), _p(out["counts"]))
     out["mass"] = tree.mass
     return out
 

@@ -385,3 +385,303 @@ class SinkProblem:
         for k, v in {**self.par, **over}.items():
             setattr(p, k, v)
         return p
+
+
+# ------------------------------------------------------------------------------------------------
+# Inputs of the sink tests (tests/test_sink_cpu.py, tests/test_gpu_sink.py) on top of SinkProblem:
+# contested victims, chains of claims, mutual claims, the central object's boundaries and the branches
+# of the sinks' h iteration.  All of them are checked against tests/sink_ref.py (all pairs, written
+# from blackhole.c and density.c), whose density pass rides along as `sp.dens`.
+# ------------------------------------------------------------------------------------------------
+SINK_SWITCHES = [(1, 1), (0, 1), (0, 0)]       # (accretion_of_dust_only, accretion_density)
+SINK_CRIT_DENSITY = 1.0
+SINK_TRIES = 20
+
+
+def sink_over(dust_only, acc_density):
+    return dict(accretion_of_dust_only=dust_only, accretion_density=acc_density, CritDensity=SINK_CRIT_DENSITY)
+
+
+def sink_ref_par(sp, **over):
+    """the parameters of the passes for tests/sink_ref.py: any object with the members of ghip_bh_params"""
+    import types
+    return types.SimpleNamespace(**{**sp.par, **over})
+
+
+def sink_ref_density(sp):
+    import sink_ref
+    pr = sp.pr
+    return sink_ref.sink_density(pr.ic["pos"], pr.ic["mass"], pr.ic["type"], pr.velpred, pr.entropy, sp.sinks,
+                                 sp.hsml, pr.des_ngb, 1.5, pr.max_dev, pr.min_gas_hsml, pr.box, pr.periodic)
+
+
+def _sink_dist(sp, i):
+    pr = sp.pr
+    d = pr.ic["pos"][i][None, :] - pr.ic["pos"]
+    if pr.periodic:
+        d -= pr.box * np.round(d / pr.box)
+    return np.sqrt((d * d).sum(axis=1))
+
+
+def sink_ties(sp, dens, rel=1e-9):
+    """How many candidates lie within `rel` (relative) of a threshold at which a sink pass decides: r against
+    every h the iteration tried (gas), r against the final h and the three boundaries, e_tot against 0 (all
+    candidates of the marking pass), the gas density against CritDensity.  Mass and ID comparisons are exact by
+    construction.  An input with such a tie could be decided either way by a correctly rounded variant of the
+    same arithmetic, so the generators below reject it."""
+    pr = sp.pr
+    typ, mass, vel = pr.ic["type"], pr.ic["mass"], pr.ic["vel"]
+    ties = int((np.abs(sp.gas_density - SINK_CRIT_DENSITY) <= rel * SINK_CRIT_DENSITY).sum())
+    for a, i in enumerate(sp.sinks):
+        r = _sink_dist(sp, i)
+        for h in dens["h_tried"][a]:
+            ties += int((np.abs(r[typ == 0] - h) <= rel * h).sum())
+        h = dens["hsml"][i]
+        cand = ((typ == 0) | (typ == 2) | (typ == 5)) & (r < 1.001 * h) & (r > 0)
+        for b in (h, sp.par["InnerBoundary"], sp.par["SinkBoundary"], sp.par["SofteningBndry"]):
+            ties += int((np.abs(r[cand] - b) <= rel * b).sum())
+        kin = 0.5 * ((vel[cand] - vel[i]) ** 2).sum(axis=1)
+        pot = mass[i] / r[cand]
+        ties += int((np.abs(kin - pot) <= rel * (kin + pot)).sum()) if mass[i] > 0 else 0
+    return ties
+
+
+def _dm_mass(pr):
+    return float(pr.ic["mass"][pr.ic["type"] == 1][0])
+
+
+def _unit(rng):
+    v = rng.standard_normal(3)
+    return v / np.linalg.norm(v)
+
+
+def _finish(sp):
+    pr = sp.pr
+    sp.bh_mass = np.zeros(pr.n)
+    sp.bh_mass[sp.sinks] = 0.5 * pr.ic["mass"][sp.sinks]
+    pr.extent = O.domain_extent(pr.ic["pos"])
+    return sp
+
+
+def _sink_clump(periodic, seed):
+    """12 sinks: sink 0 the central object where SinkProblem put it; sinks 1-11 inside a cube of 1.2 spacings
+    at the corner of the box (periodic search spheres wrap), so that every one of them lies inside
+    SofteningBndry (2.4 spacings > the cube's diagonal) of every other: each claims all that are not heavier.
+    Masses 40, 40, 44 ... 72 DM masses and one 0, in a seeded order; IDs a seeded permutation (not monotone in
+    list order: "largest ID", "last claim" and "first claim" differ); every third grain 200 times faster
+    (unbound: refused); one sink in time bin 0 (no feedback)."""
+    sp = SinkProblem(ng=10, periodic=periodic, nsink=12, ndust=300, seed=seed)
+    pr = sp.pr
+    rng = np.random.default_rng(1000 + seed)
+    s, dm = pr.ic["spacing"], _dm_mass(pr)
+    cl = sp.sinks[1:]
+    pr.ic["pos"][cl] = 0.1 * s + 1.2 * s * rng.random((11, 3))
+    pr.ic["mass"][cl] = dm * rng.permutation(np.array([40., 40., 44., 48., 52., 56., 60., 64., 68., 72., 0.]))
+    sp.ids = rng.permutation(sp.ids)
+    # 40 of the 300 grains around the clump, so that grains are contested under every switch setting and
+    # fast ones come inside a boundary whether or not the box wraps
+    pr.ic["pos"][sp.dust[:40]] = 0.05 * s + 2.45 * s * rng.random((40, 3))
+    pr.ic["vel"][sp.dust[::3]] *= 200.0
+    pr.timebin[cl[3]] = 0
+    return _finish(sp)
+
+
+def _sink_pair(periodic, seed, at=None):
+    """two isolated sinks of equal mass, neither the central object, 1 spacing apart: inside SofteningBndry of
+    each other, `Mass <= mass` holds both ways -- each claims the other, and (blackhole.c:528-532) neither
+    swallows anything.  at: where the first of them goes (in box lengths; default: where SinkProblem put it)"""
+    sp = SinkProblem(ng=10, periodic=periodic, nsink=2, ndust=300, seed=seed)
+    pr = sp.pr
+    rng = np.random.default_rng(2000 + seed)
+    s, dm = pr.ic["spacing"], _dm_mass(pr)
+    if at is not None:
+        pr.ic["pos"][sp.sinks[0]] = pr.box * np.asarray(at, np.float64)
+    pr.ic["mass"][sp.sinks] = 40.0 * dm
+    sp.SMBHmass = sp.par["SMBHmass"] = 400.0 * dm
+    pr.ic["pos"][sp.sinks[1]] = np.mod(pr.ic["pos"][sp.sinks[0]] + 1.0 * s * _unit(rng), pr.box)
+    return _finish(sp)
+
+
+def _sink_central(periodic, seed):
+    """the central object with two light sinks: one at 1 spacing (inside InnerBoundary = 2: merged) and one at
+    2.1 spacings (outside InnerBoundary, inside SofteningBndry = 2.4: the central object must leave it alone,
+    any other sink would take it)"""
+    sp = SinkProblem(ng=10, periodic=periodic, nsink=3, ndust=300, seed=seed)
+    pr = sp.pr
+    rng = np.random.default_rng(3000 + seed)
+    s, dm = pr.ic["spacing"], _dm_mass(pr)
+    c = sp.sinks[0]
+    pr.ic["mass"][sp.sinks[1:]] = dm * np.array([40.0, 44.0])
+    pr.ic["pos"][sp.sinks[1]] = np.mod(pr.ic["pos"][c] + 1.0 * s * _unit(rng), pr.box)
+    pr.ic["pos"][sp.sinks[2]] = np.mod(pr.ic["pos"][c] + 2.1 * s * _unit(rng), pr.box)
+    sp.ids = rng.permutation(sp.ids)
+    return _finish(sp)
+
+
+SINK_HITER = ("tight", "minh", "clamp", "small", "large", "void")
+
+
+def _sink_hiter(variant):
+    """the stock problem with the sinks' h iteration (density.c:559-652) sent down its other branches:
+    tight   MaxNumNgbDeviation = 1e-9: bisection until (Right - Left) < 1e-3 Left ends it
+    minh    MinGasHsml = the median converged h: a sink with too many neighbours at h <= 1.01 MinGasHsml is accepted
+    clamp   MinGasHsml = 1.05 x the median converged h: the step h / 1.26 lands below it and is reset to it
+    small   first h x 0.2: growth by 1.26, then bisection
+    large   first h x 3: shrinking by 1.26, then bisection
+    void    one sink where the gas is thinnest, with no gas inside its first h (rho = 0 in that pass)"""
+    def build(periodic, seed):
+        sp = SinkProblem(ng=10, periodic=periodic, nsink=8, seed=seed)
+        pr = sp.pr
+        if variant == "tight":
+            pr.max_dev = 1e-9
+        elif variant in ("minh", "clamp"):
+            pr.min_gas_hsml = (1.0 if variant == "minh" else 1.05) * \
+                float(np.median(sink_ref_density(sp)["hsml"][sp.sinks]))
+        elif variant == "small":
+            sp.hsml[sp.sinks] *= 0.2
+        elif variant == "large":
+            sp.hsml[sp.sinks] *= 3.0
+        elif variant == "void":
+            rng = np.random.default_rng(4000 + seed)
+            pts = rng.random((4000, 3)) * pr.box
+            gas = pr.ic["pos"][:pr.ngas]
+            d = pts[:, None, :] - gas[None, :, :]
+            d -= pr.box * np.round(d / pr.box)
+            dmin = np.sqrt((d * d).sum(axis=2)).min(axis=1)
+            k = int(np.argmax(dmin))
+            pr.ic["pos"][sp.sinks[3]] = pts[k]
+            sp.hsml[sp.sinks[3]] = 0.8 * dmin[k]
+        else:
+            raise ValueError(variant)
+        return _finish(sp)
+    return build
+
+
+_SINK_BUILDERS = dict(clump=_sink_clump, pair=_sink_pair, central=_sink_central,
+                      **{"hiter-" + v: _sink_hiter(v) for v in SINK_HITER})
+_SINK_CACHE = {}
+
+
+def sink_case(name, periodic=1, seed0=5, **how):
+    """The input `name` ("clump", "pair", "central", "hiter-<variant>") from the first of the seeds seed0,
+    seed0 + 1, ... that has no candidate within 1e-9 of a decision threshold (sink_ties); fails loudly after
+    SINK_TRIES seeds.  `how`: further arguments of the input's builder.  sp.seed is the seed taken, sp.gas_density the gas densities the marking pass reads,
+    sp.dens the density pass of tests/sink_ref.py.  A fresh copy per call: the passes change masses."""
+    import copy
+    key = (name, periodic, seed0, repr(sorted(how.items())))
+    if key not in _SINK_CACHE:
+        for seed in range(seed0, seed0 + SINK_TRIES):
+            sp = _SINK_BUILDERS[name](periodic, seed, **how)
+            sp.case, sp.seed = name, seed
+            sp.gas_density = 0.5 + np.random.default_rng(3).random(sp.pr.ngas)
+            sp.dens = sink_ref_density(sp)
+            assert sp.dens["iterations"] >= 0, "%s: the reference's h iteration did not converge" % name
+            if sink_ties(sp, sp.dens) == 0:
+                _SINK_CACHE[key] = sp
+                break
+        else:
+            raise AssertionError("sink_case(%r): %d seeds from %d on all have a candidate within 1e-9 of a "
+                                 "decision threshold" % (name, SINK_TRIES, seed0))
+    return copy.deepcopy(_SINK_CACHE[key])
+
+
+_SINK_REF_CACHE = {}
+
+
+def sink_reference(name, periodic, dust_only, acc_density, **how):
+    """tests/sink_ref.py on the input `name` under one switch setting, computed once and shared (nobody
+    changes it): dict(par, over, sw, inj -- the marks under the project's rule; last, first -- the marks under
+    the two other rules; claims; swallow -- the swallow pass on `sw`)."""
+    import sink_ref
+    key = (name, periodic, dust_only, acc_density, repr(sorted(how.items())))
+    if key not in _SINK_REF_CACHE:
+        sp = sink_case(name, periodic, **how)
+        ic, pr, d = sp.pr.ic, sp.pr, sp.dens
+        over = sink_over(dust_only, acc_density)
+        par = sink_ref_par(sp, **over)
+        a = (ic["pos"], ic["vel"], ic["mass"], ic["type"], sp.ids, sp.sinks, d["hsml"])
+        ev = {rule: sink_ref.evaluate(*a, pr.timebin, sp.mdot, d["density"], sp.gas_density, par, rule=rule)
+              for rule in ("max", "last", "first")}
+        _SINK_REF_CACHE[key] = dict(
+            par=par, over=over, sw=ev["max"][0], inj=ev["max"][1], last=ev["last"][0], first=ev["first"][0],
+            claims=sink_ref.claims(ic["pos"], ic["vel"], ic["mass"], ic["type"], sp.sinks, d["hsml"],
+                                   sp.gas_density, par),
+            swallow=sink_ref.swallow(*a, ev["max"][0], sp.bh_mass, par))
+    return _SINK_REF_CACHE[key]
+
+
+def check_sink_passes(sp, ref, dens=None, marks=None, swallowed=None, mass=None):
+    """One side's results (the oracle's or the device's) of the three passes on the input `sp` against
+    tests/sink_ref.py (`ref` = sink_reference(...)), with the tolerances of test_sink_passes_parity:
+    marks, counts, iteration counts and masses exact, sums to summation order.  dens: dict(hsml, numngb,
+    density, entropy, gasvel [nsink], iterations); marks: (SwallowID [n], injected [ngas]); swallowed:
+    dict(counts, acc_mass, acc_bhmass, acc_dustmass, acc_momentum, bh_mass [nsink]); mass [n]: the masses after
+    the swallow pass.  Returns the measured errors (the caller prints them).
+
+    Measured worst cases over all inputs (MI355X, one device and 3 / 8 shards; the oracle's are of the same
+    size): hsml 0, numngb 1.4e-14 absolute, density 2.7e-16, entropy 3.9e-16, gasvel 3.6e-16, injected energy
+    3.9e-16 of the largest, accreted mass 2.7e-17, accreted momentum 1.9e-16, total mass 1.6e-16 -- the order
+    of at most 12 atomic adds per particle and of the wave reductions, three to four decades inside the bounds."""
+    pr, rd, sk = sp.pr, sp.dens, sp.sinks
+    err = {}
+    if dens is not None:
+        assert dens["iterations"] == rd["iterations"] >= 1
+        err["hsml"] = relerr(dens["hsml"], rd["hsml"][sk])
+        err["numngb"] = float(np.abs(dens["numngb"] - rd["numngb"]).max())
+        err["density"], err["entropy"] = relerr(dens["density"], rd["density"]), relerr(dens["entropy"], rd["entropy"])
+        err["gasvel"] = float(np.abs(dens["gasvel"] - rd["gasvel"]).max() / np.abs(rd["gasvel"]).max())
+        assert err["hsml"] < 1e-13 and err["numngb"] < 1e-10, err
+        assert err["density"] < 1e-12 and err["entropy"] < 1e-12 and err["gasvel"] < 1e-12, err
+    if marks is not None:
+        sw, inj = marks
+        assert np.array_equal(sw, ref["sw"]), "SwallowID differs at %s" % np.where(sw != ref["sw"])[0][:10]
+        top = np.abs(ref["inj"]).max()
+        assert top > 0
+        err["injected"] = float(np.abs(inj - ref["inj"]).max() / top)
+        assert err["injected"] <= 1e-12, err
+    if swallowed is not None:
+        rs = ref["swallow"]
+        assert np.array_equal(swallowed["counts"], rs["counts"]), (swallowed["counts"], rs["counts"])
+        for k in ("acc_mass", "acc_bhmass", "acc_dustmass", "acc_momentum"):
+            top = max(np.abs(rs[k]).max(), 1e-300)
+            err[k] = float(np.abs(swallowed[k] - rs[k]).max() / top)
+            assert err[k] <= 1e-13, (k, err)
+            # a sink that was itself claimed is passed over (blackhole.c:528-532): zero sums, exactly
+            assert not np.any(np.asarray(swallowed[k])[rs["skipped"]]), k
+        # BH_Mass of a sink is zeroed only if it really was swallowed (:1276), not if it was merely marked
+        assert np.array_equal(swallowed["bh_mass"], rs["bh_mass"][sk])
+        assert np.array_equal(swallowed["bh_mass"] == 0, rs["swallowed"][sk] | (sp.bh_mass[sk] == 0))
+    if mass is not None:
+        rs = ref["swallow"]
+        assert np.array_equal(mass, rs["mass"]), "masses differ at %s" % np.where(mass != rs["mass"])[0][:10]
+        if swallowed is not None:
+            before = pr.ic["mass"].sum()
+            err["total_mass"] = float(abs(swallowed["acc_mass"].sum() + mass.sum() - before) / before)
+            assert err["total_mass"] < 1e-14, err
+    return err
+
+
+# every input under the settings it is run with: (name, periodic, (accretion_of_dust_only, accretion_density))
+SINK_CASES = [("clump", p, s) for p in (0, 1) for s in SINK_SWITCHES] + \
+             [("pair", 1, s) for s in SINK_SWITCHES] + [("central", 1, s) for s in SINK_SWITCHES] + \
+             [("hiter-" + v, 1, (0, 0)) for v in SINK_HITER]
+# where the pair goes in the tests on shards: cut into 3 and into 8 key ranges, each of the two sinks has
+# victims of its own on other shards than itself (asserted there)
+SINK_PAIR_AT = (0.72, 0.53, 0.31)
+
+
+def oracle_sink_passes(sp, over):
+    """the three passes on the oracle's tree -> (dens, marks, swallowed, mass) as check_sink_passes takes them"""
+    pr = sp.pr
+    ic = pr.ic
+    T = O.Tree(ic["pos"], ic["vel"], ic["mass"].copy(), ic["type"], pr.force_soft, hsml=sp.hsml,
+               extent=pr.extent)
+    od = O.sink_density(T, pr.o_dens(), 1.5, sp.sinks, pr.velpred, pr.entropy, sp.hsml)
+    hs = od["hsml"]
+    op = sp.params(O.BhParams, **over)
+    sw, inj = O.blackhole_evaluate(T, op, sp.sinks, sp.ids, hs, pr.timebin, sp.mdot, od["density"],
+                                   sp.gas_density, np.zeros(pr.n, np.uint32), np.zeros(pr.ngas))
+    oo = O.blackhole_swallow(T, op, sp.sinks, sp.ids, hs, sw, sp.bh_mass, unclaimed_only=True)
+    oo["bh_mass"] = oo["bh_mass"][sp.sinks]
+    od["hsml"] = hs[sp.sinks]
+    return od, (sw, inj), oo, T.mass

@@ -168,7 +168,7 @@ def main():
                         hsml=hs, extent=pr.extent)
             osw, oinj = O.blackhole_evaluate(T2, op, sp.sinks, sp.ids, hs, pr.timebin, sp.mdot, osk["density"],
                                              od["density"][:ng], np.zeros(n, np.uint32), np.zeros(ng))
-            oo = O.blackhole_swallow(T2, op, sp.sinks, sp.ids, hs, osw, sp.bh_mass)
+            oo = O.blackhole_swallow(T2, op, sp.sinks, sp.ids, hs, osw, sp.bh_mass, unclaimed_only=True)
             out["marks_equal"] = bool(np.array_equal(Pg["SwallowID"], osw))
             out["victims"] = int((osw > 0).sum())
             out["rel_injected"] = float(np.abs(Sg["Injected_BH_Energy"] - oinj).max() /

@@ -187,7 +187,7 @@ def test_shipped_bundle_records_through_the_reference_named_drivers():
                     extent=pr.extent)
         osw, oinj = O.blackhole_evaluate(T2, op, sp.sinks, sp.ids, hs, pr.timebin, sp.mdot, osk["density"],
                                          od["density"][:ng], np.zeros(n, np.uint32), np.zeros(ng))
-        oo = O.blackhole_swallow(T2, op, sp.sinks, sp.ids, hs, osw, sp.bh_mass)
+        oo = O.blackhole_swallow(T2, op, sp.sinks, sp.ids, hs, osw, sp.bh_mass, unclaimed_only=True)
         L.blackhole_accretion_neighbour_passes()
         assert host.endrun_codes == [], L.gadget_force_last_error()
         assert np.array_equal(P["SwallowID"], osw) and (osw > 0).sum() > 3
@@ -214,6 +214,54 @@ def test_shipped_bundle_records_through_the_reference_named_drivers():
         assert host.endrun_codes == [], L.gadget_force_last_error()
         for name in ("Pos", "Vel", "ID", "Type", "rest"):
             assert np.array_equal(P[name], keep[name]), name
+    finally:
+        host.close()
+
+
+@pytest.mark.parametrize("name", ["pair", "clump"])
+def test_claimed_sinks_swallow_nothing_through_the_reference_named_driver(name):
+    """blackhole_accretion_neighbour_passes() on 536-byte records of the two inputs in which sinks claim each
+    other (tests/common.py: `pair`, the mutual claim; `clump`, the chain C -> B -> A), accretion of gas on:
+    P[].SwallowID and P[].Mass afterwards are those of blackhole.c restated over all pairs
+    (tests/sink_ref.py), where the swallow pass runs only for sinks with SwallowID == 0 (blackhole.c:528-532).
+    The sinks' Hsml and BH_Density and the gas Density are put into the records as density() leaves them."""
+    from common import check_sink_passes, sink_case, sink_reference
+    B = bindings()
+    H = importlib.import_module("gadget-leicester_amd.hostapi")
+    sp = sink_case(name, 1)
+    ref = sink_reference(name, 1, 0, 0)
+    pr, sk, rs = sp.pr, sp.sinks, ref["swallow"]
+    lay, bh = bundle_layouts(B, H)
+    P, S = bundle_records(sp)
+    P["Hsml"] = sp.dens["hsml"]
+    P["BH_Density"][sk] = sp.dens["density"]
+    S["Density"] = sp.gas_density
+    keep = P.copy()
+    host = H.Host(periodic=1, black_holes=1, dust=1, accretion_of_dust_only=0, accretion_density=0)
+    try:
+        host.bind_records(P, S, lay, bh)
+        set_all(host, sp, pr.force_soft[0] / 2.8)
+        host.All.SofteningBndry = sp.par["SofteningBndry"]      # (after set_softenings(): the table keeps eps)
+        host.set_active(None)
+        host.domain()
+        L = host.L
+        L.blackhole_accretion_neighbour_passes()
+        assert host.endrun_codes == [], L.gadget_force_last_error()
+        got = dict(counts=np.array([C.c_int.in_dll(L, k).value for k in
+                                    ("N_gas_swallowed", "N_BH_swallowed", "N_dust_swallowed")]),
+                   acc_mass=P["BH_accreted_Mass"][sk], acc_bhmass=P["BH_accreted_BHMass"][sk],
+                   acc_dustmass=P["BH_accreted_DustMass"][sk], acc_momentum=P["BH_accreted_momentum"][sk],
+                   bh_mass=P["BH_Mass"][sk])
+        err = check_sink_passes(sp, ref, None, (P["SwallowID"], S["Injected_BH_Energy"]), got, P["Mass"])
+        print(name, err)
+        claimed = ref["sw"][sk] > 0
+        assert claimed.sum() >= 2 and rs["skipped"][claimed].all()
+        kept = (ref["sw"] > 0) & ~rs["swallowed"]               # the victims of claimed sinks
+        assert kept.sum() >= 6 and np.array_equal(P["Mass"][kept], keep["Mass"][kept])
+        if name == "pair":
+            assert not got["counts"].any() and np.array_equal(P["Mass"], keep["Mass"])
+        for field in ("Pos", "Vel", "ID", "Type", "rest"):
+            assert np.array_equal(P[field], keep[field]), field
     finally:
         host.close()
 

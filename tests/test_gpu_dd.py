@@ -284,7 +284,7 @@ def test_config_c5_256cubed_with_sinks_as_eight_logical_shards():
         assert np.array_equal(gsw, osw) and (osw > 0).sum() > 300
         assert np.abs(ginj - oinj).max() <= 1e-11 * np.abs(oinj).max()
         oo = O.blackhole_swallow(T, sp.params(O.BhParams, **par), sp.sinks, sp.ids, od["hsml"], osw,
-                                 sp.bh_mass)
+                                 sp.bh_mass, unclaimed_only=True)
         res = run(B.DD_BH_SWALLOW, lambda r: B.dd_sink_args(
             where[r][0], sink_ids=sp.ids[sp.sinks][where[r][1]], bh=gp,
             sink_bh_mass=sp.bh_mass[sp.sinks][where[r][1]]))

@@ -1832,7 +1832,7 @@ def test_config_c5_size_256cubed_one_step_sampled():
     assert np.array_equal(gsw, osw) and (osw > 0).sum() > 300
     assert np.abs(ginj - oinj).max() <= 1e-11 * np.abs(oinj).max()
     oo = O.blackhole_swallow(T, sp.params(O.BhParams, **par), sp.sinks, sp.ids, od["hsml"], osw,
-                             sp.bh_mass)
+                             sp.bh_mass, unclaimed_only=True)
     go = fp.blackhole_swallow(sp.params(B.BhParams, **par), sp.sinks, sp.ids[sp.sinks],
                               sp.bh_mass[sp.sinks])
     assert np.array_equal(go["counts"], oo["counts"])
