@@ -231,6 +231,39 @@ class SyncPoint(C.Structure):
                     else int(getattr(self, k))) for k, _ in self._fields_}
 
 
+class FofParams(C.Structure):
+    """ghip_fof_params (fof_fof, fof.c:94-333): LinkL <= 0 asks for the LINKLENGTH rule on the device"""
+    _fields_ = [("LinkL", C.c_double), ("linklength", C.c_double), ("rhodm", C.c_double),
+                ("primary_types", C.c_int), ("secondary_types", C.c_int), ("group_min_len", C.c_int),
+                ("BoxSize", C.c_double), ("periodic", C.c_int), ("MaxIter", C.c_int)]
+
+
+class FofResult(C.Structure):
+    """ghip_fof_result"""
+    _fields_ = [("Ngroups", C.c_int), ("Nids", C.c_longlong), ("largest", C.c_int), ("LinkL", C.c_double),
+                ("nearest_iterations", C.c_int)]
+
+
+class FofGroup(C.Structure):
+    """ghip_fof_group: the members of struct group_properties (fof.h:26-60) the resident state can fill"""
+    _fields_ = [("Len", C.c_int), ("Offset", C.c_int), ("MinID", C.c_int), ("GrNr", C.c_int),
+                ("LenType", C.c_int * 6), ("MassType", C.c_double * 6), ("Mass", C.c_double),
+                ("CM", C.c_double * 3), ("Vel", C.c_double * 3), ("MaxDens", C.c_double),
+                ("index_maxdens", C.c_int)]
+
+
+# numpy view of FofGroup[] (same offsets, trailing padding included)
+FOF_GROUP_DTYPE = np.dtype({"names": ["Len", "Offset", "MinID", "GrNr", "LenType", "MassType", "Mass", "CM", "Vel",
+                                      "MaxDens", "index_maxdens"],
+                            "formats": ["<i4", "<i4", "<i4", "<i4", ("<i4", 6), ("<f8", 6), "<f8", ("<f8", 3),
+                                        ("<f8", 3), "<f8", "<i4"],
+                            "offsets": [FofGroup.Len.offset, FofGroup.Offset.offset, FofGroup.MinID.offset,
+                                        FofGroup.GrNr.offset, FofGroup.LenType.offset, FofGroup.MassType.offset,
+                                        FofGroup.Mass.offset, FofGroup.CM.offset, FofGroup.Vel.offset,
+                                        FofGroup.MaxDens.offset, FofGroup.index_maxdens.offset],
+                            "itemsize": C.sizeof(FofGroup)})
+
+
 class GlobalParams(C.Structure):
     """ghip_global_params (compute_global_quantities_of_system, global.c:18-238)"""
     _fields_ = [("Ti_Current", C.c_int), ("Timebase_interval", C.c_double),
@@ -355,7 +388,9 @@ EXPORTS = [
     "ghip_set_viscosity", "ghip_visc_set_alpha", "ghip_visc_get", "ghip_visc_derive", "ghip_visc_params_size",
     "ghip_set_rnd_table", "ghip_tree_max_level", "ghip_dd_set_guests", "ghip_dd_guest_counts",
     "ghip_debug_prim",
-    "ghip_find_next_sync_point", "ghip_get_active", "ghip_find_extent", "ghip_dd_get_sync_point"]
+    "ghip_find_next_sync_point", "ghip_get_active", "ghip_find_extent", "ghip_dd_get_sync_point",
+    "ghip_fof", "ghip_fof_get_groups", "ghip_fof_get_ids", "ghip_fof_get_labels", "ghip_fof_params_size",
+    "ghip_fof_group_size", "ghip_fof_get_timing"]
 
 
 def lib():
@@ -500,6 +535,16 @@ def lib():
         L.ghip_get_active.argtypes = [vp, vp, C.POINTER(C.c_int)]
         L.ghip_find_extent.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
         L.ghip_dd_get_sync_point.argtypes = [vp, C.POINTER(SyncPoint)]
+        L.ghip_fof.argtypes = [vp, C.POINTER(FofParams), C.POINTER(FofResult)]
+        L.ghip_fof_get_groups.argtypes = [vp, vp]
+        L.ghip_fof_get_ids.argtypes = [vp, vp]
+        L.ghip_fof_get_labels.argtypes = [vp, vp, vp]
+        L.ghip_fof_get_timing.argtypes = [vp, vp]
+        for fn, cls in ((L.ghip_fof_params_size, FofParams), (L.ghip_fof_group_size, FofGroup)):
+            fn.argtypes = []
+            fn.restype = C.c_size_t
+            if fn() != C.sizeof(cls):
+                raise RuntimeError("%s: %d bytes here, %d in libghip.so" % (cls.__name__, C.sizeof(cls), fn()))
         _LIB = L
     return _LIB
 
@@ -601,6 +646,42 @@ class ForcePath:
         p, out = SyncParams(int(ti_current), int(ti_nextoutput)), SyncPoint()
         self._chk(self.L.ghip_find_next_sync_point(self.h, C.byref(p), C.byref(out)))
         return out
+
+    def fof(self, link_length=0.0, primary_types=2, secondary_types=0, group_min_len=32, boxsize=0.0,
+            periodic=False, max_iter=150, linklength=0.2, rhodm=0.0):
+        """ghip_fof: friends-of-friends groups of the resident state on the gravity tree in place (fof_fof,
+        fof.c:94-333) -> FofResult.  link_length <= 0: the LINKLENGTH rule, linklength * (mass / number of the
+        primaries / rhodm)^(1/3), on the device.  The catalogue: fof_groups(), fof_ids(), fof_labels()."""
+        p = FofParams(float(link_length), float(linklength), float(rhodm), int(primary_types), int(secondary_types),
+                      int(group_min_len), float(boxsize), int(bool(periodic)), int(max_iter))
+        out = FofResult()
+        self._chk(self.L.ghip_fof(self.h, C.byref(p), C.byref(out)))
+        self._fof = (out.Ngroups, out.Nids)
+        return out
+
+    def fof_groups(self):
+        """ghip_fof_get_groups -> structured array (FOF_GROUP_DTYPE) in GrNr order"""
+        g = np.zeros(self._fof[0], FOF_GROUP_DTYPE)
+        self._chk(self.L.ghip_fof_get_groups(self.h, _ptr(g) if len(g) else None))
+        return g
+
+    def fof_ids(self):
+        """ghip_fof_get_ids -> int32[Nids], sorted by (GrNr, ID)"""
+        ids = np.zeros(self._fof[1], np.int32)
+        self._chk(self.L.ghip_fof_get_ids(self.h, _ptr(ids) if len(ids) else None))
+        return ids
+
+    def fof_labels(self):
+        """ghip_fof_get_labels -> (MinID of each particle's group, its GrNr or -1), int32[n] each"""
+        minid, grnr = np.zeros(self.n, np.int32), np.zeros(self.n, np.int32)
+        self._chk(self.L.ghip_fof_get_labels(self.h, _ptr(minid), _ptr(grnr)))
+        return minid, grnr
+
+    def fof_timing(self):
+        """device milliseconds of the last fof(): linking, flattening and labels, secondary rounds, catalogue"""
+        ms = np.zeros(4)
+        self._chk(self.L.ghip_fof_get_timing(self.h, _ptr(ms)))
+        return ms
 
     def get_active(self):
         """ghip_get_active: the particle indices of the list in force (int32; 0 .. n-1 when all are active)"""

@@ -401,6 +401,31 @@ struct PmMesh
   } open;
 };
 
+// friends-of-friends groups (ghip_fof.hip): work arrays of the last call and its catalogue.  s* arrays are in
+// the gravity tree's sorted order, the others in host order or per group.
+struct FofState
+{
+  DevBuf sid, sflag, parent, rootmin, slabel;   // i32[n]: IDs, kind (1 primary, 2 secondary), union-find, min ID per root, labels
+  DevBuf plist, slist;                          // i32: sorted indices of the primaries / the secondaries
+  DevBuf hcur;                                  // f64[nsec]: search radius of each secondary
+  DevBuf words;                                 // FofWords: counters and the link length
+  DevBuf part;                                  // f64: block sums of the LINKLENGTH rule
+  DevBuf label, key, skey, val, sval;           // i32[n] labels (host order); (label, ID) keys and members, sorted
+  DevBuf head, segof, segstart, gkey, gskey, gval, gorder, glen, goff, grnr;   // segments = candidate groups
+  DevBuf pgrnr, ids;                            // i32[n] GrNr per particle; i32[Nids] the ID list
+  DevBuf groups;                                // ghip_fof_group[Ngroups]
+  int n = -1, ngroups = 0;                      // particle count of the last successful call (-1: none)
+  long long nids = 0;
+  double ms[4] = {0, 0, 0, 0};
+  hipEvent_t ev[5] = {};
+  ~FofState()
+  {
+    for(int i = 0; i < 5; i++)
+      if(ev[i])
+        (void) hipEventDestroy(ev[i]);
+  }
+};
+
 // The Newtonian walk of a Newton + Ewald pair is held to W one-wavefront workgroups per SIMD (4 W per
 // CU) by unused dynamic LDS: the largest allocation of which 4 W fit into a CU's 160 KB, a whole
 // number of 2 KB allocation granules.  W = 4: 10 KB (16 per CU), W = 5: 8 KB (20), W = 6: 6 KB (24 fit;
@@ -595,6 +620,7 @@ struct ghip_ctx
   double potcorr_box = 0;
   DevBuf srpot;                    // float[NTAB]: shortrange_table_potential (forcetree.c:4201)
   DevBuf gq_work;                  // partial sums, kick tables and photon momenta of ghip_global_quantities
+  FofState fof;                    // ghip_fof (ghip_fof.hip)
 };
 #define GHIP_NEV 16
 

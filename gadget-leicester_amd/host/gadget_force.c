@@ -3014,6 +3014,216 @@ void compute_potential(void)
   TreeOnDevice = 0;
 }
 
+/* ------------------------------------------------------------------------------------------
+ * fof_fof() (fof.c:94-333) and fof_make_black_holes() (fof.c:1783-1886)
+ * ---------------------------------------------------------------------------------------- */
+int Ngroups = 0, TotNgroups = 0;
+long long TotNids = 0;
+struct gadget_force_group *Group = NULL;
+int Stars_converted = 0;
+static struct gadget_force_fof_layout FofLay;
+static int FofBound = 0, FofSeeds = 0;
+static const char *FofAll = NULL;
+
+void gadget_force_bind_fof(void *host_All, const struct gadget_force_fof_layout *lay)
+{
+  FofBound = lay != NULL;
+  if(lay)
+    FofLay = *lay;
+  FofAll = lay ? (const char *) host_All : NULL;
+}
+
+int gadget_force_fof_layout_count(void)
+{
+  return (int) (sizeof(struct gadget_force_fof_layout) / sizeof(int));
+}
+
+int gadget_force_fof_new_seeds(void)
+{
+  return FofSeeds;
+}
+
+static double fof_all(int off, double own)
+{
+  return off >= 0 && FofAll ? *(const double *) (FofAll + off) : own;
+}
+
+static int fof_compare_group_minid(const void *a, const void *b)   /* fof_compare_Group_MinID, fof.c:2368-2377 */
+{
+  const int x = ((const struct gadget_force_group *) a)->MinID, y = ((const struct gadget_force_group *) b)->MinID;
+  return x < y ? -1 : (x > y ? +1 : 0);
+}
+
+void fof_fof(int num)
+{
+  const char *who = "fof_fof";
+  /* a call that ends early leaves no catalogue of an earlier one behind */
+  FofSeeds = 0;
+  Ngroups = TotNgroups = 0;
+  TotNids = 0;
+  free(Group);
+  Group = NULL;
+  if(need_ctx(who))
+    return;
+  if(NTask > 1)
+    {
+      refuse(90016, "%s: NTask = %d: groups that span ranks are not built (they need an exchange of labels "
+                    "between the shards); run the group finder on a single rank", who, NTask);
+      return;
+    }
+  if(!FofBound)
+    {
+      potential_missing(who, "bind the parameters with gadget_force_bind_fof() first");
+      return;
+    }
+  gadget_force_flush();
+  all_pull();
+  const double omega0 = fof_all(FofLay.a_omega0, All.Omega0), omegab = fof_all(FofLay.a_omega_baryon, All.OmegaBaryon);
+  const double hubble = fof_all(FofLay.a_hubble, All.Hubble), G = fof_all(FofLay.a_g, All.G);
+  const double time = fof_all(FofLay.a_time, All.Time);
+  if(NumPart <= 0)
+    return;
+  /* fof.c:108-110, 149-150: the tree of the current records */
+  if(ensure_tree_split(0))
+    return;
+  int *ids = (int *) scratch((size_t) NumPart * sizeof(int));
+  if(!ids)
+    return;
+  for(int i = 0; i < NumPart; i++)
+    ids[i] = BhLay.p_id >= 0 ? (int) *(unsigned int *) (prec(i) + BhLay.p_id) : i;
+  int rc = chk(ghip_set_field(Ctx, GHIP_F_ID, ids), "ghip_set_field");
+  if(rc)
+    {
+      free(ids);
+      return;
+    }
+  ghip_fof_params fp;
+  memset(&fp, 0, sizeof(fp));
+  fp.LinkL = 0;   /* fof.c:112-124 on the device */
+  fp.linklength = 0.2;   /* LINKLENGTH, allvars.h:141 */
+  fp.rhodm = (omega0 - omegab) * 3 * hubble * hubble / (8 * M_PI * G);
+  fp.primary_types = FofLay.primary_types;
+  fp.secondary_types = FofLay.secondary_types;
+  fp.group_min_len = FofLay.group_min_len > 0 ? FofLay.group_min_len : 32;
+  fp.BoxSize = All.BoxSize;
+  fp.periodic = Cfg.periodic;
+  fp.MaxIter = 150;   /* MAXITER, allvars.h:139 */
+  ghip_fof_result res;
+  rc = ghip_fof(Ctx, &fp, &res);
+  if(rc == GHIP_ENOCONV)
+    {
+      snprintf(ErrBuf, sizeof(ErrBuf), "%s: %s", who, ghip_last_error(Ctx));
+      fprintf(stderr, "gadget_force: %s\n", ErrBuf);
+      free(ids);
+      endrun(1159);   /* fof.c:1651 */
+      return;
+    }
+  if(chk(rc, "ghip_fof"))
+    {
+      free(ids);
+      return;
+    }
+  const int ng = res.Ngroups;
+  ghip_fof_group *dg = (ghip_fof_group *) scratch((size_t) (ng > 0 ? ng : 1) * sizeof(ghip_fof_group));
+  int *grnr = (int *) scratch((size_t) NumPart * sizeof(int));
+  struct gadget_force_group *gr =
+    (struct gadget_force_group *) calloc((size_t) (ng > 0 ? ng : 1), sizeof(struct gadget_force_group));
+  if(!dg || !grnr || !gr || chk(ghip_fof_get_groups(Ctx, dg), "ghip_fof_get_groups") ||
+     chk(ghip_fof_get_labels(Ctx, NULL, grnr), "ghip_fof_get_labels"))
+    {
+      free(ids);
+      free(dg);
+      free(grnr);
+      free(gr);
+      return;
+    }
+  const int off_bhm = FofLay.p_bh_mass >= 0 ? FofLay.p_bh_mass : BhLay.p_bh_mass;
+  const int off_bhd = FofLay.p_bh_mdot >= 0 ? FofLay.p_bh_mdot : BhLay.p_bh_mdot;
+  for(int g = 0; g < ng; g++)
+    {
+      struct gadget_force_group *o = gr + g;
+      o->Len = dg[g].Len;
+      o->Offset = dg[g].Offset;
+      o->MinID = dg[g].MinID;
+      o->MinIDTask = ThisTask;
+      o->GrNr = dg[g].GrNr;
+      for(int k = 0; k < 6; k++)
+        {
+          o->LenType[k] = dg[g].LenType[k];
+          o->MassType[k] = dg[g].MassType[k];
+        }
+      o->Mass = dg[g].Mass;
+      for(int k = 0; k < 3; k++)
+        {
+          o->CM[k] = dg[g].CM[k];
+          o->Vel[k] = dg[g].Vel[k];
+        }
+      o->MaxDens = dg[g].MaxDens;
+      o->index_maxdens = dg[g].index_maxdens;
+      o->task_maxdens = dg[g].index_maxdens >= 0 ? ThisTask : -1;
+    }
+  /* what only the records hold (fof.c:945-949), and FirstPos: in index order */
+  for(int i = 0; i < NumPart; i++)
+    {
+      const int g = grnr[i];
+      if(g < 0 || g >= ng)
+        continue;
+      if(ids[i] == gr[g].MinID)
+        for(int k = 0; k < 3; k++)
+          gr[g].FirstPos[k] = PF64(i, Lay.p_pos)[k];
+      if(p_type(i) == 5)
+        {
+          if(off_bhm >= 0)
+            gr[g].BH_Mass += *PF64(i, off_bhm);
+          if(off_bhd >= 0)
+            gr[g].BH_Mdot += *PF64(i, off_bhd);
+        }
+    }
+  free(ids);
+  free(dg);
+  free(grnr);
+  Ngroups = TotNgroups = ng;
+  TotNids = res.Nids;
+  Group = gr;
+  if(num < 0)
+    {
+      /* fof_make_black_holes(), fof.c:1783-1886, in GrNr order */
+      const double mt1 = fof_all(FofLay.a_mass_table_1, 0.0);
+      const double massDMpart = mt1 > 0 ? mt1 : fof_all(FofLay.a_mass_dm_part, 0.0);
+      const double minmass = fof_all(FofLay.a_min_fof_mass_for_new_seed, 0.0);
+      const double seed = fof_all(FofLay.a_seed_black_hole_mass, 0.0);
+      int made = 0;
+      for(int g = 0; g < ng; g++)
+        if(gr[g].LenType[1] * massDMpart >= (omega0 - omegab) / omega0 * minmass)
+          if(gr[g].LenType[5] == 0 && gr[g].index_maxdens >= 0)
+            {
+              const int i = gr[g].index_maxdens;
+              if(i >= NumPart || p_type(i) != 0)
+                {
+                  refuse(7772, "%s: the densest gas member %d of group %d is not a gas particle", who, i, g);
+                  return;
+                }
+              *(short *) (prec(i) + Lay.p_type) = 5;   /* make it a black hole particle */
+              if(FofLay.p_stellar_age >= 0)
+                *PF64(i, FofLay.p_stellar_age) = time;
+              if(off_bhm >= 0)
+                *PF64(i, off_bhm) = seed;
+              if(off_bhd >= 0)
+                *PF64(i, off_bhd) = 0;
+              made++;
+            }
+      Stars_converted += made;
+      FofSeeds = made;
+      if(made)
+        {
+          /* the device's records are behind the host's now: the next driver uploads them again */
+          DeviceFresh = 0;
+          TreeOnDevice = 0;
+        }
+    }
+  qsort(Group, (size_t) ng, sizeof(struct gadget_force_group), fof_compare_group_minid);   /* fof.c:1117 */
+}
+
 static void sys_put(int off, const double *v, int count)
 {
   if(off >= 0)

@@ -130,6 +130,25 @@ class PotentialLayout(C.Structure):
         [("rad_fac", C.c_double)]
 
 
+class FofLayout(C.Structure):
+    """struct gadget_force_fof_layout: byte offsets of the doubles fof_fof reads in the host's All (-1: the mirror's
+    own member, or 0 where it has none), the link type masks and the minimum length as values, byte offsets of
+    P[].BH_Mass / BH_Mdot / StellarAge in the bound records (-1: absent)"""
+    _fields_ = [(k, C.c_int) for k in (
+        "a_omega0", "a_omega_baryon", "a_hubble", "a_g", "a_time", "a_min_fof_mass_for_new_seed",
+        "a_seed_black_hole_mass", "a_mass_table_1", "a_mass_dm_part", "primary_types", "secondary_types",
+        "group_min_len", "p_bh_mass", "p_bh_mdot", "p_stellar_age")]
+
+
+class HostGroup(C.Structure):
+    """struct gadget_force_group: struct group_properties of fof.h:26-47 (-DSFR -DBLACK_HOLES)"""
+    _fields_ = [("Len", C.c_int), ("Offset", C.c_int), ("MinID", C.c_int), ("MinIDTask", C.c_int),
+                ("GrNr", C.c_int), ("LenType", C.c_int * 6), ("MassType", C.c_double * 6), ("Mass", C.c_double),
+                ("CM", C.c_double * 3), ("Vel", C.c_double * 3), ("FirstPos", C.c_double * 3), ("Sfr", C.c_double),
+                ("BH_Mass", C.c_double), ("BH_Mdot", C.c_double), ("MaxDens", C.c_double),
+                ("index_maxdens", C.c_int), ("task_maxdens", C.c_int)]
+
+
 class TopNode(C.Structure):
     """struct topnode_data, allvars.h:437-447"""
     _fields_ = [("Size", C.c_ulonglong), ("StartKey", C.c_ulonglong), ("Count", C.c_longlong),
@@ -187,7 +206,9 @@ EXPORTS = ["gadget_force_bind_all", "gadget_force_all_layout_count",
            "gadget_force_set_allgather", "ThisTask", "NTask", "gadget_force_flush",
            "gadget_force_bind_dust", "dust_density", "dust_drag", "gadget_force_bind_integration",
            "gadget_force_bind_potential", "compute_potential", "compute_global_quantities_of_system",
-           "gadget_force_bind_viscosity", "gadget_force_bind_rndtable", "gadget_force_bind_dust_model"]
+           "gadget_force_bind_viscosity", "gadget_force_bind_rndtable", "gadget_force_bind_dust_model",
+           "gadget_force_bind_fof", "gadget_force_fof_layout_count", "gadget_force_fof_new_seeds", "fof_fof",
+           "Ngroups", "TotNgroups", "TotNids", "Group", "Stars_converted"]
 
 _LIB = None
 
@@ -250,6 +271,10 @@ def lib():
         L.gadget_force_bind_potential.restype = None
         L.compute_potential.restype = None
         L.compute_global_quantities_of_system.restype = None
+        L.gadget_force_bind_fof.argtypes = [C.c_void_p, C.c_void_p]
+        L.gadget_force_bind_fof.restype = None
+        L.fof_fof.argtypes = [C.c_int]
+        L.fof_fof.restype = None
         _LIB = L
     return _LIB
 
@@ -374,6 +399,31 @@ class Host:
         self.L.gadget_force_bind_potential(None if sysstate is None else C.c_void_p(sysstate.ctypes.data),
                                            C.cast(C.byref(lay), C.c_void_p))
 
+    def bind_fof(self, host_all, lay):
+        """gadget_force_bind_fof: `host_all` as for bind_dust (the doubles the table's a_* name), `lay` a
+        FofLayout; None unbinds"""
+        if lay is None:
+            self.L.gadget_force_bind_fof(None, None)
+            self._fof = None
+            return
+        assert self.L.gadget_force_fof_layout_count() == len(FofLayout._fields_)
+        self._fof = (host_all, lay)             # keep alive
+        self.L.gadget_force_bind_fof(None if host_all is None else C.c_void_p(host_all.ctypes.data),
+                                     C.cast(C.byref(lay), C.c_void_p))
+
+    def fof_fof(self, num):
+        """fof_fof(num): the catalogue into Ngroups / TotNgroups / TotNids / Group[]; num < 0 also makes the new
+        sink seeds in the bound records -> the groups as a list of HostGroup copies (sorted by MinID)"""
+        self.L.fof_fof(int(num))
+        ng = self._geti("Ngroups")
+        ptr = C.POINTER(HostGroup).in_dll(self.L, "Group")
+        out = []
+        for k in range(ng if ptr else 0):
+            g = HostGroup()
+            C.memmove(C.byref(g), C.byref(ptr[k]), C.sizeof(HostGroup))
+            out.append(g)
+        return out
+
     def compute_potential(self):
         self.L.compute_potential()
 
@@ -421,6 +471,7 @@ class Host:
         self.L.gadget_force_bind_dust_model(None, None)
         self.L.gadget_force_bind_integration(None, None, None, None, None, None)
         self.L.gadget_force_bind_potential(None, None)
+        self.L.gadget_force_bind_fof(None, None)
         self.L.gadget_force_bind_viscosity(None, None)
         self.L.gadget_force_bind_rndtable(None, 0)
         self.L.gadget_force_set_allgather(C.cast(None, HOST_ALLGATHER_CB), None)

@@ -401,6 +401,65 @@ void compute_potential(void);
 void compute_global_quantities_of_system(void);
 
 /* ---- the reference's call surface ---- */
+/* ---- fof_fof() (fof.c:94-333; accel.c:176-189 calls fof_fof(-1) between hydro_force() and blackhole_accretion()
+ * under -DFOF -DBLACK_HOLES): the group catalogue of this rank's records by ghip_fof, and for num < 0 the new
+ * sink seeds of fof_make_black_holes() (fof.c:1783-1886).  One table of ints:
+ *   a_*    byte offsets of doubles in `host_All`: Omega0, OmegaBaryon, Hubble, G, Time (-1: the mirror's own
+ *          `All` / gadget_force_bind_all), MinFoFMassForNewSeed, SeedBlackHoleMass, MassTable[1], massDMpart
+ *          (-1: 0; the seeds need the first two and one of the last two)
+ *   primary_types, secondary_types, group_min_len   FOF_PRIMARY_LINK_TYPES (2), FOF_SECONDARY_LINK_TYPES,
+ *          GROUP_MIN_LEN (32) as VALUES (<= 0 for the last: 32)
+ *   p_bh_mass, p_bh_mdot, p_stellar_age   byte offsets of P[].BH_Mass, P[].BH_Mdot (doubles; -1: p_bh_mass /
+ *          p_bh_mdot of the bh table of gadget_force_bind_records, if bound) and P[].StellarAge (-1: absent)
+ * fof_fof(num) uploads the records if the device copy is stale, uploads P[].ID (p_id of the bh table; without one
+ * the ID is the index), builds the tree if none of the current records is in place (fof.c:149-150), runs ghip_fof
+ * with LinkL from the LINKLENGTH rule (fof.c:112-124) and fills Ngroups, TotNgroups, TotNids and Group[], which
+ * the mirror owns and which stay valid until the next call.  Group[] is left sorted by MinID (fof.c:1117);
+ * FirstPos is the position of the member that carries MinID; Sfr, BH_Mass and BH_Mdot of a group are summed from
+ * the records where their members are bound (Sfr is not), else 0; task_maxdens = ThisTask where index_maxdens >= 0.
+ * num < 0: every group with LenType[1] * massDMpart >= (Omega0 - OmegaBaryon) / Omega0 * MinFoFMassForNewSeed,
+ * no Type-5 member and a gas member gets a seed at index_maxdens: endrun(7772) if that record is not gas, else
+ * Type = 5, StellarAge = All.Time, BH_Mass = SeedBlackHoleMass, BH_Mdot = 0; Stars_converted grows by their
+ * number, which gadget_force_fof_new_seeds() also returns (All.TotBHs += / All.TotN_gas -= stay the host's).
+ * The device copy is marked stale then.  num >= 0 computes the same catalogue and returns: the group files are the
+ * host's I/O, SUBFIND is not built.
+ * NTask > 1: endrun(90016) -- groups that span ranks need an exchange of labels that is not built.  No table
+ * bound: endrun(90013).  The nearest-primary search did not converge: endrun(1159), as fof.c:1651. */
+struct gadget_force_fof_layout
+{
+  int a_omega0, a_omega_baryon, a_hubble, a_g, a_time;
+  int a_min_fof_mass_for_new_seed, a_seed_black_hole_mass, a_mass_table_1, a_mass_dm_part;
+  int primary_types, secondary_types, group_min_len;
+  int p_bh_mass, p_bh_mdot, p_stellar_age;
+};
+void gadget_force_bind_fof(void *host_All, const struct gadget_force_fof_layout *lay);   /* lay == NULL unbinds */
+int gadget_force_fof_layout_count(void);   /* number of ints in the table (ABI check for bindings) */
+int gadget_force_fof_new_seeds(void);      /* seeds the last fof_fof(num < 0) made */
+struct gadget_force_group                  /* struct group_properties, fof.h:26-47 (-DSFR -DBLACK_HOLES) */
+{
+  int Len;
+  int Offset;
+  int MinID;
+  int MinIDTask;
+  int GrNr;
+  int LenType[6];
+  double MassType[6];
+  double Mass;
+  double CM[3];
+  double Vel[3];
+  double FirstPos[3];
+  double Sfr;
+  double BH_Mass;
+  double BH_Mdot;
+  double MaxDens;
+  int index_maxdens, task_maxdens;
+};
+extern int Ngroups, TotNgroups;
+extern long long TotNids;
+extern struct gadget_force_group *Group;
+extern int Stars_converted;
+void fof_fof(int num);
+
 void endrun(int ierr);
 void set_softenings(void);
 /* gravtree.c:892-907 (order by Task, then Index) and :909-963 (a stable sort of data_index records

@@ -30,6 +30,7 @@
  *   ghip_global_quantities                compute_global_quantities_of_system()  global.c:18-238
  *   ghip_find_next_sync_point             find_next_sync_point_and_drift() without its drift  run.c:190-340
  *   ghip_find_extent                      domain_findExtent() of one context   domain.c:1972-2014
+ *   ghip_fof                              fof_fof() without group files / SUBFIND   fof.c:94-333
  * The host-side mirror with the reference's own names (gravity_tree(), density(), hydro_force(),
  * force_treeevaluate(), ...) is include/gadget_force.h.
  */
@@ -1277,6 +1278,56 @@ int ghip_run_begin(ghip_ctx *ctx, int max_steps);
 int ghip_step_begin(ghip_ctx *ctx);
 int ghip_step_end(ghip_ctx *ctx);
 int ghip_run_end(ghip_ctx *ctx, ghip_run_stats *out);
+
+/* ---- friends-of-friends groups (fof_fof, fof.c:94-333; ghip_fof.hip) ----
+ * ghip_fof finds the FOF groups of the resident state on the gravity tree of the current positions
+ * (ghip_tree_build; no tree is built here):
+ *   linking      two particles of a primary type are linked when their nearest-image distance satisfies
+ *                r2 <= LinkL^2 (ngb_treefind_fof_primary, ngb.c:351-368: equality links); the groups are the
+ *                connected components (fof_find_groups, fof.c:337-706), labelled with their smallest ID
+ *   secondaries  a particle of a secondary type (and of no primary type) takes the label of the nearest primary
+ *                with r2 < h^2; h starts at Hsml for gas and at 0.1 LinkL otherwise and is doubled while nothing
+ *                is found, at most MaxIter times (GHIP_ENOCONV then: endrun(1159)); fof.c:1434-1776.  Equally
+ *                distant primaries: the one with the smaller ID (the reference keeps the first in traversal order)
+ *   catalogue    a group is the set of all particles with one label (a particle of neither kind is a group of
+ *                its own, as in the reference); kept with Len >= group_min_len, ordered by Len descending, then
+ *                MinID ascending; GrNr = 0 .. Ngroups-1, Offset the running sum of Len (fof.c:710-974, 1081-1119).
+ *                CM: periodic, the mass-weighted nearest images about the member that carries MinID, wrapped into
+ *                [0, BoxSize); else the mass-weighted mean.  MaxDens / index_maxdens: the gas member (Type 0)
+ *                of largest GHIP_F_DENSITY > 0, ties to the smaller particle index; -1 without one.
+ * Sums are taken in a fixed order without floating-point atomics: two calls on one state give identical bytes.
+ * Sfr, BH_Mass and BH_Mdot are no resident fields: they stay with the host, which has the member list.
+ * GHIP_EINVAL: no tree built, GHIP_F_ID never set, no particle of a primary type, a domain decomposition on
+ * (groups that span shards are not built).  Duplicate IDs are outside the contract, as under the reference's
+ * IGNORE_NON_UNIQUE.  The getters return what the last successful ghip_fof of this context found. */
+typedef struct {
+  double LinkL;          /* > 0: taken as is.  <= 0: LINKLENGTH rule of fof.c:112-124, computed on the device:
+                            linklength * pow(masstot / ndmtot / rhodm, 1/3) over the primary types */
+  double linklength;     /* LINKLENGTH (0.2), used when LinkL <= 0 */
+  double rhodm;          /* (Omega0 - OmegaBaryon) * 3 H^2 / (8 pi G), host-computed, used when LinkL <= 0 */
+  int primary_types;     /* FOF_PRIMARY_LINK_TYPES, bit mask of 1 << Type */
+  int secondary_types;   /* FOF_SECONDARY_LINK_TYPES; 0 = none */
+  int group_min_len;     /* GROUP_MIN_LEN (32) */
+  double BoxSize; int periodic;
+  int MaxIter;           /* MAXITER (150) of the nearest-primary search */
+} ghip_fof_params;
+
+typedef struct { int Ngroups; long long Nids; int largest; double LinkL; int nearest_iterations; } ghip_fof_result;
+
+typedef struct {          /* struct group_properties, fof.h:26-60, the members the resident state can fill */
+  int Len, Offset, MinID, GrNr, LenType[6];
+  double MassType[6], Mass, CM[3], Vel[3];
+  double MaxDens; int index_maxdens;      /* densest gas member (fof.c:950-961); -1 = no gas member */
+} ghip_fof_group;
+
+int ghip_fof(ghip_ctx *ctx, const ghip_fof_params *p, ghip_fof_result *out);
+int ghip_fof_get_groups(ghip_ctx *ctx, ghip_fof_group *groups /* [Ngroups] */);
+int ghip_fof_get_ids(ghip_ctx *ctx, int *ids /* [Nids], sorted by (GrNr, ID): fof_compare_ID_list_GrNrID */);
+int ghip_fof_get_labels(ghip_ctx *ctx, int *minid /* [n] */, int *grnr /* [n]; -1 = in no kept group */);
+size_t ghip_fof_params_size(void);
+size_t ghip_fof_group_size(void);   /* for the bindings' ABI check */
+/* device milliseconds of the last ghip_fof: linking, flattening + labels, secondary rounds, catalogue */
+int ghip_fof_get_timing(ghip_ctx *ctx, double ms[4]);
 
 /* ---- introspection ---- */
 int ghip_get_stats(const ghip_ctx *ctx, ghip_stats *out);
