@@ -390,7 +390,7 @@ EXPORTS = [
     "ghip_debug_prim",
     "ghip_find_next_sync_point", "ghip_get_active", "ghip_find_extent", "ghip_dd_get_sync_point",
     "ghip_fof", "ghip_fof_get_groups", "ghip_fof_get_ids", "ghip_fof_get_labels", "ghip_fof_params_size",
-    "ghip_fof_group_size", "ghip_fof_get_timing"]
+    "ghip_fof_group_size", "ghip_fof_get_timing", "ghip_fof_get_maxdens_task", "ghip_dd_fof_args_size"]
 
 
 def lib():
@@ -540,11 +540,17 @@ def lib():
         L.ghip_fof_get_ids.argtypes = [vp, vp]
         L.ghip_fof_get_labels.argtypes = [vp, vp, vp]
         L.ghip_fof_get_timing.argtypes = [vp, vp]
+        L.ghip_fof_get_maxdens_task.argtypes = [vp, vp]
+        L.ghip_dd_fof_args_size.restype = C.c_size_t
+        L.ghip_dd_fof_args_size.argtypes = []
         for fn, cls in ((L.ghip_fof_params_size, FofParams), (L.ghip_fof_group_size, FofGroup)):
             fn.argtypes = []
             fn.restype = C.c_size_t
             if fn() != C.sizeof(cls):
                 raise RuntimeError("%s: %d bytes here, %d in libghip.so" % (cls.__name__, C.sizeof(cls), fn()))
+        if L.ghip_dd_fof_args_size() != C.sizeof(DdFofArgs):
+            raise RuntimeError("DdFofArgs: %d bytes here, %d in libghip.so"
+                               % (C.sizeof(DdFofArgs), L.ghip_dd_fof_args_size()))
         _LIB = L
     return _LIB
 
@@ -682,6 +688,19 @@ class ForcePath:
         ms = np.zeros(4)
         self._chk(self.L.ghip_fof_get_timing(self.h, _ptr(ms)))
         return ms
+
+    def fof_maxdens_task(self):
+        """ghip_fof_get_maxdens_task -> int32[Ngroups]: the shard whose local index index_maxdens is (-1: no gas
+        member; 0 on a context without a decomposition)"""
+        task = np.zeros(self._fof[0], np.int32)
+        self._chk(self.L.ghip_fof_get_maxdens_task(self.h, _ptr(task) if len(task) else None))
+        return task
+
+    def fof_adopt(self, keep):
+        """after a completed DD_GLOBAL_QUANTITIES with walk = FOF_FORM (dd_fof_args -> keep): the sizes the
+        catalogue getters read -- Ngroups of the whole system, this shard's own members of kept groups"""
+        self._fof = (keep["out"].Ngroups, int(keep["counts"][0]))
+        return keep["out"]
 
     def get_active(self):
         """ghip_get_active: the particle indices of the list in force (int32; 0 .. n-1 when all are active)"""
@@ -1375,6 +1394,7 @@ DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 DD_DECOMPOSE = 13
 DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
+FOF_FORM = 1             # `walk` of dd_begin / dd_run for DD_GLOBAL_QUANTITIES with DdFofArgs: the FOF groups of all shards
 SYNC_POINT_FORM = 1      # `walk` of dd_begin / dd_run for DD_DECOMPOSE with SyncParams: the sync point of all shards
 DUST_GRAINS_FORM = 1     # `walk` of dd_begin / dd_run for DD_DUST_DENSITY / DD_DUST_DRAG with DdDustGrainsArgs
 
@@ -1481,6 +1501,31 @@ def dd_global_args(params, n, grav_kick_table=None, hydro_kick_table=None, old_p
     A = DdGlobalArgs()
     A.p = C.pointer(p)
     A.out = C.pointer(keep["out"])
+    return A, keep
+
+
+class DdFofArgs(C.Structure):
+    """ghip_dd_fof_args (include/ghip.h): the friends-of-friends groups of all shards, DD_GLOBAL_QUANTITIES begun
+    with walk = FOF_FORM"""
+    _fields_ = [("p", C.POINTER(FofParams)), ("out", C.POINTER(FofResult)), ("counts", C.POINTER(C.c_longlong))]
+
+
+FOF_COUNTS = ("members", "primaries_sent", "primaries_received", "label_rounds", "queries_sent", "partials_sent",
+              "bytes_sent", "groups_owned")
+
+
+def dd_fof_args(link_length=0.0, primary_types=2, secondary_types=0, group_min_len=32, boxsize=0.0,
+                periodic=False, max_iter=150, linklength=0.2, rhodm=0.0):
+    """(args, keep) for DD_GLOBAL_QUANTITIES with walk = FOF_FORM: a filled DdFofArgs and the dict it points into
+    (params: FofParams as ForcePath.fof takes them, the same on every shard; out: FofResult; counts: int64[8],
+    FOF_COUNTS).  Keep `keep` alive until the operation has finished; then ForcePath.fof_adopt(keep)."""
+    p = FofParams(float(link_length), float(linklength), float(rhodm), int(primary_types), int(secondary_types),
+                  int(group_min_len), float(boxsize), int(bool(periodic)), int(max_iter))
+    keep = dict(params=p, out=FofResult(), counts=np.zeros(8, np.int64))
+    A = DdFofArgs()
+    A.p = C.pointer(p)
+    A.out = C.pointer(keep["out"])
+    A.counts = C.cast(keep["counts"].ctypes.data, C.POINTER(C.c_longlong))
     return A, keep
 
 

@@ -1234,6 +1234,68 @@ int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord,
 }
 
 // ---------------------------------------------------------------------------------------------
+// friends-of-friends groups on shards: whose primary boxes does a sphere reach? (ghip_fof.hip runs the operation)
+// ---------------------------------------------------------------------------------------------
+struct FofSrc   // items `list` as indices of the merged gravity tree, which are their mask slots too; radius
+{               // hs[s] (a settled secondary carries a negative one: radius 0 reaches nothing) or, hs == nullptr, h0
+  const int *list;
+  const double *sx, *sy, *sz, *hs;
+  double h0;
+  __device__ __forceinline__ void load(int t, bool, int &i, double &x, double &y, double &z, double &h) const
+  {
+    const int s = list[t];
+    i = s;
+    x = sx[s];
+    y = sy[s];
+    z = sz[s];
+    const double hh = hs ? hs[s] : h0;
+    h = hh > 0 ? hh : 0;
+  }
+};
+
+// this shard's group table over its own primaries (tree indices, ascending); the all-gather is left pending
+int ghip_dd_fof_groups(ghip_ctx *ctx, const int *plist, int nprim)
+{
+  DDState &D = ctx->dd;
+  // (the groups carry the least mass in place of OldAcc: the sphere test reads neither)
+  GCHK(build_groups(ctx, false, plist, nprim, P<double>(ctx->f[GHIP_F_MASS])));
+  ghip_dd_set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+  return 1;
+}
+
+int ghip_dd_fof_status(ghip_ctx *ctx, const char *what) { return check_group_status(ctx, what); }
+
+// the per-destination lists (ascending tree index) of the nitem items whose spheres reach another shard's primaries;
+// mask: u64[ctx->gt.n], cleared here
+int ghip_dd_fof_select(ghip_ctx *ctx, int nitem, const int *items, const double *hs, double h0, double boxsize,
+                       int periodic, DevBuf &mask, DevBuf &list, int *scount, int *soff, int *total)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int P_ = D.nranks, nt = ctx->gt.n;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    scount[r] = soff[r] = 0;
+  *total = 0;
+  GCHK(ghip_ensure(ctx, list, 4));
+  if(nitem == 0 || P_ < 2 || nt == 0)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, mask, (size_t) nt * 8));
+  HIPCHK(hipMemsetAsync(mask.p, 0, (size_t) nt * 8, st));
+  const FofSrc S = {items, P<double>(ctx->sx), P<double>(ctx->sy), P<double>(ctx->sz), hs, h0};
+  k_dd_select<FofSrc, SphereReach><<<cdiv(nitem, 64) * (P_ - 1), 64, 0, st>>>(
+    nitem, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(mask));
+  HIPCHK(hipGetLastError());
+  return multi_select(ctx, nt, P<unsigned long long>(mask), list, scount, soff, total);
+}
+
+// multi_select for the callers outside this file: the items of mask[0 .. n) per rank whose bit is set
+int ghip_dd_select_ranks(ghip_ctx *ctx, int n, const unsigned long long *mask, DevBuf &list, int *scount, int *soff,
+                         int *total)
+{
+  return multi_select(ctx, n, mask, list, scount, soff, total);
+}
+
+// ---------------------------------------------------------------------------------------------
 // the state machine: compute until the next exchange, exchange, continue
 // ---------------------------------------------------------------------------------------------
 #define set_allgather ghip_dd_set_allgather

@@ -296,6 +296,7 @@ struct DDState
                                   // (selected for all particles as targets), not the step's GHIP_DD_GRAVITY's
   ghip_dd_global_args gq;         // GHIP_DD_GLOBAL_QUANTITIES: arguments, a copy of *gq.p
   ghip_global_params gq_p;
+  int gq_form = 0;                // 0: the energy sums; GHIP_FOF_FORM: the group finder (ghip_fof.hip, state in ctx->fof)
   DevBuf gq_send, gq_all;         // ghip_global_sums of this shard / of all shards (rank order)
   // GHIP_DD_DECOMPOSE (ghip_decomp.hip)
   ghip_dd_decomp_params dcp;      // arguments of the operation in progress
@@ -415,9 +416,36 @@ struct FofState
   DevBuf pgrnr, ids;                            // i32[n] GrNr per particle; i32[Nids] the ID list
   DevBuf groups;                                // ghip_fof_group[Ngroups]
   int n = -1, ngroups = 0;                      // particle count of the last successful call (-1: none)
-  long long nids = 0;
+  long long nids = 0;                           // entries of `ids` (the collective form: this shard's own members)
   double ms[4] = {0, 0, 0, 0};
   hipEvent_t ev[5] = {};
+  // ---- the collective form on shards (GHIP_DD_GLOBAL_QUANTITIES begun with walk = GHIP_FOF_FORM; ghip_dd_fof_step).
+  // Tree order means the merged tree of GHIP_DD_GRAVITY: nt = own particles + imports; the union-find has the
+  // nimp imported primaries behind them.  A label word is (MinID ^ sign bit) << 32 | MinIDTask.
+  bool dd = false;                              // the catalogue in place came from the collective form
+  ghip_dd_fof_args a = {};                      // arguments of the operation in progress, a copy of *a.p
+  ghip_fof_params p = {};
+  int nt = 0, nprim = 0, nsec = 0, nimp = 0, nexp = 0, nseg = 0, nown = 0, nkept = 0, iter = 0, rounds = 0;
+  long long totprim = 0, totsec = 0, queries = 0, parts_sent = 0;
+  double linkl = 0;
+  DevBuf stat_own, stat_all;                    // f64[4]: mass and number of the primaries, secondaries, error flag
+  DevBuf word_own, word_all;                    // u64: the one-word all-gathers (labels fell / secondaries left)
+  DevBuf rlab, plab, plabh;                     // u64: label word per root [nt + nimp], per particle [nt], host order [n]
+  DevBuf xmask, xlist, xsend, xrecv;            // border primaries: destinations, lists (tree indices), (x, y, z, label)
+  DevBuf lsend, lrecv;                          // u64: the labels of a round, along the same lists
+  DevBuf parent2;                               // the union-find while it grows by the imports
+  DevBuf hs, cr2, cid, clab;                    // secondaries, by tree index: radius (< 0 settled), best r2 / ID / label
+  DevBuf qlist, qsend, qrecv, asend, arecv;     // their queries (x, y, z, h) and the answers (r2, ID, label)
+  DevBuf smask, seglist, psend, precv;          // catalogue: owner of each local segment, partial records out / in
+  DevBuf rqsend, rqrecv, rpsend, rprecv;        // ... "about which position": the labels asked / FirstPos answered
+  DevBuf pkey, pskey, pval, psval, phead, psegof, psegstart;   // the partials an owner received, by (MinID, source)
+  DevBuf own, keep, klist, ksend, kall;         // owned groups, who is kept, the kept records of this shard / of all
+  DevBuf mkey, msk, mval, msv;                  // kept groups by MinID, for the look-up of GrNr
+  DevBuf key2, skey2;                           // (GrNr, ID) of the own members
+  DevBuf task;                                  // i32[Ngroups]: the shard index_maxdens counts on
+  int x_scount[GHIP_MAXRANKS] = {}, x_soff[GHIP_MAXRANKS] = {}, x_rcount[GHIP_MAXRANKS] = {};
+  int q_scount[GHIP_MAXRANKS] = {}, q_soff[GHIP_MAXRANKS] = {};
+  int p_scount[GHIP_MAXRANKS] = {}, p_soff[GHIP_MAXRANKS] = {};
   ~FofState()
   {
     for(int i = 0; i < 5; i++)
@@ -837,6 +865,8 @@ int ghip_dd_pot_begin(ghip_ctx *ctx, int op, const void *params, int walk);     
 int ghip_dd_pot_step(ghip_ctx *ctx);
 int ghip_dd_gq_begin(ghip_ctx *ctx, int op, const void *params, int walk);
 int ghip_dd_gq_step(ghip_ctx *ctx);
+int ghip_dd_fof_begin(ghip_ctx *ctx, int op, const void *params, int walk);      // fof.hip: GHIP_FOF_FORM of the above
+int ghip_dd_fof_step(ghip_ctx *ctx);
 int ghip_dd_decomp_begin(ghip_ctx *ctx, int op, const void *params, int walk);   // decomp.hip
 int ghip_dd_decomp_step(ghip_ctx *ctx);
 int ghip_dd_sync_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // sync.hip: GHIP_SYNC_POINT_FORM

@@ -946,8 +946,13 @@ static int gq_local(ghip_ctx *ctx, const ghip_global_params *p, ghip_global_sums
 #define GQ_SUM_DOUBLES (sizeof(ghip_global_sums) / sizeof(double))
 static_assert(sizeof(ghip_global_sums) % sizeof(double) == 0, "ghip_global_sums is an array of doubles");
 
-int ghip_dd_gq_begin(ghip_ctx *ctx, int, const void *params, int)
+// Begun with walk = GHIP_FOF_FORM the operation is the group finder of all shards (ghip_fof.hip), whose catalogue
+// has this operation's contract: the same bytes on all shards, sums added in rank order, no atomics.
+int ghip_dd_gq_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
+  ctx->dd.gq_form = walk == GHIP_FOF_FORM ? GHIP_FOF_FORM : 0;
+  if(ctx->dd.gq_form == GHIP_FOF_FORM)
+    return ghip_dd_fof_begin(ctx, op, params, walk);
   GHIP_JOIN(ctx);
   DDState &D = ctx->dd;
   D.gq = *reinterpret_cast<const ghip_dd_global_args *>(params);
@@ -960,6 +965,8 @@ int ghip_dd_gq_begin(ghip_ctx *ctx, int, const void *params, int)
 int ghip_dd_gq_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
+  if(D.gq_form == GHIP_FOF_FORM)
+    return ghip_dd_fof_step(ctx);
   hipStream_t st = ctx->stream;
   enum { OWN_SUMS, ADD };
   if(D.phase == OWN_SUMS)

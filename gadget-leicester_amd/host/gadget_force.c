@@ -3068,7 +3068,9 @@ void fof_fof(int num)
   if(NTask > 1)
     {
       refuse(90016, "%s: NTask = %d: groups that span ranks are not built (they need an exchange of labels "
-                    "between the shards); run the group finder on a single rank", who, NTask);
+                    "between the shards); run the group finder on a single rank, or call the library's collective "
+                    "form (GHIP_DD_GLOBAL_QUANTITIES begun with walk = GHIP_FOF_FORM), which this mirror does not "
+                    "drive: who creates a seed is a decision of the host", who, NTask);
       return;
     }
   if(!FofBound)

@@ -196,6 +196,12 @@ def find_guests(keys, holder, splits=None, segments=None):
     return guests, host[guests].astype(_np.int32)
 
 
+def _fof_result(path, keep):
+    out = path.fof_adopt(keep)
+    out.counts = keep["counts"]
+    return out
+
+
 class DomainShards:
     """All shards of a run as contexts of THIS process (one after the other on one GPU, or one per
     visible GPU): the parity-test and rehearsal form of the multi-GPU path.  Exchanges are
@@ -291,6 +297,15 @@ class DomainShards:
                  for r, p in enumerate(self.paths)]
         self.run(self.B.DD_GLOBAL_QUANTITIES, [b[0] for b in built])
         return [b[1]["out"].asdict() for b in built]
+
+    def fof(self, **params):
+        """GHIP_DD_GLOBAL_QUANTITIES begun with walk = FOF_FORM (params: those of ForcePath.fof, the same for all):
+        the friends-of-friends groups of the whole system on the merged trees of this step's gravity().  Returns
+        the FofResult per shard (with .counts: int64[8], bindings.FOF_COUNTS); afterwards every path's fof_groups()
+        / fof_maxdens_task() give the complete catalogue, fof_labels() / fof_ids() its own particles."""
+        built = [self.B.dd_fof_args(**params) for _ in self.paths]
+        self.run(self.B.DD_GLOBAL_QUANTITIES, [b[0] for b in built], self.B.FOF_FORM)
+        return [_fof_result(p, b[1]) for p, b in zip(self.paths, built)]
 
 
 class DomainRank:
@@ -419,3 +434,11 @@ class DomainRank:
                                            old_photon_momentum, potential)
         self._run(self.B.DD_GLOBAL_QUANTITIES, args)
         return keep["out"].asdict()
+
+    def fof(self, **params):
+        """GHIP_DD_GLOBAL_QUANTITIES begun with walk = FOF_FORM, a collective (params: those of ForcePath.fof, the
+        same on every rank): the FofResult of the whole system (the same bytes on every rank, with .counts);
+        afterwards the path's fof_groups() / fof_maxdens_task() / fof_labels() / fof_ids() answer"""
+        args, keep = self.B.dd_fof_args(**params)
+        self._run(self.B.DD_GLOBAL_QUANTITIES, args, self.B.FOF_FORM)
+        return _fof_result(self.p, keep)

@@ -988,6 +988,10 @@ typedef struct
   const ghip_global_params *p;
   ghip_global_sums *out;
 } ghip_dd_global_args;
+/* ... begun with walk = GHIP_FOF_FORM and params a ghip_dd_fof_args: the friends-of-friends groups of ALL shards
+ * (fof_fof on NTask > 1, fof.c; "friends-of-friends groups" below says what the collective form does).  The
+ * traffic counter of GHIP_DD_GLOBAL_QUANTITIES (ghip_dd_bytes_sent) serves whichever form ran last. */
+#define GHIP_FOF_FORM 1
 /* domain_Decomposition on shards (params: ghip_dd_decomp_params): the ranges of ghip_dd_set_splits, and on
  * request the cube of ghip_dd_set_domain, are computed from the RESIDENT particles of all shards; no rank
  * ever holds another rank's keys.  Three steps, two all-gathers:
@@ -1298,7 +1302,7 @@ int ghip_run_end(ghip_ctx *ctx, ghip_run_stats *out);
  * Sums are taken in a fixed order without floating-point atomics: two calls on one state give identical bytes.
  * Sfr, BH_Mass and BH_Mdot are no resident fields: they stay with the host, which has the member list.
  * GHIP_EINVAL: no tree built, GHIP_F_ID never set, no particle of a primary type, a domain decomposition on
- * (groups that span shards are not built).  Duplicate IDs are outside the contract, as under the reference's
+ * (groups that span shards are found by the collective form below).  Duplicate IDs are outside the contract, as under the reference's
  * IGNORE_NON_UNIQUE.  The getters return what the last successful ghip_fof of this context found. */
 typedef struct {
   double LinkL;          /* > 0: taken as is.  <= 0: LINKLENGTH rule of fof.c:112-124, computed on the device:
@@ -1328,6 +1332,36 @@ size_t ghip_fof_params_size(void);
 size_t ghip_fof_group_size(void);   /* for the bindings' ABI check */
 /* device milliseconds of the last ghip_fof: linking, flattening + labels, secondary rounds, catalogue */
 int ghip_fof_get_timing(ghip_ctx *ctx, double ms[4]);
+
+/* On domain-decomposed shards ghip_fof is refused; the groups of the WHOLE system are found by the collective
+ *   ghip_dd_begin / ghip_dd_run(ctx, GHIP_DD_GLOBAL_QUANTITIES, &ghip_dd_fof_args, GHIP_FOF_FORM)
+ * on the merged gravity tree of this step's GHIP_DD_GRAVITY (GHIP_EINVAL without it, or with the tree that
+ * GHIP_DD_POTENTIAL leaves behind); no tree is built, no resident field changed.  Own primaries are linked on the
+ * merged tree; primaries within LinkL of another shard's primary boxes travel there once as (x, y, z, label), are
+ * linked against that shard's tree by the same pair test, and labels (MinID, MinIDTask) are exchanged along the
+ * same lists until none falls (fof.c:416-583).  A secondary asks every shard whose primaries its sphere reaches
+ * and takes the smallest (r2, ID) (fof.c:1434-1776).  Partial group records go to MinIDTask, are added there in
+ * rank order (fof.c:977-1119), and the kept groups are gathered and ordered on every shard.  Afterwards, on every
+ * shard: ghip_fof_get_groups -> the complete catalogue, identical bytes everywhere (index_maxdens: the local index
+ * on the shard ghip_fof_get_maxdens_task names; ties of MaxDens to the lower rank, then the smaller index);
+ * ghip_fof_get_labels -> MinID and global GrNr of the shard's own particles; ghip_fof_get_ids -> the IDs of its own
+ * members of kept groups by (GrNr, ID), counts[0] of them; ghip_fof_get_timing -> this shard's device time,
+ * exchanges excluded.  No floating-point atomics: two runs give identical bytes.  Errors every shard sees alike
+ * (NULL members, the parameter rules of ghip_fof, GHIP_F_ID never set) come from ghip_dd_begin; "no primary on any
+ * shard" (GHIP_EINVAL), more than MaxIter doublings (GHIP_ENOCONV) and labels that do not settle (GHIP_EDEVICE)
+ * stop all shards together, which stay usable. */
+typedef struct {
+  const ghip_fof_params *p;   /* the same values on every rank */
+  ghip_fof_result *out;       /* Ngroups, Nids, largest: of the WHOLE system; LinkL; nearest_iterations: rounds of the
+                                 collective search.  The same bytes on every rank */
+  long long *counts;          /* may be NULL; [8]: own members of kept groups (= entries of ghip_fof_get_ids), primaries
+                                 sent, primaries received, label rounds, secondary queries sent (all rounds),
+                                 partial group records sent, bytes sent, kept groups this rank owns (MinIDTask) */
+} ghip_dd_fof_args;
+/* the shard whose local index index_maxdens is (task_maxdens, fof.h:46); without a decomposition 0 where
+ * index_maxdens >= 0 */
+int ghip_fof_get_maxdens_task(ghip_ctx *ctx, int *task /* [Ngroups]; -1 = no gas member */);
+size_t ghip_dd_fof_args_size(void);
 
 /* ---- introspection ---- */
 int ghip_get_stats(const ghip_ctx *ctx, ghip_stats *out);
