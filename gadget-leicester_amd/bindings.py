@@ -30,6 +30,7 @@ EN = 64
 GHIP_ERRORS = {-90001: "GHIP_EHIP", -90002: "GHIP_EINVAL", -90003: "GHIP_ENOMEM",
                -90004: "GHIP_ENOCONV", -90005: "GHIP_ENODEVICE", -90006: "GHIP_ETIMESTEP",
                -90008: "GHIP_EDEVICE", -90009: "GHIP_ECOMM", -90010: "GHIP_EREGION"}
+GHIP_ENOCONV = -90004
 
 
 class Layout(C.Structure):
@@ -146,6 +147,29 @@ def dust_grains(dust, particle_density=None, dust_density=None, dust_entropy=Non
     for k, v in a.items():
         setattr(g, k, v.ctypes.data)
     return g, a
+
+
+class WindParams(C.Structure):
+    """ghip_wind_params: the wind particles of the shipped flag bundle (FB_MOMENTUM, include/ghip.h)"""
+    _fields_ = [("periodic", C.c_int)] + \
+        [(k, C.c_double) for k in ("BoxSize", "Time", "dt_fac", "dt_fac_gas", "FeedBackVelocity",
+                                   "UnitVelocity_in_cm_per_s", "UnitDensity_in_cgs", "UnitLength_in_cm",
+                                   "VirtualCrosSection", "VirtualMass", "VirtualTime", "OuterBoundary",
+                                   "DesNumNgb", "OriginalGasMass", "SofteningGas", "SofteningGasMaxPhys",
+                                   "SofteningBulgeMaxPhys", "PhotonSearchRadius", "dt_total_floor")] + \
+        [(k, C.c_int) for k in ("fly_through_empty_space", "variable_search_radius", "rad_accel", "max_iter")]
+
+
+class WindState(C.Structure):
+    """ghip_wind_state: the per-particle arrays of ghip_wind_feedback, in list order (include/ghip.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("stellar_age", "birth_energy", "old_momentum", "new_density", "drmin",
+                                           "dt1", "dt2", "dt_jump", "delta_momentum", "deleted")]
+
+
+class WindResult(C.Structure):
+    """ghip_wind_result (include/ghip.h)"""
+    _fields_ = [("iterations", C.c_int), ("bits", C.c_longlong), ("ndeleted", C.c_int),
+                ("deleted_momentum", C.c_double)]
 
 
 class IntegrationFlags(C.Structure):
@@ -390,7 +414,10 @@ EXPORTS = [
     "ghip_debug_prim",
     "ghip_find_next_sync_point", "ghip_get_active", "ghip_find_extent", "ghip_dd_get_sync_point",
     "ghip_fof", "ghip_fof_get_groups", "ghip_fof_get_ids", "ghip_fof_get_labels", "ghip_fof_params_size",
-    "ghip_fof_group_size", "ghip_fof_get_timing", "ghip_fof_get_maxdens_task", "ghip_dd_fof_args_size"]
+    "ghip_fof_group_size", "ghip_fof_get_timing", "ghip_fof_get_maxdens_task", "ghip_dd_fof_args_size",
+    "ghip_wind_params_size", "ghip_wind_density", "ghip_wind_spread", "ghip_wind_feedback",
+    "ghip_wind_get_injected", "ghip_wind_set_injected", "ghip_wind_get_rad_accel", "ghip_wind_set_rad_accel",
+    "ghip_set_rad_accel", "ghip_wind_get_timing"]
 
 
 def lib():
@@ -508,6 +535,19 @@ def lib():
             if fn() != C.sizeof(cls):
                 raise RuntimeError("%s: %d bytes here, %d in libghip.so" % (cls.__name__, C.sizeof(cls), fn()))
         L.ghip_dust_set_drag_heating.argtypes = [vp, vp]
+        L.ghip_wind_params_size.argtypes = []
+        L.ghip_wind_params_size.restype = C.c_size_t
+        if L.ghip_wind_params_size() != C.sizeof(WindParams):
+            raise RuntimeError("WindParams: %d bytes here, %d in libghip.so"
+                               % (C.sizeof(WindParams), L.ghip_wind_params_size()))
+        L.ghip_wind_density.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
+        L.ghip_wind_spread.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
+        L.ghip_wind_feedback.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, C.POINTER(WindState),
+                                         C.POINTER(WindResult)]
+        for fn in (L.ghip_wind_get_injected, L.ghip_wind_set_injected, L.ghip_wind_get_rad_accel,
+                   L.ghip_wind_set_rad_accel, L.ghip_wind_get_timing):
+            fn.argtypes = [vp, vp]
+        L.ghip_set_rad_accel.argtypes = [vp, C.c_int]
         L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
         L.ghip_find_smbh.argtypes = [vp, C.c_double, vp, C.POINTER(C.c_int)]
         L.ghip_set_integration_flags.argtypes = [vp, C.POINTER(IntegrationFlags)]
@@ -1193,6 +1233,75 @@ class ForcePath:
         dh = np.ascontiguousarray(dh, np.float64)
         assert dh.shape == (self.ngas,)
         self._chk(self.L.ghip_dust_set_drag_heating(self.h, _ptr(dh)))
+
+    # ---- wind particles (momentum_feedback.c): Type-3 particles in list order ----
+    def wind_density(self, params, wind, dt_jump):
+        """one virtual_density(): -> (new_density, drmin)"""
+        wind = np.ascontiguousarray(wind, np.int32)
+        dtj = np.ascontiguousarray(dt_jump, np.float64)
+        assert dtj.shape == wind.shape
+        rho, drmin = np.zeros(len(wind)), np.zeros(len(wind))
+        self._chk(self.L.ghip_wind_density(self.h, C.byref(params), len(wind), _ptr(wind), _ptr(dtj), _ptr(rho),
+                                           _ptr(drmin)))
+        return rho, drmin
+
+    def wind_spread(self, params, wind, dt_jump, new_density, delta_momentum):
+        """one virtual_spread_momentum() into the resident Injected_BH_Momentum"""
+        wind = np.ascontiguousarray(wind, np.int32)
+        a = [np.ascontiguousarray(v, np.float64) for v in (dt_jump, new_density, delta_momentum)]
+        assert all(v.shape == wind.shape for v in a)
+        self._chk(self.L.ghip_wind_spread(self.h, C.byref(params), len(wind), _ptr(wind), *[_ptr(v) for v in a]))
+
+    def wind_feedback(self, params, wind, stellar_age, birth_energy, old_momentum, new_density, drmin,
+                      check=True):
+        """the propagation loop -> dict(rc, old_momentum, new_density, drmin, dt1, dt2, dt_jump, delta_momentum,
+        deleted, iterations, bits, ndeleted, deleted_momentum); check = False returns GHIP_ENOCONV as rc"""
+        wind = np.ascontiguousarray(wind, np.int32)
+        nw = len(wind)
+        f64 = lambda v: np.ascontiguousarray(v, np.float64).reshape(nw).copy()
+        a = dict(stellar_age=f64(stellar_age), birth_energy=f64(birth_energy), old_momentum=f64(old_momentum),
+                 new_density=f64(new_density), drmin=f64(drmin), dt1=np.zeros(nw), dt2=np.zeros(nw),
+                 dt_jump=np.zeros(nw), delta_momentum=np.zeros(nw), deleted=np.zeros(nw, np.int32))
+        st = WindState()
+        for k, v in a.items():
+            setattr(st, k, v.ctypes.data)
+        res = WindResult()
+        rc = self.L.ghip_wind_feedback(self.h, C.byref(params), nw, _ptr(wind), C.byref(st), C.byref(res))
+        if check or rc != GHIP_ENOCONV:
+            self._chk(rc)
+        a.update(rc=rc, iterations=res.iterations, bits=res.bits, ndeleted=res.ndeleted,
+                 deleted_momentum=res.deleted_momentum)
+        return a
+
+    def wind_injected(self):
+        out = np.zeros((self.ngas, 3))
+        self._chk(self.L.ghip_wind_get_injected(self.h, _ptr(out)))
+        return out
+
+    def set_wind_injected(self, v):
+        v = np.ascontiguousarray(v, np.float64)
+        assert v.shape == (self.ngas, 3)
+        self._chk(self.L.ghip_wind_set_injected(self.h, _ptr(v)))
+
+    def wind_rad_accel(self):
+        out = np.zeros((self.ngas, 3))
+        self._chk(self.L.ghip_wind_get_rad_accel(self.h, _ptr(out)))
+        return out
+
+    def set_wind_rad_accel(self, v):
+        v = np.ascontiguousarray(v, np.float64)
+        assert v.shape == (self.ngas, 3)
+        self._chk(self.L.ghip_wind_set_rad_accel(self.h, _ptr(v)))
+
+    def set_rad_accel(self, on):
+        """RAD_ACCEL in advance_timesteps, pm_kick and drift"""
+        self._chk(self.L.ghip_set_rad_accel(self.h, int(bool(on))))
+
+    def wind_timing(self):
+        """ms of the last wind_feedback: move, density, spread, list, whole call"""
+        ms = np.zeros(5)
+        self._chk(self.L.ghip_wind_get_timing(self.h, _ptr(ms)))
+        return ms
 
     # ---- the shipped bundle's integrator rules (ghip_set_integration_flags) ----
     def set_integration_flags(self, flags=None):

@@ -340,6 +340,7 @@ ghip_ctx::~ghip_ctx()
   destroy(ev_ring.data(), (int) ev_ring.size());
   destroy(evx, 4);
   destroy(evt, 2);
+  destroy(wind_ev, 8);
   for(hipStream_t s : {stream2, stream3, stream})
     if(s)
       (void) hipStreamDestroy(s);

@@ -10,6 +10,7 @@
 #include "ghip_internal.h"
 
 #include "ghip_timefac.h"
+#include <type_traits>
 
 // the shipped bundle's rules (ghip_set_integration_flags); the default kernel has none of them
 struct DriftB
@@ -17,6 +18,16 @@ struct DriftB
   int dust, virt;
   const double *drag;   // SphP[].da.DragAccel [3][ngas] or null (zero)
 };
+
+// ghip_set_rad_accel: RAD_ACCEL in drift_particle (predict.c:190-192); stands FIRST in the pack of k_drift
+struct DriftR
+{
+  const double *ra;   // SphP[].ra.RadAccel [3][ngas]
+};
+template <class... T>
+__device__ __forceinline__ const DriftR &d_driftr(const DriftR &r, const T &...) { return r; }
+__device__ __forceinline__ const DriftB &d_driftb(const DriftB &x) { return x; }
+__device__ __forceinline__ const DriftB &d_driftb(const DriftR &, const DriftB &x) { return x; }
 
 // X... is empty for the default kernel (the minimal flag set: same signature, same code as before the
 // bundle existed) and one DriftB for the bundle's rules
@@ -38,7 +49,7 @@ __global__ void k_drift(int n, int ngas, DriftK k, double *__restrict__ pos,
   bool skip = false;   // predict.c:134-136: a virtual particle is not drifted
   if constexpr(BUNDLE)
     {
-      const DriftB &x = (xs, ...);
+      const DriftB &x = d_driftb(xs...);
       skip = x.virt && type[i] == 3;
     }
   int time0 = ti_current[i];
@@ -73,9 +84,11 @@ __global__ void k_drift(int n, int ngas, DriftK k, double *__restrict__ pos,
                 g = g + gravpm[(size_t) j * n + i];
               velpred[(size_t) j * ngas + i] +=
                 g * dt_gravkick + hydroaccel[(size_t) j * ngas + i] * dt_hydrokick;
+              if constexpr((... || std::is_same_v<X, DriftR>))   // predict.c:190-192
+                velpred[(size_t) j * ngas + i] += d_driftr(xs...).ra[(size_t) j * ngas + i] * dt_hydrokick;
               if constexpr(BUNDLE)
                 {
-                  const DriftB &x = (xs, ...);
+                  const DriftB &x = d_driftb(xs...);
                   if(x.dust && x.drag)   // predict.c:195-198
                     velpred[(size_t) j * ngas + i] += x.drag[(size_t) j * ngas + i] * dt_hydrokick;
                 }
@@ -149,7 +162,27 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
   if(ctx->iflags_on && ctx->has_drag && ctx->kick_fields_ngas != ng)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_drift: DragAccel was set for %d gas particles, the context "
                      "has %d (ghip_kick_set_fields again)", ctx->kick_fields_ngas, ng);
-  if(ctx->iflags_on)
+  DriftR r = {nullptr};   // ghip_set_rad_accel: the instantiations with RadAccel, else the kernels as they were
+  GCHK(ghip_rad_accel_field(ctx, "ghip_drift", &r.ra));
+#define DRIFT_ARGS                                                                                       \
+  n, ng, k, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_VEL]), P<int>(ctx->f[GHIP_F_TYPE]),  \
+    P<int>(ctx->f[GHIP_F_TI_CURRENT]), P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), \
+    P<double>(ctx->f[GHIP_F_GRAVACCEL]), p->pmgrid ? P<double>(ctx->f[GHIP_F_GRAVPM]) : (const double *) nullptr, \
+    P<double>(ctx->f[GHIP_F_VELPRED]), P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_DENSITY]), \
+    P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]), P<double>(ctx->f[GHIP_F_ENTROPY]), \
+    P<double>(ctx->f[GHIP_F_DTENTROPY]), P<double>(ctx->f[GHIP_F_PRESSURE]), derr,                      \
+    ctx->async ? ghip_errword(ctx, GHIP_ERRW_DRIFT) : nullptr
+  if(r.ra && ctx->iflags_on)
+    {
+      DriftB x;
+      x.dust = ctx->iflags.dust;
+      x.virt = ctx->iflags.virtual_particles;
+      x.drag = ctx->has_drag ? P<double>(ctx->kick_drag) : nullptr;
+      k_drift<true><<<cdiv(n, 256), 256, 0, st>>>(DRIFT_ARGS, r, x);
+    }
+  else if(r.ra)
+    k_drift<false><<<cdiv(n, 256), 256, 0, st>>>(DRIFT_ARGS, r);
+  else if(ctx->iflags_on)
     {
       DriftB x;
       x.dust = ctx->iflags.dust;
@@ -180,6 +213,7 @@ extern "C" int ghip_drift(ghip_ctx *ctx, const ghip_drift_params *p)
       P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_DIVVEL]),
       P<double>(ctx->f[GHIP_F_ENTROPY]), P<double>(ctx->f[GHIP_F_DTENTROPY]),
       P<double>(ctx->f[GHIP_F_PRESSURE]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_DRIFT) : nullptr);
+#undef DRIFT_ARGS
   HIPCHK(hipGetLastError());
   ctx->gt.built = false;  // positions moved: the trees are stale
   ctx->st.built = false;

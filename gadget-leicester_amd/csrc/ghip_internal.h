@@ -572,6 +572,13 @@ struct ghip_ctx
   DevBuf kick_drag, kick_ddm, kick_newdens;   // f64[3][ngas], f64[3][ngas], f64[n]
   bool has_drag = false, has_ddm = false, has_newdens = false;
   int kick_fields_n = -1, kick_fields_ngas = -1;   // counts the fields were set for
+  // wind particles (ghip_wind.hip): the list and its orders, per-particle planes, sorted pairs; the resident gas
+  // fields Injected_BH_Momentum and RadAccel f64[3][ngas] with the gas count they hold (-1: not made yet)
+  DevBuf wind_idx, wind_work, wind_pairs, wind_inj, wind_ra;
+  int wind_inj_ngas = -1, wind_ra_ngas = -1;
+  bool rad_accel_on = false;        // ghip_set_rad_accel: kick, PM kick and drift read RadAccel
+  hipEvent_t wind_ev[8] = {};       // phase marks of ghip_wind_feedback (made by its first call)
+  double wind_ms[5] = {0, 0, 0, 0, 0};
 
   // the physics switches of the dust passes (ghip_set_dust_model, ghip_dust.hip)
   bool dust_model_on = false;          // any switch set: the k_dust_grain<DustM> / k_dust_density<G, DustVel> instantiations run
@@ -732,6 +739,8 @@ int ghip_gravity_finish_on(ghip_ctx *ctx, double G, int pmgrid, double comoving_
                            hipStream_t st);
 int ghip_join_pair(ghip_ctx *ctx);   // wait for a pair in flight only (entry of the gravity walks)
 int ghip_finish_gas_tree(ghip_ctx *ctx);   // complete a deferred gas tree (entry of the SPH phases)
+// ghip_wind.hip: SphP[].ra.RadAccel [3][ngas] for the kick, the PM kick and the drift (nullptr: ghip_set_rad_accel off)
+int ghip_rad_accel_field(ghip_ctx *ctx, const char *who, const double **ra);
 #define GHIP_JOIN(ctx)                          \
   do                                            \
     {                                           \

@@ -73,6 +73,19 @@ struct KickBV : KickB
 __device__ __forceinline__ const KickV &d_kickv(const KickV &v) { return v; }
 __device__ __forceinline__ const KickV &d_kickv(const KickBV &x) { return x.v; }
 
+// ghip_set_rad_accel: RAD_ACCEL in get_timestep and do_the_kick (timestep.c:668-671, 497-500).  A KickR stands
+// FIRST in the pack of k_advance_timesteps, in front of what the pack would hold without it
+struct KickR
+{
+  const double *ra;   // SphP[].ra.RadAccel [3][ngas]
+};
+template <class T>
+__device__ __forceinline__ const KickV &d_kickv(const KickR &, const T &t) { return d_kickv(t); }
+template <class... T>
+__device__ __forceinline__ const KickR &d_kickr(const KickR &r, const T &...) { return r; }
+__device__ __forceinline__ const KickB &d_kickb(const KickB &x) { return x; }
+__device__ __forceinline__ const KickB &d_kickb(const KickR &, const KickB &x) { return x; }
+
 // X... is empty for the default kernel (the minimal flag set: same signature, same code as before the
 // bundle existed) and one KickB for the bundle's rules; every rule sits in an `if constexpr`
 template <bool BUNDLE, class... X>
@@ -128,9 +141,19 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
       ax += k.fac2 * hy[0];
       ay += k.fac2 * hy[1];
       az += k.fac2 * hy[2];
+      if constexpr((... || std::is_same_v<X, KickR>))   // timestep.c:668-671
+        {
+          if(gas)
+            {
+              const double *ra = d_kickr(xs...).ra;
+              ax += k.fac2 * ra[i];
+              ay += k.fac2 * ra[(size_t) ngas + i];
+              az += k.fac2 * ra[2 * (size_t) ngas + i];
+            }
+        }
       if constexpr(BUNDLE)
         {
-          const KickB &x = (xs, ...);
+          const KickB &x = d_kickb(xs...);
           if(x.dust && gas && x.drag)   // timestep.c:673-677
             {
               ax += k.fac2 * x.drag[i];
@@ -145,7 +168,7 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
   double dt = sqrt(2 * k.errtol * k.atime * k.soft[ty] / ac);
   if constexpr(BUNDLE)
     {
-      const KickB &x = (xs, ...);
+      const KickB &x = d_kickb(xs...);
       if(x.dust_timestep && ty == 0 && x.mass[i] > 0)   // timestep.c:710-722
         {
           const double m = x.mass[i];
@@ -181,7 +204,7 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
     }
   if constexpr(BUNDLE)
     {
-      const KickB &x = (xs, ...);
+      const KickB &x = d_kickb(xs...);
       if(x.virt && ty == 3)   // timestep.c:887-897
         {
           if(dt > x.dt_abs)
@@ -258,7 +281,7 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
   bool grain = false;   // timestep.c:410-418: dv = 0, dust_drag has integrated the grain's velocity
   if constexpr(BUNDLE)
     {
-      const KickB &x = (xs, ...);
+      const KickB &x = d_kickb(xs...);
       if(x.virt && ty == 3)
         return;   // timestep.c:375-377: no kick, no force_kick_node
       grain = x.dust && ty == 2;
@@ -294,12 +317,18 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
         {
           v[j] += hy[j] * dt_hydrokick;   // timestep.c:491-494
           double vp = v[j] - dt_gravkick2 * g[j] - dt_hydrokick2 * hy[j];
+          if constexpr((... || std::is_same_v<X, KickR>))   // timestep.c:497-500: VelPred is SET, as the text has it
+            {
+              const double ra = d_kickr(xs...).ra[(size_t) j * ngas + i];
+              v[j] += ra * dt_hydrokick;
+              vp = v[j] - dt_hydrokick2 * ra;
+            }
           if(k.pmgrid)
             vp += pm[j] * k.dt_gravkickB;   // timestep.c:511-513
           velpred[(size_t) j * ngas + i] = vp;
           if constexpr(BUNDLE)
             {
-              const KickB &x = (xs, ...);
+              const KickB &x = d_kickb(xs...);
               if(x.dust && x.drag)
                 x.drag[(size_t) j * ngas + i] = 0.;   // timestep.c:508
             }
@@ -346,6 +375,12 @@ __global__ void k_advance_timesteps(int nact, const int *__restrict__ act, int n
       else
         for(int j = 0; j < 3; j++)
           kick_dv[(size_t) j * n + i] = g[j] * dt_gravkick + (gas ? hy[j] * dt_hydrokick : 0.0);
+      if constexpr((... || std::is_same_v<X, KickR>))   // timestep.c:498
+        {
+          if(gas)
+            for(int j = 0; j < 3; j++)
+              kick_dv[(size_t) j * n + i] += d_kickr(xs...).ra[(size_t) j * ngas + i] * dt_hydrokick;
+        }
       kick_flag[i] = 1;
     }
   for(int j = 0; j < 3; j++)
@@ -617,6 +652,8 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
     }
   KickB x;
   GCHK(kick_bundle_args(ctx, &x, "ghip_advance_timesteps"));
+  KickR r = {nullptr};   // ghip_set_rad_accel: the instantiations with RadAccel, else the kernels as they were
+  GCHK(ghip_rad_accel_field(ctx, "ghip_advance_timesteps", &r.ra));
   // the arguments every instantiation takes, before its pack
 #define KICK_ARGS                                                                                          \
   nact, act, n, ng, k, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),                         \
@@ -627,7 +664,26 @@ extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
     P<double>(ctx->f[GHIP_F_MAXSIGNALVEL]), P<int>(ctx->f[GHIP_F_TIMEBIN]),                                \
     P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), derr, ctx->async ? ghip_errword(ctx, GHIP_ERRW_TIMESTEP) : nullptr, \
     record ? P<double>(ctx->dyn.kick_dv) : nullptr, record ? P<int>(ctx->dyn.kick_flag) : nullptr
-  if(nact > 0 && ctx->visc_on && ctx->visc.time_dependent)
+  if(nact > 0 && r.ra && ctx->visc_on && ctx->visc.time_dependent)
+    {
+      const KickV w = {P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha), ctx->visc.ArtBulkViscConst,
+                       ctx->visc.AlphaMin};
+      if(ctx->iflags_on)
+        {
+          KickBV xw;
+          static_cast<KickB &>(xw) = x;
+          xw.v = w;
+          k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, r, xw);
+        }
+      else
+        k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, r, w);
+      ctx->visc_epoch++;
+    }
+  else if(nact > 0 && r.ra && ctx->iflags_on)
+    k_advance_timesteps<true><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, r, x);
+  else if(nact > 0 && r.ra)
+    k_advance_timesteps<false><<<cdiv(nact, 256), 256, 0, st>>>(KICK_ARGS, r);
+  else if(nact > 0 && ctx->visc_on && ctx->visc.time_dependent)
     {
       const KickV w = {P<double>(ctx->visc_alpha), P<double>(ctx->visc_dtalpha), ctx->visc.ArtBulkViscConst,
                        ctx->visc.AlphaMin};
@@ -790,12 +846,14 @@ extern "C" int ghip_velocity_moments(ghip_ctx *ctx, double v2sum[6], double min_
 // The long-range kick at the end of a PM step (timestep.c:269-345): every particle gets
 // Vel += GravPM * dt_gravkick; the predicted velocity of every gas particle is rebuilt from the new
 // Vel at the current time (its own step's mid-point kicks + the new PM half-step dt_gravkickB).
+// X... is empty for the kernel as it was and one KickR under ghip_set_rad_accel (timestep.c:337-339)
+template <class... X>
 __global__ void k_pm_kick(int n, int ngas, int ti_current, DriftK tab, double dt_gravkick,
                           double dt_gravkickB, const int *__restrict__ type,
                           const int *__restrict__ timebin, const int *__restrict__ ti_begstep,
                           double *__restrict__ vel, const double *__restrict__ gravaccel,
                           const double *__restrict__ gravpm, const double *__restrict__ hydroaccel,
-                          double *__restrict__ velpred)
+                          double *__restrict__ velpred, X... xs)
 {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i >= n)
@@ -826,6 +884,9 @@ __global__ void k_pm_kick(int n, int ngas, int ti_current, DriftK tab, double dt
         velpred[(size_t) j * ngas + i] = v[j] + gravaccel[(size_t) j * n + i] * dt_gravkickA +
                                          hydroaccel[(size_t) j * ngas + i] * dt_hydrokick +
                                          pm[j] * dt_gravkickB;
+      if constexpr(sizeof...(X) > 0)   // timestep.c:337-339: VelPred is SET
+        for(int j = 0; j < 3; j++)
+          velpred[(size_t) j * ngas + i] = v[j] + d_kickr(xs...).ra[(size_t) j * ngas + i] * dt_hydrokick;
     }
 }
 
@@ -859,11 +920,18 @@ extern "C" int ghip_pm_kick(ghip_ctx *ctx, const ghip_pmkick_params *p)
       tab.gravkick = d + DRIFT_TABLE_LENGTH;
       tab.hydrokick = d + 2 * DRIFT_TABLE_LENGTH;
     }
-  k_pm_kick<<<cdiv(n, 256), 256, 0, st>>>(
-    n, ng, p->Ti_Current, tab, p->dt_gravkick, p->dt_gravkickB, P<int>(ctx->f[GHIP_F_TYPE]),
-    P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), P<double>(ctx->f[GHIP_F_VEL]),
-    P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),
-    P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_VELPRED]));
+  KickR r = {nullptr};
+  GCHK(ghip_rad_accel_field(ctx, "ghip_pm_kick", &r.ra));
+#define PMKICK_ARGS                                                                                    \
+  n, ng, p->Ti_Current, tab, p->dt_gravkick, p->dt_gravkickB, P<int>(ctx->f[GHIP_F_TYPE]),             \
+    P<int>(ctx->f[GHIP_F_TIMEBIN]), P<int>(ctx->f[GHIP_F_TI_BEGSTEP]), P<double>(ctx->f[GHIP_F_VEL]),  \
+    P<double>(ctx->f[GHIP_F_GRAVACCEL]), P<double>(ctx->f[GHIP_F_GRAVPM]),                             \
+    P<double>(ctx->f[GHIP_F_HYDROACCEL]), P<double>(ctx->f[GHIP_F_VELPRED])
+  if(r.ra)
+    k_pm_kick<<<cdiv(n, 256), 256, 0, st>>>(PMKICK_ARGS, r);
+  else
+    k_pm_kick<<<cdiv(n, 256), 256, 0, st>>>(PMKICK_ARGS);
+#undef PMKICK_ARGS
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }

@@ -1,0 +1,1056 @@
+// ghip_wind.hip -- the wind particles of the reference's shipped flag bundle (-DVIRTUAL -DFB_MOMENTUM): the
+// propagation loop of momentum_feedback() with its two neighbour passes.  VIRTUAL_FLY_THORUGH_EMPTY_SPACE,
+// VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL are switches of ghip_wind_params.  Not built: spawning
+// (momentum_feedback.c:70-245, host code), fb_particles.c, REAL_EOS, NON_GRAY_RAD_TRANSFER, shards and ranks.
+//
+// Replaces the particle loops of
+//   momentum_feedback, the loop and the elimination   momentum_feedback.c:283-568
+//   virtual_density / virtual_evaluate_select         virtual_density.c:79-378, 382-625
+//   virtual_spread_momentum / _evaluate_onthespot     virtual_spread_momentum.c:58-308, 310-469
+//   ngb_treefind_virtual_active                       virtual_density.c:628-748
+//
+// Wind particles are many and cheap, so a particle is a THREAD, as a grain is (ghip_dust.hip).  The list is
+// ordered once per call by the particles' place in the gravity tree (a radix sort of the tree's inverse
+// permutation), so that the 64 lanes of a wavefront walk neighbouring parts of the gas tree; the active list of
+// every iteration is an order-preserving selection of that order.  It is NOT re-ordered inside the loop: a
+// particle moves at most 0.2 Hsml per iteration, which is less than the width of the leaves its lanes share,
+// and a re-sort would cost a sort per iteration, about what the density pass costs.
+//
+// The scatter into the gas: the pairs (gas j, wind slot a) are counted in the density pass, written as 64-bit
+// keys (j << 32 | a) with their kernel weight, radix sorted, and one thread per gas particle adds its run of
+// pairs in list order.  No floating-point atomics; every sum is a per-thread loop in a fixed order: two
+// identical calls give identical bits, whatever the launch order of the list.
+//
+// ONE DELIBERATE DEVIATION from the C text (tests/wind_ref.py takes it too): when the time cap of
+// momentum_feedback.c:345-346 sets the jump, dt1 = dt_jump exactly and the particle ends the iteration with
+// dt_jump = 0.  The reference recomputes dt1 = dr * U / C * FBV (:348) and subtracts it (:371-372); the residue
+// of that round trip is 0 or +-1 ulp, and on its sign hangs one more iteration of length ~1e-17.
+//
+// no a*b+c -> fma contraction in this file (before the headers, so that their inline functions follow): every
+// comparison below decides with the C text's own roundings.
+#pragma clang fp contract(off)
+
+#include <chrono>
+#include <climits>
+
+#include "ghip_ngb.h"
+#include "ghip_prim.h"
+
+#define WIND_C 2.9979e10          // allvars.h:86
+#define WIND_THOMPSON 6.65245e-25 // allvars.h:91
+#define WIND_LEAF 16              // a tree node with at most this many particles is swept flat
+
+// per-particle planes of wind_work ([WIND_NPLANES][nw] doubles, list order)
+enum
+{
+  WP_AGE = 0,   // in      StellarAge
+  WP_BIRTH,     // in      BirthPhotonEnergy
+  WP_OLD,       // in/out  OldPhotonMomentum
+  WP_RHO,       // in/out  NewDensity
+  WP_DRMIN,     // in/out  b1.BH_Density
+  WP_DT1,       // out
+  WP_DT2,       // out
+  WP_DTJ,       // out     DtJump
+  WP_DMOM,      // out     DeltaPhotonMomentum
+  WP_VX,        // Vel [3] of the particle and |Vel| (virtual_spread_momentum.c:391), gathered once per call
+  WP_VY,
+  WP_VZ,
+  WP_VABS,
+  WIND_NPLANES
+};
+#define WIND_NIN (WP_DRMIN + 1)           // planes uploaded by ghip_wind_feedback
+#define WIND_NOUT (WP_DMOM - WP_OLD + 1)  // planes read back: WP_OLD .. WP_DMOM
+
+struct WindK
+{
+  BoxK b;
+  double Time, dt_fac, dt_fac_gas, fbv, uvel, udens, ulength, xsec, vmass, vtime, outer;
+  double desngb, ogm, softgas, softgasmax, softbulgemax, psr;
+  int fly, varsr;
+};
+
+// what the host reads once per iteration
+struct WindWords
+{
+  unsigned long long npairs;   // pairs of this iteration's spread pass
+  int npos;                    // listed particles with dt_jump > 0: the passes' list
+  int nunder;                  // ... with dt_jump > 1e-40: the reference's NextPhoton list (:446)
+  int err;                     // a listed particle is not Type 3
+  int pad;
+  double dt_total;
+  unsigned long long hmax;     // bits of the largest Hsml of the gas with Mass > 0 (+inf if one is not > 0 and finite)
+};
+
+// The largest h_j of the gas that can be anybody's neighbour, once per call (the gas does not change inside the
+// loop).  A pair contributes to a density or receives momentum only where r < h_j <= hmax, so those walks search
+// min(Hsml, hmax) instead of the wind particle's own Hsml, which momentum_feedback.c:400 makes three times the
+// radius of DesNumNgb neighbours: two orders of magnitude fewer candidates, the same pairs in the same order.
+// (The bit patterns of positive doubles order like unsigned integers: an integer atomic, exact.)
+__global__ void k_wind_hmax(int ngas, const double *__restrict__ hsml, const double *__restrict__ mass,
+                            const int *__restrict__ type, WindWords *words)
+{
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long b = 0;
+  if(j < ngas && type[j] == 0 && mass[j] > 0)
+    {
+      const double h = hsml[j];
+      b = (h > 0 && h < 1.e300) ? (unsigned long long) __double_as_longlong(h) : 0x7ff0000000000000ULL;
+    }
+  for(int o = 32; o > 0; o >>= 1)
+    {
+      const unsigned long long x = __shfl_down(b, o, 64);
+      b = x > b ? x : b;
+    }
+  if((threadIdx.x & 63) == 0 && b)
+    atomicMax(&words->hmax, b);
+}
+
+// sort key of list slot a: its place in the gravity tree
+__global__ void k_wind_order_keys(int nw, const int *__restrict__ idx, const int *__restrict__ iperm,
+                                  unsigned int *__restrict__ key, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nw)
+    return;
+  key[a] = (unsigned int) iperm[idx[a]];
+  slot[a] = a;
+}
+
+// the velocity planes of the list; a particle that is not Type 3 raises words->err
+__global__ void k_wind_vel(int nw, const int *__restrict__ idx, int n, const int *__restrict__ type,
+                           const double *__restrict__ vel, double *__restrict__ w, WindWords *words)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nw)
+    return;
+  const int i = idx[a];
+  const size_t N = (size_t) n, D = (size_t) nw;
+  if(type[i] != 3)
+    atomicMax(&words->err, 1);
+  const double v0 = vel[i], v1 = vel[N + i], v2 = vel[2 * N + i];
+  w[WP_VX * D + a] = v0;
+  w[WP_VY * D + a] = v1;
+  w[WP_VZ * D + a] = v2;
+  w[WP_VABS * D + a] = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+}
+
+// momentum_feedback.c:285-293
+__global__ void k_wind_init(int nw, const int *__restrict__ idx, const int *__restrict__ timebin,
+                            double *__restrict__ w, int *__restrict__ deleted, double dt_fac)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nw)
+    return;
+  const size_t D = (size_t) nw;
+  const int tb = timebin[idx[a]] & 31;
+  w[WP_DTJ * D + a] = (tb ? (double) (1 << tb) : 0.0) * dt_fac;
+  w[WP_DT1 * D + a] = 0.;
+  w[WP_DT2 * D + a] = 0.;
+  w[WP_DMOM * D + a] = 0.;
+  deleted[a] = 0;
+}
+
+// sum of x[0, nw) in a fixed order: thread t adds x[t], x[t + 1024], ...; then a tree over the threads
+__global__ void __launch_bounds__(1024) k_wind_sum(int nw, const double *__restrict__ x, double *__restrict__ out)
+{
+  __shared__ double s[1024];
+  double c = 0;
+  for(int a = threadIdx.x; a < nw; a += 1024)
+    c += x[a];
+  s[threadIdx.x] = c;
+  __syncthreads();
+  for(unsigned int o = 512; o > 0; o >>= 1)
+    {
+      if(threadIdx.x < o)
+        s[threadIdx.x] += s[threadIdx.x + o];
+      __syncthreads();
+    }
+  if(threadIdx.x == 0)
+    *out = s[0];
+}
+
+// flags[t] = the t-th particle of the list has dt_jump > 0; counts those above 1e-40 (:446)
+__global__ void __launch_bounds__(256) k_wind_flags(int m, const int *__restrict__ list, const double *__restrict__ dtj,
+                                                    int *__restrict__ flags, WindWords *words)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  bool under = false;
+  if(t < m)
+    {
+      const double d = dtj[list[t]];
+      flags[t] = d > 0.;
+      under = d > 1.e-40;
+    }
+  const unsigned long long bal = __ballot(under);
+  if((threadIdx.x & 63) == 0 && bal)
+    atomicAdd(&words->nunder, __popcll(bal));
+}
+
+__global__ void k_wind_reset(int nw, double *__restrict__ w)   // virtual_density.c:107-127
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nw)
+    return;
+  w[(size_t) WP_RHO * nw + a] = 0.;
+  w[(size_t) WP_DRMIN * nw + a] = 1.e40;
+}
+
+// One candidate of ngb_treefind_virtual_active (virtual_density.c:650-664) and the pair geometry of
+// virtual_evaluate_select (:495-524): a gas particle of this context with Mass > 0 within the wind particle's
+// own h; r and the gas particle's h_j come back.  The nearest image is the text's two comparisons per axis
+// (d_wrap, ghip_ngb.h).
+__device__ __forceinline__ bool d_wind_pair(int j, int n, int ngas, const double *__restrict__ pos,
+                                            const double *__restrict__ hsml, const double *__restrict__ mass,
+                                            const int *__restrict__ type, double px, double py, double pz, double h,
+                                            const BoxK b, double &r, double &hj)
+{
+  if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0))
+    return false;
+  const double dx = d_wrap(px - pos[j], b), dy = d_wrap(py - pos[(size_t) n + j], b),
+               dz = d_wrap(pz - pos[2 * (size_t) n + j], b);
+  const double r2 = dx * dx + dy * dy + dz * dz;
+  if(r2 > h * h)
+    return false;
+  r = sqrt(r2);
+  hj = hsml[j];
+  return true;
+}
+
+// virtual_evaluate_select for the m particles of the list: those with dt_jump > 0 are evaluated, the others
+// reset.  cnt != nullptr: cnt[t] = the pairs the spread pass will write for the t-th particle (u < 1, and none
+// where new_density comes out 0).
+__global__ void __launch_bounds__(64)
+k_wind_density(int m, const int *__restrict__ list, const int *__restrict__ idx, int n, int ngas,
+               const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
+               const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
+               const int *__restrict__ perm, BoxK b, int nw, double *__restrict__ w,
+               unsigned long long *__restrict__ cnt, const WindWords *__restrict__ words)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= m)
+    return;
+  const int a = list[t];
+  const size_t D = (size_t) nw;
+  double rho = 0., drmin = 1.e40;
+  unsigned long long c = 0;
+  if(w[WP_DTJ * D + a] > 0.)
+    {
+      const int i = idx[a];
+      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i], h = hsml[i];
+      // every pair with u < 1 has r < h_j <= hmax: this walk meets them all, in the order the walk of the whole
+      // sphere h would (its nodes are a subset in the same pre-order)
+      const double hmax = __longlong_as_double((long long) words->hmax);
+      const double r1 = fmin(h, hmax);
+      d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
+        double r, hj;
+        const int j = perm[p];
+        if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
+          return;
+        const double drcheck = fabs(r - hj) + 0.25 * hj;   // :519-520
+        if(drcheck < drmin)
+          drmin = drcheck;
+        const double u = r / hj;
+        if(u < 1)
+          {
+            const double hinv = 1 / hj;
+            rho += mass[j] * d_spline_wk(u, hinv * hinv * hinv);
+            c++;
+          }
+      });
+      // drmin is a minimum over the whole sphere h.  |r - h_j| + h_j / 4 >= r - 3/4 hmax: beyond
+      // r2 = drmin + 3/4 hmax nothing can lower it (a little further, for the roundings of the two sides)
+      if(r1 < h)
+        {
+          const double r2 = fmin(h, (drmin + 0.75 * hmax) * (1. + 1.e-9));
+          if(r2 > r1)
+            d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r2, b, [&](int p) {
+              double r, hj;
+              const int j = perm[p];
+              if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
+                return;
+              const double drcheck = fabs(r - hj) + 0.25 * hj;
+              if(drcheck < drmin)
+                drmin = drcheck;
+            });
+        }
+    }
+  w[WP_RHO * D + a] = rho;
+  w[WP_DRMIN * D + a] = drmin;
+  if(cnt)
+    cnt[t] = rho > 0. ? c : 0;
+}
+
+// the pairs of virtual_evaluate_onthespot (virtual_spread_momentum.c:129-130, 393-419) for the m particles of
+// the list.  fill == 0: count them into cnt[t]; fill == 1: write (j << 32 | a, W) from off[t] on.
+template <int fill>
+__global__ void __launch_bounds__(64)
+k_wind_pairs(int m, const int *__restrict__ list, const int *__restrict__ idx, int n, int ngas,
+             const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
+             const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
+             const int *__restrict__ perm, BoxK b, int nw, const double *__restrict__ w,
+             unsigned long long *__restrict__ cnt, const unsigned long long *__restrict__ off,
+             unsigned long long npairs, unsigned long long *__restrict__ key, double *__restrict__ wgt,
+             const WindWords *__restrict__ words)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= m)
+    return;
+  const int a = list[t];
+  const size_t D = (size_t) nw;
+  unsigned long long c = 0;
+  if(w[WP_RHO * D + a] > 0. && w[WP_DTJ * D + a] > 0.)
+    {
+      const unsigned long long o = fill ? off[t] : 0;
+      const int i = idx[a];
+      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i], h = hsml[i];
+      const double r1 = fmin(h, __longlong_as_double((long long) words->hmax));   // (as k_wind_density)
+      d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
+        double r, hj;
+        const int j = perm[p];
+        if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
+          return;
+        const double u = r / hj;
+        if(!(u < 1))
+          return;
+        if(fill)
+          {
+            if(o + c < npairs)   // (the count of the same walk: never false)
+              {
+                const double hinv = 1 / hj;
+                key[o + c] = ((unsigned long long) j << 32) | (unsigned int) a;
+                wgt[o + c] = d_spline_wk(u, hinv * hinv * hinv);
+              }
+          }
+        c++;
+      });
+    }
+  if(!fill)
+    cnt[t] = c;
+}
+
+// the momentum one gas particle receives from its run of sorted pairs, in list order
+// (virtual_spread_momentum.c:432, 447-448)
+__global__ void k_wind_apply(long long npairs, const unsigned long long *__restrict__ key,
+                             const double *__restrict__ wgt, int nw, const double *__restrict__ w,
+                             const double *__restrict__ mass, int ngas, double *__restrict__ inj)
+{
+  const long long s0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+  if(s0 >= npairs)
+    return;
+  const unsigned int j = (unsigned int) (key[s0] >> 32);
+  if(s0 > 0 && (unsigned int) (key[s0 - 1] >> 32) == j)
+    return;   // not the first pair of its gas particle
+  if(j >= (unsigned int) ngas)
+    return;
+  const size_t D = (size_t) nw, G = (size_t) ngas;
+  const double mj = mass[j];
+  double i0 = inj[j], i1 = inj[G + j], i2 = inj[2 * G + j];
+  for(long long s = s0; s < npairs && (unsigned int) (key[s] >> 32) == j; s++)
+    {
+      const unsigned int a = (unsigned int) (key[s] & 0xffffffffULL);
+      if(a >= (unsigned int) nw)
+        continue;
+      const double ddpm = w[WP_DMOM * D + a] * mj * wgt[s] / w[WP_RHO * D + a];
+      const double va = w[WP_VABS * D + a];
+      i0 += ddpm * w[WP_VX * D + a] / va;
+      i1 += ddpm * w[WP_VY * D + a] / va;
+      i2 += ddpm * w[WP_VZ * D + a] / va;
+    }
+  inj[j] = i0;
+  inj[G + j] = i1;
+  inj[2 * G + j] = i2;
+}
+
+// momentum_feedback.c:312-427 for the m particles of the list (all have dt_jump > 0; the reference's own list
+// holds those above 1e-40)
+__global__ void k_wind_move(int m, const int *__restrict__ list, const int *__restrict__ idx, int n,
+                            double *__restrict__ pos, double *__restrict__ hsml, double *__restrict__ mass, int nw,
+                            double *__restrict__ w, WindK K)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= m)
+    return;
+  const int a = list[t];
+  const size_t D = (size_t) nw, N = (size_t) n;
+#define PL(q) w[(size_t) (q) * D + a]
+  double dt_bh = PL(WP_DTJ);
+  if(!(dt_bh > 1.e-40))
+    return;
+  const int i = idx[a];
+  const double newdens = PL(WP_RHO);
+  double h = hsml[i];
+  double desired_dr = 0.2 * h;
+  if(K.fly)   // :337-340
+    {
+      const double lim = 0.5 * PL(WP_DRMIN) + 2. * K.softgas;
+      if(desired_dr > lim)
+        desired_dr = lim;
+    }
+  const double cap = WIND_C * dt_bh / K.uvel / K.fbv;   // :345-346
+  const bool capped = desired_dr > cap;
+  if(capped)
+    desired_dr = cap;
+  // :348, and the deviation: the capped jump takes all the time that is left
+  double dt1 = capped ? dt_bh : desired_dr * K.uvel / WIND_C * K.fbv;
+  const double dtau_max = 10. * desired_dr / h;
+  double dtau = K.xsec * WIND_THOMPSON / PROTONMASS * newdens * desired_dr * K.udens * K.ulength;
+  if(dtau > dtau_max)
+    dtau = dtau_max;
+  double old = PL(WP_OLD);
+  const double dmom = old * (1. - exp(-dtau));
+  old -= dmom;
+  PL(WP_DMOM) = dmom;
+  PL(WP_OLD) = old;
+  mass[i] = K.vmass * old;
+  double x[3];
+  for(int k = 0; k < 3; k++)
+    {
+      x[k] = pos[k * N + i] + dt1 * PL(WP_VX + k);
+      pos[k * N + i] = x[k];
+    }
+  double dtj = capped ? 0. : dt_bh - dt1;
+  double dt2 = PL(WP_DT2) + dt1;
+  if(K.b.periodic)   // :382-395
+    for(int k = 0; k < 3; k++)
+      {
+        if(x[k] > K.b.boxhalf)
+          x[k] -= K.b.boxsize;
+        if(x[k] < -K.b.boxhalf)
+          x[k] += K.b.boxsize;
+      }
+  const double r2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+  if(newdens > 0)   // :398-405
+    h = 3. * pow((K.desngb * K.ogm / (newdens + 1.e-38)), 0.33333) + K.softgasmax;
+  else
+    h *= 1.2;
+  if(K.varsr)   // :409-410
+    {
+      const double lim = K.psr * sqrt(r2) + K.softbulgemax;
+      if(h > lim)
+        h = lim;
+    }
+  hsml[i] = h;
+  if(old < 0.01 * PL(WP_BIRTH) / WIND_C * K.uvel)   // :417-424: hide it
+    {
+      dt2 += dtj;
+      dtj = 0.;
+      dt1 = 0.;
+    }
+  PL(WP_DTJ) = dtj;
+  PL(WP_DT2) = dt2;
+  PL(WP_DT1) = dt1;
+#undef PL
+}
+
+// momentum_feedback.c:550-568
+__global__ void k_wind_eliminate(int nw, const int *__restrict__ idx, int n, const double *__restrict__ pos,
+                                 double *__restrict__ mass, const double *__restrict__ w,
+                                 int *__restrict__ deleted, WindK K)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nw)
+    return;
+  const int i = idx[a];
+  const size_t D = (size_t) nw, N = (size_t) n;
+  int code = 0;
+  if(mass[i] != 0.)
+    {
+      const double x = pos[i], y = pos[N + i], z = pos[2 * N + i];
+      const double r = sqrt(x * x + y * y + z * z);
+      if(r > K.outer || K.Time - w[WP_AGE * D + a] > K.vtime)
+        code = 1;
+      else if(w[WP_OLD * D + a] < 0.01 * w[WP_BIRTH * D + a] / WIND_C * K.uvel)
+        code = 2;
+      if(code)
+        mass[i] = 0.;
+    }
+  deleted[a] = code;
+}
+
+// momentum_feedback.c:497-538 for the active gas
+__global__ void k_wind_rad_accel(int nact, const int *__restrict__ act, int ngas, const int *__restrict__ type,
+                                 const int *__restrict__ timebin, const double *__restrict__ mass,
+                                 double *__restrict__ inj, double *__restrict__ ra, double dt_fac_gas)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if(t >= nact)
+    return;
+  const int i = act ? act[t] : t;
+  if(i < 0 || i >= ngas || type[i] != 0)
+    return;
+  const size_t G = (size_t) ngas;
+  const int tb = timebin[i] & 31;
+  const double dt = (tb ? (double) (1 << tb) : 0.0) * dt_fac_gas;
+  const double m = mass[i];
+  double r[3] = {0., 0., 0.};
+  if(dt != 0. && m > 0.)
+    {
+      for(int k = 0; k < 3; k++)
+        r[k] = inj[k * G + i] / dt / m;
+      const double ac = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+      const double acmax = 1.e4 / dt;
+      if(ac >= acmax)
+        for(int k = 0; k < 3; k++)
+          r[k] *= (acmax / ac);
+    }
+  for(int k = 0; k < 3; k++)
+    {
+      ra[k * G + i] = r[k];
+      inj[k * G + i] = 0.;
+    }
+}
+
+__global__ void k_wind_npairs(const unsigned long long *__restrict__ off, int m, WindWords *words)
+{
+  if(blockIdx.x == 0 && threadIdx.x == 0)
+    words->npairs = off[m];
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static WindK wind_k(const ghip_wind_params *p)
+{
+  WindK K;
+  K.b = make_box(p->BoxSize, p->periodic);
+  K.Time = p->Time;
+  K.dt_fac = p->dt_fac;
+  K.dt_fac_gas = p->dt_fac_gas;
+  K.fbv = p->FeedBackVelocity;
+  K.uvel = p->UnitVelocity_in_cm_per_s;
+  K.udens = p->UnitDensity_in_cgs;
+  K.ulength = p->UnitLength_in_cm;
+  K.xsec = p->VirtualCrosSection;
+  K.vmass = p->VirtualMass;
+  K.vtime = p->VirtualTime;
+  K.outer = p->OuterBoundary;
+  K.desngb = p->DesNumNgb;
+  K.ogm = p->OriginalGasMass;
+  K.softgas = p->SofteningGas;
+  K.softgasmax = p->SofteningGasMaxPhys;
+  K.softbulgemax = p->SofteningBulgeMaxPhys;
+  K.psr = p->PhotonSearchRadius;
+  K.fly = p->fly_through_empty_space != 0;
+  K.varsr = p->variable_search_radius != 0;
+  return K;
+}
+
+static bool wind_sharded(const ghip_ctx *ctx)
+{
+  return ctx->shard_n > 1 || ctx->dd.on;
+}
+
+static int wind_refuse_sharded(ghip_ctx *ctx, const char *who)
+{
+  if(wind_sharded(ctx))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded or multi-GPU context (ghip_set_shard / "
+                     "ghip_dd_init): the wind passes are single-rank only", who);
+  return GHIP_OK;
+}
+
+// the device arrays of a call
+struct WindDev
+{
+  int nw;
+  int *idx, *ord, *lista, *listb, *flags, *deleted;
+  WindWords *words;
+  double *w;
+  unsigned long long *cnt, *off;
+};
+
+static WindDev wind_dev(ghip_ctx *ctx, int nw)
+{
+  const size_t D = (size_t) nw;
+  WindDev d;
+  d.nw = nw;
+  // wind_idx: idx | ord | key | key' | slot | list A | list B | flags | deleted   ([nw] each)  | WindWords
+  d.idx = P<int>(ctx->wind_idx);
+  d.ord = d.idx + D;
+  d.lista = d.idx + 5 * D;
+  d.listb = d.idx + 6 * D;
+  d.flags = d.idx + 7 * D;
+  d.deleted = d.idx + 8 * D;
+  d.words = reinterpret_cast<WindWords *>(reinterpret_cast<char *>(ctx->wind_idx.p) + ((9 * D * 4 + 63) & ~(size_t) 63));
+  // wind_work: planes [WIND_NPLANES][nw] | cnt [nw + 1] | off [nw + 1]   (64-bit)
+  d.w = P<double>(ctx->wind_work);
+  d.cnt = reinterpret_cast<unsigned long long *>(d.w + WIND_NPLANES * D);
+  d.off = d.cnt + D + 1;
+  return d;
+}
+
+// What every entry point asks of the context; then the list to the device, its tree order into `ord`, the
+// velocity planes, and words->err raised where an index does not name a Type-3 particle
+static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const int *idx, const char *who, WindDev *out)
+{
+  GCHK(wind_refuse_sharded(ctx, who));
+  if(!p || nw < 0 || (nw > 0 && !idx))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  out->nw = nw;
+  if(nw == 0)
+    return GHIP_OK;
+  if(ctx->ngas > 0)
+    GCHK(ghip_finish_gas_tree(ctx));
+  if(!ctx->gt.built || (ctx->ngas > 0 && !ctx->st.built))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
+  for(int a = 0; a < nw; a++)
+    if(idx[a] < 0 || idx[a] >= ctx->n)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range", who, idx[a]);
+  hipStream_t st = ctx->stream;
+  const size_t D = (size_t) nw;
+  GCHK(ghip_ensure(ctx, ctx->wind_idx, ((9 * D * 4 + 63) & ~(size_t) 63) + 64));
+  GCHK(ghip_ensure(ctx, ctx->wind_work, (WIND_NPLANES * D + 2 * (D + 1)) * 8 + 256));
+  const WindDev d = wind_dev(ctx, nw);
+  *out = d;
+  HIPCHK(hipMemcpyAsync(d.idx, idx, D * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d.words, 0, sizeof(WindWords), st));
+  unsigned int *dkey = reinterpret_cast<unsigned int *>(d.idx + 2 * D), *dkey2 = dkey + D;
+  int *dslot = d.idx + 4 * D;
+  k_wind_order_keys<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->gt.iperm), dkey, dslot);
+  HIPCHK(hipGetLastError());
+  const long long nsorted = ctx->gt.n > ctx->n ? ctx->gt.n : ctx->n;
+  int end_bit = 1;
+  while(end_bit < 32 && (1LL << end_bit) <= nsorted)
+    end_bit++;
+  GCHK(ghip_sort_pairs(ctx, dkey, dkey2, dslot, d.ord, nw, end_bit, st));
+  k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
+                                            P<double>(ctx->f[GHIP_F_VEL]), d.w, d.words);
+  if(ctx->ngas > 0)
+    k_wind_hmax<<<cdiv(ctx->ngas, 256), 256, 0, st>>>(ctx->ngas, P<double>(ctx->f[GHIP_F_HSML]),
+                                                      P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]),
+                                                      d.words);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+static int wind_type_error(ghip_ctx *ctx, const char *who)
+{
+  return ghip_fail(ctx, GHIP_EINVAL, "%s: wind_idx names a particle that is not Type 3", who);
+}
+
+// a resident gas field [3][ngas]: made and zeroed at first use, refused when it holds another gas count
+static int wind_gas_field(ghip_ctx *ctx, DevBuf &b, int *held, const char *name, const char *setter, const char *who)
+{
+  const int ng = ctx->ngas;
+  if(*held >= 0 && *held != ng)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: %s is held for %d gas particles, the context has %d (%s again)", who,
+                     name, *held, ng, setter);
+  if(*held < 0)
+    {
+      const size_t bytes = 3 * (size_t) (ng > 0 ? ng : 1) * 8;
+      GCHK(ghip_ensure(ctx, b, bytes));
+      HIPCHK(hipMemsetAsync(b.p, 0, bytes, ctx->stream));
+      *held = ng;
+    }
+  return GHIP_OK;
+}
+
+static int wind_injected(ghip_ctx *ctx, const char *who)
+{
+  return wind_gas_field(ctx, ctx->wind_inj, &ctx->wind_inj_ngas, "Injected_BH_Momentum", "ghip_wind_set_injected", who);
+}
+
+static int wind_rad_accel(ghip_ctx *ctx, const char *who)
+{
+  return wind_gas_field(ctx, ctx->wind_ra, &ctx->wind_ra_ngas, "RadAccel", "ghip_wind_set_rad_accel", who);
+}
+
+// the resident fields and tree of the gas as the kernels take them
+#define WIND_GAS_ARGS                                                                                         \
+  ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),                           \
+    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), ctx->ngas > 0 ? ctx->st.nelem : 0,           \
+    P<SphNode>(ctx->st.mq), P<int>(ctx->st.perm)
+
+// The scatter of the m particles of `list` (cnt[0, m) counted, cnt[m] = 0, scanned into off; npairs = off[m]):
+// fill, sort, apply
+static int wind_scatter(ghip_ctx *ctx, const WindDev &d, const BoxK &b, int m, const int *list, long long npairs)
+{
+  if(npairs < 0 || npairs > (long long) INT_MAX)
+    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_wind: %lld wind-gas pairs", npairs);
+  if(npairs == 0 || m == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const size_t np = (size_t) npairs;
+  // wind_pairs: key [np] | key' [np] | W [np] | W' [np]
+  GCHK(ghip_ensure(ctx, ctx->wind_pairs, np * 32 + 256));
+  unsigned long long *k0 = P<unsigned long long>(ctx->wind_pairs), *k1 = k0 + np;
+  double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
+  k_wind_pairs<1><<<cdiv(m, 64), 64, 0, st>>>(m, list, d.idx, WIND_GAS_ARGS, b, d.nw, d.w, nullptr, d.off,
+                                              (unsigned long long) npairs, k0, w0, d.words);
+  HIPCHK(hipGetLastError());
+  int end_bit = 33;
+  while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
+    end_bit++;
+  GCHK(ghip_sort_pairs(ctx, k0, k1, w0, w1, (int) np, end_bit, st));
+  k_wind_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, d.nw, d.w, P<double>(ctx->f[GHIP_F_MASS]),
+                                                  ctx->ngas, P<double>(ctx->wind_inj));
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// host [m][3] <-> device planes [3][m]
+static int wind_upload3(ghip_ctx *ctx, DevBuf &b, const double *h, int m)
+{
+  GCHK(ghip_ensure(ctx, b, 3 * (size_t) (m > 0 ? m : 1) * 8));
+  std::vector<double> t(3 * (size_t) m);
+  for(int a = 0; a < m; a++)
+    for(int j = 0; j < 3; j++)
+      t[(size_t) j * m + a] = h[3 * (size_t) a + j];
+  if(m > 0)
+    HIPCHK(hipMemcpyAsync(b.p, t.data(), t.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  return GHIP_OK;
+}
+
+static int wind_download3(ghip_ctx *ctx, const DevBuf &b, double *h, int m)
+{
+  std::vector<double> t(3 * (size_t) m);
+  if(m > 0)
+    HIPCHK(hipMemcpyAsync(t.data(), b.p, t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(int a = 0; a < m; a++)
+    for(int j = 0; j < 3; j++)
+      h[3 * (size_t) a + j] = t[(size_t) j * m + a];
+  return GHIP_OK;
+}
+
+extern "C" size_t ghip_wind_params_size(void)
+{
+  return sizeof(ghip_wind_params);
+}
+
+extern "C" int ghip_wind_density(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                                 const double *dt_jump, double *new_density, double *drmin)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_density";
+  if(nwind > 0 && (!dt_jump || !new_density || !drmin))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  WindDev d;
+  GCHK(wind_begin(ctx, p, nwind, wind_idx, who, &d));
+  if(nwind == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const size_t D = (size_t) nwind;
+  HIPCHK(hipMemcpyAsync(d.w + WP_DTJ * D, dt_jump, D * 8, hipMemcpyHostToDevice, st));
+  k_wind_density<<<cdiv(nwind, 64), 64, 0, st>>>(nwind, d.ord, d.idx, WIND_GAS_ARGS, make_box(p->BoxSize, p->periodic),
+                                                 nwind, d.w, nullptr, d.words);
+  HIPCHK(hipGetLastError());
+  WindWords h;
+  HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+  // (WP_RHO and WP_DRMIN are neighbours)
+  std::vector<double> o(2 * D);
+  HIPCHK(hipMemcpyAsync(o.data(), d.w + WP_RHO * D, 2 * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(h.err)
+    return wind_type_error(ctx, who);
+  memcpy(new_density, o.data(), D * 8);
+  memcpy(drmin, o.data() + D, D * 8);
+  return GHIP_OK;
+}
+
+extern "C" int ghip_wind_spread(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                                const double *dt_jump, const double *new_density, const double *delta_momentum)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_spread";
+  if(nwind > 0 && (!dt_jump || !new_density || !delta_momentum))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  WindDev d;
+  GCHK(wind_begin(ctx, p, nwind, wind_idx, who, &d));
+  GCHK(wind_injected(ctx, who));
+  if(nwind == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const size_t D = (size_t) nwind;
+  const BoxK b = make_box(p->BoxSize, p->periodic);
+  HIPCHK(hipMemcpyAsync(d.w + WP_DTJ * D, dt_jump, D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d.w + WP_RHO * D, new_density, D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d.w + WP_DMOM * D, delta_momentum, D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(d.cnt, 0, (D + 1) * 8, st));
+  k_wind_pairs<0><<<cdiv(nwind, 64), 64, 0, st>>>(nwind, d.ord, d.idx, WIND_GAS_ARGS, b, nwind, d.w, d.cnt, nullptr,
+                                                  0ULL, nullptr, nullptr, d.words);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, nwind + 1, st));
+  k_wind_npairs<<<1, 64, 0, st>>>(d.off, nwind, d.words);
+  HIPCHK(hipGetLastError());
+  WindWords h;
+  HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));   // the pair count sizes the sort
+  if(h.err)
+    return wind_type_error(ctx, who);
+  return wind_scatter(ctx, d, b, nwind, d.ord, (long long) h.npairs);
+}
+
+// the out planes back to the caller's arrays
+static int wind_download_state(ghip_ctx *ctx, const WindDev &d, const ghip_wind_state *s, bool inout)
+{
+  const size_t D = (size_t) d.nw;
+  hipStream_t st = ctx->stream;
+  std::vector<double> h(WIND_NOUT * D);
+  HIPCHK(hipMemcpyAsync(h.data(), d.w + WP_OLD * D, WIND_NOUT * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(s->deleted, d.deleted, D * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  auto plane = [&](int q) { return h.data() + (size_t) (q - WP_OLD) * D; };
+  if(inout)
+    {
+      memcpy(s->old_momentum, plane(WP_OLD), D * 8);
+      memcpy(s->new_density, plane(WP_RHO), D * 8);
+      memcpy(s->drmin, plane(WP_DRMIN), D * 8);
+    }
+  memcpy(s->dt1, plane(WP_DT1), D * 8);
+  memcpy(s->dt2, plane(WP_DT2), D * 8);
+  memcpy(s->dt_jump, plane(WP_DTJ), D * 8);
+  memcpy(s->delta_momentum, plane(WP_DMOM), D * 8);
+  return GHIP_OK;
+}
+
+extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                                  const ghip_wind_state *s, ghip_wind_result *result)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_feedback";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if(result)
+    memset(result, 0, sizeof(*result));
+  if(!result || !p || (nwind > 0 && (!s || !s->stellar_age || !s->birth_energy || !s->old_momentum ||
+                                     !s->new_density || !s->drmin || !s->dt1 || !s->dt2 || !s->dt_jump ||
+                                     !s->delta_momentum || !s->deleted)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(p->max_iter < 1 || !(p->dt_fac >= 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
+  WindDev d;
+  GCHK(wind_begin(ctx, p, nwind, wind_idx, who, &d));
+  for(int k = 0; k < 5; k++)
+    ctx->wind_ms[k] = 0;
+  if(nwind == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const int nw = nwind;
+  const size_t D = (size_t) nw;
+  const WindK K = wind_k(p);
+  for(int k = 0; k < 6; k++)
+    if(!ctx->wind_ev[k])
+      HIPCHK(hipEventCreate(&ctx->wind_ev[k]));
+  hipEvent_t *ev = ctx->wind_ev;
+
+  // ---- the state in; dt_jump, its sum and the first list (:285-302) ----
+  {
+    std::vector<double> h(WIND_NIN * D);
+    memcpy(h.data() + WP_AGE * D, s->stellar_age, D * 8);
+    memcpy(h.data() + WP_BIRTH * D, s->birth_energy, D * 8);
+    memcpy(h.data() + WP_OLD * D, s->old_momentum, D * 8);
+    memcpy(h.data() + WP_RHO * D, s->new_density, D * 8);
+    memcpy(h.data() + WP_DRMIN * D, s->drmin, D * 8);
+    HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
+  }
+  k_wind_init<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->f[GHIP_F_TIMEBIN]), d.w, d.deleted, K.dt_fac);
+  k_wind_sum<<<1, 1024, 0, st>>>(nw, d.w + WP_DTJ * D, &d.words->dt_total);
+  k_wind_flags<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.ord, d.w + WP_DTJ * D, d.flags, d.words);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, d.ord, d.flags, d.lista, &d.words->npos, nw, st));
+  WindWords h;
+  HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(h.err)
+    return wind_type_error(ctx, who);
+  if(h.dt_total <= p->dt_total_floor)   // :302: the loop is not entered, nothing changes
+    return wind_download_state(ctx, d, s, false);
+  GCHK(wind_injected(ctx, who));
+  if(p->rad_accel)
+    GCHK(wind_rad_accel(ctx, who));
+  ctx->pot_n = -1;   // (positions and masses change)
+
+  // ---- :305: the density at the start ----
+  int *cur = d.lista, *nxt = d.listb;
+  int m = h.npos;
+  if(m < 0 || m > nw)
+    return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, m, nw);
+  k_wind_reset<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.w);
+  if(m > 0)
+    k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, cur, d.idx, WIND_GAS_ARGS, K.b, nw, d.w, nullptr, d.words);
+  HIPCHK(hipGetLastError());
+
+  // ---- :307-490 ----
+  int iter = 0, under = h.nunder;
+  long long bits = 0;
+  bool spread_pending = false;
+  double *pos = P<double>(ctx->f[GHIP_F_POS]), *hsml = P<double>(ctx->f[GHIP_F_HSML]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  auto add_ms = [&](int k, hipEvent_t a, hipEvent_t b) {
+    float f = 0;
+    if(hipEventElapsedTime(&f, a, b) == hipSuccess)
+      ctx->wind_ms[k] += f;
+  };
+  bool noconv = false;
+  while(true)
+    {
+      iter++;
+      bits += (iter == 1) ? m : under;
+      HIPCHK(hipEventRecord(ev[0], st));
+      HIPCHK(hipMemsetAsync(d.words, 0, 16, st));   // npairs, npos, nunder
+      if(m > 0)
+        k_wind_move<<<cdiv(m, 256), 256, 0, st>>>(m, cur, d.idx, ctx->n, pos, hsml, mass, nw, d.w, K);
+      HIPCHK(hipEventRecord(ev[1], st));
+      HIPCHK(hipMemsetAsync(d.cnt + m, 0, 8, st));
+      if(m > 0)
+        k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, cur, d.idx, WIND_GAS_ARGS, K.b, nw, d.w, d.cnt, d.words);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, m + 1, st));
+      k_wind_npairs<<<1, 64, 0, st>>>(d.off, m, d.words);
+      HIPCHK(hipEventRecord(ev[2], st));
+      if(m > 0)
+        {
+          k_wind_flags<<<cdiv(m, 256), 256, 0, st>>>(m, cur, d.w + WP_DTJ * D, d.flags, d.words);
+          HIPCHK(hipGetLastError());
+          GCHK(ghip_select_flagged(ctx, cur, d.flags, nxt, &d.words->npos, m, st));
+        }
+      HIPCHK(hipEventRecord(ev[3], st));
+      HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // the one read of the iteration: the pair count sizes the sort
+      add_ms(0, ev[0], ev[1]);
+      add_ms(1, ev[1], ev[2]);
+      add_ms(3, ev[2], ev[3]);
+      if(spread_pending)
+        add_ms(2, ev[4], ev[5]);
+      spread_pending = false;
+      if(h.npos < 0 || h.npos > m)
+        return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, h.npos, m);
+      if(h.npairs > 0)
+        {
+          HIPCHK(hipEventRecord(ev[4], st));
+          GCHK(wind_scatter(ctx, d, K.b, m, cur, (long long) h.npairs));
+          HIPCHK(hipEventRecord(ev[5], st));
+          spread_pending = true;
+        }
+      std::swap(cur, nxt);
+      m = h.npos;
+      under = h.nunder;
+      if(under == 0)
+        break;
+      if(iter >= p->max_iter)
+        {
+          noconv = true;
+          break;
+        }
+    }
+  result->iterations = iter;
+  result->bits = bits;
+  if(!noconv)
+    {
+      if(p->rad_accel)   // :497-538
+        {
+          const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
+          const int *act = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
+          if(nact > 0 && ctx->ngas > 0)
+            k_wind_rad_accel<<<cdiv(nact, 256), 256, 0, st>>>(nact, act, ctx->ngas, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                              P<int>(ctx->f[GHIP_F_TIMEBIN]), mass, P<double>(ctx->wind_inj),
+                                                              P<double>(ctx->wind_ra), K.dt_fac_gas);
+        }
+      k_wind_eliminate<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, pos, mass, d.w, d.deleted, K);
+      HIPCHK(hipGetLastError());
+    }
+  GCHK(wind_download_state(ctx, d, s, true));
+  if(spread_pending)
+    add_ms(2, ev[4], ev[5]);
+  for(int a = 0; a < nw; a++)   // :558-559, in list order
+    if(s->deleted[a])
+      {
+        result->ndeleted++;
+        if(s->deleted[a] == 1)
+          result->deleted_momentum += s->old_momentum[a];
+      }
+  ctx->wind_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  if(noconv)
+    return ghip_fail(ctx, GHIP_ENOCONV, "%s: %d wind particles still under way after max_iter = %d iterations", who,
+                     under, p->max_iter);
+  return GHIP_OK;
+}
+
+extern "C" int ghip_wind_get_timing(ghip_ctx *ctx, double ms[5])
+{
+  if(!ctx || !ms)
+    return GHIP_EINVAL;
+  for(int k = 0; k < 5; k++)
+    ms[k] = ctx->wind_ms[k];
+  return GHIP_OK;
+}
+
+extern "C" int ghip_wind_get_injected(ghip_ctx *ctx, double *injected)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_injected"));
+  if(!injected)
+    return GHIP_OK;
+  GCHK(wind_injected(ctx, "ghip_wind_get_injected"));
+  return wind_download3(ctx, ctx->wind_inj, injected, ctx->ngas);
+}
+
+extern "C" int ghip_wind_set_injected(ghip_ctx *ctx, const double *injected)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_injected"));
+  if(!injected)
+    return GHIP_OK;
+  GCHK(wind_upload3(ctx, ctx->wind_inj, injected, ctx->ngas));
+  ctx->wind_inj_ngas = ctx->ngas;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_wind_get_rad_accel(ghip_ctx *ctx, double *rad_accel)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_rad_accel"));
+  if(!rad_accel)
+    return GHIP_OK;
+  GCHK(wind_rad_accel(ctx, "ghip_wind_get_rad_accel"));
+  return wind_download3(ctx, ctx->wind_ra, rad_accel, ctx->ngas);
+}
+
+extern "C" int ghip_wind_set_rad_accel(ghip_ctx *ctx, const double *rad_accel)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_rad_accel"));
+  if(!rad_accel)
+    return GHIP_OK;
+  GCHK(wind_upload3(ctx, ctx->wind_ra, rad_accel, ctx->ngas));
+  ctx->wind_ra_ngas = ctx->ngas;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_set_rad_accel(ghip_ctx *ctx, int on)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  if(on)
+    GCHK(wind_refuse_sharded(ctx, "ghip_set_rad_accel"));
+  ctx->rad_accel_on = on != 0;
+  return GHIP_OK;
+}
+
+// RadAccel [3][ngas] for the kick, the PM kick and the drift under ghip_set_rad_accel (made and zeroed at
+// first use): *ra = nullptr with the switch off
+int ghip_rad_accel_field(ghip_ctx *ctx, const char *who, const double **ra)
+{
+  *ra = nullptr;
+  if(!ctx->rad_accel_on)
+    return GHIP_OK;
+  GCHK(wind_refuse_sharded(ctx, who));
+  GCHK(wind_rad_accel(ctx, who));
+  *ra = P<double>(ctx->wind_ra);
+  return GHIP_OK;
+}

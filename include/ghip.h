@@ -882,6 +882,107 @@ size_t ghip_dust_grains_size(void);
 int ghip_dust_density_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g);
 int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_dust_grains *g);
 
+/* ---- wind particles of the shipped flag bundle (-DVIRTUAL -DFB_MOMENTUM, with VIRTUAL_FLY_THORUGH_EMPTY_SPACE,
+ * VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL as run-time switches): the propagation loop of momentum_feedback()
+ * (momentum_feedback.c:251-591) with its two neighbour passes virtual_density() and virtual_spread_momentum().
+ * ghip_set_integration_flags gives a Type-3 particle its step limit and neither kick nor drift; THIS is where
+ * it moves.  Not built: spawning (:70-245, host code: it draws random numbers and changes NumPart),
+ * fb_particles.c (PHOTONS, VIRTUAL_HEATING, re-emission), REAL_EOS, NON_GRAY_RAD_TRANSFER.
+ * The wind particles are given by their particle indices: the active Type-3 particles with StellarAge < Time
+ * and WindOrPhoton == 0, in active-list order (:253-278); their per-particle state travels in host arrays in
+ * list order.  Resident fields read: TYPE, TIMEBIN, VEL, and of the gas POS, HSML, MASS; written at the wind
+ * indices by ghip_wind_feedback: POS, HSML, MASS.  Needs the trees of this step (GHIP_EINVAL "call
+ * ghip_tree_build first" otherwise); the gas tree stays valid, the gas does not move.  The gravity tree keeps
+ * the wind particles where they were when it was built, as the reference's does.  Single-rank: on a sharded
+ * or multi-GPU context every entry point below returns GHIP_EINVAL.  An index that does not name a Type-3
+ * particle is GHIP_EINVAL. ---- */
+typedef struct
+{
+  int periodic;
+  double BoxSize;
+  double Time;
+  double dt_fac;        /* wind particles: All.Timebase_interval / hubble_a (momentum_feedback.c:288) */
+  double dt_fac_gas;    /* gas (rad_accel): All.Timebase_interval, / time_hubble_a when comoving (:502-505) */
+  double FeedBackVelocity, UnitVelocity_in_cm_per_s, UnitDensity_in_cgs, UnitLength_in_cm;
+  double VirtualCrosSection, VirtualMass, VirtualTime, OuterBoundary;
+  double DesNumNgb, OriginalGasMass, SofteningGas, SofteningGasMaxPhys, SofteningBulgeMaxPhys;
+  double PhotonSearchRadius;
+  double dt_total_floor;   /* 1e-15 * All.VirtualTime * (All.MaxPart * NTask), :302 */
+  int fly_through_empty_space;   /* VIRTUAL_FLY_THORUGH_EMPTY_SPACE: the drmin step limit of :337-340 */
+  int variable_search_radius;    /* VARIABLE_PHOTON_SEARCH_RADIUS: the Hsml cap of :409-410 */
+  int rad_accel;                 /* RAD_ACCEL: :497-538 at the end of ghip_wind_feedback */
+  int max_iter;                  /* a guard the reference lacks: GHIP_ENOCONV after this many iterations */
+} ghip_wind_params;
+size_t ghip_wind_params_size(void);
+/* one virtual_density() (virtual_density.c:79-748).  In [nwind]: dt_jump.  Out [nwind]: new_density
+ * (P[].NewDensity) and drmin (b1.BH_Density).  Every listed particle gets new_density = 0 and drmin = 1e40
+ * (:107-127); those with dt_jump > 0 are evaluated: over the gas neighbours j with Mass > 0 within the
+ * particle's own resident HSML, drmin = min(drmin, |r - h_j| + 0.25 h_j) (:519-520) and, where r / h_j < 1,
+ * new_density += m_j W(r, h_j) with the GAS particle's h_j (:524-539).  Read-only on the resident fields. */
+int ghip_wind_density(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                      const double *dt_jump, double *new_density, double *drmin);
+/* one virtual_spread_momentum() (virtual_spread_momentum.c:58-469).  In [nwind]: dt_jump, new_density,
+ * delta_momentum (DeltaPhotonMomentum).  For the listed particles with new_density > 0 && dt_jump > 0
+ * (:129-130) every gas neighbour found as above with u < 1 receives delta_momentum m_j W / new_density
+ * Vel[k] / |Vel| (:432, 448) into the resident SphP[].i.Injected_BH_Momentum.  Each gas particle receives its
+ * wind particles in list order and every sum runs in a fixed order: two identical calls give identical
+ * bits. */
+int ghip_wind_spread(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                     const double *dt_jump, const double *new_density, const double *delta_momentum);
+/* the per-particle state of ghip_wind_feedback, host arrays [nwind] in list order, none may be NULL */
+typedef struct
+{
+  const double *stellar_age;     /* in      P[].StellarAge */
+  const double *birth_energy;    /* in      P[].BirthPhotonEnergy */
+  double *old_momentum;          /* in/out  P[].OldPhotonMomentum */
+  double *new_density;           /* in/out  P[].NewDensity */
+  double *drmin;                 /* in/out  P[].b1.BH_Density */
+  double *dt1, *dt2, *dt_jump;   /* out     P[].dt1, P[].dt2, P[].DtJump */
+  double *delta_momentum;        /* out     P[].DeltaPhotonMomentum (kept 0 for a particle that never moved) */
+  int *deleted;                  /* out     0 = kept, 1 = left OuterBoundary or older than VirtualTime, 2 = depleted */
+} ghip_wind_state;
+typedef struct
+{
+  int iterations;              /* N_iter */
+  long long bits;              /* basic steps of all particles (:324) */
+  int ndeleted;                /* count_deleted_photon */
+  double deleted_momentum;     /* OldPhotonMomentum of the deleted of the first kind, summed in list order (:559) */
+} ghip_wind_result;
+/* momentum_feedback.c:283-568 without the prints and the diagnostic files.  dt_jump from the time bin, dt2 = 0;
+ * if the sum of dt_jump is at or below dt_total_floor the call returns having changed nothing (the out arrays
+ * are filled: dt_jump, zeros).  Otherwise one density pass, then per iteration the move of every particle with
+ * dt_jump > 0 (:312-427), a density pass, a spread pass and the new list (dt_jump > 1e-40), until the list is
+ * empty; with rad_accel :497-538 for the active gas (ghip_set_active); then the elimination (:550-568: Mass = 0
+ * and the code in `deleted`).  The per-particle state crosses the link once in and once out; inside the loop
+ * one 40-byte read per iteration (pair and list counts) reaches the host.  The neighbour walks search
+ * min(Hsml, the largest h_j of the gas) for the sums and the pairs, and as far beyond as drmin needs: the pairs
+ * and their order are those of the whole sphere.
+ * ONE DELIBERATE DEVIATION: when the time cap of :345-346 sets the jump, dt1 = dt_jump exactly and the particle
+ * ends the iteration with dt_jump = 0.  The reference recomputes dt1 = dr * U / C * FBV (:348) and subtracts it
+ * (:371-372); the residue of that round trip is 0 or +-1 ulp, and on its sign hangs one more iteration of
+ * length ~1e-17.
+ * max_iter reached with particles under way: GHIP_ENOCONV, the state as it stands (no rad_accel, no
+ * elimination), ghip_last_error says how many were under way. */
+int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                       const ghip_wind_state *state, ghip_wind_result *result);
+/* the resident gas fields SphP[].i.Injected_BH_Momentum [ngas][3] and SphP[].ra.RadAccel [ngas][3], zero when
+ * first used; NULL = skip.  Values held for one ngas are refused after ghip_set_counts changes it (set them
+ * again), as ghip_kick_set_fields does. */
+int ghip_wind_get_injected(ghip_ctx *ctx, double *injected);
+int ghip_wind_set_injected(ghip_ctx *ctx, const double *injected);
+int ghip_wind_get_rad_accel(ghip_ctx *ctx, double *rad_accel);
+int ghip_wind_set_rad_accel(ghip_ctx *ctx, const double *rad_accel);
+/* RAD_ACCEL in the integrator: the timestep criterion adds fac2 RadAccel (timestep.c:668-671); the kick adds
+ * RadAccel dt_hydrokick to Vel and then SETS VelPred = Vel - dt_hydrokick2 RadAccel (:497-500, overwriting the
+ * line above it, as the C text does; the PMGRID term of :512 still follows); ghip_pm_kick sets VelPred = Vel +
+ * RadAccel dt_hydrokick (:337-339); ghip_drift adds RadAccel dt_hydrokick to VelPred (predict.c:190-192).
+ * Kernel instantiations of their own: with the switch off (the default) the existing kernels run and a
+ * resident RadAccel is not read.  Single-rank contexts only. */
+int ghip_set_rad_accel(ghip_ctx *ctx, int on);
+/* milliseconds of the last ghip_wind_feedback from events around its phases, summed over the iterations:
+ * move, density, spread, list, and the whole call; synchronises */
+int ghip_wind_get_timing(ghip_ctx *ctx, double ms[5]);
+
 /* The dust passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG through ghip_dd_begin /
  * ghip_dd_run): the reference's export of the grains (dust.c:60-261, 560-746).  Each grain goes to every
  * other shard whose local Type 0 / Type 2 particles its sphere (Pos, Hsml) can reach (a sphere test
