@@ -467,6 +467,10 @@ static int kick_nodes_host(ghip_ctx *ctx, int nkicked, const int *idx, const dou
   if(!ctx->dyn_on || !ctx->dyn_valid)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_tree_kick_nodes: no kept tree (ghip_set_dynamic_tree, then "
                      "ghip_tree_build)");
+  // (the kept tree's particle elements index the kick planes, which are sized by the counts of now)
+  if(ctx->dyn.tree.n != ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_tree_kick_nodes: the particle number changed since the full build "
+                     "(%d -> %d): rebuild", ctx->dyn.tree.n, ctx->n);
   if(nkicked == 0)
     return GHIP_OK;
   const size_t n = (size_t) ctx->n;

@@ -254,7 +254,39 @@ const char *ghip_version(void);
 long long ghip_device_bytes_in_use(void);
 
 /* ---- particle data ---- */
-/* declare particle counts (gas = indices [0,ngas), allvars.h:1384); (re)allocates device arrays */
+/* declare particle counts (gas = indices [0,ngas), allvars.h:1384); (re)allocates device arrays.
+ *
+ * A context is made once and lives through many particle sets (tests/test_gpu_context_reuse.py drives
+ * one through changing counts, geometries, walk kinds, meshes and switches and holds every result to a
+ * context made for that problem alone).  What a call with CHANGED counts does to the state it finds:
+ *   discarded   both trees and the kept geometry of the shards (the next walk or SPH pass needs
+ *               ghip_tree_build); the active list (everybody is active again) and the target lists; the
+ *               potential of ghip_potential; "GHIP_F_ID has been given" (a bound RndTable needs the IDs of
+ *               the new particles before the next build)
+ *   refused     values that were given per gas particle or per particle for the old counts -- alpha /
+ *   until       Dtalpha (ghip_visc_set_alpha), DragAccel / DeltaDustMomentum (ghip_kick_set_fields, read
+ *   given       under integration flags only), DragHeating, Injected_BH_Momentum / RadAccel, the sink
+ *   again       marks: the pass that reads them fails with GHIP_EINVAL and a message instead of reading
+ *               them at another pitch; ghip_tree_substep and ghip_tree_kick_nodes refuse a kept tree
+ *               (ghip_set_dynamic_tree) of another particle number until a full build has captured the
+ *               new one
+ *   undefined   the contents of all 24 fields: a field is [ncomp][count] with pitch count, so the old
+ *               bytes mean nothing at the new counts (a buffer that had to grow is zeroed, one that did
+ *               not keeps its bytes).  Inputs are set again; an output field holds values only for the
+ *               targets of the pass that wrote it since.  The region of ghip_pm_find_region belongs to
+ *               the particles it was found for: find or set it again.
+ *   kept        every switch and what it was given -- ghip_set_massless_gas_rule,
+ *               ghip_set_adaptive_gravsoft, ghip_set_dynamic_tree, ghip_set_rnd_table,
+ *               ghip_set_viscosity, ghip_set_dust_model, ghip_set_integration_flags, ghip_set_async,
+ *               ghip_set_hydro_release, the shard set-up (ghip_set_shard, ghip_dd_init and the domain,
+ *               splits or segments, which a new decomposition sets again); the tables and plans, each
+ *               keyed by the one parameter it depends on and remade when a call brings another value
+ *               (Ewald force and potential tables: BoxSize; FFT plans and Green's functions: PMGRID; the
+ *               short-range tables: none); capacities (buffers only grow), the sort width a clustered
+ *               build switched to, the walk plan history and the pair balance -- these change speed and,
+ *               for gravity accelerations, the order of a target's partial sums, nothing else.
+ * A call with the SAME counts keeps everything, the active list and the trees included (the fields are
+ * set again by ghip_set_field, which invalidates the trees where they depend on the field). */
 int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas);
 /* copy one field host->device / device->host, host arrays in the plain layouts listed above */
 int ghip_set_field(ghip_ctx *ctx, int field, const void *host);

@@ -1,7 +1,8 @@
 """Development aid: seeded random sweeps of the parity checks -- particle numbers, distributions
 (plane-wave clustered lattices, Plummer spheres, uniform noise), periodic / open boundaries, equal /
 unequal softenings, full and partial active lists -- device against the oracle, counts exactly.
-python tests/gpu_fuzz.py [nseeds] [first seed]"""
+python tests/gpu_fuzz.py [nseeds] [first seed]
+python tests/gpu_fuzz.py --chain N [first]: N chains of CHAIN_LENGTH such problems, each chain through ONE context"""
 import sys
 import time
 
@@ -11,9 +12,12 @@ from common import O, Problem, bindings, ics, relerr
 
 B = bindings()
 TOL = 1e-11
+CHAIN_LENGTH = 6
 
 
-def one(seed):
+def one(seed, fp=None):
+    """fp: a context to reuse (it may have run anything before); None: a fresh one"""
+    reuse = fp is not None
     rng = np.random.default_rng(seed)
     kind = rng.integers(0, 3)
     periodic = int(rng.integers(0, 2))
@@ -50,9 +54,12 @@ def one(seed):
     pr = Problem(ic=ic, periodic=periodic, unequal=unequal,
                  des_ngb=float(min(33.0, max(ic["ngas"] - 1, 1))))
     n, ng = pr.n, pr.ngas
-    fp = pr.device()
+    fp = pr.load(fp) if reuse else pr.device()
     fp.set_massless_gas_rule(rule)
     adaptive = bool(ng > 0 and rng.random() < 0.3)           # ADAPTIVE_GRAVSOFT_FORGAS
+    if reuse:      # the switches a fresh context has not got: back to what this problem draws
+        fp.set_active(None)
+        fp.set_adaptive_gravsoft(False)
     if adaptive:
         pr.hsml0[:ng] *= rng.uniform(0.05, 1.0, ng)
         fp.set_field(B.F_HSML, pr.hsml0)
@@ -116,12 +123,12 @@ def one(seed):
         assert np.abs(ha - want).max() <= 1e-10 * (np.abs(want).max() + 1e-300), "hydro"
     substeps = 0
     if not adaptive and rng.random() < 0.4:
-        substeps = substep_sequence(rng, pr, periodic)
+        substeps = substep_sequence(rng, pr, periodic, fp if reuse else None)
     O.set_massless_gas_rule(0)
     return kind, n, ng, mode, unequal, adaptive, (None if act is None else len(act)), substeps, rule
 
 
-def substep_sequence(rng, pr, periodic):
+def substep_sequence(rng, pr, periodic, fp=None):
     """Sub-steps on the tree of the last full build (forcetree.c:1356-1520): random kicks of random
     subsets, drifts of everybody, gravity for random active lists on the kept tree -- counts against the
     oracle's drifted and kicked insertion tree."""
@@ -130,7 +137,8 @@ def substep_sequence(rng, pr, periodic):
     ext = (c - 0.1 * ln, ce.copy(), 1.2 * ln)               # room to drift inside the domain cube
     vel = pr.ic["vel"].copy()
     vscale = np.abs(vel).max() + 1e-300
-    fp = pr.device()
+    reuse = fp is not None
+    fp = pr.load(fp) if reuse else pr.device()
     fp.set_dynamic_tree(True)
     fp.tree_build(ext[0], ext[1], ext[2], pr.force_soft)
     T = O.Tree(pr.ic["pos"].copy(), vel, pr.ic["mass"], pr.ic["type"], pr.force_soft, hsml=pr.hsml0, extent=ext)
@@ -164,18 +172,38 @@ def substep_sequence(rng, pr, periodic):
         assert np.abs(fp.get_field(B.F_GRAVACCEL)[tg] - oa).max() < 1e-10 * (np.abs(oa).max() + 1e-300), \
             "gravity on the kept tree"
         fp.set_active(None)
-    fp.close()
+    if reuse:
+        fp.set_dynamic_tree(False)
+    else:
+        fp.close()
     return nsub
 
 
+def chain(seed, length=CHAIN_LENGTH):
+    """`length` problems, the seeds 100 seed, 100 seed + 1, ..., through one context: what one() asserts of each
+    of them alone it asserts of each of them here, whatever the context ran before -- the sub-steps on the
+    kept tree included, which otherwise get a context of their own"""
+    fp = B.ForcePath(0)
+    try:
+        infos = [one(100 * int(seed) + k, fp) for k in range(length)]
+        fp.sync()
+    finally:
+        O.set_massless_gas_rule(0)
+        fp.close()
+    return infos
+
+
 if __name__ == "__main__":
+    chains = len(sys.argv) > 1 and sys.argv[1] == "--chain"
+    if chains:
+        del sys.argv[1]
     nseeds = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    first = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
+    first = int(sys.argv[2]) if len(sys.argv) > 2 else (10 if chains else 1000)
     t0 = time.time()
     bad = 0
     for seed in range(first, first + nseeds):
         try:
-            info = one(seed)
+            info = chain(seed) if chains else one(seed)
             print("seed %d ok %s" % (seed, info), flush=True)
         except AssertionError as e:
             bad += 1

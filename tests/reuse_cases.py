@@ -1,0 +1,769 @@
+"""One long-lived context through changing problems: the table of stages that tests/test_reuse_cases_cpu.py
+checks on the CPU and tests/test_gpu_context_reuse.py drives through the device.
+
+A Stage is a Problem (seeded, built once and never changed), the switches of the context that hold while it
+runs, and the passes run on it.  A sequence is a list of stages that ONE context runs in order: the product
+(host/gadget_force.c) creates its context once and keeps it while NumPart, N_gas, the geometry, the walk kinds,
+the meshes and the switches change underneath it.  transitions(seq) names what happens between neighbouring
+stages -- derived from the stages' own properties, not from labels -- and REQUIRED lists what the table as a
+whole must contain.
+
+oracle_stage(st) is the reference's result of a stage (the oracle alone, on the CPU), device_stage(fp, st) the
+device's result on a context that may have run anything before; both return dicts of named arrays, compared
+under RULES."""
+import os
+import re
+
+import numpy as np
+
+from common import O, Problem, bindings, box_edge_particles, ics
+
+MAX_N = 4000
+MAX_STAGES = 8
+
+# the switches of a context and what a fresh one holds
+DEFAULTS = dict(rule=0, adaptive=False, dynamic=False, rnd=False, visc=None, dust=None, iflags=None)
+
+
+# ------------------------------------------------------------------------------------------------
+# problems
+# ------------------------------------------------------------------------------------------------
+def _scaled(ic, box):
+    ic = dict(ic)
+    ic["pos"] = np.ascontiguousarray(ic["pos"] * box)
+    ic["pos"][ic["pos"] >= box] = 0.0
+    ic["vel"] = ic["vel"] * box
+    ic["boxsize"] = float(box)
+    ic["spacing"] = ic["spacing"] * box
+    return ic
+
+
+def cosmo(ng, seed=12345, rms=1.0, box=1.0, gas=True):
+    ic = ics.make_ics(ng, gas=gas, seed=seed, clustered=True, rms_disp=rms)
+    return ic if box == 1.0 else _scaled(ic, box)
+
+
+def plummer(n, seed=7, a=0.05, gas_fraction=0.3, center=(0.5, 0.5, 0.5)):
+    return ics.make_plummer(n, seed=seed, a=a, gas_fraction=gas_fraction, center=center)
+
+
+def noise(n, ngas, seed):
+    """the uniform-noise generator of tests/gpu_fuzz.py"""
+    rng = np.random.default_rng(seed)
+    pos = rng.random((n, 3))
+    typ = np.where(np.arange(n) < ngas, 0, rng.integers(1, 6, n)).astype(np.int32)
+    return dict(pos=pos, vel=rng.standard_normal((n, 3)), mass=rng.uniform(0.5, 2.0, n) / n, type=typ, ngas=ngas,
+                boxsize=1.0, spacing=1.0 / max(2.0, n ** (1 / 3)), id=np.arange(1, n + 1, dtype=np.uint32),
+                u=np.full(ngas, 0.01))
+
+
+def marked(ic, seed):
+    """the construction of gpu_fuzz.one: some records of the gas block have become sinks / stars (Type != 0), some
+    gas has been swallowed (Mass == 0)"""
+    rng = np.random.default_rng(seed)
+    ic = dict(ic)
+    ngas0 = int(ic["ngas"])
+    conv = rng.choice(ngas0, max(1, ngas0 // 40), replace=False)
+    ic["type"] = ic["type"].copy()
+    ic["type"][conv] = rng.choice([4, 5], len(conv))
+    gone = rng.choice(ngas0, max(1, ngas0 // 30), replace=False)
+    ic["mass"] = ic["mass"].copy()
+    ic["mass"][gone] = 0.0
+    return ic
+
+
+def clumps(n=3000, clump=90):
+    """the clumps of test_tight_clumps_sort_paths: a clump of gas and one of collisionless particles, each inside one
+    level-12 cell, so that all its keys share the top 32 bits -- a run of more than 32 sends the build to the
+    63-bit sort, for good (ghip_ctx::sort_wide)"""
+    ic = plummer(n, gas_fraction=0.3)
+    rng = np.random.default_rng(3)
+    corner, _, dlen = O.domain_extent(ic["pos"])
+    cell = dlen / 4096
+    for first in (5, ic["ngas"] + 5):
+        c = corner + (np.floor((ic["pos"][first] - corner) / cell) + 0.5) * cell
+        ic["pos"][first:first + clump] = c + 0.2 * cell * (rng.random((clump, 3)) - 0.5)
+    assert np.array_equal(O.domain_extent(ic["pos"])[0], corner)
+    return ic
+
+
+def close_pairs(n, ngas, seed, sep=2.0 ** -17):
+    """n / 2 pairs at random places, the partners `sep` of the box apart: every pair hangs at the end of a chain of
+    cells a dozen levels long, several times the nodes of a smooth set of the same size"""
+    rng = np.random.default_rng(seed)
+    ic = noise(n, ngas, seed)
+    half = n // 2
+    a = np.arange(0, 2 * half, 2)
+    u = rng.standard_normal((half, 3))
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    ic["pos"][a] = 0.05 + 0.9 * ic["pos"][a]
+    ic["pos"][a + 1] = ic["pos"][a] + sep * u
+    return ic
+
+
+def coincident(n):
+    """treernd_ref.standard_state: a Plummer sphere with groups of particles at one identical position and pairs
+    1e-12 apart; the tree of such a set is the reference's only with its RndTable bound"""
+    import treernd_ref
+    return treernd_ref.standard_state(n)[0]
+
+
+def rnd_table():
+    import treernd_ref
+    if "t" not in _CACHE:
+        _CACHE["t"] = treernd_ref.tiny_table(262144)
+    return _CACHE["t"]
+
+
+_CACHE = {}
+VISC = dict(time_dependent=1, ArtBulkViscConst=0.8)
+DUST = ("real_pebble_collisions",)
+IFLAGS = dict(OuterBoundary=300.0, FeedBackVelocity=10.0)
+
+
+# ------------------------------------------------------------------------------------------------
+# stages
+# ------------------------------------------------------------------------------------------------
+class Stage:
+    """make: () -> ics dict; passes: tuples, see device_stage; pad: room around the particles in the domain cube (a
+    kept tree drifts inside it); soft_frac, periodic, unequal: Problem's; the remaining keywords: switches"""
+
+    def __init__(self, name, make, passes, periodic=1, unequal=False, soft_frac=0.04, pad=0.0, adaptive_hsml=False,
+                 **switches):
+        assert set(switches) <= set(DEFAULTS), switches
+        self.name, self.make, self.passes = name, make, list(passes)
+        self.periodic, self.unequal, self.soft_frac, self.pad = int(periodic), bool(unequal), soft_frac, pad
+        self.adaptive_hsml = adaptive_hsml
+        self.switches = {**DEFAULTS, **switches}
+        self._pr = None
+
+    @property
+    def pr(self):
+        if self._pr is None:
+            ic = self.make()
+            pr = Problem(ic=ic, periodic=self.periodic, unequal=self.unequal, soft_frac=self.soft_frac,
+                         des_ngb=float(min(33.0, max(int(ic["ngas"]) - 1, 1))))
+            if self.adaptive_hsml:     # gpu_fuzz.one: gas softenings that differ from particle to particle
+                pr.hsml0[:pr.ngas] *= np.random.default_rng(17).uniform(0.05, 1.0, pr.ngas)
+            if pr.n == 0:      # nobody: the domain cube of the run, as a rank without particles sees it
+                pr.extent = (np.zeros(3), np.full(3, 0.5), 1.0)
+            if pr.n and self.pad:
+                c, ce, ln = pr.extent
+                pr.extent = (c - self.pad * ln, ce.copy(), (1 + 2 * self.pad) * ln)
+            self._pr = pr
+        return self._pr
+
+    def sph(self):
+        return any(p[0] == "density" for p in self.passes)
+
+    def walks(self):
+        return [(p[1],) + tuple(p[3:]) for p in self.passes if p[0] == "gravity"]
+
+
+def _std(kind="pair", theta=0.4):
+    """kind "two": the Newtonian walk, then the Ewald correction in a call of its own"""
+    walks = [("gravity", "newton", theta), ("gravity", "ewald", theta)] if kind == "two" else [("gravity", kind, theta)]
+    return walks + [("density",), ("hydro",)]
+
+
+def _sequences():
+    S = Stage
+    ng7 = lambda seed: (lambda: cosmo(7, seed=seed))       # noqa: E731
+    seqs = {}
+    seqs["counts"] = [
+        S("small", lambda: cosmo(6), _std()),
+        S("grown", lambda: plummer(3600, seed=3), _std("newton", 0.0), periodic=0),
+        S("shrunk", ng7(1), _std()),
+        S("same n, other particles", ng7(2), _std("two", 0.8)),
+        S("nobody", lambda: noise(0, 0, 1), [("gravity", "newton", 0.4)]),
+        S("same n again", ng7(2), _std("two", 0.8)),
+        S("two particles", lambda: noise(2, 1, 5), [("gravity", "newton", 0.0)], periodic=0),
+        S("back", lambda: cosmo(6), _std()),
+    ]
+    gas = lambda ngas, seed: (lambda: noise(900, ngas, seed))      # noqa: E731
+    mk = lambda seed: (lambda: marked(noise(900, 500, seed), seed))       # noqa: E731
+    seqs["gas"] = [
+        S("600 gas", gas(600, 12), _std()),
+        S("no gas", gas(0, 13), [("gravity", "pair", 0.4)]),
+        S("600 gas again", gas(600, 12), _std()),
+        S("marked, no rule", mk(13), _std()),
+        S("marked, rule 1", mk(14), _std(), rule=1),
+        S("marked, rule 3", mk(15), _std(), rule=3),
+        S("marked, rule 0", mk(16), _std()),
+        S("pure", gas(500, 17), _std()),
+    ]
+    seqs["builds"] = [
+        S("smooth", lambda: noise(3000, 1200, 21), _std("newton", 0.0), periodic=0),
+        S("tight pairs, same n", lambda: close_pairs(3000, 1200, 22), _std("newton", 0.0), periodic=0,
+          soft_frac=0.0004),
+        S("clumps", clumps, [("gravity", "newton", 0.5)], periodic=0, soft_frac=0.0004),
+        S("ordinary after clumps", lambda: plummer(3000, seed=9), _std("newton", 0.5), periodic=0),
+        S("coincident, table bound", lambda: coincident(3000), [("gravity", "newton", 0.5)], periodic=0, rnd=True),
+        S("ordinary, table gone", lambda: plummer(3000, seed=10), _std("newton", 0.5), periodic=0),
+    ]
+    pot = lambda theta, pm=0: ("potential", theta, pm)       # noqa: E731
+    seqs["geometry"] = [
+        S("periodic", lambda: cosmo(8), [("gravity", "pair", 0.4), pot(0.0)]),
+        S("box 2.5", lambda: cosmo(8, seed=3, box=2.5), [("gravity", "newton", 0.0), ("gravity", "ewald", 0.0),
+                                                         pot(0.0)]),
+        S("box 1 again", lambda: cosmo(8, seed=4), [("gravity", "newton", 0.0), ("gravity", "ewald", 0.0), pot(0.5)]),
+        S("open", lambda: cosmo(8), [("gravity", "newton", 0.4), pot(0.0)], periodic=0),
+        S("sphere in a corner", lambda: plummer(1000, seed=5, center=(0.25, 0.3, 0.2), a=0.02),
+          [("gravity", "newton", 0.4), pot(0.0)], periodic=0),
+        S("sphere in the middle", lambda: plummer(1000, seed=6, a=0.08), _std("newton", 0.4), periodic=0),
+    ]
+    g = lambda kind, theta=0.4, *a: ("gravity", kind, theta) + a      # noqa: E731
+    # every walk kind after every other one: N E P S N P E | S P N S E N
+    seqs["walks"] = [
+        S("first walks", lambda: cosmo(8), [g("newton"), g("ewald"), g("pair", 0.0), g("shortrange", 0.4, 8),
+                                             g("newton", 0.0), g("pair"), g("ewald")]),
+        S("more walks", lambda: cosmo(8, seed=5), [g("shortrange", 0.0, 16), g("pair"), g("newton"),
+                                                    g("shortrange", 0.4, 32), g("ewald", 0.4), g("newton", 0.8)]),
+    ]
+    seqs["mesh"] = [
+        S("mesh 16", lambda: cosmo(8), [g("newton"), ("pm", 16), pot(0.0)]),
+        S("mesh 32", lambda: cosmo(8, seed=2), [g("newton"), ("pm", 32), pot(0.0, 32)]),
+        S("mesh 16 again", lambda: cosmo(8, seed=3), [g("newton"), ("pm", 16), pot(0.0)]),
+        S("open mesh", lambda: plummer(1500, seed=4, gas_fraction=0.0), [g("newton"), ("pmnp", 16)], periodic=0),
+        S("periodic mesh again", lambda: cosmo(8, seed=4), [g("newton"), ("pm", 16), pot(0.0, 16)]),
+        S("cells at the box edge", lambda: box_edge_particles(1.0, 8), [("pm", 8)]),
+    ]
+    act = lambda frac, seed: ("active", frac, seed)      # noqa: E731
+    seqs["softening"] = [
+        S("equal", lambda: cosmo(7), _std()),
+        S("unequal", lambda: cosmo(7, seed=2), _std(), unequal=True),
+        S("equal again", lambda: cosmo(7, seed=3), _std()),
+        S("adaptive", lambda: plummer(1500, seed=4), _std("newton", 0.0), periodic=0, adaptive=True,
+          adaptive_hsml=True),
+        S("adaptive off, a partial list", lambda: plummer(1500, seed=5),
+          [("density",), act(0.3, 1), g("newton", 0.0), ("hydro",)], periodic=0),
+        S("other counts", lambda: plummer(1200, seed=6), _std("newton", 0.0), periodic=0),
+        S("everybody", lambda: plummer(1200, seed=7), [("density",), act(0.5, 2), g("newton", 0.0), ("everybody",),
+                                                       g("newton", 0.8), ("hydro",)], periodic=0),
+    ]
+    seqs["kept tree"] = [
+        S("kept tree", ng7(1), [g("pair"), ("substep", 1)], pad=0.1, dynamic=True),
+        S("other n, still kept", lambda: plummer(2000, seed=8), [g("newton", 0.0), ("substep", 2)], periodic=0,
+          pad=0.1, dynamic=True),
+        S("released", ng7(3), _std()),
+    ]
+    seqs["optional kernels"] = [
+        S("viscosity", lambda: cosmo(7), [g("pair"), ("density",), ("hydro",)], visc=VISC),
+        S("viscosity gone", lambda: cosmo(7, seed=2), _std()),
+        S("dust model", lambda: cosmo(7, seed=3), _std(), dust=DUST),
+        S("dust model gone", lambda: cosmo(7, seed=4), _std()),
+        S("integration flags", lambda: cosmo(7, seed=5), _std(), iflags=IFLAGS),
+        S("integration flags gone", lambda: cosmo(7, seed=6), _std()),
+    ]
+    return seqs
+
+
+SEQUENCES = _sequences()
+
+
+# ------------------------------------------------------------------------------------------------
+# what happens between neighbouring stages
+# ------------------------------------------------------------------------------------------------
+REQUIRED = [
+    "n grows past every capacity", "n shrinks to under half", "n equal, particles differ", "n -> 0 -> n", "n = 2",
+    "ngas changes, n fixed", "ngas -> 0 -> ngas",
+    "same n, more nodes than the slack",
+    "wide sort, then an ordinary problem", "coincident particles under a table",
+    "periodic -> open", "open -> periodic", "box 1 -> 2.5 -> 1 with Ewald and potential walks",
+    "domain extent moves",
+    "every walk kind after every other", "shortrange grids 8, 16, 32",
+    "mesh 16 -> 32 -> 16", "periodic mesh -> open mesh -> periodic mesh", "potential with and without a mesh",
+    "equal -> unequal -> equal softening", "adaptive softening on -> off",
+    "massless rule 0 -> 1 -> 3 -> 0 with marked records", "mixed gas block -> pure",
+    "kept tree -> other n, still kept -> released",
+    "partial list -> other counts -> everybody",
+    "rnd set -> None", "visc set -> None", "dust set -> None", "iflags set -> None",
+]
+WALK_KINDS = ("newton", "ewald", "pair", "shortrange")
+
+
+def tree_slack():
+    """(d, c): a synchronous build leaves room for nnodes / d + c more nodes than it counted -- read from the
+    build's own source, so that the overflow stage follows it"""
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gadget-leicester_amd", "csrc",
+                       "ghip_tree.hip")
+    with open(src) as f:
+        m = re.findall(r"cap = z\.nnodes \+ z\.nnodes / (\d+) \+ (\d+);", f.read())
+    assert len(m) == 1, "the slack of tree_adopt_sizes was not found in ghip_tree.hip"
+    return int(m[0][0]), int(m[0][1])
+
+
+def _mixed(st):
+    pr = st.pr
+    return bool(pr.ngas and (pr.ic["type"][:pr.ngas] != 0).any())
+
+
+def _massless(st):
+    pr = st.pr
+    return bool(pr.ngas and (pr.ic["mass"][:pr.ngas] == 0).any())
+
+
+def _has(st, kind, *rest):
+    return any(p[0] == kind and tuple(p[1:1 + len(rest)]) == rest for p in st.passes)
+
+
+def _pot_kinds(st):
+    return {bool(p[2]) for p in st.passes if p[0] == "potential"}
+
+
+def transitions(seq, nodes=None):
+    """the names of REQUIRED that the sequence `seq` contains.  nodes: the oracle's node count per stage (needed for
+    the overflow transition only; without it that one is not reported)"""
+    out = set()
+    n = [s.pr.n for s in seq]
+    ng = [s.pr.ngas for s in seq]
+    k = len(seq)
+    sw = [s.switches for s in seq]
+    for i in range(1, k):
+        a, b = seq[i - 1], seq[i]
+        if n[i] > max(n[:i]) and ng[i] > max(ng[:i]) and n[i] >= 2 * max(n[:i]):
+            out.add("n grows past every capacity")
+        if 0 < n[i] < n[i - 1] / 2:
+            out.add("n shrinks to under half")
+        if n[i] == n[i - 1] and n[i] > 0 and not np.array_equal(a.pr.ic["pos"], b.pr.ic["pos"]):
+            out.add("n equal, particles differ")
+            if ng[i] != ng[i - 1]:
+                out.add("ngas changes, n fixed")
+            if nodes is not None and ng[i] == ng[i - 1]:
+                d, c = tree_slack()
+                # the first build of this n in the context was stage i - 1's: its buffers hold what it counted
+                # plus the slack, and nothing before it was larger
+                if nodes[i] > nodes[i - 1] + nodes[i - 1] // d + c and n[i - 1] >= max(n[:i]) and \
+                        b.passes[0][0] == "gravity":
+                    out.add("same n, more nodes than the slack")
+        if a.periodic and not b.periodic:
+            out.add("periodic -> open")
+        if b.periodic and not a.periodic:
+            out.add("open -> periodic")
+        if n[i] and n[i - 1] and not np.array_equal(a.pr.extent[0], b.pr.extent[0]) and a.pr.extent[2] != b.pr.extent[2]:
+            out.add("domain extent moves")
+        if sw[i - 1]["adaptive"] and not sw[i]["adaptive"]:
+            out.add("adaptive softening on -> off")
+        if _mixed(a) and not _mixed(b) and ng[i] and b.sph():
+            out.add("mixed gas block -> pure")
+        if _has(a, "gravity", "newton") and clumps_run(a) > 32 and clumps_run(b) <= 32:
+            out.add("wide sort, then an ordinary problem")
+        if sw[i]["rnd"] and coincidences(b):
+            out.add("coincident particles under a table")
+        for key in ("rnd", "visc", "dust", "iflags"):
+            if sw[i - 1][key] and not sw[i][key]:
+                out.add(key + " set -> None")
+    for i in range(2, k):
+        a, b, c = seq[i - 2], seq[i - 1], seq[i]
+        if n[i - 2] > 0 and n[i - 1] == 0 and n[i] == n[i - 2]:
+            out.add("n -> 0 -> n")
+        if ng[i - 2] > 0 and ng[i - 1] == 0 and ng[i] == ng[i - 2] and n[i - 1] > 0:
+            out.add("ngas -> 0 -> ngas")
+        if (a.pr.box, b.pr.box, c.pr.box) == (1.0, 2.5, 1.0) and all(
+                s.periodic and (_has(s, "gravity", "ewald") or _has(s, "gravity", "pair")) and _pot_kinds(s)
+                for s in (a, b, c)):
+            out.add("box 1 -> 2.5 -> 1 with Ewald and potential walks")
+        if [p[1] for s in (a, b, c) for p in s.passes if p[0] == "pm"] == [16, 32, 16]:
+            out.add("mesh 16 -> 32 -> 16")
+        if _has(a, "pm") and _has(b, "pmnp") and _has(c, "pm"):
+            out.add("periodic mesh -> open mesh -> periodic mesh")
+        if (a.unequal, b.unequal, c.unequal) == (False, True, False):
+            out.add("equal -> unequal -> equal softening")
+        if sw[i - 2]["dynamic"] and sw[i - 1]["dynamic"] and not sw[i]["dynamic"] and n[i - 1] != n[i - 2] and \
+                _has(a, "substep") and _has(b, "substep"):
+            out.add("kept tree -> other n, still kept -> released")
+        if _has(a, "active") and not _has(a, "everybody") and (n[i - 1], ng[i - 1]) != (n[i - 2], ng[i - 2]) and \
+                not _has(b, "active") and _has(c, "everybody"):
+            out.add("partial list -> other counts -> everybody")
+    if 2 in n:
+        out.add("n = 2")
+    rules = [s["rule"] for s in sw]
+    for i in range(3, k):
+        if rules[i - 3:i + 1] == [0, 1, 3, 0] and all(_mixed(s) and _massless(s) and s.sph() for s in seq[i - 3:i + 1]):
+            out.add("massless rule 0 -> 1 -> 3 -> 0 with marked records")
+    walks = [w for s in seq for w in s.walks()]
+    follows = {(walks[i - 1][0], walks[i][0]) for i in range(1, len(walks))}
+    if all((x, y) in follows for x in WALK_KINDS for y in WALK_KINDS if x != y):
+        out.add("every walk kind after every other")
+    if {w[1] for w in walks if w[0] == "shortrange"} >= {8, 16, 32}:
+        out.add("shortrange grids 8, 16, 32")
+    pk = [x for s in seq for x in sorted(_pot_kinds(s))]
+    if any(pk[i - 1] != pk[i] for i in range(1, len(pk))) and True in pk and False in pk:
+        out.add("potential with and without a mesh")
+    return out
+
+
+def clumps_run(st):
+    """the longest run of particles whose keys share the top 32 bits (11 bits per axis below the domain cube's
+    first split, as test_tight_clumps_sort_paths counts them: one level-12 cell)"""
+    pr = st.pr
+    if pr.n == 0:
+        return 0
+    cell = np.floor((pr.ic["pos"] - pr.extent[0]) / (pr.extent[2] / 4096)).astype(np.int64)
+    _, cnt = np.unique(cell, axis=0, return_counts=True)
+    return int(cnt.max())
+
+
+def coincidences(st):
+    pos = st.pr.ic["pos"]
+    return len(pos) - len(np.unique(pos, axis=0))
+
+
+# ------------------------------------------------------------------------------------------------
+# one stage on the oracle and on the device
+# ------------------------------------------------------------------------------------------------
+# name -> (how the device is held to the oracle, how a reused context is held to a fresh one)
+#   "exact"        equal
+#   ("max", t)     max |a - b| <= t * max |b|            (gravity, hydro, the mesh force: gpu_fuzz.one and
+#   ("rel", t)     max |a - b| / |b| < t                  test_pm_periodic_long_range_force_parity)
+#   None           not compared with the oracle
+# A reused context computes every result to the bit, with two exceptions that DESIGN documents:
+#   acc*   gravity accelerations: the wavefronts per bucket follow the plan history of the context, and with them
+#          the order of a target's partial sums
+#   gravpm the mesh force: its mass assignment adds with fp64 atomics in the order the wavefronts arrive (4.8)
+# These two are held to the bound they have against the oracle; so is potmesh, the potential with a mesh part, whose
+# mass assignment is the same one (the bound of test_finish_and_mesh_potential).
+RULES = {
+    "nodes": ("exact", "exact"), "cost": ("exact", "exact"), "dens_iter": ("exact", "exact"),
+    "pairs": ("exact", "exact"),
+    "acc": (("max", 1e-10), ("max", 1e-10)), "hydroaccel": (("max", 1e-10), "exact"),
+    "density": (("rel", 1e-11), "exact"), "hsml": (("rel", 1e-11), "exact"),
+    "gravpm": (("max", 1e-11), ("max", 1e-11)),
+    "potential": (None, "exact"), "pot_nint": (None, "exact"), "potmesh": (None, ("pot", 1e-10)),
+    "numngb": (None, "exact"), "dhsmlfac": (None, "exact"), "divvel": (None, "exact"), "curlvel": (None, "exact"),
+    "pressure": (None, "exact"), "dtentropy": (None, "exact"), "maxsignalvel": (None, "exact"),
+    "dtalpha": (None, "exact"),
+}
+
+
+def rule_of(key):
+    return RULES[key.rstrip("0123456789")]
+
+
+def differs(how, a, b):
+    """None if `a` meets `b` under `how`, else a description of the difference"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape:
+        return "shapes %r and %r" % (a.shape, b.shape)
+    if how == "exact":
+        if np.array_equal(a, b):
+            return None
+        if a.dtype.kind != "f":
+            return "%d of %d differ" % (int((a != b).sum()), a.size)
+        bad = a != b
+        return "%d of %d differ, by up to %.3e of the largest" % (
+            int(bad.sum()), a.size, np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+    kind, tol = how
+    if a.size == 0:
+        return None
+    if kind == "pot":      # tests/test_gpu_potential.py:_err
+        err = float(np.max(np.abs(a - b) / np.maximum(np.abs(b), np.abs(b).mean())))
+        return None if err < tol else "%.3e (bound %g)" % (err, tol)
+    if kind == "max":
+        err = np.abs(a - b).max() / (np.abs(b).max() + 1e-300)
+        return None if err <= tol else "%.3e of the largest (bound %g)" % (err, tol)
+    err = float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))
+    return None if err < tol else "relative %.3e (bound %g)" % (err, tol)
+
+
+def _oldacc(st):
+    return 0.2 + np.random.default_rng(101).random(st.pr.n)
+
+
+def _active(st, frac, seed):
+    n = st.pr.n
+    return np.sort(np.random.default_rng(seed).choice(n, max(1, int(frac * n)), replace=False)).astype(np.int32)
+
+
+def _substep_draw(st, seed):
+    """one sub-step as gpu_fuzz.substep_sequence draws it: who is kicked and by how much, the drift, the targets"""
+    pr = st.pr
+    n = pr.n
+    rng = np.random.default_rng(seed)
+    vscale = np.abs(pr.ic["vel"]).max() + 1e-300
+    k = n // 3
+    act = np.sort(rng.choice(n, k, replace=False)).astype(np.int32)
+    dv = 0.2 * vscale * rng.standard_normal((k, 3))
+    dt = float(rng.uniform(0.0005, 0.01)) * pr.extent[2] / vscale
+    tg = np.sort(rng.choice(n, max(1, n // 2), replace=False)).astype(np.int32)
+    return act, dv, dt, tg
+
+
+def _gas_of(st):
+    pr = st.pr
+    return np.where(pr.ic["type"][:pr.ngas] == 0)[0].astype(np.int32)
+
+
+def _visc_alpha(st):
+    return 0.1 + 0.7 * np.random.default_rng(7).random(st.pr.ngas)
+
+
+def _asmth(st, grid):
+    return 1.25 * st.pr.box / grid
+
+
+def oracle_stage(st):
+    """the reference's results of the stage, computed once and shared (nobody changes them); out["T"] is kept out"""
+    if "oracle" in st.__dict__:
+        return st.oracle
+    pr = st.pr
+    n, ng = pr.n, pr.ngas
+    out = {}
+    if n == 0:
+        out["nodes"] = 0
+        for i, _ in enumerate(p for p in st.passes if p[0] == "gravity"):
+            out["cost%d" % i] = np.zeros(0, np.int32)
+            out["acc%d" % i] = np.zeros((0, 3))
+        st.oracle = out
+        return out
+    O.set_massless_gas_rule(st.switches["rule"])
+    try:
+        ic = pr.ic
+        T = O.Tree(ic["pos"].copy(), ic["vel"].copy(), ic["mass"], ic["type"], pr.force_soft, hsml=pr.hsml0,
+                   extent=pr.extent)
+        if st.switches["adaptive"]:
+            T.adaptive_gravsoft()
+        out["nodes"] = T.numnodes
+        old = _oldacc(st)
+        tg = np.arange(n, dtype=np.int32)
+        allgas = _gas_of(st)
+        od = None
+        ig = 0
+        acc = cost = None
+        for p in st.passes:
+            if p[0] == "gravity":
+                kind, theta = p[1], p[2]
+                if kind == "shortrange":
+                    a = _asmth(st, p[3])
+                    acc, cost = T.gravity(pr.o_grav(theta, rcut=4.5 * a, asmth=a), tg, old, kind="shortrange")
+                elif kind == "ewald":
+                    # the correction alone adds to what the call before it left
+                    if acc is None or len(acc) != len(tg):
+                        raise AssertionError("%s: an Ewald walk needs a walk of the same targets before it" % st.name)
+                    acc, cost = acc.copy(), cost.copy()
+                    T.gravity_ewald_add(pr.o_grav(theta), O.ewald_table(pr.box), tg, old, acc, cost)
+                else:
+                    acc, cost = T.gravity(pr.o_grav(theta), tg, old)
+                    if kind == "pair":
+                        T.gravity_ewald_add(pr.o_grav(theta), O.ewald_table(pr.box), tg, old, acc, cost)
+                out["acc%d" % ig], out["cost%d" % ig] = acc, cost
+                ig += 1
+            elif p[0] == "density":
+                od = T.density(pr.o_dens(), allgas, pr.velpred, pr.entropy, pr.dtentropy, pr.timebin, pr.ti_begstep,
+                               pr.hsml0)
+                out["dens_iter"] = od["iterations"]
+                out["hsml"], out["density"] = od["hsml"][allgas], od["density"][allgas]
+                T.update_hmax(allgas, od["hsml"], od["divvel"])
+            elif p[0] == "hydro":
+                gas = tg[tg < ng]
+                gas = gas[ic["type"][gas] == 0]
+                if st.switches["visc"]:
+                    import visc_ref
+                    ds = {k: od[k][:ng] for k in ("hsml", "density", "pressure", "dhsmlfac", "divvel", "curlvel")}
+                    oh = visc_ref.hydro(pr, ds, _visc_alpha(st), visc_ref.params(**st.switches["visc"]), pr.o_hydro(),
+                                        act=gas)
+                else:
+                    oh = T.hydro(pr.o_hydro(), gas, pr.velpred, od["hsml"], od["density"], od["pressure"],
+                                 od["dhsmlfac"], od["divvel"], od["curlvel"], pr.timebin)
+                out["pairs"] = oh["npairs"]
+                out["hydroaccel"] = oh["hydroaccel"][gas]
+            elif p[0] == "active":
+                tg = _active(st, p[1], p[2])
+                acc = None
+            elif p[0] == "everybody":
+                tg = np.arange(n, dtype=np.int32)
+                acc = None
+            elif p[0] == "pm":
+                out["gravpm"] = O.pm_periodic(ic["pos"], ic["mass"], pr.box, pr.G, p[1])
+            elif p[0] == "pmnp":
+                import pm_nonperiodic_ref as NP
+                out["gravpm"] = NP.pm_force(ic["pos"], ic["mass"], NP.region(ic["pos"], p[1]), pr.G)
+            elif p[0] == "substep":
+                act, dv, dt, stg = _substep_draw(st, p[1])
+                T.vel[act] += dv
+                T.kick_nodes(act, dv)
+                T.pos += T.vel * dt
+                T.drift_nodes(dt)
+                theta = 0.6
+                a2, c2 = T.gravity(pr.o_grav(theta), stg, old)
+                if pr.periodic:
+                    T.gravity_ewald_add(pr.o_grav(theta), O.ewald_table(pr.box), stg, old, a2, c2)
+                out["acc%d" % ig], out["cost%d" % ig] = a2, c2
+                ig += 1
+                out["_substep_pos"], out["_substep_vel"] = T.pos.copy(), T.vel.copy()
+            elif p[0] == "potential":
+                pass      # (checked on the device's own exported tree, as tests/test_gpu_potential.py does)
+            else:
+                raise ValueError(p)
+    finally:
+        O.set_massless_gas_rule(0)
+    st.oracle = out
+    return out
+
+
+def apply_switches(fp, have, want, st):
+    """call the setter of every switch whose value changes; returns the new state"""
+    B = bindings()
+    if have["rule"] != want["rule"]:
+        fp.set_massless_gas_rule(want["rule"])
+    if have["adaptive"] != want["adaptive"]:
+        fp.set_adaptive_gravsoft(bool(want["adaptive"]))
+    if have["dynamic"] != want["dynamic"]:
+        fp.set_dynamic_tree(bool(want["dynamic"]))
+    if have["rnd"] != want["rnd"]:
+        if want["rnd"]:
+            fp.set_field(B.F_ID, np.arange(st.pr.n, dtype=np.int32))
+        fp.set_rnd_table(rnd_table() if want["rnd"] else None)
+    if have["visc"] != want["visc"]:
+        if want["visc"]:
+            import visc_ref
+            P = B.ViscParams()
+            for k, v in visc_ref.params(**want["visc"]).items():
+                setattr(P, k, v)
+            fp.set_viscosity(P)
+        else:
+            fp.set_viscosity(None)
+    if have["dust"] != want["dust"]:
+        if want["dust"]:
+            import dust_model_ref
+            M = B.DustModel()
+            for k, v in dust_model_ref.model(*want["dust"]).items():
+                setattr(M, k, v)
+            fp.set_dust_model(M)
+        else:
+            fp.set_dust_model(None)
+    if have["iflags"] != want["iflags"]:
+        if want["iflags"]:
+            import kick_ref
+            F = B.IntegrationFlags()
+            for k, v in kick_ref.bundle(**want["iflags"]).items():
+                setattr(F, k, v)
+            fp.set_integration_flags(F)
+        else:
+            fp.set_integration_flags(None)
+    return dict(want)
+
+
+def device_stage(fp, st, have, on_potential=None):
+    """Load the stage's problem into the context `fp`, whose switches are `have`, and run its passes.  Returns (the
+    results, the switches now).  Only what a fresh-context test sets is set: the fields of Problem.load, OLDACC
+    before the walks, alpha under a viscosity mode, ID under a table.  on_potential(fp, st, pass, potential,
+    oldacc): called after every potential pass (the caller's check against the reference walk)."""
+    B = bindings()
+    pr = st.pr
+    n, ng = pr.n, pr.ngas
+    out = {}
+    # a switch that refuses the counts it finds (a table bound needs IDs of the new particles) goes first when
+    # it is taken away, last when it is set
+    want = st.switches
+    gone = {k: (want[k] if not want[k] else have[k]) for k in have}
+    have = apply_switches(fp, have, gone, st)
+    pr.load(fp)
+    have = apply_switches(fp, have, want, st)
+    if want["rnd"] and n:
+        fp.set_field(B.F_ID, np.arange(n, dtype=np.int32))
+    if want["visc"] and ng:
+        fp.visc_set_alpha(_visc_alpha(st))
+    pr.device_tree(fp)
+    old = _oldacc(st)
+    tg = np.arange(n, dtype=np.int32)
+    allgas = _gas_of(st)
+    ig = 0
+    fp.set_field(B.F_OLDACC, old)
+    for p in st.passes:
+        if p[0] == "gravity":
+            kind, theta = p[1], p[2]
+            if kind == "shortrange":
+                a = _asmth(st, p[3])
+                fp.gravity(pr.g_grav(theta, 4.5 * a, a), B.WALK_SHORTRANGE)
+            else:
+                fp.gravity(pr.g_grav(theta), {"newton": B.WALK_NEWTON, "ewald": B.WALK_EWALD,
+                                              "pair": B.WALK_NEWTON_EWALD}[kind])
+            out["cost%d" % ig] = fp.get_field(B.F_GRAVCOST)[tg]
+            out["acc%d" % ig] = fp.get_field(B.F_GRAVACCEL)[tg]
+            ig += 1
+        elif p[0] == "density":
+            fp.density(pr.g_dens())
+            out["dens_iter"] = fp.stats()["dens_iterations"]
+            for key, f in (("hsml", B.F_HSML), ("density", B.F_DENSITY), ("numngb", B.F_NUMNGB),
+                           ("dhsmlfac", B.F_DHSMLFAC), ("divvel", B.F_DIVVEL), ("curlvel", B.F_CURLVEL),
+                           ("pressure", B.F_PRESSURE)):
+                out[key] = fp.get_field(f)[allgas]
+            fp.update_hmax()
+        elif p[0] == "hydro":
+            gas = tg[tg < ng]
+            gas = gas[pr.ic["type"][gas] == 0]
+            fp.hydro(pr.g_hydro())
+            out["pairs"] = fp.stats()["hydro_pairs"]
+            for key, f in (("hydroaccel", B.F_HYDROACCEL), ("dtentropy", B.F_DTENTROPY),
+                           ("maxsignalvel", B.F_MAXSIGNALVEL)):
+                out[key] = fp.get_field(f)[gas]
+            if want["visc"]:
+                out["dtalpha"] = fp.visc_get()[1][gas]
+        elif p[0] == "active":
+            tg = _active(st, p[1], p[2])
+            fp.set_active(tg)
+        elif p[0] == "everybody":
+            tg = np.arange(n, dtype=np.int32)
+            fp.set_active(None)
+        elif p[0] == "pm":
+            fp.pm_periodic(p[1], pr.box, pr.G)
+            out["gravpm"] = fp.get_field(B.F_GRAVPM)
+        elif p[0] == "pmnp":
+            fp.pm_find_region(p[1])
+            fp.pm_nonperiodic(p[1], pr.G)
+            out["gravpm"] = fp.get_field(B.F_GRAVPM)
+        elif p[0] == "substep":
+            out["nodes"] = fp.stats()["tree_nodes"]      # (of the full build: the sub-step has no count of its own)
+            ref = oracle_stage(st)
+            act, dv, dt, stg = _substep_draw(st, p[1])
+            fp.set_field(B.F_VEL, ref["_substep_vel"])
+            fp.tree_kick_nodes(act, dv)
+            fp.set_field(B.F_POS, ref["_substep_pos"])
+            fp.tree_substep(dt)
+            fp.set_active(stg)
+            fp.gravity(pr.g_grav(0.6), B.WALK_NEWTON_EWALD if pr.periodic else B.WALK_NEWTON)
+            out["cost%d" % ig] = fp.get_field(B.F_GRAVCOST)[stg]
+            out["acc%d" % ig] = fp.get_field(B.F_GRAVACCEL)[stg]
+            ig += 1
+            fp.set_active(None)
+        elif p[0] == "potential":
+            import test_gpu_potential as TP
+            fp.potential(TP._pot_params(pr, p[1], pmgrid=p[2]))
+            k = sum(1 for q in out if q.startswith("pot_nint"))
+            pot = fp.get_potential()
+            out[("potmesh%d" if p[2] else "potential%d") % k] = pot
+            out["pot_nint%d" % k] = np.asarray(fp.potential_interactions())
+            if on_potential is not None:
+                on_potential(fp, st, p, pot, old)
+        else:
+            raise ValueError(p)
+    # the node count is read last: a build that outgrew its buffers is noticed by the walks, not by this
+    out.setdefault("nodes", fp.stats()["tree_nodes"])
+    return out, have
+
+
+def fresh_stage(st):
+    """the stage alone on a context made for it"""
+    B = bindings()
+    fp = B.ForcePath(0)
+    try:
+        return device_stage(fp, st, dict(DEFAULTS))[0]
+    finally:
+        fp.close()
+
+
+def compare(got, want, column, only=None):
+    """{key: description} for the keys of `want` (not starting with _) that `got` misses under RULES[.][column]"""
+    bad = {}
+    for key, w in want.items():
+        if key.startswith("_") or (only is not None and key not in only):
+            continue
+        how = rule_of(key)[column]
+        if how is None:
+            continue
+        assert key in got, "%s was not computed" % key
+        d = differs(how, got[key], w)
+        if d:
+            bad[key] = d
+    return bad

@@ -295,3 +295,89 @@ def test_four_call_sequence_on_two_ranks_through_the_reference_named_symbols():
     assert out["marks_equal"] and out["victims"] > 3 and out["masses_equal"]
     assert out["rel_injected"] < 1e-12 and out["rel_accreted"] < 1e-13
     assert out["swallow_counts"] == out["swallow_counts_oracle"]
+
+
+# ------------------------------------------------------------------------------------------------
+# one mirror through a changing NumPart
+# ------------------------------------------------------------------------------------------------
+def _mirror_problems():
+    from common import Problem
+    rng = np.random.default_rng(41)
+
+    def uniform(n, ngas):
+        typ = np.where(np.arange(n) < ngas, 0, 1).astype(np.int32)
+        return dict(pos=rng.random((n, 3)), vel=rng.standard_normal((n, 3)), mass=rng.uniform(0.5, 2.0, n) / n,
+                    type=typ, ngas=ngas, boxsize=1.0, spacing=1.0 / max(2.0, n ** (1 / 3)),
+                    id=np.arange(1, n + 1, dtype=np.uint32), u=np.full(ngas, 0.01))
+    return [Problem(ng=8, gas=True, periodic=1),                       # 1024 particles, 512 of them gas
+            Problem(ic=uniform(1500, 300), periodic=1),                # fewer gas records, more particles
+            Problem(ic=uniform(50, 0), periodic=1)]                    # a small set with no gas
+
+
+def _mirror_step(host, H, pr):
+    """accel.c's sequence on the particles of `pr`, given to the mirror `host` with set_particles"""
+    P = np.zeros(pr.n, H.P_DTYPE)
+    S = np.zeros(pr.ngas, H.SPH_DTYPE) if pr.ngas else None
+    P["Pos"], P["Vel"], P["Mass"], P["Type"] = pr.ic["pos"], pr.ic["vel"], pr.ic["mass"], pr.ic["type"]
+    P["ID"] = pr.ic["id"]
+    P["TimeBin"], P["Ti_begstep"] = pr.timebin, pr.ti_begstep
+    if pr.ngas:
+        S["VelPred"], S["Entropy"], S["DtEntropy"] = pr.velpred, pr.entropy, pr.dtentropy
+        S["Hsml"] = pr.hsml0[:pr.ngas]
+    host.set_particles(P, S)
+    A = host.All
+    A.G, A.ErrTolTheta, A.ErrTolForceAcc, A.TypeOfOpeningCriterion = pr.G, pr.theta, pr.ErrTolForceAcc, 1
+    A.BoxSize, A.DesNumNgb, A.MaxNumNgbDeviation = pr.box, pr.des_ngb, pr.max_dev
+    A.ArtBulkViscConst, A.Ti_Current, A.Timebase_interval = pr.visc, pr.ti_current, pr.timebase
+    A.ComovingIntegrationOn, A.MinGasHsmlFractional = 0, 0.0
+    eps = pr.force_soft[0] / 2.8
+    for name in ("Gas", "Halo", "Disk", "Bulge", "Stars", "Bndry"):
+        setattr(A, "Softening" + name, eps)
+    host.L.set_softenings()
+    host.set_active(None)
+    host.domain()
+    L = host.L
+    L.gravity_tree()
+    L.gravity_tree()                     # (the second pass opens cells by the first one's accelerations)
+    if pr.ngas:
+        L.density()
+        L.force_update_hmax()
+        L.hydro_force()
+    assert host.endrun_codes == [], L.gadget_force_last_error()
+    out = {k: P[k].copy() for k in ("GravAccel", "OldAcc", "GravCost")}
+    if pr.ngas:
+        out.update({k: S[k].copy() for k in ("Density", "Hsml", "HydroAccel", "DtEntropy", "DivVel", "Pressure",
+                                             "MaxSignalVel")})
+    return out
+
+
+def test_one_mirror_through_three_particle_sets_equals_a_mirror_per_set():
+    """set_particles three times on ONE Host -- some n and ngas; fewer gas records but more particles; a small
+    set with no gas -- with accel.c's gravity (and, where there is gas, density and hydro) after each: what the
+    mirror keeps between the calls (gadget_force_mark_dirty, TreeReconstructFlag, its context) does not reach
+    the results.  Each step equals a Host created for it alone: every integer and every SPH result to the
+    bit, the gravity accelerations (and OldAcc, their norm) to 1e-10 of the largest -- the order of a target's
+    partial sums follows the plan history of the context, the bound is that of tests/gpu_fuzz.py."""
+    H = importlib.import_module("gadget-leicester_amd.hostapi")
+    problems = _mirror_problems()
+    assert problems[1].n > problems[0].n and 0 < problems[1].ngas < problems[0].ngas
+    assert problems[2].ngas == 0 and problems[2].n < problems[0].n // 2
+    host = H.Host(periodic=1)
+    try:
+        kept = [_mirror_step(host, H, pr) for pr in problems]
+    finally:
+        host.close()
+    for step, pr in enumerate(problems):
+        host = H.Host(periodic=1)
+        try:
+            alone = _mirror_step(host, H, pr)
+        finally:
+            host.close()
+        assert kept[step].keys() == alone.keys()
+        differ = {k: float(np.abs(kept[step][k] - alone[k]).max() / np.abs(alone[k]).max())
+                  for k in alone if not np.array_equal(kept[step][k], alone[k])}
+        print("step %d (n %d, gas %d): not bit-equal to a mirror of its own: %r" % (step, pr.n, pr.ngas, differ))
+        assert np.abs(alone["GravAccel"]).max() > 0
+        for k, v in differ.items():
+            assert k in ("GravAccel", "OldAcc"), "step %d: %s differs by %.3e" % (step, k, v)
+            assert v < 1e-10, (step, k, v)
