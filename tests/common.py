@@ -355,10 +355,15 @@ def failing_collective(paths, op, params, walk=0):
 class SinkProblem:
     """A Problem with a few Type-5 sinks and Type-2 dust grains (config c5's ingredients): some DM
     particles are re-typed, one sink is the heavy central object.  Parameters of the shipped flag
-    bundle's sink passes (blackhole.c) in code units."""
+    bundle's sink passes (blackhole.c) in code units.  box: the same problem in a box of that size
+    (scale_cases.rescale_problem): every length here is a multiple of the spacing, every mass one of a
+    particle's, so they follow."""
 
-    def __init__(self, ng=8, periodic=1, nsink=6, ndust=200, seed=5):
+    def __init__(self, ng=8, periodic=1, nsink=6, ndust=200, seed=5, box=1.0):
         pr = Problem(ng=ng, gas=True, periodic=periodic)
+        if box != 1.0:
+            from scale_cases import rescale_problem
+            pr = rescale_problem(pr, box)
         self.pr = pr
         rng = np.random.default_rng(seed)
         n, ngas = pr.n, pr.ngas

@@ -17,6 +17,7 @@ import re
 import numpy as np
 
 from common import O, Problem, bindings, box_edge_particles, ics
+from scale_cases import rescaled
 
 MAX_N = 4000
 MAX_STAGES = 8
@@ -28,19 +29,9 @@ DEFAULTS = dict(rule=0, adaptive=False, dynamic=False, rnd=False, visc=None, dus
 # ------------------------------------------------------------------------------------------------
 # problems
 # ------------------------------------------------------------------------------------------------
-def _scaled(ic, box):
-    ic = dict(ic)
-    ic["pos"] = np.ascontiguousarray(ic["pos"] * box)
-    ic["pos"][ic["pos"] >= box] = 0.0
-    ic["vel"] = ic["vel"] * box
-    ic["boxsize"] = float(box)
-    ic["spacing"] = ic["spacing"] * box
-    return ic
-
-
 def cosmo(ng, seed=12345, rms=1.0, box=1.0, gas=True):
     ic = ics.make_ics(ng, gas=gas, seed=seed, clustered=True, rms_disp=rms)
-    return ic if box == 1.0 else _scaled(ic, box)
+    return ic if box == 1.0 else rescaled(ic, box)
 
 
 def plummer(n, seed=7, a=0.05, gas_fraction=0.3, center=(0.5, 0.5, 0.5)):

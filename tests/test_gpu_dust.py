@@ -25,10 +25,13 @@ def _scaled_err(a, b):
 class DustCase:
     """A SinkProblem whose Type-2 grains get drag inputs (d1-d3, radius, d7, d9, DustVcoll) chosen so
     that every stopping-time regime of dust.c:385-417 occurs, plus gas that the scatter must skip
-    (massless, dt == 0).  `dust` is the grain list in list order."""
+    (massless, dt == 0).  `dust` is the grain list in list order.  box: the SinkProblem in a box of that
+    size; the accelerations, the grains' summed velocities (d9) and MinEgySpec go with it, the drag inputs
+    stay as drawn: they are chosen against the sound speed of (rho, ent), in the physical units of
+    dust_ref.params."""
 
-    def __init__(self, periodic, ndust=600, ng=10, seed=7, sp=None):
-        sp = sp or SinkProblem(ng=ng, periodic=periodic, nsink=2, ndust=ndust, seed=seed)
+    def __init__(self, periodic, ndust=600, ng=10, seed=7, sp=None, box=1.0):
+        sp = sp or SinkProblem(ng=ng, periodic=periodic, nsink=2, ndust=ndust, seed=seed, box=box)
         pr = sp.pr
         self.sp, self.pr = sp, pr
         rng = np.random.default_rng(seed)
@@ -43,8 +46,8 @@ class DustCase:
         self.mass[gas_zero_mass] = 0.0
         rest = np.setdiff1d(np.arange(ngas), gas_zero_mass)
         self.timebin[rng.choice(rest, max(ngas // 40, 3), replace=False)] = 0
-        self.grav = 0.1 * rng.standard_normal((n, 3))
-        self.par = R.params(pr.box, periodic, pr.timebase, MinEgySpec=0.008)
+        self.grav = 0.1 * rng.standard_normal((n, 3)) * box
+        self.par = R.params(pr.box, periodic, pr.timebase, MinEgySpec=0.008 * box ** 2)
         par = self.par
         # per-grain drag inputs, by group a % 6: Epstein, Stokes rey < 1, 1 <= rey < 800, rey >= 800,
         # delta_vel == 0, dt == 0
@@ -64,7 +67,7 @@ class DustCase:
         self.gasvel = vel - dv[:, None] * d
         self.gasvel[grp == 4] = vel[grp == 4]
         self.timebin[self.dust[grp == 5]] = 0
-        self.d9 = 1e-4 * (1 + rng.random((nd, 3)))
+        self.d9 = 1e-4 * (1 + rng.random((nd, 3))) * box
         self.vcoll = rng.random(nd)
         self.gas_entropy = pr.entropy * (0.5 + rng.random(ngas))
 

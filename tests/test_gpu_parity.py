@@ -1346,8 +1346,10 @@ def test_pm_long_range_kick_parity(comoving):
     assert np.abs(want["vel"] - pr.ic["vel"]).max() > 0
 
 
-@pytest.mark.parametrize("flavour", ["one bin", "treepm", "individual steps", "comoving"])
-def test_resident_integration_loop_matches_the_oracle_loop(flavour):
+@pytest.mark.parametrize("flavour,box", [pytest.param(f, 1.0, id=f) for f in
+                                         ("one bin", "treepm", "individual steps", "comoving")] +
+                         [pytest.param("treepm", 2.5, id="treepm-box2.5")])
+def test_resident_integration_loop_matches_the_oracle_loop(flavour, box):
     """What row N1 is for: the particle state never leaves HBM between steps.  run.c's loop --
     drift to the next sync point, tree build, gravity walks, density, hmax, hydro for the ACTIVE
     particles, timestep + kick -- on the resident fields, against the same loop composed of the
@@ -1361,11 +1363,16 @@ def test_resident_integration_loop_matches_the_oracle_loop(flavour):
                         sync points with partial active lists, inactive neighbours entering with
                         their drifted (predicted) state, bins opening only when synchronised
       comoving          ComovingIntegrationOn: logarithmic timeline, drift / kick factors from the
-                        tables, a-dependent factors in the criterion, the kick and the viscosity"""
+                        tables, a-dependent factors in the criterion, the kick and the viscosity
+    box: the same problem in a box of that size (tests/scale_cases.py): lengths and velocities x box, masses
+    x box^3, entropies x box^2, the times as they are; the position bound is in units of the box."""
     B = bindings()
     treepm, multi = flavour == "treepm", flavour == "individual steps"
     comoving = flavour == "comoving"
     pr = Problem(ng=10, gas=True, periodic=1)
+    if box != 1.0:
+        from scale_cases import rescale_problem
+        pr = rescale_problem(pr, box)
     if treepm:
         pr.G = 1.7              # GravPM carries G, the tree accelerations do not (gravtree.c:379-383)
     n, ng, box = pr.n, pr.ngas, pr.box
@@ -1518,7 +1525,7 @@ def test_resident_integration_loop_matches_the_oracle_loop(flavour):
     else:
         assert visited == [0, 1 << bin_, 2 << bin_] and np.all(o["timebin"] == bin_)
     assert not treepm or (pm_beg, pm_end) == (2 << bin_, 4 << bin_)   # PM steps at Ti = 0 and 2^21
-    assert np.abs(fp.get_field(B.F_POS) - o["pos"]).max() < 1e-13
+    assert np.abs(fp.get_field(B.F_POS) - o["pos"]).max() < 1e-13 * box
     assert np.array_equal(fp.get_field(B.F_TI_BEGSTEP), o["ti_begstep"])
     assert np.array_equal(fp.get_field(B.F_TI_CURRENT), o["ti_current"])
     for fid, want in ((B.F_VEL, o["vel"]), (B.F_VELPRED, o["velpred"]), (B.F_GRAVACCEL, o["grav"]),
@@ -1529,7 +1536,7 @@ def test_resident_integration_loop_matches_the_oracle_loop(flavour):
     assert relerr(fp.get_field(B.F_DENSITY), o["density"]) < 1e-9
     if treepm:
         assert np.abs(fp.get_field(B.F_GRAVPM) - o_gpm).max() <= 1e-10 * np.abs(o_gpm).max()
-    assert np.abs(o["pos"] - pr.ic["pos"]).max() > 1e-8       # the particles did move
+    assert np.abs(o["pos"] - pr.ic["pos"]).max() > 1e-8 * box      # the particles did move
 
 
 def test_advance_and_find_timesteps_on_aos_records():

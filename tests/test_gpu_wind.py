@@ -32,10 +32,15 @@ class WindCase:
     a few more are massless (nobody's neighbour: empty space for the wind); the gas of the slab next to it has a
     small h_j and mostly only sets drmin.  `wind` is the list in list order.  Units: a wind particle covers
     C / U / FBV = 50 lengths per time, its speed; per step (time bins 0..3 of 1e-3) up to 0.4 box lengths in jumps
-    of at most 0.2 Hsml."""
+    of at most 0.2 Hsml.  box: all of it in a box of that size (scale_cases.rescale_problem): the placement range,
+    the slab limits, the boundaries, softenings and search radius x box, the masses x box^3, the momenta x box^4,
+    and the wind's speed x box through FeedBackVelocity / box."""
 
-    def __init__(self, periodic, nwind=480, ng=10, seed=2):
+    def __init__(self, periodic, nwind=480, ng=10, seed=2, box=1.0):
         pr = Problem(ng=ng, gas=True, periodic=periodic)
+        if box != 1.0:
+            from scale_cases import rescale_problem
+            pr = rescale_problem(pr, box)
         self.pr = pr
         rng = np.random.default_rng(seed)
         n, ngas = pr.n, pr.ngas
@@ -45,13 +50,15 @@ class WindCase:
         pr.ic["type"] = typ
         pos = pr.ic["pos"].copy()
         lo, hi = (0.02, 0.98) if periodic else (-0.15, 1.15)
-        pos[self.wind] = rng.uniform(lo, hi, (nwind, 3))
+        pos[self.wind] = rng.uniform(lo, hi, (nwind, 3)) * box
         pr.ic["pos"] = pos
         pr.extent = O.domain_extent(pos)
         self.par = R.params(periodic=periodic, BoxSize=pr.box, Time=1.0, dt_fac=pr.timebase, dt_fac_gas=pr.timebase,
-                            UnitDensity_in_cgs=60.0, VirtualTime=0.5, OuterBoundary=1.45, OriginalGasMass=1.6e-4,
-                            SofteningGas=0.004, SofteningGasMaxPhys=0.004, SofteningBulgeMaxPhys=0.02,
-                            PhotonSearchRadius=0.3, dt_total_floor=1e-15 * 0.5 * n, rad_accel=1, max_iter=400)
+                            UnitDensity_in_cgs=60.0, VirtualTime=0.5, OuterBoundary=1.45 * box,
+                            OriginalGasMass=1.6e-4 * box ** 3, SofteningGas=0.004 * box,
+                            SofteningGasMaxPhys=0.004 * box, SofteningBulgeMaxPhys=0.02 * box,
+                            PhotonSearchRadius=0.3 * box, dt_total_floor=1e-15 * 0.5 * n, rad_accel=1, max_iter=400,
+                            FeedBackVelocity=1.0 / box)
         speed = R.C_LIGHT / self.par["UnitVelocity_in_cm_per_s"] / self.par["FeedBackVelocity"]
         d = rng.standard_normal((nwind, 3))
         vel = pr.ic["vel"].copy()
@@ -60,19 +67,19 @@ class WindCase:
         self.hsml = pr.hsml0.copy()
         self.hsml[self.wind] = pr.ic["spacing"] * (1.2 + 1.0 * rng.random(nwind))
         gx = pos[:ngas, 0]
-        self.hsml[:ngas][(gx >= 0.4) & (gx < 0.5)] = 0.3 * pr.ic["spacing"]          # gas that only sets drmin
+        self.hsml[:ngas][(gx >= 0.4 * box) & (gx < 0.5 * box)] = 0.3 * pr.ic["spacing"]    # gas that only sets drmin
         self.mass = pr.ic["mass"].copy()
-        self.mass[:ngas][gx < 0.4] = 0.0                                             # empty space
+        self.mass[:ngas][gx < 0.4 * box] = 0.0                                       # empty space
         self.mass[rng.choice(ngas, 25, replace=False)] = 0.0
-        self.mass[self.wind] = 1e-6
+        self.mass[self.wind] = 1e-6 * box ** 3
         self.timebin = pr.timebin.copy()
         self.timebin[self.wind[rng.random(nwind) < 0.1]] = 0                        # listed, dt_jump = 0
         self.timebin[rng.choice(ngas, 30, replace=False)] = 0                        # gas with dt = 0 (RadAccel)
         self.active = np.sort(np.concatenate([rng.choice(ngas, ngas // 2, replace=False), self.wind])).astype(np.int32)
         # the state: ages on both sides of VirtualTime; every third particle is born bright (hidden at 50 %)
         self.age = rng.uniform(0.2, 0.95, nwind)
-        self.old = 1e-3 * (1 + rng.random(nwind))
-        self.birth = self.old * 50.0 * np.where(np.arange(nwind) % 3 == 0, 50.0, 1.0)
+        self.old = 1e-3 * (1 + rng.random(nwind)) * box ** 4
+        self.birth = self.old * 50.0 * box * np.where(np.arange(nwind) % 3 == 0, 50.0, 1.0)
         self.rho0 = rng.random(nwind)
         self.drmin0 = rng.random(nwind)
 
