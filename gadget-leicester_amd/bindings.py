@@ -172,6 +172,14 @@ class WindResult(C.Structure):
                 ("deleted_momentum", C.c_double)]
 
 
+class DdWindArgs(C.Structure):
+    """ghip_dd_wind_args (include/ghip.h): the wind particles resident on one multi-GPU shard, GHIP_DD_WIND"""
+    _fields_ = [("p", C.POINTER(WindParams)), ("nwind", C.c_int), ("wind_idx", C.c_void_p),
+                ("state", C.POINTER(WindState)), ("dt_jump", C.c_void_p), ("new_density", C.c_void_p),
+                ("drmin", C.c_void_p), ("delta_momentum", C.c_void_p), ("result", C.POINTER(WindResult)),
+                ("counts", C.c_void_p)]
+
+
 class IntegrationFlags(C.Structure):
     """ghip_integration_flags: the shipped bundle's rules of get_timestep / do_the_kick /
     drift_particle (include/ghip.h)"""
@@ -417,7 +425,7 @@ EXPORTS = [
     "ghip_fof_group_size", "ghip_fof_get_timing", "ghip_fof_get_maxdens_task", "ghip_dd_fof_args_size",
     "ghip_wind_params_size", "ghip_wind_density", "ghip_wind_spread", "ghip_wind_feedback",
     "ghip_wind_get_injected", "ghip_wind_set_injected", "ghip_wind_get_rad_accel", "ghip_wind_set_rad_accel",
-    "ghip_set_rad_accel", "ghip_wind_get_timing"]
+    "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size"]
 
 
 def lib():
@@ -540,6 +548,11 @@ def lib():
         if L.ghip_wind_params_size() != C.sizeof(WindParams):
             raise RuntimeError("WindParams: %d bytes here, %d in libghip.so"
                                % (C.sizeof(WindParams), L.ghip_wind_params_size()))
+        L.ghip_dd_wind_args_size.argtypes = []
+        L.ghip_dd_wind_args_size.restype = C.c_size_t
+        if L.ghip_dd_wind_args_size() != C.sizeof(DdWindArgs):
+            raise RuntimeError("DdWindArgs: %d bytes here, %d in libghip.so"
+                               % (C.sizeof(DdWindArgs), L.ghip_dd_wind_args_size()))
         L.ghip_wind_density.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
         L.ghip_wind_spread.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
         L.ghip_wind_feedback.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, C.POINTER(WindState),
@@ -1503,6 +1516,9 @@ DD_DUST_DENSITY, DD_DUST_DRAG = 9, 10
 DD_POTENTIAL, DD_GLOBAL_QUANTITIES = 11, 12
 DD_DECOMPOSE = 13
 DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
+WIND_OP = DD_DUST_DRAG   # GHIP_DD_WIND: the wind particles on shards share the dust drag's operation code ...
+WIND_FORM, WIND_DENSITY_FORM, WIND_SPREAD_FORM = 16, 17, 18   # ... and are its forms: `walk` of dd_begin / dd_run
+WIND_COUNTS = ("records_sent", "records_received", "imported_pairs", "exchanges", "bytes_sent", "iterations")
 FOF_FORM = 1             # `walk` of dd_begin / dd_run for DD_GLOBAL_QUANTITIES with DdFofArgs: the FOF groups of all shards
 SYNC_POINT_FORM = 1      # `walk` of dd_begin / dd_run for DD_DECOMPOSE with SyncParams: the sync point of all shards
 DUST_GRAINS_FORM = 1     # `walk` of dd_begin / dd_run for DD_DUST_DENSITY / DD_DUST_DRAG with DdDustGrainsArgs
@@ -1569,6 +1585,52 @@ def dd_dust_args(params, dust, particle_density=None, dust_density=None, dust_en
         setattr(A, k, getattr(g, k))
     a["_params"] = params
     return A, a
+
+
+def dd_wind_args(params, wind, state=None, dt_jump=None, new_density=None, delta_momentum=None):
+    """(args, arrays) for GHIP_DD_WIND on one shard: `wind` are its local indices in list order.  WIND_FORM:
+    state = dict(stellar_age, birth_energy, old_momentum, new_density, drmin) as ForcePath.wind_feedback takes
+    them; WIND_DENSITY_FORM: dt_jump; WIND_SPREAD_FORM: dt_jump, new_density, delta_momentum.  A filled DdWindArgs
+    and the dict of numpy arrays it points into -- inputs copied, outputs allocated (the state arrays, new_density,
+    drmin, result: WindResult, counts: int64[6], WIND_COUNTS); keep `arrays` alive until the operation has
+    finished."""
+    wind = np.ascontiguousarray(wind, np.int32)
+    nw = len(wind)
+    f64 = lambda v: np.zeros(nw) if v is None else np.ascontiguousarray(v, np.float64).reshape(nw).copy()
+    a = dict(wind_idx=wind, dt_jump_in=f64(dt_jump), new_density=f64(new_density), drmin=np.zeros(nw),
+             delta_momentum_in=f64(delta_momentum), counts=np.zeros(6, np.int64), result=WindResult(),
+             _params=params)
+    A = DdWindArgs()
+    A.p = C.pointer(params)
+    A.nwind = nw
+    A.wind_idx = wind.ctypes.data
+    if state is not None:
+        st = dict(stellar_age=f64(state["stellar_age"]), birth_energy=f64(state["birth_energy"]),
+                  old_momentum=f64(state["old_momentum"]), new_density=f64(state["new_density"]),
+                  drmin=f64(state["drmin"]), dt1=np.zeros(nw), dt2=np.zeros(nw), dt_jump=np.zeros(nw),
+                  delta_momentum=np.zeros(nw), deleted=np.zeros(nw, np.int32))
+        S = WindState()
+        for k, v in st.items():
+            setattr(S, k, v.ctypes.data)
+        a.update(state=st, _state=S)
+        A.state = C.pointer(S)
+    A.dt_jump = a["dt_jump_in"].ctypes.data
+    A.new_density = a["new_density"].ctypes.data
+    A.drmin = a["drmin"].ctypes.data
+    A.delta_momentum = a["delta_momentum_in"].ctypes.data
+    A.result = C.pointer(a["result"])
+    A.counts = a["counts"].ctypes.data
+    return A, a
+
+
+def dd_wind_result(arrays):
+    """what a finished GHIP_DD_WIND (walk = WIND_FORM) left in `arrays` of dd_wind_args, as ForcePath.wind_feedback returns
+    it: the state arrays, iterations (global), and this shard's bits, ndeleted, deleted_momentum; counts"""
+    res = arrays["result"]
+    out = dict(arrays["state"]) if "state" in arrays else {}
+    out.update(iterations=res.iterations, bits=res.bits, ndeleted=res.ndeleted,
+               deleted_momentum=res.deleted_momentum, counts=arrays["counts"].copy())
+    return out
 
 
 class DdDustGrainsArgs(C.Structure):

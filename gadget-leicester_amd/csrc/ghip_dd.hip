@@ -1003,6 +1003,36 @@ struct DustSrc   // the grains of a dust pass: list slots `ord` in tree order, l
   }
 };
 
+struct WindSrc   // the listed wind particles: list slots `list`, local indices `idx`, the planes dtj / drmin [nw].
+{                // A particle with dt_jump <= 0 takes no part in a pass: radius 0 reaches nothing.  cut = 1: the
+                 // sphere is cut to what can still change new_density (r < h_j <= hmax) or lower drmin
+                 // (|r - h_j| + h_j / 4 >= r - 3/4 hmax), with the largest h_j of all shards' gas and the drmin of the
+                 // own pass, once that found a candidate; cut = 2 (the spread alone): r < hmax
+  const int *list, *idx;
+  int n, cut;
+  const double *pos, *hsml, *dtj, *drmin;
+  double hmax;
+  __device__ __forceinline__ void load(int t, bool, int &i, double &x, double &y, double &z, double &h) const
+  {
+    const int a = list[t];
+    i = idx[a];
+    x = pos[i];
+    y = pos[(size_t) n + i];
+    z = pos[2 * (size_t) n + i];
+    h = hsml[i];
+    if(!(dtj[a] > 0.))
+      h = 0;
+    else if(cut == 2)
+      h = h < hmax ? h : hmax;
+    else if(cut == 1 && drmin[a] < 1.e40)
+      {
+        const double far = (drmin[a] + 0.75 * hmax) * (1. + 1.e-9);
+        const double c = far > hmax ? far : hmax;
+        h = h < c ? h : c;
+      }
+  }
+};
+
 // bounding box of the valid lanes' positions around lane 0's (nearest-image offsets: a chunk is compact,
 // the box may straddle the periodic boundary) and their largest radius (h = 0 in the other lanes)
 struct ChunkBox
@@ -1229,6 +1259,103 @@ int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord,
   const DustSrc S = {ord, idx, n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML])};
   k_dd_select<DustSrc, SphereReach><<<cdiv(nd, 64) * (P_ - 1), 64, 0, st>>>(
     nd, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(D.du_mask));
+  HIPCHK(hipGetLastError());
+  return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the wind particles: which shards' gas can a wind particle's sphere reach? (ghip_wind.hip runs the operation)
+// ---------------------------------------------------------------------------------------------
+// the local Type-0 particles with Mass > 0 (the candidates of both passes, virtual_density.c:650-664)
+__global__ void k_flag_wind_partners(int nt, const int *__restrict__ perm, int n, const int *__restrict__ type,
+                                     const double *__restrict__ mass, int *__restrict__ flags)
+{
+  int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if(s >= nt)
+    return;
+  const int i = perm[s];
+  flags[s] = (i < n && type[i] == 0 && mass[i] > 0) ? 1 : 0;
+}
+
+// This shard's group table over those particles, and in the status record behind it three words of the wind
+// operation (the largest h_j as a double, the dt_jump sum, the list length) and whether this shard has failed
+// already (own_rc != GHIP_OK, its message in ctx->err); the all-gather is left pending
+int ghip_dd_wind_groups(ghip_ctx *ctx, const double extra[3], int own_rc)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const std::string own_msg = ctx->err;
+  const int nt = ctx->gt.n;
+  int nsel = 0;
+  GCHK(ghip_ensure(ctx, D.gas_tgt, (size_t) (nt > 0 ? nt : 1) * 4));
+  if(nt > 0 && ctx->n > 0)
+    {
+      GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
+      k_flag_wind_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                          P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->dflags));
+      HIPCHK(hipGetLastError());
+      int *dnum = &ghip_words(ctx)->dust_partners;
+      GCHK(ghip_select_flagged(ctx, nullptr, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
+      HIPCHK(hipMemcpyAsync(&nsel, dnum, 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+    }
+  GCHK(build_groups(ctx, false, P<int>(D.gas_tgt), nsel, P<double>(ctx->f[GHIP_F_MASS])));
+  if(own_rc != GHIP_OK)   // (build_groups held its own check, which passed)
+    {
+      D.held.rc = own_rc;
+      D.held.msg = own_msg;
+    }
+  DDGroup status;
+  memset(&status, 0, sizeof(status));
+  status.cx = D.held.rc != GHIP_OK ? 1.0 : 0.0;
+  status.cy = D.guests_on ? (double) D.guests_held : 0.0;
+  status.cz = extra[0];
+  status.ex = extra[1];
+  status.ey = extra[2];
+  HIPCHK(hipMemcpyAsync(P<DDGroup>(D.grp_own) + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, st));
+  HIPCHK(ghip_stream_sync(ctx, st));   // (`status` lives on this frame)
+  ghip_dd_set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+  return 1;
+}
+
+// after that all-gather: every shard stops here if one has failed; else extra[r][3] of every shard, in rank order
+int ghip_dd_wind_status(ghip_ctx *ctx, const char *what, double *extra)
+{
+  DDState &D = ctx->dd;
+  GCHK(check_group_status(ctx, what));
+  DDGroup rec[GHIP_MAXRANKS];
+  HIPCHK(hipMemcpy2DAsync(rec, sizeof(DDGroup), P<DDGroup>(D.grp_all) + DD_TABLE, (size_t) DD_STRIDE * sizeof(DDGroup),
+                          sizeof(DDGroup), (size_t) D.nranks, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(int r = 0; r < D.nranks; r++)
+    {
+      extra[3 * r] = rec[r].cz;
+      extra[3 * r + 1] = rec[r].ex;
+      extra[3 * r + 2] = rec[r].ey;
+    }
+  return GHIP_OK;
+}
+
+// the destinations of the m listed wind particles (list: slots in tree order; idx: local indices; dtj, drmin: planes
+// in slot order) against the all-gathered tables: the per-destination lists of their local indices in ascending
+// order (D.du_list, D.du_scount / du_soff), the total.  cut, hmax: see WindSrc
+int ghip_dd_wind_select(ghip_ctx *ctx, int m, const int *list, const int *idx, const double *dtj, const double *drmin,
+                        int cut, double hmax, double boxsize, int periodic, int *total)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int P_ = D.nranks, n = ctx->n;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    D.du_scount[r] = D.du_soff[r] = 0;
+  *total = 0;
+  GCHK(ghip_ensure(ctx, D.du_list, 4));
+  if(m == 0 || P_ < 2 || n == 0)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, D.du_mask, (size_t) n * 8));
+  HIPCHK(hipMemsetAsync(D.du_mask.p, 0, (size_t) n * 8, st));
+  const WindSrc S = {list, idx, n, cut, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]), dtj, drmin, hmax};
+  k_dd_select<WindSrc, SphereReach><<<cdiv(m, 64) * (P_ - 1), 64, 0, st>>>(
+    m, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(D.du_mask));
   HIPCHK(hipGetLastError());
   return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
 }
@@ -1718,10 +1845,13 @@ static int density_step(ghip_ctx *ctx)
 // domain_exchange (domain.c:665-1060): after a drift some particles lie outside their shard's key
 // range; each moves to the shard that owns its key, with every resident field.  One record per
 // particle: 8-byte slots, the fields in enum order (ints widened), then the shard's DragHeating when it
-// holds one (ghip_dust.hip), then alpha and Dtalpha when it holds them (ghip_visc_set_alpha), slot
-// MIG_SLOTS-1 = 1 for gas.  The three optional slots have fixed places and travel as zero from a shard
+// holds one (ghip_dust.hip), then alpha and Dtalpha when it holds them (ghip_visc_set_alpha), then the three
+// components of Injected_BH_Momentum and of RadAccel when it holds them for its gas count (ghip_wind.hip), slot
+// MIG_SLOTS-1 = 1 for gas.  The optional slots have fixed places and travel as zero from a shard
 // that does not hold the array.
-#define MIG_SLOTS 40
+#define MIG_SLOTS 48
+#define MIG_NOPT 5     // optional per-gas arrays: DragHeating, alpha, Dtalpha, Injected_BH_Momentum, RadAccel
+#define MIG_XSLOTS 9   // ... and their slots (the last two have three components)
 struct MigRec
 {
   unsigned long long s[MIG_SLOTS];
@@ -1734,8 +1864,8 @@ struct MigField
 struct MigTable
 {
   int nf;
-  MigField f[GHIP_F_COUNT + 3];   // the fields, + DragHeating, alpha, Dtalpha
-  int xslot;                      // first of the three optional slots
+  MigField f[GHIP_F_COUNT + MIG_NOPT];   // the fields, + the optional arrays
+  int xslot;                             // first of the optional slots
 };
 struct MigSplits
 {
@@ -1744,8 +1874,9 @@ struct MigSplits
   const int *owner;                // [nseg]
 };
 
-// heat: the per-gas DragHeating, or nullptr when the shard holds none; visc: alpha and Dtalpha, or nullptr
-static MigTable mig_table(DevBuf *bufs, DevBuf *heat, DevBuf *const *visc)
+// heat: the per-gas DragHeating, or nullptr when the shard holds none; visc: alpha and Dtalpha, or nullptr; wind:
+// Injected_BH_Momentum and RadAccel, each or nullptr
+static MigTable mig_table(DevBuf *bufs, DevBuf *heat, DevBuf *const *visc, DevBuf *const *wind)
 {
   MigTable T;
   T.nf = GHIP_F_COUNT;
@@ -1758,18 +1889,22 @@ static MigTable mig_table(DevBuf *bufs, DevBuf *heat, DevBuf *const *visc)
       slot += T.f[f].ncomp;
     }
   T.xslot = slot;
-  DevBuf *const opt[3] = {heat, visc ? visc[0] : nullptr, visc ? visc[1] : nullptr};
-  for(int k = 0; k < 3; k++)
-    if(opt[k])
-      {
-        MigField &F = T.f[T.nf++];
-        F.p = opt[k]->p;
-        F.ncomp = 1;
-        F.isint = 0;
-        F.gas = 1;
-        F.slot = slot + k;
-      }
-  return T;   // slot + 3 <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
+  DevBuf *const opt[MIG_NOPT] = {heat, visc ? visc[0] : nullptr, visc ? visc[1] : nullptr, wind[0], wind[1]};
+  for(int k = 0; k < MIG_NOPT; k++)
+    {
+      const int ncomp = k < 3 ? 1 : 3;
+      if(opt[k])
+        {
+          MigField &F = T.f[T.nf++];
+          F.p = opt[k]->p;
+          F.ncomp = ncomp;
+          F.isint = 0;
+          F.gas = 1;
+          F.slot = slot;
+        }
+      slot += ncomp;
+    }
+  return T;   // T.xslot + MIG_XSLOTS <= MIG_SLOTS - 1 (checked by ghip_dd_begin)
 }
 
 __global__ void k_mig_dest(int n, const double *__restrict__ x, const double *__restrict__ y,
@@ -1804,7 +1939,7 @@ __global__ void k_mig_pack(int nrec, const int *__restrict__ list, int n, int ng
   const int i = list[a];
   MigRec &r = out[a];
   const bool isgas = i < ngas;
-  for(int k = 0; k < 3; k++)   // an optional array this shard does not hold: its slot travels as zero
+  for(int k = 0; k < MIG_XSLOTS; k++)   // an optional array this shard does not hold: its slots travel as zero
     r.s[T.xslot + k] = 0;
   for(int f = 0; f < T.nf; f++)
     {
@@ -1917,7 +2052,7 @@ static int migrate_begin(ghip_ctx *ctx, int, const void *, int)
       ghip_field_info(f, &gas, &ncomp, &isint);
       slots += ncomp;
     }
-  slots += 3;   // DragHeating, alpha, Dtalpha, when the shard holds them
+  slots += MIG_XSLOTS;   // the optional arrays, when the shard holds them
   if(slots > MIG_SLOTS - 1)
     return ghip_fail(ctx, GHIP_EINVAL, "migration record too small for %d field slots", slots);
   return GHIP_OK;
@@ -1935,6 +2070,10 @@ static int migrate_step(ghip_ctx *ctx)
   DevBuf *const visc_bufs[2] = {&ctx->visc_alpha, &ctx->visc_dtalpha};
   DevBuf *const visc_shadow[2] = {&D.visc_shadow[0], &D.visc_shadow[1]};
   DevBuf *const *visc = (ctx->visc_alpha.p && ctx->visc_dtalpha.p && ctx->visc_ngas == ng) ? visc_bufs : nullptr;
+  // (the same for Injected_BH_Momentum and RadAccel: carried when they are held for the gas this shard holds)
+  DevBuf *const wind[2] = {(ctx->wind_inj.p && ctx->wind_inj_ngas == ng) ? &ctx->wind_inj : nullptr,
+                           (ctx->wind_ra.p && ctx->wind_ra_ngas == ng) ? &ctx->wind_ra : nullptr};
+  DevBuf *const wind_shadow[2] = {wind[0] ? &D.wind_shadow[0] : nullptr, wind[1] ? &D.wind_shadow[1] : nullptr};
   enum { SEND, MERGE, DONE };
   if(D.phase == SEND)
     {
@@ -1964,7 +2103,7 @@ static int migrate_step(ghip_ctx *ctx)
       if(total > 0)
         {
           k_mig_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.mig_list), n, ng,
-                                                      mig_table(ctx->f, heat, visc), P<MigRec>(D.mig_send));
+                                                      mig_table(ctx->f, heat, visc, wind), P<MigRec>(D.mig_send));
           HIPCHK(hipGetLastError());
         }
       D.mig_out = total;
@@ -1980,6 +2119,11 @@ static int migrate_step(ghip_ctx *ctx)
       ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
       if(nrecv == 0 && D.mig_out == 0)
         return GHIP_OK;   // nobody left, nobody came: the resident arrays stay as they are
+      // (a wind field held for another gas count is not carried: it is dropped with the layout it belonged to)
+      if(!wind[0])
+        ctx->wind_inj_ngas = -1;
+      if(!wind[1])
+        ctx->wind_ra_ngas = -1;
       // new positions: kept gas, received gas, kept others, received others
       GCHK(ghip_ensure(ctx, D.mig_scan, (size_t) (n + nrecv + 2) * 16));
       unsigned long long *vo = P<unsigned long long>(D.mig_scan), *ro = vo + (n + 1),
@@ -2019,8 +2163,12 @@ static int migrate_step(ghip_ctx *ctx)
       if(visc)
         for(int k = 0; k < 2; k++)
           GCHK(ghip_ensure(ctx, D.visc_shadow[k], (size_t) (ngn > 0 ? ngn : 1) * 8));
-      const MigTable A = mig_table(ctx->f, heat, visc),
-                     Bn = mig_table(D.fshadow, heat ? &D.heat_shadow : nullptr, visc ? visc_shadow : nullptr);
+      for(int k = 0; k < 2; k++)
+        if(wind[k])
+          GCHK(ghip_ensure(ctx, D.wind_shadow[k], 3 * (size_t) (ngn > 0 ? ngn : 1) * 8));
+      const MigTable A = mig_table(ctx->f, heat, visc, wind),
+                     Bn = mig_table(D.fshadow, heat ? &D.heat_shadow : nullptr, visc ? visc_shadow : nullptr,
+                                    wind_shadow);
       if(n > 0)
         k_mig_move_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), ro, C,
                                                      A, Bn);
@@ -2036,6 +2184,16 @@ static int migrate_step(ghip_ctx *ctx)
         {
           ctx->visc_alpha.swap(D.visc_shadow[0]);
           ctx->visc_dtalpha.swap(D.visc_shadow[1]);
+        }
+      if(wind[0])
+        {
+          ctx->wind_inj.swap(D.wind_shadow[0]);
+          ctx->wind_inj_ngas = ngn;
+        }
+      if(wind[1])
+        {
+          ctx->wind_ra.swap(D.wind_shadow[1]);
+          ctx->wind_ra_ngas = ngn;
         }
       ctx->visc_ngas = visc ? ngn : -1;
       ctx->visc_epoch++;

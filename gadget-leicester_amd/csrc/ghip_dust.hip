@@ -1093,12 +1093,17 @@ static DustCall dust_call_dd_args(const void *params, bool drag, const char *who
 int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
   GHIP_JOIN(ctx);
+  ctx->dd.walk = walk;
+  // the wind particles share this operation's code and requirements (ghip_wind.hip): their forms hand over
+  if(op == GHIP_DD_WIND && walk >= GHIP_WIND_FORM && walk <= GHIP_WIND_SPREAD_FORM)
+    return ghip_dd_wind_begin(ctx, op, params, walk);
   const bool grains = walk == GHIP_DUST_GRAINS_FORM;
   const bool drag = op == GHIP_DD_DUST_DRAG;
   const char *who = drag ? "ghip_dd dust drag" : "ghip_dd dust density";
   const char *other = "walk = GHIP_DUST_GRAINS_FORM with ghip_dd_dust_grains_args";
   if(walk != 0 && !grains)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: walk = %d is neither 0 nor GHIP_DUST_GRAINS_FORM", who, walk);
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: walk = %d is neither 0 nor GHIP_DUST_GRAINS_FORM%s", who, walk,
+                     drag ? " nor one of the wind forms GHIP_WIND_FORM, GHIP_WIND_DENSITY_FORM, GHIP_WIND_SPREAD_FORM" : "");
   DustCall &c = ctx->dd.dust;
   if(grains)
     {
@@ -1136,6 +1141,8 @@ static void dust_write_counts(const DDState &D, long long npairs)
 int ghip_dd_dust_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
+  if(D.op == GHIP_DD_WIND && D.walk >= GHIP_WIND_FORM)
+    return ghip_dd_wind_step(ctx);
   const DustCall &c = D.dust;
   const ghip_dust_params *p = c.p;
   hipStream_t st = ctx->stream;

@@ -191,6 +191,23 @@ struct DustCall
 
 #define DD_NOPS (GHIP_DD_PM_NONPERIODIC + 1)   // operations of ghip_dd_begin, 0 = none (dd_ops[] in ghip_dd.hip)
 
+// GHIP_DD_WIND in progress (ghip_wind.hip): copies of the arguments, the form, and where the loop stands
+struct WindDD
+{
+  ghip_dd_wind_args a = {};
+  ghip_wind_params p = {};
+  int form = 0;            // GHIP_WIND_FORM, _DENSITY_FORM or _SPREAD_FORM
+  int iter = 0;            // global iterations begun (0: the density at the start)
+  int m = 0, under = 0;    // this shard's list; its particles above 1e-40
+  int m_next = 0, under_next = 0;
+  long long under_all = 0; // ... of all shards, as of the last status round
+  double hmax_all = 0;     // the largest h_j of any shard's gas
+  int cur = 0;             // which of the two list buffers holds the list
+  int nimp = 0;            // density records imported this iteration (kept for the spread pass)
+  long long bits = 0, sent = 0, recvd = 0, imp_pairs = 0, exchanges = 0;
+  bool entered = false;    // the loop was entered (the floor was passed)
+};
+
 struct DDState
 {
   bool on = false;
@@ -277,6 +294,11 @@ struct DDState
   long long gh_alpha_epoch = -1;  // ctx->visc_epoch when the ghost records in place were packed
   int du_scount[GHIP_MAXRANKS], du_soff[GHIP_MAXRANKS];
   int du_sent = 0, du_recvd = 0;
+  // the wind particles on shards (ghip_wind.hip) use the dust passes' selection and record buffers, and:
+  WindDD wind;                    // the operation in progress
+  DevBuf wd_spread, wd_srecv;     // spread records out / in; the density records in du_recv stay for the spread pass
+  DevBuf wd_cnt;                  // u64: pair counts and offsets of the combined scatter (own list | imported)
+  DevBuf wind_shadow[2];          // Injected_BH_Momentum / RadAccel of the migration's new layout
   // The trees of this step after GHIP_DD_BH_SWALLOW: only masses changed (the victims' are 0), so their
   // geometry still serves the dust passes, which read the resident masses.  Cleared wherever particles
   // move or a tree is built.
@@ -880,6 +902,8 @@ int ghip_dd_decomp_begin(ghip_ctx *ctx, int op, const void *params, int walk);  
 int ghip_dd_decomp_step(ghip_ctx *ctx);
 int ghip_dd_sync_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // sync.hip: GHIP_SYNC_POINT_FORM
 int ghip_dd_sync_step(ghip_ctx *ctx);
+int ghip_dd_wind_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // wind.hip: the wind forms of GHIP_DD_DUST_DRAG
+int ghip_dd_wind_step(ghip_ctx *ctx);
 // all shards stop together: hold keeps rc (with ctx->err if it is a failure) and says whether it failed, the flag
 // travels with the next exchange; raise(r = first rank whose flag is set, < 0: none, GHIP_OK) then fails with this
 // shard's own code and message if it holds one, else with the formatted message and GHIP_EDEVICE

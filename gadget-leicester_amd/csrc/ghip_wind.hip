@@ -1,7 +1,8 @@
 // ghip_wind.hip -- the wind particles of the reference's shipped flag bundle (-DVIRTUAL -DFB_MOMENTUM): the
 // propagation loop of momentum_feedback() with its two neighbour passes.  VIRTUAL_FLY_THORUGH_EMPTY_SPACE,
 // VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL are switches of ghip_wind_params.  Not built: spawning
-// (momentum_feedback.c:70-245, host code), fb_particles.c, REAL_EOS, NON_GRAY_RAD_TRANSFER, shards and ranks.
+// (momentum_feedback.c:70-245, host code), fb_particles.c, REAL_EOS, NON_GRAY_RAD_TRANSFER.  The loop on
+// domain-decomposed shards is GHIP_DD_WIND, at the end of this file.
 //
 // Replaces the particle loops of
 //   momentum_feedback, the loop and the elimination   momentum_feedback.c:283-568
@@ -216,11 +217,24 @@ __device__ __forceinline__ bool d_wind_pair(int j, int n, int ngas, const double
   return true;
 }
 
-// virtual_evaluate_select for the m particles of the list: those with dt_jump > 0 are evaluated, the others
-// reset.  cnt != nullptr: cnt[t] = the pairs the spread pass will write for the t-th particle (u < 1, and none
-// where new_density comes out 0).
+// Where target t of a neighbour pass comes from.  Own (rec == nullptr): list slot a = list[t] of this context's
+// wind particles, position and radius resident at idx[a], the planes w.  Imported (GHIP_DD_WIND): record t of
+// another shard's particles, {Pos, Hsml} in rec [4], and for the spread pass {NewDensity, DeltaPhotonMomentum,
+// Vel, |Vel|} in srec [6]; its slot in the pair keys is nw + t, behind the own ones.
+#define WIND_REC_DENS 4
+#define WIND_REC_SPREAD 6
+struct WindTgt
+{
+  const int *list, *idx;
+  const double *rec, *srec;
+};
+
+// virtual_evaluate_select for the m targets: those with dt_jump > 0 are evaluated, the others reset (an imported
+// record has dt_jump > 0, or it would not have been sent).  Own targets write the planes, imported ones
+// part[2 t] = the sum, part[2 t + 1] = drmin over THIS context's gas.  cnt != nullptr: cnt[t] = the pairs the
+// spread pass will write for the t-th particle (u < 1, and none where new_density comes out 0).
 __global__ void __launch_bounds__(64)
-k_wind_density(int m, const int *__restrict__ list, const int *__restrict__ idx, int n, int ngas,
+k_wind_density(int m, WindTgt T, double *__restrict__ part, int n, int ngas,
                const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
                const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
                const int *__restrict__ perm, BoxK b, int nw, double *__restrict__ w,
@@ -229,14 +243,28 @@ k_wind_density(int m, const int *__restrict__ list, const int *__restrict__ idx,
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= m)
     return;
-  const int a = list[t];
+  const int a = T.rec ? 0 : T.list[t];
   const size_t D = (size_t) nw;
   double rho = 0., drmin = 1.e40;
   unsigned long long c = 0;
-  if(w[WP_DTJ * D + a] > 0.)
+  if(T.rec || w[WP_DTJ * D + a] > 0.)
     {
-      const int i = idx[a];
-      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i], h = hsml[i];
+      double px, py, pz, h;
+      if(T.rec)
+        {
+          px = T.rec[WIND_REC_DENS * (size_t) t];
+          py = T.rec[WIND_REC_DENS * (size_t) t + 1];
+          pz = T.rec[WIND_REC_DENS * (size_t) t + 2];
+          h = T.rec[WIND_REC_DENS * (size_t) t + 3];
+        }
+      else
+        {
+          const int i = T.idx[a];
+          px = pos[i];
+          py = pos[(size_t) n + i];
+          pz = pos[2 * (size_t) n + i];
+          h = hsml[i];
+        }
       // every pair with u < 1 has r < h_j <= hmax: this walk meets them all, in the order the walk of the whole
       // sphere h would (its nodes are a subset in the same pre-order)
       const double hmax = __longlong_as_double((long long) words->hmax);
@@ -274,17 +302,25 @@ k_wind_density(int m, const int *__restrict__ list, const int *__restrict__ idx,
             });
         }
     }
-  w[WP_RHO * D + a] = rho;
-  w[WP_DRMIN * D + a] = drmin;
+  if(T.rec)
+    {
+      part[2 * (size_t) t] = rho;
+      part[2 * (size_t) t + 1] = drmin;
+    }
+  else
+    {
+      w[WP_RHO * D + a] = rho;
+      w[WP_DRMIN * D + a] = drmin;
+    }
   if(cnt)
     cnt[t] = rho > 0. ? c : 0;
 }
 
 // the pairs of virtual_evaluate_onthespot (virtual_spread_momentum.c:129-130, 393-419) for the m particles of
-// the list.  fill == 0: count them into cnt[t]; fill == 1: write (j << 32 | a, W) from off[t] on.
+// m targets.  fill == 0: count them into cnt[t]; fill == 1: write (j << 32 | slot, W) from off[t] on.
 template <int fill>
 __global__ void __launch_bounds__(64)
-k_wind_pairs(int m, const int *__restrict__ list, const int *__restrict__ idx, int n, int ngas,
+k_wind_pairs(int m, WindTgt T, int n, int ngas,
              const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
              const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
              const int *__restrict__ perm, BoxK b, int nw, const double *__restrict__ w,
@@ -295,14 +331,28 @@ k_wind_pairs(int m, const int *__restrict__ list, const int *__restrict__ idx, i
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= m)
     return;
-  const int a = list[t];
+  const int a = T.rec ? nw + t : T.list[t];   // the slot of the pair keys
   const size_t D = (size_t) nw;
   unsigned long long c = 0;
-  if(w[WP_RHO * D + a] > 0. && w[WP_DTJ * D + a] > 0.)
+  if(T.rec ? T.srec[WIND_REC_SPREAD * (size_t) t] > 0. : (w[WP_RHO * D + a] > 0. && w[WP_DTJ * D + a] > 0.))
     {
       const unsigned long long o = fill ? off[t] : 0;
-      const int i = idx[a];
-      const double px = pos[i], py = pos[(size_t) n + i], pz = pos[2 * (size_t) n + i], h = hsml[i];
+      double px, py, pz, h;
+      if(T.rec)
+        {
+          px = T.rec[WIND_REC_DENS * (size_t) t];
+          py = T.rec[WIND_REC_DENS * (size_t) t + 1];
+          pz = T.rec[WIND_REC_DENS * (size_t) t + 2];
+          h = T.rec[WIND_REC_DENS * (size_t) t + 3];
+        }
+      else
+        {
+          const int i = T.idx[a];
+          px = pos[i];
+          py = pos[(size_t) n + i];
+          pz = pos[2 * (size_t) n + i];
+          h = hsml[i];
+        }
       const double r1 = fmin(h, __longlong_as_double((long long) words->hmax));   // (as k_wind_density)
       d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
         double r, hj;
@@ -328,11 +378,13 @@ k_wind_pairs(int m, const int *__restrict__ list, const int *__restrict__ idx, i
     cnt[t] = c;
 }
 
-// the momentum one gas particle receives from its run of sorted pairs, in list order
-// (virtual_spread_momentum.c:432, 447-448)
+// the momentum one gas particle receives from its run of sorted pairs, in slot order: the own wind particles in
+// list order, slots [0, nw), from the planes; then the nimp imported ones in receive order, slots nw + t, from
+// their spread records (virtual_spread_momentum.c:432, 447-448)
 __global__ void k_wind_apply(long long npairs, const unsigned long long *__restrict__ key,
-                             const double *__restrict__ wgt, int nw, const double *__restrict__ w,
-                             const double *__restrict__ mass, int ngas, double *__restrict__ inj)
+                             const double *__restrict__ wgt, int nw, const double *__restrict__ w, int nimp,
+                             const double *__restrict__ srec, const double *__restrict__ mass, int ngas,
+                             double *__restrict__ inj)
 {
   const long long s0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
   if(s0 >= npairs)
@@ -348,13 +400,32 @@ __global__ void k_wind_apply(long long npairs, const unsigned long long *__restr
   for(long long s = s0; s < npairs && (unsigned int) (key[s] >> 32) == j; s++)
     {
       const unsigned int a = (unsigned int) (key[s] & 0xffffffffULL);
-      if(a >= (unsigned int) nw)
+      if(a >= (unsigned int) nw + (unsigned int) nimp)
         continue;
-      const double ddpm = w[WP_DMOM * D + a] * mj * wgt[s] / w[WP_RHO * D + a];
-      const double va = w[WP_VABS * D + a];
-      i0 += ddpm * w[WP_VX * D + a] / va;
-      i1 += ddpm * w[WP_VY * D + a] / va;
-      i2 += ddpm * w[WP_VZ * D + a] / va;
+      double rho, dmom, v0, v1, v2, va;
+      if(a < (unsigned int) nw)
+        {
+          rho = w[WP_RHO * D + a];
+          dmom = w[WP_DMOM * D + a];
+          v0 = w[WP_VX * D + a];
+          v1 = w[WP_VY * D + a];
+          v2 = w[WP_VZ * D + a];
+          va = w[WP_VABS * D + a];
+        }
+      else
+        {
+          const double *q = srec + WIND_REC_SPREAD * (size_t) (a - (unsigned int) nw);
+          rho = q[0];
+          dmom = q[1];
+          v0 = q[2];
+          v1 = q[3];
+          v2 = q[4];
+          va = q[5];
+        }
+      const double ddpm = dmom * mj * wgt[s] / rho;
+      i0 += ddpm * v0 / va;
+      i1 += ddpm * v1 / va;
+      i2 += ddpm * v2 / va;
     }
   inj[j] = i0;
   inj[G + j] = i1;
@@ -535,16 +606,17 @@ static WindK wind_k(const ghip_wind_params *p)
   return K;
 }
 
-static bool wind_sharded(const ghip_ctx *ctx)
+// A ghip_set_shard context is refused everywhere.  A ghip_dd_init context is refused by the three passes, which
+// run there as GHIP_DD_WIND; the resident gas fields and RAD_ACCEL in the integrator are per-particle and serve it
+// (dd_ok).
+static int wind_refuse_sharded(ghip_ctx *ctx, const char *who, bool dd_ok = false)
 {
-  return ctx->shard_n > 1 || ctx->dd.on;
-}
-
-static int wind_refuse_sharded(ghip_ctx *ctx, const char *who)
-{
-  if(wind_sharded(ctx))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded or multi-GPU context (ghip_set_shard / "
-                     "ghip_dd_init): the wind passes are single-rank only", who);
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard): the wind passes "
+                     "are single-rank only", who);
+  if(ctx->dd.on && !dd_ok)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU context (ghip_dd_init): this entry point is "
+                     "single-rank, shards run GHIP_DD_WIND with walk = GHIP_WIND_FORM (ghip_dd_begin / ghip_dd_run)", who);
   return GHIP_OK;
 }
 
@@ -661,12 +733,16 @@ static int wind_rad_accel(ghip_ctx *ctx, const char *who)
     P<SphNode>(ctx->st.mq), P<int>(ctx->st.perm)
 
 // The scatter of the m particles of `list` (cnt[0, m) counted, cnt[m] = 0, scanned into off; npairs = off[m]):
-// fill, sort, apply
-static int wind_scatter(ghip_ctx *ctx, const WindDev &d, const BoxK &b, int m, const int *list, long long npairs)
+// fill, sort, apply.  GHIP_DD_WIND: behind them the nimp imported records of `imp`, counted and scanned behind the
+// own ones (off[m .. m + nimp], npairs = off[m + nimp])
+static int wind_scatter(ghip_ctx *ctx, const WindDev &d, const BoxK &b, int m, const int *list, long long npairs,
+                        const unsigned long long *off = nullptr, int nimp = 0, const WindTgt *imp = nullptr)
 {
+  if(!off)
+    off = d.off;
   if(npairs < 0 || npairs > (long long) INT_MAX)
     return ghip_fail(ctx, GHIP_EDEVICE, "ghip_wind: %lld wind-gas pairs", npairs);
-  if(npairs == 0 || m == 0)
+  if(npairs == 0 || m + nimp == 0)
     return GHIP_OK;
   hipStream_t st = ctx->stream;
   const size_t np = (size_t) npairs;
@@ -674,15 +750,19 @@ static int wind_scatter(ghip_ctx *ctx, const WindDev &d, const BoxK &b, int m, c
   GCHK(ghip_ensure(ctx, ctx->wind_pairs, np * 32 + 256));
   unsigned long long *k0 = P<unsigned long long>(ctx->wind_pairs), *k1 = k0 + np;
   double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
-  k_wind_pairs<1><<<cdiv(m, 64), 64, 0, st>>>(m, list, d.idx, WIND_GAS_ARGS, b, d.nw, d.w, nullptr, d.off,
-                                              (unsigned long long) npairs, k0, w0, d.words);
+  if(m > 0)
+    k_wind_pairs<1><<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{list, d.idx, nullptr, nullptr}, WIND_GAS_ARGS, b, d.nw, d.w,
+                                                nullptr, off, (unsigned long long) npairs, k0, w0, d.words);
+  if(nimp > 0)
+    k_wind_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, *imp, WIND_GAS_ARGS, b, d.nw, d.w, nullptr, off + m,
+                                                   (unsigned long long) npairs, k0, w0, d.words);
   HIPCHK(hipGetLastError());
   int end_bit = 33;
   while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
     end_bit++;
   GCHK(ghip_sort_pairs(ctx, k0, k1, w0, w1, (int) np, end_bit, st));
-  k_wind_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, d.nw, d.w, P<double>(ctx->f[GHIP_F_MASS]),
-                                                  ctx->ngas, P<double>(ctx->wind_inj));
+  k_wind_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, d.nw, d.w, nimp, imp ? imp->srec : nullptr,
+                                                  P<double>(ctx->f[GHIP_F_MASS]), ctx->ngas, P<double>(ctx->wind_inj));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -734,8 +814,8 @@ extern "C" int ghip_wind_density(ghip_ctx *ctx, const ghip_wind_params *p, int n
   hipStream_t st = ctx->stream;
   const size_t D = (size_t) nwind;
   HIPCHK(hipMemcpyAsync(d.w + WP_DTJ * D, dt_jump, D * 8, hipMemcpyHostToDevice, st));
-  k_wind_density<<<cdiv(nwind, 64), 64, 0, st>>>(nwind, d.ord, d.idx, WIND_GAS_ARGS, make_box(p->BoxSize, p->periodic),
-                                                 nwind, d.w, nullptr, d.words);
+  k_wind_density<<<cdiv(nwind, 64), 64, 0, st>>>(nwind, WindTgt{d.ord, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS,
+                                                 make_box(p->BoxSize, p->periodic), nwind, d.w, nullptr, d.words);
   HIPCHK(hipGetLastError());
   WindWords h;
   HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -771,8 +851,8 @@ extern "C" int ghip_wind_spread(ghip_ctx *ctx, const ghip_wind_params *p, int nw
   HIPCHK(hipMemcpyAsync(d.w + WP_RHO * D, new_density, D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d.w + WP_DMOM * D, delta_momentum, D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d.cnt, 0, (D + 1) * 8, st));
-  k_wind_pairs<0><<<cdiv(nwind, 64), 64, 0, st>>>(nwind, d.ord, d.idx, WIND_GAS_ARGS, b, nwind, d.w, d.cnt, nullptr,
-                                                  0ULL, nullptr, nullptr, d.words);
+  k_wind_pairs<0><<<cdiv(nwind, 64), 64, 0, st>>>(nwind, WindTgt{d.ord, d.idx, nullptr, nullptr}, WIND_GAS_ARGS, b, nwind,
+                                                  d.w, d.cnt, nullptr, 0ULL, nullptr, nullptr, d.words);
   HIPCHK(hipGetLastError());
   GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, nwind + 1, st));
   k_wind_npairs<<<1, 64, 0, st>>>(d.off, nwind, d.words);
@@ -874,7 +954,8 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
     return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, m, nw);
   k_wind_reset<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.w);
   if(m > 0)
-    k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, cur, d.idx, WIND_GAS_ARGS, K.b, nw, d.w, nullptr, d.words);
+    k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{cur, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, K.b, nw,
+                                               d.w, nullptr, d.words);
   HIPCHK(hipGetLastError());
 
   // ---- :307-490 ----
@@ -899,7 +980,8 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
       HIPCHK(hipEventRecord(ev[1], st));
       HIPCHK(hipMemsetAsync(d.cnt + m, 0, 8, st));
       if(m > 0)
-        k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, cur, d.idx, WIND_GAS_ARGS, K.b, nw, d.w, d.cnt, d.words);
+        k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{cur, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, K.b,
+                                                   nw, d.w, d.cnt, d.words);
       HIPCHK(hipGetLastError());
       GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, m + 1, st));
       k_wind_npairs<<<1, 64, 0, st>>>(d.off, m, d.words);
@@ -986,7 +1068,7 @@ extern "C" int ghip_wind_get_injected(ghip_ctx *ctx, double *injected)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_injected"));
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_injected", true));
   if(!injected)
     return GHIP_OK;
   GCHK(wind_injected(ctx, "ghip_wind_get_injected"));
@@ -998,7 +1080,7 @@ extern "C" int ghip_wind_set_injected(ghip_ctx *ctx, const double *injected)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_injected"));
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_injected", true));
   if(!injected)
     return GHIP_OK;
   GCHK(wind_upload3(ctx, ctx->wind_inj, injected, ctx->ngas));
@@ -1011,7 +1093,7 @@ extern "C" int ghip_wind_get_rad_accel(ghip_ctx *ctx, double *rad_accel)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_rad_accel"));
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_get_rad_accel", true));
   if(!rad_accel)
     return GHIP_OK;
   GCHK(wind_rad_accel(ctx, "ghip_wind_get_rad_accel"));
@@ -1023,7 +1105,7 @@ extern "C" int ghip_wind_set_rad_accel(ghip_ctx *ctx, const double *rad_accel)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_rad_accel"));
+  GCHK(wind_refuse_sharded(ctx, "ghip_wind_set_rad_accel", true));
   if(!rad_accel)
     return GHIP_OK;
   GCHK(wind_upload3(ctx, ctx->wind_ra, rad_accel, ctx->ngas));
@@ -1037,7 +1119,7 @@ extern "C" int ghip_set_rad_accel(ghip_ctx *ctx, int on)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
   if(on)
-    GCHK(wind_refuse_sharded(ctx, "ghip_set_rad_accel"));
+    GCHK(wind_refuse_sharded(ctx, "ghip_set_rad_accel", true));
   ctx->rad_accel_on = on != 0;
   return GHIP_OK;
 }
@@ -1049,8 +1131,599 @@ int ghip_rad_accel_field(ghip_ctx *ctx, const char *who, const double **ra)
   *ra = nullptr;
   if(!ctx->rad_accel_on)
     return GHIP_OK;
-  GCHK(wind_refuse_sharded(ctx, who));
+  GCHK(wind_refuse_sharded(ctx, who, true));
   GCHK(wind_rad_accel(ctx, who));
   *ra = P<double>(ctx->wind_ra);
   return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the loop on multi-GPU shards (GHIP_DD_WIND: GHIP_DD_DUST_DRAG begun with one of the wind forms as `walk`;
+// ghip_dd_dust_begin / _step hand over)
+//
+// The reference runs momentum_feedback() under NTask > 1: dt_total and N_active are all-reduced
+// (momentum_feedback.c:301, 469-470), virtual_density() and virtual_spread_momentum() export a particle to the
+// tasks its sphere touches and add (virtual_density.c:344) or minimise (:356) what comes back.  Here a wind
+// particle stays on its home shard, which moves it; it goes to every other shard whose gas boxes its sphere can
+// reach (the all-gathered group boxes of the Type-0 particles with Mass > 0, ghip_dd.hip):
+//   GROUPS    list, order, velocities, dt_jump and its sum, the first list; group table -> all-gather, with the
+//             shard's hmax, dt_jump sum, list length and failure flag in the status record behind it
+//   START     the floor test on the sum of all shards (ascending rank order); the density at the start (:305)
+//   per iteration  [move and] own density partial; selection; records {Pos, Hsml}      -> all-to-all-v
+//     DENS_IMP   the imported records against this shard's gas; partials {rho, drmin}  -> all-to-all-v (home)
+//     DENS_ADD   own + partials in ascending rank order, drmin = min; the new list;
+//                {list length, above 1e-40, failed}                                    -> all-gather
+//     STATUS     every shard stops if one failed; records {rho, dmom, Vel, |Vel|}       -> all-to-all-v
+//     SPREAD     the scatter of the own list and the imported records into this shard's gas; stop or go on
+// Four exchanges per iteration: the spread needs the total density (two dependent all-to-all-v), the stop decision
+// is the reference's all-reduce, and the spread records need that density.  The importing shard keeps the density
+// records, so the spread record carries no position.  DENSITY_FORM ends in DENS_ADD, SPREAD_FORM goes from START
+// over the position records (SPREAD_POS) to SPREAD.
+// ---------------------------------------------------------------------------------------------
+int ghip_dd_wind_groups(ghip_ctx *ctx, const double extra[3], int own_rc);   // ghip_dd.hip
+int ghip_dd_wind_status(ghip_ctx *ctx, const char *what, double *extra);
+int ghip_dd_wind_select(ghip_ctx *ctx, int m, const int *list, const int *idx, const double *dtj, const double *drmin,
+                        int cut, double hmax, double boxsize, int periodic, int *total);
+
+__global__ void k_wind_slots(int nw, const int *__restrict__ idx, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < nw)
+    slot[idx[a]] = a;
+}
+
+// record r of the send lists: local particle list[r], list slot slot[list[r]].  K = WIND_REC_DENS: {Pos, Hsml};
+// K = WIND_REC_SPREAD: {NewDensity, DeltaPhotonMomentum, Vel, |Vel|} from the planes
+template <int K>
+__global__ void k_wind_pack(int total, const int *__restrict__ list, const int *__restrict__ slot, int n,
+                            const double *__restrict__ pos, const double *__restrict__ hsml, int nw,
+                            const double *__restrict__ w, double *__restrict__ out)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r >= total)
+    return;
+  const int i = list[r];
+  double *o = out + (size_t) K * r;
+  if(K == WIND_REC_DENS)
+    {
+      o[0] = pos[i];
+      o[1] = pos[(size_t) n + i];
+      o[2] = pos[2 * (size_t) n + i];
+      o[3] = hsml[i];
+    }
+  else
+    {
+      const int a = slot[i];
+      const size_t D = (size_t) nw;
+      o[0] = w[WP_RHO * D + a];
+      o[1] = w[WP_DMOM * D + a];
+      o[2] = w[WP_VX * D + a];
+      o[3] = w[WP_VY * D + a];
+      o[4] = w[WP_VZ * D + a];
+      o[5] = w[WP_VABS * D + a];
+    }
+}
+
+// the partials {rho, drmin} one shard returned for the cnt particles it was sent: NewDensity += , drmin = min
+__global__ void k_wind_add_parts(int cnt, const int *__restrict__ list, const int *__restrict__ slot,
+                                 const double *__restrict__ back, int nw, double *__restrict__ w)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if(k >= cnt)
+    return;
+  const int a = slot[list[k]];
+  const size_t D = (size_t) nw;
+  w[WP_RHO * D + a] += back[2 * (size_t) k];
+  const double dr = back[2 * (size_t) k + 1];
+  if(dr < w[WP_DRMIN * D + a])
+    w[WP_DRMIN * D + a] = dr;
+}
+
+extern "C" size_t ghip_dd_wind_args_size(void)
+{
+  return sizeof(ghip_dd_wind_args);
+}
+
+enum { WDD_GROUPS, WDD_START, WDD_DENS_IMP, WDD_DENS_ADD, WDD_STATUS, WDD_SPREAD, WDD_SPREAD_POS };
+
+static const char *wind_dd_who(int form)
+{
+  return form == GHIP_WIND_DENSITY_FORM ? "ghip_dd wind density"
+                                        : (form == GHIP_WIND_SPREAD_FORM ? "ghip_dd wind spread" : "ghip_dd wind feedback");
+}
+
+int ghip_dd_wind_begin(ghip_ctx *ctx, int, const void *params, int walk)
+{
+  GHIP_JOIN(ctx);
+  const char *who = wind_dd_who(walk);
+  if(walk != GHIP_WIND_FORM && walk != GHIP_WIND_DENSITY_FORM && walk != GHIP_WIND_SPREAD_FORM)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd wind: walk = %d is none of GHIP_WIND_FORM, GHIP_WIND_DENSITY_FORM and "
+                     "GHIP_WIND_SPREAD_FORM", walk);
+  GCHK(wind_refuse_sharded(ctx, who, true));
+  const ghip_dd_wind_args &a = *reinterpret_cast<const ghip_dd_wind_args *>(params);
+  const ghip_wind_state *s = a.state;
+  bool bad = !a.p || a.nwind < 0 || (a.nwind > 0 && !a.wind_idx);
+  if(walk == GHIP_WIND_FORM)
+    bad = bad || !a.result || (a.nwind > 0 && (!s || !s->stellar_age || !s->birth_energy || !s->old_momentum ||
+                                               !s->new_density || !s->drmin || !s->dt1 || !s->dt2 || !s->dt_jump ||
+                                               !s->delta_momentum || !s->deleted));
+  else if(walk == GHIP_WIND_DENSITY_FORM)
+    bad = bad || (a.nwind > 0 && (!a.dt_jump || !a.new_density || !a.drmin));
+  else
+    bad = bad || (a.nwind > 0 && (!a.dt_jump || !a.new_density || !a.delta_momentum));
+  if(bad)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(walk == GHIP_WIND_FORM && (a.p->max_iter < 1 || !(a.p->dt_fac >= 0)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
+  // (after GHIP_DD_BH_SWALLOW the trees are marked stale for their moments; their geometry still holds)
+  if(!ctx->gt.built && !ctx->dd.geom_kept)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_GRAVITY of this step first", who);
+  if(!ctx->st.built && !ctx->dd.geom_kept)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_DENSITY of this step first", who);
+  for(int k = 0; k < a.nwind; k++)
+    if(a.wind_idx[k] < 0 || a.wind_idx[k] >= ctx->n)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range", who, a.wind_idx[k]);
+  WindDD &W = ctx->dd.wind;
+  W = WindDD();
+  W.a = a;
+  W.p = *a.p;
+  W.a.p = &W.p;
+  W.form = walk;
+  for(int k = 0; k < 5; k++)
+    ctx->wind_ms[k] = 0;
+  if(a.result)
+    memset(a.result, 0, sizeof(*a.result));
+  if(a.counts)
+    for(int k = 0; k < 6; k++)
+      a.counts[k] = 0;
+  return GHIP_OK;
+}
+
+static void wind_dd_counts(const DDState &D)
+{
+  const WindDD &W = D.wind;
+  if(!W.a.counts)
+    return;
+  W.a.counts[0] = W.sent;
+  W.a.counts[1] = W.recvd;
+  W.a.counts[2] = W.imp_pairs;
+  W.a.counts[3] = W.exchanges;
+  W.a.counts[4] = D.bytes_sent[D.op];
+  W.a.counts[5] = W.iter;
+}
+
+static int *wind_dd_list(const WindDev &d, const WindDD &W, bool next = false)
+{
+  if(W.form != GHIP_WIND_FORM)
+    return d.ord;
+  return (W.cur ^ (next ? 1 : 0)) ? d.listb : d.lista;
+}
+
+// Device milliseconds of the operation's phases on this shard, for ghip_wind_get_timing: [0] move, [1] own density,
+// [2] spread (count, fill, sort, apply), [3] list, [4] imported density -- summed over the iterations.  An event pair
+// is read after the next wait of the host that the operation has anyway.
+enum { WT_MOVE = 0, WT_OWN = 1, WT_SPREAD = 2, WT_LIST = 3, WT_IMP = 4 };
+static int wind_dd_mark(ghip_ctx *ctx, int k)
+{
+  if(!ctx->wind_ev[k])
+    HIPCHK(hipEventCreate(&ctx->wind_ev[k]));
+  HIPCHK(hipEventRecord(ctx->wind_ev[k], ctx->stream));
+  return GHIP_OK;
+}
+static void wind_dd_add_ms(ghip_ctx *ctx, int slot, int k)   // events k, k + 1, both complete
+{
+  float f = 0;
+  if(ctx->wind_ev[k] && ctx->wind_ev[k + 1] && hipEventElapsedTime(&f, ctx->wind_ev[k], ctx->wind_ev[k + 1]) == hipSuccess)
+    ctx->wind_ms[slot] += f;
+}
+
+// the own density partial of the list, the destinations, the position records on their way
+static int wind_dd_density_send(ghip_ctx *ctx, int next_phase)
+{
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  hipStream_t st = ctx->stream;
+  const WindDev d = wind_dev(ctx, W.a.nwind > 0 ? W.a.nwind : 1);
+  const int nw = W.a.nwind, m = W.m;
+  const size_t Dn = (size_t) d.nw;
+  const BoxK b = make_box(W.p.BoxSize, W.p.periodic);
+  const int *list = wind_dd_list(d, W);
+  const bool spread_only = W.form == GHIP_WIND_SPREAD_FORM;
+  GCHK(wind_dd_mark(ctx, 2));
+  if(m > 0 && !spread_only)
+    {
+      k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{list, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, b, d.nw,
+                                                 d.w, nullptr, d.words);
+      HIPCHK(hipGetLastError());
+    }
+  GCHK(wind_dd_mark(ctx, 3));
+  int total = 0;
+  // (GHIP_WIND_DD_CUT=0, for measurements: select with the whole sphere Hsml; the results are the same)
+  const bool cut = !(getenv("GHIP_WIND_DD_CUT") && atoi(getenv("GHIP_WIND_DD_CUT")) == 0);
+  GCHK(ghip_dd_wind_select(ctx, m, list, d.idx, d.w + WP_DTJ * Dn, d.w + WP_DRMIN * Dn, !cut ? 0 : (spread_only ? 2 : 1), W.hmax_all,
+                           W.p.BoxSize, W.p.periodic, &total));
+  if(D.nranks > 1 && m > 0 && ctx->n > 0)   // (the selection waited for the device)
+    {
+      wind_dd_add_ms(ctx, WT_OWN, 2);
+      if(W.iter > 0)
+        wind_dd_add_ms(ctx, WT_MOVE, 0);
+    }
+  GCHK(ghip_ensure(ctx, D.du_send, (size_t) (total > 0 ? total : 1) * WIND_REC_DENS * 8));
+  if(total > 0)
+    {
+      k_wind_pack<WIND_REC_DENS><<<cdiv(total, 256), 256, 0, st>>>(
+        total, P<int>(D.du_list), P<int>(D.du_slot), ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+        P<double>(ctx->f[GHIP_F_HSML]), nw, d.w, P<double>(D.du_send));
+      HIPCHK(hipGetLastError());
+    }
+  D.du_sent = total;
+  W.sent += total;
+  ghip_dd_set_alltoallv(D, D.du_send.p, (size_t) WIND_REC_DENS * 8, D.du_scount, D.du_soff, &D.du_recv);
+  W.exchanges++;
+  D.phase = next_phase;
+  return 1;
+}
+
+// one more iteration: the move of the own list, then its density pass
+static int wind_dd_iterate(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  hipStream_t st = ctx->stream;
+  const WindDev d = wind_dev(ctx, W.a.nwind > 0 ? W.a.nwind : 1);
+  W.iter++;
+  W.bits += (W.iter == 1) ? W.m : W.under;
+  GCHK(wind_dd_mark(ctx, 0));
+  if(W.m > 0)
+    {
+      k_wind_move<<<cdiv(W.m, 256), 256, 0, st>>>(W.m, wind_dd_list(d, W), d.idx, ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+                                                  P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_MASS]), d.nw, d.w,
+                                                  wind_k(&W.p));
+      HIPCHK(hipGetLastError());
+    }
+  GCHK(wind_dd_mark(ctx, 1));
+  return wind_dd_density_send(ctx, WDD_DENS_IMP);
+}
+
+// the end of the loop on this shard: RAD_ACCEL and the elimination (not after max_iter), the state back
+static int wind_dd_finish(ghip_ctx *ctx, bool noconv)
+{
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  hipStream_t st = ctx->stream;
+  const int nw = W.a.nwind;
+  const WindDev d = wind_dev(ctx, nw > 0 ? nw : 1);
+  const WindK K = wind_k(&W.p);
+  ghip_wind_result *res = W.a.result;
+  res->iterations = W.iter;
+  res->bits = W.bits;
+  if(!noconv)
+    {
+      if(W.p.rad_accel)
+        {
+          const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
+          const int *act = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
+          if(nact > 0 && ctx->ngas > 0)
+            k_wind_rad_accel<<<cdiv(nact, 256), 256, 0, st>>>(nact, act, ctx->ngas, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                              P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(ctx->f[GHIP_F_MASS]),
+                                                              P<double>(ctx->wind_inj), P<double>(ctx->wind_ra), K.dt_fac_gas);
+        }
+      if(nw > 0)
+        k_wind_eliminate<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+                                                        P<double>(ctx->f[GHIP_F_MASS]), d.w, d.deleted, K);
+      HIPCHK(hipGetLastError());
+    }
+  if(nw > 0)
+    {
+      const ghip_wind_state *s = W.a.state;
+      GCHK(wind_download_state(ctx, d, s, true));
+      for(int a = 0; a < nw; a++)   // :558-559, in list order
+        if(s->deleted[a])
+          {
+            res->ndeleted++;
+            if(s->deleted[a] == 1)
+              res->deleted_momentum += s->old_momentum[a];
+          }
+    }
+  HIPCHK(ghip_stream_sync(ctx, st));
+  wind_dd_counts(D);
+  if(noconv)
+    return ghip_fail(ctx, GHIP_ENOCONV, "%s: %lld wind particles still under way after max_iter = %d iterations",
+                     wind_dd_who(W.form), W.under_all, W.p.max_iter);
+  return 0;
+}
+
+int ghip_dd_wind_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  hipStream_t st = ctx->stream;
+  const char *who = wind_dd_who(W.form);
+  const int nw = W.a.nwind, n = ctx->n;
+  const size_t Dn = (size_t) (nw > 0 ? nw : 1);
+  const BoxK b = make_box(W.p.BoxSize, W.p.periodic);
+  if(D.phase == WDD_GROUPS)
+    {
+      // the arrays are made for one particle at least: a shard without wind still holds the words
+      GCHK(ghip_ensure(ctx, ctx->wind_idx, ((9 * Dn * 4 + 63) & ~(size_t) 63) + 64));
+      GCHK(ghip_ensure(ctx, ctx->wind_work, (WIND_NPLANES * Dn + 2 * (Dn + 1)) * 8 + 256));
+      GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
+      const WindDev d = wind_dev(ctx, (int) Dn);
+      HIPCHK(hipMemsetAsync(d.words, 0, sizeof(WindWords), st));
+      if(nw > 0)
+        {
+          HIPCHK(hipMemcpyAsync(d.idx, W.a.wind_idx, Dn * 4, hipMemcpyHostToDevice, st));
+          unsigned int *dkey = reinterpret_cast<unsigned int *>(d.idx + 2 * Dn), *dkey2 = dkey + Dn;
+          int *dslot = d.idx + 4 * Dn;
+          k_wind_order_keys<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->gt.iperm), dkey, dslot);
+          HIPCHK(hipGetLastError());
+          const long long nsorted = ctx->gt.n > n ? ctx->gt.n : n;
+          int end_bit = 1;
+          while(end_bit < 32 && (1LL << end_bit) <= nsorted)
+            end_bit++;
+          GCHK(ghip_sort_pairs(ctx, dkey, dkey2, dslot, d.ord, nw, end_bit, st));
+          k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, n, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
+                                                    d.w, d.words);
+          k_wind_slots<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(D.du_slot));
+          HIPCHK(hipGetLastError());
+        }
+      if(ctx->ngas > 0)
+        k_wind_hmax<<<cdiv(ctx->ngas, 256), 256, 0, st>>>(ctx->ngas, P<double>(ctx->f[GHIP_F_HSML]),
+                                                          P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), d.words);
+      HIPCHK(hipGetLastError());
+      if(nw > 0 && W.form == GHIP_WIND_FORM)
+        {
+          const ghip_wind_state *s = W.a.state;
+          std::vector<double> h(WIND_NIN * Dn);
+          memcpy(h.data() + WP_AGE * Dn, s->stellar_age, Dn * 8);
+          memcpy(h.data() + WP_BIRTH * Dn, s->birth_energy, Dn * 8);
+          memcpy(h.data() + WP_OLD * Dn, s->old_momentum, Dn * 8);
+          memcpy(h.data() + WP_RHO * Dn, s->new_density, Dn * 8);
+          memcpy(h.data() + WP_DRMIN * Dn, s->drmin, Dn * 8);
+          HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+          HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
+          k_wind_init<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->f[GHIP_F_TIMEBIN]), d.w, d.deleted, W.p.dt_fac);
+          k_wind_sum<<<1, 1024, 0, st>>>(nw, d.w + WP_DTJ * Dn, &d.words->dt_total);
+          k_wind_flags<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.ord, d.w + WP_DTJ * Dn, d.flags, d.words);
+          HIPCHK(hipGetLastError());
+          GCHK(ghip_select_flagged(ctx, d.ord, d.flags, d.lista, &d.words->npos, nw, st));
+        }
+      else if(nw > 0)
+        {
+          HIPCHK(hipMemcpyAsync(d.w + WP_DTJ * Dn, W.a.dt_jump, Dn * 8, hipMemcpyHostToDevice, st));
+          if(W.form == GHIP_WIND_SPREAD_FORM)
+            {
+              HIPCHK(hipMemcpyAsync(d.w + WP_RHO * Dn, W.a.new_density, Dn * 8, hipMemcpyHostToDevice, st));
+              HIPCHK(hipMemcpyAsync(d.w + WP_DMOM * Dn, W.a.delta_momentum, Dn * 8, hipMemcpyHostToDevice, st));
+            }
+        }
+      WindWords h;
+      HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      // what this shard met travels with the group tables: every shard stops in the next step (ghip_dd_hold's path)
+      int own_rc = GHIP_OK;
+      if(h.err)
+        own_rc = wind_type_error(ctx, who);
+      else if(W.form == GHIP_WIND_FORM && (h.npos < 0 || h.npos > nw))
+        own_rc = ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, h.npos, nw);
+      W.m = W.form == GHIP_WIND_FORM ? h.npos : nw;
+      W.under = h.nunder;
+      W.cur = 0;
+      const double extra[3] = {__builtin_bit_cast(double, h.hmax), h.dt_total, (double) nw};
+      D.phase = WDD_START;
+      W.exchanges++;
+      return ghip_dd_wind_groups(ctx, extra, own_rc);
+    }
+  const WindDev d = wind_dev(ctx, (int) Dn);
+  if(D.phase == WDD_START)
+    {
+      double extra[3 * GHIP_MAXRANKS];
+      GCHK(ghip_dd_wind_status(ctx, who, extra));
+      double hmax = 0, dt_total = 0;
+      for(int r = 0; r < D.nranks; r++)   // (the sum in ascending rank order: the same bits on every shard)
+        {
+          if(extra[3 * r] > hmax)
+            hmax = extra[3 * r];
+          dt_total += extra[3 * r + 1];
+        }
+      W.hmax_all = hmax;
+      if(W.form == GHIP_WIND_FORM)
+        {
+          if(dt_total <= W.p.dt_total_floor)   // :302: the loop is not entered, nothing changes on any shard
+            {
+              if(nw > 0)
+                GCHK(wind_download_state(ctx, d, W.a.state, false));
+              wind_dd_counts(D);
+              return 0;
+            }
+          GCHK(wind_injected(ctx, who));
+          if(W.p.rad_accel)
+            GCHK(wind_rad_accel(ctx, who));
+          ctx->pot_n = -1;   // (positions and masses change)
+        }
+      else if(W.form == GHIP_WIND_SPREAD_FORM)
+        {
+          GCHK(wind_injected(ctx, who));
+          return wind_dd_density_send(ctx, WDD_SPREAD_POS);
+        }
+      if(nw > 0)
+        {
+          k_wind_reset<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.w);
+          HIPCHK(hipGetLastError());
+        }
+      return wind_dd_density_send(ctx, WDD_DENS_IMP);
+    }
+  if(D.phase == WDD_DENS_IMP)
+    {
+      // the imported particles against this shard's gas; the partials go home over the receive layout
+      const int nimp = D.x.rtotal;
+      W.nimp = nimp;
+      W.recvd += nimp;
+      GCHK(ghip_ensure(ctx, D.du_part, (size_t) (nimp > 0 ? nimp : 1) * 16));
+      GCHK(wind_dd_mark(ctx, 4));
+      if(nimp > 0)
+        {
+          k_wind_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, WindTgt{nullptr, nullptr, P<double>(D.du_recv), nullptr},
+                                                        P<double>(D.du_part), WIND_GAS_ARGS, b, d.nw, d.w, nullptr, d.words);
+          HIPCHK(hipGetLastError());
+        }
+      int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];
+      for(int r = 0; r < D.nranks; r++)
+        {
+          sc[r] = D.x.rcount[r];
+          so[r] = D.x.roff[r];
+        }
+      GCHK(wind_dd_mark(ctx, 5));
+      ghip_dd_set_alltoallv(D, D.du_part.p, 16, sc, so, &D.du_back);
+      W.exchanges++;
+      D.phase = WDD_DENS_ADD;
+      return 1;
+    }
+  if(D.phase == WDD_DENS_ADD)
+    {
+      for(int r = 0; r < D.nranks; r++)
+        if(D.x.rcount[r] != (r == D.rank ? 0 : D.du_scount[r]))
+          return ghip_fail(ctx, GHIP_ECOMM, "%s: %d partial sums came back from rank %d, %d particles went there", who,
+                           D.x.rcount[r], r, D.du_scount[r]);
+      for(int r = 0; r < D.nranks; r++)   // own sum first, then the ranks in ascending order (virtual_density.c:344)
+        if(r != D.rank && D.du_scount[r] > 0)
+          k_wind_add_parts<<<cdiv(D.du_scount[r], 256), 256, 0, st>>>(D.du_scount[r], P<int>(D.du_list) + D.du_soff[r],
+                                                                      P<int>(D.du_slot),
+                                                                      P<double>(D.du_back) + 2 * (size_t) D.x.roff[r], d.nw, d.w);
+      HIPCHK(hipGetLastError());
+      if(W.form == GHIP_WIND_DENSITY_FORM)
+        {
+          if(nw > 0)
+            {
+              // (WP_RHO and WP_DRMIN are neighbours)
+              std::vector<double> o(2 * Dn);
+              HIPCHK(hipMemcpyAsync(o.data(), d.w + WP_RHO * Dn, 2 * Dn * 8, hipMemcpyDeviceToHost, st));
+              HIPCHK(ghip_stream_sync(ctx, st));
+              memcpy(W.a.new_density, o.data(), Dn * 8);
+              memcpy(W.a.drmin, o.data() + Dn, Dn * 8);
+            }
+          HIPCHK(ghip_stream_sync(ctx, st));
+          wind_dd_counts(D);
+          return 0;
+        }
+      if(W.iter == 0)   // that was the density at the start
+        return wind_dd_iterate(ctx);
+      // the new list, and what every shard needs to know of it
+      const int m = W.m;
+      if(ctx->wind_ev[5])   // (the exchange of the partials lies behind them)
+        HIPCHK(hipEventSynchronize(ctx->wind_ev[5]));
+      wind_dd_add_ms(ctx, WT_IMP, 4);
+      GCHK(wind_dd_mark(ctx, 6));
+      HIPCHK(hipMemsetAsync(d.words, 0, 16, st));   // npairs, npos, nunder
+      if(m > 0)
+        {
+          k_wind_flags<<<cdiv(m, 256), 256, 0, st>>>(m, wind_dd_list(d, W), d.w + WP_DTJ * Dn, d.flags, d.words);
+          HIPCHK(hipGetLastError());
+          GCHK(ghip_select_flagged(ctx, wind_dd_list(d, W), d.flags, wind_dd_list(d, W, true), &d.words->npos, m, st));
+        }
+      GCHK(wind_dd_mark(ctx, 7));
+      WindWords h;
+      HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      wind_dd_add_ms(ctx, WT_LIST, 6);
+      bool failed = false;
+      if(h.npos < 0 || h.npos > m)
+        failed = ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, h.npos, m));
+      else
+        ghip_dd_hold(ctx, GHIP_OK);
+      W.m_next = failed ? 0 : h.npos;
+      W.under_next = failed ? 0 : h.nunder;
+      const double mine[4] = {(double) W.m_next, (double) W.under_next, failed ? 1.0 : 0.0, 0.0};
+      GCHK(ghip_ensure(ctx, D.status_own, 32));
+      HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 32, hipMemcpyHostToDevice, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // (`mine` lives on this frame)
+      ghip_dd_set_allgather(D, D.status_own.p, 32, &D.status_all);
+      W.exchanges++;
+      D.phase = WDD_STATUS;
+      return 1;
+    }
+  if(D.phase == WDD_STATUS)
+    {
+      double all[4 * GHIP_MAXRANKS];
+      HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) D.nranks * 32, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      int first_failed = -1;
+      W.under_all = 0;
+      for(int r = 0; r < D.nranks; r++)
+        {
+          if(all[4 * r + 2] != 0 && first_failed < 0)
+            first_failed = r;
+          W.under_all += (long long) all[4 * r + 1];
+        }
+      GCHK(ghip_dd_raise(ctx, first_failed, "%s: shard %d reported an error in iteration %d (its own message says what); "
+                         "every shard stops here", who, first_failed, W.iter));
+    }
+  if(D.phase == WDD_STATUS || D.phase == WDD_SPREAD_POS)
+    {
+      if(D.phase == WDD_SPREAD_POS)
+        {
+          W.nimp = D.x.rtotal;
+          W.recvd += W.nimp;
+        }
+      // the spread records of the particles that went out, to the same shards in the same order
+      const int total = D.du_sent;
+      GCHK(ghip_ensure(ctx, D.wd_spread, (size_t) (total > 0 ? total : 1) * WIND_REC_SPREAD * 8));
+      if(total > 0)
+        {
+          k_wind_pack<WIND_REC_SPREAD><<<cdiv(total, 256), 256, 0, st>>>(
+            total, P<int>(D.du_list), P<int>(D.du_slot), n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
+            d.nw, d.w, P<double>(D.wd_spread));
+          HIPCHK(hipGetLastError());
+        }
+      ghip_dd_set_alltoallv(D, D.wd_spread.p, (size_t) WIND_REC_SPREAD * 8, D.du_scount, D.du_soff, &D.wd_srecv);
+      W.exchanges++;
+      D.phase = WDD_SPREAD;
+      return 1;
+    }
+  if(D.phase == WDD_SPREAD)
+    {
+      const int nimp = W.nimp, m = W.m;
+      if(D.x.rtotal != nimp)
+        return ghip_fail(ctx, GHIP_ECOMM, "%s: %d spread records came for %d imported particles", who, D.x.rtotal, nimp);
+      // this shard's particles in list order (slots [0, nw)), then the imported ones in receive order (nw + t)
+      const size_t M = (size_t) m + (size_t) nimp;
+      GCHK(ghip_ensure(ctx, D.wd_cnt, 2 * (M + 1) * 8));
+      unsigned long long *cnt = P<unsigned long long>(D.wd_cnt), *off = cnt + M + 1;
+      const WindTgt own = {wind_dd_list(d, W), d.idx, nullptr, nullptr};
+      const WindTgt imp = {nullptr, nullptr, P<double>(D.du_recv), P<double>(D.wd_srecv)};
+      GCHK(wind_dd_mark(ctx, 4));
+      HIPCHK(hipMemsetAsync(cnt, 0, (M + 1) * 8, st));
+      if(m > 0)
+        k_wind_pairs<0><<<cdiv(m, 64), 64, 0, st>>>(m, own, WIND_GAS_ARGS, b, d.nw, d.w, cnt, nullptr, 0ULL, nullptr, nullptr,
+                                                    d.words);
+      if(nimp > 0)
+        k_wind_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, imp, WIND_GAS_ARGS, b, d.nw, d.w, cnt + m, nullptr, 0ULL, nullptr,
+                                                       nullptr, d.words);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_scan(ctx, (const unsigned long long *) cnt, off, (int) M + 1, st));
+      unsigned long long tot[2];
+      HIPCHK(hipMemcpyAsync(&tot[0], off + m, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&tot[1], off + M, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // (the pair count sizes the sort)
+      W.imp_pairs += (long long) (tot[1] - tot[0]);
+      GCHK(wind_scatter(ctx, d, b, m, own.list, (long long) tot[1], off, nimp, &imp));
+      GCHK(wind_dd_mark(ctx, 5));
+      HIPCHK(hipEventSynchronize(ctx->wind_ev[5]));
+      wind_dd_add_ms(ctx, WT_SPREAD, 4);
+      if(W.form == GHIP_WIND_SPREAD_FORM)
+        {
+          HIPCHK(ghip_stream_sync(ctx, st));
+          wind_dd_counts(D);
+          return 0;
+        }
+      W.cur ^= 1;
+      W.m = W.m_next;
+      W.under = W.under_next;
+      if(W.under_all == 0)
+        return wind_dd_finish(ctx, false);
+      if(W.iter >= W.p.max_iter)   // (the global count: all shards stop together)
+        return wind_dd_finish(ctx, true);
+      return wind_dd_iterate(ctx);
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the wind operation has no phase %d", D.phase);
 }

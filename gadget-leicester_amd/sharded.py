@@ -196,6 +196,11 @@ def find_guests(keys, holder, splits=None, segments=None):
     return guests, host[guests].astype(_np.int32)
 
 
+def _empty_wind_state():
+    z = _np.zeros(0)
+    return dict(stellar_age=z, birth_energy=z, old_momentum=z, new_density=z, drmin=z)
+
+
 def _fof_result(path, keep):
     out = path.fof_adopt(keep)
     out.counts = keep["counts"]
@@ -306,6 +311,32 @@ class DomainShards:
         built = [self.B.dd_fof_args(**params) for _ in self.paths]
         self.run(self.B.DD_GLOBAL_QUANTITIES, [b[0] for b in built], self.B.FOF_FORM)
         return [_fof_result(p, b[1]) for p, b in zip(self.paths, built)]
+
+    def wind_feedback(self, params, wind, state):
+        """GHIP_DD_WIND in its WIND_FORM, the whole loop (momentum_feedback.c:283-568): wind[r] are shard r's local indices in list
+        order, state[r] its dict(stellar_age, birth_energy, old_momentum, new_density, drmin) or None where the
+        shard has no wind.  params.dt_total_floor is the GLOBAL floor.  Returns one dict per shard as
+        ForcePath.wind_feedback does: iterations is the global count, bits / ndeleted / deleted_momentum are the
+        shard's own (add them in rank order); counts: int64[6] (bindings.WIND_COUNTS).  Afterwards wind particles
+        may lie outside their shard's key ranges: redistribute(), or accept_guests()."""
+        built = [self.B.dd_wind_args(params, wind[r], state=state[r] if len(wind[r]) else _empty_wind_state())
+                 for r in range(len(self.paths))]
+        self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WIND_FORM)
+        return [self.B.dd_wind_result(b[1]) for b in built]
+
+    def wind_density(self, params, wind, dt_jump):
+        """GHIP_DD_WIND in its WIND_DENSITY_FORM: one virtual_density() -> [(new_density, drmin, counts)] per shard"""
+        built = [self.B.dd_wind_args(params, wind[r], dt_jump=dt_jump[r]) for r in range(len(self.paths))]
+        self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WIND_DENSITY_FORM)
+        return [(b[1]["new_density"], b[1]["drmin"], b[1]["counts"].copy()) for b in built]
+
+    def wind_spread(self, params, wind, dt_jump, new_density, delta_momentum):
+        """GHIP_DD_WIND in its WIND_SPREAD_FORM: one virtual_spread_momentum() into every shard's resident
+        Injected_BH_Momentum -> [counts] per shard"""
+        built = [self.B.dd_wind_args(params, wind[r], dt_jump=dt_jump[r], new_density=new_density[r],
+                                     delta_momentum=delta_momentum[r]) for r in range(len(self.paths))]
+        self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WIND_SPREAD_FORM)
+        return [b[1]["counts"].copy() for b in built]
 
 
 class DomainRank:
@@ -442,3 +473,25 @@ class DomainRank:
         args, keep = self.B.dd_fof_args(**params)
         self._run(self.B.DD_GLOBAL_QUANTITIES, args, self.B.FOF_FORM)
         return _fof_result(self.p, keep)
+
+    def wind_feedback(self, params, wind, state=None):
+        """GHIP_DD_WIND in its WIND_FORM, a collective: the whole loop of momentum_feedback.c:283-568 for this rank's wind particles
+        (local indices in list order; state: dict(stellar_age, birth_energy, old_momentum, new_density, drmin)).
+        params.dt_total_floor is the GLOBAL floor.  Returns a dict as ForcePath.wind_feedback does: iterations is
+        the global count, bits / ndeleted / deleted_momentum are this rank's own; counts: bindings.WIND_COUNTS"""
+        args, keep = self.B.dd_wind_args(params, wind, state=state if len(wind) else _empty_wind_state())
+        self._run(self.B.WIND_OP, args, self.B.WIND_FORM)
+        return self.B.dd_wind_result(keep)
+
+    def wind_density(self, params, wind, dt_jump):
+        """GHIP_DD_WIND in its WIND_DENSITY_FORM, a collective -> (new_density, drmin, counts) of this rank's list"""
+        args, keep = self.B.dd_wind_args(params, wind, dt_jump=dt_jump)
+        self._run(self.B.WIND_OP, args, self.B.WIND_DENSITY_FORM)
+        return keep["new_density"], keep["drmin"], keep["counts"].copy()
+
+    def wind_spread(self, params, wind, dt_jump, new_density, delta_momentum):
+        """GHIP_DD_WIND in its WIND_SPREAD_FORM, a collective, into this rank's Injected_BH_Momentum -> counts"""
+        args, keep = self.B.dd_wind_args(params, wind, dt_jump=dt_jump, new_density=new_density,
+                                         delta_momentum=delta_momentum)
+        self._run(self.B.WIND_OP, args, self.B.WIND_SPREAD_FORM)
+        return keep["counts"].copy()

@@ -925,9 +925,10 @@ int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_d
  * list order.  Resident fields read: TYPE, TIMEBIN, VEL, and of the gas POS, HSML, MASS; written at the wind
  * indices by ghip_wind_feedback: POS, HSML, MASS.  Needs the trees of this step (GHIP_EINVAL "call
  * ghip_tree_build first" otherwise); the gas tree stays valid, the gas does not move.  The gravity tree keeps
- * the wind particles where they were when it was built, as the reference's does.  Single-rank: on a sharded
- * or multi-GPU context every entry point below returns GHIP_EINVAL.  An index that does not name a Type-3
- * particle is GHIP_EINVAL. ---- */
+ * the wind particles where they were when it was built, as the reference's does.  ghip_wind_density,
+ * ghip_wind_spread and ghip_wind_feedback are single-rank: on a ghip_dd_init context they return GHIP_EINVAL and
+ * name GHIP_DD_WIND, the operation that runs them on shards (below); on a ghip_set_shard context every entry
+ * point below returns GHIP_EINVAL.  An index that does not name a Type-3 particle is GHIP_EINVAL. ---- */
 typedef struct
 {
   int periodic;
@@ -939,7 +940,8 @@ typedef struct
   double VirtualCrosSection, VirtualMass, VirtualTime, OuterBoundary;
   double DesNumNgb, OriginalGasMass, SofteningGas, SofteningGasMaxPhys, SofteningBulgeMaxPhys;
   double PhotonSearchRadius;
-  double dt_total_floor;   /* 1e-15 * All.VirtualTime * (All.MaxPart * NTask), :302 */
+  double dt_total_floor;   /* 1e-15 * All.VirtualTime * (All.MaxPart * NTask), :302.  GHIP_DD_WIND: the GLOBAL floor,
+                            * with NTask in it, the same on every shard: it is compared with the sum over all shards */
   int fly_through_empty_space;   /* VIRTUAL_FLY_THORUGH_EMPTY_SPACE: the drmin step limit of :337-340 */
   int variable_search_radius;    /* VARIABLE_PHOTON_SEARCH_RADIUS: the Hsml cap of :409-410 */
   int rad_accel;                 /* RAD_ACCEL: :497-538 at the end of ghip_wind_feedback */
@@ -999,7 +1001,8 @@ int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, cons
                        const ghip_wind_state *state, ghip_wind_result *result);
 /* the resident gas fields SphP[].i.Injected_BH_Momentum [ngas][3] and SphP[].ra.RadAccel [ngas][3], zero when
  * first used; NULL = skip.  Values held for one ngas are refused after ghip_set_counts changes it (set them
- * again), as ghip_kick_set_fields does. */
+ * again), as ghip_kick_set_fields does.  On a ghip_dd_init context they are the fields of the shard's own gas
+ * and travel with their particle in GHIP_DD_MIGRATE (a field held for another gas count is not carried). */
 int ghip_wind_get_injected(ghip_ctx *ctx, double *injected);
 int ghip_wind_set_injected(ghip_ctx *ctx, const double *injected);
 int ghip_wind_get_rad_accel(ghip_ctx *ctx, double *rad_accel);
@@ -1009,10 +1012,12 @@ int ghip_wind_set_rad_accel(ghip_ctx *ctx, const double *rad_accel);
  * line above it, as the C text does; the PMGRID term of :512 still follows); ghip_pm_kick sets VelPred = Vel +
  * RadAccel dt_hydrokick (:337-339); ghip_drift adds RadAccel dt_hydrokick to VelPred (predict.c:190-192).
  * Kernel instantiations of their own: with the switch off (the default) the existing kernels run and a
- * resident RadAccel is not read.  Single-rank contexts only. */
+ * resident RadAccel is not read.  Per-particle arithmetic: a ghip_dd_init shard reads its own RadAccel; not on
+ * a ghip_set_shard context. */
 int ghip_set_rad_accel(ghip_ctx *ctx, int on);
 /* milliseconds of the last ghip_wind_feedback from events around its phases, summed over the iterations:
- * move, density, spread, list, and the whole call; synchronises */
+ * move, density, spread, list, and the whole call; synchronises.  After GHIP_DD_WIND: this shard's move, own
+ * density, spread, list, and in ms[4] the density of the imported particles */
 int ghip_wind_get_timing(ghip_ctx *ctx, double ms[5]);
 
 /* The dust passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG through ghip_dd_begin /
@@ -1174,6 +1179,66 @@ typedef struct
  * scattered into the zeroed padded mesh and solved on every shard, which reads out its own particles.  A
  * particle outside the region on ANY shard makes EVERY shard return GHIP_EREGION, nothing written anywhere. */
 #define GHIP_DD_PM_NONPERIODIC 15
+/* The wind particles on multi-GPU shards (GHIP_DD_WIND begun with one of the three wind forms as `walk`, through
+ * ghip_dd_begin / ghip_dd_run): the loop of
+ * momentum_feedback() under NTask > 1 (momentum_feedback.c:301, 469-470 all-reduce dt_total and N_active;
+ * virtual_density.c:236-361 and virtual_spread_momentum.c export a particle to the tasks its sphere touches).
+ * No operation code is added: the codes stay 1..15 and 16 stays unknown to ghip_dd_begin, as the friends-of-friends
+ * groups and the sync point took a form of an existing operation.  GHIP_DD_WIND is the operation whose requirements
+ * the wind shares, GHIP_DD_DUST_DRAG, and `walk` selects the form (its traffic counter serves whichever form ran
+ * last):
+ *   GHIP_WIND_FORM           the whole loop (:283-568), as ghip_wind_feedback
+ *   GHIP_WIND_DENSITY_FORM   one virtual_density():         in dt_jump, out new_density, drmin
+ *   GHIP_WIND_SPREAD_FORM    one virtual_spread_momentum(): in dt_jump, new_density, delta_momentum
+ * (GHIP_WIND_FORM + 0, 1, 2; walk = 0 and GHIP_DUST_GRAINS_FORM stay the dust drag's, any other walk is GHIP_EINVAL).
+ * Needs GHIP_DD_GRAVITY and GHIP_DD_DENSITY of this step: the list is ordered by
+ * the gravity tree and the walks run on the shard's gas tree.  Arrays describe the wind particles resident on
+ * THIS shard; a wind particle stays resident on its home shard for the whole call, wherever it flies, and the gas
+ * neither moves nor changes mass.  Every shard takes every exchange, with or without wind or gas of its own.
+ *   begin     one all-gather: the group boxes of the shard's Type-0 particles with Mass > 0, its largest h_j,
+ *             its dt_jump sum and its list length.  The dt_jump sums are added in ascending rank order and
+ *             compared with p->dt_total_floor, the GLOBAL floor: at or below it every shard returns having
+ *             changed nothing.
+ *   per iteration, four exchanges:
+ *     1. the move of the own list and the own density partial over the shard's own gas; then {Pos, Hsml} of the
+ *        listed particles with dt_jump > 0 go to every other shard whose gas boxes their sphere can reach (the
+ *        radius is cut to what can still change new_density or drmin once the own pass found a candidate);
+ *     2. every shard evaluates what it imported against its own gas; {new_density, drmin} partials go home,
+ *        where new_density = own + partials in ascending rank order (virtual_density.c:344) and drmin = the
+ *        minimum of all;
+ *     3. the new list (dt_jump > 0); {list length, particles above 1e-40, failure} of every shard are
+ *        all-gathered: the loop ends when no shard has a particle above 1e-40 (:470-472), and max_iter counts
+ *        the global iterations, so all shards stop together (GHIP_ENOCONV);
+ *     4. {new_density, DeltaPhotonMomentum, Vel, |Vel|} of the exported particles go to the same shards, and
+ *        every shard scatters into its own Injected_BH_Momentum: a gas particle takes this shard's wind
+ *        particles in list order, then the imported ones by sending rank ascending and within a rank by the
+ *        sender's local particle index ascending (the dust drag's rule).  No floating-point atomics.
+ *   end       RAD_ACCEL for the shard's active gas (ghip_set_active) and the elimination, locally.
+ * result->iterations is the global count; bits, ndeleted and deleted_momentum are THIS shard's: the host adds
+ * them in rank order where the reference all-reduces (:572-573).  A failure on one shard (an index that is not
+ * Type 3, a list length that makes no sense) ends the operation on all shards in the same step.  Afterwards a
+ * wind particle may lie outside its shard's key ranges or outside the domain cube: the operation reads no keys
+ * and does not mind; the host runs GHIP_DD_DECOMPOSE / GHIP_DD_MIGRATE next, or accepts guests
+ * (ghip_dd_set_guests). */
+typedef struct
+{
+  const ghip_wind_params *p;
+  int nwind;                       /* wind particles resident on this shard */
+  const int *wind_idx;             /* their local particle indices, in active-list order */
+  const ghip_wind_state *state;    /* WIND_FORM: as ghip_wind_feedback takes it */
+  const double *dt_jump;           /* the single passes, in [nwind] */
+  double *new_density;             /* DENSITY_FORM out, SPREAD_FORM in [nwind] */
+  double *drmin;                   /* DENSITY_FORM out [nwind] */
+  const double *delta_momentum;    /* SPREAD_FORM in [nwind] */
+  ghip_wind_result *result;        /* WIND_FORM */
+  long long *counts;               /* out [6] (may be NULL): records this shard sent, records it received, pairs it
+                                      scattered for imported particles, exchanges run, bytes sent, iterations */
+} ghip_dd_wind_args;
+size_t ghip_dd_wind_args_size(void);
+#define GHIP_DD_WIND GHIP_DD_DUST_DRAG   /* with one of the following as `walk` */
+#define GHIP_WIND_FORM 16           /* `walk` of ghip_dd_begin / ghip_dd_run for GHIP_DD_WIND: the whole loop */
+#define GHIP_WIND_DENSITY_FORM 17
+#define GHIP_WIND_SPREAD_FORM 18
 /* ghip_find_next_sync_point on shards: GHIP_DD_DECOMPOSE begun with walk = GHIP_SYNC_POINT_FORM and params a
  * ghip_sync_params (the result: ghip_dd_get_sync_point) -- the two things run() does between two steps share one
  * operation, as the two forms of the dust operations do; no operation code is added.  Every
