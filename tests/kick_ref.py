@@ -61,9 +61,17 @@ def _factors(p):
     return dict(fac1=1.0, fac2=1.0, fac3=1.0, hubble_a=1.0, a3inv=1.0, atime=1.0)
 
 
-def get_timestep(i, p, f, s, F):
+CRITERIA = ("accel", "dust-dt", "adaptive", "courant", "virtual", "accretion", "max", "disp")
+BIN_MOVES = ("down", "same", "up", "up-blocked", "end")
+KICK_LABELS = CRITERIA + BIN_MOVES + ("binold0", "entropy-add", "entropy-halve", "minegy-floor",
+                                      "dtentropy-limited")
+
+
+def get_timestep(i, p, f, s, F, why=None):
     """get_timestep(i, &aphys, 0): the physical step before its integer mapping, or an endrun code
-    (888 / 818) as a negative int.  s: the particle state (arrays), F: _factors(p)."""
+    (888 / 818) as a negative int.  s: the particle state (arrays), F: _factors(p).  why: a list that
+    receives the criterion (CRITERIA) whose value dt ends with -- the last assignment that held."""
+    w = ["accel"]
     ty = int(s["type"][i])
     ngas = len(s["entropy"])
     gas = ty == 0 and i < ngas
@@ -95,11 +103,13 @@ def get_timestep(i, p, f, s, F):
             dt_new = math.sqrt(2 * p["ErrTolIntAccuracy"] * F["atime"] * soft / ac)
             if dt_new < dt:
                 dt = dt_new
+                w[0] = "dust-dt"
     if f["dust"] and ty == 2:                                           # timestep.c:725-726
         dt = dt / 2
     if p["AdaptiveGravsoftForGasHsml"] and ty == 0:                     # timestep.c:740-743: overwrites
         dt = math.sqrt(2 * p["ErrTolIntAccuracy"] * F["atime"] * s["hsml"][i] / 2.8 / ac) \
             if ac != 0 else math.inf
+        w[0] = "adaptive"
     if gas:                                                             # timestep.c:768-772
         if p["ComovingIntegrationOn"]:
             dtc = 2 * p["CourantFac"] * p["Time"] * s["hsml"][i] / (F["fac3"] * s["vsig"][i])
@@ -107,6 +117,7 @@ def get_timestep(i, p, f, s, F):
             dtc = 2 * p["CourantFac"] * s["hsml"][i] / s["vsig"][i]
         if dtc < dt:
             dt = dtc
+            w[0] = "courant"
     if f["virtual_particles"] and ty == 3:                              # timestep.c:887-897
         dt_abs = 0.03 * f["OuterBoundary"] / C_LIGHT * f["UnitVelocity_in_cm_per_s"] * f["FeedBackVelocity"]
         dt_ff = 1.0             # (NewDensity > 0: the reference divides by an uninitialised rho)
@@ -114,6 +125,7 @@ def get_timestep(i, p, f, s, F):
             dt_abs = dt_ff
         if dt > dt_abs:
             dt = dt_abs
+            w[0] = "virtual"
     if f["black_holes"] and ty == 5:                                    # timestep.c:908-947
         dt_accr = 0.03 * (f["OuterBoundary"] / 100.)
         if f["accretion_radius"]:
@@ -127,11 +139,16 @@ def get_timestep(i, p, f, s, F):
                 dt_accr = dt_a
         if dt_accr < dt:
             dt = dt_accr
+            w[0] = "accretion"
     dt *= F["hubble_a"]                                                 # timestep.c:1044-1058
     if dt >= p["MaxSizeTimestep"]:
         dt = p["MaxSizeTimestep"]
+        w[0] = "max"
     if dt >= p["dt_displacement"]:
         dt = p["dt_displacement"]
+        w[0] = "disp"
+    if why is not None:
+        why.append(w[0])
     if dt < p["MinSizeTimestep"]:
         return -888
     ti_step = int(dt / p["Timebase_interval"])
@@ -153,11 +170,15 @@ def state(type, mass, vel, grav, hyd, velpred, entropy, dtentropy, density, hsml
                 ddm=np.zeros((ngas, 3)) if ddm is None else f(ddm, (ngas, 3)))
 
 
-def advance_timesteps(p, f, s, active=None, tables=None):
+def advance_timesteps(p, f, s, active=None, tables=None, trace=None):
     """the loop of timestep.c:142-260 on the state s (modified in place).  p: the kick parameters
     (names of ghip_kick_params, SofteningTable a sequence, TimeBinActive a bit mask), f: flags(),
     tables: (gravkick, hydrokick) when comoving.  Returns dict(rc, kick_dv [n][3], kick_flag [n],
-    binold [n]) -- rc 0 or the endrun code of the first failing particle in list order."""
+    binold [n]) -- rc 0 or the endrun code of the first failing particle in list order.
+    trace: a dict that receives, per particle of the list that passed the checks, the set of labels
+    (KICK_LABELS) of what the loop did with it: the criterion that set dt, the bin move ("end": the
+    Ti_Current >= TIMEBASE block), "binold0", and for gas which way Entropy went (:553-557), the
+    MinEgySpec floor (:574-583) and the DtEntropy limiter (:590-593)."""
     n, ngas = len(s["type"]), len(s["entropy"])
     F = _factors(p)
     kick_dv = np.zeros((n, 3))
@@ -168,7 +189,8 @@ def advance_timesteps(p, f, s, active=None, tables=None):
         i = int(i)
         ty = int(s["type"][i])
         gas = ty == 0 and i < ngas
-        ti_step = get_timestep(i, p, f, s, F)
+        why = []
+        ti_step = get_timestep(i, p, f, s, F, why)
         if ti_step < 0:
             rc = rc or -ti_step
             continue
@@ -181,14 +203,22 @@ def advance_timesteps(p, f, s, active=None, tables=None):
             continue
         bin = ti_step.bit_length() - 1 if ti_step else 0
         binold = int(s["timebin"][i])
+        move = "down" if bin < binold else "same" if bin == binold else "up"
         if bin > binold and not (p["TimeBinActive"] >> bin) & 1:
             bin = binold
             ti_step = (1 << bin) if bin else 0
+            move = "up-blocked"
         if p["Ti_Current"] >= TIMEBASE:
             ti_step = bin = 0
+            move = "end"
         if TIMEBASE - p["Ti_Current"] < ti_step:
             rc = rc or 888
             continue
+        lab = {why[0], move}
+        if binold == 0:
+            lab.add("binold0")
+        if trace is not None:
+            trace[i] = lab
         s["timebin"][i] = bin
         ti_step_old = (1 << binold) if binold else 0
         tb0 = int(s["ti_begstep"][i])
@@ -226,16 +256,20 @@ def advance_timesteps(p, f, s, active=None, tables=None):
             A, dA = float(s["entropy"][i]), float(s["dtentropy"][i])
             if dA * dt_entr > -0.5 * A:                                 # timestep.c:553-557
                 A += dA * dt_entr
+                lab.add("entropy-add")
             else:
                 A *= 0.5
+                lab.add("entropy-halve")
             if p["MinEgySpec"]:                                         # timestep.c:574-583
                 minentropy = p["MinEgySpec"] * GAMMA_MINUS1 / math.pow(s["density"][i] * F["a3inv"],
                                                                        GAMMA_MINUS1)
                 if A < minentropy:
                     A, dA = minentropy, 0.0
+                    lab.add("minegy-floor")
             dt_entr = ((1 << bin) if bin else 0) // 2 * p["Timebase_interval"]   # timestep.c:590-593
             if A + dA * dt_entr < 0.5 * A:
                 dA = -0.5 * A / dt_entr
+                lab.add("dtentropy-limited")
             s["entropy"][i], s["dtentropy"][i] = A, dA
         kick_dv[i] = dv                                                 # force_kick_node(i, dv)
         kick_flag[i] = 1
@@ -281,7 +315,22 @@ def drift(p, f, s, time1, tables=None):
             dt_entr = (time1 - (int(s["ti_begstep"][i]) + dt_step // 2)) * p["Timebase_interval"]
             s["pressure"][i] = (s["entropy"][i] + s["dtentropy"][i] * dt_entr) * math.pow(s["density"][i], GAMMA)
         s["ti_current"][i] = time1
+    if p.get("box_wrap"):
+        box_wrap(s["pos"], p["BoxSize"])
     return 0
+
+
+def box_wrap(pos, boxsize):
+    """do_box_wrapping (predict.c:282-310) for every particle, in place: the two loops of :299-307.  They end
+    only for finite coordinates of a moderate number of boxes."""
+    for i in range(len(pos)):
+        for j in range(3):
+            x = float(pos[i, j])
+            while x < 0:
+                x += boxsize
+            while x >= boxsize:
+                x -= boxsize
+            pos[i, j] = x
 
 
 def bin_sums(order, ptype, binold, binnew, sfr=None, dust_mass=None, total_mass=None, mass=None,

@@ -1622,6 +1622,27 @@ def test_timestep_failure_reports_the_reference_endrun_code():
     with pytest.raises(B.GhipError) as ei:
         fp.advance_timesteps(_fill(B.KickParams(), par, pr.force_soft / 2.8))
     assert ei.value.endrun == 818
+    # one offending particle among valid ones (tests/kick_edges.py), one code per call: the device reports the
+    # largest code of a call, the reference the first in list order.  888 (dt < MinSizeTimestep), 818, 112313
+    # (a step of one tick) and 888 (TIMEBASE - Ti_Current < ti_step); without that particle the call succeeds.
+    # Nothing is claimed about the state after a refusal.
+    import kick_edges as E
+    import kick_ref as R
+    from test_gpu_kick_bundle import device, kick_params
+    codes = []
+    for name, code, p, s, i in E.endrun_cases():
+        assert R.advance_timesteps(p, R.flags(), E.copy_state(s))["rc"] == code, name
+        fp2 = device(s, fields=False)
+        with pytest.raises(B.GhipError) as ei:
+            fp2.advance_timesteps(kick_params(p))
+        assert ei.value.endrun == code, name
+        fp2.close()
+        fp2 = device(s, fields=False)
+        fp2.set_active(np.setdiff1d(np.arange(len(s["type"])), [i]).astype(np.int32))
+        fp2.advance_timesteps(kick_params(p))
+        fp2.close()
+        codes.append(code)
+    assert codes == [888, 818, 112313, 888]
 
 
 def test_velocity_moments_match_the_serial_sums():
@@ -1717,6 +1738,8 @@ def test_config_c2_64cubed_full_step_properties():
                    pr.ti_begstep, pr.hsml0)
     assert relerr(fp.get_field(B.F_DENSITY)[act], od["density"][act]) < TOL
     assert relerr(fp.get_field(B.F_HSML)[act], od["hsml"][act]) < TOL
+    # hydro_force of the sample against the oracle's hydro_evaluate (hydra.c:822) on the same state
+    assert sampled_hydro_check(pr, T, fp.get_field, act) > 20 * len(act)
 
 
 def test_config_c3_128cubed_shortrange_tree_and_sph_sampled():
