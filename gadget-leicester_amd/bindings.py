@@ -263,6 +263,21 @@ class SyncPoint(C.Structure):
                     else int(getattr(self, k))) for k, _ in self._fields_}
 
 
+class RearrangeParams(C.Structure):
+    """ghip_rearrange_params: the -DSFR part (converted gas leaves the gas block) and the -DBLACK_HOLES part with
+    -DDUST (Mass == 0 is eliminated, whatever the type) of rearrange_particle_sequence, sfr_eff.c:1018-1129"""
+    _fields_ = [("fix_converted", C.c_int), ("eliminate_massless", C.c_int)]
+
+
+class RearrangeResult(C.Structure):
+    """ghip_rearrange_result: the counts after the call and what this context eliminated"""
+    _fields_ = [("numpart", C.c_int), ("ngas", C.c_int), ("converted", C.c_int), ("count_elim", C.c_int),
+                ("count_gaselim", C.c_int), ("count_dustelim", C.c_int), ("changed", C.c_int)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class FofParams(C.Structure):
     """ghip_fof_params (fof_fof, fof.c:94-333): LinkL <= 0 asks for the LINKLENGTH rule on the device"""
     _fields_ = [("LinkL", C.c_double), ("linklength", C.c_double), ("rhodm", C.c_double),
@@ -425,7 +440,8 @@ EXPORTS = [
     "ghip_fof_group_size", "ghip_fof_get_timing", "ghip_fof_get_maxdens_task", "ghip_dd_fof_args_size",
     "ghip_wind_params_size", "ghip_wind_density", "ghip_wind_spread", "ghip_wind_feedback",
     "ghip_wind_get_injected", "ghip_wind_set_injected", "ghip_wind_get_rad_accel", "ghip_wind_set_rad_accel",
-    "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size"]
+    "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size",
+    "ghip_kick_get_fields", "ghip_rearrange", "ghip_peano_order", "ghip_sequence_get_map", "ghip_sequence_get_info"]
 
 
 def lib():
@@ -585,6 +601,11 @@ def lib():
         L.ghip_set_rnd_table.argtypes = [vp, vp, C.c_int]
         L.ghip_tree_max_level.argtypes = []
         L.ghip_find_next_sync_point.argtypes = [vp, C.POINTER(SyncParams), C.POINTER(SyncPoint)]
+        L.ghip_kick_get_fields.argtypes = [vp, vp, vp, vp, vp]
+        L.ghip_rearrange.argtypes = [vp, C.POINTER(RearrangeParams), C.POINTER(RearrangeResult)]
+        L.ghip_peano_order.argtypes = [vp, vp, C.c_double, C.POINTER(C.c_int)]
+        L.ghip_sequence_get_map.argtypes = [vp, vp, vp]
+        L.ghip_sequence_get_info.argtypes = [vp, vp]
         L.ghip_get_active.argtypes = [vp, vp, C.POINTER(C.c_int)]
         L.ghip_find_extent.argtypes = [vp, vp, vp, C.POINTER(C.c_double)]
         L.ghip_dd_get_sync_point.argtypes = [vp, C.POINTER(SyncPoint)]
@@ -705,6 +726,47 @@ class ForcePath:
         p, out = SyncParams(int(ti_current), int(ti_nextoutput)), SyncPoint()
         self._chk(self.L.ghip_find_next_sync_point(self.h, C.byref(p), C.byref(out)))
         return out
+
+    def rearrange(self, fix_converted=True, eliminate_massless=True):
+        """ghip_rearrange: rearrange_particle_sequence (sfr_eff.c:1018-1129) as an order-preserving compaction of
+        the resident state -> RearrangeResult; .n and .ngas follow.  Converted records of the gas block go behind
+        it, Mass == 0 records are eliminated; every field and every optional array held for the current counts
+        travels.  After a call that changed something: tree_build, and find_next_sync_point for the active list."""
+        p = RearrangeParams(int(bool(fix_converted)), int(bool(eliminate_massless)))
+        out = RearrangeResult()
+        self._chk(self.L.ghip_rearrange(self.h, C.byref(p), C.byref(out)))
+        self.n, self.ngas = out.numpart, out.ngas
+        if out.changed:
+            self._active_n = None
+        return out
+
+    def peano_order(self, corner=None, dlen=0.0):
+        """ghip_peano_order: peano_hilbert_order (peano.c:25-185), the gas block and the block behind it each
+        sorted stably by the key of dd_keys() in the cube (corner, dlen) -> True when a record moved.  corner
+        None: the domain of a dd_init context.  GhipError (GHIP_EINVAL), nothing moved, for a position outside
+        the cube."""
+        c0 = None if corner is None else np.ascontiguousarray(corner, np.float64)
+        ch = C.c_int(0)
+        self._chk(self.L.ghip_peano_order(self.h, _ptr(c0), float(dlen), C.byref(ch)))
+        if ch.value:
+            self._active_n = None
+        return bool(ch.value)
+
+    def sequence_info(self):
+        """ghip_sequence_get_info of the last rearrange() / peano_order(): dict(n_before, n_after, bytes_moved,
+        planes)"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.ghip_sequence_get_info(self.h, _ptr(out)))
+        return dict(n_before=int(out[0]), n_after=int(out[1]), bytes_moved=int(out[2]), planes=int(out[3]))
+
+    def sequence_map(self):
+        """ghip_sequence_get_map of the last rearrange() / peano_order() -> (new_of_old int32[n before], -1 for
+        an eliminated record; old_of_new int32[n after])"""
+        info = self.sequence_info()
+        new_of_old = np.zeros(max(info["n_before"], 0), np.int32)
+        old_of_new = np.zeros(max(info["n_after"], 0), np.int32)
+        self._chk(self.L.ghip_sequence_get_map(self.h, _ptr(new_of_old), _ptr(old_of_new)))
+        return new_of_old, old_of_new
 
     def fof(self, link_length=0.0, primary_types=2, secondary_types=0, group_min_len=32, boxsize=0.0,
             periodic=False, max_iter=150, linklength=0.2, rhodm=0.0):
@@ -1363,6 +1425,14 @@ class ForcePath:
         for v, shape in zip(a, ((self.ngas, 3), (self.ngas, 3), (self.n,))):
             assert v is None or v.shape == shape
         self._chk(self.L.ghip_kick_set_fields(self.h, *[None if v is None else _ptr(v) for v in a]))
+
+    def kick_fields(self):
+        """ghip_kick_get_fields -> (DragAccel [ngas][3], DeltaDustMomentum [ngas][3], NewDensity [n]); None for an
+        array the context does not hold for its current counts"""
+        a = [np.zeros((self.ngas, 3)), np.zeros((self.ngas, 3)), np.zeros(self.n)]
+        held = np.zeros(3, np.int32)
+        self._chk(self.L.ghip_kick_get_fields(self.h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(held)))
+        return tuple(v if h else None for v, h in zip(a, held))
 
     def kick_drag_accel(self):
         out = np.zeros((self.ngas, 3))

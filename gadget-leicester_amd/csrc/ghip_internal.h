@@ -487,6 +487,22 @@ struct FofState
 static_assert(GHIP_PAIR_LDS(4) == 10240 && GHIP_PAIR_LDS(5) == 8192 && GHIP_PAIR_LDS(6) == 6144,
               "dynamic-LDS caps of the pair");
 
+// ghip_rearrange / ghip_peano_order (ghip_sequence.hip): the maps of the last call, its work arrays, and the
+// shadows of the optional resident arrays (the GHIP_F_* fields use DDState::fshadow, as the migration does)
+#define SEQ_NOPT 10
+struct SeqState
+{
+  DevBuf new_of_old, old_of_new;   // i32[n before] (-1: eliminated), i32[n after]
+  int n_before = -1, n_after = -1; // -1: no call yet
+  long long bytes_moved = 0;       // read + written by the move of the last call (0: nothing moved), its planes
+  int planes = 0;
+  DevBuf flags, rank;              // u64[n + 1]: survivor flags (gas low word, others high word), their exclusive scan
+  DevBuf key, skey, idx, sidx;     // u64[n], u64[n], i32[n], i32[n]: the stable pair sort of the two blocks
+  DevBuf words;                    // i32[8]: counters and flags of a call
+  DevBuf xshadow[SEQ_NOPT];        // new layout of DragHeating, alpha, Dtalpha, Injected_BH_Momentum, RadAccel,
+                                   // SwallowID, Injected_BH_Energy, DragAccel, DeltaDustMomentum, NewDensity
+};
+
 struct ghip_ctx
 {
   ghip_ctx() = default;
@@ -678,6 +694,7 @@ struct ghip_ctx
   DevBuf srpot;                    // float[NTAB]: shortrange_table_potential (forcetree.c:4201)
   DevBuf gq_work;                  // partial sums, kick tables and photon momenta of ghip_global_quantities
   FofState fof;                    // ghip_fof (ghip_fof.hip)
+  SeqState seq;                    // ghip_rearrange / ghip_peano_order (ghip_sequence.hip)
 };
 #define GHIP_NEV 16
 

@@ -572,6 +572,42 @@ extern "C" int ghip_kick_get_drag_accel(ghip_ctx *ctx, double *drag_accel)
   return ghip_check_device_errors(ctx);
 }
 
+// device planes [3][m] -> host [m][3]
+static int download_planes(ghip_ctx *ctx, const DevBuf &b, double *h, int m)
+{
+  std::vector<double> t(3 * (size_t) m);
+  if(m > 0)
+    HIPCHK(hipMemcpyAsync(t.data(), b.p, t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(int a = 0; a < m; a++)
+    for(int j = 0; j < 3; j++)
+      h[3 * (size_t) a + j] = t[(size_t) j * m + a];
+  return GHIP_OK;
+}
+
+extern "C" int ghip_kick_get_fields(ghip_ctx *ctx, double *drag_accel, double *gas_dust_momentum,
+                                    double *new_density, int held[3])
+{
+  if(!ctx || !held)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  const int n = ctx->n, ng = ctx->ngas;
+  const bool ok = ctx->kick_fields_n == n && ctx->kick_fields_ngas == ng;
+  held[0] = ok && ctx->has_drag;
+  held[1] = ok && ctx->has_ddm;
+  held[2] = ok && ctx->has_newdens;
+  if(drag_accel && held[0])
+    GCHK(download_planes(ctx, ctx->kick_drag, drag_accel, ng));
+  if(gas_dust_momentum && held[1])
+    GCHK(download_planes(ctx, ctx->kick_ddm, gas_dust_momentum, ng));
+  if(new_density && held[2] && n > 0)
+    {
+      HIPCHK(hipMemcpyAsync(new_density, ctx->kick_newdens.p, (size_t) n * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+    }
+  return GHIP_OK;
+}
+
 extern "C" int ghip_advance_timesteps(ghip_ctx *ctx, const ghip_kick_params *p,
                                       long long *TimeBinCount, long long *TimeBinCountSph)
 {

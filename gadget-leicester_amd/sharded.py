@@ -207,6 +207,21 @@ def _fof_result(path, keep):
     return out
 
 
+def _rearrange(path, how):
+    if how is True:
+        return path.rearrange()
+    return path.rearrange(bool(how.fix_converted), bool(how.eliminate_massless))
+
+
+def _elim_counts(res):
+    return (int(res.count_elim), int(res.count_gaselim), int(res.count_dustelim))
+
+
+def _redistributed(results, counts, ordered):
+    tot = [sum(c[k] for c in counts) for k in range(3)]
+    return dict(results=results, tot_elim=tot[0], tot_gaselim=tot[1], tot_dustelim=tot[2], ordered=ordered)
+
+
 class DomainShards:
     """All shards of a run as contexts of THIS process (one after the other on one GPU, or one per
     visible GPU): the parity-test and rehearsal form of the multi-GPU path.  Exchanges are
@@ -264,10 +279,24 @@ class DomainShards:
         ranges (and on request a new cube) from the resident particles of all shards.  Moves nothing."""
         self.run(self.B.DD_DECOMPOSE, params if params is not None else self.B.DecompParams())
 
-    def redistribute(self, params=None):
-        """decompose, then migrate: afterwards every particle sits on the shard its key names"""
+    def redistribute(self, params=None, rearrange=None, peano_order=False):
+        """decompose, then migrate: afterwards every particle sits on the shard its key names.  As
+        domain_Decomposition() does (domain.c:120-135, 281-285): with rearrange = a RearrangeParams (or True: both
+        of its switches) every shard first runs ghip_rearrange, and with peano_order every shard ends with
+        ghip_peano_order in the domain in force.  Returns None with the defaults, else a dict: results (one
+        RearrangeResult per shard, or None), tot_elim / tot_gaselim / tot_dustelim (their sums), ordered (per
+        shard: whether the order moved a record)."""
+        if rearrange is None and not peano_order:
+            self.decompose(params)
+            self.migrate()
+            return None
+        results = None
+        if rearrange is not None:
+            results = [_rearrange(p, rearrange) for p in self.paths]
         self.decompose(params)
         self.migrate()
+        ordered = [p.peano_order() for p in self.paths] if peano_order else None
+        return _redistributed(results, [_elim_counts(r) for r in results] if results else [], ordered)
 
     def pm_region(self, pmgrid):
         """GHIP_DD_PM_REGION: the region of the non-periodic mesh from the resident particles of all shards,
@@ -428,10 +457,29 @@ class DomainRank:
         contributes one 128-byte block and one histogram, never its keys.  Moves nothing."""
         self._run(self.B.DD_DECOMPOSE, params if params is not None else self.B.DecompParams())
 
-    def redistribute(self, params=None):
-        """decompose, then migrate: afterwards every particle sits on the rank its key names"""
+    def redistribute(self, params=None, rearrange=None, peano_order=False):
+        """decompose, then migrate: afterwards every particle sits on the rank its key names.  With rearrange (a
+        RearrangeParams, or True: both switches) this rank first runs ghip_rearrange, with peano_order it ends with
+        ghip_peano_order in the domain in force (domain.c:120-135, 281-285); both are local.  Returns None with
+        the defaults, else a dict as DomainShards.redistribute: results = [this rank's RearrangeResult], the
+        totals summed over all ranks through the host all-gather of transport "host" (with "rccl" the caller's
+        MPI adds them: the totals are then this rank's own and `local_totals` says so)."""
+        if rearrange is None and not peano_order:
+            self.decompose(params)
+            self.migrate()
+            return None
+        res = _rearrange(self.p, rearrange) if rearrange is not None else None
         self.decompose(params)
         self.migrate()
+        ordered = [self.p.peano_order()] if peano_order else None
+        mine = _elim_counts(res) if res is not None else (0, 0, 0)
+        counts, local = [mine], self.nranks > 1
+        if res is not None and self.allgather is not None:
+            got = _np.frombuffer(self.allgather(_np.array(mine, _np.int64).tobytes()), _np.int64)
+            counts, local = [tuple(int(v) for v in row) for row in got.reshape(self.nranks, 3)], False
+        out = _redistributed([res] if res is not None else None, counts if res is not None else [], ordered)
+        out["local_totals"] = bool(local and res is not None)
+        return out
 
     def pm_region(self, pmgrid):
         """GHIP_DD_PM_REGION, a collective: the region of the non-periodic mesh from the resident particles of

@@ -31,6 +31,8 @@
  *   ghip_find_next_sync_point             find_next_sync_point_and_drift() without its drift  run.c:190-340
  *   ghip_find_extent                      domain_findExtent() of one context   domain.c:1972-2014
  *   ghip_fof                              fof_fof() without group files / SUBFIND   fof.c:94-333
+ *   ghip_rearrange                        rearrange_particle_sequence() sfr_eff.c:1018-1129
+ *   ghip_peano_order                      peano_hilbert_order()        peano.c:25-185
  * The host-side mirror with the reference's own names (gravity_tree(), density(), hydro_force(),
  * force_treeevaluate(), ...) is include/gadget_force.h.
  */
@@ -539,6 +541,10 @@ int ghip_set_integration_flags(ghip_ctx *ctx, const ghip_integration_flags *f);
 int ghip_kick_set_fields(ghip_ctx *ctx, const double *drag_accel, const double *gas_dust_momentum,
                          const double *new_density);
 int ghip_kick_get_drag_accel(ghip_ctx *ctx, double *drag_accel);
+/* the three arrays of ghip_kick_set_fields as the context holds them: held[k] = 1 when array k is held for the
+ * current counts (it then lands in its host array, layouts as above; NULL = skip), else 0 and nothing is written */
+int ghip_kick_get_fields(ghip_ctx *ctx, double *drag_accel, double *gas_dust_momentum, double *new_density,
+                         int held[3]);
 /* the bin populations after the last ghip_advance_timesteps, recounted over all particles
  * (reconstruct_timebins, predict.c:14-127); synchronises */
 int ghip_timebin_counts(ghip_ctx *ctx, long long *TimeBinCount, long long *TimeBinCountSph);
@@ -1560,6 +1566,58 @@ typedef struct {
  * index_maxdens >= 0 */
 int ghip_fof_get_maxdens_task(ghip_ctx *ctx, int *task /* [Ngroups]; -1 = no gas member */);
 size_t ghip_dd_fof_args_size(void);
+
+/* ---- the particle sequence: rearrange_particle_sequence() and peano_hilbert_order() on the device ----
+ * What domain_Decomposition() runs around its cut (domain.c:120-135, 281-285), for a resident run whose passes
+ * leave Mass == 0 records (ghip_blackhole_swallow, the wind loop) and Type != 0 records inside the gas block
+ * (ghip_sfr_cooling, sinks formed from ghip_fof groups).
+ *
+ * ghip_rearrange (sfr_eff.c:1018-1129) is an ORDER-PRESERVING compaction.  The new layout: the gas survivors in
+ * their old order, then (fix_converted) the records of the old gas block whose Type is not 0, in their old
+ * order, then the other survivors in their old order; eliminate_massless drops every record with Mass == 0,
+ * whatever its type.  With both set the gas block afterwards is exactly {Type == 0, Mass != 0} of the old gas
+ * block.  A converted record keeps its per-particle fields and drops its per-gas ones.  This is the -DDUST
+ * build's behaviour, the only one built: without -DDUST the reference counts a massless record that is not gas
+ * and leaves it in place.  The reference's serial swap-from-the-end leaves another order; peano_hilbert_order()
+ * follows it at domain.c:285 and its merge sort is stable, so after ghip_peano_order the two sequences differ
+ * inside runs of equal keys at most.  count_gaselim counts eliminated Type 0 records, count_dustelim Type 2;
+ * `converted` is counted on the device (there is no Stars_converted to pass, hence no endrun(181170)).
+ *
+ * ghip_peano_order (peano.c:25-185) sorts the gas block [0, ngas) and the block behind it separately, each
+ * stably, by the key of ghip_dd_keys (domain.c's Key[i]: 21 bits per dimension in the cube DomainCorner,
+ * DomainLen).  DomainCorner == NULL: on a ghip_dd_init context the domain of ghip_dd_set_domain /
+ * GHIP_DD_DECOMPOSE (DomainLen is ignored), on any other context GHIP_EINVAL.  A position that is not finite or
+ * lies outside [corner, corner + len) in a dimension: GHIP_EINVAL, nothing moved.  It sorts whatever types the
+ * blocks hold (a mixed gas block is legal).
+ *
+ * With a record travel, bit for bit, in both calls: every GHIP_F_* field and every optional resident array held
+ * for the current counts -- DragHeating, alpha and Dtalpha, Injected_BH_Momentum, RadAccel, SwallowID and
+ * Injected_BH_Energy, DragAccel, DeltaDustMomentum and NewDensity of ghip_kick_set_fields.  An array held for
+ * other counts is dropped, as by GHIP_DD_MIGRATE.  A call that moved something leaves the rest of the state as
+ * a migration does: both trees are gone, a kept tree (ghip_set_dynamic_tree) is refused until a full build, the
+ * target lists and the active list are gone (everybody is active; ghip_find_next_sync_point makes the next list,
+ * as reconstruct_timebins() at domain.c:305), the potential and the FOF labels are stale and refused.  Every
+ * switch is kept.  A call that moved nothing (changed == 0) invalidates nothing.  Both calls wait for the
+ * context's streams first; both are local on a ghip_dd_init context (no exchange) and GHIP_EINVAL on a
+ * replicated shard (ghip_set_shard with nranks > 1).  The host mirror (gadget_force.h) has neither: a host that
+ * owns P[] keeps its own functions. */
+typedef struct {
+  int fix_converted;        /* the -DSFR part, sfr_eff.c:1030-1053 */
+  int eliminate_massless;   /* the -DBLACK_HOLES part with -DDUST, sfr_eff.c:1055-1095 */
+} ghip_rearrange_params;
+typedef struct {
+  int numpart, ngas;        /* after the call */
+  int converted;            /* records that left the gas block and survive */
+  int count_elim, count_gaselim, count_dustelim;   /* this context's; a caller with shards adds them up */
+  int changed;              /* 0: no record moved */
+} ghip_rearrange_result;
+int ghip_rearrange(ghip_ctx *ctx, const ghip_rearrange_params *p, ghip_rearrange_result *out);
+int ghip_peano_order(ghip_ctx *ctx, const double DomainCorner[3], double DomainLen, int *changed);
+/* the permutation of the last of the two calls (the identity when it moved nothing): new_of_old[n before the
+ * call], -1 for an eliminated record; old_of_new[n after it].  Either may be NULL */
+int ghip_sequence_get_map(ghip_ctx *ctx, int *new_of_old, int *old_of_new);
+/* of the same call: {n before, n after (-1, -1: no call yet), bytes its move read and wrote, planes it moved} */
+int ghip_sequence_get_info(ghip_ctx *ctx, long long out[4]);
 
 /* ---- introspection ---- */
 int ghip_get_stats(const ghip_ctx *ctx, ghip_stats *out);
