@@ -1199,22 +1199,38 @@ __global__ void k_ghost_growth(int nt, const int *__restrict__ tgt, const int *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// the dust passes: which shards can a grain's sphere reach? (ghip_dust.hip runs the passes)
+// the dust passes, the wind particles and the friends-of-friends groups: which shards can a sphere reach?
+// (ghip_dust.hip, ghip_wind.hip and ghip_fof.hip run the operations)
 // ---------------------------------------------------------------------------------------------
-// the local Type 0 and Type 2 particles (the candidates of both passes) in curve order, as indices of
-// the merged gravity tree
-__global__ void k_flag_dust_partners(int nt, const int *__restrict__ perm, int n, const int *__restrict__ type,
-                                     int *__restrict__ flags)
+// the partners of a pass among this shard's particles: the local Type 0 and Type 2 particles (the candidates of
+// both dust passes) / the local Type-0 particles with Mass > 0 (those of both wind passes, virtual_density.c:650-664)
+struct DustPartner
+{
+  const int *type;
+  __device__ __forceinline__ bool operator()(int i) const { return type[i] == 0 || type[i] == 2; }
+};
+struct WindPartner
+{
+  const int *type;
+  const double *mass;
+  __device__ __forceinline__ bool operator()(int i) const { return type[i] == 0 && mass[i] > 0; }
+};
+
+// ... flagged in curve order, by their indices of the merged gravity tree
+template <class Partner>
+__global__ void k_flag_partners(int nt, const int *__restrict__ perm, int n, Partner partner, int *__restrict__ flags)
 {
   int s = blockIdx.x * blockDim.x + threadIdx.x;
   if(s >= nt)
     return;
   const int i = perm[s];
-  flags[s] = (i < n && (type[i] == 0 || type[i] == 2)) ? 1 : 0;
+  flags[s] = (i < n && partner(i)) ? 1 : 0;
 }
 
-// this shard's group table over its local Type 0 / Type 2 particles; the all-gather is left pending
-int ghip_dd_dust_groups(ghip_ctx *ctx)
+// this shard's group table over its partners (val: what the groups carry in place of the least OldAcc, which the
+// sphere test does not read); the all-gather is left pending
+template <class Partner>
+static int dd_partner_groups(ghip_ctx *ctx, const Partner &partner, const double *val)
 {
   DDState &D = ctx->dd;
   hipStream_t st = ctx->stream;
@@ -1224,82 +1240,70 @@ int ghip_dd_dust_groups(ghip_ctx *ctx)
   if(nt > 0 && ctx->n > 0)
     {
       GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
-      k_flag_dust_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n,
-                                                          P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->dflags));
+      k_flag_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n, partner, P<int>(ctx->dflags));
       HIPCHK(hipGetLastError());
       int *dnum = &ghip_words(ctx)->dust_partners;
       GCHK(ghip_select_flagged(ctx, nullptr, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
       HIPCHK(hipMemcpyAsync(&nsel, dnum, 4, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
     }
-  // (the groups carry the least OldAcc, which the sphere test below does not read)
-  GCHK(build_groups(ctx, false, P<int>(D.gas_tgt), nsel));
+  GCHK(build_groups(ctx, false, P<int>(D.gas_tgt), nsel, val));
   ghip_dd_set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
   return 1;
 }
 
-// after the all-gather of the group tables: the destinations of this shard's nd grains (ord: list slots
-// in tree order, idx: local indices, both on the device), the per-destination lists of their local
-// indices in ascending order (D.du_list, D.du_scount / du_soff), the total
+int ghip_dd_dust_groups(ghip_ctx *ctx)
+{
+  return dd_partner_groups(ctx, DustPartner{P<int>(ctx->f[GHIP_F_TYPE])}, nullptr);
+}
+
+// After the all-gather of the group tables: the destinations of the nitem items of S (a Src of k_dd_select) whose
+// spheres reach another shard's groups, as per-destination lists of their mask slots in ascending order (list,
+// scount / soff) and their total.  mask: u64 [nmask], cleared here
+template <class Src>
+static int dd_sphere_select(ghip_ctx *ctx, int nitem, const Src &S, double boxsize, int periodic, int nmask,
+                            DevBuf &mask, DevBuf &list, int *scount, int *soff, int *total)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int P_ = D.nranks;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    scount[r] = soff[r] = 0;
+  *total = 0;
+  GCHK(ghip_ensure(ctx, list, 4));
+  if(nitem == 0 || P_ < 2 || nmask == 0)
+    return GHIP_OK;
+  GCHK(ghip_ensure(ctx, mask, (size_t) nmask * 8));
+  HIPCHK(hipMemsetAsync(mask.p, 0, (size_t) nmask * 8, st));
+  k_dd_select<Src, SphereReach><<<cdiv(nitem, 64) * (P_ - 1), 64, 0, st>>>(
+    nitem, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(mask));
+  HIPCHK(hipGetLastError());
+  return multi_select(ctx, nmask, P<unsigned long long>(mask), list, scount, soff, total);
+}
+
+// the destinations of this shard's nd grains (ord: list slots in tree order, idx: local indices, both on the
+// device): D.du_list holds their local indices, D.du_scount / du_soff the layout
 int ghip_dd_dust_select(ghip_ctx *ctx, const char *what, int nd, const int *ord, const int *idx, double boxsize,
                         int periodic, int *total)
 {
   DDState &D = ctx->dd;
-  hipStream_t st = ctx->stream;
-  const int P_ = D.nranks, n = ctx->n;
   GCHK(check_group_status(ctx, what));
-  for(int r = 0; r < GHIP_MAXRANKS; r++)
-    D.du_scount[r] = D.du_soff[r] = 0;
-  *total = 0;
-  GCHK(ghip_ensure(ctx, D.du_list, 4));
-  if(nd == 0 || P_ < 2)
-    return GHIP_OK;
-  GCHK(ghip_ensure(ctx, D.du_mask, (size_t) n * 8));
-  HIPCHK(hipMemsetAsync(D.du_mask.p, 0, (size_t) n * 8, st));
-  const DustSrc S = {ord, idx, n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML])};
-  k_dd_select<DustSrc, SphereReach><<<cdiv(nd, 64) * (P_ - 1), 64, 0, st>>>(
-    nd, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(D.du_mask));
-  HIPCHK(hipGetLastError());
-  return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
+  const DustSrc S = {ord, idx, ctx->n, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML])};
+  return dd_sphere_select(ctx, nd, S, boxsize, periodic, ctx->n, D.du_mask, D.du_list, D.du_scount, D.du_soff, total);
 }
 
-// ---------------------------------------------------------------------------------------------
-// the wind particles: which shards' gas can a wind particle's sphere reach? (ghip_wind.hip runs the operation)
-// ---------------------------------------------------------------------------------------------
-// the local Type-0 particles with Mass > 0 (the candidates of both passes, virtual_density.c:650-664)
-__global__ void k_flag_wind_partners(int nt, const int *__restrict__ perm, int n, const int *__restrict__ type,
-                                     const double *__restrict__ mass, int *__restrict__ flags)
-{
-  int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if(s >= nt)
-    return;
-  const int i = perm[s];
-  flags[s] = (i < n && type[i] == 0 && mass[i] > 0) ? 1 : 0;
-}
-
-// This shard's group table over those particles, and in the status record behind it three words of the wind
-// operation (the largest h_j as a double, the dt_jump sum, the list length) and whether this shard has failed
-// already (own_rc != GHIP_OK, its message in ctx->err); the all-gather is left pending
+// The wind's group table, and in the status record behind it three words of the wind operation (the largest h_j as
+// a double, the dt_jump sum, the list length) and whether this shard has failed already (own_rc != GHIP_OK, its
+// message in ctx->err); the all-gather is left pending
 int ghip_dd_wind_groups(ghip_ctx *ctx, const double extra[3], int own_rc)
 {
   DDState &D = ctx->dd;
-  hipStream_t st = ctx->stream;
   const std::string own_msg = ctx->err;
-  const int nt = ctx->gt.n;
-  int nsel = 0;
-  GCHK(ghip_ensure(ctx, D.gas_tgt, (size_t) (nt > 0 ? nt : 1) * 4));
-  if(nt > 0 && ctx->n > 0)
-    {
-      GCHK(ghip_ensure(ctx, ctx->dflags, (size_t) nt * 4));
-      k_flag_wind_partners<<<cdiv(nt, 256), 256, 0, st>>>(nt, P<int>(ctx->gt.perm), ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                          P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->dflags));
-      HIPCHK(hipGetLastError());
-      int *dnum = &ghip_words(ctx)->dust_partners;
-      GCHK(ghip_select_flagged(ctx, nullptr, P<int>(ctx->dflags), P<int>(D.gas_tgt), dnum, nt, st));
-      HIPCHK(hipMemcpyAsync(&nsel, dnum, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-    }
-  GCHK(build_groups(ctx, false, P<int>(D.gas_tgt), nsel, P<double>(ctx->f[GHIP_F_MASS])));
+  const double *mass = P<double>(ctx->f[GHIP_F_MASS]);
+  const int rc = dd_partner_groups(ctx, WindPartner{P<int>(ctx->f[GHIP_F_TYPE]), mass}, mass);
+  if(rc != 1)
+    return rc;
+  // (the all-gather is pending, not begun: the status record still gets into grp_own)
   if(own_rc != GHIP_OK)   // (build_groups held its own check, which passed)
     {
       D.held.rc = own_rc;
@@ -1312,9 +1316,8 @@ int ghip_dd_wind_groups(ghip_ctx *ctx, const double extra[3], int own_rc)
   status.cz = extra[0];
   status.ex = extra[1];
   status.ey = extra[2];
-  HIPCHK(hipMemcpyAsync(P<DDGroup>(D.grp_own) + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, st));
-  HIPCHK(ghip_stream_sync(ctx, st));   // (`status` lives on this frame)
-  ghip_dd_set_allgather(D, D.grp_own.p, (size_t) DD_STRIDE * sizeof(DDGroup), &D.grp_all);
+  HIPCHK(hipMemcpyAsync(P<DDGroup>(D.grp_own) + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));   // (`status` lives on this frame)
   return 1;
 }
 
@@ -1337,27 +1340,13 @@ int ghip_dd_wind_status(ghip_ctx *ctx, const char *what, double *extra)
 }
 
 // the destinations of the m listed wind particles (list: slots in tree order; idx: local indices; dtj, drmin: planes
-// in slot order) against the all-gathered tables: the per-destination lists of their local indices in ascending
-// order (D.du_list, D.du_scount / du_soff), the total.  cut, hmax: see WindSrc
+// in slot order), where the dust passes leave theirs.  cut, hmax: see WindSrc
 int ghip_dd_wind_select(ghip_ctx *ctx, int m, const int *list, const int *idx, const double *dtj, const double *drmin,
                         int cut, double hmax, double boxsize, int periodic, int *total)
 {
   DDState &D = ctx->dd;
-  hipStream_t st = ctx->stream;
-  const int P_ = D.nranks, n = ctx->n;
-  for(int r = 0; r < GHIP_MAXRANKS; r++)
-    D.du_scount[r] = D.du_soff[r] = 0;
-  *total = 0;
-  GCHK(ghip_ensure(ctx, D.du_list, 4));
-  if(m == 0 || P_ < 2 || n == 0)
-    return GHIP_OK;
-  GCHK(ghip_ensure(ctx, D.du_mask, (size_t) n * 8));
-  HIPCHK(hipMemsetAsync(D.du_mask.p, 0, (size_t) n * 8, st));
-  const WindSrc S = {list, idx, n, cut, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]), dtj, drmin, hmax};
-  k_dd_select<WindSrc, SphereReach><<<cdiv(m, 64) * (P_ - 1), 64, 0, st>>>(
-    m, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(D.du_mask));
-  HIPCHK(hipGetLastError());
-  return multi_select(ctx, n, P<unsigned long long>(D.du_mask), D.du_list, D.du_scount, D.du_soff, total);
+  const WindSrc S = {list, idx, ctx->n, cut, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]), dtj, drmin, hmax};
+  return dd_sphere_select(ctx, m, S, boxsize, periodic, ctx->n, D.du_mask, D.du_list, D.du_scount, D.du_soff, total);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1393,26 +1382,12 @@ int ghip_dd_fof_groups(ghip_ctx *ctx, const int *plist, int nprim)
 int ghip_dd_fof_status(ghip_ctx *ctx, const char *what) { return check_group_status(ctx, what); }
 
 // the per-destination lists (ascending tree index) of the nitem items whose spheres reach another shard's primaries;
-// mask: u64[ctx->gt.n], cleared here
+// mask: u64[ctx->gt.n]
 int ghip_dd_fof_select(ghip_ctx *ctx, int nitem, const int *items, const double *hs, double h0, double boxsize,
                        int periodic, DevBuf &mask, DevBuf &list, int *scount, int *soff, int *total)
 {
-  DDState &D = ctx->dd;
-  hipStream_t st = ctx->stream;
-  const int P_ = D.nranks, nt = ctx->gt.n;
-  for(int r = 0; r < GHIP_MAXRANKS; r++)
-    scount[r] = soff[r] = 0;
-  *total = 0;
-  GCHK(ghip_ensure(ctx, list, 4));
-  if(nitem == 0 || P_ < 2 || nt == 0)
-    return GHIP_OK;
-  GCHK(ghip_ensure(ctx, mask, (size_t) nt * 8));
-  HIPCHK(hipMemsetAsync(mask.p, 0, (size_t) nt * 8, st));
   const FofSrc S = {items, P<double>(ctx->sx), P<double>(ctx->sy), P<double>(ctx->sz), hs, h0};
-  k_dd_select<FofSrc, SphereReach><<<cdiv(nitem, 64) * (P_ - 1), 64, 0, st>>>(
-    nitem, S, P<DDGroup>(D.grp_all), make_box(boxsize, periodic), P_, D.rank, P<unsigned long long>(mask));
-  HIPCHK(hipGetLastError());
-  return multi_select(ctx, nt, P<unsigned long long>(mask), list, scount, soff, total);
+  return dd_sphere_select(ctx, nitem, S, boxsize, periodic, ctx->gt.n, mask, list, scount, soff, total);
 }
 
 // multi_select for the callers outside this file: the items of mask[0 .. n) per rank whose bit is set

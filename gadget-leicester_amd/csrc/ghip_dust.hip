@@ -17,17 +17,13 @@
 // inverse permutation), which makes the walks of the 64 lanes of a wavefront neighbours in space.
 //
 // The scatter into the gas is order dependent (the entropy update is multiplicative, with a floor and a
-// cap): for each gas particle the reference applies the grains in the order of the active list.  The
-// pairs (gas j, grain a) are therefore counted, written as 64-bit keys (j << 32 | a) with their kernel
-// weight, radix sorted, and one thread per gas particle applies its run of pairs in list order.  Every
-// sum is a per-thread loop in a fixed order: two identical calls give identical bits.
-#include <climits>
-
-#include "ghip_ngb.h"
-#include "ghip_prim.h"
+// cap): for each gas particle the reference applies the grains in the order of the active list.  That is the
+// ordered pair scatter of ghip_pairs.h; this file gives it the dust-gas pair (DustTarget) and
+// what a gas particle does with its run of grains (k_dust_apply).  Every sum is a per-thread loop in a fixed
+// order: two identical calls give identical bits.
+#include "ghip_pairs.h"
 
 #define DUST_RHO_GRAIN 3.           // rho_dust, dust.c:379
-#define DUST_LEAF 16                // a tree node with at most this many particles is swept flat
 
 // per-grain planes of the staging buffer ([DUST_NPLANES][nd] doubles)
 enum
@@ -134,17 +130,6 @@ struct DustGrainRec
   }
 };
 
-// sort key of grain a: its place in the gravity tree
-__global__ void k_dust_order_keys(int nd, const int *__restrict__ idx, const int *__restrict__ iperm,
-                                  unsigned int *__restrict__ key, int *__restrict__ slot)
-{
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if(a >= nd)
-    return;
-  key[a] = (unsigned int) iperm[idx[a]];
-  slot[a] = a;
-}
-
 // dust_evaluate_density (dust.c:748-887): the Type-2 neighbours with Mass > 0 within the grain's h,
 // the grain itself included, each weighted with the GRAIN's own mass (dust.c:849: `dustmass` is
 // PPP[target].Mass -- a reference quirk kept as it is: the result is m_i * sum_j W_ij, not a density of
@@ -173,7 +158,7 @@ k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__
       const DustVel &dv = d_only(v...);
       const double *__restrict__ vel = dv.vel;
       double s0 = 0, s1 = 0, s2 = 0;
-      d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
+      d_ngb_walk_thread<PAIR_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
         const int j = perm[p];
         if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
           return;
@@ -195,7 +180,7 @@ k_dust_density(int nd, const int *__restrict__ ord, G g, int n, const double *__
     }
   else
     {
-      d_ngb_walk_thread<DUST_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
+      d_ngb_walk_thread<PAIR_LEAF>(GravElems{lk, cl}, nelem, px, py, pz, h, b, [&](int p) {
         const int j = perm[p];
         if(j < 0 || j >= n || type[j] != 2 || !(mass[j] > 0))
           return;
@@ -362,87 +347,96 @@ __global__ void k_dust_grain(int nd, const int *__restrict__ idx, int n, const i
 #undef PL
 }
 
-// the gas neighbours that dust_evaluate_select updates (dust.c:962-1000): Type 0, Mass > 0, u < 1,
-// the gas particle's own dt > 0 and the grain's DUST_Density > 0 -- this context's own gas only (a
-// shard's ghosts, j >= ngas, are skipped).  fill == 0: count them into cnt[a]; fill == 1: write
-// (j << 32 | obase + a, W) from off[a] on.  obase + a is the grain's place in the order in which a gas
-// particle receives the grains.
-template <int fill, class G>
-__global__ void __launch_bounds__(64)
-k_dust_pairs(int nd, const int *__restrict__ ord, G g, int obase, int n, int ngas,
-             const double *__restrict__ pos, const double *__restrict__ mass, const int *__restrict__ type,
-             const int *__restrict__ timebin, int nelem, const SphNode *__restrict__ nodes,
-             const int *__restrict__ perm, BoxK b, long long *__restrict__ cnt,
-             const long long *__restrict__ off, unsigned long long *__restrict__ key,
-             double *__restrict__ wgt)
+// The dust-gas pair of dust_evaluate_select (dust.c:962-1000) as a Target of k_pairs (ghip_pairs.h): the gas
+// neighbours a grain updates are Type 0, Mass > 0, u < 1 with the gas particle's own dt > 0 -- this context's own
+// gas only (a shard's ghosts, j >= ngas, are skipped) -- searched at the grain's h ...
+struct DustGas
 {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if(t >= nd)
-    return;
-  const int a = ord ? ord[t] : t;
-  double px, py, pz, h, grho;
-  g.get(a, px, py, pz, h, grho);
-  long long c = 0;
-  if(grho > 0.)
-    {
-      const long long o = fill ? off[a] : 0;
-      d_ngb_walk_thread<DUST_LEAF>(GasElems{nodes}, nelem, px, py, pz, h, b, [&](int p) {
-        const int j = perm[p];
-        if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0) || timebin[j] == 0)
-          return;
-        double wk;
-        if(!d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk))
-          return;
-        if(fill)
-          {
-            key[o + c] = ((unsigned long long) j << 32) | (unsigned int) (obase + a);
-            wgt[o + c] = wk;
-          }
-        c++;
-      });
-    }
-  if(!fill)
-    cnt[a] = c;
-}
+  int n, ngas;
+  const double *pos, *mass;
+  const int *type, *timebin;
+  __device__ __forceinline__ bool pair(int j, double px, double py, double pz, double h, const BoxK b, double &wk) const
+  {
+    if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0) || timebin[j] == 0)
+      return false;
+    return d_dust_weight(px, py, pz, pos[j], pos[(size_t) n + j], pos[2 * (size_t) n + j], h, b, wk);
+  }
+};
 
-// the update of one gas particle by the grains of its run of sorted pairs, in list order
-// (dust.c:987-996)
+// ... and the grain has its DUST_Density > 0.  G: DustGrainLocal, launched in the tree order ord, or DustGrainRec
+// (ord == nullptr); grain a takes slot obase + a
+template <class G>
+struct DustTarget : DustGas
+{
+  G g;
+  const int *ord;
+  int obase;
+  __device__ __forceinline__ bool get(int t, int &slot, double &x, double &y, double &z, double &h, double &rs) const
+  {
+    const int a = ord ? ord[t] : t;
+    double grho;
+    g.get(a, x, y, z, h, grho);
+    slot = obase + a;
+    rs = h;
+    return grho > 0.;
+  }
+};
+
+#define DUST_REC_DENS 5   // x, y, z, Hsml, Mass
+#define DUST_REC_DRAG 9   // x, y, z, Hsml, DUST_Density, DeltaDustMomentum [3], DeltaDragEnergy
+
+// the update of one gas particle by the grains of its run of sorted pairs, in slot order (dust.c:987-996): this
+// context's grains, slots [0, nd), from the planes w; then a shard's nimp imported ones, slots nd + t, from their
+// drag records
 __global__ void k_dust_apply(long long npairs, const unsigned long long *__restrict__ key,
-                             const double *__restrict__ wgt, int nd, const double *__restrict__ w,
-                             int n, const double *__restrict__ mass, const int *__restrict__ timebin,
-                             double *__restrict__ vel, double *__restrict__ entropy,
-                             double *__restrict__ heat, DustK K)
+                             const double *__restrict__ wgt, int nd, const double *__restrict__ w, int nimp,
+                             const double *__restrict__ rec, int n, int ngas, const double *__restrict__ mass,
+                             const int *__restrict__ timebin, double *__restrict__ vel,
+                             double *__restrict__ entropy, double *__restrict__ heat, DustK K)
 {
   const long long s0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-  if(s0 >= npairs)
+  unsigned int j;
+  if(!d_pair_run_head(s0, npairs, key, ngas, j))
     return;
-  const unsigned int j = (unsigned int) (key[s0] >> 32);
-  if(s0 > 0 && (unsigned int) (key[s0 - 1] >> 32) == j)
-    return;   // not the first pair of its gas particle
   const size_t N = (size_t) n, D = (size_t) nd;
   const int tb = timebin[j];
   const double dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac_gas;
   const double mj = mass[j];
   double v0 = vel[j], v1 = vel[N + j], v2 = vel[2 * N + j], A = entropy[j], dh = heat[j];
-  for(long long s = s0; s < npairs && (unsigned int) (key[s] >> 32) == j; s++)
-    {
-      const unsigned int a = (unsigned int) (key[s] & 0xffffffffULL);
-      const double wk = wgt[s];
-      const double density = w[(size_t) DP_RHO * D + a];
-      const double E = w[(size_t) DP_DE * D + a];
-      v0 -= w[(size_t) DP_DMOM * D + a] / density * wk;
-      v1 -= w[(size_t) (DP_DMOM + 1) * D + a] / density * wk;
-      v2 -= w[(size_t) (DP_DMOM + 2) * D + a] / density * wk;
-      double u_old = A / GAMMA_MINUS1 * pow(density, GAMMA_MINUS1);
-      if(K.minegy > u_old)   // DMAX(All.MinEgySpec, ...), allvars.h:273
-        u_old = K.minegy;
-      const double u_new = u_old + E * wk / density;
-      double u_inc = u_new / u_old;
-      if(u_inc > 1.5)
-        u_inc = 1.5;
-      A *= u_inc;
-      dh += 1.e-20 * (E * wk / density * mj / dt);
-    }
+  d_pair_run(s0, npairs, key, wgt, j, [&](unsigned int a, double wk) {
+    if(a >= (unsigned int) nd + (unsigned int) nimp)
+      return;
+    double density, m0, m1, m2, E;
+    if(a < (unsigned int) nd)
+      {
+        density = w[(size_t) DP_RHO * D + a];
+        m0 = w[(size_t) DP_DMOM * D + a];
+        m1 = w[(size_t) (DP_DMOM + 1) * D + a];
+        m2 = w[(size_t) (DP_DMOM + 2) * D + a];
+        E = w[(size_t) DP_DE * D + a];
+      }
+    else
+      {
+        const double *q = rec + DUST_REC_DRAG * (size_t) (a - (unsigned int) nd);
+        density = q[4];
+        m0 = q[5];
+        m1 = q[6];
+        m2 = q[7];
+        E = q[8];
+      }
+    v0 -= m0 / density * wk;
+    v1 -= m1 / density * wk;
+    v2 -= m2 / density * wk;
+    double u_old = A / GAMMA_MINUS1 * pow(density, GAMMA_MINUS1);
+    if(K.minegy > u_old)   // DMAX(All.MinEgySpec, ...), allvars.h:273
+      u_old = K.minegy;
+    const double u_new = u_old + E * wk / density;
+    double u_inc = u_new / u_old;
+    if(u_inc > 1.5)
+      u_inc = 1.5;
+    A *= u_inc;
+    dh += 1.e-20 * (E * wk / density * mj / dt);
+  });
   vel[j] = v0;
   vel[N + j] = v1;
   vel[2 * N + j] = v2;
@@ -451,18 +445,8 @@ __global__ void k_dust_apply(long long npairs, const unsigned long long *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// multi-GPU shards: the grain records that travel
+// multi-GPU shards: the grain records that travel (DUST_REC_DENS / DUST_REC_DRAG doubles each)
 // ---------------------------------------------------------------------------------------------
-#define DUST_REC_DENS 5   // x, y, z, Hsml, Mass
-#define DUST_REC_DRAG 9   // x, y, z, Hsml, DUST_Density, DeltaDustMomentum [3], DeltaDragEnergy
-
-__global__ void k_dust_slots(int nd, const int *__restrict__ idx, int *__restrict__ slot)
-{
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if(a < nd)
-    slot[idx[a]] = a;
-}
-
 // record r of the send lists: local particle list[r], list slot slot[list[r]]; w: the planes (drag)
 template <int K>
 __global__ void k_dust_pack(int nrec, const int *__restrict__ list, const int *__restrict__ slot, int n,
@@ -510,32 +494,6 @@ __global__ void k_dust_add_parts4(int cnt, const int *__restrict__ list, const i
   const size_t a = (size_t) slot[list[k]];
   for(int c = 0; c < 4; c++)
     out[c * nd + a] += part[4 * (size_t) k + c];
-}
-
-// the planes k_dust_apply reads, over this shard's grains [0, nd) and the imported ones [nd, nd + nimp)
-__global__ void k_dust_combine(int nd, int nimp, const double *__restrict__ w, const double *__restrict__ rec,
-                               double *__restrict__ cw)
-{
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  const int m = nd + nimp;
-  if(a >= m)
-    return;
-  const size_t M = (size_t) m, D = (size_t) nd;
-  if(a < nd)
-    {
-      cw[DP_RHO * M + a] = w[DP_RHO * D + a];
-      for(int k = 0; k < 3; k++)
-        cw[(DP_DMOM + k) * M + a] = w[(DP_DMOM + k) * D + a];
-      cw[DP_DE * M + a] = w[DP_DE * D + a];
-    }
-  else
-    {
-      const double *r = rec + (size_t) (a - nd) * DUST_REC_DRAG;
-      cw[DP_RHO * M + a] = r[4];
-      for(int k = 0; k < 3; k++)
-        cw[(DP_DMOM + k) * M + a] = r[5 + k];
-      cw[DP_DE * M + a] = r[8];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -622,14 +580,7 @@ static int dust_upload_list(ghip_ctx *ctx, int nd, const int *idx, const char *w
   int *didx = P<int>(ctx->dust_idx), *dord = didx + D, *dslot = dord + 3 * D;
   unsigned int *dkey = reinterpret_cast<unsigned int *>(dord + D), *dkey2 = dkey + D;
   HIPCHK(hipMemcpyAsync(didx, idx, D * 4, hipMemcpyHostToDevice, st));
-  k_dust_order_keys<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(ctx->gt.iperm), dkey, dslot);
-  HIPCHK(hipGetLastError());
-  // (sorted positions of a shard's merged tree run up to its local particles + imported elements)
-  const long long nsorted = ctx->gt.n > ctx->n ? ctx->gt.n : ctx->n;
-  int end_bit = 1;
-  while(end_bit < 32 && (1LL << end_bit) <= nsorted)
-    end_bit++;
-  return ghip_sort_pairs(ctx, dkey, dkey2, dslot, dord, nd, end_bit, st);
+  return ghip_tree_order(ctx, nd, didx, dkey, dkey2, dslot, dord, st);
 }
 
 // One pass in the record every layer below the entries reads.  g == nullptr (a *_grains entry without its struct)
@@ -797,12 +748,11 @@ static int dust_download_density(ghip_ctx *ctx, const DustCall &c)
   return GHIP_OK;
 }
 
-// The scatter into this context's gas: count, scan, fill, sort, apply.  Grains [0, nd) are the list's
-// (slots in dust_idx, planes w with stride nd, launched in tree order), [nd, nd + nimp) the imported
-// records rec; cw holds the planes k_dust_apply reads with stride nd + nimp (w itself when nimp = 0).
-// cnt, off: nd + nimp + 1 each.
+// The scatter into this context's gas: count, scan, fill, sort, apply (ghip_pairs.h).  Grains [0, nd) are the
+// list's (slots in dust_idx, planes w with stride nd, launched in tree order), [nd, nd + nimp) the imported drag
+// records rec.  cnt, off: nd + nimp + 1 each.
 static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, int nimp, const double *rec,
-                        const double *cw, long long *dcnt, long long *doff, long long *npairs_out)
+                        unsigned long long *dcnt, unsigned long long *doff, long long *npairs_out)
 {
   hipStream_t st = ctx->stream;
   const int m = nd + nimp;
@@ -810,52 +760,41 @@ static int dust_scatter(ghip_ctx *ctx, const DustK &K, int nd, const double *w, 
   const int *didx = P<int>(ctx->dust_idx), *dord = didx + D;
   TreeDev &t = ctx->st;
   const SphNode *nodes = P<SphNode>(t.mq);
+  const int *perm = P<int>(t.perm);
   const double *pos = P<double>(ctx->f[GHIP_F_POS]), *mass = P<double>(ctx->f[GHIP_F_MASS]);
-  const int *type = P<int>(ctx->f[GHIP_F_TYPE]), *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
-  DustGrainLocal gl = {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, nullptr, w + DP_RHO * D};
-  DustGrainRec gr = {rec, DUST_REC_DRAG};
+  const int *tbin = P<int>(ctx->f[GHIP_F_TIMEBIN]);
+  const DustGas gas = {ctx->n, ctx->ngas, pos, mass, P<int>(ctx->f[GHIP_F_TYPE]), tbin};
+  const DustTarget<DustGrainLocal> own = {
+    gas, {didx, pos, P<double>(ctx->f[GHIP_F_HSML]), ctx->n, nullptr, w + DP_RHO * D}, dord, 0};
+  const DustTarget<DustGrainRec> imp = {gas, {rec, DUST_REC_DRAG}, nullptr, nd};
   HIPCHK(hipMemsetAsync(dcnt, 0, (size_t) (m + 1) * 8, st));
   if(ctx->ngas > 0 && nd > 0)
-    k_dust_pairs<0><<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, 0, ctx->n, ctx->ngas, pos, mass, type, tbin,
-                                                 t.nelem, nodes, P<int>(t.perm), K.b, dcnt, nullptr, nullptr,
-                                                 nullptr);
+    k_pairs<0><<<cdiv(nd, 64), 64, 0, st>>>(nd, own, t.nelem, nodes, perm, K.b, dcnt, nullptr, 0ULL, nullptr, nullptr);
   if(ctx->ngas > 0 && nimp > 0)
-    k_dust_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, nd, ctx->n, ctx->ngas, pos, mass, type,
-                                                   tbin, t.nelem, nodes, P<int>(t.perm), K.b, dcnt + D,
-                                                   nullptr, nullptr, nullptr);
+    k_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, imp, t.nelem, nodes, perm, K.b, dcnt + D, nullptr, 0ULL, nullptr,
+                                              nullptr);
   HIPCHK(hipGetLastError());
-  // (counts: never negative, and a sum of 64-bit words has the same bits signed or unsigned)
-  GCHK(ghip_scan(ctx, reinterpret_cast<const unsigned long long *>(dcnt),
-                     reinterpret_cast<unsigned long long *>(doff), m + 1, st));
-  long long npairs = 0;
+  GCHK(ghip_scan<unsigned long long>(ctx, dcnt, doff, m + 1, st));
+  unsigned long long npairs = 0;
   if(ctx->ngas > 0)
     HIPCHK(hipMemcpyAsync(&npairs, doff + m, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));   // the pair count sizes the sort
-  *npairs_out = npairs;
-  if(npairs < 0 || npairs > (long long) INT_MAX)
-    return ghip_fail(ctx, GHIP_EDEVICE, "dust_drag: %lld dust-gas pairs", npairs);
-  if(npairs == 0)
+  *npairs_out = (long long) npairs;
+  const unsigned long long *key;
+  const double *wgt;
+  GCHK(ghip_pairs_fill_sort(ctx, ctx->dust_pairs, (long long) npairs, "dust_drag", "dust-gas", [&](const PairBuf &pb) {
+    if(nd > 0)
+      k_pairs<1><<<cdiv(nd, 64), 64, 0, st>>>(nd, own, t.nelem, nodes, perm, K.b, nullptr, doff, npairs, pb.k0, pb.w0);
+    if(nimp > 0)
+      k_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, imp, t.nelem, nodes, perm, K.b, nullptr, doff + D, npairs, pb.k0,
+                                                pb.w0);
+  }, &key, &wgt));
+  if(!key)
     return GHIP_OK;
-  const size_t np = (size_t) npairs;
-  // dust_pairs: key [np] | key' [np] | W [np] | W' [np]
-  GCHK(ghip_ensure(ctx, ctx->dust_pairs, np * 32 + 256));
-  unsigned long long *k0 = P<unsigned long long>(ctx->dust_pairs), *k1 = k0 + np;
-  double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
-  if(nd > 0)
-    k_dust_pairs<1><<<cdiv(nd, 64), 64, 0, st>>>(nd, dord, gl, 0, ctx->n, ctx->ngas, pos, mass, type, tbin,
-                                                 t.nelem, nodes, P<int>(t.perm), K.b, nullptr, doff, k0, w0);
-  if(nimp > 0)
-    k_dust_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, nullptr, gr, nd, ctx->n, ctx->ngas, pos, mass, type,
-                                                   tbin, t.nelem, nodes, P<int>(t.perm), K.b, nullptr,
-                                                   doff + D, k0, w0);
-  HIPCHK(hipGetLastError());
-  int end_bit = 33;
-  while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
-    end_bit++;
-  GCHK(ghip_sort_pairs(ctx, k0, k1, w0, w1, (int) np, end_bit, st));
-  k_dust_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, m, cw, ctx->n, mass, tbin,
-                                                  P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_ENTROPY]),
-                                                  P<double>(ctx->dust_heat), K);
+  k_dust_apply<<<cdiv((long long) npairs, 256), 256, 0, st>>>((long long) npairs, key, wgt, nd, w, nimp, rec, ctx->n,
+                                                              ctx->ngas, mass, tbin, P<double>(ctx->f[GHIP_F_VEL]),
+                                                              P<double>(ctx->f[GHIP_F_ENTROPY]),
+                                                              P<double>(ctx->dust_heat), K);
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -915,9 +854,9 @@ static int dust_drag_impl(ghip_ctx *ctx, const DustCall &c)
   dust_run_grains(ctx, c);
   HIPCHK(hipGetLastError());
   double *dw = P<double>(ctx->dust_work);
-  long long *dcnt = reinterpret_cast<long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
+  unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(dw + DUST_NPLANES * D), *doff = dcnt + D + 1;
   long long npairs = 0;
-  GCHK(dust_scatter(ctx, dust_k(c.p), ndust, dw, 0, nullptr, dw, dcnt, doff, &npairs));
+  GCHK(dust_scatter(ctx, dust_k(c.p), ndust, dw, 0, nullptr, dcnt, doff, &npairs));
   return dust_download_grains(ctx, c, h);
 }
 
@@ -1176,8 +1115,7 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
             GCHK(dust_run_density(ctx, c));
           HIPCHK(hipGetLastError());
           GCHK(ghip_ensure(ctx, D.du_slot, (size_t) (n > 0 ? n : 1) * 4));
-          k_dust_slots<<<cdiv(nd, 256), 256, 0, st>>>(nd, didx, P<int>(D.du_slot));
-          HIPCHK(hipGetLastError());
+          GCHK(ghip_list_slots(ctx, nd, didx, P<int>(D.du_slot), st));
         }
       D.phase = SELECT;
       return ghip_dd_dust_groups(ctx);
@@ -1255,20 +1193,13 @@ int ghip_dd_dust_step(ghip_ctx *ctx)
       // this shard's grains in list order, then the imported ones in receive order
       const int nimp = D.x.rtotal;
       D.du_recvd = nimp;
-      const int m = nd + nimp;
-      const size_t M = (size_t) m;
-      // du_part: planes [DUST_NPLANES][m] | cnt [m + 1] | off [m + 1]   (64-bit)
-      GCHK(ghip_ensure(ctx, D.du_part, (DUST_NPLANES * M + 2 * (M + 1)) * 8 + 256));
-      double *cw = P<double>(D.du_part);
-      long long *dcnt = reinterpret_cast<long long *>(cw + DUST_NPLANES * M), *doff = dcnt + M + 1;
+      const size_t M = (size_t) nd + (size_t) nimp;
+      // du_part: cnt [M + 1] | off [M + 1]   (64-bit)
+      GCHK(ghip_ensure(ctx, D.du_part, 2 * (M + 1) * 8 + 256));
+      unsigned long long *dcnt = P<unsigned long long>(D.du_part), *doff = dcnt + M + 1;
       const double *rec = nimp > 0 ? P<double>(D.du_recv) : nullptr;
-      if(m > 0)
-        {
-          k_dust_combine<<<cdiv(m, 256), 256, 0, st>>>(nd, nimp, P<double>(ctx->dust_work), rec, cw);
-          HIPCHK(hipGetLastError());
-        }
       long long npairs = 0;
-      GCHK(dust_scatter(ctx, dust_k(p), nd, P<double>(ctx->dust_work), nimp, rec, cw, dcnt, doff, &npairs));
+      GCHK(dust_scatter(ctx, dust_k(p), nd, P<double>(ctx->dust_work), nimp, rec, dcnt, doff, &npairs));
       if(nd > 0)
         {
           std::vector<double> h((size_t) DUST_NPLANES * Dn);

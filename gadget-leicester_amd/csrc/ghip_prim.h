@@ -18,6 +18,13 @@ int ghip_sort_keys(ghip_ctx *ctx, const unsigned long long *kin, unsigned long l
                    hipStream_t st);
 // out = the in[a] with flags[a] != 0, in order; their number -> *dcount (device).  in == nullptr: the indices a
 int ghip_select_flagged(ghip_ctx *ctx, const int *in, const int *flags, int *out, int *dcount, int n, hipStream_t st);
+// A list of particles (a pass's grains, wind particles, ...) in the order of the gravity tree: ord[t] = the list
+// slot whose particle idx[slot] stands t-th in the tree, a sort of gt.iperm[idx[slot]].  All pointers on the
+// device, n words each; key, key2 and slot are scratch
+int ghip_tree_order(ghip_ctx *ctx, int n, const int *idx, unsigned int *key, unsigned int *key2, int *slot, int *ord,
+                    hipStream_t st);
+// slot[idx[a]] = a for the n particles of a list: the list slot by particle index
+int ghip_list_slots(ghip_ctx *ctx, int n, const int *idx, int *slot, hipStream_t st);
 
 // ---- out of one-wavefront workgroups (why: ghip_prim.hip), PRIM_BLOCK items each ----
 #define PRIM_ITEMS 16

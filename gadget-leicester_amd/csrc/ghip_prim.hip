@@ -69,6 +69,44 @@ int ghip_sort_keys(ghip_ctx *ctx, const unsigned long long *kin, unsigned long l
   });
 }
 
+// sort key of list slot a: the place of its particle in the gravity tree
+__global__ void k_list_order_keys(int n, const int *__restrict__ idx, const int *__restrict__ iperm,
+                                  unsigned int *__restrict__ key, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= n)
+    return;
+  key[a] = (unsigned int) iperm[idx[a]];
+  slot[a] = a;
+}
+
+int ghip_tree_order(ghip_ctx *ctx, int n, const int *idx, unsigned int *key, unsigned int *key2, int *slot, int *ord,
+                    hipStream_t st)
+{
+  k_list_order_keys<<<cdiv(n, 256), 256, 0, st>>>(n, idx, P<int>(ctx->gt.iperm), key, slot);
+  HIPCHK(hipGetLastError());
+  // (sorted positions of a shard's merged tree run up to its local particles + imported elements)
+  const long long nsorted = ctx->gt.n > ctx->n ? ctx->gt.n : ctx->n;
+  int end_bit = 1;
+  while(end_bit < 32 && (1LL << end_bit) <= nsorted)
+    end_bit++;
+  return ghip_sort_pairs(ctx, key, key2, slot, ord, n, end_bit, st);
+}
+
+__global__ void k_list_slots(int n, const int *__restrict__ idx, int *__restrict__ slot)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < n)
+    slot[idx[a]] = a;
+}
+
+int ghip_list_slots(ghip_ctx *ctx, int n, const int *idx, int *slot, hipStream_t st)
+{
+  k_list_slots<<<cdiv(n, 256), 256, 0, st>>>(n, idx, slot);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
 int ghip_select_flagged(ghip_ctx *ctx, const int *in, const int *flags, int *out, int *dcount, int n, hipStream_t st)
 {
   auto from = [&](auto src) {

@@ -17,9 +17,9 @@
 // particle moves at most 0.2 Hsml per iteration, which is less than the width of the leaves its lanes share,
 // and a re-sort would cost a sort per iteration, about what the density pass costs.
 //
-// The scatter into the gas: the pairs (gas j, wind slot a) are counted in the density pass, written as 64-bit
-// keys (j << 32 | a) with their kernel weight, radix sorted, and one thread per gas particle adds its run of
-// pairs in list order.  No floating-point atomics; every sum is a per-thread loop in a fixed order: two
+// The scatter into the gas is the ordered pair scatter of ghip_pairs.h: the pairs are counted in
+// the density pass; this file gives the scatter the wind-gas pair (WindOwn, WindImp) and what a gas particle adds
+// from its run (k_wind_apply).  No floating-point atomics; every sum is a per-thread loop in a fixed order: two
 // identical calls give identical bits, whatever the launch order of the list.
 //
 // ONE DELIBERATE DEVIATION from the C text (tests/wind_ref.py takes it too): when the time cap of
@@ -27,19 +27,16 @@
 // dt_jump = 0.  The reference recomputes dt1 = dr * U / C * FBV (:348) and subtracts it (:371-372); the residue
 // of that round trip is 0 or +-1 ulp, and on its sign hangs one more iteration of length ~1e-17.
 //
-// no a*b+c -> fma contraction in this file (before the headers, so that their inline functions follow): every
-// comparison below decides with the C text's own roundings.
+// no a*b+c -> fma contraction in this file (before the headers, so that their inline functions and the templates
+// of ghip_pairs.h follow): every comparison below decides with the C text's own roundings.
 #pragma clang fp contract(off)
 
 #include <chrono>
-#include <climits>
 
-#include "ghip_ngb.h"
-#include "ghip_prim.h"
+#include "ghip_pairs.h"
 
 #define WIND_C 2.9979e10          // allvars.h:86
 #define WIND_THOMPSON 6.65245e-25 // allvars.h:91
-#define WIND_LEAF 16              // a tree node with at most this many particles is swept flat
 
 // per-particle planes of wind_work ([WIND_NPLANES][nw] doubles, list order)
 enum
@@ -104,17 +101,6 @@ __global__ void k_wind_hmax(int ngas, const double *__restrict__ hsml, const dou
     }
   if((threadIdx.x & 63) == 0 && b)
     atomicMax(&words->hmax, b);
-}
-
-// sort key of list slot a: its place in the gravity tree
-__global__ void k_wind_order_keys(int nw, const int *__restrict__ idx, const int *__restrict__ iperm,
-                                  unsigned int *__restrict__ key, int *__restrict__ slot)
-{
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if(a >= nw)
-    return;
-  key[a] = (unsigned int) iperm[idx[a]];
-  slot[a] = a;
 }
 
 // the velocity planes of the list; a particle that is not Type 3 raises words->err
@@ -196,83 +182,144 @@ __global__ void k_wind_reset(int nw, double *__restrict__ w)   // virtual_densit
   w[(size_t) WP_DRMIN * nw + a] = 1.e40;
 }
 
-// One candidate of ngb_treefind_virtual_active (virtual_density.c:650-664) and the pair geometry of
-// virtual_evaluate_select (:495-524): a gas particle of this context with Mass > 0 within the wind particle's
-// own h; r and the gas particle's h_j come back.  The nearest image is the text's two comparisons per axis
-// (d_wrap, ghip_ngb.h).
-__device__ __forceinline__ bool d_wind_pair(int j, int n, int ngas, const double *__restrict__ pos,
-                                            const double *__restrict__ hsml, const double *__restrict__ mass,
-                                            const int *__restrict__ type, double px, double py, double pz, double h,
-                                            const BoxK b, double &r, double &hj)
+// The gas side of a wind-gas pair, and the base of the two targets below.  near(): one candidate of
+// ngb_treefind_virtual_active (virtual_density.c:650-664) and the pair geometry of virtual_evaluate_select
+// (:495-524): a gas particle of this context with Mass > 0 within the wind particle's own h; r and the gas
+// particle's h_j and mass come back.  The nearest image is the text's two comparisons per axis (d_wrap, ghip_ngb.h).
+// pair(): the pairs of virtual_evaluate_onthespot (virtual_spread_momentum.c:129-130, 393-419), u = r / h_j < 1,
+// with their kernel weight -- what k_pairs (ghip_pairs.h) counts and writes.
+struct WindGas
 {
-  if(j < 0 || j >= ngas || type[j] != 0 || !(mass[j] > 0))
-    return false;
-  const double dx = d_wrap(px - pos[j], b), dy = d_wrap(py - pos[(size_t) n + j], b),
-               dz = d_wrap(pz - pos[2 * (size_t) n + j], b);
-  const double r2 = dx * dx + dy * dy + dz * dz;
-  if(r2 > h * h)
-    return false;
-  r = sqrt(r2);
-  hj = hsml[j];
-  return true;
-}
-
-// Where target t of a neighbour pass comes from.  Own (rec == nullptr): list slot a = list[t] of this context's
-// wind particles, position and radius resident at idx[a], the planes w.  Imported (GHIP_DD_WIND): record t of
-// another shard's particles, {Pos, Hsml} in rec [4], and for the spread pass {NewDensity, DeltaPhotonMomentum,
-// Vel, |Vel|} in srec [6]; its slot in the pair keys is nw + t, behind the own ones.
-#define WIND_REC_DENS 4
-#define WIND_REC_SPREAD 6
-struct WindTgt
-{
-  const int *list, *idx;
-  const double *rec, *srec;
+  int n, ngas;
+  const double *pos, *hsml, *mass;
+  const int *type;
+  const WindWords *words;
+  __device__ __forceinline__ bool near(int j, double px, double py, double pz, double h, const BoxK b, double &r,
+                                       double &hj, double &mj) const
+  {
+    if(j < 0 || j >= ngas || type[j] != 0 || !((mj = mass[j]) > 0))
+      return false;
+    const double dx = d_wrap(px - pos[j], b), dy = d_wrap(py - pos[(size_t) n + j], b),
+                 dz = d_wrap(pz - pos[2 * (size_t) n + j], b);
+    const double r2 = dx * dx + dy * dy + dz * dz;
+    if(r2 > h * h)
+      return false;
+    r = sqrt(r2);
+    hj = hsml[j];
+    return true;
+  }
+  __device__ __forceinline__ bool pair(int j, double px, double py, double pz, double h, const BoxK b, double &wk) const
+  {
+    double r, hj, mj;
+    if(!near(j, px, py, pz, h, b, r, hj, mj))
+      return false;
+    const double u = r / hj;
+    if(!(u < 1))
+      return false;
+    const double hinv = 1 / hj;
+    wk = d_spline_wk(u, hinv * hinv * hinv);
+    return true;
+  }
+  __device__ __forceinline__ double hmax() const { return __longlong_as_double((long long) words->hmax); }
 };
 
-// virtual_evaluate_select for the m targets: those with dt_jump > 0 are evaluated, the others reset (an imported
-// record has dt_jump > 0, or it would not have been sent).  Own targets write the planes, imported ones
-// part[2 t] = the sum, part[2 t + 1] = drmin over THIS context's gas.  cnt != nullptr: cnt[t] = the pairs the
-// spread pass will write for the t-th particle (u < 1, and none where new_density comes out 0).
+// Where target t of a neighbour pass comes from.  place(): its slot in the pair keys and, where it takes part in a
+// density pass, its position and radius.  get(): the same for the spread pass (a Target of k_pairs), which no
+// particle with new_density = 0 takes part in; the walk searches min(h, hmax), see k_wind_hmax.  put(): where the
+// density pass leaves its two results.
+// Own: list slot list[t] of this context's wind particles, position and radius resident at idx[slot], the planes w;
+// takes part with dt_jump > 0, and is reset otherwise.
+struct WindOwn : WindGas
+{
+  const int *list, *idx;
+  int nw;
+  double *w;
+  __device__ __forceinline__ bool place(int t, int &slot, double &x, double &y, double &z, double &h) const
+  {
+    slot = list[t];
+    if(!(w[WP_DTJ * (size_t) nw + slot] > 0.))
+      return false;
+    const int i = idx[slot];
+    x = pos[i];
+    y = pos[(size_t) n + i];
+    z = pos[2 * (size_t) n + i];
+    h = hsml[i];
+    return true;
+  }
+  __device__ __forceinline__ bool get(int t, int &slot, double &x, double &y, double &z, double &h, double &rs) const
+  {
+    if(!(w[WP_RHO * (size_t) nw + list[t]] > 0.) || !place(t, slot, x, y, z, h))
+      return false;
+    rs = fmin(h, hmax());
+    return true;
+  }
+  __device__ __forceinline__ void put(int, int slot, double rho, double drmin) const
+  {
+    w[WP_RHO * (size_t) nw + slot] = rho;
+    w[WP_DRMIN * (size_t) nw + slot] = drmin;
+  }
+};
+
+// Imported (GHIP_DD_WIND): record t of another shard's particles, {Pos, Hsml} in rec [4], and for the spread pass
+// {NewDensity, DeltaPhotonMomentum, Vel, |Vel|} in srec [6]; its slot in the pair keys is nw + t, behind the own
+// ones.  It has dt_jump > 0, or it would not have been sent.  The density pass leaves part[2 t] = the sum,
+// part[2 t + 1] = drmin over THIS context's gas.
+#define WIND_REC_DENS 4
+#define WIND_REC_SPREAD 6
+struct WindImp : WindGas
+{
+  const double *rec, *srec;
+  int nw;
+  double *part;
+  __device__ __forceinline__ bool place(int t, int &slot, double &x, double &y, double &z, double &h) const
+  {
+    const double *q = rec + WIND_REC_DENS * (size_t) t;
+    slot = nw + t;
+    x = q[0];
+    y = q[1];
+    z = q[2];
+    h = q[3];
+    return true;
+  }
+  __device__ __forceinline__ bool get(int t, int &slot, double &x, double &y, double &z, double &h, double &rs) const
+  {
+    if(!(srec[WIND_REC_SPREAD * (size_t) t] > 0.) || !place(t, slot, x, y, z, h))
+      return false;
+    rs = fmin(h, hmax());
+    return true;
+  }
+  __device__ __forceinline__ void put(int t, int, double rho, double drmin) const
+  {
+    part[2 * (size_t) t] = rho;
+    part[2 * (size_t) t + 1] = drmin;
+  }
+};
+
+// virtual_evaluate_select for the m targets T (WindOwn or WindImp): those that take part are evaluated, the others
+// reset.  cnt != nullptr: cnt[t] = the pairs the spread pass will write for the t-th target (u < 1, and none where
+// new_density comes out 0).
+template <class Target>
 __global__ void __launch_bounds__(64)
-k_wind_density(int m, WindTgt T, double *__restrict__ part, int n, int ngas,
-               const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
-               const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
-               const int *__restrict__ perm, BoxK b, int nw, double *__restrict__ w,
-               unsigned long long *__restrict__ cnt, const WindWords *__restrict__ words)
+k_wind_density(int m, Target T, int nelem, const SphNode *__restrict__ nodes, const int *__restrict__ perm, BoxK b,
+               unsigned long long *__restrict__ cnt)
 {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if(t >= m)
     return;
-  const int a = T.rec ? 0 : T.list[t];
-  const size_t D = (size_t) nw;
+  int slot;
+  double px, py, pz, h;
   double rho = 0., drmin = 1.e40;
   unsigned long long c = 0;
-  if(T.rec || w[WP_DTJ * D + a] > 0.)
+  if(T.place(t, slot, px, py, pz, h))
     {
-      double px, py, pz, h;
-      if(T.rec)
-        {
-          px = T.rec[WIND_REC_DENS * (size_t) t];
-          py = T.rec[WIND_REC_DENS * (size_t) t + 1];
-          pz = T.rec[WIND_REC_DENS * (size_t) t + 2];
-          h = T.rec[WIND_REC_DENS * (size_t) t + 3];
-        }
-      else
-        {
-          const int i = T.idx[a];
-          px = pos[i];
-          py = pos[(size_t) n + i];
-          pz = pos[2 * (size_t) n + i];
-          h = hsml[i];
-        }
       // every pair with u < 1 has r < h_j <= hmax: this walk meets them all, in the order the walk of the whole
       // sphere h would (its nodes are a subset in the same pre-order)
-      const double hmax = __longlong_as_double((long long) words->hmax);
+      const double hmax = T.hmax();
       const double r1 = fmin(h, hmax);
-      d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
-        double r, hj;
+      d_ngb_walk_thread<PAIR_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
+        double r, hj, mj;
         const int j = perm[p];
-        if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
+        if(!T.near(j, px, py, pz, h, b, r, hj, mj))
           return;
         const double drcheck = fabs(r - hj) + 0.25 * hj;   // :519-520
         if(drcheck < drmin)
@@ -281,7 +328,7 @@ k_wind_density(int m, WindTgt T, double *__restrict__ part, int n, int ngas,
         if(u < 1)
           {
             const double hinv = 1 / hj;
-            rho += mass[j] * d_spline_wk(u, hinv * hinv * hinv);
+            rho += mj * d_spline_wk(u, hinv * hinv * hinv);
             c++;
           }
       });
@@ -291,10 +338,10 @@ k_wind_density(int m, WindTgt T, double *__restrict__ part, int n, int ngas,
         {
           const double r2 = fmin(h, (drmin + 0.75 * hmax) * (1. + 1.e-9));
           if(r2 > r1)
-            d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r2, b, [&](int p) {
-              double r, hj;
+            d_ngb_walk_thread<PAIR_LEAF>(GasElems{nodes}, nelem, px, py, pz, r2, b, [&](int p) {
+              double r, hj, mj;
               const int j = perm[p];
-              if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
+              if(!T.near(j, px, py, pz, h, b, r, hj, mj))
                 return;
               const double drcheck = fabs(r - hj) + 0.25 * hj;
               if(drcheck < drmin)
@@ -302,80 +349,9 @@ k_wind_density(int m, WindTgt T, double *__restrict__ part, int n, int ngas,
             });
         }
     }
-  if(T.rec)
-    {
-      part[2 * (size_t) t] = rho;
-      part[2 * (size_t) t + 1] = drmin;
-    }
-  else
-    {
-      w[WP_RHO * D + a] = rho;
-      w[WP_DRMIN * D + a] = drmin;
-    }
+  T.put(t, slot, rho, drmin);
   if(cnt)
     cnt[t] = rho > 0. ? c : 0;
-}
-
-// the pairs of virtual_evaluate_onthespot (virtual_spread_momentum.c:129-130, 393-419) for the m particles of
-// m targets.  fill == 0: count them into cnt[t]; fill == 1: write (j << 32 | slot, W) from off[t] on.
-template <int fill>
-__global__ void __launch_bounds__(64)
-k_wind_pairs(int m, WindTgt T, int n, int ngas,
-             const double *__restrict__ pos, const double *__restrict__ hsml, const double *__restrict__ mass,
-             const int *__restrict__ type, int nelem, const SphNode *__restrict__ nodes,
-             const int *__restrict__ perm, BoxK b, int nw, const double *__restrict__ w,
-             unsigned long long *__restrict__ cnt, const unsigned long long *__restrict__ off,
-             unsigned long long npairs, unsigned long long *__restrict__ key, double *__restrict__ wgt,
-             const WindWords *__restrict__ words)
-{
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if(t >= m)
-    return;
-  const int a = T.rec ? nw + t : T.list[t];   // the slot of the pair keys
-  const size_t D = (size_t) nw;
-  unsigned long long c = 0;
-  if(T.rec ? T.srec[WIND_REC_SPREAD * (size_t) t] > 0. : (w[WP_RHO * D + a] > 0. && w[WP_DTJ * D + a] > 0.))
-    {
-      const unsigned long long o = fill ? off[t] : 0;
-      double px, py, pz, h;
-      if(T.rec)
-        {
-          px = T.rec[WIND_REC_DENS * (size_t) t];
-          py = T.rec[WIND_REC_DENS * (size_t) t + 1];
-          pz = T.rec[WIND_REC_DENS * (size_t) t + 2];
-          h = T.rec[WIND_REC_DENS * (size_t) t + 3];
-        }
-      else
-        {
-          const int i = T.idx[a];
-          px = pos[i];
-          py = pos[(size_t) n + i];
-          pz = pos[2 * (size_t) n + i];
-          h = hsml[i];
-        }
-      const double r1 = fmin(h, __longlong_as_double((long long) words->hmax));   // (as k_wind_density)
-      d_ngb_walk_thread<WIND_LEAF>(GasElems{nodes}, nelem, px, py, pz, r1, b, [&](int p) {
-        double r, hj;
-        const int j = perm[p];
-        if(!d_wind_pair(j, n, ngas, pos, hsml, mass, type, px, py, pz, h, b, r, hj))
-          return;
-        const double u = r / hj;
-        if(!(u < 1))
-          return;
-        if(fill)
-          {
-            if(o + c < npairs)   // (the count of the same walk: never false)
-              {
-                const double hinv = 1 / hj;
-                key[o + c] = ((unsigned long long) j << 32) | (unsigned int) a;
-                wgt[o + c] = d_spline_wk(u, hinv * hinv * hinv);
-              }
-          }
-        c++;
-      });
-    }
-  if(!fill)
-    cnt[t] = c;
 }
 
 // the momentum one gas particle receives from its run of sorted pairs, in slot order: the own wind particles in
@@ -387,46 +363,40 @@ __global__ void k_wind_apply(long long npairs, const unsigned long long *__restr
                              double *__restrict__ inj)
 {
   const long long s0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-  if(s0 >= npairs)
-    return;
-  const unsigned int j = (unsigned int) (key[s0] >> 32);
-  if(s0 > 0 && (unsigned int) (key[s0 - 1] >> 32) == j)
-    return;   // not the first pair of its gas particle
-  if(j >= (unsigned int) ngas)
+  unsigned int j;
+  if(!d_pair_run_head(s0, npairs, key, ngas, j))
     return;
   const size_t D = (size_t) nw, G = (size_t) ngas;
   const double mj = mass[j];
   double i0 = inj[j], i1 = inj[G + j], i2 = inj[2 * G + j];
-  for(long long s = s0; s < npairs && (unsigned int) (key[s] >> 32) == j; s++)
-    {
-      const unsigned int a = (unsigned int) (key[s] & 0xffffffffULL);
-      if(a >= (unsigned int) nw + (unsigned int) nimp)
-        continue;
-      double rho, dmom, v0, v1, v2, va;
-      if(a < (unsigned int) nw)
-        {
-          rho = w[WP_RHO * D + a];
-          dmom = w[WP_DMOM * D + a];
-          v0 = w[WP_VX * D + a];
-          v1 = w[WP_VY * D + a];
-          v2 = w[WP_VZ * D + a];
-          va = w[WP_VABS * D + a];
-        }
-      else
-        {
-          const double *q = srec + WIND_REC_SPREAD * (size_t) (a - (unsigned int) nw);
-          rho = q[0];
-          dmom = q[1];
-          v0 = q[2];
-          v1 = q[3];
-          v2 = q[4];
-          va = q[5];
-        }
-      const double ddpm = dmom * mj * wgt[s] / rho;
-      i0 += ddpm * v0 / va;
-      i1 += ddpm * v1 / va;
-      i2 += ddpm * v2 / va;
-    }
+  d_pair_run(s0, npairs, key, wgt, j, [&](unsigned int a, double wk) {
+    if(a >= (unsigned int) nw + (unsigned int) nimp)
+      return;
+    double rho, dmom, v0, v1, v2, va;
+    if(a < (unsigned int) nw)
+      {
+        rho = w[WP_RHO * D + a];
+        dmom = w[WP_DMOM * D + a];
+        v0 = w[WP_VX * D + a];
+        v1 = w[WP_VY * D + a];
+        v2 = w[WP_VZ * D + a];
+        va = w[WP_VABS * D + a];
+      }
+    else
+      {
+        const double *q = srec + WIND_REC_SPREAD * (size_t) (a - (unsigned int) nw);
+        rho = q[0];
+        dmom = q[1];
+        v0 = q[2];
+        v1 = q[3];
+        v2 = q[4];
+        va = q[5];
+      }
+    const double ddpm = dmom * mj * wk / rho;
+    i0 += ddpm * v0 / va;
+    i1 += ddpm * v1 / va;
+    i2 += ddpm * v2 / va;
+  });
   inj[j] = i0;
   inj[G + j] = i1;
   inj[2 * G + j] = i2;
@@ -650,6 +620,14 @@ static WindDev wind_dev(ghip_ctx *ctx, int nw)
   return d;
 }
 
+// the tree order of the list d.idx into d.ord (key, key', slot: the three words behind them)
+static int wind_tree_order(ghip_ctx *ctx, const WindDev &d, hipStream_t st)
+{
+  const size_t D = (size_t) d.nw;
+  unsigned int *key = reinterpret_cast<unsigned int *>(d.idx + 2 * D);
+  return ghip_tree_order(ctx, d.nw, d.idx, key, key + D, d.idx + 4 * D, d.ord, st);
+}
+
 // What every entry point asks of the context; then the list to the device, its tree order into `ord`, the
 // velocity planes, and words->err raised where an index does not name a Type-3 particle
 static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const int *idx, const char *who, WindDev *out)
@@ -675,15 +653,7 @@ static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const in
   *out = d;
   HIPCHK(hipMemcpyAsync(d.idx, idx, D * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d.words, 0, sizeof(WindWords), st));
-  unsigned int *dkey = reinterpret_cast<unsigned int *>(d.idx + 2 * D), *dkey2 = dkey + D;
-  int *dslot = d.idx + 4 * D;
-  k_wind_order_keys<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->gt.iperm), dkey, dslot);
-  HIPCHK(hipGetLastError());
-  const long long nsorted = ctx->gt.n > ctx->n ? ctx->gt.n : ctx->n;
-  int end_bit = 1;
-  while(end_bit < 32 && (1LL << end_bit) <= nsorted)
-    end_bit++;
-  GCHK(ghip_sort_pairs(ctx, dkey, dkey2, dslot, d.ord, nw, end_bit, st));
+  GCHK(wind_tree_order(ctx, d, st));
   k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
                                             P<double>(ctx->f[GHIP_F_VEL]), d.w, d.words);
   if(ctx->ngas > 0)
@@ -726,42 +696,46 @@ static int wind_rad_accel(ghip_ctx *ctx, const char *who)
   return wind_gas_field(ctx, ctx->wind_ra, &ctx->wind_ra_ngas, "RadAccel", "ghip_wind_set_rad_accel", who);
 }
 
-// the resident fields and tree of the gas as the kernels take them
-#define WIND_GAS_ARGS                                                                                         \
-  ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),                           \
-    P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), ctx->ngas > 0 ? ctx->st.nelem : 0,           \
-    P<SphNode>(ctx->st.mq), P<int>(ctx->st.perm)
+// the resident fields of the gas as the targets take them, and its tree as the kernels do
+static WindGas wind_gas(ghip_ctx *ctx, const WindDev &d)
+{
+  return WindGas{ctx->n, ctx->ngas, P<double>(ctx->f[GHIP_F_POS]), P<double>(ctx->f[GHIP_F_HSML]),
+                 P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_TYPE]), d.words};
+}
+#define WIND_TREE_ARGS ctx->ngas > 0 ? ctx->st.nelem : 0, P<SphNode>(ctx->st.mq), P<int>(ctx->st.perm)
+
+// the particles of `list` (slots of this context's list) / the imported records of GHIP_DD_WIND as targets
+static WindOwn wind_own(ghip_ctx *ctx, const WindDev &d, const int *list)
+{
+  return WindOwn{wind_gas(ctx, d), list, d.idx, d.nw, d.w};
+}
+static WindImp wind_imp(ghip_ctx *ctx, const WindDev &d, const double *rec, const double *srec, double *part)
+{
+  return WindImp{wind_gas(ctx, d), rec, srec, d.nw, part};
+}
 
 // The scatter of the m particles of `list` (cnt[0, m) counted, cnt[m] = 0, scanned into off; npairs = off[m]):
 // fill, sort, apply.  GHIP_DD_WIND: behind them the nimp imported records of `imp`, counted and scanned behind the
 // own ones (off[m .. m + nimp], npairs = off[m + nimp])
 static int wind_scatter(ghip_ctx *ctx, const WindDev &d, const BoxK &b, int m, const int *list, long long npairs,
-                        const unsigned long long *off = nullptr, int nimp = 0, const WindTgt *imp = nullptr)
+                        const unsigned long long *off = nullptr, int nimp = 0, const WindImp *imp = nullptr)
 {
   if(!off)
     off = d.off;
-  if(npairs < 0 || npairs > (long long) INT_MAX)
-    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_wind: %lld wind-gas pairs", npairs);
-  if(npairs == 0 || m + nimp == 0)
-    return GHIP_OK;
   hipStream_t st = ctx->stream;
-  const size_t np = (size_t) npairs;
-  // wind_pairs: key [np] | key' [np] | W [np] | W' [np]
-  GCHK(ghip_ensure(ctx, ctx->wind_pairs, np * 32 + 256));
-  unsigned long long *k0 = P<unsigned long long>(ctx->wind_pairs), *k1 = k0 + np;
-  double *w0 = reinterpret_cast<double *>(k1 + np), *w1 = w0 + np;
-  if(m > 0)
-    k_wind_pairs<1><<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{list, d.idx, nullptr, nullptr}, WIND_GAS_ARGS, b, d.nw, d.w,
-                                                nullptr, off, (unsigned long long) npairs, k0, w0, d.words);
-  if(nimp > 0)
-    k_wind_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, *imp, WIND_GAS_ARGS, b, d.nw, d.w, nullptr, off + m,
-                                                   (unsigned long long) npairs, k0, w0, d.words);
-  HIPCHK(hipGetLastError());
-  int end_bit = 33;
-  while(end_bit < 64 && (1LL << (end_bit - 32)) <= (long long) ctx->ngas)
-    end_bit++;
-  GCHK(ghip_sort_pairs(ctx, k0, k1, w0, w1, (int) np, end_bit, st));
-  k_wind_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, k1, w1, d.nw, d.w, nimp, imp ? imp->srec : nullptr,
+  const unsigned long long *key;
+  const double *wgt;
+  GCHK(ghip_pairs_fill_sort(ctx, ctx->wind_pairs, npairs, "ghip_wind", "wind-gas", [&](const PairBuf &pb) {
+    if(m > 0)
+      k_pairs<1><<<cdiv(m, 64), 64, 0, st>>>(m, wind_own(ctx, d, list), WIND_TREE_ARGS, b, nullptr, off,
+                                             (unsigned long long) npairs, pb.k0, pb.w0);
+    if(nimp > 0)
+      k_pairs<1><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, *imp, WIND_TREE_ARGS, b, nullptr, off + m,
+                                                (unsigned long long) npairs, pb.k0, pb.w0);
+  }, &key, &wgt));
+  if(!key)
+    return GHIP_OK;
+  k_wind_apply<<<cdiv(npairs, 256), 256, 0, st>>>(npairs, key, wgt, d.nw, d.w, nimp, imp ? imp->srec : nullptr,
                                                   P<double>(ctx->f[GHIP_F_MASS]), ctx->ngas, P<double>(ctx->wind_inj));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
@@ -814,8 +788,8 @@ extern "C" int ghip_wind_density(ghip_ctx *ctx, const ghip_wind_params *p, int n
   hipStream_t st = ctx->stream;
   const size_t D = (size_t) nwind;
   HIPCHK(hipMemcpyAsync(d.w + WP_DTJ * D, dt_jump, D * 8, hipMemcpyHostToDevice, st));
-  k_wind_density<<<cdiv(nwind, 64), 64, 0, st>>>(nwind, WindTgt{d.ord, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS,
-                                                 make_box(p->BoxSize, p->periodic), nwind, d.w, nullptr, d.words);
+  k_wind_density<<<cdiv(nwind, 64), 64, 0, st>>>(nwind, wind_own(ctx, d, d.ord), WIND_TREE_ARGS,
+                                                 make_box(p->BoxSize, p->periodic), nullptr);
   HIPCHK(hipGetLastError());
   WindWords h;
   HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -851,10 +825,10 @@ extern "C" int ghip_wind_spread(ghip_ctx *ctx, const ghip_wind_params *p, int nw
   HIPCHK(hipMemcpyAsync(d.w + WP_RHO * D, new_density, D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(d.w + WP_DMOM * D, delta_momentum, D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d.cnt, 0, (D + 1) * 8, st));
-  k_wind_pairs<0><<<cdiv(nwind, 64), 64, 0, st>>>(nwind, WindTgt{d.ord, d.idx, nullptr, nullptr}, WIND_GAS_ARGS, b, nwind,
-                                                  d.w, d.cnt, nullptr, 0ULL, nullptr, nullptr, d.words);
+  k_pairs<0><<<cdiv(nwind, 64), 64, 0, st>>>(nwind, wind_own(ctx, d, d.ord), WIND_TREE_ARGS, b, d.cnt, nullptr, 0ULL,
+                                             nullptr, nullptr);
   HIPCHK(hipGetLastError());
-  GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, nwind + 1, st));
+  GCHK(ghip_scan<unsigned long long>(ctx, d.cnt, d.off, nwind + 1, st));
   k_wind_npairs<<<1, 64, 0, st>>>(d.off, nwind, d.words);
   HIPCHK(hipGetLastError());
   WindWords h;
@@ -954,8 +928,7 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
     return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, m, nw);
   k_wind_reset<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.w);
   if(m > 0)
-    k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{cur, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, K.b, nw,
-                                               d.w, nullptr, d.words);
+    k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, wind_own(ctx, d, cur), WIND_TREE_ARGS, K.b, nullptr);
   HIPCHK(hipGetLastError());
 
   // ---- :307-490 ----
@@ -980,10 +953,9 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
       HIPCHK(hipEventRecord(ev[1], st));
       HIPCHK(hipMemsetAsync(d.cnt + m, 0, 8, st));
       if(m > 0)
-        k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{cur, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, K.b,
-                                                   nw, d.w, d.cnt, d.words);
+        k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, wind_own(ctx, d, cur), WIND_TREE_ARGS, K.b, d.cnt);
       HIPCHK(hipGetLastError());
-      GCHK(ghip_scan(ctx, (const unsigned long long *) d.cnt, d.off, m + 1, st));
+      GCHK(ghip_scan<unsigned long long>(ctx, d.cnt, d.off, m + 1, st));
       k_wind_npairs<<<1, 64, 0, st>>>(d.off, m, d.words);
       HIPCHK(hipEventRecord(ev[2], st));
       if(m > 0)
@@ -1165,13 +1137,6 @@ int ghip_dd_wind_status(ghip_ctx *ctx, const char *what, double *extra);
 int ghip_dd_wind_select(ghip_ctx *ctx, int m, const int *list, const int *idx, const double *dtj, const double *drmin,
                         int cut, double hmax, double boxsize, int periodic, int *total);
 
-__global__ void k_wind_slots(int nw, const int *__restrict__ idx, int *__restrict__ slot)
-{
-  const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if(a < nw)
-    slot[idx[a]] = a;
-}
-
 // record r of the send lists: local particle list[r], list slot slot[list[r]].  K = WIND_REC_DENS: {Pos, Hsml};
 // K = WIND_REC_SPREAD: {NewDensity, DeltaPhotonMomentum, Vel, |Vel|} from the planes
 template <int K>
@@ -1332,8 +1297,7 @@ static int wind_dd_density_send(ghip_ctx *ctx, int next_phase)
   GCHK(wind_dd_mark(ctx, 2));
   if(m > 0 && !spread_only)
     {
-      k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, WindTgt{list, d.idx, nullptr, nullptr}, nullptr, WIND_GAS_ARGS, b, d.nw,
-                                                 d.w, nullptr, d.words);
+      k_wind_density<<<cdiv(m, 64), 64, 0, st>>>(m, wind_own(ctx, d, list), WIND_TREE_ARGS, b, nullptr);
       HIPCHK(hipGetLastError());
     }
   GCHK(wind_dd_mark(ctx, 3));
@@ -1453,19 +1417,11 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       if(nw > 0)
         {
           HIPCHK(hipMemcpyAsync(d.idx, W.a.wind_idx, Dn * 4, hipMemcpyHostToDevice, st));
-          unsigned int *dkey = reinterpret_cast<unsigned int *>(d.idx + 2 * Dn), *dkey2 = dkey + Dn;
-          int *dslot = d.idx + 4 * Dn;
-          k_wind_order_keys<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->gt.iperm), dkey, dslot);
-          HIPCHK(hipGetLastError());
-          const long long nsorted = ctx->gt.n > n ? ctx->gt.n : n;
-          int end_bit = 1;
-          while(end_bit < 32 && (1LL << end_bit) <= nsorted)
-            end_bit++;
-          GCHK(ghip_sort_pairs(ctx, dkey, dkey2, dslot, d.ord, nw, end_bit, st));
+          GCHK(wind_tree_order(ctx, d, st));
           k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, n, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
                                                     d.w, d.words);
-          k_wind_slots<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(D.du_slot));
           HIPCHK(hipGetLastError());
+          GCHK(ghip_list_slots(ctx, nw, d.idx, P<int>(D.du_slot), st));
         }
       if(ctx->ngas > 0)
         k_wind_hmax<<<cdiv(ctx->ngas, 256), 256, 0, st>>>(ctx->ngas, P<double>(ctx->f[GHIP_F_HSML]),
@@ -1563,8 +1519,8 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       GCHK(wind_dd_mark(ctx, 4));
       if(nimp > 0)
         {
-          k_wind_density<<<cdiv(nimp, 64), 64, 0, st>>>(nimp, WindTgt{nullptr, nullptr, P<double>(D.du_recv), nullptr},
-                                                        P<double>(D.du_part), WIND_GAS_ARGS, b, d.nw, d.w, nullptr, d.words);
+          k_wind_density<<<cdiv(nimp, 64), 64, 0, st>>>(
+            nimp, wind_imp(ctx, d, P<double>(D.du_recv), nullptr, P<double>(D.du_part)), WIND_TREE_ARGS, b, nullptr);
           HIPCHK(hipGetLastError());
         }
       int sc[GHIP_MAXRANKS], so[GHIP_MAXRANKS];
@@ -1689,18 +1645,16 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       const size_t M = (size_t) m + (size_t) nimp;
       GCHK(ghip_ensure(ctx, D.wd_cnt, 2 * (M + 1) * 8));
       unsigned long long *cnt = P<unsigned long long>(D.wd_cnt), *off = cnt + M + 1;
-      const WindTgt own = {wind_dd_list(d, W), d.idx, nullptr, nullptr};
-      const WindTgt imp = {nullptr, nullptr, P<double>(D.du_recv), P<double>(D.wd_srecv)};
+      const WindOwn own = wind_own(ctx, d, wind_dd_list(d, W));
+      const WindImp imp = wind_imp(ctx, d, P<double>(D.du_recv), P<double>(D.wd_srecv), nullptr);
       GCHK(wind_dd_mark(ctx, 4));
       HIPCHK(hipMemsetAsync(cnt, 0, (M + 1) * 8, st));
       if(m > 0)
-        k_wind_pairs<0><<<cdiv(m, 64), 64, 0, st>>>(m, own, WIND_GAS_ARGS, b, d.nw, d.w, cnt, nullptr, 0ULL, nullptr, nullptr,
-                                                    d.words);
+        k_pairs<0><<<cdiv(m, 64), 64, 0, st>>>(m, own, WIND_TREE_ARGS, b, cnt, nullptr, 0ULL, nullptr, nullptr);
       if(nimp > 0)
-        k_wind_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, imp, WIND_GAS_ARGS, b, d.nw, d.w, cnt + m, nullptr, 0ULL, nullptr,
-                                                       nullptr, d.words);
+        k_pairs<0><<<cdiv(nimp, 64), 64, 0, st>>>(nimp, imp, WIND_TREE_ARGS, b, cnt + m, nullptr, 0ULL, nullptr, nullptr);
       HIPCHK(hipGetLastError());
-      GCHK(ghip_scan(ctx, (const unsigned long long *) cnt, off, (int) M + 1, st));
+      GCHK(ghip_scan<unsigned long long>(ctx, cnt, off, (int) M + 1, st));
       unsigned long long tot[2];
       HIPCHK(hipMemcpyAsync(&tot[0], off + m, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(&tot[1], off + M, 8, hipMemcpyDeviceToHost, st));

@@ -203,6 +203,50 @@ def test_gas_receives_grains_in_the_per_rank_order():
         S.close()
 
 
+def _drag_on_two_shards(case, own1=True, gas_timebin=None):
+    """both passes on two shards (own1 = False: shard 1 lists no grain of its own) -> what the scatter left and, per
+    shard, the restatement's pair counts per gas particle of the own and of the imported grains"""
+    B = bindings()
+    ngas = case.pr.ngas
+    T = DdDust(case, 2)
+    S = T.S
+    try:
+        if not own1:
+            T.lists[1], T.local[1] = T.lists[1][:0], T.local[1][:0]
+        if gas_timebin is not None:
+            S.set_field(B.F_TIMEBIN, np.concatenate([np.full(ngas, gas_timebin, case.timebin.dtype), case.timebin[ngas:]]))
+        vel0, ent0 = S.get_field(B.F_VEL), S.get_field(B.F_ENTROPY)
+        d7, _ = T.density()
+        out, cnt = T.drag(d7)
+        vel, ent, heat = S.get_field(B.F_VEL), S.get_field(B.F_ENTROPY), T.heat()
+        if gas_timebin == 0:
+            return cnt, (vel[:ngas], vel0[:ngas]), (ent, ent0), heat
+        gv, ge, gh, counts = T.ref_gas(out)
+        assert [int(c[2]) for c in cnt] == [int(c["touched"].sum()) for c in counts]      # (gas, grain) pairs exactly
+        assert _scaled_err(vel[:ngas], gv) < TOL and relerr(ent, ge) < TOL and _scaled_err(heat, gh) < TOL
+        orders, nown = DR.rank_orders(T.lists, T.local), [len(x) for x in T.lists]
+        own = T.ref_gas(out, orders=[o[:k] for o, k in zip(orders, nown)])[3]
+        imp = T.ref_gas(out, orders=[o[k:] for o, k in zip(orders, nown)])[3]
+        return cnt, [c["touched"] for c in own], [c["touched"] for c in imp]
+    finally:
+        S.close()
+
+
+def test_scatter_of_imported_grains_alone_of_mixed_runs_and_without_pairs():
+    """The three shapes of a shard's scatter, on two shards.  A shard that lists no grain and imports some: its gas
+    receives pairs, all of imported grains.  Both shards with lists: gas particles receive own and imported grains in
+    one run.  No gas particle on a timestep: no pair anywhere, and the gas stays as it was bit for bit."""
+    case = DustCase(1, ndust=600)
+    cnt, own, imp = _drag_on_two_shards(case, own1=False)
+    assert int(cnt[1][0]) == 0 and int(cnt[1][1]) > 0 and int(cnt[1][2]) > 0
+    assert own[1].sum() == 0 and imp[1].sum() == int(cnt[1][2])
+    cnt, own, imp = _drag_on_two_shards(case)
+    assert all(np.count_nonzero((o > 0) & (i > 0)) > 0 for o, i in zip(own, imp))
+    cnt, vel, ent, heat = _drag_on_two_shards(case, gas_timebin=0)
+    assert all(int(c[2]) == 0 for c in cnt) and sum(int(c[1]) for c in cnt) > 0
+    assert np.array_equal(*vel) and np.array_equal(*ent) and np.all(heat == 0)
+
+
 def test_dust_operations_refuse_without_the_trees_of_the_step():
     case = DustCase(1, ndust=100, ng=8)
     pr = case.pr

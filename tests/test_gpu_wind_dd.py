@@ -220,6 +220,53 @@ def test_spread_form(nshards, periodic, domains):
         T.close()
 
 
+def test_spread_of_imported_particles_alone_of_mixed_runs_and_without_pairs():
+    """The three shapes of a shard's scatter, on two shards.  A shard that lists no wind particle and imports some: its
+    gas receives pairs, all of imported particles.  Both shards with lists: gas particles receive own and imported
+    particles in one run.  new_density = 0 everywhere: no pair anywhere, Injected_BH_Momentum stays bit-zero."""
+    c = _case(0)
+    f = c.fields()
+    ng, nw = c.pr.ngas, len(c.wind)
+    dtj = c.dt_jump()
+    M = R.Margins()
+    rho, _ = R.density(c.par, R.gas_of(f), f["pos"][c.wind], f["hsml"][c.wind], dtj, M)
+    dmom = c.old * (0.1 + 0.5 * np.random.default_rng(9).random(nw))
+
+    def ref_of(sub):                                       # what the gas receives from the particles `sub` of the list
+        inj = np.zeros((ng, 3), R.LD)
+        w = c.wind[sub]
+        R.spread(c.par, R.gas_of(f), f["pos"][w], f["hsml"][w], f["vel"][w], dtj[sub], rho[sub], dmom[sub], inj, M)
+        return inj.astype(np.float64)
+
+    for own1 in (False, True):
+        T = DdWind(c, 2)
+        try:
+            if not own1:
+                T.lists[1], T.local[1] = T.lists[1][:0], T.local[1][:0]
+            parts = [ref_of(o) for o in T.lists]
+            assert M.smallest() >= MARGIN, M.by_kind
+            cnt = T.spread(dtj, rho, dmom)
+            got, ref = T.injected(), parts[0] + parts[1]
+            assert _scaled_err(got, ref) < TOL and np.abs(ref).max() > 0
+            gas1 = T.S.gid[1][:T.S.ngas[1]]
+            if not own1:
+                assert int(cnt[1][0]) == 0 and int(cnt[1][1]) > 0 and int(cnt[1][2]) > 0
+                assert np.abs(got[gas1]).max() > 0
+            else:
+                for r in range(2):
+                    gas = T.S.gid[r][:T.S.ngas[r]]
+                    assert np.count_nonzero(np.any(parts[0][gas] != 0, axis=1) & np.any(parts[1][gas] != 0, axis=1)) > 0
+        finally:
+            T.close()
+    T = DdWind(c, 2)
+    try:
+        cnt = T.spread(dtj, np.zeros(nw), dmom)
+        assert all(int(k[2]) == 0 for k in cnt) and sum(int(k[1]) for k in cnt) > 0
+        assert np.all(T.injected() == 0)
+    finally:
+        T.close()
+
+
 def _check_rad_accel(c, T, ref, ra0):
     ng = c.pr.ngas
     touched = ref["rad_touched"]
