@@ -22,7 +22,8 @@ HIP_SOURCES = ["ghip_api.hip", "ghip_tree.hip", "ghip_gravity.hip", "ghip_sph.hi
                "ghip_shard.hip", "ghip_drift.hip", "ghip_kick.hip", "ghip_export.hip", "ghip_pm.hip",
                "ghip_dd.hip", "ghip_comm.hip", "ghip_sink.hip", "ghip_dust.hip",
                "ghip_sfr.hip", "ghip_potential.hip", "ghip_decomp.hip", "ghip_prim.hip",
-               "ghip_records.hip", "ghip_sync.hip", "ghip_fof.hip", "ghip_wind.hip", "ghip_sequence.hip"]
+               "ghip_records.hip", "ghip_sync.hip", "ghip_fof.hip", "ghip_wind.hip", "ghip_sequence.hip",
+               "ghip_accretion.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 

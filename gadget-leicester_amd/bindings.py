@@ -103,6 +103,34 @@ class BhParams(C.Structure):
                 ("accretion_of_dust_only", C.c_int), ("accretion_density", C.c_int)]
 
 
+# columns of the resident sink table (GHIP_SK_*, include/ghip.h)
+(SK_BH_MASS, SK_ACCDISC_MASS, SK_BH_MDOT, SK_DUST_MASS, SK_TOTAL_MASS, SK_BH_DENSITY, SK_BH_ENTROPY,
+ SK_GASVEL) = range(8)
+SK_NUMNGB = SK_GASVEL + 3
+SK_ACC_MASS, SK_ACC_BHMASS, SK_ACC_DUSTMASS, SK_ACC_MOMENTUM = range(SK_NUMNGB + 1, SK_NUMNGB + 5)
+SK_COUNT = SK_ACC_MOMENTUM + 3
+
+
+class BhAccretionParams(C.Structure):
+    """ghip_bh_accretion_params: the Mdot step and the finish of blackhole_accretion() (include/ghip.h)"""
+    _fields_ = [("limited_accretion", C.c_int), ("accretion_at_eddington_rate", C.c_int),
+                ("enforce_eddington_limit", C.c_int), ("bh_mass_real", C.c_int), ("medd_fac", C.c_double),
+                ("tvisc", C.c_double), ("EddingtonFactor", C.c_double)]
+
+
+class BhAccretionReport(C.Structure):
+    """ghip_bh_accretion_report"""
+    _fields_ = [("TimeBin_BH_mass", C.c_double * 32), ("TimeBin_BH_dynamicalmass", C.c_double * 32),
+                ("TimeBin_BH_Mdot", C.c_double * 32), ("swallowed", C.c_longlong * 3),
+                ("nactive_sinks", C.c_int), ("missing", C.c_int), ("missing_id", C.c_uint), ("pad", C.c_int)]
+
+
+class SfrFormReport(C.Structure):
+    """ghip_sfr_form_report"""
+    _fields_ = [("stars_converted", C.c_int), ("pad", C.c_int), ("sum_mass_stars", C.c_double),
+                ("converted_in_bin", C.c_int * 32)]
+
+
 class DustParams(C.Structure):
     """ghip_dust_params: the dust-gas drag passes of the shipped flag bundle (include/ghip.h)"""
     _fields_ = [("periodic", C.c_int), ("BoxSize", C.c_double), ("dt_fac", C.c_double),
@@ -441,7 +469,9 @@ EXPORTS = [
     "ghip_wind_params_size", "ghip_wind_density", "ghip_wind_spread", "ghip_wind_feedback",
     "ghip_wind_get_injected", "ghip_wind_set_injected", "ghip_wind_get_rad_accel", "ghip_wind_set_rad_accel",
     "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size",
-    "ghip_kick_get_fields", "ghip_rearrange", "ghip_peano_order", "ghip_sequence_get_map", "ghip_sequence_get_info"]
+    "ghip_kick_get_fields", "ghip_rearrange", "ghip_peano_order", "ghip_sequence_get_map", "ghip_sequence_get_info",
+    "ghip_sinks_set_table", "ghip_sinks_get_table", "ghip_sinks_clear", "ghip_sinks_density",
+    "ghip_blackhole_accretion", "ghip_sfr_form_sinks"]
 
 
 def lib():
@@ -537,6 +567,13 @@ def lib():
         L.ghip_blackhole_evaluate.argtypes = [vp, C.POINTER(BhParams), C.c_int, vp, vp, vp, vp]
         L.ghip_blackhole_swallow.argtypes = [vp, C.POINTER(BhParams), C.c_int, vp, vp, vp, vp, vp,
                                              vp, vp, vp]
+        L.ghip_sinks_set_table.argtypes = [vp, C.c_int, vp, vp]
+        L.ghip_sinks_get_table.argtypes = [vp, C.POINTER(C.c_int), vp, vp]
+        L.ghip_sinks_clear.argtypes = [vp]
+        L.ghip_sinks_density.argtypes = [vp, C.POINTER(DensParams), C.c_double, C.POINTER(C.c_int)]
+        L.ghip_blackhole_accretion.argtypes = [vp, C.POINTER(BhParams), C.POINTER(BhAccretionParams),
+                                               C.POINTER(BhAccretionReport)]
+        L.ghip_sfr_form_sinks.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(SfrFormReport)]
         L.ghip_set_async.argtypes = [vp, C.c_int]
         L.ghip_timebin_counts.argtypes = [vp, vp, vp]
         L.ghip_run_begin.argtypes = [vp, C.c_int]
@@ -1191,6 +1228,52 @@ class ForcePath:
                                            _ptr(out["gasvel"]), C.byref(it)))
         out["iterations"] = it.value
         return out
+
+    # ---- the sinks on the resident state: the table keyed by ID, blackhole_accretion(), BH_FORM ----
+    def sinks_set_table(self, ids, rows):
+        """ghip_sinks_set_table: ids [nsink] (P[].ID), rows [nsink][SK_COUNT], in any order"""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        rows = np.ascontiguousarray(rows, np.float64).reshape(len(ids), SK_COUNT)
+        self._chk(self.L.ghip_sinks_set_table(self.h, len(ids), _ptr(ids), _ptr(rows)))
+
+    def sinks_table(self):
+        """ghip_sinks_get_table -> (ids uint32 [nsink] ascending, rows [nsink][SK_COUNT])"""
+        ns = C.c_int(0)
+        self._chk(self.L.ghip_sinks_get_table(self.h, C.byref(ns), None, None))
+        ids, rows = np.zeros(ns.value, np.uint32), np.zeros((ns.value, SK_COUNT))
+        self._chk(self.L.ghip_sinks_get_table(self.h, C.byref(ns), _ptr(ids), _ptr(rows)))
+        return ids, rows
+
+    def sinks_clear(self):
+        self._chk(self.L.ghip_sinks_clear(self.h))
+
+    def sinks_density(self, params, ngb_factor):
+        """ghip_sinks_density for the active Type-5 particles -> the iteration count; Hsml goes to F_HSML, the
+        other results into the table's rows"""
+        it = C.c_int(0)
+        self._chk(self.L.ghip_sinks_density(self.h, C.byref(params), float(ngb_factor), C.byref(it)))
+        return it.value
+
+    def blackhole_accretion(self, bh_params, acc_params):
+        """ghip_blackhole_accretion -> dict(bin_mass, bin_dynmass, bin_mdot [32], counts [3] = gas / sinks /
+        dust swallowed, nactive)"""
+        rep = BhAccretionReport()
+        self._chk(self.L.ghip_blackhole_accretion(self.h, C.byref(bh_params), C.byref(acc_params), C.byref(rep)))
+        return dict(bin_mass=np.array(rep.TimeBin_BH_mass), bin_dynmass=np.array(rep.TimeBin_BH_dynamicalmass),
+                    bin_mdot=np.array(rep.TimeBin_BH_Mdot), counts=np.array(rep.swallowed, np.int64),
+                    nactive=rep.nactive_sinks)
+
+    def sfr_form_sinks(self, ncand, u01, limited_accretion=True):
+        """ghip_sfr_form_sinks for the candidates of the last sfr_cooling() -> dict(stars_converted,
+        sum_mass_stars, converted_in_bin [32])"""
+        u = np.ascontiguousarray(u01, np.float64)
+        if len(u) < ncand:
+            raise ValueError("u01 holds %d draws for %d candidates" % (len(u), ncand))
+        rep = SfrFormReport()
+        self._chk(self.L.ghip_sfr_form_sinks(self.h, int(ncand), _ptr(u), int(bool(limited_accretion)),
+                                             C.byref(rep)))
+        return dict(stars_converted=rep.stars_converted, sum_mass_stars=rep.sum_mass_stars,
+                    converted_in_bin=np.array(rep.converted_in_bin, np.int64))
 
     def sink_reset(self):
         self._chk(self.L.ghip_sink_reset(self.h))

@@ -1,0 +1,820 @@
+// ghip_accretion.hip -- the sinks on the resident state: the sink table, blackhole_accretion() as a whole and the
+// BH_FORM conversion, for the shipped flags BLACK_HOLES, BH_FORM, SWALLOWGAS, ACCRETION_RADIUS, BH_MASS_REAL,
+// LIMITED_ACCRETION_AND_FEEDBACK (and their siblings ACCRETION_AT_EDDINGTON_RATE, ENFORCE_EDDINGTON_LIMIT).
+//
+// Replaces, for a host with a resident run,
+//   blackhole_accretion()                         blackhole.c:70-791 without the log files
+//     the Mdot loop                               :119-286   -> k_acc_begin
+//     blackhole_evaluate / _evaluate_swallow      the kernels of ghip_sink.hip, unchanged (ghip_bh_launch_*)
+//     the finish and the per-bin sums             :679-735   -> k_acc_finish, k_acc_report
+//   the BH_FORM branch of cooling_and_starformation   sfr_eff.c:602-629   -> k_form_rows, k_form_apply
+//   density() for Type-5 targets                  ghip_sink_density's kernel and h iteration (ghip_sinks_density)
+//
+// The per-sink state lives in a table of GHIP_SK_COUNT doubles per Type-5 particle, keyed by P[].ID and sorted by
+// it: a pass selects the active Type-5 particles on the device, in active-list order, and finds each one's row
+// by a binary search.  Nothing here is keyed by particle index, so no reordering of the particles moves the table.
+// Sinks are few (hundreds): everything below but the two neighbour passes is one thread per sink, and the sums
+// that have an order (the report) are added by a single thread in active-list order.
+//
+// ghip_blackhole_accretion waits for the device once, for its report.  The number of active sinks is not known
+// on the host before that: the passes are launched for as many records as the table has rows, and a record
+// beyond the active sinks is inert (mass 0: marks nothing; its own mark set: sweeps nothing).
+//
+// no a*b+c -> fma contraction in this file (before the headers, as in ghip_wind.hip): every result equals the
+// op-by-op IEEE evaluation of the C text, which the tests restate in numpy.
+#pragma clang fp contract(off)
+
+#include "ghip_prim.h"
+
+#define SK_NC GHIP_SK_COUNT
+
+// ints at the front of SinkTable::work
+enum
+{
+  SKW_COUNT = 0,   // active Type-5 particles selected
+  SKW_ERR,         // one of them has no row
+  SKW_ERRID,       // ... the largest such ID
+  SKW_DUP,         // two rows with the same ID
+  SKW_DUPID,
+  SKW_KEPT,        // rows kept by ghip_sinks_drop_eliminated
+  SKW_WORDS = 16
+};
+#define SK_REPORT_BYTES 1024   // room for either report behind the words
+static_assert(sizeof(ghip_bh_accretion_report) <= SK_REPORT_BYTES && sizeof(ghip_sfr_form_report) <= SK_REPORT_BYTES,
+              "the report block of SinkTable::work");
+
+struct SkWork
+{
+  int *words;
+  char *report;
+  int *a, *b, *row;   // i32[na], i32[na], i32[nrow]
+};
+
+static int sk_work(ghip_ctx *ctx, size_t na, size_t nrow, SkWork &W)
+{
+  const size_t head = SKW_WORDS * 4 + SK_REPORT_BYTES;
+  GCHK(ghip_ensure(ctx, ctx->sk.work, head + (2 * na + nrow) * 4 + 64));
+  char *base = P<char>(ctx->sk.work);
+  W.words = reinterpret_cast<int *>(base);
+  W.report = base + SKW_WORDS * 4;
+  W.a = reinterpret_cast<int *>(base + head);
+  W.b = W.a + na;
+  W.row = W.b + na;
+  return GHIP_OK;
+}
+
+struct AccK
+{
+  int limited, at_edd, enforce, mass_real, dust;
+  double medd_fac, tvisc, eddf, dt_fac;
+};
+
+// the row of `id` in the ascending list ids[0, n), -1: none
+__device__ __forceinline__ int d_sk_find(int n, const unsigned int *__restrict__ ids, unsigned int id)
+{
+  int lo = 0, hi = n;
+  while(lo < hi)
+    {
+      const int mid = (lo + hi) >> 1;
+      if(ids[mid] < id)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+  return (lo < n && ids[lo] == id) ? lo : -1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the table
+// ---------------------------------------------------------------------------------------------
+__global__ void k_sk_iota(int m, int *__restrict__ v)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r < m)
+    v[r] = r;
+}
+
+__global__ void k_sk_fill(int m, int value, int *__restrict__ v)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r < m)
+    v[r] = value;
+}
+
+// dst row r = src row from[r]
+__global__ void k_sk_gather_rows(int m, const int *__restrict__ from, const double *__restrict__ src,
+                                 double *__restrict__ dst)
+{
+  const long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+  if(e < (long long) m * SK_NC)
+    {
+      const int r = (int) (e / SK_NC), c = (int) (e % SK_NC);
+      dst[e] = src[(size_t) from[r] * SK_NC + c];
+    }
+}
+
+__global__ void k_sk_gather_ids(int m, const int *__restrict__ from, const unsigned int *__restrict__ src,
+                                unsigned int *__restrict__ dst)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r < m)
+    dst[r] = src[from[r]];
+}
+
+__global__ void k_sk_dups(int m, const unsigned int *__restrict__ ids, int *__restrict__ words)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r + 1 < m && ids[r] == ids[r + 1])
+    {
+      words[SKW_DUP] = 1;
+      atomicMax(reinterpret_cast<unsigned int *>(words + SKW_DUPID), ids[r]);
+    }
+}
+
+// the m rows in sk.tmp_id / sk.tmp_rows, in any order, become the table: sorted by ID, duplicates refused
+static int sk_install(ghip_ctx *ctx, int m, const char *who)
+{
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  T.on = false;
+  T.n = 0;
+  T.stale = false;
+  if(m > 0)
+    {
+      SkWork W;
+      GCHK(sk_work(ctx, (size_t) m, 0, W));
+      GCHK(ghip_ensure(ctx, T.id, (size_t) m * 4));
+      GCHK(ghip_ensure(ctx, T.rows, (size_t) m * SK_NC * 8));
+      HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+      k_sk_iota<<<cdiv(m, 256), 256, 0, st>>>(m, W.a);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_sort_pairs(ctx, P<unsigned int>(T.tmp_id), P<unsigned int>(T.id), W.a, W.b, m, 32, st));
+      k_sk_gather_rows<<<cdiv((long long) m * SK_NC, 256), 256, 0, st>>>(m, W.b, P<double>(T.tmp_rows),
+                                                                        P<double>(T.rows));
+      k_sk_dups<<<cdiv(m, 256), 256, 0, st>>>(m, P<unsigned int>(T.id), W.words);
+      HIPCHK(hipGetLastError());
+      int w[SKW_WORDS];
+      HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(w[SKW_DUP])
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: two rows of the sink table have the ID %u (the context holds no "
+                         "table now)", who, (unsigned int) w[SKW_DUPID]);
+    }
+  T.on = true;
+  T.n = m;
+  return GHIP_OK;
+}
+
+// what every entry point of the section refuses
+static int sk_enter(ghip_ctx *ctx, const char *who, bool need_table)
+{
+  if(ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU shard (%d ranks): the sink table covers "
+                     "one GPU", who, ctx->dd.nranks);
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a replicated shard (ghip_set_shard with %d ranks)",
+                     who, ctx->shard_n);
+  HIPCHK(hipSetDevice(ctx->device));
+  if(!ctx->id_given)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table is keyed by P[].ID, and GHIP_F_ID has not been given "
+                     "since ghip_set_counts (ghip_set_field)", who);
+  if(need_table)
+    {
+      if(ctx->sk.on && ctx->sk.stale)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table was given for other counts: give it again after "
+                         "ghip_set_counts (ghip_sinks_set_table)", who);
+      if(!ctx->sk.on)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: no sink table (ghip_sinks_set_table)", who);
+    }
+  return GHIP_OK;
+}
+
+extern "C" int ghip_sinks_set_table(ghip_ctx *ctx, int nsink, const unsigned int *id, const double *rows)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || nsink < 0 || (nsink > 0 && (!id || !rows)))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_set_table: bad arguments");
+  GCHK(sk_enter(ctx, "ghip_sinks_set_table", false));
+  SinkTable &T = ctx->sk;
+  if(nsink > 0)
+    {
+      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) nsink * 4));
+      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) nsink * SK_NC * 8));
+      HIPCHK(hipMemcpyAsync(T.tmp_id.p, id, (size_t) nsink * 4, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, rows, (size_t) nsink * SK_NC * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+  return sk_install(ctx, nsink, "ghip_sinks_set_table");
+}
+
+extern "C" int ghip_sinks_get_table(ghip_ctx *ctx, int *nsink, unsigned int *id, double *rows)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !nsink)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_get_table: bad arguments");
+  GCHK(sk_enter(ctx, "ghip_sinks_get_table", true));
+  SinkTable &T = ctx->sk;
+  *nsink = T.n;
+  if(T.n > 0 && (id || rows))
+    {
+      if(id)
+        HIPCHK(hipMemcpyAsync(id, T.id.p, (size_t) T.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if(rows)
+        HIPCHK(hipMemcpyAsync(rows, T.rows.p, (size_t) T.n * SK_NC * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+    }
+  return GHIP_OK;
+}
+
+extern "C" int ghip_sinks_clear(ghip_ctx *ctx)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  ghip_renew(ctx->sk);
+  return GHIP_OK;
+}
+
+// keep[row] = 0 for the row of every Type-5 particle that the map eliminates
+__global__ void k_sk_mark_dead(int n, const int *__restrict__ type, const int *__restrict__ idf,
+                               const int *__restrict__ new_of_old, int nrows, const unsigned int *__restrict__ ids,
+                               int *__restrict__ keep)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if(i < n && type[i] == 5 && new_of_old[i] < 0)
+    {
+      const int r = d_sk_find(nrows, ids, (unsigned int) idf[i]);
+      if(r >= 0)
+        keep[r] = 0;
+    }
+}
+
+int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old)
+{
+  SinkTable &T = ctx->sk;
+  if(!T.on || T.n == 0 || n_before <= 0 || !ctx->id_given)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const int m = T.n;
+  SkWork W;
+  GCHK(sk_work(ctx, (size_t) m, 0, W));
+  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+  k_sk_fill<<<cdiv(m, 256), 256, 0, st>>>(m, 1, W.a);
+  k_sk_mark_dead<<<cdiv(n_before, 256), 256, 0, st>>>(n_before, P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_ID]),
+                                                     new_of_old, m, P<unsigned int>(T.id), W.a);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, nullptr, W.a, W.b, W.words + SKW_KEPT, m, st));
+  int kept = 0;
+  HIPCHK(hipMemcpyAsync(&kept, W.words + SKW_KEPT, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(kept < 0 || kept > m)
+    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_rearrange: %d of %d rows of the sink table kept", kept, m);
+  if(kept == m)
+    return GHIP_OK;
+  if(kept > 0)
+    {
+      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) kept * 4));
+      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) kept * SK_NC * 8));
+      k_sk_gather_ids<<<cdiv(kept, 256), 256, 0, st>>>(kept, W.b, P<unsigned int>(T.id), P<unsigned int>(T.tmp_id));
+      k_sk_gather_rows<<<cdiv((long long) kept * SK_NC, 256), 256, 0, st>>>(kept, W.b, P<double>(T.rows),
+                                                                           P<double>(T.tmp_rows));
+      HIPCHK(hipGetLastError());
+      T.id.swap(T.tmp_id);   // (ascending still: the selection keeps the order)
+      T.rows.swap(T.tmp_rows);
+    }
+  T.n = kept;
+  return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the active Type-5 particles, in active-list order, and their rows
+// ---------------------------------------------------------------------------------------------
+__global__ void k_sk_flag_sinks(int nact, const int *__restrict__ act, int n, const int *__restrict__ type,
+                                int *__restrict__ flags)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nact)
+    return;
+  const int i = act ? act[a] : a;
+  flags[a] = (i >= 0 && i < n && type[i] == 5) ? 1 : 0;
+}
+
+// row[a] of the a-th selected particle, a < min(count, G); whoever has none is an error.  (More selected particles
+// than rows: one of them has none, or two carry the same ID -- SK_BAD covers both.)
+#define SK_BAD(words, G) ((words)[SKW_ERR] != 0 || (words)[SKW_COUNT] > (G))
+__global__ void k_sk_rows(int nact, const int *__restrict__ sel, const int *__restrict__ idf, int nrows,
+                          const unsigned int *__restrict__ ids, int G, int *__restrict__ row, int *__restrict__ words)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nact || a >= words[SKW_COUNT])
+    return;
+  const unsigned int id = (unsigned int) idf[sel[a]];
+  const int r = d_sk_find(nrows, ids, id);
+  if(r < 0)
+    {
+      words[SKW_ERR] = 1;
+      atomicMax(reinterpret_cast<unsigned int *>(words + SKW_ERRID), id);
+    }
+  else if(a < G)
+    row[a] = r;
+}
+
+// selection + rows, everything left on the device: W.b = the particles, W.row = their rows, W.words
+static int sk_select(ghip_ctx *ctx, int G, SkWork &W, int *nact_out)
+{
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
+  *nact_out = nact;
+  GCHK(sk_work(ctx, (size_t) (nact > 0 ? nact : 1), (size_t) (G > 0 ? G : 1), W));
+  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+  if(nact <= 0)
+    return GHIP_OK;
+  const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
+  k_sk_flag_sinks<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), W.a);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + SKW_COUNT, nact, st));
+  k_sk_rows<<<cdiv(nact, 256), 256, 0, st>>>(nact, W.b, P<int>(ctx->f[GHIP_F_ID]), T.n, P<unsigned int>(T.id), G,
+                                             W.row, W.words);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// The G sink records of a pass.  Record a < min(count, G) is the a-th active sink: its state from the fields and
+// its row, after the Mdot step (blackhole.c:119-286) when do_mdot.  Every other record -- and every record once a
+// row is missing -- is inert: mass 0 (marks nothing), its own mark set (sweeps nothing).
+__global__ void k_acc_begin(int G, const int *__restrict__ words, const int *__restrict__ sel,
+                            const int *__restrict__ row, int n, const double *__restrict__ pos,
+                            const double *__restrict__ vel, const double *__restrict__ mass,
+                            const double *__restrict__ hsml, const int *__restrict__ timebin,
+                            const int *__restrict__ idf, double *__restrict__ rows, AccK K, int do_mdot,
+                            SinkRec *__restrict__ recs, double *__restrict__ dh)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= G)
+    return;
+  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  SinkRec S;
+  if(a >= cnt || SK_BAD(words, G))
+    {
+      S.x = S.y = S.z = S.vx = S.vy = S.vz = S.mass = S.h = S.mdot = 0;
+      S.rho = 1.0;
+      S.id = 0;
+      S.timebin = 0;
+      S.index = 0;
+      S.mark = 1;
+      recs[a] = S;
+      if(dh)
+        dh[a] = 0;
+      return;
+    }
+  const int i = sel[a];
+  double *R = rows + (size_t) row[a] * SK_NC;
+  const int tb = timebin[i];
+  const double m = mass[i];
+  if(do_mdot)
+    {
+      const double dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac;
+      const double meddington = K.medd_fac * (K.mass_real ? m : R[GHIP_SK_BH_MASS]);
+      double mdot = 0;
+      if(K.limited)
+        {
+          if(!K.at_edd)
+            {
+              mdot = R[GHIP_SK_ACCDISC_MASS] / (dt + K.tvisc);
+              if(K.enforce && mdot > K.eddf * meddington)
+                mdot = K.eddf * meddington;
+              R[GHIP_SK_ACCDISC_MASS] -= mdot * dt;
+              R[GHIP_SK_BH_MASS] += mdot * dt;
+            }
+          else
+            {
+              mdot = K.eddf * meddington;
+              R[GHIP_SK_BH_MASS] += mdot * dt;
+            }
+        }
+      else if(K.enforce && mdot > K.eddf * meddington)
+        mdot = K.eddf * meddington;
+      R[GHIP_SK_BH_MDOT] = mdot;
+    }
+  S.x = pos[i];
+  S.y = pos[(size_t) n + i];
+  S.z = pos[2 * (size_t) n + i];
+  S.vx = vel[i];
+  S.vy = vel[(size_t) n + i];
+  S.vz = vel[2 * (size_t) n + i];
+  S.mass = m;
+  S.h = hsml[i];
+  S.mdot = R[GHIP_SK_BH_MDOT];
+  S.rho = R[GHIP_SK_BH_DENSITY];
+  S.id = (unsigned int) idf[i];
+  S.timebin = tb;
+  S.index = i;
+  S.mark = 0;
+  recs[a] = S;
+  if(dh)
+    dh[a] = S.h;
+}
+
+// ---------------------------------------------------------------------------------------------
+// density() for the active sinks
+// ---------------------------------------------------------------------------------------------
+// res: h | numngb | rho | entropy [ns] | gasvel [ns][3]
+__global__ void k_sk_store_density(int ns, const int *__restrict__ sel, const int *__restrict__ row,
+                                   const double *__restrict__ res, double *__restrict__ hsml,
+                                   double *__restrict__ rows)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= ns)
+    return;
+  double *R = rows + (size_t) row[a] * SK_NC;
+  hsml[sel[a]] = res[a];
+  R[GHIP_SK_NUMNGB] = res[(size_t) ns + a];
+  R[GHIP_SK_BH_DENSITY] = res[2 * (size_t) ns + a];
+  R[GHIP_SK_BH_ENTROPY] = res[3 * (size_t) ns + a];
+  for(int k = 0; k < 3; k++)
+    R[GHIP_SK_GASVEL + k] = res[4 * (size_t) ns + 3 * (size_t) a + k];
+}
+
+extern "C" int ghip_sinks_density(ghip_ctx *ctx, const ghip_dens_params *p, double ngb_factor, int *iterations)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !p)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: bad arguments");
+  if(iterations)
+    *iterations = 0;
+  GCHK(sk_enter(ctx, "ghip_sinks_density", true));
+  GCHK(ghip_finish_gas_tree(ctx));
+  if(!ctx->st.built)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: call ghip_tree_build first");
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  SkWork W;
+  int nact = 0;
+  GCHK(sk_select(ctx, T.n, W, &nact));
+  int w[SKW_WORDS];
+  HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(w[SKW_ERR])
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: the active Type-5 particle with ID %u has no row in "
+                     "the sink table (%d rows, %d active sinks)", (unsigned int) w[SKW_ERRID], T.n, w[SKW_COUNT]);
+  const int ns = w[SKW_COUNT];
+  if(ns > T.n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: %d active Type-5 particles for %d rows of the sink "
+                     "table: two of them carry the same ID", ns, T.n);
+  if(ns <= 0)
+    return GHIP_OK;
+  // staging: SinkRec[ns] | h[ns] | out[6][ns] | slot[ns], as ghip_sink_density
+  GCHK(ghip_ensure(ctx, ctx->stage, (size_t) ns * (sizeof(SinkRec) + 8 + 48 + 4) + 256));
+  SinkRec *drecs = P<SinkRec>(ctx->stage);
+  double *dh = reinterpret_cast<double *>(drecs + ns), *dout = dh + ns;
+  int *dslot = reinterpret_cast<int *>(dout + 6 * (size_t) ns);
+  AccK K = {};
+  k_acc_begin<<<cdiv(ns, 64), 64, 0, st>>>(ns, W.words, W.b, W.row, ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+                                           P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_MASS]),
+                                           P<double>(ctx->f[GHIP_F_HSML]), P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                           P<int>(ctx->f[GHIP_F_ID]), P<double>(T.rows), K, 0, drecs, dh);
+  HIPCHK(hipGetLastError());
+  SinkIter I;
+  sink_iter_init(I, ns);
+  HIPCHK(hipMemcpyAsync(I.h.data(), dh, (size_t) ns * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  std::vector<double> hout((size_t) ns * 7);
+  const int maxiter = p->MaxIter > 0 ? p->MaxIter : 150;
+  int ncur = ns, iter = 0;
+  while(ncur > 0)
+    {
+      GCHK(sink_density_pass(ctx, p, ns, drecs, dh, dslot, dout, I, ncur, 0));
+      HIPCHK(hipMemcpyAsync(hout.data(), dout, (size_t) ns * 48, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      ncur = sink_iterate(p, ngb_factor, ns, hout.data(), ncur, I);
+      if(ncur > 0)
+        {
+          iter++;
+          if(iter > maxiter)
+            return ghip_fail(ctx, GHIP_ENOCONV, "sink density: %d sinks not converged after %d h-iterations "
+                             "(reference: endrun(1155))", ncur, maxiter);
+        }
+    }
+  // the results go back as one block (dh | dout hold 7 planes) and from there into HSML and the rows
+  for(int a = 0; a < ns; a++)
+    {
+      hout[a] = I.h[a];
+      hout[(size_t) ns + a] = I.numngb[a];
+      hout[2 * (size_t) ns + a] = I.rho[a];
+      hout[3 * (size_t) ns + a] = I.entropy[a];
+      for(int k = 0; k < 3; k++)
+        hout[4 * (size_t) ns + 3 * (size_t) a + k] = I.gasvel[3 * (size_t) a + k];
+    }
+  HIPCHK(hipMemcpyAsync(dh, hout.data(), (size_t) ns * 56, hipMemcpyHostToDevice, st));
+  k_sk_store_density<<<cdiv(ns, 64), 64, 0, st>>>(ns, W.b, W.row, dh, P<double>(ctx->f[GHIP_F_HSML]),
+                                                  P<double>(T.rows));
+  HIPCHK(hipGetLastError());
+  HIPCHK(ghip_stream_sync(ctx, st));   // (hout goes out of scope)
+  if(iterations)
+    *iterations = iter;
+  return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// blackhole_accretion()
+// ---------------------------------------------------------------------------------------------
+// before the swallow pass: each sink's own SwallowID as the marking pass left it, and BH_Mass by particle
+__global__ void k_acc_marks(int G, const int *__restrict__ words, const int *__restrict__ row,
+                            const unsigned int *__restrict__ swallow, const double *__restrict__ rows,
+                            SinkRec *__restrict__ recs, double *__restrict__ dpbh)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  if(a >= cnt || SK_BAD(words, G))
+    return;
+  const int i = recs[a].index;
+  recs[a].mark = swallow[i];
+  dpbh[i] = rows[(size_t) row[a] * SK_NC + GHIP_SK_BH_MASS];
+}
+
+// blackhole.c:679-714 for sink a; out: the [9][G] planes of k_bh_swallow
+__global__ void k_acc_finish(int G, const int *__restrict__ words, const int *__restrict__ row,
+                             const SinkRec *__restrict__ recs, const double *__restrict__ out,
+                             const int *__restrict__ victim, int n, double *__restrict__ vel,
+                             double *__restrict__ mass, double *__restrict__ rows, AccK K)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  if(a >= cnt || SK_BAD(words, G))
+    return;
+  const int i = recs[a].index;
+  double *R = rows + (size_t) row[a] * SK_NC;
+  const double am = out[a], ab = out[(size_t) G + a], ad = out[2 * (size_t) G + a];
+  if(victim[i])
+    R[GHIP_SK_BH_MASS] = 0;   // P[j].BH_Mass = 0 of a swallowed sink (blackhole.c:1274)
+  R[GHIP_SK_ACC_MASS] = am;
+  R[GHIP_SK_ACC_BHMASS] = ab;
+  R[GHIP_SK_ACC_DUSTMASS] = ad;
+  for(int k = 0; k < 3; k++)
+    R[GHIP_SK_ACC_MOMENTUM + k] = out[(size_t) (3 + k) * G + a];
+  if(am > 0)
+    {
+      const double m = mass[i];
+      for(int k = 0; k < 3; k++)
+        {
+          const double v = vel[(size_t) k * n + i];
+          vel[(size_t) k * n + i] = (v * m + out[(size_t) (3 + k) * G + a]) / (m + am);
+        }
+      double mnew = m + am;
+      R[GHIP_SK_BH_MASS] += ab;
+      if(K.dust)
+        R[GHIP_SK_DUST_MASS] += ad;
+      if(K.limited)
+        {
+          R[GHIP_SK_ACCDISC_MASS] += am;
+          if(K.at_edd)
+            mnew = R[GHIP_SK_BH_MASS];
+        }
+      if(K.dust)
+        R[GHIP_SK_TOTAL_MASS] += am;
+      mass[i] = mnew;
+    }
+}
+
+// blackhole.c:715-719 and the counts: one thread, active-list order
+__global__ void k_acc_report(int G, const int *__restrict__ words, const int *__restrict__ row,
+                             const SinkRec *__restrict__ recs, const double *__restrict__ out,
+                             const double *__restrict__ mass, const double *__restrict__ rows,
+                             ghip_bh_accretion_report *__restrict__ rep)
+{
+  if(blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  for(int b = 0; b < 32; b++)
+    rep->TimeBin_BH_mass[b] = rep->TimeBin_BH_dynamicalmass[b] = rep->TimeBin_BH_Mdot[b] = 0;
+  rep->swallowed[0] = rep->swallowed[1] = rep->swallowed[2] = 0;
+  rep->nactive_sinks = words[SKW_COUNT];
+  rep->missing = words[SKW_ERR] ? 1 : (words[SKW_COUNT] > G ? 2 : 0);
+  rep->missing_id = (unsigned int) words[SKW_ERRID];
+  rep->pad = 0;
+  if(rep->missing)
+    return;
+  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  for(int a = 0; a < cnt; a++)
+    {
+      const double *R = rows + (size_t) row[a] * SK_NC;
+      const int bin = recs[a].timebin;
+      if(bin >= 0 && bin < 32)
+        {
+          rep->TimeBin_BH_mass[bin] += R[GHIP_SK_BH_MASS];
+          rep->TimeBin_BH_dynamicalmass[bin] += mass[recs[a].index];
+          rep->TimeBin_BH_Mdot[bin] += R[GHIP_SK_BH_MDOT];
+        }
+      for(int k = 0; k < 3; k++)
+        rep->swallowed[k] += (long long) (out[(size_t) (6 + k) * G + a] + 0.5);
+    }
+}
+
+extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh, const ghip_bh_accretion_params *p,
+                                        ghip_bh_accretion_report *report)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !bh || !p || !report)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: bad arguments");
+  memset(report, 0, sizeof(*report));
+  GCHK(sk_enter(ctx, "ghip_blackhole_accretion", true));
+  if(!ctx->gt.built)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: call ghip_tree_build first");
+  GCHK(ghip_sink_buffers(ctx));
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int G = T.n;
+  const size_t n = (size_t) ctx->n;
+  AccK K;
+  K.limited = p->limited_accretion != 0;
+  K.at_edd = p->accretion_at_eddington_rate != 0;
+  K.enforce = p->enforce_eddington_limit != 0;
+  K.mass_real = p->bh_mass_real != 0;
+  K.dust = bh->dust != 0;
+  K.medd_fac = p->medd_fac;
+  K.tvisc = p->tvisc;
+  K.eddf = p->EddingtonFactor;
+  K.dt_fac = bh->dt_fac;
+  // staging: SinkRec[G] | out [9][G] ; particle-indexed: bh mass [n], victim [n]
+  const size_t g1 = (size_t) (G > 0 ? G : 1), n1 = n > 0 ? n : 1;
+  GCHK(ghip_ensure(ctx, ctx->stage, g1 * (sizeof(SinkRec) + 72) + n1 * 12 + 512));
+  SinkRec *drecs = P<SinkRec>(ctx->stage);
+  double *dout = reinterpret_cast<double *>(drecs + g1), *dpbh = dout + 9 * g1;
+  int *dvict = reinterpret_cast<int *>(dpbh + n1);
+  SkWork W;
+  int nact = 0;
+  GCHK(sk_select(ctx, G, W, &nact));
+  ghip_bh_accretion_report *drep = reinterpret_cast<ghip_bh_accretion_report *>(W.report);
+  // P[].SwallowID = 0, Injected_BH_Energy = 0 (blackhole.c: the start of blackhole_accretion)
+  HIPCHK(hipMemsetAsync(ctx->bh_swallow.p, 0, ctx->bh_swallow.cap, st));
+  HIPCHK(hipMemsetAsync(ctx->bh_injected.p, 0, ctx->bh_injected.cap, st));
+  if(G > 0 && nact > 0 && n > 0)
+    {
+      const int nb = cdiv(G, 64);
+      HIPCHK(hipMemsetAsync(dpbh, 0, n * 12, st));
+      k_acc_begin<<<nb, 64, 0, st>>>(G, W.words, W.b, W.row, ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+                                     P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_MASS]),
+                                     P<double>(ctx->f[GHIP_F_HSML]), P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                     P<int>(ctx->f[GHIP_F_ID]), P<double>(T.rows), K, 1, drecs, nullptr);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_bh_launch_evaluate(ctx, bh, G, drecs));
+      k_acc_marks<<<nb, 64, 0, st>>>(G, W.words, W.row, P<unsigned int>(ctx->bh_swallow), P<double>(T.rows), drecs,
+                                     dpbh);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_bh_launch_swallow(ctx, bh, G, drecs, dpbh, dvict, dout));
+      k_acc_finish<<<nb, 64, 0, st>>>(G, W.words, W.row, drecs, dout, dvict, ctx->n, P<double>(ctx->f[GHIP_F_VEL]),
+                                      P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows), K);
+      HIPCHK(hipGetLastError());
+    }
+  k_acc_report<<<1, 64, 0, st>>>(G, W.words, W.row, drecs, dout,
+                                 P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows), drep);
+  HIPCHK(hipGetLastError());
+  // the one blocking read of the call
+  HIPCHK(hipMemcpyAsync(report, drep, sizeof(*report), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(report->missing == 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: the active Type-5 particle with ID %u has no row "
+                     "in the sink table (%d rows, %d active sinks); nothing but the marks was changed",
+                     report->missing_id, T.n, report->nactive_sinks);
+  if(report->missing)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: %d active Type-5 particles for %d rows of the sink "
+                     "table: two of them carry the same ID; nothing but the marks was changed",
+                     report->nactive_sinks, T.n);
+  ctx->gt.built = false;   // masses changed: the trees' moments are stale
+  ctx->st.built = false;
+  return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// BH_FORM: a flagged gas particle becomes a sink (sfr_eff.c:602-629)
+// ---------------------------------------------------------------------------------------------
+// the new rows and masses of the candidates; no field is written yet
+__global__ void k_form_rows(int ncand, const int *__restrict__ cand, const double *__restrict__ u01, int n,
+                            const double *__restrict__ mass, const int *__restrict__ idf, int limited,
+                            unsigned int *__restrict__ new_id, double *__restrict__ new_rows,
+                            double *__restrict__ mold, double *__restrict__ mnew)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if(k >= ncand)
+    return;
+  const int i = cand[k];
+  const bool ok = i >= 0 && i < n;
+  const double m = ok ? mass[i] : 0.0;
+  const double mm = m * (0.995 + 0.005 * u01[k]);
+  mold[k] = m;
+  mnew[k] = mm;
+  new_id[k] = ok ? (unsigned int) idf[i] : 0u;
+  double *R = new_rows + (size_t) k * SK_NC;
+  for(int c = 0; c < SK_NC; c++)
+    R[c] = 0;
+  if(limited)
+    R[GHIP_SK_ACCDISC_MASS] = mm;
+  else
+    R[GHIP_SK_BH_MASS] = mm;
+}
+
+__global__ void k_form_apply(int ncand, const int *__restrict__ cand, const double *__restrict__ mnew, int n,
+                             double *__restrict__ mass, int *__restrict__ type)
+{
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if(k >= ncand)
+    return;
+  const int i = cand[k];
+  if(i >= 0 && i < n)
+    {
+      type[i] = 5;
+      mass[i] = mnew[k];
+    }
+}
+
+// one thread, list order
+__global__ void k_form_report(int ncand, const int *__restrict__ cand, const double *__restrict__ mold, int n,
+                              const int *__restrict__ timebin, ghip_sfr_form_report *__restrict__ rep)
+{
+  if(blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  rep->stars_converted = ncand;
+  rep->pad = 0;
+  rep->sum_mass_stars = 0;
+  for(int b = 0; b < 32; b++)
+    rep->converted_in_bin[b] = 0;
+  for(int k = 0; k < ncand; k++)
+    {
+      rep->sum_mass_stars += mold[k];
+      const int i = cand[k];
+      const int bin = (i >= 0 && i < n) ? timebin[i] : -1;
+      if(bin >= 0 && bin < 32)
+        rep->converted_in_bin[bin]++;
+    }
+}
+
+extern "C" int ghip_sfr_form_sinks(ghip_ctx *ctx, int ncand, const double *u01, int limited_accretion,
+                                   ghip_sfr_form_report *report)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !report || ncand < 0 || (ncand > 0 && !u01))
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: bad arguments");
+  GCHK(sk_enter(ctx, "ghip_sfr_form_sinks", false));
+  SinkTable &T = ctx->sk;
+  if(T.on && T.stale)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: the sink table was given for other counts: give it "
+                     "again after ghip_set_counts (ghip_sinks_set_table)");
+  if(ctx->sfr_ncand < 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: no candidates in place: ghip_sfr_cooling has not run "
+                     "since the particles were last reordered, recounted or converted");
+  if(ncand != ctx->sfr_ncand)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: ncand = %d, the last ghip_sfr_cooling found %d", ncand,
+                     ctx->sfr_ncand);
+  memset(report, 0, sizeof(*report));
+  ctx->sfr_ncand = -1;   // consumed
+  if(!T.on)
+    {
+      T.on = true;
+      T.n = 0;
+      T.stale = false;
+    }
+  if(ncand == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const int old = T.n, m = old + ncand;
+  GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) m * 4));
+  GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) m * SK_NC * 8));
+  // staging: u01 | mass before | mass after [ncand]
+  GCHK(ghip_ensure(ctx, ctx->stage, (size_t) ncand * 24 + 256));
+  SkWork W;
+  GCHK(sk_work(ctx, (size_t) m, 0, W));
+  double *du = P<double>(ctx->stage), *dmold = du + ncand, *dmnew = dmold + ncand;
+  const int *dcand = P<int>(ctx->sfr_cand);
+  if(old > 0)
+    {
+      HIPCHK(hipMemcpyAsync(T.tmp_id.p, T.id.p, (size_t) old * 4, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, T.rows.p, (size_t) old * SK_NC * 8, hipMemcpyDeviceToDevice, st));
+    }
+  HIPCHK(hipMemcpyAsync(du, u01, (size_t) ncand * 8, hipMemcpyHostToDevice, st));
+  k_form_rows<<<cdiv(ncand, 256), 256, 0, st>>>(ncand, dcand, du, ctx->n, P<double>(ctx->f[GHIP_F_MASS]),
+                                                P<int>(ctx->f[GHIP_F_ID]), limited_accretion != 0,
+                                                P<unsigned int>(T.tmp_id) + old,
+                                                P<double>(T.tmp_rows) + (size_t) old * SK_NC, dmold, dmnew);
+  HIPCHK(hipGetLastError());
+  // (sorts, and waits: a duplicate ID is refused before any field changes)
+  GCHK(sk_install(ctx, m, "ghip_sfr_form_sinks"));
+  GCHK(sk_work(ctx, (size_t) m, 0, W));
+  ghip_sfr_form_report *drep = reinterpret_cast<ghip_sfr_form_report *>(W.report);
+  k_form_report<<<1, 64, 0, st>>>(ncand, dcand, dmold, ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]), drep);
+  k_form_apply<<<cdiv(ncand, 256), 256, 0, st>>>(ncand, dcand, dmnew, ctx->n, P<double>(ctx->f[GHIP_F_MASS]),
+                                                 P<int>(ctx->f[GHIP_F_TYPE]));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(report, drep, sizeof(*report), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  // as after ghip_set_field of TYPE and MASS
+  ctx->pot_n = -1;
+  ctx->gt.built = false;
+  ctx->st.built = false;
+  ctx->dd.geom_kept = false;
+  return ghip_check_gas_types(ctx);
+}

@@ -424,6 +424,9 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
       ctx->pot_n = -1;      // (the potential of ghip_potential belongs to the particle set it was made for)
       ctx->visc_ngas = -1;  // (... and alpha / Dtalpha of ghip_visc_set_alpha too)
       ctx->id_given = false;
+      if(ctx->sk.on)
+        ctx->sk.stale = true;   // (the sink table: refused until given again)
+      ctx->sfr_ncand = -1;      // (the candidates of ghip_sfr_cooling are particle indices of the old counts)
     }
   ctx->n = numpart;
   ctx->ngas = ngas;

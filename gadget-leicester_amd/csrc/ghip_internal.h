@@ -178,6 +178,28 @@ struct SinkIter
   std::vector<int> todo;
 };
 
+// what a sink pass needs of its sink (ghip_sink.hip: the host fills it from the resident fields' values;
+// ghip_accretion.hip: a kernel does, from the fields and the resident sink table)
+struct SinkRec
+{
+  double x, y, z, vx, vy, vz, mass, h, mdot, rho;
+  unsigned int id;
+  int timebin, index;
+  unsigned int mark;   // the sink's own resident SwallowID (the swallow pass; 0 in the other passes)
+};
+
+// The resident sink table (ghip_accretion.hip): one row of GHIP_SK_COUNT doubles per Type-5 particle, keyed by
+// P[].ID and kept in ascending ID order, so that no reordering of the particles moves it.
+struct SinkTable
+{
+  DevBuf id, rows;           // u32[n], f64[n][GHIP_SK_COUNT]
+  DevBuf tmp_id, tmp_rows;   // the unsorted image a new table is sorted from
+  DevBuf work;               // selections, sort values, row indices, words, the report
+  int n = 0;
+  bool on = false;           // a table was given (possibly of 0 rows)
+  bool stale = false;        // ghip_set_counts changed the counts since: refused until given again
+};
+
 // One dust pass as ghip_dust.hip runs it: each of the four entry forms (positional, *_grains, GHIP_DD_DUST_* with
 // walk = 0 or GHIP_DUST_GRAINS_FORM) fills this once, and everything below the entry reads only it
 struct DustCall
@@ -695,6 +717,9 @@ struct ghip_ctx
   DevBuf gq_work;                  // partial sums, kick tables and photon momenta of ghip_global_quantities
   FofState fof;                    // ghip_fof (ghip_fof.hip)
   SeqState seq;                    // ghip_rearrange / ghip_peano_order (ghip_sequence.hip)
+  SinkTable sk;                    // the resident sink table (ghip_accretion.hip)
+  DevBuf sfr_cand;                 // i32: the candidates of the last ghip_sfr_cooling, in active-list order
+  int sfr_ncand = -1;              // their number (-1: none in place; ghip_sfr_form_sinks consumes them)
 };
 #define GHIP_NEV 16
 
@@ -765,6 +790,17 @@ int ghip_read_slots(ghip_ctx *ctx, DevBuf &buf, unsigned long long out[GHIP_CK_C
 #define GAS_MARK_MASSLESS (-2.0)    // Mass == 0 under ghip_set_massless_gas_rule; off for hydro_force() under rule 1
 int ghip_mark_converted_gas(ghip_ctx *ctx);
 int ghip_sink_buffers(ghip_ctx *ctx);        // SwallowID / Injected_BH_Energy, zeroed when first made
+// ghip_sink.hip, for the resident forms of ghip_accretion.hip: the h iteration of the sinks and one pass of its
+// kernel sums; the marking pass and the swallow pass (with the victims' masses zeroed) for ns records on the device
+void sink_iter_init(SinkIter &I, int ns);
+int sink_iterate(const ghip_dens_params *p, double ngb_factor, int ns, const double *sums, int ncur, SinkIter &I);
+int sink_density_pass(ghip_ctx *ctx, const ghip_dens_params *p, int ns, const SinkRec *drecs, double *dh,
+                      int *dslot, double *dout, const SinkIter &I, int ncur, int local_only);
+int ghip_bh_launch_evaluate(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const SinkRec *drecs);
+int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const SinkRec *drecs,
+                           const double *dpbh, int *dvict, double *dout);
+// ghip_accretion.hip: ghip_rearrange drops the rows of the Type-5 particles it eliminates (a table exists)
+int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old);
 int ghip_unmark_massless_for_hydro(ghip_ctx *ctx);
 int ghip_remark_massless_for_density(ghip_ctx *ctx);
 int ghip_check_gas_types(ghip_ctx *ctx);   // after TYPE changed: recount, sets ctx->gas_mixed (synchronises)

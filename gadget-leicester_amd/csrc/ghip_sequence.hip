@@ -246,6 +246,7 @@ static int seq_apply(ghip_ctx *ctx, int nn, int ngn)
   ctx->lists_dirty = ctx->gas_list_dirty = true;
   ctx->pot_n = -1;
   ctx->fof.n = -1;
+  ctx->sfr_ncand = -1;   // (the candidates of ghip_sfr_cooling were indices of the old layout)
   S.bytes_moved = moved;
   S.planes = T.np;
   return GHIP_OK;
@@ -326,6 +327,8 @@ extern "C" int ghip_rearrange(ghip_ctx *ctx, const ghip_rearrange_params *p, ghi
     return seq_identity(ctx, n);
   k_seq_maps<<<cdiv(n, 256), 256, 0, st>>>(n, ngn, v, rk, P<int>(S.new_of_old), P<int>(S.old_of_new));
   HIPCHK(hipGetLastError());
+  if(ctx->sk.on && !ctx->sk.stale && w[SW_ELIM])   // the rows of the eliminated Type-5 particles go with them
+    GCHK(ghip_sinks_drop_eliminated(ctx, n, P<int>(S.new_of_old)));
   GCHK(seq_apply(ctx, nn, ngn));
   S.n_before = n;
   S.n_after = nn;

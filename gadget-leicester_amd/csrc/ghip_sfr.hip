@@ -13,7 +13,8 @@
 // candidates are compacted in active-list order without atomics: the pass leaves one 64-bit ballot
 // mask and its population count per wavefront, an exclusive scan of the counts gives every wavefront
 // its first slot, and a scatter writes each candidate at its slot plus the number of candidates below
-// it in the mask.  The host reads two ints and the ncand candidates, never an [ngas] array.
+// it in the mask.  The host reads two ints and the ncand candidates, never an [ngas] array.  The list itself
+// stays on the device (ctx->sfr_cand) for ghip_sfr_form_sinks, which converts exactly those particles.
 #include "ghip_ngb.h"   // the reference's constants
 #include "ghip_prim.h"
 
@@ -197,6 +198,7 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_cooling: comoving needs Time > 0 and hubble_a > 0");
   GHIP_JOIN(ctx);
   *ncand = 0;
+  ctx->sfr_ncand = -1;
   GCHK(ghip_sink_buffers(ctx));
   double *dragheat = nullptr;
   if(p->dust && ctx->dust_heat.p)   // never set: zero everywhere, and it stays unallocated
@@ -208,7 +210,10 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
     }
   const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
   if(nact <= 0)
-    return GHIP_OK;
+    {
+      ctx->sfr_ncand = 0;
+      return GHIP_OK;
+    }
   SfrK K;
   K.cooling = p->cooling;
   K.tapper = p->beta_tapper_off;
@@ -242,11 +247,14 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
   hipStream_t st = ctx->stream;
   const int nb = cdiv(nact, 256);
   const size_t nw = (size_t) nb * (256 / GHIP_WAVE);
-  // sfr_work: mask u64[nw] | cnt i32[nw + 1] | off i32[nw + 1] | nfloor i32 | cand i32[nact]
-  GCHK(ghip_ensure(ctx, ctx->sfr_work, nw * 8 + (2 * nw + 3) * 4 + (size_t) nact * 4 + 64));
+  // sfr_work: mask u64[nw] | cnt i32[nw + 1] | off i32[nw + 1] | nfloor i32
+  GCHK(ghip_ensure(ctx, ctx->sfr_work, nw * 8 + (2 * nw + 3) * 4 + 64));
   unsigned long long *dmask = P<unsigned long long>(ctx->sfr_work);
   int *dcnt = reinterpret_cast<int *>(dmask + nw), *doff = dcnt + nw + 1, *dnfloor = doff + nw + 1;
-  int *dcand = dnfloor + 1;
+  // the candidates stay on the device for ghip_sfr_form_sinks (ghip_accretion.hip)
+  ctx->sfr_ncand = -1;
+  GCHK(ghip_ensure(ctx, ctx->sfr_cand, (size_t) nact * 4));
+  int *dcand = P<int>(ctx->sfr_cand);
   HIPCHK(hipMemsetAsync(dcnt + nw, 0, 4, st));
   HIPCHK(hipMemsetAsync(dnfloor, 0, 4, st));
   const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
@@ -257,17 +265,15 @@ extern "C" int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *nc
                                     P<double>(ctx->bh_injected), dragheat, K, dmask, dcnt, dnfloor);
   HIPCHK(hipGetLastError());
   GCHK(ghip_scan(ctx, dcnt, doff, (int) nw + 1, st));
-  if(cand_idx)
-    {
-      k_sfr_scatter<<<nb, 256, 0, st>>>(nact, dact, dmask, doff, dcand);
-      HIPCHK(hipGetLastError());
-    }
+  k_sfr_scatter<<<nb, 256, 0, st>>>(nact, dact, dmask, doff, dcand);
+  HIPCHK(hipGetLastError());
   int tot[2] = {0, 0};   // candidates, floored grains
   HIPCHK(hipMemcpyAsync(tot, doff + nw, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
   if(tot[0] < 0 || tot[0] > nact)
     return ghip_fail(ctx, GHIP_EDEVICE, "ghip_sfr_cooling: %d candidates of %d active", tot[0], nact);
   *ncand = tot[0];
+  ctx->sfr_ncand = tot[0];
   if(cand_idx && tot[0] > 0)
     {
       HIPCHK(hipMemcpyAsync(cand_idx, dcand, (size_t) tot[0] * 4, hipMemcpyDeviceToHost, st));

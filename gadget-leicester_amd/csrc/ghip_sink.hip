@@ -26,14 +26,7 @@
 // ---------------------------------------------------------------------------------------------
 // density for sink targets: one fixed-h evaluation per launch (gas tree: SphNode list + gp records)
 // ---------------------------------------------------------------------------------------------
-struct SinkRec   // what a pass needs of its sink (host fills it from the resident fields' values)
-{
-  double x, y, z, vx, vy, vz, mass, h, mdot, rho;
-  unsigned int id;
-  int timebin, index;
-  unsigned int mark;   // the sink's own resident SwallowID (the swallow pass; 0 in the other passes)
-};
-
+// (SinkRec, what a pass needs of its sink: ghip_internal.h)
 // out: [6][ns] planes: rho, weighted numngb, sum m w A, sum m w v[3].  local_only (a multi-GPU shard,
 // whose gas tree also holds ghosts): candidates are this shard's own gas particles only -- the other
 // shards add theirs
@@ -134,8 +127,8 @@ static int gather_sinks(ghip_ctx *ctx, int nsink, const int *idx, const unsigned
 // Newton step, which needs SphP[].h.DhsmlDensityFactor: gas only, :613, 629), for sinks `todo[0..ncur)`
 // whose kernel sums of this pass are in sums[k * ns + a] (rho, numngb, entropy, gasvel[3]).  Returns the
 // number of sinks that need another pass (compacted to the front of `todo`).
-static int sink_iterate(const ghip_dens_params *p, double ngb_factor, int ns, const double *sums,
-                        int ncur, SinkIter &I)
+int sink_iterate(const ghip_dens_params *p, double ngb_factor, int ns, const double *sums, int ncur,
+                 SinkIter &I)
 {
   const double desnumngb = p->DesNumNgb * ngb_factor;
   int left = 0;
@@ -191,7 +184,7 @@ static int sink_iterate(const ghip_dens_params *p, double ngb_factor, int ns, co
   return left;
 }
 
-static void sink_iter_init(SinkIter &I, int ns)
+void sink_iter_init(SinkIter &I, int ns)
 {
   I.h.assign(ns, 0.0);
   I.left.assign(ns, 0.0);
@@ -206,9 +199,8 @@ static void sink_iter_init(SinkIter &I, int ns)
 }
 
 // one pass: kernel sums of the sinks todo[0..ncur) at their current h, into dout [6][ns]
-static int sink_density_pass(ghip_ctx *ctx, const ghip_dens_params *p, int ns, const SinkRec *drecs,
-                             double *dh, int *dslot, double *dout, const SinkIter &I, int ncur,
-                             int local_only)
+int sink_density_pass(ghip_ctx *ctx, const ghip_dens_params *p, int ns, const SinkRec *drecs, double *dh,
+                      int *dslot, double *dout, const SinkIter &I, int ncur, int local_only)
 {
   hipStream_t st = ctx->stream;
   TreeDev &t = ctx->st;
@@ -514,6 +506,38 @@ static int check_bh_call(ghip_ctx *ctx, const ghip_bh_params *p, int nsink, cons
   return GHIP_OK;
 }
 
+// the two passes for ns sink records in device memory, on the main stream (the entry points below; the resident
+// form ghip_blackhole_accretion): the marks exist (ghip_sink_buffers), the gravity tree is built
+int ghip_bh_launch_evaluate(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const SinkRec *drecs)
+{
+  TreeDev &t = ctx->gt;
+  k_bh_evaluate<<<ns, 64, 0, ctx->stream>>>(ns, drecs, t.nelem, P<int4>(t.lk), P<double4>(t.cl),
+                                            P<double>(ctx->sx), P<double>(ctx->sy), P<double>(ctx->sz),
+                                            P<int>(t.perm), ctx->n, ctx->ngas, P<int>(ctx->f[GHIP_F_TYPE]),
+                                            P<double>(ctx->f[GHIP_F_MASS]), P<double>(ctx->f[GHIP_F_VEL]),
+                                            P<double>(ctx->f[GHIP_F_DENSITY]), bh_kparams(p),
+                                            P<unsigned int>(ctx->bh_swallow), P<double>(ctx->bh_injected));
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// dpbh [n]: BH_Mass by particle; dvict [n] zeroed by the caller; dout [9][ns].  The victims' masses are 0 afterwards
+int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const SinkRec *drecs,
+                           const double *dpbh, int *dvict, double *dout)
+{
+  TreeDev &t = ctx->gt;
+  hipStream_t st = ctx->stream;
+  const size_t n = (size_t) ctx->n;
+  k_bh_swallow<<<ns, 64, 0, st>>>(ns, drecs, t.nelem, P<int4>(t.lk), P<double4>(t.cl), P<double>(ctx->sx),
+                                  P<double>(ctx->sy), P<double>(ctx->sz), P<int>(t.perm), ctx->n,
+                                  P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_MASS]),
+                                  P<double>(ctx->f[GHIP_F_VEL]), dpbh, bh_kparams(p),
+                                  P<unsigned int>(ctx->bh_swallow), dvict, dout);
+  k_bh_zero_victims<<<cdiv((long long) n, 256), 256, 0, st>>>((int) n, dvict, P<double>(ctx->f[GHIP_F_MASS]));
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
 extern "C" int ghip_sink_reset(ghip_ctx *ctx)
 {
   if(!ctx)
@@ -540,18 +564,10 @@ extern "C" int ghip_blackhole_evaluate(ghip_ctx *ctx, const ghip_bh_params *p, i
   std::vector<SinkRec> S;
   GCHK(gather_sinks(ctx, nsink, sink_idx, sink_id, bh_mdot, bh_density, S));
   hipStream_t st = ctx->stream;
-  TreeDev &t = ctx->gt;
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) nsink * sizeof(SinkRec) + 256));
   HIPCHK(hipMemcpyAsync(ctx->stage.p, S.data(), (size_t) nsink * sizeof(SinkRec),
                         hipMemcpyHostToDevice, st));
-  k_bh_evaluate<<<nsink, 64, 0, st>>>(nsink, P<SinkRec>(ctx->stage), t.nelem, P<int4>(t.lk),
-                                      P<double4>(t.cl), P<double>(ctx->sx), P<double>(ctx->sy),
-                                      P<double>(ctx->sz), P<int>(t.perm), ctx->n, ctx->ngas,
-                                      P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_MASS]),
-                                      P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_DENSITY]),
-                                      bh_kparams(p), P<unsigned int>(ctx->bh_swallow),
-                                      P<double>(ctx->bh_injected));
-  HIPCHK(hipGetLastError());
+  GCHK(ghip_bh_launch_evaluate(ctx, p, nsink, P<SinkRec>(ctx->stage)));
   HIPCHK(ghip_stream_sync(ctx, st));
   return GHIP_OK;
 }
@@ -575,7 +591,6 @@ extern "C" int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, in
   std::vector<SinkRec> S;
   GCHK(gather_sinks(ctx, nsink, sink_idx, sink_id, nullptr, nullptr, S, true));
   hipStream_t st = ctx->stream;
-  TreeDev &t = ctx->gt;
   const size_t n = (size_t) ctx->n;
   // staging: SinkRec[ns] | bh mass of the sinks [ns] | out [9][ns] ; particle-indexed: bh mass [n], victim [n]
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) nsink * (sizeof(SinkRec) + 80) + n * 12 + 512));
@@ -586,14 +601,7 @@ extern "C" int ghip_blackhole_swallow(ghip_ctx *ctx, const ghip_bh_params *p, in
   HIPCHK(hipMemcpyAsync(dbh, sink_bh_mass, (size_t) nsink * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(dpbh, 0, n * 12, st));
   k_bh_scatter<<<cdiv(nsink, 64), 64, 0, st>>>(nsink, dS, dbh, dpbh);
-  k_bh_swallow<<<nsink, 64, 0, st>>>(nsink, dS, t.nelem, P<int4>(t.lk), P<double4>(t.cl),
-                                     P<double>(ctx->sx), P<double>(ctx->sy), P<double>(ctx->sz),
-                                     P<int>(t.perm), ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
-                                     P<double>(ctx->f[GHIP_F_MASS]), P<double>(ctx->f[GHIP_F_VEL]), dpbh,
-                                     bh_kparams(p), P<unsigned int>(ctx->bh_swallow), dvict, dout);
-  k_bh_zero_victims<<<cdiv((long long) n, 256), 256, 0, st>>>((int) n, dvict,
-                                                             P<double>(ctx->f[GHIP_F_MASS]));
-  HIPCHK(hipGetLastError());
+  GCHK(ghip_bh_launch_swallow(ctx, p, nsink, dS, dpbh, dvict, dout));
   std::vector<double> out((size_t) 9 * nsink);
   std::vector<int> vict(nsink);
   HIPCHK(hipMemcpyAsync(out.data(), dout, (size_t) 9 * nsink * 8, hipMemcpyDeviceToHost, st));

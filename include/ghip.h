@@ -268,7 +268,8 @@ long long ghip_device_bytes_in_use(void);
  *   refused     values that were given per gas particle or per particle for the old counts -- alpha /
  *   until       Dtalpha (ghip_visc_set_alpha), DragAccel / DeltaDustMomentum (ghip_kick_set_fields, read
  *   given       under integration flags only), DragHeating, Injected_BH_Momentum / RadAccel, the sink
- *   again       marks: the pass that reads them fails with GHIP_EINVAL and a message instead of reading
+ *   again       marks, the sink table (ghip_sinks_set_table) and the candidates of ghip_sfr_cooling:
+ *               the pass that reads them fails with GHIP_EINVAL and a message instead of reading
  *               them at another pitch; ghip_tree_substep and ghip_tree_kick_nodes refuse a kept tree
  *               (ghip_set_dynamic_tree) of another particle number until a full build has captured the
  *               new one
@@ -693,9 +694,12 @@ int ghip_global_quantities(ghip_ctx *ctx, const ghip_global_params *p, ghip_glob
  * ACCRETION_RADIUS, ACCRETION_DENSITY, ACCRETION_OF_DUST_ONLY, BH_MERGERS_WITHIN_H,
  * BH_THERMALFEEDBACK + TMP_FEEDBACK, DUST, COOLING, SFR, BH_FORM).  The sinks are given by their
  * particle indices; their per-sink state (ID, Mdot, BH_Density, BH_Mass ...) travels in small host
- * arrays, the victims' marks (P[].SwallowID, SphP[].i.Injected_BH_Energy) are resident.  Scalar
- * bookkeeping per sink (blackhole_accretion(), blackhole.c:133-300, 680-760) and the conversion of a
- * flagged gas particle into a sink (sfr_eff.c:606-640, GSL stream) stay host code.  The cooling
+ * arrays, the victims' marks (P[].SwallowID, SphP[].i.Injected_BH_Energy) are resident.  A host
+ * with a resident run keeps the per-sink state in the resident sink table instead ("the sinks on the
+ * resident state" below): ghip_sinks_density, ghip_blackhole_accretion (the whole of
+ * blackhole_accretion(), blackhole.c:70-791, scalar bookkeeping included) and ghip_sfr_form_sinks (the
+ * conversion of a flagged gas particle into a sink, sfr_eff.c:602-629; only the GSL stream stays with
+ * the host) then need no per-sink host array.  The cooling
  * function (DoCooling, cooling.c) runs on the device in ghip_sfr_cooling below.  On a multi-GPU shard the neighbour passes run through GHIP_DD_SINK_DENSITY /
  * GHIP_DD_BH_EVALUATE / GHIP_DD_BH_SWALLOW below. ---- */
 typedef struct
@@ -803,6 +807,108 @@ int ghip_sfr_cooling(ghip_ctx *ctx, const ghip_sfr_params *p, int *ncand, int *c
  * none), *count = how many there are.  Across ranks the host adds pos and count (MPI_Allreduce SUM,
  * as the reference does). */
 int ghip_find_smbh(ghip_ctx *ctx, double SMBHmass, double pos[3], int *count);
+
+/* ---- the sinks on the resident state: the sink table, blackhole_accretion() as a whole
+ * (blackhole.c:70-791 without the log files) and the BH_FORM conversion (sfr_eff.c:602-629), for the
+ * shipped flags BLACK_HOLES, BH_FORM, SWALLOWGAS, ACCRETION_RADIUS, BH_MASS_REAL,
+ * LIMITED_ACCRETION_AND_FEEDBACK.  One GPU: every entry point of this section returns GHIP_EINVAL on a
+ * multi-GPU shard (ghip_dd_init with more than one rank) and on a replicated shard (ghip_set_shard).
+ *
+ * The table holds one row per Type-5 particle, keyed by P[].ID (GHIP_F_ID must have been given since the
+ * counts last changed: GHIP_EINVAL otherwise) and kept in ascending ID order in device memory owned by the
+ * context.  Because it is keyed by ID, ghip_rearrange and ghip_peano_order do not move it; ghip_rearrange
+ * drops the rows of the Type-5 particles it eliminates.  A pass finds its sinks by a device selection of
+ * the active Type-5 particles (in active-list order) and a search of each one's ID in the table: no host
+ * index array enters.  An active Type-5 particle without a row: GHIP_EINVAL, the message names its ID, and
+ * nothing but the marks (reset) has changed.  After ghip_set_counts with CHANGED counts the table is
+ * refused until it is given again.  Mass, Vel, Hsml, TimeBin and Type stay in the GHIP_F_* fields. ---- */
+enum
+{
+  GHIP_SK_BH_MASS = 0,       /* P[].BH_Mass */
+  GHIP_SK_ACCDISC_MASS,      /* P[].AccDisc_Mass */
+  GHIP_SK_BH_MDOT,           /* P[].BH_Mdot */
+  GHIP_SK_DUST_MASS,         /* P[].Dust_Mass */
+  GHIP_SK_TOTAL_MASS,        /* P[].Total_Mass */
+  GHIP_SK_BH_DENSITY,        /* P[].b1.BH_Density */
+  GHIP_SK_BH_ENTROPY,        /* P[].b2.BH_Entropy */
+  GHIP_SK_GASVEL,            /* P[].b3.BH_SurroundingGasVel[3]: three columns */
+  GHIP_SK_NUMNGB = GHIP_SK_GASVEL + 3,   /* PPP[].n.NumNgb */
+  GHIP_SK_ACC_MASS,          /* the last ghip_blackhole_accretion's BH_accreted_Mass (before the reset of :713) */
+  GHIP_SK_ACC_BHMASS,        /* ... BH_accreted_BHMass */
+  GHIP_SK_ACC_DUSTMASS,      /* ... BH_accreted_DustMass */
+  GHIP_SK_ACC_MOMENTUM,      /* ... BH_accreted_momentum[3]: three columns */
+  GHIP_SK_COUNT = GHIP_SK_ACC_MOMENTUM + 3
+};
+/* id [nsink], rows [nsink][GHIP_SK_COUNT] in any order (sorted on the device).  Two rows with the same ID:
+ * GHIP_EINVAL (the message names the ID) and the context holds no table.  nsink = 0: an empty table. */
+int ghip_sinks_set_table(ghip_ctx *ctx, int nsink, const unsigned int *id, const double *rows);
+/* *nsink rows in ascending ID order; id and rows NULL: the count only */
+int ghip_sinks_get_table(ghip_ctx *ctx, int *nsink, unsigned int *id, double *rows);
+int ghip_sinks_clear(ghip_ctx *ctx);   /* no table; its device memory is given back */
+/* The resident form of ghip_sink_density: the same kernels and the same h iteration, for the active Type-5
+ * particles in active-list order (ghip_set_active / ghip_find_next_sync_point).  Hsml is read from and
+ * written to GHIP_F_HSML; NumNgb, BH_Density, BH_Entropy and BH_SurroundingGasVel go into the rows.
+ * *iterations (may be NULL) = the iteration count.  The h update itself is the host's (its pow() decides
+ * the bisection, bit for bit as in ghip_sink_density): per pass the six kernel sums of the sinks come to
+ * the host, the results do not. */
+int ghip_sinks_density(ghip_ctx *ctx, const ghip_dens_params *p, double ngb_factor, int *iterations);
+typedef struct
+{
+  int limited_accretion;            /* -DLIMITED_ACCRETION_AND_FEEDBACK with -DACCRETION_RADIUS (shipped: 1) */
+  int accretion_at_eddington_rate;  /* -DACCRETION_AT_EDDINGTON_RATE (read under limited_accretion only) */
+  int enforce_eddington_limit;      /* -DENFORCE_EDDINGTON_LIMIT */
+  int bh_mass_real;                 /* -DBH_MASS_REAL: meddington from P[].Mass, else from P[].BH_Mass */
+  double medd_fac;   /* (4 M_PI GRAVITY C PROTONMASS / (0.1 C C THOMPSON)) * All.UnitTime_in_s
+                        (blackhole.c:149-159): meddington = medd_fac * mass */
+  double tvisc;      /* All.ViscousTimescale / All.UnitTime_in_s (:196) */
+  double EddingtonFactor;   /* All.BlackHoleEddingtonFactor */
+} ghip_bh_accretion_params;
+typedef struct
+{
+  double TimeBin_BH_mass[32], TimeBin_BH_dynamicalmass[32], TimeBin_BH_Mdot[32];   /* this call's active sinks,
+                                       added in active-list order by one thread (blackhole.c:715-719) */
+  long long swallowed[3];           /* gas / sinks / dust swallowed */
+  int nactive_sinks;
+  int missing;                      /* the call fails -- 1: an active Type-5 particle has no row; 2: there are more
+                                       of them than rows, so two of them carry the same ID */
+  unsigned int missing_id;          /* ... the largest such ID */
+  int pad;
+} ghip_bh_accretion_report;
+/* blackhole_accretion() for the active Type-5 particles in active-list order (a sink of Mass == 0 that an
+ * earlier step swallowed included, as in the reference).  Needs the gravity tree of this step.
+ *   Mdot (blackhole.c:119-286), one thread per sink: dt = (TimeBin ? 1 << TimeBin : 0) * bh->dt_fac;
+ *     limited_accretion: mdot = AccDisc_Mass / (dt + tvisc), clamped to EddingtonFactor * meddington under
+ *     enforce_eddington_limit, AccDisc_Mass -= mdot dt, BH_Mass += mdot dt (:196-202); with
+ *     accretion_at_eddington_rate mdot = EddingtonFactor * meddington, BH_Mass += mdot dt (:205-206);
+ *     without limited_accretion mdot = 0 (BONDI is not built) under the clamp of :218-219.  BH_Mdot = mdot.
+ *   the marks are reset; blackhole_evaluate and blackhole_evaluate_swallow are the kernels of
+ *     ghip_blackhole_evaluate / ghip_blackhole_swallow, reading mdot, BH_Density, the IDs and BH_Mass from
+ *     device memory; only a sink whose own SwallowID is 0 swallows; BH_Mass of a swallowed sink becomes 0
+ *   finish (:679-735), one thread per sink: if BH_accreted_Mass > 0, Vel = (Vel Mass + momentum) / (Mass +
+ *     accreted_Mass), Mass += accreted_Mass, BH_Mass += accreted_BHMass, Dust_Mass += accreted_DustMass and
+ *     Total_Mass += accreted_Mass (bh->dust), AccDisc_Mass += accreted_Mass (limited_accretion; at the
+ *     Eddington rate then Mass = BH_Mass), written into GHIP_F_VEL, GHIP_F_MASS and the rows.
+ * All of this arithmetic is compiled without contraction: it equals the op-by-op IEEE evaluation.
+ * One device-to-host copy of the report is the only blocking read of the call.  Afterwards, as after
+ * ghip_blackhole_swallow: victims have mass 0 and the trees are stale in mass only. */
+int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh, const ghip_bh_accretion_params *p,
+                             ghip_bh_accretion_report *report);
+typedef struct
+{
+  int stars_converted;
+  int pad;
+  double sum_mass_stars;            /* the masses before the change, added in list order (sfr_eff.c:607) */
+  int converted_in_bin[32];         /* per TimeBin: what the host subtracts from TimeBinCountSph (:628) */
+} ghip_sfr_form_report;
+/* sfr_eff.c:602-629 for the candidates the last ghip_sfr_cooling found (kept on the device; ncand must be
+ * the count it returned, and the particles must not have been reordered since: GHIP_EINVAL otherwise, and
+ * nothing changes).  Candidate k in active-list order: Type = 5, Mass *= 0.995 + 0.005 * u01[k], and a new
+ * row with its ID, all zero except BH_Mass = Mass -- with limited_accretion AccDisc_Mass = Mass and
+ * BH_Mass = 0.  u01 [ncand]: the host's gsl_rng_uniform draws, one per conversion, in order.  A context
+ * without a table gets one.  The candidates are consumed.  Afterwards the state is as after any change of
+ * TYPE (the gas block is mixed until ghip_rearrange takes the records out of it; both trees are stale). */
+int ghip_sfr_form_sinks(ghip_ctx *ctx, int ncand, const double *u01, int limited_accretion,
+                        ghip_sfr_form_report *report);
 
 /* ---- the dust-gas drag passes of the shipped flag bundle (DUST, DUST_TIMESTEP, DUST_POWERLAW,
  * CONSTANT_MEAN_MOLECULAR_WEIGHT): dust_density() and dust_drag() (dust.c:60-1029, called at accel.c:194,
