@@ -471,7 +471,7 @@ EXPORTS = [
     "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size",
     "ghip_kick_get_fields", "ghip_rearrange", "ghip_peano_order", "ghip_sequence_get_map", "ghip_sequence_get_info",
     "ghip_sinks_set_table", "ghip_sinks_get_table", "ghip_sinks_clear", "ghip_sinks_density",
-    "ghip_blackhole_accretion", "ghip_sfr_form_sinks"]
+    "ghip_blackhole_accretion", "ghip_sfr_form_sinks", "ghip_dd_sinks_args_size"]
 
 
 def lib():
@@ -606,6 +606,11 @@ def lib():
         if L.ghip_dd_wind_args_size() != C.sizeof(DdWindArgs):
             raise RuntimeError("DdWindArgs: %d bytes here, %d in libghip.so"
                                % (C.sizeof(DdWindArgs), L.ghip_dd_wind_args_size()))
+        L.ghip_dd_sinks_args_size.argtypes = []
+        L.ghip_dd_sinks_args_size.restype = C.c_size_t
+        if L.ghip_dd_sinks_args_size() != C.sizeof(DdSinksArgs):
+            raise RuntimeError("DdSinksArgs: %d bytes here, %d in libghip.so"
+                               % (C.sizeof(DdSinksArgs), L.ghip_dd_sinks_args_size()))
         L.ghip_wind_density.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
         L.ghip_wind_spread.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, vp, vp, vp]
         L.ghip_wind_feedback.argtypes = [vp, C.POINTER(WindParams), C.c_int, vp, C.POINTER(WindState),
@@ -1713,6 +1718,41 @@ def dd_sink_args(sinks, sink_ids=None, dens=None, ngb_factor=1.0, bh=None, hsml=
     A.sink_bh_mass, A.acc_mass, A.acc_bhmass = vp(a["bh_mass"]), vp(a["acc_mass"]), vp(a["acc_bhmass"])
     A.acc_dustmass, A.acc_momentum, A.counts = vp(a["acc_dustmass"]), vp(a["acc_momentum"]), vp(a["counts"])
     return A, a
+
+
+SINKS_RESIDENT_FORM = 1   # `walk` of dd_begin / dd_run for DD_SINK_DENSITY / DD_BH_SWALLOW with DdSinksArgs
+
+
+class DdSinksArgs(C.Structure):
+    """ghip_dd_sinks_args (include/ghip.h): the resident form of the sink operations on a multi-GPU shard"""
+    _fields_ = [("dens", C.POINTER(DensParams)), ("ngb_factor", C.c_double), ("iterations", C.POINTER(C.c_int)),
+                ("bh", C.POINTER(BhParams)), ("acc", C.POINTER(BhAccretionParams)),
+                ("report", C.POINTER(BhAccretionReport))]
+
+
+def dd_sinks_args(dens=None, ngb_factor=1.0, bh=None, acc=None):
+    """(args, keep) for DD_SINK_DENSITY (dens, ngb_factor) or DD_BH_SWALLOW (bh, acc) begun with walk =
+    SINKS_RESIDENT_FORM on one shard: a filled DdSinksArgs and the dict of what it points to -- keep it alive until
+    the operation has finished; then keep["iterations"].value and dd_sinks_report(keep) hold the results."""
+    keep = dict(iterations=C.c_int(0), report=BhAccretionReport(), _dens=dens, _bh=bh, _acc=acc)
+    A = DdSinksArgs()
+    A.dens = C.pointer(dens) if dens is not None else None
+    A.ngb_factor = float(ngb_factor)
+    A.iterations = C.pointer(keep["iterations"])
+    A.bh = C.pointer(bh) if bh is not None else None
+    A.acc = C.pointer(acc) if acc is not None else None
+    A.report = C.pointer(keep["report"])
+    return A, keep
+
+
+def dd_sinks_report(keep):
+    """what a finished DD_BH_SWALLOW (walk = SINKS_RESIDENT_FORM) left in `keep` of dd_sinks_args, as
+    ForcePath.blackhole_accretion returns it: the sums over THIS shard's sinks, counts = the particles of this
+    shard that were swallowed"""
+    rep = keep["report"]
+    return dict(bin_mass=np.array(rep.TimeBin_BH_mass), bin_dynmass=np.array(rep.TimeBin_BH_dynamicalmass),
+                bin_mdot=np.array(rep.TimeBin_BH_Mdot), counts=np.array(rep.swallowed, np.int64),
+                nactive=rep.nactive_sinks)
 
 
 class DdDustArgs(C.Structure):

@@ -16,6 +16,10 @@
 // Sinks are few (hundreds): everything below but the two neighbour passes is one thread per sink, and the sums
 // that have an order (the report) are added by a single thread in active-list order.
 //
+// On a multi-GPU shard the table holds the rows of the shard's own Type-5 particles: GHIP_DD_MIGRATE carries a row
+// with its particle, and the two passes are collectives (GHIP_DD_SINK_DENSITY / GHIP_DD_BH_SWALLOW begun with
+// walk = GHIP_SINKS_RESIDENT_FORM) -- the second half of this file.
+//
 // ghip_blackhole_accretion waits for the device once, for its report.  The number of active sinks is not known
 // on the host before that: the passes are launched for as many records as the table has rows, and a record
 // beyond the active sinks is inert (mass 0: marks nothing; its own mark set: sweeps nothing).
@@ -156,6 +160,7 @@ static int sk_install(ghip_ctx *ctx, int m, const char *who)
       int w[SKW_WORDS];
       HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
+      T.last_dup = (unsigned int) w[SKW_DUPID];
       if(w[SKW_DUP])
         return ghip_fail(ctx, GHIP_EINVAL, "%s: two rows of the sink table have the ID %u (the context holds no "
                          "table now)", who, (unsigned int) w[SKW_DUPID]);
@@ -168,9 +173,6 @@ static int sk_install(ghip_ctx *ctx, int m, const char *who)
 // what every entry point of the section refuses
 static int sk_enter(ghip_ctx *ctx, const char *who, bool need_table)
 {
-  if(ctx->dd.on && ctx->dd.nranks > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a multi-GPU shard (%d ranks): the sink table covers "
-                     "one GPU", who, ctx->dd.nranks);
   if(ctx->shard_n > 1)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a replicated shard (ghip_set_shard with %d ranks)",
                      who, ctx->shard_n);
@@ -186,6 +188,16 @@ static int sk_enter(ghip_ctx *ctx, const char *who, bool need_table)
       if(!ctx->sk.on)
         return ghip_fail(ctx, GHIP_EINVAL, "%s: no sink table (ghip_sinks_set_table)", who);
     }
+  return GHIP_OK;
+}
+
+// the two passes that one GPU runs alone are collectives on a multi-GPU shard, where the table holds the rows of
+// the shard's own Type-5 particles
+static int sk_one_gpu(ghip_ctx *ctx, const char *who, const char *op)
+{
+  if(ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: on a multi-GPU shard (%d ranks) use %s with walk = "
+                     "GHIP_SINKS_RESIDENT_FORM (ghip_dd_sinks_args)", who, ctx->dd.nranks, op);
   return GHIP_OK;
 }
 
@@ -446,6 +458,7 @@ extern "C" int ghip_sinks_density(ghip_ctx *ctx, const ghip_dens_params *p, doub
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: bad arguments");
   if(iterations)
     *iterations = 0;
+  GCHK(sk_one_gpu(ctx, "ghip_sinks_density", "GHIP_DD_SINK_DENSITY"));
   GCHK(sk_enter(ctx, "ghip_sinks_density", true));
   GCHK(ghip_finish_gas_tree(ctx));
   if(!ctx->st.built)
@@ -540,11 +553,12 @@ __global__ void k_acc_marks(int G, const int *__restrict__ words, const int *__r
 __global__ void k_acc_finish(int G, const int *__restrict__ words, const int *__restrict__ row,
                              const SinkRec *__restrict__ recs, const double *__restrict__ out,
                              const int *__restrict__ victim, int n, double *__restrict__ vel,
-                             double *__restrict__ mass, double *__restrict__ rows, AccK K)
+                             double *__restrict__ mass, double *__restrict__ rows, AccK K,
+                             const unsigned long long *__restrict__ gate)
 {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
-  if(a >= cnt || SK_BAD(words, G))
+  if(a >= cnt || SK_BAD(words, G) || (gate && *gate))   // gate: the shards' common verdict, not 0 = the call fails
     return;
   const int i = recs[a].index;
   double *R = rows + (size_t) row[a] * SK_NC;
@@ -613,22 +627,8 @@ __global__ void k_acc_report(int G, const int *__restrict__ words, const int *__
     }
 }
 
-extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh, const ghip_bh_accretion_params *p,
-                                        ghip_bh_accretion_report *report)
+static AccK acc_kparams(const ghip_bh_params *bh, const ghip_bh_accretion_params *p)
 {
-  if(ctx)
-    GHIP_JOIN(ctx);
-  if(!ctx || !bh || !p || !report)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: bad arguments");
-  memset(report, 0, sizeof(*report));
-  GCHK(sk_enter(ctx, "ghip_blackhole_accretion", true));
-  if(!ctx->gt.built)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: call ghip_tree_build first");
-  GCHK(ghip_sink_buffers(ctx));
-  SinkTable &T = ctx->sk;
-  hipStream_t st = ctx->stream;
-  const int G = T.n;
-  const size_t n = (size_t) ctx->n;
   AccK K;
   K.limited = p->limited_accretion != 0;
   K.at_edd = p->accretion_at_eddington_rate != 0;
@@ -639,6 +639,27 @@ extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh,
   K.tvisc = p->tvisc;
   K.eddf = p->EddingtonFactor;
   K.dt_fac = bh->dt_fac;
+  return K;
+}
+
+extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh, const ghip_bh_accretion_params *p,
+                                        ghip_bh_accretion_report *report)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  if(!ctx || !bh || !p || !report)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: bad arguments");
+  memset(report, 0, sizeof(*report));
+  GCHK(sk_one_gpu(ctx, "ghip_blackhole_accretion", "GHIP_DD_BH_SWALLOW"));
+  GCHK(sk_enter(ctx, "ghip_blackhole_accretion", true));
+  if(!ctx->gt.built)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: call ghip_tree_build first");
+  GCHK(ghip_sink_buffers(ctx));
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int G = T.n;
+  const size_t n = (size_t) ctx->n;
+  const AccK K = acc_kparams(bh, p);
   // staging: SinkRec[G] | out [9][G] ; particle-indexed: bh mass [n], victim [n]
   const size_t g1 = (size_t) (G > 0 ? G : 1), n1 = n > 0 ? n : 1;
   GCHK(ghip_ensure(ctx, ctx->stage, g1 * (sizeof(SinkRec) + 72) + n1 * 12 + 512));
@@ -667,7 +688,7 @@ extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh,
       HIPCHK(hipGetLastError());
       GCHK(ghip_bh_launch_swallow(ctx, bh, G, drecs, dpbh, dvict, dout));
       k_acc_finish<<<nb, 64, 0, st>>>(G, W.words, W.row, drecs, dout, dvict, ctx->n, P<double>(ctx->f[GHIP_F_VEL]),
-                                      P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows), K);
+                                      P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows), K, nullptr);
       HIPCHK(hipGetLastError());
     }
   k_acc_report<<<1, 64, 0, st>>>(G, W.words, W.row, drecs, dout,
@@ -817,4 +838,595 @@ extern "C" int ghip_sfr_form_sinks(ghip_ctx *ctx, int ncand, const double *u01, 
   ctx->st.built = false;
   ctx->dd.geom_kept = false;
   return ghip_check_gas_types(ctx);
+}
+
+extern "C" size_t ghip_dd_sinks_args_size(void) { return sizeof(ghip_dd_sinks_args); }
+
+// ---------------------------------------------------------------------------------------------
+// the rows in GHIP_DD_MIGRATE: a departing Type-5 particle takes its row to the shard that receives it, in a
+// second all-to-all-v of (ID, SK_NC doubles) records beside the particles' own (ghip_dd.hip, migrate_step)
+// ---------------------------------------------------------------------------------------------
+struct SkMigRec
+{
+  unsigned long long id;
+  double c[SK_NC];
+};
+struct SkMigOff
+{
+  int v[GHIP_MAXRANKS];
+};
+
+// rows per destination; keep[row] = 0 for a row that departs.  (A departing Type-5 particle without a row departs
+// without one: the next pass says so.)
+__global__ void k_skm_count(int total, const int *__restrict__ list, const unsigned long long *__restrict__ mask,
+                            const int *__restrict__ type, const int *__restrict__ idf, int nrows,
+                            const unsigned int *__restrict__ ids, int *__restrict__ keep, int *__restrict__ cnt)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= total)
+    return;
+  const int i = list[a];
+  if(type[i] != 5 || mask[i] == 0)
+    return;
+  const int r = d_sk_find(nrows, ids, (unsigned int) idf[i]);
+  if(r < 0)
+    return;
+  keep[r] = 0;
+  atomicAdd(cnt + (__ffsll((long long) mask[i]) - 1), 1);
+}
+
+// (the order within a destination is that of the atomics: the receiver sorts by ID)
+__global__ void k_skm_pack(int total, const int *__restrict__ list, const unsigned long long *__restrict__ mask,
+                           const int *__restrict__ type, const int *__restrict__ idf, int nrows,
+                           const unsigned int *__restrict__ ids, const double *__restrict__ rows, SkMigOff off,
+                           SkMigOff lim, int *__restrict__ cur, SkMigRec *__restrict__ out)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= total)
+    return;
+  const int i = list[a];
+  if(type[i] != 5 || mask[i] == 0)
+    return;
+  const unsigned int id = (unsigned int) idf[i];
+  const int r = d_sk_find(nrows, ids, id);
+  if(r < 0)
+    return;
+  const int dest = __ffsll((long long) mask[i]) - 1;
+  const int k = atomicAdd(cur + dest, 1);
+  if(k >= lim.v[dest])   // (cannot happen: k_skm_count counted the same records)
+    return;
+  SkMigRec &R = out[off.v[dest] + k];
+  R.id = id;
+  for(int c = 0; c < SK_NC; c++)
+    R.c[c] = rows[(size_t) r * SK_NC + c];
+}
+
+__global__ void k_skm_unpack(int nrecv, const SkMigRec *__restrict__ rec, unsigned int *__restrict__ id,
+                             double *__restrict__ rows)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= nrecv)
+    return;
+  id[a] = (unsigned int) rec[a].id;
+  for(int c = 0; c < SK_NC; c++)
+    rows[(size_t) a * SK_NC + c] = rec[a].c[c];
+}
+
+int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigned long long *mask)
+{
+  static_assert(sizeof(SkMigRec) == 8 + 8 * SK_NC, "SkMigRec layout");
+  DDState &D = ctx->dd;
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int m = T.n, P_ = D.nranks;
+  GCHK(ghip_ensure(ctx, D.sk_keep, (size_t) (m > 0 ? m : 1) * 4));
+  GCHK(ghip_ensure(ctx, D.sk_rcnt, (size_t) 2 * GHIP_MAXRANKS * 4));
+  HIPCHK(hipMemsetAsync(D.sk_rcnt.p, 0, (size_t) 2 * GHIP_MAXRANKS * 4, st));
+  int cnt[GHIP_MAXRANKS];
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    cnt[r] = D.sk_rscount[r] = D.sk_rsoff[r] = 0;
+  if(m > 0)
+    k_sk_fill<<<cdiv(m, 256), 256, 0, st>>>(m, 1, P<int>(D.sk_keep));
+  const bool any = m > 0 && total > 0 && ctx->id_given;
+  if(any)
+    {
+      k_skm_count<<<cdiv(total, 256), 256, 0, st>>>(total, list, mask, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                   P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.id),
+                                                   P<int>(D.sk_keep), P<int>(D.sk_rcnt));
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(cnt, D.sk_rcnt.p, (size_t) P_ * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+    }
+  HIPCHK(hipGetLastError());
+  SkMigOff off, lim;
+  int tot = 0;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    {
+      const int c = (r < P_ && cnt[r] > 0 && cnt[r] <= m) ? cnt[r] : 0;
+      off.v[r] = tot;
+      lim.v[r] = c;
+      D.sk_rscount[r] = c;
+      D.sk_rsoff[r] = tot;
+      tot += c;
+    }
+  GCHK(ghip_ensure(ctx, D.sk_rsend, (size_t) (tot > 0 ? tot : 1) * sizeof(SkMigRec)));
+  if(tot > 0)
+    {
+      k_skm_pack<<<cdiv(total, 256), 256, 0, st>>>(total, list, mask, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                  P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.id),
+                                                  P<double>(T.rows), off, lim, P<int>(D.sk_rcnt) + GHIP_MAXRANKS,
+                                                  P<SkMigRec>(D.sk_rsend));
+      HIPCHK(hipGetLastError());
+    }
+  return GHIP_OK;
+}
+
+void ghip_sinks_mig_post(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  ghip_dd_set_alltoallv(D, D.sk_rsend.p, sizeof(SkMigRec), D.sk_rscount, D.sk_rsoff, &D.sk_rrecv);
+}
+
+// after the second exchange: the rows that left are dropped, the arrivals join, the table is sorted again
+int ghip_sinks_mig_merge(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int m = T.n, nrecv = D.x.rtotal;
+  int sent = 0;
+  for(int r = 0; r < D.nranks; r++)
+    sent += D.sk_rscount[r];
+  if(sent == 0 && nrecv == 0)
+    return GHIP_OK;
+  SkWork W;
+  GCHK(sk_work(ctx, (size_t) (m + nrecv + 1), 0, W));
+  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+  int kept = 0;
+  if(m > 0)
+    {
+      GCHK(ghip_select_flagged(ctx, nullptr, P<int>(D.sk_keep), W.b, W.words + SKW_KEPT, m, st));
+      HIPCHK(hipMemcpyAsync(&kept, W.words + SKW_KEPT, 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(kept < 0 || kept > m)
+        return ghip_fail(ctx, GHIP_EDEVICE, "GHIP_DD_MIGRATE: %d of %d rows of the sink table kept", kept, m);
+    }
+  const int tot = kept + nrecv;
+  if(tot > 0)
+    {
+      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) tot * 4));
+      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) tot * SK_NC * 8));
+    }
+  if(kept > 0)
+    {
+      k_sk_gather_ids<<<cdiv(kept, 256), 256, 0, st>>>(kept, W.b, P<unsigned int>(T.id), P<unsigned int>(T.tmp_id));
+      k_sk_gather_rows<<<cdiv((long long) kept * SK_NC, 256), 256, 0, st>>>(kept, W.b, P<double>(T.rows),
+                                                                           P<double>(T.tmp_rows));
+    }
+  if(nrecv > 0)
+    k_skm_unpack<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<SkMigRec>(D.sk_rrecv), P<unsigned int>(T.tmp_id) + kept,
+                                                  P<double>(T.tmp_rows) + (size_t) kept * SK_NC);
+  HIPCHK(hipGetLastError());
+  return sk_install(ctx, tot, "GHIP_DD_MIGRATE");
+}
+
+// ---------------------------------------------------------------------------------------------
+// ghip_sinks_density and ghip_blackhole_accretion on shards: GHIP_DD_SINK_DENSITY / GHIP_DD_BH_SWALLOW begun with
+// walk = GHIP_SINKS_RESIDENT_FORM.  The exchanges are those of the per-pass forms (ghip_sink.hip); what differs is
+// where a shard's sinks come from (the device selection and the table) and where the results go (the fields and
+// the rows).  A shard that cannot post its sinks -- no table, an active Type-5 particle without a row -- posts ONE
+// failure record instead (index -1: timebin = the kind, id, x = its rank) and holds its error (ghip_dd_hold).
+// Every shard reads the same gathered records, so k_skd_check gives every shard the same verdict without another
+// exchange: kind << 40 | rank << 32 | id, the largest, 0 = fine.  When it is not 0 the gathered records are made
+// inert (mass 0: marks nothing; mark set: sweeps nothing), the rows are put back as they were before the Mdot step,
+// the finish is gated, every exchange still takes place, and all shards fail together at the end.
+// ---------------------------------------------------------------------------------------------
+enum { SKD_NOROW = 1, SKD_LOCALDUP, SKD_NOTABLE, SKD_DUP };
+#define SKD_WORD(kind, rank, id) \
+  (((unsigned long long) (kind) << 40) | ((unsigned long long) ((rank) & 0xff) << 32) | (unsigned long long) (id))
+
+__global__ void k_skd_check(int ns, const SinkRec *__restrict__ recs, unsigned long long *__restrict__ gw)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a >= ns)
+    return;
+  const int idx = recs[a].index;
+  const unsigned int id = recs[a].id;
+  if(idx < 0)
+    {
+      atomicMax(gw, SKD_WORD(recs[a].timebin, (int) recs[a].x, id));
+      return;
+    }
+  for(int b = a + 1; b < ns; b++)   // (hundreds of sinks)
+    if(recs[b].index >= 0 && recs[b].id == id)
+      {
+        atomicMax(gw, SKD_WORD(SKD_DUP, 0xff, id));
+        break;
+      }
+}
+
+__global__ void k_skd_inert(int ns, SinkRec *__restrict__ recs, const unsigned long long *__restrict__ gw)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < ns && *gw)
+    {
+      recs[a].mass = 0;
+      recs[a].mark = 1;
+    }
+}
+
+__global__ void k_skd_restore(long long m, const double *__restrict__ snap, double *__restrict__ rows,
+                              const unsigned long long *__restrict__ gw)
+{
+  const long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+  if(e < m && *gw)
+    rows[e] = snap[e];
+}
+
+__global__ void k_skd_h(int ns, const SinkRec *__restrict__ recs, double *__restrict__ h)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if(a < ns)
+    h[a] = recs[a].h;
+}
+
+// the all-gathered partial planes [nranks][9][ns] of this shard's own sinks [off, off + cnt), added in ascending rank
+// order from 0.0 with plain adds: the bits of the per-pass form's host loop (dd_sink_sum_parts).  out: [9][cnt]
+__global__ void k_skd_sum_own(int nranks, int ns, int off, int cnt, const double *__restrict__ parts,
+                              double *__restrict__ out)
+{
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if(e >= 9 * cnt)
+    return;
+  const int plane = e / cnt, a = e % cnt;
+  double s = 0.0;
+  for(int r = 0; r < nranks; r++)
+    s += parts[((size_t) r * 9 + plane) * ns + off + a];
+  out[e] = s;
+}
+
+// the report on a shard: the counts are those of THIS shard's particles (its own partial planes, all sinks), and
+// a failed call reports its verdict and no sums
+__global__ void k_skd_report(int ns, const double *__restrict__ part, const unsigned long long *__restrict__ gw,
+                             ghip_bh_accretion_report *__restrict__ rep)
+{
+  if(blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  for(int k = 0; k < 3; k++)
+    {
+      long long c = 0;
+      for(int g = 0; g < ns; g++)
+        c += (long long) (part[(size_t) (6 + k) * ns + g] + 0.5);
+      rep->swallowed[k] = c;
+    }
+  const unsigned long long w = *gw;
+  if(w)
+    {
+      for(int b = 0; b < 32; b++)
+        rep->TimeBin_BH_mass[b] = rep->TimeBin_BH_dynamicalmass[b] = rep->TimeBin_BH_Mdot[b] = 0;
+      rep->missing = (int) (w >> 40);
+      rep->missing_id = (unsigned int) w;
+    }
+}
+
+static int skd_w(ghip_ctx *ctx, SkWork &W) { return sk_work(ctx, ctx->dd.sk_na, ctx->dd.sk_nrow, W); }
+
+// all shards stop together: the shard that posted the failure record with its own message, the others with the
+// verdict they all read
+static int skd_fail(ghip_ctx *ctx, unsigned long long w, const char *who)
+{
+  if(ctx->dd.held.rc != GHIP_OK)
+    return ghip_fail(ctx, ctx->dd.held.rc, "%s", ctx->dd.held.msg.c_str());
+  const int kind = (int) (w >> 40), rank = (int) ((w >> 32) & 0xff);
+  const unsigned int id = (unsigned int) w;
+  const char *tail = "every shard stops here; nothing but the marks was changed";
+  switch(kind)
+    {
+    case SKD_NOROW:
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: on shard %d the active Type-5 particle with ID %u has no row in the "
+                       "sink table; %s", who, rank, id, tail);
+    case SKD_LOCALDUP:
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: shard %d has more active Type-5 particles than rows in its sink table: "
+                       "two of them carry the same ID; %s", who, rank, tail);
+    case SKD_NOTABLE:
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: shard %d holds no sink table (or has not been given GHIP_F_ID): either "
+                       "all shards hold one (an empty one counts) or none does; %s", who, rank, tail);
+    default:
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: two active Type-5 particles of the run carry the ID %u; %s", who, id,
+                       tail);
+    }
+}
+
+int ghip_dd_sinks_begin(ghip_ctx *ctx, int op, const void *params)
+{
+  DDState &D = ctx->dd;
+  const char *who = op == GHIP_DD_SINK_DENSITY ? "GHIP_DD_SINK_DENSITY" : "GHIP_DD_BH_SWALLOW";
+  D.sinks = *reinterpret_cast<const ghip_dd_sinks_args *>(params);
+  const ghip_dd_sinks_args &A = D.sinks;
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a replicated shard (ghip_set_shard with %d ranks)", who,
+                     ctx->shard_n);
+  if(op == GHIP_DD_SINK_DENSITY)
+    {
+      if(!A.dens)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s (resident form): bad arguments", who);
+      if(A.iterations)
+        *A.iterations = 0;
+      if(!ctx->st.built)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_DENSITY of this step first", who);
+    }
+  else
+    {
+      if(!A.bh || !A.acc || !A.report)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s (resident form): bad arguments", who);
+      memset(A.report, 0, sizeof(*A.report));
+      if(!ctx->gt.built)
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: run GHIP_DD_GRAVITY of this step first", who);
+    }
+  D.sink = ghip_dd_sink_args();   // (what the shared passes of ghip_sink.hip read)
+  D.sink.dens = A.dens;
+  D.sink.ngb_factor = A.ngb_factor;
+  D.sink.bh = A.bh;
+  D.sk_form = GHIP_SINKS_RESIDENT_FORM;
+  return GHIP_OK;
+}
+
+// POST: this shard's active sinks, found in its table, to every shard
+static int skd_post(ghip_ctx *ctx, bool swallow, const char *who)
+{
+  DDState &D = ctx->dd;
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const ghip_dd_sinks_args &A = D.sinks;
+  GCHK(ghip_sink_buffers(ctx));
+  if(swallow)
+    {
+      // P[].SwallowID = 0, Injected_BH_Energy = 0 on every shard (ghip_sink_reset)
+      HIPCHK(hipMemsetAsync(ctx->bh_swallow.p, 0, ctx->bh_swallow.cap, st));
+      HIPCHK(hipMemsetAsync(ctx->bh_injected.p, 0, ctx->bh_injected.cap, st));
+    }
+  GCHK(ghip_ensure(ctx, D.sk_gw, 64));
+  HIPCHK(hipMemsetAsync(D.sk_gw.p, 0, 64, st));
+  int kind = 0, cnt = 0;
+  unsigned int errid = 0;
+  SkWork W;
+  D.sk_na = D.sk_nrow = 1;
+  if(!ctx->id_given || !T.on || T.stale)
+    {
+      kind = SKD_NOTABLE;
+      GCHK(skd_w(ctx, W));
+      HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+      if(!ctx->id_given)
+        ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table is keyed by P[].ID, and GHIP_F_ID has not "
+                                    "been given since ghip_set_counts (ghip_set_field)", who));
+      else if(T.on)
+        ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table was given for other counts: give it again "
+                                    "after ghip_set_counts (ghip_sinks_set_table)", who));
+      else
+        ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: this shard holds no sink table (ghip_sinks_set_table; "
+                                    "either all shards hold one or none does)", who));
+    }
+  else
+    {
+      int nact = 0, w[SKW_WORDS];
+      GCHK(sk_select(ctx, T.n, W, &nact));
+      D.sk_na = (size_t) (nact > 0 ? nact : 1);
+      D.sk_nrow = (size_t) (T.n > 0 ? T.n : 1);
+      // (the first of the two blocking reads: the exchange needs the count)
+      HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(w[SKW_ERR])
+        {
+          kind = SKD_NOROW;
+          errid = (unsigned int) w[SKW_ERRID];
+          ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-5 particle with ID %u has no row in this "
+                                      "shard's sink table (%d rows, %d active sinks); nothing but the marks was "
+                                      "changed", who, errid, T.n, w[SKW_COUNT]));
+        }
+      else if(w[SKW_COUNT] > T.n)
+        {
+          kind = SKD_LOCALDUP;
+          ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: %d active Type-5 particles for %d rows of this shard's "
+                                      "sink table: two of them carry the same ID; nothing but the marks was changed",
+                                      who, w[SKW_COUNT], T.n));
+        }
+      else
+        cnt = w[SKW_COUNT] > 0 ? w[SKW_COUNT] : 0;
+    }
+  D.sk_cnt = cnt;
+  const int nsend = kind ? 1 : cnt;
+  GCHK(ghip_ensure(ctx, D.sk_send, (size_t) (nsend > 0 ? nsend : 1) * sizeof(SinkRec)));
+  if(kind)
+    {
+      SinkRec E;
+      memset(&E, 0, sizeof(E));
+      E.x = (double) D.rank;
+      E.rho = 1.0;
+      E.id = errid;
+      E.timebin = kind;
+      E.index = -1;
+      E.mark = 1;
+      HIPCHK(hipMemcpyAsync(D.sk_send.p, &E, sizeof(E), hipMemcpyHostToDevice, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // (`E` lives on this frame)
+    }
+  else if(cnt > 0)
+    {
+      AccK K = {};
+      if(swallow)
+        {
+          K = acc_kparams(A.bh, A.acc);
+          GCHK(ghip_ensure(ctx, D.sk_snap, (size_t) T.n * SK_NC * 8));
+          HIPCHK(hipMemcpyAsync(D.sk_snap.p, T.rows.p, (size_t) T.n * SK_NC * 8, hipMemcpyDeviceToDevice, st));
+        }
+      k_acc_begin<<<cdiv(cnt, 64), 64, 0, st>>>(cnt, W.words, W.b, W.row, ctx->n, P<double>(ctx->f[GHIP_F_POS]),
+                                                P<double>(ctx->f[GHIP_F_VEL]), P<double>(ctx->f[GHIP_F_MASS]),
+                                                P<double>(ctx->f[GHIP_F_HSML]), P<int>(ctx->f[GHIP_F_TIMEBIN]),
+                                                P<int>(ctx->f[GHIP_F_ID]), P<double>(T.rows), K, swallow ? 1 : 0,
+                                                P<SinkRec>(D.sk_send), nullptr);
+      HIPCHK(hipGetLastError());
+    }
+  int scount[GHIP_MAXRANKS], soff[GHIP_MAXRANKS];
+  for(int r = 0; r < D.nranks; r++)
+    {
+      scount[r] = nsend;
+      soff[r] = 0;
+    }
+  ghip_dd_set_alltoallv(D, D.sk_send.p, sizeof(SinkRec), scount, soff, &D.sk_all);
+  return 1;
+}
+
+int ghip_dd_sinks_step(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const ghip_dd_sinks_args &A = D.sinks;
+  const bool swallow = D.op == GHIP_DD_BH_SWALLOW;
+  const char *who = swallow ? "GHIP_DD_BH_SWALLOW" : "GHIP_DD_SINK_DENSITY";
+  enum { POST, EVALUATE, SWALLOW, FINISH };   // (the density's third phase is COLLECT of ghip_sink.hip)
+  const int cnt = D.sk_cnt;
+  const size_t n = (size_t) ctx->n;
+  unsigned long long *gw = P<unsigned long long>(D.sk_gw);
+  if(D.phase == POST)
+    {
+      D.phase = EVALUATE;
+      return skd_post(ctx, swallow, who);
+    }
+  if(D.phase == EVALUATE)
+    {
+      D.sk_total = D.x.rtotal;
+      D.sk_off = D.x.roff[D.rank];
+      const int ns = D.sk_total;
+      if(D.x.rcount[D.rank] != (D.held.rc != GHIP_OK ? 1 : cnt))
+        return ghip_fail(ctx, GHIP_ECOMM, "%s: the exchange lost this shard's own records", who);
+      if(ns == 0)
+        return 0;   // no active sink anywhere (the report is zero)
+      SinkRec *all = P<SinkRec>(D.sk_all);
+      k_skd_check<<<cdiv(ns, 64), 64, 0, st>>>(ns, all, gw);
+      HIPCHK(hipGetLastError());
+      if(!swallow)
+        {
+          // the h iteration is the host's: it starts from every sink's h, and it can stop here
+          GCHK(ghip_ensure(ctx, D.sk_part, (size_t) ns * 48));
+          k_skd_h<<<cdiv(ns, 64), 64, 0, st>>>(ns, all, P<double>(D.sk_part));
+          HIPCHK(hipGetLastError());
+          unsigned long long w = 0;
+          sink_iter_init(D.sk_it, ns);
+          HIPCHK(hipMemcpyAsync(D.sk_it.h.data(), D.sk_part.p, (size_t) ns * 8, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(&w, gw, 8, hipMemcpyDeviceToHost, st));
+          HIPCHK(ghip_stream_sync(ctx, st));
+          if(w)
+            return skd_fail(ctx, w, who);
+          D.sk_ncur = ns;
+          D.sk_iter = 0;
+          D.phase = 2;   // COLLECT
+          return dd_sink_density_pass(ctx);
+        }
+      k_skd_inert<<<cdiv(ns, 64), 64, 0, st>>>(ns, all, gw);
+      if(cnt > 0)
+        k_skd_restore<<<cdiv((long long) T.n * SK_NC, 256), 256, 0, st>>>((long long) T.n * SK_NC, P<double>(D.sk_snap),
+                                                                         P<double>(T.rows), gw);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_bh_launch_evaluate(ctx, A.bh, ns, all));
+      // each sink's own SwallowID as the marking pass left it goes into its record (the particle is local: its
+      // mark saw every claim), BH_Mass by particle stays here; the records are posted again
+      GCHK(ghip_ensure(ctx, D.sk_work, (n > 0 ? n : 1) * 12 + 64));
+      double *dpbh = P<double>(D.sk_work);
+      if(n > 0)
+        HIPCHK(hipMemsetAsync(dpbh, 0, n * 12, st));
+      if(cnt > 0)
+        {
+          SkWork W;
+          GCHK(skd_w(ctx, W));
+          k_acc_marks<<<cdiv(cnt, 64), 64, 0, st>>>(cnt, W.words, W.row, P<unsigned int>(ctx->bh_swallow),
+                                                    P<double>(T.rows), P<SinkRec>(D.sk_send), dpbh);
+          HIPCHK(hipGetLastError());
+        }
+      D.x.kind = 2;   // (the same send buffer, counts and offsets as the first time)
+      D.phase = SWALLOW;
+      return 1;
+    }
+  const int ns = D.sk_total;
+  double *dpbh = P<double>(D.sk_work);
+  int *dvict = reinterpret_cast<int *>(dpbh + n);
+  if(D.phase == SWALLOW)
+    {
+      if(D.x.rtotal != ns)
+        return ghip_fail(ctx, GHIP_ECOMM, "%s: %d records came back, %d went", who, D.x.rtotal, ns);
+      SinkRec *all = P<SinkRec>(D.sk_all);
+      k_skd_inert<<<cdiv(ns, 64), 64, 0, st>>>(ns, all, gw);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_ensure(ctx, D.sk_part, (size_t) ns * 72));
+      GCHK(ghip_bh_launch_swallow(ctx, A.bh, ns, all, dpbh, dvict, P<double>(D.sk_part)));
+      ghip_dd_set_allgather(D, D.sk_part.p, (size_t) ns * 72, &D.sk_parts);
+      D.phase = FINISH;
+      return 1;
+    }
+  if(D.phase == FINISH)
+    {
+      SkWork W;
+      GCHK(skd_w(ctx, W));
+      GCHK(ghip_ensure(ctx, D.sk_own, (size_t) (cnt > 0 ? cnt : 1) * 72));
+      ghip_bh_accretion_report *drep = reinterpret_cast<ghip_bh_accretion_report *>(W.report);
+      if(cnt > 0)
+        {
+          k_skd_sum_own<<<cdiv(9 * cnt, 64), 64, 0, st>>>(D.nranks, ns, D.sk_off, cnt, P<double>(D.sk_parts),
+                                                         P<double>(D.sk_own));
+          k_acc_finish<<<cdiv(cnt, 64), 64, 0, st>>>(cnt, W.words, W.row, P<SinkRec>(D.sk_send), P<double>(D.sk_own),
+                                                     dvict, ctx->n, P<double>(ctx->f[GHIP_F_VEL]),
+                                                     P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows),
+                                                     acc_kparams(A.bh, A.acc), gw);
+          HIPCHK(hipGetLastError());
+        }
+      k_acc_report<<<1, 64, 0, st>>>(cnt, W.words, W.row, P<SinkRec>(D.sk_send), P<double>(D.sk_own),
+                                     P<double>(ctx->f[GHIP_F_MASS]), P<double>(T.rows), drep);
+      k_skd_report<<<1, 64, 0, st>>>(ns, P<double>(D.sk_part), gw, drep);
+      HIPCHK(hipGetLastError());
+      // the second blocking read: the report, and the verdict with it
+      unsigned long long w = 0;
+      HIPCHK(hipMemcpyAsync(A.report, drep, sizeof(*A.report), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&w, gw, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(w)
+        return skd_fail(ctx, w, who);
+      ctx->gt.built = false;   // masses changed: the trees' moments are stale
+      ctx->st.built = false;
+      D.geom_kept = true;      // (their geometry is not: the dust passes may still use them)
+      return 0;
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the resident sink passes have no phase %d", D.phase);
+}
+
+// the end of GHIP_DD_SINK_DENSITY in its resident form: the converged values of this shard's own sinks
+int ghip_dd_sinks_store_density(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  hipStream_t st = ctx->stream;
+  const int cnt = D.sk_cnt, off = D.sk_off;
+  const SinkIter &I = D.sk_it;
+  if(cnt > 0)
+    {
+      std::vector<double> hout((size_t) cnt * 7);
+      for(int a = 0; a < cnt; a++)
+        {
+          const int g = off + a;
+          hout[a] = I.h[g];
+          hout[(size_t) cnt + a] = I.numngb[g];
+          hout[2 * (size_t) cnt + a] = I.rho[g];
+          hout[3 * (size_t) cnt + a] = I.entropy[g];
+          for(int k = 0; k < 3; k++)
+            hout[4 * (size_t) cnt + 3 * (size_t) a + k] = I.gasvel[3 * (size_t) g + k];
+        }
+      SkWork W;
+      GCHK(skd_w(ctx, W));
+      GCHK(ghip_ensure(ctx, D.sk_own, (size_t) cnt * 72));
+      HIPCHK(hipMemcpyAsync(D.sk_own.p, hout.data(), (size_t) cnt * 56, hipMemcpyHostToDevice, st));
+      k_sk_store_density<<<cdiv(cnt, 64), 64, 0, st>>>(cnt, W.b, W.row, P<double>(D.sk_own),
+                                                       P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->sk.rows));
+      HIPCHK(hipGetLastError());
+      HIPCHK(ghip_stream_sync(ctx, st));   // (hout goes out of scope)
+    }
+  if(D.sinks.iterations)
+    *D.sinks.iterations = D.sk_iter;
+  return 0;
 }

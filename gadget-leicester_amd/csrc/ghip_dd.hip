@@ -1945,12 +1945,34 @@ __global__ void k_mig_flags_old(int n, int ngas, const unsigned long long *__res
     v[i] = mask[i] ? 0ULL : (i < ngas ? 1ULL : (1ULL << 32));
 }
 
+// (a header record -- slot MIG_SLOTS-1 = MIG_HEADER, "the sender holds a sink table" -- is no particle: counted in
+// *headers, ranked nowhere)
+#define MIG_HEADER 2ULL
 __global__ void k_mig_flags_new(int nrecv, const MigRec *__restrict__ rec,
-                                unsigned long long *__restrict__ v)
+                                unsigned long long *__restrict__ v, unsigned long long *__restrict__ headers)
 {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if(j < nrecv)
-    v[j] = rec[j].s[MIG_SLOTS - 1] ? 1ULL : (1ULL << 32);
+  if(j >= nrecv)
+    return;
+  const unsigned long long kind = rec[j].s[MIG_SLOTS - 1];
+  if(kind == MIG_HEADER)
+    {
+      v[j] = 0;
+      atomicAdd(headers, 1ULL);
+    }
+  else
+    v[j] = kind ? 1ULL : (1ULL << 32);
+}
+
+struct MigHeaders
+{
+  int pos[GHIP_MAXRANKS];   // where the header of each destination goes, -1: none
+};
+__global__ void k_mig_headers(int nranks, MigHeaders H, MigRec *__restrict__ out)
+{
+  const int r = blockIdx.x, k = threadIdx.x;
+  if(r < nranks && H.pos[r] >= 0 && k < MIG_SLOTS)
+    out[H.pos[r]].s[k] = k == MIG_SLOTS - 1 ? MIG_HEADER : 0ULL;
 }
 
 struct MigCounts
@@ -1993,6 +2015,8 @@ __global__ void k_mig_move_new(int nrecv, const MigRec *__restrict__ rec,
   if(a >= nrecv)
     return;
   const MigRec &r = rec[a];
+  if(r.s[MIG_SLOTS - 1] == MIG_HEADER)
+    return;
   const bool isgas = r.s[MIG_SLOTS - 1] != 0;
   const int nn = C.kg + C.ko + C.rg + C.ro, ngn = C.kg + C.rg;
   const unsigned long long rk = rank[a];
@@ -2017,6 +2041,10 @@ __global__ void k_mig_move_new(int nrecv, const MigRec *__restrict__ rec,
 // GHIP_DD_MIGRATE:
 //   SEND   the owner of every local particle's key; those of other shards packed   -> all-to-all-v of MigRec
 //   MERGE  kept and received particles into the new layout (gas first), the resident arrays swapped
+// and, when the shards hold sink tables (ghip_accretion.hip; a header record in the first exchange says who does):
+//   ROWS         the rows of the Type-5 particles that left                          -> all-to-all-v of row records
+//   ROWS_STATUS  departed rows dropped, arrivals merged, the table sorted again      -> all-gather of the status
+//                an ID that stands twice in one table stops all shards
 static int migrate_begin(ghip_ctx *ctx, int, const void *, int)
 {
   static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
@@ -2049,7 +2077,7 @@ static int migrate_step(ghip_ctx *ctx)
   DevBuf *const wind[2] = {(ctx->wind_inj.p && ctx->wind_inj_ngas == ng) ? &ctx->wind_inj : nullptr,
                            (ctx->wind_ra.p && ctx->wind_ra_ngas == ng) ? &ctx->wind_ra : nullptr};
   DevBuf *const wind_shadow[2] = {wind[0] ? &D.wind_shadow[0] : nullptr, wind[1] ? &D.wind_shadow[1] : nullptr};
-  enum { SEND, MERGE, DONE };
+  enum { SEND, MERGE, DONE, ROWS, ROWS_STATUS };
   if(D.phase == SEND)
     {
       GHIP_JOIN(ctx);
@@ -2074,8 +2102,36 @@ static int migrate_step(ghip_ctx *ctx)
         }
       else if(n > 0)
         HIPCHK(hipMemsetAsync(D.mig_mask.p, 0, (size_t) n * 8, st));
-      GCHK(ghip_ensure(ctx, D.mig_send, (size_t) (total > 0 ? total : 1) * sizeof(MigRec)));
-      if(total > 0)
+      // A shard that holds a sink table (ghip_accretion.hip) says so to every other shard with one header record in
+      // front of that shard's particles, and the rows of its departing Type-5 particles follow in a second exchange:
+      // every shard then sees who holds a table, and all of them enter the second exchange or none does.
+      D.mig_tab = ctx->sk.on && !ctx->sk.stale && P_ > 1;
+      GCHK(ghip_ensure(ctx, D.mig_send, (size_t) (D.mig_tab ? total + P_ : (total > 0 ? total : 1)) * sizeof(MigRec)));
+      if(D.mig_tab)
+        {
+          GCHK(ghip_sinks_mig_pack(ctx, total, P<int>(D.mig_list), P<unsigned long long>(D.mig_mask)));
+          const MigTable T = mig_table(ctx->f, heat, visc, wind);
+          MigHeaders H;
+          int shift = 0;
+          for(int r = 0; r < GHIP_MAXRANKS; r++)
+            H.pos[r] = -1;
+          for(int r = 0; r < P_; r++)
+            {
+              const int from = soff[r];
+              soff[r] += shift;
+              if(r == D.rank)
+                continue;
+              H.pos[r] = soff[r];
+              if(scount[r] > 0)
+                k_mig_pack<<<cdiv(scount[r], 256), 256, 0, st>>>(scount[r], P<int>(D.mig_list) + from, n, ng, T,
+                                                                P<MigRec>(D.mig_send) + soff[r] + 1);
+              scount[r]++;
+              shift++;
+            }
+          k_mig_headers<<<P_, 64, 0, st>>>(P_, H, P<MigRec>(D.mig_send));
+          HIPCHK(hipGetLastError());
+        }
+      else if(total > 0)
         {
           k_mig_pack<<<cdiv(total, 256), 256, 0, st>>>(total, P<int>(D.mig_list), n, ng,
                                                       mig_table(ctx->f, heat, visc, wind), P<MigRec>(D.mig_send));
@@ -2091,32 +2147,50 @@ static int migrate_step(ghip_ctx *ctx)
       const int nrecv = D.x.rtotal;
       D.mig_in = nrecv;
       D.phase = DONE;
+      if(nrecv == 0 && D.mig_out == 0 && !D.mig_tab)
+        {
+          ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
+          return GHIP_OK;    // nobody left, nobody came: the resident arrays stay as they are
+        }
+      // new positions: kept gas, received gas, kept others, received others
+      GCHK(ghip_ensure(ctx, D.mig_scan, (size_t) (n + nrecv + 2) * 16 + 8));
+      unsigned long long *vo = P<unsigned long long>(D.mig_scan), *ro = vo + (n + 1),
+                         *vn = ro + (n + 1), *rn = vn + (nrecv + 1), *hw = rn + (nrecv + 1);
+      // (layout: flags_old[n+1], rank_old[n+1], flags_new[nrecv+1], rank_new[nrecv+1]; the extra
+      // zero entry makes the last rank the total; then the count of header records)
+      HIPCHK(hipMemsetAsync(vo, 0, (size_t) (n + nrecv + 2) * 16 + 8, st));
+      if(n > 0)
+        k_mig_flags_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), vo);
+      if(nrecv > 0)
+        k_mig_flags_new<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<MigRec>(D.mig_recv), vn, hw);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_scan(ctx, vo, ro, n + 1, ctx->stream));
+      GCHK(ghip_scan(ctx, vn, rn, nrecv + 1, ctx->stream));
+      unsigned long long tot[3];
+      HIPCHK(hipMemcpyAsync(&tot[0], ro + n, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&tot[1], rn + nrecv, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&tot[2], hw, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      // every other shard's header, or none: all shards see the same picture and stop together, before anything moved
+      const int nhdr = (int) tot[2];
+      if(nhdr != (D.mig_tab ? P_ - 1 : 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_MIGRATE: %d of the %d other shards hold a sink table and this one "
+                         "holds %s: either all shards hold one (an empty one counts) or none does "
+                         "(ghip_sinks_set_table / ghip_sinks_clear); every shard stops here, nothing was moved",
+                         nhdr, P_ - 1, D.mig_tab ? "one" : "none");
+      D.mig_in = nrecv - nhdr;
       ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
-      if(nrecv == 0 && D.mig_out == 0)
-        return GHIP_OK;   // nobody left, nobody came: the resident arrays stay as they are
+      if(D.mig_in == 0 && D.mig_out == 0)
+        {
+          ghip_sinks_mig_post(ctx);   // (only shards with tables come here: the rows' exchange is a collective)
+          D.phase = ROWS;
+          return 1;
+        }
       // (a wind field held for another gas count is not carried: it is dropped with the layout it belonged to)
       if(!wind[0])
         ctx->wind_inj_ngas = -1;
       if(!wind[1])
         ctx->wind_ra_ngas = -1;
-      // new positions: kept gas, received gas, kept others, received others
-      GCHK(ghip_ensure(ctx, D.mig_scan, (size_t) (n + nrecv + 2) * 16));
-      unsigned long long *vo = P<unsigned long long>(D.mig_scan), *ro = vo + (n + 1),
-                         *vn = ro + (n + 1), *rn = vn + (nrecv + 1);
-      // (layout: flags_old[n+1], rank_old[n+1], flags_new[nrecv+1], rank_new[nrecv+1]; the extra
-      // zero entry makes the last rank the total)
-      HIPCHK(hipMemsetAsync(vo, 0, (size_t) (n + nrecv + 2) * 16, st));
-      if(n > 0)
-        k_mig_flags_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), vo);
-      if(nrecv > 0)
-        k_mig_flags_new<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<MigRec>(D.mig_recv), vn);
-      HIPCHK(hipGetLastError());
-      GCHK(ghip_scan(ctx, vo, ro, n + 1, ctx->stream));
-      GCHK(ghip_scan(ctx, vn, rn, nrecv + 1, ctx->stream));
-      unsigned long long tot[2];
-      HIPCHK(hipMemcpyAsync(&tot[0], ro + n, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(&tot[1], rn + nrecv, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
       MigCounts C;
       C.kg = (int) (tot[0] & 0xffffffffULL);
       C.ko = (int) (tot[0] >> 32);
@@ -2180,7 +2254,30 @@ static int migrate_step(ghip_ctx *ctx)
       ctx->nactive = -1;
       ctx->lists_dirty = ctx->gas_list_dirty = true;
       ctx->gas_types_unknown = true;   // (an arrival may be a converted particle of its old gas block)
-      return GHIP_OK;
+      if(!D.mig_tab)
+        return GHIP_OK;
+      ghip_sinks_mig_post(ctx);   // the rows of the Type-5 particles that left   -> all-to-all-v of row records
+      D.phase = ROWS;
+      return 1;
+    }
+  if(D.phase == ROWS)
+    {
+      // the rows that left are dropped, the arrivals merged, the table sorted by ID again; an ID that now stands
+      // twice stops all shards (the status round carries it)
+      const bool failed = ghip_dd_hold(ctx, ghip_sinks_mig_merge(ctx));
+      GCHK(dd_post_status(ctx, failed ? (double) ctx->sk.last_dup : 0.0, failed));
+      D.phase = ROWS_STATUS;
+      return 1;
+    }
+  if(D.phase == ROWS_STATUS)
+    {
+      double id = 0;
+      int failed = -1;
+      GCHK(dd_read_status(ctx, &id, &failed));
+      D.phase = DONE;
+      return ghip_dd_raise(ctx, failed, "GHIP_DD_MIGRATE: shard %d could not merge the arriving rows into its sink "
+                           "table: the ID %u stands in it twice (its own message says so; that shard holds no table "
+                           "now); every shard stops here", failed, (unsigned int) id);
     }
   return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: migration has no phase %d", D.phase);
 }

@@ -198,6 +198,7 @@ struct SinkTable
   int n = 0;
   bool on = false;           // a table was given (possibly of 0 rows)
   bool stale = false;        // ghip_set_counts changed the counts since: refused until given again
+  unsigned int last_dup = 0; // the ID that the last refused installation found twice
 };
 
 // One dust pass as ghip_dust.hip runs it: each of the four entry forms (positional, *_grains, GHIP_DD_DUST_* with
@@ -303,6 +304,20 @@ struct DDState
   DevBuf sk_work;                 // per pass: h[total] | slots[total]; swallow: BH masses [n] | victims [n]
   int sk_total = 0, sk_off = 0, sk_iter = 0, sk_ncur = 0;
   SinkIter sk_it;                 // h iteration state of ALL sinks (identical on all ranks)
+  // ... in their resident form (walk = GHIP_SINKS_RESIDENT_FORM, ghip_accretion.hip): no host array, this shard's
+  // sinks are selected on the device and found in its sink table
+  ghip_dd_sinks_args sinks = {};  // arguments of the operation in progress
+  int sk_form = 0;                // 0: the per-pass form; GHIP_SINKS_RESIDENT_FORM
+  int sk_cnt = 0;                 // this shard's active sinks (0 on a shard that posted a failure record)
+  size_t sk_na = 1, sk_nrow = 1;  // the sizes its selection asked of SinkTable::work (the same block every phase)
+  DevBuf sk_gw;                   // u64: the verdict on the gathered records (0: fine), the same on all shards
+  DevBuf sk_snap;                 // f64: this shard's rows before the Mdot step, put back when the call fails
+  DevBuf sk_own;                  // f64[9][sk_cnt]: the rank-ordered sums of this shard's own sinks
+  // the rows of the sink table in GHIP_DD_MIGRATE
+  bool mig_tab = false;           // this shard holds a table: its records carry a header, the rows follow
+  DevBuf sk_keep, sk_rcnt;        // i32[rows]: 0 = the row departs; i32: rows per destination, pack cursors
+  DevBuf sk_rsend, sk_rrecv;      // (ID, GHIP_SK_COUNT doubles) records out / in
+  int sk_rscount[GHIP_MAXRANKS], sk_rsoff[GHIP_MAXRANKS];
   // the dust passes on shards (ghip_dust.hip): this shard's grains go to the shards their spheres reach,
   // partial d7 come back (density), drag records are scattered into every shard's own gas (drag)
   DustCall dust;                  // the operation in progress
@@ -801,6 +816,16 @@ int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const
                            const double *dpbh, int *dvict, double *dout);
 // ghip_accretion.hip: ghip_rearrange drops the rows of the Type-5 particles it eliminates (a table exists)
 int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old);
+// the rows in GHIP_DD_MIGRATE (ghip_accretion.hip): the rows of the departing Type-5 particles `list` (destination
+// 1 << r in mask[]) packed per destination; the second exchange posted; departed rows out, arrivals in, sorted
+int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigned long long *mask);
+void ghip_sinks_mig_post(ghip_ctx *ctx);
+int ghip_sinks_mig_merge(ghip_ctx *ctx);
+// the resident form of the sink operations on shards (ghip_accretion.hip), called by ghip_dd_sink_begin / _step
+int ghip_dd_sinks_begin(ghip_ctx *ctx, int op, const void *params);
+int ghip_dd_sinks_step(ghip_ctx *ctx);
+int ghip_dd_sinks_store_density(ghip_ctx *ctx);
+int dd_sink_density_pass(ghip_ctx *ctx);
 int ghip_unmark_massless_for_hydro(ghip_ctx *ctx);
 int ghip_remark_massless_for_density(ghip_ctx *ctx);
 int ghip_check_gas_types(ghip_ctx *ctx);   // after TYPE changed: recount, sets ctx->gas_mixed (synchronises)

@@ -533,7 +533,8 @@ int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const
                                   P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_MASS]),
                                   P<double>(ctx->f[GHIP_F_VEL]), dpbh, bh_kparams(p),
                                   P<unsigned int>(ctx->bh_swallow), dvict, dout);
-  k_bh_zero_victims<<<cdiv((long long) n, 256), 256, 0, st>>>((int) n, dvict, P<double>(ctx->f[GHIP_F_MASS]));
+  if(n > 0)   // (a shard may hold no particle)
+    k_bh_zero_victims<<<cdiv((long long) n, 256), 256, 0, st>>>((int) n, dvict, P<double>(ctx->f[GHIP_F_MASS]));
   HIPCHK(hipGetLastError());
   return GHIP_OK;
 }
@@ -752,10 +753,17 @@ extern "C" int ghip_cooling_and_starformation(ghip_ctx *ctx, double Timebase_int
 // all-gathered and added in rank order on every shard: the h iteration then takes the same decisions
 // everywhere without another exchange, and a victim, local to exactly one shard, sees every claim.
 // ---------------------------------------------------------------------------------------------
-int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int)
+int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int walk)
 {
   GHIP_JOIN(ctx);
   DDState &D = ctx->dd;
+  // the resident form (ghip_accretion.hip) takes another struct; the marking pass alone has no such form
+  if(op == GHIP_DD_BH_EVALUATE && walk != 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_BH_EVALUATE: walk = %d; it has only its per-pass form (walk = 0): "
+                     "GHIP_DD_BH_SWALLOW with walk = GHIP_SINKS_RESIDENT_FORM runs the marking pass itself", walk);
+  if(walk == GHIP_SINKS_RESIDENT_FORM)
+    return ghip_dd_sinks_begin(ctx, op, params);
+  D.sk_form = 0;
   D.sink = *reinterpret_cast<const ghip_dd_sink_args *>(params);
   const ghip_dd_sink_args &A = D.sink;
   if(A.nsink < 0 || (A.nsink > 0 && !A.sink_idx))
@@ -784,7 +792,7 @@ int ghip_dd_sink_begin(ghip_ctx *ctx, int op, const void *params, int)
 
 // one density pass of the sinks still iterating, over this shard's own gas; the partial sums go
 // to everybody
-static int dd_sink_density_pass(ghip_ctx *ctx)
+int dd_sink_density_pass(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
   const int ns = D.sk_total;
@@ -826,6 +834,9 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
   hipStream_t st = ctx->stream;
   const int op = D.op, nloc = A.nsink;
   enum { POST, EVALUATE, COLLECT };
+  // the resident form has its own phases (ghip_accretion.hip); its density shares the passes of COLLECT below
+  if(D.sk_form && !(op == GHIP_DD_SINK_DENSITY && D.phase == COLLECT))
+    return ghip_dd_sinks_step(ctx);
   if(D.phase == POST)
     {
       // this shard's sinks to every shard (itself included: the receive buffer is the rank-ordered
@@ -930,6 +941,8 @@ int ghip_dd_sink_step(ghip_ctx *ctx)
                              "h-iterations (reference: endrun(1155))", D.sk_ncur, maxiter);
           return dd_sink_density_pass(ctx);
         }
+      if(D.sk_form)
+        return ghip_dd_sinks_store_density(ctx);
       const SinkIter &I = D.sk_it;
       for(int a = 0; a < nloc; a++)
         {

@@ -353,6 +353,21 @@ class DomainShards:
         self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WIND_FORM)
         return [self.B.dd_wind_result(b[1]) for b in built]
 
+    def sinks_density(self, params, ngb_factor):
+        """GHIP_DD_SINK_DENSITY in its SINKS_RESIDENT_FORM: ForcePath.sinks_density for the active Type-5 particles
+        of all shards, each found in its shard's sink table -> the iteration count (the same on all shards)"""
+        built = [self.B.dd_sinks_args(dens=params, ngb_factor=ngb_factor) for _ in self.paths]
+        self.run(self.B.DD_SINK_DENSITY, [b[0] for b in built], self.B.SINKS_RESIDENT_FORM)
+        return built[0][1]["iterations"].value
+
+    def blackhole_accretion(self, bh_params, acc_params):
+        """GHIP_DD_BH_SWALLOW in its SINKS_RESIDENT_FORM: blackhole_accretion() as one collective -> one dict per
+        shard as ForcePath.blackhole_accretion returns it: the per-bin sums and nactive are those of the shard's
+        own sinks, counts the particles of that shard that were swallowed (add them in rank order)"""
+        built = [self.B.dd_sinks_args(bh=bh_params, acc=acc_params) for _ in self.paths]
+        self.run(self.B.DD_BH_SWALLOW, [b[0] for b in built], self.B.SINKS_RESIDENT_FORM)
+        return [self.B.dd_sinks_report(b[1]) for b in built]
+
     def wind_density(self, params, wind, dt_jump):
         """GHIP_DD_WIND in its WIND_DENSITY_FORM: one virtual_density() -> [(new_density, drmin, counts)] per shard"""
         built = [self.B.dd_wind_args(params, wind[r], dt_jump=dt_jump[r]) for r in range(len(self.paths))]
@@ -530,6 +545,21 @@ class DomainRank:
         args, keep = self.B.dd_wind_args(params, wind, state=state if len(wind) else _empty_wind_state())
         self._run(self.B.WIND_OP, args, self.B.WIND_FORM)
         return self.B.dd_wind_result(keep)
+
+    def sinks_density(self, params, ngb_factor):
+        """GHIP_DD_SINK_DENSITY in its SINKS_RESIDENT_FORM, a collective: ForcePath.sinks_density for the active
+        Type-5 particles of all ranks, this rank's found in its own sink table -> the iteration count"""
+        args, keep = self.B.dd_sinks_args(dens=params, ngb_factor=ngb_factor)
+        self._run(self.B.DD_SINK_DENSITY, args, self.B.SINKS_RESIDENT_FORM)
+        return keep["iterations"].value
+
+    def blackhole_accretion(self, bh_params, acc_params):
+        """GHIP_DD_BH_SWALLOW in its SINKS_RESIDENT_FORM, a collective: blackhole_accretion() -> a dict as
+        ForcePath.blackhole_accretion returns it, of this rank's own sinks and swallowed particles (the host adds
+        the ranks' values, blackhole.c:659-661, 749-751)"""
+        args, keep = self.B.dd_sinks_args(bh=bh_params, acc=acc_params)
+        self._run(self.B.DD_BH_SWALLOW, args, self.B.SINKS_RESIDENT_FORM)
+        return self.B.dd_sinks_report(keep)
 
     def wind_density(self, params, wind, dt_jump):
         """GHIP_DD_WIND in its WIND_DENSITY_FORM, a collective -> (new_density, drmin, counts) of this rank's list"""

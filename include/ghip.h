@@ -811,8 +811,11 @@ int ghip_find_smbh(ghip_ctx *ctx, double SMBHmass, double pos[3], int *count);
 /* ---- the sinks on the resident state: the sink table, blackhole_accretion() as a whole
  * (blackhole.c:70-791 without the log files) and the BH_FORM conversion (sfr_eff.c:602-629), for the
  * shipped flags BLACK_HOLES, BH_FORM, SWALLOWGAS, ACCRETION_RADIUS, BH_MASS_REAL,
- * LIMITED_ACCRETION_AND_FEEDBACK.  One GPU: every entry point of this section returns GHIP_EINVAL on a
- * multi-GPU shard (ghip_dd_init with more than one rank) and on a replicated shard (ghip_set_shard).
+ * LIMITED_ACCRETION_AND_FEEDBACK.  Every entry point of this section returns GHIP_EINVAL on a replicated
+ * shard (ghip_set_shard).  On a multi-GPU shard (ghip_dd_init with more than one rank) the table holds the
+ * rows of the Type-5 particles resident on that shard and travels with GHIP_DD_MIGRATE; ghip_sinks_density
+ * and ghip_blackhole_accretion return GHIP_EINVAL there and name the collective to use instead
+ * (GHIP_DD_SINK_DENSITY / GHIP_DD_BH_SWALLOW with walk = GHIP_SINKS_RESIDENT_FORM, ghip_dd_sinks_args).
  *
  * The table holds one row per Type-5 particle, keyed by P[].ID (GHIP_F_ID must have been given since the
  * counts last changed: GHIP_EINVAL otherwise) and kept in ascending ID order in device memory owned by the
@@ -1189,6 +1192,42 @@ typedef struct
 #define GHIP_DD_BH_EVALUATE 6    /* needs GHIP_DD_GRAVITY of this step (the shard's gravity tree) */
 #define GHIP_DD_BH_SWALLOW 7     /* a sink whose own SwallowID is set swallows nothing (blackhole.c:528-532, see
                                     ghip_blackhole_swallow): its mark travels to the other shards in its record */
+/* The sinks on the resident state of shards and ranks: GHIP_DD_SINK_DENSITY and GHIP_DD_BH_SWALLOW begun with
+ * walk = GHIP_SINKS_RESIDENT_FORM take a ghip_dd_sinks_args and no host array.  Every shard holds the rows
+ * of the Type-5 particles resident on it (ghip_sinks_set_table / _get_table / _clear / ghip_sfr_form_sinks act
+ * on those rows); either all shards hold a table (an empty one counts) or none does.  GHIP_DD_MIGRATE carries
+ * the row of a departing Type-5 particle to the shard that receives the particle, as a second all-to-all-v
+ * of (ID, GHIP_SK_COUNT doubles) records that runs only when the shards hold tables; a departing Type-5
+ * particle without a row departs without one; an ID that arrives where it already has a row fails the
+ * migration on all shards.  One shard with a table beside one without: GHIP_DD_MIGRATE and both forms below
+ * fail on all shards, nothing moved.
+ *   GHIP_DD_SINK_DENSITY  ghip_sinks_density for the active Type-5 particles of all shards: each shard selects
+ *     its own in active-list order and finds their rows; the exchanges are those of the walk = 0 form (the
+ *     96-byte records to everybody, 6 partial sums per sink and h pass all-gathered, the h update on every
+ *     shard's host).  The home shard writes h into GHIP_F_HSML and NumNgb, BH_Density, BH_Entropy and
+ *     BH_SurroundingGasVel into the rows.  *iterations (may be NULL): the iteration count.
+ *   GHIP_DD_BH_SWALLOW    ghip_blackhole_accretion as ONE collective: the Mdot loop into the rows and the reset
+ *     of the marks; the records to everybody; blackhole_evaluate for all sinks over each shard's particles;
+ *     the records again, now with each sink's own SwallowID as the marking pass left it (BH_Mass stays at
+ *     home: a swallowed sink's BH_Mass is read on the shard that holds it); the sweep and the all-gather of
+ *     its 9 partial planes; their sum in ascending rank order from 0.0 on the device (the bits of the
+ *     walk = 0 form's host loop); the finish into GHIP_F_VEL, GHIP_F_MASS and the rows of this shard's sinks.
+ *     *report: this shard's sinks (the per-bin sums, nactive_sinks) and the particles of THIS shard that
+ *     were swallowed -- the per-task values of the reference, which the host adds (blackhole.c:659-661,
+ *     749-751).  Blocking reads: the selection's words and the report.  Afterwards as after the walk = 0
+ *     form: the trees are stale in mass only.
+ * GHIP_DD_BH_EVALUATE has no such form (any walk but 0: GHIP_EINVAL).  An active Type-5 particle without a
+ * row on its home shard, a shard without a table, two active sinks of the run with one ID: GHIP_EINVAL on
+ * all shards, the message names the ID, and nothing but the marks (reset) has changed.  A sink swallowed
+ * while inactive does not add its BH_Mass (as on one GPU). */
+typedef struct
+{
+  const ghip_dens_params *dens; double ngb_factor; int *iterations;        /* GHIP_DD_SINK_DENSITY */
+  const ghip_bh_params *bh; const ghip_bh_accretion_params *acc;
+  ghip_bh_accretion_report *report;                                        /* GHIP_DD_BH_SWALLOW */
+} ghip_dd_sinks_args;
+size_t ghip_dd_sinks_args_size(void);
+#define GHIP_SINKS_RESIDENT_FORM 1   /* `walk` of ghip_dd_begin / ghip_dd_run for the two operations above */
 /* pmforce_periodic on shards (params: ghip_pm_params): every shard deposits ITS particles on the full
  * PMGRID^3 mesh, the meshes are all-gathered and added in rank order (8 PMGRID^3 bytes per shard:
  * 16.8 MB at PMGRID = 128), then every shard transforms the identical mesh and interpolates the
