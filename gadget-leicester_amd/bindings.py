@@ -200,6 +200,29 @@ class WindResult(C.Structure):
                 ("deleted_momentum", C.c_double)]
 
 
+# columns of the resident wind table (GHIP_WK_*, include/ghip.h)
+(WK_STELLAR_AGE, WK_BIRTH_ENERGY, WK_OLD_MOMENTUM, WK_NEW_DENSITY, WK_DRMIN, WK_DT1, WK_DT2, WK_DT_JUMP,
+ WK_DELTA_MOMENTUM, WK_DELETED, WK_COUNT) = range(11)
+
+
+class WindSpawnParams(C.Structure):
+    """ghip_wind_spawn_params: the creation of wind particles by the massive sinks (momentum_feedback.c:70-246)"""
+    _fields_ = [(k, C.c_double) for k in ("Time", "dt_fac", "SMBHmass", "VirtualStart", "VirtualFeedBack",
+                                           "VirtualMomentum", "VirtualMass", "FeedBackVelocity",
+                                           "UnitVelocity_in_cm_per_s", "UnitTime_in_s", "SofteningBndryMaxPhys",
+                                           "InnerBoundary")] + \
+        [(k, C.c_int) for k in ("NumCurrentTiStep", "MaxPart", "fraction_of_ledd_feedback",
+                                "accretion_at_eddington_rate", "startup_luminosity", "isotropic",
+                                "accretion_radius", "fly_through_empty_space")] + \
+        [("rnd_table", C.c_void_p), ("nrnd", C.c_int), ("pad", C.c_int)]
+
+
+class WindSpawnReport(C.Structure):
+    """ghip_wind_spawn_report (include/ghip.h)"""
+    _fields_ = [("spawned", C.c_int), ("nsinks_emitting", C.c_int), ("first_index", C.c_int), ("pad", C.c_int),
+                ("new_wind_exact_sum", C.c_double), ("gsl_draws", C.c_longlong)]
+
+
 class DdWindArgs(C.Structure):
     """ghip_dd_wind_args (include/ghip.h): the wind particles resident on one multi-GPU shard, GHIP_DD_WIND"""
     _fields_ = [("p", C.POINTER(WindParams)), ("nwind", C.c_int), ("wind_idx", C.c_void_p),
@@ -619,6 +642,17 @@ def lib():
                    L.ghip_wind_set_rad_accel, L.ghip_wind_get_timing):
             fn.argtypes = [vp, vp]
         L.ghip_set_rad_accel.argtypes = [vp, C.c_int]
+        for fn, cls in ((L.ghip_wind_spawn_params_size, WindSpawnParams),
+                        (L.ghip_wind_spawn_report_size, WindSpawnReport)):
+            fn.argtypes = []
+            fn.restype = C.c_size_t
+            if fn() != C.sizeof(cls):
+                raise RuntimeError("%s: %d bytes here, %d in libghip.so" % (cls.__name__, C.sizeof(cls), fn()))
+        L.ghip_winds_set_table.argtypes = [vp, C.c_int, vp, vp]
+        L.ghip_winds_get_table.argtypes = [vp, C.POINTER(C.c_int), vp, vp]
+        L.ghip_winds_clear.argtypes = [vp]
+        L.ghip_winds_feedback.argtypes = [vp, C.POINTER(WindParams), C.POINTER(WindResult)]
+        L.ghip_wind_spawn.argtypes = [vp, C.POINTER(WindSpawnParams), C.POINTER(WindSpawnReport)]
         L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
         L.ghip_find_smbh.argtypes = [vp, C.c_double, vp, C.POINTER(C.c_int)]
         L.ghip_set_integration_flags.argtypes = [vp, C.POINTER(IntegrationFlags)]
@@ -1435,6 +1469,51 @@ class ForcePath:
         a.update(rc=rc, iterations=res.iterations, bits=res.bits, ndeleted=res.ndeleted,
                  deleted_momentum=res.deleted_momentum)
         return a
+
+    # ---- the wind particles on the resident state: the table keyed by particle index, the loop, the spawn ----
+    def winds_set_table(self, idx, rows):
+        """ghip_winds_set_table: idx [nwind] (particle indices of Type-3 particles), rows [nwind][WK_COUNT], in
+        any order"""
+        idx = np.ascontiguousarray(idx, np.int32)
+        rows = np.ascontiguousarray(rows, np.float64).reshape(len(idx), WK_COUNT)
+        self._chk(self.L.ghip_winds_set_table(self.h, len(idx), _ptr(idx), _ptr(rows)))
+
+    def winds_table(self):
+        """ghip_winds_get_table -> (idx int32 [nwind] ascending, rows [nwind][WK_COUNT])"""
+        nw = C.c_int(0)
+        self._chk(self.L.ghip_winds_get_table(self.h, C.byref(nw), None, None))
+        idx, rows = np.zeros(nw.value, np.int32), np.zeros((nw.value, WK_COUNT))
+        self._chk(self.L.ghip_winds_get_table(self.h, C.byref(nw), _ptr(idx), _ptr(rows)))
+        return idx, rows
+
+    def winds_clear(self):
+        self._chk(self.L.ghip_winds_clear(self.h))
+
+    def winds_feedback(self, params, check=True):
+        """ghip_winds_feedback: the propagation loop for the active Type-3 particles with a row and StellarAge <
+        Time -> dict(rc, iterations, bits, ndeleted, deleted_momentum); the state is in winds_table().  check =
+        False returns GHIP_ENOCONV as rc"""
+        res = WindResult()
+        rc = self.L.ghip_winds_feedback(self.h, C.byref(params), C.byref(res))
+        if check or rc != GHIP_ENOCONV:
+            self._chk(rc)
+        return dict(rc=rc, iterations=res.iterations, bits=res.bits, ndeleted=res.ndeleted,
+                    deleted_momentum=res.deleted_momentum)
+
+    def wind_spawn(self, params, rnd_table=None):
+        """ghip_wind_spawn: the massive active sinks create wind particles -> dict(spawned, nsinks_emitting,
+        first_index, new_wind_exact_sum, gsl_draws); .n follows.  rnd_table None: the table of set_rnd_table.
+        After a call that spawned: tree_build."""
+        t = None if rnd_table is None else np.ascontiguousarray(rnd_table, np.float64)
+        params.rnd_table = None if t is None else t.ctypes.data
+        params.nrnd = 0 if t is None else len(t)
+        rep = WindSpawnReport()
+        self._chk(self.L.ghip_wind_spawn(self.h, C.byref(params), C.byref(rep)))
+        self.n += rep.spawned
+        if rep.spawned and getattr(self, "_active_n", None) is not None:
+            self._active_n += rep.spawned
+        return dict(spawned=rep.spawned, nsinks_emitting=rep.nsinks_emitting, first_index=rep.first_index,
+                    new_wind_exact_sum=rep.new_wind_exact_sum, gsl_draws=rep.gsl_draws)
 
     def wind_injected(self):
         out = np.zeros((self.ngas, 3))

@@ -9,6 +9,7 @@
 //     the finish and the per-bin sums             :679-735   -> k_acc_finish, k_acc_report
 //   the BH_FORM branch of cooling_and_starformation   sfr_eff.c:602-629   -> k_form_rows, k_form_apply
 //   density() for Type-5 targets                  ghip_sink_density's kernel and h iteration (ghip_sinks_density)
+//   momentum_feedback(), the sinks' emission      momentum_feedback.c:70-246   -> ghip_wind_spawn, the end of this file
 //
 // The per-sink state lives in a table of GHIP_SK_COUNT doubles per Type-5 particle, keyed by P[].ID and sorted by
 // it: a pass selects the active Type-5 particles on the device, in active-list order, and finds each one's row
@@ -1429,4 +1430,360 @@ int ghip_dd_sinks_store_density(ghip_ctx *ctx)
   if(D.sinks.iterations)
     *D.sinks.iterations = D.sk_iter;
   return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// ghip_wind_spawn: the massive sinks create wind particles (momentum_feedback.c:70-246)
+//
+//   count   one thread per active sink (sk_select: active-list order), new_wind and correction_wind   :75-133
+//   scan    exclusive scan of the counts; the total is the one blocking read; NumPart + total <= MaxPart  :149-156
+//   grow    old_of_new[j] = j (j < n), = the parent sink of the appended j; the planes move as in ghip_rearrange  :158
+//   fill    one thread per new particle: its sink by a search in the scanned counts, `bits` its rank there  :159-228
+// The counts are of the order of the sinks: one 64-lane wavefront per workgroup; the map and the fill run over
+// particles: 256 threads per workgroup.  Every store is a plain vector store.
+// ---------------------------------------------------------------------------------------------
+#define SPAWN_C 2.9979e10          // allvars.h:86
+#define SPAWN_GRAVITY 6.672e-8     // allvars.h:79
+#define SPAWN_THOMPSON 6.65245e-25 // allvars.h:91
+#define SPAWN_PROTONMASS 1.6726e-24 // allvars.h:89
+#define SPAWN_MAX_PER_SINK (1ULL << 30)
+
+struct SpawnK
+{
+  double Time, dt_fac, smbh, vstart, vfb, vmass, fbv, uvel, soft, inner;
+  double ledd;   // L_Edd_dimensionless (:36-37)
+  double ewm;    // energy_wind_min (:39)
+  double cu;     // C / UnitVelocity_in_cm_per_s
+  int step, frac_ledd, at_edd, startup, isotropic, acc_radius, fly;
+};
+
+// what the host reads
+struct SpawnWords
+{
+  unsigned long long total;
+  int nactive, emitting, missing;
+  unsigned int missing_id;
+  double exact_sum;
+};
+
+struct SpawnDev
+{
+  SpawnWords *words;
+  unsigned long long *cnt, *off;   // [G + 1]
+  double *exact, *corr, *dt, *drm; // [G]
+  int *qual;                       // [G]: the sink counts (:75)
+};
+
+static int spawn_dev(ghip_ctx *ctx, int G, SpawnDev &S)
+{
+  const size_t g1 = (size_t) G + 1;
+  GCHK(ghip_ensure(ctx, ctx->wk.spawn, 64 + g1 * (2 * 8 + 4 * 8 + 4) + 64));
+  char *base = P<char>(ctx->wk.spawn);
+  S.words = reinterpret_cast<SpawnWords *>(base);
+  S.cnt = reinterpret_cast<unsigned long long *>(base + 64);
+  S.off = S.cnt + g1;
+  S.exact = reinterpret_cast<double *>(S.off + g1);
+  S.corr = S.exact + g1;
+  S.dt = S.corr + g1;
+  S.drm = S.dt + g1;
+  S.qual = reinterpret_cast<int *>(S.drm + g1);
+  return GHIP_OK;
+}
+static_assert(sizeof(SpawnWords) <= 64, "the words block of WindTable::spawn");
+
+// :75-133 for record a < G; record G holds the zero behind the counts
+__global__ void __launch_bounds__(64) k_spawn_count(int G, const int *__restrict__ words, const int *__restrict__ sel,
+                                                    const int *__restrict__ row, const double *__restrict__ mass,
+                                                    const int *__restrict__ timebin, const double *__restrict__ rows,
+                                                    SpawnK K, SpawnDev S)
+{
+  const int a = blockIdx.x * 64 + threadIdx.x;
+  if(a > G)
+    return;
+  if(a == G)
+    {
+      S.cnt[G] = 0;
+      return;
+    }
+  const int c = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  unsigned long long new_wind = 0;
+  double exact = 0, corr = 1., dt = 0, drm = 0;
+  int qual = 0;
+  if(a < c && !SK_BAD(words, G))
+    {
+      const int i = sel[a];
+      const double *R = rows + (size_t) row[a] * SK_NC;
+      const double m = mass[i];
+      if(m > 0.5 * K.smbh && K.Time > K.vstart)
+        {
+          qual = 1;
+          const int tb = timebin[i];
+          dt = (tb ? (double) (1 << tb) : 0.0) * K.dt_fac;
+          drm = R[GHIP_SK_BH_DENSITY];
+          if(K.frac_ledd)
+            exact = K.vfb * K.ledd * (K.at_edd ? R[GHIP_SK_BH_MASS] : m) * dt / K.ewm;   // :85, :88
+          else
+            {
+              const double cc = K.cu * K.cu;   // pow(C / U, 2)
+              double lum = K.vfb * 0.1 * R[GHIP_SK_BH_MDOT] * cc;   // :100
+              if(lum > K.ledd * m)
+                lum = K.ledd * m;
+              exact = K.vfb * lum * dt / K.ewm;   // :105
+            }
+          if(K.startup ? exact > 1.e-4 : exact > 0.)
+            {
+              // (int) new_wind_exact + 1; a count that no MaxPart can hold stands for itself
+              new_wind = exact < (double) SPAWN_MAX_PER_SINK ? (unsigned long long) (int) exact + 1ULL : SPAWN_MAX_PER_SINK;
+              corr = exact / (double) new_wind;
+            }
+        }
+    }
+  S.cnt[a] = new_wind;
+  S.exact[a] = exact;
+  S.corr[a] = corr;
+  S.dt[a] = dt;
+  S.drm[a] = drm;
+  S.qual[a] = qual;
+}
+
+// one thread, active-list order
+__global__ void k_spawn_words(int G, const int *__restrict__ words, SpawnDev S)
+{
+  if(blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  SpawnWords w;
+  w.total = S.off[G];
+  w.nactive = words[SKW_COUNT];
+  w.missing = words[SKW_ERR] ? 1 : (words[SKW_COUNT] > G ? 2 : 0);
+  w.missing_id = (unsigned int) words[SKW_ERRID];
+  w.emitting = 0;
+  w.exact_sum = 0;
+  for(int a = 0; a < G; a++)
+    if(S.cnt[a] > 0)
+      {
+        w.emitting++;
+        w.exact_sum += S.exact[a];
+      }
+  *S.words = w;
+}
+
+// :89: P[i].Mass = P[i].BH_Mass of every counting sink
+__global__ void __launch_bounds__(64) k_spawn_edd_mass(int G, const int *__restrict__ sel, const int *__restrict__ row,
+                                                       const double *__restrict__ rows, const int *__restrict__ qual,
+                                                       double *__restrict__ mass)
+{
+  const int a = blockIdx.x * 64 + threadIdx.x;
+  if(a < G && qual[a])
+    mass[sel[a]] = rows[(size_t) row[a] * SK_NC + GHIP_SK_BH_MASS];
+}
+
+// the sink of the t-th new particle: the last a with off[a] <= t (off[G] = total > t, so its count is not 0)
+__device__ __forceinline__ int d_spawn_sink(int G, const unsigned long long *__restrict__ off, unsigned long long t)
+{
+  int lo = 0, hi = G;   // off[lo] <= t < off[hi]
+  while(hi - lo > 1)
+    {
+      const int mid = (lo + hi) >> 1;
+      if(off[mid] <= t)
+        lo = mid;
+      else
+        hi = mid;
+    }
+  return lo;
+}
+
+__global__ void __launch_bounds__(256) k_spawn_map(int n, int nn, int G, const unsigned long long *__restrict__ off,
+                                                   const int *__restrict__ sel, int *__restrict__ old_of_new)
+{
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if(j >= nn)
+    return;
+  old_of_new[j] = j < n ? j : sel[d_spawn_sink(G, off, (unsigned long long) (j - n))];
+}
+
+// :159-228 for the new particle j = n + t, whose record is a copy of its sink's
+__global__ void __launch_bounds__(256) k_spawn_fill(int total, int n, int nn, int G, SpawnDev S,
+                                                    const int *__restrict__ sel, SpawnK K, int nrnd,
+                                                    const double *__restrict__ rnd, int *__restrict__ type,
+                                                    double *__restrict__ hsml, double *__restrict__ vel,
+                                                    double *__restrict__ mass, int *__restrict__ idf,
+                                                    double *__restrict__ kick_newdens, int *__restrict__ act_tail,
+                                                    int *__restrict__ tab_idx, double *__restrict__ tab_rows)
+{
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if(t >= total)
+    return;
+  const int a = d_spawn_sink(G, S.off, (unsigned long long) t);
+  const unsigned int bits = (unsigned int) ((unsigned long long) t - S.off[a]);
+  const int j = n + t;
+  const size_t N = (size_t) nn;
+  type[j] = 3;
+  double h = hsml[j];
+  h += K.soft;
+  if(K.acc_radius)
+    h += K.inner;
+  hsml[j] = h;
+  const unsigned int id = (unsigned int) idf[sel[a]], m = (unsigned int) nrnd;
+  const double r1 = rnd[(id + 2u + bits + (unsigned int) K.step) % m];
+  const double r2 = rnd[(id + 3u + bits + (unsigned int) K.step) % m];
+  const double theta = K.isotropic ? acos(2. * r1 - 1.) : acos(0.5 * r1 + 0.5);
+  const double phi = 2 * M_PI * (r2 + K.Time);
+  const double dir[3] = {sin(theta) * cos(phi), sin(theta) * sin(phi), cos(theta)};
+  for(int k = 0; k < 3; k++)
+    vel[(size_t) k * N + j] = K.cu * dir[k] / K.fbv;   // :191
+  idf[j] = (int) (id + (unsigned int) j);   // :215
+  const double corr = S.corr[a];
+  const double old = K.ewm / SPAWN_C * K.uvel * corr, birth = K.ewm * corr;   // :225-226
+  mass[j] = K.vmass * old;
+  if(kick_newdens)
+    kick_newdens[j] = 0.;
+  if(act_tail)
+    act_tail[t] = j;
+  tab_idx[t] = j;
+  double *R = tab_rows + (size_t) t * GHIP_WK_COUNT;
+  for(int c = 0; c < GHIP_WK_COUNT; c++)
+    R[c] = 0;
+  R[GHIP_WK_STELLAR_AGE] = K.Time;
+  R[GHIP_WK_BIRTH_ENERGY] = birth;
+  R[GHIP_WK_OLD_MOMENTUM] = old;
+  R[GHIP_WK_DRMIN] = K.fly ? 0. : S.drm[a];
+  R[GHIP_WK_DT1] = S.dt[a];
+}
+
+extern "C" size_t ghip_wind_spawn_params_size(void)
+{
+  return sizeof(ghip_wind_spawn_params);
+}
+
+extern "C" size_t ghip_wind_spawn_report_size(void)
+{
+  return sizeof(ghip_wind_spawn_report);
+}
+
+extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, ghip_wind_spawn_report *report)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_spawn";
+  if(!ctx || !p || !report)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  memset(report, 0, sizeof(*report));
+  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(sk_enter(ctx, who, true));
+  if(ctx->wk.on && ctx->wk.stale)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the wind table was given for other counts: give it again after "
+                     "ghip_set_counts (ghip_winds_set_table)", who);
+  if(!(p->rnd_table && p->nrnd > 0) && ctx->rnd_n <= 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: no RndTable: neither rnd_table / nrnd nor a table bound with "
+                     "ghip_set_rnd_table", who);
+  if(p->MaxPart < ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: MaxPart = %d is below NumPart = %d", who, p->MaxPart, ctx->n);
+  SinkTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const int G = T.n, n = ctx->n;
+  report->first_index = n;
+  SpawnK K;
+  K.Time = p->Time;
+  K.dt_fac = p->dt_fac;
+  K.smbh = p->SMBHmass;
+  K.vstart = p->VirtualStart;
+  K.vfb = p->VirtualFeedBack;
+  K.vmass = p->VirtualMass;
+  K.fbv = p->FeedBackVelocity;
+  K.uvel = p->UnitVelocity_in_cm_per_s;
+  K.soft = p->SofteningBndryMaxPhys;
+  K.inner = p->InnerBoundary;
+  // :36-37; pow(x, 2) is x * x
+  K.ledd = (4 * M_PI * SPAWN_GRAVITY * SPAWN_C * SPAWN_PROTONMASS / SPAWN_THOMPSON) / (K.uvel * K.uvel) * p->UnitTime_in_s;
+  K.ewm = p->VirtualMomentum * SPAWN_C / K.uvel;
+  K.cu = SPAWN_C / K.uvel;
+  K.step = p->NumCurrentTiStep;
+  K.frac_ledd = p->fraction_of_ledd_feedback != 0;
+  K.at_edd = K.frac_ledd && p->accretion_at_eddington_rate != 0;
+  K.startup = p->startup_luminosity != 0;
+  K.isotropic = p->isotropic != 0;
+  K.acc_radius = p->accretion_radius != 0;
+  K.fly = p->fly_through_empty_space != 0;
+
+  // ---- count, scan, the one blocking read ----
+  SkWork W;
+  int nact = 0;
+  GCHK(sk_select(ctx, G, W, &nact));
+  if(nact <= 0 || n == 0)
+    return GHIP_OK;
+  SpawnDev S;
+  GCHK(spawn_dev(ctx, G, S));
+  k_spawn_count<<<cdiv(G + 1, 64), 64, 0, st>>>(G, W.words, W.b, W.row, P<double>(ctx->f[GHIP_F_MASS]),
+                                               P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(T.rows), K, S);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_scan<unsigned long long>(ctx, S.cnt, S.off, G + 1, st));
+  k_spawn_words<<<1, 64, 0, st>>>(G, W.words, S);
+  HIPCHK(hipGetLastError());
+  SpawnWords h;
+  HIPCHK(hipMemcpyAsync(&h, S.words, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(h.missing == 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-5 particle with ID %u has no row in the sink table (%d "
+                     "rows, %d active sinks); nothing was changed", who, h.missing_id, T.n, h.nactive);
+  if(h.missing)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: %d active Type-5 particles for %d rows of the sink table: two of them "
+                     "carry the same ID; nothing was changed", who, h.nactive, T.n);
+  if((unsigned long long) n + h.total > (unsigned long long) p->MaxPart)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: NumPart = %d and %llu new wind particles do not fit MaxPart = %d (the "
+                     "reference's endrun(8888)); nothing was changed", who, n, h.total, p->MaxPart);
+  const int total = (int) h.total, nn = n + total;
+  report->spawned = total;
+  report->nsinks_emitting = h.emitting;
+  report->new_wind_exact_sum = h.exact_sum;
+  report->gsl_draws = 3LL * total;
+  if(K.at_edd && G > 0)
+    {
+      k_spawn_edd_mass<<<cdiv(G, 64), 64, 0, st>>>(G, W.b, W.row, P<double>(T.rows), S.qual, P<double>(ctx->f[GHIP_F_MASS]));
+      HIPCHK(hipGetLastError());
+    }
+  if(total == 0)
+    return GHIP_OK;
+
+  // ---- grow ----
+  const double *rnd = P<double>(ctx->rnd_table);
+  int nrnd = ctx->rnd_n;
+  if(p->rnd_table && p->nrnd > 0)
+    {
+      nrnd = p->nrnd;
+      GCHK(ghip_ensure(ctx, ctx->wk.rnd, (size_t) nrnd * 8));
+      HIPCHK(hipMemcpyAsync(ctx->wk.rnd.p, p->rnd_table, (size_t) nrnd * 8, hipMemcpyHostToDevice, st));
+      rnd = P<double>(ctx->wk.rnd);
+    }
+  int *tab_idx = nullptr, *act_tail = nullptr, *old_of_new = nullptr;
+  double *tab_rows = nullptr;
+  GCHK(ghip_winds_reserve(ctx, total, &tab_idx, &tab_rows));
+  const int old_nact = ctx->nactive;
+  if(old_nact >= 0)   // the list in force, and the new particles behind it (:202-204)
+    {
+      GCHK(ghip_ensure(ctx, ctx->act_next, (size_t) (old_nact + total) * 4));
+      if(old_nact > 0)
+        HIPCHK(hipMemcpyAsync(ctx->act_next.p, ctx->act_host_idx.p, (size_t) old_nact * 4, hipMemcpyDeviceToDevice, st));
+      act_tail = P<int>(ctx->act_next) + old_nact;
+    }
+  GCHK(ghip_seq_grow_begin(ctx, nn, &old_of_new));
+  k_spawn_map<<<cdiv(nn, 256), 256, 0, st>>>(n, nn, G, S.off, W.b, old_of_new);
+  HIPCHK(hipGetLastError());
+  // (k_seq_move takes this map, which is not a permutation, and nn > n: see ghip_seq_grow_apply)
+  GCHK(ghip_seq_grow_apply(ctx, nn));
+
+  // ---- fill (the fields are the new layout's now) ----
+  const bool nd = ctx->has_newdens && ctx->kick_fields_n == nn;
+  k_spawn_fill<<<cdiv(total, 256), 256, 0, st>>>(total, n, nn, G, S, W.b, K, nrnd, rnd, P<int>(ctx->f[GHIP_F_TYPE]),
+                                                 P<double>(ctx->f[GHIP_F_HSML]), P<double>(ctx->f[GHIP_F_VEL]),
+                                                 P<double>(ctx->f[GHIP_F_MASS]), P<int>(ctx->f[GHIP_F_ID]),
+                                                 nd ? P<double>(ctx->kick_newdens) : nullptr, act_tail, tab_idx, tab_rows);
+  HIPCHK(hipGetLastError());
+  HIPCHK(ghip_stream_sync(ctx, st));   // (the caller's rnd_table has been read)
+  ghip_winds_appended(ctx, total);
+  if(old_nact >= 0)
+    {
+      ctx->act_host_idx.swap(ctx->act_next);
+      ctx->nactive = old_nact + total;
+    }
+  return GHIP_OK;
 }

@@ -426,6 +426,8 @@ extern "C" int ghip_set_counts(ghip_ctx *ctx, int numpart, int ngas)
       ctx->id_given = false;
       if(ctx->sk.on)
         ctx->sk.stale = true;   // (the sink table: refused until given again)
+      if(ctx->wk.on)
+        ctx->wk.stale = true;   // (the wind table, keyed by particle index, too)
       ctx->sfr_ncand = -1;      // (the candidates of ghip_sfr_cooling are particle indices of the old counts)
     }
   ctx->n = numpart;

@@ -201,6 +201,20 @@ struct SinkTable
   unsigned int last_dup = 0; // the ID that the last refused installation found twice
 };
 
+// The resident wind table (ghip_wind.hip): one row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE
+// INDEX (two live wind particles can carry the same ID) and kept in ascending index order: ghip_rearrange and
+// ghip_peano_order send it through their maps (ghip_winds_remap), ghip_wind_spawn appends to it.
+struct WindTable
+{
+  DevBuf idx, rows;           // i32[n], f64[n][GHIP_WK_COUNT]
+  DevBuf tmp_idx, tmp_rows;   // the unsorted image a new table is sorted from; the larger block a table grows into
+  DevBuf work;                // words, flags, sort keys and values, the selected list
+  DevBuf spawn, rnd;          // ghip_wind_spawn: per-sink counts, offsets and records; its copy of a RndTable
+  int n = 0;
+  bool on = false;            // a table was given (possibly of 0 rows)
+  bool stale = false;         // ghip_set_counts changed the counts since: refused until given again
+};
+
 // One dust pass as ghip_dust.hip runs it: each of the four entry forms (positional, *_grains, GHIP_DD_DUST_* with
 // walk = 0 or GHIP_DUST_GRAINS_FORM) fills this once, and everything below the entry reads only it
 struct DustCall
@@ -654,6 +668,7 @@ struct ghip_ctx
   bool rad_accel_on = false;        // ghip_set_rad_accel: kick, PM kick and drift read RadAccel
   hipEvent_t wind_ev[8] = {};       // phase marks of ghip_wind_feedback (made by its first call)
   double wind_ms[5] = {0, 0, 0, 0, 0};
+  WindTable wk;                     // the resident wind table (ghip_winds_set_table)
 
   // the physics switches of the dust passes (ghip_set_dust_model, ghip_dust.hip)
   bool dust_model_on = false;          // any switch set: the k_dust_grain<DustM> / k_dust_density<G, DustVel> instantiations run
@@ -816,6 +831,19 @@ int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const
                            const double *dpbh, int *dvict, double *dout);
 // ghip_accretion.hip: ghip_rearrange drops the rows of the Type-5 particles it eliminates (a table exists)
 int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old);
+// ghip_wind.hip: the wind table through a reordering (every index through new_of_old, the rows of eliminated
+// particles dropped, ascending order restored); what every entry point of the resident wind section refuses;
+// room for `extra` rows behind the table's own (a context without a table gets an empty one), the tails to fill,
+// and the rows counted in
+int ghip_winds_remap(ghip_ctx *ctx, int n_before, const int *new_of_old);
+int ghip_winds_enter(ghip_ctx *ctx, const char *who);
+int ghip_winds_reserve(ghip_ctx *ctx, int extra, int **idx_tail, double **rows_tail);
+void ghip_winds_appended(ghip_ctx *ctx, int extra);
+// ghip_sequence.hip, for ghip_wind_spawn: the state grows from n to nn particles.  _begin gives the map to fill,
+// old_of_new [nn] on the device (the source record of every record of the new layout); _apply moves every plane
+// along it and leaves the state as after ghip_rearrange, the maps of ghip_sequence_get_map included
+int ghip_seq_grow_begin(ghip_ctx *ctx, int nn, int **old_of_new);
+int ghip_seq_grow_apply(ghip_ctx *ctx, int nn);
 // the rows in GHIP_DD_MIGRATE (ghip_accretion.hip): the rows of the departing Type-5 particles `list` (destination
 // 1 << r in mask[]) packed per destination; the second exchange posted; departed rows out, arrivals in, sorted
 int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigned long long *mask);

@@ -39,7 +39,7 @@ __global__ void __launch_bounds__(256) k_seq_move(SeqPlanes T, int n_old, int ng
     return;
   const int i = old_of_new[j];
   if((unsigned int) i >= (unsigned int) (pl.gas ? ng_old : n_old))
-    return;   // (never: the maps are permutations by construction; a read outside the old layout is refused)
+    return;   // (never: the maps are permutations, or name a parent, by construction; a read outside the old layout is refused)
   if(pl.w4)
     reinterpret_cast<unsigned int *>(pl.dst)[j] = reinterpret_cast<const unsigned int *>(pl.src)[i];
   else
@@ -329,6 +329,8 @@ extern "C" int ghip_rearrange(ghip_ctx *ctx, const ghip_rearrange_params *p, ghi
   HIPCHK(hipGetLastError());
   if(ctx->sk.on && !ctx->sk.stale && w[SW_ELIM])   // the rows of the eliminated Type-5 particles go with them
     GCHK(ghip_sinks_drop_eliminated(ctx, n, P<int>(S.new_of_old)));
+  if(ctx->wk.on && !ctx->wk.stale)   // the wind table is keyed by index: it follows the map
+    GCHK(ghip_winds_remap(ctx, n, P<int>(S.new_of_old)));
   GCHK(seq_apply(ctx, nn, ngn));
   S.n_before = n;
   S.n_after = nn;
@@ -397,6 +399,8 @@ extern "C" int ghip_peano_order(ghip_ctx *ctx, const double DomainCorner[3], dou
     return seq_identity(ctx, n);
   S.old_of_new.swap(S.sidx);
   S.new_of_old.swap(S.idx);
+  if(ctx->wk.on && !ctx->wk.stale)
+    GCHK(ghip_winds_remap(ctx, n, P<int>(S.new_of_old)));
   GCHK(seq_apply(ctx, n, ng));
   S.n_before = S.n_after = n;
   if(changed)
@@ -430,5 +434,38 @@ extern "C" int ghip_sequence_get_info(ghip_ctx *ctx, long long out[4])
   out[1] = ctx->seq.n_after;
   out[2] = ctx->seq.bytes_moved;
   out[3] = ctx->seq.planes;
+  return GHIP_OK;
+}
+
+// ---- growth (ghip_wind_spawn) ----------------------------------------------------------------------------------
+// The one operation above that is not a permutation: the state goes from n to nn > n particles, and every record
+// behind the old ones is a copy of an old record (its parent sink), P[NumPart + stars_spawned] = P[i].
+int ghip_seq_grow_begin(ghip_ctx *ctx, int nn, int **old_of_new)
+{
+  SeqState &S = ctx->seq;
+  if(nn < ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_seq_grow: %d particles cannot grow to %d", ctx->n, nn);
+  GCHK(ghip_ensure(ctx, S.old_of_new, (size_t) (nn > 0 ? nn : 1) * 4));
+  GCHK(ghip_ensure(ctx, S.new_of_old, (size_t) (ctx->n > 0 ? ctx->n : 1) * 4));
+  S.n_before = S.n_after = -1;   // (the maps of the last call are overwritten)
+  *old_of_new = P<int>(S.old_of_new);
+  return GHIP_OK;
+}
+
+int ghip_seq_grow_apply(ghip_ctx *ctx, int nn)
+{
+  SeqState &S = ctx->seq;
+  const int n = ctx->n, ng = ctx->ngas;
+  if(n > 0)
+    {
+      k_seq_iota<<<cdiv(n, 256), 256, 0, ctx->stream>>>(n, P<int>(S.new_of_old), nullptr);
+      HIPCHK(hipGetLastError());
+    }
+  // k_seq_move with a map that is not a permutation and nn > n: thread j < nn writes dst[j] of a plane sized for nn
+  // (seq_apply sizes the shadows by the new counts) and reads src[old_of_new[j]], which it refuses outside [0, n);
+  // several j may read the same source.  A gas plane has ngn = ng <= n threads, and the map is the identity there.
+  GCHK(seq_apply(ctx, nn, ng));
+  S.n_before = n;
+  S.n_after = nn;
   return GHIP_OK;
 }

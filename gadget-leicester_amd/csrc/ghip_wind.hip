@@ -1,8 +1,9 @@
 // ghip_wind.hip -- the wind particles of the reference's shipped flag bundle (-DVIRTUAL -DFB_MOMENTUM): the
 // propagation loop of momentum_feedback() with its two neighbour passes.  VIRTUAL_FLY_THORUGH_EMPTY_SPACE,
-// VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL are switches of ghip_wind_params.  Not built: spawning
-// (momentum_feedback.c:70-245, host code), fb_particles.c, REAL_EOS, NON_GRAY_RAD_TRANSFER.  The loop on
-// domain-decomposed shards is GHIP_DD_WIND, at the end of this file.
+// VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL are switches of ghip_wind_params.  The creation of wind particles
+// (momentum_feedback.c:70-246) is ghip_wind_spawn (ghip_accretion.hip, next to the sinks that emit them).  Not
+// built: fb_particles.c, REAL_EOS, NON_GRAY_RAD_TRANSFER.  The resident form (the wind table, ghip_winds_feedback)
+// follows ghip_wind_feedback; the loop on domain-decomposed shards is GHIP_DD_WIND, at the end of this file.
 //
 // Replaces the particle loops of
 //   momentum_feedback, the loop and the elimination   momentum_feedback.c:283-568
@@ -628,30 +629,27 @@ static int wind_tree_order(ghip_ctx *ctx, const WindDev &d, hipStream_t st)
   return ghip_tree_order(ctx, d.nw, d.idx, key, key + D, d.idx + 4 * D, d.ord, st);
 }
 
-// What every entry point asks of the context; then the list to the device, its tree order into `ord`, the
-// velocity planes, and words->err raised where an index does not name a Type-3 particle
-static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const int *idx, const char *who, WindDev *out)
+// What every entry point asks of the context (wind_begin); then the list to the device, its tree order into
+// `ord`, the velocity planes, and words->err raised where an index does not name a Type-3 particle
+static int wind_need_trees(ghip_ctx *ctx, const char *who)
 {
-  GCHK(wind_refuse_sharded(ctx, who));
-  if(!p || nw < 0 || (nw > 0 && !idx))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  out->nw = nw;
-  if(nw == 0)
-    return GHIP_OK;
   if(ctx->ngas > 0)
     GCHK(ghip_finish_gas_tree(ctx));
   if(!ctx->gt.built || (ctx->ngas > 0 && !ctx->st.built))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: call ghip_tree_build first", who);
-  for(int a = 0; a < nw; a++)
-    if(idx[a] < 0 || idx[a] >= ctx->n)
-      return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range", who, idx[a]);
+  return GHIP_OK;
+}
+
+// the list of nw particles on the device (host == false: device to device)
+static int wind_begin_list(ghip_ctx *ctx, int nw, const int *idx, bool host, WindDev *out)
+{
   hipStream_t st = ctx->stream;
   const size_t D = (size_t) nw;
   GCHK(ghip_ensure(ctx, ctx->wind_idx, ((9 * D * 4 + 63) & ~(size_t) 63) + 64));
   GCHK(ghip_ensure(ctx, ctx->wind_work, (WIND_NPLANES * D + 2 * (D + 1)) * 8 + 256));
   const WindDev d = wind_dev(ctx, nw);
   *out = d;
-  HIPCHK(hipMemcpyAsync(d.idx, idx, D * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d.idx, idx, D * 4, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemsetAsync(d.words, 0, sizeof(WindWords), st));
   GCHK(wind_tree_order(ctx, d, st));
   k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]),
@@ -662,6 +660,21 @@ static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const in
                                                       d.words);
   HIPCHK(hipGetLastError());
   return GHIP_OK;
+}
+
+static int wind_begin(ghip_ctx *ctx, const ghip_wind_params *p, int nw, const int *idx, const char *who, WindDev *out)
+{
+  GCHK(wind_refuse_sharded(ctx, who));
+  if(!p || nw < 0 || (nw > 0 && !idx))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  out->nw = nw;
+  if(nw == 0)
+    return GHIP_OK;
+  GCHK(wind_need_trees(ctx, who));
+  for(int a = 0; a < nw; a++)
+    if(idx[a] < 0 || idx[a] >= ctx->n)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range", who, idx[a]);
+  return wind_begin_list(ctx, nw, idx, true, out);
 }
 
 static int wind_type_error(ghip_ctx *ctx, const char *who)
@@ -862,48 +875,29 @@ static int wind_download_state(ghip_ctx *ctx, const WindDev &d, const ghip_wind_
   return GHIP_OK;
 }
 
-extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
-                                  const ghip_wind_state *s, ghip_wind_result *result)
+// The loop for the list and the in planes of `d` (WP_AGE .. WP_DRMIN), which both entry forms have put in place:
+// dt_jump, its sum and the first list (:285-302), the density at the start, the iterations, RAD_ACCEL and the
+// elimination.  *end says how it ended; the out planes and d.deleted are left on the device.
+enum { WIND_FLOOR, WIND_DONE, WIND_NOCONV };
+struct WindEnd
 {
-  if(!ctx)
-    return GHIP_EINVAL;
-  GHIP_JOIN(ctx);
-  static const char *who = "ghip_wind_feedback";
-  const auto t_begin = std::chrono::steady_clock::now();
-  if(result)
-    memset(result, 0, sizeof(*result));
-  if(!result || !p || (nwind > 0 && (!s || !s->stellar_age || !s->birth_energy || !s->old_momentum ||
-                                     !s->new_density || !s->drmin || !s->dt1 || !s->dt2 || !s->dt_jump ||
-                                     !s->delta_momentum || !s->deleted)))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  if(p->max_iter < 1 || !(p->dt_fac >= 0))
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
-  WindDev d;
-  GCHK(wind_begin(ctx, p, nwind, wind_idx, who, &d));
-  for(int k = 0; k < 5; k++)
-    ctx->wind_ms[k] = 0;
-  if(nwind == 0)
-    return GHIP_OK;
+  int stage = WIND_FLOOR;        // WIND_FLOOR: the sum of dt_jump is at or below the floor (:302), nothing has changed
+  int under = 0;                 // WIND_NOCONV: particles still under way
+  bool spread_pending = false;   // the last spread's events are not read yet (wind_spread_ms)
+};
+
+static int wind_loop(ghip_ctx *ctx, const ghip_wind_params *p, const WindDev &d, const char *who,
+                     ghip_wind_result *result, WindEnd *end)
+{
   hipStream_t st = ctx->stream;
-  const int nw = nwind;
+  const int nw = d.nw;
   const size_t D = (size_t) nw;
   const WindK K = wind_k(p);
   for(int k = 0; k < 6; k++)
     if(!ctx->wind_ev[k])
       HIPCHK(hipEventCreate(&ctx->wind_ev[k]));
   hipEvent_t *ev = ctx->wind_ev;
-
-  // ---- the state in; dt_jump, its sum and the first list (:285-302) ----
-  {
-    std::vector<double> h(WIND_NIN * D);
-    memcpy(h.data() + WP_AGE * D, s->stellar_age, D * 8);
-    memcpy(h.data() + WP_BIRTH * D, s->birth_energy, D * 8);
-    memcpy(h.data() + WP_OLD * D, s->old_momentum, D * 8);
-    memcpy(h.data() + WP_RHO * D, s->new_density, D * 8);
-    memcpy(h.data() + WP_DRMIN * D, s->drmin, D * 8);
-    HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
-  }
+  // ---- dt_jump, its sum and the first list (:285-302) ----
   k_wind_init<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->f[GHIP_F_TIMEBIN]), d.w, d.deleted, K.dt_fac);
   k_wind_sum<<<1, 1024, 0, st>>>(nw, d.w + WP_DTJ * D, &d.words->dt_total);
   k_wind_flags<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.ord, d.w + WP_DTJ * D, d.flags, d.words);
@@ -914,8 +908,8 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
   HIPCHK(ghip_stream_sync(ctx, st));
   if(h.err)
     return wind_type_error(ctx, who);
-  if(h.dt_total <= p->dt_total_floor)   // :302: the loop is not entered, nothing changes
-    return wind_download_state(ctx, d, s, false);
+  if(h.dt_total <= p->dt_total_floor)
+    return GHIP_OK;
   GCHK(wind_injected(ctx, who));
   if(p->rad_accel)
     GCHK(wind_rad_accel(ctx, who));
@@ -1009,9 +1003,63 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
       k_wind_eliminate<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->n, pos, mass, d.w, d.deleted, K);
       HIPCHK(hipGetLastError());
     }
+  end->stage = noconv ? WIND_NOCONV : WIND_DONE;
+  end->under = under;
+  end->spread_pending = spread_pending;
+  return GHIP_OK;
+}
+
+// the last spread's milliseconds, once the caller has waited for the stream
+static void wind_spread_ms(ghip_ctx *ctx, const WindEnd &end)
+{
+  float f = 0;
+  if(end.spread_pending && hipEventElapsedTime(&f, ctx->wind_ev[4], ctx->wind_ev[5]) == hipSuccess)
+    ctx->wind_ms[2] += f;
+}
+
+extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int nwind, const int *wind_idx,
+                                  const ghip_wind_state *s, ghip_wind_result *result)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_feedback";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if(result)
+    memset(result, 0, sizeof(*result));
+  if(!result || !p || (nwind > 0 && (!s || !s->stellar_age || !s->birth_energy || !s->old_momentum ||
+                                     !s->new_density || !s->drmin || !s->dt1 || !s->dt2 || !s->dt_jump ||
+                                     !s->delta_momentum || !s->deleted)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(p->max_iter < 1 || !(p->dt_fac >= 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
+  WindDev d;
+  GCHK(wind_begin(ctx, p, nwind, wind_idx, who, &d));
+  for(int k = 0; k < 5; k++)
+    ctx->wind_ms[k] = 0;
+  if(nwind == 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const int nw = nwind;
+  const size_t D = (size_t) nw;
+
+  // ---- the state in ----
+  {
+    std::vector<double> h(WIND_NIN * D);
+    memcpy(h.data() + WP_AGE * D, s->stellar_age, D * 8);
+    memcpy(h.data() + WP_BIRTH * D, s->birth_energy, D * 8);
+    memcpy(h.data() + WP_OLD * D, s->old_momentum, D * 8);
+    memcpy(h.data() + WP_RHO * D, s->new_density, D * 8);
+    memcpy(h.data() + WP_DRMIN * D, s->drmin, D * 8);
+    HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
+  }
+  WindEnd end;
+  GCHK(wind_loop(ctx, p, d, who, result, &end));
+  if(end.stage == WIND_FLOOR)   // :302: the loop is not entered, nothing changes
+    return wind_download_state(ctx, d, s, false);
   GCHK(wind_download_state(ctx, d, s, true));
-  if(spread_pending)
-    add_ms(2, ev[4], ev[5]);
+  wind_spread_ms(ctx, end);
   for(int a = 0; a < nw; a++)   // :558-559, in list order
     if(s->deleted[a])
       {
@@ -1020,9 +1068,476 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
           result->deleted_momentum += s->old_momentum[a];
       }
   ctx->wind_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  if(noconv)
+  if(end.stage == WIND_NOCONV)
     return ghip_fail(ctx, GHIP_ENOCONV, "%s: %d wind particles still under way after max_iter = %d iterations", who,
-                     under, p->max_iter);
+                     end.under, p->max_iter);
+  return GHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the wind particles on the resident state: the wind table and the loop without host arrays
+//
+// One row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE INDEX and kept in ascending index order
+// (DESIGN.md 4.18 says why not by ID).  ghip_winds_feedback makes its list by a device selection over the active
+// list, gathers the in planes from the rows, runs wind_loop and scatters the out planes back.
+// ---------------------------------------------------------------------------------------------
+#define WK_NC GHIP_WK_COUNT
+static_assert(GHIP_WK_STELLAR_AGE == WP_AGE && GHIP_WK_DRMIN == WP_DRMIN && GHIP_WK_DELTA_MOMENTUM == WP_DMOM,
+              "the first nine columns of a row are the planes WP_AGE .. WP_DMOM");
+
+// ints at the front of WindTable::work; the result of ghip_winds_feedback behind them
+enum
+{
+  WKW_COUNT = 0,   // rows kept / particles listed
+  WKW_ERR,         // 1: an index names a particle that is not Type 3 / an active Type-3 particle has no row
+  WKW_ERRIDX,      // ... the largest such index
+  WKW_DUP,         // an index stands twice
+  WKW_DUPIDX,
+  WKW_WORDS = 16
+};
+
+struct WkWork
+{
+  int *words;
+  ghip_wind_result *result;
+  int *a, *b;             // i32[m] each
+  unsigned int *k0, *k1;  // u32[m] each
+};
+
+static int wk_work(ghip_ctx *ctx, size_t m, WkWork &W)
+{
+  const size_t head = WKW_WORDS * 4 + 64;
+  static_assert(sizeof(ghip_wind_result) <= 64, "the result block of WindTable::work");
+  if(m == 0)
+    m = 1;
+  GCHK(ghip_ensure(ctx, ctx->wk.work, head + 4 * m * 4 + 64));
+  char *base = P<char>(ctx->wk.work);
+  W.words = reinterpret_cast<int *>(base);
+  W.result = reinterpret_cast<ghip_wind_result *>(base + WKW_WORDS * 4);
+  W.a = reinterpret_cast<int *>(base + head);
+  W.b = W.a + m;
+  W.k0 = reinterpret_cast<unsigned int *>(W.b + m);
+  W.k1 = W.k0 + m;
+  return GHIP_OK;
+}
+
+// the row of particle i in the ascending list idx[0, n), -1: none
+__device__ __forceinline__ int d_wk_find(int n, const int *__restrict__ idx, int i)
+{
+  int lo = 0, hi = n;
+  while(lo < hi)
+    {
+      const int mid = (lo + hi) >> 1;
+      if(idx[mid] < i)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+  return (lo < n && idx[lo] == i) ? lo : -1;
+}
+
+// sort keys and values of m unsorted rows; an index whose particle is not Type 3 raises the error words
+// (type == nullptr: not checked)
+__global__ void __launch_bounds__(256) k_wk_keys(int m, const int *__restrict__ idx, int n,
+                                                 const int *__restrict__ type, unsigned int *__restrict__ key,
+                                                 int *__restrict__ val, int *__restrict__ words)
+{
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if(r >= m)
+    return;
+  const int i = idx[r];
+  key[r] = (unsigned int) i;
+  val[r] = r;
+  if(type && (i < 0 || i >= n || type[i] != 3))
+    {
+      words[WKW_ERR] = 1;
+      atomicMax(words + WKW_ERRIDX, i);
+    }
+}
+
+// dst row r = src row from[r]; idx[r] = the sorted key; two equal neighbours raise the duplicate words
+__global__ void __launch_bounds__(256) k_wk_gather(int m, const int *__restrict__ from,
+                                                   const unsigned int *__restrict__ key,
+                                                   const double *__restrict__ src, double *__restrict__ dst,
+                                                   int *__restrict__ idx, int *__restrict__ words)
+{
+  const long long e = (long long) blockIdx.x * 256 + threadIdx.x;
+  if(e >= (long long) m * WK_NC)
+    return;
+  const int r = (int) (e / WK_NC), c = (int) (e % WK_NC);
+  dst[e] = src[(size_t) from[r] * WK_NC + c];
+  if(c == 0)
+    {
+      idx[r] = (int) key[r];
+      if(r + 1 < m && key[r] == key[r + 1])
+        {
+          words[WKW_DUP] = 1;
+          atomicMax(words + WKW_DUPIDX, (int) key[r]);
+        }
+    }
+}
+
+// the m rows of the image T.tmp_idx / T.tmp_rows, in any order, become the table T.idx / T.rows, sorted by index
+// (T.n is the caller's to set); the error and duplicate words are raised on the device
+static int wk_sort_in(ghip_ctx *ctx, int m, WkWork &W, bool check_type)
+{
+  WindTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  GCHK(ghip_ensure(ctx, T.idx, (size_t) m * 4));
+  GCHK(ghip_ensure(ctx, T.rows, (size_t) m * WK_NC * 8));
+  k_wk_keys<<<cdiv(m, 256), 256, 0, st>>>(m, P<int>(T.tmp_idx), ctx->n, check_type ? P<int>(ctx->f[GHIP_F_TYPE]) : nullptr,
+                                         W.k0, W.a, W.words);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_sort_pairs(ctx, W.k0, W.k1, W.a, W.b, m, 32, st));
+  k_wk_gather<<<cdiv((long long) m * WK_NC, 256), 256, 0, st>>>(m, W.b, W.k1, P<double>(T.tmp_rows), P<double>(T.rows),
+                                                               P<int>(T.idx), W.words);
+  HIPCHK(hipGetLastError());
+  return GHIP_OK;
+}
+
+// what every entry point of the section refuses
+int ghip_winds_enter(ghip_ctx *ctx, const char *who)
+{
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard): the resident wind "
+                     "particles are single-rank only", who);
+  if(ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the shard form is not built: on a multi-GPU context (ghip_dd_init with %d "
+                     "ranks) the wind particles run GHIP_DD_WIND with host arrays", who, ctx->dd.nranks);
+  HIPCHK(hipSetDevice(ctx->device));
+  return GHIP_OK;
+}
+
+static int wk_need_table(ghip_ctx *ctx, const char *who)
+{
+  if(ctx->wk.on && ctx->wk.stale)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the wind table was given for other counts: give it again after "
+                     "ghip_set_counts (ghip_winds_set_table)", who);
+  if(!ctx->wk.on)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: no wind table (ghip_winds_set_table)", who);
+  return GHIP_OK;
+}
+
+extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  static const char *who = "ghip_winds_set_table";
+  if(!ctx || nwind < 0 || (nwind > 0 && (!idx || !rows)))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  GCHK(ghip_winds_enter(ctx, who));
+  WindTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  T.on = false;
+  T.n = 0;
+  T.stale = false;
+  for(int r = 0; r < nwind; r++)
+    if(idx[r] < 0 || idx[r] >= ctx->n)
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range (the context holds no table now)",
+                       who, idx[r]);
+  if(nwind > 0)
+    {
+      WkWork W;
+      GCHK(wk_work(ctx, (size_t) nwind, W));
+      GCHK(ghip_ensure(ctx, T.tmp_idx, (size_t) nwind * 4));
+      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) nwind * WK_NC * 8));
+      HIPCHK(hipMemcpyAsync(T.tmp_idx.p, idx, (size_t) nwind * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, rows, (size_t) nwind * WK_NC * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4, st));
+      GCHK(wk_sort_in(ctx, nwind, W, true));
+      int w[WKW_WORDS];
+      HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      if(w[WKW_ERR])
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: index %d names a particle that is not Type 3 (the context holds no "
+                         "table now)", who, w[WKW_ERRIDX]);
+      if(w[WKW_DUP])
+        return ghip_fail(ctx, GHIP_EINVAL, "%s: two rows of the wind table have the index %d (the context holds no "
+                         "table now)", who, w[WKW_DUPIDX]);
+    }
+  T.on = true;
+  T.n = nwind;
+  return GHIP_OK;
+}
+
+extern "C" int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  static const char *who = "ghip_winds_get_table";
+  if(!ctx || !nwind)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(wk_need_table(ctx, who));
+  WindTable &T = ctx->wk;
+  *nwind = T.n;
+  if(T.n > 0 && (idx || rows))
+    {
+      if(idx)
+        HIPCHK(hipMemcpyAsync(idx, T.idx.p, (size_t) T.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if(rows)
+        HIPCHK(hipMemcpyAsync(rows, T.rows.p, (size_t) T.n * WK_NC * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+    }
+  return GHIP_OK;
+}
+
+extern "C" int ghip_winds_clear(ghip_ctx *ctx)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  GCHK(ghip_winds_enter(ctx, "ghip_winds_clear"));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  ghip_renew(ctx->wk);
+  return GHIP_OK;
+}
+
+// ---- the table through ghip_rearrange / ghip_peano_order ----
+// keep[r] = the particle of row r survives; its new index is the row's new key
+__global__ void __launch_bounds__(256) k_wk_map(int m, const int *__restrict__ idx, int n_before,
+                                                const int *__restrict__ new_of_old, int *__restrict__ newidx,
+                                                int *__restrict__ keep)
+{
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if(r >= m)
+    return;
+  const int i = idx[r];
+  const int j = (i >= 0 && i < n_before) ? new_of_old[i] : -1;
+  newidx[r] = j;
+  keep[r] = j >= 0;
+}
+
+// the kept rows, unsorted, into the image: tmp_idx[a] = newidx[sel[a]], tmp_rows[a] = rows[sel[a]]
+__global__ void __launch_bounds__(256) k_wk_compact(int kept, const int *__restrict__ sel,
+                                                    const int *__restrict__ newidx, const double *__restrict__ rows,
+                                                    int *__restrict__ tmp_idx, double *__restrict__ tmp_rows)
+{
+  const long long e = (long long) blockIdx.x * 256 + threadIdx.x;
+  if(e >= (long long) kept * WK_NC)
+    return;
+  const int a = (int) (e / WK_NC), c = (int) (e % WK_NC);
+  const int r = sel[a];
+  tmp_rows[e] = rows[(size_t) r * WK_NC + c];
+  if(c == 0)
+    tmp_idx[a] = newidx[r];
+}
+
+int ghip_winds_remap(ghip_ctx *ctx, int n_before, const int *new_of_old)
+{
+  WindTable &T = ctx->wk;
+  if(!T.on || T.n == 0 || n_before <= 0)
+    return GHIP_OK;
+  hipStream_t st = ctx->stream;
+  const int m = T.n;
+  WkWork W;
+  GCHK(wk_work(ctx, (size_t) m, W));
+  GCHK(ghip_ensure(ctx, T.tmp_idx, (size_t) m * 4));
+  GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) m * WK_NC * 8));
+  HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4, st));
+  int *newidx = reinterpret_cast<int *>(W.k0), *sel = reinterpret_cast<int *>(W.k1);
+  k_wk_map<<<cdiv(m, 256), 256, 0, st>>>(m, P<int>(T.idx), n_before, new_of_old, newidx, W.a);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, nullptr, W.a, sel, W.words + WKW_COUNT, m, st));
+  int kept = 0;
+  HIPCHK(hipMemcpyAsync(&kept, W.words + WKW_COUNT, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(kept < 0 || kept > m)
+    return ghip_fail(ctx, GHIP_EDEVICE, "%d of %d rows of the wind table kept", kept, m);
+  T.n = kept;
+  if(kept == 0)
+    return GHIP_OK;
+  k_wk_compact<<<cdiv((long long) kept * WK_NC, 256), 256, 0, st>>>(kept, sel, newidx, P<double>(T.rows),
+                                                                   P<int>(T.tmp_idx), P<double>(T.tmp_rows));
+  HIPCHK(hipGetLastError());
+  // (the image is complete before wk_sort_in reuses k0 / k1 as sort keys: one stream)
+  return wk_sort_in(ctx, kept, W, false);
+}
+
+// ---- growth (ghip_wind_spawn, ghip_accretion.hip) ----
+int ghip_winds_reserve(ghip_ctx *ctx, int extra, int **idx_tail, double **rows_tail)
+{
+  WindTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  if(!T.on)
+    {
+      T.on = true;
+      T.n = 0;
+      T.stale = false;
+    }
+  const size_t m = (size_t) T.n + (size_t) (extra > 0 ? extra : 0);
+  if(T.idx.cap < m * 4 || T.rows.cap < m * WK_NC * 8)   // into a larger block, which then becomes the table
+    {
+      GCHK(ghip_ensure(ctx, T.tmp_idx, m * 4));
+      GCHK(ghip_ensure(ctx, T.tmp_rows, m * WK_NC * 8));
+      if(T.n > 0)
+        {
+          HIPCHK(hipMemcpyAsync(T.tmp_idx.p, T.idx.p, (size_t) T.n * 4, hipMemcpyDeviceToDevice, st));
+          HIPCHK(hipMemcpyAsync(T.tmp_rows.p, T.rows.p, (size_t) T.n * WK_NC * 8, hipMemcpyDeviceToDevice, st));
+        }
+      T.idx.swap(T.tmp_idx);
+      T.rows.swap(T.tmp_rows);
+    }
+  *idx_tail = P<int>(T.idx) + T.n;
+  *rows_tail = P<double>(T.rows) + (size_t) T.n * WK_NC;
+  return GHIP_OK;
+}
+
+void ghip_winds_appended(ghip_ctx *ctx, int extra)
+{
+  ctx->wk.n += extra;
+}
+
+// ---- the loop ----
+// flags[a] = the a-th active particle is Type 3 and has a row with StellarAge < Time (:259); an active Type-3
+// particle without a row raises the error words
+__global__ void __launch_bounds__(256) k_wk_flag_list(int nact, const int *__restrict__ act, int n,
+                                                      const int *__restrict__ type, int nrows,
+                                                      const int *__restrict__ idx, const double *__restrict__ rows,
+                                                      double Time, int *__restrict__ flags, int *__restrict__ words)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= nact)
+    return;
+  const int i = act ? act[a] : a;
+  int f = 0;
+  if(i >= 0 && i < n && type[i] == 3)
+    {
+      const int r = d_wk_find(nrows, idx, i);
+      if(r < 0)
+        {
+          words[WKW_ERR] = 1;
+          atomicMax(words + WKW_ERRIDX, i);
+        }
+      else
+        f = rows[(size_t) r * WK_NC + GHIP_WK_STELLAR_AGE] < Time;
+    }
+  flags[a] = f;
+}
+
+// the in planes of the list from the rows
+__global__ void __launch_bounds__(256) k_wk_load(int nw, const int *__restrict__ list, int nrows,
+                                                 const int *__restrict__ idx, const double *__restrict__ rows,
+                                                 double *__restrict__ w)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= nw)
+    return;
+  const int r = d_wk_find(nrows, idx, list[a]);
+  if(r < 0)
+    return;   // (never: the selection listed only particles with a row)
+  const double *R = rows + (size_t) r * WK_NC;
+  for(int q = WP_AGE; q <= WP_DRMIN; q++)
+    w[(size_t) q * nw + a] = R[q];
+}
+
+// the out planes WP_OLD .. WP_DMOM back into the rows (all == 0: WP_DT1 .. WP_DMOM only, after a call that did not
+// enter the loop), and the code of the elimination
+__global__ void __launch_bounds__(256) k_wk_store(int nw, const int *__restrict__ list, int nrows,
+                                                  const int *__restrict__ idx, double *__restrict__ rows,
+                                                  const double *__restrict__ w, const int *__restrict__ deleted, int all)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= nw)
+    return;
+  const int r = d_wk_find(nrows, idx, list[a]);
+  if(r < 0)
+    return;
+  double *R = rows + (size_t) r * WK_NC;
+  for(int q = all ? WP_OLD : WP_DT1; q <= WP_DMOM; q++)
+    R[q] = w[(size_t) q * nw + a];
+  R[GHIP_WK_DELETED] = (double) deleted[a];
+}
+
+// :558-559: one thread, list order (what ghip_wind_feedback adds on the host from its out arrays)
+__global__ void k_wk_result(int nw, const int *__restrict__ deleted, const double *__restrict__ old,
+                            ghip_wind_result *__restrict__ res)
+{
+  if(blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  int nd = 0;
+  double mom = 0;
+  for(int a = 0; a < nw; a++)
+    if(deleted[a])
+      {
+        nd++;
+        if(deleted[a] == 1)
+          mom += old[a];
+      }
+  res->ndeleted = nd;
+  res->deleted_momentum = mom;
+}
+
+extern "C" int ghip_winds_feedback(ghip_ctx *ctx, const ghip_wind_params *p, ghip_wind_result *result)
+{
+  if(!ctx)
+    return GHIP_EINVAL;
+  GHIP_JOIN(ctx);
+  static const char *who = "ghip_winds_feedback";
+  const auto t_begin = std::chrono::steady_clock::now();
+  if(result)
+    memset(result, 0, sizeof(*result));
+  if(!result || !p)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  if(p->max_iter < 1 || !(p->dt_fac >= 0))
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
+  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(wk_need_table(ctx, who));
+  WindTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  for(int k = 0; k < 5; k++)
+    ctx->wind_ms[k] = 0;
+  // ---- the list: a selection over the active list, its length to the host ----
+  const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
+  const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
+  if(nact <= 0)
+    return GHIP_OK;
+  WkWork W;
+  GCHK(wk_work(ctx, (size_t) nact, W));
+  HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4 + 64, st));
+  k_wk_flag_list<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), T.n, P<int>(T.idx),
+                                                  P<double>(T.rows), p->Time, W.a, W.words);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + WKW_COUNT, nact, st));
+  int w[WKW_WORDS];
+  HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  if(w[WKW_ERR])
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-3 particle %d has no row in the wind table (%d rows); "
+                     "nothing was changed", who, w[WKW_ERRIDX], T.n);
+  const int nw = w[WKW_COUNT];
+  if(nw < 0 || nw > nact || nw > T.n)
+    return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d active particles, %d rows", who, nw, nact, T.n);
+  if(nw == 0)
+    return GHIP_OK;
+  GCHK(wind_need_trees(ctx, who));
+  WindDev d;
+  GCHK(wind_begin_list(ctx, nw, W.b, false, &d));
+  const size_t D = (size_t) nw;
+  k_wk_load<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<int>(T.idx), P<double>(T.rows), d.w);
+  HIPCHK(hipGetLastError());
+  WindEnd end;
+  GCHK(wind_loop(ctx, p, d, who, result, &end));
+  const bool all = end.stage != WIND_FLOOR;
+  k_wk_store<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<int>(T.idx), P<double>(T.rows), d.w, d.deleted, all);
+  HIPCHK(hipGetLastError());
+  if(all)
+    {
+      k_wk_result<<<1, 64, 0, st>>>(nw, d.deleted, d.w + WP_OLD * D, W.result);
+      HIPCHK(hipGetLastError());
+      ghip_wind_result r;
+      HIPCHK(hipMemcpyAsync(&r, W.result, sizeof(r), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      result->ndeleted = r.ndeleted;
+      result->deleted_momentum = r.deleted_momentum;
+      wind_spread_ms(ctx, end);
+    }
+  else
+    HIPCHK(ghip_stream_sync(ctx, st));
+  ctx->wind_ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  if(end.stage == WIND_NOCONV)
+    return ghip_fail(ctx, GHIP_ENOCONV, "%s: %d wind particles still under way after max_iter = %d iterations", who,
+                     end.under, p->max_iter);
   return GHIP_OK;
 }
 

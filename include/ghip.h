@@ -268,7 +268,8 @@ long long ghip_device_bytes_in_use(void);
  *   refused     values that were given per gas particle or per particle for the old counts -- alpha /
  *   until       Dtalpha (ghip_visc_set_alpha), DragAccel / DeltaDustMomentum (ghip_kick_set_fields, read
  *   given       under integration flags only), DragHeating, Injected_BH_Momentum / RadAccel, the sink
- *   again       marks, the sink table (ghip_sinks_set_table) and the candidates of ghip_sfr_cooling:
+ *   again       marks, the sink table (ghip_sinks_set_table), the wind table (ghip_winds_set_table)
+ *               and the candidates of ghip_sfr_cooling:
  *               the pass that reads them fails with GHIP_EINVAL and a message instead of reading
  *               them at another pitch; ghip_tree_substep and ghip_tree_kick_nodes refuse a kept tree
  *               (ghip_set_dynamic_tree) of another particle number until a full build has captured the
@@ -1033,7 +1034,7 @@ int ghip_dust_drag_grains(ghip_ctx *ctx, const ghip_dust_params *p, const ghip_d
  * VARIABLE_PHOTON_SEARCH_RADIUS and RAD_ACCEL as run-time switches): the propagation loop of momentum_feedback()
  * (momentum_feedback.c:251-591) with its two neighbour passes virtual_density() and virtual_spread_momentum().
  * ghip_set_integration_flags gives a Type-3 particle its step limit and neither kick nor drift; THIS is where
- * it moves.  Not built: spawning (:70-245, host code: it draws random numbers and changes NumPart),
+ * it moves.  The creation of wind particles (:70-246) is ghip_wind_spawn, below.  Not built:
  * fb_particles.c (PHOTONS, VIRTUAL_HEATING, re-emission), REAL_EOS, NON_GRAY_RAD_TRANSFER.
  * The wind particles are given by their particle indices: the active Type-3 particles with StellarAge < Time
  * and WindOrPhoton == 0, in active-list order (:253-278); their per-particle state travels in host arrays in
@@ -1134,6 +1135,121 @@ int ghip_set_rad_accel(ghip_ctx *ctx, int on);
  * move, density, spread, list, and the whole call; synchronises.  After GHIP_DD_WIND: this shard's move, own
  * density, spread, list, and in ms[4] the density of the imported particles */
 int ghip_wind_get_timing(ghip_ctx *ctx, double ms[5]);
+
+/* ---- the wind particles on the resident state: the wind table, the propagation loop without host arrays and
+ * the creation of wind particles by the massive sinks (momentum_feedback.c:70-246).  With them the wind cycle
+ * closes on the device: the sinks accrete (ghip_blackhole_accretion), emit (ghip_wind_spawn), the wind
+ * propagates (ghip_winds_feedback) and what is spent leaves with ghip_rearrange; no per-particle host array and
+ * no pass through the host is involved.  Everything here is for one GPU: a plain context or a ghip_dd_init
+ * context of a single rank.  On a ghip_set_shard context every entry point of this section returns GHIP_EINVAL;
+ * on a ghip_dd_init context with more than one rank it returns GHIP_EINVAL and says that the shard form is not
+ * built.  Not built either: force_add_star_to_tree (a spawn discards the trees), fb_particles.c / PHOTONS,
+ * SPH_EMIT, and the P[i].dt1 the reference writes into the sink's own record (:80).
+ *
+ * The table holds one row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE INDEX and kept in
+ * ascending index order in device memory owned by the context.  It cannot be keyed by P[].ID as the sink table
+ * is: :215 sets ID = the sink's ID + (NumPart + stars_spawned), and NumPart shrinks when
+ * rearrange_particle_sequence() eliminates particles, so two live wind particles can carry the same ID (the
+ * shipped -DIGNORE_NON_UNIQUE tolerates it).  Because it is keyed by index, ghip_rearrange and ghip_peano_order
+ * carry it: every index goes through their new_of_old, the rows of eliminated particles are dropped, and the
+ * rows are put back in ascending order.  After ghip_set_counts with CHANGED counts the table is refused until
+ * it is given again. ---- */
+enum
+{
+  GHIP_WK_STELLAR_AGE = 0,   /* P[].StellarAge */
+  GHIP_WK_BIRTH_ENERGY,      /* P[].BirthPhotonEnergy */
+  GHIP_WK_OLD_MOMENTUM,      /* P[].OldPhotonMomentum */
+  GHIP_WK_NEW_DENSITY,       /* P[].NewDensity */
+  GHIP_WK_DRMIN,             /* P[].b1.BH_Density */
+  GHIP_WK_DT1,               /* P[].dt1 */
+  GHIP_WK_DT2,               /* P[].dt2 */
+  GHIP_WK_DT_JUMP,           /* P[].DtJump */
+  GHIP_WK_DELTA_MOMENTUM,    /* P[].DeltaPhotonMomentum */
+  GHIP_WK_DELETED,           /* the code of ghip_wind_state.deleted of the last ghip_winds_feedback: 0.0, 1.0 or 2.0 */
+  GHIP_WK_COUNT
+};
+/* idx [nwind], rows [nwind][GHIP_WK_COUNT] in any order (sorted on the device).  GHIP_EINVAL, and the context
+ * holds no table: an index out of range, an index that names a particle that is not Type 3, an index given
+ * twice (the message names the index).  nwind = 0: an empty table. */
+int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows);
+/* *nwind rows in ascending index order; idx and rows NULL: the count only */
+int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows);
+int ghip_winds_clear(ghip_ctx *ctx);   /* no table; its device memory is given back */
+/* The resident form of ghip_wind_feedback: the same kernels and the same loop, no wind_idx, no ghip_wind_state.
+ * The list is a device selection: the active Type-3 particles (ghip_set_active / ghip_find_next_sync_point)
+ * that have a row with StellarAge < Time (:259), in active-list order.  An active Type-3 particle without a
+ * row: GHIP_EINVAL, the message names its index, and nothing has changed.  The state of the listed particles is
+ * gathered from the rows, and after the loop and the elimination every column but StellarAge and BirthEnergy
+ * is written back (GHIP_WK_DELETED with the code); a row that is not listed is not touched.  The host reads
+ * the length of the list (8 bytes) where ghip_wind_feedback uploads the state, then as there the 40 bytes per
+ * iteration, and the result, which one thread adds in list order.  Everything else is as ghip_wind_feedback
+ * says, the deviation and GHIP_ENOCONV included; the values equal, bit for bit, those of ghip_wind_feedback
+ * called with the same list and the rows' state. */
+int ghip_winds_feedback(ghip_ctx *ctx, const ghip_wind_params *p, ghip_wind_result *result);
+typedef struct
+{
+  double Time;
+  double dt_fac;                 /* All.Timebase_interval / hubble_a (:79) */
+  double SMBHmass, VirtualStart, VirtualFeedBack, VirtualMomentum, VirtualMass, FeedBackVelocity;
+  double UnitVelocity_in_cm_per_s, UnitTime_in_s;
+  double SofteningBndryMaxPhys;
+  double InnerBoundary;          /* added to Hsml behind the softening under accretion_radius (:182) */
+  int NumCurrentTiStep;
+  int MaxPart;
+  int fraction_of_ledd_feedback;     /* -DFRACTION_OF_LEDD_FEEDBACK: :85, else :100-105 */
+  int accretion_at_eddington_rate;   /* -DACCRETION_AT_EDDINGTON_RATE (read under fraction_of_ledd_feedback): :88-89 */
+  int startup_luminosity;            /* -DSTARTUP_LUMINOSITY: emit above 1e-4, else above 0 (:114-118) */
+  int isotropic;                     /* -DISOTROPIC: :169, else :171 */
+  int accretion_radius;              /* -DACCRETION_RADIUS: :182 */
+  int fly_through_empty_space;       /* -DVIRTUAL_FLY_THORUGH_EMPTY_SPACE: the new row's drmin = 0 (:198), else the
+                                        sink's b1.BH_Density, which :158 copies */
+  const double *rnd_table;           /* the host's RndTable [nrnd], copied by the call; NULL: the table bound with */
+  int nrnd;                          /* ghip_set_rnd_table.  Neither: GHIP_EINVAL */
+  int pad;
+} ghip_wind_spawn_params;
+typedef struct
+{
+  int spawned;                /* stars_spawned */
+  int nsinks_emitting;        /* sinks with new_wind > 0 */
+  int first_index;            /* index of the first new particle: NumPart before the call */
+  int pad;
+  double new_wind_exact_sum;  /* new_wind_exact of the emitting sinks, added in list order by one thread */
+  long long gsl_draws;        /* 3 * spawned: the draws of :193 (multiplied by 0. there), which the host takes from its
+                                 own random_generator to keep its stream where the reference's would be */
+} ghip_wind_spawn_report;
+size_t ghip_wind_spawn_params_size(void);
+size_t ghip_wind_spawn_report_size(void);
+/* momentum_feedback.c:70-246 on the device.  Needs the sink table (ghip_sinks_set_table: BH_Mdot and BH_Mass are
+ * read from the rows; an active Type-5 particle without a row is GHIP_EINVAL as in the sink passes) and a wind
+ * table; a context without a wind table gets an empty one.
+ *   count   one thread per active Type-5 particle, in active-list order.  A sink counts when Mass > 0.5 SMBHmass
+ *           && Time > VirtualStart (:75).  dt = (TimeBin ? 1 << TimeBin : 0) * dt_fac; new_wind_exact from :85-88
+ *           under the switches or :100-105; new_wind = (int) new_wind_exact + 1 above the threshold, else 0;
+ *           correction_wind = new_wind_exact / new_wind (:126-133).  Compiled without contraction.
+ *   scan    an exclusive scan of the counts and the one blocking read of the call, the total.  NumPart + total >
+ *           MaxPart: GHIP_EINVAL (the reference's endrun(8888); the message has both numbers), nothing has changed.
+ *   grow    the state goes from n to n + total particles: every GHIP_F_* field and every optional per-particle
+ *           array (SwallowID, the kick's NewDensity) of an appended particle is its sink's, P[NumPart +
+ *           stars_spawned] = P[i] (:158).  Arrays per gas particle do not change: ngas does not.
+ *   fill    one thread per new particle j, the bits-th of its sink: Type = 3; Hsml += SofteningBndryMaxPhys (+=
+ *           InnerBoundary); theta and phi from RndTable[(ID + 2 + bits + NumCurrentTiStep) % nrnd] and [(ID + 3 +
+ *           ...) % nrnd] in unsigned 32-bit arithmetic (:168-173); Vel = C / UnitVelocity * dir / FeedBackVelocity
+ *           (:191); Pos stays the sink's (the term of :193 is multiplied by 0.); ID += j in unsigned arithmetic
+ *           (:215); OldMomentum = VirtualMomentum-energy / C * UnitVelocity * correction, BirthEnergy = energy *
+ *           correction (:225-226); Mass = VirtualMass * OldMomentum (:228); the kick's NewDensity = 0; the row is
+ *           StellarAge = Time, dt1 = dt (:80, copied by :158), drmin as above, everything else 0, appended to
+ *           the table (the new particles have the largest indices: it stays sorted).
+ * Under accretion_at_eddington_rate a counting sink's Mass = BH_Mass (:89), whether it emits or not.
+ * Afterwards the new particles stand at the end of the active list in force (everybody active: still
+ * everybody, :202-204); the bin counts are recounted by the next ghip_find_next_sync_point; both trees and the
+ * kept tree of ghip_set_dynamic_tree are discarded (force_add_star_to_tree is not built): ghip_tree_build comes
+ * next.  The sink table is untouched: its key is the ID, and no sink moved.  spawned == 0 leaves every byte of
+ * the state, the lists and the trees as they were.
+ * CALL ORDER.  A particle born at Time is not propagated until StellarAge < Time (:259), and propagation does
+ * not touch the sinks: ghip_wind_spawn may run AFTER ghip_winds_feedback and the other neighbour passes of the
+ * step, so that they use the trees of the step, with the same result as the reference's order.  That is the
+ * intended order: ghip_blackhole_accretion, ghip_winds_feedback, ghip_wind_spawn, the kick. */
+int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, ghip_wind_spawn_report *report);
 
 /* The dust passes on a multi-GPU shard (GHIP_DD_DUST_DENSITY / GHIP_DD_DUST_DRAG through ghip_dd_begin /
  * ghip_dd_run): the reference's export of the grains (dust.c:60-261, 560-746).  Each grain goes to every
@@ -1738,7 +1854,9 @@ size_t ghip_dd_fof_args_size(void);
  * With a record travel, bit for bit, in both calls: every GHIP_F_* field and every optional resident array held
  * for the current counts -- DragHeating, alpha and Dtalpha, Injected_BH_Momentum, RadAccel, SwallowID and
  * Injected_BH_Energy, DragAccel, DeltaDustMomentum and NewDensity of ghip_kick_set_fields.  An array held for
- * other counts is dropped, as by GHIP_DD_MIGRATE.  A call that moved something leaves the rest of the state as
+ * other counts is dropped, as by GHIP_DD_MIGRATE.  The wind table (ghip_winds_set_table), which is keyed by
+ * particle index, follows: every index goes through new_of_old, the rows of eliminated particles are dropped and
+ * the rows are put back in ascending index order.  A call that moved something leaves the rest of the state as
  * a migration does: both trees are gone, a kept tree (ghip_set_dynamic_tree) is refused until a full build, the
  * target lists and the active list are gone (everybody is active; ghip_find_next_sync_point makes the next list,
  * as reconstruct_timebins() at domain.c:305), the potential and the FOF labels are stale and refused.  Every
