@@ -23,7 +23,7 @@ HIP_SOURCES = ["ghip_api.hip", "ghip_tree.hip", "ghip_gravity.hip", "ghip_sph.hi
                "ghip_dd.hip", "ghip_comm.hip", "ghip_sink.hip", "ghip_dust.hip",
                "ghip_sfr.hip", "ghip_potential.hip", "ghip_decomp.hip", "ghip_prim.hip",
                "ghip_records.hip", "ghip_sync.hip", "ghip_fof.hip", "ghip_wind.hip", "ghip_sequence.hip",
-               "ghip_accretion.hip"]
+               "ghip_accretion.hip", "ghip_rowtable.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17"]
 
 

@@ -11,9 +11,11 @@
 //   density() for Type-5 targets                  ghip_sink_density's kernel and h iteration (ghip_sinks_density)
 //   momentum_feedback(), the sinks' emission      momentum_feedback.c:70-246   -> ghip_wind_spawn, the end of this file
 //
-// The per-sink state lives in a table of GHIP_SK_COUNT doubles per Type-5 particle, keyed by P[].ID and sorted by
-// it: a pass selects the active Type-5 particles on the device, in active-list order, and finds each one's row
-// by a binary search.  Nothing here is keyed by particle index, so no reordering of the particles moves the table.
+// The per-sink state lives in a keyed row table (ghip_rowtable.h) of GHIP_SK_COUNT doubles per
+// Type-5 particle, keyed by P[].ID: a pass selects the active Type-5 particles on the device, in active-list order,
+// and finds each one's row by d_rt_find.  Nothing here is keyed by particle index, so no reordering of the particles
+// moves the table.  Sorting, compaction, growth and the table's refusals are the row table's; this file says which
+// rows (k_sk_mark_dead, k_sk_flag_sinks, k_sk_rows, the k_skm_* kernels) and what is in them.
 // Sinks are few (hundreds): everything below but the two neighbour passes is one thread per sink, and the sums
 // that have an order (the report) are added by a single thread in active-list order.
 //
@@ -29,147 +31,15 @@
 // op-by-op IEEE evaluation of the C text, which the tests restate in numpy.
 #pragma clang fp contract(off)
 
-#include "ghip_prim.h"
+#include "ghip_rowtable.h"
 
 #define SK_NC GHIP_SK_COUNT
-
-// ints at the front of SinkTable::work
-enum
-{
-  SKW_COUNT = 0,   // active Type-5 particles selected
-  SKW_ERR,         // one of them has no row
-  SKW_ERRID,       // ... the largest such ID
-  SKW_DUP,         // two rows with the same ID
-  SKW_DUPID,
-  SKW_KEPT,        // rows kept by ghip_sinks_drop_eliminated
-  SKW_WORDS = 16
-};
-#define SK_REPORT_BYTES 1024   // room for either report behind the words
-static_assert(sizeof(ghip_bh_accretion_report) <= SK_REPORT_BYTES && sizeof(ghip_sfr_form_report) <= SK_REPORT_BYTES,
-              "the report block of SinkTable::work");
-
-struct SkWork
-{
-  int *words;
-  char *report;
-  int *a, *b, *row;   // i32[na], i32[na], i32[nrow]
-};
-
-static int sk_work(ghip_ctx *ctx, size_t na, size_t nrow, SkWork &W)
-{
-  const size_t head = SKW_WORDS * 4 + SK_REPORT_BYTES;
-  GCHK(ghip_ensure(ctx, ctx->sk.work, head + (2 * na + nrow) * 4 + 64));
-  char *base = P<char>(ctx->sk.work);
-  W.words = reinterpret_cast<int *>(base);
-  W.report = base + SKW_WORDS * 4;
-  W.a = reinterpret_cast<int *>(base + head);
-  W.b = W.a + na;
-  W.row = W.b + na;
-  return GHIP_OK;
-}
 
 struct AccK
 {
   int limited, at_edd, enforce, mass_real, dust;
   double medd_fac, tvisc, eddf, dt_fac;
 };
-
-// the row of `id` in the ascending list ids[0, n), -1: none
-__device__ __forceinline__ int d_sk_find(int n, const unsigned int *__restrict__ ids, unsigned int id)
-{
-  int lo = 0, hi = n;
-  while(lo < hi)
-    {
-      const int mid = (lo + hi) >> 1;
-      if(ids[mid] < id)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-  return (lo < n && ids[lo] == id) ? lo : -1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// the table
-// ---------------------------------------------------------------------------------------------
-__global__ void k_sk_iota(int m, int *__restrict__ v)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if(r < m)
-    v[r] = r;
-}
-
-__global__ void k_sk_fill(int m, int value, int *__restrict__ v)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if(r < m)
-    v[r] = value;
-}
-
-// dst row r = src row from[r]
-__global__ void k_sk_gather_rows(int m, const int *__restrict__ from, const double *__restrict__ src,
-                                 double *__restrict__ dst)
-{
-  const long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-  if(e < (long long) m * SK_NC)
-    {
-      const int r = (int) (e / SK_NC), c = (int) (e % SK_NC);
-      dst[e] = src[(size_t) from[r] * SK_NC + c];
-    }
-}
-
-__global__ void k_sk_gather_ids(int m, const int *__restrict__ from, const unsigned int *__restrict__ src,
-                                unsigned int *__restrict__ dst)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if(r < m)
-    dst[r] = src[from[r]];
-}
-
-__global__ void k_sk_dups(int m, const unsigned int *__restrict__ ids, int *__restrict__ words)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if(r + 1 < m && ids[r] == ids[r + 1])
-    {
-      words[SKW_DUP] = 1;
-      atomicMax(reinterpret_cast<unsigned int *>(words + SKW_DUPID), ids[r]);
-    }
-}
-
-// the m rows in sk.tmp_id / sk.tmp_rows, in any order, become the table: sorted by ID, duplicates refused
-static int sk_install(ghip_ctx *ctx, int m, const char *who)
-{
-  SinkTable &T = ctx->sk;
-  hipStream_t st = ctx->stream;
-  T.on = false;
-  T.n = 0;
-  T.stale = false;
-  if(m > 0)
-    {
-      SkWork W;
-      GCHK(sk_work(ctx, (size_t) m, 0, W));
-      GCHK(ghip_ensure(ctx, T.id, (size_t) m * 4));
-      GCHK(ghip_ensure(ctx, T.rows, (size_t) m * SK_NC * 8));
-      HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
-      k_sk_iota<<<cdiv(m, 256), 256, 0, st>>>(m, W.a);
-      HIPCHK(hipGetLastError());
-      GCHK(ghip_sort_pairs(ctx, P<unsigned int>(T.tmp_id), P<unsigned int>(T.id), W.a, W.b, m, 32, st));
-      k_sk_gather_rows<<<cdiv((long long) m * SK_NC, 256), 256, 0, st>>>(m, W.b, P<double>(T.tmp_rows),
-                                                                        P<double>(T.rows));
-      k_sk_dups<<<cdiv(m, 256), 256, 0, st>>>(m, P<unsigned int>(T.id), W.words);
-      HIPCHK(hipGetLastError());
-      int w[SKW_WORDS];
-      HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      T.last_dup = (unsigned int) w[SKW_DUPID];
-      if(w[SKW_DUP])
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: two rows of the sink table have the ID %u (the context holds no "
-                         "table now)", who, (unsigned int) w[SKW_DUPID]);
-    }
-  T.on = true;
-  T.n = m;
-  return GHIP_OK;
-}
 
 // what every entry point of the section refuses
 static int sk_enter(ghip_ctx *ctx, const char *who, bool need_table)
@@ -181,15 +51,7 @@ static int sk_enter(ghip_ctx *ctx, const char *who, bool need_table)
   if(!ctx->id_given)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table is keyed by P[].ID, and GHIP_F_ID has not been given "
                      "since ghip_set_counts (ghip_set_field)", who);
-  if(need_table)
-    {
-      if(ctx->sk.on && ctx->sk.stale)
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table was given for other counts: give it again after "
-                         "ghip_set_counts (ghip_sinks_set_table)", who);
-      if(!ctx->sk.on)
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: no sink table (ghip_sinks_set_table)", who);
-    }
-  return GHIP_OK;
+  return need_table ? ghip_rt_need(ctx, ctx->sk, who, true) : GHIP_OK;
 }
 
 // the two passes that one GPU runs alone are collectives on a multi-GPU shard, where the table holds the rows of
@@ -209,15 +71,9 @@ extern "C" int ghip_sinks_set_table(ghip_ctx *ctx, int nsink, const unsigned int
   if(!ctx || nsink < 0 || (nsink > 0 && (!id || !rows)))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_set_table: bad arguments");
   GCHK(sk_enter(ctx, "ghip_sinks_set_table", false));
-  SinkTable &T = ctx->sk;
-  if(nsink > 0)
-    {
-      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) nsink * 4));
-      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) nsink * SK_NC * 8));
-      HIPCHK(hipMemcpyAsync(T.tmp_id.p, id, (size_t) nsink * 4, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, rows, (size_t) nsink * SK_NC * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-  return sk_install(ctx, nsink, "ghip_sinks_set_table");
+  int hw[RTW_WORDS];
+  GCHK(ghip_rt_stage_host(ctx, ctx->sk, nsink, id, rows));
+  return ghip_rt_install(ctx, ctx->sk, nsink, "ghip_sinks_set_table", false, hw);
 }
 
 extern "C" int ghip_sinks_get_table(ghip_ctx *ctx, int *nsink, unsigned int *id, double *rows)
@@ -227,17 +83,7 @@ extern "C" int ghip_sinks_get_table(ghip_ctx *ctx, int *nsink, unsigned int *id,
   if(!ctx || !nsink)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_get_table: bad arguments");
   GCHK(sk_enter(ctx, "ghip_sinks_get_table", true));
-  SinkTable &T = ctx->sk;
-  *nsink = T.n;
-  if(T.n > 0 && (id || rows))
-    {
-      if(id)
-        HIPCHK(hipMemcpyAsync(id, T.id.p, (size_t) T.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-      if(rows)
-        HIPCHK(hipMemcpyAsync(rows, T.rows.p, (size_t) T.n * SK_NC * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-    }
-  return GHIP_OK;
+  return ghip_rt_get(ctx, ctx->sk, nsink, id, rows);
 }
 
 extern "C" int ghip_sinks_clear(ghip_ctx *ctx)
@@ -245,9 +91,7 @@ extern "C" int ghip_sinks_clear(ghip_ctx *ctx)
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  ghip_renew(ctx->sk);
-  return GHIP_OK;
+  return ghip_rt_clear(ctx, ctx->sk);
 }
 
 // keep[row] = 0 for the row of every Type-5 particle that the map eliminates
@@ -258,7 +102,7 @@ __global__ void k_sk_mark_dead(int n, const int *__restrict__ type, const int *_
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if(i < n && type[i] == 5 && new_of_old[i] < 0)
     {
-      const int r = d_sk_find(nrows, ids, (unsigned int) idf[i]);
+      const int r = d_rt_find(nrows, ids, (unsigned int) idf[i]);
       if(r >= 0)
         keep[r] = 0;
     }
@@ -266,39 +110,19 @@ __global__ void k_sk_mark_dead(int n, const int *__restrict__ type, const int *_
 
 int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old)
 {
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   if(!T.on || T.n == 0 || n_before <= 0 || !ctx->id_given)
     return GHIP_OK;
   hipStream_t st = ctx->stream;
   const int m = T.n;
-  SkWork W;
-  GCHK(sk_work(ctx, (size_t) m, 0, W));
-  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
-  k_sk_fill<<<cdiv(m, 256), 256, 0, st>>>(m, 1, W.a);
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, (size_t) m, 0, W, true));
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(W.a), 1, (size_t) m, st));
   k_sk_mark_dead<<<cdiv(n_before, 256), 256, 0, st>>>(n_before, P<int>(ctx->f[GHIP_F_TYPE]), P<int>(ctx->f[GHIP_F_ID]),
-                                                     new_of_old, m, P<unsigned int>(T.id), W.a);
+                                                     new_of_old, m, P<unsigned int>(T.key), W.a);
   HIPCHK(hipGetLastError());
-  GCHK(ghip_select_flagged(ctx, nullptr, W.a, W.b, W.words + SKW_KEPT, m, st));
-  int kept = 0;
-  HIPCHK(hipMemcpyAsync(&kept, W.words + SKW_KEPT, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  if(kept < 0 || kept > m)
-    return ghip_fail(ctx, GHIP_EDEVICE, "ghip_rearrange: %d of %d rows of the sink table kept", kept, m);
-  if(kept == m)
-    return GHIP_OK;
-  if(kept > 0)
-    {
-      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) kept * 4));
-      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) kept * SK_NC * 8));
-      k_sk_gather_ids<<<cdiv(kept, 256), 256, 0, st>>>(kept, W.b, P<unsigned int>(T.id), P<unsigned int>(T.tmp_id));
-      k_sk_gather_rows<<<cdiv((long long) kept * SK_NC, 256), 256, 0, st>>>(kept, W.b, P<double>(T.rows),
-                                                                           P<double>(T.tmp_rows));
-      HIPCHK(hipGetLastError());
-      T.id.swap(T.tmp_id);   // (ascending still: the selection keeps the order)
-      T.rows.swap(T.tmp_rows);
-    }
-  T.n = kept;
-  return GHIP_OK;
+  int kept = 0;   // (in place: the selection keeps the order, nothing is sorted)
+  return ghip_rt_compact(ctx, T, "ghip_rearrange", W, W.a, nullptr, 0, &kept);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -316,40 +140,39 @@ __global__ void k_sk_flag_sinks(int nact, const int *__restrict__ act, int n, co
 
 // row[a] of the a-th selected particle, a < min(count, G); whoever has none is an error.  (More selected particles
 // than rows: one of them has none, or two carry the same ID -- SK_BAD covers both.)
-#define SK_BAD(words, G) ((words)[SKW_ERR] != 0 || (words)[SKW_COUNT] > (G))
+#define SK_BAD(words, G) ((words)[RTW_ERR] != 0 || (words)[RTW_COUNT] > (G))
 __global__ void k_sk_rows(int nact, const int *__restrict__ sel, const int *__restrict__ idf, int nrows,
                           const unsigned int *__restrict__ ids, int G, int *__restrict__ row, int *__restrict__ words)
 {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  if(a >= nact || a >= words[SKW_COUNT])
+  if(a >= nact || a >= words[RTW_COUNT])
     return;
   const unsigned int id = (unsigned int) idf[sel[a]];
-  const int r = d_sk_find(nrows, ids, id);
+  const int r = d_rt_find(nrows, ids, id);
   if(r < 0)
     {
-      words[SKW_ERR] = 1;
-      atomicMax(reinterpret_cast<unsigned int *>(words + SKW_ERRID), id);
+      words[RTW_ERR] = 1;
+      atomicMax(reinterpret_cast<unsigned int *>(words + RTW_ERRKEY), id);
     }
   else if(a < G)
     row[a] = r;
 }
 
 // selection + rows, everything left on the device: W.b = the particles, W.row = their rows, W.words
-static int sk_select(ghip_ctx *ctx, int G, SkWork &W, int *nact_out)
+static int sk_select(ghip_ctx *ctx, int G, RtWork &W, int *nact_out)
 {
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
   *nact_out = nact;
-  GCHK(sk_work(ctx, (size_t) (nact > 0 ? nact : 1), (size_t) (G > 0 ? G : 1), W));
-  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+  GCHK(ghip_rt_work(ctx, T, (size_t) (nact > 0 ? nact : 1), (size_t) (G > 0 ? G : 1), W, true));
   if(nact <= 0)
     return GHIP_OK;
   const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
   k_sk_flag_sinks<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), W.a);
   HIPCHK(hipGetLastError());
-  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + SKW_COUNT, nact, st));
-  k_sk_rows<<<cdiv(nact, 256), 256, 0, st>>>(nact, W.b, P<int>(ctx->f[GHIP_F_ID]), T.n, P<unsigned int>(T.id), G,
+  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + RTW_COUNT, nact, st));
+  k_sk_rows<<<cdiv(nact, 256), 256, 0, st>>>(nact, W.b, P<int>(ctx->f[GHIP_F_ID]), T.n, P<unsigned int>(T.key), G,
                                              W.row, W.words);
   HIPCHK(hipGetLastError());
   return GHIP_OK;
@@ -368,7 +191,7 @@ __global__ void k_acc_begin(int G, const int *__restrict__ words, const int *__r
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if(a >= G)
     return;
-  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  const int cnt = words[RTW_COUNT] < G ? words[RTW_COUNT] : G;
   SinkRec S;
   if(a >= cnt || SK_BAD(words, G))
     {
@@ -464,18 +287,18 @@ extern "C" int ghip_sinks_density(ghip_ctx *ctx, const ghip_dens_params *p, doub
   GCHK(ghip_finish_gas_tree(ctx));
   if(!ctx->st.built)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: call ghip_tree_build first");
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
-  SkWork W;
+  RtWork W;
   int nact = 0;
   GCHK(sk_select(ctx, T.n, W, &nact));
-  int w[SKW_WORDS];
+  int w[RTW_WORDS];
   HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
-  if(w[SKW_ERR])
+  if(w[RTW_ERR])
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: the active Type-5 particle with ID %u has no row in "
-                     "the sink table (%d rows, %d active sinks)", (unsigned int) w[SKW_ERRID], T.n, w[SKW_COUNT]);
-  const int ns = w[SKW_COUNT];
+                     "the sink table (%d rows, %d active sinks)", (unsigned int) w[RTW_ERRKEY], T.n, w[RTW_COUNT]);
+  const int ns = w[RTW_COUNT];
   if(ns > T.n)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sinks_density: %d active Type-5 particles for %d rows of the sink "
                      "table: two of them carry the same ID", ns, T.n);
@@ -542,7 +365,7 @@ __global__ void k_acc_marks(int G, const int *__restrict__ words, const int *__r
                             SinkRec *__restrict__ recs, double *__restrict__ dpbh)
 {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  const int cnt = words[RTW_COUNT] < G ? words[RTW_COUNT] : G;
   if(a >= cnt || SK_BAD(words, G))
     return;
   const int i = recs[a].index;
@@ -558,7 +381,7 @@ __global__ void k_acc_finish(int G, const int *__restrict__ words, const int *__
                              const unsigned long long *__restrict__ gate)
 {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
-  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  const int cnt = words[RTW_COUNT] < G ? words[RTW_COUNT] : G;
   if(a >= cnt || SK_BAD(words, G) || (gate && *gate))   // gate: the shards' common verdict, not 0 = the call fails
     return;
   const int i = recs[a].index;
@@ -606,13 +429,13 @@ __global__ void k_acc_report(int G, const int *__restrict__ words, const int *__
   for(int b = 0; b < 32; b++)
     rep->TimeBin_BH_mass[b] = rep->TimeBin_BH_dynamicalmass[b] = rep->TimeBin_BH_Mdot[b] = 0;
   rep->swallowed[0] = rep->swallowed[1] = rep->swallowed[2] = 0;
-  rep->nactive_sinks = words[SKW_COUNT];
-  rep->missing = words[SKW_ERR] ? 1 : (words[SKW_COUNT] > G ? 2 : 0);
-  rep->missing_id = (unsigned int) words[SKW_ERRID];
+  rep->nactive_sinks = words[RTW_COUNT];
+  rep->missing = words[RTW_ERR] ? 1 : (words[RTW_COUNT] > G ? 2 : 0);
+  rep->missing_id = (unsigned int) words[RTW_ERRKEY];
   rep->pad = 0;
   if(rep->missing)
     return;
-  const int cnt = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  const int cnt = words[RTW_COUNT] < G ? words[RTW_COUNT] : G;
   for(int a = 0; a < cnt; a++)
     {
       const double *R = rows + (size_t) row[a] * SK_NC;
@@ -656,7 +479,7 @@ extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh,
   if(!ctx->gt.built)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_blackhole_accretion: call ghip_tree_build first");
   GCHK(ghip_sink_buffers(ctx));
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const int G = T.n;
   const size_t n = (size_t) ctx->n;
@@ -667,7 +490,7 @@ extern "C" int ghip_blackhole_accretion(ghip_ctx *ctx, const ghip_bh_params *bh,
   SinkRec *drecs = P<SinkRec>(ctx->stage);
   double *dout = reinterpret_cast<double *>(drecs + g1), *dpbh = dout + 9 * g1;
   int *dvict = reinterpret_cast<int *>(dpbh + n1);
-  SkWork W;
+  RtWork W;
   int nact = 0;
   GCHK(sk_select(ctx, G, W, &nact));
   ghip_bh_accretion_report *drep = reinterpret_cast<ghip_bh_accretion_report *>(W.report);
@@ -782,10 +605,8 @@ extern "C" int ghip_sfr_form_sinks(ghip_ctx *ctx, int ncand, const double *u01, 
   if(!ctx || !report || ncand < 0 || (ncand > 0 && !u01))
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: bad arguments");
   GCHK(sk_enter(ctx, "ghip_sfr_form_sinks", false));
-  SinkTable &T = ctx->sk;
-  if(T.on && T.stale)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: the sink table was given for other counts: give it "
-                     "again after ghip_set_counts (ghip_sinks_set_table)");
+  RowTable &T = ctx->sk;
+  GCHK(ghip_rt_need(ctx, T, "ghip_sfr_form_sinks", false));
   if(ctx->sfr_ncand < 0)
     return ghip_fail(ctx, GHIP_EINVAL, "ghip_sfr_form_sinks: no candidates in place: ghip_sfr_cooling has not run "
                      "since the particles were last reordered, recounted or converted");
@@ -794,38 +615,27 @@ extern "C" int ghip_sfr_form_sinks(ghip_ctx *ctx, int ncand, const double *u01, 
                      ctx->sfr_ncand);
   memset(report, 0, sizeof(*report));
   ctx->sfr_ncand = -1;   // consumed
-  if(!T.on)
-    {
-      T.on = true;
-      T.n = 0;
-      T.stale = false;
-    }
+  ghip_rt_open_empty(T);
   if(ncand == 0)
     return GHIP_OK;
   hipStream_t st = ctx->stream;
   const int old = T.n, m = old + ncand;
-  GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) m * 4));
-  GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) m * SK_NC * 8));
+  GCHK(ghip_rt_stage(ctx, T, m, true));   // the old rows in front, the new ones behind
   // staging: u01 | mass before | mass after [ncand]
   GCHK(ghip_ensure(ctx, ctx->stage, (size_t) ncand * 24 + 256));
-  SkWork W;
-  GCHK(sk_work(ctx, (size_t) m, 0, W));
   double *du = P<double>(ctx->stage), *dmold = du + ncand, *dmnew = dmold + ncand;
   const int *dcand = P<int>(ctx->sfr_cand);
-  if(old > 0)
-    {
-      HIPCHK(hipMemcpyAsync(T.tmp_id.p, T.id.p, (size_t) old * 4, hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, T.rows.p, (size_t) old * SK_NC * 8, hipMemcpyDeviceToDevice, st));
-    }
   HIPCHK(hipMemcpyAsync(du, u01, (size_t) ncand * 8, hipMemcpyHostToDevice, st));
   k_form_rows<<<cdiv(ncand, 256), 256, 0, st>>>(ncand, dcand, du, ctx->n, P<double>(ctx->f[GHIP_F_MASS]),
                                                 P<int>(ctx->f[GHIP_F_ID]), limited_accretion != 0,
-                                                P<unsigned int>(T.tmp_id) + old,
+                                                P<unsigned int>(T.tmp_key) + old,
                                                 P<double>(T.tmp_rows) + (size_t) old * SK_NC, dmold, dmnew);
   HIPCHK(hipGetLastError());
   // (sorts, and waits: a duplicate ID is refused before any field changes)
-  GCHK(sk_install(ctx, m, "ghip_sfr_form_sinks"));
-  GCHK(sk_work(ctx, (size_t) m, 0, W));
+  int hw[RTW_WORDS];
+  RtWork W;
+  GCHK(ghip_rt_install(ctx, T, m, "ghip_sfr_form_sinks", false, hw));
+  GCHK(ghip_rt_work(ctx, T, (size_t) m, 0, W, false));
   ghip_sfr_form_report *drep = reinterpret_cast<ghip_sfr_form_report *>(W.report);
   k_form_report<<<1, 64, 0, st>>>(ncand, dcand, dmold, ctx->n, P<int>(ctx->f[GHIP_F_TIMEBIN]), drep);
   k_form_apply<<<cdiv(ncand, 256), 256, 0, st>>>(ncand, dcand, dmnew, ctx->n, P<double>(ctx->f[GHIP_F_MASS]),
@@ -869,7 +679,7 @@ __global__ void k_skm_count(int total, const int *__restrict__ list, const unsig
   const int i = list[a];
   if(type[i] != 5 || mask[i] == 0)
     return;
-  const int r = d_sk_find(nrows, ids, (unsigned int) idf[i]);
+  const int r = d_rt_find(nrows, ids, (unsigned int) idf[i]);
   if(r < 0)
     return;
   keep[r] = 0;
@@ -889,7 +699,7 @@ __global__ void k_skm_pack(int total, const int *__restrict__ list, const unsign
   if(type[i] != 5 || mask[i] == 0)
     return;
   const unsigned int id = (unsigned int) idf[i];
-  const int r = d_sk_find(nrows, ids, id);
+  const int r = d_rt_find(nrows, ids, id);
   if(r < 0)
     return;
   const int dest = __ffsll((long long) mask[i]) - 1;
@@ -917,7 +727,7 @@ int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigne
 {
   static_assert(sizeof(SkMigRec) == 8 + 8 * SK_NC, "SkMigRec layout");
   DDState &D = ctx->dd;
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const int m = T.n, P_ = D.nranks;
   GCHK(ghip_ensure(ctx, D.sk_keep, (size_t) (m > 0 ? m : 1) * 4));
@@ -927,12 +737,12 @@ int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigne
   for(int r = 0; r < GHIP_MAXRANKS; r++)
     cnt[r] = D.sk_rscount[r] = D.sk_rsoff[r] = 0;
   if(m > 0)
-    k_sk_fill<<<cdiv(m, 256), 256, 0, st>>>(m, 1, P<int>(D.sk_keep));
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(D.sk_keep.p), 1, (size_t) m, st));
   const bool any = m > 0 && total > 0 && ctx->id_given;
   if(any)
     {
       k_skm_count<<<cdiv(total, 256), 256, 0, st>>>(total, list, mask, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                   P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.id),
+                                                   P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.key),
                                                    P<int>(D.sk_keep), P<int>(D.sk_rcnt));
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(cnt, D.sk_rcnt.p, (size_t) P_ * 4, hipMemcpyDeviceToHost, st));
@@ -954,7 +764,7 @@ int ghip_sinks_mig_pack(ghip_ctx *ctx, int total, const int *list, const unsigne
   if(tot > 0)
     {
       k_skm_pack<<<cdiv(total, 256), 256, 0, st>>>(total, list, mask, P<int>(ctx->f[GHIP_F_TYPE]),
-                                                  P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.id),
+                                                  P<int>(ctx->f[GHIP_F_ID]), m, P<unsigned int>(T.key),
                                                   P<double>(T.rows), off, lim, P<int>(D.sk_rcnt) + GHIP_MAXRANKS,
                                                   P<SkMigRec>(D.sk_rsend));
       HIPCHK(hipGetLastError());
@@ -972,7 +782,7 @@ void ghip_sinks_mig_post(ghip_ctx *ctx)
 int ghip_sinks_mig_merge(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const int m = T.n, nrecv = D.x.rtotal;
   int sent = 0;
@@ -980,35 +790,16 @@ int ghip_sinks_mig_merge(ghip_ctx *ctx)
     sent += D.sk_rscount[r];
   if(sent == 0 && nrecv == 0)
     return GHIP_OK;
-  SkWork W;
-  GCHK(sk_work(ctx, (size_t) (m + nrecv + 1), 0, W));
-  HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
-  int kept = 0;
-  if(m > 0)
-    {
-      GCHK(ghip_select_flagged(ctx, nullptr, P<int>(D.sk_keep), W.b, W.words + SKW_KEPT, m, st));
-      HIPCHK(hipMemcpyAsync(&kept, W.words + SKW_KEPT, 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      if(kept < 0 || kept > m)
-        return ghip_fail(ctx, GHIP_EDEVICE, "GHIP_DD_MIGRATE: %d of %d rows of the sink table kept", kept, m);
-    }
-  const int tot = kept + nrecv;
-  if(tot > 0)
-    {
-      GCHK(ghip_ensure(ctx, T.tmp_id, (size_t) tot * 4));
-      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) tot * SK_NC * 8));
-    }
-  if(kept > 0)
-    {
-      k_sk_gather_ids<<<cdiv(kept, 256), 256, 0, st>>>(kept, W.b, P<unsigned int>(T.id), P<unsigned int>(T.tmp_id));
-      k_sk_gather_rows<<<cdiv((long long) kept * SK_NC, 256), 256, 0, st>>>(kept, W.b, P<double>(T.rows),
-                                                                           P<double>(T.tmp_rows));
-    }
-  if(nrecv > 0)
-    k_skm_unpack<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<SkMigRec>(D.sk_rrecv), P<unsigned int>(T.tmp_id) + kept,
-                                                  P<double>(T.tmp_rows) + (size_t) kept * SK_NC);
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, (size_t) (m + nrecv + 1), 0, W, true));
+  int kept = 0, hw[RTW_WORDS];
+  GCHK(ghip_rt_compact(ctx, T, "GHIP_DD_MIGRATE", W, P<int>(D.sk_keep), nullptr, nrecv, &kept));
+  if(nrecv == 0)
+    return GHIP_OK;   // (nothing arrived: compacted in place, ascending still)
+  k_skm_unpack<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<SkMigRec>(D.sk_rrecv), P<unsigned int>(T.tmp_key) + kept,
+                                                P<double>(T.tmp_rows) + (size_t) kept * SK_NC);
   HIPCHK(hipGetLastError());
-  return sk_install(ctx, tot, "GHIP_DD_MIGRATE");
+  return ghip_rt_install(ctx, T, kept + nrecv, "GHIP_DD_MIGRATE", false, hw);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1110,7 +901,10 @@ __global__ void k_skd_report(int ns, const double *__restrict__ part, const unsi
     }
 }
 
-static int skd_w(ghip_ctx *ctx, SkWork &W) { return sk_work(ctx, ctx->dd.sk_na, ctx->dd.sk_nrow, W); }
+static int skd_w(ghip_ctx *ctx, RtWork &W)
+{
+  return ghip_rt_work(ctx, ctx->sk, ctx->dd.sk_na, ctx->dd.sk_nrow, W, false);
+}
 
 // all shards stop together: the shard that posted the failure record with its own message, the others with the
 // verdict they all read
@@ -1176,7 +970,7 @@ int ghip_dd_sinks_begin(ghip_ctx *ctx, int op, const void *params)
 static int skd_post(ghip_ctx *ctx, bool swallow, const char *who)
 {
   DDState &D = ctx->dd;
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const ghip_dd_sinks_args &A = D.sinks;
   GCHK(ghip_sink_buffers(ctx));
@@ -1190,49 +984,47 @@ static int skd_post(ghip_ctx *ctx, bool swallow, const char *who)
   HIPCHK(hipMemsetAsync(D.sk_gw.p, 0, 64, st));
   int kind = 0, cnt = 0;
   unsigned int errid = 0;
-  SkWork W;
+  RtWork W;
   D.sk_na = D.sk_nrow = 1;
   if(!ctx->id_given || !T.on || T.stale)
     {
       kind = SKD_NOTABLE;
-      GCHK(skd_w(ctx, W));
-      HIPCHK(hipMemsetAsync(W.words, 0, SKW_WORDS * 4, st));
+      GCHK(ghip_rt_work(ctx, T, D.sk_na, D.sk_nrow, W, true));
       if(!ctx->id_given)
         ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table is keyed by P[].ID, and GHIP_F_ID has not "
                                     "been given since ghip_set_counts (ghip_set_field)", who));
       else if(T.on)
-        ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the sink table was given for other counts: give it again "
-                                    "after ghip_set_counts (ghip_sinks_set_table)", who));
+        ghip_dd_hold(ctx, ghip_rt_need(ctx, T, who, true));   // (stale)
       else
         ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: this shard holds no sink table (ghip_sinks_set_table; "
                                     "either all shards hold one or none does)", who));
     }
   else
     {
-      int nact = 0, w[SKW_WORDS];
+      int nact = 0, w[RTW_WORDS];
       GCHK(sk_select(ctx, T.n, W, &nact));
       D.sk_na = (size_t) (nact > 0 ? nact : 1);
       D.sk_nrow = (size_t) (T.n > 0 ? T.n : 1);
       // (the first of the two blocking reads: the exchange needs the count)
       HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
-      if(w[SKW_ERR])
+      if(w[RTW_ERR])
         {
           kind = SKD_NOROW;
-          errid = (unsigned int) w[SKW_ERRID];
+          errid = (unsigned int) w[RTW_ERRKEY];
           ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-5 particle with ID %u has no row in this "
                                       "shard's sink table (%d rows, %d active sinks); nothing but the marks was "
-                                      "changed", who, errid, T.n, w[SKW_COUNT]));
+                                      "changed", who, errid, T.n, w[RTW_COUNT]));
         }
-      else if(w[SKW_COUNT] > T.n)
+      else if(w[RTW_COUNT] > T.n)
         {
           kind = SKD_LOCALDUP;
           ghip_dd_hold(ctx, ghip_fail(ctx, GHIP_EINVAL, "%s: %d active Type-5 particles for %d rows of this shard's "
                                       "sink table: two of them carry the same ID; nothing but the marks was changed",
-                                      who, w[SKW_COUNT], T.n));
+                                      who, w[RTW_COUNT], T.n));
         }
       else
-        cnt = w[SKW_COUNT] > 0 ? w[SKW_COUNT] : 0;
+        cnt = w[RTW_COUNT] > 0 ? w[RTW_COUNT] : 0;
     }
   D.sk_cnt = cnt;
   const int nsend = kind ? 1 : cnt;
@@ -1279,7 +1071,7 @@ static int skd_post(ghip_ctx *ctx, bool swallow, const char *who)
 int ghip_dd_sinks_step(ghip_ctx *ctx)
 {
   DDState &D = ctx->dd;
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const ghip_dd_sinks_args &A = D.sinks;
   const bool swallow = D.op == GHIP_DD_BH_SWALLOW;
@@ -1337,7 +1129,7 @@ int ghip_dd_sinks_step(ghip_ctx *ctx)
         HIPCHK(hipMemsetAsync(dpbh, 0, n * 12, st));
       if(cnt > 0)
         {
-          SkWork W;
+          RtWork W;
           GCHK(skd_w(ctx, W));
           k_acc_marks<<<cdiv(cnt, 64), 64, 0, st>>>(cnt, W.words, W.row, P<unsigned int>(ctx->bh_swallow),
                                                     P<double>(T.rows), P<SinkRec>(D.sk_send), dpbh);
@@ -1365,7 +1157,7 @@ int ghip_dd_sinks_step(ghip_ctx *ctx)
     }
   if(D.phase == FINISH)
     {
-      SkWork W;
+      RtWork W;
       GCHK(skd_w(ctx, W));
       GCHK(ghip_ensure(ctx, D.sk_own, (size_t) (cnt > 0 ? cnt : 1) * 72));
       ghip_bh_accretion_report *drep = reinterpret_cast<ghip_bh_accretion_report *>(W.report);
@@ -1418,7 +1210,7 @@ int ghip_dd_sinks_store_density(ghip_ctx *ctx)
           for(int k = 0; k < 3; k++)
             hout[4 * (size_t) cnt + 3 * (size_t) a + k] = I.gasvel[3 * (size_t) g + k];
         }
-      SkWork W;
+      RtWork W;
       GCHK(skd_w(ctx, W));
       GCHK(ghip_ensure(ctx, D.sk_own, (size_t) cnt * 72));
       HIPCHK(hipMemcpyAsync(D.sk_own.p, hout.data(), (size_t) cnt * 56, hipMemcpyHostToDevice, st));
@@ -1477,8 +1269,8 @@ struct SpawnDev
 static int spawn_dev(ghip_ctx *ctx, int G, SpawnDev &S)
 {
   const size_t g1 = (size_t) G + 1;
-  GCHK(ghip_ensure(ctx, ctx->wk.spawn, 64 + g1 * (2 * 8 + 4 * 8 + 4) + 64));
-  char *base = P<char>(ctx->wk.spawn);
+  GCHK(ghip_ensure(ctx, ctx->wk_spawn, 64 + g1 * (2 * 8 + 4 * 8 + 4) + 64));
+  char *base = P<char>(ctx->wk_spawn);
   S.words = reinterpret_cast<SpawnWords *>(base);
   S.cnt = reinterpret_cast<unsigned long long *>(base + 64);
   S.off = S.cnt + g1;
@@ -1489,7 +1281,7 @@ static int spawn_dev(ghip_ctx *ctx, int G, SpawnDev &S)
   S.qual = reinterpret_cast<int *>(S.drm + g1);
   return GHIP_OK;
 }
-static_assert(sizeof(SpawnWords) <= 64, "the words block of WindTable::spawn");
+static_assert(sizeof(SpawnWords) <= 64, "the words block of ghip_ctx::wk_spawn");
 
 // :75-133 for record a < G; record G holds the zero behind the counts
 __global__ void __launch_bounds__(64) k_spawn_count(int G, const int *__restrict__ words, const int *__restrict__ sel,
@@ -1505,7 +1297,7 @@ __global__ void __launch_bounds__(64) k_spawn_count(int G, const int *__restrict
       S.cnt[G] = 0;
       return;
     }
-  const int c = words[SKW_COUNT] < G ? words[SKW_COUNT] : G;
+  const int c = words[RTW_COUNT] < G ? words[RTW_COUNT] : G;
   unsigned long long new_wind = 0;
   double exact = 0, corr = 1., dt = 0, drm = 0;
   int qual = 0;
@@ -1553,9 +1345,9 @@ __global__ void k_spawn_words(int G, const int *__restrict__ words, SpawnDev S)
     return;
   SpawnWords w;
   w.total = S.off[G];
-  w.nactive = words[SKW_COUNT];
-  w.missing = words[SKW_ERR] ? 1 : (words[SKW_COUNT] > G ? 2 : 0);
-  w.missing_id = (unsigned int) words[SKW_ERRID];
+  w.nactive = words[RTW_COUNT];
+  w.missing = words[RTW_ERR] ? 1 : (words[RTW_COUNT] > G ? 2 : 0);
+  w.missing_id = (unsigned int) words[RTW_ERRKEY];
   w.emitting = 0;
   w.exact_sum = 0;
   for(int a = 0; a < G; a++)
@@ -1608,7 +1400,7 @@ __global__ void __launch_bounds__(256) k_spawn_fill(int total, int n, int nn, in
                                                     double *__restrict__ hsml, double *__restrict__ vel,
                                                     double *__restrict__ mass, int *__restrict__ idf,
                                                     double *__restrict__ kick_newdens, int *__restrict__ act_tail,
-                                                    int *__restrict__ tab_idx, double *__restrict__ tab_rows)
+                                                    unsigned int *__restrict__ tab_idx, double *__restrict__ tab_rows)
 {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if(t >= total)
@@ -1639,7 +1431,7 @@ __global__ void __launch_bounds__(256) k_spawn_fill(int total, int n, int nn, in
     kick_newdens[j] = 0.;
   if(act_tail)
     act_tail[t] = j;
-  tab_idx[t] = j;
+  tab_idx[t] = (unsigned int) j;
   double *R = tab_rows + (size_t) t * GHIP_WK_COUNT;
   for(int c = 0; c < GHIP_WK_COUNT; c++)
     R[c] = 0;
@@ -1670,15 +1462,13 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
   memset(report, 0, sizeof(*report));
   GCHK(ghip_winds_enter(ctx, who));
   GCHK(sk_enter(ctx, who, true));
-  if(ctx->wk.on && ctx->wk.stale)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: the wind table was given for other counts: give it again after "
-                     "ghip_set_counts (ghip_winds_set_table)", who);
+  GCHK(ghip_rt_need(ctx, ctx->wk, who, false));   // (no wind table yet: the first wind particles open one)
   if(!(p->rnd_table && p->nrnd > 0) && ctx->rnd_n <= 0)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: no RndTable: neither rnd_table / nrnd nor a table bound with "
                      "ghip_set_rnd_table", who);
   if(p->MaxPart < ctx->n)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: MaxPart = %d is below NumPart = %d", who, p->MaxPart, ctx->n);
-  SinkTable &T = ctx->sk;
+  RowTable &T = ctx->sk;
   hipStream_t st = ctx->stream;
   const int G = T.n, n = ctx->n;
   report->first_index = n;
@@ -1706,7 +1496,7 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
   K.fly = p->fly_through_empty_space != 0;
 
   // ---- count, scan, the one blocking read ----
-  SkWork W;
+  RtWork W;
   int nact = 0;
   GCHK(sk_select(ctx, G, W, &nact));
   if(nact <= 0 || n == 0)
@@ -1750,13 +1540,14 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
   if(p->rnd_table && p->nrnd > 0)
     {
       nrnd = p->nrnd;
-      GCHK(ghip_ensure(ctx, ctx->wk.rnd, (size_t) nrnd * 8));
-      HIPCHK(hipMemcpyAsync(ctx->wk.rnd.p, p->rnd_table, (size_t) nrnd * 8, hipMemcpyHostToDevice, st));
-      rnd = P<double>(ctx->wk.rnd);
+      GCHK(ghip_ensure(ctx, ctx->wk_rnd, (size_t) nrnd * 8));
+      HIPCHK(hipMemcpyAsync(ctx->wk_rnd.p, p->rnd_table, (size_t) nrnd * 8, hipMemcpyHostToDevice, st));
+      rnd = P<double>(ctx->wk_rnd);
     }
-  int *tab_idx = nullptr, *act_tail = nullptr, *old_of_new = nullptr;
+  unsigned int *tab_idx = nullptr;
+  int *act_tail = nullptr, *old_of_new = nullptr;
   double *tab_rows = nullptr;
-  GCHK(ghip_winds_reserve(ctx, total, &tab_idx, &tab_rows));
+  GCHK(ghip_rt_reserve(ctx, ctx->wk, total, &tab_idx, &tab_rows));
   const int old_nact = ctx->nactive;
   if(old_nact >= 0)   // the list in force, and the new particles behind it (:202-204)
     {
@@ -1779,7 +1570,7 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
                                                  nd ? P<double>(ctx->kick_newdens) : nullptr, act_tail, tab_idx, tab_rows);
   HIPCHK(hipGetLastError());
   HIPCHK(ghip_stream_sync(ctx, st));   // (the caller's rnd_table has been read)
-  ghip_winds_appended(ctx, total);
+  ghip_rt_appended(ctx->wk, total);
   if(old_nact >= 0)
     {
       ctx->act_host_idx.swap(ctx->act_next);

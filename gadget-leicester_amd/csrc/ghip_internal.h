@@ -188,31 +188,25 @@ struct SinkRec
   unsigned int mark;   // the sink's own resident SwallowID (the swallow pass; 0 in the other passes)
 };
 
-// The resident sink table (ghip_accretion.hip): one row of GHIP_SK_COUNT doubles per Type-5 particle, keyed by
-// P[].ID and kept in ascending ID order, so that no reordering of the particles moves it.
-struct SinkTable
+// A keyed row table on the device (ghip_rowtable.h): an ascending 32-bit key column and one row of
+// `nc` doubles per key.  The resident sink table is one, keyed by P[].ID, so that no reordering of the particles
+// moves it; the resident wind table is one, keyed by PARTICLE INDEX (two live wind particles can carry the same ID),
+// so that ghip_rearrange and ghip_peano_order send it through their maps and ghip_wind_spawn appends to it.
+struct RowTable
 {
-  DevBuf id, rows;           // u32[n], f64[n][GHIP_SK_COUNT]
-  DevBuf tmp_id, tmp_rows;   // the unsorted image a new table is sorted from
-  DevBuf work;               // selections, sort values, row indices, words, the report
+  DevBuf key, rows;           // u32[n] ascending, f64[n][nc]
+  DevBuf tmp_key, tmp_rows;   // the image: rows in any order that a new table is sorted from, or grows into
+  DevBuf work;                // status words, a report, the int arrays of selections and sorts (RtWork)
   int n = 0;
-  bool on = false;           // a table was given (possibly of 0 rows)
-  bool stale = false;        // ghip_set_counts changed the counts since: refused until given again
-  unsigned int last_dup = 0; // the ID that the last refused installation found twice
-};
-
-// The resident wind table (ghip_wind.hip): one row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE
-// INDEX (two live wind particles can carry the same ID) and kept in ascending index order: ghip_rearrange and
-// ghip_peano_order send it through their maps (ghip_winds_remap), ghip_wind_spawn appends to it.
-struct WindTable
-{
-  DevBuf idx, rows;           // i32[n], f64[n][GHIP_WK_COUNT]
-  DevBuf tmp_idx, tmp_rows;   // the unsorted image a new table is sorted from; the larger block a table grows into
-  DevBuf work;                // words, flags, sort keys and values, the selected list
-  DevBuf spawn, rnd;          // ghip_wind_spawn: per-sink counts, offsets and records; its copy of a RndTable
-  int n = 0;
+  const int nc;
+  const char *const what, *const key_what, *const setter;   // in messages: "sink", "ID", "ghip_sinks_set_table"
   bool on = false;            // a table was given (possibly of 0 rows)
   bool stale = false;         // ghip_set_counts changed the counts since: refused until given again
+  unsigned int last_dup = 0;  // the key that the last refused installation found twice
+  RowTable(int nc_, const char *what_, const char *key_what_, const char *setter_)
+      : nc(nc_), what(what_), key_what(key_what_), setter(setter_)
+  {
+  }
 };
 
 // One dust pass as ghip_dust.hip runs it: each of the four entry forms (positional, *_grains, GHIP_DD_DUST_* with
@@ -323,7 +317,7 @@ struct DDState
   ghip_dd_sinks_args sinks = {};  // arguments of the operation in progress
   int sk_form = 0;                // 0: the per-pass form; GHIP_SINKS_RESIDENT_FORM
   int sk_cnt = 0;                 // this shard's active sinks (0 on a shard that posted a failure record)
-  size_t sk_na = 1, sk_nrow = 1;  // the sizes its selection asked of SinkTable::work (the same block every phase)
+  size_t sk_na = 1, sk_nrow = 1;  // the sizes its selection asked of the sink table's work: the same block every phase
   DevBuf sk_gw;                   // u64: the verdict on the gathered records (0: fine), the same on all shards
   DevBuf sk_snap;                 // f64: this shard's rows before the Mdot step, put back when the call fails
   DevBuf sk_own;                  // f64[9][sk_cnt]: the rank-ordered sums of this shard's own sinks
@@ -668,7 +662,8 @@ struct ghip_ctx
   bool rad_accel_on = false;        // ghip_set_rad_accel: kick, PM kick and drift read RadAccel
   hipEvent_t wind_ev[8] = {};       // phase marks of ghip_wind_feedback (made by its first call)
   double wind_ms[5] = {0, 0, 0, 0, 0};
-  WindTable wk;                     // the resident wind table (ghip_winds_set_table)
+  RowTable wk{GHIP_WK_COUNT, "wind", "index", "ghip_winds_set_table"};   // the resident wind table
+  DevBuf wk_spawn, wk_rnd;          // ghip_wind_spawn: per-sink counts, offsets and records; its copy of a RndTable
 
   // the physics switches of the dust passes (ghip_set_dust_model, ghip_dust.hip)
   bool dust_model_on = false;          // any switch set: the k_dust_grain<DustM> / k_dust_density<G, DustVel> instantiations run
@@ -747,7 +742,7 @@ struct ghip_ctx
   DevBuf gq_work;                  // partial sums, kick tables and photon momenta of ghip_global_quantities
   FofState fof;                    // ghip_fof (ghip_fof.hip)
   SeqState seq;                    // ghip_rearrange / ghip_peano_order (ghip_sequence.hip)
-  SinkTable sk;                    // the resident sink table (ghip_accretion.hip)
+  RowTable sk{GHIP_SK_COUNT, "sink", "ID", "ghip_sinks_set_table"};   // the resident sink table (ghip_accretion.hip)
   DevBuf sfr_cand;                 // i32: the candidates of the last ghip_sfr_cooling, in active-list order
   int sfr_ncand = -1;              // their number (-1: none in place; ghip_sfr_form_sinks consumes them)
 };
@@ -832,13 +827,9 @@ int ghip_bh_launch_swallow(ghip_ctx *ctx, const ghip_bh_params *p, int ns, const
 // ghip_accretion.hip: ghip_rearrange drops the rows of the Type-5 particles it eliminates (a table exists)
 int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_old);
 // ghip_wind.hip: the wind table through a reordering (every index through new_of_old, the rows of eliminated
-// particles dropped, ascending order restored); what every entry point of the resident wind section refuses;
-// room for `extra` rows behind the table's own (a context without a table gets an empty one), the tails to fill,
-// and the rows counted in
-int ghip_winds_remap(ghip_ctx *ctx, int n_before, const int *new_of_old);
+// particles dropped, ascending order restored); what every entry point of the resident wind section refuses
+int ghip_winds_remap(ghip_ctx *ctx, const char *who, int n_before, const int *new_of_old);
 int ghip_winds_enter(ghip_ctx *ctx, const char *who);
-int ghip_winds_reserve(ghip_ctx *ctx, int extra, int **idx_tail, double **rows_tail);
-void ghip_winds_appended(ghip_ctx *ctx, int extra);
 // ghip_sequence.hip, for ghip_wind_spawn: the state grows from n to nn particles.  _begin gives the map to fill,
 // old_of_new [nn] on the device (the source record of every record of the new layout); _apply moves every plane
 // along it and leaves the state as after ghip_rearrange, the maps of ghip_sequence_get_map included

@@ -330,7 +330,7 @@ extern "C" int ghip_rearrange(ghip_ctx *ctx, const ghip_rearrange_params *p, ghi
   if(ctx->sk.on && !ctx->sk.stale && w[SW_ELIM])   // the rows of the eliminated Type-5 particles go with them
     GCHK(ghip_sinks_drop_eliminated(ctx, n, P<int>(S.new_of_old)));
   if(ctx->wk.on && !ctx->wk.stale)   // the wind table is keyed by index: it follows the map
-    GCHK(ghip_winds_remap(ctx, n, P<int>(S.new_of_old)));
+    GCHK(ghip_winds_remap(ctx, "ghip_rearrange", n, P<int>(S.new_of_old)));
   GCHK(seq_apply(ctx, nn, ngn));
   S.n_before = n;
   S.n_after = nn;
@@ -400,7 +400,7 @@ extern "C" int ghip_peano_order(ghip_ctx *ctx, const double DomainCorner[3], dou
   S.old_of_new.swap(S.sidx);
   S.new_of_old.swap(S.idx);
   if(ctx->wk.on && !ctx->wk.stale)
-    GCHK(ghip_winds_remap(ctx, n, P<int>(S.new_of_old)));
+    GCHK(ghip_winds_remap(ctx, "ghip_peano_order", n, P<int>(S.new_of_old)));
   GCHK(seq_apply(ctx, n, ng));
   S.n_before = S.n_after = n;
   if(changed)

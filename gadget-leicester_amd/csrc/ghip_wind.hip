@@ -35,6 +35,7 @@
 #include <chrono>
 
 #include "ghip_pairs.h"
+#include "ghip_rowtable.h"
 
 #define WIND_C 2.9979e10          // allvars.h:86
 #define WIND_THOMPSON 6.65245e-25 // allvars.h:91
@@ -1077,122 +1078,30 @@ extern "C" int ghip_wind_feedback(ghip_ctx *ctx, const ghip_wind_params *p, int 
 // ---------------------------------------------------------------------------------------------
 // the wind particles on the resident state: the wind table and the loop without host arrays
 //
-// One row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE INDEX and kept in ascending index order
-// (DESIGN.md 4.18 says why not by ID).  ghip_winds_feedback makes its list by a device selection over the active
-// list, gathers the in planes from the rows, runs wind_loop and scatters the out planes back.
+// One row of GHIP_WK_COUNT doubles per wind particle in a keyed row table (ghip_rowtable.h), keyed
+// by PARTICLE INDEX (DESIGN.md 4.18 says why not by ID).  Sorting, compaction, growth and the table's refusals are
+// the row table's; this file says which indices may have a row (k_wk_check_type), where a row goes when the particles
+// are reordered (k_wk_map), and what the loop reads and writes (k_wk_flag_list, k_wk_load, k_wk_store).
+// ghip_winds_feedback makes its list by a device selection over the active list, gathers the in planes from the
+// rows, runs wind_loop and scatters the out planes back.
 // ---------------------------------------------------------------------------------------------
 #define WK_NC GHIP_WK_COUNT
 static_assert(GHIP_WK_STELLAR_AGE == WP_AGE && GHIP_WK_DRMIN == WP_DRMIN && GHIP_WK_DELTA_MOMENTUM == WP_DMOM,
               "the first nine columns of a row are the planes WP_AGE .. WP_DMOM");
 
-// ints at the front of WindTable::work; the result of ghip_winds_feedback behind them
-enum
-{
-  WKW_COUNT = 0,   // rows kept / particles listed
-  WKW_ERR,         // 1: an index names a particle that is not Type 3 / an active Type-3 particle has no row
-  WKW_ERRIDX,      // ... the largest such index
-  WKW_DUP,         // an index stands twice
-  WKW_DUPIDX,
-  WKW_WORDS = 16
-};
-
-struct WkWork
-{
-  int *words;
-  ghip_wind_result *result;
-  int *a, *b;             // i32[m] each
-  unsigned int *k0, *k1;  // u32[m] each
-};
-
-static int wk_work(ghip_ctx *ctx, size_t m, WkWork &W)
-{
-  const size_t head = WKW_WORDS * 4 + 64;
-  static_assert(sizeof(ghip_wind_result) <= 64, "the result block of WindTable::work");
-  if(m == 0)
-    m = 1;
-  GCHK(ghip_ensure(ctx, ctx->wk.work, head + 4 * m * 4 + 64));
-  char *base = P<char>(ctx->wk.work);
-  W.words = reinterpret_cast<int *>(base);
-  W.result = reinterpret_cast<ghip_wind_result *>(base + WKW_WORDS * 4);
-  W.a = reinterpret_cast<int *>(base + head);
-  W.b = W.a + m;
-  W.k0 = reinterpret_cast<unsigned int *>(W.b + m);
-  W.k1 = W.k0 + m;
-  return GHIP_OK;
-}
-
-// the row of particle i in the ascending list idx[0, n), -1: none
-__device__ __forceinline__ int d_wk_find(int n, const int *__restrict__ idx, int i)
-{
-  int lo = 0, hi = n;
-  while(lo < hi)
-    {
-      const int mid = (lo + hi) >> 1;
-      if(idx[mid] < i)
-        lo = mid + 1;
-      else
-        hi = mid;
-    }
-  return (lo < n && idx[lo] == i) ? lo : -1;
-}
-
-// sort keys and values of m unsorted rows; an index whose particle is not Type 3 raises the error words
-// (type == nullptr: not checked)
-__global__ void __launch_bounds__(256) k_wk_keys(int m, const int *__restrict__ idx, int n,
-                                                 const int *__restrict__ type, unsigned int *__restrict__ key,
-                                                 int *__restrict__ val, int *__restrict__ words)
+// an index of the m unsorted rows whose particle is not Type 3 raises the error words
+__global__ void __launch_bounds__(256) k_wk_check_type(int m, const unsigned int *__restrict__ idx, int n,
+                                                       const int *__restrict__ type, int *__restrict__ words)
 {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if(r >= m)
     return;
-  const int i = idx[r];
-  key[r] = (unsigned int) i;
-  val[r] = r;
-  if(type && (i < 0 || i >= n || type[i] != 3))
+  const int i = (int) idx[r];
+  if(i < 0 || i >= n || type[i] != 3)
     {
-      words[WKW_ERR] = 1;
-      atomicMax(words + WKW_ERRIDX, i);
+      words[RTW_ERR] = 1;
+      atomicMax(words + RTW_ERRKEY, i);
     }
-}
-
-// dst row r = src row from[r]; idx[r] = the sorted key; two equal neighbours raise the duplicate words
-__global__ void __launch_bounds__(256) k_wk_gather(int m, const int *__restrict__ from,
-                                                   const unsigned int *__restrict__ key,
-                                                   const double *__restrict__ src, double *__restrict__ dst,
-                                                   int *__restrict__ idx, int *__restrict__ words)
-{
-  const long long e = (long long) blockIdx.x * 256 + threadIdx.x;
-  if(e >= (long long) m * WK_NC)
-    return;
-  const int r = (int) (e / WK_NC), c = (int) (e % WK_NC);
-  dst[e] = src[(size_t) from[r] * WK_NC + c];
-  if(c == 0)
-    {
-      idx[r] = (int) key[r];
-      if(r + 1 < m && key[r] == key[r + 1])
-        {
-          words[WKW_DUP] = 1;
-          atomicMax(words + WKW_DUPIDX, (int) key[r]);
-        }
-    }
-}
-
-// the m rows of the image T.tmp_idx / T.tmp_rows, in any order, become the table T.idx / T.rows, sorted by index
-// (T.n is the caller's to set); the error and duplicate words are raised on the device
-static int wk_sort_in(ghip_ctx *ctx, int m, WkWork &W, bool check_type)
-{
-  WindTable &T = ctx->wk;
-  hipStream_t st = ctx->stream;
-  GCHK(ghip_ensure(ctx, T.idx, (size_t) m * 4));
-  GCHK(ghip_ensure(ctx, T.rows, (size_t) m * WK_NC * 8));
-  k_wk_keys<<<cdiv(m, 256), 256, 0, st>>>(m, P<int>(T.tmp_idx), ctx->n, check_type ? P<int>(ctx->f[GHIP_F_TYPE]) : nullptr,
-                                         W.k0, W.a, W.words);
-  HIPCHK(hipGetLastError());
-  GCHK(ghip_sort_pairs(ctx, W.k0, W.k1, W.a, W.b, m, 32, st));
-  k_wk_gather<<<cdiv((long long) m * WK_NC, 256), 256, 0, st>>>(m, W.b, W.k1, P<double>(T.tmp_rows), P<double>(T.rows),
-                                                               P<int>(T.idx), W.words);
-  HIPCHK(hipGetLastError());
-  return GHIP_OK;
 }
 
 // what every entry point of the section refuses
@@ -1208,16 +1117,6 @@ int ghip_winds_enter(ghip_ctx *ctx, const char *who)
   return GHIP_OK;
 }
 
-static int wk_need_table(ghip_ctx *ctx, const char *who)
-{
-  if(ctx->wk.on && ctx->wk.stale)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: the wind table was given for other counts: give it again after "
-                     "ghip_set_counts (ghip_winds_set_table)", who);
-  if(!ctx->wk.on)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: no wind table (ghip_winds_set_table)", who);
-  return GHIP_OK;
-}
-
 extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows)
 {
   if(ctx)
@@ -1226,7 +1125,7 @@ extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, co
   if(!ctx || nwind < 0 || (nwind > 0 && (!idx || !rows)))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
   GCHK(ghip_winds_enter(ctx, who));
-  WindTable &T = ctx->wk;
+  RowTable &T = ctx->wk;
   hipStream_t st = ctx->stream;
   T.on = false;
   T.n = 0;
@@ -1235,29 +1134,25 @@ extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, co
     if(idx[r] < 0 || idx[r] >= ctx->n)
       return ghip_fail(ctx, GHIP_EINVAL, "%s: wind particle index %d out of range (the context holds no table now)",
                        who, idx[r]);
-  if(nwind > 0)
+  int hw[RTW_WORDS] = {};
+  if(nwind > 0)   // (the indices are in [0, n): the same bits as unsigned keys)
     {
-      WkWork W;
-      GCHK(wk_work(ctx, (size_t) nwind, W));
-      GCHK(ghip_ensure(ctx, T.tmp_idx, (size_t) nwind * 4));
-      GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) nwind * WK_NC * 8));
-      HIPCHK(hipMemcpyAsync(T.tmp_idx.p, idx, (size_t) nwind * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(T.tmp_rows.p, rows, (size_t) nwind * WK_NC * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4, st));
-      GCHK(wk_sort_in(ctx, nwind, W, true));
-      int w[WKW_WORDS];
-      HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
-      HIPCHK(ghip_stream_sync(ctx, st));
-      if(w[WKW_ERR])
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: index %d names a particle that is not Type 3 (the context holds no "
-                         "table now)", who, w[WKW_ERRIDX]);
-      if(w[WKW_DUP])
-        return ghip_fail(ctx, GHIP_EINVAL, "%s: two rows of the wind table have the index %d (the context holds no "
-                         "table now)", who, w[WKW_DUPIDX]);
+      RtWork W;
+      GCHK(ghip_rt_work(ctx, T, (size_t) nwind, 0, W, true));
+      GCHK(ghip_rt_stage_host(ctx, T, nwind, reinterpret_cast<const unsigned int *>(idx), rows));
+      k_wk_check_type<<<cdiv(nwind, 256), 256, 0, st>>>(nwind, P<unsigned int>(T.tmp_key), ctx->n,
+                                                       P<int>(ctx->f[GHIP_F_TYPE]), W.words);
+      HIPCHK(hipGetLastError());
     }
-  T.on = true;
-  T.n = nwind;
-  return GHIP_OK;
+  const int rc = ghip_rt_install(ctx, T, nwind, who, true, hw);
+  if(hw[RTW_ERR])   // (read with the duplicate words, and said first)
+    {
+      T.on = false;
+      T.n = 0;
+      return ghip_fail(ctx, GHIP_EINVAL, "%s: index %d names a particle that is not Type 3 (the context holds no "
+                       "table now)", who, hw[RTW_ERRKEY]);
+    }
+  return rc;
 }
 
 extern "C" int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows)
@@ -1268,18 +1163,8 @@ extern "C" int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double 
   if(!ctx || !nwind)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
   GCHK(ghip_winds_enter(ctx, who));
-  GCHK(wk_need_table(ctx, who));
-  WindTable &T = ctx->wk;
-  *nwind = T.n;
-  if(T.n > 0 && (idx || rows))
-    {
-      if(idx)
-        HIPCHK(hipMemcpyAsync(idx, T.idx.p, (size_t) T.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-      if(rows)
-        HIPCHK(hipMemcpyAsync(rows, T.rows.p, (size_t) T.n * WK_NC * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-    }
-  return GHIP_OK;
+  GCHK(ghip_rt_need(ctx, ctx->wk, who, true));
+  return ghip_rt_get(ctx, ctx->wk, nwind, reinterpret_cast<unsigned int *>(idx), rows);
 }
 
 extern "C" int ghip_winds_clear(ghip_ctx *ctx)
@@ -1288,104 +1173,42 @@ extern "C" int ghip_winds_clear(ghip_ctx *ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
   GCHK(ghip_winds_enter(ctx, "ghip_winds_clear"));
-  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
-  ghip_renew(ctx->wk);
+  GCHK(ghip_rt_clear(ctx, ctx->wk));
+  (void) ctx->wk_spawn.release();
+  (void) ctx->wk_rnd.release();
   return GHIP_OK;
 }
 
 // ---- the table through ghip_rearrange / ghip_peano_order ----
 // keep[r] = the particle of row r survives; its new index is the row's new key
-__global__ void __launch_bounds__(256) k_wk_map(int m, const int *__restrict__ idx, int n_before,
-                                                const int *__restrict__ new_of_old, int *__restrict__ newidx,
+__global__ void __launch_bounds__(256) k_wk_map(int m, const unsigned int *__restrict__ idx, int n_before,
+                                                const int *__restrict__ new_of_old, unsigned int *__restrict__ newidx,
                                                 int *__restrict__ keep)
 {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if(r >= m)
     return;
-  const int i = idx[r];
+  const int i = (int) idx[r];
   const int j = (i >= 0 && i < n_before) ? new_of_old[i] : -1;
-  newidx[r] = j;
+  newidx[r] = (unsigned int) j;
   keep[r] = j >= 0;
 }
 
-// the kept rows, unsorted, into the image: tmp_idx[a] = newidx[sel[a]], tmp_rows[a] = rows[sel[a]]
-__global__ void __launch_bounds__(256) k_wk_compact(int kept, const int *__restrict__ sel,
-                                                    const int *__restrict__ newidx, const double *__restrict__ rows,
-                                                    int *__restrict__ tmp_idx, double *__restrict__ tmp_rows)
+int ghip_winds_remap(ghip_ctx *ctx, const char *who, int n_before, const int *new_of_old)
 {
-  const long long e = (long long) blockIdx.x * 256 + threadIdx.x;
-  if(e >= (long long) kept * WK_NC)
-    return;
-  const int a = (int) (e / WK_NC), c = (int) (e % WK_NC);
-  const int r = sel[a];
-  tmp_rows[e] = rows[(size_t) r * WK_NC + c];
-  if(c == 0)
-    tmp_idx[a] = newidx[r];
-}
-
-int ghip_winds_remap(ghip_ctx *ctx, int n_before, const int *new_of_old)
-{
-  WindTable &T = ctx->wk;
+  RowTable &T = ctx->wk;
   if(!T.on || T.n == 0 || n_before <= 0)
     return GHIP_OK;
-  hipStream_t st = ctx->stream;
   const int m = T.n;
-  WkWork W;
-  GCHK(wk_work(ctx, (size_t) m, W));
-  GCHK(ghip_ensure(ctx, T.tmp_idx, (size_t) m * 4));
-  GCHK(ghip_ensure(ctx, T.tmp_rows, (size_t) m * WK_NC * 8));
-  HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4, st));
-  int *newidx = reinterpret_cast<int *>(W.k0), *sel = reinterpret_cast<int *>(W.k1);
-  k_wk_map<<<cdiv(m, 256), 256, 0, st>>>(m, P<int>(T.idx), n_before, new_of_old, newidx, W.a);
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, (size_t) m, 0, W, true));
+  unsigned int *newidx = reinterpret_cast<unsigned int *>(W.c);
+  k_wk_map<<<cdiv(m, 256), 256, 0, ctx->stream>>>(m, P<unsigned int>(T.key), n_before, new_of_old, newidx, W.a);
   HIPCHK(hipGetLastError());
-  GCHK(ghip_select_flagged(ctx, nullptr, W.a, sel, W.words + WKW_COUNT, m, st));
   int kept = 0;
-  HIPCHK(hipMemcpyAsync(&kept, W.words + WKW_COUNT, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(ghip_stream_sync(ctx, st));
-  if(kept < 0 || kept > m)
-    return ghip_fail(ctx, GHIP_EDEVICE, "%d of %d rows of the wind table kept", kept, m);
-  T.n = kept;
-  if(kept == 0)
-    return GHIP_OK;
-  k_wk_compact<<<cdiv((long long) kept * WK_NC, 256), 256, 0, st>>>(kept, sel, newidx, P<double>(T.rows),
-                                                                   P<int>(T.tmp_idx), P<double>(T.tmp_rows));
-  HIPCHK(hipGetLastError());
-  // (the image is complete before wk_sort_in reuses k0 / k1 as sort keys: one stream)
-  return wk_sort_in(ctx, kept, W, false);
-}
-
-// ---- growth (ghip_wind_spawn, ghip_accretion.hip) ----
-int ghip_winds_reserve(ghip_ctx *ctx, int extra, int **idx_tail, double **rows_tail)
-{
-  WindTable &T = ctx->wk;
-  hipStream_t st = ctx->stream;
-  if(!T.on)
-    {
-      T.on = true;
-      T.n = 0;
-      T.stale = false;
-    }
-  const size_t m = (size_t) T.n + (size_t) (extra > 0 ? extra : 0);
-  if(T.idx.cap < m * 4 || T.rows.cap < m * WK_NC * 8)   // into a larger block, which then becomes the table
-    {
-      GCHK(ghip_ensure(ctx, T.tmp_idx, m * 4));
-      GCHK(ghip_ensure(ctx, T.tmp_rows, m * WK_NC * 8));
-      if(T.n > 0)
-        {
-          HIPCHK(hipMemcpyAsync(T.tmp_idx.p, T.idx.p, (size_t) T.n * 4, hipMemcpyDeviceToDevice, st));
-          HIPCHK(hipMemcpyAsync(T.tmp_rows.p, T.rows.p, (size_t) T.n * WK_NC * 8, hipMemcpyDeviceToDevice, st));
-        }
-      T.idx.swap(T.tmp_idx);
-      T.rows.swap(T.tmp_rows);
-    }
-  *idx_tail = P<int>(T.idx) + T.n;
-  *rows_tail = P<double>(T.rows) + (size_t) T.n * WK_NC;
-  return GHIP_OK;
-}
-
-void ghip_winds_appended(ghip_ctx *ctx, int extra)
-{
-  ctx->wk.n += extra;
+  GCHK(ghip_rt_compact(ctx, T, who, W, W.a, newidx, 0, &kept));
+  // (sorted again without a read: a map sends no two particles to one index)
+  return ghip_rt_install(ctx, T, kept, who, true, nullptr);
 }
 
 // ---- the loop ----
@@ -1393,8 +1216,8 @@ void ghip_winds_appended(ghip_ctx *ctx, int extra)
 // particle without a row raises the error words
 __global__ void __launch_bounds__(256) k_wk_flag_list(int nact, const int *__restrict__ act, int n,
                                                       const int *__restrict__ type, int nrows,
-                                                      const int *__restrict__ idx, const double *__restrict__ rows,
-                                                      double Time, int *__restrict__ flags, int *__restrict__ words)
+                                                      const unsigned int *__restrict__ idx,
+                                                      const double *__restrict__ rows, double Time, int *__restrict__ flags, int *__restrict__ words)
 {
   const int a = blockIdx.x * 256 + threadIdx.x;
   if(a >= nact)
@@ -1403,11 +1226,11 @@ __global__ void __launch_bounds__(256) k_wk_flag_list(int nact, const int *__res
   int f = 0;
   if(i >= 0 && i < n && type[i] == 3)
     {
-      const int r = d_wk_find(nrows, idx, i);
+      const int r = d_rt_find(nrows, idx, (unsigned int) i);
       if(r < 0)
         {
-          words[WKW_ERR] = 1;
-          atomicMax(words + WKW_ERRIDX, i);
+          words[RTW_ERR] = 1;
+          atomicMax(words + RTW_ERRKEY, i);
         }
       else
         f = rows[(size_t) r * WK_NC + GHIP_WK_STELLAR_AGE] < Time;
@@ -1417,13 +1240,13 @@ __global__ void __launch_bounds__(256) k_wk_flag_list(int nact, const int *__res
 
 // the in planes of the list from the rows
 __global__ void __launch_bounds__(256) k_wk_load(int nw, const int *__restrict__ list, int nrows,
-                                                 const int *__restrict__ idx, const double *__restrict__ rows,
-                                                 double *__restrict__ w)
+                                                 const unsigned int *__restrict__ idx,
+                                                 const double *__restrict__ rows, double *__restrict__ w)
 {
   const int a = blockIdx.x * 256 + threadIdx.x;
   if(a >= nw)
     return;
-  const int r = d_wk_find(nrows, idx, list[a]);
+  const int r = d_rt_find(nrows, idx, (unsigned int) list[a]);
   if(r < 0)
     return;   // (never: the selection listed only particles with a row)
   const double *R = rows + (size_t) r * WK_NC;
@@ -1434,13 +1257,13 @@ __global__ void __launch_bounds__(256) k_wk_load(int nw, const int *__restrict__
 // the out planes WP_OLD .. WP_DMOM back into the rows (all == 0: WP_DT1 .. WP_DMOM only, after a call that did not
 // enter the loop), and the code of the elimination
 __global__ void __launch_bounds__(256) k_wk_store(int nw, const int *__restrict__ list, int nrows,
-                                                  const int *__restrict__ idx, double *__restrict__ rows,
+                                                  const unsigned int *__restrict__ idx, double *__restrict__ rows,
                                                   const double *__restrict__ w, const int *__restrict__ deleted, int all)
 {
   const int a = blockIdx.x * 256 + threadIdx.x;
   if(a >= nw)
     return;
-  const int r = d_wk_find(nrows, idx, list[a]);
+  const int r = d_rt_find(nrows, idx, (unsigned int) list[a]);
   if(r < 0)
     return;
   double *R = rows + (size_t) r * WK_NC;
@@ -1482,8 +1305,8 @@ extern "C" int ghip_winds_feedback(ghip_ctx *ctx, const ghip_wind_params *p, ghi
   if(p->max_iter < 1 || !(p->dt_fac >= 0))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: need max_iter >= 1 and dt_fac >= 0", who);
   GCHK(ghip_winds_enter(ctx, who));
-  GCHK(wk_need_table(ctx, who));
-  WindTable &T = ctx->wk;
+  GCHK(ghip_rt_need(ctx, ctx->wk, who, true));
+  RowTable &T = ctx->wk;
   hipStream_t st = ctx->stream;
   for(int k = 0; k < 5; k++)
     ctx->wind_ms[k] = 0;
@@ -1492,20 +1315,20 @@ extern "C" int ghip_winds_feedback(ghip_ctx *ctx, const ghip_wind_params *p, ghi
   const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
   if(nact <= 0)
     return GHIP_OK;
-  WkWork W;
-  GCHK(wk_work(ctx, (size_t) nact, W));
-  HIPCHK(hipMemsetAsync(W.words, 0, WKW_WORDS * 4 + 64, st));
-  k_wk_flag_list<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), T.n, P<int>(T.idx),
-                                                  P<double>(T.rows), p->Time, W.a, W.words);
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, (size_t) nact, 0, W, true));
+  ghip_wind_result *dres = reinterpret_cast<ghip_wind_result *>(W.report);
+  k_wk_flag_list<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), T.n,
+                                                  P<unsigned int>(T.key), P<double>(T.rows), p->Time, W.a, W.words);
   HIPCHK(hipGetLastError());
-  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + WKW_COUNT, nact, st));
-  int w[WKW_WORDS];
+  GCHK(ghip_select_flagged(ctx, dact, W.a, W.b, W.words + RTW_COUNT, nact, st));
+  int w[RTW_WORDS];
   HIPCHK(hipMemcpyAsync(w, W.words, sizeof(w), hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
-  if(w[WKW_ERR])
+  if(w[RTW_ERR])
     return ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-3 particle %d has no row in the wind table (%d rows); "
-                     "nothing was changed", who, w[WKW_ERRIDX], T.n);
-  const int nw = w[WKW_COUNT];
+                     "nothing was changed", who, w[RTW_ERRKEY], T.n);
+  const int nw = w[RTW_COUNT];
   if(nw < 0 || nw > nact || nw > T.n)
     return ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d active particles, %d rows", who, nw, nact, T.n);
   if(nw == 0)
@@ -1514,19 +1337,20 @@ extern "C" int ghip_winds_feedback(ghip_ctx *ctx, const ghip_wind_params *p, ghi
   WindDev d;
   GCHK(wind_begin_list(ctx, nw, W.b, false, &d));
   const size_t D = (size_t) nw;
-  k_wk_load<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<int>(T.idx), P<double>(T.rows), d.w);
+  k_wk_load<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<unsigned int>(T.key), P<double>(T.rows), d.w);
   HIPCHK(hipGetLastError());
   WindEnd end;
   GCHK(wind_loop(ctx, p, d, who, result, &end));
   const bool all = end.stage != WIND_FLOOR;
-  k_wk_store<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<int>(T.idx), P<double>(T.rows), d.w, d.deleted, all);
+  k_wk_store<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<unsigned int>(T.key), P<double>(T.rows), d.w, d.deleted,
+                                            all);
   HIPCHK(hipGetLastError());
   if(all)
     {
-      k_wk_result<<<1, 64, 0, st>>>(nw, d.deleted, d.w + WP_OLD * D, W.result);
+      k_wk_result<<<1, 64, 0, st>>>(nw, d.deleted, d.w + WP_OLD * D, dres);
       HIPCHK(hipGetLastError());
       ghip_wind_result r;
-      HIPCHK(hipMemcpyAsync(&r, W.result, sizeof(r), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&r, dres, sizeof(r), hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
       result->ndeleted = r.ndeleted;
       result->deleted_momentum = r.deleted_momentum;
