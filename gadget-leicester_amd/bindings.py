@@ -231,6 +231,15 @@ class DdWindArgs(C.Structure):
                 ("counts", C.c_void_p)]
 
 
+class DdWindsArgs(C.Structure):
+    """ghip_dd_winds_args (include/ghip.h): GHIP_DD_WIND with walk = WINDS_RESIDENT_FORM, the loop from the
+    shard's wind table (p, result, counts), or WINDS_SPAWN_FORM, the creation of wind particles (spawn, report,
+    tot_spawned)"""
+    _fields_ = [("p", C.POINTER(WindParams)), ("result", C.POINTER(WindResult)), ("counts", C.c_void_p),
+                ("spawn", C.POINTER(WindSpawnParams)), ("report", C.POINTER(WindSpawnReport)),
+                ("tot_spawned", C.POINTER(C.c_longlong))]
+
+
 class IntegrationFlags(C.Structure):
     """ghip_integration_flags: the shipped bundle's rules of get_timestep / do_the_kick /
     drift_particle (include/ghip.h)"""
@@ -492,6 +501,7 @@ EXPORTS = [
     "ghip_wind_params_size", "ghip_wind_density", "ghip_wind_spread", "ghip_wind_feedback",
     "ghip_wind_get_injected", "ghip_wind_set_injected", "ghip_wind_get_rad_accel", "ghip_wind_set_rad_accel",
     "ghip_set_rad_accel", "ghip_wind_get_timing", "ghip_dd_wind_args_size",
+    "ghip_dd_winds_args_size", "ghip_dd_winds_set_table", "ghip_dd_winds_get_table", "ghip_dd_winds_clear",
     "ghip_kick_get_fields", "ghip_rearrange", "ghip_peano_order", "ghip_sequence_get_map", "ghip_sequence_get_info",
     "ghip_sinks_set_table", "ghip_sinks_get_table", "ghip_sinks_clear", "ghip_sinks_density",
     "ghip_blackhole_accretion", "ghip_sfr_form_sinks", "ghip_dd_sinks_args_size"]
@@ -629,6 +639,11 @@ def lib():
         if L.ghip_dd_wind_args_size() != C.sizeof(DdWindArgs):
             raise RuntimeError("DdWindArgs: %d bytes here, %d in libghip.so"
                                % (C.sizeof(DdWindArgs), L.ghip_dd_wind_args_size()))
+        L.ghip_dd_winds_args_size.argtypes = []
+        L.ghip_dd_winds_args_size.restype = C.c_size_t
+        if L.ghip_dd_winds_args_size() != C.sizeof(DdWindsArgs):
+            raise RuntimeError("DdWindsArgs: %d bytes here, %d in libghip.so"
+                               % (C.sizeof(DdWindsArgs), L.ghip_dd_winds_args_size()))
         L.ghip_dd_sinks_args_size.argtypes = []
         L.ghip_dd_sinks_args_size.restype = C.c_size_t
         if L.ghip_dd_sinks_args_size() != C.sizeof(DdSinksArgs):
@@ -651,6 +666,9 @@ def lib():
         L.ghip_winds_set_table.argtypes = [vp, C.c_int, vp, vp]
         L.ghip_winds_get_table.argtypes = [vp, C.POINTER(C.c_int), vp, vp]
         L.ghip_winds_clear.argtypes = [vp]
+        L.ghip_dd_winds_set_table.argtypes = [vp, C.c_int, vp, vp]
+        L.ghip_dd_winds_get_table.argtypes = [vp, C.POINTER(C.c_int), vp, vp]
+        L.ghip_dd_winds_clear.argtypes = [vp]
         L.ghip_winds_feedback.argtypes = [vp, C.POINTER(WindParams), C.POINTER(WindResult)]
         L.ghip_wind_spawn.argtypes = [vp, C.POINTER(WindSpawnParams), C.POINTER(WindSpawnReport)]
         L.ghip_sfr_cooling.argtypes = [vp, C.POINTER(SfrParams), C.POINTER(C.c_int), vp]
@@ -1489,6 +1507,24 @@ class ForcePath:
     def winds_clear(self):
         self._chk(self.L.ghip_winds_clear(self.h))
 
+    def dd_winds_set_table(self, idx, rows):
+        """ghip_dd_winds_set_table: the wind table of this shard (a dd_init context of any rank count); idx are
+        LOCAL particle indices"""
+        idx = np.ascontiguousarray(idx, np.int32)
+        rows = np.ascontiguousarray(rows, np.float64).reshape(len(idx), WK_COUNT)
+        self._chk(self.L.ghip_dd_winds_set_table(self.h, len(idx), _ptr(idx), _ptr(rows)))
+
+    def dd_winds_table(self):
+        """ghip_dd_winds_get_table -> (local idx int32 [nwind] ascending, rows [nwind][WK_COUNT])"""
+        nw = C.c_int(0)
+        self._chk(self.L.ghip_dd_winds_get_table(self.h, C.byref(nw), None, None))
+        idx, rows = np.zeros(nw.value, np.int32), np.zeros((nw.value, WK_COUNT))
+        self._chk(self.L.ghip_dd_winds_get_table(self.h, C.byref(nw), _ptr(idx), _ptr(rows)))
+        return idx, rows
+
+    def dd_winds_clear(self):
+        self._chk(self.L.ghip_dd_winds_clear(self.h))
+
     def winds_feedback(self, params, check=True):
         """ghip_winds_feedback: the propagation loop for the active Type-3 particles with a row and StellarAge <
         Time -> dict(rc, iterations, bits, ndeleted, deleted_momentum); the state is in winds_table().  check =
@@ -1755,6 +1791,8 @@ DD_DECOMPOSE = 13
 DD_PM_REGION, DD_PM_NONPERIODIC = 14, 15
 WIND_OP = DD_DUST_DRAG   # GHIP_DD_WIND: the wind particles on shards share the dust drag's operation code ...
 WIND_FORM, WIND_DENSITY_FORM, WIND_SPREAD_FORM = 16, 17, 18   # ... and are its forms: `walk` of dd_begin / dd_run
+WINDS_RESIDENT_FORM = 32   # GHIP_DD_WIND from the shard's wind table (DdWindsArgs): ghip_winds_feedback as a collective
+WINDS_SPAWN_FORM = 33      # ... ghip_wind_spawn as a collective (the spawn members of DdWindsArgs)
 WIND_COUNTS = ("records_sent", "records_received", "imported_pairs", "exchanges", "bytes_sent", "iterations")
 FOF_FORM = 1             # `walk` of dd_begin / dd_run for DD_GLOBAL_QUANTITIES with DdFofArgs: the FOF groups of all shards
 SYNC_POINT_FORM = 1      # `walk` of dd_begin / dd_run for DD_DECOMPOSE with SyncParams: the sync point of all shards
@@ -1893,6 +1931,41 @@ def dd_wind_args(params, wind, state=None, dt_jump=None, new_density=None, delta
     A.result = C.pointer(a["result"])
     A.counts = a["counts"].ctypes.data
     return A, a
+
+
+def dd_winds_args(params=None, spawn=None, rnd_table=None):
+    """(args, arrays) for GHIP_DD_WIND on one shard, a filled DdWindsArgs and what it points into.  walk =
+    WINDS_RESIDENT_FORM: params (WindParams) -> result: WindResult, counts: int64[6] (WIND_COUNTS); the list and
+    the state are the shard's wind table and active list; dd_wind_result(arrays) reads it when the operation has
+    finished.  walk = WINDS_SPAWN_FORM: spawn (WindSpawnParams) and rnd_table, which must be given (a copy of the
+    params points to a copy of it) -> report: WindSpawnReport, tot_spawned: c_longlong; dd_winds_spawn_report(arrays)."""
+    a = dict(counts=np.zeros(6, np.int64), result=WindResult(), report=WindSpawnReport(),
+             tot_spawned=C.c_longlong(0), _params=params)
+    A = DdWindsArgs()
+    if params is not None:
+        A.p = C.pointer(params)
+    A.result = C.pointer(a["result"])
+    A.counts = a["counts"].ctypes.data
+    if spawn is not None:
+        sp = WindSpawnParams()
+        C.memmove(C.byref(sp), C.byref(spawn), C.sizeof(sp))
+        t = None if rnd_table is None else np.ascontiguousarray(rnd_table, np.float64).copy()
+        sp.rnd_table = None if t is None else t.ctypes.data
+        sp.nrnd = 0 if t is None else len(t)
+        a.update(_spawn=sp, _rnd=t)
+        A.spawn = C.pointer(sp)
+        A.report = C.pointer(a["report"])
+        A.tot_spawned = C.pointer(a["tot_spawned"])
+    return A, a
+
+
+def dd_winds_spawn_report(arrays):
+    """what a finished GHIP_DD_WIND (walk = WINDS_SPAWN_FORM) left in `arrays` of dd_winds_args, as ForcePath.wind_spawn
+    returns it, and tot_spawned, the sum over all shards"""
+    rep = arrays["report"]
+    return dict(spawned=rep.spawned, nsinks_emitting=rep.nsinks_emitting, first_index=rep.first_index,
+                new_wind_exact_sum=rep.new_wind_exact_sum, gsl_draws=rep.gsl_draws,
+                tot_spawned=int(arrays["tot_spawned"].value))
 
 
 def dd_wind_result(arrays):

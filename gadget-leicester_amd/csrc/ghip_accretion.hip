@@ -1452,26 +1452,19 @@ extern "C" size_t ghip_wind_spawn_report_size(void)
   return sizeof(ghip_wind_spawn_report);
 }
 
-extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, ghip_wind_spawn_report *report)
+// One call in three parts, so that the shard form (GHIP_WINDS_SPAWN_FORM, below) can put an exchange between the
+// second and the third: the count and the scan with the one blocking read; what the words refuse; grow and fill.
+struct SpawnRun
 {
-  if(ctx)
-    GHIP_JOIN(ctx);
-  static const char *who = "ghip_wind_spawn";
-  if(!ctx || !p || !report)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  memset(report, 0, sizeof(*report));
-  GCHK(ghip_winds_enter(ctx, who));
-  GCHK(sk_enter(ctx, who, true));
-  GCHK(ghip_rt_need(ctx, ctx->wk, who, false));   // (no wind table yet: the first wind particles open one)
-  if(!(p->rnd_table && p->nrnd > 0) && ctx->rnd_n <= 0)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: no RndTable: neither rnd_table / nrnd nor a table bound with "
-                     "ghip_set_rnd_table", who);
-  if(p->MaxPart < ctx->n)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: MaxPart = %d is below NumPart = %d", who, p->MaxPart, ctx->n);
-  RowTable &T = ctx->sk;
-  hipStream_t st = ctx->stream;
-  const int G = T.n, n = ctx->n;
-  report->first_index = n;
+  SpawnK K;
+  SpawnWords h;
+  int G, n;
+  size_t na, nrow;   // the sizes the selection asked of the sink table's work: the same block later
+  int counted;       // 0: no active particle, nothing was counted and nothing is to do
+};
+
+static SpawnK spawn_k(const ghip_wind_spawn_params *p)
+{
   SpawnK K;
   K.Time = p->Time;
   K.dt_fac = p->dt_fac;
@@ -1494,33 +1487,77 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
   K.isotropic = p->isotropic != 0;
   K.acc_radius = p->accretion_radius != 0;
   K.fly = p->fly_through_empty_space != 0;
+  return K;
+}
 
-  // ---- count, scan, the one blocking read ----
+// ---- count, scan, the one blocking read ----
+static int spawn_scan(ghip_ctx *ctx, const ghip_wind_spawn_params *p, SpawnRun &R)
+{
+  RowTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  memset(&R, 0, sizeof(R));
+  R.K = spawn_k(p);
+  R.G = T.n;
+  R.n = ctx->n;
+  const int G = R.G;
   RtWork W;
   int nact = 0;
   GCHK(sk_select(ctx, G, W, &nact));
-  if(nact <= 0 || n == 0)
+  R.na = (size_t) (nact > 0 ? nact : 1);
+  R.nrow = (size_t) (G > 0 ? G : 1);
+  if(nact <= 0 || R.n == 0)
     return GHIP_OK;
   SpawnDev S;
   GCHK(spawn_dev(ctx, G, S));
   k_spawn_count<<<cdiv(G + 1, 64), 64, 0, st>>>(G, W.words, W.b, W.row, P<double>(ctx->f[GHIP_F_MASS]),
-                                               P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(T.rows), K, S);
+                                               P<int>(ctx->f[GHIP_F_TIMEBIN]), P<double>(T.rows), R.K, S);
   HIPCHK(hipGetLastError());
   GCHK(ghip_scan<unsigned long long>(ctx, S.cnt, S.off, G + 1, st));
   k_spawn_words<<<1, 64, 0, st>>>(G, W.words, S);
   HIPCHK(hipGetLastError());
-  SpawnWords h;
-  HIPCHK(hipMemcpyAsync(&h, S.words, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&R.h, S.words, sizeof(R.h), hipMemcpyDeviceToHost, st));
   HIPCHK(ghip_stream_sync(ctx, st));
+  R.counted = 1;
+  return GHIP_OK;
+}
+
+// what the words refuse; nothing has changed
+static int spawn_verdict(ghip_ctx *ctx, const ghip_wind_spawn_params *p, const char *who, const SpawnRun &R)
+{
+  const SpawnWords &h = R.h;
+  if(!R.counted)
+    return GHIP_OK;
   if(h.missing == 1)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-5 particle with ID %u has no row in the sink table (%d "
-                     "rows, %d active sinks); nothing was changed", who, h.missing_id, T.n, h.nactive);
+                     "rows, %d active sinks); nothing was changed", who, h.missing_id, ctx->sk.n, h.nactive);
   if(h.missing)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: %d active Type-5 particles for %d rows of the sink table: two of them "
-                     "carry the same ID; nothing was changed", who, h.nactive, T.n);
-  if((unsigned long long) n + h.total > (unsigned long long) p->MaxPart)
+                     "carry the same ID; nothing was changed", who, h.nactive, ctx->sk.n);
+  if((unsigned long long) R.n + h.total > (unsigned long long) p->MaxPart)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: NumPart = %d and %llu new wind particles do not fit MaxPart = %d (the "
-                     "reference's endrun(8888)); nothing was changed", who, n, h.total, p->MaxPart);
+                     "reference's endrun(8888)); nothing was changed", who, R.n, h.total, p->MaxPart);
+  return GHIP_OK;
+}
+
+// :89, then grow and fill
+static int spawn_grow(ghip_ctx *ctx, const ghip_wind_spawn_params *p, const SpawnRun &R,
+                      ghip_wind_spawn_report *report)
+{
+  if(!R.counted)
+    return GHIP_OK;
+  RowTable &T = ctx->sk;
+  hipStream_t st = ctx->stream;
+  const SpawnK &K = R.K;
+  const SpawnWords &h = R.h;
+  const int G = R.G, n = R.n;
+  // The selection of spawn_scan again: the same sizes give the same block of ctx->sk.work, not cleared.  On shards an
+  // exchange lies between the two parts; the invariant is that NOTHING uses the sink table's work block between
+  // phase 0 and phase 1 of ghip_dd_spawn_step -- the all-gather of the status record touches status_own / status_all
+  // only, and no other entry point may run on the context while the operation is in progress (ghip_dd_begin).
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, R.na, R.nrow, W, false));
+  SpawnDev S;
+  GCHK(spawn_dev(ctx, G, S));
   const int total = (int) h.total, nn = n + total;
   report->spawned = total;
   report->nsinks_emitting = h.emitting;
@@ -1577,4 +1614,136 @@ extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, g
       ctx->nactive = old_nact + total;
     }
   return GHIP_OK;
+}
+
+extern "C" int ghip_wind_spawn(ghip_ctx *ctx, const ghip_wind_spawn_params *p, ghip_wind_spawn_report *report)
+{
+  if(ctx)
+    GHIP_JOIN(ctx);
+  static const char *who = "ghip_wind_spawn";
+  if(!ctx || !p || !report)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
+  memset(report, 0, sizeof(*report));
+  if(ctx->dd.on && ctx->dd.nranks > 1 && ctx->shard_n <= 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the shard form is not built into this entry point: on a multi-GPU context "
+                     "(ghip_dd_init with %d ranks) wind particles are created by GHIP_DD_WIND with walk = "
+                     "GHIP_WINDS_SPAWN_FORM (ghip_dd_winds_args)", who, ctx->dd.nranks);
+  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(sk_enter(ctx, who, true));
+  GCHK(ghip_rt_need(ctx, ctx->wk, who, false));   // (no wind table yet: the first wind particles open one)
+  if(!(p->rnd_table && p->nrnd > 0) && ctx->rnd_n <= 0)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: no RndTable: neither rnd_table / nrnd nor a table bound with "
+                     "ghip_set_rnd_table", who);
+  if(p->MaxPart < ctx->n)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: MaxPart = %d is below NumPart = %d", who, p->MaxPart, ctx->n);
+  report->first_index = ctx->n;
+  SpawnRun R;
+  GCHK(spawn_scan(ctx, p, R));
+  GCHK(spawn_verdict(ctx, p, who, R));
+  return spawn_grow(ctx, p, R, report);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ghip_wind_spawn on shards: GHIP_DD_WIND begun with walk = GHIP_WINDS_SPAWN_FORM (ghip_dd_wind_begin / _step hand
+// over).  The reference's creation is local per task (momentum_feedback.c:70-246): the new particle is P[NumPart +
+// stars_spawned] of the TASK, its ID the sink's plus that local index, only tot_spawned is all-reduced (:240), and
+// endrun(8888) on any task ends all.  So every shard runs the three parts of ghip_wind_spawn on its own sinks, with
+// one all-gather of {spawned, sinks emitting, new_wind_exact sum, failed} between the verdict and the growth: a
+// shard that cannot go on (no sink or wind table, no RndTable in the params, an active Type-5 particle without a
+// row, NumPart + total > MaxPart) holds its message, every shard takes the exchange, and then all return GHIP_EINVAL
+// naming the shard, no byte changed anywhere.  Otherwise each shard grows and fills locally; a shard that spawns
+// nothing changes nothing.
+// ---------------------------------------------------------------------------------------------
+int ghip_dd_spawn_begin(ghip_ctx *ctx, const void *params)
+{
+  static const char *who = "ghip_dd wind spawn";
+  const ghip_dd_winds_args &a = *reinterpret_cast<const ghip_dd_winds_args *>(params);
+  if(!a.spawn || !a.report || !a.tot_spawned)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments (spawn, report and tot_spawned of ghip_dd_winds_args)", who);
+  if(ctx->shard_n > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard)", who);
+  WindDD &W = ctx->dd.wind;
+  W = WindDD();
+  W.form = GHIP_WINDS_SPAWN_FORM;
+  W.spawn_args = a;
+  W.spawn_p = *a.spawn;
+  memset(a.report, 0, sizeof(*a.report));
+  *a.tot_spawned = 0;
+  return GHIP_OK;
+}
+
+int ghip_dd_spawn_step(ghip_ctx *ctx)
+{
+  static const char *who = "ghip_dd wind spawn";
+  static_assert(sizeof(SpawnRun) <= sizeof(WindDD::spawn_run), "WindDD::spawn_run holds a SpawnRun");
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  hipStream_t st = ctx->stream;
+  const ghip_wind_spawn_params *p = &W.spawn_p;
+  SpawnRun R;
+  if(D.phase == 0)
+    {
+      GHIP_JOIN(ctx);
+      memset(&R, 0, sizeof(R));
+      // (what fails here is held, not returned: every shard takes the exchange)
+      int rc = ghip_winds_enter(ctx, who, true);
+      if(rc == GHIP_OK)
+        rc = sk_enter(ctx, who, true);
+      if(rc == GHIP_OK)
+        rc = ghip_rt_need(ctx, ctx->wk, who, true);
+      if(rc == GHIP_OK && !(p->rnd_table && p->nrnd > 0))
+        rc = ghip_fail(ctx, GHIP_EINVAL, "%s: no RndTable: rnd_table / nrnd must come in the params (ghip_dd_begin "
+                       "refuses a table bound with ghip_set_rnd_table)", who);
+      if(rc == GHIP_OK && p->MaxPart < ctx->n)
+        rc = ghip_fail(ctx, GHIP_EINVAL, "%s: MaxPart = %d is below NumPart = %d", who, p->MaxPart, ctx->n);
+      if(rc == GHIP_OK)
+        rc = spawn_scan(ctx, p, R);
+      if(rc == GHIP_OK)
+        rc = spawn_verdict(ctx, p, who, R);
+      if(rc != GHIP_OK)
+        {
+          const std::string why = ctx->err;
+          rc = ghip_fail(ctx, GHIP_EINVAL, "%s (rank %d of %d); no shard has changed anything", why.c_str(), D.rank,
+                         D.nranks);
+          R.counted = 0;
+        }
+      const bool failed = ghip_dd_hold(ctx, rc);
+      memcpy(W.spawn_run, &R, sizeof(R));
+      const double mine[4] = {failed ? 0.0 : (double) R.h.total, failed ? 0.0 : (double) R.h.emitting,
+                              failed ? 0.0 : R.h.exact_sum, failed ? 1.0 : 0.0};
+      GCHK(ghip_ensure(ctx, D.status_own, 32));
+      HIPCHK(hipMemcpyAsync(D.status_own.p, mine, 32, hipMemcpyHostToDevice, st));
+      HIPCHK(ghip_stream_sync(ctx, st));   // (`mine` lives on this frame)
+      ghip_dd_set_allgather(D, D.status_own.p, 32, &D.status_all);
+      D.phase = 1;
+      return 1;
+    }
+  if(D.phase == 1)
+    {
+      memcpy(&R, W.spawn_run, sizeof(R));
+      double all[4 * GHIP_MAXRANKS];
+      HIPCHK(hipMemcpyAsync(all, D.status_all.p, (size_t) D.nranks * 32, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      int first_failed = -1;
+      long long tot = 0;
+      for(int r = 0; r < D.nranks; r++)
+        {
+          if(all[4 * r + 3] != 0 && first_failed < 0)
+            first_failed = r;
+          tot += (long long) all[4 * r];
+        }
+      if(first_failed >= 0)   // (GHIP_EINVAL on every shard: what a shard holds back here is an argument error)
+        {
+          if(D.held.rc != GHIP_OK)
+            return ghip_fail(ctx, D.held.rc, "%s", D.held.msg.c_str());
+          return ghip_fail(ctx, GHIP_EINVAL, "%s: shard %d cannot create its wind particles (its own message says "
+                           "why); every shard stops here, no shard has changed anything", who, first_failed);
+        }
+      *W.spawn_args.tot_spawned = tot;
+      W.spawn_args.report->first_index = R.n;
+      GCHK(spawn_grow(ctx, p, R, W.spawn_args.report));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      return 0;
+    }
+  return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd_step: the wind spawn has no phase %d", D.phase);
 }

@@ -1316,16 +1316,39 @@ int ghip_dd_wind_groups(ghip_ctx *ctx, const double extra[3], int own_rc)
   status.cz = extra[0];
   status.ex = extra[1];
   status.ey = extra[2];
+  // (the resident form: the code too, so that the other shards return what the failing one does)
+  status.ez = D.held.rc != GHIP_OK && D.wind.resident ? (double) D.held.rc : 0.0;
   HIPCHK(hipMemcpyAsync(P<DDGroup>(D.grp_own) + DD_TABLE, &status, sizeof(status), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ghip_stream_sync(ctx, ctx->stream));   // (`status` lives on this frame)
   return 1;
+}
+
+// the code the first failed shard published with its status record (the resident form does), GHIP_OK: none
+static int wind_failed_code(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  DDGroup rec[GHIP_MAXRANKS];
+  HIPCHK(hipMemcpy2DAsync(rec, sizeof(DDGroup), P<DDGroup>(D.grp_all) + DD_TABLE, (size_t) DD_STRIDE * sizeof(DDGroup),
+                          sizeof(DDGroup), (size_t) D.nranks, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ghip_stream_sync(ctx, ctx->stream));
+  for(int r = 0; r < D.nranks; r++)
+    if(rec[r].cx != 0)
+      return (int) rec[r].ez;
+  return GHIP_OK;
 }
 
 // after that all-gather: every shard stops here if one has failed; else extra[r][3] of every shard, in rank order
 int ghip_dd_wind_status(ghip_ctx *ctx, const char *what, double *extra)
 {
   DDState &D = ctx->dd;
-  GCHK(check_group_status(ctx, what));
+  const int rc = check_group_status(ctx, what);
+  if(rc != GHIP_OK && D.held.rc == GHIP_OK)   // another shard failed: its code if it said it, under the same message
+    {
+      const std::string msg = ctx->err;
+      const int code = wind_failed_code(ctx);
+      return code < 0 ? ghip_fail(ctx, code, "%s", msg.c_str()) : rc;
+    }
+  GCHK(rc);
   DDGroup rec[GHIP_MAXRANKS];
   HIPCHK(hipMemcpy2DAsync(rec, sizeof(DDGroup), P<DDGroup>(D.grp_all) + DD_TABLE, (size_t) DD_STRIDE * sizeof(DDGroup),
                           sizeof(DDGroup), (size_t) D.nranks, hipMemcpyDeviceToHost, ctx->stream));
@@ -1945,9 +1968,11 @@ __global__ void k_mig_flags_old(int n, int ngas, const unsigned long long *__res
     v[i] = mask[i] ? 0ULL : (i < ngas ? 1ULL : (1ULL << 32));
 }
 
-// (a header record -- slot MIG_SLOTS-1 = MIG_HEADER, "the sender holds a sink table" -- is no particle: counted in
-// *headers, ranked nowhere)
+// (a header record -- slot MIG_SLOTS-1 = MIG_HEADER, slot 0 = which tables the sender holds: MIG_HAS_SINKS |
+// MIG_HAS_WINDS -- is no particle: counted in headers[0], and per kind in headers[1] and [2], ranked nowhere)
 #define MIG_HEADER 2ULL
+#define MIG_HAS_SINKS 1ULL
+#define MIG_HAS_WINDS 2ULL
 __global__ void k_mig_flags_new(int nrecv, const MigRec *__restrict__ rec,
                                 unsigned long long *__restrict__ v, unsigned long long *__restrict__ headers)
 {
@@ -1959,6 +1984,10 @@ __global__ void k_mig_flags_new(int nrecv, const MigRec *__restrict__ rec,
     {
       v[j] = 0;
       atomicAdd(headers, 1ULL);
+      if(rec[j].s[0] & MIG_HAS_SINKS)
+        atomicAdd(headers + 1, 1ULL);
+      if(rec[j].s[0] & MIG_HAS_WINDS)
+        atomicAdd(headers + 2, 1ULL);
     }
   else
     v[j] = kind ? 1ULL : (1ULL << 32);
@@ -1968,11 +1997,11 @@ struct MigHeaders
 {
   int pos[GHIP_MAXRANKS];   // where the header of each destination goes, -1: none
 };
-__global__ void k_mig_headers(int nranks, MigHeaders H, MigRec *__restrict__ out)
+__global__ void k_mig_headers(int nranks, MigHeaders H, unsigned long long tables, MigRec *__restrict__ out)
 {
   const int r = blockIdx.x, k = threadIdx.x;
   if(r < nranks && H.pos[r] >= 0 && k < MIG_SLOTS)
-    out[H.pos[r]].s[k] = k == MIG_SLOTS - 1 ? MIG_HEADER : 0ULL;
+    out[H.pos[r]].s[k] = k == MIG_SLOTS - 1 ? MIG_HEADER : (k == 0 ? tables : 0ULL);
 }
 
 struct MigCounts
@@ -2041,10 +2070,14 @@ __global__ void k_mig_move_new(int nrecv, const MigRec *__restrict__ rec,
 // GHIP_DD_MIGRATE:
 //   SEND   the owner of every local particle's key; those of other shards packed   -> all-to-all-v of MigRec
 //   MERGE  kept and received particles into the new layout (gas first), the resident arrays swapped
-// and, when the shards hold sink tables (ghip_accretion.hip; a header record in the first exchange says who does):
+// and, when the shards hold wind tables (ghip_wind.hip; a header record in the first exchange says who holds what):
+//   WROWS        the rows of the Type-3 particles that left, by their place in the run   -> all-to-all-v of row records
+//                then: the staying rows re-keyed to the new layout, the arrivals keyed by theirs, sorted again
+// and, when the shards hold sink tables (ghip_accretion.hip):
 //   ROWS         the rows of the Type-5 particles that left                          -> all-to-all-v of row records
 //   ROWS_STATUS  departed rows dropped, arrivals merged, the table sorted again      -> all-gather of the status
 //                an ID that stands twice in one table stops all shards
+// Exchanges: 1 without tables, 2 with wind tables, 3 with sink tables, 4 with both.
 static int migrate_begin(ghip_ctx *ctx, int, const void *, int)
 {
   static_assert(sizeof(MigRec) == MIG_SLOTS * 8, "MigRec layout");
@@ -2077,7 +2110,15 @@ static int migrate_step(ghip_ctx *ctx)
   DevBuf *const wind[2] = {(ctx->wind_inj.p && ctx->wind_inj_ngas == ng) ? &ctx->wind_inj : nullptr,
                            (ctx->wind_ra.p && ctx->wind_ra_ngas == ng) ? &ctx->wind_ra : nullptr};
   DevBuf *const wind_shadow[2] = {wind[0] ? &D.wind_shadow[0] : nullptr, wind[1] ? &D.wind_shadow[1] : nullptr};
-  enum { SEND, MERGE, DONE, ROWS, ROWS_STATUS };
+  enum { SEND, MERGE, DONE, ROWS, ROWS_STATUS, WROWS };
+  // after the particles (and the wind rows): the sink rows' exchange, or the end
+  auto sink_rows_or_done = [&]() {
+    if(!D.mig_tab)
+      return (int) GHIP_OK;
+    ghip_sinks_mig_post(ctx);   // the rows of the Type-5 particles that left   -> all-to-all-v of row records
+    D.phase = ROWS;
+    return 1;
+  };
   if(D.phase == SEND)
     {
       GHIP_JOIN(ctx);
@@ -2105,11 +2146,18 @@ static int migrate_step(ghip_ctx *ctx)
       // A shard that holds a sink table (ghip_accretion.hip) says so to every other shard with one header record in
       // front of that shard's particles, and the rows of its departing Type-5 particles follow in a second exchange:
       // every shard then sees who holds a table, and all of them enter the second exchange or none does.
+      // The same for the wind table (ghip_wind.hip), independently: its rows are keyed by particle index, so they are
+      // packed by their particle's place in the run of its destination, before anything moves.
       D.mig_tab = ctx->sk.on && !ctx->sk.stale && P_ > 1;
-      GCHK(ghip_ensure(ctx, D.mig_send, (size_t) (D.mig_tab ? total + P_ : (total > 0 ? total : 1)) * sizeof(MigRec)));
+      D.mig_wk = ctx->wk.on && !ctx->wk.stale && P_ > 1;
+      const bool headers = D.mig_tab || D.mig_wk;
+      GCHK(ghip_ensure(ctx, D.mig_send, (size_t) (headers ? total + P_ : (total > 0 ? total : 1)) * sizeof(MigRec)));
+      if(D.mig_wk)
+        GCHK(ghip_winds_mig_pack(ctx, total, P<int>(D.mig_list), scount, soff));
       if(D.mig_tab)
+        GCHK(ghip_sinks_mig_pack(ctx, total, P<int>(D.mig_list), P<unsigned long long>(D.mig_mask)));
+      if(headers)
         {
-          GCHK(ghip_sinks_mig_pack(ctx, total, P<int>(D.mig_list), P<unsigned long long>(D.mig_mask)));
           const MigTable T = mig_table(ctx->f, heat, visc, wind);
           MigHeaders H;
           int shift = 0;
@@ -2128,7 +2176,8 @@ static int migrate_step(ghip_ctx *ctx)
               scount[r]++;
               shift++;
             }
-          k_mig_headers<<<P_, 64, 0, st>>>(P_, H, P<MigRec>(D.mig_send));
+          k_mig_headers<<<P_, 64, 0, st>>>(P_, H, (D.mig_tab ? MIG_HAS_SINKS : 0ULL) | (D.mig_wk ? MIG_HAS_WINDS : 0ULL),
+                                           P<MigRec>(D.mig_send));
           HIPCHK(hipGetLastError());
         }
       else if(total > 0)
@@ -2147,18 +2196,20 @@ static int migrate_step(ghip_ctx *ctx)
       const int nrecv = D.x.rtotal;
       D.mig_in = nrecv;
       D.phase = DONE;
-      if(nrecv == 0 && D.mig_out == 0 && !D.mig_tab)
+      D.wk_plan.moved = false;
+      if(nrecv == 0 && D.mig_out == 0 && !D.mig_tab && !D.mig_wk)
         {
           ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
           return GHIP_OK;    // nobody left, nobody came: the resident arrays stay as they are
         }
       // new positions: kept gas, received gas, kept others, received others
-      GCHK(ghip_ensure(ctx, D.mig_scan, (size_t) (n + nrecv + 2) * 16 + 8));
+      GCHK(ghip_ensure(ctx, D.mig_scan, (size_t) (n + nrecv + 2) * 16 + 24));
       unsigned long long *vo = P<unsigned long long>(D.mig_scan), *ro = vo + (n + 1),
                          *vn = ro + (n + 1), *rn = vn + (nrecv + 1), *hw = rn + (nrecv + 1);
       // (layout: flags_old[n+1], rank_old[n+1], flags_new[nrecv+1], rank_new[nrecv+1]; the extra
-      // zero entry makes the last rank the total; then the count of header records)
-      HIPCHK(hipMemsetAsync(vo, 0, (size_t) (n + nrecv + 2) * 16 + 8, st));
+      // zero entry makes the last rank the total; then the count of header records, of those that say "sink table" and
+      // of those that say "wind table")
+      HIPCHK(hipMemsetAsync(vo, 0, (size_t) (n + nrecv + 2) * 16 + 24, st));
       if(n > 0)
         k_mig_flags_old<<<cdiv(n, 256), 256, 0, st>>>(n, ng, P<unsigned long long>(D.mig_mask), vo);
       if(nrecv > 0)
@@ -2166,25 +2217,38 @@ static int migrate_step(ghip_ctx *ctx)
       HIPCHK(hipGetLastError());
       GCHK(ghip_scan(ctx, vo, ro, n + 1, ctx->stream));
       GCHK(ghip_scan(ctx, vn, rn, nrecv + 1, ctx->stream));
-      unsigned long long tot[3];
+      unsigned long long tot[5];
       HIPCHK(hipMemcpyAsync(&tot[0], ro + n, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipMemcpyAsync(&tot[1], rn + nrecv, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(&tot[2], hw, 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(&tot[2], hw, 24, hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
-      // every other shard's header, or none: all shards see the same picture and stop together, before anything moved
-      const int nhdr = (int) tot[2];
-      if(nhdr != (D.mig_tab ? P_ - 1 : 0))
+      // every other shard's header says the same, per kind of table, or no shard holds that kind: all shards see the
+      // same picture and stop together, before anything moved
+      const int nhdr = (int) tot[2], nsk = (int) tot[3], nwk = (int) tot[4];
+      if(nsk != (D.mig_tab ? P_ - 1 : 0))
         return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_MIGRATE: %d of the %d other shards hold a sink table and this one "
                          "holds %s: either all shards hold one (an empty one counts) or none does "
                          "(ghip_sinks_set_table / ghip_sinks_clear); every shard stops here, nothing was moved",
-                         nhdr, P_ - 1, D.mig_tab ? "one" : "none");
+                         nsk, P_ - 1, D.mig_tab ? "one" : "none");
+      if(nwk != (D.mig_wk ? P_ - 1 : 0))
+        return ghip_fail(ctx, GHIP_EINVAL, "GHIP_DD_MIGRATE: %d of the %d other shards hold a wind table and this one "
+                         "holds %s: either all shards hold one (an empty one counts) or none does "
+                         "(ghip_dd_winds_set_table / ghip_dd_winds_clear); every shard stops here, nothing was moved",
+                         nwk, P_ - 1, D.mig_wk ? "one" : "none");
+      if(nhdr != (D.mig_tab || D.mig_wk ? P_ - 1 : 0))
+        return ghip_fail(ctx, GHIP_ECOMM, "GHIP_DD_MIGRATE: %d header records from %d other shards", nhdr, P_ - 1);
       D.mig_in = nrecv - nhdr;
       ctx->pot_n = -1;   // (the result of GHIP_DD_POTENTIAL belongs to the particle set before the migration)
       if(D.mig_in == 0 && D.mig_out == 0)
         {
-          ghip_sinks_mig_post(ctx);   // (only shards with tables come here: the rows' exchange is a collective)
-          D.phase = ROWS;
-          return 1;
+          // (only shards with tables come here: the rows' exchanges are collectives)
+          if(D.mig_wk)
+            {
+              ghip_winds_mig_post(ctx);
+              D.phase = WROWS;
+              return 1;
+            }
+          return sink_rows_or_done();
         }
       // (a wind field held for another gas count is not carried: it is dropped with the layout it belonged to)
       if(!wind[0])
@@ -2254,11 +2318,43 @@ static int migrate_step(ghip_ctx *ctx)
       ctx->nactive = -1;
       ctx->lists_dirty = ctx->gas_list_dirty = true;
       ctx->gas_types_unknown = true;   // (an arrival may be a converted particle of its old gas block)
-      if(!D.mig_tab)
-        return GHIP_OK;
-      ghip_sinks_mig_post(ctx);   // the rows of the Type-5 particles that left   -> all-to-all-v of row records
-      D.phase = ROWS;
-      return 1;
+      // (SwallowID is per particle and does not travel: no mark of the old layout may be read as one of the new)
+      if(ctx->bh_swallow.p)
+        HIPCHK(hipMemsetAsync(ctx->bh_swallow.p, 0, ctx->bh_swallow.cap, st));
+      // the wind table is keyed by particle index: what MERGE knows of the renumbering stays for its rows (the
+      // table counts as stale until they are merged; one that was stale before is not carried)
+      if(ctx->wk.on)
+        ctx->wk.stale = true;
+      if(D.mig_wk)
+        {
+          WkMigPlan &M = D.wk_plan;
+          M.moved = true;
+          M.n_old = n;
+          M.ng_old = ng;
+          M.nrecv = nrecv;
+          M.ngn = ngn;
+          M.ko = C.ko;
+          M.mask = P<unsigned long long>(D.mig_mask);
+          M.ro = ro;
+          M.vn = vn;
+          M.rn = rn;
+          for(int r = 0; r < GHIP_MAXRANKS; r++)   // (every other shard sent a header in front of its particles)
+            {
+              const bool other = r < P_ && r != D.rank;
+              M.first[r] = other ? D.x.roff[r] + 1 : 0;
+              M.cnt[r] = other ? D.x.rcount[r] - 1 : 0;
+            }
+          ghip_winds_mig_post(ctx);   // the rows of the Type-3 particles that left   -> all-to-all-v of row records
+          D.phase = WROWS;
+          return 1;
+        }
+      return sink_rows_or_done();
+    }
+  if(D.phase == WROWS)
+    {
+      GCHK(ghip_winds_mig_merge(ctx));
+      D.phase = DONE;
+      return sink_rows_or_done();
     }
   if(D.phase == ROWS)
     {

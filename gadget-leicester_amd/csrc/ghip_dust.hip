@@ -1034,7 +1034,7 @@ int ghip_dd_dust_begin(ghip_ctx *ctx, int op, const void *params, int walk)
   GHIP_JOIN(ctx);
   ctx->dd.walk = walk;
   // the wind particles share this operation's code and requirements (ghip_wind.hip): their forms hand over
-  if(op == GHIP_DD_WIND && walk >= GHIP_WIND_FORM && walk <= GHIP_WIND_SPREAD_FORM)
+  if(op == GHIP_DD_WIND && ((walk >= GHIP_WIND_FORM && walk <= GHIP_WIND_SPREAD_FORM) || walk == GHIP_WINDS_RESIDENT_FORM || walk == GHIP_WINDS_SPAWN_FORM))
     return ghip_dd_wind_begin(ctx, op, params, walk);
   const bool grains = walk == GHIP_DUST_GRAINS_FORM;
   const bool drag = op == GHIP_DD_DUST_DRAG;

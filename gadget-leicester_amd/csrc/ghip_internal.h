@@ -220,6 +220,18 @@ struct DustCall
   const char *who = "", *other = "";   // the entry in messages; the form that dust_model_ready points to
 };
 
+// The renumbering of a migration as the wind rows need it (ghip_dd.hip, migrate_step, fills it in MERGE; mig_scan and
+// mig_mask hold the arrays until the next migration): the new layout is kept gas, received gas, kept others, received
+// others.  A kept particle i that is not gas goes to ngn + (ro[i] >> 32); the particle at receive position q, not gas
+// (vn[q] == 1 << 32), to ngn + ko + (rn[q] >> 32).
+struct WkMigPlan
+{
+  bool moved = false;             // the layout changed (else: nobody left or came, every key stands)
+  int n_old = 0, ng_old = 0, nrecv = 0, ngn = 0, ko = 0;
+  const unsigned long long *mask = nullptr, *ro = nullptr, *vn = nullptr, *rn = nullptr;
+  int first[GHIP_MAXRANKS], cnt[GHIP_MAXRANKS];   // per sender: receive position of its first particle, its particles
+};
+
 #define DD_NOPS (GHIP_DD_PM_NONPERIODIC + 1)   // operations of ghip_dd_begin, 0 = none (dd_ops[] in ghip_dd.hip)
 
 // GHIP_DD_WIND in progress (ghip_wind.hip): copies of the arguments, the form, and where the loop stands
@@ -228,6 +240,11 @@ struct WindDD
   ghip_dd_wind_args a = {};
   ghip_wind_params p = {};
   int form = 0;            // GHIP_WIND_FORM, _DENSITY_FORM or _SPREAD_FORM
+  bool resident = false;   // GHIP_WINDS_RESIDENT_FORM: form = GHIP_WIND_FORM, the list and the planes from the wind table
+  // GHIP_WINDS_SPAWN_FORM (ghip_accretion.hip): the arguments, a copy of the params, and what the count found (a SpawnRun)
+  ghip_dd_winds_args spawn_args = {};
+  ghip_wind_spawn_params spawn_p = {};
+  alignas(8) char spawn_run[256] = {};
   int iter = 0;            // global iterations begun (0: the density at the start)
   int m = 0, under = 0;    // this shard's list; its particles above 1e-40
   int m_next = 0, under_next = 0;
@@ -326,6 +343,12 @@ struct DDState
   DevBuf sk_keep, sk_rcnt;        // i32[rows]: 0 = the row departs; i32: rows per destination, pack cursors
   DevBuf sk_rsend, sk_rrecv;      // (ID, GHIP_SK_COUNT doubles) records out / in
   int sk_rscount[GHIP_MAXRANKS], sk_rsoff[GHIP_MAXRANKS];
+  // the rows of the wind table in GHIP_DD_MIGRATE (ghip_wind.hip): keyed by particle index, so they are re-keyed
+  bool mig_wk = false;            // this shard holds a wind table: the header says so, the rows follow
+  DevBuf wk_flag;                 // i32: departing particle has a row [total + 1] | its scan [total + 1] | rows per run
+  DevBuf wk_rsend, wk_rrecv;      // (ordinal in the sender's run, GHIP_WK_COUNT doubles) records out / in
+  int wk_rscount[GHIP_MAXRANKS], wk_rsoff[GHIP_MAXRANKS];
+  WkMigPlan wk_plan;              // what MERGE knew of the renumbering, kept for the rows
   // the dust passes on shards (ghip_dust.hip): this shard's grains go to the shards their spheres reach,
   // partial d7 come back (density), drag records are scattered into every shard's own gas (drag)
   DustCall dust;                  // the operation in progress
@@ -829,7 +852,13 @@ int ghip_sinks_drop_eliminated(ghip_ctx *ctx, int n_before, const int *new_of_ol
 // ghip_wind.hip: the wind table through a reordering (every index through new_of_old, the rows of eliminated
 // particles dropped, ascending order restored); what every entry point of the resident wind section refuses
 int ghip_winds_remap(ghip_ctx *ctx, const char *who, int n_before, const int *new_of_old);
-int ghip_winds_enter(ghip_ctx *ctx, const char *who);
+int ghip_winds_enter(ghip_ctx *ctx, const char *who, bool dd = false);
+// the wind rows in GHIP_DD_MIGRATE: before anything moves, the rows of the departing Type-3 particles (list: the runs
+// of the destinations, scount / soff as multi_select left them); the exchange left pending; after it the table
+// re-keyed to the new layout and merged with the arrivals
+int ghip_winds_mig_pack(ghip_ctx *ctx, int total, const int *list, const int *scount, const int *soff);
+void ghip_winds_mig_post(ghip_ctx *ctx);
+int ghip_winds_mig_merge(ghip_ctx *ctx);
 // ghip_sequence.hip, for ghip_wind_spawn: the state grows from n to nn particles.  _begin gives the map to fill,
 // old_of_new [nn] on the device (the source record of every record of the new layout); _apply moves every plane
 // along it and leaves the state as after ghip_rearrange, the maps of ghip_sequence_get_map included
@@ -1001,6 +1030,8 @@ int ghip_dd_sync_begin(ghip_ctx *ctx, int op, const void *params, int walk);    
 int ghip_dd_sync_step(ghip_ctx *ctx);
 int ghip_dd_wind_begin(ghip_ctx *ctx, int op, const void *params, int walk);     // wind.hip: the wind forms of GHIP_DD_DUST_DRAG
 int ghip_dd_wind_step(ghip_ctx *ctx);
+int ghip_dd_spawn_begin(ghip_ctx *ctx, const void *params);                      // accretion.hip: GHIP_WINDS_SPAWN_FORM
+int ghip_dd_spawn_step(ghip_ctx *ctx);
 // all shards stop together: hold keeps rc (with ctx->err if it is a failure) and says whether it failed, the flag
 // travels with the next exchange; raise(r = first rank whose flag is set, < 0: none, GHIP_OK) then fails with this
 // shard's own code and message if it holds one, else with the formatted message and GHIP_EDEVICE

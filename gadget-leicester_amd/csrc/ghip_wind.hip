@@ -1104,27 +1104,35 @@ __global__ void __launch_bounds__(256) k_wk_check_type(int m, const unsigned int
     }
 }
 
-// what every entry point of the section refuses
-int ghip_winds_enter(ghip_ctx *ctx, const char *who)
+// what every entry point of the section refuses.  dd == false: the single-rank family (a plain context or a
+// ghip_dd_init context of one rank); dd == true: the shard family ghip_dd_winds_* and the wind forms of GHIP_DD_WIND
+// that read the table (a ghip_dd_init context of any rank count)
+int ghip_winds_enter(ghip_ctx *ctx, const char *who, bool dd)
 {
   if(ctx->shard_n > 1)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: not available on a sharded context (ghip_set_shard): the resident wind "
-                     "particles are single-rank only", who);
-  if(ctx->dd.on && ctx->dd.nranks > 1)
-    return ghip_fail(ctx, GHIP_EINVAL, "%s: the shard form is not built: on a multi-GPU context (ghip_dd_init with %d "
-                     "ranks) the wind particles run GHIP_DD_WIND with host arrays", who, ctx->dd.nranks);
+                     "particles are %s", who, dd ? "for ghip_dd_init contexts" : "single-rank only");
+  if(dd && !ctx->dd.on)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: not a multi-GPU context (ghip_dd_init): on a plain context the wind table "
+                     "is ghip_winds_set_table / ghip_winds_get_table / ghip_winds_clear and the loop ghip_winds_feedback",
+                     who);
+  if(!dd && ctx->dd.on && ctx->dd.nranks > 1)
+    return ghip_fail(ctx, GHIP_EINVAL, "%s: the shard form is not built into this entry point: on a multi-GPU context "
+                     "(ghip_dd_init with %d ranks) the table is ghip_dd_winds_set_table / ghip_dd_winds_get_table / "
+                     "ghip_dd_winds_clear and the loop GHIP_DD_WIND with walk = GHIP_WINDS_RESIDENT_FORM", who,
+                     ctx->dd.nranks);
   HIPCHK(hipSetDevice(ctx->device));
   return GHIP_OK;
 }
 
-extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows)
+// the bodies of the two families (dd: ghip_winds_enter)
+static int winds_set_table(ghip_ctx *ctx, const char *who, bool dd, int nwind, const int *idx, const double *rows)
 {
   if(ctx)
     GHIP_JOIN(ctx);
-  static const char *who = "ghip_winds_set_table";
   if(!ctx || nwind < 0 || (nwind > 0 && (!idx || !rows)))
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(ghip_winds_enter(ctx, who, dd));
   RowTable &T = ctx->wk;
   hipStream_t st = ctx->stream;
   T.on = false;
@@ -1155,29 +1163,48 @@ extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, co
   return rc;
 }
 
-extern "C" int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows)
+static int winds_get_table(ghip_ctx *ctx, const char *who, bool dd, int *nwind, int *idx, double *rows)
 {
   if(ctx)
     GHIP_JOIN(ctx);
-  static const char *who = "ghip_winds_get_table";
   if(!ctx || !nwind)
     return ghip_fail(ctx, GHIP_EINVAL, "%s: bad arguments", who);
-  GCHK(ghip_winds_enter(ctx, who));
+  GCHK(ghip_winds_enter(ctx, who, dd));
   GCHK(ghip_rt_need(ctx, ctx->wk, who, true));
   return ghip_rt_get(ctx, ctx->wk, nwind, reinterpret_cast<unsigned int *>(idx), rows);
 }
 
-extern "C" int ghip_winds_clear(ghip_ctx *ctx)
+static int winds_clear(ghip_ctx *ctx, const char *who, bool dd)
 {
   if(!ctx)
     return GHIP_EINVAL;
   GHIP_JOIN(ctx);
-  GCHK(ghip_winds_enter(ctx, "ghip_winds_clear"));
+  GCHK(ghip_winds_enter(ctx, who, dd));
   GCHK(ghip_rt_clear(ctx, ctx->wk));
   (void) ctx->wk_spawn.release();
   (void) ctx->wk_rnd.release();
   return GHIP_OK;
 }
+
+extern "C" int ghip_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows)
+{
+  return winds_set_table(ctx, "ghip_winds_set_table", false, nwind, idx, rows);
+}
+extern "C" int ghip_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows)
+{
+  return winds_get_table(ctx, "ghip_winds_get_table", false, nwind, idx, rows);
+}
+extern "C" int ghip_winds_clear(ghip_ctx *ctx) { return winds_clear(ctx, "ghip_winds_clear", false); }
+// the table of a shard: local indices, a ghip_dd_init context of any rank count
+extern "C" int ghip_dd_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows)
+{
+  return winds_set_table(ctx, "ghip_dd_winds_set_table", true, nwind, idx, rows);
+}
+extern "C" int ghip_dd_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows)
+{
+  return winds_get_table(ctx, "ghip_dd_winds_get_table", true, nwind, idx, rows);
+}
+extern "C" int ghip_dd_winds_clear(ghip_ctx *ctx) { return winds_clear(ctx, "ghip_dd_winds_clear", true); }
 
 // ---- the table through ghip_rearrange / ghip_peano_order ----
 // keep[r] = the particle of row r survives; its new index is the row's new key
@@ -1209,6 +1236,221 @@ int ghip_winds_remap(ghip_ctx *ctx, const char *who, int n_before, const int *ne
   GCHK(ghip_rt_compact(ctx, T, who, W, W.a, newidx, 0, &kept));
   // (sorted again without a read: a map sends no two particles to one index)
   return ghip_rt_install(ctx, T, kept, who, true, nullptr);
+}
+
+// ---- the table through GHIP_DD_MIGRATE (ghip_dd.hip, migrate_step) ----
+// A migration renumbers the shard: kept gas, received gas, kept others, received others (k_mig_move_old / _new).
+// A row of a particle that stays is re-keyed to the particle's new index.  A row of a particle that leaves travels in
+// an exchange of its own as (the particle's ordinal in the sender's run for that destination, the row): the receiver
+// finds the particle at that ordinal behind the sender's receive offset and keys the row by its new index.  A
+// departing Type-3 particle without a row departs without one; an arrival without a record stays without a row.
+struct WkMigRec
+{
+  unsigned long long ordinal;
+  double c[WK_NC];
+};
+struct WkMigOff
+{
+  int v[GHIP_MAXRANKS];
+};
+
+// flags[a] = the a-th departing particle is Type 3 and has a row
+__global__ void __launch_bounds__(256) k_wkm_count(int total, const int *__restrict__ list, int n,
+                                                   const int *__restrict__ type, int nrows,
+                                                   const unsigned int *__restrict__ idx, int *__restrict__ flags)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= total)
+    return;
+  const int i = list[a];
+  flags[a] = i >= 0 && i < n && type[i] == 3 && d_rt_find(nrows, idx, (unsigned int) i) >= 0;
+}
+
+// cnt[r] = the rows of the run of destination r (pos: the exclusive scan of flags [total + 1])
+__global__ void k_wkm_runs(int nranks, WkMigOff start, WkMigOff len, const int *__restrict__ pos, int *__restrict__ cnt)
+{
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if(r < nranks)
+    cnt[r] = pos[start.v[r] + len.v[r]] - pos[start.v[r]];
+}
+
+// the records of the flagged particles, per destination in the order of its run
+__global__ void __launch_bounds__(256) k_wkm_pack(int total, const int *__restrict__ list, const int *__restrict__ flags,
+                                                  const int *__restrict__ pos, int nranks, WkMigOff start, WkMigOff len,
+                                                  WkMigOff out_off, WkMigOff out_len, int nrows,
+                                                  const unsigned int *__restrict__ idx, const double *__restrict__ rows,
+                                                  WkMigRec *__restrict__ out)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= total || !flags[a])
+    return;
+  int dest = -1;
+  for(int r = 0; r < nranks; r++)
+    if(a >= start.v[r] && a < start.v[r] + len.v[r])
+      dest = r;
+  if(dest < 0)
+    return;
+  const int k = pos[a] - pos[start.v[dest]];
+  const int row = d_rt_find(nrows, idx, (unsigned int) list[a]);
+  if(k < 0 || k >= out_len.v[dest] || row < 0)   // (cannot happen: k_wkm_runs counted the same flags)
+    return;
+  WkMigRec &R = out[out_off.v[dest] + k];
+  R.ordinal = (unsigned long long) (a - start.v[dest]);
+  for(int c = 0; c < WK_NC; c++)
+    R.c[c] = rows[(size_t) row * WK_NC + c];
+}
+
+// keep[r] = the particle of row r stays; its new index is the row's new key
+__global__ void __launch_bounds__(256) k_wkm_rekey(int m, const unsigned int *__restrict__ idx, WkMigPlan M,
+                                                   unsigned int *__restrict__ newidx, int *__restrict__ keep)
+{
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if(r >= m)
+    return;
+  const int i = (int) idx[r];
+  const bool stays = i >= M.ng_old && i < M.n_old && M.mask[i] == 0;
+  newidx[r] = stays ? (unsigned int) (M.ngn + (int) (M.ro[i] >> 32)) : 0u;
+  keep[r] = stays;
+}
+
+// record a of the arrivals (from: where each sender's records begin, [nranks] and the total behind them) -> the new
+// index of the particle it names and its row; a record that names no arriving particle of the block behind the gas
+// raises the error words
+__global__ void __launch_bounds__(256) k_wkm_unpack(int nrecv, const WkMigRec *__restrict__ rec, int nranks,
+                                                    WkMigOff from, WkMigPlan M, unsigned int *__restrict__ newidx,
+                                                    double *__restrict__ rows, int *__restrict__ words)
+{
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if(a >= nrecv)
+    return;
+  int s = 0;
+  for(int r = 1; r < nranks; r++)
+    if(a >= from.v[r])
+      s = r;
+  const unsigned long long o = rec[a].ordinal;
+  unsigned int key = 0xffffffffu - (unsigned int) a;   // (an error: no two rows under one key, the words say the rest)
+  bool ok = o < (unsigned long long) M.cnt[s];
+  if(ok)
+    {
+      const int q = M.first[s] + (int) o;
+      ok = q >= 0 && q < M.nrecv && M.vn[q] == (1ULL << 32);
+      if(ok)
+        key = (unsigned int) (M.ngn + M.ko + (int) (M.rn[q] >> 32));
+    }
+  if(!ok)
+    {
+      words[RTW_ERR] = 1;
+      atomicMax(words + RTW_ERRKEY, a);
+    }
+  newidx[a] = key;
+  for(int c = 0; c < WK_NC; c++)
+    rows[(size_t) a * WK_NC + c] = rec[a].c[c];
+}
+
+int ghip_winds_mig_pack(ghip_ctx *ctx, int total, const int *list, const int *scount, const int *soff)
+{
+  static_assert(sizeof(WkMigRec) == 8 + 8 * WK_NC, "WkMigRec layout");
+  DDState &D = ctx->dd;
+  RowTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  const int m = T.n, P_ = D.nranks;
+  WkMigOff start, len, out_off, out_len;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    {
+      start.v[r] = r < P_ ? soff[r] : 0;
+      len.v[r] = r < P_ && r != D.rank ? scount[r] : 0;
+      out_off.v[r] = out_len.v[r] = D.wk_rscount[r] = D.wk_rsoff[r] = 0;
+    }
+  int tot = 0;
+  if(m > 0 && total > 0)
+    {
+      const size_t t1 = (size_t) total + 1;
+      GCHK(ghip_ensure(ctx, D.wk_flag, (2 * t1 + GHIP_MAXRANKS) * 4));
+      int *flags = P<int>(D.wk_flag), *pos = flags + t1, *cnt = pos + t1;
+      HIPCHK(hipMemsetAsync(flags, 0, (2 * t1 + GHIP_MAXRANKS) * 4, st));
+      k_wkm_count<<<cdiv(total, 256), 256, 0, st>>>(total, list, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), m,
+                                                   P<unsigned int>(T.key), flags);
+      HIPCHK(hipGetLastError());
+      GCHK(ghip_scan<int>(ctx, flags, pos, total + 1, st));
+      k_wkm_runs<<<1, GHIP_MAXRANKS, 0, st>>>(P_, start, len, pos, cnt);
+      HIPCHK(hipGetLastError());
+      int h[GHIP_MAXRANKS];
+      HIPCHK(hipMemcpyAsync(h, cnt, (size_t) P_ * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      for(int r = 0; r < P_; r++)
+        if(h[r] < 0 || h[r] > len.v[r] || h[r] > m)
+          return ghip_fail(ctx, GHIP_EDEVICE, "GHIP_DD_MIGRATE: %d wind rows in a run of %d particles for rank %d, %d "
+                           "rows held", h[r], len.v[r], r, m);
+      for(int r = 0; r < P_; r++)
+        {
+          const int c = h[r];
+          out_off.v[r] = D.wk_rsoff[r] = tot;
+          out_len.v[r] = D.wk_rscount[r] = c;
+          tot += c;
+        }
+      GCHK(ghip_ensure(ctx, D.wk_rsend, (size_t) (tot > 0 ? tot : 1) * sizeof(WkMigRec)));
+      if(tot > 0)
+        {
+          k_wkm_pack<<<cdiv(total, 256), 256, 0, st>>>(total, list, flags, pos, P_, start, len, out_off, out_len, m,
+                                                      P<unsigned int>(T.key), P<double>(T.rows), P<WkMigRec>(D.wk_rsend));
+          HIPCHK(hipGetLastError());
+        }
+    }
+  if(tot == 0)
+    GCHK(ghip_ensure(ctx, D.wk_rsend, sizeof(WkMigRec)));
+  return GHIP_OK;
+}
+
+void ghip_winds_mig_post(ghip_ctx *ctx)
+{
+  DDState &D = ctx->dd;
+  ghip_dd_set_alltoallv(D, D.wk_rsend.p, sizeof(WkMigRec), D.wk_rscount, D.wk_rsoff, &D.wk_rrecv);
+}
+
+int ghip_winds_mig_merge(ghip_ctx *ctx)
+{
+  static const char *who = "GHIP_DD_MIGRATE";
+  DDState &D = ctx->dd;
+  RowTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  const WkMigPlan &M = D.wk_plan;
+  const int m = T.n, nrecv = D.x.rtotal;
+  if(!M.moved)   // (nobody left this shard and nobody came: every key stands, and no record can name a particle)
+    {
+      if(nrecv > 0)
+        return ghip_fail(ctx, GHIP_ECOMM, "%s: %d wind rows came to a shard that received no particle", who, nrecv);
+      return GHIP_OK;
+    }
+  WkMigOff from;
+  for(int r = 0; r < GHIP_MAXRANKS; r++)
+    from.v[r] = r < D.nranks ? D.x.roff[r] : nrecv;
+  RtWork W;
+  GCHK(ghip_rt_work(ctx, T, (size_t) (m + nrecv + 1), 0, W, true));
+  unsigned int *newidx = reinterpret_cast<unsigned int *>(W.c);
+  if(m > 0)
+    {
+      k_wkm_rekey<<<cdiv(m, 256), 256, 0, st>>>(m, P<unsigned int>(T.key), M, newidx, W.a);
+      HIPCHK(hipGetLastError());
+    }
+  int kept = 0, hw[RTW_WORDS] = {};
+  GCHK(ghip_rt_compact(ctx, T, who, W, W.a, newidx, nrecv, &kept));
+  if(nrecv > 0)
+    {
+      k_wkm_unpack<<<cdiv(nrecv, 256), 256, 0, st>>>(nrecv, P<WkMigRec>(D.wk_rrecv), D.nranks, from, M,
+                                                    P<unsigned int>(T.tmp_key) + kept,
+                                                    P<double>(T.tmp_rows) + (size_t) kept * WK_NC, W.words);
+      HIPCHK(hipGetLastError());
+    }
+  // (sorted again: the kept rows are ascending still, the arrivals lie behind them in the block)
+  const int rc = ghip_rt_install(ctx, T, kept + nrecv, who, true, hw);
+  if(hw[RTW_ERR])
+    {
+      T.on = false;
+      T.n = 0;
+      return ghip_fail(ctx, GHIP_ECOMM, "%s: wind row record %d names no arriving particle behind the gas block (the "
+                       "context holds no wind table now)", who, hw[RTW_ERRKEY]);
+    }
+  return rc;
 }
 
 // ---- the loop ----
@@ -1528,10 +1770,17 @@ extern "C" size_t ghip_dd_wind_args_size(void)
   return sizeof(ghip_dd_wind_args);
 }
 
+extern "C" size_t ghip_dd_winds_args_size(void)
+{
+  return sizeof(ghip_dd_winds_args);
+}
+
 enum { WDD_GROUPS, WDD_START, WDD_DENS_IMP, WDD_DENS_ADD, WDD_STATUS, WDD_SPREAD, WDD_SPREAD_POS };
 
-static const char *wind_dd_who(int form)
+static const char *wind_dd_who(int form, bool resident = false)
 {
+  if(resident)
+    return "ghip_dd winds feedback";
   return form == GHIP_WIND_DENSITY_FORM ? "ghip_dd wind density"
                                         : (form == GHIP_WIND_SPREAD_FORM ? "ghip_dd wind spread" : "ghip_dd wind feedback");
 }
@@ -1539,12 +1788,27 @@ static const char *wind_dd_who(int form)
 int ghip_dd_wind_begin(ghip_ctx *ctx, int, const void *params, int walk)
 {
   GHIP_JOIN(ctx);
-  const char *who = wind_dd_who(walk);
-  if(walk != GHIP_WIND_FORM && walk != GHIP_WIND_DENSITY_FORM && walk != GHIP_WIND_SPREAD_FORM)
-    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd wind: walk = %d is none of GHIP_WIND_FORM, GHIP_WIND_DENSITY_FORM and "
-                     "GHIP_WIND_SPREAD_FORM", walk);
+  if(walk == GHIP_WINDS_SPAWN_FORM)   // (the creation of wind particles, ghip_accretion.hip: it asks for no tree)
+    return ghip_dd_spawn_begin(ctx, params);
+  const bool resident = walk == GHIP_WINDS_RESIDENT_FORM;
+  const char *who = wind_dd_who(walk, resident);
+  if(walk != GHIP_WIND_FORM && walk != GHIP_WIND_DENSITY_FORM && walk != GHIP_WIND_SPREAD_FORM && !resident)
+    return ghip_fail(ctx, GHIP_EINVAL, "ghip_dd wind: walk = %d is none of GHIP_WIND_FORM, GHIP_WIND_DENSITY_FORM, "
+                     "GHIP_WIND_SPREAD_FORM, GHIP_WINDS_RESIDENT_FORM and GHIP_WINDS_SPAWN_FORM", walk);
   GCHK(wind_refuse_sharded(ctx, who, true));
-  const ghip_dd_wind_args &a = *reinterpret_cast<const ghip_dd_wind_args *>(params);
+  // the resident form is the whole loop with another source of the list and the planes: its arguments become
+  // those of GHIP_WIND_FORM with no list yet (the selection of the first step sets nwind)
+  ghip_dd_wind_args a = {};
+  if(resident)
+    {
+      const ghip_dd_winds_args &r = *reinterpret_cast<const ghip_dd_winds_args *>(params);
+      a.p = r.p;
+      a.result = r.result;
+      a.counts = r.counts;
+      walk = GHIP_WIND_FORM;
+    }
+  else
+    a = *reinterpret_cast<const ghip_dd_wind_args *>(params);
   const ghip_wind_state *s = a.state;
   bool bad = !a.p || a.nwind < 0 || (a.nwind > 0 && !a.wind_idx);
   if(walk == GHIP_WIND_FORM)
@@ -1573,6 +1837,7 @@ int ghip_dd_wind_begin(ghip_ctx *ctx, int, const void *params, int walk)
   W.p = *a.p;
   W.a.p = &W.p;
   W.form = walk;
+  W.resident = resident;
   for(int k = 0; k < 5; k++)
     ctx->wind_ms[k] = 0;
   if(a.result)
@@ -1688,6 +1953,82 @@ static int wind_dd_iterate(ghip_ctx *ctx)
   return wind_dd_density_send(ctx, WDD_DENS_IMP);
 }
 
+// GHIP_WINDS_RESIDENT_FORM, the front end: this shard's list by the selection of ghip_winds_feedback over its active
+// list into d.idx, W.a.nwind = its length (one read).  What the shard cannot do -- no table, a stale one, an active
+// Type-3 particle without a row -- comes back as *own_rc with no list: the status record of the first all-gather
+// carries it, and every shard stops in the next step.
+static int wind_dd_resident_list(ghip_ctx *ctx, const char *who, int *own_rc)
+{
+  DDState &D = ctx->dd;
+  WindDD &W = D.wind;
+  RowTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  W.a.nwind = 0;
+  *own_rc = ghip_winds_enter(ctx, who, true);
+  if(*own_rc == GHIP_OK)
+    *own_rc = ghip_rt_need(ctx, T, who, true);
+  if(*own_rc != GHIP_OK)
+    {
+      const std::string why = ctx->err;
+      *own_rc = ghip_fail(ctx, GHIP_EINVAL, "%s (rank %d of %d; either all shards hold a wind table, an empty one "
+                          "counts, or the loop is GHIP_WIND_FORM with host arrays: ghip_dd_winds_set_table); nothing "
+                          "was changed", why.c_str(), D.rank, D.nranks);
+      return GHIP_OK;
+    }
+  const int nact = ctx->nactive < 0 ? ctx->n : ctx->nactive;
+  const int *dact = ctx->nactive < 0 ? nullptr : P<int>(ctx->act_host_idx);
+  if(nact <= 0)
+    return GHIP_OK;
+  RtWork R;
+  GCHK(ghip_rt_work(ctx, T, (size_t) nact, 0, R, true));
+  k_wk_flag_list<<<cdiv(nact, 256), 256, 0, st>>>(nact, dact, ctx->n, P<int>(ctx->f[GHIP_F_TYPE]), T.n,
+                                                  P<unsigned int>(T.key), P<double>(T.rows), W.p.Time, R.a, R.words);
+  HIPCHK(hipGetLastError());
+  GCHK(ghip_select_flagged(ctx, dact, R.a, R.b, R.words + RTW_COUNT, nact, st));
+  int w[RTW_WORDS];
+  HIPCHK(hipMemcpyAsync(w, R.words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIPCHK(ghip_stream_sync(ctx, st));
+  const int nw = w[RTW_COUNT];
+  if(w[RTW_ERR])
+    *own_rc = ghip_fail(ctx, GHIP_EINVAL, "%s: the active Type-3 particle %d of rank %d has no row in the shard's wind "
+                        "table (%d rows); nothing was changed", who, w[RTW_ERRKEY], D.rank, T.n);
+  else if(nw < 0 || nw > nact || nw > T.n)
+    *own_rc = ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d active particles, %d rows (rank %d)", who, nw, nact,
+                        T.n, D.rank);
+  if(*own_rc != GHIP_OK || nw == 0)
+    return GHIP_OK;
+  const size_t Dn = (size_t) nw;
+  GCHK(ghip_ensure(ctx, ctx->wind_idx, ((9 * Dn * 4 + 63) & ~(size_t) 63) + 64));
+  HIPCHK(hipMemcpyAsync(ctx->wind_idx.p, R.b, Dn * 4, hipMemcpyDeviceToDevice, st));
+  W.a.nwind = nw;
+  return GHIP_OK;
+}
+
+// ... and the back end: the out planes and the code of the elimination into the rows (all == false: after a call
+// that did not enter the loop, as ghip_winds_feedback); res != nullptr: what one thread adds in list order
+static int wind_dd_store_rows(ghip_ctx *ctx, const WindDev &d, bool all, ghip_wind_result *res)
+{
+  RowTable &T = ctx->wk;
+  hipStream_t st = ctx->stream;
+  const int nw = d.nw;
+  k_wk_store<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, T.n, P<unsigned int>(T.key), P<double>(T.rows), d.w, d.deleted,
+                                            all);
+  HIPCHK(hipGetLastError());
+  if(res)
+    {
+      RtWork R;
+      GCHK(ghip_rt_work(ctx, T, 1, 0, R, false));
+      ghip_wind_result *dres = reinterpret_cast<ghip_wind_result *>(R.report), r;
+      k_wk_result<<<1, 64, 0, st>>>(nw, d.deleted, d.w + WP_OLD * (size_t) nw, dres);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(&r, dres, sizeof(r), hipMemcpyDeviceToHost, st));
+      HIPCHK(ghip_stream_sync(ctx, st));
+      res->ndeleted = r.ndeleted;
+      res->deleted_momentum = r.deleted_momentum;
+    }
+  return GHIP_OK;
+}
+
 // the end of the loop on this shard: RAD_ACCEL and the elimination (not after max_iter), the state back
 static int wind_dd_finish(ghip_ctx *ctx, bool noconv)
 {
@@ -1716,7 +2057,9 @@ static int wind_dd_finish(ghip_ctx *ctx, bool noconv)
                                                         P<double>(ctx->f[GHIP_F_MASS]), d.w, d.deleted, K);
       HIPCHK(hipGetLastError());
     }
-  if(nw > 0)
+  if(nw > 0 && W.resident)
+    GCHK(wind_dd_store_rows(ctx, d, true, res));
+  else if(nw > 0)
     {
       const ghip_wind_state *s = W.a.state;
       GCHK(wind_download_state(ctx, d, s, true));
@@ -1732,7 +2075,7 @@ static int wind_dd_finish(ghip_ctx *ctx, bool noconv)
   wind_dd_counts(D);
   if(noconv)
     return ghip_fail(ctx, GHIP_ENOCONV, "%s: %lld wind particles still under way after max_iter = %d iterations",
-                     wind_dd_who(W.form), W.under_all, W.p.max_iter);
+                     wind_dd_who(W.form, W.resident), W.under_all, W.p.max_iter);
   return 0;
 }
 
@@ -1741,7 +2084,16 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
   DDState &D = ctx->dd;
   WindDD &W = D.wind;
   hipStream_t st = ctx->stream;
-  const char *who = wind_dd_who(W.form);
+  if(W.form == GHIP_WINDS_SPAWN_FORM)
+    return ghip_dd_spawn_step(ctx);
+  const char *who = wind_dd_who(W.form, W.resident);
+  int list_rc = GHIP_OK;
+  std::string list_msg;
+  if(D.phase == WDD_GROUPS && W.resident)
+    {
+      GCHK(wind_dd_resident_list(ctx, who, &list_rc));
+      list_msg = ctx->err;
+    }
   const int nw = W.a.nwind, n = ctx->n;
   const size_t Dn = (size_t) (nw > 0 ? nw : 1);
   const BoxK b = make_box(W.p.BoxSize, W.p.periodic);
@@ -1755,7 +2107,8 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       HIPCHK(hipMemsetAsync(d.words, 0, sizeof(WindWords), st));
       if(nw > 0)
         {
-          HIPCHK(hipMemcpyAsync(d.idx, W.a.wind_idx, Dn * 4, hipMemcpyHostToDevice, st));
+          if(!W.resident)   // (the resident list stands there already)
+            HIPCHK(hipMemcpyAsync(d.idx, W.a.wind_idx, Dn * 4, hipMemcpyHostToDevice, st));
           GCHK(wind_tree_order(ctx, d, st));
           k_wind_vel<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, n, P<int>(ctx->f[GHIP_F_TYPE]), P<double>(ctx->f[GHIP_F_VEL]),
                                                     d.w, d.words);
@@ -1768,15 +2121,24 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       HIPCHK(hipGetLastError());
       if(nw > 0 && W.form == GHIP_WIND_FORM)
         {
-          const ghip_wind_state *s = W.a.state;
-          std::vector<double> h(WIND_NIN * Dn);
-          memcpy(h.data() + WP_AGE * Dn, s->stellar_age, Dn * 8);
-          memcpy(h.data() + WP_BIRTH * Dn, s->birth_energy, Dn * 8);
-          memcpy(h.data() + WP_OLD * Dn, s->old_momentum, Dn * 8);
-          memcpy(h.data() + WP_RHO * Dn, s->new_density, Dn * 8);
-          memcpy(h.data() + WP_DRMIN * Dn, s->drmin, Dn * 8);
-          HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
-          HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
+          if(W.resident)
+            {
+              k_wk_load<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, ctx->wk.n, P<unsigned int>(ctx->wk.key),
+                                                       P<double>(ctx->wk.rows), d.w);
+              HIPCHK(hipGetLastError());
+            }
+          else
+            {
+              const ghip_wind_state *s = W.a.state;
+              std::vector<double> h(WIND_NIN * Dn);
+              memcpy(h.data() + WP_AGE * Dn, s->stellar_age, Dn * 8);
+              memcpy(h.data() + WP_BIRTH * Dn, s->birth_energy, Dn * 8);
+              memcpy(h.data() + WP_OLD * Dn, s->old_momentum, Dn * 8);
+              memcpy(h.data() + WP_RHO * Dn, s->new_density, Dn * 8);
+              memcpy(h.data() + WP_DRMIN * Dn, s->drmin, Dn * 8);
+              HIPCHK(hipMemcpyAsync(d.w, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
+              HIPCHK(ghip_stream_sync(ctx, st));   // (h leaves scope)
+            }
           k_wind_init<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.idx, P<int>(ctx->f[GHIP_F_TIMEBIN]), d.w, d.deleted, W.p.dt_fac);
           k_wind_sum<<<1, 1024, 0, st>>>(nw, d.w + WP_DTJ * Dn, &d.words->dt_total);
           k_wind_flags<<<cdiv(nw, 256), 256, 0, st>>>(nw, d.ord, d.w + WP_DTJ * Dn, d.flags, d.words);
@@ -1796,8 +2158,10 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
       HIPCHK(hipMemcpyAsync(&h, d.words, sizeof(h), hipMemcpyDeviceToHost, st));
       HIPCHK(ghip_stream_sync(ctx, st));
       // what this shard met travels with the group tables: every shard stops in the next step (ghip_dd_hold's path)
-      int own_rc = GHIP_OK;
-      if(h.err)
+      int own_rc = list_rc;
+      if(own_rc != GHIP_OK)
+        ctx->err = list_msg;   // (the selection's own message is the shard's)
+      else if(h.err)
         own_rc = wind_type_error(ctx, who);
       else if(W.form == GHIP_WIND_FORM && (h.npos < 0 || h.npos > nw))
         own_rc = ghip_fail(ctx, GHIP_EDEVICE, "%s: a list of %d of %d particles", who, h.npos, nw);
@@ -1813,6 +2177,7 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
   if(D.phase == WDD_START)
     {
       double extra[3 * GHIP_MAXRANKS];
+      // (in the resident form a failing shard's code travels in its status record: the other shards return it too)
       GCHK(ghip_dd_wind_status(ctx, who, extra));
       double hmax = 0, dt_total = 0;
       for(int r = 0; r < D.nranks; r++)   // (the sum in ascending rank order: the same bits on every shard)
@@ -1826,7 +2191,12 @@ int ghip_dd_wind_step(ghip_ctx *ctx)
         {
           if(dt_total <= W.p.dt_total_floor)   // :302: the loop is not entered, nothing changes on any shard
             {
-              if(nw > 0)
+              if(nw > 0 && W.resident)
+                {
+                  GCHK(wind_dd_store_rows(ctx, d, false, nullptr));
+                  HIPCHK(ghip_stream_sync(ctx, st));
+                }
+              else if(nw > 0)
                 GCHK(wind_download_state(ctx, d, W.a.state, false));
               wind_dd_counts(D);
               return 0;

@@ -353,6 +353,28 @@ class DomainShards:
         self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WIND_FORM)
         return [self.B.dd_wind_result(b[1]) for b in built]
 
+    def winds_feedback(self, params):
+        """GHIP_DD_WIND in its WINDS_RESIDENT_FORM: ForcePath.winds_feedback as one collective.  Every shard lists
+        its active Type-3 particles that have a row with StellarAge < Time in its wind table (dd_winds_set_table),
+        takes the state from the rows and writes it back.  Returns one dict per shard: iterations (global), the
+        shard's bits / ndeleted / deleted_momentum, counts.  An active Type-3 particle without a row, or a shard
+        without a table: GhipError on all shards, nothing changed."""
+        built = [self.B.dd_winds_args(params) for _ in self.paths]
+        self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WINDS_RESIDENT_FORM)
+        return [self.B.dd_wind_result(b[1]) for b in built]
+
+    def wind_spawn(self, params, rnd):
+        """GHIP_DD_WIND in its WINDS_SPAWN_FORM: ForcePath.wind_spawn as one collective.  Every shard's massive active
+        sinks (found in its sink table) create wind particles behind its own particles and rows in its wind table;
+        rnd is the host's RndTable, which must be given.  Returns one dict per shard as ForcePath.wind_spawn does,
+        with tot_spawned, the sum over all shards; every path's .n follows.  One shard that cannot (no table, a
+        missing row, MaxPart): GhipError on all shards, nothing changed anywhere."""
+        built = [self.B.dd_winds_args(spawn=params, rnd_table=rnd) for _ in self.paths]
+        self.run(self.B.WIND_OP, [b[0] for b in built], self.B.WINDS_SPAWN_FORM)
+        for p in self.paths:
+            p.counts()
+        return [self.B.dd_winds_spawn_report(b[1]) for b in built]
+
     def sinks_density(self, params, ngb_factor):
         """GHIP_DD_SINK_DENSITY in its SINKS_RESIDENT_FORM: ForcePath.sinks_density for the active Type-5 particles
         of all shards, each found in its shard's sink table -> the iteration count (the same on all shards)"""
@@ -545,6 +567,22 @@ class DomainRank:
         args, keep = self.B.dd_wind_args(params, wind, state=state if len(wind) else _empty_wind_state())
         self._run(self.B.WIND_OP, args, self.B.WIND_FORM)
         return self.B.dd_wind_result(keep)
+
+    def winds_feedback(self, params):
+        """GHIP_DD_WIND in its WINDS_RESIDENT_FORM, a collective: ForcePath.winds_feedback for this rank's active
+        Type-3 particles with a row in its wind table (dd_winds_set_table) -> a dict: iterations (global), this
+        rank's bits / ndeleted / deleted_momentum, counts"""
+        args, keep = self.B.dd_winds_args(params)
+        self._run(self.B.WIND_OP, args, self.B.WINDS_RESIDENT_FORM)
+        return self.B.dd_wind_result(keep)
+
+    def wind_spawn(self, params, rnd):
+        """GHIP_DD_WIND in its WINDS_SPAWN_FORM, a collective: ForcePath.wind_spawn for this rank's own sinks -> a
+        dict as there, with tot_spawned, the sum over all ranks; the path's .n follows"""
+        args, keep = self.B.dd_winds_args(spawn=params, rnd_table=rnd)
+        self._run(self.B.WIND_OP, args, self.B.WINDS_SPAWN_FORM)
+        self.p.counts()
+        return self.B.dd_winds_spawn_report(keep)
 
     def sinks_density(self, params, ngb_factor):
         """GHIP_DD_SINK_DENSITY in its SINKS_RESIDENT_FORM, a collective: ForcePath.sinks_density for the active

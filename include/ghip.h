@@ -1140,11 +1140,16 @@ int ghip_wind_get_timing(ghip_ctx *ctx, double ms[5]);
  * the creation of wind particles by the massive sinks (momentum_feedback.c:70-246).  With them the wind cycle
  * closes on the device: the sinks accrete (ghip_blackhole_accretion), emit (ghip_wind_spawn), the wind
  * propagates (ghip_winds_feedback) and what is spent leaves with ghip_rearrange; no per-particle host array and
- * no pass through the host is involved.  Everything here is for one GPU: a plain context or a ghip_dd_init
- * context of a single rank.  On a ghip_set_shard context every entry point of this section returns GHIP_EINVAL;
- * on a ghip_dd_init context with more than one rank it returns GHIP_EINVAL and says that the shard form is not
- * built.  Not built either: force_add_star_to_tree (a spawn discards the trees), fb_particles.c / PHOTONS,
- * SPH_EMIT, and the P[i].dt1 the reference writes into the sink's own record (:80).
+ * no pass through the host is involved.  There are two families.  The entry points of THIS section are for one
+ * GPU: a plain context or a ghip_dd_init context of a single rank; on a ghip_dd_init context with more than one
+ * rank each of them returns GHIP_EINVAL, says that the shard form is not built into it and names the shard family.
+ * The shard family is for a ghip_dd_init context of any rank count: the table ghip_dd_winds_set_table /
+ * _get_table / _clear (local indices), which GHIP_DD_MIGRATE carries, and the loop as the collective GHIP_DD_WIND
+ * with walk = GHIP_WINDS_RESIDENT_FORM (both below, with the other wind forms); on a plain context they return
+ * GHIP_EINVAL and name the single-rank function.  On a ghip_set_shard context every entry point of both families
+ * returns GHIP_EINVAL.  ghip_wind_spawn on more than one rank is GHIP_DD_WIND with walk = GHIP_WINDS_SPAWN_FORM.
+ * Not built: force_add_star_to_tree (a spawn discards the trees), fb_particles.c / PHOTONS, SPH_EMIT, and the P[i].dt1 the
+ * reference writes into the sink's own record (:80).
  *
  * The table holds one row of GHIP_WK_COUNT doubles per wind particle, keyed by PARTICLE INDEX and kept in
  * ascending index order in device memory owned by the context.  It cannot be keyed by P[].ID as the sink table
@@ -1506,6 +1511,63 @@ size_t ghip_dd_wind_args_size(void);
 #define GHIP_WIND_FORM 16           /* `walk` of ghip_dd_begin / ghip_dd_run for GHIP_DD_WIND: the whole loop */
 #define GHIP_WIND_DENSITY_FORM 17
 #define GHIP_WIND_SPREAD_FORM 18
+/* The resident wind particles on shards ("Resident, on shards").  The wind table of a shard:
+ * ghip_dd_winds_set_table / _get_table / _clear for a ghip_dd_init context of ANY rank count; idx holds LOCAL particle
+ * indices of the shard.  The refusals are those of the single-rank functions (an index out of range, not Type 3,
+ * given twice: no table; stale after ghip_set_counts with changed counts); on a plain context they are GHIP_EINVAL
+ * and name the single-rank function, on a ghip_set_shard context GHIP_EINVAL.  ghip_rearrange and ghip_peano_order,
+ * which are local on a ghip_dd_init context, carry the table as on one GPU.
+ * GHIP_DD_MIGRATE carries it too.  A migration renumbers the shard (kept gas, received gas, kept others, received
+ * others), so a row of a particle that stays is re-keyed to its particle's new index, and a row of a Type-3 particle
+ * that leaves travels, in one more all-to-all-v after the particles', as its particle's ordinal in the sender's run
+ * for that destination plus the GHIP_WK_COUNT doubles (88 bytes); the receiver keys it by the new index of the
+ * particle at that ordinal, and the table is sorted again.  A departing Type-3 particle without a row departs
+ * without one; an arrival without a record has no row.  The header record of the particles' exchange says which
+ * tables the sender holds: either all shards hold a wind table (an empty one counts) or none does, else every shard
+ * returns GHIP_EINVAL before anything moved -- independently of the same rule for the sink tables.  Exchanges of a
+ * migration: 1 without tables, 2 with wind tables, 3 with sink tables, 4 with both.  A stale table is not carried
+ * and stays refused. */
+int ghip_dd_winds_set_table(ghip_ctx *ctx, int nwind, const int *idx, const double *rows);
+int ghip_dd_winds_get_table(ghip_ctx *ctx, int *nwind, int *idx, double *rows);
+int ghip_dd_winds_clear(ghip_ctx *ctx);
+/* ghip_winds_feedback as a collective: GHIP_DD_WIND begun with walk = GHIP_WINDS_RESIDENT_FORM and params a
+ * ghip_dd_winds_args.  Everything GHIP_WIND_FORM says holds -- the same kernels, the four exchanges per iteration,
+ * the selection cut, the rank-order sums, the end --; only the source of the list and of the planes differs.  The
+ * list is the device selection of ghip_winds_feedback over the shard's active list: Type 3, a row, StellarAge <
+ * Time, in active-list order.  The in planes are gathered from the rows; at the end the out planes and the code of
+ * the elimination are scattered back; a row that is not listed is not touched.  An active Type-3 particle without
+ * a row on its shard, a shard without a table, or one with a stale table: GHIP_EINVAL on ALL shards in the same
+ * step (the status record of the first all-gather carries it; the failing shard's message names the index and the
+ * rank), every exchange up to there is taken, nothing has changed.  Blocking reads per shard: the words of the
+ * selection with the list length replace the upload of the state; the rest is as GHIP_WIND_FORM.  The values are
+ * bit for bit those of GHIP_WIND_FORM given the same lists and the rows' state. */
+/* ghip_wind_spawn as a collective: GHIP_DD_WIND begun with walk = GHIP_WINDS_SPAWN_FORM and the spawn members of
+ * the same struct (p, result and counts are not read).  The reference's creation is local per task
+ * (momentum_feedback.c:70-246): the new particle is P[NumPart + stars_spawned] of the TASK, its ID the sink's ID +
+ * that LOCAL index, only tot_spawned is all-reduced (:240), and endrun(8888) on any task ends all tasks.  So every
+ * shard does what ghip_wind_spawn does, on its own sinks from its own sink table, with ONE all-gather of {spawned,
+ * sinks emitting, new_wind_exact sum, failed} between the scan and the growth.  spawn->rnd_table / nrnd MUST be
+ * given: ghip_dd_begin refuses a context with a table bound by ghip_set_rnd_table.  A shard without a sink table or
+ * without a wind table (ghip_dd_winds_set_table; an empty one counts), with an active Type-5 particle without a
+ * row, or with NumPart + spawned > MaxPart makes EVERY shard return GHIP_EINVAL in the same step -- the failing
+ * shard's message says why and names its rank, the others name the shard -- and no shard has changed a byte.
+ * Otherwise each shard grows and fills locally: *report is the shard's own (first_index: its NumPart before),
+ * *tot_spawned the sum over all shards, the same on all of them, for All.TotNumPart.  A shard that spawns nothing
+ * changes nothing but takes the exchange.  The form does not ask for the trees of the step; on a shard that
+ * spawned, both trees are gone afterwards, as on one GPU.  A new particle stands where its sink stands, inside the
+ * shard's key range: no migration is implied. */
+typedef struct
+{
+  const ghip_wind_params *p;       /* RESIDENT_FORM */
+  ghip_wind_result *result;        /* RESIDENT_FORM: this shard's, as GHIP_WIND_FORM leaves it */
+  long long *counts;               /* RESIDENT_FORM: out [6] (may be NULL), as ghip_dd_wind_args.counts */
+  const ghip_wind_spawn_params *spawn;   /* SPAWN_FORM, with rnd_table / nrnd */
+  ghip_wind_spawn_report *report;        /* SPAWN_FORM: this shard's */
+  long long *tot_spawned;                /* SPAWN_FORM: the sum over all shards */
+} ghip_dd_winds_args;
+size_t ghip_dd_winds_args_size(void);
+#define GHIP_WINDS_RESIDENT_FORM 32 /* `walk` for GHIP_DD_WIND: the whole loop from the shard's wind table */
+#define GHIP_WINDS_SPAWN_FORM 33    /* ... the creation of wind particles by the shard's massive sinks */
 /* ghip_find_next_sync_point on shards: GHIP_DD_DECOMPOSE begun with walk = GHIP_SYNC_POINT_FORM and params a
  * ghip_sync_params (the result: ghip_dd_get_sync_point) -- the two things run() does between two steps share one
  * operation, as the two forms of the dust operations do; no operation code is added.  Every
